@@ -2,7 +2,7 @@
 """Headline benchmark: ICP iterations/sec (incl. kNN) of point-to-plane ICP on
 synthetic clouds (BASELINE.json metric; BASELINE.md section 3 inputs).
 
-    python bench.py [--gpus N --steps K --warmup W] [--points 10000000]
+    python bench.py [--gpus N --steps K --warmup W] [--points 10000000] [--dump-outputs DIR]
 
 One "step" = one iteration of registration::RegistrationICP's loop
 (registration.cu:155-163): 6x6 solve of the previous reduction -> compose T ->
@@ -22,7 +22,8 @@ overlapping source, a cold whole call (tree build + staging + 30 iterations), th
 pass and the build times.  cpu_baseline.parity_sample compares the oracle's nearest neighbours
 for its sample with the engine's, bit for bit.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR: rank 0 also writes what the last timed step computed as
+DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds run with the same arguments compare file for file.
 """
 import argparse
 import json
@@ -103,6 +104,29 @@ def cpu_baseline(src, tgt, nrm, max_dist, n_total, engine_nn=None):
                                 "idx_mismatch": int(len(diff)),
                                 "idx_mismatch_all_exact_ties": bool(np.array_equal(alt, od[diff]))}
     return out
+
+
+DUMP_SAMPLE = 1 << 20   # source points of the correspondence set in --dump-outputs (16 MB as two float64 columns)
+
+
+def dump_outputs(out_dir, res, corr, n_source, global_ids=None):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the RegistrationResult
+    (transformation, fitness, inlier RMSE, number of correspondences) and its correspondence set, the latter as the
+    target index matched to each source point of a fixed, seeded sample of at most DUMP_SAMPLE (-1: no match).
+    corr: the engine's (source, target) pairs; global_ids: the original indices of this rank's source points (N > 1)."""
+    os.makedirs(out_dir, exist_ok=True)
+    matched = np.full(n_source, -1, np.int64)
+    matched[corr[:, 0]] = corr[:, 1]
+    pick = np.sort(np.random.default_rng(0).choice(n_source, min(n_source, DUMP_SAMPLE), replace=False))
+    ids = pick if global_ids is None else np.asarray(global_ids)[pick]
+    arrays = {"transformation": np.array(res.transformation, np.float64).reshape(4, 4).T,
+              "fitness": np.array([res.fitness], np.float64),
+              "inlier_rmse": np.array([res.inlier_rmse], np.float64),
+              "n_correspondences": np.array([res.n_correspondences], np.float64),
+              "correspondence_source_index": ids.astype(np.float64),
+              "correspondence_target_index": matched[pick].astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def secondary(eng, src, tgt, nrm, d_tgt, d_nrm, d_src, max_dist, n, torch, _lib):
@@ -393,6 +417,8 @@ def main():
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--big-points", type=int, default=100_000_000,
                     help="size of secondary.strong_100M (the strong-scaling bench again at a size an 8-way shard still fills); 0: skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; at most ~16 MB)")
     args = ap.parse_args()
 
     import torch
@@ -553,6 +579,9 @@ def main():
             w = float(t.item())
         windows.append(w)
     elapsed = float(np.median(windows))
+    if args.dump_outputs and rank == 0:
+        # (before the profiled window below moves the loop on)
+        dump_outputs(args.dump_outputs, res, eng.get_correspondences(), len(src_local), mine if world > 1 else None)
     # did the loop start a build of the target's halos (2 ms of GPU time at 10M points) inside the timed windows?
     halo_builds_in_windows = eng.get_profile()["halo_builds_by_loops"] - halo_builds_before
     eng.set_profiling(True)

@@ -107,17 +107,25 @@ def test_lzf_against_the_references_vendored_liblzf():
     """csrc/lzf.h restates the LZF format; the reference's PCD reader / writer call the liblzf vendored under
     third_party/liblzf (file_pcd.cu:218,461,690).  Both ways: streams THAT compressor writes decode here to the
     input, streams this compressor writes decode THERE -- what a file exchanged with the reference needs.  (The two
-    compressors' byte streams need not be equal: the format leaves the match search to the writer.)"""
+    compressors' byte streams need not be equal: the format leaves the match search to the writer.)
+    What that library answered is stored in tests/golden/ref_lzf_streams.npz (oracle/make_ref_vectors.py): its streams
+    must decode here, and this compressor must still write the streams it decoded.  Where oracle/_ref/libref_lzf.so
+    is built, the library itself is asked as well."""
     import ctypes as C
     from cupoch_amd.io import lzf_compress, lzf_decompress
+    from oracle.make_ref_vectors import LZF_VECTORS, lzf_cases
+    cases = lzf_cases()
+    stored = np.load(LZF_VECTORS)
+    for i, data in enumerate(cases):
+        ref = stored["ref_%d" % i].tobytes()
+        assert lzf_decompress(ref, len(data)) == data                       # the reference compressed, the engine decodes
+        comp = lzf_compress(data)
+        assert comp == stored["eng_%d" % i].tobytes()                        # a stream the reference decoded to `data`
+        if len(ref) < len(data) // 2:
+            assert len(comp) <= 1.25 * len(ref) + 64
     L = orc.ref_lzf()
     if L is None:
-        pytest.skip("oracle/_ref/libref_lzf.so not built (needs /root/reference)")
-    rng = np.random.default_rng(3)
-    pts = rng.random((4000, 3), dtype=np.float32)
-    cases = [b"a" * 5, bytes(rng.integers(0, 256, 20000, dtype=np.uint8)), np.repeat(rng.random(700, dtype=np.float32), 5).tobytes(),
-             bytes(70000), b"0123456789" * 2500, np.ascontiguousarray(pts.T).tobytes(),          # field-major floats: a PCD payload
-             np.round(pts * 64).astype(np.float32).T.tobytes()]
+        return
     for data in cases:
         # the reference compresses, the engine decodes
         cap = len(data) * 2 + 64

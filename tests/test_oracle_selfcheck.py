@@ -36,28 +36,35 @@ def test_radius_is_strict_and_ties_take_lowest_index():
     assert orc.search_radius(np.zeros((0, 3)), qry, 1.0, 1)[0] == -1   # kdtree_flann.cu:72-73
 
 
-@pytest.mark.skipif(not orc.ref_flann_available(), reason="oracle/_ref not built")
+def _flann_answers(g, tgt, qry):
+    """What the reference's FLANN CPU kd-tree answers on the test's inputs: as recorded in
+    tests/golden/ref_flann_search.npz (oracle/make_ref_vectors.py) and, where oracle/_ref is built, asked again."""
+    from oracle.make_ref_vectors import FLANN_MAX_NN, FLANN_RADIUS, FLANN_VECTORS
+    v = np.load(FLANN_VECTORS)
+    yield (v["golden_knn_idx"], v["knn_idx"], v["knn_d2"], int(v["radius_count"][0]), v["radius_idx"], v["radius_d2"])
+    if orc.ref_flann_available():
+        gi, _ = orc.ref_flann_knn(g["points"], [g["query"]], g["knn"])
+        yield (gi[0],) + orc.ref_flann_knn(tgt, qry, 5) + orc.ref_flann_radius(tgt, qry, FLANN_RADIUS, FLANN_MAX_NN)
+
+
 def test_kdtree_equals_reference_flann_cpu(golden):
+    from oracle.make_ref_vectors import FLANN_MAX_NN, FLANN_RADIUS, flann_inputs
     g = golden["kdtree_search_knn"]
-    idx, d2 = orc.ref_flann_knn(g["points"], [g["query"]], g["knn"])
-    assert idx[0].tolist() == g["ref_indices"]
-    rng = np.random.default_rng(1)
-    tgt = rng.random((20000, 3), dtype=np.float32)
-    qry = rng.random((2000, 3), dtype=np.float32)
-    fi, fd = orc.ref_flann_knn(tgt, qry, 5)
+    tgt, qry = flann_inputs()
     _, oi, od = orc.search_knn(tgt, qry, 5)
-    # FLANN's randomized-kd-tree "exact" mode accumulates its lower bound per
-    # split instead of per dimension and so misses a true neighbour in ~0.5% of
-    # the slots (never the other way round): the oracle must never be beaten
-    # and must agree on the overwhelming majority.
-    assert (od <= fd * (1 + 2e-6)).all()
-    assert (fi == oi).mean() > 0.98
-    same = fi == oi
-    np.testing.assert_allclose(fd[same], od[same], rtol=2e-6)
-    r, fi, fd = orc.ref_flann_radius(tgt, qry, 0.02, 3)
-    r2, oi, od = orc.search_radius(tgt, qry, 0.02, 3)
-    assert (od <= fd * (1 + 2e-6)).all()
-    assert (fi == oi).mean() > 0.98 and abs(r - r2) <= 0.02 * r2
+    r2, roi, rod = orc.search_radius(tgt, qry, FLANN_RADIUS, FLANN_MAX_NN)
+    for gidx, fi, fd, r, ri, rd in _flann_answers(g, tgt, qry):
+        assert gidx.tolist() == g["ref_indices"]
+        # FLANN's randomized-kd-tree "exact" mode accumulates its lower bound per
+        # split instead of per dimension and so misses a true neighbour in ~0.5% of
+        # the slots (never the other way round): the oracle must never be beaten
+        # and must agree on the overwhelming majority.
+        assert (od <= fd * (1 + 2e-6)).all()
+        assert (fi == oi).mean() > 0.98
+        same = fi == oi
+        np.testing.assert_allclose(fd[same], od[same], rtol=2e-6)
+        assert (rod <= rd * (1 + 2e-6)).all()
+        assert (ri == roi).mean() > 0.98 and abs(r - r2) <= 0.02 * r2
 
 
 def test_rodrigues_and_solve():
