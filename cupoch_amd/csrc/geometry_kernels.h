@@ -185,11 +185,53 @@ struct VoxelGrid {
     int bits_y, bits_z;  // packed key = kx << (by+bz) | ky << bz | kz
 };
 
+// The grid of a cloud from its bounds (min[3], max[3]) -- one definition for the host and the device plan
+// (voxel_dense.h vx_make_plan): origin = min - voxel / 2 (down_sample.cu:180-185), the bits of every axis' cell index,
+// and overflow = the grid's extent in voxels does not fit int32 (down_sample.cu:186-189: no voxels at all).
+struct VoxelGridFit {
+    VoxelGrid g;
+    int bits[3];
+    bool overflow;
+};
+
+__host__ __device__ inline VoxelGridFit voxel_grid_fit(const float* bounds, float voxel) {
+    VoxelGridFit f;
+    float origin[3], ext = 0.0f;
+    for (int k = 0; k < 3; ++k) {
+        origin[k] = bounds[k] - voxel * 0.5f;
+        ext = fmaxf(ext, (bounds[3 + k] + voxel * 0.5f) - origin[k]);
+        const double cells = floor(((double)bounds[3 + k] - (double)origin[k]) / (double)voxel) + 2.0;
+        int b = 1;
+        while (b < 32 && (double)(1ull << b) < cells) ++b;
+        f.bits[k] = b;
+    }
+    f.overflow = voxel * (float)INT32_MAX < ext;
+    f.g.ox = origin[0];
+    f.g.oy = origin[1];
+    f.g.oz = origin[2];
+    f.g.voxel = voxel;
+    f.g.bits_y = f.bits[1];
+    f.g.bits_z = f.bits[2];
+    return f;
+}
+
+// one axis of down_sample.cu:69-73, floor(x / voxel) with x = pt - voxel_min_bound, by the IEEE division.  A quotient
+// that is not finite (a NaN coordinate) is cell 0, which is what gfx950's conversion of NaN gives.  (q - q is 0 for a
+// finite q and NaN otherwise.)
+__device__ __forceinline__ int32_t voxel_cell(float x, float voxel) {
+    const float q = floorf(x / voxel);
+    return (int32_t)(q - q == 0.0f ? q : 0.0f);
+}
+
+// the packed key of a grid whose key fits 32 bits
+__device__ __forceinline__ uint32_t voxel_pack32(const VoxelGrid& g, int32_t kx, int32_t ky, int32_t kz) {
+    return ((uint32_t)kx << (g.bits_y + g.bits_z)) | ((uint32_t)ky << g.bits_z) | (uint32_t)kz;
+}
+
 __device__ __forceinline__ void voxel_key3(const VoxelGrid& g, const float* p, int32_t* k) {
-    // down_sample.cu:69-73: floor((pt - voxel_min_bound) / voxel_size)
-    k[0] = (int32_t)floorf((p[0] - g.ox) / g.voxel);
-    k[1] = (int32_t)floorf((p[1] - g.oy) / g.voxel);
-    k[2] = (int32_t)floorf((p[2] - g.oz) / g.voxel);
+    k[0] = voxel_cell(p[0] - g.ox, g.voxel);
+    k[1] = voxel_cell(p[1] - g.oy, g.voxel);
+    k[2] = voxel_cell(p[2] - g.oz, g.voxel);
 }
 
 // axis < 0: packed lexicographic key of element i; axis 0..2: that axis' cell
@@ -317,7 +359,7 @@ static __global__ __launch_bounds__(256) void voxel_keys32(const float* __restri
     if (i >= n) return;
     int32_t k[3];
     voxel_key3(g, pts + i * 3, k);
-    keys[i] = ((uint32_t)k[0] << (g.bits_y + g.bits_z)) | ((uint32_t)k[1] << g.bits_z) | (uint32_t)k[2];
+    keys[i] = voxel_pack32(g, k[0], k[1], k[2]);
 }
 
 // head(i) = sorted element i opens a new run (its key >> L differs from its predecessor's).  Tile sums of the head

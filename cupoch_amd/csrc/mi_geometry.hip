@@ -30,13 +30,6 @@ int occupancy_geometry(int which) {
 
 extern "C" {
 
-#ifdef MI_VX_CLOCKS
-// measurements only (scripts/dev/voxel_dense_clocks.py): the phase clocks of the last vx_scatter / vx_finish launches
-int mi_vx_clocks_dump(unsigned long long* out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_vx_clk), sizeof(unsigned long long) * 2 * 4096 * kVxClkSlots) == hipSuccess ? 0 : -1;
-}
-#endif
-
 // ---------------------------------------------------------------------------
 int mi_icp_transform(mi_icp_ctx* c, const float* T, float* xyz, float* normals, float* covs,
                      int64_t n, int mem_kind) {
@@ -166,93 +159,124 @@ static int vx_order_ok(mi_icp_ctx* c, bool* ok) {
     return MI_ICP_OK;
 }
 
+// The partition kernels' tables in c->vx_tab, behind `head` words the caller keeps for itself: [ntiles][2048],
+// [nsegs][2048], bucket_start[2049], the control words (the rows are sized for 2048 buckets whatever the plan's B is)
+struct VxTables {
+    uint32_t *head, *tab, *seg_tot, *bucket_start, *ctl;
+    int ntiles, nsegs;
+};
+
+static int vx_tables(mi_icp_ctx* c, int64_t n, size_t head, VxTables* t) {
+    t->ntiles = (int)((n + kVxTile - 1) / kVxTile);
+    t->nsegs = (t->ntiles + kVxSeg - 1) / kVxSeg;
+    const size_t words = head + ((size_t)t->ntiles + t->nsegs) * kVxMaxBins + kVxMaxBins + 1 + kVxCtlWords;
+    TRY(ensure(c, c->vx_tab, words, &t->head));
+    t->tab = t->head + head;
+    t->seg_tot = t->tab + (size_t)t->ntiles * kVxMaxBins;
+    t->bucket_start = t->seg_tot + (size_t)t->nsegs * kVxMaxBins;
+    t->ctl = t->bucket_start + kVxMaxBins + 1;
+    return MI_ICP_OK;
+}
+
+// the arrays that are there (the points always), packed to the front for vx_scatter<na>; returns na
+static int vx_pack(const Pay3* const in[3], Pay3* const out[3], VxArrays* a) {
+    int na = 0;
+    for (int k = 0; k < 3; ++k) {
+        a->in[k] = nullptr;
+        a->out[k] = nullptr;
+    }
+    for (int k = 0; k < 3; ++k)
+        if (in[k]) {
+            a->in[na] = in[k];
+            a->out[na] = out[k];
+            ++na;
+        }
+    return na;
+}
+
+// one stable partition of the cloud by the plan at d (voxel_dense.h 1-3): the dense path's bucket pass, or one 11-bit
+// radix pass of voxel_wide_sort.  Every kernel reads the plan on the device.
+static void vx_partition(mi_icp_ctx* c, const VxDev* d, const VxArrays& a, int na, int n, const VxTables& t) {
+    vx_hist<<<t.ntiles, kVxThreads, 0, c->stream>>>(a.in[0], n, d, t.tab);
+    vx_colsum<<<dim3((unsigned)t.nsegs, (unsigned)(kVxMaxBins / 256)), 256, 0, c->stream>>>(t.tab, t.ntiles, d, t.seg_tot);
+    vx_colscan<<<1, 1024, 0, c->stream>>>(t.seg_tot, t.nsegs, n, d, t.bucket_start, t.ctl);
+    const int grid = std::min(t.ntiles, vx_cu_count());
+    if (na == 1) vx_scatter<1><<<grid, kVxThreads, 0, c->stream>>>(a, n, t.ntiles, d, t.tab, t.seg_tot, t.bucket_start, t.ctl);
+    else if (na == 2) vx_scatter<2><<<grid, kVxThreads, 0, c->stream>>>(a, n, t.ntiles, d, t.tab, t.seg_tot, t.bucket_start, t.ctl);
+    else vx_scatter<3><<<grid, kVxThreads, 0, c->stream>>>(a, n, t.ntiles, d, t.tab, t.seg_tot, t.bucket_start, t.ctl);
+}
+
+// Where the means of up to m voxels go: the caller's arrays, or (MI_ICP_HOST) staging buffers; nullptr for an array
+// that is not there.  voxel_out_back copies them to the caller and waits for the stream.
+static int voxel_out(mi_icp_ctx* c, const float* const in[3], float* const out[3], int64_t m, int mem_kind, float* dst[3]) {
+    for (int k = 0; k < 3; ++k) {
+        dst[k] = in[k] ? out[k] : nullptr;
+        if (in[k] && mem_kind == MI_ICP_HOST) TRY(ensure(c, c->stage[3 + k], (size_t)m * 3, &dst[k]));
+    }
+    return MI_ICP_OK;
+}
+
+static int voxel_out_back(mi_icp_ctx* c, float* const dst[3], float* const out[3], int64_t m, int mem_kind) {
+    if (mem_kind == MI_ICP_HOST)
+        for (int k = 0; k < 3; ++k)
+            if (dst[k]) TRY(from_device(c, (const float*)dst[k], out[k], (size_t)m * 3, mem_kind));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MI_ICP_OK;
+}
+
 // VoxelDownSample of a DENSE grid (voxel_dense.h): every point moves once.  Launched BEHIND the bounds kernels without
-// waiting for them: the plan is made on the device (vx_plan_kernel: a packed key of 14 ... 21 bits and enough points per
+// waiting for them: the plan is made on the device (vx_bounds_plan: a packed key of 14 ... 22 bits and enough points per
 // bucket), every kernel reads it there and does nothing when the grid is not one for this path.  The caller then waits
 // ONCE, for the bounds and this path's control words together.  *launched = false: nothing was started.
-static int voxel_dense_launch(mi_icp_ctx* c, const float* dp, const float* dn, const float* dcol, int64_t n, float voxel,
-                              float* out_xyz, float* out_normals, float* out_colors, int mem_kind,
-                              bool* launched, float** op_, float** on_, float** oc_) {
+static int voxel_dense_launch(mi_icp_ctx* c, const float* const in[3], int64_t n, float voxel, float* const out[3], int mem_kind,
+                              bool* launched, float* dst[3]) {
     *launched = false;
     if (std::getenv("MI_ICP_NO_DENSE_VOXEL")) return MI_ICP_OK;  // A/B switch, read at every call (tests compare both paths)
     if (n < (1 << 17) || n > ((int64_t)1 << 26)) return MI_ICP_OK;
     bool ordered = false;
     TRY(vx_order_ok(c, &ordered));
     if (!ordered) return MI_ICP_OK;
-    const int ncu = vx_cu_count();
-    const int ntiles = (int)((n + kVxTile - 1) / kVxTile);
-    const int nsegs = (ntiles + kVxSeg - 1) / kVxSeg;
-    // the tables, sized for 2048 buckets: the buckets' occupied-voxel counts, the plan, [ntiles][2048], [nsegs][2048],
-    // bucket_start[2049], the control words
+    // ahead of the tables: the buckets' occupied-voxel counts, the plan
     const size_t plan_words = (sizeof(VxDev) + 7) / 8 * 2;
-    const size_t words = (size_t)kVxMaxBins + plan_words + ((size_t)ntiles + nsegs) * kVxMaxBins + kVxMaxBins + 1 + kVxCtlWords;
-    uint32_t* w;
-    TRY(ensure(c, c->vx_tab, words, &w));
-    uint32_t* occ = w;
-    VxDev* plan = reinterpret_cast<VxDev*>(w + (size_t)kVxMaxBins);
-    uint32_t* tab = w + (size_t)kVxMaxBins + plan_words;
-    uint32_t* seg_tot = tab + (size_t)ntiles * kVxMaxBins;
-    uint32_t* bucket_start = seg_tot + (size_t)nsegs * kVxMaxBins;
-    uint32_t* ctl = bucket_start + kVxMaxBins + 1;
-    VxArrays a;
-    const float* in[3] = {dp, dn, dcol};
-    const int64_t vmax = std::min<int64_t>(n, (int64_t)1 << 22);
+    VxTables t;
+    TRY(vx_tables(c, n, (size_t)kVxMaxBins + plan_words, &t));
+    uint32_t* occ = t.head;
+    VxDev* plan = reinterpret_cast<VxDev*>(t.head + (size_t)kVxMaxBins);
+    const Pay3* pin[3];
+    Pay3* pout[3] = {nullptr, nullptr, nullptr};
     Pay3* tmp[3] = {nullptr, nullptr, nullptr};  // the buckets' means before they are moved together: a slot per cell of the grid
     for (int k = 0; k < 3; ++k) {
-        a.in[k] = reinterpret_cast<const Pay3*>(in[k]);
-        a.out[k] = nullptr;
+        pin[k] = reinterpret_cast<const Pay3*>(in[k]);
         if (in[k]) {
-            TRY(ensure(c, c->vpay[k], (size_t)n, &a.out[k]));
+            TRY(ensure(c, c->vpay[k], (size_t)n, &pout[k]));
             TRY(ensure(c, c->vpay[3 + k], (size_t)1 << 22, &tmp[k]));
         }
     }
-    float *op = out_xyz, *on = out_normals, *oc = out_colors;
-    if (mem_kind == MI_ICP_HOST) {
-        TRY(ensure(c, c->stage[3], (size_t)vmax * 3, &op));
-        if (dn) TRY(ensure(c, c->stage[4], (size_t)vmax * 3, &on));
-        if (dcol) TRY(ensure(c, c->stage[5], (size_t)vmax * 3, &oc));
-    }
+    TRY(voxel_out(c, in, out, std::min<int64_t>(n, (int64_t)1 << 22), mem_kind, dst));
     {   // the bounds (compute_bounds' two launches, the second one making the plan as well)
         float* part;
         TRY(ensure(c, c->bounds_part, (size_t)kBoundsBlocks * 6, &part));
         const int nb = (int)std::min<int64_t>(kBoundsBlocks, blocks_for(n));
-        bounds_partial<<<nb, 256, 0, c->stream>>>(dp, (int)n, part);
-        static const int hb_force = [] { const char* e = std::getenv("MI_ICP_VOXEL_HB"); return e ? std::atoi(e) : 0; }();  // measurements
-        vx_bounds_plan<<<1, 64, 0, c->stream>>>(part, nb, voxel, (long long)n, hb_force, plan, ctl);
+        bounds_partial<<<nb, 256, 0, c->stream>>>(in[0], (int)n, part);
+        vx_bounds_plan<<<1, 64, 0, c->stream>>>(part, nb, voxel, (long long)n, plan, t.ctl);
     }
-    vx_hist<<<ntiles, kVxThreads, 0, c->stream>>>(a.in[0], (int)n, plan, tab);
-    vx_colsum<<<dim3((unsigned)nsegs, (unsigned)(kVxMaxBins / 256)), 256, 0, c->stream>>>(tab, ntiles, plan, seg_tot);
-    vx_colscan<<<1, 1024, 0, c->stream>>>(seg_tot, nsegs, (int)n, plan, bucket_start, ctl);
-    {   // the arrays that are there, packed to the front (vx_scatter<kArrays>)
-        VxArrays pk = a;
-        int na = 1;
-        for (int k = 1; k < 3; ++k)
-            if (a.in[k]) {
-                pk.in[na] = a.in[k];
-                pk.out[na] = a.out[k];
-                ++na;
-            }
-        const int grid = std::min(ntiles, ncu);
-        if (na == 1) vx_scatter<1><<<grid, kVxThreads, 0, c->stream>>>(pk, (int)n, ntiles, plan, tab, seg_tot, bucket_start, ctl);
-        else if (na == 2) vx_scatter<2><<<grid, kVxThreads, 0, c->stream>>>(pk, (int)n, ntiles, plan, tab, seg_tot, bucket_start, ctl);
-        else vx_scatter<3><<<grid, kVxThreads, 0, c->stream>>>(pk, (int)n, ntiles, plan, tab, seg_tot, bucket_start, ctl);
-    }
+    VxArrays a;
+    const int na = vx_pack(pin, pout, &a);
+    vx_partition(c, plan, a, na, (int)n, t);
 #define MI_VX_FINISH(N, C)                                                                                                     \
-    vx_finish<N, C><<<std::min(kVxMaxBins, ncu), kVxFinThreads, 0, c->stream>>>(a.out[0], a.out[1], a.out[2], plan, bucket_start, ctl, \
-                                                                               occ, tmp[0], tmp[1], tmp[2])
-    if (dn && dcol) MI_VX_FINISH(true, true);
-    else if (dn) MI_VX_FINISH(true, false);
-    else if (dcol) MI_VX_FINISH(false, true);
+    vx_finish<N, C><<<std::min(kVxMaxBins, vx_cu_count()), kVxFinThreads, 0, c->stream>>>(pout[0], pout[1], pout[2], plan,   \
+                                                                                         t.bucket_start, t.ctl, occ, tmp[0], \
+                                                                                         tmp[1], tmp[2])
+    if (in[1] && in[2]) MI_VX_FINISH(true, true);
+    else if (in[1]) MI_VX_FINISH(true, false);
+    else if (in[2]) MI_VX_FINISH(false, true);
     else MI_VX_FINISH(false, false);
 #undef MI_VX_FINISH
-    vx_compact<<<kVxMaxBins, 256, 0, c->stream>>>(plan, ctl, occ, tmp[0], tmp[1], tmp[2], reinterpret_cast<Pay3*>(op),
-                                                   reinterpret_cast<Pay3*>(dn ? on : nullptr), reinterpret_cast<Pay3*>(dcol ? oc : nullptr));
+    vx_compact<<<kVxMaxBins, 256, 0, c->stream>>>(plan, t.ctl, occ, tmp[0], tmp[1], tmp[2], reinterpret_cast<Pay3*>(dst[0]),
+                                                   reinterpret_cast<Pay3*>(dst[1]), reinterpret_cast<Pay3*>(dst[2]));
     KCHK(c);
-    HIPCHK(c, hipMemcpyAsync(c->u_host, ctl, kVxCtlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));  // (with the bounds)
+    HIPCHK(c, hipMemcpyAsync(c->u_host, t.ctl, kVxCtlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));  // (with the bounds)
     *launched = true;
-    *op_ = op;
-    *on_ = on;
-    *oc_ = oc;
     return MI_ICP_OK;
 }
 
@@ -260,27 +284,17 @@ static int voxel_dense_launch(mi_icp_ctx* c, const float* dp, const float* dn, c
 // kernels as a radix sort of 11-bit digits -- two or three stable passes for a key of up to 32 bits where 8-bit digits
 // take three or four, keys recomputed from the points in every pass instead of carried and stored, four launches a pass
 // instead of five.  The plans of the passes (digit = (key >> L) & (B - 1)) are written by the host, which knows the grid
-// here.  pay[]: the arrays that hold the sorted cloud.
+// here.  Its ranks, like the dense path's, need vx_order_ok.  pay[]: the arrays that hold the sorted cloud.
 static int voxel_wide_sort(mi_icp_ctx* c, const Pay3* const first[3], int64_t n, const VoxelGrid& grid, int bits, const Pay3* pay[3]) {
     const int npass = (bits + 10) / 11, width = (bits + npass - 1) / npass;
-    const int ntiles = (int)((n + kVxTile - 1) / kVxTile);
-    const int nsegs = (ntiles + kVxSeg - 1) / kVxSeg;
     static_assert(sizeof(VxDev) == 64, "three plans in 192 bytes of the pinned block");
-    const size_t plan_words = 3 * sizeof(VxDev) / 4;
-    const size_t words = plan_words + ((size_t)ntiles + nsegs) * kVxMaxBins + kVxMaxBins + 1 + kVxCtlWords;
-    uint32_t* w;
-    TRY(ensure(c, c->vx_tab, words, &w));
-    VxDev* plans = reinterpret_cast<VxDev*>(w);
-    uint32_t* tab = w + plan_words;
-    uint32_t* seg_tot = tab + (size_t)ntiles * kVxMaxBins;
-    uint32_t* bucket_start = seg_tot + (size_t)nsegs * kVxMaxBins;
-    uint32_t* ctl = bucket_start + kVxMaxBins + 1;
+    VxTables t;
+    TRY(vx_tables(c, n, 3 * sizeof(VxDev) / 4, &t));
+    VxDev* plans = reinterpret_cast<VxDev*>(t.head);
     VxDev* hp = reinterpret_cast<VxDev*>(c->f_host + 16);  // (pinned; [0..7] hold the bounds)
     for (int p = 0; p < npass; ++p) {
         VxDev v;
-        v.g.g = grid;
-        v.g.inv = 1.0f / grid.voxel;
-        v.g.key_mask = (bits >= 32) ? 0xffffffffu : ((1u << bits) - 1u);
+        v.g = vx_grid(grid, bits);
         v.bits = bits;
         v.L = p * width;
         v.hb = std::min(width, bits - p * width);
@@ -297,29 +311,10 @@ static int voxel_wide_sort(mi_icp_ctx* c, const Pay3* const first[3], int64_t n,
         for (int a = 0; a < 3; ++a)
             if (first[a]) TRY(ensure(c, c->vpay[set * 3 + a], (size_t)n, &buf[set][a]));
     for (int a = 0; a < 3; ++a) pay[a] = first[a];
-    int na = 0;
-    for (int a = 0; a < 3; ++a) na += first[a] ? 1 : 0;
-    const int grid_sc = std::min(ntiles, vx_cu_count());
     for (int p = 0; p < npass; ++p) {
         VxArrays pk;
-        int k = 0;
-        for (int a = 0; a < 3; ++a) {
-            pk.in[a] = nullptr;
-            pk.out[a] = nullptr;
-        }
-        for (int a = 0; a < 3; ++a)
-            if (first[a]) {
-                pk.in[k] = pay[a];
-                pk.out[k] = buf[p & 1][a];
-                ++k;
-            }
-        const VxDev* d = plans + p;
-        vx_hist<<<ntiles, kVxThreads, 0, c->stream>>>(pk.in[0], (int)n, d, tab);
-        vx_colsum<<<dim3((unsigned)nsegs, (unsigned)(kVxMaxBins / 256)), 256, 0, c->stream>>>(tab, ntiles, d, seg_tot);
-        vx_colscan<<<1, 1024, 0, c->stream>>>(seg_tot, nsegs, (int)n, d, bucket_start, ctl);
-        if (na == 1) vx_scatter<1><<<grid_sc, kVxThreads, 0, c->stream>>>(pk, (int)n, ntiles, d, tab, seg_tot, bucket_start, ctl);
-        else if (na == 2) vx_scatter<2><<<grid_sc, kVxThreads, 0, c->stream>>>(pk, (int)n, ntiles, d, tab, seg_tot, bucket_start, ctl);
-        else vx_scatter<3><<<grid_sc, kVxThreads, 0, c->stream>>>(pk, (int)n, ntiles, d, tab, seg_tot, bucket_start, ctl);
+        const int na = vx_pack(pay, buf[p & 1], &pk);
+        vx_partition(c, plans + p, pk, na, (int)n, t);
         for (int a = 0; a < 3; ++a)
             if (first[a]) pay[a] = buf[p & 1][a];
     }
@@ -330,10 +325,9 @@ static int voxel_wide_sort(mi_icp_ctx* c, const Pay3* const first[3], int64_t n,
 // VoxelDownSample for grids whose packed (x, y, z) key fits 32 bits (geometry_kernels.h, "the path for grids ..."):
 // keys -> radix passes on the bits above the lowest L that carry the payload -> runs of equal key >> L -> which voxels
 // occur in each run -> their output positions -> means.  Two host synchronisations in the whole call (the bounds that
-// place the grid, the voxel count that sizes the output), as before.
-static int voxel_downsample_keys32(mi_icp_ctx* c, const float* dp, const float* dn, const float* dcol, int64_t n,
-                                   const VoxelGrid& g, int bits, float* out_xyz, float* out_normals, float* out_colors,
-                                   int64_t* m, int mem_kind) {
+// place the grid, the voxel count that sizes the output).
+static int voxel_downsample_keys32(mi_icp_ctx* c, const float* const in[3], int64_t n, const VoxelGrid& g, int bits,
+                                   float* const out[3], int64_t* m, int mem_kind) {
     SortBuffers sb;
     TRY(sort_buffers(c, n, &sb));
     uint32_t* const keys[2] = {reinterpret_cast<uint32_t*>(sb.keys[0]), reinterpret_cast<uint32_t*>(sb.keys[1])};
@@ -346,18 +340,19 @@ static int voxel_downsample_keys32(mi_icp_ctx* c, const float* dp, const float* 
         L = 0;
         passes = (bits + 7) / 8;
     }
-    const Pay3* first[3] = {reinterpret_cast<const Pay3*>(dp), reinterpret_cast<const Pay3*>(dn), reinterpret_cast<const Pay3*>(dcol)};
+    const Pay3* first[3] = {reinterpret_cast<const Pay3*>(in[0]), reinterpret_cast<const Pay3*>(in[1]), reinterpret_cast<const Pay3*>(in[2])};
     const Pay3* pay[3];
     const uint32_t* skeys;
-    static const bool no_wide = std::getenv("MI_ICP_NO_WIDE_VOXEL_SORT") != nullptr;  // A/B switch
-    if (L == 0 && n >= (1 << 17) && n <= ((int64_t)1 << 26) && bits >= 12 && !no_wide) {
+    bool wide = false;
+    if (L == 0 && n >= (1 << 17) && n <= ((int64_t)1 << 26) && bits >= 12) TRY(vx_order_ok(c, &wide));
+    if (wide) {
         // a large cloud, the key sorted whole: 11-bit digits, the keys made once, from the sorted points
         TRY(voxel_wide_sort(c, first, n, g, bits, pay));
         voxel_keys32<<<blocks_for(n), 256, 0, c->stream>>>(reinterpret_cast<const float*>(pay[0]), n, g, keys[0]);
         KCHK(c);
         skeys = keys[0];
     } else {
-        voxel_keys32<<<blocks_for(n), 256, 0, c->stream>>>(dp, n, g, keys[0]);
+        voxel_keys32<<<blocks_for(n), 256, 0, c->stream>>>(in[0], n, g, keys[0]);
         KCHK(c);
         Pay3* scratch[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
         for (int set = 0; set < std::min(passes, 2); ++set)
@@ -390,30 +385,20 @@ static int voxel_downsample_keys32(mi_icp_ctx* c, const float* dp, const float* 
     HIPCHK(c, hipMemcpyAsync(c->u_host, total, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int64_t nvox = (int64_t)c->u_host[0];
-    float *op = out_xyz, *on = out_normals, *oc = out_colors;
-    if (mem_kind == MI_ICP_HOST) {
-        TRY(ensure(c, c->stage[3], (size_t)nvox * 3, &op));
-        if (dn) TRY(ensure(c, c->stage[4], (size_t)nvox * 3, &on));
-        if (dcol) TRY(ensure(c, c->stage[5], (size_t)nvox * 3, &oc));
-    }
+    float* dst[3];
+    TRY(voxel_out(c, in, out, nvox, mem_kind, dst));
     if (L > 0) {  // a wave per run
         const int64_t rmax = (bits - L >= 31) ? n : std::min<int64_t>(n, (int64_t)1 << (bits - L));
         voxel_means_wave<<<(unsigned)rmax, 64, 0, c->stream>>>(skeys, pay[0], pay[1], pay[2], run_start, voff, mask, nruns, rmax, L,
-                                                                      op, dn ? on : nullptr, dcol ? oc : nullptr);
+                                                                      dst[0], dst[1], dst[2]);
     } else if (n <= 16 * nvox) {  // a run is a voxel, and a short one: a thread each
-        voxel_means_thread<<<blocks_for(nvox), 256, 0, c->stream>>>(pay[0], pay[1], pay[2], run_start, nvox, op, dn ? on : nullptr,
-                                                                    dcol ? oc : nullptr);
+        voxel_means_thread<<<blocks_for(nvox), 256, 0, c->stream>>>(pay[0], pay[1], pay[2], run_start, nvox, dst[0], dst[1], dst[2]);
     } else {      // a run is a voxel: 8 lanes each
         voxel_means_runs<<<blocks_for(nvox * 8), 256, 0, c->stream>>>(skeys, pay[0], pay[1], pay[2], run_start, voff, mask, nruns, L,
-                                                                     nvox, op, dn ? on : nullptr, dcol ? oc : nullptr);
+                                                                     nvox, dst[0], dst[1], dst[2]);
     }
     KCHK(c);
-    if (mem_kind == MI_ICP_HOST) {
-        TRY(from_device(c, (const float*)op, out_xyz, (size_t)nvox * 3, mem_kind));
-        if (dn) TRY(from_device(c, (const float*)on, out_normals, (size_t)nvox * 3, mem_kind));
-        if (dcol) TRY(from_device(c, (const float*)oc, out_colors, (size_t)nvox * 3, mem_kind));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    TRY(voxel_out_back(c, dst, out, nvox, mem_kind));
     *m = nvox;
     return MI_ICP_OK;
 }
@@ -430,23 +415,24 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
     if (!xyz || !out_xyz || (normals && !out_normals) || (colors && !out_colors))
         return fail(c, MI_ICP_ERR_INVALID, "voxel_downsample: null buffer");
 
-    const float *dp, *dn, *dcol;
-    TRY(to_device(c, xyz, (size_t)n * 3, mem_kind, c->stage[0], &dp));
-    TRY(to_device(c, normals, (size_t)n * 3, mem_kind, c->stage[1], &dn));
-    TRY(to_device(c, colors, (size_t)n * 3, mem_kind, c->stage[2], &dcol));
+    const float* in[3];
+    TRY(to_device(c, xyz, (size_t)n * 3, mem_kind, c->stage[0], &in[0]));
+    TRY(to_device(c, normals, (size_t)n * 3, mem_kind, c->stage[1], &in[1]));
+    TRY(to_device(c, colors, (size_t)n * 3, mem_kind, c->stage[2], &in[2]));
+    float* const out[3] = {out_xyz, out_normals, out_colors};
 
     // a dense grid: one move of every point (voxel_dense.h), started behind the bounds without waiting for them; the
     // bounds come back with its control words
     bool dense = false;
-    float *dop = nullptr, *don = nullptr, *doc = nullptr;
+    float* dst[3];
     // (a context whose last call with this voxel size and a cloud of about this size was turned away by the plan -- a grid
     // of too many or too few cells -- does not try again: the attempt is seven launches that do nothing, ~25 us in front
     // of the general path.  Speed only; a stream of scans of one scene is the case in mind.)
     const bool turned_away = c->vx_refused_voxel == voxel && n >= c->vx_refused_n / 2 && n <= c->vx_refused_n * 2;
-    if (!turned_away) TRY(voxel_dense_launch(c, dp, dn, dcol, n, voxel, out_xyz, out_normals, out_colors, mem_kind, &dense, &dop, &don, &doc));
+    if (!turned_away) TRY(voxel_dense_launch(c, in, n, voxel, out, mem_kind, &dense, dst));
     if (!dense) {
         float* bnd;
-        TRY(compute_bounds(c, dp, n, &bnd));
+        TRY(compute_bounds(c, in[0], n, &bnd));
         HIPCHK(c, hipMemcpyAsync(c->f_host, bnd, 8 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -461,53 +447,30 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
     }
     if (dense && c->u_host[0] == 0u) {  // (1: the cloud crowds into a few buckets, 2: not a grid for that path -- nothing was written)
         const int64_t nvox = (int64_t)c->u_host[2];
-        if (mem_kind == MI_ICP_HOST) {
-            TRY(from_device(c, (const float*)dop, out_xyz, (size_t)nvox * 3, mem_kind));
-            if (dn) TRY(from_device(c, (const float*)don, out_normals, (size_t)nvox * 3, mem_kind));
-            if (dcol) TRY(from_device(c, (const float*)doc, out_colors, (size_t)nvox * 3, mem_kind));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
+        if (mem_kind == MI_ICP_HOST) TRY(voxel_out_back(c, dst, out, nvox, mem_kind));  // (device arrays: already waited for)
         *m = nvox;
         c->last_voxel_path = 1;
         return MI_ICP_OK;
     }
-    VoxelGrid g;
-    float ext = 0.0f;
-    int bits[3];
-    {
-        const float* b = c->f_host;
-        const float origin[3] = {b[0] - voxel * 0.5f, b[1] - voxel * 0.5f, b[2] - voxel * 0.5f};
-        for (int d = 0; d < 3; ++d) ext = std::fmax(ext, (b[3 + d] + voxel * 0.5f) - origin[d]);
-        if (voxel * (float)INT32_MAX < ext) return MI_ICP_OK;  // down_sample.cu:186-189
-        c->last_voxel_path = 0;
-        g.ox = origin[0];
-        g.oy = origin[1];
-        g.oz = origin[2];
-        g.voxel = voxel;
-        for (int d = 0; d < 3; ++d) {
-            const double cells = std::floor(((double)b[3 + d] - (double)origin[d]) / (double)voxel) + 2.0;
-            int nb = 1;
-            while (nb < 32 && (double)(1ull << nb) < cells) ++nb;
-            bits[d] = nb;
-        }
-        g.bits_y = bits[1];
-        g.bits_z = bits[2];
-    }
+    const VoxelGridFit f = voxel_grid_fit(c->f_host, voxel);
+    if (f.overflow) return MI_ICP_OK;
+    c->last_voxel_path = 0;
+    const VoxelGrid& g = f.g;
+    const int bits = f.bits[0] + f.bits[1] + f.bits[2];
 
     // (grids whose packed key needs more than 32 bits keep the first form below: 64-bit keys + indices, one gather)
-    if (bits[0] + bits[1] + bits[2] <= 32)
-        return voxel_downsample_keys32(c, dp, dn, dcol, n, g, bits[0] + bits[1] + bits[2], out_xyz, out_normals, out_colors, m,
-                                       mem_kind);
+    if (bits <= 32) return voxel_downsample_keys32(c, in, n, g, bits, out, m, mem_kind);
 
+    const float* dp = in[0];
     SortBuffers sb;
     TRY(sort_buffers(c, n, &sb));
     const uint32_t* order;
     const uint64_t* packed_sorted = nullptr;  // sorted voxel keys when one key identifies the voxel
     const int nb = blocks_for(n);
-    if (bits[0] + bits[1] + bits[2] <= 64) {
+    if (bits <= 64) {
         voxel_keys<<<nb, 256, 0, c->stream>>>(dp, n, g, -1, nullptr, sb.keys[0], sb.vals[0]);
         KCHK(c);
-        const int cur = radix_sort_pairs(c->stream, sb, n, bits[0] + bits[1] + bits[2]);
+        const int cur = radix_sort_pairs(c->stream, sb, n, bits);
         order = sb.vals[cur];
         packed_sorted = sb.keys[cur];
     } else {
@@ -521,10 +484,7 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
             }
             voxel_keys<<<nb, 256, 0, c->stream>>>(dp, n, g, axis, tmp_order, sb.keys[0], sb.vals[0]);
             KCHK(c);
-            prev = sb.vals[radix_sort_pairs(c->stream, sb, n, bits[axis])];
-            if (prev != sb.vals[0] && axis > 0) {
-                // next round writes keys[0]/vals[0]; the result already sits in the other pair
-            }
+            prev = sb.vals[radix_sort_pairs(c->stream, sb, n, f.bits[axis])];
         }
         order = prev;
     }
@@ -547,21 +507,10 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
     voxel_seg_starts<<<nb, 256, 0, c->stream>>>(head, pos, n, seg_start);
     KCHK(c);
 
-    float *op = out_xyz, *on = out_normals, *oc = out_colors;
-    if (mem_kind == MI_ICP_HOST) {
-        TRY(ensure(c, c->stage[3], (size_t)nvox * 3, &op));
-        if (dn) TRY(ensure(c, c->stage[4], (size_t)nvox * 3, &on));
-        if (dcol) TRY(ensure(c, c->stage[5], (size_t)nvox * 3, &oc));
-    }
-    voxel_means<<<blocks_for(nvox * 8), 256, 0, c->stream>>>(dp, dn, dcol, order, seg_start, nvox, n, op,
-                                                            dn ? on : nullptr, dcol ? oc : nullptr);
+    TRY(voxel_out(c, in, out, nvox, mem_kind, dst));
+    voxel_means<<<blocks_for(nvox * 8), 256, 0, c->stream>>>(dp, in[1], in[2], order, seg_start, nvox, n, dst[0], dst[1], dst[2]);
     KCHK(c);
-    if (mem_kind == MI_ICP_HOST) {
-        TRY(from_device(c, (const float*)op, out_xyz, (size_t)nvox * 3, mem_kind));
-        if (dn) TRY(from_device(c, (const float*)on, out_normals, (size_t)nvox * 3, mem_kind));
-        if (dcol) TRY(from_device(c, (const float*)oc, out_colors, (size_t)nvox * 3, mem_kind));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    TRY(voxel_out_back(c, dst, out, nvox, mem_kind));
     *m = nvox;
     return MI_ICP_OK;
 }

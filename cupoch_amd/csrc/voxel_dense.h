@@ -21,8 +21,7 @@
 // contiguous stretch of the tile and private counters, two 16-bit counters to a word, and takes the rank from ONE
 // ds_add_rtn_u32 per point: lanes of one instruction that meet in a word are served in ascending lane order on gfx950
 // (scripts/dev/probes/lds_atomic_order.hip: 150M ranks in 18 conflict patterns, none out of order; vx_probe_order below
-// re-checks it once per context and the path is not taken if it ever fails).  The first form matched the lanes of a
-// bin with one ballot per key bit: 11.7 of a tile's 24 us.
+// re-checks it once per context, and neither this path nor voxel_wide_sort is taken if it ever fails).
 //
 // Keys.  floor((p - origin) / voxel) per axis as down_sample.cu:69-73 evaluates it (IEEE division): the quotient is first
 // estimated with the reciprocal; unless it lies within 4 ulp-bounds of an integer its floor IS the division's floor,
@@ -58,6 +57,15 @@ struct VxGrid {
     uint32_t key_mask;
 };
 
+// (the dense path's plan and the host's plans of voxel_wide_sort)
+__host__ __device__ inline VxGrid vx_grid(const VoxelGrid& g, int bits) {
+    VxGrid v;
+    v.g = g;
+    v.inv = 1.0f / g.voxel;
+    v.key_mask = (bits >= 32) ? 0xffffffffu : ((1u << bits) - 1u);
+    return v;
+}
+
 // The plan, made ON THE DEVICE from the bounds (vx_bounds_plan) so that the host does not have to wait for them before it
 // launches: every kernel below reads it, and does nothing when `ok` is 0 (the grid is not one for this path; the host
 // learns that with the result and takes the general path).
@@ -76,36 +84,19 @@ struct VxDev {
 constexpr int kVxCtlWords = 12;
 constexpr int kVxCtlBounds = 4;
 
-// -DMI_VX_CLOCKS (measurements only): thread 0 of every workgroup of vx_scatter / vx_finish notes the 100-MHz clock at its
-// phase boundaries; mi_vx_clocks_dump (mi_geometry.hip) copies the table out
-#ifdef MI_VX_CLOCKS
-constexpr int kVxClkSlots = 12;
-__device__ unsigned long long g_vx_clk[2][4096][kVxClkSlots];
-#define VX_CLK(kernel, wg, slot)                                                                                  \
-    do {                                                                                                          \
-        if (threadIdx.x == 0 && (wg) < 4096) g_vx_clk[kernel][wg][slot] = (unsigned long long)wall_clock64();     \
-    } while (0)
-#define VX_DRAIN() __builtin_amdgcn_s_waitcnt(0)
-#else
-#define VX_CLK(kernel, wg, slot) do { } while (0)
-#define VX_DRAIN() do { } while (0)
-#endif
-
-// one axis: floor(x / voxel) with x = p - origin
+// one axis: voxel_cell (geometry_kernels.h) with x = p - origin
 __device__ __forceinline__ int32_t vx_cell(float x, float voxel, float inv) {
     const float q = x * inv;             // within 1.5 * 2^-23 |q| of the correctly rounded quotient
     const float fl = floorf(q);
     const float f = q - fl;              // (exact)
     const float margin = fabsf(q) * 0x1p-21f;
     if (f > margin && f < 1.0f - margin) return (int32_t)fl;
-    return (int32_t)floorf(x / voxel);   // near an integer, zero, or not finite: the division itself
+    return voxel_cell(x, voxel);         // near an integer, zero, or not finite: the division itself
 }
 
 __device__ __forceinline__ uint32_t vx_key(const VxGrid& g, const Pay3& p) {
-    const uint32_t kx = (uint32_t)vx_cell(p.x - g.g.ox, g.g.voxel, g.inv);
-    const uint32_t ky = (uint32_t)vx_cell(p.y - g.g.oy, g.g.voxel, g.inv);
-    const uint32_t kz = (uint32_t)vx_cell(p.z - g.g.oz, g.g.voxel, g.inv);
-    return ((kx << (g.g.bits_y + g.g.bits_z)) | (ky << g.g.bits_z) | kz) & g.key_mask;
+    return voxel_pack32(g.g, vx_cell(p.x - g.g.ox, g.g.voxel, g.inv), vx_cell(p.y - g.g.oy, g.g.voxel, g.inv),
+                        vx_cell(p.z - g.g.oz, g.g.voxel, g.inv)) & g.key_mask;
 }
 
 // A workgroup barrier for data shared through LDS only: __syncthreads() also makes the workgroup's GLOBAL stores
@@ -184,38 +175,21 @@ static __global__ __launch_bounds__(256) void vx_probe_order(uint32_t* __restric
 }
 
 // ---- 0b: the plan ----------------------------------------------------------------------------------------------------
-// bounds: min[3], max[3] (lbvh.h bounds_final).  The host evaluates the same expressions (mi_geometry.hip) when it needs
-// the grid itself; hb is chosen for ~6k points per bucket (one LDS chunk of vx_finish).
-__device__ __forceinline__ void vx_make_plan(const float* bounds, float voxel, long long n, int hb_force, VxDev* __restrict__ d, uint32_t* __restrict__ ctl) {
+// bounds: min[3], max[3] (lbvh.h bounds_final); the grid is voxel_grid_fit's, as on the host (mi_geometry.hip).  hb is
+// chosen for ~6k points per bucket (one LDS chunk of vx_finish).
+__device__ __forceinline__ void vx_make_plan(const float* bounds, float voxel, long long n, VxDev* __restrict__ d, uint32_t* __restrict__ ctl) {
     VxDev v;
-    float origin[3], ext = 0.0f;
-    int nb[3];
-    for (int k = 0; k < 3; ++k) {
-        origin[k] = bounds[k] - voxel * 0.5f;
-        ext = fmaxf(ext, (bounds[3 + k] + voxel * 0.5f) - origin[k]);
-        const double cells = floor(((double)bounds[3 + k] - (double)origin[k]) / (double)voxel) + 2.0;
-        int b = 1;
-        while (b < 32 && (double)(1ull << b) < cells) ++b;
-        nb[k] = b;
-    }
-    v.empty = (voxel * (float)INT32_MAX < ext) ? 1 : 0;
-    v.g.g.ox = origin[0];
-    v.g.g.oy = origin[1];
-    v.g.g.oz = origin[2];
-    v.g.g.voxel = voxel;
-    v.g.g.bits_y = nb[1];
-    v.g.g.bits_z = nb[2];
-    v.g.inv = 1.0f / voxel;
-    const int bits = nb[0] + nb[1] + nb[2];
+    const VoxelGridFit f = voxel_grid_fit(bounds, voxel);
+    const int bits = f.bits[0] + f.bits[1] + f.bits[2];
+    v.empty = f.overflow ? 1 : 0;
+    v.g = vx_grid(f.g, bits);
     v.bits = bits;
-    v.g.key_mask = (bits >= 32) ? 0xffffffffu : ((1u << bits) - 1u);
     int hb = 0;
     const long long per_bucket = max(12288ll, n >> 10);  // ~12k points per bucket, and no more than 1024 buckets, the grid permitting ...
     while ((per_bucket << hb) < n) ++hb;         // (30M points, 21-bit key: 1024 buckets 0.645 ms, 2048: 0.685)
     if (hb < 8 && (n >> 8) >= 1024) hb = 8;      // ... but a bucket per CU at least (1M points: 128 buckets 0.125 ms, 256: 0.087)
     hb = max(hb, bits - 11);                     // (a bucket has at most 2048 voxels)
     hb = min(hb, min(11, bits - 6));
-    if (hb_force > 0 && hb_force >= bits - 11 && hb_force <= min(11, bits - 6)) hb = hb_force;  // (measurements: MI_ICP_VOXEL_HB)
     v.ok = (!v.empty && bits >= 14 && bits <= 22 && hb >= bits - 11 && hb >= 0 && (n >> max(hb, 0)) >= 256) ? 1 : 0;
     if (!v.ok) hb = 0;
     v.hb = hb;
@@ -235,7 +209,7 @@ __device__ __forceinline__ void vx_make_plan(const float* bounds, float voxel, l
 }
 
 // one wave behind bounds_partial (lbvh.h): the bounds of the cloud -- bounds_final's reduction -- and, in the same launch, the plan
-static __global__ __launch_bounds__(64) void vx_bounds_plan(const float* __restrict__ partial, int nblocks, float voxel, long long n, int hb_force,
+static __global__ __launch_bounds__(64) void vx_bounds_plan(const float* __restrict__ partial, int nblocks, float voxel, long long n,
                                                       VxDev* __restrict__ d, uint32_t* __restrict__ ctl) {
     const int lane = lane_id();
     float mn[3] = {INFINITY, INFINITY, INFINITY};
@@ -253,7 +227,7 @@ static __global__ __launch_bounds__(64) void vx_bounds_plan(const float* __restr
         b6[k] = wave_min(mn[k]);      // (lane 0 holds the result)
         b6[3 + k] = wave_max(mx[k]);
     }
-    if (lane == 0) vx_make_plan(b6, voxel, n, hb_force, d, ctl);
+    if (lane == 0) vx_make_plan(b6, voxel, n, d, ctl);
 }
 
 // ---- 1: the [tile][bucket] table ------------------------------------------------------------------------------------
@@ -418,10 +392,6 @@ static __global__ __launch_bounds__(kVxThreads) void vx_scatter(VxArrays a, int 
         const int64_t tbase = (int64_t)tile * kVxTile;
         const int tile_n = (int)min((int64_t)kVxTile, (int64_t)n - tbase);
         const int next = tile + (int)gridDim.x;
-        VX_CLK(0, tile, 0);
-#ifdef MI_VX_Q_EARLY
-        if (kArrays >= 2) MI_VX_LOAD(q, a.in[1], tile);
-#endif
         for (int k = lane; k < kVxMaxBins / 2; k += 64) row[k] = 0u;
         __builtin_amdgcn_wave_barrier();
         // where the tile's bucket runs go: fetched now, used after the ranks
@@ -435,8 +405,6 @@ static __global__ __launch_bounds__(kVxThreads) void vx_scatter(VxArrays a, int 
                 if (j < per && b < B) goff[j] = bucket_start[b] + srow[b] + trow[b];
             }
         }
-        VX_DRAIN();
-        VX_CLK(0, tile, 1);
         uint32_t packed[kVxItems];  // bucket << 16 | rank among the wave's earlier elements of that bucket; later the local position
 #pragma unroll
         for (int c = 0; c < kVxItems; ++c) {
@@ -444,11 +412,8 @@ static __global__ __launch_bounds__(kVxThreads) void vx_scatter(VxArrays a, int 
             const uint32_t bin = (vx_key(g, Pay3{px[c], py[c], pz[c]}) >> L) & (uint32_t)(B - 1);
             packed[c] = (bin << 16) | vx_rank(row, bin, e < tile_n);
         }
-#ifndef MI_VX_Q_EARLY
         if (kArrays >= 2) MI_VX_LOAD(q, a.in[1], tile);  // (behind the ranks: at the top of the tile it delayed the points it queued behind)
-#endif
         vx_barrier();  // (also: every thread has finished writing the previous tile out of the stage)
-        VX_CLK(0, tile, 2);
         // the tile's bucket runs: every wave's first position in every bucket, and where the run goes
         {
             uint32_t k[4][kVxWaves];
@@ -484,7 +449,6 @@ static __global__ __launch_bounds__(kVxThreads) void vx_scatter(VxArrays a, int 
             }
         }
         vx_barrier();
-        VX_CLK(0, tile, 3);
 #pragma unroll
         for (int c = 0; c < kVxItems; ++c) {
             const int e = wid * kVxWaveSeg + c * 64 + lane;
@@ -500,9 +464,7 @@ static __global__ __launch_bounds__(kVxThreads) void vx_scatter(VxArrays a, int 
         if (kArrays == 3) MI_VX_LOAD(p, a.in[2], tile);
         else if (next < ntiles) MI_VX_LOAD(p, a.in[0], next);
         vx_barrier();
-        VX_CLK(0, tile, 4);
         MI_VX_WRITE_OUT(a.out[0]);
-        VX_CLK(0, tile, 5);
         if (kArrays >= 2) {
             vx_barrier();
             MI_VX_RESTAGE(q);
@@ -516,9 +478,6 @@ static __global__ __launch_bounds__(kVxThreads) void vx_scatter(VxArrays a, int 
             vx_barrier();
             MI_VX_WRITE_OUT(a.out[2]);
         }
-#ifdef MI_VX_CLOCKS
-        VX_CLK(0, tile, 6);
-#endif
     }
 }
 #undef MI_VX_LOAD
@@ -581,7 +540,6 @@ __device__ __forceinline__ void vx_finish_body(unsigned char* __restrict__ lds, 
     }
     const int v0 = tid * kVpt;  // this thread's voxels: v0 ... v0 + kVpt - 1
     while (bucket < B) {
-        VX_CLK(1, bucket, 1);
         // the next ticket: asked for now, kept in a register until the bucket's end (stored to LDS at once it would be waited for at once)
         uint32_t ticket = 0;
         if (tid == 0) ticket = __hip_atomic_fetch_add(&ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -600,8 +558,6 @@ __device__ __forceinline__ void vx_finish_body(unsigned char* __restrict__ lds, 
             if (cbase != s) load(pts, cbase, cn);  // (the first chunk was asked for ahead)
             for (int k = lane; k < kSub / 2; k += 64) row[k] = 0u;
             __builtin_amdgcn_wave_barrier();
-            VX_DRAIN();
-            VX_CLK(1, bucket, 2);
             uint32_t packed[kItems];  // voxel << 16 | rank among the wave's earlier points of that voxel; later the position
 #pragma unroll
             for (int k = 0; k < kItems; ++k) {
@@ -610,7 +566,6 @@ __device__ __forceinline__ void vx_finish_body(unsigned char* __restrict__ lds, 
                 packed[k] = (sub << 16) | vx_rank(row, sub, i < cn);
             }
             vx_barrier();
-            VX_CLK(1, bucket, 3);
             uint32_t mine[kVpt];  // points of this thread's voxels in this chunk
 #pragma unroll
             for (int h = 0; h < kVpt; ++h) mine[h] = 0u;
@@ -658,7 +613,6 @@ __device__ __forceinline__ void vx_finish_body(unsigned char* __restrict__ lds, 
             } else {
                 vx_barrier();
             }
-            VX_CLK(1, bucket, 4);
 #pragma unroll
             for (int k = 0; k < kItems; ++k) {
                 const int i = wid * kWaveSeg + k * 64 + lane;
@@ -672,7 +626,6 @@ __device__ __forceinline__ void vx_finish_body(unsigned char* __restrict__ lds, 
             if (kNrm) load(nrm, cbase, cn);  // on their way while the points are added up
             else if (kCol) load(col, cbase, cn);
             vx_barrier();
-            VX_CLK(1, bucket, 5);
             auto add_runs = [&](double (&acc)[kVpt][3]) {
 #pragma unroll
                 for (int h = 0; h < kVpt; ++h)
@@ -707,9 +660,7 @@ __device__ __forceinline__ void vx_finish_body(unsigned char* __restrict__ lds, 
                 add_runs(ac);
             }
             if (!last) vx_barrier();  // the stage and the counters are reused
-            VX_CLK(1, bucket, 6);
         }
-        VX_CLK(1, bucket, 7);
         if (tid == 0) {
             s_bucket = ticket;
             occ[bucket] = occupied;
@@ -739,7 +690,6 @@ __device__ __forceinline__ void vx_finish_body(unsigned char* __restrict__ lds, 
                 if (kCol) tmp_col[slot] = Pay3{(float)(ac[h][0] / cnt), (float)(ac[h][1] / cnt), (float)(ac[h][2] / cnt)};
             }
         }
-        VX_CLK(1, done, 8);
         vx_barrier();  // (s_bucket is read by all before the next bucket's end rewrites it -- an empty bucket has no other barrier)
     }
 }

@@ -495,7 +495,8 @@ def test_voxel_downsample_matches_oracle(eng, n, voxel):
 def test_voxel_downsample_edge_shapes(eng):
     """The run-wise mean kernel's corners: one point; a voxel that holds 50k copies of one point next to sparse ones (a
     run of hundreds of 64-element chunks); colours without normals; every point in ONE voxel; a cloud smaller than a
-    wave -- each against the oracle (same voxels, same lexicographic order)."""
+    wave; a grid whose key needs more than 64 bits (three stable sorts, one per axis) -- each against the oracle (same
+    voxels, same lexicographic order)."""
     rng = np.random.default_rng(77)
     one = np.array([[0.3, -0.2, 0.9]], np.float32)
     p, _, _ = eng.voxel_downsample(one, 0.05)
@@ -517,6 +518,14 @@ def test_voxel_downsample_edge_shapes(eng):
         assert len(p) == len(rp) and (voxel < 1.0 or len(p) == 1)
         np.testing.assert_allclose(p, rp, atol=1e-6)
         np.testing.assert_allclose(nn, rn, atol=2e-5)
+    wide = (rng.random((4000, 3)) * 3000.0).astype(np.float32)    # 3 x 22 key bits at voxel 0.001
+    wn = rng.standard_normal((4000, 3)).astype(np.float32)
+    p, nn, c = eng.voxel_downsample(cuda(wide), 0.001, cuda(wn), cuda(col[:4000]))
+    rp, rn, rc = orc.voxel_downsample(wide, 0.001, wn, col[:4000])
+    assert len(p) == len(rp)
+    np.testing.assert_allclose(p.cpu().numpy(), rp, rtol=1e-6, atol=1e-6)
+    np.testing.assert_allclose(nn.cpu().numpy(), rn, atol=2e-5)
+    np.testing.assert_allclose(c.cpu().numpy(), rc, atol=2e-6)
 
 
 def test_voxel_downsample_both_forms_agree_to_the_last_bit_or_two(eng):

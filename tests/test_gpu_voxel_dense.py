@@ -165,7 +165,8 @@ def test_points_exactly_on_cell_faces_and_non_finite_coordinates(eng):
     """Keys: the reciprocal estimate with the division as the fallback near an integer (voxel_dense.h "Keys") -- points ON
     the faces of the cells (multiples of the voxel size from the grid's origin, the quotient an exact integer or one ulp
     off it) must land where the division puts them; and a NaN coordinate must neither crash the path nor move any
-    other voxel (its own cell index is whatever the conversion of NaN gives: not compared)."""
+    other voxel: its cell is 0 on that axis (geometry_kernels.h voxel_cell) on both paths, so the cloud downsamples as
+    the oracle's cloud with the NaN replaced by that axis' minimum (cell 0, the bounds unchanged) does."""
     rng = np.random.default_rng(3)
     n, voxel = 600_000, np.float32(0.0125)
     pts = rng.random((n, 3), dtype=np.float32)
@@ -183,7 +184,12 @@ def test_points_exactly_on_cell_faces_and_non_finite_coordinates(eng):
     bad[12345, 1] = np.nan
     pn, _, _ = dense(eng, cuda(bad), float(voxel))
     assert took_dense_path(eng)
-    assert abs(len(pn) - len(rp)) <= 1
+    gn, _, _ = general(eng, cuda(bad), float(voxel))
+    assert not took_dense_path(eng)
+    np.testing.assert_array_equal(pn.cpu().numpy(), gn.cpu().numpy())    # (NaN equals NaN here)
+    at_min = bad.copy()
+    at_min[12345, 1] = np.delete(bad[:, 1], 12345).min()
+    assert len(pn) == len(orc.voxel_downsample(at_min, float(voxel))[0])
 
 
 @pytest.mark.parametrize("n,voxel,off", [(600_000, 0.004, 0.0), (500_000, 0.0012, -3.0), (250_000, 0.002, 40.0), (1_500_000, 0.0031, 0.0)])
