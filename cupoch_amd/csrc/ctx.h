@@ -54,7 +54,7 @@ struct mi_icp_ctx {
     mi::eng::DevBuf tblk, tnrm, trec, tcov, tgrad, nodes, inv_t, tidx, thalo, tlinks_tmp;  // (leaf regions: the leaf lines' fourth rows, lreg_of)
     mi::eng::DevBuf cell_planes, cell_samples, cell_cstart, cell_gstart, cell_boxes, cell_hist;  // (kd_planes.h: the sample's boxes and histograms)
     mi::eng::DevBuf gplanes;   // every group's own 511 split planes (kd_build.h): with cell_planes / cell_gstart the binary descent of locate_by_planes
-    int cell_levels = -1;      // levels of cell planes of the present target; < 0: no kd cells (Morton-run fallback tree), nothing to descend
+    int cell_levels = -1;      // levels of cell planes of the present target; < 0: no target built yet
     uint32_t* cell_total_host = nullptr;  // pinned
     bool inv_t_valid = false;
     bool links_ready = false, links_allowed = false;  // leaf_halo.h
@@ -320,8 +320,8 @@ inline int check_ctx(mi_icp_ctx* c) {
 // ---- mi_build.hip
 int compute_bounds(mi_icp_ctx* c, const float* pts, int64_t n, float** bounds_out);  // min[3], max[3], extent into c->bounds
 int sort_buffers(mi_icp_ctx* c, int64_t n, SortBuffers* sb);
-int morton_order(mi_icp_ctx* c, const float* pts, int64_t n, const uint32_t** order, bool kd_refine,
-                 const float* grid_bounds = nullptr, int grid_bits = 0, float** own_bounds = nullptr);
+int morton_order(mi_icp_ctx* c, const float* pts, int64_t n, const uint32_t** order, const float* grid_bounds = nullptr,
+                 int grid_bits = 0, float** own_bounds = nullptr);
 int ensure_links(mi_icp_ctx* c);          // the halos complete before the next kernel on the context's stream
 int start_links_async(mi_icp_ctx* c);     // ... started on the private stream
 bool halo_poll(mi_icp_ctx* c);            // are they there?  never waits

@@ -2,10 +2,10 @@
 // its finished piece of the target tree: the points are median-split 9 times in LDS
 // (kd_sort_levels) and, still from LDS, written out as 512 leaf lines, the sorted
 // normals / covariances, and the 512 + 64 + 8 + 1 boxes of the group's three record
-// levels and of the group itself.  This replaces, for the target, the chain
-// cells_scatter -> kd_refine_groups -> build_leaves -> 3 x build_level and their
-// intermediate order[] arrays; build_leaves' per-leaf gathers of 8 scattered points were
-// the slowest single kernel of the build.
+// levels and of the group itself.  It replaces, for the target, a chain of kernels (scatter
+// by cell -> median splits of every group -> leaf gathers -> 3 levels of records) and their
+// intermediate order[] arrays; the per-leaf gathers of 8 scattered points were the slowest
+// single kernel of that build.
 #pragma once
 #include "kd_cells.h"
 #include "lbvh.h"
@@ -91,11 +91,7 @@ static __global__ __launch_bounds__(kKdThreads) __attribute__((amdgpu_waves_per_
 #pragma unroll
             for (int t = 0; t < kPer; ++t) {
                 const int i = min(tid + t * kKdThreads, count - 1);
-#ifdef MI_AB_COHERENT
-                o[t] = (int64_t)src0 + i;
-#else
                 o[t] = a.vals[src0 + i];
-#endif
             }
 #pragma unroll
             for (int t = 0; t < kPer; ++t) {
@@ -115,9 +111,7 @@ static __global__ __launch_bounds__(kKdThreads) __attribute__((amdgpu_waves_per_
         }
     }
     __syncthreads();
-#ifndef MI_AB_NO_SORT
     kd_sort_levels<true, true>(s, 9, a.gplanes + (size_t)g * 512u, 1u);
-#endif
 
     // ---- leaf lines + sorted attributes: position p of the group = slot g*4096 + p
     const int64_t slot0 = (int64_t)g * kKdGroup;
@@ -135,11 +129,7 @@ static __global__ __launch_bounds__(kKdThreads) __attribute__((amdgpu_waves_per_
         if (count > 0) {  // (uniform)
 #pragma unroll
             for (int t = 0; t < kPer; ++t) {
-#ifdef MI_AB_COHERENT
-                o[t] = (int64_t)src0 + min(li[t], count - 1);
-#else
                 o[t] = (int64_t)a.vals[src0 + min(li[t], count - 1)];
-#endif
             }
             if (a.tnrm) {
 #pragma unroll
@@ -155,9 +145,6 @@ static __global__ __launch_bounds__(kKdThreads) __attribute__((amdgpu_waves_per_
             const int p = tid + t * kKdThreads;
             const bool real = li[t] < count;
             if (!real) o[t] = -1;
-#ifdef MI_AB_NO_WRITE
-            if (a.link_delta != 12345.0f) continue;
-#endif
             float* line = a.tblk + (slot0 + p) / kLeaf * kLeafFloats + (p & 7);
             line[0] = s.cx[li[t]];
             line[8] = s.cy[li[t]];
@@ -191,7 +178,7 @@ static __global__ __launch_bounds__(kKdThreads) __attribute__((amdgpu_waves_per_
             if (li < count) {
                 const float p[3] = {s.cx[li], s.cy[li], s.cz[li]};
 #pragma unroll
-                for (int d = 0; d < 3; ++d) {  // as build_leaves: every coordinate of a real point counts
+                for (int d = 0; d < 3; ++d) {  // every coordinate of a real point counts
                     mn[d] = fminf(mn[d], p[d]);
                     mx[d] = fmaxf(mx[d], p[d]);
                 }

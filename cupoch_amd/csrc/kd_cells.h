@@ -18,7 +18,7 @@
 //   3. every point descends the d planes -> cell id; one short radix sort by cell id
 //      (ceil(d/8) passes instead of the 5 of a 39-bit Morton key);
 //   4. cell c owns max(1, ceil(count_c/4096)) groups of 4096 SLOTS, points left-packed,
-//      the rest padding (kNoPoint); kd_refine_groups + build_leaves take it from there.
+//      the rest padding; kd_build_groups (kd_build.h) takes it from there.
 //
 // Cells are defined by planes, so the boxes of different cells -- and of the 8-ary
 // nodes above them, which are kd subtrees when no cell overflows -- are disjoint.
@@ -39,11 +39,6 @@ constexpr int kCellMaxLevels = 19;
 
 // The layout with the fewest cells whose mean fill stays within kCellTargetFill: 2^d cells, or 3 * 2^k (kd_descend.h
 // TRI).  Returns the plane tree's depth, + kCellTriFlag for a TRI layout.
-static inline int cell_layout_pow2(int64_t n, int fill) {  // 2^d cells only (A/B: MI_ICP_CELL_LAYOUT)
-    int d = 0;
-    while (d < kCellMaxLevels && ((int64_t)fill << d) < n) ++d;
-    return d;
-}
 static inline int cell_layout_for(int64_t n) {
     int d = 0;
     while (d < kCellMaxLevels && ((int64_t)kCellTargetFill << d) < n) ++d;
@@ -140,11 +135,6 @@ static __global__ __launch_bounds__(256) void cells_scatter(const uint64_t* __re
     const uint32_t c = (uint32_t)keys[p];
     const int64_t slot = (int64_t)gstart[c] * kKdGroup + (p - (int64_t)cstart[c]);
     order_padded[slot] = vals[p];
-}
-
-static __global__ __launch_bounds__(256) void fill_u32(uint32_t* __restrict__ a, int64_t n, uint32_t v) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) a[i] = v;
 }
 
 }  // namespace mi

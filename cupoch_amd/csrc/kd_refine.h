@@ -10,15 +10,14 @@
 //
 // Building a global kd-tree costs a segmented sort per level (what the reference's
 // FLANN builder does).  Here a coarse partition does the global work -- kd cells from
-// sampled planes for the target (kd_cells.h), the Morton order for the source -- and each
-// group of 4096 positions is then split by ONE workgroup in LDS (kd_sort_levels): 9 rounds
+// sampled planes (kd_cells.h) -- and each group of 4096 positions is then split by ONE
+// workgroup in LDS (kd_sort_levels): 9 rounds
 // of {per-segment bbox -> longest axis -> median split of the segment along it} (a radix-select
 // partition while a segment spans several waves, a register bitonic sort inside a wave), i.e.
 // exact median splits down to the 8-point leaves.  After it a point lies in 1.27 leaf
 // boxes (1.64 / 2.2 at the 64 / 512 levels, for Morton groups).
-// Users: kd_build_groups (kd_build.h: the target's groups, written out as finished tree
-// pieces), cells_planes (kd_cells.h: split planes from samples), kd_refine_groups (below:
-// order only -- the Morton-run fallback tree).
+// User: kd_build_groups (kd_build.h: the target's groups, written out as finished tree
+// pieces).
 // Cost: 4 partition rounds + 110 compare-exchange stages per group, 1.19 ms for the 2442 groups of a
 // 10M-point target with normals (of which 0.57 ms are the gathers of the points / normals and the
 // stores; the all-sort first version: 354 stages, 1.29 ms).
@@ -291,9 +290,6 @@ __device__ __forceinline__ uint32_t kd_make_key(float x, float lo, float sc, uin
 // located next door to their partner's leaf.)  No upper half (padding only): +inf, nothing goes right.  Halves that
 // overlap by a sliver (the quantised split, below) or are a rounding apart: the upper half's minimum, as before.
 __device__ __forceinline__ float kd_plane_between(float lower_max, float upper_min) {
-#ifdef MI_AB_PLANES_THROUGH
-    return upper_min;
-#endif
     const float mid = 0.5f * (lower_max + upper_min);  // (-inf + inf: NaN -> the upper minimum, +inf)
     return (mid > lower_max) ? mid : upper_min;
 }
@@ -538,39 +534,6 @@ __device__ __forceinline__ void kd_sort_levels(KdShared& s, int levels, float2* 
     }
     reinterpret_cast<uint4*>(s.key)[tid] = make_uint4(v[0], v[1], v[2], v[3]);
     __syncthreads();
-}
-
-constexpr uint32_t kNoPoint = 0xffffffffu;  // order[] entry of a padding slot
-
-// order_in / order_out: sorted position -> original index (distinct buffers); n = number
-// of positions (a multiple of 4096 when the layout is padded); kNoPoint entries are
-// padding and end up behind the group's points.
-static __global__ __launch_bounds__(kKdThreads) void kd_refine_groups(const float* __restrict__ pts,
-                                                               const uint32_t* __restrict__ order_in,
-                                                               uint32_t* __restrict__ order_out, int64_t n) {
-    __shared__ KdShared s;
-    const int tid = (int)threadIdx.x;
-    const int64_t base = (int64_t)blockIdx.x * kKdGroup;
-    const int count = (int)min((int64_t)kKdGroup, n - base);
-
-    for (int i = tid; i < kKdGroup; i += kKdThreads) {
-        float x = INFINITY, y = INFINITY, z = INFINITY;  // padding sorts to the end on every axis
-        if (i < count) {
-            const uint32_t o = order_in[base + i];
-            if (o != kNoPoint) {
-                x = pts[(int64_t)o * 3];
-                y = pts[(int64_t)o * 3 + 1];
-                z = pts[(int64_t)o * 3 + 2];
-            }
-        }
-        s.cx[i] = x;
-        s.cy[i] = y;
-        s.cz[i] = z;
-        s.key[i] = (uint32_t)i;
-    }
-    __syncthreads();
-    kd_sort_levels<false>(s, 9, nullptr, 0u);
-    for (int i = tid; i < count; i += kKdThreads) order_out[base + i] = order_in[base + (s.key[i] & 4095u)];
 }
 
 }  // namespace mi

@@ -6,13 +6,12 @@
 // kdtree_cuda_builder.h:401-700), i.e. three thrust sorts plus ~10 thrust passes per
 // tree level with a host round trip per level.  Topology is implicit: a complete 8-ary
 // tree over leaves of 8 points (one 128-B line each), one 256-B record of 8 child boxes
-// per node (traverse.h), refitted bottom-up.  The default build is
+// per node (traverse.h), refitted bottom-up.  The build is
 //   kd cells (kd_cells.h) -> one workgroup per 4096-slot group writes its leaves and
 //   three record levels (kd_build.h) -> build_level once per level above the groups;
 // this file holds build_level, the record store helpers, and the Morton path
-//   bounds -> 3*B-bit Morton keys -> LSD radix sort -> build_leaves -> build_level ...
-// which stages the source (keys + gather_source) and remains as the A/B fallback for the
-// target (MI_ICP_NO_CELLS).
+//   bounds -> 3*B-bit Morton keys -> LSD radix sort -> gather_source
+// which stages the source.
 #pragma once
 #include "device_utils.h"
 #include "kd_descend.h"
@@ -166,62 +165,6 @@ __device__ __forceinline__ void store_own(float* __restrict__ records, uint32_t 
     pr[kOwnFlag - kOwnBox] = __uint_as_float(flag);
 }
 
-// one thread per leaf slot L in [0, nslots), nslots = 8 * ceil(nleaf / 8): gathers the
-// leaf's <=8 points into the 128-B leaf line, sorted normals / covariances next
-// to them, and writes the leaf box into its parent's record.  Slots past nleaf
-// get the inverted box.  n = number of sorted positions; order[] entries equal to
-// kNoPoint are padding (kd_cells.h): +inf coordinates, original index -1.
-static __global__ __launch_bounds__(256) void build_leaves(
-        const uint32_t* __restrict__ order, const float* __restrict__ pts,
-        const float* __restrict__ nrm, const float* __restrict__ cov, int64_t n, int nleaf, int nslots,
-        uint32_t leaf_first, float* __restrict__ tblk, float4* __restrict__ tnrm,
-        float* __restrict__ tcov, float* __restrict__ records, float* __restrict__ trec, int32_t* __restrict__ tidx) {
-    const int L = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (L >= nslots) return;
-    float mn[3] = {INFINITY, INFINITY, INFINITY};
-    float mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    if (L < nleaf) {
-        float* line = tblk + (int64_t)L * kLeafFloats;
-#pragma unroll
-        for (int k = 0; k < kLeaf; ++k) {
-            const int64_t s = (int64_t)L * kLeaf + k;
-            float p[3] = {INFINITY, INFINITY, INFINITY};
-            int o = -1;
-            const uint32_t ou = (s < n) ? order[s] : 0xffffffffu;
-            if (ou != 0xffffffffu) {
-                o = (int)ou;
-#pragma unroll
-                for (int d = 0; d < 3; ++d) {
-                    p[d] = pts[(int64_t)o * 3 + d];
-                    mn[d] = fminf(mn[d], p[d]);
-                    mx[d] = fmaxf(mx[d], p[d]);
-                }
-                if (nrm) {
-                    tnrm[s] = make_float4(nrm[(int64_t)o * 3], nrm[(int64_t)o * 3 + 1],
-                                          nrm[(int64_t)o * 3 + 2], 0.0f);
-                    if (trec) {
-#pragma unroll
-                        for (int d = 0; d < 3; ++d) {
-                            trec[s * 6 + d] = p[d];
-                            trec[s * 6 + 3 + d] = nrm[(int64_t)o * 3 + d];
-                        }
-                    }
-                }
-                if (cov) {
-#pragma unroll
-                    for (int e = 0; e < 9; ++e) tcov[s * 9 + e] = cov[(int64_t)o * 9 + e];
-                }
-            }
-            line[k] = p[0];
-            line[8 + k] = p[1];
-            line[16 + k] = p[2];
-            tidx[s] = o;
-        }
-    }
-    // the leaf is child (L & 7) of last-level node leaf_first + (L >> 3)
-    store_box(records, (leaf_first + ((uint32_t)L >> 3)) * 8u + ((uint32_t)L & 7u), mn, mx);
-}
-
 // level-k nodes first + t, t in [0, count): box = union of the node's 8 child slots,
 // written into the parent's record; t >= used (padding up to a multiple of 8)
 // writes the inverted box.
@@ -281,15 +224,6 @@ static __global__ __launch_bounds__(256) void build_level(float* __restrict__ re
         }
     }
     store_box(records, id, mn, mx);
-}
-
-// leaf regions of a tree that has none (Morton-run fallback): nothing is inside, no halo
-static __global__ __launch_bounds__(256) void fill_invalid_leaf_regions(float* __restrict__ lreg, int nleaf) {
-    const int L = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (L >= nleaf) return;
-    float4* out = reinterpret_cast<float4*>(lreg + (size_t)L * kLeafRegStride);
-    out[0] = make_float4(INFINITY, INFINITY, INFINITY, 0.0f);
-    out[1] = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
 }
 
 // ---- source: Morton-ordered SoA copy ---------------------------------------

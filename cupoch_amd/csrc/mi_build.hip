@@ -64,9 +64,8 @@ int sort_buffers(mi_icp_ctx* c, int64_t n, SortBuffers* sb) {
 
 // Morton order of an AoS cloud: returns the device array order[sorted] = original.
 // grid_bounds/grid_bits: quantise on another cloud's grid instead of the cloud's own.
-// kd_refine: also split every group of 4096 Morton-consecutive points into kd cells (kd_refine.h)
-int morton_order(mi_icp_ctx* c, const float* pts, int64_t n, const uint32_t** order, bool kd_refine,
-                 const float* grid_bounds, int grid_bits, float** own_bounds) {
+int morton_order(mi_icp_ctx* c, const float* pts, int64_t n, const uint32_t** order, const float* grid_bounds,
+                 int grid_bits, float** own_bounds) {
     float* bnd = nullptr;
     if (!grid_bounds || own_bounds) TRY(compute_bounds(c, pts, n, &bnd));
     if (own_bounds) *own_bounds = bnd;
@@ -85,15 +84,7 @@ int morton_order(mi_icp_ctx* c, const float* pts, int64_t n, const uint32_t** or
         cur = radix_sort_pairs(c->stream, sb, n, 3 * bits);
     }
     KCHK(c);
-    if (!kd_refine) {
-        *order = sb.vals[cur];
-        return MI_ICP_OK;
-    }
-    // Morton runs -> kd cells inside every group of 4096 points (kd_refine.h)
-    const int ngroups = (int)((n + kKdGroup - 1) / kKdGroup);
-    kd_refine_groups<<<ngroups, kKdThreads, 0, c->stream>>>(pts, sb.vals[cur], sb.vals[cur ^ 1], n);
-    KCHK(c);
-    *order = sb.vals[cur ^ 1];
+    *order = sb.vals[cur];
     return MI_ICP_OK;
 }
 
@@ -111,10 +102,7 @@ struct CellLayout {
 };
 
 int kd_cell_layout(mi_icp_ctx* c, const float* pts, int64_t n, CellLayout* out) {
-    // (MI_ICP_CELL_LAYOUT, A/B switch: "pow2" -- 2^d cells only, still filled to 80 %; "r4" -- 2^d cells at <= 2/3 fill,
-    // rounds 2-4's layout, on this round's planes)
-    static const int forced = [] { const char* e = std::getenv("MI_ICP_CELL_LAYOUT"); return !e ? 0 : (std::strcmp(e, "pow2") == 0 ? 1 : (std::strcmp(e, "r4") == 0 ? 2 : 0)); }();
-    const int lv = forced == 0 ? cell_layout_for(n) : cell_layout_pow2(n, forced == 2 ? 2731 : kCellTargetFill);
+    const int lv = cell_layout_for(n);
     const int d = cell_depth(lv);
     const int ncells = (int)cell_count(lv);
     SortBuffers sb;
@@ -205,11 +193,10 @@ int kd_cell_layout(mi_icp_ctx* c, const float* pts, int64_t n, CellLayout* out) 
 // registered before (mi_icp_set_target), otherwise by the first registration loop / seeded search
 // (one-shot searches, k-NN and normal estimation on a fresh context never pay for it).
 int build_links(mi_icp_ctx* c, hipStream_t st) {
-    static const bool no_links = std::getenv("MI_ICP_NO_LINKS") != nullptr;  // A/B switch
-    if (!c->links_allowed || no_links) return MI_ICP_OK;  // (every leaf's largest reach is 0 as built: no query asks for a line)
+    if (!c->links_allowed) return MI_ICP_OK;  // (every leaf's largest reach is 0 as built: no query asks for a line)
     float* halo;
     const size_t ntiles = ((size_t)c->nleaf + 63) / 64;
-    TRY(ensure(c, c->thalo, ntiles * 64 * kHaloStored * kHaloLineFloats, &halo));
+    TRY(ensure(c, c->thalo, ntiles * 64 * kHaloLines * kHaloLineFloats, &halo));
     uint2* cand;  // scratch: up to 64 candidate leaves per leaf
     TRY(ensure(c, c->tlinks_tmp, ntiles * 64 * kLinkCand, &cand));
     const uint32_t lblocks = (uint32_t)ntiles;
@@ -251,8 +238,7 @@ bool halo_poll(mi_icp_ctx* c) {
         c->links_ready = true;
     }
     (void)hipGetLastError();  // (hipErrorNotReady is not an error)
-    static const bool no_links = std::getenv("MI_ICP_NO_LINKS") != nullptr;
-    return c->links_ready && c->links_allowed && !no_links && c->thalo.p != nullptr;
+    return c->links_ready && c->links_allowed && c->thalo.p != nullptr;
 }
 
 // Start the build on the private stream (behind everything enqueued on the context's stream so far); the
@@ -373,16 +359,9 @@ int mi_icp_set_target(mi_icp_ctx* c, const float* xyz, const float* normals, con
     TRY(to_device(c, normals, (size_t)n * 3, mem_kind, c->stage[1], &d_nrm));
     TRY(to_device(c, covs, (size_t)n * 9, mem_kind, c->stage[2], &d_cov));
 
-    static const bool no_cells = std::getenv("MI_ICP_NO_CELLS") != nullptr;  // A/B switch: Morton runs on top
-    const uint32_t* order = nullptr;
-    CellLayout lay = {};
-    int64_t nts = n;
-    if (no_cells) {
-        TRY(morton_order(c, d_pts, n, &order, true));
-    } else {
-        TRY(kd_cell_layout(c, d_pts, n, &lay));
-        nts = lay.ngroups * kKdGroup;
-    }
+    CellLayout lay;
+    TRY(kd_cell_layout(c, d_pts, n, &lay));
+    const int64_t nts = lay.ngroups * kKdGroup;
 
     const int nleaf = (int)((nts + kLeaf - 1) / kLeaf);
     int levels = 1;  // 8-ary levels of records above the leaves
@@ -410,48 +389,35 @@ int mi_icp_set_target(mi_icp_ctx* c, const float* xyz, const float* normals, con
     if (d_nrm) TRY(ensure(c, c->trec, (size_t)nts * 6, &trec));
     c->t_has_rec = trec != nullptr;
     if (d_cov) TRY(ensure(c, c->tcov, (size_t)nts * 9, &tcov));
-    uint32_t first, used;  // the level whose nodes' boxes still have to be formed from their records
     // nodes above the groups are kd subtrees -- disjoint boxes -- when every cell has exactly one group
-    const uint32_t upper_flag = (!no_cells && lay.ngroups == (int64_t)lay.ncells) ? 1u : 0u;
-    if (no_cells) {
-        // own boxes / flags of the leaf-level records stay zero: no early stop on a Morton-run tree
-        HIPCHK(c, hipMemsetAsync(nodes, 0, (size_t)nrecords * kRecordFloats * sizeof(float), c->stream));
-        fill_invalid_leaf_regions<<<blocks_for(nleaf), 256, 0, c->stream>>>(lreg, nleaf);  // no leaf regions either
-        KCHK(c);
-        const int nslots = (int)used_last * 8;
-        build_leaves<<<blocks_for(nslots), 256, 0, c->stream>>>(order, d_pts, d_nrm, d_cov, nts, nleaf, nslots,
-                                                                leaf_first, tblk, tnrm, tcov, nodes, trec, tidx);
-        KCHK(c);
-        first = leaf_first;
-        used = used_last;
-    } else {
-        GroupBuildArgs ga;
-        ga.pts = d_pts;
-        ga.nrm = d_nrm;
-        ga.cov = d_cov;
-        ga.vals = lay.vals;
-        ga.cstart = lay.cstart;
-        ga.gstart = lay.gstart;
-        ga.ncells = lay.ncells;
-        ga.planes = lay.planes;
-        ga.cell_levels = lay.levels;
-        ga.ngroups = (uint32_t)lay.ngroups;
-        ga.leaf_first = leaf_first;
-        ga.tblk = tblk;
-        ga.tnrm = tnrm;
-        ga.trec = trec;
-        ga.tcov = tcov;
-        ga.records = nodes;
-        ga.lreg = lreg;
-        ga.tidx = tidx;
-        TRY(ensure(c, c->gplanes, (size_t)lay.ngroups * 512, &ga.gplanes));
-        ga.link_delta = 0.25f;     // the halos' bound: a quarter of the leaf-level node's size (kd_build.h)
-        ga.region_margin = 0.5f;   // a leaf's region stays within half that bound of its own box
-        kd_build_groups<<<(unsigned)lay.ngroups, kKdThreads, 0, c->stream>>>(ga);
-        KCHK(c);
-        first = leaf_first >> 9;  // the groups' own boxes sit in the records of this level
-        used = ((uint32_t)lay.ngroups + 7u) / 8u;
-    }
+    const uint32_t upper_flag = (lay.ngroups == (int64_t)lay.ncells) ? 1u : 0u;
+    GroupBuildArgs ga;
+    ga.pts = d_pts;
+    ga.nrm = d_nrm;
+    ga.cov = d_cov;
+    ga.vals = lay.vals;
+    ga.cstart = lay.cstart;
+    ga.gstart = lay.gstart;
+    ga.ncells = lay.ncells;
+    ga.planes = lay.planes;
+    ga.cell_levels = lay.levels;
+    ga.ngroups = (uint32_t)lay.ngroups;
+    ga.leaf_first = leaf_first;
+    ga.tblk = tblk;
+    ga.tnrm = tnrm;
+    ga.trec = trec;
+    ga.tcov = tcov;
+    ga.records = nodes;
+    ga.lreg = lreg;
+    ga.tidx = tidx;
+    TRY(ensure(c, c->gplanes, (size_t)lay.ngroups * 512, &ga.gplanes));
+    ga.link_delta = 0.25f;     // the halos' bound: a quarter of the leaf-level node's size (kd_build.h)
+    ga.region_margin = 0.5f;   // a leaf's region stays within half that bound of its own box
+    kd_build_groups<<<(unsigned)lay.ngroups, kKdThreads, 0, c->stream>>>(ga);
+    KCHK(c);
+    // `first`: the level whose nodes' boxes still have to be formed from their records
+    uint32_t first = leaf_first >> 9;  // the groups' own boxes sit in the records of this level
+    uint32_t used = ((uint32_t)lay.ngroups + 7u) / 8u;
     int above_groups = 1;  // 8-ary levels between `first` and the groups' level
     for (; first > 1u; first /= 8u, ++above_groups) {
         const uint32_t count = ((used + 7u) / 8u) * 8u;
@@ -473,13 +439,13 @@ int mi_icp_set_target(mi_icp_ctx* c, const float* xyz, const float* normals, con
     }
     c->links_ready = false;  // (the leaves' halos: started below, or by the registration loop / the first seeded search)
     c->halo_iters = c->halo_asked = c->halo_lanes = 0;
-    c->links_allowed = !no_cells && (uint32_t)nleaf <= kLinkIdMask;
+    c->links_allowed = (uint32_t)nleaf <= kLinkIdMask;
     c->nt = n;
     c->nts = nts;
     c->nleaf = nleaf;
     c->leaf_first = leaf_first;
     c->nrecords = nrecords;
-    c->cell_levels = no_cells ? -1 : lay.levels;
+    c->cell_levels = lay.levels;
     // A context whose loops have ASKED for halos will run another such loop.  For a small target (frame-to-frame
     // callers: KinFu, odometry) the halos are then started right away, on the private stream, next to the staging of the
     // source: the loop's first seeded iterations find them ready.  For a large one the build would fight the staging
@@ -528,7 +494,7 @@ int mi_icp_set_source(mi_icp_ctx* c, const float* xyz, const float* normals, con
     // 10M -- than it saves in that one pass, 0.15 ms.)
     const uint32_t* order;
     float* own_bounds = nullptr;
-    TRY(morton_order(c, d_pts, n, &order, false, nullptr, 0, &own_bounds));
+    TRY(morton_order(c, d_pts, n, &order, nullptr, 0, &own_bounds));
     {   // (c->bounds is every build's scratch: the source's box is kept for the loop, loop.h "re-location")
         float* sb;
         TRY(ensure(c, c->src_bounds, 8, &sb));
@@ -567,7 +533,7 @@ int mi_icp_spatial_order(mi_icp_ctx* c, const float* xyz, int64_t n, uint32_t* o
     const float* d_pts;
     TRY(to_device(c, xyz, (size_t)n * 3, mem_kind, c->stage[0], &d_pts));
     const uint32_t* order;
-    TRY(morton_order(c, d_pts, n, &order, false));
+    TRY(morton_order(c, d_pts, n, &order));
     TRY(from_device(c, order, order_out, (size_t)n, mem_kind));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MI_ICP_OK;

@@ -31,10 +31,9 @@ static int64_t coarse_first_min() {
 }
 
 // The target has kd cells and its groups' planes: a query's own leaf is a binary descent away (nn_search.h
-// locate_by_planes).  MI_ICP_NO_LOCATE_PLANES: A/B switch -- the greedy record descent (locate_leaves), no re-location.
+// locate_by_planes).
 bool planes_available(const mi_icp_ctx* c) {
-    static const bool off = std::getenv("MI_ICP_NO_LOCATE_PLANES") != nullptr;
-    return !off && c->cell_levels >= 0 && c->gplanes.p != nullptr && c->cell_planes.p != nullptr && c->cell_gstart.p != nullptr &&
+    return c->cell_levels >= 0 && c->gplanes.p != nullptr && c->cell_planes.p != nullptr && c->cell_gstart.p != nullptr &&
            c->leaf_first > 1u && c->nleaf > 0;
 }
 
@@ -77,7 +76,6 @@ int launch_nn(mi_icp_ctx* c, const Mat4& T, float r2, bool seed, unsigned long l
     const float* links = have_halo ? (const float*)c->thalo.p : nullptr;
     uint32_t* want = (loop && !have_halo && !c->links_inflight && c->links_allowed) ? (uint32_t*)c->halo_want.p : nullptr;
     bool self_seeded = false;
-    static const bool no_coarse = std::getenv("MI_ICP_NO_COARSE_FIRST") != nullptr;  // A/B switch
     auto launch = [&](bool seeded, const float* sx, const float* sy, const float* sz, int64_t ns, int32_t* out_idx,
                       float* out_d2) {
         const uint32_t npackets = (uint32_t)((ns + 63) / 64);
@@ -96,20 +94,12 @@ int launch_nn(mi_icp_ctx* c, const Mat4& T, float r2, bool seed, unsigned long l
         }
 #undef MI_NN_ARGS
     };
-    // No previous matches, but the target's halos are there: every query takes the leaf a greedy descent lands in
-    // as its seed (nn_search.h: locate_leaves) and the seeded search does the rest.  (Without halos every lane
-    // whose seed leaf's region does not finish it walks up from there -- under the displacement a registration
-    // starts with that is most packets, and costs more than the walk from the root: 10M points 3.9 against 1.2 ms.)
-    if (!use_seed && !stats && !no_coarse && c->leaf_first > 1u && c->ns >= coarse_first_min() && have_halo) {
-        if (planes_available(c)) {
-            TRY(launch_locate_by_planes(c, X, loop, 0));
-        } else {
-            locate_leaves<<<blocks_for(c->ns), 256, 0, c->stream>>>((const float*)c->sx.p, (const float*)c->sy.p,
-                                                                    (const float*)c->sz.p, (int)c->ns,
-                                                                    (const float*)c->nodes.p, c->leaf_first,
-                                                                    (uint32_t)c->nleaf, X, loop, idx);
-            KCHK(c);
-        }
+    // No previous matches, but the target's halos are there: every query takes the leaf it falls into as its seed
+    // (nn_search.h: locate_by_planes) and the seeded search does the rest.  (Without halos every lane whose seed
+    // leaf's region does not finish it walks up from there -- under the displacement a registration starts with that
+    // is most packets, and costs more than the walk from the root: 10M points 3.9 against 1.2 ms.)
+    if (!use_seed && !stats && c->ns >= coarse_first_min() && have_halo && planes_available(c)) {
+        TRY(launch_locate_by_planes(c, X, loop, 0));
         self_seeded = true;
     }
     c->last_search_kind = use_seed ? 1 : (self_seeded ? 2 : 0);
@@ -237,8 +227,7 @@ int launch_reduce(mi_icp_ctx* c, int est, int mode, const Mat4& T, DevLoop* loop
         est = kEstP2P;
         mode = 1;
     }
-    static const bool no_fast_reduce = std::getenv("MI_ICP_NO_FAST_REDUCE") != nullptr;  // A/B switch
-    if (est == kEstPt2Pl && mode == 0 && !a.pairs && a.trec && a.count > 0 && !no_fast_reduce) {
+    if (est == kEstPt2Pl && mode == 0 && !a.pairs && a.trec && a.count > 0) {
         // four elements in flight per thread; at most 512 blocks (2 per CU): measured best on the 10M bench
         // (256 / 512 / 1024 / 2048 blocks: 0.090 / 0.079 / 0.080 / 0.091 ms; 6 or 8 elements in flight on 512,
         // 768 or 1024 blocks: 0.078 - 0.084 ms -- the kernel sits at ~5.1 TB/s of the ~6.3 a pure stream reaches)
@@ -672,7 +661,7 @@ static int loop_pull(mi_icp_ctx* c) {  // device state -> pinned mirror, synchro
 // reduction, the step -- is ONE launch (fused_small.h).  Measured, the loop of a 30-iteration call, one launch /
 // two launches per iteration: 20k points 0.47 / 0.55 ms, 80k 0.61, 112k 0.70, 150k 0.78 / 0.81, 200k 0.89 / 0.84,
 // 307k 1.18 / 0.91 -- past ~170k points the per-packet totals (one set of 30 sums per 64 points instead of
-// one per 4096) cost more than the second launch; MI_ICP_FUSED_MAX moves the limit.
+// one per 4096) cost more than the second launch.
 constexpr int64_t kFusedMax = 170000;
 // (point-to-point: its rows are cheaper to form than to total -- on converged clean clouds the one launch wins by 10 % at
 // 50k points, 5 % at 114k and loses 6 % at 170k, 20 % at 250k against search + reduction + step:
@@ -680,10 +669,9 @@ constexpr int64_t kFusedMax = 170000;
 constexpr int64_t kFusedMaxP2P = 135000;
 static bool fused_iteration_applies(const mi_icp_ctx* c, bool seed) {
     static const bool off = std::getenv("MI_ICP_NO_FUSED_ITERATION") != nullptr;  // A/B switch
-    static const int64_t forced = [] { const char* e = std::getenv("MI_ICP_FUSED_MAX"); return e ? std::atoll(e) : (int64_t)-1; }();
     const bool pt2pl = c->loop_est == kEstPt2Pl && estimator_ready(c, kEstPt2Pl) && c->t_has_rec && c->trec.p != nullptr;
     const bool p2p = c->loop_est == kEstP2P;
-    const int64_t limit = forced >= 0 ? forced : (p2p ? kFusedMaxP2P : kFusedMax);
+    const int64_t limit = p2p ? kFusedMaxP2P : kFusedMax;
     return !off && seed && c->nn_valid && (pt2pl || p2p) && !c->comm && !c->mail_dev &&
            c->n_user_pairs < 0 && c->ns > 0 && c->ns <= limit && c->nt > 0;
 }
@@ -933,8 +921,7 @@ static int loop_begin(mi_icp_ctx* c, int est, float max_distance, const float* i
             c->halo_use = halo_poll(c);
         }
     }
-    static const bool no_resort = std::getenv("MI_ICP_NO_RESORT") != nullptr;  // A/B switch for tuning
-    const bool resort = !no_resort && c->ns >= 32768 && (max_iterations >= 4 || max_iterations == 0);
+    const bool resort = c->ns >= 32768 && (max_iterations >= 4 || max_iterations == 0);
     // (Round 5 tried the match-order sort AHEAD of the first search, on the leaves the queries fall into
     // (locate_by_planes): the first search gains nothing from packets that share their lines -- 0.85 ms against 0.79 --
     // and every later iteration of a clean registration loses ~20 %, because the order then follows where the queries

@@ -28,11 +28,7 @@
 
 namespace mi {
 
-#ifdef MI_AB_WANT_ONE
-constexpr uint32_t kWantSlots = 1u;
-#else
 constexpr uint32_t kWantSlots = 1024u;  // words of the halo_want counter (below; a power of two)
-#endif
 constexpr int kNNThreads = 64;   // one packet per workgroup: the dispatcher refills wave slots one at a time (3 % faster than 4)
 constexpr int kNNPacketsPerBlock = kNNThreads / 64;
 
@@ -147,7 +143,7 @@ __device__ __forceinline__ void drain_halo(PacketShared& sh, const float* halo_g
     const float oy = __int_as_float(__builtin_amdgcn_ds_bpermute(ql << 2, __float_as_int(qy)));
     const float oz = __int_as_float(__builtin_amdgcn_ds_bpermute(ql << 2, __float_as_int(qz)));
     if (have) {
-        const float* lf = halo_g + ((size_t)L * kHaloStored + f) * kHaloLineFloats;
+        const float* lf = halo_g + ((size_t)L * kHaloLines + f) * kHaloLineFloats;
         const float4* line = reinterpret_cast<const float4*>(lf);
         const float4 x0 = line[0], x1 = line[1], y0 = line[2], y1 = line[3], z0 = line[4], z1 = line[5];
         const uint32_t held_bits = (uint32_t)(sh.best[ql] >> 32);  // what the owner holds (or a batch-mate has found)
@@ -268,7 +264,7 @@ __device__ __forceinline__ bool nn_packet_body(
                 const float lx = g0.x - cube.lox, ly = g0.y - cube.loy, lz = g0.z - cube.loz;
                 const float over = fmaxf(fmaxf(fmaxf(ux, lx), fmaxf(uy, ly)), fmaxf(uz, lz)) * 1.000001f;
                 nlines = halo_lines_needed(g0.w, g1.w, over);
-                linked = halo_g != nullptr && nlines <= (uint32_t)kHaloStored;  // (no halos (yet), or beyond their reach: walk)
+                linked = halo_g != nullptr && nlines <= (uint32_t)kHaloLines;  // (no halos (yet), or beyond their reach: walk)
                 if (STATS) why = !(g0.x <= g1.x) ? 1u : (__float_as_uint(g1.w) == 0u ? 2u : (!linked ? 3u : 0u));
             }
         }
@@ -296,7 +292,7 @@ __device__ __forceinline__ bool nn_packet_body(
             // every lane that needs anything needs its leaf's first line only: each evaluates its own (no queue,
             // no exchange; the common case of small noise)
             if (STATS) ++batches, halo_items += (uint32_t)__popcll(__ballot(linked));
-            const float* lf = halo_g + (size_t)seed_leaf * (kHaloStored * kHaloLineFloats);
+            const float* lf = halo_g + (size_t)seed_leaf * (kHaloLines * kHaloLineFloats);
             const float4* line = reinterpret_cast<const float4*>(lf);
             const float4 x0 = line[0], x1 = line[1], y0 = line[2], y1 = line[3], z0 = line[4], z1 = line[5];
             if (linked) {
@@ -546,92 +542,11 @@ __global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(SEED
     if (STAMP && stamps && threadIdx.x == 0 && blockIdx.x + 256u >= gridDim.x) atomicMax(stamps + 1, stamp_now());
 }
 
-// ---------------------------------------------------------------------------
-// Result export in the reference's layout.
-// ---------------------------------------------------------------------------
-
-// dense per-source arrays in ORIGINAL source order with ORIGINAL target indices
-// (KDTreeFlann::SearchRadius outputs, knn/kdtree_flann.inl:96-122)
-// The first pass of a registration loop has no previous matches to start from.  It makes its own:
-// every query walks down the tree on its own, at each record into the child whose box is nearest
-// (inside: distance 0), and takes the leaf it arrives at as its seed.  No backtracking, so the leaf
-// is only near the true match -- the seeded search above turns it into the exact answer through
-// that leaf's region and halo.  Consecutive queries are spatial neighbours (the source is
-// staged in Morton order): the upper records are the same for a whole wave, the lower ones shared
-// by many lanes, so the 12 vector loads per level mostly hit the same few lines.
-// (While a wave's lanes still agree on the node -- the upper levels -- its record comes through the
-// scalar unit, one round trip for the wave; the 12 vector loads of a divergent level cost the texture
-// path 16 cycles each whatever the addresses: 0.48 ms for 10M queries when every level went that way.)
-__device__ __forceinline__ uint32_t nearest_child(const float (&w)[48], float qx, float qy, float qz) {
-    float best = INFINITY;
-    uint32_t c = 0u;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const float* b = w + p * kPairStride;  // {Amin.x,Bmin.x, Amin.y,Bmin.y, Amin.z,Bmin.z, Amax.x,Bmax.x, ...}
-        const float ax = fmaxf(fmaxf(b[0] - qx, qx - b[6]), 0.0f), bx = fmaxf(fmaxf(b[1] - qx, qx - b[7]), 0.0f);
-        const float ay = fmaxf(fmaxf(b[2] - qy, qy - b[8]), 0.0f), by = fmaxf(fmaxf(b[3] - qy, qy - b[9]), 0.0f);
-        const float az = fmaxf(fmaxf(b[4] - qz, qz - b[10]), 0.0f), bz = fmaxf(fmaxf(b[5] - qz, qz - b[11]), 0.0f);
-        const float da = ax * ax + ay * ay + az * az, db = bx * bx + by * by + bz * bz;  // empty child: +inf
-        if (da < best) { best = da; c = 2u * (uint32_t)p; }
-        if (db < best) { best = db; c = 2u * (uint32_t)p + 1u; }
-    }
-    return c;
-}
-
-static __global__ __launch_bounds__(256) void locate_leaves(const float* __restrict__ sx, const float* __restrict__ sy,
-                                                     const float* __restrict__ sz, int ns,
-                                                     const float* __restrict__ records_g, uint32_t leaf_first,
-                                                     uint32_t nleaf, Xform Tv, const DevLoop* __restrict__ loop,
-                                                     int32_t* __restrict__ nn_idx) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int ic = min(i, ns - 1);  // (lanes past the end walk along: the wave stays whole for the scalar path)
-    Xform T = Tv;
-    if (loop) {
-        if (loop->done) return;
-        T = loop->X;
-    }
-    float qx, qy, qz;
-    xform_point(T, sx[ic], sy[ic], sz[ic], qx, qy, qz);
-    typedef const __attribute__((address_space(4))) char* cchar_p;
-    const cchar_p sbase = (cchar_p)(uintptr_t)records_g;
-    uint32_t id = 1u, c = 0u;
-    bool uniform = true;
-    for (;;) {
-        float w[48];
-        const uint32_t uid = __builtin_amdgcn_readfirstlane(id);
-        uniform = uniform && __ballot(id != uid) == 0ull;
-        if (uniform) {
-            const cf16_p rec = (cf16_p)(sbase + ((size_t)record_index(uid) << 8));
-            const f16v r0 = rec[0], r1 = rec[1], r2 = rec[2];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                w[e] = r0[e];
-                w[16 + e] = r1[e];
-                w[32 + e] = r2[e];
-            }
-        } else {
-            const float4* rec = reinterpret_cast<const float4*>(records_g + (size_t)record_index(id) * kRecordFloats);
-#pragma unroll
-            for (int e = 0; e < 12; ++e) {
-                const float4 v = rec[e];
-                w[4 * e] = v.x;
-                w[4 * e + 1] = v.y;
-                w[4 * e + 2] = v.z;
-                w[4 * e + 3] = v.w;
-            }
-        }
-        c = nearest_child(w, qx, qy, qz);
-        if (id >= leaf_first) break;  // (all ids of a wave sit on the same level)
-        id = 8u * id + c;
-    }
-    const uint32_t leaf = min(8u * (id - leaf_first) + c, nleaf - 1u);
-    if (i < ns) nn_idx[i] = (int32_t)(leaf * (uint32_t)kLeaf);
-}
-
-// THE SAME BY BINARY PLANES (round 5): the leaf a query FALLS INTO -- cell planes (kd_cells.h), the cell's first group,
-// the group's own 511 planes (kd_build.h) -- 21 dependent 8-byte loads per query at 10M points instead of seven
-// 192-byte records with 48 compares each; consecutive queries are neighbours, so the upper levels are broadcasts and the
-// lower ones hit a 4-KB table per group.  Two users:
+// The leaf a query FALLS INTO, by binary planes -- cell planes (kd_cells.h), the cell's first group, the group's own 511
+// planes (kd_build.h): 21 dependent 8-byte loads per query at 10M points instead of a greedy walk down seven 192-byte
+// records with 48 compares each; consecutive queries are neighbours, so the upper levels are broadcasts and the lower
+// ones hit a 4-KB table per group.  The seed is only near the true match: the seeded search (above) turns it into the
+// exact answer through that leaf's region and halo.  Two users:
 //  * a first pass when the target's halos exist: locate, then the seeded search (launch_nn);
 //  * RE-LOCATION inside a loop (gated != 0: nothing happens unless the step just taken set loop->relocate, loop.h): a
 //    step that moved the points by more than a leaf's width leaves every seed a leaf or more off, and the seeded walk
@@ -658,6 +573,12 @@ static __global__ __launch_bounds__(256) void locate_by_planes(
     }
 }
 
+// ---------------------------------------------------------------------------
+// Result export in the reference's layout.
+// ---------------------------------------------------------------------------
+
+// dense per-source arrays in ORIGINAL source order with ORIGINAL target indices
+// (KDTreeFlann::SearchRadius outputs, knn/kdtree_flann.inl:96-122)
 static __global__ __launch_bounds__(256) void export_dense(const int32_t* __restrict__ nn_idx,
                                                     const float* __restrict__ nn_d2,
                                                     const int32_t* __restrict__ sperm,
@@ -697,9 +618,6 @@ static __global__ __launch_bounds__(256) void corr_compact(const int32_t* __rest
     }
 }
 
-// explicit CorrespondenceSet -> the engine's internal form: nn_idx[sorted
-// source position] = sorted target position.  inv_s / inv_t map original ->
-// sorted index.  Source points absent from the set get -1.
 static __global__ __launch_bounds__(256) void fill_i32(int32_t* __restrict__ a, int64_t n, int32_t v) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) a[i] = v;
@@ -718,17 +636,6 @@ static __global__ __launch_bounds__(256) void invert_perm_target(const int32_t* 
         const int32_t o = tidx[s];
         if (o >= 0) inv[o] = (int32_t)s;
     }
-}
-
-static __global__ __launch_bounds__(256) void import_pairs(const int32_t* __restrict__ pairs, int64_t c,
-                                                    const int32_t* __restrict__ inv_s,
-                                                    const int32_t* __restrict__ inv_t, int ns,
-                                                    int nt, int32_t* __restrict__ nn_idx) {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= c) return;
-    const int32_t i = pairs[2 * k], j = pairs[2 * k + 1];
-    if (i < 0 || i >= ns || j < 0 || j >= nt) return;
-    nn_idx[inv_s[i]] = inv_t[j];
 }
 
 }  // namespace mi

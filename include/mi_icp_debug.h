@@ -63,8 +63,8 @@ MI_ICP_API int mi_icp_debug_occupancy(int which);
 MI_ICP_API int mi_icp_debug_loop_counters(mi_icp_ctx* ctx, int32_t* out4);
 /* The leaf every staged source point FALLS INTO under T (column-major 4x4 or NULL) by the binary descent through the
  * cell planes and its group's planes (nn_search.h locate_by_planes): leaf_out[original source index] = leaf (host memory,
- * one per source point).  The located leaves are left behind as the seeds of the next seeded pass.  Fails on a tree
- * without planes (MI_ICP_NO_CELLS, a target below one group). */
+ * one per source point).  The located leaves are left behind as the seeds of the next seeded pass.  Fails without a
+ * staged source and target. */
 MI_ICP_API int mi_icp_debug_locate(mi_icp_ctx* ctx, const float* T, int32_t* leaf_out);
 MI_ICP_API int mi_icp_debug_set_step_stamps(mi_icp_ctx* ctx, int enable);
 MI_ICP_API int mi_icp_debug_get_step_stamps(mi_icp_ctx* ctx, uint64_t* out32, double* ticks_per_us);

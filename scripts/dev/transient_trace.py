@@ -1,5 +1,5 @@
 """The bench's transient, iteration by iteration: search time (HIP events) and how many re-locations have run -- one line per
-iteration.  MI_ICP_NO_LOCATE_PLANES=1 gives the former form (stale seeds, greedy first descent) for comparison."""
+iteration."""
 import os, sys, time, numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -18,7 +18,6 @@ init[:3, :3] = np.array([[np.cos(ang), -np.sin(ang), 0.0], [np.sin(ang), np.cos(
 rng = np.random.default_rng(6)
 noisy_all = (src + rng.normal(0.0, 0.15 * s, src.shape)).astype(np.float32)
 d_noisy = torch.from_numpy(np.ascontiguousarray(noisy_all)).cuda()
-mode = "former form (MI_ICP_NO_LOCATE_PLANES)" if os.environ.get("MI_ICP_NO_LOCATE_PLANES") else "locate by planes + re-location"
 for rep in range(2):      # (the first repetition builds the halos inside the loop; the second -- a context that has asked before -- ahead of it)
     eng.set_target(d_tgt, d_nrm)
     eng.set_source(d_noisy)
@@ -27,7 +26,7 @@ for rep in range(2):      # (the first repetition builds the halos inside the lo
     res = eng.icp_begin(_lib.EST_POINT_TO_PLANE, max_dist, init, -1.0)
     torch.cuda.synchronize(); tb = (time.perf_counter() - t0) * 1e3
     p = eng.get_profile()
-    line = ["%s, repetition %d: begin %.2f ms (first search %.3f ms, kind %d);" % (mode, rep, tb, p["nn_ms"], eng.last_search_kind())]
+    line = ["repetition %d: begin %.2f ms (first search %.3f ms, kind %d);" % (rep, tb, p["nn_ms"], eng.last_search_kind())]
     total = tb
     for k in range(30):
         p0 = eng.get_profile()

@@ -22,9 +22,7 @@ MI_ICP_FORCE_COMM=2 timeout 600 python bench.py --no-cpu-baseline --no-secondary
 timeout 600 python scripts/measure_colored.py 2>&1 | grep '^{' > $O/colored.jsonl
 timeout 600 python scripts/measure_kinfu.py 2>&1 | grep '^{' > $O/kinfu.jsonl
 timeout 600 python scripts/measure_odometry.py 2>&1 | grep '^{' > $O/odometry.jsonl
-timeout 600 python scripts/measure_links_payoff.py 2>&1 | grep '^{' > $O/links_payoff.jsonl; MI_ICP_NO_LINKS=1 timeout 600 python scripts/measure_links_payoff.py 2>&1 | grep '^{' >> $O/links_payoff.jsonl
 timeout 600 python scripts/measure_knn.py 1,0.0 8,0.0 30,0.0 30,0.01 64,0.0 100,0.0 100,0.02 2>&1 | grep '^{' > $O/knn_search.jsonl
-timeout 600 scripts/gpu_reduce_sweep.sh > $O/reduce_variants.txt 2>&1
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_stats -o r02 -- python $R/bench.py --no-cpu-baseline --no-secondary > $R/$O/rocprof_stats.log 2>&1; echo "stats rc=$?"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_cold -o r02cold -- python $R/scripts/measure_latency.py 10000000 > $R/$O/rocprof_cold.log 2>&1; echo "cold stats rc=$?"

@@ -26,6 +26,6 @@ T = np.array(res.transformation, np.float32).reshape(4, 4).T
 out = (C.c_uint64 * 4)()
 a = np.ascontiguousarray(T.T)
 eng._chk(eng._L.mi_icp_debug_nn_stats(eng._ctx, a.ctypes.data_as(C.c_void_p), 0.04, 1, out))
-print(json.dumps({"cells": os.environ.get("MI_ICP_NO_CELLS") is None, "n": len(vt), "it_per_s": 30 / dt, "us_per_iter": dt / 30 * 1e6,
+print(json.dumps({"n": len(vt), "it_per_s": 30 / dt, "us_per_iter": dt / 30 * 1e6,
                   "nn_us": (p1["nn_ms"] - p0["nn_ms"]) / 30 * 1e3, "reduce_us": (p1["reduce_ms"] - p0["reduce_ms"]) / 30 * 1e3,
                   "nodes_per_packet": out[0] / out[2], "leaves_per_packet": out[1] / out[2], "max_visits_of_a_packet": out[3]}))

@@ -149,7 +149,7 @@ def build_halos(e):
 @pytest.mark.parametrize("kind", ["uniform", "clustered", "surface"])
 def test_first_pass_from_its_own_seeds_equals_the_walk_from_the_root(kind):
     """Where the target's halos exist already, a registration loop's FIRST pass starts every query from the
-    leaf a greedy descent lands in (launch_nn: locate_leaves) instead of walking the tree from the root.
+    leaf it falls into (launch_nn: locate_by_planes) instead of walking the tree from the root.
     Same correspondences, bit for bit, as the first pass of a loop without halos and a one-shot search (both
     walk from the root) and as the oracle -- under a poor initial guess, with partial overlap and noise."""
     from cupoch_amd.engine import Engine
@@ -165,8 +165,7 @@ def test_first_pass_from_its_own_seeds_equals_the_walk_from_the_root(kind):
     _, oi, od = tree.search_radius(orc.transform_points(init, src), radius, 1)
     tree.close()
     oi = oi[:, 0]
-    never = os.environ.get("MI_ICP_NO_COARSE_FIRST") is not None    # (A/B switches of the library, read once per process)
-    always = os.environ.get("MI_ICP_WAIT_LINKS") is not None
+    always = os.environ.get("MI_ICP_WAIT_LINKS") is not None    # (an A/B switch of the library, read once per process)
     got = {}
     for name in ("root", "loop", "seeds+halos"):
         e = Engine(0)
@@ -180,7 +179,7 @@ def test_first_pass_from_its_own_seeds_equals_the_walk_from_the_root(kind):
             if name == "seeds+halos":
                 build_halos(e)
             res = e.icp_begin(P2P, radius, init, -1.0)
-            assert e.last_search_kind() == (2 if (name == "seeds+halos" or always) and not never else 0)
+            assert e.last_search_kind() == (2 if name == "seeds+halos" or always else 0)
             corr = e.get_correspondences()
             dense = np.full(len(src), -1, np.int32)
             dense[corr[:, 0]] = corr[:, 1]
@@ -274,13 +273,9 @@ def test_relocation_after_large_steps_changes_nothing_but_the_seeds():
     build_halos(e)
     res = e.registration_icp(P2P, radius, init, 0.0, 0.0, 25, -1.0)
     it, passes, reloc, armed = _loop_counters(e)
-    have_planes = os.environ.get("MI_ICP_NO_CELLS") is None and os.environ.get("MI_ICP_NO_LOCATE_PLANES") is None
-    if have_planes:
-        assert e.last_search_kind() in (1, 2)
-        assert 1 <= reloc < it, (reloc, it)            # the early steps re-located, the late ones did not
-        assert armed == 0                              # ... and the launches were taken off again
-    else:
-        assert reloc == 0
+    assert e.last_search_kind() in (1, 2)
+    assert 1 <= reloc < it, (reloc, it)                # the early steps re-located, the late ones did not
+    assert armed == 0                                  # ... and the launches were taken off again
     o = orc.registration_icp(src, tgt, radius, init=init, est=orc.EST_P2P, det_thresh=-1.0, max_iteration=25,
                              relative_fitness=0.0, relative_rmse=0.0, composed=True)
     T = np.array(res.transformation, np.float32).reshape(4, 4).T

@@ -5,7 +5,6 @@ exactness argument rests on (cupoch_amd/csrc/traverse.h):
   * a node's REGION (record floats 48..53, flag 54) contains no point of any other node in its
     interior -- what lets a lane whose search cube lies inside it stop looking elsewhere."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -41,7 +40,7 @@ def record_index(node):
 def check_tree(eng, pts, expect_all_flagged):
     eng.set_target(pts)
     nts, nleaf, leaf_first, rec, lines, nt = get_tree(eng)
-    assert nt == len(pts) and nleaf == (nts + 7) // 8      # (the Morton-run fallback tree does not pad to groups)
+    assert nt == len(pts) and nleaf == (nts + 7) // 8
     nts = nleaf * 8
     xyz = np.stack([lines[:, 0:8], lines[:, 8:16], lines[:, 16:24]], -1).reshape(-1, 3)      # slot -> coordinates
     orig = lines[:, 24:32].copy().view(np.int32).reshape(-1)
@@ -126,9 +125,6 @@ def check_leaf_halos(eng, nleaf, xyz, finite):
     lo, hi = reg[:, 0:3], reg[:, 4:7]
     wa, wb = reg[:, 3].copy().view(np.uint32), reg[:, 7].copy().view(np.uint32)
     have = np.flatnonzero(wb != 0)
-    if os.environ.get("MI_ICP_NO_CELLS") is not None or os.environ.get("MI_ICP_NO_LINKS") is not None:
-        assert len(have) == 0
-        return 0
     leaf_of = np.arange(len(xyz)) // 8
     pts = xyz.astype(np.float64)
     with_points = long_reach = 0
@@ -186,7 +182,7 @@ def check_leaf_regions(eng, nleaf, xyz, finite):
 
 def test_regions_uniform_cloud(eng):
     rng = np.random.default_rng(1)
-    f, t = check_tree(eng, rng.random((60000, 3), dtype=np.float32), os.environ.get("MI_ICP_NO_CELLS") is None)
+    f, t = check_tree(eng, rng.random((60000, 3), dtype=np.float32), True)
     assert t > 900
 
 
@@ -204,7 +200,7 @@ def _layout_cells(n, fill=3300):
 def test_regions_small_and_tiny_clouds(eng):
     rng = np.random.default_rng(2)
     for n in (1, 9, 100, 3300, 3301, 4097, 6601, 9000, 9901, 13201):
-        check_tree(eng, rng.random((n, 3), dtype=np.float32), os.environ.get("MI_ICP_NO_CELLS") is None)
+        check_tree(eng, rng.random((n, 3), dtype=np.float32), True)
 
 
 @pytest.mark.parametrize("n", [6601, 26401, 60000, 160000, 307200, 1000000, 5000000])
@@ -213,8 +209,6 @@ def test_cell_layouts_fill_their_groups_without_overflow(eng, n):
     uniform data every cell stays within its one 4096-slot group -- the tree has exactly as many groups as the layout
     has cells -- although the mean fill now goes up to 80 % (it was held below two thirds because the sampled medians
     left the counts +-12 %); the fullest cell says how much room is left."""
-    if os.environ.get("MI_ICP_NO_CELLS") is not None:
-        pytest.skip("Morton-run fallback tree: no cells")
     rng = np.random.default_rng(n)
     pts = rng.random((n, 3), dtype=np.float32)
     eng.set_target(pts)
@@ -246,10 +240,7 @@ def test_overflowing_cell_has_no_regions_but_the_rest_does(eng):
     pts = np.concatenate([rng.random((30000, 3), dtype=np.float32),
                           np.tile(np.array([[0.5, 0.5, 0.5]], np.float32), (20000, 1))])    # 20k copies: several groups
     flagged, total = check_tree(eng, pts, False)
-    if os.environ.get("MI_ICP_NO_CELLS") is None:
-        assert 0 < flagged < total
-    else:
-        assert flagged == 0                      # Morton runs are not kd cells: no regions at all
+    assert 0 < flagged < total
 
 
 @pytest.mark.parametrize("n", [70000, 307200, 1000000, 3000000])
@@ -259,8 +250,6 @@ def test_locate_by_planes_finds_the_leaf_a_target_point_lives_in(eng, n):
     point: any leaf is a valid seed, so the search tests cannot see a descent that lands next door -- only its cost
     does.  The target's own points as the source, under the identity: all but a handful (a coordinate equal to a plane
     through a quantised median, kd_refine.h) are found where they are stored."""
-    if os.environ.get("MI_ICP_NO_CELLS") is not None or os.environ.get("MI_ICP_NO_LOCATE_PLANES") is not None:
-        pytest.skip("no split planes on this tree")
     rng = np.random.default_rng(n + 7)
     pts = rng.random((n, 3), dtype=np.float32)
     eng.set_target(pts)
