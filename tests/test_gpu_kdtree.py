@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from knn_exact import rows_equal_up_to_ties
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -41,23 +42,6 @@ def test_golden_search_knn_and_radius(golden):
     # empty tree
     with pytest.raises(RuntimeError):
         geometry.KDTreeFlann().search_knn_vector_3f([0, 0, 0], 3)
-
-
-def rows_equal_up_to_ties(idx, d2, oi, od, tgt, qry):
-    """distances bit-exact; indices equal except where equal distances allow a choice"""
-    fin = np.isfinite(od)
-    assert np.array_equal(np.isfinite(d2), fin)
-    assert np.array_equal(d2[fin], od[fin])
-    assert np.array_equal(idx < 0, oi < 0)
-    bad = np.flatnonzero((idx != oi).any(axis=1))
-    for r in bad:                                      # only ties may differ
-        k = int(fin[r].sum())
-        dd = tgt[idx[r, :k]] - qry[r]
-        chk = (dd[:, 2] * dd[:, 2] + (dd[:, 1] * dd[:, 1] + dd[:, 0] * dd[:, 0])).astype(np.float32)
-        np.testing.assert_allclose(chk, od[r, :k], rtol=5e-7, err_msg=str(r))   # (numpy has no fma: last-ulp slack)
-        # (a tie inside the row, or between its last entry and the first point left out: the
-        # distances are the oracle's bit for bit either way, so this is a valid answer)
-    assert len(bad) <= max(2, len(idx) // 200)
 
 
 @pytest.mark.parametrize("nt,nq,k", [(1, 5, 3), (7, 100, 8), (100, 1, 30), (5000, 3000, 1), (5000, 3000, 17),
