@@ -46,8 +46,8 @@ def needs_build():
 def build(force=False, verbose=False, variant=None, defines=()):
     """hipcc --offload-arch=gfx950 -c csrc/<unit>.hip for every unit (in parallel; a unit whose object is newer than
     every source is kept), then hipcc -shared ... -o cupoch_amd/lib/libmi_icp.so
-    variant / defines: a second build for same-box A/B runs (MI_ICP_LIB_PATH), e.g. variant="census",
-    defines=("-DMI_KNN_CENSUS",) -> cupoch_amd/lib/libmi_icp_census.so
+    variant / defines: a second build for same-box A/B runs (MI_ICP_LIB_PATH), e.g. variant="ab",
+    defines=("-DNAME=1",) -> cupoch_amd/lib/libmi_icp_ab.so
     Safe against several processes building at once (every rank of a multi-process test imports the package): one
     file lock around the whole build, objects and the library written under a temporary name and renamed; objects
     compiled with other flags / defines are never reused (a stamp in the object directory holds their hash)."""

@@ -11,7 +11,7 @@
 //      kd order (spatially close, so the k-th distance is already tight);
 //   B. wave-uniform tree traversal as in nn_search.h with the lane's current
 //      k-th distance as its bound (seed leaves are skipped) -- for the lanes that
-//      belong to their packet; the others walk on their own (knn_walks_alone);
+//      belong to their packet; the others walk on their own (knn_walk);
 //   C. fp32 cumulants over the lane's k neighbours, closed-form eigenvector
 //      (FastEigen3x3MinMaxVec), written to the point's ORIGINAL index.
 // Neighbours include the point itself; fewer than 3 neighbours or a zero
@@ -29,8 +29,8 @@
 
 namespace mi {
 
-// Candidate lists come in two capacities: 32 slots (every caller on the ICP path -- normals with 30,
-// GICP 20, colour gradients 30) and 104 slots for anything up to knn::NUM_MAX_NN = 100
+// Candidate lists come in three capacities: 32 slots (every caller on the ICP path -- normals with 30,
+// GICP 20, colour gradients 30), 64, and 104 slots for anything up to knn::NUM_MAX_NN = 100
 // (knn/kdtree_search_param.h:26).  One wave per workgroup: a wave's life depends on its packet, and a
 // workgroup of two held its LDS until the slower one was done (normals of 10M points 29.4 -> 24.2 ms).
 // Only the DISTANCES live in LDS (8 KB per wave with 32 slots: 20 waves per CU; 26 KB with 104: 6); the
@@ -41,7 +41,6 @@ constexpr int kMaxKnn = 32;       // capacity of the small instantiation
 constexpr int kMaxKnnMid = 64;    // ... of the middle one (16 KB of LDS: 10 waves per CU)
 constexpr int kMaxKnnBig = 104;   // ... of the big one (a multiple of 8: the maxima are tracked per group of 8)
 constexpr int kKnnLimit = 100;    // NUM_MAX_NN: the most neighbours a search may ask for
-__host__ __device__ constexpr int knn_waves(int) { return 1; }
 __host__ __device__ constexpr int knn_capacity(int k) { return k <= kMaxKnn ? kMaxKnn : (k <= kMaxKnnMid ? kMaxKnnMid : kMaxKnnBig); }
 constexpr int kKnnSeedBefore = 4, kKnnSeedAfter = 12;  // leaves around the packet's first leaf
 
@@ -107,7 +106,6 @@ struct KnnStateT {
         }
     }
 };
-typedef KnnStateT<kMaxKnn> KnnState;
 
 // The 24 coordinates of leaf L (wave-uniform) through the scalar unit: three s_load_dwordx8 issued together,
 // one wait -- left to the compiler they became one load per coordinate, each waited for just before its use
@@ -197,6 +195,44 @@ __device__ __forceinline__ bool knn_offer(float* kd2, int32_t* kidx, int lane, i
     return shrunk;
 }
 
+// A lane's list of the k nearest: its distance column in LDS, its index column in the slab row, the k it keeps
+// and its state.  It starts empty, with bound `bound` (-1: the lane takes nothing).
+template <int KCAP>
+struct KnnList {
+    float* kd2;
+    int32_t* kidx;
+    int lane, k;
+    KnnStateT<KCAP> st;
+    __device__ __forceinline__ KnnList(float* kd2_, int32_t* kidx_, int k_, float bound)
+        : kd2(kd2_), kidx(kidx_), lane(lane_id()), k(k_) {
+        st.init(bound);
+        knn_clear<KCAP>(kd2, lane);
+    }
+    __device__ __forceinline__ bool offer(float d2, int32_t j) { return knn_offer(kd2, kidx, lane, k, st, d2, j); }
+};
+
+// Leaf L offered to this lane alone (divergent paths: the solo walk, the search's seeding), its 24 coordinates read
+// by the lane as six 16-byte loads.  A lane with `on` unset reads leaf 0 and is offered +inf.
+template <int KCAP>
+__device__ __forceinline__ void knn_offer_leaf(const float* tblk_g, uint32_t L, bool on, float qx, float qy, float qz,
+                                               KnnList<KCAP>& l) {
+    const float4* line = reinterpret_cast<const float4*>(tblk_g + (size_t)(on ? L : 0u) * kLeafFloats);
+    float c[24];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+        const float4 f = line[e];
+        c[4 * e] = f.x;
+        c[4 * e + 1] = f.y;
+        c[4 * e + 2] = f.z;
+        c[4 * e + 3] = f.w;
+    }
+#pragma unroll
+    for (int u = 0; u < kLeaf; ++u) {
+        const float d2 = on ? sq3(qx - c[u], qy - c[8 + u], qz - c[16 + u]) : INFINITY;
+        l.offer(d2, (int32_t)(L * kLeaf) + u);  // padding points: d2 = +inf
+    }
+}
+
 // ---- lanes that do not belong to their packet ---------------------------------------------------------------
 // The walk is wave-uniform: a packet enters every box that ANY of its lanes' cubes overlaps, and every lane is
 // offered every point found there.  That is cheap while the 64 queries are neighbours with similar bounds -- and
@@ -264,167 +300,68 @@ __device__ __forceinline__ bool knn_packet_reaches_too_far(const float* records_
     return nodes > kSoloNodes;
 }
 
-// OUT 0: normals_out[orig] (3 floats).  OUT 1: tgrad[sorted] (float4, w = 0) and, when
-// not null, normals_out[orig] receives the gradient for inspection; tnrm = sorted target
-// normals with the intensity in .w.
-template <int OUT, int KCAP = kMaxKnn>
-__global__ __launch_bounds__(knn_waves(KCAP) * 64) void knn_normals_kernel(
-        const float* __restrict__ records_g, const float* __restrict__ tblk_g, const int32_t* __restrict__ tidx_g,
-        uint32_t leaf_first, int64_t n, int nleaf,
-        int k, float r2, uint32_t nblocks, float* __restrict__ normals_out,
-        const float4* __restrict__ tnrm, float4* __restrict__ tgrad, KnnSlab slab) {
-    constexpr int kWaves = knn_waves(KCAP);
-    __shared__ float s_d2[kWaves][KCAP * 64];
-    uint32_t logical;
-    if (!xcd_remap(nblocks, logical)) return;
-    const cfloat_p tblk = (cfloat_p)(uintptr_t)tblk_g;
-    const int lane = lane_id(), wid = (int)(threadIdx.x >> 6);
-    float* kd2 = s_d2[wid];
-
-    const int pkt = __builtin_amdgcn_readfirstlane((int)logical * kWaves + wid);
-    const int leaf0 = pkt * 8;
-    if (leaf0 >= nleaf) return;  // whole wave out of range (no block barriers below)
-    const uint32_t row = knn_row_claim(slab, (uint32_t)pkt);
-    int32_t* kidx = slab.rows + (size_t)row * (KCAP * 64);
-    [&]() {  // (lanes leave this body one by one; the row goes back when all of them have)
-    const int64_t i = (int64_t)pkt * 64 + lane;
-    float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-    int32_t orig = -1;
-    if (i < n) {  // n = sorted positions; padding slots carry original index -1
-        const float* line = tblk_g + (i >> 3) * kLeafFloats + (i & 7);
-        qx = line[0];
-        qy = line[8];
-        qz = line[16];
-        orig = tidx_g[i];
-    }
-    const bool valid = orig >= 0;
-    KnnStateT<KCAP> st;
-    // r2 = +inf: plain k-NN; finite: the k nearest with d2 < r2 (KDTreeSearchParamRadius)
-    st.init((valid && k > 0) ? r2 : -1.0f);
-    knn_clear<KCAP>(kd2, lane);
-
-    // ---- A: seed from the Morton neighbourhood ---------------------------------
-    const int seed_lo = max(0, leaf0 - kKnnSeedBefore);
-    const int seed_hi = min(nleaf, leaf0 + kKnnSeedAfter);
-    for (int L = seed_lo; L < seed_hi; ++L) {
-        const LeafXYZ p = load_leaf(tblk, L);
-#pragma unroll
-        for (int t = 0; t < kLeaf; ++t) {
-            const float d2 = sq3(qx - p.x[t], qy - p.y[t], qz - p.z[t]);
-            knn_offer(kd2, kidx, lane, k, st, d2, L * kLeaf + t);  // padding points have d2 = +inf
-        }
-    }
-    // lanes that would drag the packet through the tree walk alone, after the others (knn_walks_alone)
-    bool solo = knn_walks_alone(valid && k > 0, qx, qy, qz, st.worst);
-    const float solo_bound = st.worst;
+// ---- B: the walk of both kernels ------------------------------------------------------------------------------
+// The lanes that would drag the packet through the tree (knn_walks_alone, knn_packet_reaches_too_far) are left out of
+// the wave's walk and walk on their own after it; the others walk with the packet.  active: the lane searches at all.
+// [seed_lo, seed_hi): the leaves this lane has been offered already.  kPacketSeeds: the range is the packet's (normals
+// kernel) and the wave skips those leaves unread; otherwise it is the lane's own (search) and they are offered at +inf.
+template <bool kPacketSeeds, int KCAP>
+__device__ __forceinline__ void knn_walk(const float* records_g, const float* tblk_g, uint32_t leaf_first, bool active,
+                                         float qx, float qy, float qz, uint32_t seed_lo, uint32_t seed_hi,
+                                         KnnList<KCAP>& l) {
+    bool solo = knn_walks_alone(active, qx, qy, qz, l.st.worst);
+    const float solo_bound = l.st.worst;
     Cube cube;
-    set_cube(cube, qx, qy, qz, solo ? -1.0f : st.worst);
+    set_cube(cube, qx, qy, qz, solo ? -1.0f : l.st.worst);
     if (knn_packet_reaches_too_far(records_g, leaf_first, cube)) {
-        solo = valid && k > 0;
+        solo = active;
         set_cube(cube, qx, qy, qz, -1.0f);
     }
-    if (solo) st.worst = -1.0f;  // (nothing is below that: the wave's walk offers them nothing)
-
-    // ---- B: traversal -------------------------------------------------------------
+    if (solo) l.st.worst = -1.0f;  // (nothing is below that: the wave's walk offers them nothing)
+    const cfloat_p tblk = (cfloat_p)(uintptr_t)tblk_g;
     traverse_wide(records_g, leaf_first, cube, [&](uint32_t Lu) {
         const int L = __builtin_amdgcn_readfirstlane((int)Lu);  // (wave-uniform by construction)
-        if (L >= seed_lo && L < seed_hi) return;
+        const bool seeded = (uint32_t)L >= seed_lo && (uint32_t)L < seed_hi;
+        if (kPacketSeeds && seeded) return;
         const LeafXYZ p = load_leaf(tblk, L);
         bool shrunk = false;
 #pragma unroll
         for (int t = 0; t < kLeaf; ++t) {
-            const float d2 = sq3(qx - p.x[t], qy - p.y[t], qz - p.z[t]);
-            shrunk |= knn_offer(kd2, kidx, lane, k, st, d2, L * kLeaf + t);
+            const float d2 = (!kPacketSeeds && seeded) ? INFINITY : sq3(qx - p.x[t], qy - p.y[t], qz - p.z[t]);
+            shrunk |= l.offer(d2, L * kLeaf + t);  // padding points: d2 = +inf
         }
-        if (shrunk) set_cube(cube, qx, qy, qz, st.worst);
+        if (shrunk) set_cube(cube, qx, qy, qz, l.st.worst);
     });
     if (__ballot(solo) != 0ull) {  // (rare: wave-uniform)
-        if (solo) st.worst = solo_bound;
-        solo_walk(records_g, leaf_first, solo, qx, qy, qz, [&]() { return st.worst; }, [&](uint32_t L) {
-            if ((int)L >= seed_lo && (int)L < seed_hi) return;
-            const float4* line = reinterpret_cast<const float4*>(tblk_g + (size_t)L * kLeafFloats);
-            float c[24];
-#pragma unroll
-            for (int e = 0; e < 6; ++e) {
-                const float4 f = line[e];
-                c[4 * e] = f.x;
-                c[4 * e + 1] = f.y;
-                c[4 * e + 2] = f.z;
-                c[4 * e + 3] = f.w;
-            }
-#pragma unroll
-            for (int t = 0; t < kLeaf; ++t)
-                knn_offer(kd2, kidx, lane, k, st, sq3(qx - c[t], qy - c[8 + t], qz - c[16 + t]), (int32_t)(L * kLeaf) + t);
+        if (solo) l.st.worst = solo_bound;
+        solo_walk(records_g, leaf_first, solo, qx, qy, qz, [&]() { return l.st.worst; }, [&](uint32_t L) {
+            if (L >= seed_lo && L < seed_hi) return;
+            knn_offer_leaf(tblk_g, L, true, qx, qy, qz, l);
         });
     }
+}
 
-    if (!valid) return;
-    if (OUT == 1) {
-        // ---- C': colour gradient (colored_icp.cu:88-120) ------------------------------------
-        float gx = 0.0f, gy = 0.0f, gz = 0.0f;
-        if (k > 0 && st.count >= 5) {  // nn = count - 1 >= 4
-            int skip = 0;  // the reference drops the first (nearest) entry of the sorted list
-            float dmin = kd2[lane];
-            for (int t = 1; t < st.count; ++t) {
-                const float v = kd2[t * 64 + lane];
-                if (v < dmin) {
-                    dmin = v;
-                    skip = t;
-                }
-            }
-            const float4 n4 = tnrm[i];
-            const float nt[3] = {n4.x, n4.y, n4.z};
-            const float it = n4.w;
-            M3 A;
-            float b[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c2 = 0; c2 < 3; ++c2) A.m[r][c2] = 0.0f;
-            for (int t = 0; t < st.count; ++t) {
-                if (t == skip) continue;
-                const int32_t j = kidx[t * 64 + lane];
-                const float* line = tblk_g + (int64_t)(j >> 3) * kLeafFloats + (j & 7);
-                const float da[3] = {line[0] - qx, line[8] - qy, line[16] - qz};
-                const float h = dot3(da, nt);
-                const float v[3] = {(line[0] - h * nt[0]) - qx, (line[8] - h * nt[1]) - qy,
-                                    (line[16] - h * nt[2]) - qz};
-                const float di = tnrm[j].w - it;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-#pragma unroll
-                    for (int c2 = 0; c2 < 3; ++c2) A.m[r][c2] += v[r] * v[c2];
-                    b[r] += di * v[r];
-                }
-            }
-            const int nn = st.count - 1;
-            const float w = (float)((nn - 1) * (nn - 1));
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-#pragma unroll
-                for (int c2 = 0; c2 < 3; ++c2) A.m[r][c2] += w * nt[r] * nt[c2];
-                A.m[r][r] += 1.0e-6f;
-            }
-            M3 Ai;
-            inverse3(A, Ai);
-            gx = Ai.m[0][0] * b[0] + Ai.m[0][1] * b[1] + Ai.m[0][2] * b[2];
-            gy = Ai.m[1][0] * b[0] + Ai.m[1][1] * b[1] + Ai.m[1][2] * b[2];
-            gz = Ai.m[2][0] * b[0] + Ai.m[2][1] * b[1] + Ai.m[2][2] * b[2];
-        }
-        tgrad[i] = make_float4(gx, gy, gz, 0.0f);
-        if (normals_out) {
-            normals_out[(int64_t)orig * 3] = gx;
-            normals_out[(int64_t)orig * 3 + 1] = gy;
-            normals_out[(int64_t)orig * 3 + 2] = gz;
-        }
-        return;
-    }
-    // ---- C: covariance of the neighbours -> normal ------------------------------------
+// The frame of both kernels: one wave per workgroup, one packet per wave.  body(pkt, kd2, kidx) gets the wave's
+// packet (< nblocks, the number of packets), its distance columns in LDS and the index columns of a slab row claimed
+// for it; the row goes back when body returns.
+template <int KCAP, class Body>
+__device__ __forceinline__ void knn_wave(uint32_t nblocks, const KnnSlab& slab, Body&& body) {
+    __shared__ float s_d2[KCAP * 64];
+    uint32_t pkt;
+    if (!xcd_remap(nblocks, pkt)) return;
+    const uint32_t row = knn_row_claim(slab, pkt);
+    body(pkt, s_d2, slab.rows + (size_t)row * (KCAP * 64));
+    knn_row_release(slab, row);
+}
+
+// ---- C: covariance of the lane's neighbours -> normal ((0,0,1) for fewer than 3 of them or no eigenvector)
+template <int KCAP>
+__device__ __forceinline__ float3 knn_normal(const float* tblk_g, const KnnList<KCAP>& l) {
     float nx = 0.0f, ny = 0.0f, nz = 1.0f;
-    if (k > 0 && st.count >= 3) {
+    if (l.k > 0 && l.st.count >= 3) {
         float cum[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int t = 0; t < st.count; ++t) {
-            const int32_t j = kidx[t * 64 + lane];
+        for (int t = 0; t < l.st.count; ++t) {
+            const int32_t j = l.kidx[t * 64 + l.lane];
             const float* line = tblk_g + (int64_t)(j >> 3) * kLeafFloats + (j & 7);
             const float px = line[0], py = line[8], pz = line[16];
             cum[0] += px;
@@ -437,7 +374,7 @@ __global__ __launch_bounds__(knn_waves(KCAP) * 64) void knn_normals_kernel(
             cum[7] += py * pz;
             cum[8] += pz * pz;
         }
-        const float cnt = (float)st.count;
+        const float cnt = (float)l.st.count;
 #pragma unroll
         for (int e = 0; e < 9; ++e) cum[e] = cum[e] / cnt;
         M3 A;
@@ -455,270 +392,173 @@ __global__ __launch_bounds__(knn_waves(KCAP) * 64) void knn_normals_kernel(
         const float vx = (mi_ == 0) ? e[0][0] : ((mi_ == 1) ? e[1][0] : e[2][0]);
         const float vy = (mi_ == 0) ? e[0][1] : ((mi_ == 1) ? e[1][1] : e[2][1]);
         const float vz = (mi_ == 0) ? e[0][2] : ((mi_ == 1) ? e[1][2] : e[2][2]);
-        const float l = sqrtf(vx * vx + vy * vy + vz * vz);
-        if (l != 0.0f && !isnan(l)) {
+        const float len = sqrtf(vx * vx + vy * vy + vz * vz);
+        if (len != 0.0f && !isnan(len)) {
             nx = vx;
             ny = vy;
             nz = vz;
         }
     }
-    normals_out[(int64_t)orig * 3] = nx;
-    normals_out[(int64_t)orig * 3 + 1] = ny;
-    normals_out[(int64_t)orig * 3 + 2] = nz;
-    }();
-    knn_row_release(slab, row);
+    return make_float3(nx, ny, nz);
 }
 
-// ---- knn::KDTreeFlann::SearchKNN / SearchRadius for arbitrary queries ---------------------
-// (knn/kdtree_flann.inl:46-122: FLANN knnSearch / radiusSearch with sorted results).
-// A wave owns 64 Morton-consecutive QUERIES (staged like the ICP source); candidates live
-// in the same LDS columns as above, the walk is top-down from the root (no seeds: a query
-// need not be near any particular leaf), and at the end every lane sorts its candidates in
-// registers -- a 32-input bitonic network on (d2, original index) -- and writes its row
-// [k] of indices / squared distances, padded with -1 / +inf, at the query's ORIGINAL index.
-template <int KCAP = kMaxKnn>
-__global__ __launch_bounds__(knn_waves(KCAP) * 64) void knn_search_kernel(
-        const float* __restrict__ records_g, const float* __restrict__ tblk_g, const int32_t* __restrict__ tidx_g,
-        uint32_t leaf_first, const float* __restrict__ qx_g, const float* __restrict__ qy_g, const float* __restrict__ qz_g,
-        const int32_t* __restrict__ qperm, int nq, int nleaf, int k, float r2, uint32_t nblocks,
-        int32_t* __restrict__ idx_out, float* __restrict__ d2_out, unsigned long long* __restrict__ found,
-        KnnSlab slab) {
-    constexpr int kWaves = knn_waves(KCAP);
-    __shared__ float s_d2[kWaves][KCAP * 64];
-    uint32_t logical;
-    if (!xcd_remap(nblocks, logical)) return;
-    const cfloat_p tblk = (cfloat_p)(uintptr_t)tblk_g;
-    const int lane = lane_id(), wid = (int)(threadIdx.x >> 6);
-    float* kd2 = s_d2[wid];
-    const int64_t i = ((int64_t)logical * kWaves + wid) * 64 + lane;
-    if (i - lane >= nq) return;  // whole wave out of range (no block barriers below)
-    const uint32_t row = knn_row_claim(slab, logical * (uint32_t)kWaves + (uint32_t)wid);
-    int32_t* kidx = slab.rows + (size_t)row * (KCAP * 64);
-    [&]() {  // (as in knn_normals_kernel)
-    const bool valid = i < nq;
-    float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-    if (valid) {
-        qx = qx_g[i];
-        qy = qy_g[i];
-        qz = qz_g[i];
-    }
-    KnnStateT<KCAP> st;
-    st.init((valid && k > 0) ? r2 : -1.0f);  // r2 = +inf: plain k-NN
-    knn_clear<KCAP>(kd2, lane);
-
-    // ---- A: a first bound.  A plain k-NN query starts with an infinite search cube, and a
-    // depth-first walk in child order would wade through the whole tree before the k-th
-    // distance means anything (measured: 2.8 s for 2M queries).  So every LANE first descends
-    // greedily on its own -- at each record into the child whose box is nearest (Linf) to its
-    // query; neighbouring lanes read the same records, so the divergent loads hit L1 -- and
-    // offers itself the 64 slots under the leaf-level node it arrives at: the k-th distance
-    // among a query's own 64 nearest-cell points is within a small factor of the true one.
-    // (A packet-level seed -- one descent for the
-    // packet's first query -- left the far lanes with a packet-diameter bound and the walk
-    // 10x wider: 92 ms instead of ~10 for 2M queries at k = 8.)  Each lane skips its own
-    // seeded leaves [seed_lo, seed_hi) in the walk below.
-    uint32_t seed_lo = 0u, seed_hi = 0u;
-    if (k > 0) {
-        uint32_t id = 1u;
-        int32_t off = -1;
-        while (id < leaf_first) {  // same depth for every lane
-            const float4* rec = reinterpret_cast<const float4*>(records_g + ((size_t)(id + (uint32_t)off) << 6));
-            float w[48];
-#pragma unroll
-            for (int e = 0; e < 12; ++e) {
-                const float4 f = rec[e];
-                w[4 * e] = f.x;
-                w[4 * e + 1] = f.y;
-                w[4 * e + 2] = f.z;
-                w[4 * e + 3] = f.w;
-            }
-            float bestd = INFINITY;
-            int bestc = 0;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const float* b = w + (c >> 1) * kPairStride + (c & 1);
-                // max over the axes of the distance to the slab; an empty (inverted) box gives +inf
-                const float dx = fmaxf(fmaxf(b[0] - qx, qx - b[6]), 0.0f);
-                const float dy = fmaxf(fmaxf(b[2] - qy, qy - b[8]), 0.0f);
-                const float dz = fmaxf(fmaxf(b[4] - qz, qz - b[10]), 0.0f);
-                const float d = fmaxf(dx, fmaxf(dy, dz));
-                if (d < bestd) {
-                    bestd = d;
-                    bestc = c;
-                }
-            }
-            id = id * 8u + (uint32_t)bestc;
-            off = off * 8 + 1;
-        }
-        const uint32_t own = (id - leaf_first) * 8u;          // first leaf under the node reached
-        const uint32_t nleaf_u = (uint32_t)nleaf;
-        // leaf lb + s of every lane that takes part, s = 0..7
-        auto offer_leaves = [&](uint32_t lb, bool take) {
-            if (__ballot(take) == 0ull) return;
-            for (uint32_t s = 0; s < 8u; ++s) {
-                const uint32_t L = lb + s;
-                const bool on = take && L < nleaf_u;
-                const float4* line = reinterpret_cast<const float4*>(tblk_g + (size_t)(on ? L : 0u) * kLeafFloats);
-                float c[24];
-#pragma unroll
-                for (int e = 0; e < 6; ++e) {
-                    const float4 f = line[e];
-                    c[4 * e] = f.x;
-                    c[4 * e + 1] = f.y;
-                    c[4 * e + 2] = f.z;
-                    c[4 * e + 3] = f.w;
-                }
-#pragma unroll
-                for (int u = 0; u < kLeaf; ++u) {
-                    const float d2 = on ? sq3(qx - c[u], qy - c[8 + u], qz - c[16 + u]) : INFINITY;
-                    knn_offer(kd2, kidx, lane, k, st, d2, (int32_t)(L * kLeaf) + u);  // padding points: d2 = +inf
-                }
-            }
-        };
-        offer_leaves(own, valid);
-        seed_lo = own;
-        seed_hi = own + 8u;
-        // Lanes still short of k candidates (a node in a group's padded tail can hold any number
-        // of real points, down to one) widen to the node's parent, grandparent, ... -- without
-        // this their bound stays infinite and the walk below offers them the whole cloud (a
-        // handful of such packets cost 90 ms at k = 4).
-        const uint32_t all = leaf_first * 8u;  // leaves under the root
-        for (uint32_t nspan = 64u; nspan <= all; nspan *= 8u) {
-            const bool more = valid && st.count < k && st.worst == INFINITY;  // (a radius search is bounded anyway)
-            if (__ballot(more) == 0ull) break;
-            const uint32_t nlo = own & ~(nspan - 1u);
-            for (uint32_t s = 0; s < nspan; s += 8u) {
-                const uint32_t lb = nlo + s;
-                offer_leaves(lb, more && (lb < seed_lo || lb >= seed_hi));
-            }
-            if (more) {
-                seed_lo = nlo;
-                seed_hi = nlo + nspan;
+// ---- C': colour gradient (colored_icp.cu:88-120) of the lane's point (query q, sorted index i) in its tangent plane
+template <int KCAP>
+__device__ __forceinline__ float3 knn_color_gradient(const float* tblk_g, const float4* tnrm, int64_t i, float qx,
+                                                     float qy, float qz, const KnnList<KCAP>& l) {
+    const float* kd2 = l.kd2;
+    const int32_t* kidx = l.kidx;
+    const int lane = l.lane, count = l.st.count;
+    float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    if (l.k > 0 && count >= 5) {  // nn = count - 1 >= 4
+        int skip = 0;  // the reference drops the first (nearest) entry of the sorted list
+        float dmin = kd2[lane];
+        for (int t = 1; t < count; ++t) {
+            const float v = kd2[t * 64 + lane];
+            if (v < dmin) {
+                dmin = v;
+                skip = t;
             }
         }
-    }
-    bool solo = knn_walks_alone(valid && k > 0, qx, qy, qz, st.worst);  // (see there)
-    const float solo_bound = st.worst;
-    Cube cube;
-    set_cube(cube, qx, qy, qz, solo ? -1.0f : st.worst);
-    if (knn_packet_reaches_too_far(records_g, leaf_first, cube)) {
-        solo = valid && k > 0;
-        set_cube(cube, qx, qy, qz, -1.0f);
-    }
-    if (solo) st.worst = -1.0f;
-    // ---- B: the exact walk
-#ifdef MI_KNN_CENSUS
-    unsigned long long cs_leaves = 0ull, cs_waveacc = 0ull, cs_laneacc = 0ull, cs_shrinks = 0ull;
-    const float cs_bound0 = st.worst;
-#endif
-#ifdef MI_KNN_CENSUS
-    const uint32_t cs_records =
-#endif
-    traverse_wide(records_g, leaf_first, cube, [&](uint32_t Lu) {
-        const bool seeded = Lu >= seed_lo && Lu < seed_hi;  // this lane has these points already
-        const int L = __builtin_amdgcn_readfirstlane((int)Lu);
-        const LeafXYZ p = load_leaf(tblk, L);
-        bool shrunk = false;
+        const float4 n4 = tnrm[i];
+        const float nt[3] = {n4.x, n4.y, n4.z};
+        const float it = n4.w;
+        M3 A;
+        float b[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
-        for (int t = 0; t < kLeaf; ++t) {
-            const float d2 = seeded ? INFINITY : sq3(qx - p.x[t], qy - p.y[t], qz - p.z[t]);
-#ifdef MI_KNN_CENSUS
-            const uint64_t cs_m = __ballot(d2 < st.worst);
-            cs_waveacc += cs_m != 0ull ? 1ull : 0ull;
-            cs_laneacc += (unsigned long long)__popcll(cs_m);
-#endif
-            shrunk |= knn_offer(kd2, kidx, lane, k, st, d2, L * kLeaf + t);  // padding points: d2 = +inf
-        }
-#ifdef MI_KNN_CENSUS
-        cs_leaves += 1ull;
-        cs_shrinks += __ballot(shrunk) != 0ull ? 1ull : 0ull;
-#endif
-        if (shrunk) set_cube(cube, qx, qy, qz, st.worst);
-    });
-#ifdef MI_KNN_CENSUS
-    if (found) {
-        // sums over the packets: leaves offered, candidates some lane accepted, lane-accepts, leaves after which a cube
-        // shrank, records visited, packets; and the lanes' bounds (radii) before / after the walk, summed over finite ones
-        const float r0 = __builtin_amdgcn_sqrtf(fmaxf(cs_bound0, 0.0f)), r1 = __builtin_amdgcn_sqrtf(fmaxf(st.worst, 0.0f));
-        const bool fin = valid && k > 0 && r0 < INFINITY && !solo;
-        const float s0 = wave_all_sum(fin ? r0 : 0.0f), s1 = wave_all_sum(fin ? r1 : 0.0f), sn = wave_all_sum(fin ? 1.0f : 0.0f);
-        const float mx0 = wave_all_max(fin ? r0 : 0.0f), mn0 = wave_all_min(fin ? r0 : INFINITY);
-        if (lane == 0) {
-            atomicAdd(found + 1, cs_leaves);
-            atomicAdd(found + 2, cs_waveacc);
-            atomicAdd(found + 3, cs_laneacc);
-            atomicAdd(found + 4, cs_shrinks);
-            atomicAdd(found + 5, (unsigned long long)cs_records);
-            atomicAdd(found + 6, 1ull);
-            atomicAdd(reinterpret_cast<double*>(found + 7), (double)s0);
-            atomicAdd(reinterpret_cast<double*>(found + 8), (double)s1);
-            atomicAdd(reinterpret_cast<double*>(found + 9), (double)sn);
-            atomicAdd(reinterpret_cast<double*>(found + 10), (double)mx0);
-            atomicAdd(reinterpret_cast<double*>(found + 11), (double)mn0);
-            atomicAdd(found + 12, (unsigned long long)__popcll(__ballot(solo)));
-        }
-    }
-#endif
-    if (__ballot(solo) != 0ull) {
-        if (solo) st.worst = solo_bound;
-        solo_walk(records_g, leaf_first, solo, qx, qy, qz, [&]() { return st.worst; }, [&](uint32_t L) {
-            if (L >= seed_lo && L < seed_hi) return;
-            const float4* line = reinterpret_cast<const float4*>(tblk_g + (size_t)L * kLeafFloats);
-            float c[24];
+        for (int r = 0; r < 3; ++r)
 #pragma unroll
-            for (int e = 0; e < 6; ++e) {
-                const float4 f = line[e];
-                c[4 * e] = f.x;
-                c[4 * e + 1] = f.y;
-                c[4 * e + 2] = f.z;
-                c[4 * e + 3] = f.w;
-            }
-#pragma unroll
-            for (int u = 0; u < kLeaf; ++u)
-                knn_offer(kd2, kidx, lane, k, st, sq3(qx - c[u], qy - c[8 + u], qz - c[16 + u]), (int32_t)(L * kLeaf) + u);
-        });
-    }
-    if (!valid) return;
-    const int64_t row = (int64_t)qperm[i] * k;
-    if constexpr (KCAP > kMaxKnn) {
-        // ---- the big lists: every entry goes to the row position of its RANK by (d2, original index) --
-        // the number of entries with a smaller distance, read from the lane's LDS column; the indices
-        // (global memory) are compared only between entries whose distances are equal
-        for (int t = 0; t < st.count; ++t) {
+            for (int c2 = 0; c2 < 3; ++c2) A.m[r][c2] = 0.0f;
+        for (int t = 0; t < count; ++t) {
+            if (t == skip) continue;
             const int32_t j = kidx[t * 64 + lane];
-            kidx[t * 64 + lane] = tidx_g[j];
-        }
-        for (int a = 0; a < st.count; ++a) {
-            const float dv = kd2[a * 64 + lane];
-            int rank = 0, same = 0;
-            for (int b = 0; b < st.count; ++b) {
-                const float db = kd2[b * 64 + lane];
-                rank += (db < dv) ? 1 : 0;
-                same += (db == dv) ? 1 : 0;
+            const float* line = tblk_g + (int64_t)(j >> 3) * kLeafFloats + (j & 7);
+            const float da[3] = {line[0] - qx, line[8] - qy, line[16] - qz};
+            const float h = dot3(da, nt);
+            const float v[3] = {(line[0] - h * nt[0]) - qx, (line[8] - h * nt[1]) - qy,
+                                (line[16] - h * nt[2]) - qz};
+            const float di = tnrm[j].w - it;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                for (int c2 = 0; c2 < 3; ++c2) A.m[r][c2] += v[r] * v[c2];
+                b[r] += di * v[r];
             }
-            const int32_t iv = kidx[a * 64 + lane];
-            if (same > 1) {
-                for (int b = 0; b < st.count; ++b)
-                    if (b != a && kd2[b * 64 + lane] == dv && kidx[b * 64 + lane] < iv) ++rank;
-            }
-            idx_out[row + rank] = iv;
-            d2_out[row + rank] = dv;
         }
-        for (int t = st.count; t < k; ++t) {
-            idx_out[row + t] = -1;
-            d2_out[row + t] = INFINITY;
+        const int nn = count - 1;
+        const float w = (float)((nn - 1) * (nn - 1));
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int c2 = 0; c2 < 3; ++c2) A.m[r][c2] += w * nt[r] * nt[c2];
+            A.m[r][r] += 1.0e-6f;
         }
-    } else {
-    // ---- sort (d2, original index) ascending in registers, unused slots last
+        M3 Ai;
+        inverse3(A, Ai);
+        gx = Ai.m[0][0] * b[0] + Ai.m[0][1] * b[1] + Ai.m[0][2] * b[2];
+        gy = Ai.m[1][0] * b[0] + Ai.m[1][1] * b[1] + Ai.m[1][2] * b[2];
+        gz = Ai.m[2][0] * b[0] + Ai.m[2][1] * b[1] + Ai.m[2][2] * b[2];
+    }
+    return make_float3(gx, gy, gz);
+}
+
+// OUT 0: normals_out[orig] (3 floats).  OUT 1: tgrad[sorted] (float4, w = 0) and, when
+// not null, normals_out[orig] receives the gradient for inspection; tnrm = sorted target
+// normals with the intensity in .w.
+template <int OUT, int KCAP = kMaxKnn>
+__global__ __launch_bounds__(64) void knn_normals_kernel(
+        const float* __restrict__ records_g, const float* __restrict__ tblk_g, const int32_t* __restrict__ tidx_g,
+        uint32_t leaf_first, int64_t n, int nleaf, int k, float r2, float* __restrict__ normals_out,
+        const float4* __restrict__ tnrm, float4* __restrict__ tgrad, uint32_t nblocks, KnnSlab slab) {
+    knn_wave<KCAP>(nblocks, slab, [&](uint32_t pkt, float* kd2, int32_t* kidx) {
+        const int64_t i = (int64_t)pkt * 64 + lane_id();
+        float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+        int32_t orig = -1;
+        if (i < n) {  // n = sorted positions; padding slots carry original index -1
+            const float* line = tblk_g + (i >> 3) * kLeafFloats + (i & 7);
+            qx = line[0];
+            qy = line[8];
+            qz = line[16];
+            orig = tidx_g[i];
+        }
+        const bool valid = orig >= 0;
+        // r2 = +inf: plain k-NN; finite: the k nearest with d2 < r2 (KDTreeSearchParamRadius)
+        KnnList<KCAP> l(kd2, kidx, k, (valid && k > 0) ? r2 : -1.0f);
+
+        // ---- A: seed from the Morton neighbourhood
+        const cfloat_p tblk = (cfloat_p)(uintptr_t)tblk_g;
+        const int leaf0 = (int)pkt * 8;
+        const int seed_lo = max(0, leaf0 - kKnnSeedBefore);
+        const int seed_hi = min(nleaf, leaf0 + kKnnSeedAfter);
+        for (int L = seed_lo; L < seed_hi; ++L) {
+            const LeafXYZ p = load_leaf(tblk, L);
+#pragma unroll
+            for (int t = 0; t < kLeaf; ++t)
+                l.offer(sq3(qx - p.x[t], qy - p.y[t], qz - p.z[t]), L * kLeaf + t);  // padding points have d2 = +inf
+        }
+        knn_walk<true>(records_g, tblk_g, leaf_first, valid && k > 0, qx, qy, qz, (uint32_t)seed_lo, (uint32_t)seed_hi, l);
+
+        if (!valid) return;
+        const float3 v = OUT == 1 ? knn_color_gradient(tblk_g, tnrm, i, qx, qy, qz, l) : knn_normal(tblk_g, l);
+        if (OUT == 1) tgrad[i] = make_float4(v.x, v.y, v.z, 0.0f);
+        if (OUT == 0 || normals_out) {
+            normals_out[(int64_t)orig * 3] = v.x;
+            normals_out[(int64_t)orig * 3 + 1] = v.y;
+            normals_out[(int64_t)orig * 3 + 2] = v.z;
+        }
+    });
+}
+
+// ---- the search's row (d2 ascending, ties by original index), padded with -1 / +inf, at `row`.
+// Big lists: every entry goes to the row position of its RANK by (d2, original index) -- the number of entries with
+// a smaller distance, read from the lane's LDS column; the indices (global memory) are compared only between entries
+// whose distances are equal.
+template <int KCAP>
+__device__ __forceinline__ void knn_write_row_ranked(const KnnList<KCAP>& l, const int32_t* tidx_g,
+                                                     int32_t* idx_out, float* d2_out, int64_t row) {
+    const float* kd2 = l.kd2;
+    int32_t* kidx = l.kidx;
+    const int lane = l.lane, count = l.st.count;
+    for (int t = 0; t < count; ++t) {
+        const int32_t j = kidx[t * 64 + lane];
+        kidx[t * 64 + lane] = tidx_g[j];
+    }
+    for (int a = 0; a < count; ++a) {
+        const float dv = kd2[a * 64 + lane];
+        int rank = 0, same = 0;
+        for (int b = 0; b < count; ++b) {
+            const float db = kd2[b * 64 + lane];
+            rank += (db < dv) ? 1 : 0;
+            same += (db == dv) ? 1 : 0;
+        }
+        const int32_t iv = kidx[a * 64 + lane];
+        if (same > 1) {
+            for (int b = 0; b < count; ++b)
+                if (b != a && kd2[b * 64 + lane] == dv && kidx[b * 64 + lane] < iv) ++rank;
+        }
+        idx_out[row + rank] = iv;
+        d2_out[row + rank] = dv;
+    }
+    for (int t = count; t < l.k; ++t) {
+        idx_out[row + t] = -1;
+        d2_out[row + t] = INFINITY;
+    }
+}
+
+// Small lists (32 slots): sorted in registers by a 32-input bitonic network, unused slots last.
+template <int KCAP>
+__device__ __forceinline__ void knn_write_row_sorted(const KnnList<KCAP>& l, const int32_t* tidx_g,
+                                                     int32_t* idx_out, float* d2_out, int64_t row) {
+    static_assert(KCAP == kMaxKnn, "the network sorts 32 slots");
     float v[kMaxKnn];
     int32_t p[kMaxKnn];
 #pragma unroll
     for (int t = 0; t < kMaxKnn; ++t) {
         v[t] = INFINITY;
         p[t] = 0x7fffffff;
-        if (t < st.count) {
-            const int32_t j = kidx[t * 64 + lane];
-            v[t] = kd2[t * 64 + lane];
+        if (t < l.st.count) {
+            const int32_t j = l.kidx[t * 64 + l.lane];
+            v[t] = l.kd2[t * 64 + l.lane];
             p[t] = tidx_g[j];
         }
     }
@@ -728,31 +568,134 @@ __global__ __launch_bounds__(knn_waves(KCAP) * 64) void knn_search_kernel(
         for (int jj = kk >> 1; jj > 0; jj >>= 1)
 #pragma unroll
             for (int t = 0; t < kMaxKnn; ++t) {
-                const int l = t ^ jj;
-                if (l > t) {
+                const int u = t ^ jj;
+                if (u > t) {
                     const bool asc = (t & kk) == 0;
-                    const bool gt = (v[t] > v[l]) || (v[t] == v[l] && p[t] > p[l]);
+                    const bool gt = (v[t] > v[u]) || (v[t] == v[u] && p[t] > p[u]);
                     if (gt == asc) {
                         const float tv = v[t];
-                        v[t] = v[l];
-                        v[l] = tv;
+                        v[t] = v[u];
+                        v[u] = tv;
                         const int32_t tp = p[t];
-                        p[t] = p[l];
-                        p[l] = tp;
+                        p[t] = p[u];
+                        p[u] = tp;
                     }
                 }
             }
 #pragma unroll
     for (int t = 0; t < kMaxKnn; ++t)
-        if (t < k) {
-            const bool have = t < st.count;
+        if (t < l.k) {
+            const bool have = t < l.st.count;
             idx_out[row + t] = have ? p[t] : -1;
             d2_out[row + t] = have ? v[t] : INFINITY;
         }
-    }
-    if (found) atomicAdd(found, (unsigned long long)st.count);
-    }();
-    knn_row_release(slab, row);
+}
+
+// ---- knn::KDTreeFlann::SearchKNN / SearchRadius for arbitrary queries ---------------------
+// (knn/kdtree_flann.inl:46-122: FLANN knnSearch / radiusSearch with sorted results).
+// A wave owns 64 Morton-consecutive QUERIES (staged like the ICP source); candidates live
+// in the same LDS columns as above, the walk is top-down from the root (no seeds: a query
+// need not be near any particular leaf), and at the end every lane writes its row [k] of
+// indices / squared distances, sorted and padded with -1 / +inf, at the query's ORIGINAL index.
+template <int KCAP = kMaxKnn>
+__global__ __launch_bounds__(64) void knn_search_kernel(
+        const float* __restrict__ records_g, const float* __restrict__ tblk_g, const int32_t* __restrict__ tidx_g,
+        uint32_t leaf_first, const float* __restrict__ qx_g, const float* __restrict__ qy_g, const float* __restrict__ qz_g,
+        const int32_t* __restrict__ qperm, int nq, int nleaf, int k, float r2,
+        int32_t* __restrict__ idx_out, float* __restrict__ d2_out, unsigned long long* __restrict__ found,
+        uint32_t nblocks, KnnSlab slab) {
+    knn_wave<KCAP>(nblocks, slab, [&](uint32_t pkt, float* kd2, int32_t* kidx) {
+        const int64_t i = (int64_t)pkt * 64 + lane_id();
+        const bool valid = i < nq;
+        float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+        if (valid) {
+            qx = qx_g[i];
+            qy = qy_g[i];
+            qz = qz_g[i];
+        }
+        KnnList<KCAP> l(kd2, kidx, k, (valid && k > 0) ? r2 : -1.0f);  // r2 = +inf: plain k-NN
+
+        // ---- A: a first bound.  A plain k-NN query starts with an infinite search cube, and a
+        // depth-first walk in child order would wade through the whole tree before the k-th
+        // distance means anything (measured: 2.8 s for 2M queries).  So every LANE first descends
+        // greedily on its own -- at each record into the child whose box is nearest (Linf) to its
+        // query; neighbouring lanes read the same records, so the divergent loads hit L1 -- and
+        // offers itself the 64 slots under the leaf-level node it arrives at: the k-th distance
+        // among a query's own 64 nearest-cell points is within a small factor of the true one.
+        // (A packet-level seed -- one descent for the
+        // packet's first query -- left the far lanes with a packet-diameter bound and the walk
+        // 10x wider: 92 ms instead of ~10 for 2M queries at k = 8.)  Each lane skips its own
+        // seeded leaves [seed_lo, seed_hi) in the walk below.
+        uint32_t seed_lo = 0u, seed_hi = 0u;
+        if (k > 0) {
+            uint32_t id = 1u;
+            int32_t off = -1;
+            while (id < leaf_first) {  // same depth for every lane
+                const float4* rec = reinterpret_cast<const float4*>(records_g + ((size_t)(id + (uint32_t)off) << 6));
+                float w[48];
+#pragma unroll
+                for (int e = 0; e < 12; ++e) {
+                    const float4 f = rec[e];
+                    w[4 * e] = f.x;
+                    w[4 * e + 1] = f.y;
+                    w[4 * e + 2] = f.z;
+                    w[4 * e + 3] = f.w;
+                }
+                float bestd = INFINITY;
+                int bestc = 0;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) {
+                    const float* b = w + (c >> 1) * kPairStride + (c & 1);
+                    // max over the axes of the distance to the slab; an empty (inverted) box gives +inf
+                    const float dx = fmaxf(fmaxf(b[0] - qx, qx - b[6]), 0.0f);
+                    const float dy = fmaxf(fmaxf(b[2] - qy, qy - b[8]), 0.0f);
+                    const float dz = fmaxf(fmaxf(b[4] - qz, qz - b[10]), 0.0f);
+                    const float d = fmaxf(dx, fmaxf(dy, dz));
+                    if (d < bestd) {
+                        bestd = d;
+                        bestc = c;
+                    }
+                }
+                id = id * 8u + (uint32_t)bestc;
+                off = off * 8 + 1;
+            }
+            const uint32_t own = (id - leaf_first) * 8u;  // first leaf under the node reached
+            const uint32_t nleaf_u = (uint32_t)nleaf;
+            // leaf lb + s of every lane that takes part, s = 0..7
+            auto offer_leaves = [&](uint32_t lb, bool take) {
+                if (__ballot(take) == 0ull) return;
+                for (uint32_t s = 0; s < 8u; ++s) knn_offer_leaf(tblk_g, lb + s, take && lb + s < nleaf_u, qx, qy, qz, l);
+            };
+            offer_leaves(own, valid);
+            seed_lo = own;
+            seed_hi = own + 8u;
+            // Lanes still short of k candidates (a node in a group's padded tail can hold any number
+            // of real points, down to one) widen to the node's parent, grandparent, ... -- without
+            // this their bound stays infinite and the walk below offers them the whole cloud (a
+            // handful of such packets cost 90 ms at k = 4).
+            const uint32_t all = leaf_first * 8u;  // leaves under the root
+            for (uint32_t nspan = 64u; nspan <= all; nspan *= 8u) {
+                const bool more = valid && l.st.count < k && l.st.worst == INFINITY;  // (a radius search is bounded anyway)
+                if (__ballot(more) == 0ull) break;
+                const uint32_t nlo = own & ~(nspan - 1u);
+                for (uint32_t s = 0; s < nspan; s += 8u) {
+                    const uint32_t lb = nlo + s;
+                    offer_leaves(lb, more && (lb < seed_lo || lb >= seed_hi));
+                }
+                if (more) {
+                    seed_lo = nlo;
+                    seed_hi = nlo + nspan;
+                }
+            }
+        }
+        knn_walk<false>(records_g, tblk_g, leaf_first, valid && k > 0, qx, qy, qz, seed_lo, seed_hi, l);
+
+        if (!valid) return;
+        const int64_t row = (int64_t)qperm[i] * k;
+        if constexpr (KCAP > kMaxKnn) knn_write_row_ranked(l, tidx_g, idx_out, d2_out, row);
+        else knn_write_row_sorted(l, tidx_g, idx_out, d2_out, row);
+        if (found) atomicAdd(found, (unsigned long long)l.st.count);
+    });
 }
 
 }  // namespace mi

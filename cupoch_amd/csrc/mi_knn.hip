@@ -16,16 +16,45 @@ template <class K>
 int knn_slab(mi_icp_ctx* c, K kernel, int cap, KnnSlab* out) {
     static const int ncu = [] { hipDeviceProp_t p; int dev = 0; (void)hipGetDevice(&dev); return (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }();
     int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, knn_waves(cap) * 64, 0) != hipSuccess || occ <= 0) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 64, 0) != hipSuccess || occ <= 0) {
         (void)hipGetLastError();
         occ = std::min(32, (160 * 1024) / (cap * 64 * 4));  // one wave per workgroup; the lists' distances fill the LDS
     }
-    const uint32_t per_xcc = (uint32_t)(((int64_t)occ * knn_waves(cap) * ((ncu + 7) / 8) * 5 + 3) / 4 + 8);
+    const uint32_t per_xcc = (uint32_t)(((int64_t)occ * ((ncu + 7) / 8) * 5 + 3) / 4 + 8);
     TRY(ensure(c, c->knn_idx, (size_t)8 * per_xcc * cap * 64, &out->rows));
     TRY(ensure(c, c->knn_flags, (size_t)8 * per_xcc, &out->flags));
     HIPCHK(c, hipMemsetAsync(out->flags, 0, (size_t)8 * per_xcc * sizeof(uint32_t), c->stream));
     out->per_xcc = per_xcc;
     return MI_ICP_OK;
+}
+
+template <int KCAP>
+using Cap = std::integral_constant<int, KCAP>;
+
+// Launches one k-NN kernel over `nblocks` packets (one 64-lane workgroup each, the grid rounded up to whole rounds of
+// the 8 XCDs for xcd_remap) in the instantiation for k's capacity, `pick(Cap<KCAP>())`, with a slab sized for that
+// same instantiation; args...: the kernel's arguments ahead of nblocks and the slab.
+template <class Pick, class... Args>
+int knn_launch(mi_icp_ctx* c, int k, uint32_t nblocks, Pick pick, Args... args) {
+    const int cap = knn_capacity(k);
+    auto go = [&](auto kernel) -> int {
+        KnnSlab slab;
+        TRY(knn_slab(c, kernel, cap, &slab));
+        kernel<<<((nblocks + 7u) / 8u) * 8u, 64, 0, c->stream>>>(args..., nblocks, slab);
+        KCHK(c);
+        return MI_ICP_OK;
+    };
+    if (cap == kMaxKnn) return go(pick(Cap<kMaxKnn>()));
+    if (cap == kMaxKnnMid) return go(pick(Cap<kMaxKnnMid>()));
+    return go(pick(Cap<kMaxKnnBig>()));
+}
+
+// knn_normals_kernel<OUT> over the target's leaves: EstimateNormals (OUT = 0) or the colour gradients (OUT = 1)
+template <int OUT>
+int launch_knn_normals(mi_icp_ctx* c, int k, float r2, float* out, const float4* tnrm, float4* tgrad) {
+    return knn_launch(c, k, (uint32_t)((c->nleaf + 7) / 8), [](auto kc) { return knn_normals_kernel<OUT, decltype(kc)::value>; },
+                      (const float*)c->nodes.p, (const float*)c->tblk.p, (const int32_t*)c->tidx.p, c->leaf_first, c->nts,
+                      c->nleaf, k, r2, out, tnrm, tgrad);
 }
 
 }  // namespace
@@ -51,20 +80,7 @@ static int estimate_normals_impl(mi_icp_ctx* c, const float* xyz, int64_t n, int
         TRY(mi_icp_set_target(a, xyz, nullptr, nullptr, n, mem_kind));
         float* dn = normals;
         if (mem_kind == MI_ICP_HOST) TRY(ensure(a, a->stage[1], (size_t)n * 3, &dn));
-        const int cap = knn_capacity(knn), waves = knn_waves(cap);
-        const uint32_t nblocks = (uint32_t)((a->nleaf + waves * 8 - 1) / (waves * 8));
-        const uint32_t grid = ((nblocks + 7u) / 8u) * 8u;
-        KnnSlab slab;
-        if (cap == kMaxKnn) TRY(knn_slab(a, knn_normals_kernel<0, kMaxKnn>, cap, &slab));
-        else if (cap == kMaxKnnMid) TRY(knn_slab(a, knn_normals_kernel<0, kMaxKnnMid>, cap, &slab));
-        else TRY(knn_slab(a, knn_normals_kernel<0, kMaxKnnBig>, cap, &slab));
-#define MI_NRM_ARGS (const float*)a->nodes.p, (const float*)a->tblk.p, (const int32_t*)a->tidx.p, a->leaf_first, a->nts, a->nleaf, knn, r2, nblocks, \
-                    dn, nullptr, nullptr, slab
-        if (cap == kMaxKnn) knn_normals_kernel<0, kMaxKnn><<<grid, waves * 64, 0, a->stream>>>(MI_NRM_ARGS);
-        else if (cap == kMaxKnnMid) knn_normals_kernel<0, kMaxKnnMid><<<grid, waves * 64, 0, a->stream>>>(MI_NRM_ARGS);
-        else knn_normals_kernel<0, kMaxKnnBig><<<grid, waves * 64, 0, a->stream>>>(MI_NRM_ARGS);
-#undef MI_NRM_ARGS
-        KCHK(a);
+        TRY(launch_knn_normals<0>(a, knn, r2, dn, nullptr, nullptr));
         if (mem_kind == MI_ICP_HOST) TRY(from_device(a, (const float*)dn, normals, (size_t)n * 3, mem_kind));
         HIPCHK(a, hipStreamSynchronize(a->stream));
         return MI_ICP_OK;
@@ -104,41 +120,19 @@ int mi_icp_search_knn(mi_icp_ctx* c, const float* queries, int64_t nq, int knn, 
         TRY(ensure(c, c->stage[5], (size_t)nq * knn, &d_d2));
     }
     unsigned long long* cnt;
-    TRY(ensure(c, c->flags, 16, (unsigned long long**)&cnt));
-    HIPCHK(c, hipMemsetAsync(cnt, 0, 16 * sizeof(unsigned long long), c->stream));
-    const uint32_t npackets = (uint32_t)((nq + 63) / 64);
-    const int cap = knn_capacity(knn), waves = knn_waves(cap);
-    const uint32_t nblocks = (npackets + waves - 1) / waves;
-    const uint32_t grid = ((nblocks + 7u) / 8u) * 8u;
-    KnnSlab slab;
-    if (cap == kMaxKnn) TRY(knn_slab(c, knn_search_kernel<kMaxKnn>, cap, &slab));
-    else if (cap == kMaxKnnMid) TRY(knn_slab(c, knn_search_kernel<kMaxKnnMid>, cap, &slab));
-    else TRY(knn_slab(c, knn_search_kernel<kMaxKnnBig>, cap, &slab));
-#define MI_KNN_ARGS (const float*)c->nodes.p, (const float*)c->tblk.p, (const int32_t*)c->tidx.p, c->leaf_first, (const float*)c->sx.p, \
-                    (const float*)c->sy.p, (const float*)c->sz.p, (const int32_t*)c->sperm.p, (int)nq, c->nleaf, knn, \
-                    radius > 0.0f ? radius * radius : INFINITY, nblocks, d_idx, d_d2, cnt, slab
-    if (cap == kMaxKnn) knn_search_kernel<kMaxKnn><<<grid, waves * 64, 0, c->stream>>>(MI_KNN_ARGS);
-    else if (cap == kMaxKnnMid) knn_search_kernel<kMaxKnnMid><<<grid, waves * 64, 0, c->stream>>>(MI_KNN_ARGS);
-    else knn_search_kernel<kMaxKnnBig><<<grid, waves * 64, 0, c->stream>>>(MI_KNN_ARGS);
-#undef MI_KNN_ARGS
-    KCHK(c);
+    TRY(ensure(c, c->flags, 1, (unsigned long long**)&cnt));
+    HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(unsigned long long), c->stream));
+    TRY(knn_launch(c, knn, (uint32_t)((nq + 63) / 64), [](auto kc) { return knn_search_kernel<decltype(kc)::value>; },
+                   (const float*)c->nodes.p, (const float*)c->tblk.p, (const int32_t*)c->tidx.p, c->leaf_first,
+                   (const float*)c->sx.p, (const float*)c->sy.p, (const float*)c->sz.p, (const int32_t*)c->sperm.p, (int)nq,
+                   c->nleaf, knn, radius > 0.0f ? radius * radius : INFINITY, d_idx, d_d2, cnt));
     if (mem_kind == MI_ICP_HOST) {
         TRY(from_device(c, (const int32_t*)d_idx, idx_out, (size_t)nq * knn, mem_kind));
         TRY(from_device(c, (const float*)d_d2, d2_out, (size_t)nq * knn, mem_kind));
     }
-    HIPCHK(c, hipMemcpyAsync(c->sys_host, cnt, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->sys_host, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (found) *found = (int64_t) * reinterpret_cast<unsigned long long*>(c->sys_host);
-#ifdef MI_KNN_CENSUS
-    {   // (a census build: scripts/dev/knn_census.sh)
-        const unsigned long long* u = reinterpret_cast<const unsigned long long*>(c->sys_host);
-        const double* d = reinterpret_cast<const double*>(c->sys_host);
-        const double p = (double)std::max<unsigned long long>(u[6], 1ull), ln = std::max(d[9], 1.0);
-        std::fprintf(stderr, "knn census k=%d: per packet: leaves offered %.1f, candidates some lane accepted %.1f (%.1f %% of the offered), lane-accepts %.1f, "
-                     "leaves after which a cube shrank %.1f, records %.1f; mean bound before the walk %.3g (packet max %.3g, min %.3g), after %.3g; lanes that walked alone %.2f\n",
-                     knn, u[1] / p, u[2] / p, 100.0 * u[2] / std::max<double>(8.0 * u[1], 1.0), u[3] / p, u[4] / p, u[5] / p, d[7] / ln, d[10] / p, d[11] / p, d[8] / ln, u[12] / p);
-    }
-#endif
     return MI_ICP_OK;
 }
 
@@ -155,20 +149,7 @@ int mi_icp_compute_color_gradients(mi_icp_ctx* c, float radius, int max_nn, floa
     TRY(ensure(c, c->tgrad, (size_t)c->nts, &tgrad));
     float* dg = gradients_out;
     if (gradients_out && mem_kind == MI_ICP_HOST) TRY(ensure(c, c->stage[1], (size_t)n * 3, &dg));
-    const int cap = knn_capacity(max_nn), waves = knn_waves(cap);
-    const uint32_t nblocks = (uint32_t)((c->nleaf + waves * 8 - 1) / (waves * 8));
-    const uint32_t grid = ((nblocks + 7u) / 8u) * 8u;
-    KnnSlab slab;
-    if (cap == kMaxKnn) TRY(knn_slab(c, knn_normals_kernel<1, kMaxKnn>, cap, &slab));
-    else if (cap == kMaxKnnMid) TRY(knn_slab(c, knn_normals_kernel<1, kMaxKnnMid>, cap, &slab));
-    else TRY(knn_slab(c, knn_normals_kernel<1, kMaxKnnBig>, cap, &slab));
-#define MI_GRAD_ARGS (const float*)c->nodes.p, (const float*)c->tblk.p, (const int32_t*)c->tidx.p, c->leaf_first, c->nts, c->nleaf, max_nn, \
-                     radius * radius, nblocks, dg, (const float4*)c->tnrm.p, tgrad, slab
-    if (cap == kMaxKnn) knn_normals_kernel<1, kMaxKnn><<<grid, waves * 64, 0, c->stream>>>(MI_GRAD_ARGS);
-    else if (cap == kMaxKnnMid) knn_normals_kernel<1, kMaxKnnMid><<<grid, waves * 64, 0, c->stream>>>(MI_GRAD_ARGS);
-    else knn_normals_kernel<1, kMaxKnnBig><<<grid, waves * 64, 0, c->stream>>>(MI_GRAD_ARGS);
-#undef MI_GRAD_ARGS
-    KCHK(c);
+    TRY(launch_knn_normals<1>(c, max_nn, radius * radius, dg, (const float4*)c->tnrm.p, tgrad));
     c->t_has_grad = true;
     if (gradients_out) {
         if (mem_kind == MI_ICP_HOST) TRY(from_device(c, (const float*)dg, gradients_out, (size_t)n * 3, mem_kind));

@@ -144,7 +144,7 @@ def test_outliers_around_a_dense_cloud_walk_alone(eng):
     the wave-uniform walk their cubes hold all of it and their packets were offered every point (EstimateNormals of
     2M + 1000 such points: 177 ms).  They leave their packets -- by their bounds (knn_walks_alone) or, where whole
     packets are like that, by the probe of the tree's upper levels (knn_packet_reaches_too_far) -- and walk alone
-    with L2 pruning (knn_normals.h knn_solo_walk): same rows as the oracle's, in a time of the usual order."""
+    with L2 pruning (knn_normals.h knn_walk, traverse.h solo_walk): same rows as the oracle's, in a time of the usual order."""
     import time
     rng = np.random.default_rng(123)
     dense = (rng.random((300_000, 3), dtype=np.float32) * np.float32(0.1)).astype(np.float32)
