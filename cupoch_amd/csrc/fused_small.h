@@ -10,7 +10,7 @@
 // last block totals the rows in a fixed order and takes the loop's step, reduce.h / loop.h).  Four packets
 // per workgroup; no occupancy bound to respect (the search body's 63 registers plus 30 fp64 sums), which
 // is why this is a kernel of its own and not a mode of nn_packet_kernel.
-// Same per-element arithmetic as reduce_pt2pl_kernel (the transformed point is the search's own, bit for
+// The rows are the reductions' own (reduce.h trec_gather, pt2pl_row; the transformed point is the search's own, bit for
 // bit); the summation order differs, so the sums agree to ~1e-15 relative, not bitwise.
 // EST = point-to-point (late in round 5): the wave's rows are {transformed point, matched point, d^2} and its lanes
 // total the Kabsch sums of reduce_kernel<point-to-point, 0> (sums of both, the nine products, d^2 twice, the count).
@@ -24,14 +24,15 @@ namespace mi {
 
 constexpr int kFusedPackets = kReduceThreads / 64;  // packets per workgroup
 
-// one evaluation + step; returns (to every thread of the block) whether this block was the one that stepped
+// one evaluation + step
 template <int EST>
-__device__ __forceinline__ bool icp_small_iteration_body(
+__global__ __launch_bounds__(kReduceThreads) void icp_small_iteration_kernel(
         const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int ns,
         const float* __restrict__ records_g, const float* __restrict__ tblk_g, const float* __restrict__ lreg_g,
         const float* __restrict__ halo_g, uint32_t leaf_first, float r2, uint32_t npackets, uint32_t nblocks,
         int32_t* __restrict__ nn_idx, uint32_t* __restrict__ want, const float* __restrict__ trec, DevLoop* __restrict__ loop,
         double* __restrict__ partial, uint32_t* __restrict__ ticket, double* __restrict__ out32) {
+    if (loop->done) return;  // (every wave of every workgroup alike)
     __shared__ PacketShared s_pk[kFusedPackets];
     const int wid = (int)(threadIdx.x >> 6);
     uint32_t logical;
@@ -48,7 +49,7 @@ __device__ __forceinline__ bool icp_small_iteration_body(
         (void)nn_packet_body<true, false>(s_pk[wid], packet, sx, sy, sz, ns, records_g, tblk_g, lreg_g, halo_g, leaf_first,
                                           none, loop, r2, nn_idx, nullptr, nullptr, want, r);
     }
-    // ---- this lane's row of the system (reduce_pt2pl_kernel's arithmetic): J[6], residual, d2 into LDS
+    // ---- this lane's row of the system (reduce.h pt2pl_row): J[6], residual, d2 into LDS
     // ([component][lane], component stride 65 floats: the sums below read one column per lane group without
     // bank conflicts)
     __shared__ float s_rows[kFusedPackets][8 * 65];
@@ -56,32 +57,23 @@ __device__ __forceinline__ bool icp_small_iteration_body(
     const int lane = lane_id();
     const bool have = r.valid && r.bidx >= 0;
     float row[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    float vt[3], nt[3];
     if (EST == kEstPt2Pl) {
-        const F3* rec = reinterpret_cast<const F3*>(trec + (int64_t)(have ? r.bidx : 0) * 6);
-        const F3 tp = rec[0], tn = rec[1];
+        trec_gather(trec, have ? r.bidx : 0, vt, nt);
         if (have) {
             const float vs[3] = {r.qx, r.qy, r.qz};
-            const float nt[3] = {tn.x, tn.y, tn.z};
-            const float d[3] = {vs[0] - tp.x, vs[1] - tp.y, vs[2] - tp.z};
-            cross3(vs, nt, row);
-            row[3] = nt[0];
-            row[4] = nt[1];
-            row[5] = nt[2];
-            row[6] = dot3(d, nt);
-            row[7] = sq3(d[0], d[1], d[2]);
+            pt2pl_row(vs, vt, nt, row, row[6], row[7]);
         }
-    } else {  // point-to-point: the matched point from its leaf line (reduce_kernel's gather)
-        const int32_t j = have ? r.bidx : 0;
-        const float* line = tblk_g + (int64_t)(j >> 3) * kLeafFloats + (j & 7);
-        const float tx = line[0], ty = line[8], tz = line[16];
+    } else {  // point-to-point: the matched point
+        leaf_point(tblk_g, have ? r.bidx : 0, vt);
         if (have) {
             row[0] = r.qx;
             row[1] = r.qy;
             row[2] = r.qz;
-            row[3] = tx;
-            row[4] = ty;
-            row[5] = tz;
-            row[7] = sq3(r.qx - tx, r.qy - ty, r.qz - tz);
+            row[3] = vt[0];
+            row[4] = vt[1];
+            row[5] = vt[2];
+            row[7] = sq3(r.qx - vt[0], r.qy - vt[1], r.qz - vt[2]);
         }
     }
     float* mine = s_rows[wid];
@@ -146,22 +138,6 @@ __device__ __forceinline__ bool icp_small_iteration_body(
         __shared__ DevLoop st_s;
         loop_step_block(loop, out32, 0, st_s, pre);
     }
-    return last;
 }
-
-#define MI_SMALL_ARGS sx, sy, sz, ns, records_g, tblk_g, lreg_g, halo_g, leaf_first, r2, npackets, nblocks, nn_idx, want, trec, loop, partial, ticket, out32
-
-template <int EST>
-__global__ __launch_bounds__(kReduceThreads) void icp_small_iteration_kernel(
-        const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int ns,
-        const float* __restrict__ records_g, const float* __restrict__ tblk_g, const float* __restrict__ lreg_g,
-        const float* __restrict__ halo_g, uint32_t leaf_first, float r2, uint32_t npackets, uint32_t nblocks,
-        int32_t* __restrict__ nn_idx, uint32_t* __restrict__ want, const float* __restrict__ trec, DevLoop* __restrict__ loop,
-        double* __restrict__ partial, uint32_t* __restrict__ ticket, double* __restrict__ out32) {
-    if (loop->done) return;  // (every wave of every workgroup alike)
-    (void)icp_small_iteration_body<EST>(MI_SMALL_ARGS);
-}
-
-#undef MI_SMALL_ARGS
 
 }  // namespace mi

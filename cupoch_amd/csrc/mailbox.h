@@ -59,14 +59,15 @@ struct MailBox {
 };
 constexpr size_t kMailInboxWords = (size_t)2 * kMailRanks * 64;
 
+// MailArgs{}: no mailbox (a single rank, or the ranks exchange through RCCL)
 struct MailArgs {
-    MailBox* box;       // device address of the registered host mapping; null: no mailbox
-    uint32_t* seq_dev;  // this rank's exchange counter (device memory, zeroed with the box)
-    int rank, nranks;
-    uint32_t spin_limit;
+    MailBox* box = nullptr;       // device address of the registered host mapping; null: no mailbox
+    uint32_t* seq_dev = nullptr;  // this rank's exchange counter (device memory, zeroed with the box)
+    int rank = 0, nranks = 1;
+    uint32_t spin_limit = 0u;
     // device mode (else null): this rank's inbox and the device addresses of all ranks' inboxes (its own included)
-    unsigned long long* inbox;
-    unsigned long long* const* peers;
+    unsigned long long* inbox = nullptr;
+    unsigned long long* const* peers = nullptr;
 };
 
 // One workgroup of whole waves (>= 64 threads).  sys: this rank's 32 sums (global or LDS, written before a

@@ -7,7 +7,6 @@
 // allocated inside the loop.  (The other translation units: csrc/ctx.h.)
 #include "ctx.h"
 #include "fused_small.h"
-#include "loop_step_kernel.h"
 #include "lzf.h"
 #include "nn_search.h"
 #include "reduce.h"
@@ -17,6 +16,14 @@ using namespace mi::eng;
 using host::Mat4;
 
 namespace mi {
+
+// loop.h's step as a kernel of its own: behind an in-library RCCL all-reduce, for the loops whose reduction does not
+// take the step itself, and to re-open a stepping loop
+static __global__ __launch_bounds__(kStepThreads) void loop_step_kernel(DevLoop* st_g, double* sys_in, int resume, MailArgs mail) {
+    __shared__ DevLoop st_s;
+    loop_step_block(st_g, sys_in, resume, st_s, StepPre{false, 0u, 0.0, 0u}, mail);
+}
+
 namespace eng {
 
 // elements per thread that travel together in reduce_pt2pl_kernel: 2 from kPt2PlTwoFrom source points up (round 6:
@@ -47,12 +54,40 @@ int launch_locate_by_planes(mi_icp_ctx* c, const Xform& X, const DevLoop* loop, 
     return MI_ICP_OK;
 }
 
+// The halos a search of the registration loop uses or, while there are none and none are on the way, where its lanes ask
+// for them (loop_run decides about building them).  MI_ICP_WAIT_LINKS (soak tests): every evaluation builds them and waits.
+static int loop_halo(mi_icp_ctx* c, bool* have_halo, uint32_t** want) {
+    static const bool always_wait = std::getenv("MI_ICP_WAIT_LINKS") != nullptr;
+    if (always_wait) {
+        TRY(start_links_async(c));
+        TRY(ensure_links(c));
+        c->halo_use = halo_poll(c);
+    }
+    *have_halo = c->halo_use;
+    *want = (!*have_halo && !c->links_inflight && c->links_allowed) ? (uint32_t*)c->halo_want.p : nullptr;
+    return MI_ICP_OK;
+}
+
+// a search's packets of 64 queries, `per_block` to a workgroup; the grid is rounded up to whole rounds of the 8 XCDs
+// (xcd_remap)
+struct PacketGrid { uint32_t npackets, nblocks, grid; };
+static PacketGrid packet_grid(int64_t ns, uint32_t per_block) {
+    const uint32_t npackets = (uint32_t)((ns + 63) / 64);
+    const uint32_t nblocks = (npackets + per_block - 1) / per_block;
+    return PacketGrid{npackets, nblocks, ((nblocks + 7u) / 8u) * 8u};
+}
+
+// nn_packet_kernel<SEED, STATS, STAMP>; STAMP (mi_icp_debug_set_step_stamps: the same kernel + two stamps per wave) on
+// the loop's seeded searches only
+static decltype(&nn_packet_kernel<false, false>) nn_kernel(bool seeded, bool stats, bool stamp) {
+    if (stats) return seeded ? nn_packet_kernel<true, true> : nn_packet_kernel<false, true>;
+    if (seeded && stamp) return nn_packet_kernel<true, false, true>;
+    return seeded ? nn_packet_kernel<true, false> : nn_packet_kernel<false, false>;
+}
+
 int launch_nn(mi_icp_ctx* c, const Mat4& T, float r2, bool seed, unsigned long long* stats, const DevLoop* loop) {
     if (c->ns <= 0) return MI_ICP_OK;
     int32_t* idx = (int32_t*)c->nn_idx.p;
-    // (inside the registration loop the distances are not stored: nothing reads them there, and every
-    // entry point that hands distances out runs its own search first)
-    float* d2 = (float*)c->nn_d2.p;
     if (c->nt <= 0) {
         fill_i32<<<blocks_for(c->ns), 256, 0, c->stream>>>(idx, c->ns, -1);
         KCHK(c);
@@ -62,49 +97,34 @@ int launch_nn(mi_icp_ctx* c, const Mat4& T, float r2, bool seed, unsigned long l
     }
     const Xform X = make_xform(T);
     const bool use_seed = seed && c->nn_valid;
-    // Inside a registration loop the halos are used if they are there and asked for if they are not (loop_run
-    // decides about building them); a one-shot seeded search builds them on the spot.
-    static const bool always_wait = std::getenv("MI_ICP_WAIT_LINKS") != nullptr;  // A/B switch (soak tests)
-    if (!loop && use_seed) TRY(ensure_links(c));
-    if (loop && always_wait) {
-        TRY(start_links_async(c));
-        TRY(ensure_links(c));
-        c->halo_use = halo_poll(c);
+    // Inside a registration loop the halos are used if they are there and asked for if they are not (loop_halo); a
+    // one-shot seeded search builds them on the spot.
+    bool have_halo;
+    uint32_t* want = nullptr;
+    if (loop) {
+        TRY(loop_halo(c, &have_halo, &want));
+    } else {
+        if (use_seed) TRY(ensure_links(c));
+        have_halo = halo_poll(c);
     }
-    const bool have_halo = loop ? c->halo_use : halo_poll(c);
     EvTimer t(c, 0, loop != nullptr);
-    const float* links = have_halo ? (const float*)c->thalo.p : nullptr;
-    uint32_t* want = (loop && !have_halo && !c->links_inflight && c->links_allowed) ? (uint32_t*)c->halo_want.p : nullptr;
-    bool self_seeded = false;
-    auto launch = [&](bool seeded, const float* sx, const float* sy, const float* sz, int64_t ns, int32_t* out_idx,
-                      float* out_d2) {
-        const uint32_t npackets = (uint32_t)((ns + 63) / 64);
-        const uint32_t nblocks = (npackets + kNNPacketsPerBlock - 1) / kNNPacketsPerBlock;
-        const uint32_t grid = ((nblocks + 7u) / 8u) * 8u;
-#define MI_NN_ARGS sx, sy, sz, (int)ns, (const float*)c->nodes.p, (const float*)c->tblk.p, (const float*)lreg_of(c), \
-                   links, c->leaf_first, X, loop, r2, nblocks, out_idx, out_d2, stats, want
-        if (stats) {
-            if (seeded) nn_packet_kernel<true, true><<<grid, kNNThreads, 0, c->stream>>>(MI_NN_ARGS);
-            else nn_packet_kernel<false, true><<<grid, kNNThreads, 0, c->stream>>>(MI_NN_ARGS);
-        } else if (seeded && loop && c->stamps_on) {  // (mi_icp_debug_set_step_stamps: the same kernel + two stamps per wave)
-            nn_packet_kernel<true, false, true><<<grid, kNNThreads, 0, c->stream>>>(MI_NN_ARGS);
-        } else {
-            if (seeded) nn_packet_kernel<true, false><<<grid, kNNThreads, 0, c->stream>>>(MI_NN_ARGS);
-            else nn_packet_kernel<false, false><<<grid, kNNThreads, 0, c->stream>>>(MI_NN_ARGS);
-        }
-#undef MI_NN_ARGS
-    };
     // No previous matches, but the target's halos are there: every query takes the leaf it falls into as its seed
     // (nn_search.h: locate_by_planes) and the seeded search does the rest.  (Without halos every lane whose seed
     // leaf's region does not finish it walks up from there -- under the displacement a registration starts with that
     // is most packets, and costs more than the walk from the root: 10M points 3.9 against 1.2 ms.)
+    bool self_seeded = false;
     if (!use_seed && !stats && c->ns >= coarse_first_min() && have_halo && planes_available(c)) {
         TRY(launch_locate_by_planes(c, X, loop, 0));
         self_seeded = true;
     }
     c->last_search_kind = use_seed ? 1 : (self_seeded ? 2 : 0);
-    launch(use_seed || self_seeded, (const float*)c->sx.p, (const float*)c->sy.p, (const float*)c->sz.p, c->ns, idx,
-           loop ? nullptr : d2);
+    const PacketGrid g = packet_grid(c->ns, kNNPacketsPerBlock);
+    // (inside the registration loop the distances are not stored: nothing reads them there, and every
+    // entry point that hands distances out runs its own search first)
+    nn_kernel(use_seed || self_seeded, stats != nullptr, loop && c->stamps_on)<<<g.grid, kNNThreads, 0, c->stream>>>(
+            (const float*)c->sx.p, (const float*)c->sy.p, (const float*)c->sz.p, (int)c->ns, (const float*)c->nodes.p,
+            (const float*)c->tblk.p, (const float*)lreg_of(c), have_halo ? (const float*)c->thalo.p : nullptr, c->leaf_first,
+            X, loop, r2, g.nblocks, idx, loop ? nullptr : (float*)c->nn_d2.p, stats, want);
     KCHK(c);
     c->nn_valid = true;
     c->n_user_pairs = -1;
@@ -145,12 +165,6 @@ int ensure_inverse_maps(mi_icp_ctx* c) {
     return MI_ICP_OK;
 }
 
-template <int EST, int MODE>
-void launch_reduce_t(mi_icp_ctx* c, const ReduceArgs& a, const Xform& X, const DevLoop* loop, int grid,
-                     double* partial, uint32_t* ticket, double* out) {
-    reduce_kernel<EST, MODE><<<grid, kReduceThreads, 0, c->stream>>>(a, X, loop, partial, ticket, out);
-}
-
 // elements per thread below which the reduction uses fewer than its 1024 blocks: 16 measured best on
 // 1.25M-5M point shards (fewer partials for the finishing block)
 constexpr int kReduceElemsPerThread = 16;
@@ -172,22 +186,53 @@ bool estimator_ready(const mi_icp_ctx* c, int est) {
     }
 }
 
+// The reduction's scratch: `rows` per-block partial rows, the 32 sums and the arrival ticket (zeroed at its first use;
+// the finishing block re-arms it).
+int reduce_buffers(mi_icp_ctx* c, size_t rows, double** partial, double** sys, uint32_t** ticket) {
+    TRY(ensure(c, c->partial, rows * kSysSize, partial));
+    TRY(ensure(c, c->sys_dev, kSysSize, sys));
+    if (!c->ticket.p) {
+        TRY(ensure(c, c->ticket, 64, ticket));
+        HIPCHK(c, hipMemsetAsync(*ticket, 0, 256, c->stream));
+    }
+    *ticket = (uint32_t*)c->ticket.p;
+    return MI_ICP_OK;
+}
+
+// The loop's own case: point-to-plane on nearest-neighbour matches with the target's 24-byte records
+// (reduce_pt2pl_kernel; every other case is reduce_kernel<EST, MODE>).
+bool pt2pl_reduction(const mi_icp_ctx* c, int est, int mode) {
+    return est == kEstPt2Pl && mode == 0 && estimator_ready(c, est) && c->n_user_pairs < 0 && c->t_has_rec &&
+           c->trec.p != nullptr && c->ns > 0 && c->nt > 0 && c->nn_valid;
+}
+
+// reduce_pt2pl_kernel<kU, STEP, STAMP>: STAMP (mi_icp_debug_set_step_stamps) only where the step rides along
+template <int kU>
+decltype(&reduce_pt2pl_kernel<kU, 0>) pt2pl_kernel(int step, bool stamp) {
+    if (step == 2) return stamp ? reduce_pt2pl_kernel<kU, 2, true> : reduce_pt2pl_kernel<kU, 2>;
+    if (step == 1) return stamp ? reduce_pt2pl_kernel<kU, 1, true> : reduce_pt2pl_kernel<kU, 1>;
+    return reduce_pt2pl_kernel<kU, 0>;
+}
+
+template <int MODE>
+decltype(&reduce_kernel<kEstP2P, MODE>) generic_reduce_kernel(int est) {
+    switch (est) {
+        case kEstP2P: return reduce_kernel<kEstP2P, MODE>;
+        case kEstPt2Pl: return reduce_kernel<kEstPt2Pl, MODE>;
+        case kEstSym: return reduce_kernel<kEstSym, MODE>;
+        case kEstColored: return reduce_kernel<kEstColored, MODE>;
+        case kEstGICP: return reduce_kernel<kEstGICP, MODE>;
+        default: return nullptr;
+    }
+}
+
 // Accumulate sys[32] on the device (into c->sys_dev) for the current correspondences.
 // When the estimator's inputs are missing only the statistics ([28], [29]) are formed.
-// fuse_step: the loop's step may ride in the reduction's finishing block (reduce.h STEP; single GPU only);
-// *stepped tells whether it did
-int launch_reduce(mi_icp_ctx* c, int est, int mode, const Mat4& T, DevLoop* loop = nullptr, bool fuse_step = false,
-                  bool* stepped = nullptr) {
-    if (stepped) *stepped = false;
+// step != 0 (step_in_reduction): the finishing block also takes the step of the loop `loop` (reduce.h STEP).
+int launch_reduce(mi_icp_ctx* c, int est, int mode, const Mat4& T, DevLoop* loop = nullptr, int step = 0) {
     double *partial, *sys;
     uint32_t* ticket;
-    TRY(ensure(c, c->partial, (size_t)kReduceBlocks * kSysSize, &partial));
-    TRY(ensure(c, c->sys_dev, kSysSize, &sys));
-    if (!c->ticket.p) {
-        TRY(ensure(c, c->ticket, 64, &ticket));
-        HIPCHK(c, hipMemsetAsync(ticket, 0, 256, c->stream));
-    }
-    ticket = (uint32_t*)c->ticket.p;
+    TRY(reduce_buffers(c, kReduceBlocks, &partial, &sys, &ticket));
     ReduceArgs a;
     a.sx = (const float*)c->sx.p;
     a.sy = (const float*)c->sy.p;
@@ -223,56 +268,26 @@ int launch_reduce(mi_icp_ctx* c, int est, int mode, const Mat4& T, DevLoop* loop
     const int grid = (int)std::max<int64_t>(
             wide, std::min<int64_t>(kReduceBlocks, blocks_for(a.count, kReduceThreads * kReduceElemsPerThread)));
     const Xform X = make_xform(T);
+    if (pt2pl_reduction(c, est, mode)) {
+        // four elements in flight per thread; at most 512 blocks (2 per CU): measured best on the 10M bench
+        // (256 / 512 / 1024 / 2048 blocks: 0.090 / 0.079 / 0.080 / 0.091 ms; 6 or 8 elements in flight on 512,
+        // 768 or 1024 blocks: 0.078 - 0.084 ms -- the kernel sits at ~5.1 TB/s of the ~6.3 a pure stream reaches)
+        const auto kernel = (a.count >= kPt2PlTwoFrom) ? pt2pl_kernel<2>(step, c->stamps_on) : pt2pl_kernel<4>(step, c->stamps_on);
+        EvTimer t(c, 1, loop != nullptr);
+        kernel<<<std::min(grid, 512), kReduceThreads, 0, c->stream>>>(a, X, loop, partial, ticket, sys,
+                                                                     (step == 2) ? mail_args(c) : MailArgs{});
+        KCHK(c);
+        return MI_ICP_OK;
+    }
     if (!estimator_ready(c, est)) {
         est = kEstP2P;
         mode = 1;
     }
-    if (est == kEstPt2Pl && mode == 0 && !a.pairs && a.trec && a.count > 0) {
-        // four elements in flight per thread; at most 512 blocks (2 per CU): measured best on the 10M bench
-        // (256 / 512 / 1024 / 2048 blocks: 0.090 / 0.079 / 0.080 / 0.091 ms; 6 or 8 elements in flight on 512,
-        // 768 or 1024 blocks: 0.078 - 0.084 ms -- the kernel sits at ~5.1 TB/s of the ~6.3 a pure stream reaches)
-        const int g2 = std::min(grid, 512);
-        EvTimer t(c, 1, loop != nullptr);
-        const MailArgs no_mail = {nullptr, nullptr, 0, 1, 0u, nullptr, nullptr};
-        const bool mail = mail_on(c);
-        const bool two = a.count >= kPt2PlTwoFrom;
-#define MI_PT2PL(STEP, STAMP, MAILARGS)                                                                                       \
-    do {                                                                                                                     \
-        if (two) reduce_pt2pl_kernel<2, STEP, STAMP><<<g2, kReduceThreads, 0, c->stream>>>(a, X, loop, partial, ticket, sys, MAILARGS); \
-        else reduce_pt2pl_kernel<4, STEP, STAMP><<<g2, kReduceThreads, 0, c->stream>>>(a, X, loop, partial, ticket, sys, MAILARGS);     \
-    } while (0)
-        if (fuse_step && loop && mail) {  // N ranks on one node: exchange + step in the finishing block
-            if (c->stamps_on) MI_PT2PL(2, true, mail_args(c));
-            else MI_PT2PL(2, false, mail_args(c));
-            if (stepped) *stepped = true;
-        } else if (fuse_step && loop && !c->comm && !c->mail_dev) {
-            if (c->stamps_on) MI_PT2PL(1, true, no_mail);
-            else MI_PT2PL(1, false, no_mail);
-            if (stepped) *stepped = true;
-        } else {
-            MI_PT2PL(0, false, no_mail);
-        }
-#undef MI_PT2PL
-        KCHK(c);
-        return MI_ICP_OK;
-    }
-    {
-        EvTimer t(c, 1, loop != nullptr);
-        switch (est * 2 + mode) {
-            case kEstP2P * 2 + 0: launch_reduce_t<kEstP2P, 0>(c, a, X, loop, grid, partial, ticket, sys); break;
-            case kEstP2P * 2 + 1: launch_reduce_t<kEstP2P, 1>(c, a, X, loop, grid, partial, ticket, sys); break;
-            case kEstPt2Pl * 2 + 0: launch_reduce_t<kEstPt2Pl, 0>(c, a, X, loop, grid, partial, ticket, sys); break;
-            case kEstPt2Pl * 2 + 1: launch_reduce_t<kEstPt2Pl, 1>(c, a, X, loop, grid, partial, ticket, sys); break;
-            case kEstSym * 2 + 0: launch_reduce_t<kEstSym, 0>(c, a, X, loop, grid, partial, ticket, sys); break;
-            case kEstSym * 2 + 1: launch_reduce_t<kEstSym, 1>(c, a, X, loop, grid, partial, ticket, sys); break;
-            case kEstColored * 2 + 0: launch_reduce_t<kEstColored, 0>(c, a, X, loop, grid, partial, ticket, sys); break;
-            case kEstColored * 2 + 1: launch_reduce_t<kEstColored, 1>(c, a, X, loop, grid, partial, ticket, sys); break;
-            case kEstGICP * 2 + 0: launch_reduce_t<kEstGICP, 0>(c, a, X, loop, grid, partial, ticket, sys); break;
-            case kEstGICP * 2 + 1: launch_reduce_t<kEstGICP, 1>(c, a, X, loop, grid, partial, ticket, sys); break;
-            default: return fail(c, MI_ICP_ERR_INVALID, "unknown estimation type %d", est);
-        }
-        KCHK(c);
-    }
+    const auto kernel = mode ? generic_reduce_kernel<1>(est) : generic_reduce_kernel<0>(est);
+    if (!kernel) return fail(c, MI_ICP_ERR_INVALID, "unknown estimation type %d", est);
+    EvTimer t(c, 1, loop != nullptr);
+    kernel<<<grid, kReduceThreads, 0, c->stream>>>(a, X, loop, partial, ticket, sys);
+    KCHK(c);
     return MI_ICP_OK;
 }
 
@@ -677,35 +692,30 @@ static bool fused_iteration_applies(const mi_icp_ctx* c, bool seed) {
 }
 
 static int launch_fused_iteration(mi_icp_ctx* c, DevLoop* d) {
-    static const bool always_wait = std::getenv("MI_ICP_WAIT_LINKS") != nullptr;  // A/B switch (soak tests)
-    if (always_wait) {
-        TRY(start_links_async(c));
-        TRY(ensure_links(c));
-        c->halo_use = halo_poll(c);
-    }
-    const bool have_halo = c->halo_use;
-    uint32_t* want = (!have_halo && !c->links_inflight && c->links_allowed) ? (uint32_t*)c->halo_want.p : nullptr;
-    const uint32_t npackets = (uint32_t)((c->ns + 63) / 64);
-    const uint32_t nblocks = (npackets + kFusedPackets - 1) / kFusedPackets;
-    const uint32_t grid = ((nblocks + 7u) / 8u) * 8u;
+    bool have_halo;
+    uint32_t* want;
+    TRY(loop_halo(c, &have_halo, &want));
+    const PacketGrid g = packet_grid(c->ns, kFusedPackets);
     double *partial, *sys;
-    TRY(ensure(c, c->partial, (size_t)std::max<uint32_t>(kReduceBlocks, grid) * kSysSize, &partial));
-    TRY(ensure(c, c->sys_dev, kSysSize, &sys));
-    if (!c->ticket.p) {
-        uint32_t* ticket;
-        TRY(ensure(c, c->ticket, 64, &ticket));
-        HIPCHK(c, hipMemsetAsync(ticket, 0, 256, c->stream));
-    }
+    uint32_t* ticket;
+    TRY(reduce_buffers(c, std::max<uint32_t>(kReduceBlocks, g.grid), &partial, &sys, &ticket));
     EvTimer t(c, 0, true);
-#define MI_FUSED_ARGS (const float*)c->sx.p, (const float*)c->sy.p, (const float*)c->sz.p, (int)c->ns, (const float*)c->nodes.p, \
-            (const float*)c->tblk.p, (const float*)lreg_of(c), have_halo ? (const float*)c->thalo.p : nullptr, c->leaf_first, \
-            c->loop_r2, npackets, nblocks, (int32_t*)c->nn_idx.p, want, (const float*)c->trec.p, d, partial, (uint32_t*)c->ticket.p, sys
-    if (c->loop_est == kEstP2P) icp_small_iteration_kernel<kEstP2P><<<grid, kReduceThreads, 0, c->stream>>>(MI_FUSED_ARGS);
-    else icp_small_iteration_kernel<kEstPt2Pl><<<grid, kReduceThreads, 0, c->stream>>>(MI_FUSED_ARGS);
-#undef MI_FUSED_ARGS
+    const auto kernel = (c->loop_est == kEstP2P) ? icp_small_iteration_kernel<kEstP2P> : icp_small_iteration_kernel<kEstPt2Pl>;
+    kernel<<<g.grid, kReduceThreads, 0, c->stream>>>(
+            (const float*)c->sx.p, (const float*)c->sy.p, (const float*)c->sz.p, (int)c->ns, (const float*)c->nodes.p,
+            (const float*)c->tblk.p, (const float*)lreg_of(c), have_halo ? (const float*)c->thalo.p : nullptr, c->leaf_first,
+            c->loop_r2, g.npackets, g.nblocks, (int32_t*)c->nn_idx.p, want, (const float*)c->trec.p, d, partial, ticket, sys);
     KCHK(c);
     c->last_search_kind = 1;
     return MI_ICP_OK;
+}
+
+// Where the loop's step is taken (known once the search has run): in the point-to-plane reduction's finishing block -- 1:
+// one GPU, 2: after the ranks' exchange through the mailbox -- or (0) in loop_step_kernel behind the reduction.
+static int step_in_reduction(const mi_icp_ctx* c) {
+    if (!pt2pl_reduction(c, c->loop_est, 0)) return 0;
+    if (mail_on(c)) return 2;
+    return (!c->comm && !c->mail_dev) ? 1 : 0;
 }
 
 // one evaluation: search under the loop's transform, reduction, all-reduce, step kernel
@@ -724,13 +734,12 @@ static int loop_enqueue_evaluation(mi_icp_ctx* c, bool seed) {
     if (fused_iteration_applies(c, seed)) return launch_fused_iteration(c, d);
     const Mat4 I = host::identity4();
     TRY(launch_nn(c, I, c->loop_r2, seed, nullptr, d));
-    bool stepped = false;
-    TRY(launch_reduce(c, c->loop_est, 0, I, d, true, &stepped));
-    if (stepped) return MI_ICP_OK;  // (point-to-plane: the reduction's last block exchanged the sums, if need be, and took the step)
+    const int step = step_in_reduction(c);
+    TRY(launch_reduce(c, c->loop_est, 0, I, d, step));
+    if (step) return MI_ICP_OK;
     const bool mail = mail_on(c);
     if (!mail) TRY(allreduce_system(c));  // (with a mailbox the step kernel starts with the exchange)
-    const MailArgs no_mail = {nullptr, nullptr, 0, 1, 0u, nullptr, nullptr};
-    loop_step_kernel<<<1, kStepThreads, 0, c->stream>>>(d, (double*)c->sys_dev.p, 0, mail ? mail_args(c) : no_mail);
+    loop_step_kernel<<<1, kStepThreads, 0, c->stream>>>(d, (double*)c->sys_dev.p, 0, mail ? mail_args(c) : MailArgs{});
     KCHK(c);
     return MI_ICP_OK;
 }
@@ -954,7 +963,7 @@ int mi_icp_icp_iterate(mi_icp_ctx* c, int n_iterations, mi_icp_result* out) {
         // re-open the loop for n more updates: the update for the next iteration is formed
         // from the system of the last evaluation (resume = step without stats/test)
         DevLoop* d = (DevLoop*)c->loop_dev.p;
-        loop_step_kernel<<<1, kStepThreads, 0, c->stream>>>(d, (double*)c->sys_dev.p, n_iterations, MailArgs{nullptr, nullptr, 0, 1, 0u, nullptr, nullptr});
+        loop_step_kernel<<<1, kStepThreads, 0, c->stream>>>(d, (double*)c->sys_dev.p, n_iterations, MailArgs{});
         KCHK(c);
         TRY(loop_run(c, n_iterations));
         // (a stepping loop never reaches mi_icp_registration_icp's exit: the halo build's candidate scratch -- 0.9 GB for

@@ -191,6 +191,202 @@ __device__ __forceinline__ bool block_finish(const double* acc, double* __restri
     return block_finish_rows(red, partial, ticket, out32, pre, pre_state, pre_mail_seq, stamps);
 }
 
+// ---- one correspondence's rows, one function per estimator (MODE as in reduce_kernel): vs the transformed source
+// point, vt its match, d = vs - vt.  reduce_kernel, reduce_pt2pl_kernel and fused_small.h all form their rows here.
+
+// the matched point vt from its leaf line (component stride 8)
+__device__ __forceinline__ void leaf_point(const float* tblk, int32_t j, float* vt) {
+    const float* line = tblk + (int64_t)(j >> 3) * kLeafFloats + (j & 7);
+    vt[0] = line[0];
+    vt[1] = line[8];
+    vt[2] = line[16];
+}
+
+// Point-to-plane: the match's point vt and normal nt in ONE 24-byte record (two 12-byte loads): the leaf line costs 16
+// bytes per slot for the 12 used, the float4 normal another 16 -- a quarter of the reduction's traffic that nothing reads.
+__device__ __forceinline__ void trec_gather(const float* trec, int32_t j, float* vt, float* nt) {
+    const F3* r = reinterpret_cast<const F3*>(trec + (int64_t)j * 6);
+    const F3 p = r[0], n = r[1];
+    vt[0] = p.x;
+    vt[1] = p.y;
+    vt[2] = p.z;
+    nt[0] = n.x;
+    nt[1] = n.y;
+    nt[2] = n.z;
+}
+
+// J = [vs x nt | nt], r = d . nt, d2 = |d|^2 with d = vs - vt
+__device__ __forceinline__ void pt2pl_row(const float* vs, const float* vt, const float* nt, float* J, float& r, float& d2) {
+    const float d[3] = {vs[0] - vt[0], vs[1] - vt[1], vs[2] - vt[2]};
+    d2 = sq3(d[0], d[1], d[2]);
+    r = dot3(d, nt);
+    cross3(vs, nt, J);
+    J[3] = nt[0];
+    J[4] = nt[1];
+    J[5] = nt[2];
+}
+
+template <int MODE>
+__device__ __forceinline__ void pt2pl_rows(double* acc, const float* vs, const float* vt, const float* nt) {
+    float J[6], r, d2;
+    pt2pl_row(vs, vt, nt, J, r, d2);
+    acc[28] += (double)d2;
+    acc[29] += 1.0;
+    if (MODE == 0) accum_row(acc, J, r);
+    else acc[27] += (double)(r * r);
+}
+
+template <int MODE>
+__device__ __forceinline__ void sym_rows(double* acc, const Xform& T, const ReduceArgs& a, int64_t i, int32_t j,
+                                         const float* vs, const float* vt, const float* d) {
+    const float4 t4 = a.tnrm[j];
+    const float4 s4 = a.snrm[i];
+    float ns[3];
+    rotate(T, s4.x, s4.y, s4.z, ns[0], ns[1], ns[2]);
+    const float n[3] = {ns[0] + t4.x, ns[1] + t4.y, ns[2] + t4.z};
+    const float r = dot3(d, n);
+    if (MODE == 0) {
+        const float s[3] = {vs[0] + vt[0], vs[1] + vt[1], vs[2] + vt[2]};
+        float J[6];
+        cross3(s, n, J);
+        J[3] = n[0];
+        J[4] = n[1];
+        J[5] = n[2];
+        accum_row(acc, J, r);
+    } else {
+        const float e2 = r * r;  // transformation_estimation.cu:92-104 squares twice
+        acc[27] += (double)(e2 * e2);
+    }
+}
+
+template <int MODE>
+__device__ __forceinline__ void colored_rows(double* acc, const ReduceArgs& a, int64_t i, int32_t j, const float* vs,
+                                             const float* vt, const float* d) {
+    const float4 n4 = a.tnrm[j];
+    const float4 g4 = a.tgrad[j];
+    const float nt[3] = {n4.x, n4.y, n4.z};
+    const float dit[3] = {g4.x, g4.y, g4.z};
+    const float it = n4.w, is = a.sint[i];
+    const float slg = a.sqrt_lambda_geometric, slp = a.sqrt_lambda_photometric;
+    const float dn = dot3(d, nt);
+    const float r0 = slg * dn;
+    // vs projected into vt's tangent plane, intensity predicted there
+    const float e[3] = {(vs[0] - dn * nt[0]) - vt[0], (vs[1] - dn * nt[1]) - vt[1], (vs[2] - dn * nt[2]) - vt[2]};
+    const float r1 = slp * (is - (dot3(dit, e) + it));
+    if (MODE == 0) {
+        float J[6], cr[3];
+        cross3(vs, nt, cr);
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            J[p] = slg * cr[p];
+            J[3 + p] = slg * nt[p];
+        }
+        accum_row(acc, J, r0);
+        float ditM[3];  // -dit^T (I - nt nt^T)
+#pragma unroll
+        for (int col = 0; col < 3; ++col) {
+            float s = 0.0f;
+#pragma unroll
+            for (int row = 0; row < 3; ++row) {
+                const float m = (row == col) ? (1.0f - nt[row] * nt[col]) : (-(nt[row] * nt[col]));
+                s += dit[row] * m;
+            }
+            ditM[col] = -s;
+        }
+        cross3(vs, ditM, cr);
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            J[p] = slp * cr[p];
+            J[3 + p] = slp * ditM[p];
+        }
+        accum_row(acc, J, r1);
+    } else {
+        acc[27] += (double)(r0 * r0 + r1 * r1);
+    }
+}
+
+template <int MODE>
+__device__ __forceinline__ void gicp_rows(double* acc, const Xform& T, const ReduceArgs& a, int64_t i, int32_t j,
+                                          const float* vs, const float* d) {
+    M3 Cs, M, Mi;
+    rotate_cov(T, a.scov + i * 9, Cs);
+    const float* Ct = a.tcov + (int64_t)j * 9;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) M.m[r][c] = Ct[c * 3 + r] + Cs.m[r][c];
+    inverse3(M, Mi);
+    // The reference's three rows are J = [W A | W], r = W d with W = SqrtMatrix3x3(Mi) symmetric
+    // (generalized_icp.cu:88-104), so what they add to the system is
+    //   J^T J = [A^T S A, A^T S; S A, S],  J^T r = [A^T S d; S d],  r^T r = d^T S d   with S = W W:
+    // no square root of a matrix is needed -- only what SqrtMatrix3x3 takes the root OF (gicp_weight:
+    // FastEigen3x3 scales its input by its largest coefficient and never scales back).  The closed-form
+    // eigen-solver (acosf / cosf, ten divisions) was two thirds of this functor's instructions, and the
+    // three rows' 81 fp64 multiply-adds become 28 additions.  S differs from the reference's W W by that
+    // solver's own rounding (~1e-6 of the largest entry); the parity tests hold GICP's system to 2e-5.
+    if (MODE == 0) {
+        float S[3][3];
+        gicp_weight(Mi, S);
+        const float x = vs[0], y = vs[1], z = vs[2];
+        const float Sd[3] = {S[0][0] * d[0] + S[0][1] * d[1] + S[0][2] * d[2],
+                             S[1][0] * d[0] + S[1][1] * d[1] + S[1][2] * d[2],
+                             S[2][0] * d[0] + S[2][1] * d[1] + S[2][2] * d[2]};
+        // P = S A, A = [0 z -y; -z 0 x; y -x 0];  Q = A^T P (symmetric)
+        float P[3][3], Q[3][3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            P[r][0] = S[r][2] * y - S[r][1] * z;
+            P[r][1] = S[r][0] * z - S[r][2] * x;
+            P[r][2] = S[r][1] * x - S[r][0] * y;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            Q[0][c] = y * P[2][c] - z * P[1][c];
+            Q[1][c] = z * P[0][c] - x * P[2][c];
+            Q[2][c] = x * P[1][c] - y * P[0][c];
+        }
+        const float g[3] = {y * Sd[2] - z * Sd[1], z * Sd[0] - x * Sd[2], x * Sd[1] - y * Sd[0]};
+        int k = 0;
+#pragma unroll
+        for (int p = 0; p < 6; ++p)
+#pragma unroll
+            for (int q = p; q < 6; ++q, ++k) {
+                const float v = (q < 3) ? Q[p][q] : ((p < 3) ? P[q - 3][p] : S[p - 3][q - 3]);
+                acc[k] += (double)v;
+            }
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            acc[21 + p] += (double)g[p];
+            acc[24 + p] += (double)Sd[p];
+        }
+        acc[27] += (double)dot3(d, Sd);
+    } else {  // ComputeRMSE (generalized_icp.cu:121-130): d^T W d -- the root itself; not on the loop's path
+        M3 W;
+        sqrt_matrix3x3(Mi, W);
+        float Wd[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) Wd[r] = W.m[r][0] * d[0] + W.m[r][1] * d[1] + W.m[r][2] * d[2];
+        acc[27] += (double)dot3(d, Wd);
+    }
+}
+
+// point-to-point: the Kabsch sums / the squared distance
+template <int MODE>
+__device__ __forceinline__ void p2p_rows(double* acc, const float* vs, const float* vt, const float* d) {
+    if (MODE == 0) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            acc[p] += (double)vs[p];
+            acc[3 + p] += (double)vt[p];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) acc[6 + p * 3 + q] = __builtin_fma((double)vs[p], (double)vt[q], acc[6 + p * 3 + q]);
+        }
+        acc[27] += (double)sq3(d[0], d[1], d[2]);
+    } else {
+        acc[27] += (double)dot3(d, d);
+    }
+}
+
 // MODE 0: accumulate the linear system; MODE 1: accumulate only the
 // estimator's ComputeRMSE error into acc[27] (+ [28],[29]).
 // partial: [gridDim.x][32] per-block sums; ticket: arrival counter (zero before the
@@ -251,186 +447,29 @@ __global__ __launch_bounds__(kReduceThreads) void reduce_kernel(ReduceArgs a, Xf
             npz = a.sz[kc];
         }
         if (j < 0) continue;
-        float vs[3], vt[3], nt_rec[3] = {0.0f, 0.0f, 0.0f};
+        float vs[3], vt[3];
         xform_point(T, spx, spy, spz, vs[0], vs[1], vs[2]);
-        if (EST == kEstPt2Pl && a.trec) {
-            // point and normal of the match in ONE 24-byte record (two 12-byte loads): the leaf line
-            // costs 16 bytes per slot for the 12 used, the float4 normal another 16 -- a quarter of
-            // this kernel's traffic that nothing reads
-            const F3* r = reinterpret_cast<const F3*>(a.trec + (int64_t)j * 6);
-            const F3 p3 = r[0], n3 = r[1];
-            vt[0] = p3.x;
-            vt[1] = p3.y;
-            vt[2] = p3.z;
-            nt_rec[0] = n3.x;
-            nt_rec[1] = n3.y;
-            nt_rec[2] = n3.z;
-        } else {
-            const float* line = a.tblk + (int64_t)(j >> 3) * kLeafFloats + (j & 7);
-            vt[0] = line[0];
-            vt[1] = line[8];
-            vt[2] = line[16];
-        }
-        const float d[3] = {vs[0] - vt[0], vs[1] - vt[1], vs[2] - vt[2]};
-        acc[28] += (double)sq3(d[0], d[1], d[2]);
-        acc[29] += 1.0;
-
         if (EST == kEstPt2Pl) {
-            float nt[3] = {nt_rec[0], nt_rec[1], nt_rec[2]};
-            if (!a.trec) {
+            float nt[3];
+            if (a.trec) {
+                trec_gather(a.trec, j, vt, nt);
+            } else {
+                leaf_point(a.tblk, j, vt);
                 const float4 n4 = a.tnrm[j];
                 nt[0] = n4.x;
                 nt[1] = n4.y;
                 nt[2] = n4.z;
             }
-            const float r = dot3(d, nt);
-            if (MODE == 0) {
-                float J[6];
-                cross3(vs, nt, J);
-                J[3] = nt[0];
-                J[4] = nt[1];
-                J[5] = nt[2];
-                accum_row(acc, J, r);
-            } else {
-                acc[27] += (double)(r * r);
-            }
-        } else if (EST == kEstSym) {
-            const float4 t4 = a.tnrm[j];
-            const float4 s4 = a.snrm[i];
-            float ns[3];
-            rotate(T, s4.x, s4.y, s4.z, ns[0], ns[1], ns[2]);
-            const float n[3] = {ns[0] + t4.x, ns[1] + t4.y, ns[2] + t4.z};
-            const float r = dot3(d, n);
-            if (MODE == 0) {
-                const float s[3] = {vs[0] + vt[0], vs[1] + vt[1], vs[2] + vt[2]};
-                float J[6];
-                cross3(s, n, J);
-                J[3] = n[0];
-                J[4] = n[1];
-                J[5] = n[2];
-                accum_row(acc, J, r);
-            } else {
-                const float e2 = r * r;  // transformation_estimation.cu:92-104 squares twice
-                acc[27] += (double)(e2 * e2);
-            }
-        } else if (EST == kEstColored) {
-            const float4 n4 = a.tnrm[j];
-            const float4 g4 = a.tgrad[j];
-            const float nt[3] = {n4.x, n4.y, n4.z};
-            const float dit[3] = {g4.x, g4.y, g4.z};
-            const float it = n4.w, is = a.sint[i];
-            const float slg = a.sqrt_lambda_geometric, slp = a.sqrt_lambda_photometric;
-            const float dn = dot3(d, nt);
-            const float r0 = slg * dn;
-            // vs projected into vt's tangent plane, intensity predicted there
-            const float e[3] = {(vs[0] - dn * nt[0]) - vt[0], (vs[1] - dn * nt[1]) - vt[1],
-                                (vs[2] - dn * nt[2]) - vt[2]};
-            const float r1 = slp * (is - (dot3(dit, e) + it));
-            if (MODE == 0) {
-                float J[6], cr[3];
-                cross3(vs, nt, cr);
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    J[p] = slg * cr[p];
-                    J[3 + p] = slg * nt[p];
-                }
-                accum_row(acc, J, r0);
-                float ditM[3];  // -dit^T (I - nt nt^T)
-#pragma unroll
-                for (int col = 0; col < 3; ++col) {
-                    float s = 0.0f;
-#pragma unroll
-                    for (int row = 0; row < 3; ++row) {
-                        const float m = (row == col) ? (1.0f - nt[row] * nt[col]) : (-(nt[row] * nt[col]));
-                        s += dit[row] * m;
-                    }
-                    ditM[col] = -s;
-                }
-                cross3(vs, ditM, cr);
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    J[p] = slp * cr[p];
-                    J[3 + p] = slp * ditM[p];
-                }
-                accum_row(acc, J, r1);
-            } else {
-                acc[27] += (double)(r0 * r0 + r1 * r1);
-            }
-        } else if (EST == kEstGICP) {
-            M3 Cs, M, Mi;
-            rotate_cov(T, a.scov + i * 9, Cs);
-            const float* Ct = a.tcov + (int64_t)j * 9;
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) M.m[r][c] = Ct[c * 3 + r] + Cs.m[r][c];
-            inverse3(M, Mi);
-            // The reference's three rows are J = [W A | W], r = W d with W = SqrtMatrix3x3(Mi) symmetric
-            // (generalized_icp.cu:88-104), so what they add to the system is
-            //   J^T J = [A^T S A, A^T S; S A, S],  J^T r = [A^T S d; S d],  r^T r = d^T S d   with S = W W:
-            // no square root of a matrix is needed -- only what SqrtMatrix3x3 takes the root OF (gicp_weight:
-            // FastEigen3x3 scales its input by its largest coefficient and never scales back).  The closed-form
-            // eigen-solver (acosf / cosf, ten divisions) was two thirds of this functor's instructions, and the
-            // three rows' 81 fp64 multiply-adds become 28 additions.  S differs from the reference's W W by that
-            // solver's own rounding (~1e-6 of the largest entry); the parity tests hold GICP's system to 2e-5.
-            if (MODE == 0) {
-                float S[3][3];
-                gicp_weight(Mi, S);
-                const float x = vs[0], y = vs[1], z = vs[2];
-                const float Sd[3] = {S[0][0] * d[0] + S[0][1] * d[1] + S[0][2] * d[2],
-                                     S[1][0] * d[0] + S[1][1] * d[1] + S[1][2] * d[2],
-                                     S[2][0] * d[0] + S[2][1] * d[1] + S[2][2] * d[2]};
-                // P = S A, A = [0 z -y; -z 0 x; y -x 0];  Q = A^T P (symmetric)
-                float P[3][3], Q[3][3];
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    P[r][0] = S[r][2] * y - S[r][1] * z;
-                    P[r][1] = S[r][0] * z - S[r][2] * x;
-                    P[r][2] = S[r][1] * x - S[r][0] * y;
-                }
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    Q[0][c] = y * P[2][c] - z * P[1][c];
-                    Q[1][c] = z * P[0][c] - x * P[2][c];
-                    Q[2][c] = x * P[1][c] - y * P[0][c];
-                }
-                const float g[3] = {y * Sd[2] - z * Sd[1], z * Sd[0] - x * Sd[2], x * Sd[1] - y * Sd[0]};
-                int k = 0;
-#pragma unroll
-                for (int p = 0; p < 6; ++p)
-#pragma unroll
-                    for (int q = p; q < 6; ++q, ++k) {
-                        const float v = (q < 3) ? Q[p][q] : ((p < 3) ? P[q - 3][p] : S[p - 3][q - 3]);
-                        acc[k] += (double)v;
-                    }
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    acc[21 + p] += (double)g[p];
-                    acc[24 + p] += (double)Sd[p];
-                }
-                acc[27] += (double)dot3(d, Sd);
-            } else {  // ComputeRMSE (generalized_icp.cu:121-130): d^T W d -- the root itself; not on the loop's path
-                M3 W;
-                sqrt_matrix3x3(Mi, W);
-                float Wd[3];
-#pragma unroll
-                for (int r = 0; r < 3; ++r) Wd[r] = W.m[r][0] * d[0] + W.m[r][1] * d[1] + W.m[r][2] * d[2];
-                acc[27] += (double)dot3(d, Wd);
-            }
-        } else {  // point-to-point: Kabsch sums / squared distance
-            if (MODE == 0) {
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    acc[p] += (double)vs[p];
-                    acc[3 + p] += (double)vt[p];
-#pragma unroll
-                    for (int q = 0; q < 3; ++q)
-                        acc[6 + p * 3 + q] = __builtin_fma((double)vs[p], (double)vt[q], acc[6 + p * 3 + q]);
-                }
-                acc[27] += (double)sq3(d[0], d[1], d[2]);
-            } else {
-                acc[27] += (double)dot3(d, d);
-            }
+            pt2pl_rows<MODE>(acc, vs, vt, nt);
+        } else {
+            leaf_point(a.tblk, j, vt);
+            const float d[3] = {vs[0] - vt[0], vs[1] - vt[1], vs[2] - vt[2]};
+            acc[28] += (double)sq3(d[0], d[1], d[2]);
+            acc[29] += 1.0;
+            if (EST == kEstSym) sym_rows<MODE>(acc, T, a, i, j, vs, vt, d);
+            else if (EST == kEstColored) colored_rows<MODE>(acc, a, i, j, vs, vt, d);
+            else if (EST == kEstGICP) gicp_rows<MODE>(acc, T, a, i, j, vs, d);
+            else p2p_rows<MODE>(acc, vs, vt, d);
         }
     }
 
@@ -444,8 +483,8 @@ __global__ __launch_bounds__(kReduceThreads) void reduce_kernel(ReduceArgs a, Xf
 // was 76 serial memory latencies.  Here kU elements per thread travel together: their coalesced
 // loads (index + source point) are issued back to back, then their gathers, then the arithmetic;
 // no branch sits between a load and its use (lanes past the end re-read element 0, unmatched points
-// re-read slot 0; both are masked out of the sums).  Same per-element arithmetic and the same
-// per-thread summation order as reduce_kernel<point-to-plane, 0> with the same grid.
+// re-read slot 0; both are masked out of the sums).  The rows are reduce_kernel's (trec_gather, pt2pl_rows), and
+// so is the per-thread summation order with the same grid.
 //
 // STEP == 1 (single-GPU loops): the finishing block also takes the loop's step -- statistics, convergence
 // test, 6x6 solve, T <- dT * T (loop.h: loop_step_body) -- instead of a launch of its own: one kernel
@@ -489,34 +528,20 @@ __global__ __launch_bounds__(kReduceThreads) void reduce_pt2pl_kernel(ReduceArgs
 #pragma unroll
     for (int k = 0; k < 30; ++k) acc[k] = 0.0;
     for (int64_t kb = k0; kb < a.count; kb += stride * kU) {
-        F3 tp[kU], tn[kU];
+        float vt[kU][3], nt[kU][3];
         bool have[kU];
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
             have[u] = (kb + (int64_t)u * stride) < a.count && j[u] >= 0;
-            const F3* r = reinterpret_cast<const F3*>(a.trec + (int64_t)(have[u] ? j[u] : 0) * 6);
-            tp[u] = r[0];
-            tn[u] = r[1];
+            trec_gather(a.trec, have[u] ? j[u] : 0, vt[u], nt[u]);
         }
         float vs[kU][3];
 #pragma unroll
         for (int u = 0; u < kU; ++u) xform_point(T, px[u], py[u], pz[u], vs[u][0], vs[u][1], vs[u][2]);
         fetch(kb + stride * kU);  // the next batch's coalesced loads overlap this batch's arithmetic
 #pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            if (!have[u]) continue;
-            const float nt[3] = {tn[u].x, tn[u].y, tn[u].z};
-            const float d[3] = {vs[u][0] - tp[u].x, vs[u][1] - tp[u].y, vs[u][2] - tp[u].z};
-            acc[28] += (double)sq3(d[0], d[1], d[2]);
-            acc[29] += 1.0;
-            const float r = dot3(d, nt);
-            float J[6];
-            cross3(vs[u], nt, J);
-            J[3] = nt[0];
-            J[4] = nt[1];
-            J[5] = nt[2];
-            accum_row(acc, J, r);
-        }
+        for (int u = 0; u < kU; ++u)
+            if (have[u]) pt2pl_rows<0>(acc, vs[u], vt[u], nt[u]);
     }
     // (the finishing block keeps its word of the loop state, its totals and -- STEP == 2 -- the exchange counter in
     // registers: loop.h StepPre)
@@ -526,8 +551,7 @@ __global__ __launch_bounds__(kReduceThreads) void reduce_pt2pl_kernel(ReduceArgs
     if (STEP && last) {
         __shared__ DevLoop st_s;
         if (STAMP && stamps && threadIdx.x == 0) stamps[4] = stamp_now();
-        loop_step_block(loop, out32, 0, st_s, pre, (STEP == 2) ? mail : MailArgs{nullptr, nullptr, 0, 1, 0u, nullptr, nullptr},
-                        STAMP ? stamps : nullptr);
+        loop_step_block(loop, out32, 0, st_s, pre, (STEP == 2) ? mail : MailArgs{}, STAMP ? stamps : nullptr);
     }
 }
 
