@@ -2,7 +2,7 @@
 """Headline benchmark: ICP iterations/sec (incl. kNN) of point-to-plane ICP on
 synthetic clouds (BASELINE.json metric; BASELINE.md section 3 inputs).
 
-    python bench.py [--gpus N --steps K --warmup W] [--points 10000000] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--points 10000000] [--dump-outputs DIR] [--full]
 
 One "step" = one iteration of registration::RegistrationICP's loop
 (registration.cu:155-163): 6x6 solve of the previous reduction -> compose T ->
@@ -17,10 +17,17 @@ is fixed -> "scaling": "strong".
 
 The timed region is K = --steps iterations between barriers; it is repeated --repeats times
 (default 7) within one run and `value` is K / the MEDIAN window (min / max are reported too).
-config.secondary carries what the headline does not show: the same loop on a noisy, partially
-overlapping source, a cold whole call (tree build + staging + 30 iterations), the unseeded first
-pass and the build times.  cpu_baseline.parity_sample compares the oracle's nearest neighbours
-for its sample with the engine's, bit for bit.
+
+A plain run does only what the headline needs: set up, warm up, time the windows, dump, print.
+--full also measures what the headline does not show, each after the timed windows (N > 1: the
+in-library RCCL beside the mailbox, before them, as part of the exchange's set-up):
+  roofline          the kernels' average durations from one further, event-bracketed window
+  config.secondary  the same loop on a noisy, partially overlapping source, a cold whole call
+                    (tree build + staging + 30 iterations), the unseeded first pass, the build
+                    times, VoxelDownSample, a transient, and strong_100M (the loop at 100M points)
+  cpu_baseline      the oracle on the host cores; its parity_sample compares the oracle's nearest
+                    neighbours for its sample with the engine's, bit for bit
+--no-secondary, --no-cpu-baseline and --big-points trim a --full run.
 
 Prints ONE JSON line on rank 0.  --dump-outputs DIR: rank 0 also writes what the last timed step computed as
 DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds run with the same arguments compare file for file.
@@ -127,6 +134,55 @@ def dump_outputs(out_dir, res, corr, n_source, global_ids=None):
               "correspondence_target_index": matched[pick].astype(np.float64)}
     for name, a in arrays.items():
         np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def roofline(eng, steps, elapsed, n, ns_local, nt, world, torch):
+    """--full: one further window of the same `steps` iterations with HIP events around every search / reduction launch
+    (the timed windows run without them); the search kernel's achieved bandwidth against HBM_PEAK_GBS, and the whole
+    iteration's from the timed windows' median `elapsed`."""
+    eng.set_profiling(True)
+    prof0 = eng.get_profile()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    eng.icp_iterate(steps)
+    torch.cuda.synchronize()
+    profiled_window = time.perf_counter() - t0
+    prof1 = eng.get_profile()
+    eng.set_profiling(False)
+
+    nn_launches = prof1["nn_launches"] - prof0["nn_launches"]
+    nn_ms = (prof1["nn_ms"] - prof0["nn_ms"]) / max(nn_launches, 1)
+    red_launches = prof1["reduce_launches"] - prof0["reduce_launches"]
+    # (sources of up to ~110k points run search + reduction + step as ONE kernel, timed under "search")
+    red_ms = (prof1["reduce_ms"] - prof0["reduce_ms"]) / red_launches if red_launches > 0 else None
+    alg_bytes = 20.0 * ns_local + 20.0 * nt       # SURVEY.md section 8(d): kNN kernel, per launch
+    achieved = alg_bytes / (nn_ms * 1e-3) / 1e9 if nn_ms > 0 else 0.0
+    # HBM bytes of one launch of the search kernel from the PMC passes (separate rocprofv3 runs of this
+    # very command, scripts/gpu_traffic.sh, with the FETCH_SIZE calibration applied); null when the
+    # committed measurement is for another size / GPU count
+    traffic, traffic_note = None, None
+    tpath = os.path.join(ROOT, "profiles", "nn_traffic.json")
+    if os.path.exists(tpath):
+        try:
+            tj = json.load(open(tpath))
+            if tj.get("points") == n and tj.get("n_gpus", 1) == world:
+                traffic = tj.get("hbm_bytes_per_launch")
+                traffic_note = tj.get("note")
+        except Exception:
+            traffic = None
+    return {"bound": "hbm", "kernel": "nn_packet_kernel",
+            "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 5),
+            "traffic": traffic, "traffic_source": traffic_note,
+            "algorithmic_bytes_per_launch": alg_bytes,
+            "kernel_ms_avg": round(nn_ms, 4), "reduce_ms_avg": (round(red_ms, 4) if red_ms is not None else None),
+            "kernel_ms_source": "HIP events on the engine's stream around every search / reduction launch "
+                                "of one further window of the same %d steps (%.4f ms per step with the events; "
+                                "the timed windows run without them)" % (steps, profiled_window / steps * 1e3),
+            # SURVEY.md section 8(d): a whole iteration moves 60 N_s + 20 N_t algorithmic bytes
+            "iteration": {"algorithmic_bytes": 60.0 * n + 20.0 * nt,
+                          "achieved": round((60.0 * n + 20.0 * nt) * steps / elapsed / 1e9, 2),
+                          "frac": round((60.0 * n + 20.0 * nt) * steps / elapsed / 1e9 / HBM_PEAK_GBS, 5)}}
 
 
 def secondary(eng, src, tgt, nrm, d_tgt, d_nrm, d_src, max_dist, n, torch, _lib):
@@ -413,10 +469,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--points", type=int, default=10_000_000)
     ap.add_argument("--repeats", type=int, default=7, help="timed windows of --steps iterations; value = median")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, config.secondary (incl. strong_100M), "
+                         "cpu_baseline and, with N > 1, the in-library RCCL beside the mailbox")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without config.secondary")
     ap.add_argument("--big-points", type=int, default=100_000_000,
-                    help="size of secondary.strong_100M (the strong-scaling bench again at a size an 8-way shard still fills); 0: skip")
+                    help="size of secondary.strong_100M in a --full run (the strong-scaling bench again at a size an "
+                         "8-way shard still fills); 0: skip")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed as DIR/<name>.npy (rank 0; at most ~16 MB)")
     args = ap.parse_args()
@@ -512,7 +572,7 @@ def main():
             eng.set_global_source_count(n)
             if rank == 0:
                 print("bench: falling back to a host-driven loop with torch.distributed all-reduce", file=sys.stderr)
-        elif (exchange.get("setup") == "mailbox" and os.environ.get("MI_ICP_BENCH_NO_RCCL") != "1" and
+        elif (args.full and exchange.get("setup") == "mailbox" and os.environ.get("MI_ICP_BENCH_NO_RCCL") != "1" and
               (not one_device or os.environ.get("MI_ICP_BENCH_RCCL_BESIDE") == "1")):
             # (MI_ICP_BENCH_RCCL_BESIDE=1 in a one-device rehearsal: RCCL refuses several ranks on one GPU -- the error path)
             exchange["rccl_in_library"] = rccl_beside(D, Engine, local, rank, world,
@@ -537,9 +597,9 @@ def main():
     # det_thresh <= 0: at this size the fp32 determinant of JtJ overflows and the
     # reference's default check would reject every solve
     # The timed windows run WITHOUT per-kernel HIP events (two event pairs per iteration cost
-    # ~12 us of a 0.18-ms step at N = 1 and far more of a sharded one); the kernels' average
-    # durations come from one further window of the same K steps, bracketed by events on the
-    # engine's stream, right after.
+    # ~12 us of a 0.18-ms step at N = 1 and far more of a sharded one); with --full the kernels'
+    # average durations come from one further window of the same K steps, bracketed by events on
+    # the engine's stream, right after (roofline).
     eng.set_profiling(False)
 
     if host_allreduce:
@@ -580,43 +640,14 @@ def main():
         windows.append(w)
     elapsed = float(np.median(windows))
     if args.dump_outputs and rank == 0:
-        # (before the profiled window below moves the loop on)
+        # (before the profiled window of --full moves the loop on)
         dump_outputs(args.dump_outputs, res, eng.get_correspondences(), len(src_local), mine if world > 1 else None)
     # did the loop start a build of the target's halos (2 ms of GPU time at 10M points) inside the timed windows?
     halo_builds_in_windows = eng.get_profile()["halo_builds_by_loops"] - halo_builds_before
-    eng.set_profiling(True)
-    prof0 = eng.get_profile()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    eng.icp_iterate(args.steps)
-    torch.cuda.synchronize()
-    profiled_window = time.perf_counter() - t0
-    prof1 = eng.get_profile()
-    eng.set_profiling(False)
+    roof = roofline(eng, args.steps, elapsed, n, len(src_local), len(tgt), world, torch) if args.full else None
 
     T = np.array(res.transformation, np.float32).reshape(4, 4).T
     err = float(np.linalg.norm(T - T_gt))
-    nn_launches = prof1["nn_launches"] - prof0["nn_launches"]
-    nn_ms = (prof1["nn_ms"] - prof0["nn_ms"]) / max(nn_launches, 1)
-    red_launches = prof1["reduce_launches"] - prof0["reduce_launches"]
-    # (sources of up to ~110k points run search + reduction + step as ONE kernel, timed under "search")
-    red_ms = (prof1["reduce_ms"] - prof0["reduce_ms"]) / red_launches if red_launches > 0 else None
-    ns_local, nt = len(src_local), len(tgt)
-    alg_bytes = 20.0 * ns_local + 20.0 * nt       # kNN kernel, per launch
-    achieved = alg_bytes / (nn_ms * 1e-3) / 1e9 if nn_ms > 0 else 0.0
-    # HBM bytes of one launch of the search kernel from the PMC passes (separate rocprofv3 runs of this
-    # very command, scripts/gpu_traffic.sh, with the FETCH_SIZE calibration applied); null when the
-    # committed measurement is for another size / GPU count
-    traffic, traffic_note = None, None
-    tpath = os.path.join(ROOT, "profiles", "nn_traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            if tj.get("points") == n and tj.get("n_gpus", 1) == world:
-                traffic = tj.get("hbm_bytes_per_launch")
-                traffic_note = tj.get("note")
-        except Exception:
-            traffic = None
 
     if rank == 0:
         out = {
@@ -651,29 +682,19 @@ def main():
                        "final_fitness": round(float(res.fitness), 6),
                        "final_rmse": float(res.inlier_rmse),
                        "T_error_fro_vs_ground_truth": err},
-            "roofline": {"bound": "hbm", "kernel": "nn_packet_kernel",
-                         "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": traffic, "traffic_source": traffic_note,
-                         "algorithmic_bytes_per_launch": alg_bytes,
-                         "kernel_ms_avg": round(nn_ms, 4), "reduce_ms_avg": (round(red_ms, 4) if red_ms is not None else None),
-                         "kernel_ms_source": "HIP events on the engine's stream around every search / reduction launch "
-                                             "of one further window of the same %d steps (%.4f ms per step with the events; "
-                                             "the timed windows run without them)" % (args.steps, profiled_window / args.steps * 1e3),
-                         # a whole iteration moves 60 N_s + 20 N_t algorithmic bytes
-                         "iteration": {"algorithmic_bytes": 60.0 * n + 20.0 * nt,
-                                       "achieved": round((60.0 * n + 20.0 * nt) * args.steps / elapsed / 1e9, 2),
-                                       "frac": round((60.0 * n + 20.0 * nt) * args.steps / elapsed / 1e9 / HBM_PEAK_GBS, 5)}},
         }
-        if world == 1 and not host_allreduce and not args.no_secondary:
+        if roof is not None:
+            out["roofline"] = roof
+        if args.full and world == 1 and not host_allreduce and not args.no_secondary:
             out["config"]["secondary"] = secondary(eng, src, tgt, nrm, d_tgt, d_nrm, d_src, max_dist, n, torch, _lib)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             eng.drop_seeds()
             gi, gd, _ = eng.search_radius_1nn(max_dist)        # the engine's neighbours under the identity
             out["cpu_baseline"] = cpu_baseline(src, tgt, nrm, max_dist, n, (gi, gd))
     # the strong-scaling bench once more at a size where an 8-way shard is still a large cloud (every rank takes part)
     big = None
-    if args.big_points > 0 and n == 10_000_000 and not args.no_secondary and not host_allreduce and not one_device:
+    if (args.full and args.big_points > 0 and n == 10_000_000 and not args.no_secondary and not host_allreduce
+            and not one_device):
         try:
             big = strong_big(eng, args.big_points, args.steps, args.warmup, rank, world, local, torch, dist, D, _lib)
         except Exception as e:   # noqa: BLE001 -- a secondary figure must not cost the headline

@@ -4,7 +4,7 @@ O=gpurun_out/ab_touch; mkdir -p $O
 one() {
   python scripts/measure_normals_10m.py 2>&1 | grep normals
   python scripts/measure_knn.py 30,0.0 100,0.0 2>&1 | grep '^{' | cut -c50-140
-  python bench.py --no-cpu-baseline 2>&1 | grep '^{"metric' | python -c "
+  python bench.py --full --no-cpu-baseline 2>&1 | grep '^{"metric' | python -c "
 import sys,json
 j=json.loads(sys.stdin.read()); s=j['config']['secondary']
 print('head', j['value'], 'nn', j['roofline']['kernel_ms_avg'], 'cold', s['cold_30_iteration_call_ms'], 'first', s['first_pass_ms'], 'first+halos', s['first_pass_with_halos_ms'], 'noisy.15 nn', s['noisy_sigma_0.15_nn_ms'], 'transient', s['transient_30_iteration_loop_ms'])"

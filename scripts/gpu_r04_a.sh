@@ -29,7 +29,7 @@ if has transient; then
   MI_ICP_LINKS_ASYNC=1 timeout 300 python scripts/dev/transient_one.py 2>&1 | grep loop | tee $O/transient_async.txt
 fi
 if has bench; then
-  timeout 900 python bench.py 2>&1 | grep '^{"metric' | tee $O/bench_10m.json | python scripts/benchline.py
+  timeout 900 python bench.py --full 2>&1 | grep '^{"metric' | tee $O/bench_10m.json | python scripts/benchline.py
   python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r04a/bench_10m.json"))

@@ -9,7 +9,7 @@ timeout 1500 python -m pytest tests -m gpu -q -x --timeout=900 > $O/t_gpu.log 2>
 timeout 300 python __graft_entry__.py smoke 2>&1 | grep -v amdgpu.ids | tail -2 | tee $O/smoke.log
 cp gpurun_out/fuzz_registration_rules.json $O/ 2>/dev/null
 timeout 900 python scripts/measure_reference_benchmark.py > $O/reference_benchmark_fragment.jsonl 2> $O/reference_benchmark.err; echo "refbench rc=$?"; cut -c1-400 $O/reference_benchmark_fragment.jsonl; tail -3 $O/reference_benchmark.err
-timeout 900 python bench.py 2> $O/bench.err | grep '^{"metric' | tee $O/bench_10m.json | python scripts/benchline.py
+timeout 900 python bench.py --full 2> $O/bench.err | grep '^{"metric' | tee $O/bench_10m.json | python scripts/benchline.py
 timeout 600 python scripts/measure_step_breakdown.py > $O/shard_step_breakdown.txt 2> $O/breakdown.err; echo "breakdown rc=$?"; cat $O/shard_step_breakdown.txt; tail -3 $O/breakdown.err
 timeout 600 python scripts/measure_shard.py 2>$O/shard.err | grep '^{' > $O/shard_emulation.jsonl; cat $O/shard_emulation.jsonl
 du -sh $O | tail -1

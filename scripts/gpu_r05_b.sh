@@ -6,10 +6,10 @@ mkdir -p $O
 export TMPDIR=/tmp
 python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1; echo "build rc=$?"
 timeout 1500 python -m pytest tests -m gpu -q -x --timeout=900 > $O/t_gpu.log 2>&1; echo "gpu tests rc=$?"; grep -E "passed|failed|Error|error" $O/t_gpu.log | tail -5
-timeout 600 python bench.py --no-cpu-baseline --big-points 0 2> $O/bench.err | grep '^{"metric' | tee $O/bench_new.json | python scripts/benchline.py
+timeout 600 python bench.py --full --no-cpu-baseline --big-points 0 2> $O/bench.err | grep '^{"metric' | tee $O/bench_new.json | python scripts/benchline.py
 python -c "
 import json;d=json.load(open('$O/bench_new.json'))['config']['secondary'];print({k:v for k,v in d.items() if not isinstance(v,(dict,str)) or 'kind' in k})"
-MI_ICP_NO_LOCATE_PLANES=1 timeout 600 python bench.py --no-cpu-baseline --big-points 0 2> $O/bench_old.err | grep '^{"metric' | tee $O/bench_old.json | python scripts/benchline.py
+MI_ICP_NO_LOCATE_PLANES=1 timeout 600 python bench.py --full --no-cpu-baseline --big-points 0 2> $O/bench_old.err | grep '^{"metric' | tee $O/bench_old.json | python scripts/benchline.py
 python -c "
 import json;d=json.load(open('$O/bench_old.json'))['config']['secondary'];print({k:v for k,v in d.items() if not isinstance(v,(dict,str)) or 'kind' in k})"
 timeout 300 python scripts/dev/transient_trace.py > $O/transient_trace_new.txt 2>&1; cut -c1-1500 $O/transient_trace_new.txt | tail -4

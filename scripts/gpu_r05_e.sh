@@ -4,7 +4,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1; echo "build rc=$?"
 timeout 600 python -m pytest tests/test_gpu_tree_invariants.py tests/test_gpu_robustness.py -m gpu -q --timeout=600 > $O/t_tree.log 2>&1; echo "tree tests rc=$?"; grep -E "passed|failed|^FAILED|assert" $O/t_tree.log | tail -8
-timeout 600 python bench.py --no-cpu-baseline --big-points 0 2> $O/bench.err | grep '^{"metric' | tee $O/bench.json | python scripts/benchline.py
+timeout 600 python bench.py --full --no-cpu-baseline --big-points 0 2> $O/bench.err | grep '^{"metric' | tee $O/bench.json | python scripts/benchline.py
 python -c "
 import json;d=json.load(open('$O/bench.json'))['config']['secondary'];print({k:v for k,v in d.items() if not isinstance(v,(dict,str)) or 'kind' in k})"
 cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/st_cold -o s -- python $GRAFT_REPO_ROOT/scripts/measure_latency.py 10000000 > $GRAFT_REPO_ROOT/$O/st_cold.log 2>&1; cd $GRAFT_REPO_ROOT

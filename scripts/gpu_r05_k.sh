@@ -11,5 +11,5 @@ for l in open("gpurun_out/r05k/shard.jsonl"):
     print({k: r[k] for k in r if k in ("ranks", "step_ms", "nn_ms", "reduce_ms", "speedup_vs_1")})
 PY
 timeout 600 python -m pytest tests/test_gpu_seeded.py tests/test_gpu_parity.py -m gpu -q --timeout=600 2>&1 | tail -3
-timeout 600 python bench.py --no-cpu-baseline --no-secondary 2>&1 | grep '^{"metric' | tee $O/bench.json | python scripts/benchline.py
+timeout 600 python bench.py --full --no-cpu-baseline --no-secondary 2>&1 | grep '^{"metric' | tee $O/bench.json | python scripts/benchline.py
 timeout 300 python scripts/dev/transient_trace.py 2>&1 | tail -12

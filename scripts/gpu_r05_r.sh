@@ -10,7 +10,7 @@ timeout 900 python -m pytest tests -m gpu -q -x --timeout=600 2>&1 | tail -5 | t
 for v in default flat default flat; do
   L=$R/cupoch_amd/lib/libmi_icp_$v.so; [ $v = default ] && L=$R/cupoch_amd/lib/libmi_icp.so
   echo "== $v: bench"
-  MI_ICP_LIB_PATH=$L timeout 200 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-secondary 2>&1 | grep -v amdgpu.ids | python scripts/benchline.py 2>/dev/null || true
+  MI_ICP_LIB_PATH=$L timeout 200 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-secondary 2>&1 | grep -v amdgpu.ids | python scripts/benchline.py 2>/dev/null || true
   echo "== $v: shards"
   MI_ICP_LIB_PATH=$L timeout 200 python scripts/measure_shard.py 2>&1 | grep -v amdgpu.ids | cut -c1-400
 done

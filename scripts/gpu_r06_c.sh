@@ -5,7 +5,7 @@ O=gpurun_out/r06c
 mkdir -p $O
 export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_gpu_first_pass.py -x -q --timeout=600 > $O/t_gs.log 2>&1; echo "gs tests rc=$?"; tail -15 $O/t_gs.log | grep -v "^E  "
-timeout 900 python bench.py --no-cpu-baseline --big-points 0 2>&1 | grep '^{"metric' | tee $O/bench_10m.json | python scripts/benchline.py
+timeout 900 python bench.py --full --no-cpu-baseline --big-points 0 2>&1 | grep '^{"metric' | tee $O/bench_10m.json | python scripts/benchline.py
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r06c/bench_10m.json"))
