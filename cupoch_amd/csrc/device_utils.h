@@ -87,6 +87,65 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;                     // valid in lane 63
 }
 
+// inclusive prefix sum of x over the lanes of the wave
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x) {
+    const int lane = lane_id();
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    return x;
+}
+
+// the wave's total, from the inclusive scan
+__device__ __forceinline__ uint32_t wave_scan_total(uint32_t incl) { return (uint32_t)__builtin_amdgcn_readlane((int)incl, 63); }
+
+// A workgroup barrier for data shared through LDS only: __syncthreads() also makes the workgroup's GLOBAL stores
+// visible, i.e. waits until every store (and, the counter being one, every load asked for since) has come back --
+// which is exactly what some kernels must not do: their loads for the NEXT piece of work are in flight across the
+// barriers of the present one (voxel_dense.h).  Only for waves that share nothing through global memory.
+__device__ __forceinline__ void lds_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// exclusive prefix of v over the threads of a workgroup of NW waves (wtot: NW words of LDS); *total = the sum.
+// kLdsBarrier: the barriers are lds_barrier(), else __syncthreads().
+template <int NW, bool kLdsBarrier = false>
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* total, uint32_t* wtot) {
+    const int lane = lane_id();
+    const int wid = (int)(threadIdx.x >> 6);
+    const uint32_t x = wave_inclusive_scan(v);
+    if (lane == 63) wtot[wid] = x;
+    if (kLdsBarrier) lds_barrier(); else __syncthreads();
+    uint32_t woff = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        const uint32_t s = wtot[w];
+        if (w < wid) woff += s;
+        tot += s;
+    }
+    if (kLdsBarrier) lds_barrier(); else __syncthreads();
+    *total = tot;
+    return woff + x - v;
+}
+
+// the lanes (among those with `valid`) whose digit -- the low BITS bits of `bits` -- equals this lane's: one ballot per bit
+// (the bits above are ignored: callers pass the key unmasked, which keeps the bit tests single bit-field extracts)
+template <int BITS>
+__device__ __forceinline__ uint64_t ballot_digit_peers(uint32_t bits, bool valid) {
+    uint64_t peers = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < BITS; ++b) {
+        const bool bit = (bits >> b) & 1u;
+        const uint64_t m = __ballot(bit);
+        peers &= bit ? m : ~m;
+    }
+    return peers;
+}
+
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_down(v, o, 64));

@@ -393,7 +393,7 @@ static __global__ __launch_bounds__(kScanThreads) void vox_head_sums(const uint3
             prev = cur;
         }
     uint32_t tot;
-    block_exclusive_scan(s, &tot, lds4);
+    block_exclusive_scan<kScanWaves>(s, &tot, lds4);
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = tot;
 }
 
@@ -419,7 +419,7 @@ static __global__ __launch_bounds__(kScanThreads) void vox_head_apply(const uint
         s += h[k];
     }
     uint32_t tot;
-    uint32_t off = tile_offs[blockIdx.x] + block_exclusive_scan(s, &tot, lds4);
+    uint32_t off = tile_offs[blockIdx.x] + block_exclusive_scan<kScanWaves>(s, &tot, lds4);
 #pragma unroll
     for (int k = 0; k < kScanItems; ++k) {
         if (h[k]) run_start[off] = (uint32_t)(base + k);

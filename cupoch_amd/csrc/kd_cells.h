@@ -90,34 +90,20 @@ static __global__ __launch_bounds__(1024) void cells_layout(const uint32_t* __re
                                                      uint32_t* __restrict__ gstart, uint32_t* __restrict__ total) {
     __shared__ uint32_t wsum[16];
     __shared__ uint32_t s_carry;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = (int)threadIdx.x;
     if (tid == 0) s_carry = 0u;
     __syncthreads();
     for (int base = 0; base < ncells; base += 1024) {
         const int c = base + tid;
+        const uint32_t carry = s_carry;
         uint32_t g = 0u;
         if (c < ncells) {
             const uint32_t k = cstart[c + 1] - cstart[c];
             g = (k + (uint32_t)kKdGroup - 1u) / (uint32_t)kKdGroup + ((k == 0u) ? 1u : 0u);
         }
-        uint32_t x = g;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) wsum[wid] = x;
-        __syncthreads();
-        uint32_t woff = 0u, tot = 0u;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-            const uint32_t sw = wsum[w];
-            if (w < wid) woff += sw;
-            tot += sw;
-        }
-        const uint32_t carry = s_carry;
-        if (c < ncells) gstart[c] = carry + woff + x - g;
-        __syncthreads();
+        uint32_t tot;
+        const uint32_t off = block_exclusive_scan<16>(g, &tot, wsum);
+        if (c < ncells) gstart[c] = carry + off;
         if (tid == 0) s_carry = carry + tot;
         __syncthreads();
     }

@@ -153,6 +153,32 @@ static __global__ __launch_bounds__(256) void hp_hist(const float* __restrict__ 
     }
 }
 
+// The bin boundary nearest to a target count, over bins that the wave's lanes own in order (lane l: bins
+// [l * per, (l + 1) * per)); incl / mine: the lane's inclusive count and its own, bin(j): the count of its j-th bin.
+// The boundary behind bin b has cum(b) samples on the left; returns, to every lane, the b whose cum(b) is nearest to
+// the target (0 < target <= the wave's total: some lane reaches it).
+template <typename Bin>
+__device__ __forceinline__ int hp_nearest_boundary(uint32_t incl, uint32_t mine, uint32_t target, int per, Bin bin) {
+    const int lane = lane_id();
+    const uint64_t reached = __ballot(incl >= target);
+    const int owner = (int)__builtin_ctzll(reached);
+    int b = 0;
+    if (lane == owner) {
+        uint32_t run = incl - mine;
+        for (int j = 0; j < per; ++j) {
+            const uint32_t before = run;
+            run += bin(j);
+            if (run >= target) {
+                b = lane * per + j;
+                // (the boundary in front of this bin, if that is nearer and leaves something on the left)
+                if (before > 0u && target - before < run - target) b -= 1;
+                break;
+            }
+        }
+    }
+    return __builtin_amdgcn_readlane(b, owner);
+}
+
 // a wave per node of depth `level`: the plane, and -- child_boxes -- the children's boxes (the node's, cut at the plane)
 static __global__ __launch_bounds__(64) void hp_select(float2* __restrict__ planes, int level, int tri, uint32_t* __restrict__ boxmin,
                                                        uint32_t* __restrict__ boxmax, uint32_t* __restrict__ hist, int bins,
@@ -168,13 +194,8 @@ static __global__ __launch_bounds__(64) void hp_select(float2* __restrict__ plan
     uint32_t* h = hist + (size_t)blockIdx.x * (size_t)bins + (size_t)lane * (size_t)seg;
     uint32_t mine = 0u;
     for (int j = 0; j < seg; ++j) mine += h[j];
-    uint32_t incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)incl, o, 64);
-        if (lane >= o) incl += y;
-    }
-    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    const uint32_t incl = wave_inclusive_scan(mine);
+    const uint32_t total = wave_scan_total(incl);
     // the share that goes LEFT: a third at a TRI root, everything at its node 2 (whose children are node 4 and nobody)
     const bool all_left = tri && node == 2u;
     const float share = (tri && node == 1u) ? (1.0f / 3.0f) : 0.5f;
@@ -183,24 +204,7 @@ static __global__ __launch_bounds__(64) void hp_select(float2* __restrict__ plan
     float plane = INFINITY;
     int pax = 0;
     if (total > 0u && scale > 0.0f && !all_left) {
-        // boundary behind bin b: cum(b) samples on the left; the b whose cum(b) is nearest to the target
-        const uint64_t reached = __ballot(incl >= target);
-        const int owner = (int)__builtin_ctzll(reached);  // (total >= target: some lane reaches it)
-        int b = 0;
-        if (lane == owner) {
-            uint32_t run = incl - mine;
-            for (int j = 0; j < seg; ++j) {
-                const uint32_t before = run;
-                run += h[j];
-                if (run >= target) {
-                    b = lane * seg + j;
-                    // (the boundary in front of this bin, if that is nearer and leaves something on the left)
-                    if (before > 0u && target - before < run - target) b -= 1;
-                    break;
-                }
-            }
-        }
-        b = __builtin_amdgcn_readlane(b, owner);
+        const int b = hp_nearest_boundary(incl, mine, target, seg, [&](int j) { return h[j]; });
         plane = lo + (float)(b + 1) * (ext / (float)bins);
         pax = ax;
     }
@@ -365,36 +369,15 @@ __global__ __launch_bounds__(256) void hp_last_levels(const float* __restrict__ 
         if (wid < nsub) {  // wave `wid` picks sub-node `wid`'s plane: lane l owns bins 4l .. 4l + 3
             const uint4 hb = reinterpret_cast<const uint4*>(hist + wid * 256)[lane];
             const uint32_t mine = hb.x + hb.y + hb.z + hb.w;
-            uint32_t incl = mine;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t y = (uint32_t)__shfl_up((int)incl, o, 64);
-                if (lane >= o) incl += y;
-            }
-            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            const uint32_t incl = wave_inclusive_scan(mine);
+            const uint32_t total = wave_scan_total(incl);
             const uint32_t target = max((total + 1u) >> 1, 1u);
             float plane = INFINITY;
             int pax = 0;
             const float scale = s_scale[wid];
             if (total > 0u && scale > 0.0f) {
-                const uint64_t reached = __ballot(incl >= target);
-                const int owner = (int)__builtin_ctzll(reached);
-                int bsel = 0;
-                if (lane == owner) {
-                    const uint32_t hv[4] = {hb.x, hb.y, hb.z, hb.w};
-                    uint32_t run = incl - mine;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const uint32_t before = run;
-                        run += hv[j];
-                        if (run >= target) {
-                            bsel = lane * 4 + j;
-                            if (before > 0u && target - before < run - target) bsel -= 1;
-                            break;
-                        }
-                    }
-                }
-                bsel = __builtin_amdgcn_readlane(bsel, owner);
+                const uint32_t hv[4] = {hb.x, hb.y, hb.z, hb.w};
+                const int bsel = hp_nearest_boundary(incl, mine, target, 4, [&](int j) { return hv[j]; });
                 plane = s_lo[wid] + (float)(bsel + 1) / scale;
                 pax = s_ax[wid];
             }

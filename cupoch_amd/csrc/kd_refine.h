@@ -154,15 +154,6 @@ __device__ __forceinline__ void kd_bitonic_sort(KdShared& s, uint32_t v[4], int 
 constexpr int kKdSelectMinLog = 9;
 __device__ __forceinline__ uint32_t* kd_sel_state(KdShared& s) { return reinterpret_cast<uint32_t*>(&s.seg_scale[128]); }
 
-__device__ __forceinline__ uint32_t kd_wave_inclusive(uint32_t x, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)x, o, 64);
-        if (lane >= o) x += y;
-    }
-    return x;
-}
-
 // v: the thread's 4 keys (positions 4*tid .. 4*tid+3); on return s.key holds the partitioned
 // arrangement (all threads past a barrier) and kd_sel_state(s)[seg] the segment's median key.
 __device__ __forceinline__ void kd_median_partition(KdShared& s, const uint32_t v[4], int tid, int lS) {
@@ -201,7 +192,7 @@ __device__ __forceinline__ void kd_median_partition(KdShared& s, const uint32_t 
             const uint4 b = h[lane];
             h[lane] = make_uint4(0u, 0u, 0u, 0u);
             const uint32_t tot = b.x + b.y + b.z + b.w;
-            const uint32_t inc = kd_wave_inclusive(tot, lane);
+            const uint32_t inc = wave_inclusive_scan(tot);
             const uint32_t exc = inc - tot;
             const uint32_t k = kth[wid];
             if (exc <= k && k < inc) {  // exactly one lane
@@ -228,7 +219,7 @@ __device__ __forceinline__ void kd_median_partition(KdShared& s, const uint32_t 
     uint32_t cnt = 0u;
 #pragma unroll
     for (int c = 0; c < 4; ++c) cnt += (v[c] < M) ? 1u : 0u;
-    const uint32_t inc = kd_wave_inclusive(cnt, lane);
+    const uint32_t inc = wave_inclusive_scan(cnt);
     if (lane == 63) wlow[wid] = inc;
     __syncthreads();
     const int w0 = seg << (lS - 8);  // first wave of the segment (256 positions per wave)

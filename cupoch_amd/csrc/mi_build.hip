@@ -44,14 +44,7 @@ int compute_bounds(mi_icp_ctx* c, const float* pts, int64_t n, float** bounds_ou
 }
 
 int sort_buffers(mi_icp_ctx* c, int64_t n, SortBuffers* sb) {
-    // the buffers also serve sorts of FEWER elements (samples), which may use smaller tiles
-    int nseg = sort_num_segments(n);
-    nseg = std::max(nseg, sort_num_segments(std::min<int64_t>(n, (1 << 21) - 1)));
-    nseg = std::max(nseg, sort_num_segments(std::min<int64_t>(n, (1 << 18) - 1)));
-    // (the payload-carrying sort of VoxelDownSample works on tiles of at most 4096 elements)
-    nseg = std::max(nseg, sort_pay_num_segments(n));
-    nseg = std::max(nseg, sort_pay_num_segments(std::min<int64_t>(n, (1 << 20) - 1)));
-    nseg = std::max(nseg, sort_pay_num_segments(std::min<int64_t>(n, (1 << 18) - 1)));
+    const int nseg = sort_hist_segments(n);
     TRY(ensure(c, c->keys0, (size_t)n, &sb->keys[0]));
     TRY(ensure(c, c->keys1, (size_t)n, &sb->keys[1]));
     TRY(ensure(c, c->vals0, (size_t)n, &sb->vals[0]));
@@ -77,11 +70,11 @@ int morton_order(mi_icp_ctx* c, const float* pts, int64_t n, const uint32_t** or
     if (3 * bits <= 32) {  // narrow keys: a third less traffic per pass
         morton_keys<uint32_t><<<blocks_for(n), 256, 0, c->stream>>>(pts, (int)n, bnd, bits, (uint32_t*)sb.keys[0], sb.vals[0]);
         KCHK(c);
-        cur = radix_sort_pairs32(c->stream, sb, n, 3 * bits);
+        cur = radix_sort_pairs<uint32_t>(c->stream, sb, n, 3 * bits);
     } else {
         morton_keys<uint64_t><<<blocks_for(n), 256, 0, c->stream>>>(pts, (int)n, bnd, bits, sb.keys[0], sb.vals[0]);
         KCHK(c);
-        cur = radix_sort_pairs(c->stream, sb, n, 3 * bits);
+        cur = radix_sort_pairs<uint64_t>(c->stream, sb, n, 3 * bits);
     }
     KCHK(c);
     *order = sb.vals[cur];
@@ -153,7 +146,7 @@ int kd_cell_layout(mi_icp_ctx* c, const float* pts, int64_t n, CellLayout* out) 
         if (dh > 0) {  // samples grouped by their depth-dh node (plain heap numbering: no layout flag; narrow keys)
             cells_assign<uint32_t><<<blocks_for(S), 256, 0, c->stream>>>(samp, S, planes, dh, (uint32_t*)sb.keys[0], sb.vals[0]);
             KCHK(c);
-            cur = radix_sort_pairs32(c->stream, sb, S, dh);
+            cur = radix_sort_pairs<uint32_t>(c->stream, sb, S, dh);
             KCHK(c);
         }
         if (d > dh) {
@@ -166,7 +159,7 @@ int kd_cell_layout(mi_icp_ctx* c, const float* pts, int64_t n, CellLayout* out) 
     TRY(ensure(c, c->cell_gstart, (size_t)ncells, &gstart));
     cells_assign<uint32_t><<<blocks_for(n), 256, 0, c->stream>>>(pts, n, planes, lv, (uint32_t*)sb.keys[0], sb.vals[0]);
     KCHK(c);
-    const int cur = radix_sort_pairs32(c->stream, sb, n, d);  // (cell ids: narrow keys)
+    const int cur = radix_sort_pairs<uint32_t>(c->stream, sb, n, d);  // (cell ids: narrow keys)
     KCHK(c);
     cells_starts<uint32_t><<<blocks_for(n), 256, 0, c->stream>>>((const uint32_t*)sb.keys[cur], n, ncells, cstart);
     KCHK(c);
@@ -279,7 +272,7 @@ int resort_source_by_match(mi_icp_ctx* c) {
     match_order_keys<<<blocks_for(n), 256, 0, c->stream>>>((const int32_t*)c->nn_idx.p, (int)n, (uint32_t)c->nleaf,
                                                            (uint32_t*)sb.keys[0], sb.vals[0]);
     KCHK(c);
-    const uint32_t* ord = sb.vals[radix_sort_pairs32(c->stream, sb, n, bits)];
+    const uint32_t* ord = sb.vals[radix_sort_pairs<uint32_t>(c->stream, sb, n, bits)];
     KCHK(c);
     SourceArrays in, out;
     in.sx = (float*)c->sx.p; in.sy = (float*)c->sy.p; in.sz = (float*)c->sz.p;

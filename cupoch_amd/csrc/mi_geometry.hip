@@ -358,7 +358,7 @@ static int voxel_downsample_keys32(mi_icp_ctx* c, const float* const in[3], int6
         for (int set = 0; set < std::min(passes, 2); ++set)
             for (int a = 0; a < 3; ++a)
                 if (first[a]) TRY(ensure(c, c->vpay[set * 3 + a], (size_t)n, &scratch[set][a]));
-        const int cur = radix_sort_payload32(c->stream, keys, first, scratch, sb.hist, sb.scan_tmp, n, L, bits, pay);
+        const int cur = radix_sort_payload32(c->stream, sb, first, scratch, n, L, bits, pay);
         KCHK(c);
         skeys = keys[cur];
     }
@@ -470,7 +470,7 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
     if (bits <= 64) {
         voxel_keys<<<nb, 256, 0, c->stream>>>(dp, n, g, -1, nullptr, sb.keys[0], sb.vals[0]);
         KCHK(c);
-        const int cur = radix_sort_pairs(c->stream, sb, n, bits);
+        const int cur = radix_sort_pairs<uint64_t>(c->stream, sb, n, bits);
         order = sb.vals[cur];
         packed_sorted = sb.keys[cur];
     } else {
@@ -484,7 +484,7 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
             }
             voxel_keys<<<nb, 256, 0, c->stream>>>(dp, n, g, axis, tmp_order, sb.keys[0], sb.vals[0]);
             KCHK(c);
-            prev = sb.vals[radix_sort_pairs(c->stream, sb, n, f.bits[axis])];
+            prev = sb.vals[radix_sort_pairs<uint64_t>(c->stream, sb, n, f.bits[axis])];
         }
         order = prev;
     }

@@ -5,6 +5,8 @@
 // VoxelDownSample (geometry/down_sample.cu:200-203) and of the correspondence
 // compaction (registration/registration.cu:62-69).
 #pragma once
+#include <algorithm>
+
 #include "device_utils.h"
 
 namespace mi {
@@ -16,31 +18,7 @@ namespace mi {
 constexpr int kScanThreads = 256;
 constexpr int kScanItems = 8;
 constexpr int kScanTile = kScanThreads * kScanItems;
-
-// exclusive prefix of v over the 256 threads of a block; *total = block sum
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* total,
-                                                         uint32_t* lds4) {
-    const int lane = lane_id();
-    const int wid = (int)(threadIdx.x >> 6);
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) lds4[wid] = x;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kScanThreads / 64; ++w) {
-        const uint32_t s = lds4[w];
-        if (w < wid) woff += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + x - v;
-}
+constexpr int kScanWaves = kScanThreads / 64;
 
 static __global__ __launch_bounds__(kScanThreads) void scan_tile_sums(const uint32_t* __restrict__ in,
                                                                uint32_t* __restrict__ tile_sums,
@@ -52,7 +30,7 @@ static __global__ __launch_bounds__(kScanThreads) void scan_tile_sums(const uint
     for (int k = 0; k < kScanItems; ++k)
         if (base + k < n) s += in[base + k];
     uint32_t tot;
-    block_exclusive_scan(s, &tot, lds4);
+    block_exclusive_scan<kScanWaves>(s, &tot, lds4);
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = tot;
 }
 
@@ -71,7 +49,7 @@ static __global__ __launch_bounds__(kScanThreads) void scan_tile_offsets(uint32_
             s += v[k];
         }
         uint32_t tot;
-        uint32_t off = carry + block_exclusive_scan(s, &tot, lds4);
+        uint32_t off = carry + block_exclusive_scan<kScanWaves>(s, &tot, lds4);
 #pragma unroll
         for (int k = 0; k < kScanItems; ++k) {
             if (base + k < ntiles) tile_sums[base + k] = off;
@@ -95,7 +73,7 @@ static __global__ __launch_bounds__(kScanThreads) void scan_apply(const uint32_t
         s += v[k];
     }
     uint32_t tot;
-    uint32_t off = tile_offs[blockIdx.x] + block_exclusive_scan(s, &tot, lds4);
+    uint32_t off = tile_offs[blockIdx.x] + block_exclusive_scan<kScanWaves>(s, &tot, lds4);
 #pragma unroll
     for (int k = 0; k < kScanItems; ++k) {
         if (base + k < n) out[base + k] = off;
@@ -132,14 +110,43 @@ static inline void exclusive_scan_u32(hipStream_t st, const uint32_t* in, uint32
 // ---------------------------------------------------------------------------
 constexpr int kSortThreads = 512;
 constexpr int kSortWaves = kSortThreads / 64;
-constexpr int kSortMaxChunks = 16;  // 64-element chunks per wave: tiles of 8192 elements ...
 
-// ... for large inputs; small ones use smaller tiles so that the pass still fills the chip
-// (a 300k-element sort would otherwise run on 37 of the 256 CUs)
-static inline int sort_chunks_for(int64_t n) { return n >= (1 << 21) ? 16 : (n >= (1 << 18) ? 4 : 1); }
-static inline int sort_num_segments(int64_t n) {
-    const int64_t tile = (int64_t)kSortThreads * sort_chunks_for(n);
+// The tile tables: 64-element chunks per wave by input size, tiles of 8192 elements for large inputs; small ones use
+// smaller tiles so that the pass still fills the chip (a 300k-element sort would otherwise run on 37 of the 256 CUs).
+// The payload sort's tiles hold at most 4096 elements: rs_scatter_pay stages keys and one payload array of a tile
+// through LDS.
+struct SortTier {
+    int64_t from;  // inputs of at least this many elements ...
+    int chunks;    // ... use this many chunks per wave
+};
+constexpr int kSortTiers = 3;
+constexpr SortTier kPairTiers[kSortTiers] = {{1 << 21, 16}, {1 << 18, 4}, {0, 1}};
+constexpr SortTier kPayTiers[kSortTiers] = {{1 << 20, 8}, {1 << 18, 4}, {0, 1}};
+
+static inline int sort_chunks_for(const SortTier* tiers, int64_t n) {
+    while (n < tiers->from) ++tiers;
+    return tiers->chunks;
+}
+static inline int sort_num_segments(int64_t n, int chunks) {
+    const int64_t tile = (int64_t)kSortThreads * chunks;
     return (int)((n + tile - 1) / tile);
+}
+
+// The hist segments a SortBuffers for n elements must hold: the most that any sort of m <= n elements needs, pairs or
+// payload (the buffers also serve sorts of FEWER elements, samples, which may use smaller tiles).  Within a tier the
+// count grows with m, so the most is at m = n or just below the start of a tier.
+static inline int sort_hist_segments(int64_t n) {
+    int nseg = 0;
+    auto take = [&](int64_t m) {
+        nseg = std::max(nseg, sort_num_segments(m, sort_chunks_for(kPairTiers, m)));
+        nseg = std::max(nseg, sort_num_segments(m, sort_chunks_for(kPayTiers, m)));
+    };
+    take(n);
+    for (int t = 0; t < kSortTiers; ++t) {
+        if (kPairTiers[t].from > 0) take(std::min(n, kPairTiers[t].from - 1));
+        if (kPayTiers[t].from > 0) take(std::min(n, kPayTiers[t].from - 1));
+    }
+    return nseg;
 }
 
 template <typename K, int kSortChunks>
@@ -172,6 +179,57 @@ __global__ __launch_bounds__(kSortThreads) void rs_histogram(const K* __restrict
     if (tid < 256) hist[(int64_t)tid * nseg + seg] = cnt[tid];
 }
 
+// ---- the scatters' rank core ----------------------------------------------------------------------------------------
+// 1: the rank of an element (key, loaded by the caller; valid: it exists) among the same-digit elements of its wave.
+// wcnt: the wave's 256 bin counters, advanced past the chunk.  Returns digit << 16 | position inside the wave's bin.
+template <typename K>
+__device__ __forceinline__ uint32_t rs_wave_rank(uint32_t* wcnt, K key, bool valid, int shift) {
+    const int lane = lane_id();
+    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const uint32_t bits = (uint32_t)(key >> shift);
+    const uint32_t digit = bits & 255u;
+    const uint64_t peers = ballot_digit_peers<8>(bits, valid);
+    const uint32_t rank = (uint32_t)__popcll(peers & lt_mask);
+    const uint32_t cnt = (uint32_t)__popcll(peers);
+    uint32_t pos = 0;
+    if (valid) pos = wcnt[digit] + rank;
+    __builtin_amdgcn_wave_barrier();  // every lane has read its bin counter ...
+    if (valid && rank == 0) wcnt[digit] = pos + cnt;  // ... before the bin leader advances it
+    __builtin_amdgcn_wave_barrier();
+    return (digit << 16) | pos;
+}
+
+// 2: the digit runs of the tile, after a barrier behind step 1: wcnt[w][d] becomes wave w's offset inside run d and
+// tile_start[d] the run's first local position (wtot: kSortWaves words); threads 0..255 then call at_start(tile_start
+// of their digit).
+template <typename AtStart>
+__device__ __forceinline__ void rs_tile_runs(uint32_t (*wcnt)[256], uint32_t* tile_start, uint32_t* wtot, AtStart at_start) {
+    const int tid = (int)threadIdx.x;
+    const int wid = tid >> 6;
+    uint32_t total = 0;
+    if (tid < 256) {
+        uint32_t run = 0;
+#pragma unroll
+        for (int w = 0; w < kSortWaves; ++w) {
+            const uint32_t k = wcnt[w][tid];
+            wcnt[w][tid] = run;
+            run += k;
+        }
+        total = run;
+    }
+    // exclusive scan of `total` over the 256 digits (threads 0..255 = waves 0..3)
+    const uint32_t x = wave_inclusive_scan(total);
+    if (lane_id() == 63) wtot[wid] = x;
+    __syncthreads();
+    if (tid < 256) {
+        uint32_t woff = 0;
+        for (int w = 0; w < wid; ++w) woff += wtot[w];
+        const uint32_t start = woff + x - total;
+        tile_start[tid] = start;
+        at_start(start);
+    }
+}
+
 // kWhole: a pass in ONE launch for short arrays (n <= kSortWholeMax).  Every workgroup goes through ALL the keys itself
 // -- the digits' counts in the whole array and in the tiles before its own (256 KB of keys at most, from the L2) --
 // instead of reading offsets that a histogram kernel and a three-launch scan left for it: a launch is ~5 us on the
@@ -190,7 +248,7 @@ __global__ __launch_bounds__(kSortThreads) void rs_scatter(const K* __restrict__
     __shared__ uint32_t wcnt[kSortWaves][256];  // per-wave bin counters, then the wave's offset inside the bin
     __shared__ uint32_t tile_start[256];        // first local position of every digit run
     __shared__ int32_t gdelta[256];             // global position - local position, per digit (mod 2^32)
-    __shared__ uint32_t wtot[kSortThreads / 64];
+    __shared__ uint32_t wtot[kSortWaves];
     __shared__ uint16_t perm[kSortSeg];         // local sorted position -> element of the tile
     __shared__ uint32_t whole[kWhole ? 512 : 1];  // kWhole: [digit] count in the whole array | [256 + digit] in the tiles before this one
     const int tid = (int)threadIdx.x;
@@ -223,76 +281,30 @@ __global__ __launch_bounds__(kSortThreads) void rs_scatter(const K* __restrict__
     }
 
     // ---- 1: rank of every element among the same-digit elements of its wave
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     uint32_t packed[kSortChunks];  // digit << 16 | position inside the wave's bin
 #pragma unroll
     for (int c = 0; c < kSortChunks; ++c) {
         const int e = wid * kSortWaveSeg + c * 64 + lane;
         const bool valid = e < tile_n;
         const K key = valid ? keys_in[tbase + e] : (K)0;
-        const uint32_t digit = (uint32_t)(key >> shift) & 255u;
-        uint64_t peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (digit >> b) & 1u;
-            const uint64_t m = __ballot(bit);
-            peers &= bit ? m : ~m;
-        }
-        const uint32_t rank = (uint32_t)__popcll(peers & lt_mask);
-        const uint32_t cnt = (uint32_t)__popcll(peers);
-        uint32_t pos = 0;
-        if (valid) pos = wcnt[wid][digit] + rank;
-        __builtin_amdgcn_wave_barrier();  // every lane has read its bin counter ...
-        if (valid && rank == 0) wcnt[wid][digit] = pos + cnt;  // ... before the bin leader advances it
-        __builtin_amdgcn_wave_barrier();
-        packed[c] = (digit << 16) | pos;
+        packed[c] = rs_wave_rank(wcnt[wid], key, valid, shift);
     }
     __syncthreads();
 
     // ---- 2: digit runs of the tile: start of every run, every wave's offset inside it
-    uint32_t total = 0;
-    if (tid < 256) {
-        uint32_t run = 0;
-#pragma unroll
-        for (int w = 0; w < kSortWaves; ++w) {
-            const uint32_t k = wcnt[w][tid];
-            wcnt[w][tid] = run;
-            run += k;
-        }
-        total = run;
-    }
-    {   // exclusive scan of `total` over the 256 digits (threads 0..255 = waves 0..3)
-        uint32_t x = total;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) wtot[wid] = x;
+    rs_tile_runs(wcnt, tile_start, wtot, [&](uint32_t start) {
+        if (!kWhole) gdelta[tid] = (int32_t)(offs[(int64_t)tid * nseg + seg] - start);
+    });
+    if (kWhole) {  // the digit's first position in the whole array (a second scan, of the whole array's counts) + what the tiles before hold of it
+        __syncthreads();
+        const uint32_t cnt = (tid < 256) ? whole[tid] : 0u;
+        const uint32_t y = wave_inclusive_scan(cnt);
+        if (lane == 63) wtot[wid] = y;
         __syncthreads();
         if (tid < 256) {
             uint32_t woff = 0;
             for (int w = 0; w < wid; ++w) woff += wtot[w];
-            const uint32_t start = woff + x - total;
-            tile_start[tid] = start;
-            if (!kWhole) gdelta[tid] = (int32_t)(offs[(int64_t)tid * nseg + seg] - start);
-        }
-        if (kWhole) {  // the digit's first position in the whole array (a second scan, of the whole array's counts) + what the tiles before hold of it
-            __syncthreads();
-            const uint32_t cnt = (tid < 256) ? whole[tid] : 0u;
-            uint32_t y = cnt;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t z = __shfl_up(y, o, 64);
-                if (lane >= o) y += z;
-            }
-            if (lane == 63) wtot[wid] = y;
-            __syncthreads();
-            if (tid < 256) {
-                uint32_t woff = 0;
-                for (int w = 0; w < wid; ++w) woff += wtot[w];
-                gdelta[tid] = (int32_t)((woff + y - cnt) + whole[256 + tid] - tile_start[tid]);
-            }
+            gdelta[tid] = (int32_t)((woff + y - cnt) + whole[256 + tid] - tile_start[tid]);
         }
     }
     __syncthreads();
@@ -348,7 +360,7 @@ __global__ __launch_bounds__(kSortThreads) void rs_scatter_pay(const uint32_t* _
     __shared__ uint32_t wcnt[kSortWaves][256];
     __shared__ uint32_t tile_start[256];
     __shared__ int32_t gdelta[256];
-    __shared__ uint32_t wtot[kSortThreads / 64];
+    __shared__ uint32_t wtot[kSortWaves];
     __shared__ uint32_t skey[kSortSeg];   // keys in local sorted order
     __shared__ Pay3 stage[kSortSeg];      // one payload array at a time, in local sorted order
     const int tid = (int)threadIdx.x;
@@ -360,7 +372,6 @@ __global__ __launch_bounds__(kSortThreads) void rs_scatter_pay(const uint32_t* _
 #pragma unroll
     for (int k = 0; k < 4; ++k) wcnt[wid][lane + 64 * k] = 0;
     __builtin_amdgcn_wave_barrier();
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     uint32_t packed[kSortChunks];  // digit << 16 | position inside the wave's bin, later: the local sorted position
     uint32_t mykey[kSortChunks];
 #pragma unroll
@@ -369,52 +380,10 @@ __global__ __launch_bounds__(kSortThreads) void rs_scatter_pay(const uint32_t* _
         const bool valid = e < tile_n;
         const uint32_t key = keys_in[tbase + min(e, tile_n - 1)];  // (unconditional: guarded loads are waited for one by one)
         mykey[c] = valid ? key : 0u;
-        const uint32_t digit = (mykey[c] >> shift) & 255u;
-        uint64_t peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (digit >> b) & 1u;
-            const uint64_t m = __ballot(bit);
-            peers &= bit ? m : ~m;
-        }
-        const uint32_t rank = (uint32_t)__popcll(peers & lt_mask);
-        const uint32_t cnt = (uint32_t)__popcll(peers);
-        uint32_t pos = 0;
-        if (valid) pos = wcnt[wid][digit] + rank;
-        __builtin_amdgcn_wave_barrier();
-        if (valid && rank == 0) wcnt[wid][digit] = pos + cnt;
-        __builtin_amdgcn_wave_barrier();
-        packed[c] = (digit << 16) | pos;
+        packed[c] = rs_wave_rank(wcnt[wid], mykey[c], valid, shift);
     }
     __syncthreads();
-    uint32_t total = 0;
-    if (tid < 256) {
-        uint32_t run = 0;
-#pragma unroll
-        for (int w = 0; w < kSortWaves; ++w) {
-            const uint32_t k = wcnt[w][tid];
-            wcnt[w][tid] = run;
-            run += k;
-        }
-        total = run;
-    }
-    {
-        uint32_t x = total;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) wtot[wid] = x;
-        __syncthreads();
-        if (tid < 256) {
-            uint32_t woff = 0;
-            for (int w = 0; w < wid; ++w) woff += wtot[w];
-            const uint32_t start = woff + x - total;
-            tile_start[tid] = start;
-            gdelta[tid] = (int32_t)(offs[(int64_t)tid * nseg + seg] - start);
-        }
-    }
+    rs_tile_runs(wcnt, tile_start, wtot, [&](uint32_t start) { gdelta[tid] = (int32_t)(offs[(int64_t)tid * nseg + seg] - start); });
     __syncthreads();
     // the local sorted position of every element; its key goes there
 #pragma unroll
@@ -452,101 +421,74 @@ __global__ __launch_bounds__(kSortThreads) void rs_scatter_pay(const uint32_t* _
 struct SortBuffers {
     uint64_t* keys[2];
     uint32_t* vals[2];
-    uint32_t* hist;      // 256 * nseg words
-    uint32_t* scan_tmp;  // scan_num_tiles(256*nseg) + 1 words
+    uint32_t* hist;      // 256 * sort_hist_segments(n) words
+    uint32_t* scan_tmp;  // scan_num_tiles(256 * sort_hist_segments(n)) + 1 words
 };
 
-// Sorts keys[0]/vals[0] by the low `key_bits` bits; returns the index (0 or 1)
-// of the buffer pair that holds the result.  K = uint64_t or uint32_t: a pass moves 8 + 2*(sizeof(K)+4)
-// bytes per element, so keys that fit 32 bits (Morton codes of <= 10 bits per axis, leaf ids) sort
-// 1.5x faster in the narrow form.
+// a pass's digit offsets: the tiles' histograms [digit][tile], scanned in place
+template <typename K, typename Histogram>
+static inline void rs_offsets(hipStream_t st, Histogram histogram, const K* keys, const SortBuffers& b, int64_t n,
+                              int nseg, int shift) {
+    histogram<<<nseg, kSortThreads, 0, st>>>(keys, b.hist, (int)n, nseg, shift);
+    exclusive_scan_u32(st, b.hist, b.hist, (int64_t)256 * nseg, b.scan_tmp);
+}
+
+// Sorts b.keys[0] / b.vals[0], the keys read as K, by the low `key_bits` bits; returns the index (0 or 1) of the
+// buffer pair that holds the result.  K = uint64_t or uint32_t: a pass moves 8 + 2*(sizeof(K)+4) bytes per element,
+// so keys that fit 32 bits (Morton codes of <= 10 bits per axis, leaf ids, cell ids) sort 1.5x faster in the narrow form.
 template <typename K>
-static inline int radix_sort_pairs_t(hipStream_t st, K* const keys[2], uint32_t* const vals[2], uint32_t* hist,
-                                     uint32_t* scan_tmp, int64_t n, int key_bits) {
+static inline int radix_sort_pairs(hipStream_t st, const SortBuffers& b, int64_t n, int key_bits) {
+    K* const keys[2] = {reinterpret_cast<K*>(b.keys[0]), reinterpret_cast<K*>(b.keys[1])};
     if (n <= 0) return 0;
-    const int nseg = sort_num_segments(n);
-    const int nblk = nseg;  // one workgroup per tile
-    const int chunks = sort_chunks_for(n);
     const int passes = (key_bits + 7) / 8;
     int cur = 0;
     if (n <= kSortWholeMax) {  // short arrays: a pass is one launch (tiles of 2048 elements)
         const int nblk_w = (int)((n + 2047) / 2048);
         for (int p = 0; p < passes; ++p) {
-            rs_scatter<K, 4, true><<<nblk_w, kSortThreads, 0, st>>>(keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], hist, (int)n, nblk_w, p * 8);
+            rs_scatter<K, 4, true><<<nblk_w, kSortThreads, 0, st>>>(keys[cur], b.vals[cur], keys[cur ^ 1], b.vals[cur ^ 1], b.hist, (int)n, nblk_w, p * 8);
             cur ^= 1;
         }
         return cur;
     }
+    const int chunks = sort_chunks_for(kPairTiers, n);
+    const int nseg = sort_num_segments(n, chunks);  // one workgroup per tile
+    const auto histogram = chunks == 16 ? rs_histogram<K, 16> : (chunks == 4 ? rs_histogram<K, 4> : rs_histogram<K, 1>);
+    const auto scatter = chunks == 16 ? rs_scatter<K, 16> : (chunks == 4 ? rs_scatter<K, 4> : rs_scatter<K, 1>);
     for (int p = 0; p < passes; ++p) {
-        const int shift = p * 8;
-        switch (chunks) {
-            case 16: rs_histogram<K, 16><<<nblk, kSortThreads, 0, st>>>(keys[cur], hist, (int)n, nseg, shift); break;
-            case 4: rs_histogram<K, 4><<<nblk, kSortThreads, 0, st>>>(keys[cur], hist, (int)n, nseg, shift); break;
-            default: rs_histogram<K, 1><<<nblk, kSortThreads, 0, st>>>(keys[cur], hist, (int)n, nseg, shift); break;
-        }
-        exclusive_scan_u32(st, hist, hist, (int64_t)256 * nseg, scan_tmp);
-#define MI_RS_ARGS keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], hist, (int)n, nseg, shift
-        switch (chunks) {
-            case 16: rs_scatter<K, 16><<<nblk, kSortThreads, 0, st>>>(MI_RS_ARGS); break;
-            case 4: rs_scatter<K, 4><<<nblk, kSortThreads, 0, st>>>(MI_RS_ARGS); break;
-            default: rs_scatter<K, 1><<<nblk, kSortThreads, 0, st>>>(MI_RS_ARGS); break;
-        }
-#undef MI_RS_ARGS
+        rs_offsets(st, histogram, keys[cur], b, n, nseg, p * 8);
+        scatter<<<nseg, kSortThreads, 0, st>>>(keys[cur], b.vals[cur], keys[cur ^ 1], b.vals[cur ^ 1], b.hist, (int)n, nseg, p * 8);
         cur ^= 1;
     }
     return cur;
 }
 
-static inline int radix_sort_pairs(hipStream_t st, const SortBuffers& b, int64_t n, int key_bits) {
-    return radix_sort_pairs_t<uint64_t>(st, b.keys, b.vals, b.hist, b.scan_tmp, n, key_bits);
-}
-
-// 32-bit keys with float3 payload arrays, sorted on the key bits [lo_bit, hi_bit).  first_in: the caller's arrays (read
-// by the first pass only), scratch[2][3]: two sets of arrays the passes alternate between.  Returns the key buffer's
-// index (0 / 1) and through *result the arrays that hold the sorted payload (first_in itself when there is no pass).
-// (tiles of at most 4096 elements: keys and one payload array of a tile are staged through LDS)
-static inline int sort_pay_chunks_for(int64_t n) { return n >= (1 << 20) ? 8 : (n >= (1 << 18) ? 4 : 1); }
-static inline int sort_pay_num_segments(int64_t n) {
-    const int64_t tile = (int64_t)kSortThreads * sort_pay_chunks_for(n);
-    return (int)((n + tile - 1) / tile);
-}
-
-static inline int radix_sort_payload32(hipStream_t st, uint32_t* const keys[2], const Pay3* const first_in[3],
-                                       Pay3* const scratch[2][3], uint32_t* hist, uint32_t* scan_tmp, int64_t n,
-                                       int lo_bit, int hi_bit, const Pay3* result[3]) {
+// The buffers' keys as 32-bit keys with float3 payload arrays, sorted on the key bits [lo_bit, hi_bit).  first_in: the
+// caller's arrays (read by the first pass only), scratch[2][3]: two sets of arrays the passes alternate between.
+// Returns the key buffer's index (0 / 1) and through *result the arrays that hold the sorted payload (first_in itself
+// when there is no pass).
+static inline int radix_sort_payload32(hipStream_t st, const SortBuffers& b, const Pay3* const first_in[3],
+                                       Pay3* const scratch[2][3], int64_t n, int lo_bit, int hi_bit, const Pay3* result[3]) {
+    uint32_t* const keys[2] = {reinterpret_cast<uint32_t*>(b.keys[0]), reinterpret_cast<uint32_t*>(b.keys[1])};
     for (int a = 0; a < 3; ++a) result[a] = first_in[a];
     if (n <= 0) return 0;
-    const int nseg = sort_pay_num_segments(n);
-    const int chunks = sort_pay_chunks_for(n);
+    const int chunks = sort_chunks_for(kPayTiers, n);
+    const int nseg = sort_num_segments(n, chunks);
+    const auto histogram = chunks == 8 ? rs_histogram<uint32_t, 8> : (chunks == 4 ? rs_histogram<uint32_t, 4> : rs_histogram<uint32_t, 1>);
+    const auto scatter = chunks == 8 ? rs_scatter_pay<8> : (chunks == 4 ? rs_scatter_pay<4> : rs_scatter_pay<1>);
     int cur = 0, set = 0;
     for (int shift = lo_bit; shift < hi_bit; shift += 8) {
-        switch (chunks) {
-            case 8: rs_histogram<uint32_t, 8><<<nseg, kSortThreads, 0, st>>>(keys[cur], hist, (int)n, nseg, shift); break;
-            case 4: rs_histogram<uint32_t, 4><<<nseg, kSortThreads, 0, st>>>(keys[cur], hist, (int)n, nseg, shift); break;
-            default: rs_histogram<uint32_t, 1><<<nseg, kSortThreads, 0, st>>>(keys[cur], hist, (int)n, nseg, shift); break;
-        }
-        exclusive_scan_u32(st, hist, hist, (int64_t)256 * nseg, scan_tmp);
+        rs_offsets(st, histogram, keys[cur], b, n, nseg, shift);
         PayArrays pay;
         for (int a = 0; a < 3; ++a) {
             pay.in[a] = result[a];
             pay.out[a] = result[a] ? scratch[set][a] : nullptr;
         }
-        switch (chunks) {
-            case 8: rs_scatter_pay<8><<<nseg, kSortThreads, 0, st>>>(keys[cur], keys[cur ^ 1], pay, hist, (int)n, nseg, shift); break;
-            case 4: rs_scatter_pay<4><<<nseg, kSortThreads, 0, st>>>(keys[cur], keys[cur ^ 1], pay, hist, (int)n, nseg, shift); break;
-            default: rs_scatter_pay<1><<<nseg, kSortThreads, 0, st>>>(keys[cur], keys[cur ^ 1], pay, hist, (int)n, nseg, shift); break;
-        }
+        scatter<<<nseg, kSortThreads, 0, st>>>(keys[cur], keys[cur ^ 1], pay, b.hist, (int)n, nseg, shift);
         for (int a = 0; a < 3; ++a) result[a] = pay.out[a];
         cur ^= 1;
         set ^= 1;
     }
     return cur;
-}
-
-// the same buffers holding 32-bit keys
-static inline int radix_sort_pairs32(hipStream_t st, const SortBuffers& b, int64_t n, int key_bits) {
-    uint32_t* const k32[2] = {reinterpret_cast<uint32_t*>(b.keys[0]), reinterpret_cast<uint32_t*>(b.keys[1])};
-    return radix_sort_pairs_t<uint32_t>(st, k32, b.vals, b.hist, b.scan_tmp, n, key_bits);
 }
 
 }  // namespace mi

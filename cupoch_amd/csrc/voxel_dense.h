@@ -99,41 +99,6 @@ __device__ __forceinline__ uint32_t vx_key(const VxGrid& g, const Pay3& p) {
                         vx_cell(p.z - g.g.oz, g.g.voxel, g.inv)) & g.key_mask;
 }
 
-// A workgroup barrier for data shared through LDS only: __syncthreads() also makes the workgroup's GLOBAL stores
-// visible, i.e. waits until every store (and, the counter being one, every load asked for since) has come back --
-// which is exactly what the kernels below must not do: their loads for the NEXT piece of work are in flight across
-// the barriers of the present one.  Waves of a workgroup share nothing through global memory here.
-__device__ __forceinline__ void vx_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-// exclusive prefix over the threads of a workgroup of NW waves (wtot: NW words of LDS); *total = the sum
-template <int NW>
-__device__ __forceinline__ uint32_t vx_block_scan(uint32_t v, uint32_t* total, uint32_t* wtot) {
-    const int lane = lane_id();
-    const int wid = (int)(threadIdx.x >> 6);
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wtot[wid] = x;
-    vx_barrier();
-    uint32_t woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        const uint32_t s = wtot[w];
-        if (w < wid) woff += s;
-        tot += s;
-    }
-    vx_barrier();
-    *total = tot;
-    return woff + x - v;
-}
-
 // rank of this lane's element among the wave's earlier elements of bin `bin`: one add on the wave's packed counters
 // (row: the wave's counters as words, two 16-bit counters each; a wave adds at most 1024 to a counter)
 // (a lane without an element adds nothing -- no branch around the add: a guarded ds_add_rtn is followed by its own wait,
@@ -162,12 +127,7 @@ static __global__ __launch_bounds__(256) void vx_probe_order(uint32_t* __restric
             __builtin_amdgcn_wave_barrier();
             const uint32_t got = vx_rank(cnt[w], bin);
             __builtin_amdgcn_wave_barrier();
-            uint64_t peers = ~0ull;
-            for (int b = 0; b < 11; ++b) {
-                const bool bit = (bin >> b) & 1u;
-                const uint64_t m = __ballot(bit);
-                peers &= bit ? m : ~m;
-            }
+            const uint64_t peers = ballot_digit_peers<11>(bin, true);
             if (got != before + (uint32_t)__popcll(peers & lt)) ++bad;
         }
     }
@@ -313,8 +273,8 @@ static __global__ __launch_bounds__(1024) void vx_colscan(uint32_t* __restrict__
     }
     // bucket order is b = tid (first half), then tid + 1024: two scans
     uint32_t all0, all1;
-    const uint32_t s0 = vx_block_scan<16>(tot[0], &all0, wtot);
-    const uint32_t s1 = vx_block_scan<16>(tot[1], &all1, wtot);
+    const uint32_t s0 = block_exclusive_scan<16, true>(tot[0], &all0, wtot);
+    const uint32_t s1 = block_exclusive_scan<16, true>(tot[1], &all1, wtot);
     if (tid < B) bucket_start[tid] = s0;
     if (tid + 1024 < B) bucket_start[tid + 1024] = all0 + s1;
     uint32_t big = max(tot[0], tot[1]);
@@ -413,7 +373,7 @@ static __global__ __launch_bounds__(kVxThreads) void vx_scatter(VxArrays a, int 
             packed[c] = (bin << 16) | vx_rank(row, bin, e < tile_n);
         }
         if (kArrays >= 2) MI_VX_LOAD(q, a.in[1], tile);  // (behind the ranks: at the top of the tile it delayed the points it queued behind)
-        vx_barrier();  // (also: every thread has finished writing the previous tile out of the stage)
+        lds_barrier();  // (also: every thread has finished writing the previous tile out of the stage)
         // the tile's bucket runs: every wave's first position in every bucket, and where the run goes
         {
             uint32_t k[4][kVxWaves];
@@ -432,7 +392,7 @@ static __global__ __launch_bounds__(kVxThreads) void vx_scatter(VxArrays a, int 
                 }
             }
             uint32_t all;
-            uint32_t start = vx_block_scan<kVxWaves>(sum, &all, wtot);
+            uint32_t start = block_exclusive_scan<kVxWaves, true>(sum, &all, wtot);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int b = tid * per + j;
@@ -448,7 +408,7 @@ static __global__ __launch_bounds__(kVxThreads) void vx_scatter(VxArrays a, int 
                 }
             }
         }
-        vx_barrier();
+        lds_barrier();
 #pragma unroll
         for (int c = 0; c < kVxItems; ++c) {
             const int e = wid * kVxWaveSeg + c * 64 + lane;
@@ -463,19 +423,19 @@ static __global__ __launch_bounds__(kVxThreads) void vx_scatter(VxArrays a, int 
         // array after array through the stage; what is needed next is on its way while this one is written out
         if (kArrays == 3) MI_VX_LOAD(p, a.in[2], tile);
         else if (next < ntiles) MI_VX_LOAD(p, a.in[0], next);
-        vx_barrier();
+        lds_barrier();
         MI_VX_WRITE_OUT(a.out[0]);
         if (kArrays >= 2) {
-            vx_barrier();
+            lds_barrier();
             MI_VX_RESTAGE(q);
-            vx_barrier();
+            lds_barrier();
             MI_VX_WRITE_OUT(a.out[1]);
         }
         if (kArrays == 3) {
-            vx_barrier();
+            lds_barrier();
             MI_VX_RESTAGE(p);
             if (next < ntiles) MI_VX_LOAD(p, a.in[0], next);
-            vx_barrier();
+            lds_barrier();
             MI_VX_WRITE_OUT(a.out[2]);
         }
     }
@@ -565,7 +525,7 @@ __device__ __forceinline__ void vx_finish_body(unsigned char* __restrict__ lds, 
                 const uint32_t sub = vx_key(g, Pay3{px[k], py[k], pz[k]}) & sub_mask;
                 packed[k] = (sub << 16) | vx_rank(row, sub, i < cn);
             }
-            vx_barrier();
+            lds_barrier();
             uint32_t mine[kVpt];  // points of this thread's voxels in this chunk
 #pragma unroll
             for (int h = 0; h < kVpt; ++h) mine[h] = 0u;
@@ -598,7 +558,7 @@ __device__ __forceinline__ void vx_finish_body(unsigned char* __restrict__ lds, 
 #pragma unroll
             for (int h = 0; h < kVpt; ++h) msum += mine[h];
             uint32_t first[kVpt];
-            first[0] = vx_block_scan<kVxFinWaves>(msum, &all, wtot);
+            first[0] = block_exclusive_scan<kVxFinWaves, true>(msum, &all, wtot);
 #pragma unroll
             for (int h = 1; h < kVpt; ++h) first[h] = first[h - 1] + mine[h - 1];
             if (v0 < V) {
@@ -609,9 +569,9 @@ __device__ __forceinline__ void vx_finish_body(unsigned char* __restrict__ lds, 
                 uint32_t f = 0;
 #pragma unroll
                 for (int h = 0; h < kVpt; ++h) f += (count[h] + mine[h]) > 0u ? 1u : 0u;
-                orank = vx_block_scan<kVxFinWaves>(f, &occupied, wtot);
+                orank = block_exclusive_scan<kVxFinWaves, true>(f, &occupied, wtot);
             } else {
-                vx_barrier();
+                lds_barrier();
             }
 #pragma unroll
             for (int k = 0; k < kItems; ++k) {
@@ -625,7 +585,7 @@ __device__ __forceinline__ void vx_finish_body(unsigned char* __restrict__ lds, 
             }
             if (kNrm) load(nrm, cbase, cn);  // on their way while the points are added up
             else if (kCol) load(col, cbase, cn);
-            vx_barrier();
+            lds_barrier();
             auto add_runs = [&](double (&acc)[kVpt][3]) {
 #pragma unroll
                 for (int h = 0; h < kVpt; ++h)
@@ -647,25 +607,25 @@ __device__ __forceinline__ void vx_finish_body(unsigned char* __restrict__ lds, 
                 }
             };
             if (kNrm) {
-                vx_barrier();
+                lds_barrier();
                 restage();
                 if (kCol) load(col, cbase, cn);
-                vx_barrier();
+                lds_barrier();
                 add_runs(an);
             }
             if (kCol) {
-                vx_barrier();
+                lds_barrier();
                 restage();
-                vx_barrier();
+                lds_barrier();
                 add_runs(ac);
             }
-            if (!last) vx_barrier();  // the stage and the counters are reused
+            if (!last) lds_barrier();  // the stage and the counters are reused
         }
         if (tid == 0) {
             s_bucket = ticket;
             occ[bucket] = occupied;
         }
-        vx_barrier();  // (also: the stage and the counters are free)
+        lds_barrier();  // (also: the stage and the counters are free)
         const int done = bucket;
         bucket = (int)s_bucket;
         if (bucket < B) {  // the next bucket's first chunk: asked for before this one's means are worked out and stored
@@ -690,7 +650,7 @@ __device__ __forceinline__ void vx_finish_body(unsigned char* __restrict__ lds, 
                 if (kCol) tmp_col[slot] = Pay3{(float)(ac[h][0] / cnt), (float)(ac[h][1] / cnt), (float)(ac[h][2] / cnt)};
             }
         }
-        vx_barrier();  // (s_bucket is read by all before the next bucket's end rewrites it -- an empty bucket has no other barrier)
+        lds_barrier();  // (s_bucket is read by all before the next bucket's end rewrites it -- an empty bucket has no other barrier)
     }
 }
 
@@ -709,7 +669,7 @@ static __global__ __launch_bounds__(kVxFinThreads) void vx_finish(const Pay3* __
     const int L = d->L, B = d->B;
     if (threadIdx.x == 0) s_bucket = __hip_atomic_fetch_add(&ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (int b = (int)threadIdx.x; b <= B; b += kVxFinThreads) s_start[b] = bucket_start[b];
-    vx_barrier();
+    lds_barrier();
     if (L > 10) vx_finish_body<kNrm, kCol, 2>(lds, wtot, s_bucket, s_start, pts, nrm, col, g, L, B, ctl, occ, tmp_pts, tmp_nrm, tmp_col);
     else vx_finish_body<kNrm, kCol, 1>(lds, wtot, s_bucket, s_start, pts, nrm, col, g, L, B, ctl, occ, tmp_pts, tmp_nrm, tmp_col);
 }
