@@ -156,6 +156,10 @@ SIGNATURES = {
     "mi_icp_compute_bounds": (_I, [_P, _P, _L, _I, _P, _P, _P]),
     "mi_icp_affine": (_I, [_P, _P, _F, _I, _P, _P, _P, _P, _P, _L, _I]),
     "mi_icp_voxel_downsample": (_I, [_P, _P, _P, _P, _L, _F, _P, _P, _P, C.POINTER(_L), _I]),
+    "mi_icp_select_by_index": (_I, [_P, _P, _P, _P, _L, _P, _L, _I, _P, _P, _P, C.POINTER(_L), _I]),
+    "mi_icp_uniform_downsample": (_I, [_P, _P, _P, _P, _L, _L, _P, _P, _P, C.POINTER(_L), _I]),
+    "mi_icp_remove_statistical_outliers": (_I, [_P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P, C.POINTER(_L), _I]),
+    "mi_icp_remove_radius_outliers": (_I, [_P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P, C.POINTER(_L), _I]),
     "mi_icp_create_from_depth": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _F, _F, _F, _I, _I, _I, _I,
                                       _P, _P, _P, C.POINTER(_L), _I]),
     "mi_icp_compute_rgbd_odometry": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P, C.POINTER(_I), _P, _P, _I]),

@@ -5,6 +5,7 @@
 #pragma once
 #include <cmath>
 #include <memory>
+#include <tuple>
 
 #include "cupoch/camera/pinhole_camera_intrinsic.h"
 #include "cupoch/geometry/image.h"
@@ -144,6 +145,19 @@ public:
     PointCloud& Transform(const Eigen::Matrix4f& transformation) override;
     /// down_sample.cu:170-273
     std::shared_ptr<PointCloud> VoxelDownSample(float voxel_size) const;
+    /// down_sample.cu:40-62,110-129: a gather in the order given; invert: the points not named, ascending (a
+    /// repeated index counts once).  An index outside [0, size) throws.
+    std::shared_ptr<PointCloud> SelectByIndex(const utility::device_vector<size_t>& indices, bool invert = false) const;
+    /// down_sample.cu:275-316: points 0, k, 2k, ... (size / k of them); every_k_points == 0 throws
+    std::shared_ptr<PointCloud> UniformDownSample(size_t every_k_points) const;
+    /// down_sample.cu:317-352: kept iff nb_points + 1 points (itself included) lie within search_radius;
+    /// nb_points + 1 <= knn::NUM_MAX_NN.  Returns the kept cloud and their indices, ascending.
+    std::tuple<std::shared_ptr<PointCloud>, utility::device_vector<size_t>> RemoveRadiusOutliers(
+            size_t nb_points, float search_radius) const;
+    /// down_sample.cu:354-438: kept iff 0 < mean squared distance of the nb_neighbors nearest < mean + std_ratio * std
+    /// (fp64 statistics, include/mi_icp.h); nb_neighbors <= knn::NUM_MAX_NN.  Returns the kept cloud and their indices.
+    std::tuple<std::shared_ptr<PointCloud>, utility::device_vector<size_t>> RemoveStatisticalOutliers(
+            size_t nb_neighbors, float std_ratio) const;
     /// estimate_normals.cu:82-127 (KNN or radius search parameter; up to knn::NUM_MAX_NN neighbours)
     bool EstimateNormals(const knn::KDTreeSearchParam& search_param = knn::KDTreeSearchParamKNN());
 

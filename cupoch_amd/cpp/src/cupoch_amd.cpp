@@ -193,6 +193,82 @@ std::shared_ptr<PointCloud> PointCloud::VoxelDownSample(float voxel_size) const 
     return out;
 }
 
+// the output cloud of a selection: room for `rows` points (and normals / colours where this cloud has them)
+static std::shared_ptr<PointCloud> SelectionOut(const PointCloud& pc, size_t rows) {
+    auto out = std::make_shared<PointCloud>();
+    out->points_.resize(rows);
+    if (pc.HasNormals()) out->normals_.resize(rows);
+    if (pc.HasColors()) out->colors_.resize(rows);
+    return out;
+}
+
+static float* MutPtr(utility::device_vector<Eigen::Vector3f>& v) { return v.empty() ? nullptr : v.data()->data(); }
+
+static void SelectionTrim(PointCloud& out, int64_t m) {
+    out.points_.resize((size_t)m);
+    if (!out.normals_.empty()) out.normals_.resize((size_t)m);
+    if (!out.colors_.empty()) out.colors_.resize((size_t)m);
+}
+
+std::shared_ptr<PointCloud> PointCloud::SelectByIndex(const utility::device_vector<size_t>& indices, bool invert) const {
+    const size_t n = points_.size();
+    auto out = SelectionOut(*this, invert ? n : indices.size());
+    int64_t m = 0;
+    Check(mi_icp_select_by_index(Engine(), Ptr(points_), HasNormals() ? Ptr(normals_) : nullptr,
+                                 HasColors() ? Ptr(colors_) : nullptr, (int64_t)n,
+                                 (const int64_t*)indices.data(), (int64_t)indices.size(), invert ? 1 : 0,
+                                 MutPtr(out->points_), MutPtr(out->normals_), MutPtr(out->colors_), &m, MI_ICP_DEVICE));
+    SelectionTrim(*out, m);
+    return out;
+}
+
+std::shared_ptr<PointCloud> PointCloud::UniformDownSample(size_t every_k_points) const {
+    if (every_k_points == 0) throw std::runtime_error("[UniformDownSample] Illegal sample rate.");  // down_sample.cu:277-280
+    const size_t n = points_.size();
+    auto out = SelectionOut(*this, n / every_k_points);
+    int64_t m = 0;
+    Check(mi_icp_uniform_downsample(Engine(), Ptr(points_), HasNormals() ? Ptr(normals_) : nullptr,
+                                    HasColors() ? Ptr(colors_) : nullptr, (int64_t)n, (int64_t)every_k_points,
+                                    MutPtr(out->points_), MutPtr(out->normals_), MutPtr(out->colors_), &m, MI_ICP_DEVICE));
+    SelectionTrim(*out, m);
+    return out;
+}
+
+// the two filters: the kept cloud and the kept points' indices, ascending
+template <class Fn>
+static std::tuple<std::shared_ptr<PointCloud>, utility::device_vector<size_t>> OutlierFilter(const PointCloud& pc, Fn fn) {
+    const size_t n = pc.points_.size();
+    auto out = SelectionOut(pc, n);
+    utility::device_vector<size_t> idx(n);
+    int64_t m = 0;
+    Check(fn(pc.HasNormals() ? Ptr(pc.normals_) : nullptr, pc.HasColors() ? Ptr(pc.colors_) : nullptr, (int64_t)n,
+             MutPtr(out->points_), MutPtr(out->normals_), MutPtr(out->colors_),
+             n ? (int64_t*)idx.data() : nullptr, &m));
+    SelectionTrim(*out, m);
+    idx.resize((size_t)m);
+    return std::make_tuple(out, std::move(idx));
+}
+
+static int CountArg(size_t v) { return v > 1000000 ? 1000000 : (int)v; }  // (anything above the limit is refused)
+
+std::tuple<std::shared_ptr<PointCloud>, utility::device_vector<size_t>> PointCloud::RemoveRadiusOutliers(
+        size_t nb_points, float search_radius) const {
+    return OutlierFilter(*this, [&](const float* nrm, const float* col, int64_t n, float* op, float* on, float* oc,
+                                    int64_t* idx, int64_t* m) {
+        return mi_icp_remove_radius_outliers(Engine(), Ptr(points_), nrm, col, n, CountArg(nb_points), search_radius,
+                                             op, on, oc, idx, nullptr, m, MI_ICP_DEVICE);
+    });
+}
+
+std::tuple<std::shared_ptr<PointCloud>, utility::device_vector<size_t>> PointCloud::RemoveStatisticalOutliers(
+        size_t nb_neighbors, float std_ratio) const {
+    return OutlierFilter(*this, [&](const float* nrm, const float* col, int64_t n, float* op, float* on, float* oc,
+                                    int64_t* idx, int64_t* m) {
+        return mi_icp_remove_statistical_outliers(Engine(), Ptr(points_), nrm, col, n, CountArg(nb_neighbors), std_ratio,
+                                                  op, on, oc, idx, nullptr, m, MI_ICP_DEVICE);
+    });
+}
+
 bool PointCloud::EstimateNormals(const knn::KDTreeSearchParam& search_param) {
     normals_.resize(points_.size());
     if (points_.empty()) return true;

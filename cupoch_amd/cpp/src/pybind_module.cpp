@@ -2,7 +2,7 @@
 // surface (namespace cupoch, libcupoch_amd.so) instead of the CUDA library.
 //
 // Same module layout, names, defaults and property names as src/python/cupoch_pybind of the reference:
-//   cupoch_pybind.utility       Vector3fVector (device vector wrapper with .cpu()), initialize_allocator
+//   cupoch_pybind.utility       Vector3fVector, ULongVector (device vector wrappers with .cpu()), initialize_allocator
 //                               (src/python/cupoch_pybind/utility/eigen.cpp:123-200, cupoch_pybind.cpp:46-49)
 //   cupoch_pybind.geometry      PointCloud, KDTreeSearchParamKNN / Radius, KDTreeFlann
 //                               (geometry/pointcloud.cpp:33-160, geometry/kdtreeflann.cpp)
@@ -115,6 +115,25 @@ struct Vector2iVector {
         std::vector<Eigen::Vector2i> h((size_t)a.shape(0));
         if (!h.empty()) std::memcpy((void*)h.data(), a.data(), h.size() * sizeof(Eigen::Vector2i));
         data = h;
+    }
+};
+
+// utility.ULongVector: device_vector<size_t> (utility/eigen.cpp:237), the indices the outlier filters return and
+// select_by_index takes; constructed from a 1-D integer array, .cpu() gives int64
+struct ULongVector {
+    utility::device_vector<size_t> data;
+    ULongVector() = default;
+    explicit ULongVector(const py::array_t<int64_t, py::array::c_style | py::array::forcecast>& a) {
+        if (a.ndim() != 1) throw std::invalid_argument("expected a 1-D integer array");
+        std::vector<size_t> h((size_t)a.shape(0));
+        if (!h.empty()) std::memcpy((void*)h.data(), a.data(), h.size() * sizeof(size_t));
+        data = h;
+    }
+    py::array_t<int64_t> cpu() const {
+        const std::vector<size_t> h = data.to_host();
+        py::array_t<int64_t> a((py::ssize_t)h.size());
+        if (!h.empty()) std::memcpy(a.mutable_data(), (const void*)h.data(), h.size() * sizeof(size_t));
+        return a;
     }
 };
 
@@ -292,6 +311,11 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             .def(py::init<const farray&>(), "array"_a)
             .def("cpu", &Vector3fVector::cpu)
             .def("__len__", [](const Vector3fVector& v) { return v.data.size(); });
+    py::class_<ULongVector>(mu, "ULongVector")
+            .def(py::init<>())
+            .def(py::init<const py::array_t<int64_t, py::array::c_style | py::array::forcecast>&>(), "array"_a)
+            .def("cpu", &ULongVector::cpu)
+            .def("__len__", [](const ULongVector& v) { return v.data.size(); });
     py::class_<Vector2iVector>(mu, "Vector2iVector")
             .def(py::init<>())
             .def(py::init<const py::array_t<int, py::array::c_style | py::array::forcecast>&>(), "array"_a)
@@ -360,6 +384,36 @@ PYBIND11_MODULE(cupoch_pybind, m) {
                  },
                  "scale"_a, "center"_a = true)
             .def("voxel_down_sample", &geometry::PointCloud::VoxelDownSample, "voxel_size"_a)
+            .def(
+                    "select_by_index",
+                    [](const geometry::PointCloud& pc, const py::object& indices, bool invert) {
+                        if (py::isinstance<ULongVector>(indices))
+                            return pc.SelectByIndex(indices.cast<const ULongVector&>().data, invert);
+                        return pc.SelectByIndex(
+                                ULongVector(indices.cast<py::array_t<int64_t, py::array::c_style | py::array::forcecast>>())
+                                        .data,
+                                invert);
+                    },
+                    "indices"_a, "invert"_a = false)
+            .def("uniform_down_sample", &geometry::PointCloud::UniformDownSample, "every_k_points"_a)
+            .def(
+                    "remove_radius_outlier",
+                    [](const geometry::PointCloud& pc, size_t nb_points, float search_radius) {
+                        auto res = pc.RemoveRadiusOutliers(nb_points, search_radius);
+                        ULongVector idx;
+                        idx.data = std::move(std::get<1>(res));
+                        return std::make_tuple(std::get<0>(res), idx);
+                    },
+                    "nb_points"_a, "radius"_a)
+            .def(
+                    "remove_statistical_outlier",
+                    [](const geometry::PointCloud& pc, size_t nb_neighbors, float std_ratio) {
+                        auto res = pc.RemoveStatisticalOutliers(nb_neighbors, std_ratio);
+                        ULongVector idx;
+                        idx.data = std::move(std::get<1>(res));
+                        return std::make_tuple(std::get<0>(res), idx);
+                    },
+                    "nb_neighbors"_a, "std_ratio"_a)
             .def("estimate_normals", &geometry::PointCloud::EstimateNormals,
                  "search_param"_a = knn::KDTreeSearchParamKNN())
             .def("__len__", [](const geometry::PointCloud& pc) { return pc.points_.size(); });

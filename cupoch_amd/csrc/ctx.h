@@ -2,8 +2,10 @@
 // allocation / staging helpers, and the declarations of the host-side functions one unit offers the others.
 //   mi_icp.hip       context life cycle, the correspondence search, the reduction, the device-resident loop
 //   mi_build.hip     target tree (kd cells, groups, levels, halos), source staging, the match-order re-sort
-//   mi_geometry.hip  Transform / bounds / affine / covariances / VoxelDownSample / depth frames / RGB-D odometry / colours
-//   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry
+//   mi_geometry.hip  Transform / bounds / affine / covariances / VoxelDownSample / SelectByIndex / UniformDownSample /
+//                    depth frames / RGB-D odometry / colours
+//   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry,
+//                    RemoveStatisticalOutliers / RemoveRadiusOutliers
 //   mi_comm.hip      the ranks' exchange: mailbox, device inboxes, in-library RCCL, self-test and choice
 //   mi_debug.hip     include/mi_icp_debug.h (test-only entry points)
 // Kernels without template parameters are `static` in their headers, so a header may be included by several units.
@@ -337,6 +339,11 @@ bool planes_available(const mi_icp_ctx* c);
 int launch_locate_by_planes(mi_icp_ctx* c, const Xform& X, const DevLoop* loop, int gated);
 // ---- mi_geometry.hip
 int occupancy_geometry(int which);
+// The points whose flags[0..n) are set, ascending (select.h: exclusive_scan_u32 + select_gather), into out[] (the
+// caller's, staged when mem_kind is MI_ICP_HOST) and their original indices into out_idx (may be null); *m = their
+// count.  One wait on the stream, which also brings back the device word *status (may be null) into *status_out.
+int compact_by_flags(mi_icp_ctx* c, const uint32_t* flags, int64_t n, const float* const in[3], float* const out[3],
+                     int64_t* out_idx, int mem_kind, const uint32_t* status, int64_t* m, uint32_t* status_out);
 // ---- mi_comm.hip
 MailArgs mail_args(const mi_icp_ctx* c);
 void mailbox_close(mi_icp_ctx* c);

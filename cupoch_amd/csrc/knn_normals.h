@@ -22,6 +22,10 @@
 // in the tangent plane over the lane's neighbours (nearest one -- the point
 // itself -- skipped) and writes it in the tree's order for the colored-ICP
 // reduction.
+//
+// OUT = 2 and 3 reuse phases A/B for RemoveStatisticalOutliers / RemoveRadiusOutliers
+// (geometry/down_sample.cu:317-438): phase C writes one number per point, the mean of the
+// neighbours' squared distances or their count (knn_mean_d2; the tail is csrc/select.h).
 #pragma once
 #include "device_utils.h"
 #include "eigen3.h"
@@ -402,6 +406,17 @@ __device__ __forceinline__ float3 knn_normal(const float* tblk_g, const KnnList<
     return make_float3(nx, ny, nz);
 }
 
+// ---- C'': mean of the lane's neighbours' squared distances (RemoveStatisticalOutliers, down_sample.cu:368-379).
+// Only the distance column is read, not the index slab.  The fp32 d2 are added in fp64 -- exact for up to 100 of them
+// whatever their order, so the result does not depend on the order the walk offered the candidates in -- divided in
+// fp64 by the count and rounded once.  No neighbour at all gives 0 (the point is then removed).
+template <int KCAP>
+__device__ __forceinline__ float knn_mean_d2(const KnnList<KCAP>& l) {
+    double s = 0.0;
+    for (int t = 0; t < l.st.count; ++t) s += (double)l.kd2[t * 64 + l.lane];
+    return l.st.count > 0 ? (float)(s / (double)l.st.count) : 0.0f;
+}
+
 // ---- C': colour gradient (colored_icp.cu:88-120) of the lane's point (query q, sorted index i) in its tangent plane
 template <int KCAP>
 __device__ __forceinline__ float3 knn_color_gradient(const float* tblk_g, const float4* tnrm, int64_t i, float qx,
@@ -464,7 +479,9 @@ __device__ __forceinline__ float3 knn_color_gradient(const float* tblk_g, const 
 
 // OUT 0: normals_out[orig] (3 floats).  OUT 1: tgrad[sorted] (float4, w = 0) and, when
 // not null, normals_out[orig] receives the gradient for inspection; tnrm = sorted target
-// normals with the intensity in .w.
+// normals with the intensity in .w.  OUT 2: normals_out[orig] = the mean squared distance of
+// the lane's neighbours (knn_mean_d2).  OUT 3: normals_out, read as int32, [orig] = the number
+// of neighbours found (at most k; with r2 finite, those with d2 < r2).  The outlier filters.
 template <int OUT, int KCAP = kMaxKnn>
 __global__ __launch_bounds__(64) void knn_normals_kernel(
         const float* __restrict__ records_g, const float* __restrict__ tblk_g, const int32_t* __restrict__ tidx_g,
@@ -499,12 +516,18 @@ __global__ __launch_bounds__(64) void knn_normals_kernel(
         knn_walk<true>(records_g, tblk_g, leaf_first, valid && k > 0, qx, qy, qz, (uint32_t)seed_lo, (uint32_t)seed_hi, l);
 
         if (!valid) return;
-        const float3 v = OUT == 1 ? knn_color_gradient(tblk_g, tnrm, i, qx, qy, qz, l) : knn_normal(tblk_g, l);
-        if (OUT == 1) tgrad[i] = make_float4(v.x, v.y, v.z, 0.0f);
-        if (OUT == 0 || normals_out) {
-            normals_out[(int64_t)orig * 3] = v.x;
-            normals_out[(int64_t)orig * 3 + 1] = v.y;
-            normals_out[(int64_t)orig * 3 + 2] = v.z;
+        if constexpr (OUT == 2) {
+            normals_out[orig] = knn_mean_d2(l);
+        } else if constexpr (OUT == 3) {
+            reinterpret_cast<int32_t*>(normals_out)[orig] = l.st.count;
+        } else {
+            const float3 v = OUT == 1 ? knn_color_gradient(tblk_g, tnrm, i, qx, qy, qz, l) : knn_normal(tblk_g, l);
+            if (OUT == 1) tgrad[i] = make_float4(v.x, v.y, v.z, 0.0f);
+            if (OUT == 0 || normals_out) {
+                normals_out[(int64_t)orig * 3] = v.x;
+                normals_out[(int64_t)orig * 3 + 1] = v.y;
+                normals_out[(int64_t)orig * 3 + 2] = v.z;
+            }
         }
     });
 }

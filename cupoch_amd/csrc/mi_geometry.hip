@@ -1,5 +1,6 @@
 // mi_geometry.hip -- the geometry entry points beside the registration: Transform, bounds / centre, Translate / Scale /
 // Rotate, GICP covariances, VoxelDownSample, depth / RGB-D frame -> cloud, RGB-D odometry, colours
+// SelectByIndex / UniformDownSample, and the compaction behind them and the outlier filters
 // (one translation unit of libmi_icp.so; csrc/ctx.h lists them)
 #include "ctx.h"
 #include "depth_kernels.h"
@@ -7,6 +8,7 @@
 #include "lbvh.h"
 #include "odometry.h"
 #include "reduce.h"
+#include "select.h"
 #include "voxel_dense.h"
 
 using namespace mi;
@@ -25,6 +27,56 @@ int occupancy_geometry(int which) {
     else return -1;
     return e == hipSuccess ? blocks : -2;
 }
+
+// Where up to `count` selected points go: the caller's arrays, or (MI_ICP_HOST) staging buffers; nullptr for an
+// attribute that is not there.  select_out_back copies `m` of them to the caller.
+static int select_out(mi_icp_ctx* c, const float* const in[3], float* const out[3], int64_t count, int mem_kind,
+                      float* dst[3]) {
+    for (int k = 0; k < 3; ++k) {
+        dst[k] = in[k] ? out[k] : nullptr;
+        if (in[k] && mem_kind == MI_ICP_HOST) TRY(ensure(c, c->vpay[k], (size_t)count * 3, &dst[k]));
+    }
+    return MI_ICP_OK;
+}
+
+static int select_out_back(mi_icp_ctx* c, float* const dst[3], float* const out[3], int64_t m, int mem_kind) {
+    if (mem_kind == MI_ICP_HOST)
+        for (int k = 0; k < 3; ++k)
+            if (dst[k]) TRY(from_device(c, (const float*)dst[k], out[k], (size_t)m * 3, mem_kind));
+    return MI_ICP_OK;
+}
+
+int compact_by_flags(mi_icp_ctx* c, const uint32_t* flags, int64_t n, const float* const in[3], float* const out[3],
+                     int64_t* out_idx, int mem_kind, const uint32_t* status, int64_t* m, uint32_t* status_out) {
+    *m = 0;
+    if (status_out) *status_out = 0u;
+    if (n <= 0) return MI_ICP_OK;
+    uint32_t *pos, *tmp;
+    TRY(ensure(c, c->dense_idx, (size_t)n, &pos));
+    TRY(ensure(c, c->scan_tmp, (size_t)scan_num_tiles(n) + 2, &tmp));
+    exclusive_scan_u32(c->stream, flags, pos, n, tmp);
+    KCHK(c);
+    float* dst[3];
+    TRY(select_out(c, in, out, n, mem_kind, dst));
+    int64_t* didx = out_idx;
+    if (out_idx && mem_kind == MI_ICP_HOST) TRY(ensure(c, c->pairs_out, (size_t)n, &didx));
+    select_gather<<<blocks_for(n), 256, 0, c->stream>>>(flags, pos, n, in[0], in[1], in[2], dst[0], dst[1], dst[2], didx);
+    KCHK(c);
+    // the count (and the caller's status word) come back with the one wait of the call
+    HIPCHK(c, hipMemcpyAsync(c->u_host, tmp + scan_num_tiles(n), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (status) HIPCHK(c, hipMemcpyAsync(c->u_host + 1, status, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t cnt = (int64_t)c->u_host[0];
+    if (status_out && status) *status_out = c->u_host[1];
+    if (mem_kind == MI_ICP_HOST) {
+        TRY(select_out_back(c, dst, out, cnt, mem_kind));
+        if (out_idx) TRY(from_device(c, (const int64_t*)didx, out_idx, (size_t)cnt, mem_kind));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    *m = cnt;
+    return MI_ICP_OK;
+}
+
 }  // namespace eng
 }  // namespace mi
 
@@ -512,6 +564,92 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
     KCHK(c);
     TRY(voxel_out_back(c, dst, out, nvox, mem_kind));
     *m = nvox;
+    return MI_ICP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// PointCloud::SelectByIndex (geometry/down_sample.cu:40-62,110-129)
+int mi_icp_select_by_index(mi_icp_ctx* c, const float* xyz, const float* normals, const float* colors, int64_t n,
+                           const int64_t* indices, int64_t n_indices, int invert, float* out_xyz, float* out_normals,
+                           float* out_colors, int64_t* m, int mem_kind) {
+    TRY(check_ctx(c));
+    if (!m) return fail(c, MI_ICP_ERR_INVALID, "select_by_index: m is null");
+    *m = 0;
+    if (n < 0 || n > 0x7fffff00ll || n_indices < 0 || n_indices > 0x7fffff00ll)
+        return fail(c, MI_ICP_ERR_INVALID, "select_by_index: bad size");
+    if ((n > 0 && !xyz) || (n_indices > 0 && !indices)) return fail(c, MI_ICP_ERR_INVALID, "select_by_index: null buffer");
+    const int64_t count = invert ? n : n_indices;  // the most points the output can hold
+    if (count > 0 && (!out_xyz || (normals && !out_normals) || (colors && !out_colors)))
+        return fail(c, MI_ICP_ERR_INVALID, "select_by_index: null buffer");
+    if (n == 0 && n_indices > 0) return fail(c, MI_ICP_ERR_INVALID, "select_by_index: index out of range [0, 0)");
+    if (count == 0) return MI_ICP_OK;
+
+    const float* in[3];
+    TRY(to_device(c, xyz, (size_t)n * 3, mem_kind, c->stage[0], &in[0]));
+    TRY(to_device(c, normals, (size_t)n * 3, mem_kind, c->stage[1], &in[1]));
+    TRY(to_device(c, colors, (size_t)n * 3, mem_kind, c->stage[2], &in[2]));
+    const int64_t* idx = nullptr;
+    TRY(to_device(c, indices, (size_t)n_indices, mem_kind, c->keys0, &idx));
+    float* const out[3] = {out_xyz, out_normals, out_colors};
+    uint32_t* flags;
+    TRY(ensure(c, c->flags, (size_t)n + 1, &flags));  // [n]: the status word (an index outside [0, n))
+    uint32_t* status = flags + n;
+    uint32_t bad = 0u;
+    int64_t got = 0;
+    if (!invert) {
+        HIPCHK(c, hipMemsetAsync(status, 0, sizeof(uint32_t), c->stream));
+        float* dst[3];
+        TRY(select_out(c, in, out, n_indices, mem_kind, dst));
+        select_list<<<blocks_for(n_indices), 256, 0, c->stream>>>(idx, n_indices, n, in[0], in[1], in[2], dst[0], dst[1],
+                                                                  dst[2], status);
+        KCHK(c);
+        TRY(select_out_back(c, dst, out, n_indices, mem_kind));
+        HIPCHK(c, hipMemcpyAsync(c->u_host + 1, status, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        bad = c->u_host[1];
+        got = n_indices;
+    } else {
+        // the points not named, ascending; a repeated index counts once (the reference sizes the output n - n_indices)
+        HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)flags, 1, (size_t)n, c->stream));
+        HIPCHK(c, hipMemsetAsync(status, 0, sizeof(uint32_t), c->stream));
+        if (n_indices > 0) {
+            select_mark<<<blocks_for(n_indices), 256, 0, c->stream>>>(idx, n_indices, n, flags, status);
+            KCHK(c);
+        }
+        TRY(compact_by_flags(c, flags, n, in, out, nullptr, mem_kind, status, &got, &bad));
+    }
+    if (bad) return fail(c, MI_ICP_ERR_INVALID, "select_by_index: index out of range [0, %lld)", (long long)n);
+    *m = got;
+    return MI_ICP_OK;
+}
+
+// PointCloud::UniformDownSample (geometry/down_sample.cu:275-316): points 0, k, 2k, ... -- n / k of them (the size the
+// reference allocates).  A strided copy per attribute, no kernel.
+int mi_icp_uniform_downsample(mi_icp_ctx* c, const float* xyz, const float* normals, const float* colors, int64_t n,
+                              int64_t every_k_points, float* out_xyz, float* out_normals, float* out_colors, int64_t* m,
+                              int mem_kind) {
+    TRY(check_ctx(c));
+    if (!m) return fail(c, MI_ICP_ERR_INVALID, "uniform_downsample: m is null");
+    *m = 0;
+    if (n < 0) return fail(c, MI_ICP_ERR_INVALID, "uniform_downsample: bad size");
+    if (every_k_points <= 0) return fail(c, MI_ICP_ERR_INVALID, "uniform_downsample: every_k_points must be positive");
+    const int64_t cnt = n / every_k_points;
+    if (cnt == 0) return MI_ICP_OK;
+    if (!xyz || !out_xyz || (normals && !out_normals) || (colors && !out_colors))
+        return fail(c, MI_ICP_ERR_INVALID, "uniform_downsample: null buffer");
+    const float* const in[3] = {xyz, normals, colors};
+    float* const out[3] = {out_xyz, out_normals, out_colors};
+    const size_t row = 3 * sizeof(float), pitch = row * (size_t)every_k_points;
+    for (int k = 0; k < 3; ++k) {
+        if (!in[k]) continue;
+        if (mem_kind == MI_ICP_DEVICE) {
+            HIPCHK(c, hipMemcpy2DAsync(out[k], row, in[k], pitch, row, (size_t)cnt, hipMemcpyDeviceToDevice, c->stream));
+        } else {  // host arrays: the same strided copy on the host
+            for (int64_t j = 0; j < cnt; ++j) std::memcpy(out[k] + j * 3, in[k] + j * 3 * every_k_points, row);
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *m = cnt;
     return MI_ICP_OK;
 }
 

@@ -1,8 +1,10 @@
 // mi_knn.hip -- k-nearest-neighbour work on the target tree: PointCloud::EstimateNormals, KDTreeFlann::SearchKNN /
-// SearchRadius, Colored ICP's colour gradients and its registration entry (knn_normals.h)
+// SearchRadius, Colored ICP's colour gradients and its registration entry, RemoveStatisticalOutliers /
+// RemoveRadiusOutliers (knn_normals.h, select.h)
 // (one translation unit of libmi_icp.so; csrc/ctx.h lists them)
 #include "ctx.h"
 #include "knn_normals.h"
+#include "select.h"
 
 using namespace mi;
 using namespace mi::eng;
@@ -49,7 +51,8 @@ int knn_launch(mi_icp_ctx* c, int k, uint32_t nblocks, Pick pick, Args... args) 
     return go(pick(Cap<kMaxKnnBig>()));
 }
 
-// knn_normals_kernel<OUT> over the target's leaves: EstimateNormals (OUT = 0) or the colour gradients (OUT = 1)
+// knn_normals_kernel<OUT> over the target's leaves: EstimateNormals (OUT = 0), the colour gradients (OUT = 1), the
+// outlier filters' mean squared distance (OUT = 2) or neighbour count (OUT = 3)
 template <int OUT>
 int launch_knn_normals(mi_icp_ctx* c, int k, float r2, float* out, const float4* tnrm, float4* tgrad) {
     return knn_launch(c, k, (uint32_t)((c->nleaf + 7) / 8), [](auto kc) { return knn_normals_kernel<OUT, decltype(kc)::value>; },
@@ -98,6 +101,95 @@ int mi_icp_estimate_normals_knn(mi_icp_ctx* c, const float* xyz, int64_t n, int 
 int mi_icp_estimate_normals_radius(mi_icp_ctx* c, const float* xyz, int64_t n, float radius, int max_nn,
                                    float* normals, int mem_kind) {
     return estimate_normals_impl(c, xyz, n, max_nn, radius * radius, normals, mem_kind);
+}
+
+// ---------------------------------------------------------------------------
+// PointCloud::RemoveStatisticalOutliers / RemoveRadiusOutliers (geometry/down_sample.cu:317-438).  The cloud gets a tree
+// in the private scratch context, as in EstimateNormals (the caller's target, source, correspondences and loop state
+// survive); knn_normals_kernel<2 | 3> leaves one number per point, and the tail (select.h) keeps, compacts and gathers
+// on the stream -- the count comes back with the one wait at the end.
+//   radius = false: k = nb_neighbors nearest (r2 = +inf), kept iff 0 < avg < mean + std_ratio * std
+//   radius = true:  k = nb_points + 1 nearest with d2 < r2, kept iff all k were found
+static int outlier_impl(mi_icp_ctx* c, const char* what, bool radius, const float* xyz, const float* normals,
+                        const float* colors, int64_t n, int k, float r2, double std_ratio, float* out_xyz,
+                        float* out_normals, float* out_colors, int64_t* out_indices, void* stat_out, int64_t* m,
+                        int mem_kind) {
+    if (n == 0) return MI_ICP_OK;
+    if (!c->aux) {
+        const int rc = mi_icp_create(c->device, &c->aux);
+        if (rc != MI_ICP_OK) return fail(c, rc, "%s: cannot create the scratch context", what);
+    }
+    mi_icp_ctx* a = c->aux;
+    a->stream = c->stream;
+    auto run = [&]() -> int {
+        const float* in[3];
+        TRY(to_device(a, xyz, (size_t)n * 3, mem_kind, a->stage[0], &in[0]));
+        TRY(to_device(a, normals, (size_t)n * 3, mem_kind, a->stage[1], &in[1]));
+        TRY(to_device(a, colors, (size_t)n * 3, mem_kind, a->stage[2], &in[2]));
+        TRY(mi_icp_set_target(a, in[0], nullptr, nullptr, n, MI_ICP_DEVICE));
+        float* stat = (float*)stat_out;  // float avg or int32 count, [n] in the cloud's order
+        if (!stat || mem_kind == MI_ICP_HOST) TRY(ensure(a, a->stage[3], (size_t)n, &stat));
+        uint32_t* flags;
+        TRY(ensure(a, a->flags, (size_t)n, &flags));
+        if (!radius) {
+            TRY(launch_knn_normals<2>(a, k, INFINITY, stat, nullptr, nullptr));
+            double *part, *thr;
+            const int blocks = std::min(kOutlierBlocks, blocks_for(n));
+            TRY(ensure(a, a->partial, (size_t)kOutlierBlocks * 4, &part));
+            TRY(ensure(a, a->sys_dev, (size_t)kSysSize, &thr));
+            outlier_stats_partial<<<blocks, 256, 0, a->stream>>>(stat, n, part);
+            outlier_stats_final<<<1, 64, 0, a->stream>>>(part, blocks, n, std_ratio, thr);
+            outlier_flags_stat<<<blocks_for(n), 256, 0, a->stream>>>(stat, n, thr, flags);
+        } else {
+            TRY(launch_knn_normals<3>(a, k, r2, stat, nullptr, nullptr));
+            outlier_flags_radius<<<blocks_for(n), 256, 0, a->stream>>>((const int32_t*)stat, n, k, flags);
+        }
+        KCHK(a);
+        if (stat_out && mem_kind == MI_ICP_HOST) TRY(from_device(a, (const float*)stat, (float*)stat_out, (size_t)n, mem_kind));
+        float* const out[3] = {out_xyz, out_normals, out_colors};
+        return compact_by_flags(a, flags, n, in, out, out_indices, mem_kind, nullptr, m, nullptr);
+    };
+    const int rc = run();
+    if (rc != MI_ICP_OK) return fail(c, rc, "%s: %s", what, a->err.c_str());
+    return MI_ICP_OK;
+}
+
+static int outlier_args(mi_icp_ctx* c, const char* what, const float* xyz, const float* normals, const float* colors,
+                        int64_t n, float* out_xyz, float* out_normals, float* out_colors, int64_t* m) {
+    if (!m) return fail(c, MI_ICP_ERR_INVALID, "%s: m is null", what);
+    *m = 0;
+    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    if (n > 0 && (!xyz || !out_xyz || (normals && !out_normals) || (colors && !out_colors)))
+        return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+    return MI_ICP_OK;
+}
+
+int mi_icp_remove_statistical_outliers(mi_icp_ctx* c, const float* xyz, const float* normals, const float* colors,
+                                       int64_t n, int nb_neighbors, float std_ratio, float* out_xyz, float* out_normals,
+                                       float* out_colors, int64_t* out_indices, float* avg_d2, int64_t* m, int mem_kind) {
+    const char* what = "remove_statistical_outliers";
+    TRY(check_ctx(c));
+    TRY(outlier_args(c, what, xyz, normals, colors, n, out_xyz, out_normals, out_colors, m));
+    if (nb_neighbors < 1) return fail(c, MI_ICP_ERR_INVALID, "%s: nb_neighbors must be positive", what);
+    if (!(std_ratio > 0.0f)) return fail(c, MI_ICP_ERR_INVALID, "%s: std_ratio must be positive", what);
+    if (nb_neighbors > kKnnLimit)
+        return fail(c, MI_ICP_ERR_INVALID, "%s: more than %d neighbours (knn::NUM_MAX_NN) are not supported", what, kKnnLimit);
+    return outlier_impl(c, what, false, xyz, normals, colors, n, nb_neighbors, INFINITY, (double)std_ratio, out_xyz,
+                        out_normals, out_colors, out_indices, avg_d2, m, mem_kind);
+}
+
+int mi_icp_remove_radius_outliers(mi_icp_ctx* c, const float* xyz, const float* normals, const float* colors, int64_t n,
+                                  int nb_points, float radius, float* out_xyz, float* out_normals, float* out_colors,
+                                  int64_t* out_indices, int32_t* counts, int64_t* m, int mem_kind) {
+    const char* what = "remove_radius_outliers";
+    TRY(check_ctx(c));
+    TRY(outlier_args(c, what, xyz, normals, colors, n, out_xyz, out_normals, out_colors, m));
+    if (nb_points < 1) return fail(c, MI_ICP_ERR_INVALID, "%s: nb_points must be positive", what);
+    if (!(radius > 0.0f)) return fail(c, MI_ICP_ERR_INVALID, "%s: search_radius must be positive", what);
+    if (nb_points + 1 > kKnnLimit)
+        return fail(c, MI_ICP_ERR_INVALID, "%s: nb_points + 1 above %d (knn::NUM_MAX_NN) is not supported", what, kKnnLimit);
+    return outlier_impl(c, what, true, xyz, normals, colors, n, nb_points + 1, radius * radius, 0.0, out_xyz, out_normals,
+                        out_colors, out_indices, counts, m, mem_kind);
 }
 
 // ---------------------------------------------------------------------------

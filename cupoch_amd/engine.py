@@ -368,6 +368,85 @@ class Engine:
         cut = lambda t: None if t is None else t[:k]
         return cut(op) if op is not None else np.empty((0, 3), np.float32), cut(on), cut(oc)
 
+    # -- PointCloud::SelectByIndex / UniformDownSample / Remove*Outliers (down_sample.cu:40-438) -------------
+    def _cloud_args(self, points, normals, colors):
+        p = _Buf(points, np.float32, 3, self.device)
+        n = _Buf(normals, np.float32, 3, self.device)
+        c = _Buf(colors, np.float32, 3, self.device)
+        return p, n, c, self._same_kind(p, n, c)
+
+    @staticmethod
+    def _out(kind, like, rows, cols=3, dtype=np.float32):
+        """an output array of `rows` entries on the side of `like` (a _Buf); (array, pointer)"""
+        shape = (rows, cols) if cols else (rows,)
+        if kind == MI_ICP_DEVICE:
+            tdt = {np.float32: torch.float32, np.int32: torch.int32, np.int64: torch.int64}[dtype]
+            t = torch.empty(shape, dtype=tdt, device=like.keep.device)
+            return t, C.c_void_p(t.data_ptr())
+        a = np.empty(shape, dtype)
+        return a, a.ctypes.data_as(C.c_void_p)
+
+    def _cloud_outputs(self, kind, p, n, c, rows):
+        op = self._out(kind, p, rows)
+        on = self._out(kind, p, rows) if n.ptr is not None else (None, None)
+        oc = self._out(kind, p, rows) if c.ptr is not None else (None, None)
+        return op, on, oc
+
+    def _outlier_filter(self, fn, points, k, param, normals, colors, stat_dtype):
+        p, n, c, kind = self._cloud_args(points, normals, colors)
+        (op, pp), (on, pn), (oc, pc) = self._cloud_outputs(kind, p, n, c, p.n)
+        idx, pidx = self._out(kind, p, p.n, 0, np.int64)
+        stat, pstat = self._out(kind, p, p.n, 0, stat_dtype)
+        m = C.c_int64(0)
+        self._chk(fn(self._ctx, p.ptr, n.ptr, c.ptr, p.n, int(k), float(param), pp, pn, pc, pidx, pstat, C.byref(m), kind))
+        k = int(m.value)
+        cut = lambda t: None if t is None else t[:k]
+        return cut(op), cut(on), cut(oc), idx[:k], stat
+
+    def remove_statistical_outliers(self, points, nb_neighbors, std_ratio, normals=None, colors=None):
+        """PointCloud::RemoveStatisticalOutliers (down_sample.cu:354-438).  Returns (points, normals or None,
+        colors or None, indices int64 ascending, avg_d2 per input point), on the side of `points`."""
+        return self._outlier_filter(self._L.mi_icp_remove_statistical_outliers, points, nb_neighbors, std_ratio,
+                                    normals, colors, np.float32)
+
+    def remove_radius_outliers(self, points, nb_points, radius, normals=None, colors=None):
+        """PointCloud::RemoveRadiusOutliers (down_sample.cu:317-352).  Returns (points, normals or None,
+        colors or None, indices int64 ascending, counts int32 per input point, capped at nb_points + 1)."""
+        return self._outlier_filter(self._L.mi_icp_remove_radius_outliers, points, nb_points, radius,
+                                    normals, colors, np.int32)
+
+    def select_by_index(self, points, indices, invert=False, normals=None, colors=None):
+        """PointCloud::SelectByIndex (down_sample.cu:40-62,110-129).  indices: anything 1-D integer (a tensor on
+        the points' device, a numpy array, a list); returns (points, normals or None, colors or None)."""
+        p, n, c, kind = self._cloud_args(points, normals, colors)
+        if kind == MI_ICP_DEVICE:
+            ix = torch.as_tensor(indices).to(device=p.keep.device, dtype=torch.int64).reshape(-1).contiguous() \
+                if _is_tensor(indices) else torch.from_numpy(np.ascontiguousarray(np.asarray(indices, np.int64).reshape(-1))).to(p.keep.device)
+            pix, nix = C.c_void_p(ix.data_ptr()), int(ix.shape[0])
+        else:
+            ix = indices.detach().cpu().numpy() if _is_tensor(indices) else indices
+            ix = np.ascontiguousarray(np.asarray(ix, np.int64).reshape(-1))
+            pix, nix = ix.ctypes.data_as(C.c_void_p), int(ix.shape[0])
+        rows = p.n if invert else nix
+        (op, pp), (on, pn), (oc, pc) = self._cloud_outputs(kind, p, n, c, rows)
+        m = C.c_int64(0)
+        self._chk(self._L.mi_icp_select_by_index(self._ctx, p.ptr, n.ptr, c.ptr, p.n, pix, nix, int(bool(invert)),
+                                                 pp, pn, pc, C.byref(m), kind))
+        k = int(m.value)
+        cut = lambda t: None if t is None else t[:k]
+        return cut(op), cut(on), cut(oc)
+
+    def uniform_downsample(self, points, every_k_points, normals=None, colors=None):
+        """PointCloud::UniformDownSample (down_sample.cu:275-316): points 0, k, 2k, ... (n // k of them)."""
+        p, n, c, kind = self._cloud_args(points, normals, colors)
+        k = int(every_k_points)
+        rows = p.n // k if k > 0 else 0
+        (op, pp), (on, pn), (oc, pc) = self._cloud_outputs(kind, p, n, c, rows)
+        m = C.c_int64(0)
+        self._chk(self._L.mi_icp_uniform_downsample(self._ctx, p.ptr, n.ptr, c.ptr, p.n, k, pp, pn, pc,
+                                                    C.byref(m), kind))
+        return op[:int(m.value)], on, oc
+
     def create_from_depth(self, depth, intrinsic4, extrinsic=None, color=None, depth_scale=1000.0,
                           depth_trunc=1000.0, depth_cutoff=-1.0, stride=1, rgbd=False,
                           compute_normals=False, valid_only=True):

@@ -263,6 +263,47 @@ class PointCloud:
             out._colors = utility.Vector3fVector(c2.clone())
         return out
 
+    # PointCloud::SelectByIndex / UniformDownSample / Remove*Outliers (down_sample.cu:40-438) ---------------------
+    def _engine_args(self):
+        eng = get_engine(self._points.tensor.device.index)
+        n = self._normals.tensor if self.has_normals() else None
+        c = self._colors.tensor if self.has_colors() else None
+        return eng, n, c
+
+    @staticmethod
+    def _made(p, n, c):
+        out = PointCloud()
+        out._points = utility.Vector3fVector(p.clone())
+        if n is not None:
+            out._normals = utility.Vector3fVector(n.clone())
+        if c is not None:
+            out._colors = utility.Vector3fVector(c.clone())
+        return out
+
+    def select_by_index(self, indices, invert=False):
+        """points, normals and colours at `indices` (a ULongVector, list, numpy array or tensor), in that order;
+        invert=True: the points not named, ascending"""
+        if isinstance(indices, utility.DeviceVector):
+            indices = indices.tensor
+        eng, n, c = self._engine_args()
+        return self._made(*eng.select_by_index(self._points.tensor, indices, bool(invert), n, c))
+
+    def uniform_down_sample(self, every_k_points):
+        eng, n, c = self._engine_args()
+        return self._made(*eng.uniform_downsample(self._points.tensor, int(every_k_points), n, c))
+
+    def remove_statistical_outlier(self, nb_neighbors, std_ratio):
+        """(PointCloud of the kept points, ULongVector of their indices)"""
+        eng, n, c = self._engine_args()
+        p2, n2, c2, idx, _ = eng.remove_statistical_outliers(self._points.tensor, int(nb_neighbors), float(std_ratio), n, c)
+        return self._made(p2, n2, c2), utility.ULongVector(idx.clone())
+
+    def remove_radius_outlier(self, nb_points, radius):
+        """(PointCloud of the kept points, ULongVector of their indices)"""
+        eng, n, c = self._engine_args()
+        p2, n2, c2, idx, _ = eng.remove_radius_outliers(self._points.tensor, int(nb_points), float(radius), n, c)
+        return self._made(p2, n2, c2), utility.ULongVector(idx.clone())
+
     # PointCloud::EstimateNormals (estimate_normals.cu:82-127): KNN or Radius search parameter ----------
     def estimate_normals(self, search_param=None):
         eng = get_engine(self._points.tensor.device.index)

@@ -83,6 +83,23 @@ class Vector3fVector(DeviceVector):
     cols = 3
 
 
+class ULongVector(DeviceVector):
+    """device_vector<size_t> (utility/eigen.cpp: ULongVector): a 1-D int64 device vector -- the indices the outlier
+    filters return and SelectByIndex takes."""
+    cols = 0
+
+    def __init__(self, data=None):
+        if data is None:
+            data = np.zeros((0,), np.int64)
+        self.tensor = _to_device_tensor(data, 0, torch.int64).reshape(-1)
+
+    @classmethod
+    def from_dlpack(cls, capsule_or_obj):
+        obj = cls.__new__(cls)
+        obj.tensor = torch.from_dlpack(capsule_or_obj).reshape(-1).contiguous()
+        return obj
+
+
 class Vector2iVector(DeviceVector):
     cols = 2
 

@@ -245,6 +245,28 @@ MI_ICP_API int mi_icp_voxel_downsample(mi_icp_ctx* ctx, const float* xyz, const 
                                        const float* colors, int64_t n, float voxel_size,
                                        float* out_xyz, float* out_normals, float* out_colors,
                                        int64_t* m, int mem_kind);
+/* PointCloud::SelectByIndex (geometry/down_sample.cu:40-62,110-129).  indices: int64 [n_indices]
+ * (device_vector<size_t>), in the same memory kind as the points.
+ *   invert = 0  a gather in the order given: out entry j = point indices[j]; repeated indices repeat
+ *               points; *m = n_indices.  Outputs hold n_indices entries.
+ *   invert = 1  the points NOT named, ascending in index; a repeated index counts once (the
+ *               reference sizes its output n - n_indices and would misbehave on repeats).  Outputs
+ *               hold n entries.
+ * An index outside [0, n) is MI_ICP_ERR_INVALID (checked on the device; the status comes back with
+ * the count, no extra wait).  normals / colors and their outputs may be NULL.  The entry point
+ * synchronises the context's stream. */
+MI_ICP_API int mi_icp_select_by_index(mi_icp_ctx* ctx, const float* xyz, const float* normals,
+                                      const float* colors, int64_t n, const int64_t* indices,
+                                      int64_t n_indices, int invert, float* out_xyz, float* out_normals,
+                                      float* out_colors, int64_t* m, int mem_kind);
+/* PointCloud::UniformDownSample (geometry/down_sample.cu:275-316): the points at indices 0, k, 2k, ...
+ * -- *m = n / every_k_points of them (the size the reference allocates; 0 when k > n) -- with their
+ * normals / colours (either may be NULL).  every_k_points < 1 is MI_ICP_ERR_INVALID.  Outputs hold
+ * n / every_k_points entries.  A strided copy per attribute; synchronises the context's stream. */
+MI_ICP_API int mi_icp_uniform_downsample(mi_icp_ctx* ctx, const float* xyz, const float* normals,
+                                         const float* colors, int64_t n, int64_t every_k_points,
+                                         float* out_xyz, float* out_normals, float* out_colors,
+                                         int64_t* m, int mem_kind);
 /* PointCloud::CreateFromDepthImage and PointCloud::CreateFromRGBDImage
  * (geometry/pointcloud_factory.cu:43-110,117-220,286-376) incl. the
  * RemoveNoneFinitePoints pass that follows (geometry/pointcloud.cu:40-54,360-385):
@@ -348,6 +370,40 @@ MI_ICP_API int mi_icp_estimate_normals_knn(mi_icp_ctx* ctx, const float* xyz, in
 MI_ICP_API int mi_icp_estimate_normals_radius(mi_icp_ctx* ctx, const float* xyz, int64_t n,
                                               float radius, int max_nn, float* normals,
                                               int mem_kind);
+
+/* PointCloud::RemoveStatisticalOutliers(nb_neighbors, std_ratio) (geometry/down_sample.cu:354-438).
+ * Per point, avg = the mean of the SQUARED distances of its nb_neighbors nearest points, itself
+ * included (fewer when the cloud has fewer points); mean = sum(avg) / n; std = sqrt(sum over the
+ * points with avg > 0 of (avg - mean)^2 / (n - 1)); a point is kept iff avg > 0 and
+ * avg < mean + std_ratio * std -- so a point whose neighbours all coincide with it is removed, and
+ * fewer than 2 points give an empty result, as in the reference.
+ * Outputs: the kept points with their normals / colours (either may be NULL; covariances are not
+ * carried, as in the reference), out_indices (int64, may be NULL) their original indices ascending,
+ * *m their count; all arrays hold n entries.  avg_d2 (float[n] or NULL): avg of every point in the
+ * cloud's order.
+ * Deviations (deliberate): a point's k fp32 squared distances are added in fp64 -- in any order the
+ * same sum -- divided in fp64 and rounded once to fp32; mean, the sum of squares and the threshold
+ * are fp64 sums in a fixed order (per block, then over the blocks; no float atomics), the
+ * comparison is (double)avg < threshold: the same input gives the same output on every run and
+ * every context (the reference sums in fp32 in thrust's order).
+ * Limits: nb_neighbors in [1, 100] (knn::NUM_MAX_NN), std_ratio > 0; else MI_ICP_ERR_INVALID.
+ * The cloud's tree is built in the private scratch context, as for EstimateNormals: the caller's
+ * target / source / loop state survive the call.  Synchronises the context's stream. */
+MI_ICP_API int mi_icp_remove_statistical_outliers(mi_icp_ctx* ctx, const float* xyz, const float* normals,
+                                                  const float* colors, int64_t n, int nb_neighbors,
+                                                  float std_ratio, float* out_xyz, float* out_normals,
+                                                  float* out_colors, int64_t* out_indices, float* avg_d2,
+                                                  int64_t* m, int mem_kind);
+/* PointCloud::RemoveRadiusOutliers(nb_points, search_radius) (geometry/down_sample.cu:317-352): a
+ * point is kept iff SearchRadius(search_radius, max_nn = nb_points + 1) -- d2 < radius^2 in fp32,
+ * the point itself included -- finds nb_points + 1 points.  Outputs as for the statistical filter;
+ * counts (int32[n] or NULL): the number found per point in the cloud's order, capped at
+ * nb_points + 1.  Limits: nb_points >= 1 with nb_points + 1 <= 100 (knn::NUM_MAX_NN), radius > 0;
+ * else MI_ICP_ERR_INVALID.  Scratch context and synchronisation as above. */
+MI_ICP_API int mi_icp_remove_radius_outliers(mi_icp_ctx* ctx, const float* xyz, const float* normals,
+                                             const float* colors, int64_t n, int nb_points, float radius,
+                                             float* out_xyz, float* out_normals, float* out_colors,
+                                             int64_t* out_indices, int32_t* counts, int64_t* m, int mem_kind);
 
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
