@@ -158,6 +158,10 @@ public:
     /// (fp64 statistics, include/mi_icp.h); nb_neighbors <= knn::NUM_MAX_NN.  Returns the kept cloud and their indices.
     std::tuple<std::shared_ptr<PointCloud>, utility::device_vector<size_t>> RemoveStatisticalOutliers(
             size_t nb_neighbors, float std_ratio) const;
+    /// pointcloud_cluster.cu:109-179: one label per point, its cluster's number or -1 (the contract: include/mi_icp.h);
+    /// max_edges <= knn::NUM_MAX_NN.  print_progress is accepted and prints nothing.
+    std::unique_ptr<utility::device_vector<int>> ClusterDBSCAN(float eps, size_t min_points, bool print_progress = false,
+                                                               size_t max_edges = knn::NUM_MAX_NN) const;
     /// estimate_normals.cu:82-127 (KNN or radius search parameter; up to knn::NUM_MAX_NN neighbours)
     bool EstimateNormals(const knn::KDTreeSearchParam& search_param = knn::KDTreeSearchParamKNN());
 

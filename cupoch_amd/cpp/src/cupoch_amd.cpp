@@ -269,6 +269,17 @@ std::tuple<std::shared_ptr<PointCloud>, utility::device_vector<size_t>> PointClo
     });
 }
 
+std::unique_ptr<utility::device_vector<int>> PointCloud::ClusterDBSCAN(float eps, size_t min_points, bool,
+                                                                       size_t max_edges) const {
+    const size_t n = points_.size();
+    auto labels = std::make_unique<utility::device_vector<int>>(n);
+    int64_t n_clusters = 0;
+    Check(mi_icp_cluster_dbscan(Engine(), Ptr(points_), (int64_t)n, eps,
+                                (int64_t)std::min<size_t>(min_points, (size_t)1 << 40),  // (all that large mean "no core")
+                                CountArg(max_edges), n ? labels->data() : nullptr, nullptr, &n_clusters, MI_ICP_DEVICE));
+    return labels;
+}
+
 bool PointCloud::EstimateNormals(const knn::KDTreeSearchParam& search_param) {
     normals_.resize(points_.size());
     if (points_.empty()) return true;

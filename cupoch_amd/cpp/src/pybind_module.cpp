@@ -2,7 +2,8 @@
 // surface (namespace cupoch, libcupoch_amd.so) instead of the CUDA library.
 //
 // Same module layout, names, defaults and property names as src/python/cupoch_pybind of the reference:
-//   cupoch_pybind.utility       Vector3fVector, ULongVector (device vector wrappers with .cpu()), initialize_allocator
+//   cupoch_pybind.utility       Vector3fVector, ULongVector, IntVector (device vector wrappers with .cpu()),
+//                               initialize_allocator
 //                               (src/python/cupoch_pybind/utility/eigen.cpp:123-200, cupoch_pybind.cpp:46-49)
 //   cupoch_pybind.geometry      PointCloud, KDTreeSearchParamKNN / Radius, KDTreeFlann
 //                               (geometry/pointcloud.cpp:33-160, geometry/kdtreeflann.cpp)
@@ -133,6 +134,25 @@ struct ULongVector {
         const std::vector<size_t> h = data.to_host();
         py::array_t<int64_t> a((py::ssize_t)h.size());
         if (!h.empty()) std::memcpy(a.mutable_data(), (const void*)h.data(), h.size() * sizeof(size_t));
+        return a;
+    }
+};
+
+// utility.IntVector: device_vector<int> (the reference's device_vector_int wrapper), the labels cluster_dbscan returns;
+// .cpu() gives int32
+struct IntVector {
+    utility::device_vector<int> data;
+    IntVector() = default;
+    explicit IntVector(const py::array_t<int32_t, py::array::c_style | py::array::forcecast>& a) {
+        if (a.ndim() != 1) throw std::invalid_argument("expected a 1-D integer array");
+        std::vector<int> h((size_t)a.shape(0));
+        if (!h.empty()) std::memcpy((void*)h.data(), a.data(), h.size() * sizeof(int));
+        data = h;
+    }
+    py::array_t<int32_t> cpu() const {
+        const std::vector<int> h = data.to_host();
+        py::array_t<int32_t> a((py::ssize_t)h.size());
+        if (!h.empty()) std::memcpy(a.mutable_data(), (const void*)h.data(), h.size() * sizeof(int));
         return a;
     }
 };
@@ -316,6 +336,11 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             .def(py::init<const py::array_t<int64_t, py::array::c_style | py::array::forcecast>&>(), "array"_a)
             .def("cpu", &ULongVector::cpu)
             .def("__len__", [](const ULongVector& v) { return v.data.size(); });
+    py::class_<IntVector>(mu, "IntVector")
+            .def(py::init<>())
+            .def(py::init<const py::array_t<int32_t, py::array::c_style | py::array::forcecast>&>(), "array"_a)
+            .def("cpu", &IntVector::cpu)
+            .def("__len__", [](const IntVector& v) { return v.data.size(); });
     py::class_<Vector2iVector>(mu, "Vector2iVector")
             .def(py::init<>())
             .def(py::init<const py::array_t<int, py::array::c_style | py::array::forcecast>&>(), "array"_a)
@@ -414,6 +439,15 @@ PYBIND11_MODULE(cupoch_pybind, m) {
                         return std::make_tuple(std::get<0>(res), idx);
                     },
                     "nb_neighbors"_a, "std_ratio"_a)
+            .def(
+                    "cluster_dbscan",
+                    [](const geometry::PointCloud& pc, float eps, size_t min_points, bool print_progress,
+                       size_t max_edges) {
+                        IntVector labels;
+                        labels.data = std::move(*pc.ClusterDBSCAN(eps, min_points, print_progress, max_edges));
+                        return labels;
+                    },
+                    "eps"_a, "min_points"_a, "print_progress"_a = false, "max_edges"_a = knn::NUM_MAX_NN)
             .def("estimate_normals", &geometry::PointCloud::EstimateNormals,
                  "search_param"_a = knn::KDTreeSearchParamKNN())
             .def("__len__", [](const geometry::PointCloud& pc) { return pc.points_.size(); });

@@ -5,7 +5,7 @@
 //   mi_geometry.hip  Transform / bounds / affine / covariances / VoxelDownSample / SelectByIndex / UniformDownSample /
 //                    depth frames / RGB-D odometry / colours
 //   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry,
-//                    RemoveStatisticalOutliers / RemoveRadiusOutliers
+//                    RemoveStatisticalOutliers / RemoveRadiusOutliers, ClusterDBSCAN
 //   mi_comm.hip      the ranks' exchange: mailbox, device inboxes, in-library RCCL, self-test and choice
 //   mi_debug.hip     include/mi_icp_debug.h (test-only entry points)
 // Kernels without template parameters are `static` in their headers, so a header may be included by several units.
@@ -103,6 +103,7 @@ struct mi_icp_ctx {
     mi::eng::DevBuf stage[6];
     mi::eng::DevBuf tscale;   // scratch of kd_build.h tree_scale
     mi::eng::DevBuf knn_idx, knn_flags;  // the k-NN lists' index rows, [XCD][row][slot][lane], and the rows' claim flags (knn_normals.h KnnSlab)
+    mi::eng::DevBuf dbs[4];   // ClusterDBSCAN (dbscan.h): the rows, the per-point words, the one-way masks, the state
     float vx_refused_voxel = 0.0f;  // the last voxel size / cloud size the dense path's plan turned away (mi_icp_voxel_downsample)
     int64_t vx_refused_n = 0;
     int vx_order = 0;         // LDS adds of one instruction served in lane order (voxel_dense.h)?  0: not checked yet, 1: yes, -1: no

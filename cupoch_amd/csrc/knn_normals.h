@@ -26,6 +26,10 @@
 // OUT = 2 and 3 reuse phases A/B for RemoveStatisticalOutliers / RemoveRadiusOutliers
 // (geometry/down_sample.cu:317-438): phase C writes one number per point, the mean of the
 // neighbours' squared distances or their count (knn_mean_d2; the tail is csrc/select.h).
+//
+// OUT = 4 serves PointCloud::ClusterDBSCAN (csrc/dbscan.h): the lists order their candidates by
+// (d2, ORIGINAL index) -- KnnList<KCAP, true> -- so a truncated radius row holds exactly the
+// reference's points, and phase C writes the row (knn_dbscan_row).
 #pragma once
 #include "device_utils.h"
 #include "eigen3.h"
@@ -91,7 +95,7 @@ __device__ __forceinline__ void knn_row_release(const KnnSlab& sl, uint32_t row)
     if (lane_id() == 0) __hip_atomic_store(sl.flags + row, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int KCAP>
+template <int KCAP, bool kTies = false>
 struct KnnStateT {
     float worst;  // current bound: +inf (or the search radius) until k candidates are held
     int count;
@@ -99,6 +103,9 @@ struct KnnStateT {
     // the largest distance (and its slot) within each group of 8 candidate slots
     float gmax[KCAP / 8];
     int gpos[KCAP / 8];
+    // kTies: the original index of the largest entry and of each group's largest ((d2, index) order)
+    int worst_orig;
+    int gorig[KCAP / 8];
     __device__ __forceinline__ void init(float bound) {
         worst = bound;
         count = 0;
@@ -107,6 +114,11 @@ struct KnnStateT {
         for (int g = 0; g < KCAP / 8; ++g) {
             gmax[g] = -1.0f;  // below every d2
             gpos[g] = g * 8;
+        }
+        if constexpr (kTies) {
+            worst_orig = 0x7fffffff;
+#pragma unroll
+            for (int g = 0; g < KCAP / 8; ++g) gorig[g] = -1;
         }
     }
 };
@@ -142,25 +154,41 @@ __device__ __forceinline__ void knn_clear(float* kd2, int lane) {
 // are compared in registers -- instead of re-reading all 32 slots (which cost 32 LDS reads +
 // ~130 VALU per accepted candidate, and the wave executes this path whenever ANY lane
 // accepts).  Ties resolve to the lowest slot either way, so the results are unchanged.
-template <int KCAP>
-__device__ __forceinline__ bool knn_offer(float* kd2, int32_t* kidx, int lane, int k, KnnStateT<KCAP>& s,
-                                          float d2, int32_t j) {
+//
+// kTies (ClusterDBSCAN's rows): candidates are ordered by (d2, original index) -- orig_of maps the
+// tree's index j to it, and the list keeps that index instead of j.  A full list then also takes a
+// candidate tied with its largest entry when its index is lower, and the largest entry is the
+// largest by that order, so the list ends with the k smallest by (d2, index) whatever order the walk
+// offered them in.  Only candidates with d2 <= the bound read orig_of.
+template <int KCAP, bool kTies>
+__device__ __forceinline__ bool knn_offer(float* kd2, int32_t* kidx, int lane, int k, KnnStateT<KCAP, kTies>& s,
+                                          float d2, int32_t j, const int32_t* orig_of) {
     constexpr int kGroups = KCAP / 8;
     bool shrunk = false;
-    if (d2 < s.worst) {
+    bool take = d2 < s.worst;
+    int32_t o = j;
+    if constexpr (kTies) {
+        if (d2 <= s.worst) {
+            o = orig_of[j];
+            take = take || (s.count >= k && o < s.worst_orig);
+        }
+    }
+    if (take) {
         const int pos = s.worst_pos;
         const int g = pos >> 3;
         kd2[pos * 64 + lane] = d2;
-        kidx[pos * 64 + lane] = j;
+        kidx[pos * 64 + lane] = o;
         bool full;
         if (s.count < k) {  // filling: the group's maximum only grows
             ++s.count;
             s.worst_pos = s.count;
 #pragma unroll
             for (int q = 0; q < kGroups; ++q) {
-                const bool up = (q == g) && (d2 > s.gmax[q]);  // ties keep the lower slot
+                bool up = (q == g) && (d2 > s.gmax[q]);  // ties keep the lower slot
+                if constexpr (kTies) up = up || ((q == g) && d2 == s.gmax[q] && o > s.gorig[q]);
                 s.gmax[q] = up ? d2 : s.gmax[q];
                 s.gpos[q] = up ? pos : s.gpos[q];
+                if constexpr (kTies) s.gorig[q] = up ? o : s.gorig[q];
             }
             full = s.count >= k;
         } else {  // the list's largest entry (in group g) was replaced: re-read that group
@@ -171,28 +199,38 @@ __device__ __forceinline__ bool knn_offer(float* kd2, int32_t* kidx, int lane, i
             for (int u = 0; u < 8; ++u) {
                 const int slot = g * 8 + u;
                 const float v = grp[u * 64];  // slots >= k hold -1 (knn_clear): they never win (d2 >= 0)
-                const bool hi = v > m;
+                bool hi = v > m;
+                if constexpr (kTies)  // (the indices are read only on a tie)
+                    hi = hi || (v == m && v >= 0.0f && kidx[slot * 64 + lane] > kidx[mp * 64 + lane]);
                 m = hi ? v : m;
                 mp = hi ? slot : mp;
             }
+            int mo = 0;
+            if constexpr (kTies) mo = kidx[mp * 64 + lane];
 #pragma unroll
             for (int q = 0; q < kGroups; ++q) {
                 s.gmax[q] = (q == g) ? m : s.gmax[q];
                 s.gpos[q] = (q == g) ? mp : s.gpos[q];
+                if constexpr (kTies) s.gorig[q] = (q == g) ? mo : s.gorig[q];
             }
             full = true;
         }
         if (full) {  // the bound becomes the k-th (largest) distance held
             float m = s.gmax[0];
             int mp = s.gpos[0];
+            int mo = 0;
+            if constexpr (kTies) mo = s.gorig[0];
 #pragma unroll
             for (int q = 1; q < kGroups; ++q) {
-                const bool hi = s.gmax[q] > m;
+                bool hi = s.gmax[q] > m;
+                if constexpr (kTies) hi = hi || (s.gmax[q] == m && s.gorig[q] > mo);
                 m = hi ? s.gmax[q] : m;
                 mp = hi ? s.gpos[q] : mp;
+                if constexpr (kTies) mo = hi ? s.gorig[q] : mo;
             }
             s.worst = m;
             s.worst_pos = mp;
+            if constexpr (kTies) s.worst_orig = mo;
             shrunk = true;
         }
     }
@@ -200,26 +238,35 @@ __device__ __forceinline__ bool knn_offer(float* kd2, int32_t* kidx, int lane, i
 }
 
 // A lane's list of the k nearest: its distance column in LDS, its index column in the slab row, the k it keeps
-// and its state.  It starts empty, with bound `bound` (-1: the lane takes nothing).
-template <int KCAP>
+// and its state.  It starts empty, with bound `bound` (-1: the lane takes nothing).  kTies: ordered by (d2, original
+// index), orig_of = the tree's original indices (knn_offer); the index column then holds original indices.
+template <int KCAP, bool kTies = false>
 struct KnnList {
     float* kd2;
     int32_t* kidx;
     int lane, k;
-    KnnStateT<KCAP> st;
-    __device__ __forceinline__ KnnList(float* kd2_, int32_t* kidx_, int k_, float bound)
-        : kd2(kd2_), kidx(kidx_), lane(lane_id()), k(k_) {
+    KnnStateT<KCAP, kTies> st;
+    const int32_t* orig_of;
+    __device__ __forceinline__ KnnList(float* kd2_, int32_t* kidx_, int k_, float bound, const int32_t* orig_of_ = nullptr)
+        : kd2(kd2_), kidx(kidx_), lane(lane_id()), k(k_), orig_of(orig_of_) {
         st.init(bound);
         knn_clear<KCAP>(kd2, lane);
     }
-    __device__ __forceinline__ bool offer(float d2, int32_t j) { return knn_offer(kd2, kidx, lane, k, st, d2, j); }
+    __device__ __forceinline__ bool offer(float d2, int32_t j) { return knn_offer(kd2, kidx, lane, k, st, d2, j, orig_of); }
+    // The bound the walk prunes with: boxes whose points all lie beyond it are skipped.  With kTies a point AT the
+    // bound may still enter (a lower index), so the walk keeps every box that can hold one: the next float up.
+    __device__ __forceinline__ float reach() const {
+        if constexpr (kTies)
+            return (st.worst >= 0.0f && st.worst < INFINITY) ? __uint_as_float(__float_as_uint(st.worst) + 1u) : st.worst;
+        return st.worst;
+    }
 };
 
 // Leaf L offered to this lane alone (divergent paths: the solo walk, the search's seeding), its 24 coordinates read
 // by the lane as six 16-byte loads.  A lane with `on` unset reads leaf 0 and is offered +inf.
-template <int KCAP>
+template <class List>
 __device__ __forceinline__ void knn_offer_leaf(const float* tblk_g, uint32_t L, bool on, float qx, float qy, float qz,
-                                               KnnList<KCAP>& l) {
+                                               List& l) {
     const float4* line = reinterpret_cast<const float4*>(tblk_g + (size_t)(on ? L : 0u) * kLeafFloats);
     float c[24];
 #pragma unroll
@@ -309,14 +356,14 @@ __device__ __forceinline__ bool knn_packet_reaches_too_far(const float* records_
 // the wave's walk and walk on their own after it; the others walk with the packet.  active: the lane searches at all.
 // [seed_lo, seed_hi): the leaves this lane has been offered already.  kPacketSeeds: the range is the packet's (normals
 // kernel) and the wave skips those leaves unread; otherwise it is the lane's own (search) and they are offered at +inf.
-template <bool kPacketSeeds, int KCAP>
+template <bool kPacketSeeds, class List>
 __device__ __forceinline__ void knn_walk(const float* records_g, const float* tblk_g, uint32_t leaf_first, bool active,
                                          float qx, float qy, float qz, uint32_t seed_lo, uint32_t seed_hi,
-                                         KnnList<KCAP>& l) {
+                                         List& l) {
     bool solo = knn_walks_alone(active, qx, qy, qz, l.st.worst);
     const float solo_bound = l.st.worst;
     Cube cube;
-    set_cube(cube, qx, qy, qz, solo ? -1.0f : l.st.worst);
+    set_cube(cube, qx, qy, qz, solo ? -1.0f : l.reach());
     if (knn_packet_reaches_too_far(records_g, leaf_first, cube)) {
         solo = active;
         set_cube(cube, qx, qy, qz, -1.0f);
@@ -334,11 +381,11 @@ __device__ __forceinline__ void knn_walk(const float* records_g, const float* tb
             const float d2 = (!kPacketSeeds && seeded) ? INFINITY : sq3(qx - p.x[t], qy - p.y[t], qz - p.z[t]);
             shrunk |= l.offer(d2, L * kLeaf + t);  // padding points: d2 = +inf
         }
-        if (shrunk) set_cube(cube, qx, qy, qz, l.st.worst);
+        if (shrunk) set_cube(cube, qx, qy, qz, l.reach());
     });
     if (__ballot(solo) != 0ull) {  // (rare: wave-uniform)
         if (solo) l.st.worst = solo_bound;
-        solo_walk(records_g, leaf_first, solo, qx, qy, qz, [&]() { return l.st.worst; }, [&](uint32_t L) {
+        solo_walk(records_g, leaf_first, solo, qx, qy, qz, [&]() { return l.reach(); }, [&](uint32_t L) {
             if (L >= seed_lo && L < seed_hi) return;
             knn_offer_leaf(tblk_g, L, true, qx, qy, qz, l);
         });
@@ -417,6 +464,22 @@ __device__ __forceinline__ float knn_mean_d2(const KnnList<KCAP>& l) {
     return l.st.count > 0 ? (float)(s / (double)l.st.count) : 0.0f;
 }
 
+// ---- C''': ClusterDBSCAN's row of the lane's point (pointcloud_cluster.cu:41-53 over SearchRadius(eps, max_edges + 1)):
+// the list's points but the query itself, in the list's order, at rows[orig][0, deg), and word[orig] = deg, plus
+// kDbscanRowFull when the list holds k entries (the row may have been truncated: dbscan.h's mutual-edge test then reads
+// it).  The query is missing from its own row only when k points at d2 = 0 have lower indices.
+constexpr int32_t kDbscanRowFull = 1 << 16;
+template <int KCAP>
+__device__ __forceinline__ void knn_dbscan_row(const KnnList<KCAP, true>& l, int32_t orig, int32_t* rows, int32_t* word) {
+    int32_t* row = rows + (int64_t)orig * l.k;
+    int d = 0;
+    for (int t = 0; t < l.st.count; ++t) {
+        const int32_t o = l.kidx[t * 64 + l.lane];
+        if (o != orig) row[d++] = o;
+    }
+    word[orig] = d | (l.st.count >= l.k ? kDbscanRowFull : 0);
+}
+
 // ---- C': colour gradient (colored_icp.cu:88-120) of the lane's point (query q, sorted index i) in its tangent plane
 template <int KCAP>
 __device__ __forceinline__ float3 knn_color_gradient(const float* tblk_g, const float4* tnrm, int64_t i, float qx,
@@ -482,6 +545,8 @@ __device__ __forceinline__ float3 knn_color_gradient(const float* tblk_g, const 
 // normals with the intensity in .w.  OUT 2: normals_out[orig] = the mean squared distance of
 // the lane's neighbours (knn_mean_d2).  OUT 3: normals_out, read as int32, [orig] = the number
 // of neighbours found (at most k; with r2 finite, those with d2 < r2).  The outlier filters.
+// OUT 4: ClusterDBSCAN's rows (knn_dbscan_row): normals_out, read as int32, holds the rows [n][k], tgrad, read as
+// int32, the words [n]; the list orders by (d2, original index).
 template <int OUT, int KCAP = kMaxKnn>
 __global__ __launch_bounds__(64) void knn_normals_kernel(
         const float* __restrict__ records_g, const float* __restrict__ tblk_g, const int32_t* __restrict__ tidx_g,
@@ -500,7 +565,7 @@ __global__ __launch_bounds__(64) void knn_normals_kernel(
         }
         const bool valid = orig >= 0;
         // r2 = +inf: plain k-NN; finite: the k nearest with d2 < r2 (KDTreeSearchParamRadius)
-        KnnList<KCAP> l(kd2, kidx, k, (valid && k > 0) ? r2 : -1.0f);
+        KnnList<KCAP, OUT == 4> l(kd2, kidx, k, (valid && k > 0) ? r2 : -1.0f, tidx_g);
 
         // ---- A: seed from the Morton neighbourhood
         const cfloat_p tblk = (cfloat_p)(uintptr_t)tblk_g;
@@ -520,6 +585,8 @@ __global__ __launch_bounds__(64) void knn_normals_kernel(
             normals_out[orig] = knn_mean_d2(l);
         } else if constexpr (OUT == 3) {
             reinterpret_cast<int32_t*>(normals_out)[orig] = l.st.count;
+        } else if constexpr (OUT == 4) {
+            knn_dbscan_row(l, orig, reinterpret_cast<int32_t*>(normals_out), reinterpret_cast<int32_t*>(tgrad));
         } else {
             const float3 v = OUT == 1 ? knn_color_gradient(tblk_g, tnrm, i, qx, qy, qz, l) : knn_normal(tblk_g, l);
             if (OUT == 1) tgrad[i] = make_float4(v.x, v.y, v.z, 0.0f);

@@ -1,8 +1,11 @@
 // mi_knn.hip -- k-nearest-neighbour work on the target tree: PointCloud::EstimateNormals, KDTreeFlann::SearchKNN /
 // SearchRadius, Colored ICP's colour gradients and its registration entry, RemoveStatisticalOutliers /
-// RemoveRadiusOutliers (knn_normals.h, select.h)
+// RemoveRadiusOutliers, ClusterDBSCAN (knn_normals.h, select.h, dbscan.h)
 // (one translation unit of libmi_icp.so; csrc/ctx.h lists them)
+#include <cstring>
+
 #include "ctx.h"
+#include "dbscan.h"
 #include "knn_normals.h"
 #include "select.h"
 
@@ -190,6 +193,102 @@ int mi_icp_remove_radius_outliers(mi_icp_ctx* c, const float* xyz, const float* 
         return fail(c, MI_ICP_ERR_INVALID, "%s: nb_points + 1 above %d (knn::NUM_MAX_NN) is not supported", what, kKnnLimit);
     return outlier_impl(c, what, true, xyz, normals, colors, n, nb_points + 1, radius * radius, 0.0, out_xyz, out_normals,
                         out_colors, out_indices, counts, m, mem_kind);
+}
+
+// ---------------------------------------------------------------------------
+// PointCloud::ClusterDBSCAN (geometry/pointcloud_cluster.cu:109-179).  The cloud gets a tree in the private scratch
+// context, as in EstimateNormals; knn_normals_kernel<4> writes every point's row, SearchRadius(eps, max_edges + 1) in
+// (d2, index) order without the point itself, and dbscan.h turns the rows into labels.  The rounds over the one-way
+// edges run in gated batches (a settled phase returns at once); the state, the cluster count and the labels come back
+// with one wait when the first batch settles, as it does whenever no row is truncated.
+static int dbscan_impl(mi_icp_ctx* c, const float* xyz, int64_t n, float r2, int min_points, int max_edges,
+                       int32_t* labels, int32_t* degrees, int64_t* n_clusters, int mem_kind) {
+    if (!c->aux) {
+        const int rc = mi_icp_create(c->device, &c->aux);
+        if (rc != MI_ICP_OK) return fail(c, rc, "cluster_dbscan: cannot create the scratch context");
+    }
+    mi_icp_ctx* a = c->aux;
+    a->stream = c->stream;
+    const int k = max_edges + 1;
+    auto run = [&]() -> int {
+        TRY(mi_icp_set_target(a, xyz, nullptr, nullptr, n, mem_kind));
+        int32_t *rows, *node;
+        uint4* mask;
+        DbscanState* st;
+        uint32_t* tmp;
+        TRY(ensure(a, a->dbs[0], (size_t)n * k, &rows));
+        TRY(ensure(a, a->dbs[1], (size_t)n * 6, &node));
+        TRY(ensure(a, a->dbs[2], (size_t)n, &mask));
+        TRY(ensure(a, a->dbs[3], (size_t)1, &st));
+        TRY(ensure(a, a->scan_tmp, (size_t)scan_num_tiles(n) + 2, &tmp));
+        int32_t *word = node, *rep = node + n, *m = node + 2 * n, *Mx = node + 3 * n;
+        uint32_t* start = (uint32_t*)(node + 4 * n);
+        uint32_t* number = (uint32_t*)(node + 5 * n);
+        int32_t* dl = labels;
+        int32_t* dd = degrees;
+        if (mem_kind == MI_ICP_HOST) {
+            TRY(ensure(a, a->stage[1], (size_t)n, &dl));
+            if (degrees) TRY(ensure(a, a->stage[2], (size_t)n, &dd));
+        }
+        TRY(launch_knn_normals<4>(a, k, r2, (float*)rows, nullptr, (float4*)word));
+        HIPCHK(a, hipMemsetAsync(st, 0, sizeof(DbscanState), a->stream));
+        const int nb = blocks_for(n);
+        dbscan_init<<<nb, 256, 0, a->stream>>>(n, rep, m, Mx);
+        dbscan_hook<<<nb, 256, 0, a->stream>>>(rows, word, n, k, min_points, rep);
+        dbscan_flatten<<<nb, 256, 0, a->stream>>>(n, rep);
+        dbscan_classify<<<nb, 256, 0, a->stream>>>(rows, word, rep, n, k, min_points, mask, st);
+        KCHK(a);
+        for (int batch = 6;; batch = 16) {
+            for (int r = 0; r < batch; ++r) {
+                dbscan_round<<<nb, 256, 0, a->stream>>>(rows, mask, rep, n, k, m, Mx, st);
+                dbscan_step<<<1, 64, 0, a->stream>>>(st);
+            }
+            dbscan_starts<<<nb, 256, 0, a->stream>>>(word, rep, m, n, min_points, st, start);
+            exclusive_scan_u32(a->stream, start, number, n, tmp);
+            dbscan_labels<<<nb, 256, 0, a->stream>>>(word, rep, m, Mx, start, number, n, st, dl, dd);
+            KCHK(a);
+            HIPCHK(a, hipMemcpyAsync(a->u_host, st, sizeof(DbscanState), hipMemcpyDeviceToHost, a->stream));
+            HIPCHK(a, hipMemcpyAsync(a->u_host + 4, tmp + scan_num_tiles(n), sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                     a->stream));
+            if (mem_kind == MI_ICP_HOST) {
+                TRY(from_device(a, (const int32_t*)dl, labels, (size_t)n, mem_kind));
+                if (degrees) TRY(from_device(a, (const int32_t*)dd, degrees, (size_t)n, mem_kind));
+            }
+            HIPCHK(a, hipStreamSynchronize(a->stream));
+            DbscanState s;
+            std::memcpy(&s, a->u_host, sizeof(s));
+            if (s.phase == 2u) {
+                *n_clusters = (int64_t)a->u_host[4];
+                return MI_ICP_OK;
+            }
+            // each phase settles within (one-way edges) rounds that change something and one that does not
+            if ((uint64_t)s.rounds >= 2ull * ((uint64_t)s.oneway + 1ull))
+                return fail(a, MI_ICP_ERR_STATE, "the one-way edges did not settle in %u rounds", s.rounds);
+        }
+    };
+    const int rc = run();
+    if (rc != MI_ICP_OK) return fail(c, rc, "cluster_dbscan: %s", a->err.c_str());
+    return MI_ICP_OK;
+}
+
+int mi_icp_cluster_dbscan(mi_icp_ctx* c, const float* xyz, int64_t n, float eps, int64_t min_points, int max_edges,
+                          int32_t* labels, int32_t* degrees, int64_t* n_clusters, int mem_kind) {
+    const char* what = "cluster_dbscan";
+    TRY(check_ctx(c));
+    if (!n_clusters) return fail(c, MI_ICP_ERR_INVALID, "%s: n_clusters is null", what);
+    *n_clusters = 0;
+    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    if (n > 0 && (!xyz || !labels)) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+    if (!(eps > 0.0f) || !(eps * eps < INFINITY))
+        return fail(c, MI_ICP_ERR_INVALID, "%s: eps must be positive, and finite when squared", what);
+    if (min_points < 0) return fail(c, MI_ICP_ERR_INVALID, "%s: min_points must not be negative", what);
+    if (max_edges < 0 || max_edges > kKnnLimit)
+        return fail(c, MI_ICP_ERR_INVALID, "%s: max_edges outside [0, %d] (knn::NUM_MAX_NN)", what, kKnnLimit);
+    if (mem_kind != MI_ICP_HOST && mem_kind != MI_ICP_DEVICE) return fail(c, MI_ICP_ERR_INVALID, "%s: bad mem_kind", what);
+    if (n == 0) return MI_ICP_OK;
+    // (a degree is at most max_edges + 1: every larger threshold means "no core point")
+    const int mp = (int)std::min<int64_t>(min_points, kKnnLimit + 2);
+    return dbscan_impl(c, xyz, n, eps * eps, mp, max_edges, labels, degrees, n_clusters, mem_kind);
 }
 
 // ---------------------------------------------------------------------------

@@ -415,6 +415,18 @@ class Engine:
         return self._outlier_filter(self._L.mi_icp_remove_radius_outliers, points, nb_points, radius,
                                     normals, colors, np.int32)
 
+    def cluster_dbscan(self, points, eps, min_points, max_edges=100):
+        """PointCloud::ClusterDBSCAN (pointcloud_cluster.cu:109-179; the contract is in include/mi_icp.h).
+        Returns (labels int32[n], degrees int32[n], n_clusters), on the side of `points`."""
+        p = _Buf(points, np.float32, 3, self.device)
+        kind = self._same_kind(p)
+        labels, plab = self._out(kind, p, p.n, 0, np.int32)
+        degrees, pdeg = self._out(kind, p, p.n, 0, np.int32)
+        nc = C.c_int64(0)
+        self._chk(self._L.mi_icp_cluster_dbscan(self._ctx, p.ptr, p.n, float(eps), int(min_points), int(max_edges),
+                                                plab, pdeg, C.byref(nc), kind))
+        return labels, degrees, int(nc.value)
+
     def select_by_index(self, points, indices, invert=False, normals=None, colors=None):
         """PointCloud::SelectByIndex (down_sample.cu:40-62,110-129).  indices: anything 1-D integer (a tensor on
         the points' device, a numpy array, a list); returns (points, normals or None, colors or None)."""

@@ -304,6 +304,14 @@ class PointCloud:
         p2, n2, c2, idx, _ = eng.remove_radius_outliers(self._points.tensor, int(nb_points), float(radius), n, c)
         return self._made(p2, n2, c2), utility.ULongVector(idx.clone())
 
+    # PointCloud::ClusterDBSCAN (pointcloud_cluster.cu:109-179) ----------------------------------------------------
+    def cluster_dbscan(self, eps, min_points, print_progress=False, max_edges=100):
+        """an IntVector of one label per point: its cluster's number, or -1 for noise (include/mi_icp.h states the
+        contract).  print_progress is accepted and prints nothing."""
+        eng = get_engine(self._points.tensor.device.index)
+        labels, _, _ = eng.cluster_dbscan(self._points.tensor, float(eps), int(min_points), int(max_edges))
+        return utility.IntVector(labels)
+
     # PointCloud::EstimateNormals (estimate_normals.cu:82-127): KNN or Radius search parameter ----------
     def estimate_normals(self, search_param=None):
         eng = get_engine(self._points.tensor.device.index)

@@ -100,6 +100,23 @@ class ULongVector(DeviceVector):
         return obj
 
 
+class IntVector(DeviceVector):
+    """device_vector<int> (the reference's device_vector_int wrapper): a 1-D int32 device vector -- the labels
+    PointCloud.cluster_dbscan returns."""
+    cols = 0
+
+    def __init__(self, data=None):
+        if data is None:
+            data = np.zeros((0,), np.int32)
+        self.tensor = _to_device_tensor(data, 0, torch.int32).reshape(-1)
+
+    @classmethod
+    def from_dlpack(cls, capsule_or_obj):
+        obj = cls.__new__(cls)
+        obj.tensor = torch.from_dlpack(capsule_or_obj).reshape(-1).contiguous()
+        return obj
+
+
 class Vector2iVector(DeviceVector):
     cols = 2
 

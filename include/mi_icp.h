@@ -405,6 +405,40 @@ MI_ICP_API int mi_icp_remove_radius_outliers(mi_icp_ctx* ctx, const float* xyz, 
                                              float* out_xyz, float* out_normals, float* out_colors,
                                              int64_t* out_indices, int32_t* counts, int64_t* m, int mem_kind);
 
+/* PointCloud::ClusterDBSCAN(eps, min_points, print_progress, max_edges)
+ * (geometry/pointcloud_cluster.cu:109-179).  Its contract, which the labels meet exactly:
+ *   row(i)  SearchRadius(p_i, eps, max_nn = max_edges + 1): the nearest max_edges + 1 points with
+ *           fp32 d2 < eps*eps, ascending in distance, ties ascending in index, the point itself
+ *           among them (pointcloud_cluster.cu:124-125).
+ *   N(i)    row(i) without i; deg(i) = |N(i)|; i is CORE iff deg(i) >= min_points.  A non-core
+ *           point keeps no edges (pointcloud_cluster.cu:41-53).
+ *   edges   i -> j for every core i and j in N(i); reach(i) = i and all it reaches along edges.
+ *   roots   the loop at pointcloud_cluster.cu:147-178 visits the points in order and starts a BFS
+ *           from every point no earlier BFS reached: r is a ROOT iff no j < r has r in reach(j).
+ *           A root starts a cluster iff |reach(r)| >= min_points (every core root does); the
+ *           clusters are numbered 0, 1, ... in ascending order of their roots.
+ *   labels  label(x) = the number of the LARGEST root whose reach holds x (each BFS overwrites
+ *           the labels of all it reaches), or -1 when that root started no cluster.
+ * Hence, as in the reference: a border point reachable from several clusters takes the highest
+ * number; with min_points <= 1 an isolated point is a cluster of its own; with max_edges = 0
+ * every row holds one point; a truncated row can make an edge one-way (j in N(i), i not in
+ * N(j)), and a later root can then reach into an earlier cluster and relabel all of it, so a
+ * cluster number may appear on no point; and when more than max_edges points coincide with p_i
+ * at lower indices, i is not in its own row and deg(i) counts all max_edges + 1.
+ * Outputs: labels int32[n]; degrees int32[n] or NULL: deg(i), before the core test (the
+ * reference keeps 0 for non-core points); *n_clusters = the cluster numbers handed out.
+ * Limits: eps > 0 with eps*eps finite (the reference would square a negative eps: a deviation),
+ * min_points >= 0, max_edges in [0, 100] (knn::NUM_MAX_NN), n < 2^31; else MI_ICP_ERR_INVALID.
+ * n = 0 gives zero clusters.  Labels are integers fixed by the contract: every run and every
+ * context gives the same bytes.  The cloud's tree is built in the private scratch context, as for
+ * EstimateNormals: the caller's target / source / loop state survive the call.  Memory on top of
+ * the tree: n * (max_edges + 1) int32 rows and 48 bytes per point (4.5 GB at n = 10M, max_edges
+ * = 100).  Synchronises the context's stream once; truncated rows that chain one-way edges
+ * through more than a few pieces add one wait per 16 further rounds. */
+MI_ICP_API int mi_icp_cluster_dbscan(mi_icp_ctx* ctx, const float* xyz, int64_t n, float eps,
+                                     int64_t min_points, int max_edges, int32_t* labels,
+                                     int32_t* degrees, int64_t* n_clusters, int mem_kind);
+
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
  * float[nq][3] against the cloud given to mi_icp_set_target: per query the knn

@@ -7,8 +7,10 @@ reference's sample scan examples/testdata/fragment.pcd (113,662 points; tests/go
 tests/golden/make_fixtures.py), through the pybind11 module, host-visible wall time with the cloud resident on the device
 (benchmarks.py's measure_time: time.time() around one call).  Open3D is not installable here; beside every call stands
 the CPU port (oracle/) at ONE thread -- README.md:124 quotes the comparison with OMP_NUM_THREADS=1 -- and at all
-threads, and the result's parity against it.  (remove_*_outlier / cluster_dbscan of that script: SURVEY section 2 OUT OF
-SCOPE.)  One JSON line per call -> profiles/r05_reference_benchmark_fragment.jsonl.
+threads, and the result's parity against it.  The fifth row is `cluster_dbscan(0.02, 10)` (benchmarks.py:85-87): the CPU
+port has no DBSCAN, so its parity is held against the CPU restatement tests/dbscan_exact.py (labels equal at every point)
+and its CPU columns time that restatement (numpy / scipy).  (remove_*_outlier of that script: not rows here.)  One JSON
+line per call -> profiles/r05_reference_benchmark_fragment.jsonl.
 
     python scripts/measure_reference_benchmark.py
 """
@@ -24,7 +26,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 THRESHOLD, VOXEL, KNN = 0.02, 0.005, 30
+DBSCAN_EPS, DBSCAN_MIN = 0.02, 10
 PUBLISHED = {"transform": 4.3, "estimate_normals": 12.0, "voxel_down_sample": 3.2, "registration_icp": 105.0}
+CALLS = ("transform", "estimate_normals", "voxel_down_sample", "registration_icp", "cluster_dbscan")
 
 
 def trans_init():
@@ -36,7 +40,9 @@ CPU_CODE = r"""
 import json, sys, time
 import numpy as np
 sys.path.insert(0, %(root)r)
+sys.path.insert(0, %(tests)r)
 from oracle import oracle as orc
+import dbscan_exact as dx
 pts = np.load(%(npz)r)["points"]
 T30 = np.array(%(t30)r, np.float32)
 med = lambda f, k=3: float(np.median([f() for _ in range(k)]))
@@ -51,6 +57,7 @@ out["estimate_normals"] = med(timed(lambda: orc.estimate_normals_knn(pts, %(knn)
 out["voxel_down_sample"] = med(timed(lambda: orc.voxel_downsample(pts, %(voxel)r)))
 moved = orc.transform_points(T30, pts)
 out["registration_icp"] = med(timed(lambda: orc.registration_icp(moved, moved, %(thr)r, init=T30, est=orc.EST_P2P)))
+out["cluster_dbscan"] = med(timed(lambda: dx.by_definition(pts.astype(np.float32), %(eps)r, %(minp)d)))
 print(json.dumps(out))
 """
 
@@ -61,7 +68,7 @@ def cpu_times(threads):
         env["OMP_NUM_THREADS"] = str(threads)
     else:
         env.pop("OMP_NUM_THREADS", None)
-    code = CPU_CODE % dict(root=ROOT, npz=os.path.join(ROOT, "tests", "golden", "fragment_points.npz"),
+    code = CPU_CODE % dict(root=ROOT, tests=os.path.join(ROOT, "tests"), eps=DBSCAN_EPS, minp=DBSCAN_MIN, npz=os.path.join(ROOT, "tests", "golden", "fragment_points.npz"),
                            t30=trans_init().tolist(), knn=KNN, voxel=VOXEL, thr=THRESHOLD)
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=3600)
     if out.returncode != 0:
@@ -147,10 +154,21 @@ def main():
     rows["registration_icp"] = dict(first_ms=f, ms=m, ok=err <= 1e-5 and same_n,
                                     parity="|T - T_oracle|_F = %.3g, %d correspondences (oracle %d), fitness %.6f (oracle %.6f)"
                                            % (err, len(res.correspondence_set), len(ref.correspondence_set), res.fitness, ref.fitness))
+    # -- cluster_dbscan(0.02, 10) (benchmarks.py:85-87), held to the CPU restatement
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dbscan_exact as dx
+    lab, f, m = first_and_median(lambda: pc.cluster_dbscan(DBSCAN_EPS, DBSCAN_MIN))
+    gl = np.asarray(lab.cpu())
+    rl, _, rn = dx.by_definition(pts.astype(np.float32), DBSCAN_EPS, DBSCAN_MIN)
+    okd = bool(np.array_equal(gl, rl))
+    rows["cluster_dbscan"] = dict(first_ms=f, ms=m, ok=okd,
+                                  parity="labels equal the CPU restatement's (tests/dbscan_exact.py) at every point: %s; "
+                                         "%d clusters, %d noise points; CPU columns: that restatement (the port has no DBSCAN)"
+                                         % (okd, rn, int((rl < 0).sum())))
     one = cpu_times(1)
     allt = cpu_times(0)
     some = cpu_times(16)
-    for name in ("transform", "estimate_normals", "voxel_down_sample", "registration_icp"):
+    for name in CALLS:
         r = rows[name]
         print(json.dumps({
             "call": name, "points": n, "input": "examples/testdata/fragment.pcd (tests/golden/fragment_points.npz)",
@@ -162,7 +180,7 @@ def main():
             "speedup_vs_best_cpu": round(min(one[name], some[name], allt[name]) * 1e3 / r["ms"], 1),
             "speedup_vs_1_thread": round(one[name] * 1e3 / r["ms"], 1), "speedup_vs_1_thread_first_call": round(one[name] * 1e3 / r["first_ms"], 1),
             "speedup_vs_all_threads": round(allt[name] * 1e3 / r["ms"], 1),
-            "reference_published_speedup_gtx1070_vs_open3d_1_thread": PUBLISHED[name],
+            "reference_published_speedup_gtx1070_vs_open3d_1_thread": PUBLISHED.get(name),
             "parity": r["parity"], "parity_ok": bool(r["ok"])}), flush=True)
 
 
