@@ -218,8 +218,11 @@ inline void release(DevBuf& b) {
     b.bytes = 0;
 }
 
-// device view of a caller buffer (copied through a context-owned staging buffer
-// when it lives in host memory)
+// How an entry point handles a caller's buffer: MI_ICP_HOST stages it through a context-owned DevBuf, MI_ICP_DEVICE
+// reads and writes it in place (check_ctx below turns away every other kind).  None of the three helpers waits.
+//   to_device   an input: the device view of `src`
+//   out_slot    an output: where a kernel writes `count` elements for `dst` (dst itself, or `stage`); nullptr for no dst
+//   from_device back to the caller: `count` elements of `dev` into `dst`, unless dst is null or is `dev` itself
 template <class T>
 int to_device(mi_icp_ctx* c, const T* src, size_t count, int mem_kind, DevBuf& stage,
               const T** out) {
@@ -239,8 +242,17 @@ int to_device(mi_icp_ctx* c, const T* src, size_t count, int mem_kind, DevBuf& s
 }
 
 template <class T>
+int out_slot(mi_icp_ctx* c, T* dst, size_t count, int mem_kind, DevBuf& stage, T** out) {
+    if (!dst || mem_kind == MI_ICP_DEVICE) {
+        *out = dst;
+        return MI_ICP_OK;
+    }
+    return ensure(c, stage, count, out);
+}
+
+template <class T>
 int from_device(mi_icp_ctx* c, const T* dev, T* dst, size_t count, int mem_kind) {
-    if (!dst || count == 0) return MI_ICP_OK;
+    if (!dst || dst == dev || count == 0) return MI_ICP_OK;
     HIPCHK(c, hipMemcpyAsync(dst, dev, count * sizeof(T),
                              mem_kind == MI_ICP_DEVICE ? hipMemcpyDeviceToDevice
                                                        : hipMemcpyDeviceToHost,
@@ -317,6 +329,13 @@ inline int check_ctx(mi_icp_ctx* c) {
     if (!c) return MI_ICP_ERR_INVALID;
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return fail(c, MI_ICP_ERR_HIP, "hipSetDevice(%d): %s", c->device, hipGetErrorString(e));
+    return MI_ICP_OK;
+}
+
+// ... and of an entry point that takes a mem_kind, before any buffer is touched
+inline int check_ctx(mi_icp_ctx* c, int mem_kind, const char* what) {
+    TRY(check_ctx(c));
+    if (mem_kind != MI_ICP_HOST && mem_kind != MI_ICP_DEVICE) return fail(c, MI_ICP_ERR_INVALID, "%s: bad mem_kind", what);
     return MI_ICP_OK;
 }
 

@@ -28,21 +28,17 @@ int occupancy_geometry(int which) {
     return e == hipSuccess ? blocks : -2;
 }
 
-// Where up to `count` selected points go: the caller's arrays, or (MI_ICP_HOST) staging buffers; nullptr for an
-// attribute that is not there.  select_out_back copies `m` of them to the caller.
-static int select_out(mi_icp_ctx* c, const float* const in[3], float* const out[3], int64_t count, int mem_kind,
-                      float* dst[3]) {
-    for (int k = 0; k < 3; ++k) {
-        dst[k] = in[k] ? out[k] : nullptr;
-        if (in[k] && mem_kind == MI_ICP_HOST) TRY(ensure(c, c->vpay[k], (size_t)count * 3, &dst[k]));
-    }
+// Where up to `count` points of an output cloud (points, normals, colours) go: the caller's arrays out[], or (MI_ICP_HOST)
+// stage[0..2]; nullptr for an attribute that in[] does not have.  cloud_out_back copies `m` of them to the caller.
+static int cloud_out(mi_icp_ctx* c, const float* const in[3], float* const out[3], int64_t count, int mem_kind,
+                     DevBuf* stage, float* dst[3]) {
+    for (int k = 0; k < 3; ++k) TRY(out_slot(c, in[k] ? out[k] : nullptr, (size_t)count * 3, mem_kind, stage[k], &dst[k]));
     return MI_ICP_OK;
 }
 
-static int select_out_back(mi_icp_ctx* c, float* const dst[3], float* const out[3], int64_t m, int mem_kind) {
-    if (mem_kind == MI_ICP_HOST)
-        for (int k = 0; k < 3; ++k)
-            if (dst[k]) TRY(from_device(c, (const float*)dst[k], out[k], (size_t)m * 3, mem_kind));
+static int cloud_out_back(mi_icp_ctx* c, float* const dst[3], float* const out[3], int64_t m, int mem_kind) {
+    for (int k = 0; k < 3; ++k)
+        if (dst[k]) TRY(from_device(c, (const float*)dst[k], out[k], (size_t)m * 3, mem_kind));
     return MI_ICP_OK;
 }
 
@@ -57,9 +53,9 @@ int compact_by_flags(mi_icp_ctx* c, const uint32_t* flags, int64_t n, const floa
     exclusive_scan_u32(c->stream, flags, pos, n, tmp);
     KCHK(c);
     float* dst[3];
-    TRY(select_out(c, in, out, n, mem_kind, dst));
-    int64_t* didx = out_idx;
-    if (out_idx && mem_kind == MI_ICP_HOST) TRY(ensure(c, c->pairs_out, (size_t)n, &didx));
+    int64_t* didx;
+    TRY(cloud_out(c, in, out, n, mem_kind, c->vpay, dst));
+    TRY(out_slot(c, out_idx, (size_t)n, mem_kind, c->pairs_out, &didx));
     select_gather<<<blocks_for(n), 256, 0, c->stream>>>(flags, pos, n, in[0], in[1], in[2], dst[0], dst[1], dst[2], didx);
     KCHK(c);
     // the count (and the caller's status word) come back with the one wait of the call
@@ -68,9 +64,9 @@ int compact_by_flags(mi_icp_ctx* c, const uint32_t* flags, int64_t n, const floa
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int64_t cnt = (int64_t)c->u_host[0];
     if (status_out && status) *status_out = c->u_host[1];
-    if (mem_kind == MI_ICP_HOST) {
-        TRY(select_out_back(c, dst, out, cnt, mem_kind));
-        if (out_idx) TRY(from_device(c, (const int64_t*)didx, out_idx, (size_t)cnt, mem_kind));
+    if (dst[0] != out[0] || didx != out_idx) {  // staged: a second wait, for the copies to the caller
+        TRY(cloud_out_back(c, dst, out, cnt, mem_kind));
+        TRY(from_device(c, (const int64_t*)didx, out_idx, (size_t)cnt, mem_kind));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     *m = cnt;
@@ -85,7 +81,7 @@ extern "C" {
 // ---------------------------------------------------------------------------
 int mi_icp_transform(mi_icp_ctx* c, const float* T, float* xyz, float* normals, float* covs,
                      int64_t n, int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "transform"));
     if (n < 0) return fail(c, MI_ICP_ERR_INVALID, "transform: negative size");
     if (n == 0 || (!xyz && !normals && !covs)) return MI_ICP_OK;
     const Xform X = make_xform(load_T(T));
@@ -95,11 +91,9 @@ int mi_icp_transform(mi_icp_ctx* c, const float* T, float* xyz, float* normals, 
     TRY(to_device(c, (const float*)covs, (size_t)n * 9, mem_kind, c->stage[2], &dc));
     transform_cloud<<<blocks_for(n), 256, 0, c->stream>>>(X, (float*)dp, (float*)dn, (float*)dc, n);
     KCHK(c);
-    if (mem_kind == MI_ICP_HOST) {
-        TRY(from_device(c, dp, xyz, xyz ? (size_t)n * 3 : 0, mem_kind));
-        TRY(from_device(c, dn, normals, normals ? (size_t)n * 3 : 0, mem_kind));
-        TRY(from_device(c, dc, covs, covs ? (size_t)n * 9 : 0, mem_kind));
-    }
+    TRY(from_device(c, dp, xyz, (size_t)n * 3, mem_kind));
+    TRY(from_device(c, dn, normals, (size_t)n * 3, mem_kind));
+    TRY(from_device(c, dc, covs, (size_t)n * 9, mem_kind));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // pointcloud.cu:297 cudaDeviceSynchronize
     return MI_ICP_OK;
 }
@@ -107,7 +101,7 @@ int mi_icp_transform(mi_icp_ctx* c, const float* T, float* xyz, float* normals, 
 // GeometryBase3D::GetMinBound / GetMaxBound / GetCenter (geometry/pointcloud.cu:205-215)
 int mi_icp_compute_bounds(mi_icp_ctx* c, const float* xyz, int64_t n, int mem_kind, float* min3, float* max3,
                           float* center3) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "compute_bounds"));
     if (n < 0 || (n > 0 && !xyz)) return fail(c, MI_ICP_ERR_INVALID, "compute_bounds: bad size/pointer");
     const float zero[3] = {0.0f, 0.0f, 0.0f};
     if (n == 0) {  // the reference returns zero vectors for an empty cloud
@@ -143,7 +137,7 @@ int mi_icp_compute_bounds(mi_icp_ctx* c, const float* xyz, int64_t n, int mem_ki
 // GeometryBase3D::Translate / Scale / Rotate (geometry/pointcloud.cu:225-242)
 int mi_icp_affine(mi_icp_ctx* c, const float* R9, float scale, int use_scale, const float* center3,
                   const float* translate3, float* xyz, float* normals, float* covs, int64_t n, int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "affine"));
     if (n < 0) return fail(c, MI_ICP_ERR_INVALID, "affine: negative size");
     if (n == 0 || (!xyz && !normals && !covs)) return MI_ICP_OK;
     Affine A;
@@ -165,27 +159,25 @@ int mi_icp_affine(mi_icp_ctx* c, const float* R9, float scale, int use_scale, co
     affine_cloud<<<blocks_for(n), 256, 0, c->stream>>>(A, const_cast<float*>(dp), const_cast<float*>(dn),
                                                         const_cast<float*>(dc), n);
     KCHK(c);
-    if (mem_kind == MI_ICP_HOST) {
-        TRY(from_device(c, dp, xyz, (size_t)n * 3, mem_kind));
-        TRY(from_device(c, dn, normals, (size_t)n * 3, mem_kind));
-        TRY(from_device(c, dc, covs, (size_t)n * 9, mem_kind));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    TRY(from_device(c, dp, xyz, (size_t)n * 3, mem_kind));
+    TRY(from_device(c, dn, normals, (size_t)n * 3, mem_kind));
+    TRY(from_device(c, dc, covs, (size_t)n * 9, mem_kind));
+    if (dp != xyz || dn != normals || dc != covs) HIPCHK(c, hipStreamSynchronize(c->stream));  // (staged: the copies)
     return MI_ICP_OK;
 }
 
 int mi_icp_covariances_from_normals(mi_icp_ctx* c, const float* normals, int64_t n, float epsilon,
                                     float* covs, int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "covariances_from_normals"));
     if (n < 0 || (n > 0 && (!normals || !covs))) return fail(c, MI_ICP_ERR_INVALID, "covariances_from_normals: bad arguments");
     if (n == 0) return MI_ICP_OK;
     const float* dn;
     TRY(to_device(c, normals, (size_t)n * 3, mem_kind, c->stage[1], &dn));
-    float* dc = covs;
-    if (mem_kind == MI_ICP_HOST) TRY(ensure(c, c->stage[2], (size_t)n * 9, &dc));
+    float* dc;
+    TRY(out_slot(c, covs, (size_t)n * 9, mem_kind, c->stage[2], &dc));
     cov_from_normals<<<blocks_for(n), 256, 0, c->stream>>>(dn, n, epsilon, dc);
     KCHK(c);
-    if (mem_kind == MI_ICP_HOST) TRY(from_device(c, (const float*)dc, covs, (size_t)n * 9, mem_kind));
+    TRY(from_device(c, (const float*)dc, covs, (size_t)n * 9, mem_kind));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MI_ICP_OK;
 }
@@ -258,24 +250,6 @@ static void vx_partition(mi_icp_ctx* c, const VxDev* d, const VxArrays& a, int n
     else vx_scatter<3><<<grid, kVxThreads, 0, c->stream>>>(a, n, t.ntiles, d, t.tab, t.seg_tot, t.bucket_start, t.ctl);
 }
 
-// Where the means of up to m voxels go: the caller's arrays, or (MI_ICP_HOST) staging buffers; nullptr for an array
-// that is not there.  voxel_out_back copies them to the caller and waits for the stream.
-static int voxel_out(mi_icp_ctx* c, const float* const in[3], float* const out[3], int64_t m, int mem_kind, float* dst[3]) {
-    for (int k = 0; k < 3; ++k) {
-        dst[k] = in[k] ? out[k] : nullptr;
-        if (in[k] && mem_kind == MI_ICP_HOST) TRY(ensure(c, c->stage[3 + k], (size_t)m * 3, &dst[k]));
-    }
-    return MI_ICP_OK;
-}
-
-static int voxel_out_back(mi_icp_ctx* c, float* const dst[3], float* const out[3], int64_t m, int mem_kind) {
-    if (mem_kind == MI_ICP_HOST)
-        for (int k = 0; k < 3; ++k)
-            if (dst[k]) TRY(from_device(c, (const float*)dst[k], out[k], (size_t)m * 3, mem_kind));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MI_ICP_OK;
-}
-
 // VoxelDownSample of a DENSE grid (voxel_dense.h): every point moves once.  Launched BEHIND the bounds kernels without
 // waiting for them: the plan is made on the device (vx_bounds_plan: a packed key of 14 ... 22 bits and enough points per
 // bucket), every kernel reads it there and does nothing when the grid is not one for this path.  The caller then waits
@@ -304,7 +278,7 @@ static int voxel_dense_launch(mi_icp_ctx* c, const float* const in[3], int64_t n
             TRY(ensure(c, c->vpay[3 + k], (size_t)1 << 22, &tmp[k]));
         }
     }
-    TRY(voxel_out(c, in, out, std::min<int64_t>(n, (int64_t)1 << 22), mem_kind, dst));
+    TRY(cloud_out(c, in, out, std::min<int64_t>(n, (int64_t)1 << 22), mem_kind, c->stage + 3, dst));
     {   // the bounds (compute_bounds' two launches, the second one making the plan as well)
         float* part;
         TRY(ensure(c, c->bounds_part, (size_t)kBoundsBlocks * 6, &part));
@@ -438,7 +412,7 @@ static int voxel_downsample_keys32(mi_icp_ctx* c, const float* const in[3], int6
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int64_t nvox = (int64_t)c->u_host[0];
     float* dst[3];
-    TRY(voxel_out(c, in, out, nvox, mem_kind, dst));
+    TRY(cloud_out(c, in, out, nvox, mem_kind, c->stage + 3, dst));
     if (L > 0) {  // a wave per run
         const int64_t rmax = (bits - L >= 31) ? n : std::min<int64_t>(n, (int64_t)1 << (bits - L));
         voxel_means_wave<<<(unsigned)rmax, 64, 0, c->stream>>>(skeys, pay[0], pay[1], pay[2], run_start, voff, mask, nruns, rmax, L,
@@ -450,7 +424,8 @@ static int voxel_downsample_keys32(mi_icp_ctx* c, const float* const in[3], int6
                                                                      nvox, dst[0], dst[1], dst[2]);
     }
     KCHK(c);
-    TRY(voxel_out_back(c, dst, out, nvox, mem_kind));
+    TRY(cloud_out_back(c, dst, out, nvox, mem_kind));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     *m = nvox;
     return MI_ICP_OK;
 }
@@ -458,7 +433,7 @@ static int voxel_downsample_keys32(mi_icp_ctx* c, const float* const in[3], int6
 int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normals,
                             const float* colors, int64_t n, float voxel, float* out_xyz,
                             float* out_normals, float* out_colors, int64_t* m, int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "voxel_downsample"));
     if (!m) return fail(c, MI_ICP_ERR_INVALID, "voxel_downsample: m is null");
     *m = 0;
     c->last_voxel_path = -1;
@@ -499,7 +474,8 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
     }
     if (dense && c->u_host[0] == 0u) {  // (1: the cloud crowds into a few buckets, 2: not a grid for that path -- nothing was written)
         const int64_t nvox = (int64_t)c->u_host[2];
-        if (mem_kind == MI_ICP_HOST) TRY(voxel_out_back(c, dst, out, nvox, mem_kind));  // (device arrays: already waited for)
+        TRY(cloud_out_back(c, dst, out, nvox, mem_kind));
+        if (dst[0] != out[0]) HIPCHK(c, hipStreamSynchronize(c->stream));  // (staged: the copies; device arrays: already waited for)
         *m = nvox;
         c->last_voxel_path = 1;
         return MI_ICP_OK;
@@ -559,10 +535,11 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
     voxel_seg_starts<<<nb, 256, 0, c->stream>>>(head, pos, n, seg_start);
     KCHK(c);
 
-    TRY(voxel_out(c, in, out, nvox, mem_kind, dst));
+    TRY(cloud_out(c, in, out, nvox, mem_kind, c->stage + 3, dst));
     voxel_means<<<blocks_for(nvox * 8), 256, 0, c->stream>>>(dp, in[1], in[2], order, seg_start, nvox, n, dst[0], dst[1], dst[2]);
     KCHK(c);
-    TRY(voxel_out_back(c, dst, out, nvox, mem_kind));
+    TRY(cloud_out_back(c, dst, out, nvox, mem_kind));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     *m = nvox;
     return MI_ICP_OK;
 }
@@ -572,7 +549,7 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
 int mi_icp_select_by_index(mi_icp_ctx* c, const float* xyz, const float* normals, const float* colors, int64_t n,
                            const int64_t* indices, int64_t n_indices, int invert, float* out_xyz, float* out_normals,
                            float* out_colors, int64_t* m, int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "select_by_index"));
     if (!m) return fail(c, MI_ICP_ERR_INVALID, "select_by_index: m is null");
     *m = 0;
     if (n < 0 || n > 0x7fffff00ll || n_indices < 0 || n_indices > 0x7fffff00ll)
@@ -599,11 +576,11 @@ int mi_icp_select_by_index(mi_icp_ctx* c, const float* xyz, const float* normals
     if (!invert) {
         HIPCHK(c, hipMemsetAsync(status, 0, sizeof(uint32_t), c->stream));
         float* dst[3];
-        TRY(select_out(c, in, out, n_indices, mem_kind, dst));
+        TRY(cloud_out(c, in, out, n_indices, mem_kind, c->vpay, dst));
         select_list<<<blocks_for(n_indices), 256, 0, c->stream>>>(idx, n_indices, n, in[0], in[1], in[2], dst[0], dst[1],
                                                                   dst[2], status);
         KCHK(c);
-        TRY(select_out_back(c, dst, out, n_indices, mem_kind));
+        TRY(cloud_out_back(c, dst, out, n_indices, mem_kind));
         HIPCHK(c, hipMemcpyAsync(c->u_host + 1, status, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         bad = c->u_host[1];
@@ -628,7 +605,7 @@ int mi_icp_select_by_index(mi_icp_ctx* c, const float* xyz, const float* normals
 int mi_icp_uniform_downsample(mi_icp_ctx* c, const float* xyz, const float* normals, const float* colors, int64_t n,
                               int64_t every_k_points, float* out_xyz, float* out_normals, float* out_colors, int64_t* m,
                               int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "uniform_downsample"));
     if (!m) return fail(c, MI_ICP_ERR_INVALID, "uniform_downsample: m is null");
     *m = 0;
     if (n < 0) return fail(c, MI_ICP_ERR_INVALID, "uniform_downsample: bad size");
@@ -688,7 +665,7 @@ int mi_icp_create_from_depth(mi_icp_ctx* c, const void* depth, int depth_type, c
                              float depth_scale, float depth_trunc, float depth_cutoff, int stride, int rgbd,
                              int compute_normals, int valid_only, float* out_xyz, float* out_normals,
                              float* out_colors, int64_t* m, int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "create_from_depth"));
     if (!m) return fail(c, MI_ICP_ERR_INVALID, "create_from_depth: m is null");
     *m = 0;
     if (width < 0 || height < 0 || stride < 1 || !intrinsic4 || (depth_type != MI_ICP_DEPTH_F32 && depth_type != MI_ICP_DEPTH_U16) ||
@@ -746,19 +723,12 @@ int mi_icp_create_from_depth(mi_icp_ctx* c, const void* depth, int depth_type, c
         HIPCHK(c, hipStreamSynchronize(c->stream));
         kept = (int64_t)c->u_host[0];
     }
-    float *op = out_xyz, *on = compute_normals ? out_normals : nullptr, *oc = color ? out_colors : nullptr;
-    if (mem_kind == MI_ICP_HOST) {
-        TRY(ensure(c, c->stage[3], (size_t)count * 3, &op));
-        if (on) TRY(ensure(c, c->stage[4], (size_t)count * 3, &on));
-        if (oc) TRY(ensure(c, c->stage[5], (size_t)count * 3, &oc));
-    }
-    depth_emit<<<nb, 256, 0, c->stream>>>(a, count, pos, op, on, oc);
+    float* const out[3] = {out_xyz, compute_normals ? out_normals : nullptr, color ? out_colors : nullptr};
+    float* dst[3];
+    TRY(cloud_out(c, out, out, count, mem_kind, c->stage + 3, dst));
+    depth_emit<<<nb, 256, 0, c->stream>>>(a, count, pos, dst[0], dst[1], dst[2]);
     KCHK(c);
-    if (mem_kind == MI_ICP_HOST) {
-        TRY(from_device(c, (const float*)op, out_xyz, (size_t)kept * 3, mem_kind));
-        if (on) TRY(from_device(c, (const float*)on, out_normals, (size_t)kept * 3, mem_kind));
-        if (oc) TRY(from_device(c, (const float*)oc, out_colors, (size_t)kept * 3, mem_kind));
-    }
+    TRY(cloud_out_back(c, dst, out, kept, mem_kind));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *m = kept;
     return MI_ICP_OK;
@@ -772,7 +742,7 @@ static int rgbd_odometry_impl(mi_icp_ctx* c, const float* source_color, const fl
                               const mi_icp_odometry_option* option, int* success, float* transformation16,
                               double* information36, int mem_kind, bool weighted, const float* prev_twist6,
                               float* twist6) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "compute_rgbd_odometry"));
     if (twist6)
         for (int i = 0; i < 6; ++i) twist6[i] = 0.0f;
     if (!success || !transformation16 || !information36 || !intrinsic4 || !option)
@@ -1003,7 +973,7 @@ int mi_icp_compute_weighted_rgbd_odometry(mi_icp_ctx* c, const float* source_col
 // ---------------------------------------------------------------------------
 // Colored ICP (registration/colored_icp.cu)
 int mi_icp_set_target_colors(mi_icp_ctx* c, const float* rgb, int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "set_target_colors"));
     c->t_has_int = c->t_has_grad = false;
     if (!rgb || c->nt <= 0) return MI_ICP_OK;
     if (!c->t_has_nrm)  // the intensities ride in the normals' 4th lane; colored ICP needs normals anyway
@@ -1018,7 +988,7 @@ int mi_icp_set_target_colors(mi_icp_ctx* c, const float* rgb, int mem_kind) {
 }
 
 int mi_icp_set_source_colors(mi_icp_ctx* c, const float* rgb, int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "set_source_colors"));
     c->s_has_int = false;
     if (!rgb || c->ns <= 0) return MI_ICP_OK;
     const float* d_rgb;

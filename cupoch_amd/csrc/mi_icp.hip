@@ -452,7 +452,7 @@ static int export_dense_idx(mi_icp_ctx* c, int32_t** dense_out) {
 
 int mi_icp_search_radius_1nn(mi_icp_ctx* c, const float* T, float radius, int32_t* idx_out,
                              float* d2_out, int mem_kind, double* stats) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "search"));
     if (c->ns <= 0) return fail(c, MI_ICP_ERR_STATE, "search: no source set");
     const Mat4 M = load_T(T);
     const float r2 = radius * radius;  // kdtree_flann.inl:119-120
@@ -490,7 +490,7 @@ int mi_icp_search_radius_1nn(mi_icp_ctx* c, const float* T, float radius, int32_
 
 int mi_icp_get_correspondences(mi_icp_ctx* c, int32_t* pairs, int64_t capacity, int64_t* count,
                                int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "get_correspondences"));
     if (!count) return fail(c, MI_ICP_ERR_INVALID, "get_correspondences: count is null");
     *count = 0;
     if (c->n_user_pairs >= 0) {
@@ -526,7 +526,7 @@ int mi_icp_get_correspondences(mi_icp_ctx* c, int32_t* pairs, int64_t capacity, 
 }
 
 int mi_icp_set_correspondences(mi_icp_ctx* c, const int32_t* pairs, int64_t count, int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "set_correspondences"));
     if (count < 0 || (count > 0 && !pairs)) return fail(c, MI_ICP_ERR_INVALID, "set_correspondences: bad arguments");
     int32_t* d;
     TRY(ensure(c, c->user_pairs, (size_t)std::max<int64_t>(count, 1) * 2, &d));

@@ -63,37 +63,42 @@ int launch_knn_normals(mi_icp_ctx* c, int k, float r2, float* out, const float4*
                       c->nleaf, k, r2, out, tnrm, tgrad);
 }
 
+// Runs body(a) in the private scratch context a = c->aux (made on first use, on c's stream): a registration in flight
+// on c (user estimators may call EstimateNormals between iterations) keeps its target, source, correspondences and
+// loop state.  A failure is reported on c as "what: <a's error>".
+template <class Body>
+int in_scratch(mi_icp_ctx* c, const char* what, Body body) {
+    if (!c->aux) {
+        const int rc = mi_icp_create(c->device, &c->aux);
+        if (rc != MI_ICP_OK) return fail(c, rc, "%s: cannot create the scratch context", what);
+    }
+    mi_icp_ctx* a = c->aux;
+    a->stream = c->stream;
+    const int rc = body(a);
+    if (rc != MI_ICP_OK) return fail(c, rc, "%s: %s", what, a->err.c_str());
+    return MI_ICP_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 static int estimate_normals_impl(mi_icp_ctx* c, const float* xyz, int64_t n, int knn, float r2,
                                  float* normals, int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "estimate_normals"));
     if (n < 0 || (n > 0 && (!xyz || !normals))) return fail(c, MI_ICP_ERR_INVALID, "estimate_normals: bad arguments");
     if (knn > kKnnLimit) return fail(c, MI_ICP_ERR_INVALID, "estimate_normals: more than %d neighbours (knn::NUM_MAX_NN) are not supported", kKnnLimit);
     if (n == 0) return MI_ICP_OK;
-    // The cloud gets a tree of its own in a private scratch context: a registration in flight on
-    // this context (user estimators may call EstimateNormals between iterations) keeps its
-    // target, source, correspondences and loop state.
-    if (!c->aux) {
-        const int rc = mi_icp_create(c->device, &c->aux);
-        if (rc != MI_ICP_OK) return fail(c, rc, "estimate_normals: cannot create the scratch context");
-    }
-    mi_icp_ctx* a = c->aux;
-    a->stream = c->stream;
-    auto run = [&]() -> int {
+    // the cloud gets a tree of its own in the private scratch context
+    return in_scratch(c, "estimate_normals", [&](mi_icp_ctx* a) -> int {
         TRY(mi_icp_set_target(a, xyz, nullptr, nullptr, n, mem_kind));
-        float* dn = normals;
-        if (mem_kind == MI_ICP_HOST) TRY(ensure(a, a->stage[1], (size_t)n * 3, &dn));
+        float* dn;
+        TRY(out_slot(a, normals, (size_t)n * 3, mem_kind, a->stage[1], &dn));
         TRY(launch_knn_normals<0>(a, knn, r2, dn, nullptr, nullptr));
-        if (mem_kind == MI_ICP_HOST) TRY(from_device(a, (const float*)dn, normals, (size_t)n * 3, mem_kind));
+        TRY(from_device(a, (const float*)dn, normals, (size_t)n * 3, mem_kind));
         HIPCHK(a, hipStreamSynchronize(a->stream));
         return MI_ICP_OK;
-    };
-    const int rc = run();
-    if (rc != MI_ICP_OK) return fail(c, rc, "estimate_normals: %s", a->err.c_str());
-    return MI_ICP_OK;
+    });
 }
 
 int mi_icp_estimate_normals_knn(mi_icp_ctx* c, const float* xyz, int64_t n, int knn, float* normals,
@@ -118,20 +123,15 @@ static int outlier_impl(mi_icp_ctx* c, const char* what, bool radius, const floa
                         float* out_normals, float* out_colors, int64_t* out_indices, void* stat_out, int64_t* m,
                         int mem_kind) {
     if (n == 0) return MI_ICP_OK;
-    if (!c->aux) {
-        const int rc = mi_icp_create(c->device, &c->aux);
-        if (rc != MI_ICP_OK) return fail(c, rc, "%s: cannot create the scratch context", what);
-    }
-    mi_icp_ctx* a = c->aux;
-    a->stream = c->stream;
-    auto run = [&]() -> int {
+    return in_scratch(c, what, [&](mi_icp_ctx* a) -> int {
         const float* in[3];
         TRY(to_device(a, xyz, (size_t)n * 3, mem_kind, a->stage[0], &in[0]));
         TRY(to_device(a, normals, (size_t)n * 3, mem_kind, a->stage[1], &in[1]));
         TRY(to_device(a, colors, (size_t)n * 3, mem_kind, a->stage[2], &in[2]));
         TRY(mi_icp_set_target(a, in[0], nullptr, nullptr, n, MI_ICP_DEVICE));
-        float* stat = (float*)stat_out;  // float avg or int32 count, [n] in the cloud's order
-        if (!stat || mem_kind == MI_ICP_HOST) TRY(ensure(a, a->stage[3], (size_t)n, &stat));
+        float* stat;  // float avg or int32 count, [n] in the cloud's order
+        TRY(out_slot(a, (float*)stat_out, (size_t)n, mem_kind, a->stage[3], &stat));
+        if (!stat) TRY(ensure(a, a->stage[3], (size_t)n, &stat));  // (the caller does not want them)
         uint32_t* flags;
         TRY(ensure(a, a->flags, (size_t)n, &flags));
         if (!radius) {
@@ -148,13 +148,10 @@ static int outlier_impl(mi_icp_ctx* c, const char* what, bool radius, const floa
             outlier_flags_radius<<<blocks_for(n), 256, 0, a->stream>>>((const int32_t*)stat, n, k, flags);
         }
         KCHK(a);
-        if (stat_out && mem_kind == MI_ICP_HOST) TRY(from_device(a, (const float*)stat, (float*)stat_out, (size_t)n, mem_kind));
+        TRY(from_device(a, (const float*)stat, (float*)stat_out, (size_t)n, mem_kind));
         float* const out[3] = {out_xyz, out_normals, out_colors};
         return compact_by_flags(a, flags, n, in, out, out_indices, mem_kind, nullptr, m, nullptr);
-    };
-    const int rc = run();
-    if (rc != MI_ICP_OK) return fail(c, rc, "%s: %s", what, a->err.c_str());
-    return MI_ICP_OK;
+    });
 }
 
 static int outlier_args(mi_icp_ctx* c, const char* what, const float* xyz, const float* normals, const float* colors,
@@ -171,7 +168,7 @@ int mi_icp_remove_statistical_outliers(mi_icp_ctx* c, const float* xyz, const fl
                                        int64_t n, int nb_neighbors, float std_ratio, float* out_xyz, float* out_normals,
                                        float* out_colors, int64_t* out_indices, float* avg_d2, int64_t* m, int mem_kind) {
     const char* what = "remove_statistical_outliers";
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, what));
     TRY(outlier_args(c, what, xyz, normals, colors, n, out_xyz, out_normals, out_colors, m));
     if (nb_neighbors < 1) return fail(c, MI_ICP_ERR_INVALID, "%s: nb_neighbors must be positive", what);
     if (!(std_ratio > 0.0f)) return fail(c, MI_ICP_ERR_INVALID, "%s: std_ratio must be positive", what);
@@ -185,7 +182,7 @@ int mi_icp_remove_radius_outliers(mi_icp_ctx* c, const float* xyz, const float* 
                                   int nb_points, float radius, float* out_xyz, float* out_normals, float* out_colors,
                                   int64_t* out_indices, int32_t* counts, int64_t* m, int mem_kind) {
     const char* what = "remove_radius_outliers";
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, what));
     TRY(outlier_args(c, what, xyz, normals, colors, n, out_xyz, out_normals, out_colors, m));
     if (nb_points < 1) return fail(c, MI_ICP_ERR_INVALID, "%s: nb_points must be positive", what);
     if (!(radius > 0.0f)) return fail(c, MI_ICP_ERR_INVALID, "%s: search_radius must be positive", what);
@@ -203,14 +200,8 @@ int mi_icp_remove_radius_outliers(mi_icp_ctx* c, const float* xyz, const float* 
 // with one wait when the first batch settles, as it does whenever no row is truncated.
 static int dbscan_impl(mi_icp_ctx* c, const float* xyz, int64_t n, float r2, int min_points, int max_edges,
                        int32_t* labels, int32_t* degrees, int64_t* n_clusters, int mem_kind) {
-    if (!c->aux) {
-        const int rc = mi_icp_create(c->device, &c->aux);
-        if (rc != MI_ICP_OK) return fail(c, rc, "cluster_dbscan: cannot create the scratch context");
-    }
-    mi_icp_ctx* a = c->aux;
-    a->stream = c->stream;
     const int k = max_edges + 1;
-    auto run = [&]() -> int {
+    return in_scratch(c, "cluster_dbscan", [&](mi_icp_ctx* a) -> int {
         TRY(mi_icp_set_target(a, xyz, nullptr, nullptr, n, mem_kind));
         int32_t *rows, *node;
         uint4* mask;
@@ -224,12 +215,9 @@ static int dbscan_impl(mi_icp_ctx* c, const float* xyz, int64_t n, float r2, int
         int32_t *word = node, *rep = node + n, *m = node + 2 * n, *Mx = node + 3 * n;
         uint32_t* start = (uint32_t*)(node + 4 * n);
         uint32_t* number = (uint32_t*)(node + 5 * n);
-        int32_t* dl = labels;
-        int32_t* dd = degrees;
-        if (mem_kind == MI_ICP_HOST) {
-            TRY(ensure(a, a->stage[1], (size_t)n, &dl));
-            if (degrees) TRY(ensure(a, a->stage[2], (size_t)n, &dd));
-        }
+        int32_t *dl, *dd;
+        TRY(out_slot(a, labels, (size_t)n, mem_kind, a->stage[1], &dl));
+        TRY(out_slot(a, degrees, (size_t)n, mem_kind, a->stage[2], &dd));
         TRY(launch_knn_normals<4>(a, k, r2, (float*)rows, nullptr, (float4*)word));
         HIPCHK(a, hipMemsetAsync(st, 0, sizeof(DbscanState), a->stream));
         const int nb = blocks_for(n);
@@ -250,10 +238,8 @@ static int dbscan_impl(mi_icp_ctx* c, const float* xyz, int64_t n, float r2, int
             HIPCHK(a, hipMemcpyAsync(a->u_host, st, sizeof(DbscanState), hipMemcpyDeviceToHost, a->stream));
             HIPCHK(a, hipMemcpyAsync(a->u_host + 4, tmp + scan_num_tiles(n), sizeof(uint32_t), hipMemcpyDeviceToHost,
                                      a->stream));
-            if (mem_kind == MI_ICP_HOST) {
-                TRY(from_device(a, (const int32_t*)dl, labels, (size_t)n, mem_kind));
-                if (degrees) TRY(from_device(a, (const int32_t*)dd, degrees, (size_t)n, mem_kind));
-            }
+            TRY(from_device(a, (const int32_t*)dl, labels, (size_t)n, mem_kind));
+            TRY(from_device(a, (const int32_t*)dd, degrees, (size_t)n, mem_kind));
             HIPCHK(a, hipStreamSynchronize(a->stream));
             DbscanState s;
             std::memcpy(&s, a->u_host, sizeof(s));
@@ -265,16 +251,13 @@ static int dbscan_impl(mi_icp_ctx* c, const float* xyz, int64_t n, float r2, int
             if ((uint64_t)s.rounds >= 2ull * ((uint64_t)s.oneway + 1ull))
                 return fail(a, MI_ICP_ERR_STATE, "the one-way edges did not settle in %u rounds", s.rounds);
         }
-    };
-    const int rc = run();
-    if (rc != MI_ICP_OK) return fail(c, rc, "cluster_dbscan: %s", a->err.c_str());
-    return MI_ICP_OK;
+    });
 }
 
 int mi_icp_cluster_dbscan(mi_icp_ctx* c, const float* xyz, int64_t n, float eps, int64_t min_points, int max_edges,
                           int32_t* labels, int32_t* degrees, int64_t* n_clusters, int mem_kind) {
     const char* what = "cluster_dbscan";
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, what));
     if (!n_clusters) return fail(c, MI_ICP_ERR_INVALID, "%s: n_clusters is null", what);
     *n_clusters = 0;
     if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
@@ -284,7 +267,6 @@ int mi_icp_cluster_dbscan(mi_icp_ctx* c, const float* xyz, int64_t n, float eps,
     if (min_points < 0) return fail(c, MI_ICP_ERR_INVALID, "%s: min_points must not be negative", what);
     if (max_edges < 0 || max_edges > kKnnLimit)
         return fail(c, MI_ICP_ERR_INVALID, "%s: max_edges outside [0, %d] (knn::NUM_MAX_NN)", what, kKnnLimit);
-    if (mem_kind != MI_ICP_HOST && mem_kind != MI_ICP_DEVICE) return fail(c, MI_ICP_ERR_INVALID, "%s: bad mem_kind", what);
     if (n == 0) return MI_ICP_OK;
     // (a degree is at most max_edges + 1: every larger threshold means "no core point")
     const int mp = (int)std::min<int64_t>(min_points, kKnnLimit + 2);
@@ -295,7 +277,7 @@ int mi_icp_cluster_dbscan(mi_icp_ctx* c, const float* xyz, int64_t n, float eps,
 // knn::KDTreeFlann::SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122)
 int mi_icp_search_knn(mi_icp_ctx* c, const float* queries, int64_t nq, int knn, float radius, int32_t* idx_out,
                       float* d2_out, int64_t* found, int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "search_knn"));
     if (found) *found = 0;
     if (nq < 0 || knn < 0 || (nq > 0 && (!queries || !idx_out || !d2_out)))
         return fail(c, MI_ICP_ERR_INVALID, "search_knn: bad arguments");
@@ -304,12 +286,10 @@ int mi_icp_search_knn(mi_icp_ctx* c, const float* queries, int64_t nq, int knn, 
     if (nq == 0 || knn == 0) return MI_ICP_OK;
     // the queries are staged exactly like an ICP source (Morton-ordered SoA + permutation)
     TRY(mi_icp_set_source(c, queries, nullptr, nullptr, nq, mem_kind));
-    int32_t* d_idx = idx_out;
-    float* d_d2 = d2_out;
-    if (mem_kind == MI_ICP_HOST) {
-        TRY(ensure(c, c->stage[4], (size_t)nq * knn, (int32_t**)&d_idx));
-        TRY(ensure(c, c->stage[5], (size_t)nq * knn, &d_d2));
-    }
+    int32_t* d_idx;
+    float* d_d2;
+    TRY(out_slot(c, idx_out, (size_t)nq * knn, mem_kind, c->stage[4], &d_idx));
+    TRY(out_slot(c, d2_out, (size_t)nq * knn, mem_kind, c->stage[5], &d_d2));
     unsigned long long* cnt;
     TRY(ensure(c, c->flags, 1, (unsigned long long**)&cnt));
     HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(unsigned long long), c->stream));
@@ -317,10 +297,8 @@ int mi_icp_search_knn(mi_icp_ctx* c, const float* queries, int64_t nq, int knn, 
                    (const float*)c->nodes.p, (const float*)c->tblk.p, (const int32_t*)c->tidx.p, c->leaf_first,
                    (const float*)c->sx.p, (const float*)c->sy.p, (const float*)c->sz.p, (const int32_t*)c->sperm.p, (int)nq,
                    c->nleaf, knn, radius > 0.0f ? radius * radius : INFINITY, d_idx, d_d2, cnt));
-    if (mem_kind == MI_ICP_HOST) {
-        TRY(from_device(c, (const int32_t*)d_idx, idx_out, (size_t)nq * knn, mem_kind));
-        TRY(from_device(c, (const float*)d_d2, d2_out, (size_t)nq * knn, mem_kind));
-    }
+    TRY(from_device(c, (const int32_t*)d_idx, idx_out, (size_t)nq * knn, mem_kind));
+    TRY(from_device(c, (const float*)d_d2, d2_out, (size_t)nq * knn, mem_kind));
     HIPCHK(c, hipMemcpyAsync(c->sys_host, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (found) *found = (int64_t) * reinterpret_cast<unsigned long long*>(c->sys_host);
@@ -328,7 +306,7 @@ int mi_icp_search_knn(mi_icp_ctx* c, const float* queries, int64_t nq, int knn, 
 }
 
 int mi_icp_compute_color_gradients(mi_icp_ctx* c, float radius, int max_nn, float* gradients_out, int mem_kind) {
-    TRY(check_ctx(c));
+    TRY(check_ctx(c, mem_kind, "compute_color_gradients"));
     c->t_has_grad = false;
     if (c->nt <= 0) return MI_ICP_OK;
     if (!c->t_has_nrm || !c->t_has_int)
@@ -338,12 +316,12 @@ int mi_icp_compute_color_gradients(mi_icp_ctx* c, float radius, int max_nn, floa
     const int64_t n = c->nt;
     float4* tgrad;
     TRY(ensure(c, c->tgrad, (size_t)c->nts, &tgrad));
-    float* dg = gradients_out;
-    if (gradients_out && mem_kind == MI_ICP_HOST) TRY(ensure(c, c->stage[1], (size_t)n * 3, &dg));
+    float* dg;
+    TRY(out_slot(c, gradients_out, (size_t)n * 3, mem_kind, c->stage[1], &dg));
     TRY(launch_knn_normals<1>(c, max_nn, radius * radius, dg, (const float4*)c->tnrm.p, tgrad));
     c->t_has_grad = true;
     if (gradients_out) {
-        if (mem_kind == MI_ICP_HOST) TRY(from_device(c, (const float*)dg, gradients_out, (size_t)n * 3, mem_kind));
+        TRY(from_device(c, (const float*)dg, gradients_out, (size_t)n * 3, mem_kind));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return MI_ICP_OK;

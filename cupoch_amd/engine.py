@@ -24,12 +24,13 @@ def _is_tensor(a):
 
 class _Buf:
     """A float32/int32 array argument: keeps the backing object alive and exposes
-    (pointer, mem_kind)."""
+    (pointer, mem_kind) and, for a device array, its torch device."""
 
     def __init__(self, a, dtype, cols, device_index, copy=False):
         self.keep = None
         self.ptr = None
         self.kind = MI_ICP_HOST
+        self.device = None
         self.n = 0
         if a is None:
             return
@@ -44,6 +45,7 @@ class _Buf:
                     raise MiIcpError("tensor on cuda:%s passed to an engine on cuda:%s"
                                      % (t.device.index, device_index))
                 self.kind = MI_ICP_DEVICE
+                self.device = t.device
                 self.ptr = C.c_void_p(t.data_ptr())
             else:
                 t = t.numpy()
@@ -120,26 +122,37 @@ class Engine:
             raise MiIcpError("all arrays of one call must live on the same side (host or device)")
         return kinds.pop() if kinds else MI_ICP_HOST
 
+    @staticmethod
+    def _out(kind, device, shape, dtype=np.float32):
+        """an empty output array: a torch tensor on `device` (MI_ICP_DEVICE) or a numpy array; (array, pointer)"""
+        if kind == MI_ICP_DEVICE:
+            tdt = {np.float32: torch.float32, np.int32: torch.int32, np.int64: torch.int64}[dtype]
+            t = torch.empty(shape, dtype=tdt, device=device)
+            return t, C.c_void_p(t.data_ptr())
+        a = np.empty(shape, dtype)
+        return a, a.ctypes.data_as(C.c_void_p)
+
+    @staticmethod
+    def _trim(t, k):
+        return None if t is None else t[:k]
+
     # -- clouds ------------------------------------------------------------------
-    def set_target(self, points, normals=None, covariances=None):
+    def _set_cloud(self, fn, points, normals, covariances):
+        """mi_icp_set_target / mi_icp_set_source; returns the cloud's size"""
         self.generation = getattr(self, "generation", 0) + 1   # the clouds changed (registration._generic_icp)
         p = _Buf(points, np.float32, 3, self.device)
         n = _Buf(normals, np.float32, 3, self.device)
         c = _Buf(_cov_in(covariances), np.float32, 9, self.device)
         kind = self._same_kind(p, n, c)
-        self._chk(self._L.mi_icp_set_target(self._ctx, p.ptr, n.ptr, c.ptr, p.n, kind))
+        self._chk(fn(self._ctx, p.ptr, n.ptr, c.ptr, p.n, kind))
         self.synchronize()  # the staging copies above may be freed by the caller now
-        self.n_target = p.n
+        return p.n
+
+    def set_target(self, points, normals=None, covariances=None):
+        self.n_target = self._set_cloud(self._L.mi_icp_set_target, points, normals, covariances)
 
     def set_source(self, points, normals=None, covariances=None):
-        self.generation = getattr(self, "generation", 0) + 1
-        p = _Buf(points, np.float32, 3, self.device)
-        n = _Buf(normals, np.float32, 3, self.device)
-        c = _Buf(_cov_in(covariances), np.float32, 9, self.device)
-        kind = self._same_kind(p, n, c)
-        self._chk(self._L.mi_icp_set_source(self._ctx, p.ptr, n.ptr, c.ptr, p.n, kind))
-        self.synchronize()
-        self.n_source = p.n
+        self.n_source = self._set_cloud(self._L.mi_icp_set_source, points, normals, covariances)
 
     # -- KDTreeFlann-style search against the target ---------------------------------------
     def search_knn(self, queries, knn, radius=0.0):
@@ -148,14 +161,8 @@ class Engine:
         context's source cloud."""
         q = _Buf(queries, np.float32, 3, self.device)
         knn = int(knn)
-        if q.kind == MI_ICP_DEVICE:
-            idx = torch.empty((q.n, knn), dtype=torch.int32, device=q.keep.device)
-            d2 = torch.empty((q.n, knn), dtype=torch.float32, device=q.keep.device)
-            ip, dp = C.c_void_p(idx.data_ptr()), C.c_void_p(d2.data_ptr())
-        else:
-            idx = np.empty((q.n, knn), np.int32)
-            d2 = np.empty((q.n, knn), np.float32)
-            ip, dp = idx.ctypes.data_as(C.c_void_p), d2.ctypes.data_as(C.c_void_p)
+        idx, ip = self._out(q.kind, q.device, (q.n, knn), np.int32)
+        d2, dp = self._out(q.kind, q.device, (q.n, knn))
         found = C.c_int64(0)
         self._chk(self._L.mi_icp_search_knn(self._ctx, q.ptr, q.n, knn, float(radius), ip, dp,
                                             C.byref(found), q.kind))
@@ -184,10 +191,7 @@ class Engine:
     def compute_color_gradients(self, radius, max_nn=30, want_output=True):
         """InitializePointCloudForColoredICP; returns the gradients (target's original
         order, numpy) when want_output."""
-        out, optr = None, None
-        if want_output:
-            out = np.empty((self.n_target, 3), np.float32)
-            optr = out.ctypes.data_as(C.c_void_p)
+        out, optr = self._out(MI_ICP_HOST, None, (self.n_target, 3)) if want_output else (None, None)
         self._chk(self._L.mi_icp_compute_color_gradients(self._ctx, float(radius), int(max_nn), optr,
                                                          MI_ICP_HOST))
         return out
@@ -210,13 +214,11 @@ class Engine:
         p = _Buf(points, np.float32, 3, self.device)
         if p.n == 0:
             return np.zeros(0, np.int64)
+        out, optr = self._out(p.kind, p.device, (p.n,), np.int32)
+        self._chk(self._L.mi_icp_spatial_order(self._ctx, p.ptr, p.n, optr, p.kind))
         if p.kind == MI_ICP_DEVICE:
-            out = torch.empty(p.n, dtype=torch.int32, device=p.keep.device)
-            self._chk(self._L.mi_icp_spatial_order(self._ctx, p.ptr, p.n, C.c_void_p(out.data_ptr()), p.kind))
-            return out.cpu().numpy().view(np.uint32).astype(np.int64)
-        out = np.empty(p.n, np.uint32)
-        self._chk(self._L.mi_icp_spatial_order(self._ctx, p.ptr, p.n, out.ctypes.data_as(C.c_void_p), p.kind))
-        return out.astype(np.int64)
+            out = out.cpu().numpy()
+        return out.view(np.uint32).astype(np.int64)
 
     def set_global_source_count(self, n_total):
         self._chk(self._L.mi_icp_set_global_source_count(self._ctx, int(n_total)))
@@ -225,14 +227,12 @@ class Engine:
     def search_radius_1nn(self, radius, T=None, want_d2=True):
         """(indices[int32 n], d2[float32 n], stats) in original source order;
         -1 / +inf where no target point lies within `radius` (strict)."""
-        idx = np.empty(self.n_source, np.int32)
-        d2 = np.empty(self.n_source, np.float32) if want_d2 else None
+        idx, ip = self._out(MI_ICP_HOST, None, (self.n_source,), np.int32)
+        d2, dp = self._out(MI_ICP_HOST, None, (self.n_source,)) if want_d2 else (None, None)
         stats = np.zeros(3, np.float64)
         _, tp = _T_in(T)
-        self._chk(self._L.mi_icp_search_radius_1nn(
-            self._ctx, tp, float(radius), idx.ctypes.data_as(C.c_void_p),
-            None if d2 is None else d2.ctypes.data_as(C.c_void_p), MI_ICP_HOST,
-            stats.ctypes.data_as(C.c_void_p)))
+        self._chk(self._L.mi_icp_search_radius_1nn(self._ctx, tp, float(radius), ip, dp, MI_ICP_HOST,
+                                                   stats.ctypes.data_as(C.c_void_p)))
         return idx, d2, stats
 
     def drop_seeds(self):
@@ -246,10 +246,9 @@ class Engine:
     def get_correspondences(self):
         cnt = C.c_int64(0)
         self._chk(self._L.mi_icp_get_correspondences(self._ctx, None, 0, C.byref(cnt), MI_ICP_HOST))
-        out = np.empty((max(cnt.value, 0), 2), np.int32)
+        out, optr = self._out(MI_ICP_HOST, None, (max(cnt.value, 0), 2), np.int32)
         if cnt.value > 0:
-            self._chk(self._L.mi_icp_get_correspondences(
-                self._ctx, out.ctypes.data_as(C.c_void_p), cnt.value, C.byref(cnt), MI_ICP_HOST))
+            self._chk(self._L.mi_icp_get_correspondences(self._ctx, optr, cnt.value, C.byref(cnt), MI_ICP_HOST))
         return out
 
     def set_correspondences(self, pairs):
@@ -347,61 +346,38 @@ class Engine:
         self.synchronize()
         return p.keep, n.keep, _cov_out(c.keep)
 
-    def voxel_downsample(self, points, voxel_size, normals=None, colors=None):
-        p = _Buf(points, np.float32, 3, self.device)
-        n = _Buf(normals, np.float32, 3, self.device)
-        c = _Buf(colors, np.float32, 3, self.device)
-        kind = self._same_kind(p, n, c)
-        m = C.c_int64(0)
-        if kind == MI_ICP_DEVICE:
-            dev = p.keep.device
-            mk = lambda b: torch.empty((p.n, 3), dtype=torch.float32, device=dev) if b.ptr is not None else None
-            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        else:
-            mk = lambda b: np.empty((p.n, 3), np.float32) if b.ptr is not None else None
-            ptr = lambda t: None if t is None else t.ctypes.data_as(C.c_void_p)
-        op, on, oc = mk(p), mk(n), mk(c)
-        self._chk(self._L.mi_icp_voxel_downsample(self._ctx, p.ptr, n.ptr, c.ptr, p.n,
-                                                  float(voxel_size), ptr(op), ptr(on), ptr(oc),
-                                                  C.byref(m), kind))
-        k = int(m.value)
-        cut = lambda t: None if t is None else t[:k]
-        return cut(op) if op is not None else np.empty((0, 3), np.float32), cut(on), cut(oc)
-
-    # -- PointCloud::SelectByIndex / UniformDownSample / Remove*Outliers (down_sample.cu:40-438) -------------
+    # -- PointCloud::VoxelDownSample / SelectByIndex / UniformDownSample / Remove*Outliers (down_sample.cu) --------
     def _cloud_args(self, points, normals, colors):
         p = _Buf(points, np.float32, 3, self.device)
         n = _Buf(normals, np.float32, 3, self.device)
         c = _Buf(colors, np.float32, 3, self.device)
         return p, n, c, self._same_kind(p, n, c)
 
-    @staticmethod
-    def _out(kind, like, rows, cols=3, dtype=np.float32):
-        """an output array of `rows` entries on the side of `like` (a _Buf); (array, pointer)"""
-        shape = (rows, cols) if cols else (rows,)
-        if kind == MI_ICP_DEVICE:
-            tdt = {np.float32: torch.float32, np.int32: torch.int32, np.int64: torch.int64}[dtype]
-            t = torch.empty(shape, dtype=tdt, device=like.keep.device)
-            return t, C.c_void_p(t.data_ptr())
-        a = np.empty(shape, dtype)
-        return a, a.ctypes.data_as(C.c_void_p)
-
     def _cloud_outputs(self, kind, p, n, c, rows):
-        op = self._out(kind, p, rows)
-        on = self._out(kind, p, rows) if n.ptr is not None else (None, None)
-        oc = self._out(kind, p, rows) if c.ptr is not None else (None, None)
+        op = self._out(kind, p.device, (rows, 3))
+        on = self._out(kind, p.device, (rows, 3)) if n.ptr is not None else (None, None)
+        oc = self._out(kind, p.device, (rows, 3)) if c.ptr is not None else (None, None)
         return op, on, oc
+
+    def voxel_downsample(self, points, voxel_size, normals=None, colors=None):
+        p, n, c, kind = self._cloud_args(points, normals, colors)
+        (op, pp), (on, pn), (oc, pc) = self._cloud_outputs(kind, p, n, c, p.n)
+        m = C.c_int64(0)
+        self._chk(self._L.mi_icp_voxel_downsample(self._ctx, p.ptr, n.ptr, c.ptr, p.n, float(voxel_size), pp, pn, pc,
+                                                  C.byref(m), kind))
+        k = int(m.value)
+        return (self._trim(op, k) if p.ptr is not None else np.empty((0, 3), np.float32)), self._trim(on, k), \
+            self._trim(oc, k)
 
     def _outlier_filter(self, fn, points, k, param, normals, colors, stat_dtype):
         p, n, c, kind = self._cloud_args(points, normals, colors)
         (op, pp), (on, pn), (oc, pc) = self._cloud_outputs(kind, p, n, c, p.n)
-        idx, pidx = self._out(kind, p, p.n, 0, np.int64)
-        stat, pstat = self._out(kind, p, p.n, 0, stat_dtype)
+        idx, pidx = self._out(kind, p.device, (p.n,), np.int64)
+        stat, pstat = self._out(kind, p.device, (p.n,), stat_dtype)
         m = C.c_int64(0)
         self._chk(fn(self._ctx, p.ptr, n.ptr, c.ptr, p.n, int(k), float(param), pp, pn, pc, pidx, pstat, C.byref(m), kind))
         k = int(m.value)
-        cut = lambda t: None if t is None else t[:k]
-        return cut(op), cut(on), cut(oc), idx[:k], stat
+        return self._trim(op, k), self._trim(on, k), self._trim(oc, k), idx[:k], stat
 
     def remove_statistical_outliers(self, points, nb_neighbors, std_ratio, normals=None, colors=None):
         """PointCloud::RemoveStatisticalOutliers (down_sample.cu:354-438).  Returns (points, normals or None,
@@ -420,8 +396,8 @@ class Engine:
         Returns (labels int32[n], degrees int32[n], n_clusters), on the side of `points`."""
         p = _Buf(points, np.float32, 3, self.device)
         kind = self._same_kind(p)
-        labels, plab = self._out(kind, p, p.n, 0, np.int32)
-        degrees, pdeg = self._out(kind, p, p.n, 0, np.int32)
+        labels, plab = self._out(kind, p.device, (p.n,), np.int32)
+        degrees, pdeg = self._out(kind, p.device, (p.n,), np.int32)
         nc = C.c_int64(0)
         self._chk(self._L.mi_icp_cluster_dbscan(self._ctx, p.ptr, p.n, float(eps), int(min_points), int(max_edges),
                                                 plab, pdeg, C.byref(nc), kind))
@@ -432,8 +408,8 @@ class Engine:
         the points' device, a numpy array, a list); returns (points, normals or None, colors or None)."""
         p, n, c, kind = self._cloud_args(points, normals, colors)
         if kind == MI_ICP_DEVICE:
-            ix = torch.as_tensor(indices).to(device=p.keep.device, dtype=torch.int64).reshape(-1).contiguous() \
-                if _is_tensor(indices) else torch.from_numpy(np.ascontiguousarray(np.asarray(indices, np.int64).reshape(-1))).to(p.keep.device)
+            ix = torch.as_tensor(indices).to(device=p.device, dtype=torch.int64).reshape(-1).contiguous() \
+                if _is_tensor(indices) else torch.from_numpy(np.ascontiguousarray(np.asarray(indices, np.int64).reshape(-1))).to(p.device)
             pix, nix = C.c_void_p(ix.data_ptr()), int(ix.shape[0])
         else:
             ix = indices.detach().cpu().numpy() if _is_tensor(indices) else indices
@@ -445,8 +421,7 @@ class Engine:
         self._chk(self._L.mi_icp_select_by_index(self._ctx, p.ptr, n.ptr, c.ptr, p.n, pix, nix, int(bool(invert)),
                                                  pp, pn, pc, C.byref(m), kind))
         k = int(m.value)
-        cut = lambda t: None if t is None else t[:k]
-        return cut(op), cut(on), cut(oc)
+        return self._trim(op, k), self._trim(on, k), self._trim(oc, k)
 
     def uniform_downsample(self, points, every_k_points, normals=None, colors=None):
         """PointCloud::UniformDownSample (down_sample.cu:275-316): points 0, k, 2k, ... (n // k of them)."""
@@ -512,21 +487,15 @@ class Engine:
             Eptr = None
         count = (w // int(stride)) * (h // int(stride)) if stride >= 1 else 0
         kind = MI_ICP_DEVICE if on_dev else MI_ICP_HOST
-        if on_dev:
-            mk = lambda want: torch.empty((count, 3), dtype=torch.float32, device=d.device) if want else None
-            ptr = lambda t_: None if t_ is None else C.c_void_p(t_.data_ptr())
-        else:
-            mk = lambda want: np.empty((count, 3), np.float32) if want else None
-            ptr = lambda t_: None if t_ is None else t_.ctypes.data_as(C.c_void_p)
-        op, on, oc = mk(True), mk(bool(compute_normals)), mk(col is not None)
+        out = lambda want: self._out(kind, d.device if on_dev else None, (count, 3)) if want else (None, None)
+        (op, pp), (on, pn), (oc, pc) = out(True), out(compute_normals), out(col is not None)
         m = C.c_int64(0)
         self._chk(self._L.mi_icp_create_from_depth(
             self._ctx, dptr, 1 if dname == "uint16" else 0, cptr, ctype, w, h, K, Eptr,
             float(depth_scale), float(depth_trunc), float(depth_cutoff), int(stride), int(bool(rgbd)),
-            int(bool(compute_normals)), int(bool(valid_only)), ptr(op), ptr(on), ptr(oc), C.byref(m), kind))
+            int(bool(compute_normals)), int(bool(valid_only)), pp, pn, pc, C.byref(m), kind))
         k = int(m.value)
-        cut = lambda t_: None if t_ is None else t_[:k]
-        return cut(op), cut(on), cut(oc)
+        return self._trim(op, k), self._trim(on, k), self._trim(oc, k)
 
     def compute_rgbd_odometry(self, source_color, source_depth, target_color, target_depth, intrinsic4,
                               odo_init=None, jacobian=1, iterations=(20, 10, 5), max_depth_diff=0.03,
@@ -587,35 +556,20 @@ class Engine:
 
     def covariances_from_normals(self, normals, epsilon=1e-3):
         n = _Buf(normals, np.float32, 3, self.device)
-        if n.kind == MI_ICP_DEVICE:
-            out = torch.empty((n.n, 9), dtype=torch.float32, device=n.keep.device)
-            optr = C.c_void_p(out.data_ptr())
-        else:
-            out = np.empty((n.n, 9), np.float32)
-            optr = out.ctypes.data_as(C.c_void_p)
+        out, optr = self._out(n.kind, n.device, (n.n, 9))
         self._chk(self._L.mi_icp_covariances_from_normals(self._ctx, n.ptr, n.n, float(epsilon),
                                                           optr, n.kind))
         return _cov_out(out)
 
     def estimate_normals_knn(self, points, knn=30):
         p = _Buf(points, np.float32, 3, self.device)
-        if p.kind == MI_ICP_DEVICE:
-            out = torch.empty((p.n, 3), dtype=torch.float32, device=p.keep.device)
-            optr = C.c_void_p(out.data_ptr())
-        else:
-            out = np.empty((p.n, 3), np.float32)
-            optr = out.ctypes.data_as(C.c_void_p)
+        out, optr = self._out(p.kind, p.device, (p.n, 3))
         self._chk(self._L.mi_icp_estimate_normals_knn(self._ctx, p.ptr, p.n, int(knn), optr, p.kind))
         return out
 
     def estimate_normals_radius(self, points, radius, max_nn=30):
         p = _Buf(points, np.float32, 3, self.device)
-        if p.kind == MI_ICP_DEVICE:
-            out = torch.empty((p.n, 3), dtype=torch.float32, device=p.keep.device)
-            optr = C.c_void_p(out.data_ptr())
-        else:
-            out = np.empty((p.n, 3), np.float32)
-            optr = out.ctypes.data_as(C.c_void_p)
+        out, optr = self._out(p.kind, p.device, (p.n, 3))
         self._chk(self._L.mi_icp_estimate_normals_radius(self._ctx, p.ptr, p.n, float(radius),
                                                          int(max_nn), optr, p.kind))
         return out

@@ -21,7 +21,8 @@
  *     device_vector<Eigen::Vector2i> (registration/transformation_estimation.h:36).
  *   - every buffer argument carries a mem_kind: MI_ICP_HOST (pageable or
  *     pinned host memory, copied by the engine) or MI_ICP_DEVICE (a HIP device
- *     pointer on the context's GPU, read in place).  The caller owns all
+ *     pointer on the context's GPU, read in place).  Any other value returns
+ *     MI_ICP_ERR_INVALID before any buffer is read or written.  The caller owns all
  *     buffers it passes; the context owns its internal SoA copies, LBVH and
  *     scratch arena.
  *   - one context per GPU; a context is not thread-safe, independent contexts

@@ -276,3 +276,89 @@ def test_list_build_in_flight_survives_retargeting_knn_and_destroy():
         assert got.fitness == ref.fitness and got.inlier_rmse == ref.inlier_rmse
     eng.set_target(d["tgt"], d["tgt_nrm"])
     eng.close()                                                                      # destroyed with the build in flight
+
+
+# every entry point of include/mi_icp.h that takes a mem_kind: (name, its arguments after the context given the device
+# buffers `b` and the bad kind `k`).  Host-side scalars and small host arrays (transforms, intrinsics, results) stay host.
+def _kind_calls():
+    import ctypes as C
+    from cupoch_amd._lib import OdometryOption
+    P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    m, cnt = C.c_int64(7), C.c_int64(7)
+    K4 = (C.c_float * 4)(100.0, 100.0, 8.0, 8.0)
+    opt = OdometryOption()
+    opt.num_levels, opt.iterations[0], opt.max_depth = 1, 5, 4.0
+    ok = C.c_int(7)
+    T16, tw6, info36 = np.full(16, 7, np.float32), np.full(6, 7, np.float32), np.full(36, 7, np.float64)
+    hp = lambda a: a.ctypes.data_as(C.c_void_p)
+    n = 256
+    cloud = lambda b: (P(b["xyz"]), P(b["nrm"]), P(b["col"]), n)
+    outs = lambda b: (P(b["oxyz"]), P(b["onrm"]), P(b["ocol"]))
+    imgs = lambda b: (P(b["img"][0]), P(b["img"][1]), P(b["img"][2]), P(b["img"][3]), 16, 16, K4, None)
+    return [
+        ("set_target", lambda b, k: (P(b["xyz"]), P(b["nrm"]), P(b["cov"]), n, k)),
+        ("set_source", lambda b, k: (P(b["xyz"]), P(b["nrm"]), P(b["cov"]), n, k)),
+        ("search_radius_1nn", lambda b, k: (None, 0.1, P(b["i32"]), P(b["f32"]), k, None)),
+        ("get_correspondences", lambda b, k: (P(b["pairs"]), n, C.byref(cnt), k)),
+        ("set_correspondences", lambda b, k: (P(b["pairs"]), n, k)),
+        ("transform", lambda b, k: (None, P(b["xyz"]), P(b["nrm"]), P(b["cov"]), n, k)),
+        ("compute_bounds", lambda b, k: (P(b["xyz"]), n, k, None, None, None)),
+        ("affine", lambda b, k: (None, 2.0, 1, None, None, P(b["xyz"]), P(b["nrm"]), P(b["cov"]), n, k)),
+        ("voxel_downsample", lambda b, k: cloud(b) + (0.05,) + outs(b) + (C.byref(m), k)),
+        ("select_by_index", lambda b, k: cloud(b) + (P(b["i64"]), n, 0) + outs(b) + (C.byref(m), k)),
+        ("uniform_downsample", lambda b, k: cloud(b) + (2,) + outs(b) + (C.byref(m), k)),
+        ("remove_statistical_outliers", lambda b, k: cloud(b) + (8, 2.0) + outs(b) + (P(b["i64"]), P(b["f32"]), C.byref(m), k)),
+        ("remove_radius_outliers", lambda b, k: cloud(b) + (4, 0.1) + outs(b) + (P(b["i64"]), P(b["i32"]), C.byref(m), k)),
+        ("cluster_dbscan", lambda b, k: (P(b["xyz"]), n, 0.1, 4, 16, P(b["i32"]), P(b["i32b"]), C.byref(cnt), k)),
+        ("create_from_depth", lambda b, k: (P(b["img"][1]), 0, None, 0, 16, 16, K4, None, 1000.0, 1000.0, -1.0, 1, 0, 0, 1,
+                                            P(b["oxyz"]), None, None, C.byref(m), k)),
+        ("compute_rgbd_odometry", lambda b, k: imgs(b) + (1, C.byref(opt), C.byref(ok), hp(T16), hp(info36), k)),
+        ("compute_weighted_rgbd_odometry", lambda b, k: imgs(b) + (None, C.byref(opt), C.byref(ok), hp(T16), hp(tw6),
+                                                                   hp(info36), k)),
+        ("covariances_from_normals", lambda b, k: (P(b["nrm"]), n, 1e-3, P(b["cov"]), k)),
+        ("estimate_normals_knn", lambda b, k: (P(b["xyz"]), n, 8, P(b["onrm"]), k)),
+        ("estimate_normals_radius", lambda b, k: (P(b["xyz"]), n, 0.1, 8, P(b["onrm"]), k)),
+        ("search_knn", lambda b, k: (P(b["xyz"]), n, 1, 0.0, P(b["i32"]), P(b["f32"]), C.byref(cnt), k)),
+        ("set_target_colors", lambda b, k: (P(b["col"]), k)),
+        ("set_source_colors", lambda b, k: (P(b["col"]), k)),
+        ("compute_color_gradients", lambda b, k: (0.1, 8, P(b["ocol"]), k)),
+        ("spatial_order", lambda b, k: (P(b["xyz"]), n, P(b["i32"]), k)),
+    ], (T16, tw6, info36)
+
+
+@pytest.mark.parametrize("name", [c[0] for c in _kind_calls()[0]])
+def test_bad_mem_kind_is_refused_before_any_buffer(eng, name):
+    """A mem_kind other than MI_ICP_HOST / MI_ICP_DEVICE returns MI_ICP_ERR_INVALID before any buffer is read or
+    written (include/mi_icp.h).  Every buffer is a device tensor, so no host address could reach a kernel."""
+    calls, host_outs = _kind_calls()
+    args = dict(calls)[name]
+    rng = np.random.default_rng(5)
+    pts = torch.from_numpy(rng.random((256, 3), dtype=np.float32)).cuda()
+    eng.set_target(pts, torch.nn.functional.normalize(pts - 0.5, dim=1))
+    eng.set_source(pts)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    b = dict(xyz=pts.clone(), nrm=torch.nn.functional.normalize(pts - 0.5, dim=1), col=pts.clone(),
+             cov=dev(np.tile(np.eye(3, dtype=np.float32).reshape(1, 9), (256, 1))),
+             pairs=dev(np.stack([np.arange(256), np.arange(256)], 1).astype(np.int32)),
+             img=[dev(rng.random((16, 16), dtype=np.float32) + 0.5) for _ in range(4)],
+             i64=dev(np.arange(256, dtype=np.int64)),
+             oxyz=dev(np.full((256, 3), 7, np.float32)), onrm=dev(np.full((256, 3), 7, np.float32)),
+             ocol=dev(np.full((256, 3), 7, np.float32)), f32=dev(np.full((256, 4), 7, np.float32)),
+             i32=dev(np.full((256, 4), -7, np.int32)), i32b=dev(np.full(256, -7, np.int32)))
+    flat = [t for v in b.values() for t in (v if isinstance(v, list) else [v])]
+    before = [t.clone() for t in flat]
+    host_before = [a.copy() for a in host_outs]
+    torch.cuda.synchronize()
+    rc = getattr(eng._L, "mi_icp_" + name)(eng._ctx, *args(b, 2))
+    torch.cuda.synchronize()
+    assert rc == -1                                                         # MI_ICP_ERR_INVALID
+    assert b"bad mem_kind" in eng._L.mi_icp_last_error(eng._ctx)
+    for t, t0 in zip(flat, before):
+        assert torch.equal(t, t0)
+    for a, a0 in zip(host_outs, host_before):
+        np.testing.assert_array_equal(a, a0)
+    # the context still serves a valid call
+    eng.set_target(pts)
+    found, idx, d2 = eng.search_knn(pts, 1)
+    assert found == 256
+    assert torch.equal(idx[:, 0].cpu(), torch.arange(256, dtype=torch.int32)) and bool((d2 == 0).all())
