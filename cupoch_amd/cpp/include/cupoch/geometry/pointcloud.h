@@ -162,6 +162,12 @@ public:
     /// max_edges <= knn::NUM_MAX_NN.  print_progress is accepted and prints nothing.
     std::unique_ptr<utility::device_vector<int>> ClusterDBSCAN(float eps, size_t min_points, bool print_progress = false,
                                                                size_t max_edges = knn::NUM_MAX_NN) const;
+    /// segmentation.cu:187-268: RANSAC over planes through three points, the best one refit to its inliers (the
+    /// contract: include/mi_icp.h).  Returns (a, b, c, d) of a x + b y + c z + d = 0 and the inliers' indices, ascending.
+    /// The seed is taken from rand(), as the reference takes its seeds: std::srand governs the result.
+    std::tuple<Eigen::Vector4f, utility::device_vector<size_t>> SegmentPlane(float distance_threshold = 0.01,
+                                                                             size_t ransac_n = 3,
+                                                                             size_t num_iterations = 100) const;
     /// estimate_normals.cu:82-127 (KNN or radius search parameter; up to knn::NUM_MAX_NN neighbours)
     bool EstimateNormals(const knn::KDTreeSearchParam& search_param = knn::KDTreeSearchParamKNN());
 

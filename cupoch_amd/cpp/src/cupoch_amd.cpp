@@ -280,6 +280,30 @@ std::unique_ptr<utility::device_vector<int>> PointCloud::ClusterDBSCAN(float eps
     return labels;
 }
 
+std::tuple<Eigen::Vector4f, utility::device_vector<size_t>> PointCloud::SegmentPlane(float distance_threshold, size_t ransac_n,
+                                                                                      size_t num_iterations) const {
+    Eigen::Vector4f plane;
+    for (int k = 0; k < 4; ++k) plane(k) = 0.0f;
+    utility::device_vector<size_t> inliers;
+    const size_t n = points_.size();
+    if (ransac_n < 3) {  // segmentation.cu:204-212
+        LogError("ransac_n should be set to higher than or equal to 3.");
+        return std::make_tuple(plane, std::move(inliers));
+    }
+    if (n < ransac_n) {
+        LogError("There must be at least 'ransac_n' points.");
+        return std::make_tuple(plane, std::move(inliers));
+    }
+    inliers.resize(n);
+    int64_t m = 0;
+    const uint64_t seed = (uint64_t)std::rand();
+    Check(mi_icp_segment_plane(Engine(), Ptr(points_), (int64_t)n, distance_threshold, (int64_t)ransac_n,
+                               (int64_t)std::min<size_t>(num_iterations, (size_t)1 << 40), seed, plane.data(), nullptr,
+                               (int64_t*)inliers.data(), &m, nullptr, nullptr, MI_ICP_DEVICE));
+    inliers.resize((size_t)m);
+    return std::make_tuple(plane, std::move(inliers));
+}
+
 bool PointCloud::EstimateNormals(const knn::KDTreeSearchParam& search_param) {
     normals_.resize(points_.size());
     if (points_.empty()) return true;

@@ -448,6 +448,18 @@ PYBIND11_MODULE(cupoch_pybind, m) {
                         return labels;
                     },
                     "eps"_a, "min_points"_a, "print_progress"_a = false, "max_edges"_a = knn::NUM_MAX_NN)
+            .def(
+                    "segment_plane",
+                    [](const geometry::PointCloud& pc, float distance_threshold, size_t ransac_n, size_t num_iterations) {
+                        auto res = pc.SegmentPlane(distance_threshold, ransac_n, num_iterations);
+                        ULongVector idx;
+                        idx.data = std::move(std::get<1>(res));
+                        const Eigen::Vector4f& v = std::get<0>(res);
+                        py::array_t<float> plane(4);
+                        for (int k = 0; k < 4; ++k) plane.mutable_at(k) = v(k);
+                        return std::make_tuple(plane, idx);
+                    },
+                    "distance_threshold"_a = 0.01f, "ransac_n"_a = 3, "num_iterations"_a = 100)
             .def("estimate_normals", &geometry::PointCloud::EstimateNormals,
                  "search_param"_a = knn::KDTreeSearchParamKNN())
             .def("__len__", [](const geometry::PointCloud& pc) { return pc.points_.size(); });

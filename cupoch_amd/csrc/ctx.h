@@ -3,7 +3,7 @@
 //   mi_icp.hip       context life cycle, the correspondence search, the reduction, the device-resident loop
 //   mi_build.hip     target tree (kd cells, groups, levels, halos), source staging, the match-order re-sort
 //   mi_geometry.hip  Transform / bounds / affine / covariances / VoxelDownSample / SelectByIndex / UniformDownSample /
-//                    depth frames / RGB-D odometry / colours
+//                    SegmentPlane / depth frames / RGB-D odometry / colours
 //   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry,
 //                    RemoveStatisticalOutliers / RemoveRadiusOutliers, ClusterDBSCAN
 //   mi_comm.hip      the ranks' exchange: mailbox, device inboxes, in-library RCCL, self-test and choice
@@ -104,6 +104,7 @@ struct mi_icp_ctx {
     mi::eng::DevBuf tscale;   // scratch of kd_build.h tree_scale
     mi::eng::DevBuf knn_idx, knn_flags;  // the k-NN lists' index rows, [XCD][row][slot][lane], and the rows' claim flags (knn_normals.h KnnSlab)
     mi::eng::DevBuf dbs[4];   // ClusterDBSCAN (dbscan.h): the rows, the per-point words, the one-way masks, the state
+    mi::eng::DevBuf seg[4];   // SegmentPlane (segment_plane.h): the planes, the per-hypothesis words and the state, the tie sums, the refit's sums
     float vx_refused_voxel = 0.0f;  // the last voxel size / cloud size the dense path's plan turned away (mi_icp_voxel_downsample)
     int64_t vx_refused_n = 0;
     int vx_order = 0;         // LDS adds of one instruction served in lane order (voxel_dense.h)?  0: not checked yet, 1: yes, -1: no
@@ -336,6 +337,22 @@ inline int check_ctx(mi_icp_ctx* c) {
 inline int check_ctx(mi_icp_ctx* c, int mem_kind, const char* what) {
     TRY(check_ctx(c));
     if (mem_kind != MI_ICP_HOST && mem_kind != MI_ICP_DEVICE) return fail(c, MI_ICP_ERR_INVALID, "%s: bad mem_kind", what);
+    return MI_ICP_OK;
+}
+
+// Runs body(a) in the private scratch context a = c->aux (made on first use, on c's stream): a registration in flight
+// on c (user estimators may call EstimateNormals between iterations) keeps its target, source, correspondences and
+// loop state.  A failure is reported on c as "what: <a's error>".
+template <class Body>
+int in_scratch(mi_icp_ctx* c, const char* what, Body body) {
+    if (!c->aux) {
+        const int rc = mi_icp_create(c->device, &c->aux);
+        if (rc != MI_ICP_OK) return fail(c, rc, "%s: cannot create the scratch context", what);
+    }
+    mi_icp_ctx* a = c->aux;
+    a->stream = c->stream;
+    const int rc = body(a);
+    if (rc != MI_ICP_OK) return fail(c, rc, "%s: %s", what, a->err.c_str());
     return MI_ICP_OK;
 }
 

@@ -1,6 +1,6 @@
 // mi_geometry.hip -- the geometry entry points beside the registration: Transform, bounds / centre, Translate / Scale /
 // Rotate, GICP covariances, VoxelDownSample, depth / RGB-D frame -> cloud, RGB-D odometry, colours
-// SelectByIndex / UniformDownSample, and the compaction behind them and the outlier filters
+// SelectByIndex / UniformDownSample, and the compaction behind them and the outlier filters; SegmentPlane
 // (one translation unit of libmi_icp.so; csrc/ctx.h lists them)
 #include "ctx.h"
 #include "depth_kernels.h"
@@ -8,6 +8,7 @@
 #include "lbvh.h"
 #include "odometry.h"
 #include "reduce.h"
+#include "segment_plane.h"
 #include "select.h"
 #include "voxel_dense.h"
 
@@ -628,6 +629,90 @@ int mi_icp_uniform_downsample(mi_icp_ctx* c, const float* xyz, const float* norm
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *m = cnt;
     return MI_ICP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// PointCloud::SegmentPlane (geometry/segmentation.cu:187-268; segment_plane.h): every hypothesis drawn up front and
+// scored in one pass over the points, the winner chosen on the device, its inlier list and the refit behind it.  Runs
+// in the private scratch context; the state, the count and the list come back with the one wait at the end.
+int mi_icp_segment_plane(mi_icp_ctx* c, const float* xyz, int64_t n, float distance_threshold, int64_t ransac_n,
+                         int64_t num_iterations, uint64_t seed, float* plane4, float* ransac_plane4, int64_t* inliers,
+                         int64_t* m, int64_t* best_iteration, int64_t* best_count, int mem_kind) {
+    const char* what = "segment_plane";
+    TRY(check_ctx(c, mem_kind, what));
+    if (!plane4 || !m) return fail(c, MI_ICP_ERR_INVALID, "%s: plane4 or m is null", what);
+    for (int k = 0; k < 4; ++k) {
+        plane4[k] = 0.0f;
+        if (ransac_plane4) ransac_plane4[k] = 0.0f;
+    }
+    *m = 0;
+    if (best_iteration) *best_iteration = -1;
+    if (best_count) *best_count = 0;
+    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    if (num_iterations > kSegMaxIterations)
+        return fail(c, MI_ICP_ERR_INVALID, "%s: more than %lld iterations are not supported", what, (long long)kSegMaxIterations);
+    if (ransac_n < 3 || n < ransac_n) return MI_ICP_OK;  // segmentation.cu:204-212: the zero plane, no inliers
+    if (!xyz || !inliers) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+    const int H = (int)std::max<int64_t>(num_iterations, 0);
+    const float thr = distance_threshold;
+    return in_scratch(c, what, [&](mi_icp_ctx* a) -> int {
+        const float* pts;
+        TRY(to_device(a, xyz, (size_t)n * 3, mem_kind, a->stage[0], &pts));
+        float4* plane;
+        uint32_t *words, *flags, *pos, *tmp;
+        double *tie, *sums;
+        int64_t* didx;
+        const size_t hw = (size_t)std::max(H, 1);
+        TRY(ensure(a, a->seg[0], hw, &plane));
+        TRY(ensure(a, a->seg[1], 3 * hw + sizeof(SegState) / sizeof(uint32_t), &words));
+        TRY(ensure(a, a->seg[2], hw * kSegTieBlocks, &tie));
+        TRY(ensure(a, a->seg[3], (size_t)kSegRefitBlocks * 8 + 4, &sums));
+        TRY(ensure(a, a->flags, (size_t)n, &flags));
+        TRY(ensure(a, a->dense_idx, (size_t)n, &pos));
+        TRY(ensure(a, a->scan_tmp, (size_t)scan_num_tiles(n) + 2, &tmp));
+        TRY(out_slot(a, inliers, (size_t)n, mem_kind, a->pairs_out, &didx));
+        uint32_t *valid = words, *count = words + hw;
+        int32_t* tied_list = (int32_t*)(words + 2 * hw);
+        SegState* st = (SegState*)(words + 3 * hw);
+        double* centroid = sums + (size_t)kSegRefitBlocks * 8;
+        hipStream_t s = a->stream;
+        HIPCHK(a, hipMemsetAsync(count, 0, hw * sizeof(uint32_t), s));
+        if (H > 0) {
+            seg_hypotheses<<<blocks_for(H), 256, 0, s>>>(pts, n, seed, H, plane, valid);
+            const int grid = (int)std::min<int64_t>((n + kSegChunk - 1) / kSegChunk, kSegMaxBlocks);
+            seg_score<<<grid, 256, 0, s>>>(pts, n, plane, H, thr, count);
+        }
+        seg_select<<<1, 64, 0, s>>>(count, valid, H, st, tied_list);
+        if (H > 1) seg_tie_partial<<<dim3(kSegTieBlocks, std::min(H, 32)), 256, 0, s>>>(pts, n, plane, thr, st, tied_list, tie);
+        seg_pick<<<1, 64, 0, s>>>(plane, tied_list, tie, st);
+        const int nb = blocks_for(n), rb = std::min(kSegRefitBlocks, nb);
+        seg_flags<<<nb, 256, 0, s>>>(pts, n, st, thr, flags);
+        exclusive_scan_u32(s, flags, pos, n, tmp);
+        seg_list<<<nb, 256, 0, s>>>(flags, pos, n, didx);
+        seg_centroid_partial<<<rb, 256, 0, s>>>(pts, flags, n, sums);
+        seg_centroid_final<<<1, 64, 0, s>>>(sums, rb, centroid);
+        seg_moments_partial<<<rb, 256, 0, s>>>(pts, flags, n, centroid, sums);
+        seg_refit_final<<<1, 64, 0, s>>>(sums, rb, centroid, st);
+        KCHK(a);
+        constexpr int kStateWords = (int)(sizeof(SegState) / sizeof(uint32_t));
+        static_assert(kStateWords + 1 <= 16, "the state and the count share the 16 pinned words");
+        HIPCHK(a, hipMemcpyAsync(a->u_host, st, sizeof(SegState), hipMemcpyDeviceToHost, s));
+        HIPCHK(a, hipMemcpyAsync(a->u_host + kStateWords, tmp + scan_num_tiles(n), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(a, hipStreamSynchronize(s));
+        SegState h;
+        std::memcpy(&h, a->u_host, sizeof(h));
+        const int64_t cnt = (int64_t)a->u_host[kStateWords];
+        if (didx != inliers) {  // staged: a second wait, for the copy to the caller
+            TRY(from_device(a, (const int64_t*)didx, inliers, (size_t)cnt, mem_kind));
+            HIPCHK(a, hipStreamSynchronize(s));
+        }
+        std::memcpy(plane4, h.refit, sizeof(h.refit));
+        if (ransac_plane4) std::memcpy(ransac_plane4, h.ransac, sizeof(h.ransac));
+        *m = cnt;
+        if (best_iteration) *best_iteration = h.best;
+        if (best_count) *best_count = (int64_t)h.best_count;
+        return MI_ICP_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------

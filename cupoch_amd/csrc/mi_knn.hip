@@ -63,22 +63,6 @@ int launch_knn_normals(mi_icp_ctx* c, int k, float r2, float* out, const float4*
                       c->nleaf, k, r2, out, tnrm, tgrad);
 }
 
-// Runs body(a) in the private scratch context a = c->aux (made on first use, on c's stream): a registration in flight
-// on c (user estimators may call EstimateNormals between iterations) keeps its target, source, correspondences and
-// loop state.  A failure is reported on c as "what: <a's error>".
-template <class Body>
-int in_scratch(mi_icp_ctx* c, const char* what, Body body) {
-    if (!c->aux) {
-        const int rc = mi_icp_create(c->device, &c->aux);
-        if (rc != MI_ICP_OK) return fail(c, rc, "%s: cannot create the scratch context", what);
-    }
-    mi_icp_ctx* a = c->aux;
-    a->stream = c->stream;
-    const int rc = body(a);
-    if (rc != MI_ICP_OK) return fail(c, rc, "%s: %s", what, a->err.c_str());
-    return MI_ICP_OK;
-}
-
 }  // namespace
 
 extern "C" {

@@ -346,7 +346,8 @@ class Engine:
         self.synchronize()
         return p.keep, n.keep, _cov_out(c.keep)
 
-    # -- PointCloud::VoxelDownSample / SelectByIndex / UniformDownSample / Remove*Outliers (down_sample.cu) --------
+    # -- PointCloud::VoxelDownSample / SelectByIndex / UniformDownSample / Remove*Outliers (down_sample.cu), ------
+    # -- ClusterDBSCAN, SegmentPlane
     def _cloud_args(self, points, normals, colors):
         p = _Buf(points, np.float32, 3, self.device)
         n = _Buf(normals, np.float32, 3, self.device)
@@ -402,6 +403,21 @@ class Engine:
         self._chk(self._L.mi_icp_cluster_dbscan(self._ctx, p.ptr, p.n, float(eps), int(min_points), int(max_edges),
                                                 plab, pdeg, C.byref(nc), kind))
         return labels, degrees, int(nc.value)
+
+    def segment_plane(self, points, distance_threshold, ransac_n=3, num_iterations=100, seed=0):
+        """PointCloud::SegmentPlane (segmentation.cu:187-268; the contract is in include/mi_icp.h).  Returns
+        (plane float32[4] refit to the inliers, inlier indices int64 ascending on the side of `points`, the winning
+        RANSAC plane float32[4], the winner's iteration or -1, its inlier count)."""
+        p = _Buf(points, np.float32, 3, self.device)
+        kind = self._same_kind(p)
+        idx, pidx = self._out(kind, p.device, (p.n,), np.int64)
+        plane, ransac = np.zeros(4, np.float32), np.zeros(4, np.float32)
+        m, best, count = C.c_int64(0), C.c_int64(-1), C.c_int64(0)
+        self._chk(self._L.mi_icp_segment_plane(self._ctx, p.ptr, p.n, float(distance_threshold), int(ransac_n),
+                                               int(num_iterations), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                               plane.ctypes.data_as(C.c_void_p), ransac.ctypes.data_as(C.c_void_p), pidx,
+                                               C.byref(m), C.byref(best), C.byref(count), kind))
+        return plane, idx[:int(m.value)], ransac, int(best.value), int(count.value)
 
     def select_by_index(self, points, indices, invert=False, normals=None, colors=None):
         """PointCloud::SelectByIndex (down_sample.cu:40-62,110-129).  indices: anything 1-D integer (a tensor on

@@ -312,6 +312,19 @@ class PointCloud:
         labels, _, _ = eng.cluster_dbscan(self._points.tensor, float(eps), int(min_points), int(max_edges))
         return utility.IntVector(labels)
 
+    # PointCloud::SegmentPlane (segmentation.cu:187-268) -------------------------------------------------------------
+    def segment_plane(self, distance_threshold=0.01, ransac_n=3, num_iterations=100, seed=None):
+        """(plane_model float32[4], ULongVector of the inliers' indices): RANSAC over planes through three points, the
+        winner refit to its inliers (include/mi_icp.h states the contract).  seed=None draws one from Python's
+        `random` module, as the reference draws from rand(); the same seed gives the same result."""
+        if seed is None:
+            import random
+            seed = random.getrandbits(64)
+        eng = get_engine(self._points.tensor.device.index)
+        plane, idx, _, _, _ = eng.segment_plane(self._points.tensor, float(distance_threshold), int(ransac_n),
+                                                int(num_iterations), int(seed))
+        return plane, utility.ULongVector(idx.clone())
+
     # PointCloud::EstimateNormals (estimate_normals.cu:82-127): KNN or Radius search parameter ----------
     def estimate_normals(self, search_param=None):
         eng = get_engine(self._points.tensor.device.index)

@@ -440,6 +440,68 @@ MI_ICP_API int mi_icp_cluster_dbscan(mi_icp_ctx* ctx, const float* xyz, int64_t 
                                      int64_t min_points, int max_edges, int32_t* labels,
                                      int32_t* degrees, int64_t* n_clusters, int mem_kind);
 
+/* PointCloud::SegmentPlane(distance_threshold, ransac_n, num_iterations) (geometry/segmentation.cu:
+ * 187-268): RANSAC over planes through three points.  All hypotheses are drawn up front and scored
+ * in one pass over the points; the contract, which the outputs meet exactly (the refit apart):
+ *   sampler   u(j), j = 0, 1, ...: output j of splitmix64 seeded with `seed`, all in uint64:
+ *               z = seed + (j + 1) * 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *               z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  u = z ^ (z >> 31).
+ *             below(u, k) = floor(u * k / 2^64) (the high word of the 128-bit product).
+ *   triple    iteration t = 0 .. num_iterations - 1 draws  i0 = below(u(3t), n);
+ *               i1 = below(u(3t + 1), n - 1), plus 1 if i1 >= i0;
+ *               i2 = below(u(3t + 2), n - 2), plus 1 if i2 >= min(i0, i1), then plus 1 if
+ *               i2 >= max(i0, i1)  (the comparisons use the updated values).
+ *             Three distinct indices, a pure function of (seed, t, n): the head of a uniform
+ *             permutation, as the reference's three are.
+ *   plane     ComputeTrianglePlane (segmentation.cu:60-74) of p0 = xyz[i0], p1, p2 in fp32, every
+ *             operation rounded, none fused:  e0 = p1 - p0, e1 = p2 - p0,
+ *               a = e0y*e1z - e0z*e1y,  b = e0z*e1x - e0x*e1z,  c = e0x*e1y - e0y*e1x,
+ *               norm = sqrt((a*a + b*b) + c*c);  the hypothesis is VALID iff 0 < norm < inf; then
+ *               (a, b, c) /= norm (IEEE division),  d = -((a*x0 + b*y0) + c*z0).
+ *   distance  dist(p) = |fma(c, z, fma(b, y, fma(a, x, d)))| in fp32: three fused multiply-adds, d
+ *             first.  p is an INLIER iff dist(p) < distance_threshold, strictly (a NaN never is).
+ *             The scoring pass and the pass that lists the inliers evaluate this one expression.
+ *   winner    count(t) = the inliers of hypothesis t, an integer.  Among the valid hypotheses
+ *             with count >= 1: the largest count; among equal counts the smallest error sum, the
+ *             fp64 sum of the inliers' fp32 distances in a fixed order (per thread, wave, block,
+ *             then the blocks in order -- computed only when counts tie); among equal sums the
+ *             lowest t.  (At equal count the reference's inlier_rmse_ = sum / sqrt(count) orders
+ *             as the sum does, and it keeps the first of equals, segmentation.cu:237-242.)
+ *   none      no valid hypothesis with an inlier (all triples collinear, num_iterations <= 0,
+ *             threshold <= 0 or NaN): the best plane stays (0, 0, 0, 0) as in the reference, every
+ *             finite point's distance is 0, so every such point is an inlier when
+ *             distance_threshold > 0 and none otherwise.  *best_iteration = -1, *best_count = 0.
+ *   outputs   inliers (int64[n] on the side mem_kind names): the *m indices of the winning RANSAC
+ *             plane's inliers, ascending.  ransac_plane4 (host float[4] or NULL): that plane.
+ *             plane4 (host float[4]): GetPlaneFromPoints of those inliers (segmentation.cu:135-185):
+ *             centroid; the six centred second moments xx xy xz yy yz zz; det_x = yy*zz - yz*yz,
+ *             det_y = xx*zz - xz*xz, det_z = xx*yy - xy*xy; the branch of the strictly largest
+ *             (x before y before z, as written there) gives abc; abc /= |abc|; d = -abc . centroid;
+ *             no inliers or a zero norm: the zero plane.  All sums (fixed order: per block, then
+ *             the blocks in order), the centring, determinants and the normalisation in fp64,
+ *             rounded to fp32 once.  *best_iteration / *best_count (host, may be NULL): the
+ *             winner's t and count(t).
+ *   arguments ransac_n < 3 or n < ransac_n: MI_ICP_OK with the zero planes and *m = 0 (the reference
+ *             logs an error and returns exactly that).  ransac_n > 3 still samples three points,
+ *             as in the reference.
+ * Deviations (deliberate): the random stream is not the reference's (rand() seeding
+ * thrust::default_random_engine, then a sort of n keys per iteration): same distribution of triples,
+ * other triples.  Counts are compared as integers (the reference compares (float)count / (float)n,
+ * which ties distinct counts once n exceeds 2^24).  The distance is the fma chain above (the
+ * reference: Eigen's 4-vector dot in fp32, order unspecified).  The refit is fp64 (the reference sums
+ * in fp32 in thrust's order and is not reproducible bit for bit even by itself).
+ * Limits: n < 2^31, num_iterations <= 65536; else MI_ICP_ERR_INVALID.  Integers apart from the refit,
+ * whose sums have a fixed order: every run and every context gives the same bytes.  Runs in the
+ * private scratch context, as the outlier filters do: the caller's target / source / loop state
+ * survive.  The number of kernel launches does not depend on num_iterations, the points are read
+ * once for scoring per 2048 hypotheses, once for the flags, twice for the refit (and once per
+ * block row of the tie pass when counts tie).  Synchronises the context's stream once (twice with
+ * MI_ICP_HOST, for the copy of the list). */
+MI_ICP_API int mi_icp_segment_plane(mi_icp_ctx* ctx, const float* xyz, int64_t n, float distance_threshold,
+                                    int64_t ransac_n, int64_t num_iterations, uint64_t seed, float* plane4,
+                                    float* ransac_plane4, int64_t* inliers, int64_t* m,
+                                    int64_t* best_iteration, int64_t* best_count, int mem_kind);
+
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
  * float[nq][3] against the cloud given to mi_icp_set_target: per query the knn
