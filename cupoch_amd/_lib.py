@@ -157,11 +157,13 @@ SIGNATURES = {
     "mi_icp_affine": (_I, [_P, _P, _F, _I, _P, _P, _P, _P, _P, _L, _I]),
     "mi_icp_voxel_downsample": (_I, [_P, _P, _P, _P, _L, _F, _P, _P, _P, C.POINTER(_L), _I]),
     "mi_icp_select_by_index": (_I, [_P, _P, _P, _P, _L, _P, _L, _I, _P, _P, _P, C.POINTER(_L), _I]),
+    "mi_icp_select_by_mask": (_I, [_P, _P, _P, _P, _L, _P, _L, _I, _P, _P, _P, C.POINTER(_L), _I]),
     "mi_icp_uniform_downsample": (_I, [_P, _P, _P, _P, _L, _L, _P, _P, _P, C.POINTER(_L), _I]),
     "mi_icp_remove_statistical_outliers": (_I, [_P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P, C.POINTER(_L), _I]),
     "mi_icp_remove_radius_outliers": (_I, [_P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P, C.POINTER(_L), _I]),
     "mi_icp_cluster_dbscan": (_I, [_P, _P, _L, _F, _L, _I, _P, _P, C.POINTER(_L), _I]),
     "mi_icp_segment_plane": (_I, [_P, _P, _L, _F, _L, _L, C.c_uint64, _P, _P, _P, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), _I]),
+    "mi_icp_iss_keypoints": (_I, [_P, _P, _L, _F, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, C.POINTER(_L), _I]),
     "mi_icp_create_from_depth": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _F, _F, _F, _I, _I, _I, _I,
                                       _P, _P, _P, C.POINTER(_L), _I]),
     "mi_icp_compute_rgbd_odometry": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P, C.POINTER(_I), _P, _P, _I]),

@@ -148,6 +148,9 @@ public:
     /// down_sample.cu:40-62,110-129: a gather in the order given; invert: the points not named, ascending (a
     /// repeated index counts once).  An index outside [0, size) throws.
     std::shared_ptr<PointCloud> SelectByIndex(const utility::device_vector<size_t>& indices, bool invert = false) const;
+    /// down_sample.cu:131-168: the points whose mask entry is set (invert: not set), ascending.  A mask of another
+    /// size logs an error and gives an empty cloud, as in the reference.
+    std::shared_ptr<PointCloud> SelectByMask(const utility::device_vector<bool>& mask, bool invert = false) const;
     /// down_sample.cu:275-316: points 0, k, 2k, ... (size / k of them); every_k_points == 0 throws
     std::shared_ptr<PointCloud> UniformDownSample(size_t every_k_points) const;
     /// down_sample.cu:317-352: kept iff nb_points + 1 points (itself included) lie within search_radius;

@@ -222,6 +222,44 @@ std::shared_ptr<PointCloud> PointCloud::SelectByIndex(const utility::device_vect
     return out;
 }
 
+static_assert(sizeof(bool) == 1, "device_vector<bool> is handed to the engine as one byte per entry");
+
+std::shared_ptr<PointCloud> PointCloud::SelectByMask(const utility::device_vector<bool>& mask, bool invert) const {
+    const size_t n = points_.size();
+    if (n != mask.size()) {  // down_sample.cu:134-137
+        LogError("[SelectByMask] The point size should be equal to the mask size.");
+        return std::make_shared<PointCloud>();
+    }
+    auto out = SelectionOut(*this, n);
+    int64_t m = 0;
+    Check(mi_icp_select_by_mask(Engine(), Ptr(points_), HasNormals() ? Ptr(normals_) : nullptr,
+                                HasColors() ? Ptr(colors_) : nullptr, (int64_t)n, (const uint8_t*)mask.data(),
+                                (int64_t)mask.size(), invert ? 1 : 0, MutPtr(out->points_), MutPtr(out->normals_),
+                                MutPtr(out->colors_), &m, MI_ICP_DEVICE));
+    SelectionTrim(*out, m);
+    return out;
+}
+
+namespace keypoint {
+
+std::tuple<std::shared_ptr<PointCloud>, std::shared_ptr<utility::device_vector<bool>>> ComputeISSKeypoints(
+        const PointCloud& input, float salient_radius, float non_max_radius, float gamma_21, float gamma_32,
+        int min_neighbors, int max_neighbors) {
+    const size_t n = input.points_.size();
+    if (n == 0) {  // iss_keypoints.cu:117-120
+        LogWarning("[ComputeISSKeypoints] Input PointCloud is empty!");
+        return std::make_tuple(std::make_shared<PointCloud>(), std::make_shared<utility::device_vector<bool>>());
+    }
+    auto mask = std::make_shared<utility::device_vector<bool>>(n);
+    int64_t m = 0;
+    Check(mi_icp_iss_keypoints(Engine(), Ptr(input.points_), (int64_t)n, salient_radius, non_max_radius, gamma_21,
+                               gamma_32, min_neighbors, max_neighbors, (uint8_t*)mask->data(), nullptr, nullptr, nullptr,
+                               nullptr, &m, MI_ICP_DEVICE));
+    return std::make_tuple(input.SelectByMask(*mask), std::move(mask));
+}
+
+}  // namespace keypoint
+
 std::shared_ptr<PointCloud> PointCloud::UniformDownSample(size_t every_k_points) const {
     if (every_k_points == 0) throw std::runtime_error("[UniformDownSample] Illegal sample rate.");  // down_sample.cu:277-280
     const size_t n = points_.size();

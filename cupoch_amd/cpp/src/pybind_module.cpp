@@ -2,7 +2,7 @@
 // surface (namespace cupoch, libcupoch_amd.so) instead of the CUDA library.
 //
 // Same module layout, names, defaults and property names as src/python/cupoch_pybind of the reference:
-//   cupoch_pybind.utility       Vector3fVector, ULongVector, IntVector (device vector wrappers with .cpu()),
+//   cupoch_pybind.utility       Vector3fVector, ULongVector, IntVector, BoolVector (device vector wrappers with .cpu()),
 //                               initialize_allocator
 //                               (src/python/cupoch_pybind/utility/eigen.cpp:123-200, cupoch_pybind.cpp:46-49)
 //   cupoch_pybind.geometry      PointCloud, KDTreeSearchParamKNN / Radius, KDTreeFlann
@@ -26,6 +26,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "cupoch/geometry/keypoint.h"
 #include "cupoch/geometry/pointcloud.h"
 #include "cupoch/knn/kdtree_flann.h"
 #include "cupoch/knn/kdtree_search_param.h"
@@ -153,6 +154,23 @@ struct IntVector {
         const std::vector<int> h = data.to_host();
         py::array_t<int32_t> a((py::ssize_t)h.size());
         if (!h.empty()) std::memcpy(a.mutable_data(), (const void*)h.data(), h.size() * sizeof(int));
+        return a;
+    }
+};
+
+// utility.BoolVector: device_vector<bool> (the reference's device_vector_bool wrapper), the mask compute_iss_keypoints
+// returns and select_by_mask takes; .cpu() gives bool
+struct BoolVector {
+    utility::device_vector<bool> data;
+    BoolVector() = default;
+    explicit BoolVector(const py::array_t<bool, py::array::c_style | py::array::forcecast>& a) {
+        if (a.ndim() != 1) throw std::invalid_argument("expected a 1-D boolean array");
+        data.resize((size_t)a.shape(0));   // (std::vector<bool> is packed: the bytes go across as they are)
+        if (!data.empty()) utility::copy_h2d(data.data(), a.data(), data.size());
+    }
+    py::array_t<bool> cpu() const {
+        py::array_t<bool> a((py::ssize_t)data.size());
+        if (!data.empty()) utility::copy_d2h(a.mutable_data(), data.data(), data.size());
         return a;
     }
 };
@@ -341,6 +359,11 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             .def(py::init<const py::array_t<int32_t, py::array::c_style | py::array::forcecast>&>(), "array"_a)
             .def("cpu", &IntVector::cpu)
             .def("__len__", [](const IntVector& v) { return v.data.size(); });
+    py::class_<BoolVector>(mu, "BoolVector")
+            .def(py::init<>())
+            .def(py::init<const py::array_t<bool, py::array::c_style | py::array::forcecast>&>(), "array"_a)
+            .def("cpu", &BoolVector::cpu)
+            .def("__len__", [](const BoolVector& v) { return v.data.size(); });
     py::class_<Vector2iVector>(mu, "Vector2iVector")
             .def(py::init<>())
             .def(py::init<const py::array_t<int, py::array::c_style | py::array::forcecast>&>(), "array"_a)
@@ -420,6 +443,14 @@ PYBIND11_MODULE(cupoch_pybind, m) {
                                 invert);
                     },
                     "indices"_a, "invert"_a = false)
+            .def(
+                    "select_by_mask",
+                    [](const geometry::PointCloud& pc, const py::object& mask, bool invert) {
+                        if (py::isinstance<BoolVector>(mask)) return pc.SelectByMask(mask.cast<const BoolVector&>().data, invert);
+                        return pc.SelectByMask(
+                                BoolVector(mask.cast<py::array_t<bool, py::array::c_style | py::array::forcecast>>()).data, invert);
+                    },
+                    "mask"_a, "invert"_a = false)
             .def("uniform_down_sample", &geometry::PointCloud::UniformDownSample, "every_k_points"_a)
             .def(
                     "remove_radius_outlier",
@@ -463,6 +494,21 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             .def("estimate_normals", &geometry::PointCloud::EstimateNormals,
                  "search_param"_a = knn::KDTreeSearchParamKNN())
             .def("__len__", [](const geometry::PointCloud& pc) { return pc.points_.size(); });
+
+    // geometry.keypoint (geometry/keypoint.cpp; the reference spells the last keyword "max_neighbots")
+    py::module mk = mg.def_submodule("keypoint", "Keypoint Detectors.");
+    mk.def(
+            "compute_iss_keypoints",
+            [](const geometry::PointCloud& input, float salient_radius, float non_max_radius, float gamma_21, float gamma_32,
+               int min_neighbors, int max_neighbors) {
+                auto res = geometry::keypoint::ComputeISSKeypoints(input, salient_radius, non_max_radius, gamma_21, gamma_32,
+                                                                   min_neighbors, max_neighbors);
+                BoolVector mask;
+                mask.data = std::move(*std::get<1>(res));
+                return std::make_tuple(std::get<0>(res), mask);
+            },
+            "input"_a, "salient_radius"_a = 0.0f, "non_max_radius"_a = 0.0f, "gamma_21"_a = 0.975f, "gamma_32"_a = 0.975f,
+            "min_neighbors"_a = 5, "max_neighbors"_a = knn::NUM_MAX_NN);
 
     // ---------------------------------------------------------------- registration
     py::module mr = m.def_submodule("registration");

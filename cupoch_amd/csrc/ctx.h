@@ -2,10 +2,10 @@
 // allocation / staging helpers, and the declarations of the host-side functions one unit offers the others.
 //   mi_icp.hip       context life cycle, the correspondence search, the reduction, the device-resident loop
 //   mi_build.hip     target tree (kd cells, groups, levels, halos), source staging, the match-order re-sort
-//   mi_geometry.hip  Transform / bounds / affine / covariances / VoxelDownSample / SelectByIndex / UniformDownSample /
-//                    SegmentPlane / depth frames / RGB-D odometry / colours
+//   mi_geometry.hip  Transform / bounds / affine / covariances / VoxelDownSample / SelectByIndex / SelectByMask /
+//                    UniformDownSample / SegmentPlane / depth frames / RGB-D odometry / colours
 //   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry,
-//                    RemoveStatisticalOutliers / RemoveRadiusOutliers, ClusterDBSCAN
+//                    RemoveStatisticalOutliers / RemoveRadiusOutliers, ClusterDBSCAN, ComputeISSKeypoints
 //   mi_comm.hip      the ranks' exchange: mailbox, device inboxes, in-library RCCL, self-test and choice
 //   mi_debug.hip     include/mi_icp_debug.h (test-only entry points)
 // Kernels without template parameters are `static` in their headers, so a header may be included by several units.

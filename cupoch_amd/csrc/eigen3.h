@@ -156,6 +156,54 @@ __host__ __device__ __forceinline__ void fast_eigen3x3(const M3& A, float* eval,
     }
 }
 
+// FastEigen3x3Val (utility/eigenvalue.inl:164-170): the eigenvalues alone -- the closed form above without its
+// eigenvectors, every operation in the same order -- as the reference hands them out: (min, sum - min - max, max) with
+// sum = (eval0 + eval1) + eval2.  The scaling is FastEigen3x3's: the general branch gives the eigenvalues of
+// A / A.maxCoeff(), never scaled back, the diagonal branch those of A itself, max_coeff == 0 gives zeros.
+__host__ __device__ __forceinline__ void fast_eigen3x3_val(const M3& A, float* out) {
+    float max_coeff = A.m[0][0];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) max_coeff = (A.m[r][c] > max_coeff) ? A.m[r][c] : max_coeff;
+    float eval[3] = {0.0f, 0.0f, 0.0f};
+    if (max_coeff != 0.0f) {
+        const float s00 = A.m[0][0] / max_coeff, s11 = A.m[1][1] / max_coeff, s22 = A.m[2][2] / max_coeff;
+        const float s01 = A.m[0][1] / max_coeff, s02 = A.m[0][2] / max_coeff, s12 = A.m[1][2] / max_coeff;
+        const float norm = s01 * s01 + s02 * s02 + s12 * s12;
+        if (norm > 0.0f) {
+            const float q = (s00 + s11 + s22) / 3;
+            const float b00 = s00 - q, b11 = s11 - q, b22 = s22 - q;
+            const float p = sqrtf((b00 * b00 + b11 * b11 + b22 * b22 + norm * 2) / 6);
+            const float c00 = b11 * b22 - s12 * s12;
+            const float c01 = s01 * b22 - s12 * s02;
+            const float c02 = s01 * s12 - b11 * s02;
+            const float det = (b00 * c00 - s01 * c01 + s02 * c02) / (p * p * p);
+            const float half_det = fminf(fmaxf(det * 0.5f, -1.0f), 1.0f);
+            const float angle = acosf(half_det) / 3.0f;
+            const float two_thirds_pi = 2.09439510239319549f;
+            const float beta2 = cosf(angle) * 2;
+            const float beta0 = cosf(angle + two_thirds_pi) * 2;
+            const float beta1 = -(beta0 + beta2);
+            eval[0] = q + p * beta0;
+            eval[1] = q + p * beta1;
+            eval[2] = q + p * beta2;
+        } else {
+            eval[0] = A.m[0][0];
+            eval[1] = A.m[1][1];
+            eval[2] = A.m[2][2];
+        }
+    }
+    float mn = eval[0], mx = eval[0];  // Eigen's minCoeff / maxCoeff: the first, replaced on a strict comparison
+    mn = (eval[1] < mn) ? eval[1] : mn;
+    mn = (eval[2] < mn) ? eval[2] : mn;
+    mx = (eval[1] > mx) ? eval[1] : mx;
+    mx = (eval[2] > mx) ? eval[2] : mx;
+    out[0] = mn;
+    out[1] = ((eval[0] + eval[1]) + eval[2]) - mn - mx;
+    out[2] = mx;
+}
+
 // SqrtMatrix3x3 (utility/eigenvalue.inl:172-177): V diag(sqrt(eval)) V^T
 __host__ __device__ __forceinline__ void sqrt_matrix3x3(const M3& A, M3& W) {
     float eval[3], e[3][3];

@@ -1,6 +1,6 @@
 // mi_geometry.hip -- the geometry entry points beside the registration: Transform, bounds / centre, Translate / Scale /
 // Rotate, GICP covariances, VoxelDownSample, depth / RGB-D frame -> cloud, RGB-D odometry, colours
-// SelectByIndex / UniformDownSample, and the compaction behind them and the outlier filters; SegmentPlane
+// SelectByIndex / SelectByMask / UniformDownSample, and the compaction behind them and the outlier filters; SegmentPlane
 // (one translation unit of libmi_icp.so; csrc/ctx.h lists them)
 #include "ctx.h"
 #include "depth_kernels.h"
@@ -599,6 +599,35 @@ int mi_icp_select_by_index(mi_icp_ctx* c, const float* xyz, const float* normals
     if (bad) return fail(c, MI_ICP_ERR_INVALID, "select_by_index: index out of range [0, %lld)", (long long)n);
     *m = got;
     return MI_ICP_OK;
+}
+
+// PointCloud::SelectByMask (geometry/down_sample.cu:131-168): the entries whose mask byte is set (invert: clear),
+// ascending.  A byte per point becomes the flags; the scan and the gather are SelectByIndex's.
+int mi_icp_select_by_mask(mi_icp_ctx* c, const float* xyz, const float* normals, const float* colors, int64_t n,
+                          const uint8_t* mask, int64_t n_mask, int invert, float* out_xyz, float* out_normals,
+                          float* out_colors, int64_t* m, int mem_kind) {
+    const char* what = "select_by_mask";
+    TRY(check_ctx(c, mem_kind, what));
+    if (!m) return fail(c, MI_ICP_ERR_INVALID, "%s: m is null", what);
+    *m = 0;
+    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    if (n_mask != n)
+        return fail(c, MI_ICP_ERR_INVALID, "%s: the mask has %lld entries, the cloud %lld points", what, (long long)n_mask, (long long)n);
+    if (n == 0) return MI_ICP_OK;
+    if (!xyz || !mask || !out_xyz || (normals && !out_normals) || (colors && !out_colors))
+        return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+    const float* in[3];
+    TRY(to_device(c, xyz, (size_t)n * 3, mem_kind, c->stage[0], &in[0]));
+    TRY(to_device(c, normals, (size_t)n * 3, mem_kind, c->stage[1], &in[1]));
+    TRY(to_device(c, colors, (size_t)n * 3, mem_kind, c->stage[2], &in[2]));
+    const uint8_t* dmask;
+    TRY(to_device(c, mask, (size_t)n, mem_kind, c->keys0, &dmask));
+    uint32_t* flags;
+    TRY(ensure(c, c->flags, (size_t)n, &flags));
+    select_mask_flags<<<blocks_for(n), 256, 0, c->stream>>>(dmask, n, invert, flags);
+    KCHK(c);
+    float* const out[3] = {out_xyz, out_normals, out_colors};
+    return compact_by_flags(c, flags, n, in, out, nullptr, mem_kind, nullptr, m, nullptr);
 }
 
 // PointCloud::UniformDownSample (geometry/down_sample.cu:275-316): points 0, k, 2k, ... -- n / k of them (the size the

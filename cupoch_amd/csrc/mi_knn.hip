@@ -1,11 +1,12 @@
 // mi_knn.hip -- k-nearest-neighbour work on the target tree: PointCloud::EstimateNormals, KDTreeFlann::SearchKNN /
 // SearchRadius, Colored ICP's colour gradients and its registration entry, RemoveStatisticalOutliers /
-// RemoveRadiusOutliers, ClusterDBSCAN (knn_normals.h, select.h, dbscan.h)
+// RemoveRadiusOutliers, ClusterDBSCAN, ComputeISSKeypoints (knn_normals.h, select.h, dbscan.h, iss.h)
 // (one translation unit of libmi_icp.so; csrc/ctx.h lists them)
 #include <cstring>
 
 #include "ctx.h"
 #include "dbscan.h"
+#include "iss.h"
 #include "knn_normals.h"
 #include "select.h"
 
@@ -255,6 +256,98 @@ int mi_icp_cluster_dbscan(mi_icp_ctx* c, const float* xyz, int64_t n, float eps,
     // (a degree is at most max_edges + 1: every larger threshold means "no core point")
     const int mp = (int)std::min<int64_t>(min_points, kKnnLimit + 2);
     return dbscan_impl(c, xyz, n, eps * eps, mp, max_edges, labels, degrees, n_clusters, mem_kind);
+}
+
+// ---------------------------------------------------------------------------
+// geometry::keypoint::ComputeISSKeypoints (geometry/iss_keypoints.cu:108-172; iss.h).  The cloud gets a tree in the
+// private scratch context, once; the model resolution (when a radius is 0) is knn_normals_kernel<2> at k = 2 summed in
+// fp64, and its one scalar is the call's first wait; iss_kernel<0> and <1> follow on the same tree, and the count -- the
+// total of the scan select.h compacts with -- comes back with the second wait, together with whatever the caller asked for.
+static int iss_impl(mi_icp_ctx* c, const char* what, const float* xyz, int64_t n, float rs, float rn, IssGates gates,
+                    int k, uint8_t* mask_out, float* saliency_out, float* eig_out, int32_t* counts_out, float* radii_out,
+                    int64_t* m, int mem_kind) {
+    return in_scratch(c, what, [&](mi_icp_ctx* a) -> int {
+        const float* pts;
+        TRY(to_device(a, xyz, (size_t)n * 3, mem_kind, a->stage[0], &pts));
+        TRY(mi_icp_set_target(a, pts, nullptr, nullptr, n, MI_ICP_DEVICE));
+        hipStream_t s = a->stream;
+        if (rs == 0.0f || rn == 0.0f) {  // ComputeModelResolution (iss_keypoints.cu:37-49): both radii replaced
+            float* half_d2;
+            double *part, *sum;
+            const int blocks = std::min(kOutlierBlocks, blocks_for(n));
+            TRY(ensure(a, a->stage[3], (size_t)n, &half_d2));
+            TRY(ensure(a, a->partial, (size_t)kOutlierBlocks * 4, &part));
+            TRY(ensure(a, a->sys_dev, (size_t)kSysSize, &sum));
+            TRY(launch_knn_normals<2>(a, 2, INFINITY, half_d2, nullptr, nullptr));
+            outlier_stats_partial<<<blocks, 256, 0, s>>>(half_d2, n, part);
+            iss_resolution_sum<<<1, 64, 0, s>>>(part, blocks, sum);
+            KCHK(a);
+            HIPCHK(a, hipMemcpyAsync(a->sys_host, sum, sizeof(double), hipMemcpyDeviceToHost, s));
+            HIPCHK(a, hipStreamSynchronize(s));
+            const float resolution = (float)std::sqrt(a->sys_host[0] / (double)n);
+            rs = 6.0f * resolution;
+            rn = 4.0f * resolution;
+        }
+        if (radii_out) {
+            radii_out[0] = rs;
+            radii_out[1] = rn;
+        }
+        if (!(rs * rs < INFINITY) || !(rn * rn < INFINITY)) return fail(a, MI_ICP_ERR_INVALID, "a radius is not finite when squared");
+        float *sal, *eig;
+        int32_t* cnt;
+        uint8_t* mask;
+        uint32_t *flags, *pos, *tmp;
+        TRY(out_slot(a, saliency_out, (size_t)n, mem_kind, a->stage[1], &sal));
+        if (!sal) TRY(ensure(a, a->stage[1], (size_t)n, &sal));  // (the caller does not want it; pass 1 does)
+        TRY(out_slot(a, eig_out, (size_t)n * 3, mem_kind, a->stage[2], &eig));
+        TRY(out_slot(a, counts_out, (size_t)n, mem_kind, a->stage[3], &cnt));
+        TRY(out_slot(a, mask_out, (size_t)n, mem_kind, a->stage[4], &mask));
+        TRY(ensure(a, a->flags, (size_t)n, &flags));
+        TRY(ensure(a, a->dense_idx, (size_t)n, &pos));
+        TRY(ensure(a, a->scan_tmp, (size_t)scan_num_tiles(n) + 2, &tmp));
+        const uint32_t nblocks = (uint32_t)((a->nleaf + 7) / 8);
+        auto pass = [&](auto which, float r2) -> int {
+            return knn_launch(a, k, nblocks, [](auto kc) { return iss_kernel<decltype(which)::value, decltype(kc)::value>; },
+                              (const float*)a->nodes.p, (const float*)a->tblk.p, (const int32_t*)a->tidx.p, a->leaf_first,
+                              a->nts, a->nleaf, k, r2, pts, gates, sal, eig, cnt, mask, flags);
+        };
+        TRY(pass(Cap<0>(), rs * rs));
+        TRY(pass(Cap<1>(), rn * rn));
+        exclusive_scan_u32(s, flags, pos, n, tmp);
+        KCHK(a);
+        HIPCHK(a, hipMemcpyAsync(a->u_host, tmp + scan_num_tiles(n), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        TRY(from_device(a, (const float*)sal, saliency_out, (size_t)n, mem_kind));
+        TRY(from_device(a, (const float*)eig, eig_out, (size_t)n * 3, mem_kind));
+        TRY(from_device(a, (const int32_t*)cnt, counts_out, (size_t)n, mem_kind));
+        TRY(from_device(a, (const uint8_t*)mask, mask_out, (size_t)n, mem_kind));
+        HIPCHK(a, hipStreamSynchronize(s));
+        *m = (int64_t)a->u_host[0];
+        return MI_ICP_OK;
+    });
+}
+
+int mi_icp_iss_keypoints(mi_icp_ctx* c, const float* xyz, int64_t n, float salient_radius, float non_max_radius,
+                         float gamma_21, float gamma_32, int min_neighbors, int max_neighbors, uint8_t* mask_out,
+                         float* saliency_out, float* eig_out, int32_t* counts_out, float* radii_out, int64_t* m,
+                         int mem_kind) {
+    const char* what = "iss_keypoints";
+    TRY(check_ctx(c, mem_kind, what));
+    if (!m) return fail(c, MI_ICP_ERR_INVALID, "%s: m is null", what);
+    *m = 0;
+    if (radii_out) {
+        radii_out[0] = salient_radius;
+        radii_out[1] = non_max_radius;
+    }
+    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    if (n > 0 && (!xyz || !mask_out)) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+    if (!(salient_radius >= 0.0f) || !(non_max_radius >= 0.0f) || !(salient_radius * salient_radius < INFINITY) ||
+        !(non_max_radius * non_max_radius < INFINITY))
+        return fail(c, MI_ICP_ERR_INVALID, "%s: the radii must not be negative, and finite when squared", what);
+    if (max_neighbors < 1 || max_neighbors > kKnnLimit)
+        return fail(c, MI_ICP_ERR_INVALID, "%s: max_neighbors outside [1, %d] (knn::NUM_MAX_NN)", what, kKnnLimit);
+    if (n == 0) return MI_ICP_OK;
+    return iss_impl(c, what, xyz, n, salient_radius, non_max_radius, IssGates{min_neighbors, gamma_21, gamma_32},
+                    max_neighbors, mask_out, saliency_out, eig_out, counts_out, radii_out, m, mem_kind);
 }
 
 // ---------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 //                 every kept point at its scanned position, ascending in original index)
 //   SelectByIndex: select_list (a gather in the order given) or, with invert, select_mark (flags start at 1, the named
 //                 indices clear theirs) and the same scan + select_gather.
+//   SelectByMask:  select_mask_flags (a byte per point -> the flags) and the same scan + select_gather.
 // Every sum has a fixed order (per block, then the blocks in a fixed order): the same input gives the same threshold on
 // every run and every context.  Indices outside [0, n) are reported in a status word that comes back with the count.
 #pragma once
@@ -147,6 +148,14 @@ static __global__ __launch_bounds__(256) void select_mark(const int64_t* __restr
         return;
     }
     flags[i] = 0u;
+}
+
+// SelectByMask's flags: entry i is kept iff (mask[i] != 0) != invert
+static __global__ __launch_bounds__(256) void select_mask_flags(const uint8_t* __restrict__ mask, int64_t n, int invert,
+                                                               uint32_t* __restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    flags[i] = ((mask[i] != 0) != (invert != 0)) ? 1u : 0u;
 }
 
 }  // namespace mi

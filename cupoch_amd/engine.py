@@ -126,7 +126,7 @@ class Engine:
     def _out(kind, device, shape, dtype=np.float32):
         """an empty output array: a torch tensor on `device` (MI_ICP_DEVICE) or a numpy array; (array, pointer)"""
         if kind == MI_ICP_DEVICE:
-            tdt = {np.float32: torch.float32, np.int32: torch.int32, np.int64: torch.int64}[dtype]
+            tdt = {np.float32: torch.float32, np.int32: torch.int32, np.int64: torch.int64, np.uint8: torch.uint8}[dtype]
             t = torch.empty(shape, dtype=tdt, device=device)
             return t, C.c_void_p(t.data_ptr())
         a = np.empty(shape, dtype)
@@ -347,7 +347,7 @@ class Engine:
         return p.keep, n.keep, _cov_out(c.keep)
 
     # -- PointCloud::VoxelDownSample / SelectByIndex / UniformDownSample / Remove*Outliers (down_sample.cu), ------
-    # -- ClusterDBSCAN, SegmentPlane
+    # -- ClusterDBSCAN, SegmentPlane, ComputeISSKeypoints / SelectByMask
     def _cloud_args(self, points, normals, colors):
         p = _Buf(points, np.float32, 3, self.device)
         n = _Buf(normals, np.float32, 3, self.device)
@@ -436,6 +436,46 @@ class Engine:
         m = C.c_int64(0)
         self._chk(self._L.mi_icp_select_by_index(self._ctx, p.ptr, n.ptr, c.ptr, p.n, pix, nix, int(bool(invert)),
                                                  pp, pn, pc, C.byref(m), kind))
+        k = int(m.value)
+        return self._trim(op, k), self._trim(on, k), self._trim(oc, k)
+
+    def iss_keypoints(self, points, salient_radius=0.0, non_max_radius=0.0, gamma_21=0.975, gamma_32=0.975,
+                      min_neighbors=5, max_neighbors=100, want_response=False):
+        """geometry::keypoint::ComputeISSKeypoints (iss_keypoints.cu:108-172; the contract is in include/mi_icp.h).
+        Returns (mask uint8[n] on the side of `points`, the number of keypoints, (salient_radius, non_max_radius) as
+        used); with want_response also saliency float32[n], eigenvalues float32[n, 3] and salient-row counts int32[n]."""
+        p = _Buf(points, np.float32, 3, self.device)
+        kind = self._same_kind(p)
+        mask, pmask = self._out(kind, p.device, (p.n,), np.uint8)
+        sal = eig = cnt = psal = peig = pcnt = None
+        if want_response:
+            sal, psal = self._out(kind, p.device, (p.n,), np.float32)
+            eig, peig = self._out(kind, p.device, (p.n, 3), np.float32)
+            cnt, pcnt = self._out(kind, p.device, (p.n,), np.int32)
+        radii = np.zeros(2, np.float32)
+        m = C.c_int64(0)
+        self._chk(self._L.mi_icp_iss_keypoints(self._ctx, p.ptr, p.n, float(salient_radius), float(non_max_radius),
+                                               float(gamma_21), float(gamma_32), int(min_neighbors), int(max_neighbors),
+                                               pmask, psal, peig, pcnt, radii.ctypes.data_as(C.c_void_p), C.byref(m), kind))
+        out = (mask, int(m.value), (float(radii[0]), float(radii[1])))
+        return out + (sal, eig, cnt) if want_response else out
+
+    def select_by_mask(self, points, mask, invert=False, normals=None, colors=None):
+        """PointCloud::SelectByMask (down_sample.cu:131-168).  mask: anything 1-D of one truth value per point (a bool
+        or uint8 tensor on the points' device, a numpy array, a list); returns (points, normals or None, colors or None)."""
+        p, n, c, kind = self._cloud_args(points, normals, colors)
+        if kind == MI_ICP_DEVICE:
+            mk = mask if _is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0))
+            mk = (mk.reshape(-1) != 0).to(device=p.device, dtype=torch.uint8).contiguous()
+            pmk, nmk = C.c_void_p(mk.data_ptr()), int(mk.shape[0])
+        else:
+            mk = mask.detach().cpu().numpy() if _is_tensor(mask) else mask
+            mk = np.ascontiguousarray((np.asarray(mk).reshape(-1) != 0).astype(np.uint8))
+            pmk, nmk = mk.ctypes.data_as(C.c_void_p), int(mk.shape[0])
+        (op, pp), (on, pn), (oc, pc) = self._cloud_outputs(kind, p, n, c, p.n)
+        m = C.c_int64(0)
+        self._chk(self._L.mi_icp_select_by_mask(self._ctx, p.ptr, n.ptr, c.ptr, p.n, pmk, nmk, int(bool(invert)),
+                                                pp, pn, pc, C.byref(m), kind))
         k = int(m.value)
         return self._trim(op, k), self._trim(on, k), self._trim(oc, k)
 

@@ -288,6 +288,19 @@ class PointCloud:
         eng, n, c = self._engine_args()
         return self._made(*eng.select_by_index(self._points.tensor, indices, bool(invert), n, c))
 
+    def select_by_mask(self, mask, invert=False):
+        """points, normals and colours of the entries whose mask entry is set (a BoolVector, list, numpy array or
+        tensor of one entry per point; invert=True: not set), ascending"""
+        if isinstance(mask, utility.DeviceVector):
+            mask = mask.tensor
+        if len(mask) != len(self._points):
+            print("[cupoch_amd] Error: [SelectByMask] The point size should be equal to the mask size.")
+            return PointCloud()         # (down_sample.cu:134-137 logs and returns an empty cloud)
+        if not self.has_points():
+            return PointCloud()
+        eng, n, c = self._engine_args()
+        return self._made(*eng.select_by_mask(self._points.tensor, mask, bool(invert), n, c))
+
     def uniform_down_sample(self, every_k_points):
         eng, n, c = self._engine_args()
         return self._made(*eng.uniform_downsample(self._points.tensor, int(every_k_points), n, c))
@@ -335,6 +348,23 @@ class PointCloud:
             nrm = eng.estimate_normals_knn(self._points.tensor, k)
         self._normals = utility.Vector3fVector(nrm)
         return True
+
+
+class keypoint:
+    """geometry::keypoint (geometry/keypoint.h; python surface cupoch_pybind/geometry/keypoint.cpp)"""
+
+    @staticmethod
+    def compute_iss_keypoints(input, salient_radius=0.0, non_max_radius=0.0, gamma_21=0.975, gamma_32=0.975,
+                              min_neighbors=5, max_neighbors=100):
+        """(PointCloud of the ISS keypoints, BoolVector of one entry per input point); include/mi_icp.h states the
+        contract.  A radius of 0 has both radii computed from the cloud's resolution."""
+        if not input.has_points():
+            print("[cupoch_amd] Warning: [ComputeISSKeypoints] Input PointCloud is empty!")
+            return PointCloud(), utility.BoolVector()
+        eng = get_engine(input.points.tensor.device.index)
+        mask, _, _ = eng.iss_keypoints(input.points.tensor, float(salient_radius), float(non_max_radius), float(gamma_21),
+                                       float(gamma_32), int(min_neighbors), int(max_neighbors))
+        return input.select_by_mask(mask), utility.BoolVector(mask)
 
 
 class Image:

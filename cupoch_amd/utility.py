@@ -117,6 +117,17 @@ class IntVector(DeviceVector):
         return obj
 
 
+class BoolVector(DeviceVector):
+    """device_vector<bool>: a 1-D device vector of one byte per entry -- the mask keypoint.compute_iss_keypoints
+    returns and PointCloud.select_by_mask takes."""
+    cols = 0
+
+    def __init__(self, data=None):
+        if data is None:
+            data = np.zeros((0,), np.bool_)
+        self.tensor = _to_device_tensor(data, 0, torch.bool).reshape(-1)
+
+
 class Vector2iVector(DeviceVector):
     cols = 2
 

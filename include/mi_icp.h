@@ -260,6 +260,15 @@ MI_ICP_API int mi_icp_select_by_index(mi_icp_ctx* ctx, const float* xyz, const f
                                       const float* colors, int64_t n, const int64_t* indices,
                                       int64_t n_indices, int invert, float* out_xyz, float* out_normals,
                                       float* out_colors, int64_t* m, int mem_kind);
+/* PointCloud::SelectByMask (geometry/down_sample.cu:131-168).  mask: one byte per point (uint8
+ * [n_mask], device_vector<bool>), in the same memory kind as the points.  The points, and normals /
+ * colours where given, of the entries whose byte is non-zero (invert != 0: zero), ascending in
+ * index; *m = their number.  Outputs hold n entries.  n_mask != n is MI_ICP_ERR_INVALID, as the
+ * reference refuses a mask of another size.  The entry point synchronises the context's stream. */
+MI_ICP_API int mi_icp_select_by_mask(mi_icp_ctx* ctx, const float* xyz, const float* normals,
+                                     const float* colors, int64_t n, const uint8_t* mask, int64_t n_mask,
+                                     int invert, float* out_xyz, float* out_normals, float* out_colors,
+                                     int64_t* m, int mem_kind);
 /* PointCloud::UniformDownSample (geometry/down_sample.cu:275-316): the points at indices 0, k, 2k, ...
  * -- *m = n / every_k_points of them (the size the reference allocates; 0 when k > n) -- with their
  * normals / colours (either may be NULL).  every_k_points < 1 is MI_ICP_ERR_INVALID.  Outputs hold
@@ -501,6 +510,57 @@ MI_ICP_API int mi_icp_segment_plane(mi_icp_ctx* ctx, const float* xyz, int64_t n
                                     int64_t ransac_n, int64_t num_iterations, uint64_t seed, float* plane4,
                                     float* ransac_plane4, int64_t* inliers, int64_t* m,
                                     int64_t* best_iteration, int64_t* best_count, int mem_kind);
+
+/* geometry::keypoint::ComputeISSKeypoints(input, salient_radius, non_max_radius, gamma_21, gamma_32,
+ * min_neighbors, max_neighbors) (geometry/iss_keypoints.cu:37-172): Intrinsic Shape Signatures.  Its
+ * contract, which mask, counts and saliency meet exactly given the eigenvalues (these carry fp32
+ * rounding in an order the contract leaves open):
+ *   radii     salient_radius == 0 or non_max_radius == 0: BOTH are replaced (iss_keypoints.cu:124-127)
+ *             by 6 * resolution and 4 * resolution (fp32 products), resolution =
+ *             (float)sqrt(S / n) in fp64, S = the fp64 sum, in a fixed order, over all points of the
+ *             fp32 squared distance to the nearest other entry of a k = 2 search (the point itself
+ *             being the first; a duplicate counts with 0) -- an RMS, as the reference computes it.
+ *             radii_out (host float[2] or NULL): the radii used.
+ *   row(i,r)  the points j with fp32 d2(i, j) < r*r (r*r one fp32 product; d2 = fma(dz, dz,
+ *             fma(dy, dy, dx*dx)) of the fp32 differences p_i - p_j, as everywhere in this header), the
+ *             point itself among them; when more than max_neighbors, the max_neighbors smallest by
+ *             (d2, index) -- SearchRadius(r, max_neighbors), ClusterDBSCAN's row convention.
+ *   eig(i)    count = |row(i, salient_radius)|.  count < min_neighbors: eig = (-1, -1, -1).  Otherwise
+ *             the nine cumulants (x, y, z, xx, xy, xz, yy, yz, zz) of q = p_j - p_i over the row in
+ *             fp32 (the subtraction first, products unfused, the sums in an order the contract leaves
+ *             open), each divided by (float)count, C = E[qq^T] - E[q]E[q]^T entry by entry as the
+ *             reference forms it.  ZERO TEST: Eigen's isZero() at its fp32 default, i.e. every
+ *             |C_ij| <= 1e-5 ABSOLUTE (a cloud whose salient neighbourhoods are smaller than a few
+ *             millimetres in its own unit has no keypoints, in the reference as here): eig =
+ *             (-1, -1, -1).  Otherwise FastEigen3x3Val (utility/eigenvalue.inl:93-170): with
+ *             mc = the largest of the nine entries (signed), mc == 0 gives zeros; off-diagonal
+ *             entries of C / mc all zero gives the diagonal of C itself; otherwise the closed form
+ *             gives the eigenvalues of C / mc, NOT scaled back.  Sorted as the reference sorts
+ *             them: e0 = min, e2 = max, e1 = ((v0 + v1) + v2) - e0 - e2.  These values are compared
+ *             across points as they are -- scaled in one point, unscaled in the next -- in the
+ *             reference and here.
+ *   saliency  e0 if e2 > 0 && e1 / e2 < gamma_21 && e0 / e1 < gamma_32 (IEEE fp32 divisions; a NaN
+ *             compares false), else -1.  A flat or straight neighbourhood has e0 = 0 or a rounding
+ *             error of either sign: it passes the gates when e1 > 0, and its saliency is that e0.
+ *   mask(i)   saliency(i) >= 0 and no l in row(i, non_max_radius) has saliency(i) < saliency(l)
+ *             (strict: tied neighbours both stay).  So a negative e0 is never a keypoint and
+ *             suppresses nobody; e0 = 0 is one when nothing in its row is positive.
+ * Outputs, n entries each on the side mem_kind names: mask_out (uint8, 0 / 1); saliency_out (float),
+ * eig_out (float[n][3]), counts_out (int32: count above) -- each may be NULL; *m = the number of
+ * mask bytes set.  The keypoints themselves: mi_icp_select_by_mask.
+ * Deviation (deliberate): the reference accumulates raw coordinates; the covariance is the same
+ * quantity, but E[xx] - E[x]E[x] in fp32 then cancels to the order of the smallest eigenvalue for
+ * coordinates of order 1 (DESIGN.md has the measurement).  Negative radii are turned away (the
+ * reference would square them).
+ * Limits: radii >= 0 with finite squares, max_neighbors in [1, 100] (knn::NUM_MAX_NN), n < 2^31; else
+ * MI_ICP_ERR_INVALID.  n = 0 gives *m = 0.  The same input gives the same bytes on every run and
+ * context.  The cloud's tree is built once, in the private scratch context: the caller's target /
+ * source / loop state survive.  Memory on top of the tree: 13 bytes per point plus the outputs;
+ * no row is written out.  Synchronises the context's stream once, twice when the radii are computed. */
+MI_ICP_API int mi_icp_iss_keypoints(mi_icp_ctx* ctx, const float* xyz, int64_t n, float salient_radius,
+                                    float non_max_radius, float gamma_21, float gamma_32, int min_neighbors,
+                                    int max_neighbors, uint8_t* mask_out, float* saliency_out, float* eig_out,
+                                    int32_t* counts_out, float* radii_out, int64_t* m, int mem_kind);
 
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
