@@ -164,6 +164,11 @@ SIGNATURES = {
     "mi_icp_cluster_dbscan": (_I, [_P, _P, _L, _F, _L, _I, _P, _P, C.POINTER(_L), _I]),
     "mi_icp_segment_plane": (_I, [_P, _P, _L, _F, _L, _L, C.c_uint64, _P, _P, _P, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), _I]),
     "mi_icp_iss_keypoints": (_I, [_P, _P, _L, _F, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, C.POINTER(_L), _I]),
+    "mi_icp_farthest_point_downsample": (_I, [_P, _P, _P, _P, _L, _L, _P, _P, _P, _P, C.POINTER(_L), _I]),
+    "mi_icp_pass_through_filter": (_I, [_P, _P, _P, _P, _L, _I, _F, _F, _P, _P, _P, _P, C.POINTER(_L), _I]),
+    "mi_icp_crop_aabb": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, C.POINTER(_L), _I]),
+    "mi_icp_remove_none_finite": (_I, [_P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P, C.POINTER(_L), _I]),
+    "mi_icp_gaussian_filter": (_I, [_P, _P, _P, _P, _L, _F, _F, _I, _P, _P, _P, _I]),
     "mi_icp_create_from_depth": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _F, _F, _F, _I, _I, _I, _I,
                                       _P, _P, _P, C.POINTER(_L), _I]),
     "mi_icp_compute_rgbd_odometry": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P, C.POINTER(_I), _P, _P, _I]),

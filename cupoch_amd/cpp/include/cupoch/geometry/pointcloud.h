@@ -161,6 +161,22 @@ public:
     /// (fp64 statistics, include/mi_icp.h); nb_neighbors <= knn::NUM_MAX_NN.  Returns the kept cloud and their indices.
     std::tuple<std::shared_ptr<PointCloud>, utility::device_vector<size_t>> RemoveStatisticalOutliers(
             size_t nb_neighbors, float std_ratio) const;
+    /// pointcloud.cu:40-54,360-385: drops, in place, the points with a NaN (remove_nan) or infinite (remove_infinite)
+    /// coordinate, with their normals and colours
+    PointCloud& RemoveNoneFinitePoints(bool remove_nan = true, bool remove_infinite = true);
+    /// pointcloud.cu:56-106,387-434: every point, normal and colour replaced by the mean of its radius neighbours
+    /// (at most num_max_search_points <= knn::NUM_MAX_NN, itself included) weighted with exp(-0.5 d2 / sigma2); normals
+    /// are not re-normalised.  Illegal parameters log an error and give an empty cloud, as in the reference.
+    std::shared_ptr<PointCloud> GaussianFilter(float search_radius, float sigma2, size_t num_max_search_points = 50);
+    /// pointcloud.cu:108-120,436-466: the points with min_bound <= p[axis_no] <= max_bound (a NaN coordinate is kept);
+    /// axis_no >= 3 logs an error and gives an empty cloud
+    std::shared_ptr<PointCloud> PassThroughFilter(size_t axis_no, float min_bound, float max_bound);
+    /// pointcloud.cu:122-139,301-338: num_samples points, each the farthest from those chosen before it; point 0
+    /// first, ties to the lowest index (the contract: include/mi_icp.h).  More samples than points logs an error and
+    /// gives an empty cloud.
+    std::shared_ptr<PointCloud> FarthestPointDownSample(size_t num_samples) const;
+    /// pointcloud.cu:340-348: the points inside the closed box; an empty box logs an error and gives an empty cloud
+    std::shared_ptr<PointCloud> Crop(const AxisAlignedBoundingBox3& bbox) const;
     /// pointcloud_cluster.cu:109-179: one label per point, its cluster's number or -1 (the contract: include/mi_icp.h);
     /// max_edges <= knn::NUM_MAX_NN.  print_progress is accepted and prints nothing.
     std::unique_ptr<utility::device_vector<int>> ClusterDBSCAN(float eps, size_t min_points, bool print_progress = false,

@@ -307,6 +307,85 @@ std::tuple<std::shared_ptr<PointCloud>, utility::device_vector<size_t>> PointClo
     });
 }
 
+std::shared_ptr<PointCloud> PointCloud::FarthestPointDownSample(size_t num_samples) const {
+    const size_t n = points_.size();
+    if (num_samples == 0) return std::make_shared<PointCloud>();
+    if (num_samples > n) {  // pointcloud.cu:308-312
+        LogError("[FarthestPointDownSample] Illegal number of samples, must <= point size.");
+        return std::make_shared<PointCloud>();
+    }
+    auto out = SelectionOut(*this, num_samples);
+    int64_t m = 0;
+    Check(mi_icp_farthest_point_downsample(Engine(), Ptr(points_), HasNormals() ? Ptr(normals_) : nullptr,
+                                           HasColors() ? Ptr(colors_) : nullptr, (int64_t)n, (int64_t)num_samples,
+                                           MutPtr(out->points_), MutPtr(out->normals_), MutPtr(out->colors_), nullptr, &m,
+                                           MI_ICP_DEVICE));
+    SelectionTrim(*out, m);
+    return out;
+}
+
+std::shared_ptr<PointCloud> PointCloud::GaussianFilter(float search_radius, float sigma2, size_t num_max_search_points) {
+    if (!(search_radius > 0.0f) || !(sigma2 > 0.0f) || num_max_search_points == 0 ||
+        num_max_search_points > (size_t)knn::NUM_MAX_NN) {  // pointcloud.cu:390-395
+        LogError("[GaussianFilter] Illegal input parameters, radius and sigma2 must be positive.");
+        return std::make_shared<PointCloud>();
+    }
+    const size_t n = points_.size();
+    auto out = SelectionOut(*this, n);
+    Check(mi_icp_gaussian_filter(Engine(), Ptr(points_), HasNormals() ? Ptr(normals_) : nullptr,
+                                 HasColors() ? Ptr(colors_) : nullptr, (int64_t)n, search_radius, sigma2,
+                                 (int)num_max_search_points, MutPtr(out->points_), MutPtr(out->normals_),
+                                 MutPtr(out->colors_), MI_ICP_DEVICE));
+    return out;
+}
+
+// the three predicate filters: the kept cloud
+template <class Fn>
+static std::shared_ptr<PointCloud> PredicateFilter(const PointCloud& pc, Fn fn) {
+    const size_t n = pc.points_.size();
+    auto out = SelectionOut(pc, n);
+    int64_t m = 0;
+    Check(fn(pc.HasNormals() ? Ptr(pc.normals_) : nullptr, pc.HasColors() ? Ptr(pc.colors_) : nullptr, (int64_t)n,
+             MutPtr(out->points_), MutPtr(out->normals_), MutPtr(out->colors_), &m));
+    SelectionTrim(*out, m);
+    return out;
+}
+
+std::shared_ptr<PointCloud> PointCloud::PassThroughFilter(size_t axis_no, float min_bound, float max_bound) {
+    if (axis_no >= 3) {  // pointcloud.cu:440-445
+        LogError("[PassThroughFilter] Illegal input parameters, axis_no must be 0, 1 or 2.");
+        return std::make_shared<PointCloud>();
+    }
+    return PredicateFilter(*this, [&](const float* nrm, const float* col, int64_t n, float* op, float* on, float* oc, int64_t* m) {
+        return mi_icp_pass_through_filter(Engine(), Ptr(points_), nrm, col, n, (int)axis_no, min_bound, max_bound, op, on, oc,
+                                          nullptr, m, MI_ICP_DEVICE);
+    });
+}
+
+std::shared_ptr<PointCloud> PointCloud::Crop(const AxisAlignedBoundingBox3& bbox) const {
+    if (!(bbox.Volume() > 0.0f)) {  // pointcloud.cu:342-346
+        LogError("[CropPointCloud] AxisAlignedBoundingBox either has zeros size, or has wrong bounds.");
+        return std::make_shared<PointCloud>();
+    }
+    return PredicateFilter(*this, [&](const float* nrm, const float* col, int64_t n, float* op, float* on, float* oc, int64_t* m) {
+        return mi_icp_crop_aabb(Engine(), Ptr(points_), nrm, col, n, bbox.min_bound_.data(), bbox.max_bound_.data(), op, on,
+                                oc, nullptr, m, MI_ICP_DEVICE);
+    });
+}
+
+PointCloud& PointCloud::RemoveNoneFinitePoints(bool remove_nan, bool remove_infinite) {
+    const bool hn = HasNormals(), hc = HasColors();
+    auto kept = PredicateFilter(*this, [&](const float* nrm, const float* col, int64_t n, float* op, float* on, float* oc, int64_t* m) {
+        return mi_icp_remove_none_finite(Engine(), Ptr(points_), nrm, col, n, remove_nan ? 1 : 0, remove_infinite ? 1 : 0, op,
+                                         on, oc, nullptr, m, MI_ICP_DEVICE);
+    });
+    if (kept->points_.size() != points_.size()) covariances_.clear();  // (not carried, in the reference neither)
+    points_.swap(kept->points_);
+    if (hn) normals_.swap(kept->normals_);
+    if (hc) colors_.swap(kept->colors_);
+    return *this;
+}
+
 std::unique_ptr<utility::device_vector<int>> PointCloud::ClusterDBSCAN(float eps, size_t min_points, bool,
                                                                        size_t max_edges) const {
     const size_t n = points_.size();

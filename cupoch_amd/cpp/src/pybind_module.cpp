@@ -381,6 +381,26 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             .def_readwrite("radius", &knn::KDTreeSearchParamRadius::radius_)
             .def_readwrite("max_nn", &knn::KDTreeSearchParamRadius::max_nn_);
 
+    // geometry::AxisAlignedBoundingBox<3> (cupoch_pybind/geometry/boundingvolume.cpp): what PointCloud.crop takes
+    py::class_<geometry::AxisAlignedBoundingBox3, std::shared_ptr<geometry::AxisAlignedBoundingBox3>>(mg, "AxisAlignedBoundingBox")
+            .def(py::init<>())
+            .def(py::init([](const farray& lo, const farray& hi) {
+                     return std::make_shared<geometry::AxisAlignedBoundingBox3>(to_vector3(lo), to_vector3(hi));
+                 }),
+                 "min_bound"_a, "max_bound"_a)
+            .def_property(
+                    "min_bound", [](const geometry::AxisAlignedBoundingBox3& b) { return from_vector3(b.min_bound_); },
+                    [](geometry::AxisAlignedBoundingBox3& b, const farray& v) { b.min_bound_ = to_vector3(v); })
+            .def_property(
+                    "max_bound", [](const geometry::AxisAlignedBoundingBox3& b) { return from_vector3(b.max_bound_); },
+                    [](geometry::AxisAlignedBoundingBox3& b, const farray& v) { b.max_bound_ = to_vector3(v); })
+            .def("get_min_bound", [](const geometry::AxisAlignedBoundingBox3& b) { return from_vector3(b.GetMinBound()); })
+            .def("get_max_bound", [](const geometry::AxisAlignedBoundingBox3& b) { return from_vector3(b.GetMaxBound()); })
+            .def("get_center", [](const geometry::AxisAlignedBoundingBox3& b) { return from_vector3(b.GetCenter()); })
+            .def("get_extent", [](const geometry::AxisAlignedBoundingBox3& b) { return from_vector3(b.GetExtent()); })
+            .def("volume", &geometry::AxisAlignedBoundingBox3::Volume)
+            .def("is_empty", &geometry::AxisAlignedBoundingBox3::IsEmpty);
+
     py::class_<geometry::PointCloud, std::shared_ptr<geometry::PointCloud>>(mg, "PointCloud")
             .def(py::init<>())
             .def(py::init([](const py::object& pts) {
@@ -452,6 +472,21 @@ PYBIND11_MODULE(cupoch_pybind, m) {
                     },
                     "mask"_a, "invert"_a = false)
             .def("uniform_down_sample", &geometry::PointCloud::UniformDownSample, "every_k_points"_a)
+            .def("get_axis_aligned_bounding_box",
+                 [](const geometry::PointCloud& pc) {
+                     return std::make_shared<geometry::AxisAlignedBoundingBox3>(pc.GetAxisAlignedBoundingBox());
+                 })
+            .def("farthest_point_down_sample", &geometry::PointCloud::FarthestPointDownSample, "num_samples"_a)
+            .def("gaussian_filter", &geometry::PointCloud::GaussianFilter, "search_radius"_a, "sigma2"_a,
+                 "num_max_search_points"_a = 50)
+            .def("pass_through_filter", &geometry::PointCloud::PassThroughFilter, "axis_no"_a, "min_bound"_a, "max_bound"_a)
+            .def("crop", &geometry::PointCloud::Crop, "bounding_box"_a)
+            .def("remove_none_finite_points",
+                 [](std::shared_ptr<geometry::PointCloud> pc, bool remove_nan, bool remove_infinite) {
+                     pc->RemoveNoneFinitePoints(remove_nan, remove_infinite);
+                     return pc;
+                 },
+                 "remove_nan"_a = true, "remove_infinite"_a = true)
             .def(
                     "remove_radius_outlier",
                     [](const geometry::PointCloud& pc, size_t nb_points, float search_radius) {

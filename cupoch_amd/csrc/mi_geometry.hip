@@ -1,9 +1,11 @@
 // mi_geometry.hip -- the geometry entry points beside the registration: Transform, bounds / centre, Translate / Scale /
 // Rotate, GICP covariances, VoxelDownSample, depth / RGB-D frame -> cloud, RGB-D odometry, colours
-// SelectByIndex / SelectByMask / UniformDownSample, and the compaction behind them and the outlier filters; SegmentPlane
+// SelectByIndex / SelectByMask / UniformDownSample, and the compaction behind them and the outlier filters; SegmentPlane;
+// FarthestPointDownSample, PassThroughFilter / Crop / RemoveNoneFinitePoints
 // (one translation unit of libmi_icp.so; csrc/ctx.h lists them)
 #include "ctx.h"
 #include "depth_kernels.h"
+#include "farthest_point.h"
 #include "geometry_kernels.h"
 #include "lbvh.h"
 #include "odometry.h"
@@ -658,6 +660,140 @@ int mi_icp_uniform_downsample(mi_icp_ctx* c, const float* xyz, const float* norm
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *m = cnt;
     return MI_ICP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// PointCloud::FarthestPointDownSample (geometry/pointcloud.cu:122-139, 301-338; farthest_point.h): one launch per sample,
+// all of them enqueued before the one wait; the gather is SelectByIndex's select_list over the device-resident sel.
+int mi_icp_farthest_point_downsample(mi_icp_ctx* c, const float* xyz, const float* normals, const float* colors, int64_t n,
+                                     int64_t num_samples, float* out_xyz, float* out_normals, float* out_colors,
+                                     int64_t* out_idx, int64_t* m, int mem_kind) {
+    const char* what = "farthest_point_downsample";
+    TRY(check_ctx(c, mem_kind, what));
+    if (!m) return fail(c, MI_ICP_ERR_INVALID, "%s: m is null", what);
+    *m = 0;
+    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    if (num_samples < 0) return fail(c, MI_ICP_ERR_INVALID, "%s: num_samples must not be negative", what);
+    if (num_samples > n)
+        return fail(c, MI_ICP_ERR_INVALID, "%s: %lld samples asked of %lld points", what, (long long)num_samples, (long long)n);
+    if (num_samples == 0) return MI_ICP_OK;
+    if (!xyz || !out_xyz || (normals && !out_normals) || (colors && !out_colors))
+        return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+    const float* in[3];
+    TRY(to_device(c, xyz, (size_t)n * 3, mem_kind, c->stage[0], &in[0]));
+    TRY(to_device(c, normals, (size_t)n * 3, mem_kind, c->stage[1], &in[1]));
+    TRY(to_device(c, colors, (size_t)n * 3, mem_kind, c->stage[2], &in[2]));
+    int64_t* sel;
+    TRY(out_slot(c, out_idx, (size_t)num_samples, mem_kind, c->keys0, &sel));
+    if (!sel) TRY(ensure(c, c->keys0, (size_t)num_samples, &sel));  // (the caller does not want it; the gather does)
+    hipStream_t s = c->stream;
+    if (num_samples == n) {  // the reference's early return: the cloud itself
+        fps_iota<<<blocks_for(n), 256, 0, s>>>(sel, n);
+    } else {
+        float* dist;
+        FpsState* st;
+        TRY(ensure(c, c->stage[3], (size_t)n, &dist));
+        TRY(ensure(c, c->keys1, 1, &st));
+        const int blocks = std::min(kFpsMaxBlocks, blocks_for(n, kFpsThreads));
+        fps_init<<<1, 64, 0, s>>>(in[0], st, sel);
+        for (int64_t t = 0; t + 1 < num_samples; ++t) {
+            if (t == 0) fps_step<true><<<blocks, kFpsThreads, 0, s>>>(in[0], dist, n, t, st, sel);
+            else fps_step<false><<<blocks, kFpsThreads, 0, s>>>(in[0], dist, n, t, st, sel);
+        }
+    }
+    KCHK(c);
+    uint32_t* status;
+    TRY(ensure(c, c->flags, 1, &status));
+    HIPCHK(c, hipMemsetAsync(status, 0, sizeof(uint32_t), s));
+    float* const out[3] = {out_xyz, out_normals, out_colors};
+    float* dst[3];
+    TRY(cloud_out(c, in, out, num_samples, mem_kind, c->vpay, dst));
+    select_list<<<blocks_for(num_samples), 256, 0, s>>>(sel, num_samples, n, in[0], in[1], in[2], dst[0], dst[1], dst[2], status);
+    KCHK(c);
+    TRY(cloud_out_back(c, dst, out, num_samples, mem_kind));
+    TRY(from_device(c, (const int64_t*)sel, out_idx, (size_t)num_samples, mem_kind));
+    HIPCHK(c, hipMemcpyAsync(c->u_host + 1, status, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (c->u_host[1]) return fail(c, MI_ICP_ERR_STATE, "%s: a selected index left [0, %lld)", what, (long long)n);
+    *m = num_samples;
+    return MI_ICP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// PointCloud::PassThroughFilter / Crop(AxisAlignedBoundingBox) / RemoveNoneFinitePoints (geometry/pointcloud.cu:40-54,
+// 108-120, 340-348, 360-385, 436-466): a flags kernel per predicate (select.h), then the scan and gather of the selections.
+}  // extern "C"
+
+template <class Flags>
+static int predicate_filter(mi_icp_ctx* c, const char* what, const float* xyz, const float* normals, const float* colors,
+                            int64_t n, float* out_xyz, float* out_normals, float* out_colors, int64_t* out_idx, int64_t* m,
+                            int mem_kind, Flags launch_flags) {
+    if (n == 0) return MI_ICP_OK;
+    if (!xyz || !out_xyz || (normals && !out_normals) || (colors && !out_colors))
+        return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+    const float* in[3];
+    TRY(to_device(c, xyz, (size_t)n * 3, mem_kind, c->stage[0], &in[0]));
+    TRY(to_device(c, normals, (size_t)n * 3, mem_kind, c->stage[1], &in[1]));
+    TRY(to_device(c, colors, (size_t)n * 3, mem_kind, c->stage[2], &in[2]));
+    uint32_t* flags;
+    TRY(ensure(c, c->flags, (size_t)n, &flags));
+    launch_flags(in[0], flags);
+    KCHK(c);
+    float* const out[3] = {out_xyz, out_normals, out_colors};
+    return compact_by_flags(c, flags, n, in, out, out_idx, mem_kind, nullptr, m, nullptr);
+}
+
+extern "C" {
+
+static int predicate_args(mi_icp_ctx* c, const char* what, int64_t n, int64_t* m, int mem_kind) {
+    TRY(check_ctx(c, mem_kind, what));
+    if (!m) return fail(c, MI_ICP_ERR_INVALID, "%s: m is null", what);
+    *m = 0;
+    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    return MI_ICP_OK;
+}
+
+int mi_icp_pass_through_filter(mi_icp_ctx* c, const float* xyz, const float* normals, const float* colors, int64_t n,
+                               int axis_no, float min_bound, float max_bound, float* out_xyz, float* out_normals,
+                               float* out_colors, int64_t* out_idx, int64_t* m, int mem_kind) {
+    const char* what = "pass_through_filter";
+    TRY(predicate_args(c, what, n, m, mem_kind));
+    if (axis_no < 0 || axis_no > 2) return fail(c, MI_ICP_ERR_INVALID, "%s: axis_no must be 0, 1 or 2", what);
+    return predicate_filter(c, what, xyz, normals, colors, n, out_xyz, out_normals, out_colors, out_idx, m, mem_kind,
+                            [&](const float* p, uint32_t* flags) {
+                                pass_through_flags<<<blocks_for(n), 256, 0, c->stream>>>(p, n, axis_no, min_bound, max_bound, flags);
+                            });
+}
+
+int mi_icp_crop_aabb(mi_icp_ctx* c, const float* xyz, const float* normals, const float* colors, int64_t n,
+                     const float* min_bound3, const float* max_bound3, float* out_xyz, float* out_normals,
+                     float* out_colors, int64_t* out_idx, int64_t* m, int mem_kind) {
+    const char* what = "crop_aabb";
+    TRY(predicate_args(c, what, n, m, mem_kind));
+    if (!min_bound3 || !max_bound3) return fail(c, MI_ICP_ERR_INVALID, "%s: null bounds", what);
+    CropBox b;
+    for (int k = 0; k < 3; ++k) {
+        b.lo[k] = min_bound3[k];
+        b.hi[k] = max_bound3[k];
+    }
+    // AxisAlignedBoundingBox::Volume() (the product of the extents, in fp32) must be positive
+    const float volume = ((b.hi[0] - b.lo[0]) * (b.hi[1] - b.lo[1])) * (b.hi[2] - b.lo[2]);
+    if (!(volume > 0.0f)) return fail(c, MI_ICP_ERR_INVALID, "%s: the bounding box is empty", what);
+    return predicate_filter(c, what, xyz, normals, colors, n, out_xyz, out_normals, out_colors, out_idx, m, mem_kind,
+                            [&](const float* p, uint32_t* flags) {
+                                crop_flags<<<blocks_for(n), 256, 0, c->stream>>>(p, n, b, flags);
+                            });
+}
+
+int mi_icp_remove_none_finite(mi_icp_ctx* c, const float* xyz, const float* normals, const float* colors, int64_t n,
+                              int remove_nan, int remove_infinite, float* out_xyz, float* out_normals, float* out_colors,
+                              int64_t* out_idx, int64_t* m, int mem_kind) {
+    const char* what = "remove_none_finite";
+    TRY(predicate_args(c, what, n, m, mem_kind));
+    return predicate_filter(c, what, xyz, normals, colors, n, out_xyz, out_normals, out_colors, out_idx, m, mem_kind,
+                            [&](const float* p, uint32_t* flags) {
+                                finite_flags<<<blocks_for(n), 256, 0, c->stream>>>(p, n, remove_nan, remove_infinite, flags);
+                            });
 }
 
 // ---------------------------------------------------------------------------

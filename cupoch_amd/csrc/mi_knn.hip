@@ -1,11 +1,13 @@
 // mi_knn.hip -- k-nearest-neighbour work on the target tree: PointCloud::EstimateNormals, KDTreeFlann::SearchKNN /
 // SearchRadius, Colored ICP's colour gradients and its registration entry, RemoveStatisticalOutliers /
-// RemoveRadiusOutliers, ClusterDBSCAN, ComputeISSKeypoints (knn_normals.h, select.h, dbscan.h, iss.h)
+// RemoveRadiusOutliers, ClusterDBSCAN, ComputeISSKeypoints, GaussianFilter (knn_normals.h, select.h, dbscan.h, iss.h,
+// gaussian_filter.h)
 // (one translation unit of libmi_icp.so; csrc/ctx.h lists them)
 #include <cstring>
 
 #include "ctx.h"
 #include "dbscan.h"
+#include "gaussian_filter.h"
 #include "iss.h"
 #include "knn_normals.h"
 #include "select.h"
@@ -348,6 +350,43 @@ int mi_icp_iss_keypoints(mi_icp_ctx* c, const float* xyz, int64_t n, float salie
     if (n == 0) return MI_ICP_OK;
     return iss_impl(c, what, xyz, n, salient_radius, non_max_radius, IssGates{min_neighbors, gamma_21, gamma_32},
                     max_neighbors, mask_out, saliency_out, eig_out, counts_out, radii_out, m, mem_kind);
+}
+
+// ---------------------------------------------------------------------------
+// PointCloud::GaussianFilter (geometry/pointcloud.cu:56-106, 387-434; gaussian_filter.h): one tree of the cloud in the
+// private scratch context, one launch, one wait.
+int mi_icp_gaussian_filter(mi_icp_ctx* c, const float* xyz, const float* normals, const float* colors, int64_t n,
+                           float search_radius, float sigma2, int num_max_search_points, float* out_xyz,
+                           float* out_normals, float* out_colors, int mem_kind) {
+    const char* what = "gaussian_filter";
+    TRY(check_ctx(c, mem_kind, what));
+    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    if (!(search_radius > 0.0f) || !(search_radius * search_radius < INFINITY))
+        return fail(c, MI_ICP_ERR_INVALID, "%s: search_radius must be positive, and finite when squared", what);
+    if (!(sigma2 > 0.0f) || !(sigma2 < INFINITY)) return fail(c, MI_ICP_ERR_INVALID, "%s: sigma2 must be positive and finite", what);
+    if (num_max_search_points < 1 || num_max_search_points > kKnnLimit)
+        return fail(c, MI_ICP_ERR_INVALID, "%s: num_max_search_points outside [1, %d] (knn::NUM_MAX_NN)", what, kKnnLimit);
+    if (n == 0) return MI_ICP_OK;
+    if (!xyz || !out_xyz || (normals && !out_normals) || (colors && !out_colors))
+        return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+    const int k = num_max_search_points;
+    return in_scratch(c, what, [&](mi_icp_ctx* a) -> int {
+        const float* in[3];
+        TRY(to_device(a, xyz, (size_t)n * 3, mem_kind, a->stage[0], &in[0]));
+        TRY(to_device(a, normals, (size_t)n * 3, mem_kind, a->stage[1], &in[1]));
+        TRY(to_device(a, colors, (size_t)n * 3, mem_kind, a->stage[2], &in[2]));
+        TRY(mi_icp_set_target(a, in[0], nullptr, nullptr, n, MI_ICP_DEVICE));
+        float* const out[3] = {out_xyz, out_normals, out_colors};
+        float* dst[3];
+        for (int e = 0; e < 3; ++e) TRY(out_slot(a, in[e] ? out[e] : nullptr, (size_t)n * 3, mem_kind, a->stage[3 + e], &dst[e]));
+        TRY(knn_launch(a, k, (uint32_t)((a->nleaf + 7) / 8), [](auto kc) { return gaussian_kernel<decltype(kc)::value>; },
+                       (const float*)a->nodes.p, (const float*)a->tblk.p, (const int32_t*)a->tidx.p, a->leaf_first, a->nts,
+                       a->nleaf, k, search_radius * search_radius, sigma2, in[0], in[1], in[2], dst[0], dst[1], dst[2]));
+        for (int e = 0; e < 3; ++e)
+            if (dst[e]) TRY(from_device(a, (const float*)dst[e], out[e], (size_t)n * 3, mem_kind));
+        HIPCHK(a, hipStreamSynchronize(a->stream));
+        return MI_ICP_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------

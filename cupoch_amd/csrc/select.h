@@ -13,6 +13,8 @@
 //   SelectByIndex: select_list (a gather in the order given) or, with invert, select_mark (flags start at 1, the named
 //                 indices clear theirs) and the same scan + select_gather.
 //   SelectByMask:  select_mask_flags (a byte per point -> the flags) and the same scan + select_gather.
+//   PassThroughFilter / Crop / RemoveNoneFinitePoints (geometry/pointcloud.cu:40-54, 108-120, 340-348):
+//                 pass_through_flags / crop_flags / finite_flags and the same scan + select_gather.
 // Every sum has a fixed order (per block, then the blocks in a fixed order): the same input gives the same threshold on
 // every run and every context.  Indices outside [0, n) are reported in a status word that comes back with the count.
 #pragma once
@@ -156,6 +158,41 @@ static __global__ __launch_bounds__(256) void select_mask_flags(const uint8_t* _
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     flags[i] = ((mask[i] != 0) != (invert != 0)) ? 1u : 0u;
+}
+
+// PassThroughFilter's flags: kept iff !(v < lo || hi < v), v = p[axis] -- a NaN coordinate is kept, as the reference's
+// comparison keeps it
+static __global__ __launch_bounds__(256) void pass_through_flags(const float* __restrict__ xyz, int64_t n, int axis, float lo,
+                                                                float hi, uint32_t* __restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float v = xyz[i * 3 + axis];
+    flags[i] = (v < lo || hi < v) ? 0u : 1u;
+}
+
+struct CropBox {
+    float lo[3], hi[3];
+};
+
+// Crop(AxisAlignedBoundingBox)'s flags: kept iff on all three axes !(p < lo || p > hi) -- bounds inclusive, NaN kept
+static __global__ __launch_bounds__(256) void crop_flags(const float* __restrict__ xyz, int64_t n, CropBox b,
+                                                        uint32_t* __restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float x = xyz[i * 3], y = xyz[i * 3 + 1], z = xyz[i * 3 + 2];
+    const bool out = (x < b.lo[0] || x > b.hi[0]) || (y < b.lo[1] || y > b.hi[1]) || (z < b.lo[2] || z > b.hi[2]);
+    flags[i] = out ? 0u : 1u;
+}
+
+// RemoveNoneFinitePoints' flags: dropped iff (remove_nan and a coordinate is NaN) or (remove_inf and one is +-inf)
+static __global__ __launch_bounds__(256) void finite_flags(const float* __restrict__ xyz, int64_t n, int remove_nan,
+                                                          int remove_inf, uint32_t* __restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float x = xyz[i * 3], y = xyz[i * 3 + 1], z = xyz[i * 3 + 2];
+    const bool has_nan = x != x || y != y || z != z;
+    const bool has_inf = fabsf(x) == INFINITY || fabsf(y) == INFINITY || fabsf(z) == INFINITY;
+    flags[i] = ((remove_nan && has_nan) || (remove_inf && has_inf)) ? 0u : 1u;
 }
 
 }  // namespace mi

@@ -479,6 +479,59 @@ class Engine:
         k = int(m.value)
         return self._trim(op, k), self._trim(on, k), self._trim(oc, k)
 
+    # -- FarthestPointDownSample / GaussianFilter / PassThroughFilter / Crop / RemoveNoneFinitePoints (pointcloud.cu)
+    def farthest_point_downsample(self, points, num_samples, normals=None, colors=None):
+        """PointCloud::FarthestPointDownSample (pointcloud.cu:122-139, 301-338; the contract is in include/mi_icp.h:
+        sel[0] = 0, ties to the lowest index).  Returns (points, normals or None, colors or None, indices int64
+        [num_samples] in selection order), on the side of `points`."""
+        p, n, c, kind = self._cloud_args(points, normals, colors)
+        rows = max(0, min(int(num_samples), p.n))
+        (op, pp), (on, pn), (oc, pc) = self._cloud_outputs(kind, p, n, c, rows)
+        idx, pidx = self._out(kind, p.device, (rows,), np.int64)
+        m = C.c_int64(0)
+        self._chk(self._L.mi_icp_farthest_point_downsample(self._ctx, p.ptr, n.ptr, c.ptr, p.n, int(num_samples),
+                                                           pp, pn, pc, pidx, C.byref(m), kind))
+        k = int(m.value)
+        return self._trim(op, k), self._trim(on, k), self._trim(oc, k), idx[:k]
+
+    def gaussian_filter(self, points, search_radius, sigma2, num_max_search_points=50, normals=None, colors=None):
+        """PointCloud::GaussianFilter (pointcloud.cu:56-106, 387-434; the contract is in include/mi_icp.h).  Returns
+        (points, normals or None, colors or None), one entry per input point."""
+        p, n, c, kind = self._cloud_args(points, normals, colors)
+        (op, pp), (on, pn), (oc, pc) = self._cloud_outputs(kind, p, n, c, p.n)
+        self._chk(self._L.mi_icp_gaussian_filter(self._ctx, p.ptr, n.ptr, c.ptr, p.n, float(search_radius), float(sigma2),
+                                                 int(num_max_search_points), pp, pn, pc, kind))
+        return op, on, oc
+
+    def _predicate_filter(self, points, normals, colors, call):
+        p, n, c, kind = self._cloud_args(points, normals, colors)
+        (op, pp), (on, pn), (oc, pc) = self._cloud_outputs(kind, p, n, c, p.n)
+        idx, pidx = self._out(kind, p.device, (p.n,), np.int64)
+        m = C.c_int64(0)
+        self._chk(call(p, n, c, pp, pn, pc, pidx, C.byref(m), kind))
+        k = int(m.value)
+        return self._trim(op, k), self._trim(on, k), self._trim(oc, k), idx[:k]
+
+    def pass_through_filter(self, points, axis_no, min_bound, max_bound, normals=None, colors=None):
+        """PointCloud::PassThroughFilter (pointcloud.cu:108-120, 436-466): kept iff !(v < min_bound || max_bound < v),
+        v = p[axis_no].  Returns (points, normals or None, colors or None, kept indices int64 ascending)."""
+        return self._predicate_filter(points, normals, colors, lambda p, n, c, *out: self._L.mi_icp_pass_through_filter(
+            self._ctx, p.ptr, n.ptr, c.ptr, p.n, int(axis_no), float(min_bound), float(max_bound), *out))
+
+    def crop_aabb(self, points, min_bound, max_bound, normals=None, colors=None):
+        """PointCloud::Crop(AxisAlignedBoundingBox) (pointcloud.cu:340-348): kept iff inside the closed box; an empty
+        box is an error.  Returns as pass_through_filter."""
+        lo = np.ascontiguousarray(np.asarray(min_bound, np.float32).reshape(3))
+        hi = np.ascontiguousarray(np.asarray(max_bound, np.float32).reshape(3))
+        return self._predicate_filter(points, normals, colors, lambda p, n, c, *out: self._L.mi_icp_crop_aabb(
+            self._ctx, p.ptr, n.ptr, c.ptr, p.n, lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), *out))
+
+    def remove_none_finite(self, points, remove_nan=True, remove_infinite=True, normals=None, colors=None):
+        """PointCloud::RemoveNoneFinitePoints (pointcloud.cu:40-54, 360-385) into new arrays.  Returns as
+        pass_through_filter."""
+        return self._predicate_filter(points, normals, colors, lambda p, n, c, *out: self._L.mi_icp_remove_none_finite(
+            self._ctx, p.ptr, n.ptr, c.ptr, p.n, int(bool(remove_nan)), int(bool(remove_infinite)), *out))
+
     def uniform_downsample(self, points, every_k_points, normals=None, colors=None):
         """PointCloud::UniformDownSample (down_sample.cu:275-316): points 0, k, 2k, ... (n // k of them)."""
         p, n, c, kind = self._cloud_args(points, normals, colors)

@@ -317,6 +317,69 @@ class PointCloud:
         p2, n2, c2, idx, _ = eng.remove_radius_outliers(self._points.tensor, int(nb_points), float(radius), n, c)
         return self._made(p2, n2, c2), utility.ULongVector(idx.clone())
 
+    # PointCloud::FarthestPointDownSample / GaussianFilter / PassThroughFilter / Crop / RemoveNoneFinitePoints ------
+    # (pointcloud.cu:40-139, 301-466; include/mi_icp.h states the contracts)
+    def farthest_point_down_sample(self, num_samples):
+        """num_samples points, each the farthest from those chosen before it; point 0 first, ties to the lowest index"""
+        num_samples = int(num_samples)
+        if num_samples == 0:
+            return PointCloud()
+        if num_samples < 0 or num_samples > len(self._points):
+            print("[cupoch_amd] Error: Illegal number of samples: %d, must <= point size: %d" % (num_samples, len(self._points)))
+            return PointCloud()
+        eng, n, c = self._engine_args()
+        return self._made(*eng.farthest_point_downsample(self._points.tensor, num_samples, n, c)[:3])
+
+    def gaussian_filter(self, search_radius, sigma2, num_max_search_points=50):
+        """every point, normal and colour replaced by the mean of its radius neighbours weighted with
+        exp(-0.5 d2 / sigma2); normals are not re-normalised"""
+        if not (search_radius > 0 and sigma2 > 0 and 1 <= int(num_max_search_points) <= 100):
+            print("[cupoch_amd] Error: [GaussianFilter] Illegal input parameters, radius and sigma2 must be positive.")
+            return PointCloud()         # (pointcloud.cu:390-395 logs and returns an empty cloud)
+        if not self.has_points():
+            return PointCloud()
+        eng, n, c = self._engine_args()
+        return self._made(*eng.gaussian_filter(self._points.tensor, float(search_radius), float(sigma2),
+                                               int(num_max_search_points), n, c))
+
+    def pass_through_filter(self, axis_no, min_bound, max_bound):
+        """the points whose coordinate axis_no lies in [min_bound, max_bound]"""
+        if int(axis_no) not in (0, 1, 2):
+            print("[cupoch_amd] Error: [PassThroughFilter] Illegal input parameters, axis_no must be 0, 1 or 2.")
+            return PointCloud()         # (pointcloud.cu:440-445)
+        if not self.has_points():
+            return PointCloud()
+        eng, n, c = self._engine_args()
+        return self._made(*eng.pass_through_filter(self._points.tensor, int(axis_no), float(min_bound), float(max_bound), n, c)[:3])
+
+    def crop(self, bounding_box):
+        """the points inside the closed AxisAlignedBoundingBox"""
+        if not isinstance(bounding_box, AxisAlignedBoundingBox):
+            raise TypeError("crop() takes an AxisAlignedBoundingBox (an OrientedBoundingBox is not supported)")
+        if not bounding_box.volume() > 0:
+            print("[cupoch_amd] Error: [CropPointCloud] AxisAlignedBoundingBox either has zeros size, or has wrong bounds.")
+            return PointCloud()
+        if not self.has_points():
+            return PointCloud()
+        eng, n, c = self._engine_args()
+        return self._made(*eng.crop_aabb(self._points.tensor, bounding_box.min_bound, bounding_box.max_bound, n, c)[:3])
+
+    def remove_none_finite_points(self, remove_nan=True, remove_infinite=True):
+        """drops, in place, the points with a NaN (remove_nan) or infinite (remove_infinite) coordinate, with their
+        normals and colours; returns self"""
+        if not self.has_points():
+            return self
+        eng, n, c = self._engine_args()
+        p2, n2, c2, _ = eng.remove_none_finite(self._points.tensor, bool(remove_nan), bool(remove_infinite), n, c)
+        self._points = utility.Vector3fVector(p2.clone())
+        if n2 is not None:
+            self._normals = utility.Vector3fVector(n2.clone())
+        if c2 is not None:
+            self._colors = utility.Vector3fVector(c2.clone())
+        if self._covariances is not None and len(self._covariances) != len(self._points):
+            self._covariances = None      # (the reference does not carry them either)
+        return self
+
     # PointCloud::ClusterDBSCAN (pointcloud_cluster.cu:109-179) ----------------------------------------------------
     def cluster_dbscan(self, eps, min_points, print_progress=False, max_edges=100):
         """an IntVector of one label per point: its cluster's number, or -1 for noise (include/mi_icp.h states the

@@ -277,6 +277,62 @@ MI_ICP_API int mi_icp_uniform_downsample(mi_icp_ctx* ctx, const float* xyz, cons
                                          const float* colors, int64_t n, int64_t every_k_points,
                                          float* out_xyz, float* out_normals, float* out_colors,
                                          int64_t* m, int mem_kind);
+/* PointCloud::FarthestPointDownSample(num_samples) (geometry/pointcloud.cu:122-139, 301-338).  Its
+ * contract, which the selection sel[0 .. num_samples) meets exactly:
+ *   sel[0] = 0; dist[i] = +inf for every point.
+ *   After choosing s = sel[t]:  dist[i] = min(dist[i], d2(i, s)) for every point, d2 = fma(dz, dz,
+ *   fma(dy, dy, dx*dx)) of the fp32 differences p_i - p_s, as everywhere in this header.
+ *   sel[t+1] = the index of the largest dist; TIES GO TO THE LOWEST INDEX.
+ * Deviation (deliberate): the reference reduces with "a > b ? a : b" under a thrust tree, which leaves
+ * ties to the order of the reduction -- its result is not a function of its input.  Lowest-first is
+ * the rule of Open3D's FarthestPointDownSample, from which the reference's descends.  A consequence:
+ * once every remaining dist is 0 (the cloud has fewer distinct points than samples asked for), the
+ * largest is 0 at index 0 and index 0 repeats, as a repeated index would in the reference.
+ * Outputs: the selected points, with normals / colours where given (either may be NULL), in selection
+ * order; out_idx (int64 [num_samples], may be NULL) = sel; *m = num_samples.  Outputs hold
+ * num_samples entries.  num_samples == 0 gives *m = 0; num_samples == n gives the cloud itself in
+ * input order (sel = 0, 1, ..., n-1), as the reference's early return does; num_samples > n (the
+ * reference logs an error) or < 0 is MI_ICP_ERR_INVALID.
+ * Non-finite coordinates are outside the contract (mi_icp_remove_none_finite comes first).  What
+ * happens: min is IEEE minNum, so a NaN d2 leaves dist as it is; a point with a non-finite coordinate
+ * keeps dist = +inf, and the lowest such index is chosen at every step after the first.  The call
+ * terminates and every index lies in [0, n).
+ * One launch per sample, all enqueued before the call's one wait on the context's stream: the chosen
+ * index and its coordinates never leave the device in between.  A maximum of integers has no
+ * summation order: the same input gives the same bytes on every run and context.  No tree is built;
+ * the caller's target / source / loop state are not touched.  Memory: 4 bytes per point. */
+MI_ICP_API int mi_icp_farthest_point_downsample(mi_icp_ctx* ctx, const float* xyz, const float* normals,
+                                                const float* colors, int64_t n, int64_t num_samples,
+                                                float* out_xyz, float* out_normals, float* out_colors,
+                                                int64_t* out_idx, int64_t* m, int mem_kind);
+/* The predicate filters of geometry::PointCloud.  Each gives the kept points, with normals / colours
+ * where given (either may be NULL), ascending in index; out_idx (int64, may be NULL) their original
+ * indices; *m their number.  Outputs hold n entries.  n = 0 gives *m = 0.  Each synchronises the
+ * context's stream.
+ *   PassThroughFilter(axis_no, min_bound, max_bound) (pointcloud.cu:108-120, 436-466): a point is kept
+ *     iff !(v < min_bound || max_bound < v), v = p[axis_no] -- so a NaN coordinate is kept, as the
+ *     reference's comparison keeps it, and so is every point when a bound is NaN.  axis_no outside
+ *     {0, 1, 2} is MI_ICP_ERR_INVALID.
+ *   Crop(AxisAlignedBoundingBox<3>) (pointcloud.cu:340-348, boundingvolume.cu:81-101): a point is kept
+ *     iff on all three axes !(p < min || p > max): the bounds are inclusive and a NaN coordinate is
+ *     kept, as in the reference.  An empty box -- Volume() = ((max0 - min0) * (max1 - min1)) *
+ *     (max2 - min2) in fp32 not > 0 -- is MI_ICP_ERR_INVALID (the reference logs an error).
+ *   RemoveNoneFinitePoints(remove_nan, remove_infinite) (pointcloud.cu:40-54, 360-385): a point is
+ *     DROPPED iff (remove_nan and a coordinate is NaN) or (remove_infinite and a coordinate is +-inf).
+ *     The reference works in place; this entry writes to outputs like its siblings, the C++ and
+ *     Python methods replace the cloud's own arrays. */
+MI_ICP_API int mi_icp_pass_through_filter(mi_icp_ctx* ctx, const float* xyz, const float* normals,
+                                          const float* colors, int64_t n, int axis_no, float min_bound,
+                                          float max_bound, float* out_xyz, float* out_normals,
+                                          float* out_colors, int64_t* out_idx, int64_t* m, int mem_kind);
+MI_ICP_API int mi_icp_crop_aabb(mi_icp_ctx* ctx, const float* xyz, const float* normals,
+                                const float* colors, int64_t n, const float* min_bound3,
+                                const float* max_bound3, float* out_xyz, float* out_normals,
+                                float* out_colors, int64_t* out_idx, int64_t* m, int mem_kind);
+MI_ICP_API int mi_icp_remove_none_finite(mi_icp_ctx* ctx, const float* xyz, const float* normals,
+                                         const float* colors, int64_t n, int remove_nan,
+                                         int remove_infinite, float* out_xyz, float* out_normals,
+                                         float* out_colors, int64_t* out_idx, int64_t* m, int mem_kind);
 /* PointCloud::CreateFromDepthImage and PointCloud::CreateFromRGBDImage
  * (geometry/pointcloud_factory.cu:43-110,117-220,286-376) incl. the
  * RemoveNoneFinitePoints pass that follows (geometry/pointcloud.cu:40-54,360-385):
@@ -561,6 +617,32 @@ MI_ICP_API int mi_icp_iss_keypoints(mi_icp_ctx* ctx, const float* xyz, int64_t n
                                     float non_max_radius, float gamma_21, float gamma_32, int min_neighbors,
                                     int max_neighbors, uint8_t* mask_out, float* saliency_out, float* eig_out,
                                     int32_t* counts_out, float* radii_out, int64_t* m, int mem_kind);
+
+/* PointCloud::GaussianFilter(search_radius, sigma2, num_max_search_points) (geometry/pointcloud.cu:
+ * 56-106, 387-434).  Its contract:
+ *   row(i)  row(i, search_radius) of mi_icp_iss_keypoints above with max_neighbors =
+ *           num_max_search_points: fp32 d2 < r*r, the smallest by (d2, index) when more, the point
+ *           itself among them.
+ *   w_j     exp(-0.5 * d2(i, j) / sigma2) in fp32, d2 the value the row was chosen by.
+ *   out(i)  sum over row(i) of w_j * p_j, divided by the sum of the w_j; likewise the normals and
+ *           colours where given (either may be NULL).  Normals are NOT re-normalised, as in the
+ *           reference.  The point itself has w = 1, so the divisor is at least 1, and a row that holds
+ *           the point alone returns it bit for bit (a coordinate of -0 comes back as +0: 0 + 1 * -0).
+ * Everything is fp32.  The order of the sums and the rounding of exp are left open (here: the row in
+ * the order the search left it, expf within 1 ulp); the same input gives the same bytes on every run
+ * and context.  Outputs hold n entries, in the input's order; the cloud keeps its size.
+ * Non-finite coordinates are outside the contract.  What happens: such a point is in no row, its
+ * own included (no d2 compares below r*r), and its outputs are NaN (0 / 0); the finite points'
+ * outputs are as if it were absent.  The call terminates.
+ * Limits, the reference's: search_radius > 0 with a finite square, sigma2 > 0 and finite,
+ * num_max_search_points in [1, 100] (knn::NUM_MAX_NN), n < 2^31; else MI_ICP_ERR_INVALID, before any
+ * buffer is touched.  n = 0 is MI_ICP_OK.  The cloud's tree is built in the private scratch context:
+ * the caller's target / source / loop state survive.  No row is written out: memory on top of the
+ * tree is the outputs.  Synchronises the context's stream once. */
+MI_ICP_API int mi_icp_gaussian_filter(mi_icp_ctx* ctx, const float* xyz, const float* normals,
+                                      const float* colors, int64_t n, float search_radius, float sigma2,
+                                      int num_max_search_points, float* out_xyz, float* out_normals,
+                                      float* out_colors, int mem_kind);
 
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
