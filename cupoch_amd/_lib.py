@@ -212,6 +212,7 @@ SIGNATURES = {
     "mi_icp_debug_get_leaf_regions": (_I, [_P, _P]),
     "mi_icp_debug_get_leaf_halos": (_I, [_P, _P]),
     "mi_icp_debug_eigen3": (_I, [_I, _P, _L, _P, _P, _P]),
+    "mi_icp_debug_odometry_image": (_I, [_P, _I, _I, _P, C.POINTER(_I), C.POINTER(_I)]),
 }
 
 _lib = None

@@ -114,6 +114,10 @@ struct mi_icp_ctx {
     float* f_host = nullptr;     // pinned, 16 floats
     uint32_t* u_host = nullptr;  // pinned, 16 + kWantSlots words ([0]: counts read back by the one-shot entry points, [16..]: the halo_want counter's words)
     void* od_host = nullptr;     // pinned OdState mirror (odometry), allocated on first use
+    // the last odometry call's images in stage[4] (mi_icp_debug_odometry_image): levels (0: no call yet), sizes and,
+    // per level, source colour / depth, target colour / depth, dx / dy colour, dx / dy depth
+    int od_levels = 0, od_lw[MI_ICP_ODOMETRY_MAX_LEVELS] = {}, od_lh[MI_ICP_ODOMETRY_MAX_LEVELS] = {};
+    const float* od_img[MI_ICP_ODOMETRY_MAX_LEVELS][8] = {};
 
     // ---- registration loop (device-resident, loop.h) ----
     mi::eng::DevBuf loop_dev, ticket;

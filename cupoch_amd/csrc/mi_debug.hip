@@ -1,5 +1,5 @@
 // mi_debug.hip -- include/mi_icp_debug.h: test-only entry points (sort, scan, traversal census, tree / region / halo
-// export, occupancy, the step's two solvers side by side)
+// export, occupancy, the step's two solvers side by side, the odometry's images)
 // (one translation unit of libmi_icp.so; csrc/ctx.h lists them)
 #include "ctx.h"
 #include <vector>
@@ -239,6 +239,20 @@ int mi_icp_debug_get_tree(mi_icp_ctx* c, int64_t* info5, float* records_out, flo
         HIPCHK(c, hipMemcpy2DAsync(leaf_lines_out + kLeafRegOffset, kLeafFloats * sizeof(float), c->tidx.p, kLeaf * sizeof(int32_t),
                                    kLeaf * sizeof(int32_t), (size_t)c->nleaf, hipMemcpyDeviceToHost, c->stream));
     }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MI_ICP_OK;
+}
+
+int mi_icp_debug_odometry_image(mi_icp_ctx* c, int level, int which, float* out, int* width, int* height) {
+    TRY(check_ctx(c));
+    if (c->od_levels <= 0) return fail(c, MI_ICP_ERR_INVALID, "debug_odometry_image: no odometry call has run on this context");
+    if (level < 0 || level >= c->od_levels || which < 0 || which > 7)
+        return fail(c, MI_ICP_ERR_INVALID, "debug_odometry_image: level %d / image %d out of range", level, which);
+    if (width) *width = c->od_lw[level];
+    if (height) *height = c->od_lh[level];
+    if (!out) return MI_ICP_OK;  // (the size only)
+    const size_t n = (size_t)c->od_lw[level] * c->od_lh[level];
+    HIPCHK(c, hipMemcpyAsync(out, c->od_img[level][which], n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MI_ICP_OK;
 }

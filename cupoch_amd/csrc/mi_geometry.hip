@@ -993,6 +993,7 @@ static int rgbd_odometry_impl(mi_icp_ctx* c, const float* source_color, const fl
                               double* information36, int mem_kind, bool weighted, const float* prev_twist6,
                               float* twist6) {
     TRY(check_ctx(c, mem_kind, "compute_rgbd_odometry"));
+    c->od_levels = 0;  // (mi_icp_debug_odometry_image: nothing to show until this call has run)
     if (twist6)
         for (int i = 0; i < 6; ++i) twist6[i] = 0.0f;
     if (!success || !transformation16 || !information36 || !intrinsic4 || !option)
@@ -1196,6 +1197,13 @@ static int rgbd_odometry_impl(mi_icp_ctx* c, const float* source_color, const fl
         std::memcpy(transformation16, hst->T.data(), 16 * sizeof(float));
         *success = 1;  // without its determinant check the solver never reports failure (utility/eigen.cu:76-122)
     }
+    for (int l = 0; l < L; ++l) {  // what mi_icp_debug_odometry_image hands out
+        c->od_lw[l] = lw[l];
+        c->od_lh[l] = lh[l];
+        const float* img[8] = {col[0][l], dep[0][l], col[1][l], dep[1][l], grad[0][l], grad[1][l], grad[2][l], grad[3][l]};
+        for (int k = 0; k < 8; ++k) c->od_img[l][k] = img[k];
+    }
+    c->od_levels = L;
     return MI_ICP_OK;
 }
 

@@ -663,6 +663,18 @@ class Engine:
             T.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p), MI_ICP_DEVICE if on_dev else MI_ICP_HOST))
         return bool(ok.value), T.reshape(4, 4).T.copy(), info.reshape(6, 6).copy()
 
+    def debug_odometry_image(self, level, which):
+        """One image of the last odometry call (include/mi_icp_debug.h: level 0 = full size; which = 0 source colour,
+        1 source depth, 2 target colour, 3 target depth, 4 dx colour, 5 dy colour, 6 dx depth, 7 dy depth) as a
+        float32 [h, w] array.  Test-only, and valid only directly after compute_rgbd_odometry on this engine: the
+        images live in scratch memory that other calls reuse."""
+        w, h = C.c_int(0), C.c_int(0)
+        self._chk(self._L.mi_icp_debug_odometry_image(self._ctx, int(level), int(which), None, C.byref(w), C.byref(h)))
+        out = np.empty((h.value, w.value), np.float32)
+        self._chk(self._L.mi_icp_debug_odometry_image(self._ctx, int(level), int(which), out.ctypes.data_as(C.c_void_p),
+                                                      C.byref(w), C.byref(h)))
+        return out
+
     def covariances_from_normals(self, normals, epsilon=1e-3):
         n = _Buf(normals, np.float32, 3, self.device)
         out, optr = self._out(n.kind, n.device, (n.n, 9))

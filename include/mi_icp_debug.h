@@ -81,6 +81,14 @@ MI_ICP_API int mi_icp_debug_solve_both(int device, const double* systems, int n,
  * gicp_weight compute them -- on the host (device < 0: the __host__ half of the same functions, no GPU needed) or in
  * a kernel on that device (the GPU's own acosf / cosf / sqrtf / divisions).  Any output may be NULL. */
 MI_ICP_API int mi_icp_debug_eigen3(int device, const float* A, int64_t n, float* eval, float* evec, float* S);
+/* One image of the LAST mi_icp_compute_[weighted_]rgbd_odometry call on the context, as its iterations read it: level
+ * 0 .. num_levels - 1 (0 = full size), which = 0 source colour, 1 source depth, 2 target colour, 3 target depth (Gaussian3,
+ * invalid depth NaN, colour scaled by NormalizeIntensity, downsampled per level), 4 dx colour, 5 dy colour, 6 dx depth,
+ * 7 dy depth (Sobel3Dx / Sobel3Dy of the target, unscaled).  *width x *height floats to out (host memory; NULL: the size
+ * only).  The images live in a scratch buffer that other entry points reuse: valid only DIRECTLY after the odometry
+ * call, before anything else runs on the context.  MI_ICP_ERR_INVALID when no odometry call has completed on the
+ * context or level / which is out of range. */
+MI_ICP_API int mi_icp_debug_odometry_image(mi_icp_ctx* ctx, int level, int which, float* out, int* width, int* height);
 /* The target's tree as built by mi_icp_set_target, for invariant tests.  info5 = {slots
  * (padded sorted positions), leaves, leaf_first (id of the first leaf-level node), records,
  * points}.  records_out (records * 64 floats: 8 child boxes as 4 sibling pairs of 12,

@@ -296,25 +296,34 @@ ORACLE_API void oracle_matrix4_to_vector6(const float *T, float *out) {
     }
 }
 
-/* odometry::ComputeRGBDOdometry and ComputeWeightedRGBDOdometry (odometry.cu:498-528
- * InitializeRGBDOdometry, :584-631 DoSingleIteration, :633-706 DoSingleIterationWeighted over
- * utility/eigen.inl:147-195 ComputeWeightedJTJandJTr, :708-831 ComputeMultiscale[Weighted],
- * :371-394 CreateInformationMatrix, :833-879 ComputeRGBDOdometryT).  color / depth: float images
- * w x h; intrinsic4 = fx, fy, cx, cy; odo_init, trans_out: column-major 4x4; iterations[l]:
- * coarsest level first (iteration_number_per_pyramid_level_); info_out: row-major 6x6.
- * weighted != 0 (always the hybrid term, :937-941): the t-distribution weights -- w_sum = sum over
- * correspondences of r2 (nu+1) / (nu + r2 / sigma2) with r2 the correspondence's squared residual,
- * weight = (nu+1) / (nu + r2 / w_sum), sigma2 <- w_sum -- plus the motion prior
- * inv_sigma_diag . (prev_twist - current velocity); twist_out = the velocity at the end.
- * Returns is_success (failure: identity transformation and identity information, :876-878). */
-static int od_core(const float *src_color, const float *src_depth, const float *tgt_color, const float *tgt_depth,
-                   int w, int h, const float *intrinsic4, const float *odo_init, int hybrid, const int *iterations,
-                   int num_levels, float max_depth_diff, float min_depth, float max_depth, int weighted, float nu,
-                   float sigma2_init, const float *inv_sigma_diag, const float *prev_twist, float *trans_out,
-                   float *twist_out, double *info_out) {
-    const size_t n0 = (size_t)w * h;
+/* The images of a call, per level l (lw[l] x lh[l]): colour and depth of both frames (s = 0 source, 1 target)
+ * and the target's four Sobel images. */
+typedef struct {
+    int L, lw[8], lh[8];
     float *col[2][8], *dep[2][8];
-    int lw[8], lh[8];
+    float *grad[4][8]; /* dx colour, dy colour, dx depth, dy depth */
+} od_images_t;
+
+static void od_images_free(od_images_t *im) {
+    for (int l = 0; l < im->L; ++l) {
+        for (int s = 0; s < 2; ++s) {
+            free(im->col[s][l]);
+            free(im->dep[s][l]);
+        }
+        for (int g = 0; g < 4; ++g) free(im->grad[g][l]);
+    }
+}
+
+/* The front half of a call: InitializeRGBDOdometry (odometry.cu:498-528: PreprocessDepth, Gaussian3 of all four
+ * images, NormalizeIntensity over the correspondences under odo_init), the pyramids and, per level, Sobel3Dx /
+ * Sobel3Dy of the target (RGBDImage::FilterPyramid). */
+static void od_build_images(const float *src_color, const float *src_depth, const float *tgt_color,
+                            const float *tgt_depth, int w, int h, const float *K0, const float *odo_init,
+                            int num_levels, float max_depth_diff, float min_depth, float max_depth, od_images_t *im) {
+    const size_t n0 = (size_t)w * h;
+    float *(*col)[8] = im->col, *(*dep)[8] = im->dep;
+    int *lw = im->lw, *lh = im->lh;
+    im->L = num_levels;
     /* InitializeRGBDOdometry */
     for (int s = 0; s < 2; ++s) {
         col[s][0] = (float *)malloc(sizeof(float) * n0);
@@ -326,9 +335,8 @@ static int od_core(const float *src_color, const float *src_depth, const float *
         oracle_od_filter(d, w, h, 0, dep[s][0]);
         free(d);
     }
-    float K0[9] = {intrinsic4[0], 0, intrinsic4[2], 0, intrinsic4[1], intrinsic4[3], 0, 0, 1};
-    int32_t *corr = (int32_t *)malloc(sizeof(int32_t) * 4 * n0);
     {   /* NormalizeIntensity (:416-436) */
+        int32_t *corr = (int32_t *)malloc(sizeof(int32_t) * 4 * n0);
         const int64_t nc = oracle_od_correspondence(K0, odo_init, dep[0][0], dep[1][0], w, h, max_depth_diff, corr);
         double ms = 0.0, mt = 0.0;
         for (int64_t i = 0; i < nc; ++i) {
@@ -341,6 +349,7 @@ static int od_core(const float *src_color, const float *src_depth, const float *
             col[0][0][i] = sc_s * col[0][0][i] + 0.0f;
             col[1][0][i] = sc_t * col[1][0][i] + 0.0f;
         }
+        free(corr);
     }
     /* pyramids: colour Gaussian3 + Downsample, depth Downsample only (rgbdimage.cu:96-112,
      * image_factory.cu:251-278) */
@@ -359,6 +368,58 @@ static int od_core(const float *src_color, const float *src_depth, const float *
             oracle_od_downsample(dep[s][l - 1], lw[l - 1], lh[l - 1], dep[s][l]);
         }
     }
+    for (int l = 0; l < num_levels; ++l)
+        for (int g = 0; g < 4; ++g) {
+            im->grad[g][l] = (float *)malloc(sizeof(float) * (size_t)lw[l] * lh[l]);
+            oracle_od_filter(g < 2 ? col[1][l] : dep[1][l], lw[l], lh[l], 1 + (g & 1), im->grad[g][l]);
+        }
+}
+
+/* The images of a call as od_core sees them: out[l * 8 + which] receives level l's image `which` (0 source colour,
+ * 1 source depth, 2 target colour, 3 target depth, 4 dx colour, 5 dy colour, 6 dx depth, 7 dy depth), each
+ * (w >> l) x (h >> l) floats, where the pointer is not NULL. */
+ORACLE_API void oracle_od_images(const float *src_color, const float *src_depth, const float *tgt_color,
+                                 const float *tgt_depth, int w, int h, const float *intrinsic4, const float *odo_init,
+                                 int num_levels, float max_depth_diff, float min_depth, float max_depth,
+                                 float *const *out) {
+    const float K0[9] = {intrinsic4[0], 0, intrinsic4[2], 0, intrinsic4[1], intrinsic4[3], 0, 0, 1};
+    od_images_t im;
+    od_build_images(src_color, src_depth, tgt_color, tgt_depth, w, h, K0, odo_init, num_levels, max_depth_diff, min_depth,
+                    max_depth, &im);
+    for (int l = 0; l < num_levels; ++l) {
+        const size_t bytes = sizeof(float) * (size_t)im.lw[l] * im.lh[l];
+        float *const img[8] = {im.col[0][l], im.dep[0][l], im.col[1][l], im.dep[1][l],
+                               im.grad[0][l], im.grad[1][l], im.grad[2][l], im.grad[3][l]};
+        for (int k = 0; k < 8; ++k)
+            if (out[l * 8 + k]) memcpy(out[l * 8 + k], img[k], bytes);
+    }
+    od_images_free(&im);
+}
+
+/* odometry::ComputeRGBDOdometry and ComputeWeightedRGBDOdometry (odometry.cu:498-528
+ * InitializeRGBDOdometry, :584-631 DoSingleIteration, :633-706 DoSingleIterationWeighted over
+ * utility/eigen.inl:147-195 ComputeWeightedJTJandJTr, :708-831 ComputeMultiscale[Weighted],
+ * :371-394 CreateInformationMatrix, :833-879 ComputeRGBDOdometryT).  color / depth: float images
+ * w x h; intrinsic4 = fx, fy, cx, cy; odo_init, trans_out: column-major 4x4; iterations[l]:
+ * coarsest level first (iteration_number_per_pyramid_level_); info_out: row-major 6x6.
+ * weighted != 0 (always the hybrid term, :937-941): the t-distribution weights -- w_sum = sum over
+ * correspondences of r2 (nu+1) / (nu + r2 / sigma2) with r2 the correspondence's squared residual,
+ * weight = (nu+1) / (nu + r2 / w_sum), sigma2 <- w_sum -- plus the motion prior
+ * inv_sigma_diag . (prev_twist - current velocity); twist_out = the velocity at the end.
+ * Returns is_success (failure: identity transformation and identity information, :876-878). */
+static int od_core(const float *src_color, const float *src_depth, const float *tgt_color, const float *tgt_depth,
+                   int w, int h, const float *intrinsic4, const float *odo_init, int hybrid, const int *iterations,
+                   int num_levels, float max_depth_diff, float min_depth, float max_depth, int weighted, float nu,
+                   float sigma2_init, const float *inv_sigma_diag, const float *prev_twist, float *trans_out,
+                   float *twist_out, double *info_out) {
+    const size_t n0 = (size_t)w * h;
+    const float K0[9] = {intrinsic4[0], 0, intrinsic4[2], 0, intrinsic4[1], intrinsic4[3], 0, 0, 1};
+    od_images_t im;
+    od_build_images(src_color, src_depth, tgt_color, tgt_depth, w, h, K0, odo_init, num_levels, max_depth_diff, min_depth,
+                    max_depth, &im);
+    float *(*col)[8] = im.col, *(*dep)[8] = im.dep;
+    const int *lw = im.lw, *lh = im.lh;
+    int32_t *corr = (int32_t *)malloc(sizeof(int32_t) * 4 * n0);
     float T[16];
     {   /* extrinsic_initial.isZero() ? Identity : extrinsic_initial (:722-724) */
         int zero = 1;
@@ -381,13 +442,9 @@ static int od_core(const float *src_color, const float *src_depth, const float *
         const int W = lw[level], H = lh[level];
         const size_t n = (size_t)W * H;
         float *xyz = (float *)malloc(sizeof(float) * 3 * n);
-        float *dxc = (float *)malloc(sizeof(float) * n), *dyc = (float *)malloc(sizeof(float) * n);
-        float *dxd = (float *)malloc(sizeof(float) * n), *dyd = (float *)malloc(sizeof(float) * n);
+        const float *dxc = im.grad[0][level], *dyc = im.grad[1][level];
+        const float *dxd = im.grad[2][level], *dyd = im.grad[3][level];
         depth_to_xyz(dep[0][level], W, H, Kl[level], xyz);
-        oracle_od_filter(col[1][level], W, H, 1, dxc);
-        oracle_od_filter(dep[1][level], W, H, 1, dxd);
-        oracle_od_filter(col[1][level], W, H, 2, dyc);
-        oracle_od_filter(dep[1][level], W, H, 2, dyd);
         for (int iter = 0; iter < iterations[num_levels - level - 1] && ok; ++iter) {
             const int64_t nc =
                     oracle_od_correspondence(Kl[level], T, dep[0][level], dep[1][level], W, H, max_depth_diff, corr);
@@ -439,10 +496,6 @@ static int od_core(const float *src_color, const float *src_depth, const float *
             if (ok) mul4(upd, T, T);
         }
         free(xyz);
-        free(dxc);
-        free(dyc);
-        free(dxd);
-        free(dyd);
     }
     memset(trans_out, 0, sizeof(float) * 16);
     trans_out[0] = trans_out[5] = trans_out[10] = trans_out[15] = 1.0f;
@@ -467,11 +520,7 @@ static int od_core(const float *src_color, const float *src_depth, const float *
         }
         free(xyz_t);
     }
-    for (int l = 0; l < num_levels; ++l)
-        for (int s = 0; s < 2; ++s) {
-            free(col[s][l]);
-            free(dep[s][l]);
-        }
+    od_images_free(&im);
     free(corr);
     return ok;
 }

@@ -461,6 +461,25 @@ def od_jacobian(hybrid, row, corr, source_color, target_color, target_depth, sou
     return J0, float(r0.value), J1, float(r1.value)
 
 
+OD_IMAGES = ("source colour", "source depth", "target colour", "target depth", "dx colour", "dy colour", "dx depth",
+             "dy depth")
+
+
+def od_images(src_color, src_depth, tgt_color, tgt_depth, K4, odo_init=None, num_levels=3, min_depth=0.0,
+              max_depth=4.0, max_depth_diff=0.03):
+    """The images a call works on (preprocess, Gaussian3, NormalizeIntensity under odo_init, pyramids, the target's
+    Sobel images): a list over the levels of {which: array}, which = the index into OD_IMAGES"""
+    sc, sd, tc, td = _f32(src_color), _f32(src_depth), _f32(tgt_color), _f32(tgt_depth)
+    h, w = sc.shape
+    init = np.eye(4, dtype=np.float32) if odo_init is None else odo_init
+    levels = [{k: np.empty((h >> l, w >> l), np.float32) for k in range(8)} for l in range(num_levels)]
+    out = (C.c_void_p * (8 * num_levels))(*[_p(levels[l][k]) for l in range(num_levels) for k in range(8)])
+    lib().oracle_od_images(_p(sc), _p(sd), _p(tc), _p(td), C.c_int(w), C.c_int(h),
+                           _p(_f32(np.asarray(K4, np.float32))), _p(_T_in(init)), C.c_int(num_levels),
+                           C.c_float(max_depth_diff), C.c_float(min_depth), C.c_float(max_depth), out)
+    return levels
+
+
 def compute_rgbd_odometry(src_color, src_depth, tgt_color, tgt_depth, intrinsic4, odo_init=None,
                           jacobian=OD_HYBRID_TERM, iterations=(20, 10, 5), max_depth_diff=0.03, min_depth=0.0,
                           max_depth=4.0):

@@ -83,6 +83,22 @@ def test_python_surface_and_errors(eng, frames):
         eng.compute_rgbd_odometry(cb, db, ca, da, K, None, 5)                      # unknown jacobian
     with pytest.raises(MiIcpError):
         eng.compute_rgbd_odometry(cb, db, ca, da, K, None, 1, iterations=(1,) * 9)  # too many levels
+    # the debug view of the last call's images (include/mi_icp_debug.h): nothing to show before a call or after a
+    # refused one, and no level or image outside the last call's
+    from cupoch_amd.engine import Engine
+    fresh = Engine(0)
+    try:
+        with pytest.raises(MiIcpError):
+            fresh.debug_odometry_image(0, 0)                                      # no odometry call yet
+    finally:
+        fresh.close()
+    with pytest.raises(MiIcpError):
+        eng.debug_odometry_image(0, 0)                                            # the call above was refused
+    assert eng.compute_rgbd_odometry(cb, db, ca, da, K, None, 1, (1, 1), 0.03, 0.0, 6.0)[0]
+    assert eng.debug_odometry_image(1, 3).shape == (120, 160)
+    for level, which in ((2, 0), (-1, 0), (0, 8), (0, -1)):
+        with pytest.raises(MiIcpError):
+            eng.debug_odometry_image(level, which)                                # bad level or which
 
 
 def test_weighted_odometry_matches_oracle(eng, frames):

@@ -300,6 +300,91 @@ def test_weighted_odometry_and_twist_conversion():
     assert np.linalg.norm(T2 - np.eye(4)) < np.linalg.norm(T - np.eye(4))
 
 
+@pytest.mark.parametrize("c", [(7, 5, 1), (16, 16, 3), (193, 128, 2), (323, 243, 3)], ids=lambda c: "%dx%d_L%d" % c)
+@pytest.mark.parametrize("init", ["identity", "small"])
+def test_od_images_is_the_composition_of_the_public_pieces(c, init):
+    """od_core's front half (oracle_od_images) = PreprocessDepth in numpy, od_filter, the mean scaling of NormalizeIntensity in
+    numpy over od_correspondence's list, od_filter + od_downsample per level, od_filter 1 / 2 of the target: bit for bit"""
+    import odometry_exact as oe
+    w, h, L = c
+    ref = oe.case(w, h, L, init)
+    cs, ds, ct, dt = ref["frames"]
+    K, T0 = ref["K"], ref["T0"]
+
+    def preprocess(d):
+        d = d.copy()
+        with np.errstate(invalid="ignore"):
+            d[(d < np.float32(oe.MIN_DEPTH)) | (d > np.float32(oe.MAX_DEPTH)) | (d <= 0)] = np.nan
+        return d
+
+    col = [orc.od_filter(cs, 0), orc.od_filter(ct, 0)]
+    dep = [orc.od_filter(preprocess(ds), 0), orc.od_filter(preprocess(dt), 0)]
+    corr = orc.od_correspondence([[K[0], 0, K[2]], [0, K[1], K[3]], [0, 0, 1]], T0, dep[0], dep[1], oe.MAX_DEPTH_DIFF)
+    assert len(corr) == ref["count"] > 0
+    for s, (x, y) in enumerate(((corr[:, 0], corr[:, 1]), (corr[:, 2], corr[:, 3]))):
+        total = np.cumsum(col[s][y, x].astype(np.float64))[-1]                    # one after the other, in list order
+        mean = np.float32(total) / np.float32(len(corr))
+        scale = np.float32(0.5 / np.float64(mean))
+        col[s] = scale * col[s] + np.float32(0.0)
+        assert col[s].dtype == np.float32
+    for level in range(L):
+        if level:
+            col = [orc.od_downsample(orc.od_filter(a, 0)) for a in col]
+            dep = [orc.od_downsample(a) for a in dep]
+        mine = {0: col[0], 1: dep[0], 2: col[1], 3: dep[1], 4: orc.od_filter(col[1], 1), 5: orc.od_filter(col[1], 2),
+                6: orc.od_filter(dep[1], 1), 7: orc.od_filter(dep[1], 2)}
+        for which in range(8):
+            assert mine[which].shape == (h >> level, w >> level)
+            diff = oe.same_bits(ref["images"][level][which], mine[which])
+            assert diff is None, (level, orc.OD_IMAGES[which], diff)
+        assert np.isnan(dep[0]).any() and not np.isnan(col[0]).any()
+
+
+def test_od_filters_against_an_fp64_restatement():
+    """Gaussian3 on random floats (all terms positive: fp32 loses a few ulps); both Sobels on an image of small integers,
+    where fp32 is exact and a difference of neighbours cannot cancel into its own rounding error -- and on which a swap
+    of the two axes shows (the image is not symmetric)"""
+    rng = np.random.default_rng(3)
+    h, w = 19, 26
+
+    def sep(img, kx, ky):
+        pad = np.pad(img.astype(np.float64), 1, mode="edge")
+        return sum(ky[j] * sum(kx[i] * pad[j:j + h, i:i + w] for i in range(3)) for j in range(3))
+
+    g3, s1, s2 = [0.25, 0.5, 0.25], [-1.0, 0.0, 1.0], [1.0, 2.0, 1.0]
+    img = rng.random((h, w), dtype=np.float32)
+    np.testing.assert_allclose(orc.od_filter(img, 0), sep(img, g3, g3), rtol=1e-6)
+    ints = rng.integers(0, 256, (h, w)).astype(np.float32)
+    dx, dy = sep(ints, s1, s2), sep(ints, s2, s1)
+    assert np.abs(dx - dy).max() > 100
+    np.testing.assert_allclose(orc.od_filter(ints, 1), dx, rtol=1e-6)
+    np.testing.assert_allclose(orc.od_filter(ints, 2), dy, rtol=1e-6)
+
+
+def test_odometry_results_are_those_recorded_before_od_images_was_split_off():
+    """tests/golden/odometry_oracle_parent.npz: what compute_rgbd_odometry / compute_weighted_rgbd_odometry returned for these
+    two calls before od_core's front half became a function of its own.  Bit for bit."""
+    import os
+    from conftest import ROOT, render_rgbd, small_pose
+    g = np.load(os.path.join(ROOT, "tests", "golden", "odometry_oracle_parent.npz"))
+    pose = small_pose(0.02, 0.03)
+    with np.errstate(invalid="ignore"):
+        K = [65.6, 65.6, 39.5, 29.5]
+        ca, da = render_rgbd(80, 60, K, np.eye(4), holes=0.02, seed=1)
+        cb, db = render_rgbd(80, 60, K, pose, holes=0.02, seed=2)
+        for jac in (0, 1):
+            ok, T, info = orc.compute_rgbd_odometry(cb, db, ca, da, K, jacobian=jac, iterations=(3, 2, 1), max_depth=6.0)
+            assert ok and T.tobytes() == g["plain_T_%d" % jac].tobytes() and info.tobytes() == g["plain_info_%d" % jac].tobytes()
+        K = [66.4, 66.4, 40.0, 30.0]
+        ca, da = render_rgbd(81, 61, K, np.eye(4), holes=0.02, seed=3)
+        cb, db = render_rgbd(81, 61, K, pose, holes=0.02, seed=4)
+    ok, T, tw, info = orc.compute_weighted_rgbd_odometry(
+        cb, db, ca, da, K, odo_init=small_pose(0.01, 0.01), prev_twist=orc.matrix4_to_vector6(pose), iterations=(2, 2),
+        max_depth=6.0, nu=3.0, sigma2_init=0.5, inv_sigma_mat_diag=[500.0] * 6)
+    assert ok and T.tobytes() == g["weighted_T"].tobytes() and tw.tobytes() == g["weighted_twist"].tobytes()
+    assert info.tobytes() == g["weighted_info"].tobytes()
+
+
 def _kabsch_numpy_fp64(src32, tgt32):
     """registration/kabsch.cu:74-118 in fp64 with numpy's SVD: R = V diag(1, 1, det(U V)) U^T, t = ct - R cs"""
     S, G = src32.astype(np.float64), tgt32.astype(np.float64)
