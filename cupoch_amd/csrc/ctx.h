@@ -89,6 +89,11 @@ struct mi_icp_ctx {
     mi::eng::DevBuf alt[9];  // second set of the source arrays (match-order re-sort ping-pong)
     bool inv_s_valid = false;
     bool nn_valid = false;  // nn_idx holds a search result (usable as seed / correspondences)
+    // THE SEARCH SKIP (nn_search.h): one limit on the loop's odometer per packet of 64 source points, left by the loop's
+    // seeded searches.  Whatever rewrites nn_idx, re-forms the packets or starts another odometer calls drop_expiry.
+    mi::eng::DevBuf expiry;
+    bool expiry_live = false;  // the array may hold limits (else: NaN -- all ones -- or -inf throughout: no odometer reading is below either)
+    float skip_r2 = NAN;       // the squared radius those limits were measured against; NaN: none on record
     mi::eng::DevBuf src_bounds;    // min[3], max[3] of the staged source (the loop's step sizes the displacement of its corners: loop.h)
     bool relocate_armed = false;   // this loop's next chunk of iterations carries the gated re-location launches (loop_run)
     bool relocate_possible = false;  // ... this loop's step sizes its displacement (loop_begin): the launches may be armed again
@@ -263,6 +268,33 @@ int from_device(mi_icp_ctx* c, const T* dev, T* dst, size_t count, int mem_kind)
                                                        : hipMemcpyDeviceToHost,
                              c->stream));
     return MI_ICP_OK;
+}
+
+// The per-packet limits of the search skip are void from here on: nothing is skipped until a seeded search of a loop
+// has left new ones.
+inline int drop_expiry(mi_icp_ctx* c) {
+    c->skip_r2 = NAN;
+    if (c->expiry_live && c->expiry.p) HIPCHK(c, hipMemsetAsync(c->expiry.p, 0xff, c->expiry.bytes, c->stream));
+    c->expiry_live = false;
+    return MI_ICP_OK;
+}
+
+// The loop state's live[] hint (loop.h) samples one packet in 2^shift, 64 at most.
+inline uint32_t skip_live_shift(int64_t ns) {
+    uint32_t shift = 0;
+    while ((((ns + 63) / 64) >> (shift + 1)) >= 64) ++shift;
+    return shift;
+}
+// Does gating the loop's next seeded search pay?  By the sample as of the host's last look at the loop state: at least
+// a quarter of the sampled packets hold a limit.  The gated launch runs kSkipRun packets per wave one after the other:
+// forced on, it costs a loop whose searches skip nothing 3 % (noisy, converged) to 12 % (transient) -- EXPERIMENTS.md;
+// a quarter of the packets skipped is a quarter of the search saved, well clear of that.
+inline bool skip_pays(const mi_icp_ctx* c) {
+    if (!c->loop_host || c->ns <= 0) return false;
+    const int64_t samples = std::min<int64_t>(64, ((c->ns + 63) / 64) >> skip_live_shift(c->ns));
+    int64_t held = 0;
+    for (int64_t k = 0; k < samples; ++k) held += c->loop_host->live[k] ? 1 : 0;
+    return samples > 0 && held * 4 >= samples;
 }
 
 inline int blocks_for(int64_t n, int per = 256) { return (int)std::max<int64_t>(1, (n + per - 1) / per); }

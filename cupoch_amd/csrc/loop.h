@@ -50,6 +50,17 @@ struct DevLoop {
     int32_t error;       // != 0: the ranks' exchange failed (mailbox.h); the loop is finished, its result void
     int32_t relocate;    // the step just taken moved the source by more than about a leaf's width
     int32_t relocations; // steps of this loop that did
+    // THE SEARCH SKIP (nn_search.h "the skip").  `travel`: an ODOMETER -- the sum, over the updates applied so far,
+    // of the largest distance an update moved a point of the source's box (x -> A'x - Ax is affine, its norm convex:
+    // the largest is at one of the 8 corners), formed in fp64 from the two fp32 matrices the searches actually read and
+    // rounded up.  The difference between its readings at two searches bounds how far ANY source point's exact position
+    // A p moved in between (triangle inequality).  +inf where the box is unknown (`sized` below).  `fuzz`: how far the
+    // fp32 query xform_point computes under the present A may lie from that exact position (derivation at the step).
+    double travel;
+    double fuzz;
+    // the host's hint (ctx.h skip_pays): did sampled packet k -- one in 2^shift, 64 at most -- get a limit when it was last
+    // searched?  Written by the searches (plain byte stores, a packet each), carried through the step untouched.
+    uint8_t live[64];
     host::Mat4 T;        // reported transformation (column-major)
     host::Mat4 A;        // applied transformation (differs from T only by an ~identity init)
     double sys[32];      // the reduced (and all-reduced) system of the last evaluation
@@ -92,6 +103,11 @@ __host__ __device__ inline void stats_from_system(const double* sys, int64_t n_s
     }
     *fitness = (float)count / (float)n_source;
     *rmse = sqrtf((float)sys[28] / (float)count);
+}
+
+// row r of the affine map M applied to (x, y, z), in fp64 (the products of two fp32 values are exact there)
+__host__ __device__ inline double affine_row(const host::Mat4& M, int r, double x, double y, double z) {
+    return (double)host::at(M, r, 0) * x + (double)host::at(M, r, 1) * y + (double)host::at(M, r, 2) * z + (double)host::at(M, r, 3);
 }
 
 // element i of a register-held array (compile-time indexing only)
@@ -213,6 +229,21 @@ __device__ __forceinline__ void loop_step_block(DevLoop* st_g, const double* sys
     // (everything this needs from memory is asked for BEFORE the barrier, beside the solve: a load behind it was 2 us on
     // every step's critical path -- 6 % of an 8-way shard's)
     if (wid == 2 && lane == 0 && sized) far2 = (kRelocateNears * kRelocateNears) * *reinterpret_cast<const float*>(st->near2_ptr);
+    if (wid == 2 && lane == 0 && !sized) st->travel = INFINITY;  // no box, no bound: nothing is ever skipped
+    // (the odometer, wave 0's lanes 32..39: a corner of the source's box each and where the present A puts it)
+    const bool odo = wid == 0 && lane >= 32 && lane < 40 && sized;
+    double blo[3] = {0.0, 0.0, 0.0}, bhi[3] = {0.0, 0.0, 0.0}, bc[3] = {0.0, 0.0, 0.0}, was[3] = {0.0, 0.0, 0.0};
+    if (odo) {
+        const float* sb = reinterpret_cast<const float*>(st->src_bounds_ptr);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            blo[k] = (double)sb[k];
+            bhi[k] = (double)sb[3 + k];
+            bc[k] = ((lane >> k) & 1) ? bhi[k] : blo[k];
+        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r) was[r] = affine_row(st->A, r, bc[0], bc[1], bc[2]);
+    }
     if (wid == 2 && lane < 8 && sized) {
         const float* sb = reinterpret_cast<const float*>(st->src_bounds_ptr);
         const float px = sb[(lane & 1) ? 3 : 0], py = sb[(lane & 2) ? 4 : 1], pz = sb[(lane & 4) ? 5 : 2];
@@ -280,6 +311,41 @@ __device__ __forceinline__ void loop_step_block(DevLoop* st_g, const double* sys
         else if (lane < 32) st->A.m[lane - 16] = sum;
         __builtin_amdgcn_wave_barrier();
         if (lane < 12) reinterpret_cast<float*>(&st->X)[lane] = host::at(st->A, lane >> 2, lane & 3);
+        if (sized) {  // (uniform) the odometer: how far has the update moved the corners, A' p against A p?
+            double d2 = 0.0;
+            if (odo) {
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const double d = affine_row(st->A, r, bc[0], bc[1], bc[2]) - was[r];
+                    d2 += d * d;
+                }
+            }
+            d2 = fmax(d2, __shfl_xor(d2, 1, 64));
+            d2 = fmax(d2, __shfl_xor(d2, 2, 64));
+            d2 = fmax(d2, __shfl_xor(d2, 4, 64));
+            if (lane == 32) {
+                // S[r] = sum_k |A[r][k]| max|p_k| + |t_r| over the box bounds every term of xform_point's row r:
+                //   q_r = fl(fl(fma(A_r2, z, fl(fma(A_r1, y, fl(A_r0 * x))))) + t_r)
+                // is four roundings to nearest, each at most u = 2^-24 of its own result, and every result is at most S[r]:
+                // |q_r - (A p)_r| <= ((1 + u)^4 - 1) S[r] < 4.0001 u S[r], in norm at most that of |S|.
+                double S[3], s1 = 0.0, s2 = 0.0;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    S[r] = fabs((double)host::at(st->A, r, 3));
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) S[r] += fabs((double)host::at(st->A, r, k)) * fmax(fabs(blo[k]), fabs(bhi[k]));
+                    s1 += S[r];
+                    s2 += S[r] * S[r];
+                }
+                st->fuzz = 0x1.001p-22 * sqrt(s2);
+                // (rounded up: the fp64 evaluation above is good to 2^-50 of the terms' sizes, its square root to 2^-52.  An
+                // update that leaves A as it is -- a failed determinant check -- adds nothing.)
+                // (the sum's own rounding, 2^-53 of the odometer per update, is inside the 2^-48 s1 while the odometer is below
+                // 32 times the box's reach s1; beyond that -- a source dragged across tens of its own size -- nothing is skipped any more)
+                if (d2 > 0.0) st->travel += sqrt(d2) * (1.0 + 0x1p-40) + 0x1p-48 * s1;
+                if (!(st->travel < 32.0 * s1)) st->travel = INFINITY;
+            }
+        }
         if (lane == 0) {
             st->prev_fitness = st->fitness;
             st->prev_rmse = st->rmse;

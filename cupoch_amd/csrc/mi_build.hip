@@ -263,6 +263,7 @@ int drain_links(mi_icp_ctx* c) {
 int resort_source_by_match(mi_icp_ctx* c) {
     const int64_t n = c->ns;
     if (n <= 0 || c->nt <= 0 || !c->nn_valid) return MI_ICP_OK;
+    TRY(drop_expiry(c));  // (other packets)
     SortBuffers sb;
     TRY(sort_buffers(c, n, &sb));
     // the key is the matched LEAF (the order inside a leaf does not matter to a packet, and
@@ -330,6 +331,7 @@ int mi_icp_set_target(mi_icp_ctx* c, const float* xyz, const float* normals, con
     TRY(check_ctx(c, mem_kind, "set_target"));
     if (n < 0 || n > 0x7fffff00ll || (n > 0 && !xyz)) return fail(c, MI_ICP_ERR_INVALID, "set_target: bad size/pointer");
     TRY(drain_links(c));
+    TRY(drop_expiry(c));
     c->nt = 0;
     c->inv_t_valid = false;
     c->nn_valid = false;
@@ -503,6 +505,12 @@ int mi_icp_set_source(mi_icp_ctx* c, const float* xyz, const float* normals, con
     TRY(ensure(c, c->sperm, (size_t)n, &sperm));
     TRY(ensure(c, c->nn_idx, (size_t)n, &idx));
     TRY(ensure(c, c->nn_d2, (size_t)n, &d2));
+    {   // the search skip's limit per packet (nn_search.h): none yet -- and the array may be a new one
+        double* lim;
+        TRY(ensure(c, c->expiry, (size_t)((n + 63) / 64), &lim));
+        c->expiry_live = true;
+        TRY(drop_expiry(c));
+    }
     if (d_nrm) TRY(ensure(c, c->snrm, (size_t)n, &snrm));
     if (d_cov) TRY(ensure(c, c->scov, (size_t)n * 9, &scov));
     gather_source<<<blocks_for(n), 256, 0, c->stream>>>(order, d_pts, d_nrm, d_cov, (int)n, sx, sy, sz,

@@ -202,6 +202,23 @@ int mi_icp_debug_loop_counters(mi_icp_ctx* c, int32_t* out4) {
 int mi_icp_debug_drop_seeds(mi_icp_ctx* c) {
     TRY(check_ctx(c));
     c->nn_valid = false;
+    return drop_expiry(c);
+}
+
+int mi_icp_debug_search_skip(mi_icp_ctx* c, double* state2, double* limits_out, int64_t capacity, int64_t* npackets, int* armed) {
+    TRY(check_ctx(c));
+    if (!state2 || !npackets || !armed || capacity < 0) return fail(c, MI_ICP_ERR_INVALID, "debug_search_skip: bad arguments");
+    if (!c->loop_active || !c->loop_dev.p || !c->expiry.p || c->ns <= 0)
+        return fail(c, MI_ICP_ERR_STATE, "debug_search_skip: no registration loop on this context");
+    const int64_t n = (c->ns + 63) / 64;
+    *npackets = n;
+    *armed = (c->expiry_live && c->skip_r2 == c->loop_r2 && skip_pays(c)) ? 1 : 0;
+    const char* st = (const char*)c->loop_dev.p;
+    HIPCHK(c, hipMemcpyAsync(state2, st + offsetof(DevLoop, travel), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(state2 + 1, st + offsetof(DevLoop, fuzz), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (limits_out && capacity >= n)
+        HIPCHK(c, hipMemcpyAsync(limits_out, c->expiry.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return MI_ICP_OK;
 }
 
@@ -209,6 +226,7 @@ int mi_icp_debug_locate(mi_icp_ctx* c, const float* T, int32_t* leaf_out) {
     TRY(check_ctx(c));
     if (!leaf_out || c->ns <= 0 || c->nt <= 0) return fail(c, MI_ICP_ERR_INVALID, "debug_locate: bad state/arguments");
     if (!planes_available(c)) return fail(c, MI_ICP_ERR_INVALID, "debug_locate: this tree has no split planes");
+    TRY(drop_expiry(c));
     TRY(launch_locate_by_planes(c, make_xform(load_T(T)), nullptr, 0));
     c->nn_valid = true;  // (the seeds of the next seeded pass)
     c->n_user_pairs = -1;

@@ -49,7 +49,8 @@ int launch_locate_by_planes(mi_icp_ctx* c, const Xform& X, const DevLoop* loop, 
     const int grid = (int)std::min<int64_t>(blocks_for(c->ns), 8192);
     locate_by_planes<<<grid, 256, 0, c->stream>>>((const float*)c->sx.p, (const float*)c->sy.p, (const float*)c->sz.p, (int)c->ns,
                                                  (const float2*)c->cell_planes.p, c->cell_levels, (const uint32_t*)c->cell_gstart.p,
-                                                 (const float2*)c->gplanes.p, (uint32_t)c->nleaf, X, loop, gated, (int32_t*)c->nn_idx.p);
+                                                 (const float2*)c->gplanes.p, (uint32_t)c->nleaf, X, loop, gated, (int32_t*)c->nn_idx.p,
+                                                 (double*)c->expiry.p);
     KCHK(c);
     return MI_ICP_OK;
 }
@@ -79,7 +80,8 @@ static PacketGrid packet_grid(int64_t ns, uint32_t per_block) {
 
 // nn_packet_kernel<SEED, STATS, STAMP>; STAMP (mi_icp_debug_set_step_stamps: the same kernel + two stamps per wave) on
 // the loop's seeded searches only
-static decltype(&nn_packet_kernel<false, false>) nn_kernel(bool seeded, bool stats, bool stamp) {
+static decltype(&nn_packet_kernel<false, false>) nn_kernel(bool seeded, bool stats, bool stamp, bool gate) {
+    if (gate) return stamp ? nn_packet_kernel<true, false, true, true> : nn_packet_kernel<true, false, false, true>;
     if (stats) return seeded ? nn_packet_kernel<true, true> : nn_packet_kernel<false, true>;
     if (seeded && stamp) return nn_packet_kernel<true, false, true>;
     return seeded ? nn_packet_kernel<true, false> : nn_packet_kernel<false, false>;
@@ -89,6 +91,7 @@ int launch_nn(mi_icp_ctx* c, const Mat4& T, float r2, bool seed, unsigned long l
     if (c->ns <= 0) return MI_ICP_OK;
     int32_t* idx = (int32_t*)c->nn_idx.p;
     if (c->nt <= 0) {
+        TRY(drop_expiry(c));
         fill_i32<<<blocks_for(c->ns), 256, 0, c->stream>>>(idx, c->ns, -1);
         KCHK(c);
         c->nn_valid = true;
@@ -112,20 +115,30 @@ int launch_nn(mi_icp_ctx* c, const Mat4& T, float r2, bool seed, unsigned long l
     // (nn_search.h: locate_by_planes) and the seeded search does the rest.  (Without halos every lane whose seed
     // leaf's region does not finish it walks up from there -- under the displacement a registration starts with that
     // is most packets, and costs more than the walk from the root: 10M points 3.9 against 1.2 ms.)
-    bool self_seeded = false;
-    if (!use_seed && !stats && c->ns >= coarse_first_min() && have_halo && planes_available(c)) {
-        TRY(launch_locate_by_planes(c, X, loop, 0));
-        self_seeded = true;
-    }
+    const bool self_seeded = !use_seed && !stats && c->ns >= coarse_first_min() && have_halo && planes_available(c);
+    // THE SKIP (nn_search.h): a seeded search of the loop leaves a limit per packet; it may skip by the limits on record
+    // if they come from such a search at this radius with nothing in between that called drop_expiry.  Every other
+    // search rewrites matches the limits know nothing of: they are dropped first.
+    const bool limits = loop != nullptr && (use_seed || self_seeded) && !stats && c->expiry.p != nullptr;
+    const bool may_skip = limits && use_seed && c->expiry_live && c->skip_r2 == r2;
+    if (!may_skip) TRY(drop_expiry(c));
+    const uint32_t run = (may_skip && skip_pays(c)) ? kSkipRun : 1u;  // (the gate: nn_packet_kernel)
+    if (self_seeded) TRY(launch_locate_by_planes(c, X, loop, 0));
     c->last_search_kind = use_seed ? 1 : (self_seeded ? 2 : 0);
-    const PacketGrid g = packet_grid(c->ns, kNNPacketsPerBlock);
+    const PacketGrid g = packet_grid(c->ns, run);
     // (inside the registration loop the distances are not stored: nothing reads them there, and every
     // entry point that hands distances out runs its own search first)
-    nn_kernel(use_seed || self_seeded, stats != nullptr, loop && c->stamps_on)<<<g.grid, kNNThreads, 0, c->stream>>>(
+    nn_kernel(use_seed || self_seeded, stats != nullptr, loop && c->stamps_on, run > 1u)<<<g.grid, kNNThreads, 0, c->stream>>>(
             (const float*)c->sx.p, (const float*)c->sy.p, (const float*)c->sz.p, (int)c->ns, (const float*)c->nodes.p,
             (const float*)c->tblk.p, (const float*)lreg_of(c), have_halo ? (const float*)c->thalo.p : nullptr, c->leaf_first,
-            X, loop, r2, g.nblocks, idx, loop ? nullptr : (float*)c->nn_d2.p, stats, want);
+            X, loop, r2, g.nblocks, idx, loop ? nullptr : (float*)c->nn_d2.p, stats, want,
+            limits ? (double*)c->expiry.p : nullptr,
+            limits ? reinterpret_cast<uint8_t*>(c->loop_dev.p) + offsetof(DevLoop, live) : nullptr, skip_live_shift(c->ns), run);
     KCHK(c);
+    if (limits) {
+        c->expiry_live = true;
+        c->skip_r2 = r2;
+    }
     c->nn_valid = true;
     c->n_user_pairs = -1;
     return MI_ICP_OK;
@@ -367,7 +380,7 @@ void mi_icp_destroy(mi_icp_ctx* c) {
     comm_release(c);
     DevBuf* all[] = {&c->trec, &c->tidx, &c->thalo, &c->tlinks_tmp, &c->halo_want, &c->loop_hist, &c->tblk, &c->tnrm, &c->tcov, &c->tgrad, &c->sint, &c->nodes, &c->inv_t, &c->cell_planes, &c->cell_samples, &c->cell_cstart,
                      &c->cell_gstart, &c->sx, &c->sy, &c->sz,
-                     &c->sperm, &c->snrm, &c->scov, &c->nn_idx, &c->nn_d2, &c->inv_s,
+                     &c->sperm, &c->snrm, &c->scov, &c->nn_idx, &c->nn_d2, &c->expiry, &c->inv_s,
                      &c->user_pairs, &c->keys0, &c->keys1, &c->vals0, &c->vals1, &c->hist,
                      &c->scan_tmp, &c->bounds_part, &c->bounds, &c->partial, &c->sys_dev,
                      &c->dense_idx, &c->flags, &c->pairs_out, &c->seg_start, &c->loop_dev, &c->ticket, &c->mail_state, &c->alt[0],
@@ -696,6 +709,7 @@ static int launch_fused_iteration(mi_icp_ctx* c, DevLoop* d) {
     bool have_halo;
     uint32_t* want;
     TRY(loop_halo(c, &have_halo, &want));
+    TRY(drop_expiry(c));  // (the one-launch iteration rewrites the matches and keeps no limits)
     const PacketGrid g = packet_grid(c->ns, kFusedPackets);
     double *partial, *sys;
     uint32_t* ticket;
@@ -867,6 +881,11 @@ static int loop_begin(mi_icp_ctx* c, int est, float max_distance, const float* i
     L.ready = estimator_ready(c, est) ? 1 : 0;
     L.history = 0ull;
     L.stamps = 0ull;
+    // the search skip (loop.h): a new odometer -- at 0, limits measured on the last one are void -- and no bound on the
+    // queries' rounding until the first step has formed one from the source's box
+    L.travel = 0.0;
+    L.fuzz = INFINITY;
+    TRY(drop_expiry(c));
     // re-location (loop.h): sized only where the descent exists and the source is large enough to make its own seeds
     const bool can_locate = planes_available(c) && c->ns >= coarse_first_min() && c->src_bounds.p != nullptr && c->nt > 0;
     L.near2_ptr = can_locate ? (uint64_t)(uintptr_t)((const float*)c->nodes.p + kRecordNear2) : 0ull;

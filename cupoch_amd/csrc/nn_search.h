@@ -157,6 +157,55 @@ __device__ __forceinline__ void drain_halo(PacketShared& sh, const float* halo_g
     }
 }
 
+// ---- THE SKIP: a packet whose matches provably cannot have changed is not searched ------------------------
+// A seeded search of the registration loop leaves, per packet, a LIMIT on the loop's odometer (loop.h `travel`): while
+// travel + fuzz stays below it, every lane of the packet would again finish in the prologue below with the match it has
+// -- and the kernel (nn_packet_kernel, its gate) does not search the packet.
+// The limit is travel + margin - fuzz at the time of the search, margin = the least over the packet's lanes of
+//     min( (a2 - a1) / 2,  (inside - rb) / 2,  r - a1 )
+// in linear distance: a1 = sqrt(best), a2 = sqrt(the second smallest of the seed leaf's eight d2; = a1 on a tie),
+// inside / rb the prologue's own, r = sqrt(r2).  Why that is enough -- q, q' the fp32 queries then and now, x, x' the
+// exact positions A p, A' p:
+//   |q' - q| <= |q' - x'| + |x' - x| + |x - q| <= fuzz' + (travel' - travel) + fuzz =: e < margin      (loop.h)
+//   * every true distance |q - p_k| changes by at most e, and so does every distance to a face of the region;
+//   * a COMPUTED d2 = fma(dz, dz, fma(dy, dy, dx * dx)) of rounded differences is five roundings off the true one, its
+//     hardware square root (1 ulp) two more: a computed linear distance is within 3.5 u + 2 u < 6 u of the true one
+//     (u = 2^-24), `inside` -- one rounded difference -- within u, rb carries its own factor.  Comparing computed values
+//     then and now therefore costs each side at most ~12 u: the margins are formed from the values that count
+//     against them enlarged, the others shrunk, by 2^-19 = 32 u (kSkipGrow / kSkipShrink) -- a slack RELATIVE to the
+//     distances, as these roundings are; the ABSOLUTE roundings, xform_point's, are `fuzz`, formed from the box's and
+//     the transform's magnitudes in the step;
+//   * so now as then: the match's computed d2 is strictly the smallest of its leaf's (first term: the lowest-slot rule has
+//     nothing to decide), strictly below r2 (third), and the region's faces are at least the new rb away (second) -- the
+//     lane retires in the prologue with the same bidx, stores nothing and asks for no halo.
+// A lane that did not finish in the prologue, or finished there without a match, has margin 0; a lane past the end +inf.
+// Margins <= fuzz leave -inf: never skipped.  (The sums travel + ... are fp64: their own roundings, 2^-53 of an odometer
+// of a few units, disappear in the 2^-19 of the distances.)
+constexpr float kSkipGrow = 1.0f + 0x1p-19f, kSkipShrink = 1.0f - 0x1p-19f;
+
+// the wave's minimum on the DPP network (lanes without a source keep their own value); valid in lane 63
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_min_hop(float v) {
+    return fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xf, false)));
+}
+__device__ __forceinline__ float wave_min_last(float v) {
+    v = dpp_min_hop<0x111, 0xf>(v);  // row_shr:1
+    v = dpp_min_hop<0x112, 0xf>(v);  // row_shr:2
+    v = dpp_min_hop<0x114, 0xf>(v);  // row_shr:4
+    v = dpp_min_hop<0x118, 0xf>(v);  // row_shr:8
+    v = dpp_min_hop<0x142, 0xa>(v);  // row_bcast:15
+    v = dpp_min_hop<0x143, 0xc>(v);  // row_bcast:31
+    return v;
+}
+
+// the second smallest of eight (the smallest again when it occurs twice); the minimum tree is the prologue's own
+__device__ __forceinline__ float second_smallest8(const float* d) {
+    const float l0 = fminf(d[0], d[1]), l1 = fminf(d[2], d[3]), l2 = fminf(d[4], d[5]), l3 = fminf(d[6], d[7]);
+    const float h0 = fmaxf(d[0], d[1]), h1 = fmaxf(d[2], d[3]), h2 = fmaxf(d[4], d[5]), h3 = fmaxf(d[6], d[7]);
+    const float s01 = fminf(fmaxf(l0, l1), fminf(h0, h1)), s23 = fminf(fmaxf(l2, l3), fminf(h2, h3));
+    return fminf(fmaxf(fminf(l0, l1), fminf(l2, l3)), fminf(s01, s23));
+}
+
 // What a packet's search leaves in every lane (for callers that go on with it: fused_small.h)
 struct PacketResult {
     bool valid;     // the lane holds a source point
@@ -170,14 +219,19 @@ struct PacketResult {
 // index; wave-uniform).  `loop` != nullptr: the transform comes from the device-resident loop state and
 // nothing is done once that loop is finished (returns false, wave-uniformly); otherwise Tv (by value) is
 // used.  Stores the matches (and distances / statistics when asked) itself.
+// expiry != nullptr (the loop's seeded searches, "the skip" above): the packet leaves its new limit, and -- a sample of the
+// packets, one in 2^live_shift, 64 at most -- says in live[] whether it got one (the host's hint, ctx.h skip_pays).
 template <bool SEED, bool STATS>
 __device__ __forceinline__ bool nn_packet_body(
         PacketShared& sh, uint32_t packet,
         const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz,
         int ns, const float* __restrict__ records_g, const float* __restrict__ tblk_g,
         const float* __restrict__ lreg_g, const float* __restrict__ halo_g, uint32_t leaf_first, Xform Tv, const DevLoop* __restrict__ loop, float r2, int32_t* __restrict__ nn_idx,
-        float* __restrict__ nn_d2, unsigned long long* __restrict__ stats, uint32_t* __restrict__ want, PacketResult& out) {
+        float* __restrict__ nn_d2, unsigned long long* __restrict__ stats, uint32_t* __restrict__ want, PacketResult& out,
+        double* __restrict__ expiry = nullptr, uint8_t* __restrict__ live = nullptr, uint32_t live_shift = 0u) {
     const int lane = lane_id();
+    // (the census build leaves no limits: its launches are not the loop's)
+    const bool limits = SEED && !STATS && loop != nullptr && expiry != nullptr && nn_d2 == nullptr;  // (wave-uniform)
     const int i = (int)(packet * 64u) + lane;  // (ns < 2^31)
     const bool valid = i < ns;
     // Everything this lane needs from global memory that does not depend on anything else is
@@ -207,6 +261,9 @@ __device__ __forceinline__ bool nn_packet_body(
     bool linked = false;    // its cube pokes out of the seed leaf's region by less than that leaf's halo reaches
     uint32_t nlines = 0u;   // ... so that this many of the leaf's halo lines hold all it can find
     uint32_t why = 0u;      // (census) 1: seed leaf without a region, 2: without a halo, 3: overhang beyond its reach
+    // (the skip) a lane that finishes in the prologue with a match: the second smallest d2 of its leaf and the room to its
+    // region's faces; every other lane with a source point: none
+    float margin = valid ? -1.0f : INFINITY, margin2 = INFINITY;
     if (SEED) {
         // The previous iteration's match: its whole LEAF is evaluated right here (one 128-B line,
         // the same the old single-point gather touched), which gives the search radius -- and if
@@ -253,6 +310,10 @@ __device__ __forceinline__ bool nn_packet_body(
                                        fminf(g1.y - qy, g1.z - qz));
             if (inside >= rb) {  // (NaN anywhere: not finished)
                 retired = true;
+                if (limits && bidx >= 0) {  // (the skip, above; the square roots wait until the whole packet is known to be here)
+                    margin2 = second_smallest8(d);
+                    margin = inside * kSkipShrink - rb * kSkipGrow;
+                }
             } else {
                 Cube cube;  // (formed again behind the halo phase for the lanes that walk: six registers less across it)
                 set_cube(cube, qx, qy, qz, best);
@@ -277,6 +338,28 @@ __device__ __forceinline__ bool nn_packet_body(
     if (SEED && __builtin_expect(want != nullptr, 0)) {
         const uint64_t m = __ballot(valid && !retired && seed_j >= 0);
         if (m != 0ull && lane == 0) atomicAdd(want + (packet & (kWantSlots - 1u)), (uint32_t)__popcll(m));
+    }
+    if (limits) {
+        // The packet's limit: the least margin of its lanes on top of the odometer's reading.  One lane without a margin and
+        // the packet has none: the arithmetic, and the loads of the odometer, are for the packets whose every lane has one
+        // (noisy data: hardly any).
+        bool has = false;  // (lane 63)
+        if (__ballot(margin < 0.0f) == 0ull) {
+            if (valid) {
+                const float a1 = __builtin_amdgcn_sqrtf(best) * kSkipGrow;
+                const float m = fminf(fminf(0.5f * (__builtin_amdgcn_sqrtf(margin2) * kSkipShrink - a1), 0.5f * margin),
+                                      __builtin_amdgcn_sqrtf(r2) * kSkipShrink - a1);
+                margin = (m > 0.0f) ? m : 0.0f;  // (NaN: none)
+            }
+            const float pm = wave_min_last(margin);
+            const double room = (double)pm - loop->fuzz;
+            has = room > 0.0;
+            if (lane == 63) expiry[packet] = has ? loop->travel + room : -(double)INFINITY;
+        } else if (lane == 63) {
+            expiry[packet] = -(double)INFINITY;
+        }
+        if (lane == 63 && (packet & ((1u << live_shift) - 1u)) == 0u && (packet >> live_shift) < 64u)
+            live[packet >> live_shift] = has ? 1 : 0;
     }
     // the lane's running result lives in LDS, where any lane may improve it
     sh.best[lane] = ((unsigned long long)__float_as_uint(fmaxf(best, 0.0f)) << 32) | (unsigned long long)(uint32_t)bidx;
@@ -522,12 +605,21 @@ __device__ __forceinline__ bool nn_packet_body(
 // time: 3 % faster than 4 packets per workgroup), 8 waves per SIMD.
 // (the pass from the root may take 72 registers -- 7 waves per SIMD: with 64 its two rounds spilled 20 bytes per lane,
 // 150 MB of scratch writes per 10M-query launch, and it is bound by its vector instructions, not by its occupancy)
-template <bool SEED, bool STATS, bool STAMP = false>
-__global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(SEED ? 8 : 7, 8))) void nn_packet_kernel(
+// run > 1: THE SKIP's gate ("the skip" above).  The workgroup owns a RUN of `run` consecutive packets (nblocks counts runs):
+// its lanes read the run's limits with one vector load, a ballot says which packets have reached theirs, and only those are
+// searched, one after the other.  (One workgroup per packet that tests its own limit and returns was measured first: 156k
+// workgroups that do nothing but return are a 40-us launch at 10M points against 20 for this form -- EXPERIMENTS.md.)
+// (The gated instantiation is allowed 6 waves per SIMD: its loop over packets keeps the arguments in scalar registers that
+// spill into vector ones -- 78 registers, none in scratch; 28 bytes of scratch per lane with 64, 8 with 72 -- and most of
+// its waves search nothing.)
+constexpr uint32_t kSkipRun = 8;  // packets per run (<= 32; 16 measured the same: EXPERIMENTS.md)
+template <bool SEED, bool STATS, bool STAMP = false, bool GATE = false>
+__global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(GATE ? 6 : (SEED ? 8 : 7), 8))) void nn_packet_kernel(
         const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz,
         int ns, const float* __restrict__ records_g, const float* __restrict__ tblk_g,
         const float* __restrict__ lreg_g, const float* __restrict__ halo_g, uint32_t leaf_first, Xform Tv, const DevLoop* __restrict__ loop, float r2, uint32_t nblocks, int32_t* __restrict__ nn_idx,
-        float* __restrict__ nn_d2, unsigned long long* __restrict__ stats, uint32_t* __restrict__ want) {
+        float* __restrict__ nn_d2, unsigned long long* __restrict__ stats, uint32_t* __restrict__ want,
+        double* __restrict__ expiry, uint8_t* __restrict__ live, uint32_t live_shift, uint32_t run) {
     __shared__ PacketShared s_pk[kNNPacketsPerBlock];
     uint32_t logical;
     if (!xcd_remap(nblocks, logical)) return;
@@ -537,8 +629,27 @@ __global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(SEED
     // (only the first 64 and the last 256 workgroups of the dispatch order touch the two words: every wave doing so --
     // 156k atomics on one address -- made a 10M-query launch 3.5 ms instead of 0.08)
     if (STAMP && stamps && threadIdx.x == 0 && blockIdx.x < 64u) atomicMin(stamps + 0, stamp_now());
-    (void)nn_packet_body<SEED, STATS>(s_pk[0], logical, sx, sy, sz, ns, records_g, tblk_g, lreg_g, halo_g, leaf_first, Tv, loop,
-                                      r2, nn_idx, nn_d2, stats, want, unused);
+    if (!GATE) {
+        (void)nn_packet_body<SEED, STATS>(s_pk[0], logical, sx, sy, sz, ns, records_g, tblk_g, lreg_g, halo_g, leaf_first, Tv, loop,
+                                          r2, nn_idx, nn_d2, stats, want, unused, expiry, live, live_shift);
+    } else {
+        // (GATE: a seeded search of the loop that stores no distances -- the arguments a loop over packets need not
+        // keep in registers are constants here: kept, they spilled a hundred scalar registers)
+        const uint32_t npackets = ((uint32_t)ns + 63u) >> 6, lane = (uint32_t)lane_id();
+        const uint32_t first = logical * run;
+        const bool mine = lane < run && first + lane < npackets;
+        const double limit = expiry[mine ? first + lane : first];
+        const double reach = loop->travel + loop->fuzz;
+        // (wave-uniform) the packets to search: bit k = packet first + k (NaN, -inf: searched)
+        uint32_t need = (loop->done != 0) ? 0u : (uint32_t)__ballot(mine && !(reach < limit));
+        while (need != 0u) {
+            const uint32_t k = (uint32_t)__builtin_ctz(need);
+            need &= need - 1u;
+            (void)nn_packet_body<true, false>(s_pk[0], first + k, sx, sy, sz, ns, records_g, tblk_g, lreg_g, halo_g, leaf_first, Xform{},
+                                              loop, r2, nn_idx, nullptr, nullptr, want, unused, expiry, live, live_shift);
+            __builtin_amdgcn_wave_barrier();  // (the next packet takes over the wave's LDS)
+        }
+    }
     if (STAMP && stamps && threadIdx.x == 0 && blockIdx.x + 256u >= gridDim.x) atomicMax(stamps + 1, stamp_now());
 }
 
@@ -556,7 +667,7 @@ static __global__ __launch_bounds__(256) void locate_by_planes(
         const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int ns,
         const float2* __restrict__ cell_planes, int cell_levels, const uint32_t* __restrict__ gstart,
         const float2* __restrict__ gplanes, uint32_t nleaf, Xform Tv, const DevLoop* __restrict__ loop, int gated,
-        int32_t* __restrict__ nn_idx) {
+        int32_t* __restrict__ nn_idx, double* __restrict__ expiry) {
     Xform T = Tv;
     if (loop) {
         if (loop->done) return;
@@ -570,6 +681,7 @@ static __global__ __launch_bounds__(256) void locate_by_planes(
         const uint32_t g = gstart[cell];
         const uint32_t leaf = min(g * 512u + descend_group(gplanes + (size_t)g * 512u, qx, qy, qz), nleaf - 1u);
         nn_idx[i] = (int32_t)(leaf * (uint32_t)kLeaf);
+        if (expiry != nullptr && (i & 63) == 0) expiry[i >> 6] = -(double)INFINITY;  // new seeds: the packet's limit ("the skip") is void
     }
 }
 

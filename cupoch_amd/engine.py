@@ -239,6 +239,26 @@ class Engine:
         """test hook (mi_icp_debug.h): the next search starts top-down, not from the previous matches"""
         self._chk(self._L.mi_icp_debug_drop_seeds(self._ctx))
 
+    def loop_counters(self):
+        """test hook (mi_icp_debug.h): {iterations, passes, re-locations, re-location launches armed} of the present loop"""
+        out = np.zeros(4, np.int32)
+        self._chk(self._L.mi_icp_debug_loop_counters(self._ctx, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def search_skip_state(self):
+        """test hook (mi_icp_debug.h): the search skip's state of the present loop -- the odometer `travel`, the queries'
+        rounding bound `fuzz`, the per-packet `limits`, `armed` (will the next search be gated at all?) and `will_skip`, the
+        packets that search is going to skip: travel + fuzz < limit"""
+        n, armed = C.c_int64(0), C.c_int(0)
+        st = np.zeros(2, np.float64)
+        self._chk(self._L.mi_icp_debug_search_skip(self._ctx, st.ctypes.data_as(C.c_void_p), None, 0, C.byref(n), C.byref(armed)))
+        lim = np.zeros(n.value, np.float64)
+        self._chk(self._L.mi_icp_debug_search_skip(self._ctx, st.ctypes.data_as(C.c_void_p), lim.ctypes.data_as(C.c_void_p),
+                                                   n.value, C.byref(n), C.byref(armed)))
+        with np.errstate(invalid="ignore"):
+            will = (st[0] + st[1] < lim) if armed.value else np.zeros(n.value, bool)
+        return {"travel": float(st[0]), "fuzz": float(st[1]), "limits": lim, "armed": bool(armed.value), "will_skip": will}
+
     def last_search_kind(self):
         """test hook: 0 = the last search started at the root, 1 = from the previous matches, 2 = from its own seeds"""
         return int(self._L.mi_icp_debug_last_search_kind(self._ctx))

@@ -61,6 +61,15 @@ MI_ICP_API int mi_icp_debug_occupancy(int which);
  * search's seeds replaced by the leaves the moved queries fall into: csrc/loop.h, nn_search.h locate_by_planes),
  * 1 if the next chunk of iterations would still carry the gated re-location launches}. */
 MI_ICP_API int mi_icp_debug_loop_counters(mi_icp_ctx* ctx, int32_t* out4);
+/* The search skip's state (csrc/nn_search.h "the skip", csrc/loop.h) of the present registration loop, large sources
+ * only: state2 = {the loop's odometer `travel`, the present bound `fuzz` on the queries' rounding}, *npackets = the
+ * source's packets of 64 points, limits_out[packet] (host memory, filled when capacity >= *npackets; may be NULL) = the
+ * limit the packet's last search left (-inf or NaN: none), *armed = 1 if the loop's next search will be gated at all (the
+ * limits on record belong to its radius, nothing has voided them since, and by the loop state's sample at least a
+ * quarter of the packets hold one: csrc/ctx.h skip_pays).  That search skips exactly the packets with
+ * travel + fuzz < limit, travel and fuzz as its own step leaves them.  Fails without a loop. */
+MI_ICP_API int mi_icp_debug_search_skip(mi_icp_ctx* ctx, double* state2, double* limits_out, int64_t capacity,
+                                        int64_t* npackets, int* armed);
 /* The leaf every staged source point FALLS INTO under T (column-major 4x4 or NULL) by the binary descent through the
  * cell planes and its group's planes (nn_search.h locate_by_planes): leaf_out[original source index] = leaf (host memory,
  * one per source point).  The located leaves are left behind as the seeds of the next seeded pass.  Fails without a
