@@ -165,6 +165,10 @@ def test_config5_generalized_icp_five_million(eng):
     cov_t = orc.rotate_covariances(T_mid, scov.reshape(-1, 3, 3))
     ref = orc.compute_system(GICP, src_t, tgt, cor, None, None, cov_t, tcov.reshape(-1, 3, 3))
     np.testing.assert_allclose(got, ref, rtol=2e-5, atol=2e-5 * np.abs(ref).max())
+    # the statistics do not go through the weights: the count is exact, and the sum of d^2 -- the same float32 terms
+    # added in fp64 in another order -- agrees to the worst case of that, n 2^-53 (5.6e-10 here; 1e-12 needs n < 9000)
+    assert got[29] == len(cor)
+    np.testing.assert_allclose(got[28], ref[28], rtol=n * 2.0 ** -53)
     # the registration itself, fixed iteration count (6 oracle passes over 5M points)
     res = eng.registration_icp(GICP, r, None, 0.0, 0.0, 5, -1.0)
     T = np.array(res.transformation, np.float32).reshape(4, 4).T

@@ -199,6 +199,9 @@ def test_compute_system_matches_oracle(eng, est):
     scale = np.abs(ref).max()
     tol = 1e-9 if est != GICP else 2e-5            # GICP goes through acosf/cosf: libm vs device ulps
     np.testing.assert_allclose(got, ref, rtol=tol, atol=tol * scale)
+    # the statistics do not go through GICP's weights: the count is exact and the sum of d^2 is held as everywhere else
+    assert got[29] == len(cor)
+    np.testing.assert_allclose(got[28], ref[28], rtol=1e-12)
     rm = eng.compute_rmse(est, T)
     rr = orc.compute_rmse(est, src_t, d["tgt"], cor, nrm_t, d["tgt_nrm"], cov_t, d["tgt_cov"])
     assert rm == pytest.approx(rr, rel=1e-5)
@@ -244,6 +247,8 @@ def test_gicp_system_on_covariances_the_eigen_solver_special_cases(eng):
                                  orc.rotate_covariances(T, cov), cov)
         assert np.isfinite(ref).all() and len(cor) > n // 2
         np.testing.assert_allclose(got, ref, rtol=2e-5, atol=2e-5 * np.abs(ref).max())
+        assert got[29] == len(cor)                                  # (the statistics do not go through the weights)
+        np.testing.assert_allclose(got[28], ref[28], rtol=1e-12)
 
 
 def test_gicp_system_on_singular_and_indefinite_covariances(eng):
