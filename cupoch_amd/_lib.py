@@ -173,6 +173,14 @@ SIGNATURES = {
                                       _P, _P, _P, C.POINTER(_L), _I]),
     "mi_icp_compute_rgbd_odometry": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P, C.POINTER(_I), _P, _P, _I]),
     "mi_icp_compute_weighted_rgbd_odometry": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, C.POINTER(_I), _P, _P, _P, _I]),
+    "mi_icp_tsdf_create": (_I, [_P, _F, _I, _F, _I, _P, C.POINTER(_P)]),
+    "mi_icp_tsdf_destroy": (_I, [_P, _P]),
+    "mi_icp_tsdf_reset": (_I, [_P, _P]),
+    "mi_icp_tsdf_integrate": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I]),
+    "mi_icp_tsdf_extract_point_cloud": (_I, [_P, _P, _P, _P, _P, _L, C.POINTER(_L), _I]),
+    "mi_icp_tsdf_extract_voxel_point_cloud": (_I, [_P, _P, _P, _P, _L, C.POINTER(_L), _I]),
+    "mi_icp_tsdf_raycast": (_I, [_P, _P, _I, _I, _P, _P, _F, _I, _P, _P, _P, _L, C.POINTER(_L), _I]),
+    "mi_icp_tsdf_get_voxels": (_I, [_P, _P, _P, _P, _P, _I]),
     "mi_icp_covariances_from_normals": (_I, [_P, _P, _L, _F, _P, _I]),
     "mi_icp_estimate_normals_knn": (_I, [_P, _P, _L, _I, _P, _I]),
     "mi_icp_estimate_normals_radius": (_I, [_P, _P, _L, _F, _I, _P, _I]),

@@ -1,8 +1,8 @@
 // cupoch/kinfu/kinfu.h -- the ICP side of kinfu::KinfuPipeline (reference:
 // kinfu/kinfu.h:36-121, kinfu.cpp:87-143): the point-cloud pyramid of SurfaceMeasurement
-// and the coarse-to-fine PoseEstimation.  The TSDF volume, its raycaster and the image
-// filters are producers / consumers of the path and are not built; PoseEstimation is
-// therefore a free function taking the option block instead of a pipeline member.
+// and the coarse-to-fine PoseEstimation.  The volume is integration::UniformTSDFVolume
+// (cupoch/integration/uniform_tsdfvolume.h); the image filters and pyramid are not built, so
+// there is no pipeline class and PoseEstimation is a free function taking the option block.
 #pragma once
 #include <memory>
 #include <tuple>

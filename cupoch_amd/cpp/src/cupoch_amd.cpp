@@ -951,6 +951,110 @@ std::tuple<bool, Eigen::Matrix4f, Eigen::Vector6f, Eigen::Matrix6f> ComputeWeigh
 
 }  // namespace odometry
 
+// ---------------------------------------------------------------- integration
+namespace integration {
+
+UniformTSDFVolume::UniformTSDFVolume(float length, int resolution, float sdf_trunc, TSDFVolumeColorType color_type,
+                                     const Eigen::Vector3f& origin)
+    : TSDFVolume(length / (float)resolution, sdf_trunc, color_type),
+      origin_(origin),
+      length_(length),
+      resolution_(resolution),
+      voxel_num_(resolution * resolution * resolution) {
+    Check(mi_icp_tsdf_create(Engine(), length, resolution, sdf_trunc, (int)color_type, origin_.data(), &volume_));
+}
+
+UniformTSDFVolume::~UniformTSDFVolume() {
+    if (volume_) (void)mi_icp_tsdf_destroy(Engine(), volume_);
+}
+
+void UniformTSDFVolume::Reset() { Check(mi_icp_tsdf_reset(Engine(), volume_)); }
+
+void UniformTSDFVolume::Integrate(const geometry::RGBDImage& image, const camera::PinholeCameraIntrinsic& intrinsic,
+                                  const Eigen::Matrix4f& extrinsic) {
+    const geometry::Image &d = image.depth_, &c = image.color_;
+    const float k4[4] = {intrinsic.fx_, intrinsic.fy_, intrinsic.cx_, intrinsic.cy_};
+    const bool colored = color_type_ != TSDFVolumeColorType::NoColor;
+    const int rc = mi_icp_tsdf_integrate(Engine(), volume_, d.data_.empty() ? nullptr : d.data_.data(), d.width_, d.height_,
+                                         d.num_of_channels_, d.bytes_per_channel_,
+                                         (!colored || c.data_.empty()) ? nullptr : c.data_.data(), c.width_, c.height_,
+                                         c.num_of_channels_, c.bytes_per_channel_, intrinsic.width_, intrinsic.height_, k4,
+                                         extrinsic.data(), MI_ICP_DEVICE);
+    if (rc == MI_ICP_ERR_INVALID) {  // uniform_tsdfvolume.cu:677-695
+        LogError("[UniformTSDFVolume::Integrate] Unsupported image format.");
+        return;
+    }
+    Check(rc);
+}
+
+namespace {
+// the capacity rule of include/mi_icp.h: fill when it fits, else make room for the count that came back and call again
+constexpr size_t kFirstCapacity = (size_t)1 << 18;  // points an extraction makes room for before it knows the count
+
+template <class Call>
+std::shared_ptr<geometry::PointCloud> FillCloud(bool normals, bool colors, size_t capacity, Call call) {
+    auto out = std::make_shared<geometry::PointCloud>();
+    int64_t m = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        out->points_.resize(capacity);
+        if (normals) out->normals_.resize(capacity);
+        if (colors) out->colors_.resize(capacity);
+        Check(call(capacity ? out->points_.data()->data() : nullptr,
+                   (capacity && normals) ? out->normals_.data()->data() : nullptr,
+                   (capacity && colors) ? out->colors_.data()->data() : nullptr, (int64_t)capacity, &m));
+        if ((size_t)m <= capacity) break;
+        capacity = (size_t)m;
+    }
+    out->points_.resize((size_t)m);
+    if (normals) out->normals_.resize((size_t)m);
+    if (colors) out->colors_.resize((size_t)m);
+    return out;
+}
+}  // namespace
+
+std::shared_ptr<geometry::PointCloud> UniformTSDFVolume::ExtractPointCloud() {
+    mi_icp_tsdf* v = volume_;
+    return FillCloud(true, color_type_ != TSDFVolumeColorType::NoColor, kFirstCapacity, [v](float* p, float* n, float* c, int64_t cap, int64_t* m) {
+        return mi_icp_tsdf_extract_point_cloud(Engine(), v, p, n, c, cap, m, MI_ICP_DEVICE);
+    });
+}
+
+std::shared_ptr<geometry::PointCloud> UniformTSDFVolume::ExtractVoxelPointCloud() const {
+    mi_icp_tsdf* v = volume_;
+    return FillCloud(false, true, kFirstCapacity, [v](float* p, float*, float* c, int64_t cap, int64_t* m) {
+        return mi_icp_tsdf_extract_voxel_point_cloud(Engine(), v, p, c, cap, m, MI_ICP_DEVICE);
+    });
+}
+
+std::shared_ptr<geometry::PointCloud> UniformTSDFVolume::Raycast(const camera::PinholeCameraIntrinsic& intrinsic,
+                                                                 const Eigen::Matrix4f& extrinsic, float sdf_trunc,
+                                                                 bool project_valid_depth_only) const {
+    mi_icp_tsdf* v = volume_;
+    const float k4[4] = {intrinsic.fx_, intrinsic.fy_, intrinsic.cx_, intrinsic.cy_};
+    const int w = intrinsic.width_, h = intrinsic.height_;
+    const size_t npix = (w > 0 && h > 0) ? (size_t)w * (size_t)h : 0;
+    return FillCloud(true, true, npix, [&](float* p, float* n, float* c, int64_t cap, int64_t* m) {
+        return mi_icp_tsdf_raycast(Engine(), v, w, h, k4, extrinsic.data(), sdf_trunc, project_valid_depth_only ? 1 : 0, p, n,
+                                   c, cap, m, MI_ICP_DEVICE);
+    });
+}
+
+std::vector<geometry::TSDFVoxel> UniformTSDFVolume::GetVoxels() const {
+    const size_t n = (size_t)voxel_num_;
+    const bool colored = color_type_ != TSDFVolumeColorType::NoColor;
+    std::vector<float> t(n), w(n), c(colored ? 3 * n : 0);
+    Check(mi_icp_tsdf_get_voxels(Engine(), volume_, t.data(), w.data(), colored ? c.data() : nullptr, MI_ICP_HOST));
+    std::vector<geometry::TSDFVoxel> out(n);
+    for (size_t i = 0; i < n; ++i) {
+        out[i].tsdf_ = t[i];
+        out[i].weight_ = w[i];
+        if (colored) out[i].color_ = Eigen::Vector3f(c[i], c[n + i], c[2 * n + i]);
+    }
+    return out;
+}
+
+}  // namespace integration
+
 // ---------------------------------------------------------------- kinfu
 namespace kinfu {
 

@@ -26,8 +26,11 @@
 #include <type_traits>
 #include <vector>
 
+#include "cupoch/camera/pinhole_camera_intrinsic.h"
+#include "cupoch/geometry/image.h"
 #include "cupoch/geometry/keypoint.h"
 #include "cupoch/geometry/pointcloud.h"
+#include "cupoch/integration/uniform_tsdfvolume.h"
 #include "cupoch/knn/kdtree_flann.h"
 #include "cupoch/knn/kdtree_search_param.h"
 #include "cupoch/registration/generalized_icp.h"
@@ -99,6 +102,18 @@ Vector3fVector wrap(const utility::device_vector<Eigen::Vector3f>& v) {
     Vector3fVector w;
     w.data = v;
     return w;
+}
+
+// geometry.Image from a [H, W] or [H, W, C] array (the reference's Image takes the buffer protocol,
+// cupoch_pybind/geometry/image.cpp): width, height, channels and bytes per channel as the array has them
+geometry::Image image_from_array(const py::array& arr) {
+    if (arr.ndim() != 2 && arr.ndim() != 3) throw std::invalid_argument("Image: expected a [H, W] or [H, W, C] array");
+    const py::array a = py::array::ensure(arr, py::array::c_style);
+    geometry::Image img;
+    const size_t bytes = (size_t)a.nbytes();
+    img.Prepare((int)a.shape(1), (int)a.shape(0), a.ndim() == 3 ? (int)a.shape(2) : 1, (int)a.itemsize());
+    if (bytes) img.SetData(std::vector<uint8_t>((const uint8_t*)a.data(), (const uint8_t*)a.data() + bytes));
+    return img;
 }
 
 // a property that accepts a Vector3fVector or anything array-like
@@ -544,6 +559,82 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             },
             "input"_a, "salient_radius"_a = 0.0f, "non_max_radius"_a = 0.0f, "gamma_21"_a = 0.975f, "gamma_32"_a = 0.975f,
             "min_neighbors"_a = 5, "max_neighbors"_a = knn::NUM_MAX_NN);
+
+    // geometry.Image / geometry.RGBDImage as containers (cupoch_pybind/geometry/image.cpp): what integrate takes
+    py::class_<geometry::Image, std::shared_ptr<geometry::Image>>(mg, "Image")
+            .def(py::init<>())
+            .def(py::init([](const py::array& a) { return std::make_shared<geometry::Image>(image_from_array(a)); }), "array"_a)
+            .def_readonly("width", &geometry::Image::width_)
+            .def_readonly("height", &geometry::Image::height_)
+            .def_readonly("num_of_channels", &geometry::Image::num_of_channels_)
+            .def_readonly("bytes_per_channel", &geometry::Image::bytes_per_channel_)
+            .def("is_empty", &geometry::Image::IsEmpty);
+    py::class_<geometry::RGBDImage, std::shared_ptr<geometry::RGBDImage>>(mg, "RGBDImage")
+            .def(py::init<>())
+            .def(py::init<const geometry::Image&, const geometry::Image&>(), "color"_a, "depth"_a)
+            .def_readwrite("color", &geometry::RGBDImage::color_)
+            .def_readwrite("depth", &geometry::RGBDImage::depth_);
+
+    // ---------------------------------------------------------------- camera
+    py::module mc = m.def_submodule("camera");
+    py::class_<camera::PinholeCameraIntrinsic>(mc, "PinholeCameraIntrinsic")
+            .def(py::init<>())
+            .def(py::init<int, int, float, float, float, float>(), "width"_a, "height"_a, "fx"_a, "fy"_a, "cx"_a, "cy"_a)
+            .def("set_intrinsics", &camera::PinholeCameraIntrinsic::SetIntrinsics, "width"_a, "height"_a, "fx"_a, "fy"_a,
+                 "cx"_a, "cy"_a)
+            .def("get_focal_length", &camera::PinholeCameraIntrinsic::GetFocalLength)
+            .def("get_principal_point", &camera::PinholeCameraIntrinsic::GetPrincipalPoint)
+            .def("is_valid", &camera::PinholeCameraIntrinsic::IsValid)
+            .def("create_pyramid_level", &camera::PinholeCameraIntrinsic::CreatePyramidLevel, "level"_a)
+            .def_readwrite("width", &camera::PinholeCameraIntrinsic::width_)
+            .def_readwrite("height", &camera::PinholeCameraIntrinsic::height_);
+
+    // ---------------------------------------------------------------- integration
+    // cupoch_pybind/integration/integration.cpp: TSDFVolumeColorType and UniformTSDFVolume with the reference's names.
+    // Not bound, as not built: extract_triangle_mesh, extract_voxel_grid, ScalableTSDFVolume.
+    py::module mi = m.def_submodule("integration");
+    py::enum_<integration::TSDFVolumeColorType>(mi, "TSDFVolumeColorType", py::arithmetic())
+            .value("NoColor", integration::TSDFVolumeColorType::NoColor)
+            .value("RGB8", integration::TSDFVolumeColorType::RGB8)
+            .value("Gray32", integration::TSDFVolumeColorType::Gray32)
+            .export_values();
+    py::class_<integration::UniformTSDFVolume, std::shared_ptr<integration::UniformTSDFVolume>>(mi, "UniformTSDFVolume")
+            .def(py::init([](float length, int resolution, float sdf_trunc, integration::TSDFVolumeColorType color_type) {
+                     return std::make_shared<integration::UniformTSDFVolume>(length, resolution, sdf_trunc, color_type);
+                 }),
+                 "length"_a, "resolution"_a, "sdf_trunc"_a, "color_type"_a)
+            .def(py::init([](float length, int resolution, float sdf_trunc, integration::TSDFVolumeColorType color_type,
+                             const farray& origin) {
+                     return std::make_shared<integration::UniformTSDFVolume>(length, resolution, sdf_trunc, color_type,
+                                                                             to_vector3(origin));
+                 }),
+                 "length"_a, "resolution"_a, "sdf_trunc"_a, "color_type"_a, "origin"_a)
+            .def("__repr__",
+                 [](const integration::UniformTSDFVolume& v) {
+                     return std::string("integration::UniformTSDFVolume ") +
+                            (v.color_type_ == integration::TSDFVolumeColorType::NoColor ? "without color." : "with color.");
+                 })
+            .def("reset", &integration::UniformTSDFVolume::Reset)
+            .def("integrate",
+                 [](integration::UniformTSDFVolume& v, const geometry::RGBDImage& image,
+                    const camera::PinholeCameraIntrinsic& intrinsic,
+                    const farray& extrinsic) { v.Integrate(image, intrinsic, to_matrix4(extrinsic)); },
+                 "image"_a, "intrinsic"_a, "extrinsic"_a)
+            .def("extract_point_cloud", &integration::UniformTSDFVolume::ExtractPointCloud)
+            .def("extract_voxel_point_cloud", &integration::UniformTSDFVolume::ExtractVoxelPointCloud)
+            .def("raycast",
+                 [](const integration::UniformTSDFVolume& v, const camera::PinholeCameraIntrinsic& intrinsic,
+                    const farray& extrinsic, float sdf_trunc, bool project_valid_depth_only) {
+                     return v.Raycast(intrinsic, to_matrix4(extrinsic), sdf_trunc, project_valid_depth_only);
+                 },
+                 "intrinsic"_a, "extrinsic"_a, "sdf_trunc"_a, "project_valid_depth_only"_a = true)
+            .def_readonly("voxel_length", &integration::UniformTSDFVolume::voxel_length_)
+            .def_readonly("sdf_trunc", &integration::UniformTSDFVolume::sdf_trunc_)
+            .def_readonly("color_type", &integration::UniformTSDFVolume::color_type_)
+            .def_readonly("length", &integration::UniformTSDFVolume::length_)
+            .def_readonly("resolution", &integration::UniformTSDFVolume::resolution_)
+            .def_property_readonly("origin", [](const integration::UniformTSDFVolume& v) { return from_vector3(v.origin_); });
+
 
     // ---------------------------------------------------------------- registration
     py::module mr = m.def_submodule("registration");

@@ -3,7 +3,7 @@
 //   mi_icp.hip       context life cycle, the correspondence search, the reduction, the device-resident loop
 //   mi_build.hip     target tree (kd cells, groups, levels, halos), source staging, the match-order re-sort
 //   mi_geometry.hip  Transform / bounds / affine / covariances / VoxelDownSample / SelectByIndex / SelectByMask /
-//                    UniformDownSample / SegmentPlane / depth frames / RGB-D odometry / colours
+//                    UniformDownSample / SegmentPlane / depth frames / RGB-D odometry / colours / UniformTSDFVolume
 //   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry,
 //                    RemoveStatisticalOutliers / RemoveRadiusOutliers, ClusterDBSCAN, ComputeISSKeypoints
 //   mi_comm.hip      the ranks' exchange: mailbox, device inboxes, in-library RCCL, self-test and choice
@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/mi_icp.h"
 #include "../../include/mi_icp_debug.h"
@@ -159,6 +160,9 @@ struct mi_icp_ctx {
     // ---- private scratch context: PointCloud::EstimateNormals builds its own tree there, so
     // that the target / source / loop state of THIS context survive the call ----
     mi_icp_ctx* aux = nullptr;
+
+    // ---- integration::UniformTSDFVolume: the volumes this context made (mi_geometry.hip), freed with it ----
+    std::vector<mi_icp_tsdf*> tsdf_volumes;
 
     // ---- instrumentation ----
     mi::eng::DevBuf stamps;    // loop.h "where an iteration's time goes" (mi_icp_debug_set_step_stamps)
@@ -412,6 +416,7 @@ bool planes_available(const mi_icp_ctx* c);
 int launch_locate_by_planes(mi_icp_ctx* c, const Xform& X, const DevLoop* loop, int gated);
 // ---- mi_geometry.hip
 int occupancy_geometry(int which);
+void tsdf_release_all(mi_icp_ctx* c);     // mi_icp_destroy: the volumes of mi_icp_tsdf_create
 // The points whose flags[0..n) are set, ascending (select.h: exclusive_scan_u32 + select_gather), into out[] (the
 // caller's, staged when mem_kind is MI_ICP_HOST) and their original indices into out_idx (may be null); *m = their
 // count.  One wait on the stream, which also brings back the device word *status (may be null) into *status_out.

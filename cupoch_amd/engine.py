@@ -626,6 +626,105 @@ class Engine:
         k = int(m.value)
         return self._trim(op, k), self._trim(on, k), self._trim(oc, k)
 
+    # -- integration::UniformTSDFVolume (include/mi_icp.h) ----------------------------------------------
+    def tsdf_create(self, length, resolution, sdf_trunc, color_type, origin=None):
+        """-> an opaque volume handle of this engine (mi_icp_tsdf_create)"""
+        o = np.ascontiguousarray(np.zeros(3, np.float32) if origin is None else np.asarray(origin, np.float32).reshape(3))
+        h = C.c_void_p()
+        self._chk(self._L.mi_icp_tsdf_create(self._ctx, float(length), int(resolution), float(sdf_trunc), int(color_type),
+                                             o.ctypes.data_as(C.c_void_p), C.byref(h)))
+        return h
+
+    def tsdf_destroy(self, vol):
+        if getattr(self, "_ctx", None) and vol:
+            self._chk(self._L.mi_icp_tsdf_destroy(self._ctx, vol))
+
+    def tsdf_reset(self, vol):
+        self._chk(self._L.mi_icp_tsdf_reset(self._ctx, vol))
+
+    @staticmethod
+    def _image_desc(x):
+        """(array kept alive, pointer, width, height, channels, bytes per channel, on the device?) of an image:
+        [H, W] or [H, W, C], numpy or torch"""
+        if x is None:
+            return None, None, 0, 0, 0, 0, None
+        on_dev = _is_tensor(x) and x.is_cuda
+        if _is_tensor(x):
+            x = x.contiguous() if on_dev else np.ascontiguousarray(x.numpy())
+        else:
+            x = np.ascontiguousarray(x)
+        if x.ndim not in (2, 3):
+            raise MiIcpError("[UniformTSDFVolume::Integrate] Unsupported image format.")
+        bpc = int(x.element_size()) if on_dev else int(x.dtype.itemsize)
+        ptr = C.c_void_p(x.data_ptr()) if on_dev else x.ctypes.data_as(C.c_void_p)
+        return x, ptr, int(x.shape[1]), int(x.shape[0]), (int(x.shape[2]) if x.ndim == 3 else 1), bpc, on_dev
+
+    def tsdf_integrate(self, vol, depth, color, width, height, intrinsic4, extrinsic=None):
+        """UniformTSDFVolume::Integrate; depth / color numpy or torch, both on the same side.  A format the
+        reference turns away raises MiIcpError."""
+        d, dptr, dw, dh, dc, db, d_dev = self._image_desc(depth)
+        col, cptr, cw, ch, cc, cb, c_dev = self._image_desc(color)
+        if d is None:
+            raise MiIcpError("[UniformTSDFVolume::Integrate] Unsupported image format.")
+        if col is not None and c_dev != d_dev:
+            raise MiIcpError("depth and color must live on the same side")
+        if d_dev:   # a float image must be float: the C ABI sees bytes per channel only
+            ok = d.dtype == torch.float32 and (col is None or col.dtype in (torch.float32, torch.uint8))
+        else:
+            ok = d.dtype == np.float32 and (col is None or col.dtype in (np.float32, np.uint8))
+        if not ok:
+            raise MiIcpError("[UniformTSDFVolume::Integrate] Unsupported image format.")
+        K = (C.c_float * 4)(*[float(v) for v in intrinsic4])
+        _, Eptr = _T_in(extrinsic)
+        self._chk(self._L.mi_icp_tsdf_integrate(self._ctx, vol, dptr, dw, dh, dc, db, cptr, cw, ch, cc, cb, int(width),
+                                                int(height), K, Eptr, MI_ICP_DEVICE if d_dev else MI_ICP_HOST))
+
+    TSDF_FIRST_CAPACITY = 1 << 18   # points an extraction makes room for before it knows the count (9 MB for three arrays)
+
+    def _tsdf_cloud(self, call, want, capacity, device):
+        """the capacity rule of include/mi_icp.h: one call with room for `capacity` points, a second with the room
+        the first asked for only when that was not enough"""
+        kind = MI_ICP_DEVICE if device is not None else MI_ICP_HOST
+        m = C.c_int64(0)
+        outs = [self._out(kind, device, (capacity, 3)) if w else (None, None) for w in want]
+        self._chk(call([p for _, p in outs], capacity, C.byref(m), kind))
+        if int(m.value) > capacity:                     # did not fit: nothing was written, m is the room needed
+            capacity = int(m.value)
+            outs = [self._out(kind, device, (capacity, 3)) if w else (None, None) for w in want]
+            self._chk(call([p for _, p in outs], capacity, C.byref(m), kind))
+        k = int(m.value)
+        return [self._trim(a, k) for a, _ in outs]
+
+    def _tsdf_device(self, on_device):
+        return torch.device("cuda", self.device) if on_device else None
+
+    def tsdf_extract_point_cloud(self, vol, colored, on_device=True):
+        """-> (points, normals, colors or None)"""
+        return self._tsdf_cloud(lambda p, cap, m, kind: self._L.mi_icp_tsdf_extract_point_cloud(
+            self._ctx, vol, p[0], p[1], p[2], cap, m, kind), [True, True, bool(colored)], self.TSDF_FIRST_CAPACITY, self._tsdf_device(on_device))
+
+    def tsdf_extract_voxel_point_cloud(self, vol, on_device=True):
+        """-> (points, colors)"""
+        return self._tsdf_cloud(lambda p, cap, m, kind: self._L.mi_icp_tsdf_extract_voxel_point_cloud(
+            self._ctx, vol, p[0], p[1], cap, m, kind), [True, True], self.TSDF_FIRST_CAPACITY, self._tsdf_device(on_device))
+
+    def tsdf_raycast(self, vol, width, height, intrinsic4, extrinsic, sdf_trunc, valid_only=True, on_device=True):
+        """-> (points, normals, colors) in pixel order; one call, with room for every pixel"""
+        K = (C.c_float * 4)(*[float(v) for v in intrinsic4])
+        keep, Eptr = _T_in(extrinsic)
+        return self._tsdf_cloud(lambda p, cap, m, kind: self._L.mi_icp_tsdf_raycast(
+            self._ctx, vol, int(width), int(height), K, Eptr, float(sdf_trunc), int(bool(valid_only)), p[0], p[1], p[2],
+            cap, m, kind), [True, True, True], int(width) * int(height), self._tsdf_device(on_device))
+
+    def tsdf_get_voxels(self, vol, n, colored, on_device=False):
+        """-> (tsdf[n], weight[n], color[n, 3] or None)"""
+        dev = self._tsdf_device(on_device)
+        kind = MI_ICP_DEVICE if on_device else MI_ICP_HOST
+        (t, tp), (w, wp) = self._out(kind, dev, (n,)), self._out(kind, dev, (n,))
+        c, cp = self._out(kind, dev, (3, n)) if colored else (None, None)
+        self._chk(self._L.mi_icp_tsdf_get_voxels(self._ctx, vol, tp, wp, cp, kind))
+        return t, w, (None if c is None else (c.T.contiguous() if on_device else np.ascontiguousarray(c.T)))
+
     def compute_rgbd_odometry(self, source_color, source_depth, target_color, target_depth, intrinsic4,
                               odo_init=None, jacobian=1, iterations=(20, 10, 5), max_depth_diff=0.03,
                               min_depth=0.0, max_depth=4.0, weighted=False, prev_twist=None, nu=5.0,

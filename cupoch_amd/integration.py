@@ -1,0 +1,97 @@
+"""cupoch.integration mirror (src/cupoch/integration/tsdfvolume.h, uniform_tsdfvolume.h; python surface
+src/python/cupoch_pybind/integration/integration.cpp): TSDFVolumeColorType and UniformTSDFVolume.  The volume lives
+on the GPU, owned by the process-wide engine of its device; every operation runs HIP kernels through the C ABI
+(include/mi_icp.h has the numeric contract).  Not built: extract_triangle_mesh, extract_voxel_grid (no TriangleMesh /
+VoxelGrid type here), ScalableTSDFVolume, integrate_with_depth_to_camera_distance_multiplier."""
+import enum
+
+import numpy as np
+
+from . import geometry, utility
+from ._lib import MiIcpError
+
+
+class TSDFVolumeColorType(enum.IntEnum):
+    NoColor = 0
+    RGB8 = 1
+    Gray32 = 2
+
+
+class TSDFVolume:
+    """tsdfvolume.h:44-74: the base class's fields"""
+
+    def __init__(self, voxel_length, sdf_trunc, color_type):
+        self.voxel_length = float(np.float32(voxel_length))
+        self.sdf_trunc = float(np.float32(sdf_trunc))
+        self.color_type = TSDFVolumeColorType(color_type)
+
+
+def _cloud(p, n, c):
+    out = geometry.PointCloud()
+    out._points = utility.Vector3fVector(p)
+    if n is not None:
+        out._normals = utility.Vector3fVector(n)
+    if c is not None:
+        out._colors = utility.Vector3fVector(c)
+    return out
+
+
+class UniformTSDFVolume(TSDFVolume):
+    def __init__(self, length, resolution, sdf_trunc, color_type, origin=(0.0, 0.0, 0.0), device=None):
+        color_type = TSDFVolumeColorType(color_type)
+        resolution = int(resolution)
+        super().__init__(np.float32(length) / np.float32(resolution), sdf_trunc, color_type)
+        self.length = float(np.float32(length))
+        self.resolution = resolution
+        self.voxel_num = resolution * resolution * resolution
+        self.origin = np.asarray(origin, np.float32).reshape(3).copy()
+        self._eng = geometry.get_engine(device)
+        self._vol = self._eng.tsdf_create(self.length, resolution, self.sdf_trunc, int(color_type), self.origin)
+
+    def __del__(self):
+        try:
+            self._eng.tsdf_destroy(self._vol)
+        except Exception:
+            pass
+        self._vol = None
+
+    def reset(self):
+        self._eng.tsdf_reset(self._vol)
+
+    def integrate(self, image, intrinsic, extrinsic):
+        """UniformTSDFVolume::Integrate(RGBDImage, PinholeCameraIntrinsic, extrinsic).  Returns True; a format the
+        reference turns away ([UniformTSDFVolume::Integrate] Unsupported image format.) is reported, the volume is
+        left as it was and False comes back."""
+        color = None if self.color_type == TSDFVolumeColorType.NoColor else image.color
+        try:
+            if color is None and self.color_type != TSDFVolumeColorType.NoColor:
+                raise MiIcpError("[UniformTSDFVolume::Integrate] Unsupported image format.")
+            self._eng.tsdf_integrate(self._vol, image.depth, color, intrinsic.width, intrinsic.height, intrinsic.as4(),
+                                     extrinsic)
+        except MiIcpError as e:
+            if "Unsupported image format" not in str(e):
+                raise
+            print("[cupoch_amd] Error: [UniformTSDFVolume::Integrate] Unsupported image format.")
+            return False
+        return True
+
+    def extract_point_cloud(self):
+        p, n, c = self._eng.tsdf_extract_point_cloud(self._vol, self.color_type != TSDFVolumeColorType.NoColor)
+        return _cloud(p, n, c)
+
+    def extract_voxel_point_cloud(self):
+        p, c = self._eng.tsdf_extract_voxel_point_cloud(self._vol)
+        return _cloud(p, None, c)
+
+    def raycast(self, intrinsic, extrinsic, sdf_trunc, project_valid_depth_only=True):
+        p, n, c = self._eng.tsdf_raycast(self._vol, intrinsic.width, intrinsic.height, intrinsic.as4(), extrinsic,
+                                         sdf_trunc, project_valid_depth_only)
+        return _cloud(p, n, c)
+
+    def get_voxels(self):
+        """(tsdf[n], weight[n], color[n, 3]) as numpy arrays, n = resolution^3 indexed x*res*res + y*res + z; a
+        NoColor volume reports the colour every voxel starts with, (1, 1, 1)"""
+        t, w, c = self._eng.tsdf_get_voxels(self._vol, self.voxel_num, self.color_type != TSDFVolumeColorType.NoColor)
+        if c is None:
+            c = np.ones((self.voxel_num, 3), np.float32)
+        return t, w, c

@@ -1,24 +1,49 @@
-"""The ICP side of cupoch.kinfu.KinfuPipeline (src/cupoch/kinfu/kinfu.h:36-121, kinfu.cpp:87-143):
-the depth-frame -> point-cloud pyramid of SurfaceMeasurement and the coarse-to-fine PoseEstimation
-that calls RegistrationICP / RegistrationColoredICP once per pyramid level.  The TSDF volume, its
-raycaster and the image filters around them are consumers/producers of this path, not part of it,
-and are not built (scope)."""
+"""The ICP and volume sides of cupoch.kinfu.KinfuPipeline (src/cupoch/kinfu/kinfu.h:36-121, kinfu.cpp:51-143): the
+depth-frame -> point-cloud pyramid of SurfaceMeasurement, the coarse-to-fine PoseEstimation that calls
+RegistrationICP / RegistrationColoredICP once per pyramid level, and the two volume steps of ProcessFrame
+(Integrate, then one Raycast per pyramid level).  ProcessFrame as a whole is not built: it also needs the image
+pyramid and the bilateral depth filter (scope)."""
 import numpy as np
 
 from . import geometry, registration
+from .integration import TSDFVolumeColorType, UniformTSDFVolume
 from .registration import TransformationEstimationType
 
 
 class KinfuOption:
-    """kinfu.h:36-82, the fields PoseEstimation / SurfaceMeasurement read."""
+    """kinfu.h:36-82, the fields PoseEstimation / SurfaceMeasurement and the volume read (diameter, sigma_depth and
+    sigma_space belong to the bilateral filter, which is not built)."""
 
     def __init__(self, num_pyramid_levels=4, depth_cutoff=3.0, distance_threshold=0.5,
-                 icp_iterations=(20, 20, 20, 20), tf_type=TransformationEstimationType.PointToPlane):
+                 icp_iterations=(20, 20, 20, 20), tf_type=TransformationEstimationType.PointToPlane,
+                 tsdf_length=8.0, tsdf_resolution=512, sdf_trunc=0.05, tsdf_color_type=TSDFVolumeColorType.RGB8,
+                 tsdf_origin=(0.0, 0.0, 0.0)):
         self.num_pyramid_levels = int(num_pyramid_levels)
         self.depth_cutoff = float(depth_cutoff)
         self.distance_threshold = float(distance_threshold)
         self.icp_iterations = list(icp_iterations)
         self.tf_type = tf_type
+        self.tsdf_length = float(tsdf_length)
+        self.tsdf_resolution = int(tsdf_resolution)
+        self.sdf_trunc = float(sdf_trunc)
+        self.tsdf_color_type = TSDFVolumeColorType(tsdf_color_type)
+        self.tsdf_origin = np.asarray(tsdf_origin, np.float32).reshape(3)
+
+
+def create_volume(option, device=None):
+    """KinfuPipeline's volume_ (kinfu.cpp:32-36)"""
+    return UniformTSDFVolume(option.tsdf_length, option.tsdf_resolution, option.sdf_trunc, option.tsdf_color_type,
+                             option.tsdf_origin, device)
+
+
+def integrate_and_raycast(volume, option, image, intrinsic, extrinsic):
+    """ProcessFrame's volume steps (kinfu.cpp:69-73): volume.Integrate(image, intrinsic, extrinsic), then
+    volume.Raycast(intrinsic.CreatePyramidLevel(i), extrinsic, sdf_trunc) for every level -- the model pyramid that
+    pose_estimation takes as target_data for the next frame.  None when the frame's format is turned away."""
+    if not volume.integrate(image, intrinsic, extrinsic):
+        return None
+    return [volume.raycast(intrinsic.create_pyramid_level(i), extrinsic, option.sdf_trunc)
+            for i in range(option.num_pyramid_levels)]
 
 
 def point_cloud_pyramid(depth_pyramid, intrinsic, option, color_pyramid=None):

@@ -644,6 +644,142 @@ MI_ICP_API int mi_icp_gaussian_filter(mi_icp_ctx* ctx, const float* xyz, const f
                                       int num_max_search_points, float* out_xyz, float* out_normals,
                                       float* out_colors, int mem_kind);
 
+/* ---- integration::UniformTSDFVolume (integration/uniform_tsdfvolume.{h,cu}, integrate_functor.h,
+ * tsdfvolume.h; the multiplier image of geometry/image_factory.cu:32-48,136-165) ----------------------
+ * A volume of resolution^3 voxels of edge voxel_length = length / (float)resolution, each holding
+ * (tsdf, weight, colour[3]), indexed x*res*res + y*res + z.  It belongs to the context that made it:
+ * mi_icp_destroy frees the volumes still alive, and a volume is only accepted by its own context.
+ * Stored as planes (tsdf, weight, and three colour planes only when color_type != NO_COLOR): 8 or 20
+ * bytes per voxel.  Not built: ExtractTriangleMesh, ExtractVoxelGrid (there is no TriangleMesh or
+ * VoxelGrid type here), ScalableTSDFVolume, IntegrateWithDepthToCameraDistanceMultiplier as an entry.
+ *
+ * THE NUMERIC CONTRACT.  Everything is fp32, products and sums unfused, division and square root
+ * correctly rounded, in the order written; three-term sums and dot products run left to right,
+ * (a + b) + c.  h = resolution / 2 (integer division; odd resolutions are legal), half =
+ * 0.5f * voxel_length, E the extrinsic, D[r] = voxel_length * E[r][2].  A numpy fp32 restatement of
+ * these lines is bit-equal to the kernels (tests/tsdf_exact.py).
+ *  Reset      tsdf 0, weight 0, colour (1, 1, 1); a new volume is reset.
+ *  Integrate  multiplier(i, j) = sqrtf((xx*xx + yy*yy) + 1), xx = ((float)j - cx) * (1/fx),
+ *             yy = ((float)i - cy) * (1/fy); built once per (width, height, intrinsic) and kept.
+ *             For voxel (x, y, z), xr = x - h etc.:
+ *               px = (half + voxel_length*xr) + origin[0], py likewise, pz = half + origin[2] (z = 0)
+ *               P[r] = (((E[r][0]*px + E[r][1]*py) + E[r][2]*pz) + E[r][3]) + (float)zr * D[r]
+ *               skip if P[2] <= 0
+ *               u_f = (P[0]*fx / P[2] + cx) + 0.5f, v_f = (P[1]*fy / P[2] + cy) + 0.5f
+ *               skip unless u_f >= 0.0001f && u_f < (float)width - 0.0001f && v_f >= 0.0001f &&
+ *                           v_f < (float)height - 0.0001f
+ *               u = floor(u_f), v = floor(v_f); d = depth(v, u); skip if d <= 0
+ *               sdf = (d - P[2]) * multiplier(v, u); skip unless sdf > -sdf_trunc
+ *               t = min(1, sdf * (float)(1.0 / (double)sdf_trunc))   (clamped from above only)
+ *               tsdf = (tsdf*w + t) / (w + 1); each colour channel c = (c*w + s) / (w + 1) with s the
+ *               RGB8 byte of that channel (kept in 0..255) or the Gray32 value (in all three);
+ *               weight = w + 1.
+ *             A voxel that is skipped is neither read nor written.
+ *  valid      w != 0 && tsdf < 0.98f && tsdf >= -0.98f
+ *  ExtractVoxelPointCloud   the valid voxels in ascending index: point ((half + voxel_length*xr) +
+ *             origin[0], ...), colour (c, c, c) with c = (float)(((double)tsdf + 1.0) * 0.5).
+ *  ExtractPointCloud   candidates in ascending (((x-1)*(res-2) + (y-1))*(res-2) + (z-1))*3 + axis over
+ *             x, y, z in [1, res-2]: voxel 0 = (x, y, z) valid, voxel 1 = its neighbour at +1 along axis
+ *             with that coordinate + 1 < res - 1, valid, and f0*f1 < 0.  Then r0 = |f0|, r1 = |f1|,
+ *               q = (half + voxel_length*x, half + voxel_length*y, half + voxel_length*z)  (x not - h)
+ *               q[axis] = (q[axis]*r1 + (q[axis] + voxel_length)*r0) / (r0 + r1)
+ *               point = (q + origin) - (float)h * voxel_length
+ *               colour = (c0*r1 + c1*r0) / (r0 + r1), for RGB8 then / 255.0f; none for NO_COLOR
+ *               normal: n[k] = T(q with q[k] := (float)((double)q[k] + gap)) - T(q with q[k] :=
+ *               (float)((double)q[k] - gap)), gap = 0.99 * (double)voxel_length; with zz = (n0*n0 +
+ *               n1*n1) + n2*n2: n / sqrtf(zz) when zz > 0, else n as it is (Eigen's normalized()).
+ *               T(p) (GetTSDFAt): g = p / voxel_length - 0.5f, i = floor(g), r = g - (float)i,
+ *               s = 0; s += (1-r0)*(1-r1)*(1-r2)*t000; s += (1-r0)*(1-r1)*r2*t001; ... in the order
+ *               000, 001, 010, 011, 100, 101, 110, 111 of (x, y, z) offsets, each product left to right.
+ *  Raycast    pose = utility::InverseTransform(extrinsic): R = E[0..2][0..2]^T, pt[r] = ((-R[r][0])*t0 +
+ *             (-R[r][1])*t1) + (-R[r][2])*t2 with t the extrinsic's last column; t = pt - origin.
+ *             Pixel (x, y): pp = (((float)x - cx) / fx, ((float)y - cy) / fy, 1);
+ *             dir[r] = (R[r][0]*pp0 + R[r][1]*pp1) + R[r][2]; dn = sqrtf((d0*d0 + d1*d1) + d2*d2);
+ *             dir = dir / dn.  length = (float)res * voxel_length, step = sdf_trunc * 0.5f.
+ *               tmin = fmax(fmax(q0, q1), q2), q_k = ((dir_k > 0 ? 0 : length) - t_k) / dir_k
+ *               tmax = fmin(fmin(...)) of ((dir_k > 0 ? length : 0) - t_k) / dir_k
+ *             -- IEEE quotients: a zero direction component gives +-inf or NaN, and fmax / fmin return
+ *             the operand that is not NaN (np.fmax / np.fmin).  As in the reference the box tested is
+ *             [0, length]^3 in t's frame although the voxels cover [-h*voxel_length, (res-h)*voxel_length).
+ *               len = fmax(tmin, 0); invalid if len >= tmax; len = len + voxel_length
+ *               g = floor((t + dir*len) / voxel_length) + h; invalid unless every g_k in [0, res-1)
+ *               cur = tsdf(g); max = len + length * 1.41421354f
+ *               for (; len < max; len = len + step):
+ *                 g = floor((t + dir*(len + step)) / voxel_length) + h; unless every g_k in [1, res-1): next
+ *                 prev = cur; cur = tsdf(g); if prev < 0 && cur > 0: invalid
+ *                 if prev > 0 && cur < 0:
+ *                   ts = len - step*prev / (cur - prev); vtx = t + dir*ts; loc = vtx / voxel_length + (float)h
+ *                   invalid unless every loc_k in [1, res-1), and for each axis loc_k + 1 < res-1 and
+ *                   loc_k - 1 >= 1; n[k] = I(loc + e_k) - I(loc - e_k); nn = sqrtf((n0*n0 + n1*n1) + n2*n2);
+ *                   invalid if nn == 0; normal = n / nn; point = vtx + origin;
+ *                   colour of voxel (int)loc: RGB8 (float)((double)c / 255.0), Gray32 c, NO_COLOR 0.
+ *               I(p) (InterpolateTrilinearly): i = (int)p, i_k -= 1 where p_k < (float)i_k + 0.5f,
+ *               a = p - ((float)i + 0.5f); ((((((t000*(1-a0)*(1-a1)*(1-a2) + t001*(1-a0)*(1-a1)*a2) +
+ *               t010*(1-a0)*a1*(1-a2)) + t011*(1-a0)*a1*a2) + t100*a0*(1-a1)*(1-a2)) + t101*a0*(1-a1)*a2)
+ *               + t110*a0*a1*(1-a2)) + t111*a0*a1*a2, each product left to right.
+ *             Output in pixel order; invalid pixels are NaN in all nine values, removed
+ *             (RemoveNoneFinitePoints(true, true)) when valid_only != 0.
+ *  Where the reference leaves something undefined, the choice made:
+ *   - float -> int of floor(x): x is held inside +-1e9 first, a NaN counting as -1e9 (out of range).
+ *   - dn not > 0 (zero, or NaN): invalid (the reference tests == 0 only).
+ *   - len not finite after the tmin / tmax test (tmax NaN): invalid.
+ *   - a march that cannot advance, max + step == max in fp32 (camera ~1e6 steps away): invalid; the
+ *     reference does not terminate.  sdf_trunc must be positive, finite and large enough for
+ *     length * sqrt(2) / step <= MI_ICP_TSDF_MAX_MARCH, else MI_ICP_ERR_INVALID.
+ *   - the gathers of T and I hold their indices inside [0, res-2]; for finite input they are there.
+ *   - ExtractPointCloud's candidates are chosen by the crossing test; the reference tests the emitted
+ *     point for NaN, which differs only for a non-finite origin.
+ *   - non-finite extrinsics, intrinsics, origins or volumes are outside the contract; every call
+ *     terminates and stays inside its buffers.
+ *  Deviation (deliberate): the reference sizes ExtractPointCloud's outputs by the number of valid
+ *  voxels and writes up to three points per voxel into them; here outputs hold the actual count.
+ *
+ * OUTPUTS OF UNKNOWN SIZE follow one rule in all three calls: the caller passes a `capacity` (in
+ * points) and gets the needed count in *m.  When capacity >= *m the arrays are filled with *m points;
+ * otherwise nothing is written and the call is MI_ICP_OK -- call again with room (capacity 0 and null
+ * arrays make a pure count query).  A raycast never needs more than width*height.
+ *
+ * mi_icp_tsdf_integrate: the images are described as the reference's Image fields are, and checked as
+ * there (uniform_tsdfvolume.cu:677-695): depth 1 channel of 4 bytes (float32); colour 3 x 1 byte for
+ * RGB8, 1 x 4 bytes (float32) for GRAY32, ignored for NO_COLOR; all sizes equal to width x height of
+ * the intrinsic.  Otherwise MI_ICP_ERR_INVALID ("[UniformTSDFVolume::Integrate] Unsupported image
+ * format."), the volume untouched.  intrinsic4 = fx, fy, cx, cy; extrinsic column-major 4x4 (NULL:
+ * identity).  Traffic: the images once per voxel that projects into them, 8 (NO_COLOR) or 20 bytes
+ * read and written per UPDATED voxel, nothing for the others.
+ * mi_icp_tsdf_get_voxels: tsdf_out[n], weight_out[n], color_out[3][n] (planes; NO_COLOR volumes have
+ * none: pass NULL), each may be NULL.
+ * Limits: length, sdf_trunc > 0 and finite, 3 <= resolution <= MI_ICP_TSDF_MAX_RESOLUTION, image width and
+ * height each at most MI_ICP_TSDF_MAX_IMAGE_SIDE (integrate and raycast; else MI_ICP_ERR_INVALID).  The extractions and a valid_only raycast wait for the stream once for the count and
+ * once more after the fill; integrate waits only to release MI_ICP_HOST images. */
+#define MI_ICP_TSDF_NO_COLOR 0
+#define MI_ICP_TSDF_RGB8 1
+#define MI_ICP_TSDF_GRAY32 2
+#define MI_ICP_TSDF_MAX_RESOLUTION 1024
+#define MI_ICP_TSDF_MAX_MARCH 1048576
+#define MI_ICP_TSDF_MAX_IMAGE_SIDE 32768
+typedef struct mi_icp_tsdf mi_icp_tsdf;
+MI_ICP_API int mi_icp_tsdf_create(mi_icp_ctx* ctx, float length, int resolution, float sdf_trunc, int color_type,
+                                  const float* origin3, mi_icp_tsdf** out);
+MI_ICP_API int mi_icp_tsdf_destroy(mi_icp_ctx* ctx, mi_icp_tsdf* volume);
+MI_ICP_API int mi_icp_tsdf_reset(mi_icp_ctx* ctx, mi_icp_tsdf* volume);
+MI_ICP_API int mi_icp_tsdf_integrate(mi_icp_ctx* ctx, mi_icp_tsdf* volume, const void* depth, int depth_width,
+                                     int depth_height, int depth_channels, int depth_bytes_per_channel,
+                                     const void* color, int color_width, int color_height, int color_channels,
+                                     int color_bytes_per_channel, int width, int height, const float* intrinsic4,
+                                     const float* extrinsic, int mem_kind);
+MI_ICP_API int mi_icp_tsdf_extract_point_cloud(mi_icp_ctx* ctx, mi_icp_tsdf* volume, float* out_xyz,
+                                               float* out_normals, float* out_colors, int64_t capacity,
+                                               int64_t* m, int mem_kind);
+MI_ICP_API int mi_icp_tsdf_extract_voxel_point_cloud(mi_icp_ctx* ctx, mi_icp_tsdf* volume, float* out_xyz,
+                                                     float* out_colors, int64_t capacity, int64_t* m,
+                                                     int mem_kind);
+MI_ICP_API int mi_icp_tsdf_raycast(mi_icp_ctx* ctx, mi_icp_tsdf* volume, int width, int height,
+                                   const float* intrinsic4, const float* extrinsic, float sdf_trunc,
+                                   int valid_only, float* out_xyz, float* out_normals, float* out_colors,
+                                   int64_t capacity, int64_t* m, int mem_kind);
+MI_ICP_API int mi_icp_tsdf_get_voxels(mi_icp_ctx* ctx, mi_icp_tsdf* volume, float* tsdf_out, float* weight_out,
+                                      float* color_out, int mem_kind);
+
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
  * float[nq][3] against the cloud given to mi_icp_set_target: per query the knn
