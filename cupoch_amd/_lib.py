@@ -18,7 +18,7 @@ INCLUDE = os.path.join(ROOT, "include")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I/opt/rocm/include"]
 # the library's translation units (csrc/ctx.h says what each holds); compiled side by side, then linked
-UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_knn", "mi_comm", "mi_debug"]
+UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_knn", "mi_comm", "mi_debug"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 MI_ICP_HOST, MI_ICP_DEVICE = 0, 1

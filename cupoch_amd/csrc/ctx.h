@@ -2,8 +2,11 @@
 // allocation / staging helpers, and the declarations of the host-side functions one unit offers the others.
 //   mi_icp.hip       context life cycle, the correspondence search, the reduction, the device-resident loop
 //   mi_build.hip     target tree (kd cells, groups, levels, halos), source staging, the match-order re-sort
-//   mi_geometry.hip  Transform / bounds / affine / covariances / VoxelDownSample / SelectByIndex / SelectByMask /
-//                    UniformDownSample / SegmentPlane / depth frames / RGB-D odometry / colours / UniformTSDFVolume
+//   mi_geometry.hip  Transform / bounds / affine / covariances / SelectByIndex / SelectByMask / UniformDownSample /
+//                    FarthestPointDownSample / the predicate filters / compact_by_flags / SegmentPlane / colours
+//   mi_voxel.hip     VoxelDownSample (the dense-grid path and the general one)
+//   mi_rgbd.hip      depth / RGB-D frame -> cloud, RGB-D odometry
+//   mi_tsdf.hip      UniformTSDFVolume
 //   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry,
 //                    RemoveStatisticalOutliers / RemoveRadiusOutliers, ClusterDBSCAN, ComputeISSKeypoints
 //   mi_comm.hip      the ranks' exchange: mailbox, device inboxes, in-library RCCL, self-test and choice
@@ -161,7 +164,7 @@ struct mi_icp_ctx {
     // that the target / source / loop state of THIS context survive the call ----
     mi_icp_ctx* aux = nullptr;
 
-    // ---- integration::UniformTSDFVolume: the volumes this context made (mi_geometry.hip), freed with it ----
+    // ---- integration::UniformTSDFVolume: the volumes this context made (mi_tsdf.hip), freed with it ----
     std::vector<mi_icp_tsdf*> tsdf_volumes;
 
     // ---- instrumentation ----
@@ -380,6 +383,111 @@ inline int check_ctx(mi_icp_ctx* c, int mem_kind, const char* what) {
     return MI_ICP_OK;
 }
 
+// ---- What the cloud-in, cloud-out entry points share.  A cloud is three arrays: points, normals, colours (the last two
+// ---- optional).  An entry point makes each check where its contract places it: the order is part of the interface.
+// Sizes: the context and the memory kind, m (zeroed from here on), 0 <= n <= 0x7fffff00 (positions and counts are 32-bit).
+inline int check_sizes(mi_icp_ctx* c, const char* what, int64_t n, int64_t* m, int mem_kind) {
+    TRY(check_ctx(c, mem_kind, what));
+    if (!m) return fail(c, MI_ICP_ERR_INVALID, "%s: m is null", what);
+    *m = 0;
+    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    return MI_ICP_OK;
+}
+
+struct Cloud {
+    const float* in[3];  // the caller's arrays; after cloud_in / cloud_upload their device view
+    float* out[3];       // the caller's outputs
+};
+
+// the null-buffer rule: points in and out, and an output for every attribute that comes in
+inline int cloud_check(mi_icp_ctx* c, const char* what, const Cloud& a) {
+    if (!a.in[0] || !a.out[0] || (a.in[1] && !a.out[1]) || (a.in[2] && !a.out[2]))
+        return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+    return MI_ICP_OK;
+}
+
+inline int cloud_upload(mi_icp_ctx* c, Cloud* a, int64_t n, int mem_kind, DevBuf* stage) {
+    for (int k = 0; k < 3; ++k) TRY(to_device(c, a->in[k], (size_t)n * 3, mem_kind, stage[k], &a->in[k]));
+    return MI_ICP_OK;
+}
+
+inline int cloud_in(mi_icp_ctx* c, const char* what, Cloud* a, int64_t n, int mem_kind, DevBuf* stage) {
+    TRY(cloud_check(c, what, *a));
+    return cloud_upload(c, a, n, mem_kind, stage);
+}
+
+// Where up to `count` points of an output cloud go: the caller's arrays out[], or (MI_ICP_HOST) stage[0..2]; nullptr for
+// an attribute that in[] does not have.  cloud_out_back copies `m` of them to the caller.
+inline int cloud_out(mi_icp_ctx* c, const float* const in[3], float* const out[3], int64_t count, int mem_kind,
+                     DevBuf* stage, float* dst[3]) {
+    for (int k = 0; k < 3; ++k) TRY(out_slot(c, in[k] ? out[k] : nullptr, (size_t)count * 3, mem_kind, stage[k], &dst[k]));
+    return MI_ICP_OK;
+}
+
+inline int cloud_out_back(mi_icp_ctx* c, float* const dst[3], float* const out[3], int64_t m, int mem_kind) {
+    for (int k = 0; k < 3; ++k)
+        if (dst[k]) TRY(from_device(c, (const float*)dst[k], out[k], (size_t)m * 3, mem_kind));
+    return MI_ICP_OK;
+}
+
+// Emit: room for `count` points, launch(dst) writes them, `m` of them go back to the caller, one wait.
+template <class Launch>
+int cloud_emit(mi_icp_ctx* c, const float* const in[3], float* const out[3], int64_t count, int64_t m, int mem_kind,
+               DevBuf* stage, Launch launch) {
+    float* dst[3];
+    TRY(cloud_out(c, in, out, count, mem_kind, stage, dst));
+    launch(dst);
+    KCHK(c);
+    TRY(cloud_out_back(c, dst, out, m, mem_kind));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MI_ICP_OK;
+}
+
+// Scan: pos[i] = flags[0] + ... + flags[i - 1] (pos may be flags itself); *total is the device word that holds the sum
+// of all n.  The one place that knows where exclusive_scan_u32 leaves it.
+inline int scan_into(mi_icp_ctx* c, const uint32_t* flags, uint32_t* pos, int64_t n, const uint32_t** total) {
+    uint32_t* tmp;
+    TRY(ensure(c, c->scan_tmp, (size_t)scan_num_tiles(n) + 2, &tmp));
+    exclusive_scan_u32(c->stream, flags, pos, n, tmp);
+    KCHK(c);
+    *total = tmp + scan_num_tiles(n);
+    return MI_ICP_OK;
+}
+
+// ... with the positions in c->dense_idx
+inline int scan_flags(mi_icp_ctx* c, const uint32_t* flags, int64_t n, uint32_t** pos, const uint32_t** total) {
+    TRY(ensure(c, c->dense_idx, (size_t)n, pos));
+    return scan_into(c, flags, *pos, n, total);
+}
+
+// the total on its way to c->u_host[slot]: there after the next wait
+inline int read_total(mi_icp_ctx* c, const uint32_t* total, int slot = 0) {
+    HIPCHK(c, hipMemcpyAsync(c->u_host + slot, total, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    return MI_ICP_OK;
+}
+
+// Counted compaction, for a caller that gives a capacity: scan, wait for the count, *m = it; nothing is written when it
+// is zero or above `capacity` (the caller learns the room to make).  Else out[k] must be there wherever want[k], and
+// launch(pos, dst) writes the cloud.
+template <class Launch>
+int cloud_emit_counted(mi_icp_ctx* c, const char* what, const uint32_t* flags, int64_t n, float* const out_all[3],
+                       const bool (&want)[3], int64_t capacity, int64_t* m, int mem_kind, Launch launch) {
+    uint32_t* pos;
+    const uint32_t* total;
+    TRY(scan_flags(c, flags, n, &pos, &total));
+    TRY(read_total(c, total));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t cnt = (int64_t)c->u_host[0];
+    *m = cnt;
+    if (cnt == 0 || capacity < cnt) return MI_ICP_OK;
+    float* out[3];
+    for (int k = 0; k < 3; ++k) {
+        if (want[k] && !out_all[k]) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+        out[k] = want[k] ? out_all[k] : nullptr;
+    }
+    return cloud_emit(c, out, out, cnt, cnt, mem_kind, c->vpay, [&](float* const dst[3]) { launch(pos, dst); });
+}
+
 // Runs body(a) in the private scratch context a = c->aux (made on first use, on c's stream): a registration in flight
 // on c (user estimators may call EstimateNormals between iterations) keeps its target, source, correspondences and
 // loop state.  A failure is reported on c as "what: <a's error>".
@@ -414,9 +522,11 @@ int launch_nn(mi_icp_ctx* c, const Mat4& T, float r2, bool seed, unsigned long l
 int occupancy_loop(int which);
 bool planes_available(const mi_icp_ctx* c);
 int launch_locate_by_planes(mi_icp_ctx* c, const Xform& X, const DevLoop* loop, int gated);
-// ---- mi_geometry.hip
+// ---- mi_voxel.hip
 int occupancy_geometry(int which);
+// ---- mi_tsdf.hip
 void tsdf_release_all(mi_icp_ctx* c);     // mi_icp_destroy: the volumes of mi_icp_tsdf_create
+// ---- mi_geometry.hip
 // The points whose flags[0..n) are set, ascending (select.h: exclusive_scan_u32 + select_gather), into out[] (the
 // caller's, staged when mem_kind is MI_ICP_HOST) and their original indices into out_idx (may be null); *m = their
 // count.  One wait on the stream, which also brings back the device word *status (may be null) into *status_out.

@@ -75,14 +75,13 @@ int mi_icp_debug_exclusive_scan(mi_icp_ctx* c, const uint32_t* in, uint32_t* out
     if (n < 0 || (n > 0 && (!in || !out))) return fail(c, MI_ICP_ERR_INVALID, "debug_exclusive_scan: bad arguments");
     if (total) *total = 0;
     if (n == 0) return MI_ICP_OK;
-    uint32_t *d, *tmp;
+    uint32_t* d;
+    const uint32_t* sum;
     TRY(ensure(c, c->flags, (size_t)n, &d));
-    TRY(ensure(c, c->scan_tmp, (size_t)scan_num_tiles(n) + 2, &tmp));
     HIPCHK(c, hipMemcpyAsync(d, in, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    exclusive_scan_u32(c->stream, d, d, n, tmp);
-    KCHK(c);
+    TRY(scan_into(c, d, d, n, &sum));
     HIPCHK(c, hipMemcpyAsync(out, d, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->u_host, tmp + scan_num_tiles(n), 4, hipMemcpyDeviceToHost, c->stream));
+    TRY(read_total(c, sum));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (total) *total = c->u_host[0];
     return MI_ICP_OK;

@@ -517,18 +517,17 @@ int mi_icp_get_correspondences(mi_icp_ctx* c, int32_t* pairs, int64_t capacity, 
     if (!c->nn_valid || c->ns <= 0 || c->nt <= 0) return MI_ICP_OK;
     int32_t* dense;
     TRY(export_dense_idx(c, &dense));
-    uint32_t *flags, *tmp;
+    uint32_t* flags;
+    const uint32_t* total;
     int32_t* out;
     TRY(ensure(c, c->flags, (size_t)c->ns, &flags));
-    TRY(ensure(c, c->scan_tmp, (size_t)scan_num_tiles(c->ns) + 2, &tmp));
     TRY(ensure(c, c->pairs_out, (size_t)c->ns * 2, &out));
     corr_flags<<<blocks_for(c->ns), 256, 0, c->stream>>>(dense, (int)c->ns, flags);
     KCHK(c);
-    exclusive_scan_u32(c->stream, flags, flags, c->ns, tmp);
-    KCHK(c);
+    TRY(scan_into(c, flags, flags, c->ns, &total));
     corr_compact<<<blocks_for(c->ns), 256, 0, c->stream>>>(dense, flags, (int)c->ns, out);
     KCHK(c);
-    HIPCHK(c, hipMemcpyAsync(c->u_host, tmp + scan_num_tiles(c->ns), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    TRY(read_total(c, total));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int64_t m = (int64_t)c->u_host[0];
     *count = m;

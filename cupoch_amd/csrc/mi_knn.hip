@@ -111,11 +111,9 @@ static int outlier_impl(mi_icp_ctx* c, const char* what, bool radius, const floa
                         int mem_kind) {
     if (n == 0) return MI_ICP_OK;
     return in_scratch(c, what, [&](mi_icp_ctx* a) -> int {
-        const float* in[3];
-        TRY(to_device(a, xyz, (size_t)n * 3, mem_kind, a->stage[0], &in[0]));
-        TRY(to_device(a, normals, (size_t)n * 3, mem_kind, a->stage[1], &in[1]));
-        TRY(to_device(a, colors, (size_t)n * 3, mem_kind, a->stage[2], &in[2]));
-        TRY(mi_icp_set_target(a, in[0], nullptr, nullptr, n, MI_ICP_DEVICE));
+        Cloud cl{{xyz, normals, colors}, {out_xyz, out_normals, out_colors}};
+        TRY(cloud_upload(a, &cl, n, mem_kind, a->stage));
+        TRY(mi_icp_set_target(a, cl.in[0], nullptr, nullptr, n, MI_ICP_DEVICE));
         float* stat;  // float avg or int32 count, [n] in the cloud's order
         TRY(out_slot(a, (float*)stat_out, (size_t)n, mem_kind, a->stage[3], &stat));
         if (!stat) TRY(ensure(a, a->stage[3], (size_t)n, &stat));  // (the caller does not want them)
@@ -136,18 +134,15 @@ static int outlier_impl(mi_icp_ctx* c, const char* what, bool radius, const floa
         }
         KCHK(a);
         TRY(from_device(a, (const float*)stat, (float*)stat_out, (size_t)n, mem_kind));
-        float* const out[3] = {out_xyz, out_normals, out_colors};
-        return compact_by_flags(a, flags, n, in, out, out_indices, mem_kind, nullptr, m, nullptr);
+        return compact_by_flags(a, flags, n, cl.in, cl.out, out_indices, mem_kind, nullptr, m, nullptr);
     });
 }
 
+// (the buffers before the filter's own parameters)
 static int outlier_args(mi_icp_ctx* c, const char* what, const float* xyz, const float* normals, const float* colors,
-                        int64_t n, float* out_xyz, float* out_normals, float* out_colors, int64_t* m) {
-    if (!m) return fail(c, MI_ICP_ERR_INVALID, "%s: m is null", what);
-    *m = 0;
-    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
-    if (n > 0 && (!xyz || !out_xyz || (normals && !out_normals) || (colors && !out_colors)))
-        return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+                        int64_t n, float* out_xyz, float* out_normals, float* out_colors, int64_t* m, int mem_kind) {
+    TRY(check_sizes(c, what, n, m, mem_kind));
+    if (n > 0) TRY(cloud_check(c, what, Cloud{{xyz, normals, colors}, {out_xyz, out_normals, out_colors}}));
     return MI_ICP_OK;
 }
 
@@ -155,8 +150,7 @@ int mi_icp_remove_statistical_outliers(mi_icp_ctx* c, const float* xyz, const fl
                                        int64_t n, int nb_neighbors, float std_ratio, float* out_xyz, float* out_normals,
                                        float* out_colors, int64_t* out_indices, float* avg_d2, int64_t* m, int mem_kind) {
     const char* what = "remove_statistical_outliers";
-    TRY(check_ctx(c, mem_kind, what));
-    TRY(outlier_args(c, what, xyz, normals, colors, n, out_xyz, out_normals, out_colors, m));
+    TRY(outlier_args(c, what, xyz, normals, colors, n, out_xyz, out_normals, out_colors, m, mem_kind));
     if (nb_neighbors < 1) return fail(c, MI_ICP_ERR_INVALID, "%s: nb_neighbors must be positive", what);
     if (!(std_ratio > 0.0f)) return fail(c, MI_ICP_ERR_INVALID, "%s: std_ratio must be positive", what);
     if (nb_neighbors > kKnnLimit)
@@ -169,8 +163,7 @@ int mi_icp_remove_radius_outliers(mi_icp_ctx* c, const float* xyz, const float* 
                                   int nb_points, float radius, float* out_xyz, float* out_normals, float* out_colors,
                                   int64_t* out_indices, int32_t* counts, int64_t* m, int mem_kind) {
     const char* what = "remove_radius_outliers";
-    TRY(check_ctx(c, mem_kind, what));
-    TRY(outlier_args(c, what, xyz, normals, colors, n, out_xyz, out_normals, out_colors, m));
+    TRY(outlier_args(c, what, xyz, normals, colors, n, out_xyz, out_normals, out_colors, m, mem_kind));
     if (nb_points < 1) return fail(c, MI_ICP_ERR_INVALID, "%s: nb_points must be positive", what);
     if (!(radius > 0.0f)) return fail(c, MI_ICP_ERR_INVALID, "%s: search_radius must be positive", what);
     if (nb_points + 1 > kKnnLimit)
@@ -193,12 +186,11 @@ static int dbscan_impl(mi_icp_ctx* c, const float* xyz, int64_t n, float r2, int
         int32_t *rows, *node;
         uint4* mask;
         DbscanState* st;
-        uint32_t* tmp;
+        const uint32_t* total;
         TRY(ensure(a, a->dbs[0], (size_t)n * k, &rows));
         TRY(ensure(a, a->dbs[1], (size_t)n * 6, &node));
         TRY(ensure(a, a->dbs[2], (size_t)n, &mask));
         TRY(ensure(a, a->dbs[3], (size_t)1, &st));
-        TRY(ensure(a, a->scan_tmp, (size_t)scan_num_tiles(n) + 2, &tmp));
         int32_t *word = node, *rep = node + n, *m = node + 2 * n, *Mx = node + 3 * n;
         uint32_t* start = (uint32_t*)(node + 4 * n);
         uint32_t* number = (uint32_t*)(node + 5 * n);
@@ -219,12 +211,11 @@ static int dbscan_impl(mi_icp_ctx* c, const float* xyz, int64_t n, float r2, int
                 dbscan_step<<<1, 64, 0, a->stream>>>(st);
             }
             dbscan_starts<<<nb, 256, 0, a->stream>>>(word, rep, m, n, min_points, st, start);
-            exclusive_scan_u32(a->stream, start, number, n, tmp);
+            TRY(scan_into(a, start, number, n, &total));
             dbscan_labels<<<nb, 256, 0, a->stream>>>(word, rep, m, Mx, start, number, n, st, dl, dd);
             KCHK(a);
             HIPCHK(a, hipMemcpyAsync(a->u_host, st, sizeof(DbscanState), hipMemcpyDeviceToHost, a->stream));
-            HIPCHK(a, hipMemcpyAsync(a->u_host + 4, tmp + scan_num_tiles(n), sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                     a->stream));
+            TRY(read_total(a, total, 4));
             TRY(from_device(a, (const int32_t*)dl, labels, (size_t)n, mem_kind));
             TRY(from_device(a, (const int32_t*)dd, degrees, (size_t)n, mem_kind));
             HIPCHK(a, hipStreamSynchronize(a->stream));
@@ -244,6 +235,7 @@ static int dbscan_impl(mi_icp_ctx* c, const float* xyz, int64_t n, float r2, int
 int mi_icp_cluster_dbscan(mi_icp_ctx* c, const float* xyz, int64_t n, float eps, int64_t min_points, int max_edges,
                           int32_t* labels, int32_t* degrees, int64_t* n_clusters, int mem_kind) {
     const char* what = "cluster_dbscan";
+    // (its own preamble: the count is n_clusters, and the message says so)
     TRY(check_ctx(c, mem_kind, what));
     if (!n_clusters) return fail(c, MI_ICP_ERR_INVALID, "%s: n_clusters is null", what);
     *n_clusters = 0;
@@ -298,15 +290,14 @@ static int iss_impl(mi_icp_ctx* c, const char* what, const float* xyz, int64_t n
         float *sal, *eig;
         int32_t* cnt;
         uint8_t* mask;
-        uint32_t *flags, *pos, *tmp;
+        uint32_t *flags, *pos;
+        const uint32_t* total;
         TRY(out_slot(a, saliency_out, (size_t)n, mem_kind, a->stage[1], &sal));
         if (!sal) TRY(ensure(a, a->stage[1], (size_t)n, &sal));  // (the caller does not want it; pass 1 does)
         TRY(out_slot(a, eig_out, (size_t)n * 3, mem_kind, a->stage[2], &eig));
         TRY(out_slot(a, counts_out, (size_t)n, mem_kind, a->stage[3], &cnt));
         TRY(out_slot(a, mask_out, (size_t)n, mem_kind, a->stage[4], &mask));
         TRY(ensure(a, a->flags, (size_t)n, &flags));
-        TRY(ensure(a, a->dense_idx, (size_t)n, &pos));
-        TRY(ensure(a, a->scan_tmp, (size_t)scan_num_tiles(n) + 2, &tmp));
         const uint32_t nblocks = (uint32_t)((a->nleaf + 7) / 8);
         auto pass = [&](auto which, float r2) -> int {
             return knn_launch(a, k, nblocks, [](auto kc) { return iss_kernel<decltype(which)::value, decltype(kc)::value>; },
@@ -315,9 +306,8 @@ static int iss_impl(mi_icp_ctx* c, const char* what, const float* xyz, int64_t n
         };
         TRY(pass(Cap<0>(), rs * rs));
         TRY(pass(Cap<1>(), rn * rn));
-        exclusive_scan_u32(s, flags, pos, n, tmp);
-        KCHK(a);
-        HIPCHK(a, hipMemcpyAsync(a->u_host, tmp + scan_num_tiles(n), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        TRY(scan_flags(a, flags, n, &pos, &total));
+        TRY(read_total(a, total));
         TRY(from_device(a, (const float*)sal, saliency_out, (size_t)n, mem_kind));
         TRY(from_device(a, (const float*)eig, eig_out, (size_t)n * 3, mem_kind));
         TRY(from_device(a, (const int32_t*)cnt, counts_out, (size_t)n, mem_kind));
@@ -333,6 +323,7 @@ int mi_icp_iss_keypoints(mi_icp_ctx* c, const float* xyz, int64_t n, float salie
                          float* saliency_out, float* eig_out, int32_t* counts_out, float* radii_out, int64_t* m,
                          int mem_kind) {
     const char* what = "iss_keypoints";
+    // (its own preamble: radii_out is filled in between m and the size)
     TRY(check_ctx(c, mem_kind, what));
     if (!m) return fail(c, MI_ICP_ERR_INVALID, "%s: m is null", what);
     *m = 0;
@@ -367,23 +358,19 @@ int mi_icp_gaussian_filter(mi_icp_ctx* c, const float* xyz, const float* normals
     if (num_max_search_points < 1 || num_max_search_points > kKnnLimit)
         return fail(c, MI_ICP_ERR_INVALID, "%s: num_max_search_points outside [1, %d] (knn::NUM_MAX_NN)", what, kKnnLimit);
     if (n == 0) return MI_ICP_OK;
-    if (!xyz || !out_xyz || (normals && !out_normals) || (colors && !out_colors))
-        return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+    Cloud cl{{xyz, normals, colors}, {out_xyz, out_normals, out_colors}};
+    TRY(cloud_check(c, what, cl));
     const int k = num_max_search_points;
     return in_scratch(c, what, [&](mi_icp_ctx* a) -> int {
-        const float* in[3];
-        TRY(to_device(a, xyz, (size_t)n * 3, mem_kind, a->stage[0], &in[0]));
-        TRY(to_device(a, normals, (size_t)n * 3, mem_kind, a->stage[1], &in[1]));
-        TRY(to_device(a, colors, (size_t)n * 3, mem_kind, a->stage[2], &in[2]));
+        TRY(cloud_upload(a, &cl, n, mem_kind, a->stage));
+        const float* const* in = cl.in;
         TRY(mi_icp_set_target(a, in[0], nullptr, nullptr, n, MI_ICP_DEVICE));
-        float* const out[3] = {out_xyz, out_normals, out_colors};
-        float* dst[3];
-        for (int e = 0; e < 3; ++e) TRY(out_slot(a, in[e] ? out[e] : nullptr, (size_t)n * 3, mem_kind, a->stage[3 + e], &dst[e]));
+        float* dst[3];  // (not cloud_emit: the launch itself can fail)
+        TRY(cloud_out(a, in, cl.out, n, mem_kind, a->stage + 3, dst));
         TRY(knn_launch(a, k, (uint32_t)((a->nleaf + 7) / 8), [](auto kc) { return gaussian_kernel<decltype(kc)::value>; },
                        (const float*)a->nodes.p, (const float*)a->tblk.p, (const int32_t*)a->tidx.p, a->leaf_first, a->nts,
                        a->nleaf, k, search_radius * search_radius, sigma2, in[0], in[1], in[2], dst[0], dst[1], dst[2]));
-        for (int e = 0; e < 3; ++e)
-            if (dst[e]) TRY(from_device(a, (const float*)dst[e], out[e], (size_t)n * 3, mem_kind));
+        TRY(cloud_out_back(a, dst, cl.out, n, mem_kind));
         HIPCHK(a, hipStreamSynchronize(a->stream));
         return MI_ICP_OK;
     });

@@ -1,0 +1,281 @@
+// mi_tsdf.hip -- integration::UniformTSDFVolume: integrate, raycast, extract clouds
+// (one translation unit of libmi_icp.so; csrc/ctx.h lists them)
+#include "ctx.h"
+#include "select.h"
+#include "tsdf_kernels.h"
+
+using namespace mi;
+using namespace mi::eng;
+using host::Mat4;
+
+// ---------------------------------------------------------------------------
+// integration::UniformTSDFVolume (integration/uniform_tsdfvolume.cu; tsdf_kernels.h).  A volume belongs to the context
+// that made it and is freed with it at the latest.
+struct mi_icp_tsdf {
+    mi_icp_ctx* owner = nullptr;
+    TsdfVol v = {};
+    float length = 0.0f, sdf_trunc = 0.0f;
+    DevBuf planes;  // tsdf, weight and, with a colour type, three colour planes
+    DevBuf mult;    // the depth -> camera-distance multiplier image of the intrinsic below
+    int mult_w = 0, mult_h = 0;
+    float mult_k[4] = {0, 0, 0, 0};
+};
+
+namespace mi {
+namespace eng {
+void tsdf_release_all(mi_icp_ctx* c) {
+    for (mi_icp_tsdf* t : c->tsdf_volumes) {
+        release(t->planes);
+        release(t->mult);
+        delete t;
+    }
+    c->tsdf_volumes.clear();
+}
+}  // namespace eng
+}  // namespace mi
+
+static int tsdf_check(mi_icp_ctx* c, const mi_icp_tsdf* t, const char* what) {
+    if (!t || t->owner != c || std::find(c->tsdf_volumes.begin(), c->tsdf_volumes.end(), t) == c->tsdf_volumes.end())
+        return fail(c, MI_ICP_ERR_INVALID, "%s: not a volume of this context", what);
+    return MI_ICP_OK;
+}
+
+extern "C" {
+
+int mi_icp_tsdf_create(mi_icp_ctx* c, float length, int resolution, float sdf_trunc, int color_type, const float* origin3,
+                       mi_icp_tsdf** out) {
+    TRY(check_ctx(c));
+    if (!out) return fail(c, MI_ICP_ERR_INVALID, "tsdf_create: out is null");
+    *out = nullptr;
+    if (!(length > 0.0f) || !std::isfinite(length) || resolution < 3 || resolution > MI_ICP_TSDF_MAX_RESOLUTION ||
+        !(sdf_trunc > 0.0f) || !std::isfinite(sdf_trunc) ||
+        (color_type != MI_ICP_TSDF_NO_COLOR && color_type != MI_ICP_TSDF_RGB8 && color_type != MI_ICP_TSDF_GRAY32))
+        return fail(c, MI_ICP_ERR_INVALID, "tsdf_create: bad arguments");
+    mi_icp_tsdf* t = new mi_icp_tsdf;
+    t->owner = c;
+    t->length = length;
+    t->sdf_trunc = sdf_trunc;
+    TsdfVol& v = t->v;
+    v.res = resolution;
+    v.h_res = resolution / 2;
+    v.n = (int64_t)resolution * resolution * resolution;
+    v.voxel_length = length / (float)resolution;
+    v.half = 0.5f * v.voxel_length;
+    for (int k = 0; k < 3; ++k) v.origin[k] = origin3 ? origin3[k] : 0.0f;
+    v.color_type = color_type;
+    float* base;
+    const int rc = ensure(c, t->planes, (size_t)v.n * (color_type == MI_ICP_TSDF_NO_COLOR ? 2 : 5), &base);
+    if (rc != MI_ICP_OK) {
+        delete t;
+        return rc;
+    }
+    v.tsdf = base;
+    v.weight = base + v.n;
+    v.color = color_type == MI_ICP_TSDF_NO_COLOR ? nullptr : base + 2 * v.n;
+    tsdf_reset<<<blocks_for(v.n), 256, 0, c->stream>>>(v);
+    if (hipGetLastError() != hipSuccess) {
+        release(t->planes);
+        delete t;
+        return fail(c, MI_ICP_ERR_HIP, "tsdf_create: launch failed");
+    }
+    c->tsdf_volumes.push_back(t);
+    *out = t;
+    return MI_ICP_OK;
+}
+
+int mi_icp_tsdf_destroy(mi_icp_ctx* c, mi_icp_tsdf* t) {
+    TRY(check_ctx(c));
+    if (!t) return MI_ICP_OK;
+    TRY(tsdf_check(c, t, "tsdf_destroy"));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->tsdf_volumes.erase(std::find(c->tsdf_volumes.begin(), c->tsdf_volumes.end(), t));
+    release(t->planes);
+    release(t->mult);
+    delete t;
+    return MI_ICP_OK;
+}
+
+int mi_icp_tsdf_reset(mi_icp_ctx* c, mi_icp_tsdf* t) {
+    TRY(check_ctx(c));
+    TRY(tsdf_check(c, t, "tsdf_reset"));
+    tsdf_reset<<<blocks_for(t->v.n), 256, 0, c->stream>>>(t->v);
+    KCHK(c);
+    return MI_ICP_OK;
+}
+
+int mi_icp_tsdf_integrate(mi_icp_ctx* c, mi_icp_tsdf* t, const void* depth, int depth_width, int depth_height,
+                          int depth_channels, int depth_bytes_per_channel, const void* color, int color_width,
+                          int color_height, int color_channels, int color_bytes_per_channel, int width, int height,
+                          const float* intrinsic4, const float* extrinsic, int mem_kind) {
+    const char* what = "tsdf_integrate";
+    TRY(check_ctx(c, mem_kind, what));
+    TRY(tsdf_check(c, t, what));
+    if (!intrinsic4) return fail(c, MI_ICP_ERR_INVALID, "%s: null intrinsic", what);
+    const int ct = t->v.color_type;
+    // the reference's format checks (uniform_tsdfvolume.cu:677-695)
+    if (depth_channels != 1 || depth_bytes_per_channel != 4 || depth_width != width || depth_height != height ||
+        (ct == MI_ICP_TSDF_RGB8 && (color_channels != 3 || color_bytes_per_channel != 1)) ||
+        (ct == MI_ICP_TSDF_GRAY32 && (color_channels != 1 || color_bytes_per_channel != 4)) ||
+        (ct != MI_ICP_TSDF_NO_COLOR && (color_width != width || color_height != height)))
+        return fail(c, MI_ICP_ERR_INVALID, "[UniformTSDFVolume::Integrate] Unsupported image format.");
+    if (width < 1 || height < 1 || width > MI_ICP_TSDF_MAX_IMAGE_SIDE || height > MI_ICP_TSDF_MAX_IMAGE_SIDE)
+        return fail(c, MI_ICP_ERR_INVALID, "%s: bad image size (a side is at most %d)", what, MI_ICP_TSDF_MAX_IMAGE_SIDE);
+    if (!depth || (ct != MI_ICP_TSDF_NO_COLOR && !color)) return fail(c, MI_ICP_ERR_INVALID, "%s: null image", what);
+    const int64_t npix = (int64_t)width * height;
+    const float fx = intrinsic4[0], fy = intrinsic4[1], cx = intrinsic4[2], cy = intrinsic4[3];
+
+    if (!t->mult.p || t->mult_w != width || t->mult_h != height || std::memcmp(t->mult_k, intrinsic4, sizeof(float) * 4) != 0) {
+        float* m;
+        TRY(ensure(c, t->mult, (size_t)npix, &m));
+        tsdf_multiplier<<<blocks_for(npix), 256, 0, c->stream>>>(m, width, height, cx, cy, 1.0f / fx, 1.0f / fy);
+        KCHK(c);
+        t->mult_w = width;
+        t->mult_h = height;
+        std::memcpy(t->mult_k, intrinsic4, sizeof(float) * 4);
+    }
+
+    TsdfIntegrate a;
+    const uint8_t *dd, *dc;
+    TRY(to_device(c, (const uint8_t*)depth, (size_t)npix * 4, mem_kind, c->stage[0], &dd));
+    TRY(to_device(c, (const uint8_t*)(ct == MI_ICP_TSDF_NO_COLOR ? nullptr : color),
+                  (size_t)npix * (ct == MI_ICP_TSDF_RGB8 ? 3 : 4), mem_kind, c->stage[1], &dc));
+    a.depth = (const float*)dd;
+    a.color = dc;
+    a.mult = (const float*)t->mult.p;
+    const Mat4 E = load_T(extrinsic);
+    for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 4; ++k) a.E[r][k] = E.data()[k * 4 + r];
+        a.D[r] = t->v.voxel_length * a.E[r][2];
+    }
+    a.fx = fx;
+    a.fy = fy;
+    a.cx = cx;
+    a.cy = cy;
+    a.width = width;
+    a.height = height;
+    a.safe_w = (float)width - 0.0001f;
+    a.safe_h = (float)height - 0.0001f;
+    a.sdf_trunc = t->sdf_trunc;
+    a.sdf_trunc_inv = (float)(1.0 / (double)t->sdf_trunc);
+    a.cull = (std::fabs(cx) <= 65536.0f && std::fabs(cy) <= 65536.0f) ? 1 : 0;  // (the sides are at most 2^15)
+    a.k_left = cx + 1.5f;
+    a.k_right = ((float)width + 0.5f) - cx;
+    a.k_top = cy + 1.5f;
+    a.k_bottom = ((float)height + 0.5f) - cy;
+    const int zchunks = (t->v.res + 255) / 256;
+    tsdf_integrate<<<(unsigned)((int64_t)t->v.res * t->v.res * zchunks), 256, 0, c->stream>>>(t->v, a, zchunks);
+    KCHK(c);
+    if (mem_kind == MI_ICP_HOST) HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's images may go now
+    return MI_ICP_OK;
+}
+
+static int tsdf_extract_args(mi_icp_ctx* c, mi_icp_tsdf* t, const char* what, int64_t capacity, int64_t* m, int mem_kind) {
+    TRY(check_sizes(c, what, 0, m, mem_kind));  // (no cloud comes in: the sizes are the volume's)
+    TRY(tsdf_check(c, t, what));
+    if (capacity < 0) return fail(c, MI_ICP_ERR_INVALID, "%s: negative capacity", what);
+    return MI_ICP_OK;
+}
+
+int mi_icp_tsdf_extract_voxel_point_cloud(mi_icp_ctx* c, mi_icp_tsdf* t, float* out_xyz, float* out_colors, int64_t capacity,
+                                          int64_t* m, int mem_kind) {
+    const char* what = "tsdf_extract_voxel_point_cloud";
+    TRY(tsdf_extract_args(c, t, what, capacity, m, mem_kind));
+    const int64_t n = t->v.n;
+    uint32_t* flags;
+    TRY(ensure(c, c->flags, (size_t)n, &flags));
+    tsdf_voxel_flags<<<blocks_for(n), 256, 0, c->stream>>>(t->v, flags);
+    KCHK(c);
+    float* const out[3] = {out_xyz, nullptr, out_colors};
+    return cloud_emit_counted(c, what, flags, n, out, {true, false, true}, capacity, m, mem_kind,
+                              [&](const uint32_t* pos, float* const dst[3]) {
+                                  tsdf_voxel_gather<<<blocks_for(n), 256, 0, c->stream>>>(t->v, flags, pos, dst[0], dst[2]);
+                              });
+}
+
+int mi_icp_tsdf_extract_point_cloud(mi_icp_ctx* c, mi_icp_tsdf* t, float* out_xyz, float* out_normals, float* out_colors,
+                                    int64_t capacity, int64_t* m, int mem_kind) {
+    const char* what = "tsdf_extract_point_cloud";
+    TRY(tsdf_extract_args(c, t, what, capacity, m, mem_kind));
+    const int64_t r2 = t->v.res - 2, n = r2 * r2 * r2;  // the interior voxels; each has three candidate edges
+    uint32_t* count;
+    TRY(ensure(c, c->flags, (size_t)n, &count));
+    tsdf_cloud_count<<<blocks_for(n), 256, 0, c->stream>>>(t->v, n, count);
+    KCHK(c);
+    float* const out[3] = {out_xyz, out_normals, out_colors};
+    return cloud_emit_counted(c, what, count, n, out, {true, true, t->v.color_type != MI_ICP_TSDF_NO_COLOR}, capacity, m, mem_kind,
+                              [&](const uint32_t* pos, float* const dst[3]) {
+                                  tsdf_cloud_gather<<<blocks_for(n), 256, 0, c->stream>>>(t->v, n, count, pos, dst[0], dst[1], dst[2]);
+                              });
+}
+
+int mi_icp_tsdf_raycast(mi_icp_ctx* c, mi_icp_tsdf* t, int width, int height, const float* intrinsic4, const float* extrinsic,
+                        float sdf_trunc, int valid_only, float* out_xyz, float* out_normals, float* out_colors,
+                        int64_t capacity, int64_t* m, int mem_kind) {
+    const char* what = "tsdf_raycast";
+    TRY(tsdf_extract_args(c, t, what, capacity, m, mem_kind));
+    if (!intrinsic4 || width < 0 || height < 0 || width > MI_ICP_TSDF_MAX_IMAGE_SIDE || height > MI_ICP_TSDF_MAX_IMAGE_SIDE)
+        return fail(c, MI_ICP_ERR_INVALID, "%s: bad arguments (an image side is at most %d)", what, MI_ICP_TSDF_MAX_IMAGE_SIDE);
+    // the march takes length * sqrt(2) / (sdf_trunc / 2) steps at most
+    if (!(sdf_trunc > 0.0f) || !std::isfinite(sdf_trunc) ||
+        !((double)t->v.res * t->v.voxel_length * 1.4142136 / (0.5 * (double)sdf_trunc) <= (double)MI_ICP_TSDF_MAX_MARCH))
+        return fail(c, MI_ICP_ERR_INVALID, "%s: sdf_trunc must be positive and at least length * sqrt(2) * 2 / %d", what,
+                    MI_ICP_TSDF_MAX_MARCH);
+    const int64_t npix = (int64_t)width * height;
+    if (npix == 0) return MI_ICP_OK;
+
+    TsdfRaycast a;
+    const Mat4 E = load_T(extrinsic);
+    // utility::InverseTransform: R^T and -(R^T t), the sums left to right
+    for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 3; ++k) a.R[r][k] = E.data()[r * 4 + k];  // R^T[r][k] = E(k, r)
+        const float t0 = E.data()[12], t1 = E.data()[13], t2 = E.data()[14];
+        const float p = ((-a.R[r][0]) * t0 + (-a.R[r][1]) * t1) + (-a.R[r][2]) * t2;
+        a.t[r] = p - t->v.origin[r];
+    }
+    a.fx = intrinsic4[0];
+    a.fy = intrinsic4[1];
+    a.cx = intrinsic4[2];
+    a.cy = intrinsic4[3];
+    a.sdf_trunc = sdf_trunc;
+    a.width = width;
+    a.height = height;
+    const dim3 grid((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16));
+    float* const out[3] = {out_xyz, out_normals, out_colors};
+
+    if (!valid_only) {  // every pixel stays, an invalid one as NaN
+        *m = npix;
+        if (capacity < npix) return MI_ICP_OK;
+        if (!out_xyz || !out_normals || !out_colors) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+        return cloud_emit(c, out, out, npix, npix, mem_kind, c->vpay, [&](float* const dst[3]) {
+            tsdf_raycast<<<grid, 256, 0, c->stream>>>(t->v, a, dst[0], dst[1], dst[2]);
+        });
+    }
+    float* raw[3];
+    for (int k = 0; k < 3; ++k) TRY(ensure(c, c->stage[3 + k], (size_t)npix * 3, &raw[k]));
+    uint32_t* flags;
+    TRY(ensure(c, c->flags, (size_t)npix, &flags));
+    tsdf_raycast<<<grid, 256, 0, c->stream>>>(t->v, a, raw[0], raw[1], raw[2]);
+    KCHK(c);
+    finite_flags<<<blocks_for(npix), 256, 0, c->stream>>>(raw[0], npix, 1, 1, flags);  // RemoveNoneFinitePoints(true, true)
+    KCHK(c);
+    // (the count before anything is written: compact_by_flags would have to write first)
+    return cloud_emit_counted(c, what, flags, npix, out, {true, true, true}, capacity, m, mem_kind,
+                              [&](const uint32_t* pos, float* const dst[3]) {
+                                  select_gather<<<blocks_for(npix), 256, 0, c->stream>>>(flags, pos, npix, raw[0], raw[1], raw[2],
+                                                                                        dst[0], dst[1], dst[2], (int64_t*)nullptr);
+                              });
+}
+
+int mi_icp_tsdf_get_voxels(mi_icp_ctx* c, mi_icp_tsdf* t, float* tsdf_out, float* weight_out, float* color_out, int mem_kind) {
+    const char* what = "tsdf_get_voxels";
+    TRY(check_ctx(c, mem_kind, what));
+    TRY(tsdf_check(c, t, what));
+    if (color_out && !t->v.color) return fail(c, MI_ICP_ERR_INVALID, "%s: the volume has no colour planes", what);
+    TRY(from_device(c, (const float*)t->v.tsdf, tsdf_out, (size_t)t->v.n, mem_kind));
+    TRY(from_device(c, (const float*)t->v.weight, weight_out, (size_t)t->v.n, mem_kind));
+    TRY(from_device(c, (const float*)t->v.color, color_out, (size_t)t->v.n * 3, mem_kind));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MI_ICP_OK;
+}
+
+}  // extern "C"

@@ -34,6 +34,20 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert b"gfx950" in lib.mi_icp_version()
 
 
+def test_bad_mem_kind_list_names_every_entry_point_that_takes_one():
+    """test_gpu_robustness._kind_calls feeds test_bad_mem_kind_is_refused_before_any_buffer; its names are exactly the
+    functions of include/mi_icp.h with a mem_kind parameter, so a new entry point cannot stay out of that test."""
+    from test_gpu_robustness import _kind_calls
+    src = open(os.path.join(ROOT, "include", "mi_icp.h")).read()
+    src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+    takes = [m.group(1) for m in re.finditer(r"MI_ICP_API\s+[\w\s\*]+?\b(mi_icp_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)
+             if re.search(r"\bint\s+mem_kind\b", m.group(2))]
+    assert len(takes) >= 38 and set(takes) <= set(_declared())
+    listed = ["mi_icp_" + c[0] for c in _kind_calls()[0]]
+    assert len(listed) == len(set(listed))
+    assert set(listed) == set(takes)
+
+
 def test_library_contains_gfx950_code_object_only():
     from cupoch_amd import _lib
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/clang-offload-bundler", "--list", "--type=o",

@@ -290,6 +290,8 @@ def _kind_calls():
     opt.num_levels, opt.iterations[0], opt.max_depth = 1, 5, 4.0
     ok = C.c_int(7)
     T16, tw6, info36 = np.full(16, 7, np.float32), np.full(6, 7, np.float32), np.full(36, 7, np.float64)
+    plane4, ransac4 = np.full(4, 7, np.float32), np.full(4, 7, np.float32)
+    lo3, hi3 = np.zeros(3, np.float32), np.ones(3, np.float32)
     hp = lambda a: a.ctypes.data_as(C.c_void_p)
     n = 256
     cloud = lambda b: (P(b["xyz"]), P(b["nrm"]), P(b["col"]), n)
@@ -323,7 +325,23 @@ def _kind_calls():
         ("set_source_colors", lambda b, k: (P(b["col"]), k)),
         ("compute_color_gradients", lambda b, k: (0.1, 8, P(b["ocol"]), k)),
         ("spatial_order", lambda b, k: (P(b["xyz"]), n, P(b["i32"]), k)),
-    ], (T16, tw6, info36)
+        ("select_by_mask", lambda b, k: cloud(b) + (P(b["u8"]), n, 0) + outs(b) + (C.byref(m), k)),
+        ("farthest_point_downsample", lambda b, k: cloud(b) + (8,) + outs(b) + (P(b["i64"]), C.byref(m), k)),
+        ("pass_through_filter", lambda b, k: cloud(b) + (0, 0.0, 1.0) + outs(b) + (P(b["i64"]), C.byref(m), k)),
+        ("crop_aabb", lambda b, k: cloud(b) + (hp(lo3), hp(hi3)) + outs(b) + (P(b["i64"]), C.byref(m), k)),
+        ("remove_none_finite", lambda b, k: cloud(b) + (1, 1) + outs(b) + (P(b["i64"]), C.byref(m), k)),
+        ("segment_plane", lambda b, k: (P(b["xyz"]), n, 0.05, 3, 16, C.c_uint64(1), hp(plane4), hp(ransac4), P(b["i64"]),
+                                        C.byref(m), None, None, k)),
+        ("iss_keypoints", lambda b, k: (P(b["xyz"]), n, 0.2, 0.1, 0.975, 0.975, 5, 16, P(b["u8"]), P(b["f32"]),
+                                        P(b["onrm"]), P(b["i32b"]), None, C.byref(m), k)),
+        ("gaussian_filter", lambda b, k: cloud(b) + (0.1, 0.01, 8) + outs(b) + (k,)),
+        # (the volume has no colour planes: depth alone)
+        ("tsdf_integrate", lambda b, k: (b["vol"], P(b["img"][1]), 16, 16, 1, 4, None, 0, 0, 0, 0, 16, 16, K4, None, k)),
+        ("tsdf_extract_point_cloud", lambda b, k: (b["vol"],) + outs(b) + (n, C.byref(m), k)),
+        ("tsdf_extract_voxel_point_cloud", lambda b, k: (b["vol"], P(b["oxyz"]), P(b["ocol"]), n, C.byref(m), k)),
+        ("tsdf_raycast", lambda b, k: (b["vol"], 16, 16, K4, None, 0.5, 1) + outs(b) + (n, C.byref(m), k)),
+        ("tsdf_get_voxels", lambda b, k: (b["vol"], P(b["f32"]), P(b["oxyz"]), None, k)),
+    ], (T16, tw6, info36, plane4, ransac4)
 
 
 @pytest.mark.parametrize("name", [c[0] for c in _kind_calls()[0]])
@@ -344,8 +362,10 @@ def test_bad_mem_kind_is_refused_before_any_buffer(eng, name):
              i64=dev(np.arange(256, dtype=np.int64)),
              oxyz=dev(np.full((256, 3), 7, np.float32)), onrm=dev(np.full((256, 3), 7, np.float32)),
              ocol=dev(np.full((256, 3), 7, np.float32)), f32=dev(np.full((256, 4), 7, np.float32)),
-             i32=dev(np.full((256, 4), -7, np.int32)), i32b=dev(np.full(256, -7, np.int32)))
+             i32=dev(np.full((256, 4), -7, np.int32)), i32b=dev(np.full(256, -7, np.int32)),
+             u8=dev(np.ones(256, np.uint8)))
     flat = [t for v in b.values() for t in (v if isinstance(v, list) else [v])]
+    b["vol"] = eng.tsdf_create(1.0, 4, 0.5, 0) if name.startswith("tsdf_") else None   # a small real volume, no colour
     before = [t.clone() for t in flat]
     host_before = [a.copy() for a in host_outs]
     torch.cuda.synchronize()
@@ -357,6 +377,7 @@ def test_bad_mem_kind_is_refused_before_any_buffer(eng, name):
         assert torch.equal(t, t0)
     for a, a0 in zip(host_outs, host_before):
         np.testing.assert_array_equal(a, a0)
+    eng.tsdf_destroy(b["vol"])
     # the context still serves a valid call
     eng.set_target(pts)
     found, idx, d2 = eng.search_knn(pts, 1)
