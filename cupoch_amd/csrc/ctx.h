@@ -30,6 +30,7 @@
 #include "device_utils.h"
 #include "host_solver.h"
 #include "loop.h"
+#include "loop_policy.h"
 #include "mailbox.h"
 #include "primitives.h"
 
@@ -70,18 +71,7 @@ struct mi_icp_ctx {
     bool links_inflight = false;
     int last_search_kind = -1;  // mi_icp_debug.h
     int last_voxel_path = -1;   // mi_icp_debug.h
-    // Halos are built when a registration loop's searches ask for them (nn_search.h counts the lanes one would
-    // serve): clean data never does.  A context whose loops have asked before starts the build with the loop.
-    bool halo_sticky = false;
-    bool ran_loop = false;  // (a context that has registered before and gets a SMALL target starts the build behind the tree)
-    bool halo_declined = false;  // this loop's searches have been looked at and did not ask
-    int64_t halo_iters = 0;      // seeded iterations against this target since it was set ...
-    int64_t halo_asked = 0;      // ... and the lanes that asked for a halo in them
-    int64_t halo_lanes = 0;      // ... out of this many lanes (source points x iterations looked at)
-    int64_t halo_iters_unseen = 0;  // iterations since the counter was last looked at
-    uint32_t halo_chunks = 0;    // chunks of a declined loop (it looks at the counter every eighth)
-    int64_t halo_want_seen = 0;  // the counter's value at the last look (it is zeroed when a loop begins)
-    int halo_looks = 0;          // looks of this loop while undecided
+    mi::eng::HaloPolicy halo;    // when they are built (loop_policy.h)
     bool halo_use = false;       // the loop's launches take the halos (looked up once per chunk: an event query costs microseconds)
     mi::eng::DevBuf halo_want;            // the counter (nn_search.h kWantSlots words, summed by the host)
 
@@ -99,8 +89,7 @@ struct mi_icp_ctx {
     bool expiry_live = false;  // the array may hold limits (else: NaN -- all ones -- or -inf throughout: no odometer reading is below either)
     float skip_r2 = NAN;       // the squared radius those limits were measured against; NaN: none on record
     mi::eng::DevBuf src_bounds;    // min[3], max[3] of the staged source (the loop's step sizes the displacement of its corners: loop.h)
-    bool relocate_armed = false;   // this loop's next chunk of iterations carries the gated re-location launches (loop_run)
-    bool relocate_possible = false;  // ... this loop's step sizes its displacement (loop_begin): the launches may be armed again
+    mi::eng::Relocation relocate;  // whether the loop's chunks carry the gated re-location launches (loop_policy.h)
 
     // ---- explicit correspondence set ----
     mi::eng::DevBuf user_pairs;
@@ -286,23 +275,7 @@ inline int drop_expiry(mi_icp_ctx* c) {
     return MI_ICP_OK;
 }
 
-// The loop state's live[] hint (loop.h) samples one packet in 2^shift, 64 at most.
-inline uint32_t skip_live_shift(int64_t ns) {
-    uint32_t shift = 0;
-    while ((((ns + 63) / 64) >> (shift + 1)) >= 64) ++shift;
-    return shift;
-}
-// Does gating the loop's next seeded search pay?  By the sample as of the host's last look at the loop state: at least
-// a quarter of the sampled packets hold a limit.  The gated launch runs kSkipRun packets per wave one after the other:
-// forced on, it costs a loop whose searches skip nothing 3 % (noisy, converged) to 12 % (transient) -- EXPERIMENTS.md;
-// a quarter of the packets skipped is a quarter of the search saved, well clear of that.
-inline bool skip_pays(const mi_icp_ctx* c) {
-    if (!c->loop_host || c->ns <= 0) return false;
-    const int64_t samples = std::min<int64_t>(64, ((c->ns + 63) / 64) >> skip_live_shift(c->ns));
-    int64_t held = 0;
-    for (int64_t k = 0; k < samples; ++k) held += c->loop_host->live[k] ? 1 : 0;
-    return samples > 0 && held * 4 >= samples;
-}
+static_assert(sizeof(DevLoop::live) == kSkipSamples, "loop_policy.h skip_pays reads DevLoop::live[]");
 
 inline int blocks_for(int64_t n, int per = 256) { return (int)std::max<int64_t>(1, (n + per - 1) / per); }
 

@@ -321,8 +321,6 @@ int occupancy_build(int which) {
 }  // namespace eng
 }  // namespace mi
 
-constexpr int64_t kHaloAheadMax = 2000000;  // targets below this get their halos right behind the tree on a context that has registered before
-
 extern "C" {
 
 // ---------------------------------------------------------------------------
@@ -433,7 +431,7 @@ int mi_icp_set_target(mi_icp_ctx* c, const float* xyz, const float* normals, con
         KCHK(c);
     }
     c->links_ready = false;  // (the leaves' halos: started below, or by the registration loop / the first seeded search)
-    c->halo_iters = c->halo_asked = c->halo_lanes = 0;
+    c->halo.on_new_target();
     c->links_allowed = (uint32_t)nleaf <= kLinkIdMask;
     c->nt = n;
     c->nts = nts;
@@ -441,13 +439,7 @@ int mi_icp_set_target(mi_icp_ctx* c, const float* xyz, const float* normals, con
     c->leaf_first = leaf_first;
     c->nrecords = nrecords;
     c->cell_levels = lay.levels;
-    // A context whose loops have ASKED for halos will run another such loop.  For a small target (frame-to-frame
-    // callers: KinFu, odometry) the halos are then started right away, on the private stream, next to the staging of the
-    // source: the loop's first seeded iterations find them ready.  For a large one the build would fight the staging
-    // for the memory system; there the loop's own searches say whether it is wanted.  (Until round 6 ANY earlier loop on
-    // the context was enough: on clean frames the 0.18-ms build per pyramid level cost a KinFu step 2-5 % and a
-    // 100k-300k-point call 4 %, same box, for halos nothing read.)
-    if (c->ran_loop && c->halo_sticky && c->links_allowed && n < kHaloAheadMax) TRY(start_links_async(c));
+    if (c->halo.start_ahead(n, c->links_allowed)) TRY(start_links_async(c));  // (on the private stream, next to the staging of the source)
     if (c->profiling) {
         (void)hipEventRecord(e1, c->stream);
         (void)hipStreamSynchronize(c->stream);

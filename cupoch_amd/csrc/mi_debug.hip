@@ -194,7 +194,7 @@ int mi_icp_debug_loop_counters(mi_icp_ctx* c, int32_t* out4) {
     out4[0] = c->loop_host->iterations;
     out4[1] = c->loop_host->passes;
     out4[2] = c->loop_host->relocations;
-    out4[3] = c->relocate_armed ? 1 : 0;
+    out4[3] = c->relocate.armed ? 1 : 0;
     return MI_ICP_OK;
 }
 
@@ -211,7 +211,7 @@ int mi_icp_debug_search_skip(mi_icp_ctx* c, double* state2, double* limits_out, 
         return fail(c, MI_ICP_ERR_STATE, "debug_search_skip: no registration loop on this context");
     const int64_t n = (c->ns + 63) / 64;
     *npackets = n;
-    *armed = (c->expiry_live && c->skip_r2 == c->loop_r2 && skip_pays(c)) ? 1 : 0;
+    *armed = (c->expiry_live && c->skip_r2 == c->loop_r2 && skip_pays(c->loop_host->live, c->ns)) ? 1 : 0;
     const char* st = (const char*)c->loop_dev.p;
     HIPCHK(c, hipMemcpyAsync(state2, st + offsetof(DevLoop, travel), sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(state2 + 1, st + offsetof(DevLoop, fuzz), sizeof(double), hipMemcpyDeviceToHost, c->stream));

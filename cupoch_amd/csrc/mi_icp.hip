@@ -99,46 +99,32 @@ int launch_nn(mi_icp_ctx* c, const Mat4& T, float r2, bool seed, unsigned long l
         return MI_ICP_OK;
     }
     const Xform X = make_xform(T);
-    const bool use_seed = seed && c->nn_valid;
-    // Inside a registration loop the halos are used if they are there and asked for if they are not (loop_halo); a
-    // one-shot seeded search builds them on the spot.
+    // Inside a registration loop the halos are used if there and asked for if not (loop_halo); a one-shot seeded search builds them on the spot.
     bool have_halo;
     uint32_t* want = nullptr;
     if (loop) {
         TRY(loop_halo(c, &have_halo, &want));
     } else {
-        if (use_seed) TRY(ensure_links(c));
+        if (seed && c->nn_valid) TRY(ensure_links(c));
         have_halo = halo_poll(c);
     }
     EvTimer t(c, 0, loop != nullptr);
-    // No previous matches, but the target's halos are there: every query takes the leaf it falls into as its seed
-    // (nn_search.h: locate_by_planes) and the seeded search does the rest.  (Without halos every lane whose seed
-    // leaf's region does not finish it walks up from there -- under the displacement a registration starts with that
-    // is most packets, and costs more than the walk from the root: 10M points 3.9 against 1.2 ms.)
-    const bool self_seeded = !use_seed && !stats && c->ns >= coarse_first_min() && have_halo && planes_available(c);
-    // THE SKIP (nn_search.h): a seeded search of the loop leaves a limit per packet; it may skip by the limits on record
-    // if they come from such a search at this radius with nothing in between that called drop_expiry.  Every other
-    // search rewrites matches the limits know nothing of: they are dropped first.
-    const bool limits = loop != nullptr && (use_seed || self_seeded) && !stats && c->expiry.p != nullptr;
-    const bool may_skip = limits && use_seed && c->expiry_live && c->skip_r2 == r2;
-    if (!may_skip) TRY(drop_expiry(c));
-    const uint32_t run = (may_skip && skip_pays(c)) ? kSkipRun : 1u;  // (the gate: nn_packet_kernel)
-    if (self_seeded) TRY(launch_locate_by_planes(c, X, loop, 0));
-    c->last_search_kind = use_seed ? 1 : (self_seeded ? 2 : 0);
-    const PacketGrid g = packet_grid(c->ns, run);
-    // (inside the registration loop the distances are not stored: nothing reads them there, and every
-    // entry point that hands distances out runs its own search first)
-    nn_kernel(use_seed || self_seeded, stats != nullptr, loop && c->stamps_on, run > 1u)<<<g.grid, kNNThreads, 0, c->stream>>>(
+    // (loop_host is never null on a live context -- mi_icp_create fails without it -- and live[] is read only under may_skip)
+    const SearchPlan p = plan_search(loop != nullptr, seed, c->nn_valid, stats != nullptr, c->ns, coarse_first_min(), have_halo, planes_available(c),
+                                     c->expiry.p != nullptr, c->expiry_live, c->skip_r2, r2, c->loop_host->live, kSkipRun);
+    if (!p.may_skip) TRY(drop_expiry(c));
+    if (p.self_seeded) TRY(launch_locate_by_planes(c, X, loop, 0));
+    c->last_search_kind = p.kind;
+    const PacketGrid g = packet_grid(c->ns, p.run);  // (p.run > 1: the gate, nn_packet_kernel)
+    // (inside the loop the distances are not stored: nothing reads them there, and every entry point that hands distances out runs its own search first)
+    nn_kernel(p.use_seed || p.self_seeded, stats != nullptr, loop && c->stamps_on, p.run > 1u)<<<g.grid, kNNThreads, 0, c->stream>>>(
             (const float*)c->sx.p, (const float*)c->sy.p, (const float*)c->sz.p, (int)c->ns, (const float*)c->nodes.p,
             (const float*)c->tblk.p, (const float*)lreg_of(c), have_halo ? (const float*)c->thalo.p : nullptr, c->leaf_first,
             X, loop, r2, g.nblocks, idx, loop ? nullptr : (float*)c->nn_d2.p, stats, want,
-            limits ? (double*)c->expiry.p : nullptr,
-            limits ? reinterpret_cast<uint8_t*>(c->loop_dev.p) + offsetof(DevLoop, live) : nullptr, skip_live_shift(c->ns), run);
+            p.limits ? (double*)c->expiry.p : nullptr,
+            p.limits ? reinterpret_cast<uint8_t*>(c->loop_dev.p) + offsetof(DevLoop, live) : nullptr, skip_live_shift(c->ns), p.run);
     KCHK(c);
-    if (limits) {
-        c->expiry_live = true;
-        c->skip_r2 = r2;
-    }
+    if (p.limits) c->expiry_live = true, c->skip_r2 = r2;
     c->nn_valid = true;
     c->n_user_pairs = -1;
     return MI_ICP_OK;
@@ -736,13 +722,10 @@ static int step_in_reduction(const mi_icp_ctx* c) {
 // one evaluation: search under the loop's transform, reduction, all-reduce, step kernel
 static int loop_enqueue_evaluation(mi_icp_ctx* c, bool seed) {
     DevLoop* d = (DevLoop*)c->loop_dev.p;
-    // RE-LOCATION (loop.h): while this loop's steps are still large the seeded search is preceded by a launch that
-    // does nothing unless the step just taken moved the source by more than about a leaf's width -- then every seed is
-    // replaced by the leaf the moved query falls into.  Armed per chunk by loop_run; needs the halos (a located seed
-    // without them walks like a stale one: measured on the bench's cold call, whose second search -- the queries a few
-    // thousandths of a spacing from their partners after the first step -- leaves 0.85 lanes per packet unfinished from
-    // located seeds against 1.18 from the first pass's matches, 0.21 against 0.196 ms, and the descent costs 0.12).
-    if (seed && c->relocate_armed && c->halo_use && c->nn_valid && c->n_user_pairs < 0 && c->ns > 0 && c->nt > 0) {
+    // RE-LOCATION (loop_policy.h arms it per chunk); needs the halos (a located seed without them walks like a stale one: measured on the
+    // bench's cold call, whose second search -- the queries a few thousandths of a spacing from their partners after the first step -- leaves
+    // 0.85 lanes per packet unfinished from located seeds against 1.18 from the first pass's matches, 0.21 against 0.196 ms, and the descent costs 0.12).
+    if (seed && c->relocate.armed && c->halo_use && c->nn_valid && c->n_user_pairs < 0 && c->ns > 0 && c->nt > 0) {
         const Xform none = {};
         TRY(launch_locate_by_planes(c, none, d, 1));
     }
@@ -759,105 +742,43 @@ static int loop_enqueue_evaluation(mi_icp_ctx* c, bool seed) {
     return MI_ICP_OK;
 }
 
-// Enqueue up to `budget` iterations in chunks, looking at `done` between chunks -- and, while the target has
-// no halos, at how many lanes of the seeded searches asked for one.  The first seeded iteration of a
-// registration is still displaced and asks whatever the data; the second one tells noise from convergence.  So a
-// large source's first two seeded iterations are chunks of their own: if more than 40 % of the lanes ask in the
-// first, or more than ~3 % still do in the second, the halos are built -- on the private stream, and the loop's
-// stream waits for them: an iteration that walks instead costs a 10M-point loop half of what the build does.
-// Small sources (a walk costs them little, a host synchronisation much) decide at their first regular chunk's end.
-// Clean data leaves a few lanes in a few thousand asking (a converged query within rounding of a face of its
-// match's region): their packets' one-record walks are ~4 % of a search -- not worth a build to one registration,
-// worth it to a target that keeps being registered against: after kHaloLongRun iterations on the same target the
-// build is started in the background and taken up whenever it is done.
-// twice what the halos and their build's scratch take (~128 + ~56 bytes per slot) must be free on the device
 static bool halo_memory_free(const mi_icp_ctx* c) {
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
-    return free_b >= (size_t)c->nts * 368u;
+    return hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= (size_t)HaloPolicy::bytes_needed(c->nts);
 }
 
+// Enqueue up to `budget` iterations in chunks, looking at `done` between chunks; what is decided there is loop_policy.h's.
 static int loop_run(mi_icp_ctx* c, int budget) {
-    constexpr int kChunk = 8;
-    constexpr int64_t kLarge = 500000, kHaloLongRun = 40, kHaloVeryLongRun = 1000;
-    int chunk = kChunk;
+    ChunkSchedule chunks;
     while (budget > 0) {
         const bool no_halo = !c->links_ready && !c->links_inflight && c->links_allowed && c->nt > 0;
-        const bool undecided = no_halo && !c->halo_declined;
-        // (a build the loop's decision started -- or one started with the loop on a context that has asked
-        // before, or behind a small target's tree: the stream waits for what is left of it rather than walk)
-        if (c->links_inflight && !c->halo_declined) TRY(ensure_links(c));
-        // (a short remainder rides along: one host synchronisation less than it would cost.  The chunks of one call grow
-        // -- 8, 16, 32, 32 ...: a look at the loop is ~30 us of copies, synchronisation and relaunch, two iterations of a
-        // 100k-point loop; a loop that has not converged within its first chunks is unlikely to in the next few, and an
-        // iteration enqueued past the end costs ~3 us.  The sizes depend on the budget alone: every rank enqueues alike.)
-        int n = (budget <= chunk + chunk / 2) ? budget : chunk;
-        const bool grown = n == chunk;
-        // (with several ranks the chunking must not depend on anything a rank sees alone: every rank has to
-        // enqueue the same number of evaluations -- an in-library RCCL all-reduce is a host-side call per
-        // evaluation, and a rank that stops at `done` after fewer of them would leave its peers' calls unmatched)
-        const bool several_ranks = c->comm != nullptr || c->mail_dev != nullptr;
-        if (undecided && c->ns >= kLarge && !several_ranks) n = 1;
-        const int passes_before = c->loop_host->passes;
+        const bool undecided = no_halo && !c->halo.declined;
+        // (a build the loop's decision started, or a sticky context's, or one behind a small target's tree: the stream waits for it rather than walk)
+        if (c->links_inflight && !c->halo.declined) TRY(ensure_links(c));
+        const int n = chunks.plan(budget, HaloPolicy::single_iteration(undecided, c->ns, c->comm != nullptr || c->mail_dev != nullptr));
+        const int passes_before = c->loop_host->passes, relocations_before = c->loop_host->relocations;
         c->halo_use = halo_poll(c);
-        const bool carried = c->relocate_armed && c->halo_use;  // this chunk's iterations carry the gated re-location launches
-        const int relocations_before = c->loop_host->relocations;
+        const bool carried = c->relocate.armed && c->halo_use;  // this chunk's iterations carry the gated re-location launches
         for (int i = 0; i < n; ++i) TRY(loop_enqueue_evaluation(c, true));
-        // (a loop that has declined keeps counting -- a target registered against for long may still earn its halos -- but
-        // looks at the 4-KB counter only every eighth chunk: the copy is ~1 us per iteration of an 8-way shard's 36-us step)
-        const bool look = no_halo && (!c->halo_declined || (++c->halo_chunks & 7) == 0);
+        const bool look = c->halo.wants_look(no_halo);
         if (look) HIPCHK(c, hipMemcpyAsync(c->u_host + 16, c->halo_want.p, kWantSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         TRY(loop_pull(c));
         const int executed = c->loop_host->passes - passes_before;
         collect_pooled(c, executed);
-        // (a chunk that carried the launches and never needed one: the steps have become small, and they only shrink)
-        if (carried && c->loop_host->relocations == relocations_before) c->relocate_armed = false;
-        // ... and they may grow again (point-to-plane sliding, an escape from a plateau): the step keeps sizing itself on
-        // the device whether or not the launches ride along, so a chunk without them that took a large step arms the next
-        // (large sources only: a stale seed's climb costs a 10M-point search milliseconds, a 100k-point one less than the
-        // eight 5-us launches an armed chunk carries -- the reference's own benchmark call, 113k points sliding along
-        // themselves, 1.66 -> 1.71 ms with the re-arming at every size)
-        else if (!c->relocate_armed && c->relocate_possible && c->ns >= kLarge && c->loop_host->relocations != relocations_before) c->relocate_armed = true;
+        c->relocate.after_chunk(carried, c->loop_host->relocations != relocations_before, c->ns);
         budget -= n;
-        c->halo_iters += executed;
-        c->halo_iters_unseen += executed;
+        c->halo.account(executed);
         if (look) {
-            const int64_t seen_iters = c->halo_iters_unseen;
-            c->halo_iters_unseen = 0;
-            // (a 32-bit device counter that keeps counting through a long stepping loop: the difference is taken
-            // modulo 2^32, so a wrap between two looks costs nothing)
             uint32_t counted = 0u;  // (nn_search.h kWantSlots: the counter's words, summed modulo 2^32)
             for (uint32_t k = 0; k < kWantSlots; ++k) counted += c->u_host[16 + k];
-            const int64_t asked = (int64_t)(uint32_t)(counted - (uint32_t)c->halo_want_seen);  // by this chunk's iterations
-            c->halo_want_seen = (int64_t)counted;
-            c->halo_asked += asked;
-            c->halo_lanes += c->ns * std::max<int64_t>(seen_iters, 0);
-            if (undecided) {
-                ++c->halo_looks;
-                const int64_t per = std::max(executed, 1);
-                const bool many = asked * 32 > c->ns * per, most = asked * 5 > 2 * c->ns * per;
-                if (!many) {
-                    c->halo_declined = true;
-                } else if (most || c->halo_looks >= 2 || c->ns < kLarge) {
-                    c->halo_sticky = true;
-                    ++c->prof[6];
-                    TRY(start_links_async(c));
-                }
-            } else if (((c->halo_iters >= kHaloLongRun && c->halo_asked * 100 >= c->halo_lanes) ||
-                        (c->halo_iters >= kHaloVeryLongRun && c->halo_asked > 0)) && halo_memory_free(c)) {
-                // (in the background: halo_declined stays, nothing waits.  Until round 6 ANY lane that had ever asked
-                // started this build after 40 iterations -- 2.2 ms of GPU time and 1.6 GB at 10M points inside the loop
-                // of a caller whose data hardly reads a halo: one window in seven of the headline bench 70 % slow.  What
-                // the halos save such a loop is the tail of its searches -- the few packets that take a one-record walk:
-                // 2-3 us per iteration, 2 % of a 10M-point step, 7 % of an eighth's -- which pays for the build after
-                // ~1000 iterations.  So: at least 1 % of the lanes asking per iteration after 40, or anybody asking
-                // after 1000 (a map that keeps being registered against), and twice the build's memory free.)
+            const HaloAction act = c->halo.observe(counted, executed, c->ns, undecided);
+            if (act == HaloAction::BuildAndWait || (act == HaloAction::BuildInBackgroundIfMemory && halo_memory_free(c))) {
                 ++c->prof[6];
                 TRY(start_links_async(c));
             }
         }
         if (c->loop_host->done) break;
-        if (grown && n == chunk) chunk = std::min(chunk * 2, 32);
+        chunks.ran(n);
     }
     return MI_ICP_OK;
 }
@@ -890,7 +811,7 @@ static int loop_begin(mi_icp_ctx* c, int est, float max_distance, const float* i
     const bool can_locate = planes_available(c) && c->ns >= coarse_first_min() && c->src_bounds.p != nullptr && c->nt > 0;
     L.near2_ptr = can_locate ? (uint64_t)(uintptr_t)((const float*)c->nodes.p + kRecordNear2) : 0ull;
     L.src_bounds_ptr = can_locate ? (uint64_t)(uintptr_t)c->src_bounds.p : 0ull;
-    c->relocate_armed = c->relocate_possible = can_locate;
+    c->relocate.on_loop_begin(can_locate);
     if (c->stamps_on) {  // (mi_icp_debug_set_step_stamps: armed -- minima at all ones -- before the loop's first launch)
         unsigned long long* st;
         TRY(ensure(c, c->stamps, kStampWords, &st));
@@ -922,27 +843,18 @@ static int loop_begin(mi_icp_ctx* c, int est, float max_distance, const float* i
     TRY(ensure(c, c->loop_dev, 1, &d));
     HIPCHK(c, hipMemcpyAsync(d, &L, sizeof(DevLoop), hipMemcpyHostToDevice, c->stream));
     c->loop_active = true;
-    // The first pass has no previous matches; launch_nn picks how it starts.  Halos: a context whose loops
-    // have asked for them before starts the build now, next to the first pass; otherwise the first seeded
-    // iteration says whether this loop needs them (loop_run).
-    c->halo_declined = false;
-    c->halo_want_seen = 0;
-    c->halo_looks = 0;
-    c->halo_iters_unseen = 0;
-    c->halo_chunks = 0;
-    c->ran_loop = true;
+    // The first pass has no previous matches; launch_nn picks how it starts.
+    c->halo.on_loop_begin();
     {
         uint32_t* want;
         TRY(ensure(c, c->halo_want, kWantSlots, &want));
         HIPCHK(c, hipMemsetAsync(want, 0, kWantSlots * sizeof(uint32_t), c->stream));
     }
     c->halo_use = halo_poll(c);
-    // A context whose loops have asked for halos before builds them NOW, on the loop's own stream, ahead of the first
-    // pass -- which then starts from the queries' own seeds (launch_nn).  (Round 3 started the build on the private
-    // stream next to the first pass and the match-order re-sort: the 2.5-ms build and those streaming kernels fought
-    // for the memory system -- match_order_keys 28 us alone, 1.7 ms beside leaf_halo_build; leaf_halo_collect 0.73 ->
-    // 1.7 ms -- and the loop waited for the build at its first seeded iteration anyway.)
-    if (c->halo_sticky && !c->halo_use) {
+    // A sticky context builds them NOW, on the loop's own stream, ahead of the first pass.  (Round 3 started the build on the private stream next
+    // to the first pass and the match-order re-sort: the 2.5-ms build and those streaming kernels fought for the memory system -- match_order_keys
+    // 28 us alone, 1.7 ms beside leaf_halo_build; leaf_halo_collect 0.73 -> 1.7 ms -- and the loop waited for the build at its first seeded iteration anyway.)
+    if (c->halo.sticky && !c->halo_use) {
         if (c->links_inflight) {
             TRY(start_links_async(c));
         } else {

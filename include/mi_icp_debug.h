@@ -66,7 +66,7 @@ MI_ICP_API int mi_icp_debug_loop_counters(mi_icp_ctx* ctx, int32_t* out4);
  * source's packets of 64 points, limits_out[packet] (host memory, filled when capacity >= *npackets; may be NULL) = the
  * limit the packet's last search left (-inf or NaN: none), *armed = 1 if the loop's next search will be gated at all (the
  * limits on record belong to its radius, nothing has voided them since, and by the loop state's sample at least a
- * quarter of the packets hold one: csrc/ctx.h skip_pays).  That search skips exactly the packets with
+ * quarter of the packets hold one: csrc/loop_policy.h skip_pays).  That search skips exactly the packets with
  * travel + fuzz < limit, travel and fuzz as its own step leaves them.  Fails without a loop. */
 MI_ICP_API int mi_icp_debug_search_skip(mi_icp_ctx* ctx, double* state2, double* limits_out, int64_t capacity,
                                         int64_t* npackets, int* armed);
