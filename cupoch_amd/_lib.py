@@ -214,6 +214,8 @@ SIGNATURES = {
     "mi_icp_debug_occupancy": (_I, [_I]),
     "mi_icp_debug_loop_counters": (_I, [_P, _P]),
     "mi_icp_debug_search_skip": (_I, [_P, _P, _P, _L, C.POINTER(_L), C.POINTER(_I)]),
+    "mi_icp_debug_pair_state": (_I, [_P, _P, _P, _L, C.POINTER(_L)]),
+    "mi_icp_debug_drop_pairs": (_I, [_P]),
     "mi_icp_debug_locate": (_I, [_P, _P, _P]),
     "mi_icp_debug_set_step_stamps": (_I, [_P, _I]),
     "mi_icp_debug_get_step_stamps": (_I, [_P, _P, C.POINTER(C.c_double)]),

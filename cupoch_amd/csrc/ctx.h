@@ -88,6 +88,13 @@ struct mi_icp_ctx {
     mi::eng::DevBuf expiry;
     bool expiry_live = false;  // the array may hold limits (else: NaN -- all ones -- or -inf throughout: no odometer reading is below either)
     float skip_r2 = NAN;       // the squared radius those limits were measured against; NaN: none on record
+    // THE PAIR STREAM (reduce.h PairArgs): per packet a state byte and a mask of matched lanes, per staged source point the
+    // 24-byte record of its match, kept once the packet's matches have stood still through a whole search.  State and mask are
+    // sized with expiry; tpair only by a loop whose iterations take reduce_pt2pl_kernel (loop_begin), else -- or when that
+    // allocation failed -- pairs_on is false and the loop gathers as ever.  drop_expiry voids the states as well.
+    mi::eng::DevBuf pair_state, pair_mask, tpair;
+    bool pairs_on = false;    // this loop's reductions keep and read pair records
+    bool pairs_live = false;  // a state may be non-zero
     mi::eng::DevBuf src_bounds;    // min[3], max[3] of the staged source (the loop's step sizes the displacement of its corners: loop.h)
     mi::eng::Relocation relocate;  // whether the loop's chunks carry the gated re-location launches (loop_policy.h)
 
@@ -266,13 +273,21 @@ int from_device(mi_icp_ctx* c, const T* dev, T* dst, size_t count, int mem_kind)
     return MI_ICP_OK;
 }
 
+// Every packet's pair state back to 0: no record is read until the reduction has seen the packet twice more.
+inline int drop_pairs(mi_icp_ctx* c) {
+    if (c->pairs_live && c->pair_state.p) HIPCHK(c, hipMemsetAsync(c->pair_state.p, 0, c->pair_state.bytes, c->stream));
+    c->pairs_live = false;
+    return MI_ICP_OK;
+}
+
 // The per-packet limits of the search skip are void from here on: nothing is skipped until a seeded search of a loop
-// has left new ones.
-inline int drop_expiry(mi_icp_ctx* c) {
+// has left new ones.  So are the pair records (above), unless the caller is a seeded search of the loop, which lowers
+// the state of every packet it changes itself (keep_pairs).
+inline int drop_expiry(mi_icp_ctx* c, bool keep_pairs = false) {
     c->skip_r2 = NAN;
     if (c->expiry_live && c->expiry.p) HIPCHK(c, hipMemsetAsync(c->expiry.p, 0xff, c->expiry.bytes, c->stream));
     c->expiry_live = false;
-    return MI_ICP_OK;
+    return keep_pairs ? MI_ICP_OK : drop_pairs(c);
 }
 
 static_assert(sizeof(DevLoop::live) == kSkipSamples, "loop_policy.h skip_pays reads DevLoop::live[]");

@@ -499,8 +499,12 @@ int mi_icp_set_source(mi_icp_ctx* c, const float* xyz, const float* normals, con
     TRY(ensure(c, c->nn_d2, (size_t)n, &d2));
     {   // the search skip's limit per packet (nn_search.h): none yet -- and the array may be a new one
         double* lim;
+        uint8_t* pst;
+        uint64_t* pmask;
         TRY(ensure(c, c->expiry, (size_t)((n + 63) / 64), &lim));
-        c->expiry_live = true;
+        TRY(ensure(c, c->pair_state, (size_t)((n + 63) / 64), &pst));  // (the pair stream's, reduce.h: sized with the limits)
+        TRY(ensure(c, c->pair_mask, (size_t)((n + 63) / 64), &pmask));
+        c->expiry_live = c->pairs_live = true;
         TRY(drop_expiry(c));
     }
     if (d_nrm) TRY(ensure(c, c->snrm, (size_t)n, &snrm));

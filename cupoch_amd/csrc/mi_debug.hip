@@ -137,7 +137,7 @@ int mi_icp_debug_last_voxel_path(const mi_icp_ctx* c) { return c ? c->last_voxel
 
 int mi_icp_debug_occupancy(int which) {
     if (which == 0 || which == 4) return occupancy_build(which);
-    if (which >= 1 && which <= 3) return occupancy_loop(which);
+    if ((which >= 1 && which <= 3) || which == 9) return occupancy_loop(which);
     if (which >= 5 && which <= 8) return occupancy_geometry(which);
     return -1;
 }
@@ -219,6 +219,25 @@ int mi_icp_debug_search_skip(mi_icp_ctx* c, double* state2, double* limits_out, 
         HIPCHK(c, hipMemcpyAsync(limits_out, c->expiry.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MI_ICP_OK;
+}
+
+int mi_icp_debug_pair_state(mi_icp_ctx* c, uint8_t* state_out, uint64_t* mask_out, int64_t capacity, int64_t* n_out) {
+    TRY(check_ctx(c));
+    if (!n_out || capacity < 0) return fail(c, MI_ICP_ERR_INVALID, "debug_pair_state: bad arguments");
+    if (c->ns <= 0 || !c->pair_state.p || !c->pair_mask.p) return fail(c, MI_ICP_ERR_STATE, "debug_pair_state: no source set");
+    const int64_t n = (c->ns + 63) / 64;
+    *n_out = n;
+    if (capacity >= n) {
+        if (state_out) HIPCHK(c, hipMemcpyAsync(state_out, c->pair_state.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        if (mask_out) HIPCHK(c, hipMemcpyAsync(mask_out, c->pair_mask.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MI_ICP_OK;
+}
+
+int mi_icp_debug_drop_pairs(mi_icp_ctx* c) {
+    TRY(check_ctx(c));
+    return drop_pairs(c);
 }
 
 int mi_icp_debug_locate(mi_icp_ctx* c, const float* T, int32_t* leaf_out) {

@@ -50,7 +50,7 @@ int launch_locate_by_planes(mi_icp_ctx* c, const Xform& X, const DevLoop* loop, 
     locate_by_planes<<<grid, 256, 0, c->stream>>>((const float*)c->sx.p, (const float*)c->sy.p, (const float*)c->sz.p, (int)c->ns,
                                                  (const float2*)c->cell_planes.p, c->cell_levels, (const uint32_t*)c->cell_gstart.p,
                                                  (const float2*)c->gplanes.p, (uint32_t)c->nleaf, X, loop, gated, (int32_t*)c->nn_idx.p,
-                                                 (double*)c->expiry.p);
+                                                 (double*)c->expiry.p, (uint8_t*)c->pair_state.p);
     KCHK(c);
     return MI_ICP_OK;
 }
@@ -112,7 +112,11 @@ int launch_nn(mi_icp_ctx* c, const Mat4& T, float r2, bool seed, unsigned long l
     // (loop_host is never null on a live context -- mi_icp_create fails without it -- and live[] is read only under may_skip)
     const SearchPlan p = plan_search(loop != nullptr, seed, c->nn_valid, stats != nullptr, c->ns, coarse_first_min(), have_halo, planes_available(c),
                                      c->expiry.p != nullptr, c->expiry_live, c->skip_r2, r2, c->loop_host->live, kSkipRun);
-    if (!p.may_skip) TRY(drop_expiry(c));
+    // THE PAIR STREAM: a seeded search of the loop lowers the state of every packet it changes a match of; every
+    // other search rewrites matches unseen, and the host voids all states first (drop_expiry)
+    // (pairs_on: only in loops whose reductions keep records -- every other loop's searches are the kernel without the store)
+    const bool pairs_stand = loop != nullptr && c->pairs_on && p.use_seed && !stats && c->pair_state.p != nullptr;
+    if (!p.may_skip) TRY(drop_expiry(c, pairs_stand));
     if (p.self_seeded) TRY(launch_locate_by_planes(c, X, loop, 0));
     c->last_search_kind = p.kind;
     const PacketGrid g = packet_grid(c->ns, p.run);  // (p.run > 1: the gate, nn_packet_kernel)
@@ -122,7 +126,8 @@ int launch_nn(mi_icp_ctx* c, const Mat4& T, float r2, bool seed, unsigned long l
             (const float*)c->tblk.p, (const float*)lreg_of(c), have_halo ? (const float*)c->thalo.p : nullptr, c->leaf_first,
             X, loop, r2, g.nblocks, idx, loop ? nullptr : (float*)c->nn_d2.p, stats, want,
             p.limits ? (double*)c->expiry.p : nullptr,
-            p.limits ? reinterpret_cast<uint8_t*>(c->loop_dev.p) + offsetof(DevLoop, live) : nullptr, skip_live_shift(c->ns), p.run);
+            p.limits ? reinterpret_cast<uint8_t*>(c->loop_dev.p) + offsetof(DevLoop, live) : nullptr, skip_live_shift(c->ns), p.run,
+            pairs_stand ? (uint8_t*)c->pair_state.p : nullptr);
     KCHK(c);
     if (p.limits) c->expiry_live = true, c->skip_r2 = r2;
     c->nn_valid = true;
@@ -135,7 +140,8 @@ int occupancy_loop(int which) {
     hipError_t e = hipErrorInvalidValue;
     if (which == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, nn_packet_kernel<true, false>, kNNThreads, 0);
     else if (which == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, nn_packet_kernel<false, false>, kNNThreads, 0);
-    else if (which == 3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reduce_pt2pl_kernel<2, 1>, kReduceThreads, 0);
+    else if (which == 3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reduce_pt2pl_kernel<2, 1, false, true>, kReduceThreads, 0);
+    else if (which == 9) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reduce_pt2pl_kernel<4, 1, false, true>, kReduceThreads, 0);
     else return -1;
     return e == hipSuccess ? blocks : -2;
 }
@@ -200,14 +206,19 @@ int reduce_buffers(mi_icp_ctx* c, size_t rows, double** partial, double** sys, u
 
 // The loop's own case: point-to-plane on nearest-neighbour matches with the target's 24-byte records
 // (reduce_pt2pl_kernel; every other case is reduce_kernel<EST, MODE>).
+// pt2pl_inputs: what of that is known before a search has run (loop_begin sizes the pair stream by it).
+bool pt2pl_inputs(const mi_icp_ctx* c, int est, int mode) {
+    return est == kEstPt2Pl && mode == 0 && estimator_ready(c, est) && c->t_has_rec && c->trec.p != nullptr && c->ns > 0 && c->nt > 0;
+}
 bool pt2pl_reduction(const mi_icp_ctx* c, int est, int mode) {
-    return est == kEstPt2Pl && mode == 0 && estimator_ready(c, est) && c->n_user_pairs < 0 && c->t_has_rec &&
-           c->trec.p != nullptr && c->ns > 0 && c->nt > 0 && c->nn_valid;
+    return pt2pl_inputs(c, est, mode) && c->n_user_pairs < 0 && c->nn_valid;
 }
 
-// reduce_pt2pl_kernel<kU, STEP, STAMP>: STAMP (mi_icp_debug_set_step_stamps) only where the step rides along
+// reduce_pt2pl_kernel<kU, STEP, STAMP, PAIRS>: STAMP (mi_icp_debug_set_step_stamps) only where the step rides along,
+// PAIRS (the pair stream) only without it
 template <int kU>
-decltype(&reduce_pt2pl_kernel<kU, 0>) pt2pl_kernel(int step, bool stamp) {
+decltype(&reduce_pt2pl_kernel<kU, 0>) pt2pl_kernel(int step, bool stamp, bool pairs) {
+    if (pairs) return step == 2 ? reduce_pt2pl_kernel<kU, 2, false, true> : (step == 1 ? reduce_pt2pl_kernel<kU, 1, false, true> : reduce_pt2pl_kernel<kU, 0, false, true>);
     if (step == 2) return stamp ? reduce_pt2pl_kernel<kU, 2, true> : reduce_pt2pl_kernel<kU, 2>;
     if (step == 1) return stamp ? reduce_pt2pl_kernel<kU, 1, true> : reduce_pt2pl_kernel<kU, 1>;
     return reduce_pt2pl_kernel<kU, 0>;
@@ -271,10 +282,14 @@ int launch_reduce(mi_icp_ctx* c, int est, int mode, const Mat4& T, DevLoop* loop
         // four elements in flight per thread; at most 512 blocks (2 per CU): measured best on the 10M bench
         // (256 / 512 / 1024 / 2048 blocks: 0.090 / 0.079 / 0.080 / 0.091 ms; 6 or 8 elements in flight on 512,
         // 768 or 1024 blocks: 0.078 - 0.084 ms -- the kernel sits at ~5.1 TB/s of the ~6.3 a pure stream reaches)
-        const auto kernel = (a.count >= kPt2PlTwoFrom) ? pt2pl_kernel<2>(step, c->stamps_on) : pt2pl_kernel<4>(step, c->stamps_on);
+        // (the pair stream: the loop's launches only, and a stamped loop -- an instrument -- runs without it)
+        const bool pairs = loop != nullptr && c->pairs_on && !c->stamps_on && c->tpair.p != nullptr;
+        const auto kernel = (a.count >= kPt2PlTwoFrom) ? pt2pl_kernel<2>(step, c->stamps_on, pairs) : pt2pl_kernel<4>(step, c->stamps_on, pairs);
+        const PairArgs pr = pairs ? PairArgs{(uint8_t*)c->pair_state.p, (uint64_t*)c->pair_mask.p, (float2*)c->tpair.p} : PairArgs{};
+        if (pairs) c->pairs_live = true;
         EvTimer t(c, 1, loop != nullptr);
         kernel<<<std::min(grid, 512), kReduceThreads, 0, c->stream>>>(a, X, loop, partial, ticket, sys,
-                                                                     (step == 2) ? mail_args(c) : MailArgs{});
+                                                                     (step == 2) ? mail_args(c) : MailArgs{}, pr);
         KCHK(c);
         return MI_ICP_OK;
     }
@@ -367,7 +382,7 @@ void mi_icp_destroy(mi_icp_ctx* c) {
     comm_release(c);
     DevBuf* all[] = {&c->trec, &c->tidx, &c->thalo, &c->tlinks_tmp, &c->halo_want, &c->loop_hist, &c->tblk, &c->tnrm, &c->tcov, &c->tgrad, &c->sint, &c->nodes, &c->inv_t, &c->cell_planes, &c->cell_samples, &c->cell_cstart,
                      &c->cell_gstart, &c->sx, &c->sy, &c->sz,
-                     &c->sperm, &c->snrm, &c->scov, &c->nn_idx, &c->nn_d2, &c->expiry, &c->inv_s,
+                     &c->sperm, &c->snrm, &c->scov, &c->nn_idx, &c->nn_d2, &c->expiry, &c->pair_state, &c->pair_mask, &c->tpair, &c->inv_s,
                      &c->user_pairs, &c->keys0, &c->keys1, &c->vals0, &c->vals1, &c->hist,
                      &c->scan_tmp, &c->bounds_part, &c->bounds, &c->partial, &c->sys_dev,
                      &c->dense_idx, &c->flags, &c->pairs_out, &c->seg_start, &c->loop_dev, &c->ticket, &c->mail_state, &c->alt[0],
@@ -843,6 +858,26 @@ static int loop_begin(mi_icp_ctx* c, int est, float max_distance, const float* i
     TRY(ensure(c, c->loop_dev, 1, &d));
     HIPCHK(c, hipMemcpyAsync(d, &L, sizeof(DevLoop), hipMemcpyHostToDevice, c->stream));
     c->loop_active = true;
+    // THE PAIR STREAM (reduce.h): 24 bytes per staged source point -- whole packets: the last packet's lanes past the end read
+    // their slots too --, grow-only, for the loops whose iterations take reduce_pt2pl_kernel (the first pass sets nn_valid and
+    // clears user pairs).  Not `ensure`: a failed allocation is no error, the loop then gathers as ever -- and keeps the smaller
+    // buffer it had, for the smaller clouds that may follow.
+    c->pairs_on = false;
+    if (pt2pl_inputs(c, est, 0) && c->ns > kFusedMax && c->pair_state.p != nullptr) {
+        const size_t bytes = (size_t)((c->ns + 63) / 64) * 64 * kPairPlanes * sizeof(float2);
+        if (c->tpair.bytes < bytes) {
+            void* grown = nullptr;
+            if (hipMalloc(&grown, bytes) == hipSuccess) {
+                if (c->tpair.p) HIPCHK(c, hipStreamSynchronize(c->stream));  // (the old one may still be in use by enqueued work)
+                release(c->tpair);
+                c->tpair.p = grown;
+                c->tpair.bytes = bytes;
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+        c->pairs_on = c->tpair.p != nullptr && c->tpair.bytes >= bytes;
+    }
     // The first pass has no previous matches; launch_nn picks how it starts.
     c->halo.on_loop_begin();
     {

@@ -219,6 +219,7 @@ struct PacketResult {
 // index; wave-uniform).  `loop` != nullptr: the transform comes from the device-resident loop state and
 // nothing is done once that loop is finished (returns false, wave-uniformly); otherwise Tv (by value) is
 // used.  Stores the matches (and distances / statistics when asked) itself.
+// pair_state != nullptr (the loop's seeded searches): reduce.h's pair stream, voided per packet where a match changes.
 // expiry != nullptr (the loop's seeded searches, "the skip" above): the packet leaves its new limit, and -- a sample of the
 // packets, one in 2^live_shift, 64 at most -- says in live[] whether it got one (the host's hint, ctx.h skip_pays).
 template <bool SEED, bool STATS>
@@ -228,7 +229,8 @@ __device__ __forceinline__ bool nn_packet_body(
         int ns, const float* __restrict__ records_g, const float* __restrict__ tblk_g,
         const float* __restrict__ lreg_g, const float* __restrict__ halo_g, uint32_t leaf_first, Xform Tv, const DevLoop* __restrict__ loop, float r2, int32_t* __restrict__ nn_idx,
         float* __restrict__ nn_d2, unsigned long long* __restrict__ stats, uint32_t* __restrict__ want, PacketResult& out,
-        double* __restrict__ expiry = nullptr, uint8_t* __restrict__ live = nullptr, uint32_t live_shift = 0u) {
+        double* __restrict__ expiry = nullptr, uint8_t* __restrict__ live = nullptr, uint32_t live_shift = 0u,
+        uint8_t* __restrict__ pair_state = nullptr) {
     const int lane = lane_id();
     // (the census build leaves no limits: its launches are not the loop's)
     const bool limits = SEED && !STATS && loop != nullptr && expiry != nullptr && nn_d2 == nullptr;  // (wave-uniform)
@@ -578,7 +580,12 @@ __device__ __forceinline__ bool nn_packet_body(
         // a converged iteration changes (almost) no match: the store is skipped where nothing changed.
         // nn_d2 == nullptr: the caller has no use for the distances (the registration loop: the
         // reduction recomputes them from the points) -- together a fifth of this kernel's traffic
-        if (!SEED || bidx != seed_j) nn_idx[i] = bidx;
+        // pair_state != nullptr (the loop's seeded searches): a changed match voids the packet's pair record -- the
+        // same byte from every lane that stores, at a wave-uniform address
+        if (!SEED || bidx != seed_j) {
+            nn_idx[i] = bidx;
+            if (SEED && pair_state != nullptr) pair_state[packet] = 0;
+        }
         if (nn_d2) nn_d2[i] = (bidx >= 0) ? best : INFINITY;
     }
     if (STATS && lane == 0) {  // traversal census for tuning (mi_icp_debug_nn_stats)
@@ -619,7 +626,7 @@ __global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(GATE
         int ns, const float* __restrict__ records_g, const float* __restrict__ tblk_g,
         const float* __restrict__ lreg_g, const float* __restrict__ halo_g, uint32_t leaf_first, Xform Tv, const DevLoop* __restrict__ loop, float r2, uint32_t nblocks, int32_t* __restrict__ nn_idx,
         float* __restrict__ nn_d2, unsigned long long* __restrict__ stats, uint32_t* __restrict__ want,
-        double* __restrict__ expiry, uint8_t* __restrict__ live, uint32_t live_shift, uint32_t run) {
+        double* __restrict__ expiry, uint8_t* __restrict__ live, uint32_t live_shift, uint32_t run, uint8_t* __restrict__ pair_state) {
     __shared__ PacketShared s_pk[kNNPacketsPerBlock];
     uint32_t logical;
     if (!xcd_remap(nblocks, logical)) return;
@@ -631,7 +638,7 @@ __global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(GATE
     if (STAMP && stamps && threadIdx.x == 0 && blockIdx.x < 64u) atomicMin(stamps + 0, stamp_now());
     if (!GATE) {
         (void)nn_packet_body<SEED, STATS>(s_pk[0], logical, sx, sy, sz, ns, records_g, tblk_g, lreg_g, halo_g, leaf_first, Tv, loop,
-                                          r2, nn_idx, nn_d2, stats, want, unused, expiry, live, live_shift);
+                                          r2, nn_idx, nn_d2, stats, want, unused, expiry, live, live_shift, pair_state);
     } else {
         // (GATE: a seeded search of the loop that stores no distances -- the arguments a loop over packets need not
         // keep in registers are constants here: kept, they spilled a hundred scalar registers)
@@ -646,7 +653,7 @@ __global__ __launch_bounds__(kNNThreads) __attribute__((amdgpu_waves_per_eu(GATE
             const uint32_t k = (uint32_t)__builtin_ctz(need);
             need &= need - 1u;
             (void)nn_packet_body<true, false>(s_pk[0], first + k, sx, sy, sz, ns, records_g, tblk_g, lreg_g, halo_g, leaf_first, Xform{},
-                                              loop, r2, nn_idx, nullptr, nullptr, want, unused, expiry, live, live_shift);
+                                              loop, r2, nn_idx, nullptr, nullptr, want, unused, expiry, live, live_shift, pair_state);
             __builtin_amdgcn_wave_barrier();  // (the next packet takes over the wave's LDS)
         }
     }
@@ -667,7 +674,7 @@ static __global__ __launch_bounds__(256) void locate_by_planes(
         const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int ns,
         const float2* __restrict__ cell_planes, int cell_levels, const uint32_t* __restrict__ gstart,
         const float2* __restrict__ gplanes, uint32_t nleaf, Xform Tv, const DevLoop* __restrict__ loop, int gated,
-        int32_t* __restrict__ nn_idx, double* __restrict__ expiry) {
+        int32_t* __restrict__ nn_idx, double* __restrict__ expiry, uint8_t* __restrict__ pair_state) {
     Xform T = Tv;
     if (loop) {
         if (loop->done) return;
@@ -682,6 +689,7 @@ static __global__ __launch_bounds__(256) void locate_by_planes(
         const uint32_t leaf = min(g * 512u + descend_group(gplanes + (size_t)g * 512u, qx, qy, qz), nleaf - 1u);
         nn_idx[i] = (int32_t)(leaf * (uint32_t)kLeaf);
         if (expiry != nullptr && (i & 63) == 0) expiry[i >> 6] = -(double)INFINITY;  // new seeds: the packet's limit ("the skip") is void
+        if (pair_state != nullptr && (i & 63) == 0) pair_state[i >> 6] = 0;         // ... and so is its pair record (reduce.h)
     }
 }
 

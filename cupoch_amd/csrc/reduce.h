@@ -493,55 +493,201 @@ __global__ __launch_bounds__(kReduceThreads) void reduce_kernel(ReduceArgs a, Xf
 // registers cost it an occupancy step; this kernel runs two blocks per CU and has them to spare.)
 // STEP == 2 (N > 1 on one node): the finishing block first exchanges the sums with the other ranks
 // through the mailbox (mailbox.h), then steps -- still no third launch and no collective.
-template <int kU, int STEP, bool STAMP = false>
-__global__ __launch_bounds__(kReduceThreads) void reduce_pt2pl_kernel(ReduceArgs a, Xform Tv,
-                                                                      DevLoop* __restrict__ loop,
-                                                                      double* __restrict__ partial,
-                                                                      uint32_t* __restrict__ ticket,
-                                                                      double* __restrict__ out32, MailArgs mail) {
+//
+// PAIRS (the registration loop's launches when the pair stream is allocated): a packet -- 64 consecutive source
+// points, one wave's share of a trip, since the block size and the stride are multiples of 64 -- whose matches have stood
+// still through a whole search has its 64 gathered records kept next to the source (PairArgs), and the trips after that read
+// those instead of the index and the gather: pt2pl_pair_sums below.
+struct PairArgs {
+    uint8_t* state;   // per packet: 0 a match changed in the last search (or nothing known), 1 seen once since, 2 the record is valid
+    uint64_t* mask;   // per packet, valid in state 2: bit l = lane l exists and has a match
+    float2* tpair;    // per packet three planes of float2[64]: {p.x, p.y} {p.z, n.x} {n.y, n.z}
+};
+constexpr int kPairPlanes = 3;
+
+// The body of reduce_pt2pl_kernel<.., PAIRS = true>: the same elements per thread in the same order with the same nine
+// floats each as the plain kernel, so the sums are its sums bit for bit.  Per packet (everything here is wave-uniform):
+//   state 2  sx, sy, sz, the mask and the three planes: coalesced, independent, requested one trip ahead;
+//   state 1  the gather as ever; the six floats are kept in the planes, the ballot of `have` in the mask; -> 2
+//   state 0  the gather as ever; -> 1
+// The state byte of the trip after next is requested one trip ahead, the next trip's data -- on the path its state names
+// -- before this trip's arithmetic.  Only this kernel raises a state; the search lowers it (nn_search.h), the host too.
+template <int kU>
+__device__ __forceinline__ void pt2pl_pair_sums(const ReduceArgs& a, const PairArgs& pr, const DevLoop* loop, Xform& T,
+                                                bool& finished, double* acc) {
     const int64_t stride = (int64_t)gridDim.x * kReduceThreads;
     const int64_t k0 = (int64_t)blockIdx.x * kReduceThreads + threadIdx.x;
-    // the first batch is requested before the loop state is even looked at
+    const int64_t trip = stride * kU;
+    const int64_t npackets = (a.count + 63) >> 6;
+    const int lane = lane_id();
+    uint8_t* __restrict__ const state = pr.state;
+    uint64_t* __restrict__ const mask = pr.mask;
+    float2* __restrict__ const tpair = pr.tpair;
+    constexpr uint32_t kNone = 3u;  // a packet past the end: nothing to keep, nothing to promote
+    // what is in flight for the next trip (at the top of a trip: for this one)
+    uint32_t st[kU], st_raw[kU], st_far[kU];
     int32_t j[kU];
+    uint64_t m[kU];
     float px[kU], py[kU], pz[kU];
+    float2 rec[kU][kPairPlanes];
+    auto ask = [&](int64_t kb, uint32_t* raw) {
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int64_t p = (kb + (int64_t)u * stride) >> 6;
+            raw[u] = state[p < npackets ? p : 0];
+        }
+    };
+    auto settle = [&](int64_t kb, const uint32_t* raw, uint32_t* s) {
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int64_t p = (kb + (int64_t)u * stride) >> 6;
+            s[u] = (uint32_t)__builtin_amdgcn_readfirstlane((int)((p < npackets) ? raw[u] : kNone));  // (a scalar: the paths below are branches, not masks)
+        }
+    };
+    // (branch-free, like the plain kernel's: a branch around a load makes the compiler wait for loads still in flight
+    // where the paths meet.  What a path does not need is read from element 0 by every lane -- one request, in cache.)
     auto fetch = [&](int64_t kb) {
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
             const int64_t k = kb + (int64_t)u * stride;
             const int64_t kc = (k < a.count) ? k : 0;
-            j[u] = a.nn_idx[kc];
+            const bool paired = st[u] == 2u;
             px[u] = a.sx[kc];
             py[u] = a.sy[kc];
             pz[u] = a.sz[kc];
+            j[u] = a.nn_idx[paired ? 0 : kc];
+            m[u] = mask[paired ? (k >> 6) : 0];
+            // (a lane past the end of the last packet reads its own slot of that packet: tpair holds WHOLE packets, loop_begin)
+            const float2* rp = tpair + (paired ? (k >> 6) * (kPairPlanes * 64) + lane : 0);
+#pragma unroll
+            for (int q = 0; q < kPairPlanes; ++q) rec[u][q] = rp[paired ? q * 64 : 0];
         }
     };
-    fetch(k0);
-    Xform T = Tv;
-    unsigned long long* stamps = nullptr;  // (STAMP only: loop.h "where an iteration's time goes")
+    ask(k0, st_raw);
+    ask(k0 + trip, st_far);
+    settle(k0, st_raw, st);
+    fetch(k0);  // the first batch is requested before the loop state is even looked at
     if (loop) {
-        if (loop->done) return;
+        if (loop->done) {
+            finished = true;
+            return;
+        }
         T = loop->X;
-        if (STAMP) stamps = reinterpret_cast<unsigned long long*>(loop->stamps);
     }
-    if (STAMP && stamps && threadIdx.x == 0) atomicMin(stamps + 2, stamp_now());
-    double acc[30];
+    for (int64_t kb = k0; kb < a.count; kb += trip) {
+        uint32_t now[kU];
 #pragma unroll
-    for (int k = 0; k < 30; ++k) acc[k] = 0.0;
-    for (int64_t kb = k0; kb < a.count; kb += stride * kU) {
+        for (int u = 0; u < kU; ++u) {
+            now[u] = st[u];
+            st_raw[u] = st_far[u];
+        }
         float vt[kU][3], nt[kU][3];
         bool have[kU];
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
-            have[u] = (kb + (int64_t)u * stride) < a.count && j[u] >= 0;
-            trec_gather(a.trec, have[u] ? j[u] : 0, vt[u], nt[u]);
+            const bool inside = (kb + (int64_t)u * stride) < a.count;
+            if (now[u] == 2u) {
+                have[u] = inside && ((m[u] >> lane) & 1ull) != 0ull;
+                vt[u][0] = rec[u][0].x;
+                vt[u][1] = rec[u][0].y;
+                vt[u][2] = rec[u][1].x;
+                nt[u][0] = rec[u][1].y;
+                nt[u][1] = rec[u][2].x;
+                nt[u][2] = rec[u][2].y;
+            } else {
+                have[u] = inside && j[u] >= 0;
+                trec_gather(a.trec, have[u] ? j[u] : 0, vt[u], nt[u]);
+            }
         }
         float vs[kU][3];
 #pragma unroll
         for (int u = 0; u < kU; ++u) xform_point(T, px[u], py[u], pz[u], vs[u][0], vs[u][1], vs[u][2]);
-        fetch(kb + stride * kU);  // the next batch's coalesced loads overlap this batch's arithmetic
+        settle(kb + trip, st_raw, st);
+        ask(kb + 2 * trip, st_far);  // (behind the uses above: they wait for everything asked before them)
+        fetch(kb + trip);  // the next batch's coalesced loads overlap this batch's arithmetic
 #pragma unroll
         for (int u = 0; u < kU; ++u)
             if (have[u]) pt2pl_rows<0>(acc, vs[u], vt[u], nt[u]);
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int64_t p = (kb + (int64_t)u * stride) >> 6;
+            if (now[u] == 1u) {  // stood still through a whole search: keep what was gathered
+                float2* wp = tpair + p * (kPairPlanes * 64) + lane;
+                wp[0] = make_float2(vt[u][0], vt[u][1]);
+                wp[64] = make_float2(vt[u][2], nt[u][0]);
+                wp[128] = make_float2(nt[u][1], nt[u][2]);
+                const uint64_t b = __ballot(have[u]);
+                if (lane == 0) {
+                    mask[p] = b;
+                    state[p] = 2;
+                }
+            } else if (now[u] == 0u) {
+                if (lane == 0) state[p] = 1;
+            }
+        }
+    }
+}
+
+template <int kU, int STEP, bool STAMP = false, bool PAIRS = false>
+__global__ __launch_bounds__(kReduceThreads) void reduce_pt2pl_kernel(ReduceArgs a, Xform Tv,
+                                                                      DevLoop* __restrict__ loop,
+                                                                      double* __restrict__ partial,
+                                                                      uint32_t* __restrict__ ticket,
+                                                                      double* __restrict__ out32, MailArgs mail, PairArgs pr) {
+    const int64_t stride = (int64_t)gridDim.x * kReduceThreads;
+    const int64_t k0 = (int64_t)blockIdx.x * kReduceThreads + threadIdx.x;
+    Xform T = Tv;
+    unsigned long long* stamps = nullptr;  // (STAMP only: loop.h "where an iteration's time goes")
+    double acc[30];
+    // Two bodies: pt2pl_pair_sums and the plain loop below.  They must stay the same sums -- the same elements per thread in the
+    // same order through xform_point and pt2pl_rows<0> -- and tests/test_gpu_pair_stream.py holds them to it bit for bit.  The
+    // plain body is kept as it was, not folded into the other, so that every launch outside a loop is the kernel it has been.
+    if (PAIRS) {  // (never with STAMP: a stamped loop runs without the pair stream)
+#pragma unroll
+        for (int k = 0; k < 30; ++k) acc[k] = 0.0;
+        bool finished = false;
+        pt2pl_pair_sums<kU>(a, pr, loop, T, finished, acc);
+        if (finished) return;
+    } else {
+        // the first batch is requested before the loop state is even looked at
+        int32_t j[kU];
+        float px[kU], py[kU], pz[kU];
+        auto fetch = [&](int64_t kb) {
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                const int64_t k = kb + (int64_t)u * stride;
+                const int64_t kc = (k < a.count) ? k : 0;
+                j[u] = a.nn_idx[kc];
+                px[u] = a.sx[kc];
+                py[u] = a.sy[kc];
+                pz[u] = a.sz[kc];
+            }
+        };
+        fetch(k0);
+        if (loop) {
+            if (loop->done) return;
+            T = loop->X;
+            if (STAMP) stamps = reinterpret_cast<unsigned long long*>(loop->stamps);
+        }
+        if (STAMP && stamps && threadIdx.x == 0) atomicMin(stamps + 2, stamp_now());
+#pragma unroll
+        for (int k = 0; k < 30; ++k) acc[k] = 0.0;
+        for (int64_t kb = k0; kb < a.count; kb += stride * kU) {
+            float vt[kU][3], nt[kU][3];
+            bool have[kU];
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                have[u] = (kb + (int64_t)u * stride) < a.count && j[u] >= 0;
+                trec_gather(a.trec, have[u] ? j[u] : 0, vt[u], nt[u]);
+            }
+            float vs[kU][3];
+#pragma unroll
+            for (int u = 0; u < kU; ++u) xform_point(T, px[u], py[u], pz[u], vs[u][0], vs[u][1], vs[u][2]);
+            fetch(kb + stride * kU);  // the next batch's coalesced loads overlap this batch's arithmetic
+#pragma unroll
+            for (int u = 0; u < kU; ++u)
+                if (have[u]) pt2pl_rows<0>(acc, vs[u], vt[u], nt[u]);
+        }
     }
     // (the finishing block keeps its word of the loop state, its totals and -- STEP == 2 -- the exchange counter in
     // registers: loop.h StepPre)

@@ -259,6 +259,20 @@ class Engine:
             will = (st[0] + st[1] < lim) if armed.value else np.zeros(n.value, bool)
         return {"travel": float(st[0]), "fuzz": float(st[1]), "limits": lim, "armed": bool(armed.value), "will_skip": will}
 
+    def pair_state(self):
+        """test hook (mi_icp_debug.h): the pair stream's per-packet `state` (uint8: 0, 1, 2 = record valid) and `mask`
+        (uint64: the lanes with a match; meaningful in state 2) as the last launch left them"""
+        n = C.c_int64(0)
+        self._chk(self._L.mi_icp_debug_pair_state(self._ctx, None, None, 0, C.byref(n)))
+        st, mk = np.zeros(n.value, np.uint8), np.zeros(n.value, np.uint64)
+        self._chk(self._L.mi_icp_debug_pair_state(self._ctx, st.ctypes.data_as(C.c_void_p), mk.ctypes.data_as(C.c_void_p),
+                                                  n.value, C.byref(n)))
+        return {"state": st, "mask": mk}
+
+    def drop_pairs(self):
+        """test hook (mi_icp_debug.h): every packet's pair state back to 0, nothing else"""
+        self._chk(self._L.mi_icp_debug_drop_pairs(self._ctx))
+
     def last_search_kind(self):
         """test hook: 0 = the last search started at the root, 1 = from the previous matches, 2 = from its own seeds"""
         return int(self._L.mi_icp_debug_last_search_kind(self._ctx))

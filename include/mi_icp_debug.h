@@ -45,9 +45,10 @@ MI_ICP_API int mi_icp_debug_last_search_kind(const mi_icp_ctx* ctx);
  * (the switch MI_ICP_NO_DENSE_VOXEL is read at every call). */
 MI_ICP_API int mi_icp_debug_last_voxel_path(const mi_icp_ctx* ctx);
 /* Resident workgroups per CU the runtime grants a kernel at its launch shape (hipOccupancyMaxActiveBlocksPerMultiprocessor):
- * which = 0 kd_build_groups, 1 nn_packet_kernel<seeded>, 2 nn_packet_kernel<from the root>, 3 reduce_pt2pl_kernel<4,1>,
- * 4 leaf_halo_build, 5 rs_scatter_pay<8>, 6 voxel_means_wave, 7 vx_scatter<1>, 8 vx_finish<points only>.  Returns the
- * count, < 0 on error. */
+ * which = 0 kd_build_groups, 1 nn_packet_kernel<seeded>, 2 nn_packet_kernel<from the root>, 3 reduce_pt2pl_kernel<2,1> with the pair stream,
+ * 4 leaf_halo_build, 5 rs_scatter_pay<8>, 6 voxel_means_wave, 7 vx_scatter<1>, 8 vx_finish<points only>,
+ * 9 reduce_pt2pl_kernel<4,1> with the pair stream (sources below 4 Mi points; 3 is the instantiation of larger ones; until
+ * the pair stream 3 was the plain <2,1>).  The reductions are launched two workgroups per CU.  Returns the count, < 0 on error. */
 MI_ICP_API int mi_icp_debug_occupancy(int which);
 /* Where an iteration's time goes (csrc/loop.h): with stamps enabled the NEXT registration loop on the context runs the
  * same search / point-to-plane reduction kernels instantiated with device-clock stamps (s_memrealtime, one clock for the
@@ -70,6 +71,17 @@ MI_ICP_API int mi_icp_debug_loop_counters(mi_icp_ctx* ctx, int32_t* out4);
  * travel + fuzz < limit, travel and fuzz as its own step leaves them.  Fails without a loop. */
 MI_ICP_API int mi_icp_debug_search_skip(mi_icp_ctx* ctx, double* state2, double* limits_out, int64_t capacity,
                                         int64_t* npackets, int* armed);
+/* The pair stream's state (csrc/reduce.h PairArgs) as the last launch left it: *n_out = the staged source's
+ * packets of 64 points; state_out[packet] (one byte each: 0 a match changed in the last search or nothing is known, 1 the
+ * reduction has seen the packet once since, 2 its record of matched points and normals is valid) and mask_out[packet] (bit l:
+ * lane l exists and has a match; meaningful in state 2) are host memory, filled when capacity >= *n_out; either may be NULL.
+ * Fails without a staged source. */
+MI_ICP_API int mi_icp_debug_pair_state(mi_icp_ctx* ctx, uint8_t* state_out, uint64_t* mask_out, int64_t capacity,
+                                       int64_t* n_out);
+/* Every packet's pair state back to 0 -- and nothing else: matches, limits of the search skip and the loop stay.  The
+ * next two reductions of a loop gather every record again (tests compare that path with the pair stream's: the results
+ * must be identical bit for bit). */
+MI_ICP_API int mi_icp_debug_drop_pairs(mi_icp_ctx* ctx);
 /* The leaf every staged source point FALLS INTO under T (column-major 4x4 or NULL) by the binary descent through the
  * cell planes and its group's planes (nn_search.h locate_by_planes): leaf_out[original source index] = leaf (host memory,
  * one per source point).  The located leaves are left behind as the seeds of the next seeded pass.  Fails without a
