@@ -18,7 +18,7 @@ INCLUDE = os.path.join(ROOT, "include")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I/opt/rocm/include"]
 # the library's translation units (csrc/ctx.h says what each holds); compiled side by side, then linked
-UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_knn", "mi_comm", "mi_debug"]
+UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_occgrid", "mi_knn", "mi_comm", "mi_debug"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 MI_ICP_HOST, MI_ICP_DEVICE = 0, 1
@@ -126,6 +126,12 @@ class OdometryOption(C.Structure):
                 ("inv_sigma_mat_diag", C.c_float * 6)]
 
 
+class OccGridParams(C.Structure):                      # mi_icp_occgrid_params
+    _fields_ = [("voxel_size", C.c_float), ("origin", C.c_float * 3), ("clamping_thres_min", C.c_float),
+                ("clamping_thres_max", C.c_float), ("prob_hit_log", C.c_float), ("prob_miss_log", C.c_float),
+                ("occ_prob_thres_log", C.c_float)]
+
+
 # name -> (restype, argtypes); must list every MI_ICP_API symbol of include/mi_icp.h
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SIGNATURES = {
@@ -181,6 +187,17 @@ SIGNATURES = {
     "mi_icp_tsdf_extract_voxel_point_cloud": (_I, [_P, _P, _P, _P, _L, C.POINTER(_L), _I]),
     "mi_icp_tsdf_raycast": (_I, [_P, _P, _I, _I, _P, _P, _F, _I, _P, _P, _P, _L, C.POINTER(_L), _I]),
     "mi_icp_tsdf_get_voxels": (_I, [_P, _P, _P, _P, _P, _I]),
+    "mi_icp_occgrid_create": (_I, [_P, _I, C.POINTER(_P)]),
+    "mi_icp_occgrid_destroy": (_I, [_P, _P]),
+    "mi_icp_occgrid_reset": (_I, [_P, _P]),
+    "mi_icp_occgrid_reconstruct": (_I, [_P, _P, _I]),
+    "mi_icp_occgrid_insert": (_I, [_P, _P, C.POINTER(OccGridParams), _P, _L, _P, _F]),
+    "mi_icp_occgrid_add_voxels": (_I, [_P, _P, C.POINTER(OccGridParams), _P, _L, _I]),
+    "mi_icp_occgrid_set_free_area": (_I, [_P, _P, C.POINTER(OccGridParams), _P, _P]),
+    "mi_icp_occgrid_query": (_I, [_P, _P, C.POINTER(OccGridParams), _P, _L, _P, _P]),
+    "mi_icp_occgrid_extract": (_I, [_P, _P, C.POINTER(OccGridParams), _I, _P, _P, _P, _L, C.POINTER(_L)]),
+    "mi_icp_occgrid_get_bounds": (_I, [_P, _P, _P, _P]),
+    "mi_icp_occgrid_get_voxels": (_I, [_P, _P, _P]),
     "mi_icp_covariances_from_normals": (_I, [_P, _P, _L, _F, _P, _I]),
     "mi_icp_estimate_normals_knn": (_I, [_P, _P, _L, _I, _P, _I]),
     "mi_icp_estimate_normals_radius": (_I, [_P, _P, _L, _F, _I, _P, _I]),

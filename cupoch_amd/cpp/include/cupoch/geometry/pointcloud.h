@@ -18,7 +18,7 @@ namespace geometry {
 
 class Geometry {
 public:
-    enum class GeometryType { Unspecified = 0, PointCloud = 1, AxisAlignedBoundingBox = 13 };  // geometry.h:37-68
+    enum class GeometryType { Unspecified = 0, PointCloud = 1, OccupancyGrid = 3, AxisAlignedBoundingBox = 13 };  // geometry.h:37-68
     virtual ~Geometry() {}
     GeometryType GetGeometryType() const { return type_; }
     int Dimension() const { return dimension_; }
@@ -34,6 +34,7 @@ private:
 };
 
 class AxisAlignedBoundingBox3;
+class OccupancyGrid;
 
 /// geometry/geometry_base.h:33-90 with VectorT = Vector3f, MatrixT = Matrix3f, TransformT = Matrix4f
 class GeometryBase3D : public Geometry {
@@ -203,6 +204,8 @@ public:
                                                            const Eigen::Matrix4f& extrinsic = Eigen::Matrix4f::Identity(),
                                                            bool project_valid_depth_only = true,
                                                            float depth_cutoff = -1.0f, bool compute_normals = false);
+    /// pointcloud_factory.cu:418-430: the centres of the grid's occupied voxels, every colour (0, 0, 1)
+    static std::shared_ptr<PointCloud> CreateFromOccupancyGrid(const OccupancyGrid& occgrid);
 
 public:
     utility::device_vector<Eigen::Vector3f> points_;

@@ -81,6 +81,7 @@ typedef Matrix<float, 4, 1> Vector4f;
 typedef Matrix<float, 6, 1> Vector6f;
 typedef Matrix<int, 2, 1> Vector2i;
 typedef Matrix<int, 3, 1> Vector3i;
+typedef Matrix<unsigned short, 3, 1> Vector3ui16;
 typedef Matrix<float, 3, 3> Matrix3f;
 typedef Matrix<float, 4, 4> Matrix4f;
 typedef Matrix<float, 6, 6> Matrix6f;

@@ -951,6 +951,226 @@ std::tuple<bool, Eigen::Matrix4f, Eigen::Vector6f, Eigen::Matrix6f> ComputeWeigh
 
 }  // namespace odometry
 
+// ---------------------------------------------------------------- occupancy grid
+namespace geometry {
+
+namespace {
+mi_icp_occgrid_params OccParams(const OccupancyGrid& g) {
+    mi_icp_occgrid_params p;
+    p.voxel_size = g.voxel_size_;
+    for (int k = 0; k < 3; ++k) p.origin[k] = g.origin_[k];
+    p.clamping_thres_min = g.clamping_thres_min_;
+    p.clamping_thres_max = g.clamping_thres_max_;
+    p.prob_hit_log = g.prob_hit_log_;
+    p.prob_miss_log = g.prob_miss_log_;
+    p.occ_prob_thres_log = g.occ_prob_thres_log_;
+    return p;
+}
+}  // namespace
+
+OccupancyGrid::OccupancyGrid() : OccupancyGrid(0.05f, 512, Eigen::Vector3f::Zero()) {}
+
+OccupancyGrid::OccupancyGrid(float voxel_size, size_t resolution, const Eigen::Vector3f& origin)
+    : GeometryBase3D(GeometryType::OccupancyGrid), voxel_size_(voxel_size), resolution_((int)resolution), origin_(origin) {
+    min_bound_ = max_bound_ = Eigen::Vector3i(resolution_ / 2, resolution_ / 2, resolution_ / 2);
+}
+
+OccupancyGrid::~OccupancyGrid() {
+    if (grid_) (void)mi_icp_occgrid_destroy(Engine(), grid_);
+}
+
+mi_icp_occgrid* OccupancyGrid::Handle() const {
+    if (!grid_) {
+        Check(mi_icp_occgrid_create(Engine(), resolution_, &grid_));
+        made_resolution_ = resolution_;
+        RefreshBounds();
+    } else if (made_resolution_ != resolution_) {
+        const int rc = mi_icp_occgrid_reconstruct(Engine(), grid_, resolution_);
+        if (rc == MI_ICP_ERR_HIP) grid_ = nullptr;  // (the planes could not be made: the handle is gone)
+        Check(rc);
+        made_resolution_ = resolution_;
+        RefreshBounds();
+    }
+    return grid_;
+}
+
+void OccupancyGrid::RefreshBounds() const {
+    Check(mi_icp_occgrid_get_bounds(Engine(), grid_, min_bound_.data(), max_bound_.data()));
+}
+
+OccupancyGrid& OccupancyGrid::Clear() {
+    if (grid_ && made_resolution_ == resolution_) Check(mi_icp_occgrid_reset(Engine(), grid_));
+    min_bound_ = max_bound_ = Eigen::Vector3i(resolution_ / 2, resolution_ / 2, resolution_ / 2);
+    return *this;
+}
+
+Eigen::Vector3f OccupancyGrid::GetMinBound() const {
+    const int h = resolution_ / 2;
+    Eigen::Vector3f out;
+    for (int k = 0; k < 3; ++k) out[k] = (float)(min_bound_[k] - h) * voxel_size_ + origin_[k];
+    return out;
+}
+
+Eigen::Vector3f OccupancyGrid::GetMaxBound() const {
+    const int h = resolution_ / 2;
+    Eigen::Vector3f out;
+    for (int k = 0; k < 3; ++k) out[k] = (float)(max_bound_[k] - (h - 1)) * voxel_size_ + origin_[k];
+    return out;
+}
+
+AxisAlignedBoundingBox3 OccupancyGrid::GetAxisAlignedBoundingBox() const {
+    return AxisAlignedBoundingBox3(GetMinBound(), GetMaxBound());
+}
+
+OccupancyGrid& OccupancyGrid::Transform(const Eigen::Matrix4f&) {
+    LogError("OccupancyGrid::Transform is not supported");
+    return *this;
+}
+
+OccupancyGrid& OccupancyGrid::Rotate(const Eigen::Matrix3f&, bool) {
+    LogError("OccupancyGrid::Rotate is not supported");
+    return *this;
+}
+
+OccupancyGrid& OccupancyGrid::Translate(const Eigen::Vector3f& translation, bool relative) {
+    origin_ = relative ? origin_ + translation : translation;
+    return *this;
+}
+
+OccupancyGrid& OccupancyGrid::Scale(const float scale, bool) {
+    voxel_size_ *= scale;
+    return *this;
+}
+
+utility::device_vector<float> OccupancyGrid::GetProbLog(const utility::device_vector<Eigen::Vector3f>& points) const {
+    utility::device_vector<float> out(points.size());
+    if (points.empty()) return out;
+    const mi_icp_occgrid_params p = OccParams(*this);
+    Check(mi_icp_occgrid_query(Engine(), Handle(), &p, Ptr(points), (int64_t)points.size(), out.data(), nullptr));
+    Check(mi_icp_synchronize(Engine()));
+    return out;
+}
+
+std::tuple<bool, OccupancyVoxel> OccupancyGrid::GetVoxel(const Eigen::Vector3f& point) const {
+    const mi_icp_occgrid_params p = OccParams(*this);
+    utility::device_vector<Eigen::Vector3f> pt(std::vector<Eigen::Vector3f>{point});
+    utility::device_vector<float> prob(1);
+    utility::device_vector<Eigen::Vector3i> idx(1);
+    Check(mi_icp_occgrid_query(Engine(), Handle(), &p, Ptr(pt), 1, prob.data(), idx.data()->data()));
+    Check(mi_icp_synchronize(Engine()));
+    const float v = prob.to_host()[0];
+    if (std::isnan(v)) return std::make_tuple(false, OccupancyVoxel());
+    return std::make_tuple(true, OccupancyVoxel(idx.to_host()[0], v));
+}
+
+bool OccupancyGrid::IsOccupied(const Eigen::Vector3f& point) const {
+    const auto r = GetVoxel(point);
+    return std::get<0>(r) && std::get<1>(r).prob_log_ > occ_prob_thres_log_;
+}
+
+bool OccupancyGrid::IsUnknown(const Eigen::Vector3f& point) const { return !std::get<0>(GetVoxel(point)); }
+
+std::shared_ptr<std::vector<OccupancyVoxel>> OccupancyGrid::Extract(int which) const {
+    const mi_icp_occgrid_params p = OccParams(*this);
+    mi_icp_occgrid* g = Handle();
+    auto out = std::make_shared<std::vector<OccupancyVoxel>>();
+    int64_t m = 0;
+    Check(mi_icp_occgrid_extract(Engine(), g, &p, which, nullptr, nullptr, nullptr, 0, &m));
+    if (m == 0) return out;
+    utility::device_vector<Eigen::Vector3i> idx((size_t)m);
+    utility::device_vector<float> prob((size_t)m);
+    Check(mi_icp_occgrid_extract(Engine(), g, &p, which, idx.data()->data(), prob.data(), nullptr, m, &m));
+    Check(mi_icp_synchronize(Engine()));
+    const std::vector<Eigen::Vector3i> hi = idx.to_host();
+    const std::vector<float> hp = prob.to_host();
+    out->reserve((size_t)m);
+    for (size_t i = 0; i < (size_t)m; ++i) out->push_back(OccupancyVoxel(hi[i], hp[i]));
+    return out;
+}
+
+std::shared_ptr<std::vector<OccupancyVoxel>> OccupancyGrid::ExtractKnownVoxels() const { return Extract(MI_ICP_OCCGRID_KNOWN); }
+std::shared_ptr<std::vector<OccupancyVoxel>> OccupancyGrid::ExtractFreeVoxels() const { return Extract(MI_ICP_OCCGRID_FREE); }
+std::shared_ptr<std::vector<OccupancyVoxel>> OccupancyGrid::ExtractOccupiedVoxels() const { return Extract(MI_ICP_OCCGRID_OCCUPIED); }
+
+OccupancyGrid& OccupancyGrid::Reconstruct(float voxel_size, int resolution) {
+    voxel_size_ = voxel_size;
+    resolution_ = resolution;
+    if (grid_) {
+        made_resolution_ = 0;  // (also for the same resolution: every voxel unknown again)
+        (void)Handle();
+    } else {
+        min_bound_ = max_bound_ = Eigen::Vector3i(resolution_ / 2, resolution_ / 2, resolution_ / 2);
+    }
+    return *this;
+}
+
+OccupancyGrid& OccupancyGrid::SetFreeArea(const Eigen::Vector3f& min_bound, const Eigen::Vector3f& max_bound) {
+    const mi_icp_occgrid_params p = OccParams(*this);
+    Check(mi_icp_occgrid_set_free_area(Engine(), Handle(), &p, min_bound.data(), max_bound.data()));
+    RefreshBounds();
+    return *this;
+}
+
+OccupancyGrid& OccupancyGrid::Insert(const utility::device_vector<Eigen::Vector3f>& points, const Eigen::Vector3f& viewpoint,
+                                     float max_range) {
+    if (points.empty()) return *this;
+    const mi_icp_occgrid_params p = OccParams(*this);
+    Check(mi_icp_occgrid_insert(Engine(), Handle(), &p, Ptr(points), (int64_t)points.size(), viewpoint.data(), max_range));
+    RefreshBounds();
+    return *this;
+}
+
+OccupancyGrid& OccupancyGrid::Insert(const thrust::host_vector<Eigen::Vector3f>& points, const Eigen::Vector3f& viewpoint,
+                                     float max_range) {
+    return Insert(utility::device_vector<Eigen::Vector3f>(points), viewpoint, max_range);
+}
+
+OccupancyGrid& OccupancyGrid::Insert(const PointCloud& pointcloud, const Eigen::Vector3f& viewpoint, float max_range) {
+    return Insert(pointcloud.points_, viewpoint, max_range);
+}
+
+OccupancyGrid& OccupancyGrid::AddVoxel(const Eigen::Vector3i& voxel, bool occupied) {
+    return AddVoxels(utility::device_vector<Eigen::Vector3i>(std::vector<Eigen::Vector3i>{voxel}), occupied);
+}
+
+OccupancyGrid& OccupancyGrid::AddVoxels(const utility::device_vector<Eigen::Vector3i>& voxels, bool occupied) {
+    if (voxels.empty()) return *this;
+    const mi_icp_occgrid_params p = OccParams(*this);
+    mi_icp_occgrid* g = Handle();
+    const int rc = mi_icp_occgrid_add_voxels(Engine(), g, &p, voxels.data()->data(), (int64_t)voxels.size(), occupied ? 1 : 0);
+    if (rc == MI_ICP_ERR_INVALID) {  // an index outside the grid: logged, nothing changed (occupancygrid.cu:551-555)
+        LogError(mi_icp_last_error(Engine()));
+        return *this;
+    }
+    Check(rc);
+    RefreshBounds();
+    return *this;
+}
+
+std::vector<float> OccupancyGrid::GetVoxels() const {
+    const size_t n = (size_t)resolution_ * (size_t)resolution_ * (size_t)resolution_;
+    mi_icp_occgrid* g = Handle();
+    utility::device_vector<float> plane(n);
+    Check(mi_icp_occgrid_get_voxels(Engine(), g, plane.data()));
+    return plane.to_host();
+}
+
+std::shared_ptr<PointCloud> PointCloud::CreateFromOccupancyGrid(const OccupancyGrid& occgrid) {
+    auto out = std::make_shared<PointCloud>();
+    const mi_icp_occgrid_params p = OccParams(occgrid);
+    mi_icp_occgrid* g = occgrid.Handle();
+    int64_t m = 0;
+    Check(mi_icp_occgrid_extract(Engine(), g, &p, MI_ICP_OCCGRID_OCCUPIED, nullptr, nullptr, nullptr, 0, &m));
+    if (m == 0) return out;
+    out->points_.resize((size_t)m);
+    Check(mi_icp_occgrid_extract(Engine(), g, &p, MI_ICP_OCCGRID_OCCUPIED, nullptr, nullptr, out->points_.data()->data(), m, &m));
+    Check(mi_icp_synchronize(Engine()));
+    out->colors_ = std::vector<Eigen::Vector3f>((size_t)m, Eigen::Vector3f(0.0f, 0.0f, 1.0f));
+    return out;
+}
+
+}  // namespace geometry
+
 // ---------------------------------------------------------------- integration
 namespace integration {
 

@@ -22,13 +22,16 @@
 #include <cstdint>
 #include <cstring>
 #include <memory>
+#include <sstream>
 #include <stdexcept>
+#include <string>
 #include <type_traits>
 #include <vector>
 
 #include "cupoch/camera/pinhole_camera_intrinsic.h"
 #include "cupoch/geometry/image.h"
 #include "cupoch/geometry/keypoint.h"
+#include "cupoch/geometry/occupancygrid.h"
 #include "cupoch/geometry/pointcloud.h"
 #include "cupoch/integration/uniform_tsdfvolume.h"
 #include "cupoch/knn/kdtree_flann.h"
@@ -76,6 +79,19 @@ farray from_vector3(const Eigen::Vector3f& v) {
     farray a(3);
     for (int i = 0; i < 3; ++i) a.mutable_at(i) = v(i);
     return a;
+}
+
+Eigen::Vector3i to_vector3i(const py::array_t<int, py::array::c_style | py::array::forcecast>& a) {
+    if (a.size() != 3) throw std::invalid_argument("expected 3 integers");
+    const int* p = a.data();
+    return Eigen::Vector3i(p[0], p[1], p[2]);
+}
+
+// the extractions' voxels as a list of geometry.OccupancyVoxel, ascending in linear index
+py::list voxel_list(const std::vector<geometry::OccupancyVoxel>& v) {
+    py::list out;
+    for (const geometry::OccupancyVoxel& x : v) out.append(py::cast(x));
+    return out;
 }
 
 // utility.Vector3fVector: a device vector of Vector3f, constructed from an (n, 3) array (one H2D
@@ -543,6 +559,7 @@ PYBIND11_MODULE(cupoch_pybind, m) {
                     "distance_threshold"_a = 0.01f, "ransac_n"_a = 3, "num_iterations"_a = 100)
             .def("estimate_normals", &geometry::PointCloud::EstimateNormals,
                  "search_param"_a = knn::KDTreeSearchParamKNN())
+            .def_static("create_from_occupancy_grid", &geometry::PointCloud::CreateFromOccupancyGrid, "occgrid"_a)
             .def("__len__", [](const geometry::PointCloud& pc) { return pc.points_.size(); });
 
     // geometry.keypoint (geometry/keypoint.cpp; the reference spells the last keyword "max_neighbots")
@@ -574,6 +591,111 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             .def(py::init<const geometry::Image&, const geometry::Image&>(), "color"_a, "depth"_a)
             .def_readwrite("color", &geometry::RGBDImage::color_)
             .def_readwrite("depth", &geometry::RGBDImage::depth_);
+
+    // geometry.OccupancyVoxel / geometry.OccupancyGrid (cupoch_pybind/geometry/occupancygrid.cpp) with the reference's
+    // names, defaults and read-write attributes.  Not bound, as not built: create_from_voxel_grid (no VoxelGrid type).
+    py::class_<geometry::OccupancyVoxel, std::shared_ptr<geometry::OccupancyVoxel>>(mg, "OccupancyVoxel")
+            .def(py::init<>())
+            .def(py::init([](const py::array_t<int, py::array::c_style | py::array::forcecast>& g) {
+                     return std::make_shared<geometry::OccupancyVoxel>(to_vector3i(g));
+                 }),
+                 "grid_index"_a)
+            .def(py::init([](const py::array_t<int, py::array::c_style | py::array::forcecast>& g, float prob_log) {
+                     return std::make_shared<geometry::OccupancyVoxel>(to_vector3i(g), prob_log);
+                 }),
+                 "grid_index"_a, "prob_log"_a)
+            .def(py::init([](const py::array_t<int, py::array::c_style | py::array::forcecast>& g, float prob_log,
+                             const farray& color) {
+                     return std::make_shared<geometry::OccupancyVoxel>(to_vector3i(g), prob_log, to_vector3(color));
+                 }),
+                 "grid_index"_a, "prob_log"_a, "color"_a)
+            .def("__repr__",
+                 [](const geometry::OccupancyVoxel& v) {
+                     std::ostringstream repr;
+                     repr << "geometry::OccupancyVoxel with grid_index: (" << v.grid_index_(0) << ", " << v.grid_index_(1) << ", "
+                          << v.grid_index_(2) << "), prob_log: " << v.prob_log_ << ", color: (" << v.color_(0) << ", "
+                          << v.color_(1) << ", " << v.color_(2) << ")";
+                     return repr.str();
+                 })
+            .def_property(
+                    "grid_index",
+                    [](const geometry::OccupancyVoxel& v) {
+                        py::array_t<int> a(3);
+                        for (int k = 0; k < 3; ++k) a.mutable_at(k) = (int)v.grid_index_(k);
+                        return a;
+                    },
+                    [](geometry::OccupancyVoxel& v, const py::array_t<int, py::array::c_style | py::array::forcecast>& g) {
+                        const Eigen::Vector3i i = to_vector3i(g);
+                        for (int k = 0; k < 3; ++k) v.grid_index_(k) = (unsigned short)i(k);
+                    })
+            .def_readwrite("prob_log", &geometry::OccupancyVoxel::prob_log_)
+            .def_property(
+                    "color", [](const geometry::OccupancyVoxel& v) { return from_vector3(v.color_); },
+                    [](geometry::OccupancyVoxel& v, const farray& c) { v.color_ = to_vector3(c); });
+
+    py::class_<geometry::OccupancyGrid, std::shared_ptr<geometry::OccupancyGrid>>(mg, "OccupancyGrid")
+            .def(py::init<>())
+            .def(py::init([](float voxel_size, int resolution) {
+                     return std::make_shared<geometry::OccupancyGrid>(voxel_size, (size_t)resolution);
+                 }),
+                 "voxel_size"_a, "resolution"_a)
+            .def(py::init([](float voxel_size, int resolution, const farray& origin) {
+                     return std::make_shared<geometry::OccupancyGrid>(voxel_size, (size_t)resolution, to_vector3(origin));
+                 }),
+                 "voxel_size"_a, "resolution"_a, "origin"_a)
+            .def("__repr__",
+                 [](const geometry::OccupancyGrid& g) {
+                     return std::string("geometry::OccupancyGrid with ") + std::to_string(g.ExtractKnownVoxels()->size()) +
+                            " voxels.";
+                 })
+            .def_property_readonly("voxels", [](const geometry::OccupancyGrid& g) { return voxel_list(*g.ExtractKnownVoxels()); })
+            .def("extract_known_voxels", [](const geometry::OccupancyGrid& g) { return voxel_list(*g.ExtractKnownVoxels()); })
+            .def("extract_free_voxels", [](const geometry::OccupancyGrid& g) { return voxel_list(*g.ExtractFreeVoxels()); })
+            .def("extract_occupied_voxels", [](const geometry::OccupancyGrid& g) { return voxel_list(*g.ExtractOccupiedVoxels()); })
+            .def("reconstruct", [](geometry::OccupancyGrid& g, float voxel_size, int resolution) { g.Reconstruct(voxel_size, resolution); },
+                 "voxel_size"_a, "resolution"_a)
+            .def("insert",
+                 [](geometry::OccupancyGrid& g, const geometry::PointCloud& pc, const farray& viewpoint, float max_range) {
+                     g.Insert(pc, to_vector3(viewpoint), max_range);
+                 },
+                 "pointcloud"_a, "viewpoint"_a, "max_range"_a = -1.0f)
+            .def("add_voxel",
+                 [](geometry::OccupancyGrid& g, const py::array_t<int, py::array::c_style | py::array::forcecast>& v,
+                    bool occupied) { g.AddVoxel(to_vector3i(v), occupied); },
+                 "voxel"_a, "occupied"_a = false)
+            .def("set_free_area",
+                 [](geometry::OccupancyGrid& g, const farray& lo, const farray& hi) { g.SetFreeArea(to_vector3(lo), to_vector3(hi)); },
+                 "min_bound"_a, "max_bound"_a)
+            .def("get_voxel",
+                 [](const geometry::OccupancyGrid& g, const farray& point) {
+                     const auto r = g.GetVoxel(to_vector3(point));
+                     return std::make_tuple(std::get<0>(r), std::get<1>(r));
+                 },
+                 "point"_a)
+            .def("is_occupied", [](const geometry::OccupancyGrid& g, const farray& p) { return g.IsOccupied(to_vector3(p)); }, "point"_a)
+            .def("is_unknown", [](const geometry::OccupancyGrid& g, const farray& p) { return g.IsUnknown(to_vector3(p)); }, "point"_a)
+            .def("clear", [](geometry::OccupancyGrid& g) { g.Clear(); })
+            .def("get_min_bound", [](const geometry::OccupancyGrid& g) { return from_vector3(g.GetMinBound()); })
+            .def("get_max_bound", [](const geometry::OccupancyGrid& g) { return from_vector3(g.GetMaxBound()); })
+            .def("get_center", [](const geometry::OccupancyGrid& g) { return from_vector3(g.GetCenter()); })
+            .def("get_voxels",
+                 [](const geometry::OccupancyGrid& g) {
+                     const std::vector<float> h = g.GetVoxels();
+                     py::array_t<float> a((py::ssize_t)h.size());
+                     if (!h.empty()) std::memcpy(a.mutable_data(), h.data(), h.size() * sizeof(float));
+                     return a;
+                 })
+            .def_readwrite("voxel_size", &geometry::OccupancyGrid::voxel_size_)
+            .def_readwrite("resolution", &geometry::OccupancyGrid::resolution_)
+            .def_property(
+                    "origin", [](const geometry::OccupancyGrid& g) { return from_vector3(g.origin_); },
+                    [](geometry::OccupancyGrid& g, const farray& v) { g.origin_ = to_vector3(v); })
+            .def_readwrite("clamping_thres_min", &geometry::OccupancyGrid::clamping_thres_min_)
+            .def_readwrite("clamping_thres_max", &geometry::OccupancyGrid::clamping_thres_max_)
+            .def_readwrite("prob_hit_log", &geometry::OccupancyGrid::prob_hit_log_)
+            .def_readwrite("prob_miss_log", &geometry::OccupancyGrid::prob_miss_log_)
+            .def_readwrite("occ_prob_thres_log", &geometry::OccupancyGrid::occ_prob_thres_log_)
+            .def_readwrite("visualize_free_area", &geometry::OccupancyGrid::visualize_free_area_);
 
     // ---------------------------------------------------------------- camera
     py::module mc = m.def_submodule("camera");

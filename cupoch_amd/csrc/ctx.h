@@ -7,6 +7,7 @@
 //   mi_voxel.hip     VoxelDownSample (the dense-grid path and the general one)
 //   mi_rgbd.hip      depth / RGB-D frame -> cloud, RGB-D odometry
 //   mi_tsdf.hip      UniformTSDFVolume
+//   mi_occgrid.hip   OccupancyGrid
 //   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry,
 //                    RemoveStatisticalOutliers / RemoveRadiusOutliers, ClusterDBSCAN, ComputeISSKeypoints
 //   mi_comm.hip      the ranks' exchange: mailbox, device inboxes, in-library RCCL, self-test and choice
@@ -162,6 +163,8 @@ struct mi_icp_ctx {
 
     // ---- integration::UniformTSDFVolume: the volumes this context made (mi_tsdf.hip), freed with it ----
     std::vector<mi_icp_tsdf*> tsdf_volumes;
+    // ---- geometry::OccupancyGrid: the grids this context made (mi_occgrid.hip), freed with it ----
+    std::vector<mi_icp_occgrid*> occ_grids;
 
     // ---- instrumentation ----
     mi::eng::DevBuf stamps;    // loop.h "where an iteration's time goes" (mi_icp_debug_set_step_stamps)
@@ -514,6 +517,8 @@ int launch_locate_by_planes(mi_icp_ctx* c, const Xform& X, const DevLoop* loop, 
 int occupancy_geometry(int which);
 // ---- mi_tsdf.hip
 void tsdf_release_all(mi_icp_ctx* c);     // mi_icp_destroy: the volumes of mi_icp_tsdf_create
+// ---- mi_occgrid.hip
+void occgrid_release_all(mi_icp_ctx* c);  // mi_icp_destroy: the grids of mi_icp_occgrid_create
 // ---- mi_geometry.hip
 // The points whose flags[0..n) are set, ascending (select.h: exclusive_scan_u32 + select_gather), into out[] (the
 // caller's, staged when mem_kind is MI_ICP_HOST) and their original indices into out_idx (may be null); *m = their

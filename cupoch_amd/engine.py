@@ -739,6 +739,106 @@ class Engine:
         self._chk(self._L.mi_icp_tsdf_get_voxels(self._ctx, vol, tp, wp, cp, kind))
         return t, w, (None if c is None else (c.T.contiguous() if on_device else np.ascontiguousarray(c.T)))
 
+    # -- geometry::OccupancyGrid (include/mi_icp.h; arrays are device tensors, numpy inputs are uploaded) ----------
+    @staticmethod
+    def occgrid_params(voxel_size, origin, clamping_thres_min, clamping_thres_max, prob_hit_log, prob_miss_log,
+                       occ_prob_thres_log):
+        p = _lib.OccGridParams()
+        p.voxel_size = float(voxel_size)
+        p.origin[:] = [float(v) for v in np.asarray(origin, np.float32).reshape(3)]
+        p.clamping_thres_min, p.clamping_thres_max = float(clamping_thres_min), float(clamping_thres_max)
+        p.prob_hit_log, p.prob_miss_log = float(prob_hit_log), float(prob_miss_log)
+        p.occ_prob_thres_log = float(occ_prob_thres_log)
+        return p
+
+    def _occ_dev(self, a, dtype):
+        """[n, 3] of dtype on this engine's GPU: a tensor there is read in place, anything else is uploaded"""
+        tdt = {np.float32: torch.float32, np.int32: torch.int32}[dtype]
+        dev = torch.device("cuda", self.device)
+        if _is_tensor(a):
+            t = a.to(device=dev, dtype=tdt)
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dtype))).to(dev)
+        return t.reshape(-1, 3).contiguous()
+
+    def occgrid_create(self, resolution):
+        """-> an opaque grid handle of this engine (mi_icp_occgrid_create)"""
+        h = C.c_void_p()
+        self._chk(self._L.mi_icp_occgrid_create(self._ctx, int(resolution), C.byref(h)))
+        return h
+
+    def occgrid_destroy(self, grid):
+        if getattr(self, "_ctx", None) and grid:
+            self._chk(self._L.mi_icp_occgrid_destroy(self._ctx, grid))
+
+    def occgrid_reset(self, grid):
+        self._chk(self._L.mi_icp_occgrid_reset(self._ctx, grid))
+
+    def occgrid_reconstruct(self, grid, resolution):
+        self._chk(self._L.mi_icp_occgrid_reconstruct(self._ctx, grid, int(resolution)))
+
+    def occgrid_insert(self, grid, params, points, viewpoint, max_range=-1.0):
+        t = self._occ_dev(points, np.float32)
+        vp = (C.c_float * 3)(*[float(v) for v in np.asarray(viewpoint, np.float32).reshape(3)])
+        self._chk(self._L.mi_icp_occgrid_insert(self._ctx, grid, C.byref(params), C.c_void_p(t.data_ptr()), int(t.shape[0]),
+                                                vp, float(max_range)))
+
+    def occgrid_add_voxels(self, grid, params, indices, occupied=False):
+        t = self._occ_dev(indices, np.int32)
+        self._chk(self._L.mi_icp_occgrid_add_voxels(self._ctx, grid, C.byref(params), C.c_void_p(t.data_ptr()),
+                                                    int(t.shape[0]), int(bool(occupied))))
+
+    def occgrid_set_free_area(self, grid, params, min_bound, max_bound):
+        lo = (C.c_float * 3)(*[float(v) for v in np.asarray(min_bound, np.float32).reshape(3)])
+        hi = (C.c_float * 3)(*[float(v) for v in np.asarray(max_bound, np.float32).reshape(3)])
+        self._chk(self._L.mi_icp_occgrid_set_free_area(self._ctx, grid, C.byref(params), lo, hi))
+
+    def occgrid_query(self, grid, params, points):
+        """-> (log-odds [n], NaN for unknown or outside; voxel index [n, 3] int32), device tensors"""
+        t = self._occ_dev(points, np.float32)
+        n = int(t.shape[0])
+        dev = torch.device("cuda", self.device)
+        (prob, pp), (idx, ip) = self._out(MI_ICP_DEVICE, dev, (n,)), self._out(MI_ICP_DEVICE, dev, (n, 3), np.int32)
+        self._chk(self._L.mi_icp_occgrid_query(self._ctx, grid, C.byref(params), C.c_void_p(t.data_ptr()), n, pp, ip))
+        self.synchronize()   # (t may go)
+        return prob, idx
+
+    OCCGRID_FIRST_CAPACITY = 1 << 18   # voxels an extraction makes room for before it knows the count
+
+    def occgrid_extract(self, grid, params, which, want_points=False):
+        """-> (grid_index [m, 3] int32, prob_log [m], points [m, 3] or None), device tensors, ascending linear index;
+        the capacity rule of include/mi_icp.h"""
+        dev = torch.device("cuda", self.device)
+        m = C.c_int64(0)
+        capacity = self.OCCGRID_FIRST_CAPACITY
+        for _ in range(2):
+            (idx, ip), (prob, pp) = self._out(MI_ICP_DEVICE, dev, (capacity, 3), np.int32), self._out(MI_ICP_DEVICE, dev, (capacity,))
+            xyz, xp = self._out(MI_ICP_DEVICE, dev, (capacity, 3)) if want_points else (None, None)
+            self._chk(self._L.mi_icp_occgrid_extract(self._ctx, grid, C.byref(params), int(which), ip, pp, xp, capacity,
+                                                     C.byref(m)))
+            if int(m.value) <= capacity:
+                break
+            capacity = int(m.value)
+        k = int(m.value)
+        return self._trim(idx, k), self._trim(prob, k), self._trim(xyz, k)
+
+    def occgrid_count(self, grid, params, which):
+        m = C.c_int64(0)
+        self._chk(self._L.mi_icp_occgrid_extract(self._ctx, grid, C.byref(params), int(which), None, None, None, 0, C.byref(m)))
+        return int(m.value)
+
+    def occgrid_get_bounds(self, grid):
+        """-> (min_bound [3], max_bound [3]) int32 numpy, inclusive voxel indices"""
+        lo, hi = np.zeros(3, np.int32), np.zeros(3, np.int32)
+        self._chk(self._L.mi_icp_occgrid_get_bounds(self._ctx, grid, lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p)))
+        return lo, hi
+
+    def occgrid_get_voxels(self, grid, n):
+        """-> the whole log-odds plane, [n] on the device"""
+        t, tp = self._out(MI_ICP_DEVICE, torch.device("cuda", self.device), (n,))
+        self._chk(self._L.mi_icp_occgrid_get_voxels(self._ctx, grid, tp))
+        return t
+
     def compute_rgbd_odometry(self, source_color, source_depth, target_color, target_depth, intrinsic4,
                               odo_init=None, jacobian=1, iterations=(20, 10, 5), max_depth_diff=0.03,
                               min_depth=0.0, max_depth=4.0, weighted=False, prev_twist=None, nu=5.0,

@@ -1,7 +1,10 @@
 """cupoch.geometry.PointCloud mirror (src/cupoch/geometry/pointcloud.h:43-263,
 python surface src/python/cupoch_pybind/geometry/pointcloud.cpp:33-200) --
 only the members the ICP path touches.  Arrays live on the GPU as torch
-tensors; every operation below runs a HIP kernel through the C ABI."""
+tensors; every operation below runs a HIP kernel through the C ABI.
+OccupancyGrid / OccupancyVoxel mirror geometry/occupancygrid.h:31-142 (python surface
+src/python/cupoch_pybind/geometry/occupancygrid.cpp); not built: create_from_voxel_grid and the VoxelGrid,
+DistanceTransform and collision consumers (no VoxelGrid type here)."""
 import numpy as np
 
 from . import utility
@@ -500,6 +503,233 @@ def _create_from_rgbd_image(image, intrinsic, extrinsic=None, project_valid_dept
 
 PointCloud.create_from_depth_image = staticmethod(_create_from_depth_image)
 PointCloud.create_from_rgbd_image = staticmethod(_create_from_rgbd_image)
+
+
+class OccupancyVoxel:
+    """geometry::OccupancyVoxel (occupancygrid.h:31-51): grid index, log odds, colour"""
+
+    def __init__(self, grid_index=(0, 0, 0), prob_log=float("nan"), color=(0.0, 0.0, 1.0)):
+        self.grid_index = np.asarray(grid_index, np.int32).reshape(3).copy()
+        self.prob_log = float(np.float32(prob_log))
+        self.color = np.asarray(color, np.float32).reshape(3).copy()
+
+    def __repr__(self):
+        g, c = self.grid_index, self.color
+        return "geometry::OccupancyVoxel with grid_index: (%d, %d, %d), prob_log: %g, color: (%g, %g, %g)" % (
+            g[0], g[1], g[2], self.prob_log, c[0], c[1], c[2])
+
+
+class OccupancyVoxels:
+    """what an extraction returns: grid_index [m, 3] int32 and prob_log [m] as device tensors, ascending in linear
+    index; every colour is (0, 0, 1).  len() and [] give OccupancyVoxel objects."""
+
+    def __init__(self, grid_index, prob_log):
+        self.grid_index = grid_index
+        self.prob_log = prob_log
+
+    def __len__(self):
+        return int(self.prob_log.shape[0])
+
+    def __getitem__(self, i):
+        return OccupancyVoxel(self.grid_index[i].cpu().numpy(), float(self.prob_log[i]))
+
+    def cpu(self):
+        """-> (grid_index, prob_log) as numpy arrays"""
+        return self.grid_index.cpu().numpy(), self.prob_log.cpu().numpy()
+
+
+class OccupancyGrid:
+    """geometry::OccupancyGrid (occupancygrid.h:71-142).  The attributes are the reference's public members and are
+    read when a call is made; the voxels live on the GPU, made on first use (a changed `resolution` rebuilds the grid,
+    every voxel unknown, as reconstruct does).  Deviations from the reference: DESIGN.md section 6."""
+
+    KNOWN, FREE, OCCUPIED = 0, 1, 2
+
+    def __init__(self, voxel_size=0.05, resolution=512, origin=(0.0, 0.0, 0.0), device=None):
+        self.voxel_size = float(np.float32(voxel_size))
+        self.resolution = int(resolution)
+        self.origin = np.asarray(origin, np.float32).reshape(3).copy()
+        self.clamping_thres_min = -2.0
+        self.clamping_thres_max = 3.5
+        self.prob_hit_log = 0.85
+        self.prob_miss_log = -0.4
+        self.occ_prob_thres_log = 0.0
+        self.visualize_free_area = True
+        self._device = device
+        self._eng = None
+        self._grid = None
+        self._made_res = 0
+
+    def __del__(self):
+        try:
+            if self._eng is not None:
+                self._eng.occgrid_destroy(self._grid)
+        except Exception:
+            pass
+        self._grid = None
+
+    # the engine, the grid handle and the parameter block of this call
+    def _call(self):
+        if self._eng is None:
+            self._eng = get_engine(self._device)
+        if self._grid is None:
+            self._grid = self._eng.occgrid_create(self.resolution)
+            self._made_res = int(self.resolution)
+        elif self._made_res != int(self.resolution):
+            self._eng.occgrid_reconstruct(self._grid, self.resolution)
+            self._made_res = int(self.resolution)
+        return self._eng, self._grid, self._eng.occgrid_params(
+            self.voxel_size, self.origin, self.clamping_thres_min, self.clamping_thres_max, self.prob_hit_log,
+            self.prob_miss_log, self.occ_prob_thres_log)
+
+    def clear(self):
+        """every voxel unknown, the bounds back to the centre; size and memory stay"""
+        if self._grid is not None and self._made_res == int(self.resolution):
+            self._eng.occgrid_reset(self._grid)
+        return self
+
+    def reconstruct(self, voxel_size, resolution):
+        self.voxel_size = float(np.float32(voxel_size))
+        self.resolution = int(resolution)
+        if self._grid is not None:
+            self._eng.occgrid_reconstruct(self._grid, self.resolution)
+            self._made_res = self.resolution
+        return self
+
+    def insert(self, pointcloud, viewpoint, max_range=-1.0):
+        """Insert(points | PointCloud, viewpoint, max_range)"""
+        pts = pointcloud.points.tensor if isinstance(pointcloud, PointCloud) else (
+            pointcloud.tensor if isinstance(pointcloud, utility.Vector3fVector) else pointcloud)
+        e, g, p = self._call()
+        e.occgrid_insert(g, p, pts, viewpoint, max_range)
+        return self
+
+    def add_voxel(self, voxel, occupied=False):
+        return self.add_voxels(np.asarray(voxel, np.int32).reshape(1, 3), occupied)
+
+    def add_voxels(self, voxels, occupied=False):
+        e, g, p = self._call()
+        e.occgrid_add_voxels(g, p, voxels, occupied)
+        return self
+
+    def set_free_area(self, min_bound, max_bound):
+        e, g, p = self._call()
+        e.occgrid_set_free_area(g, p, min_bound, max_bound)
+        return self
+
+    # ---- queries
+    def get_prob_log(self, points):
+        """batched: [n, 3] points -> [n] log-odds on the device, NaN for unknown or outside the grid"""
+        e, g, p = self._call()
+        return e.occgrid_query(g, p, points)[0]
+
+    def get_voxel(self, point):
+        """-> (known, OccupancyVoxel)"""
+        e, g, p = self._call()
+        prob, idx = e.occgrid_query(g, p, np.asarray(point, np.float32).reshape(1, 3))
+        v = float(prob[0])
+        if v != v:
+            return False, OccupancyVoxel()
+        return True, OccupancyVoxel(idx[0].cpu().numpy(), v)
+
+    def is_occupied(self, point):
+        known, v = self.get_voxel(point)
+        return known and v.prob_log > float(np.float32(self.occ_prob_thres_log))
+
+    def is_unknown(self, point):
+        return not self.get_voxel(point)[0]
+
+    # ---- extraction
+    def _extract(self, which):
+        e, g, p = self._call()
+        idx, prob, _ = e.occgrid_extract(g, p, which)
+        return OccupancyVoxels(idx, prob)
+
+    def extract_known_voxels(self):
+        return self._extract(self.KNOWN)
+
+    def extract_free_voxels(self):
+        return self._extract(self.FREE)
+
+    def extract_occupied_voxels(self):
+        return self._extract(self.OCCUPIED)
+
+    @property
+    def voxels(self):
+        return self.extract_known_voxels()
+
+    def has_voxels(self):
+        return True
+
+    def has_colors(self):
+        return True
+
+    def __repr__(self):
+        e, g, p = self._call()
+        return "geometry::OccupancyGrid with %d voxels." % e.occgrid_count(g, p, self.KNOWN)
+
+    # ---- bounds (voxel indices, inclusive) and GeometryBase3D
+    @property
+    def min_bound(self):
+        e, g, _ = self._call()
+        return e.occgrid_get_bounds(g)[0]
+
+    @property
+    def max_bound(self):
+        e, g, _ = self._call()
+        return e.occgrid_get_bounds(g)[1]
+
+    def get_min_bound(self):
+        h = int(self.resolution) // 2
+        return ((self.min_bound - h).astype(np.float32) * np.float32(self.voxel_size) + np.asarray(self.origin, np.float32)).astype(np.float32)
+
+    def get_max_bound(self):
+        h = int(self.resolution) // 2
+        return ((self.max_bound - (h - 1)).astype(np.float32) * np.float32(self.voxel_size) + np.asarray(self.origin, np.float32)).astype(np.float32)
+
+    def get_center(self):
+        return np.asarray(self.origin, np.float32).copy()
+
+    def get_axis_aligned_bounding_box(self):
+        return AxisAlignedBoundingBox(self.get_min_bound(), self.get_max_bound())
+
+    def is_empty(self):
+        return False
+
+    def translate(self, translation, relative=True):
+        t = np.asarray(translation, np.float32).reshape(3)
+        self.origin = (np.asarray(self.origin, np.float32) + t).astype(np.float32) if relative else t.copy()
+        return self
+
+    def scale(self, scale, center=True):
+        self.voxel_size = float(np.float32(self.voxel_size) * np.float32(scale))
+        return self
+
+    def transform(self, transformation):
+        raise RuntimeError("OccupancyGrid::Transform is not supported")
+
+    def rotate(self, R, center=True):
+        raise RuntimeError("OccupancyGrid::Rotate is not supported")
+
+    def get_voxels(self):
+        """the whole log-odds plane, [resolution^3] on the device, indexed (x*res + y)*res + z; NaN: unknown"""
+        e, g, _ = self._call()
+        return e.occgrid_get_voxels(g, int(self.resolution) ** 3)
+
+
+def _create_from_occupancy_grid(occgrid):
+    """PointCloud::CreateFromOccupancyGrid (pointcloud_factory.cu:418-430): the occupied voxels' centres, all blue"""
+    e, g, p = occgrid._call()
+    _, _, xyz = e.occgrid_extract(g, p, OccupancyGrid.OCCUPIED, want_points=True)
+    out = PointCloud()
+    out._points = utility.Vector3fVector(xyz)
+    col = torch.zeros_like(xyz)
+    col[:, 2] = 1.0
+    out._colors = utility.Vector3fVector(col)
+    return out
+
+
+PointCloud.create_from_occupancy_grid = staticmethod(_create_from_occupancy_grid)
 
 
 def _v3(v):

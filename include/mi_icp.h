@@ -25,6 +25,10 @@
  *     MI_ICP_ERR_INVALID before any buffer is read or written.  The caller owns all
  *     buffers it passes; the context owns its internal SoA copies, LBVH and
  *     scratch arena.
+ *     THE ONE EXCEPTION is the mi_icp_occgrid_* family: its arrays (points, voxel
+ *     indices, outputs) are HIP device pointers only and it has no memory-kind
+ *     argument; its small fixed-size arguments (the parameter block, viewpoint3,
+ *     corners, bounds, counts) are host pointers or values.
  *   - one context per GPU; a context is not thread-safe, independent contexts
  *     may be driven from different host threads.
  *   - all work is enqueued on the context's stream (mi_icp_set_stream; the
@@ -779,6 +783,108 @@ MI_ICP_API int mi_icp_tsdf_raycast(mi_icp_ctx* ctx, mi_icp_tsdf* volume, int wid
                                    int64_t capacity, int64_t* m, int mem_kind);
 MI_ICP_API int mi_icp_tsdf_get_voxels(mi_icp_ctx* ctx, mi_icp_tsdf* volume, float* tsdf_out, float* weight_out,
                                       float* color_out, int mem_kind);
+
+/* ---- geometry::OccupancyGrid (geometry/occupancygrid.{h,cu}, densegrid.inl; the cloud of
+ * geometry/pointcloud_factory.cu:418-430) ---------------------------------------------------------
+ * A dense grid of resolution^3 voxels of side voxel_size around origin, each holding one fp32 log-odds,
+ * NaN meaning unknown; linear index (x*res + y)*res + z; h = res / 2 (integer).  It belongs to the
+ * context that made it: destroyed with mi_icp_occgrid_destroy, or with the context.  Stored as the
+ * log-odds plane alone, 4 bytes per voxel (the reference keeps 24: a grid index that is the voxel's
+ * position and a colour it never writes, always (0, 0, 1)), beside a one-byte mark per voxel that is
+ * zero between calls.  Not built: CreateFromVoxelGrid and the VoxelGrid, DistanceTransform and collision
+ * consumers (no VoxelGrid type here).
+ *
+ * ARRAYS ARE DEVICE POINTERS; there is no memory-kind argument in this family (the preamble's one
+ * exception).  `params`, viewpoint3, min3 / max3 and the counts are host memory.  voxel_size, origin and
+ * the five log-odds parameters travel with every call (the reference's public members are read when a
+ * call is made); only the resolution is the grid's own.
+ *
+ * NUMERIC CONTRACT.  fp32 in exactly the order written unless a step says double; products are never
+ * fused; / and sqrt are correctly rounded.  floor(.) to int holds the value inside +-1e9 first.
+ *  update(p, s)  p = isnan(p) ? 0 : p;  p = p + s;  p = p < clamping_thres_min ? clamping_thres_min : p;
+ *                p = p > clamping_thres_max ? clamping_thres_max : p
+ *  Insert(points, viewpoint, max_range):  n == 0 is a no-op.  A point with a coordinate that is not
+ *   finite is skipped (the reference is undefined there).
+ *   1 per point  d = p - viewpoint;  dist = sqrt((d.x*d.x + d.y*d.y) + d.z*d.z);
+ *                hit = max_range < 0 || dist <= max_range;
+ *                q = hit ? p : (dist == 0 ? viewpoint : viewpoint + (d / dist) * max_range);
+ *                r = max_k |q_k - viewpoint_k|
+ *   2 n_div = (int)ceil(max r / voxel_size);  n_buf = 3 * (n_div + 1).  n_div above
+ *     MI_ICP_OCCGRID_MAX_NDIV: MI_ICP_ERR_INVALID, nothing changed.
+ *   3 if n_div > 0, every point contributes the voxels of VoxelTraversal(start = viewpoint - origin,
+ *     end = q - origin) (occupancygrid.cu:60-133):
+ *       ray = end - start;  length = sqrt((ray.x*ray.x + ray.y*ray.y) + ray.z*ray.z);  length == 0: none
+ *       ray = ray / length;  cur = floor(start / vs);  last = floor(end / vs);  step = sign(ray)
+ *       boundary = (float)(((double)cur + 0.5 * (double)step) * (double)vs)      -- HALF a voxel
+ *       tMax = (boundary - start) / ray;  tDelta = vs / |ray|;  both +inf where step == 0
+ *       emit cur;  while emitted < n_buf:
+ *         axis = tMaxX < tMaxY ? (tMaxX < tMaxZ ? x : z) : (tMaxY < tMaxZ ? y : z)
+ *         cur[axis] += step[axis];  tMax[axis] += tDelta[axis]
+ *         stop if cur == last (the end voxel is never emitted);  stop if min(tMax) > length;  emit cur
+ *     emitted voxels get + h per axis; those outside [0, res)^3 are dropped
+ *   4 occupied voxels: floor((q - origin) / vs) + h of the hit points, those inside the grid
+ *   5 every voxel of free \ occupied: update(p, prob_miss_log), once; then every occupied voxel:
+ *     update(p, prob_hit_log), once.  No sum depends on the order of the points.
+ *   6 min_bound / max_bound (inclusive, both (h, h, h) at first) widen to the bounding box of the
+ *     voxels step 5 updated.  (That is NOT the box of the rays' end voxels: the half-voxel boundary lets
+ *     a walk leave it by a voxel.)
+ *  AddVoxels(indices int32[n][3], occupied): every DISTINCT listed voxel gets update() once (the
+ *   reference races on duplicates), the bounds widen.  An index outside the grid: MI_ICP_ERR_INVALID,
+ *   nothing changed.
+ *  SetFreeArea(min, max): imin = max(floor((min - origin) / vs) + h, 0), imax = min(floor((max - origin)
+ *   / vs) + h, res - 1); the bounds are OVERWRITTEN with them; every voxel of that box gets
+ *   p = isnan(p) ? 0 : p; p = p + prob_miss_log with NO clamp (both as the reference does).  A box that
+ *   misses the grid leaves imin > imax on an axis: no voxel changes and the extractions are empty.
+ *  query: the voxel of a point is floor((point - origin) / vs) + h per axis; out_prob_log[i] is its
+ *   log-odds, NaN when it is unknown or outside the grid ON ANY AXIS (the reference tests only the
+ *   linear index, so such a point aliases into another voxel); out_index (optional) int32[n][3].
+ *  extract(which): the voxels of the box [min_bound, max_bound] with !isnan(p) (KNOWN), additionally
+ *   p <= occ_prob_thres_log (FREE) or p > occ_prob_thres_log (OCCUPIED), ascending in linear index:
+ *   out_index int32[m][3] (the voxel's position; the reference reports (0,0,0) for voxels only
+ *   SetFreeArea touched), out_prob_log[m], out_xyz float[m][3] = ((float)index + (float)(0.5 - h)) * vs
+ *   + origin (PointCloud::CreateFromOccupancyGrid's points), each optional.  The capacity rule of the
+ *   TSDF extractions: *m is the count; with capacity < *m nothing is written.
+ *  reset: every voxel unknown, the bounds (h, h, h); size and memory stay (the reference's Clear() frees
+ *   the voxels and zeroes the resolution).  reconstruct: a new resolution, every voxel unknown.
+ *  get_bounds: min_bound, max_bound into host int32[3] each.  get_voxels: the whole plane, res^3 floats.
+ * Limits: 2 <= resolution <= MI_ICP_OCCGRID_MAX_RESOLUTION; voxel_size positive and finite; origin,
+ * viewpoint and corners finite; no NaN among the five parameters, hit and miss steps finite; n_div <=
+ * MI_ICP_OCCGRID_MAX_NDIV (a walk of 3 * 4097 voxels per ray at most; four times the largest grid side).
+ * Else MI_ICP_ERR_INVALID and nothing changes.
+ * insert and add_voxels wait for the stream once, at their end (status and bounds in one copy);
+ * extract waits once for the count; get_voxels waits; the others only enqueue. */
+#define MI_ICP_OCCGRID_MAX_RESOLUTION 1024
+#define MI_ICP_OCCGRID_MAX_NDIV 4096
+#define MI_ICP_OCCGRID_KNOWN 0
+#define MI_ICP_OCCGRID_FREE 1
+#define MI_ICP_OCCGRID_OCCUPIED 2
+typedef struct mi_icp_occgrid mi_icp_occgrid;
+typedef struct {
+    float voxel_size;          /* default 0.05 */
+    float origin[3];           /* default 0 */
+    float clamping_thres_min;  /* default -2.0 */
+    float clamping_thres_max;  /* default 3.5 */
+    float prob_hit_log;        /* default 0.85 */
+    float prob_miss_log;       /* default -0.4 */
+    float occ_prob_thres_log;  /* default 0.0 */
+} mi_icp_occgrid_params;
+MI_ICP_API int mi_icp_occgrid_create(mi_icp_ctx* ctx, int resolution, mi_icp_occgrid** out);
+MI_ICP_API int mi_icp_occgrid_destroy(mi_icp_ctx* ctx, mi_icp_occgrid* grid);
+MI_ICP_API int mi_icp_occgrid_reset(mi_icp_ctx* ctx, mi_icp_occgrid* grid);
+MI_ICP_API int mi_icp_occgrid_reconstruct(mi_icp_ctx* ctx, mi_icp_occgrid* grid, int resolution);
+MI_ICP_API int mi_icp_occgrid_insert(mi_icp_ctx* ctx, mi_icp_occgrid* grid, const mi_icp_occgrid_params* params,
+                                     const float* points, int64_t n, const float* viewpoint3, float max_range);
+MI_ICP_API int mi_icp_occgrid_add_voxels(mi_icp_ctx* ctx, mi_icp_occgrid* grid, const mi_icp_occgrid_params* params,
+                                         const int32_t* indices, int64_t n, int occupied);
+MI_ICP_API int mi_icp_occgrid_set_free_area(mi_icp_ctx* ctx, mi_icp_occgrid* grid, const mi_icp_occgrid_params* params,
+                                            const float* min3, const float* max3);
+MI_ICP_API int mi_icp_occgrid_query(mi_icp_ctx* ctx, mi_icp_occgrid* grid, const mi_icp_occgrid_params* params,
+                                    const float* points, int64_t n, float* out_prob_log, int32_t* out_index);
+MI_ICP_API int mi_icp_occgrid_extract(mi_icp_ctx* ctx, mi_icp_occgrid* grid, const mi_icp_occgrid_params* params,
+                                      int which, int32_t* out_index, float* out_prob_log, float* out_xyz,
+                                      int64_t capacity, int64_t* m);
+MI_ICP_API int mi_icp_occgrid_get_bounds(mi_icp_ctx* ctx, mi_icp_occgrid* grid, int32_t* min3, int32_t* max3);
+MI_ICP_API int mi_icp_occgrid_get_voxels(mi_icp_ctx* ctx, mi_icp_occgrid* grid, float* out_prob_log);
 
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
