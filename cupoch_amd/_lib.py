@@ -18,7 +18,7 @@ INCLUDE = os.path.join(ROOT, "include")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I/opt/rocm/include"]
 # the library's translation units (csrc/ctx.h says what each holds); compiled side by side, then linked
-UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_occgrid", "mi_knn", "mi_comm", "mi_debug"]
+UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_occgrid", "mi_voxelgrid", "mi_knn", "mi_comm", "mi_debug"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 MI_ICP_HOST, MI_ICP_DEVICE = 0, 1
@@ -198,6 +198,14 @@ SIGNATURES = {
     "mi_icp_occgrid_extract": (_I, [_P, _P, C.POINTER(OccGridParams), _I, _P, _P, _P, _L, C.POINTER(_L)]),
     "mi_icp_occgrid_get_bounds": (_I, [_P, _P, _P, _P]),
     "mi_icp_occgrid_get_voxels": (_I, [_P, _P, _P]),
+    "mi_icp_voxelgrid_from_points": (_I, [_P, _P, _P, _L, _F, _P, _P, _P, _P, _L, C.POINTER(_L)]),
+    "mi_icp_voxelgrid_dense": (_I, [_P, _I, _I, _I, _P, _P, _L, C.POINTER(_L)]),
+    "mi_icp_voxelgrid_merge": (_I, [_P, _P, _P, _L, _P, _P, _L, _I, _P, _P, _L, C.POINTER(_L)]),
+    "mi_icp_voxelgrid_carve": (_I, [_P, _P, _P, _L, _F, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, C.POINTER(_L)]),
+    "mi_icp_voxelgrid_query": (_I, [_P, _P, _L, _I, _F, _P, _P, _L, _P, _P]),
+    "mi_icp_voxelgrid_bounds": (_I, [_P, _P, _L, _F, _P, _P, _P, _P]),
+    "mi_icp_voxelgrid_select_by_index": (_I, [_P, _P, _P, _L, _P, _L, _I, _P, _P, C.POINTER(_L)]),
+    "mi_icp_voxelgrid_paint": (_I, [_P, _P, _L, _P, _L, _P]),
     "mi_icp_covariances_from_normals": (_I, [_P, _P, _L, _F, _P, _I]),
     "mi_icp_estimate_normals_knn": (_I, [_P, _P, _L, _I, _P, _I]),
     "mi_icp_estimate_normals_radius": (_I, [_P, _P, _L, _F, _I, _P, _I]),

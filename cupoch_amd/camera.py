@@ -1,5 +1,6 @@
 """cupoch.camera.PinholeCameraIntrinsic mirror (src/cupoch/camera/pinhole_camera_intrinsic.h:40-120,
-.cpp:40-92) -- the part the depth-image factories and the KinFu pose estimation use."""
+.cpp:40-92) -- the part the depth-image factories and the KinFu pose estimation use -- and
+camera.PinholeCameraParameters (camera/pinhole_camera_parameters.h), which the VoxelGrid carvings take."""
 import numpy as np
 
 
@@ -39,3 +40,15 @@ class PinholeCameraIntrinsic:
         m = self.intrinsic_matrix
         return PinholeCameraIntrinsic(self.width >> level, self.height >> level, m[0, 0] * s, m[1, 1] * s,
                                       (m[0, 2] + h) * s - h, (m[1, 2] + h) * s - h)
+
+
+class PinholeCameraParameters:
+    """camera::PinholeCameraParameters: intrinsic (a PinholeCameraIntrinsic) and extrinsic (4x4, world -> camera,
+    row-major numpy at this level; the identity until set)"""
+
+    def __init__(self, intrinsic=None, extrinsic=None):
+        self.intrinsic = PinholeCameraIntrinsic() if intrinsic is None else intrinsic
+        self.extrinsic = np.eye(4, dtype=np.float32) if extrinsic is None else np.asarray(extrinsic, np.float32).reshape(4, 4).copy()
+
+    def __repr__(self):
+        return "camera::PinholeCameraParameters class.\nAccess its data via intrinsic and extrinsic."

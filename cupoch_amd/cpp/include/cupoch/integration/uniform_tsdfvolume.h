@@ -2,7 +2,7 @@
 // integration/uniform_tsdfvolume.h:30-89) over mi_icp_tsdf_* (include/mi_icp.h has the numeric
 // contract).  The voxels live in the engine's context as planes; GetVoxels() reads them back in the
 // reference's TSDFVoxel form instead of a public voxels_ vector.
-// Not built: ExtractTriangleMesh, ExtractVoxelGrid (no TriangleMesh / VoxelGrid type here),
+// Not built: ExtractTriangleMesh (no TriangleMesh type here), ExtractVoxelGrid,
 // ScalableTSDFVolume, IntegrateWithDepthToCameraDistanceMultiplier as a public entry.
 #pragma once
 #include <vector>

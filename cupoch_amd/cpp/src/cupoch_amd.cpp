@@ -1169,6 +1169,374 @@ std::shared_ptr<PointCloud> PointCloud::CreateFromOccupancyGrid(const OccupancyG
     return out;
 }
 
+// ---- geometry::VoxelGrid (geometry/voxelgrid.cu, voxelgrid_factory.cu) over mi_icp_voxelgrid_*
+namespace {
+
+void Copy2D(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows) {
+    if (rows == 0) return;
+    const hipError_t e = hipMemcpy2D(dst, dpitch, src, spitch, width, rows, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) throw std::runtime_error(std::string("hipMemcpy2D: ") + hipGetErrorString(e));
+}
+
+// the colours of voxels_values_ as the packed array the engine takes
+utility::device_vector<Eigen::Vector3f> VoxelColors(const utility::device_vector<Voxel>& values) {
+    utility::device_vector<Eigen::Vector3f> c(values.size());
+    Copy2D(c.data(), sizeof(Eigen::Vector3f), (const char*)values.data() + offsetof(Voxel, color_), sizeof(Voxel),
+           sizeof(Eigen::Vector3f), values.size());
+    return c;
+}
+
+// ... and the way back: the first m keys and colours become the grid's voxels
+void SetVoxelArrays(VoxelGrid* g, utility::device_vector<Eigen::Vector3i>& keys, const utility::device_vector<Eigen::Vector3f>& colors,
+                    size_t m) {
+    keys.resize(m);
+    g->voxels_values_ = utility::device_vector<Voxel>(m);
+    Copy2D((char*)g->voxels_values_.data() + offsetof(Voxel, grid_index_), sizeof(Voxel), keys.data(), sizeof(Eigen::Vector3i),
+           sizeof(Eigen::Vector3i), m);
+    Copy2D((char*)g->voxels_values_.data() + offsetof(Voxel, color_), sizeof(Voxel), colors.data(), sizeof(Eigen::Vector3f),
+           sizeof(Eigen::Vector3f), m);
+    g->voxels_keys_.swap(keys);
+}
+
+const int32_t* KeyPtr(const utility::device_vector<Eigen::Vector3i>& v) { return v.empty() ? nullptr : v.data()->data(); }
+int32_t* KeyPtr(utility::device_vector<Eigen::Vector3i>& v) { return v.empty() ? nullptr : v.data()->data(); }
+float* ColPtr(utility::device_vector<Eigen::Vector3f>& v) { return v.empty() ? nullptr : v.data()->data(); }
+
+// a refusal of the engine is what the reference logs as an error
+bool Refused(int rc) {
+    if (rc == MI_ICP_ERR_INVALID) {
+        LogError(mi_icp_last_error(Engine()));
+        return true;
+    }
+    Check(rc);
+    return false;
+}
+
+int FloorIndex(float x) { return (int)std::fmin(std::fmax(std::floor(x), -1.0e9f), 1.0e9f); }
+
+int RoundCount(float extent, float voxel_size) { return (int)std::round(extent / voxel_size); }
+
+}  // namespace
+
+VoxelGrid::VoxelGrid() : GeometryBase3D(GeometryType::VoxelGrid) {}
+VoxelGrid::~VoxelGrid() {}
+VoxelGrid::VoxelGrid(const VoxelGrid& o)
+    : GeometryBase3D(GeometryType::VoxelGrid),
+      voxel_size_(o.voxel_size_),
+      origin_(o.origin_),
+      voxels_keys_(o.voxels_keys_),
+      voxels_values_(o.voxels_values_),
+      sorted_(o.sorted_) {}
+
+std::pair<thrust::host_vector<Eigen::Vector3i>, thrust::host_vector<Voxel>> VoxelGrid::GetVoxels() const {
+    return std::make_pair(voxels_keys_.to_host(), voxels_values_.to_host());
+}
+
+void VoxelGrid::SetVoxels(const thrust::host_vector<Eigen::Vector3i>& voxels_keys, const thrust::host_vector<Voxel>& voxels_values) {
+    voxels_keys_ = voxels_keys;
+    voxels_values_ = voxels_values;
+    sorted_ = false;
+}
+
+VoxelGrid& VoxelGrid::Clear() {
+    voxel_size_ = 0.0f;
+    origin_ = Eigen::Vector3f::Zero();
+    voxels_keys_.clear();
+    voxels_values_.clear();
+    sorted_ = true;
+    return *this;
+}
+
+bool VoxelGrid::IsEmpty() const { return voxels_keys_.empty(); }
+
+namespace {
+struct IndexBounds {
+    Eigen::Vector3i lo, hi;
+    double sum[3];
+};
+IndexBounds GetIndexBounds(const VoxelGrid& g) {
+    IndexBounds b;
+    Check(mi_icp_voxelgrid_bounds(Engine(), KeyPtr(g.voxels_keys_), (int64_t)g.voxels_keys_.size(), g.voxel_size_, g.origin_.data(),
+                                  b.lo.data(), b.hi.data(), b.sum));
+    return b;
+}
+}  // namespace
+
+Eigen::Vector3f VoxelGrid::GetMinBound() const {
+    if (voxels_keys_.empty()) return origin_;
+    const IndexBounds b = GetIndexBounds(*this);
+    Eigen::Vector3f out;
+    for (int k = 0; k < 3; ++k) out[k] = (float)b.lo[k] * voxel_size_ + origin_[k];
+    return out;
+}
+
+Eigen::Vector3f VoxelGrid::GetMaxBound() const {
+    if (voxels_keys_.empty()) return origin_;
+    const IndexBounds b = GetIndexBounds(*this);
+    Eigen::Vector3f out;
+    for (int k = 0; k < 3; ++k) out[k] = ((float)b.hi[k] + 1.0f) * voxel_size_ + origin_[k];
+    return out;
+}
+
+Eigen::Vector3f VoxelGrid::GetCenter() const {
+    Eigen::Vector3f out = Eigen::Vector3f::Zero();
+    if (voxels_keys_.empty()) return out;
+    const IndexBounds b = GetIndexBounds(*this);
+    for (int k = 0; k < 3; ++k) out[k] = (float)(b.sum[k] / (double)voxels_keys_.size());
+    return out;
+}
+
+AxisAlignedBoundingBox3 VoxelGrid::GetAxisAlignedBoundingBox() const {
+    return AxisAlignedBoundingBox3(GetMinBound(), GetMaxBound());
+}
+
+VoxelGrid& VoxelGrid::Transform(const Eigen::Matrix4f&) {
+    LogError("VoxelGrid::Transform is not supported");
+    return *this;
+}
+
+VoxelGrid& VoxelGrid::Rotate(const Eigen::Matrix3f&, bool) {
+    LogError("VoxelGrid::Rotate is not supported");
+    return *this;
+}
+
+VoxelGrid& VoxelGrid::Translate(const Eigen::Vector3f& translation, bool) {
+    origin_ += translation;
+    return *this;
+}
+
+VoxelGrid& VoxelGrid::Scale(const float scale, bool) {
+    voxel_size_ *= scale;
+    return *this;
+}
+
+namespace {
+// this grid's voxels, then `keys` / `colors`: one voxel per key, ascending (include/mi_icp.h, merge)
+void MergeInto(VoxelGrid* g, const utility::device_vector<Eigen::Vector3i>& keys, utility::device_vector<Eigen::Vector3f>& colors,
+               int mode) {
+    utility::device_vector<Eigen::Vector3f> mine = VoxelColors(g->voxels_values_);
+    const size_t cap = g->voxels_keys_.size() + keys.size();
+    utility::device_vector<Eigen::Vector3i> ok(cap);
+    utility::device_vector<Eigen::Vector3f> oc(cap);
+    int64_t m = 0;
+    Check(mi_icp_voxelgrid_merge(Engine(), KeyPtr(g->voxels_keys_), ColPtr(mine), (int64_t)g->voxels_keys_.size(), KeyPtr(keys),
+                                 ColPtr(colors), (int64_t)keys.size(), mode, KeyPtr(ok), ColPtr(oc), (int64_t)cap, &m));
+    SetVoxelArrays(g, ok, oc, (size_t)m);
+}
+
+void KeysOfVoxels(const utility::device_vector<Voxel>& voxels, utility::device_vector<Eigen::Vector3i>* keys) {
+    keys->resize(voxels.size());
+    Copy2D(keys->data(), sizeof(Eigen::Vector3i), (const char*)voxels.data() + offsetof(Voxel, grid_index_), sizeof(Voxel),
+           sizeof(Eigen::Vector3i), voxels.size());
+}
+}  // namespace
+
+VoxelGrid& VoxelGrid::operator+=(const VoxelGrid& voxelgrid) {
+    char msg[256];
+    if (voxel_size_ != voxelgrid.voxel_size_) {
+        std::snprintf(msg, sizeof(msg), "[VoxelGrid] Could not combine VoxelGrid because voxel_size differs (this=%f, other=%f)",
+                      voxel_size_, voxelgrid.voxel_size_);
+        LogError(msg);
+    }
+    if (!(origin_ == voxelgrid.origin_)) {
+        std::snprintf(msg, sizeof(msg), "[VoxelGrid] Could not combine VoxelGrid because origin differs (this=%f,%f,%f, other=%f,%f,%f)",
+                      origin_(0), origin_(1), origin_(2), voxelgrid.origin_(0), voxelgrid.origin_(1), voxelgrid.origin_(2));
+        LogError(msg);
+    }
+    utility::device_vector<Eigen::Vector3f> theirs = VoxelColors(voxelgrid.voxels_values_);
+    MergeInto(this, voxelgrid.voxels_keys_, theirs, MI_ICP_VOXELGRID_AVERAGE);
+    sorted_ = true;
+    return *this;
+}
+
+VoxelGrid VoxelGrid::operator+(const VoxelGrid& voxelgrid) const { return (VoxelGrid(*this) += voxelgrid); }
+
+Eigen::Vector3i VoxelGrid::GetVoxel(const Eigen::Vector3f& point) const {
+    Eigen::Vector3i out;
+    for (int k = 0; k < 3; ++k) out[k] = FloorIndex((point[k] - origin_[k]) / voxel_size_);
+    return out;
+}
+
+Eigen::Vector3f VoxelGrid::GetVoxelCenterCoordinate(const Eigen::Vector3i& idx) const {
+    // the reference's thrust::find, on the host: one key is looked up, not a batch
+    const std::vector<Eigen::Vector3i> keys = voxels_keys_.to_host();
+    for (const Eigen::Vector3i& k : keys) {
+        if (k == idx) {
+            Eigen::Vector3f out;
+            for (int d = 0; d < 3; ++d) out[d] = ((float)idx[d] + 0.5f) * voxel_size_ + origin_[d];
+            return out;
+        }
+    }
+    return Eigen::Vector3f::Zero();
+}
+
+std::array<Eigen::Vector3f, 8> VoxelGrid::GetVoxelBoundingPoints(const Eigen::Vector3i& index) const {
+    const float r = voxel_size_ / 2.0f;
+    const Eigen::Vector3f x = GetVoxelCenterCoordinate(index);
+    std::array<Eigen::Vector3f, 8> p;
+    p[0] = x + Eigen::Vector3f(-r, -r, -r);
+    p[1] = x + Eigen::Vector3f(-r, -r, r);
+    p[2] = x + Eigen::Vector3f(r, -r, -r);
+    p[3] = x + Eigen::Vector3f(r, -r, r);
+    p[4] = x + Eigen::Vector3f(-r, r, -r);
+    p[5] = x + Eigen::Vector3f(-r, r, r);
+    p[6] = x + Eigen::Vector3f(r, r, -r);
+    p[7] = x + Eigen::Vector3f(r, r, r);
+    return p;
+}
+
+void VoxelGrid::AddVoxel(const Voxel& voxel) { AddVoxels(std::vector<Voxel>{voxel}); }
+
+void VoxelGrid::AddVoxels(const utility::device_vector<Voxel>& voxels) {
+    if (voxels.empty()) return;
+    utility::device_vector<Eigen::Vector3i> keys;
+    KeysOfVoxels(voxels, &keys);
+    utility::device_vector<Eigen::Vector3f> colors = VoxelColors(voxels);
+    MergeInto(this, keys, colors, MI_ICP_VOXELGRID_KEEP_FIRST);
+    sorted_ = true;
+}
+
+void VoxelGrid::AddVoxels(const thrust::host_vector<Voxel>& voxels) { AddVoxels(utility::device_vector<Voxel>(voxels)); }
+
+VoxelGrid& VoxelGrid::PaintUniformColor(const Eigen::Vector3f& color) {
+    const size_t m = voxels_values_.size();
+    if (m == 0) return *this;
+    utility::device_vector<Eigen::Vector3f> c(m);
+    Check(mi_icp_voxelgrid_paint(Engine(), ColPtr(c), (int64_t)m, nullptr, 0, color.data()));
+    Copy2D((char*)voxels_values_.data() + offsetof(Voxel, color_), sizeof(Voxel), c.data(), sizeof(Eigen::Vector3f), sizeof(Eigen::Vector3f), m);
+    return *this;
+}
+
+VoxelGrid& VoxelGrid::PaintIndexedColor(const utility::device_vector<size_t>& indices, const Eigen::Vector3f& color) {
+    const size_t m = voxels_values_.size();
+    if (indices.empty()) return *this;
+    utility::device_vector<Eigen::Vector3f> c = VoxelColors(voxels_values_);
+    if (Refused(mi_icp_voxelgrid_paint(Engine(), ColPtr(c), (int64_t)m, (const int64_t*)indices.data(), (int64_t)indices.size(), color.data())))
+        return *this;
+    Copy2D((char*)voxels_values_.data() + offsetof(Voxel, color_), sizeof(Voxel), c.data(), sizeof(Eigen::Vector3f), sizeof(Eigen::Vector3f), m);
+    return *this;
+}
+
+thrust::host_vector<bool> VoxelGrid::CheckIfIncluded(const thrust::host_vector<Eigen::Vector3f>& queries) {
+    thrust::host_vector<bool> output(queries.size(), false);
+    if (queries.empty()) return output;
+    const utility::device_vector<Eigen::Vector3f> q(queries);
+    utility::device_vector<uint8_t> inc(queries.size());
+    if (Refused(mi_icp_voxelgrid_query(Engine(), KeyPtr(voxels_keys_), (int64_t)voxels_keys_.size(), sorted_ ? 1 : 0, voxel_size_,
+                                       origin_.data(), Ptr(q), (int64_t)q.size(), inc.data(), nullptr)))
+        return output;
+    const std::vector<uint8_t> h = inc.to_host();
+    for (size_t i = 0; i < h.size(); ++i) output[i] = h[i] != 0;
+    return output;
+}
+
+namespace {
+VoxelGrid& Carve(VoxelGrid* g, const Image& image, const camera::PinholeCameraParameters& cam, bool keep, const char* what) {
+    if (image.height_ != cam.intrinsic_.height_ || image.width_ != cam.intrinsic_.width_) {
+        LogError((std::string("[VoxelGrid] provided ") + what + " dimensions are not compatible with the provided camera_parameters").c_str());
+        return *g;
+    }
+    const size_t m = g->voxels_keys_.size();
+    if (m == 0) return *g;
+    utility::device_vector<Eigen::Vector3f> colors = VoxelColors(g->voxels_values_);
+    utility::device_vector<Eigen::Vector3i> ok(m);
+    utility::device_vector<Eigen::Vector3f> oc(m);
+    const float intr[4] = {cam.intrinsic_.fx_, cam.intrinsic_.fy_, cam.intrinsic_.cx_, cam.intrinsic_.cy_};
+    int64_t mo = 0;
+    if (Refused(mi_icp_voxelgrid_carve(Engine(), KeyPtr(g->voxels_keys_), ColPtr(colors), (int64_t)m, g->voxel_size_, g->origin_.data(),
+                                       image.data_.data(), image.width_, image.height_, image.num_of_channels_,
+                                       image.bytes_per_channel_, intr, cam.extrinsic_.data(), keep ? 1 : 0, KeyPtr(ok), ColPtr(oc), &mo)))
+        return *g;
+    SetVoxelArrays(g, ok, oc, (size_t)mo);
+    return *g;
+}
+}  // namespace
+
+VoxelGrid& VoxelGrid::CarveDepthMap(const Image& depth_map, const camera::PinholeCameraParameters& camera_parameter,
+                                    bool keep_voxels_outside_image) {
+    return Carve(this, depth_map, camera_parameter, keep_voxels_outside_image, "depth_map");
+}
+
+VoxelGrid& VoxelGrid::CarveSilhouette(const Image& silhouette_mask, const camera::PinholeCameraParameters& camera_parameter,
+                                      bool keep_voxels_outside_image) {
+    return Carve(this, silhouette_mask, camera_parameter, keep_voxels_outside_image, "silhouette_mask");
+}
+
+std::shared_ptr<VoxelGrid> VoxelGrid::SelectByIndex(const utility::device_vector<size_t>& indices, bool invert) {
+    auto dst = std::make_shared<VoxelGrid>();
+    dst->voxel_size_ = voxel_size_;
+    dst->origin_ = origin_;
+    const size_t m = voxels_keys_.size(), rows = invert ? m : indices.size();
+    utility::device_vector<Eigen::Vector3f> colors = VoxelColors(voxels_values_);
+    utility::device_vector<Eigen::Vector3i> ok(rows);
+    utility::device_vector<Eigen::Vector3f> oc(rows);
+    int64_t mo = 0;
+    if (Refused(mi_icp_voxelgrid_select_by_index(Engine(), KeyPtr(voxels_keys_), ColPtr(colors), (int64_t)m,
+                                                 indices.empty() ? nullptr : (const int64_t*)indices.data(), (int64_t)indices.size(),
+                                                 invert ? 1 : 0, KeyPtr(ok), ColPtr(oc), &mo)))
+        return dst;
+    SetVoxelArrays(dst.get(), ok, oc, (size_t)mo);
+    dst->sorted_ = false;
+    return dst;
+}
+
+std::shared_ptr<VoxelGrid> VoxelGrid::CreateDense(const Eigen::Vector3f& origin, float voxel_size, float width, float height, float depth) {
+    auto output = std::make_shared<VoxelGrid>();
+    output->origin_ = origin;
+    output->voxel_size_ = voxel_size;
+    const int nw = RoundCount(width, voxel_size), nh = RoundCount(height, voxel_size), nd = RoundCount(depth, voxel_size);
+    int64_t m = 0;
+    if (Refused(mi_icp_voxelgrid_dense(Engine(), nw, nh, nd, nullptr, nullptr, 0, &m)) || m == 0) return output;
+    utility::device_vector<Eigen::Vector3i> ok((size_t)m);
+    utility::device_vector<Eigen::Vector3f> oc((size_t)m);
+    Check(mi_icp_voxelgrid_dense(Engine(), nw, nh, nd, KeyPtr(ok), ColPtr(oc), m, &m));
+    SetVoxelArrays(output.get(), ok, oc, (size_t)m);
+    return output;
+}
+
+std::shared_ptr<VoxelGrid> VoxelGrid::CreateFromPointCloudWithinBounds(const PointCloud& input, float voxel_size,
+                                                                      const Eigen::Vector3f& min_bound, const Eigen::Vector3f& max_bound) {
+    auto output = std::make_shared<VoxelGrid>();
+    output->voxel_size_ = voxel_size;
+    output->origin_ = min_bound;
+    const size_t n = input.points_.size();
+    utility::device_vector<Eigen::Vector3i> ok(n);
+    utility::device_vector<Eigen::Vector3f> oc(n);
+    int64_t m = 0;
+    if (Refused(mi_icp_voxelgrid_from_points(Engine(), Ptr(input.points_), input.HasColors() ? Ptr(input.colors_) : nullptr, (int64_t)n,
+                                             voxel_size, min_bound.data(), max_bound.data(), KeyPtr(ok), ColPtr(oc), (int64_t)n, &m)))
+        return output;
+    SetVoxelArrays(output.get(), ok, oc, (size_t)m);
+    return output;
+}
+
+std::shared_ptr<VoxelGrid> VoxelGrid::CreateFromPointCloud(const PointCloud& input, float voxel_size) {
+    const Eigen::Vector3f half = Eigen::Vector3f(voxel_size, voxel_size, voxel_size) * 0.5f;
+    return CreateFromPointCloudWithinBounds(input, voxel_size, input.GetMinBound() - half, input.GetMaxBound() + half);
+}
+
+std::shared_ptr<VoxelGrid> VoxelGrid::CreateFromOccupancyGrid(const OccupancyGrid& input) {
+    auto output = std::make_shared<VoxelGrid>();
+    if (input.voxel_size_ <= 0.0f) {
+        LogError("[CreateFromOccupancyGrid] occupancy grid  voxel_size <= 0.");
+        return output;
+    }
+    output->voxel_size_ = input.voxel_size_;
+    output->origin_ = input.origin_;
+    const mi_icp_occgrid_params p = OccParams(input);
+    mi_icp_occgrid* g = input.Handle();
+    int64_t m = 0;
+    Check(mi_icp_occgrid_extract(Engine(), g, &p, MI_ICP_OCCGRID_OCCUPIED, nullptr, nullptr, nullptr, 0, &m));
+    if (m == 0) return output;
+    utility::device_vector<Eigen::Vector3i> ok((size_t)m);
+    utility::device_vector<Eigen::Vector3f> oc((size_t)m);
+    Check(mi_icp_occgrid_extract(Engine(), g, &p, MI_ICP_OCCGRID_OCCUPIED, KeyPtr(ok), nullptr, nullptr, m, &m));
+    const float blue[3] = {0.0f, 0.0f, 1.0f};
+    Check(mi_icp_voxelgrid_paint(Engine(), ColPtr(oc), m, nullptr, 0, blue));
+    SetVoxelArrays(output.get(), ok, oc, (size_t)m);
+    return output;
+}
+
 }  // namespace geometry
 
 // ---------------------------------------------------------------- integration

@@ -29,10 +29,12 @@
 #include <vector>
 
 #include "cupoch/camera/pinhole_camera_intrinsic.h"
+#include "cupoch/camera/pinhole_camera_parameters.h"
 #include "cupoch/geometry/image.h"
 #include "cupoch/geometry/keypoint.h"
 #include "cupoch/geometry/occupancygrid.h"
 #include "cupoch/geometry/pointcloud.h"
+#include "cupoch/geometry/voxelgrid.h"
 #include "cupoch/integration/uniform_tsdfvolume.h"
 #include "cupoch/knn/kdtree_flann.h"
 #include "cupoch/knn/kdtree_search_param.h"
@@ -93,6 +95,38 @@ py::list voxel_list(const std::vector<geometry::OccupancyVoxel>& v) {
     for (const geometry::OccupancyVoxel& x : v) out.append(py::cast(x));
     return out;
 }
+
+// geometry.DeviceVoxelMap: what VoxelGrid.voxels gives and takes -- the keys and the voxels on the device, with
+// __len__ and cpu() (grid_index (m, 3) int32, color (m, 3) float32); constructed from two such arrays
+struct DeviceVoxelMap {
+    utility::device_vector<Eigen::Vector3i> keys;
+    utility::device_vector<geometry::Voxel> values;
+    DeviceVoxelMap() = default;
+    DeviceVoxelMap(const py::array_t<int, py::array::c_style | py::array::forcecast>& k, const farray& c) {
+        if (k.ndim() != 2 || k.shape(1) != 3 || c.ndim() != 2 || c.shape(1) != 3 || c.shape(0) != k.shape(0))
+            throw std::invalid_argument("expected an (m, 3) int32 array and an (m, 3) float32 array");
+        const size_t m = (size_t)k.shape(0);
+        std::vector<Eigen::Vector3i> hk(m);
+        std::vector<geometry::Voxel> hv(m);
+        for (size_t i = 0; i < m; ++i) {
+            hk[i] = Eigen::Vector3i(k.at(i, 0), k.at(i, 1), k.at(i, 2));
+            hv[i] = geometry::Voxel(hk[i], Eigen::Vector3f(c.at(i, 0), c.at(i, 1), c.at(i, 2)));
+        }
+        keys = hk;
+        values = hv;
+    }
+    py::tuple cpu() const {
+        const std::vector<Eigen::Vector3i> hk = keys.to_host();
+        const std::vector<geometry::Voxel> hv = values.to_host();
+        py::array_t<int> k({(py::ssize_t)hk.size(), (py::ssize_t)3});
+        farray c({(py::ssize_t)hv.size(), (py::ssize_t)3});
+        for (size_t i = 0; i < hk.size(); ++i)
+            for (int d = 0; d < 3; ++d) k.mutable_at(i, d) = hk[i](d);
+        for (size_t i = 0; i < hv.size(); ++i)
+            for (int d = 0; d < 3; ++d) c.mutable_at(i, d) = hv[i].color_(d);
+        return py::make_tuple(k, c);
+    }
+};
 
 // utility.Vector3fVector: a device vector of Vector3f, constructed from an (n, 3) array (one H2D
 // copy), .cpu() copies back (device_vector_wrapper.cu:39-44,119-125)
@@ -593,7 +627,7 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             .def_readwrite("depth", &geometry::RGBDImage::depth_);
 
     // geometry.OccupancyVoxel / geometry.OccupancyGrid (cupoch_pybind/geometry/occupancygrid.cpp) with the reference's
-    // names, defaults and read-write attributes.  Not bound, as not built: create_from_voxel_grid (no VoxelGrid type).
+    // names, defaults and read-write attributes.  Not bound, as not built: create_from_voxel_grid.
     py::class_<geometry::OccupancyVoxel, std::shared_ptr<geometry::OccupancyVoxel>>(mg, "OccupancyVoxel")
             .def(py::init<>())
             .def(py::init([](const py::array_t<int, py::array::c_style | py::array::forcecast>& g) {
@@ -710,6 +744,159 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             .def("create_pyramid_level", &camera::PinholeCameraIntrinsic::CreatePyramidLevel, "level"_a)
             .def_readwrite("width", &camera::PinholeCameraIntrinsic::width_)
             .def_readwrite("height", &camera::PinholeCameraIntrinsic::height_);
+
+    py::class_<camera::PinholeCameraParameters>(mc, "PinholeCameraParameters")
+            .def(py::init<>())
+            .def_readwrite("intrinsic", &camera::PinholeCameraParameters::intrinsic_)
+            .def_property(
+                    "extrinsic", [](const camera::PinholeCameraParameters& p) { return from_matrix4(p.extrinsic_); },
+                    [](camera::PinholeCameraParameters& p, const farray& e) { p.extrinsic_ = to_matrix4(e); })
+            .def("__repr__", [](const camera::PinholeCameraParameters&) {
+                return std::string("camera::PinholeCameraParameters class.\nAccess its data via intrinsic and extrinsic.");
+            });
+
+    // geometry.Voxel / geometry.VoxelGrid (cupoch_pybind/geometry/voxelgrid.cpp) with the reference's names, argument
+    // names and defaults.  Not bound, as not built: create_from_triangle_mesh[_within_bounds],
+    // get_oriented_bounding_box.
+    using iarray = py::array_t<int, py::array::c_style | py::array::forcecast>;
+    py::class_<DeviceVoxelMap>(mg, "DeviceVoxelMap")
+            .def(py::init<>())
+            .def(py::init<const iarray&, const farray&>(), "grid_index"_a, "color"_a)
+            .def("__len__", [](const DeviceVoxelMap& v) { return v.keys.size(); })
+            .def("cpu", &DeviceVoxelMap::cpu);
+    py::class_<geometry::Voxel, std::shared_ptr<geometry::Voxel>>(mg, "Voxel")
+            .def(py::init<>())
+            .def(py::init([](const geometry::Voxel& v) { return std::make_shared<geometry::Voxel>(v); }))
+            .def("__repr__",
+                 [](const geometry::Voxel& voxel) {
+                     std::ostringstream repr;
+                     repr << "geometry::Voxel with grid_index: (" << voxel.grid_index_(0) << ", " << voxel.grid_index_(1) << ", "
+                          << voxel.grid_index_(2) << "), color: (" << voxel.color_(0) << ", " << voxel.color_(1) << ", "
+                          << voxel.color_(2) << ")";
+                     return repr.str();
+                 })
+            .def(py::init([](const iarray& g) { return std::make_shared<geometry::Voxel>(to_vector3i(g)); }), "grid_index"_a)
+            .def(py::init([](const iarray& g, const farray& c) { return std::make_shared<geometry::Voxel>(to_vector3i(g), to_vector3(c)); }),
+                 "grid_index"_a, "color"_a)
+            .def_property(
+                    "grid_index",
+                    [](const geometry::Voxel& v) {
+                        py::array_t<int> a(3);
+                        for (int k = 0; k < 3; ++k) a.mutable_at(k) = v.grid_index_(k);
+                        return a;
+                    },
+                    [](geometry::Voxel& v, const iarray& g) { v.grid_index_ = to_vector3i(g); })
+            .def_property(
+                    "color", [](const geometry::Voxel& v) { return from_vector3(v.color_); },
+                    [](geometry::Voxel& v, const farray& c) { v.color_ = to_vector3(c); });
+
+    py::class_<geometry::VoxelGrid, std::shared_ptr<geometry::VoxelGrid>>(mg, "VoxelGrid")
+            .def(py::init<>())
+            .def(py::init([](const geometry::VoxelGrid& g) { return std::make_shared<geometry::VoxelGrid>(g); }))
+            .def("__repr__",
+                 [](const geometry::VoxelGrid& g) {
+                     return std::string("geometry::VoxelGrid with ") + std::to_string(g.voxels_keys_.size()) + " voxels.";
+                 })
+            .def_property(
+                    "voxels",
+                    [](const geometry::VoxelGrid& g) {
+                        DeviceVoxelMap w;
+                        w.keys = g.voxels_keys_;
+                        w.values = g.voxels_values_;
+                        return w;
+                    },
+                    [](geometry::VoxelGrid& g, const DeviceVoxelMap& w) { g.SetVoxels(w.keys.to_host(), w.values.to_host()); })
+            .def("__add__", [](const geometry::VoxelGrid& a, const geometry::VoxelGrid& b) { return std::make_shared<geometry::VoxelGrid>(a + b); })
+            .def("__iadd__",
+                 [](std::shared_ptr<geometry::VoxelGrid> a, const geometry::VoxelGrid& b) {
+                     *a += b;
+                     return a;
+                 })
+            .def("has_colors", &geometry::VoxelGrid::HasColors)
+            .def("has_voxels", &geometry::VoxelGrid::HasVoxels)
+            .def("is_empty", &geometry::VoxelGrid::IsEmpty)
+            .def("clear", [](geometry::VoxelGrid& g) { g.Clear(); })
+            .def("get_voxel",
+                 [](const geometry::VoxelGrid& g, const farray& point) {
+                     const Eigen::Vector3i i = g.GetVoxel(to_vector3(point));
+                     py::array_t<int> a(3);
+                     for (int k = 0; k < 3; ++k) a.mutable_at(k) = i(k);
+                     return a;
+                 },
+                 "point"_a)
+            .def("get_voxel_center_coordinate",
+                 [](const geometry::VoxelGrid& g, const iarray& idx) { return from_vector3(g.GetVoxelCenterCoordinate(to_vector3i(idx))); }, "idx"_a)
+            .def("add_voxel", [](geometry::VoxelGrid& g, const geometry::Voxel& v) { g.AddVoxel(v); }, "voxel"_a)
+            .def("add_voxels", [](geometry::VoxelGrid& g, const std::vector<geometry::Voxel>& v) { g.AddVoxels(v); }, "voxels"_a)
+            .def("paint_uniform_color", [](std::shared_ptr<geometry::VoxelGrid> g, const farray& color) {
+                g->PaintUniformColor(to_vector3(color));
+                return g;
+            })
+            .def("paint_indexed_color", [](std::shared_ptr<geometry::VoxelGrid> g, const ULongVector& indices, const farray& color) {
+                g->PaintIndexedColor(indices.data, to_vector3(color));
+                return g;
+            })
+            .def("check_if_included",
+                 [](geometry::VoxelGrid& g, const farray& queries) {
+                     if (queries.ndim() != 2 || queries.shape(1) != 3) throw std::invalid_argument("expected an (n, 3) float32 array");
+                     std::vector<Eigen::Vector3f> q((size_t)queries.shape(0));
+                     if (!q.empty()) std::memcpy((void*)q.data(), queries.data(), q.size() * sizeof(Eigen::Vector3f));
+                     const std::vector<bool> r = g.CheckIfIncluded(q);
+                     py::list out;
+                     for (bool b : r) out.append(b);
+                     return out;
+                 },
+                 "queries"_a)
+            .def("carve_depth_map",
+                 [](std::shared_ptr<geometry::VoxelGrid> g, const geometry::Image& depth_map, const camera::PinholeCameraParameters& p,
+                    bool keep) {
+                     g->CarveDepthMap(depth_map, p, keep);
+                     return g;
+                 },
+                 "depth_map"_a, "camera_params"_a, "keep_voxels_outside_image"_a = false)
+            .def("carve_silhouette",
+                 [](std::shared_ptr<geometry::VoxelGrid> g, const geometry::Image& mask, const camera::PinholeCameraParameters& p, bool keep) {
+                     g->CarveSilhouette(mask, p, keep);
+                     return g;
+                 },
+                 "silhouette_mask"_a, "camera_params"_a, "keep_voxels_outside_image"_a = false)
+            .def("select_by_index",
+                 [](geometry::VoxelGrid& g, const ULongVector& indices, bool invert) { return g.SelectByIndex(indices.data, invert); },
+                 "indices"_a, "invert"_a = false)
+            .def("get_min_bound", [](const geometry::VoxelGrid& g) { return from_vector3(g.GetMinBound()); })
+            .def("get_max_bound", [](const geometry::VoxelGrid& g) { return from_vector3(g.GetMaxBound()); })
+            .def("get_center", [](const geometry::VoxelGrid& g) { return from_vector3(g.GetCenter()); })
+            .def("get_axis_aligned_bounding_box", &geometry::VoxelGrid::GetAxisAlignedBoundingBox)
+            .def("translate",
+                 [](std::shared_ptr<geometry::VoxelGrid> g, const farray& t, bool relative) {
+                     g->Translate(to_vector3(t), relative);
+                     return g;
+                 },
+                 "translation"_a, "relative"_a = true)
+            .def("scale",
+                 [](std::shared_ptr<geometry::VoxelGrid> g, float s, bool center) {
+                     g->Scale(s, center);
+                     return g;
+                 },
+                 "scale"_a, "center"_a = true)
+            .def_static(
+                    "create_dense",
+                    [](const farray& origin, float voxel_size, float width, float height, float depth) {
+                        return geometry::VoxelGrid::CreateDense(to_vector3(origin), voxel_size, width, height, depth);
+                    },
+                    "origin"_a, "voxel_size"_a, "width"_a, "height"_a, "depth"_a)
+            .def_static("create_from_point_cloud", &geometry::VoxelGrid::CreateFromPointCloud, "input"_a, "voxel_size"_a)
+            .def_static(
+                    "create_from_point_cloud_within_bounds",
+                    [](const geometry::PointCloud& input, float voxel_size, const farray& lo, const farray& hi) {
+                        return geometry::VoxelGrid::CreateFromPointCloudWithinBounds(input, voxel_size, to_vector3(lo), to_vector3(hi));
+                    },
+                    "input"_a, "voxel_size"_a, "min_bound"_a, "max_bound"_a)
+            .def_static("create_from_occupancy_grid", &geometry::VoxelGrid::CreateFromOccupancyGrid, "input"_a)
+            .def_property(
+                    "origin", [](const geometry::VoxelGrid& g) { return from_vector3(g.origin_); },
+                    [](geometry::VoxelGrid& g, const farray& v) { g.origin_ = to_vector3(v); })
+            .def_readwrite("voxel_size", &geometry::VoxelGrid::voxel_size_);
 
     // ---------------------------------------------------------------- integration
     // cupoch_pybind/integration/integration.cpp: TSDFVolumeColorType and UniformTSDFVolume with the reference's names.

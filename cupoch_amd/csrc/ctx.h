@@ -8,6 +8,7 @@
 //   mi_rgbd.hip      depth / RGB-D frame -> cloud, RGB-D odometry
 //   mi_tsdf.hip      UniformTSDFVolume
 //   mi_occgrid.hip   OccupancyGrid
+//   mi_voxelgrid.hip VoxelGrid (from points, dense, merge, carve, query, bounds, selections, paint)
 //   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry,
 //                    RemoveStatisticalOutliers / RemoveRadiusOutliers, ClusterDBSCAN, ComputeISSKeypoints
 //   mi_comm.hip      the ranks' exchange: mailbox, device inboxes, in-library RCCL, self-test and choice

@@ -96,7 +96,9 @@ static __global__ __launch_bounds__(256) void outlier_flags_radius(const int32_t
     flags[i] = count[i] >= need ? 1u : 0u;
 }
 
-__device__ __forceinline__ void copy3(const float* __restrict__ src, int64_t i, float* __restrict__ dst, int64_t p) {
+// (a 12-byte record moves the same whether it holds floats or ints: T is float for a cloud, int32_t for a VoxelGrid's keys)
+template <typename T>
+__device__ __forceinline__ void copy3(const T* __restrict__ src, int64_t i, T* __restrict__ dst, int64_t p) {
     dst[p * 3] = src[i * 3];
     dst[p * 3 + 1] = src[i * 3 + 1];
     dst[p * 3 + 2] = src[i * 3 + 2];
@@ -104,10 +106,11 @@ __device__ __forceinline__ void copy3(const float* __restrict__ src, int64_t i, 
 
 // Every flagged point i to position pos[i] (exclusive scan of the flags): its point, normal and colour (those given),
 // and i itself into out_idx when that is given.
+template <typename T>
 static __global__ __launch_bounds__(256) void select_gather(const uint32_t* __restrict__ flags,
                                                            const uint32_t* __restrict__ pos, int64_t n,
-                                                           const float* __restrict__ xyz, const float* __restrict__ nrm,
-                                                           const float* __restrict__ col, float* __restrict__ oxyz,
+                                                           const T* __restrict__ xyz, const float* __restrict__ nrm,
+                                                           const float* __restrict__ col, T* __restrict__ oxyz,
                                                            float* __restrict__ onrm, float* __restrict__ ocol,
                                                            int64_t* __restrict__ out_idx) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -121,9 +124,10 @@ static __global__ __launch_bounds__(256) void select_gather(const uint32_t* __re
 
 // SelectByIndex(indices): entry j of the output is point indices[j].  An index outside [0, n) sets *status and writes
 // nothing.
+template <typename T>
 static __global__ __launch_bounds__(256) void select_list(const int64_t* __restrict__ idx, int64_t n_idx, int64_t n,
-                                                         const float* __restrict__ xyz, const float* __restrict__ nrm,
-                                                         const float* __restrict__ col, float* __restrict__ oxyz,
+                                                         const T* __restrict__ xyz, const float* __restrict__ nrm,
+                                                         const float* __restrict__ col, T* __restrict__ oxyz,
                                                          float* __restrict__ onrm, float* __restrict__ ocol,
                                                          uint32_t* __restrict__ status) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;

@@ -839,6 +839,135 @@ class Engine:
         self._chk(self._L.mi_icp_occgrid_get_voxels(self._ctx, grid, tp))
         return t
 
+    # -- geometry::VoxelGrid (include/mi_icp.h; keys int32 [m, 3] and colours [m, 3] are device tensors) -----------
+    VOXELGRID_AVERAGE, VOXELGRID_KEEP_FIRST = 0, 1
+
+    def _vg_dev(self, a, dtype, cols=3):
+        """[n, cols] of dtype on this engine's GPU (None stays None): a tensor there is read in place"""
+        if a is None:
+            return None
+        tdt = {np.float32: torch.float32, np.int32: torch.int32, np.int64: torch.int64}[dtype]
+        dev = torch.device("cuda", self.device)
+        if _is_tensor(a):
+            t = a.to(device=dev, dtype=tdt)
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dtype))).to(dev)
+        return (t.reshape(-1, cols) if cols > 1 else t.reshape(-1)).contiguous()
+
+    @staticmethod
+    def _ptr(t):
+        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+
+    @staticmethod
+    def _f3(v):
+        return (C.c_float * 3)(*[float(x) for x in np.asarray(v, np.float32).reshape(3)])
+
+    def _vg_counted(self, first_capacity, call):
+        """the capacity rule: call(keys_ptr, colors_ptr, capacity, byref(m)) once for the count, again with room"""
+        dev = torch.device("cuda", self.device)
+        m = C.c_int64(0)
+        capacity = max(int(first_capacity), 1)
+        for _ in range(2):
+            (keys, kp), (cols, cp) = self._out(MI_ICP_DEVICE, dev, (capacity, 3), np.int32), self._out(MI_ICP_DEVICE, dev, (capacity, 3))
+            self._chk(call(kp, cp, capacity, C.byref(m)))
+            if int(m.value) <= capacity:
+                break
+            capacity = int(m.value)
+        self.synchronize()   # (uploaded inputs may go)
+        k = int(m.value)
+        return keys[:k], cols[:k]
+
+    def voxelgrid_from_points(self, points, voxel_size, min_bound, max_bound, colors=None):
+        """-> (keys [m, 3] int32 ascending, colors [m, 3]) (mi_icp_voxelgrid_from_points)"""
+        p, c = self._vg_dev(points, np.float32), self._vg_dev(colors, np.float32)
+        n = int(p.shape[0])
+        if c is not None and int(c.shape[0]) != n:
+            raise MiIcpError("voxelgrid_from_points: %d colours for %d points" % (int(c.shape[0]), n))
+        lo, hi = self._f3(min_bound), self._f3(max_bound)
+        return self._vg_counted(n, lambda kp, cp, cap, m: self._L.mi_icp_voxelgrid_from_points(
+            self._ctx, self._ptr(p), self._ptr(c), n, float(voxel_size), lo, hi, kp, cp, cap, m))
+
+    def voxelgrid_dense(self, num_w, num_h, num_d):
+        m = C.c_int64(0)
+        self._chk(self._L.mi_icp_voxelgrid_dense(self._ctx, int(num_w), int(num_h), int(num_d), None, None, 0, C.byref(m)))
+        return self._vg_counted(int(m.value), lambda kp, cp, cap, mm: self._L.mi_icp_voxelgrid_dense(
+            self._ctx, int(num_w), int(num_h), int(num_d), kp, cp, cap, mm))
+
+    def voxelgrid_merge(self, keys_a, colors_a, keys_b, colors_b, mode):
+        ka, ca = self._vg_dev(keys_a, np.int32), self._vg_dev(colors_a, np.float32)
+        kb, cb = self._vg_dev(keys_b, np.int32), self._vg_dev(colors_b, np.float32)
+        ma, mb = int(ka.shape[0]), int(kb.shape[0])
+        if int(ca.shape[0]) != ma or int(cb.shape[0]) != mb:
+            raise MiIcpError("voxelgrid_merge: keys and colours differ in length")
+        return self._vg_counted(ma + mb, lambda kp, cp, cap, m: self._L.mi_icp_voxelgrid_merge(
+            self._ctx, self._ptr(ka), self._ptr(ca), ma, self._ptr(kb), self._ptr(cb), mb, int(mode), kp, cp, cap, m))
+
+    def voxelgrid_carve(self, keys, colors, voxel_size, origin, image, intrinsic4, extrinsic=None,
+                        keep_voxels_outside_image=False):
+        """-> the (keys, colors) that stay, order kept (mi_icp_voxelgrid_carve); image: [H, W] or [H, W, C], any dtype"""
+        k, c = self._vg_dev(keys, np.int32), self._vg_dev(colors, np.float32)
+        m = int(k.shape[0])
+        dev = torch.device("cuda", self.device)
+        if _is_tensor(image):
+            img = image.to(dev).contiguous()
+        else:
+            a = np.ascontiguousarray(image)
+            if a.dtype == np.uint16:    # (torch has no arithmetic on uint16; the bytes are all that travel)
+                a = a.view(np.int16)
+            img = torch.from_numpy(a).to(dev)
+        height, width = int(img.shape[0]), int(img.shape[1])
+        channels = int(img.shape[2]) if img.dim() == 3 else 1
+        intr = (C.c_float * 4)(*[float(v) for v in intrinsic4])
+        E, Ep = _T_in(extrinsic)
+        (ok, okp), (oc, ocp) = self._out(MI_ICP_DEVICE, dev, (max(m, 1), 3), np.int32), self._out(MI_ICP_DEVICE, dev, (max(m, 1), 3))
+        mo = C.c_int64(0)
+        self._chk(self._L.mi_icp_voxelgrid_carve(self._ctx, self._ptr(k), self._ptr(c), m, float(voxel_size), self._f3(origin),
+                                                 self._ptr(img), width, height, channels, int(img.element_size()), intr, Ep,
+                                                 int(bool(keep_voxels_outside_image)), okp, ocp, C.byref(mo)))
+        return ok[:int(mo.value)], oc[:int(mo.value)]
+
+    def voxelgrid_query(self, keys, voxel_size, origin, queries, keys_sorted=False):
+        """-> (included [nq] uint8, index [nq, 3] int32), device tensors (mi_icp_voxelgrid_query)"""
+        k, q = self._vg_dev(keys, np.int32), self._vg_dev(queries, np.float32)
+        m, nq = int(k.shape[0]), int(q.shape[0])
+        dev = torch.device("cuda", self.device)
+        (inc, ip), (idx, xp) = self._out(MI_ICP_DEVICE, dev, (nq,), np.uint8), self._out(MI_ICP_DEVICE, dev, (nq, 3), np.int32)
+        self._chk(self._L.mi_icp_voxelgrid_query(self._ctx, self._ptr(k), m, int(bool(keys_sorted)), float(voxel_size),
+                                                 self._f3(origin), self._ptr(q), nq, ip, xp))
+        self.synchronize()   # (q may go)
+        return inc, idx
+
+    def voxelgrid_bounds(self, keys, voxel_size, origin):
+        """-> (min_index [3] int32, max_index [3] int32, centre_sum [3] float64), numpy; the grid must not be empty"""
+        k = self._vg_dev(keys, np.int32)
+        lo, hi, s = np.zeros(3, np.int32), np.zeros(3, np.int32), np.zeros(3, np.float64)
+        self._chk(self._L.mi_icp_voxelgrid_bounds(self._ctx, self._ptr(k), int(k.shape[0]), float(voxel_size), self._f3(origin),
+                                                  lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p),
+                                                  s.ctypes.data_as(C.c_void_p)))
+        return lo, hi, s
+
+    def voxelgrid_select_by_index(self, keys, colors, indices, invert=False):
+        k, c = self._vg_dev(keys, np.int32), self._vg_dev(colors, np.float32)
+        idx = self._vg_dev(indices, np.int64, 1)
+        m, ni = int(k.shape[0]), int(idx.shape[0])
+        rows = max(m if invert else ni, 1)
+        dev = torch.device("cuda", self.device)
+        (ok, okp), (oc, ocp) = self._out(MI_ICP_DEVICE, dev, (rows, 3), np.int32), self._out(MI_ICP_DEVICE, dev, (rows, 3))
+        mo = C.c_int64(0)
+        self._chk(self._L.mi_icp_voxelgrid_select_by_index(self._ctx, self._ptr(k), self._ptr(c), m, self._ptr(idx), ni,
+                                                           int(bool(invert)), okp, ocp, C.byref(mo)))
+        return ok[:int(mo.value)], oc[:int(mo.value)]
+
+    def voxelgrid_paint(self, colors, color, indices=None):
+        """paints the device tensor `colors` [m, 3] in place: every row, or the rows listed"""
+        idx = None if indices is None else self._vg_dev(indices, np.int64, 1)
+        ni = 0 if idx is None else int(idx.shape[0])
+        if idx is not None and ni == 0:
+            return
+        self._chk(self._L.mi_icp_voxelgrid_paint(self._ctx, self._ptr(colors), int(colors.shape[0]), self._ptr(idx), ni,
+                                                 self._f3(color)))
+        self.synchronize()   # (idx may go)
+
     def compute_rgbd_odometry(self, source_color, source_depth, target_color, target_depth, intrinsic4,
                               odo_init=None, jacobian=1, iterations=(20, 10, 5), max_depth_diff=0.03,
                               min_depth=0.0, max_depth=4.0, weighted=False, prev_twist=None, nu=5.0,

@@ -3,8 +3,10 @@ python surface src/python/cupoch_pybind/geometry/pointcloud.cpp:33-200) --
 only the members the ICP path touches.  Arrays live on the GPU as torch
 tensors; every operation below runs a HIP kernel through the C ABI.
 OccupancyGrid / OccupancyVoxel mirror geometry/occupancygrid.h:31-142 (python surface
-src/python/cupoch_pybind/geometry/occupancygrid.cpp); not built: create_from_voxel_grid and the VoxelGrid,
-DistanceTransform and collision consumers (no VoxelGrid type here)."""
+src/python/cupoch_pybind/geometry/occupancygrid.cpp); not built: OccupancyGrid.create_from_voxel_grid.
+Voxel / VoxelGrid mirror geometry/voxelgrid.h:48-214 (python surface src/python/cupoch_pybind/geometry/voxelgrid.cpp);
+not built: create_from_triangle_mesh[_within_bounds] (no TriangleMesh here), get_oriented_bounding_box, VoxelGrid file
+I/O, visualisation, DistanceTransform and collision."""
 import numpy as np
 
 from . import utility
@@ -730,6 +732,346 @@ def _create_from_occupancy_grid(occgrid):
 
 
 PointCloud.create_from_occupancy_grid = staticmethod(_create_from_occupancy_grid)
+
+
+class Voxel:
+    """geometry::Voxel (voxelgrid.h:48-62): grid index and colour.  Voxel(), Voxel(grid_index), Voxel(color=...),
+    Voxel(grid_index, color) are the reference's four constructors."""
+
+    def __init__(self, grid_index=(0, 0, 0), color=(1.0, 1.0, 1.0)):
+        self.grid_index = np.asarray(grid_index, np.int32).reshape(3).copy()
+        self.color = np.asarray(color, np.float32).reshape(3).copy()
+
+    def __repr__(self):
+        g, c = self.grid_index, self.color
+        return "geometry::Voxel with grid_index: (%d, %d, %d), color: (%g, %g, %g)" % (g[0], g[1], g[2], c[0], c[1], c[2])
+
+
+class DeviceVoxelMap:
+    """what VoxelGrid.voxels gives and takes: grid_index [m, 3] int32 and color [m, 3] float32, device tensors (numpy
+    arrays are uploaded when the map is assigned).  len(), [] (a Voxel) and cpu()."""
+
+    def __init__(self, grid_index=None, color=None):
+        self.grid_index = grid_index
+        self.color = color
+
+    def __len__(self):
+        return 0 if self.grid_index is None else int(self.grid_index.shape[0])
+
+    def __getitem__(self, i):
+        return Voxel(self.grid_index[i].cpu().numpy(), self.color[i].cpu().numpy())
+
+    def cpu(self):
+        """-> (grid_index, color) as numpy arrays"""
+        if self.grid_index is None:
+            return np.zeros((0, 3), np.int32), np.zeros((0, 3), np.float32)
+        to = lambda a: a.cpu().numpy() if (torch is not None and torch.is_tensor(a)) else np.asarray(a)
+        return to(self.grid_index).astype(np.int32).reshape(-1, 3), to(self.color).astype(np.float32).reshape(-1, 3)
+
+
+def _floor_index(v):
+    """floor(.) of fp32 values as int32, held inside +-1e9 first (the rule of include/mi_icp.h)"""
+    return np.clip(np.floor(v), np.float32(-1.0e9), np.float32(1.0e9)).astype(np.int32)
+
+
+def _index_list(indices):
+    """a ULongVector, a tensor or anything numpy takes -> what the engine uploads as int64"""
+    indices = getattr(indices, "tensor", indices)
+    return indices if (torch is not None and torch.is_tensor(indices)) else np.asarray(indices, np.int64)
+
+
+def _round_count(extent, voxel_size):
+    """int(std::round(extent / voxel_size)) in fp32: halves away from zero"""
+    q = float(np.float32(extent) / np.float32(voxel_size))
+    return int(np.floor(q + 0.5)) if q >= 0.0 else -int(np.floor(-q + 0.5))
+
+
+class VoxelGrid:
+    """geometry::VoxelGrid (voxelgrid.h:84-214): voxel_size, origin and the voxels as two device tensors, keys int32
+    [m, 3] and colours float32 [m, 3].  Every factory and +, += leave the keys distinct and ascending (x most significant).
+    Deviations from the reference: DESIGN.md section 6."""
+
+    def __init__(self, other=None, device=None):
+        self.voxel_size = 0.0
+        self.origin = np.zeros(3, np.float32)
+        self._keys = None
+        self._colors = None
+        self._sorted = True
+        self._device = device
+        if other is not None:   # the copy constructor
+            self.voxel_size = float(other.voxel_size)
+            self.origin = np.asarray(other.origin, np.float32).reshape(3).copy()
+            self._device = other._device
+            self._sorted = other._sorted
+            if other._keys is not None:
+                self._keys, self._colors = other._keys.clone(), other._colors.clone()
+
+    # ---- plumbing
+    def _eng(self):
+        return get_engine(self._device)
+
+    def _set(self, keys, colors, is_sorted):
+        self._keys, self._colors, self._sorted = keys, colors, bool(is_sorted)
+        return self
+
+    def _like(self, keys, colors, is_sorted):
+        out = VoxelGrid(device=self._device)
+        out.voxel_size, out.origin = float(self.voxel_size), np.asarray(self.origin, np.float32).reshape(3).copy()
+        return out._set(keys, colors, is_sorted)
+
+    def __len__(self):
+        return 0 if self._keys is None else int(self._keys.shape[0])
+
+    def _arrays(self):
+        """the keys and colours as device tensors (an empty grid: two [0, 3] tensors)"""
+        if self._keys is None:
+            e = self._eng()
+            return e._vg_dev(np.zeros((0, 3), np.int32), np.int32), e._vg_dev(np.zeros((0, 3), np.float32), np.float32)
+        return self._keys, self._colors
+
+    # ---- the voxels
+    @property
+    def voxels(self):
+        return DeviceVoxelMap(self._keys, self._colors)
+
+    @voxels.setter
+    def voxels(self, v):
+        """a DeviceVoxelMap, a (grid_index, color) pair of arrays, or a list of Voxel; taken as given, in any order"""
+        if isinstance(v, DeviceVoxelMap):
+            k, c = v.grid_index, v.color
+        elif isinstance(v, (list, tuple)) and len(v) > 0 and isinstance(v[0], Voxel):
+            k, c = np.stack([x.grid_index for x in v]), np.stack([x.color for x in v])
+        elif isinstance(v, (list, tuple)) and len(v) == 2:
+            k, c = v
+        else:
+            k, c = None, None
+        if k is None or len(k) == 0:
+            self._set(None, None, True)
+            return
+        e = self._eng()
+        k, c = e._vg_dev(k, np.int32), e._vg_dev(c, np.float32)
+        if int(k.shape[0]) != int(c.shape[0]):
+            raise ValueError("VoxelGrid.voxels: %d keys, %d colours" % (int(k.shape[0]), int(c.shape[0])))
+        self._set(k, c, False)
+
+    def get_voxels(self):
+        return self.voxels
+
+    def set_voxels(self, voxels_keys, voxels_values=None):
+        self.voxels = voxels_keys if voxels_values is None else (voxels_keys, voxels_values)
+
+    def clear(self):
+        self.voxel_size = 0.0
+        self.origin = np.zeros(3, np.float32)
+        self._set(None, None, True)
+        return self
+
+    def is_empty(self):
+        return len(self) == 0
+
+    def has_voxels(self):
+        return len(self) > 0
+
+    def has_colors(self):
+        return True   # (the reference: by default the colours are (1, 1, 1))
+
+    def __repr__(self):
+        return "geometry::VoxelGrid with %d voxels." % len(self)
+
+    # ---- GeometryBase3D
+    def _index_bounds(self):
+        return self._eng().voxelgrid_bounds(self._keys, self.voxel_size, self.origin)
+
+    def get_min_bound(self):
+        o = np.asarray(self.origin, np.float32).reshape(3)
+        if self.is_empty():
+            return o.copy()
+        lo, _, _ = self._index_bounds()
+        return (lo.astype(np.float32) * np.float32(self.voxel_size) + o).astype(np.float32)
+
+    def get_max_bound(self):
+        o = np.asarray(self.origin, np.float32).reshape(3)
+        if self.is_empty():
+            return o.copy()
+        _, hi, _ = self._index_bounds()
+        return ((hi.astype(np.float32) + np.float32(1.0)) * np.float32(self.voxel_size) + o).astype(np.float32)
+
+    def get_center(self):
+        if self.is_empty():
+            return np.zeros(3, np.float32)
+        _, _, s = self._index_bounds()
+        return (s / float(len(self))).astype(np.float32)
+
+    def get_axis_aligned_bounding_box(self):
+        return AxisAlignedBoundingBox(self.get_min_bound(), self.get_max_bound())
+
+    def translate(self, translation, relative=True):
+        self.origin = (np.asarray(self.origin, np.float32).reshape(3) + np.asarray(translation, np.float32).reshape(3)).astype(np.float32)
+        return self
+
+    def scale(self, scale, center=True):
+        self.voxel_size = float(np.float32(self.voxel_size) * np.float32(scale))
+        return self
+
+    def transform(self, transformation):
+        raise RuntimeError("VoxelGrid::Transform is not supported")
+
+    def rotate(self, R, center=True):
+        raise RuntimeError("VoxelGrid::Rotate is not supported")
+
+    # ---- merging
+    def _merge(self, keys, colors, mode):
+        ka, ca = self._arrays()
+        k, c = self._eng().voxelgrid_merge(ka, ca, keys, colors, mode)
+        return self._set(k, c, True) if int(k.shape[0]) else self._set(None, None, True)
+
+    def __iadd__(self, other):
+        if float(np.float32(self.voxel_size)) != float(np.float32(other.voxel_size)):
+            raise RuntimeError("[VoxelGrid] Could not combine VoxelGrid because voxel_size differs (this=%f, other=%f)"
+                               % (self.voxel_size, other.voxel_size))
+        a, b = np.asarray(self.origin, np.float32).reshape(3), np.asarray(other.origin, np.float32).reshape(3)
+        if not np.array_equal(a, b):
+            raise RuntimeError("[VoxelGrid] Could not combine VoxelGrid because origin differs (this=%f,%f,%f, other=%f,%f,%f)"
+                               % (a[0], a[1], a[2], b[0], b[1], b[2]))
+        kb, cb = other._arrays()
+        return self._merge(kb, cb, Engine.VOXELGRID_AVERAGE)
+
+    def __add__(self, other):
+        out = VoxelGrid(self)
+        out += other
+        return out
+
+    def add_voxel(self, voxel):
+        return self.add_voxels([voxel])
+
+    def add_voxels(self, voxels):
+        """a list of Voxel, a DeviceVoxelMap or a (grid_index, color) pair: an existing voxel stays as it is, and among
+        added voxels of one index the first listed stays"""
+        if isinstance(voxels, DeviceVoxelMap):
+            k, c = voxels.grid_index, voxels.color
+        elif isinstance(voxels, (list, tuple)) and len(voxels) > 0 and isinstance(voxels[0], Voxel):
+            k, c = np.stack([x.grid_index for x in voxels]), np.stack([x.color for x in voxels])
+        elif len(voxels) == 0:
+            return self
+        else:
+            k, c = voxels
+        e = self._eng()
+        return self._merge(e._vg_dev(k, np.int32), e._vg_dev(c, np.float32), Engine.VOXELGRID_KEEP_FIRST)
+
+    # ---- single voxels (host arithmetic in fp32, as the reference's host code)
+    def get_voxel(self, point):
+        p = np.asarray(point, np.float32).reshape(3)
+        with np.errstate(all="ignore"):
+            return _floor_index((p - np.asarray(self.origin, np.float32).reshape(3)) / np.float32(self.voxel_size))
+
+    def _has_index(self, idx):
+        """is the voxel `idx` in the grid?  (the query kernel on the unit grid: idx + 0.5 is exact below 2^22)"""
+        idx = np.asarray(idx, np.int32).reshape(3)
+        if self.is_empty():
+            return False
+        if np.abs(idx.astype(np.int64)).max() >= (1 << 22):
+            raise ValueError("VoxelGrid: a single-voxel lookup takes indices below 2^22")
+        q = (idx.astype(np.float32) + np.float32(0.5)).reshape(1, 3)
+        inc, _ = self._eng().voxelgrid_query(self._keys, 1.0, (0.0, 0.0, 0.0), q, keys_sorted=self._sorted)
+        return bool(int(inc[0]))
+
+    def get_voxel_center_coordinate(self, idx):
+        idx = np.asarray(idx, np.int32).reshape(3)
+        if not self._has_index(idx):
+            return np.zeros(3, np.float32)
+        return ((idx.astype(np.float32) + np.float32(0.5)) * np.float32(self.voxel_size)
+                + np.asarray(self.origin, np.float32).reshape(3)).astype(np.float32)
+
+    def get_voxel_bounding_points(self, index):
+        r = np.float32(np.float32(self.voxel_size) / np.float32(2.0))
+        x = self.get_voxel_center_coordinate(index)
+        signs = [(-1, -1, -1), (-1, -1, 1), (1, -1, -1), (1, -1, 1), (-1, 1, -1), (-1, 1, 1), (1, 1, -1), (1, 1, 1)]
+        return [(x + np.asarray(sg, np.float32) * r).astype(np.float32) for sg in signs]
+
+    # ---- batched operations
+    def check_if_included(self, queries):
+        """[nq, 3] points (numpy, a Vector3fVector or a tensor) -> numpy bool [nq]"""
+        q = queries.tensor if isinstance(queries, utility.Vector3fVector) else queries
+        k, _ = self._arrays()
+        inc, _ = self._eng().voxelgrid_query(k, self.voxel_size, self.origin, q, keys_sorted=self._sorted)
+        return inc.cpu().numpy().astype(bool)
+
+    def paint_uniform_color(self, color):
+        if not self.is_empty():
+            self._eng().voxelgrid_paint(self._colors, color)
+        return self
+
+    def paint_indexed_color(self, indices, color):
+        k, c = self._arrays()
+        self._eng().voxelgrid_paint(c, color, _index_list(indices))
+        return self
+
+    def select_by_index(self, indices, invert=False):
+        k, c = self._arrays()
+        ok, oc = self._eng().voxelgrid_select_by_index(k, c, _index_list(indices), invert)
+        return self._like(ok, oc, False) if int(ok.shape[0]) else self._like(None, None, True)
+
+    def _carve(self, image, camera_params, keep_voxels_outside_image, what):
+        img = _img(image)
+        intr = camera_params.intrinsic
+        if int(img.shape[0]) != int(intr.height) or int(img.shape[1]) != int(intr.width):
+            raise RuntimeError("[VoxelGrid] provided %s dimensions are not compatible with the provided camera_parameters" % what)
+        if self.is_empty():
+            return self
+        k, c = self._eng().voxelgrid_carve(self._keys, self._colors, self.voxel_size, self.origin, img, intr.as4(),
+                                           camera_params.extrinsic, keep_voxels_outside_image)
+        return self._set(k, c, self._sorted) if int(k.shape[0]) else self._set(None, None, True)
+
+    def carve_depth_map(self, depth_map, camera_params, keep_voxels_outside_image=False):
+        return self._carve(depth_map, camera_params, keep_voxels_outside_image, "depth_map")
+
+    def carve_silhouette(self, silhouette_mask, camera_params, keep_voxels_outside_image=False):
+        return self._carve(silhouette_mask, camera_params, keep_voxels_outside_image, "silhouette_mask")
+
+    # ---- factories
+    @staticmethod
+    def create_dense(origin, voxel_size, width, height, depth, device=None):
+        out = VoxelGrid(device=device)
+        out.origin = np.asarray(origin, np.float32).reshape(3).copy()
+        out.voxel_size = float(np.float32(voxel_size))
+        nw, nh, nd = (_round_count(x, voxel_size) for x in (width, height, depth))
+        k, c = out._eng().voxelgrid_dense(nw, nh, nd)
+        return out._set(k, c, True) if int(k.shape[0]) else out
+
+    @staticmethod
+    def create_from_point_cloud_within_bounds(input, voxel_size, min_bound, max_bound):
+        pts = input.points.tensor if input.has_points() else None
+        out = VoxelGrid(device=None if pts is None else pts.device.index)
+        lo = np.asarray(min_bound, np.float32).reshape(3)
+        out.voxel_size, out.origin = float(np.float32(voxel_size)), lo.copy()
+        if pts is None:
+            pts = np.zeros((0, 3), np.float32)
+        col = input.colors.tensor if input.has_colors() else None
+        k, c = out._eng().voxelgrid_from_points(pts, voxel_size, lo, max_bound, col)
+        return out._set(k, c, True) if int(k.shape[0]) else out
+
+    @staticmethod
+    def create_from_point_cloud(input, voxel_size):
+        half = np.float32(voxel_size) * np.float32(0.5)
+        lo = (np.asarray(input.get_min_bound(), np.float32) - half).astype(np.float32)
+        hi = (np.asarray(input.get_max_bound(), np.float32) + half).astype(np.float32)
+        return VoxelGrid.create_from_point_cloud_within_bounds(input, voxel_size, lo, hi)
+
+    @staticmethod
+    def create_from_occupancy_grid(input):
+        """the occupied voxels of an OccupancyGrid, their grid indices as keys (ascending), every colour (0, 0, 1)"""
+        if not (float(input.voxel_size) > 0.0):
+            raise RuntimeError("[CreateFromOccupancyGrid] occupancy grid  voxel_size <= 0.")
+        e, g, p = input._call()
+        out = VoxelGrid(device=e.device)
+        out.voxel_size, out.origin = float(np.float32(input.voxel_size)), np.asarray(input.origin, np.float32).reshape(3).copy()
+        idx, _, _ = e.occgrid_extract(g, p, OccupancyGrid.OCCUPIED)
+        if int(idx.shape[0]) == 0:
+            return out
+        idx = idx.contiguous()
+        col = torch.empty((int(idx.shape[0]), 3), dtype=torch.float32, device=idx.device)
+        e.voxelgrid_paint(col, (0.0, 0.0, 1.0))
+        return out._set(idx, col, True)
 
 
 def _v3(v):

@@ -25,9 +25,10 @@
  *     MI_ICP_ERR_INVALID before any buffer is read or written.  The caller owns all
  *     buffers it passes; the context owns its internal SoA copies, LBVH and
  *     scratch arena.
- *     THE ONE EXCEPTION is the mi_icp_occgrid_* family: its arrays (points, voxel
- *     indices, outputs) are HIP device pointers only and it has no memory-kind
- *     argument; its small fixed-size arguments (the parameter block, viewpoint3,
+ *     THE ONE EXCEPTION is the mi_icp_occgrid_* family and the mi_icp_voxelgrid_*
+ *     family beside it: their arrays (points, voxel
+ *     indices, outputs) are HIP device pointers only and they have no memory-kind
+ *     argument; their small fixed-size arguments (the parameter block, viewpoint3,
  *     corners, bounds, counts) are host pointers or values.
  *   - one context per GPU; a context is not thread-safe, independent contexts
  *     may be driven from different host threads.
@@ -654,8 +655,8 @@ MI_ICP_API int mi_icp_gaussian_filter(mi_icp_ctx* ctx, const float* xyz, const f
  * (tsdf, weight, colour[3]), indexed x*res*res + y*res + z.  It belongs to the context that made it:
  * mi_icp_destroy frees the volumes still alive, and a volume is only accepted by its own context.
  * Stored as planes (tsdf, weight, and three colour planes only when color_type != NO_COLOR): 8 or 20
- * bytes per voxel.  Not built: ExtractTriangleMesh, ExtractVoxelGrid (there is no TriangleMesh or
- * VoxelGrid type here), ScalableTSDFVolume, IntegrateWithDepthToCameraDistanceMultiplier as an entry.
+ * bytes per voxel.  Not built: ExtractTriangleMesh (there is no TriangleMesh type here), ExtractVoxelGrid,
+ * ScalableTSDFVolume, IntegrateWithDepthToCameraDistanceMultiplier as an entry.
  *
  * THE NUMERIC CONTRACT.  Everything is fp32, products and sums unfused, division and square root
  * correctly rounded, in the order written; three-term sums and dot products run left to right,
@@ -791,8 +792,8 @@ MI_ICP_API int mi_icp_tsdf_get_voxels(mi_icp_ctx* ctx, mi_icp_tsdf* volume, floa
  * context that made it: destroyed with mi_icp_occgrid_destroy, or with the context.  Stored as the
  * log-odds plane alone, 4 bytes per voxel (the reference keeps 24: a grid index that is the voxel's
  * position and a colour it never writes, always (0, 0, 1)), beside a one-byte mark per voxel that is
- * zero between calls.  Not built: CreateFromVoxelGrid and the VoxelGrid, DistanceTransform and collision
- * consumers (no VoxelGrid type here).
+ * zero between calls.  Not built: CreateFromVoxelGrid, and the DistanceTransform and collision consumers.
+ * The occupied space leaves the library as a geometry::VoxelGrid (VoxelGrid::CreateFromOccupancyGrid, below).
  *
  * ARRAYS ARE DEVICE POINTERS; there is no memory-kind argument in this family (the preamble's one
  * exception).  `params`, viewpoint3, min3 / max3 and the counts are host memory.  voxel_size, origin and
@@ -885,6 +886,100 @@ MI_ICP_API int mi_icp_occgrid_extract(mi_icp_ctx* ctx, mi_icp_occgrid* grid, con
                                       int64_t capacity, int64_t* m);
 MI_ICP_API int mi_icp_occgrid_get_bounds(mi_icp_ctx* ctx, mi_icp_occgrid* grid, int32_t* min3, int32_t* max3);
 MI_ICP_API int mi_icp_occgrid_get_voxels(mi_icp_ctx* ctx, mi_icp_occgrid* grid, float* out_prob_log);
+
+/* ---- geometry::VoxelGrid (geometry/voxelgrid.{h,cu}, voxelgrid_factory.cu) --------------------------
+ * A sparse voxel set: keys int32[m][3] (grid indices) + colors float[m][3], with voxel_size and origin[3].
+ * There is no handle: a grid is those two device arrays and the two host values, and nothing is kept
+ * between calls.  Every producer below emits keys DISTINCT and ASCENDING lexicographically, x most
+ * significant (the reference's operator< on Vector3i, utility/helper.h:114).  Not built:
+ * CreateFromTriangleMesh[WithinBounds] (no TriangleMesh here), GetOrientedBoundingBox, file I/O,
+ * visualisation, DistanceTransform, collision; OccupancyGrid::CreateFromVoxelGrid and
+ * UniformTSDFVolume::ExtractVoxelGrid.
+ *
+ * ARRAYS ARE DEVICE POINTERS; there is no memory-kind argument in this family (the preamble's
+ * exception).  voxel_size, bounds, origin, camera matrices, counts and the three bounds outputs are host
+ * memory.  THE CAPACITY RULE of every extraction here: *m is the count; with capacity < *m nothing is
+ * written.  A refusal is MI_ICP_ERR_INVALID with nothing changed.
+ *
+ * NUMERIC CONTRACT.  fp32 in exactly the order written unless a step says double; products are never
+ * fused.  floor(.) to int holds the value inside +-1e9 first.  A key whose x is INT32_MIN is no key: the
+ * sorting entries (merge, an unsorted query) leave such an entry out.
+ *  from_points(xyz, colors | NULL, n, voxel_size, min_bound, max_bound)  CreateFromPointCloudWithinBounds.
+ *   key = floor((p - min_bound) / voxel_size) per axis.  A point with a coordinate that is not finite is
+ *   skipped (the reference is undefined there).  Keys may be negative.  Without colours every voxel is
+ *   (1, 1, 1); with colours a voxel's colour is the mean of its points' colours, summed IN DOUBLE and
+ *   divided by the count in double, rounded once -- the rule of mi_icp_voxel_downsample.  Runs of up to
+ *   32 points are added in input order (the sort is stable); a longer run is added 64 wide: partial sum
+ *   l takes elements l, l + 64, ... in order and the 64 are added in a fixed order.  Either way the same
+ *   input gives the same bits on every call, and the result is within one fp32 ulp of the input-order
+ *   mean.  (The reference adds in fp32 in thrust's order.)  Refused: voxel_size <= 0 or not finite;
+ *   voxel_size * INT_MAX < max(max_bound - min_bound) (both as the reference logs an error); a bound that
+ *   is not finite.  n == 0: an empty grid.  No span of keys is refused: key - min is packed into exactly
+ *   the bits the three extents need and sorted as one 32-bit or one 64-bit key; extents that need more
+ *   than 64 bits together (two clusters 3e6 voxels apart on every axis already do: 3 x 22 bits) take two
+ *   stable sorts, (y, z) then x.
+ *  dense(num_w, num_h, num_d)  CreateDense's keys: idx -> (idx / (h*d), (idx % (h*d)) / d, idx % d),
+ *   colour (1, 1, 1); already ascending.  A count <= 0: empty.  More than 2^31 - 1 voxels: refused (the
+ *   reference overflows an int).  The host makes num_* = (int)round(extent / voxel_size).
+ *  merge(A, B, mode)  A's entries then B's, stable-sorted by key, one entry per key.
+ *   MI_ICP_VOXELGRID_AVERAGE (operator+=): the fp32 sum of the run's colours, left to right in that
+ *   order, divided by the run length in fp32.  MI_ICP_VOXELGRID_KEEP_FIRST (AddVoxel / AddVoxels): the
+ *   run's first entry -- an existing voxel over an added one, the first listed among added duplicates
+ *   (the reference's sort_by_key + unique_by_key does not promise which).
+ *  carve(image, intrinsic4 = fx fy cx cy, extrinsic16 column-major | NULL)  CarveDepthMap and
+ *   CarveSilhouette (they differ in their error text only).  Per voxel: c = ((float)key + 0.5f) * vs +
+ *   origin; r = vs / 2; corners c + (-+r, -+r, -+r) in the order of GetVoxelBoundingPoints; per corner
+ *   X = ((R row . p), summed left to right) + t; uvz = K X with the full 3x3 K, zeros included, each row
+ *   summed left to right; z = uvz.z, u = uvz.x / z, v = uvz.y / z.  within = image is 1 channel x 4
+ *   bytes && 0 <= u <= width - 1 && 0 <= v <= height - 1 (a NaN u or v is not within; the reference
+ *   converts it to int, which is undefined).  d = FloatValueAt (geometry/image.h:240-264): ui =
+ *   clamp((int)u, 0, width - 2), vi likewise, pu = u - ui, pv = v - vi, d = (v00*(1-pv) + v01*pv)*(1-pu)
+ *   + (v10*(1-pv) + v11*pv)*pu with v01 the pixel BELOW v00.  The voxel stays iff some corner has
+ *   (!within && keep_voxels_outside_image) || (within && d > 0 && z >= d).  Output: the voxels that stay,
+ *   in their order; out arrays of m entries.  Refused: width or height < 2.
+ *  query(keys, m, keys_sorted, queries, nq)  CheckIfIncluded: the voxel of a query is floor((q - origin) /
+ *   vs); out_included[i] = 1 iff that key is in the grid -- a binary search per query; with keys_sorted
+ *   == 0 the entry sorts a scratch copy once first.  A query that is not finite is not included and has
+ *   index (0, 0, 0).  out_index (optional) int32[nq][3].
+ *  bounds(keys, m > 0)  per-axis min and max index and, per axis, the DOUBLE sum of the voxel centres
+ *   ((float)key * vs + origin) + 0.5f * vs (each in fp32), in a fixed order.  The host applies
+ *   GetMinBound = min * vs + origin, GetMaxBound = (max + 1) * vs + origin, GetCenter = sum / m rounded
+ *   once (the reference sums in fp32); an empty grid gives origin / origin / zero without a call.
+ *  select_by_index: the rules of mi_icp_select_by_index (an index out of range is an error; invert
+ *   treats a repeated index once), on keys + colours.  paint: indices == NULL paints every voxel
+ *   (PaintUniformColor), else the listed ones (PaintIndexedColor; an index out of range is an error and
+ *   nothing is painted).
+ * Limits: counts up to 0x7fffff00; voxel_size positive and finite and origin finite wherever they are
+ * used (bounds takes any finite voxel_size).
+ * Waits: from_points and merge wait twice (the key extents that size the sort, the count); carve,
+ * bounds, select_by_index and an indexed paint once; an unsorted query twice; dense, a sorted query and a
+ * uniform paint only enqueue. */
+#define MI_ICP_VOXELGRID_AVERAGE 0
+#define MI_ICP_VOXELGRID_KEEP_FIRST 1
+MI_ICP_API int mi_icp_voxelgrid_from_points(mi_icp_ctx* ctx, const float* xyz, const float* colors, int64_t n,
+                                            float voxel_size, const float* min_bound3, const float* max_bound3,
+                                            int32_t* out_keys, float* out_colors, int64_t capacity, int64_t* m);
+MI_ICP_API int mi_icp_voxelgrid_dense(mi_icp_ctx* ctx, int num_w, int num_h, int num_d, int32_t* out_keys,
+                                      float* out_colors, int64_t capacity, int64_t* m);
+MI_ICP_API int mi_icp_voxelgrid_merge(mi_icp_ctx* ctx, const int32_t* keys_a, const float* colors_a, int64_t m_a,
+                                      const int32_t* keys_b, const float* colors_b, int64_t m_b, int mode,
+                                      int32_t* out_keys, float* out_colors, int64_t capacity, int64_t* m);
+MI_ICP_API int mi_icp_voxelgrid_carve(mi_icp_ctx* ctx, const int32_t* keys, const float* colors, int64_t m,
+                                      float voxel_size, const float* origin3, const void* image, int width, int height,
+                                      int channels, int bytes_per_channel, const float* intrinsic4,
+                                      const float* extrinsic16, int keep_voxels_outside_image, int32_t* out_keys,
+                                      float* out_colors, int64_t* m_out);
+MI_ICP_API int mi_icp_voxelgrid_query(mi_icp_ctx* ctx, const int32_t* keys, int64_t m, int keys_sorted,
+                                      float voxel_size, const float* origin3, const float* queries, int64_t nq,
+                                      uint8_t* out_included, int32_t* out_index);
+MI_ICP_API int mi_icp_voxelgrid_bounds(mi_icp_ctx* ctx, const int32_t* keys, int64_t m, float voxel_size,
+                                       const float* origin3, int32_t* out_min_index3, int32_t* out_max_index3,
+                                       double* out_center_sum3);
+MI_ICP_API int mi_icp_voxelgrid_select_by_index(mi_icp_ctx* ctx, const int32_t* keys, const float* colors, int64_t m,
+                                                const int64_t* indices, int64_t n_indices, int invert,
+                                                int32_t* out_keys, float* out_colors, int64_t* m_out);
+MI_ICP_API int mi_icp_voxelgrid_paint(mi_icp_ctx* ctx, float* colors, int64_t m, const int64_t* indices,
+                                      int64_t n_indices, const float* color3);
 
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
