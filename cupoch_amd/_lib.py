@@ -18,7 +18,7 @@ INCLUDE = os.path.join(ROOT, "include")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I/opt/rocm/include"]
 # the library's translation units (csrc/ctx.h says what each holds); compiled side by side, then linked
-UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_occgrid", "mi_voxelgrid", "mi_knn", "mi_comm", "mi_debug"]
+UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_occgrid", "mi_voxelgrid", "mi_edt", "mi_knn", "mi_comm", "mi_debug"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 MI_ICP_HOST, MI_ICP_DEVICE = 0, 1
@@ -26,8 +26,11 @@ EST_POINT_TO_POINT, EST_POINT_TO_PLANE, EST_SYMMETRIC, EST_GENERALIZED = 1, 2, 3
 EST_COLORED = 4
 
 
+MI_ICP_ERR_INVALID, MI_ICP_ERR_STATE, MI_ICP_ERR_HIP, MI_ICP_ERR_COMM, MI_ICP_ERR_NO_DEVICE = -1, -2, -3, -4, -5
+
+
 class MiIcpError(RuntimeError):
-    pass
+    code = None     # the C ABI's status where the error came from a call (engine.Engine._chk)
 
 
 def _sources():
@@ -198,6 +201,14 @@ SIGNATURES = {
     "mi_icp_occgrid_extract": (_I, [_P, _P, C.POINTER(OccGridParams), _I, _P, _P, _P, _L, C.POINTER(_L)]),
     "mi_icp_occgrid_get_bounds": (_I, [_P, _P, _P, _P]),
     "mi_icp_occgrid_get_voxels": (_I, [_P, _P, _P]),
+    "mi_icp_dt_create": (_I, [_P, _I, C.POINTER(_P)]),
+    "mi_icp_dt_destroy": (_I, [_P, _P]),
+    "mi_icp_dt_reconstruct": (_I, [_P, _P, _I]),
+    "mi_icp_dt_compute_cells": (_I, [_P, _P, _P, _L, C.POINTER(_L)]),
+    "mi_icp_dt_compute_voxelgrid": (_I, [_P, _P, _F, _P, _P, _L, _F, _P, C.POINTER(_L)]),
+    "mi_icp_dt_compute_occgrid": (_I, [_P, _P, _P, _F]),
+    "mi_icp_dt_query": (_I, [_P, _P, _F, _P, _P, _L, _P, _P]),
+    "mi_icp_dt_get_voxels": (_I, [_P, _P, _F, _P, _P]),
     "mi_icp_voxelgrid_from_points": (_I, [_P, _P, _P, _L, _F, _P, _P, _P, _P, _L, C.POINTER(_L)]),
     "mi_icp_voxelgrid_dense": (_I, [_P, _I, _I, _I, _P, _P, _L, C.POINTER(_L)]),
     "mi_icp_voxelgrid_merge": (_I, [_P, _P, _P, _L, _P, _P, _L, _I, _P, _P, _L, C.POINTER(_L)]),

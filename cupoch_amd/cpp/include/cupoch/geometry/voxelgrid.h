@@ -5,7 +5,7 @@
 // Every factory, operator+= and AddVoxel[s] leave the keys distinct and ascending (x most significant).  LogError logs
 // and returns, as in the reference.  Deviations from the reference: DESIGN.md section 6.
 // Not built: CreateFromTriangleMesh[WithinBounds] (no TriangleMesh here), GetOrientedBoundingBox, VoxelGrid file I/O,
-// visualisation, DistanceTransform, collision.
+// visualisation, collision.  (The distance field of a grid: geometry/distancetransform.h.)
 #pragma once
 #include <array>
 #include <memory>

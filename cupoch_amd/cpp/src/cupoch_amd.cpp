@@ -8,6 +8,8 @@
 #include <typeinfo>
 #include <hip/hip_runtime_api.h>
 
+#include <cfloat>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
@@ -1534,6 +1536,160 @@ std::shared_ptr<VoxelGrid> VoxelGrid::CreateFromOccupancyGrid(const OccupancyGri
     const float blue[3] = {0.0f, 0.0f, 1.0f};
     Check(mi_icp_voxelgrid_paint(Engine(), ColPtr(oc), m, nullptr, 0, blue));
     SetVoxelArrays(output.get(), ok, oc, (size_t)m);
+    return output;
+}
+
+// ---- geometry::DistanceTransform (distancetransform.cu, distancetransform_factory.cu, densegrid.inl) over mi_icp_dt_*
+namespace {
+DistanceVoxel MakeDistanceVoxel(const Eigen::Vector3i& nearest, float distance) {
+    DistanceVoxel v;
+    v.nearest_index_ = Eigen::Vector3ui16((unsigned short)nearest[0], (unsigned short)nearest[1], (unsigned short)nearest[2]);
+    v.state_ = nearest[0] < 0 ? (unsigned char)DistanceVoxel::NotSite : (unsigned char)0;
+    v.distance_ = distance;
+    return v;
+}
+}  // namespace
+
+DistanceTransform::DistanceTransform() : DistanceTransform(0.05f, 512, Eigen::Vector3f::Zero()) {}
+
+DistanceTransform::DistanceTransform(float voxel_size, size_t resolution, const Eigen::Vector3f& origin)
+    : GeometryBase3D(GeometryType::DistanceTransform), voxel_size_(voxel_size), resolution_((int)resolution), origin_(origin) {}
+
+DistanceTransform::~DistanceTransform() {
+    if (dt_) (void)mi_icp_dt_destroy(Engine(), dt_);
+}
+
+mi_icp_dt* DistanceTransform::Handle() const {
+    if (!dt_) {
+        Check(mi_icp_dt_create(Engine(), resolution_, &dt_));
+        made_resolution_ = resolution_;
+    } else if (made_resolution_ != resolution_) {
+        const int rc = mi_icp_dt_reconstruct(Engine(), dt_, resolution_);
+        if (rc == MI_ICP_ERR_HIP) dt_ = nullptr;  // (the planes could not be made: the handle is gone)
+        Check(rc);
+        made_resolution_ = resolution_;
+    }
+    return dt_;
+}
+
+DistanceTransform& DistanceTransform::Clear() {
+    if (dt_ && made_resolution_ == resolution_) Check(mi_icp_dt_compute_cells(Engine(), dt_, nullptr, 0, nullptr));
+    return *this;
+}
+
+Eigen::Vector3f DistanceTransform::GetMinBound() const {
+    const float len = voxel_size_ * (float)resolution_ * 0.5f;
+    return origin_ - Eigen::Vector3f(len, len, len);
+}
+
+Eigen::Vector3f DistanceTransform::GetMaxBound() const {
+    const float len = voxel_size_ * (float)resolution_ * 0.5f;
+    return origin_ + Eigen::Vector3f(len, len, len);
+}
+
+AxisAlignedBoundingBox3 DistanceTransform::GetAxisAlignedBoundingBox() const {
+    return AxisAlignedBoundingBox3(GetMinBound(), GetMaxBound());
+}
+
+DistanceTransform& DistanceTransform::Transform(const Eigen::Matrix4f&) {
+    LogError("DenseGrid::Transform is not supported");
+    return *this;
+}
+
+DistanceTransform& DistanceTransform::Rotate(const Eigen::Matrix3f&, bool) {
+    LogError("DenseGrid::Rotate is not supported");
+    return *this;
+}
+
+DistanceTransform& DistanceTransform::Translate(const Eigen::Vector3f& translation, bool relative) {
+    origin_ = relative ? origin_ + translation : translation;
+    return *this;
+}
+
+DistanceTransform& DistanceTransform::Scale(const float scale, bool) {
+    voxel_size_ *= scale;
+    return *this;
+}
+
+DistanceTransform& DistanceTransform::Reconstruct(float voxel_size, size_t resolution) {
+    voxel_size_ = voxel_size;
+    resolution_ = (int)resolution;
+    if (dt_) {
+        made_resolution_ = 0;  // (also for the same resolution: no sites again)
+        (void)Handle();
+    }
+    return *this;
+}
+
+DistanceTransform& DistanceTransform::ComputeEDT(const utility::device_vector<Eigen::Vector3i>& points) {
+    Check(mi_icp_dt_compute_cells(Engine(), Handle(), points.empty() ? nullptr : points.data()->data(), (int64_t)points.size(),
+                                  nullptr));
+    Check(mi_icp_synchronize(Engine()));
+    return *this;
+}
+
+DistanceTransform& DistanceTransform::ComputeEDT(const VoxelGrid& voxelgrid) {
+    if (std::abs(voxel_size_ - voxelgrid.voxel_size_) > FLT_EPSILON) {  // distancetransform.cu:332-337
+        LogError("Unsupport computing Voronoi diagrams from different voxel size.");
+        return *this;
+    }
+    const auto& keys = voxelgrid.voxels_keys_;
+    Check(mi_icp_dt_compute_voxelgrid(Engine(), Handle(), voxel_size_, origin_.data(), keys.empty() ? nullptr : keys.data()->data(),
+                                      (int64_t)keys.size(), voxelgrid.voxel_size_, voxelgrid.origin_.data(), nullptr));
+    Check(mi_icp_synchronize(Engine()));
+    return *this;
+}
+
+DistanceTransform& DistanceTransform::ComputeVoronoiDiagram(const utility::device_vector<Eigen::Vector3i>& points) {
+    return ComputeEDT(points);
+}
+
+DistanceTransform& DistanceTransform::ComputeVoronoiDiagram(const VoxelGrid& voxelgrid) { return ComputeEDT(voxelgrid); }
+
+std::unique_ptr<utility::device_vector<float>> DistanceTransform::GetDistances(
+        const utility::device_vector<Eigen::Vector3f>& queries) const {
+    auto out = std::make_unique<utility::device_vector<float>>(queries.size());
+    if (queries.empty()) return out;
+    Check(mi_icp_dt_query(Engine(), Handle(), voxel_size_, origin_.data(), Ptr(queries), (int64_t)queries.size(), out->data(),
+                          nullptr));
+    Check(mi_icp_synchronize(Engine()));
+    return out;
+}
+
+std::tuple<bool, DistanceVoxel> DistanceTransform::GetVoxel(const Eigen::Vector3f& point) const {
+    utility::device_vector<Eigen::Vector3f> pt(std::vector<Eigen::Vector3f>{point});
+    utility::device_vector<float> dist(1);
+    utility::device_vector<Eigen::Vector3i> idx(1);
+    Check(mi_icp_dt_query(Engine(), Handle(), voxel_size_, origin_.data(), Ptr(pt), 1, dist.data(), idx.data()->data()));
+    Check(mi_icp_synchronize(Engine()));
+    const float d = dist.to_host()[0];
+    if (std::isnan(d)) return std::make_tuple(false, DistanceVoxel());
+    return std::make_tuple(true, MakeDistanceVoxel(idx.to_host()[0], d));
+}
+
+float DistanceTransform::GetDistance(const Eigen::Vector3f& query) const {
+    const auto r = GetVoxel(query);
+    return std::get<0>(r) ? std::get<1>(r).distance_ : std::numeric_limits<float>::quiet_NaN();
+}
+
+std::vector<DistanceVoxel> DistanceTransform::GetVoxels() const {
+    const size_t n = (size_t)resolution_ * (size_t)resolution_ * (size_t)resolution_;
+    mi_icp_dt* h = Handle();
+    utility::device_vector<Eigen::Vector3i> idx(n);
+    utility::device_vector<float> dist(n);
+    Check(mi_icp_dt_get_voxels(Engine(), h, voxel_size_, idx.data()->data(), dist.data()));
+    const std::vector<Eigen::Vector3i> hi = idx.to_host();
+    const std::vector<float> hd = dist.to_host();
+    std::vector<DistanceVoxel> out;
+    out.reserve(n);
+    for (size_t i = 0; i < n; ++i) out.push_back(MakeDistanceVoxel(hi[i], hd[i]));
+    return out;
+}
+
+std::shared_ptr<DistanceTransform> DistanceTransform::CreateFromOccupancyGrid(const OccupancyGrid& input) {
+    if (input.voxel_size_ <= 0.0f) LogError("[CreateOccupancyGrid] occupancy grid  voxel_size <= 0.");  // distancetransform_factory.cu:42-45
+    auto output = std::make_shared<DistanceTransform>(input.voxel_size_, (size_t)input.resolution_, input.origin_);
+    Check(mi_icp_dt_compute_occgrid(Engine(), output->Handle(), input.Handle(), input.occ_prob_thres_log_));
     return output;
 }
 

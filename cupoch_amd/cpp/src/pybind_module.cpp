@@ -30,6 +30,7 @@
 
 #include "cupoch/camera/pinhole_camera_intrinsic.h"
 #include "cupoch/camera/pinhole_camera_parameters.h"
+#include "cupoch/geometry/distancetransform.h"
 #include "cupoch/geometry/image.h"
 #include "cupoch/geometry/keypoint.h"
 #include "cupoch/geometry/occupancygrid.h"
@@ -897,6 +898,87 @@ PYBIND11_MODULE(cupoch_pybind, m) {
                     "origin", [](const geometry::VoxelGrid& g) { return from_vector3(g.origin_); },
                     [](geometry::VoxelGrid& g, const farray& v) { g.origin_ = to_vector3(v); })
             .def_readwrite("voxel_size", &geometry::VoxelGrid::voxel_size_);
+
+    // geometry.DistanceVoxel / geometry.DistanceTransform (cupoch_pybind/geometry/distancetransform.cpp) with the
+    // reference's names and defaults, and beside them compute_voronoi_diagram, get_voxel, get_voxels and the DenseGrid
+    // members.  get_distances takes a Vector3fVector or an (n, 3) array and returns a numpy array.
+    py::class_<geometry::DistanceVoxel, std::shared_ptr<geometry::DistanceVoxel>>(mg, "DistanceVoxel")
+            .def(py::init<>())
+            .def("__repr__",
+                 [](const geometry::DistanceVoxel& v) {
+                     std::ostringstream repr;
+                     repr << "geometry::DistanceVoxel with nearest_index: (" << v.nearest_index_(0) << ", " << v.nearest_index_(1)
+                          << ", " << v.nearest_index_(2) << "), distance: " << v.distance_ << ")";
+                     return repr.str();
+                 })
+            .def_property(
+                    "nearest_index",
+                    [](const geometry::DistanceVoxel& v) {
+                        py::array_t<int> a(3);
+                        for (int k = 0; k < 3; ++k) a.mutable_at(k) = (int)v.nearest_index_(k);
+                        return a;
+                    },
+                    [](geometry::DistanceVoxel& v, const iarray& g) {
+                        const Eigen::Vector3i i = to_vector3i(g);
+                        for (int k = 0; k < 3; ++k) v.nearest_index_(k) = (unsigned short)i(k);
+                    })
+            .def_readwrite("distance", &geometry::DistanceVoxel::distance_)
+            .def("is_not_site", &geometry::DistanceVoxel::IsNotSite);
+
+    py::class_<geometry::DistanceTransform, std::shared_ptr<geometry::DistanceTransform>>(mg, "DistanceTransform")
+            .def(py::init<>())
+            .def(py::init([](float voxel_size, int resolution, const farray& origin) {
+                     return std::make_shared<geometry::DistanceTransform>(voxel_size, (size_t)resolution, to_vector3(origin));
+                 }),
+                 "voxel_size"_a, "resolution"_a, "origin"_a = from_vector3(Eigen::Vector3f::Zero()))
+            .def("__repr__",
+                 [](const geometry::DistanceTransform& d) {
+                     return std::string("geometry::DistanceTransform with ") + std::to_string(d.resolution_) + " resolution.";
+                 })
+            .def("reconstruct",
+                 [](geometry::DistanceTransform& d, float voxel_size, int resolution) { d.Reconstruct(voxel_size, (size_t)resolution); },
+                 "voxel_size"_a, "resolution"_a)
+            .def("compute_edt", [](geometry::DistanceTransform& d, const geometry::VoxelGrid& g) { d.ComputeEDT(g); }, "voxelgrid"_a)
+            .def("compute_voronoi_diagram", [](geometry::DistanceTransform& d, const geometry::VoxelGrid& g) { d.ComputeVoronoiDiagram(g); },
+                 "voxelgrid"_a)
+            .def("get_distance", [](const geometry::DistanceTransform& d, const farray& q) { return d.GetDistance(to_vector3(q)); }, "query"_a)
+            .def("get_distances",
+                 [](const geometry::DistanceTransform& d, const py::object& queries) {
+                     utility::device_vector<Eigen::Vector3f> q;
+                     set_vec(q, queries);
+                     const std::vector<float> h = d.GetDistances(q)->to_host();
+                     py::array_t<float> a((py::ssize_t)h.size());
+                     if (!h.empty()) std::memcpy(a.mutable_data(), h.data(), h.size() * sizeof(float));
+                     return a;
+                 },
+                 "queries"_a)
+            .def("get_voxel",
+                 [](const geometry::DistanceTransform& d, const farray& point) {
+                     const auto r = d.GetVoxel(to_vector3(point));
+                     return std::make_tuple(std::get<0>(r), std::get<1>(r));
+                 },
+                 "point"_a)
+            .def("get_voxels",
+                 [](const geometry::DistanceTransform& d) {
+                     const std::vector<geometry::DistanceVoxel> h = d.GetVoxels();
+                     py::array_t<int> idx({(py::ssize_t)h.size(), (py::ssize_t)3});
+                     py::array_t<float> dist((py::ssize_t)h.size());
+                     for (size_t i = 0; i < h.size(); ++i) {
+                         for (int k = 0; k < 3; ++k) idx.mutable_at(i, k) = h[i].IsNotSite() ? -1 : (int)h[i].nearest_index_(k);
+                         dist.mutable_at(i) = h[i].distance_;
+                     }
+                     return std::make_tuple(idx, dist);
+                 })
+            .def("clear", [](geometry::DistanceTransform& d) { d.Clear(); })
+            .def("get_min_bound", [](const geometry::DistanceTransform& d) { return from_vector3(d.GetMinBound()); })
+            .def("get_max_bound", [](const geometry::DistanceTransform& d) { return from_vector3(d.GetMaxBound()); })
+            .def("get_center", [](const geometry::DistanceTransform& d) { return from_vector3(d.GetCenter()); })
+            .def_static("create_from_occupancy_grid", &geometry::DistanceTransform::CreateFromOccupancyGrid, "input"_a)
+            .def_readwrite("voxel_size", &geometry::DistanceTransform::voxel_size_)
+            .def_readwrite("resolution", &geometry::DistanceTransform::resolution_)
+            .def_property(
+                    "origin", [](const geometry::DistanceTransform& d) { return from_vector3(d.origin_); },
+                    [](geometry::DistanceTransform& d, const farray& v) { d.origin_ = to_vector3(v); });
 
     // ---------------------------------------------------------------- integration
     // cupoch_pybind/integration/integration.cpp: TSDFVolumeColorType and UniformTSDFVolume with the reference's names.

@@ -8,6 +8,7 @@
 //   mi_rgbd.hip      depth / RGB-D frame -> cloud, RGB-D odometry
 //   mi_tsdf.hip      UniformTSDFVolume
 //   mi_occgrid.hip   OccupancyGrid
+//   mi_edt.hip       DistanceTransform
 //   mi_voxelgrid.hip VoxelGrid (from points, dense, merge, carve, query, bounds, selections, paint)
 //   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry,
 //                    RemoveStatisticalOutliers / RemoveRadiusOutliers, ClusterDBSCAN, ComputeISSKeypoints
@@ -166,6 +167,8 @@ struct mi_icp_ctx {
     std::vector<mi_icp_tsdf*> tsdf_volumes;
     // ---- geometry::OccupancyGrid: the grids this context made (mi_occgrid.hip), freed with it ----
     std::vector<mi_icp_occgrid*> occ_grids;
+    // ---- geometry::DistanceTransform: the transforms this context made (mi_edt.hip), freed with it ----
+    std::vector<mi_icp_dt*> dts;
 
     // ---- instrumentation ----
     mi::eng::DevBuf stamps;    // loop.h "where an iteration's time goes" (mi_icp_debug_set_step_stamps)
@@ -520,6 +523,10 @@ int occupancy_geometry(int which);
 void tsdf_release_all(mi_icp_ctx* c);     // mi_icp_destroy: the volumes of mi_icp_tsdf_create
 // ---- mi_occgrid.hip
 void occgrid_release_all(mi_icp_ctx* c);  // mi_icp_destroy: the grids of mi_icp_occgrid_create
+// a grid's log-odds plane, resolution and inclusive bounds (min[3], max[3]) for a reader on the device
+int occgrid_view(mi_icp_ctx* c, const mi_icp_occgrid* o, const char* what, const float** prob, int* resolution, int* bounds6);
+// ---- mi_edt.hip
+void dt_release_all(mi_icp_ctx* c);       // mi_icp_destroy: the transforms of mi_icp_dt_create
 // ---- mi_geometry.hip
 // The points whose flags[0..n) are set, ascending (select.h: exclusive_scan_u32 + select_gather), into out[] (the
 // caller's, staged when mem_kind is MI_ICP_HOST) and their original indices into out_idx (may be null); *m = their

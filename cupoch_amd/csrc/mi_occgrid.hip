@@ -35,6 +35,15 @@ void occgrid_release_all(mi_icp_ctx* c) {
     }
     c->occ_grids.clear();
 }
+
+int occgrid_view(mi_icp_ctx* c, const mi_icp_occgrid* o, const char* what, const float** prob, int* resolution, int* bounds6) {
+    if (!o || o->owner != c || std::find(c->occ_grids.begin(), c->occ_grids.end(), o) == c->occ_grids.end())
+        return fail(c, MI_ICP_ERR_INVALID, "%s: not a grid of this context", what);
+    *prob = o->g.prob;
+    *resolution = o->g.res;
+    for (int k = 0; k < 6; ++k) bounds6[k] = o->bounds[k];
+    return MI_ICP_OK;
+}
 }  // namespace eng
 }  // namespace mi
 

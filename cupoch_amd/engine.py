@@ -96,7 +96,9 @@ class Engine:
     def _chk(self, rc):
         if rc < 0:
             msg = self._L.mi_icp_last_error(self._ctx)
-            raise MiIcpError("mi_icp error %d: %s" % (rc, (msg or b"").decode()))
+            err = MiIcpError("mi_icp error %d: %s" % (rc, (msg or b"").decode()))
+            err.code = int(rc)
+            raise err
         return rc
 
     def close(self):
@@ -838,6 +840,65 @@ class Engine:
         t, tp = self._out(MI_ICP_DEVICE, torch.device("cuda", self.device), (n,))
         self._chk(self._L.mi_icp_occgrid_get_voxels(self._ctx, grid, tp))
         return t
+
+    # -- geometry::DistanceTransform (include/mi_icp.h; arrays are device tensors, numpy inputs are uploaded) -------
+    @staticmethod
+    def _f3(v):
+        return (C.c_float * 3)(*[float(x) for x in np.asarray(v, np.float32).reshape(3)])
+
+    def dt_create(self, resolution):
+        """-> an opaque transform handle of this engine (mi_icp_dt_create)"""
+        h = C.c_void_p()
+        self._chk(self._L.mi_icp_dt_create(self._ctx, int(resolution), C.byref(h)))
+        return h
+
+    def dt_destroy(self, dt):
+        if getattr(self, "_ctx", None) and dt:
+            self._chk(self._L.mi_icp_dt_destroy(self._ctx, dt))
+
+    def dt_reconstruct(self, dt, resolution):
+        self._chk(self._L.mi_icp_dt_reconstruct(self._ctx, dt, int(resolution)))
+
+    def dt_compute_cells(self, dt, cells, want_dropped=False):
+        """the sites are the cells [n, 3] int32 inside the grid; -> the number dropped (None unless asked for)"""
+        t = self._occ_dev(cells, np.int32)
+        m = C.c_int64(0)
+        self._chk(self._L.mi_icp_dt_compute_cells(self._ctx, dt, C.c_void_p(t.data_ptr()), int(t.shape[0]),
+                                                  C.byref(m) if want_dropped else None))
+        if not want_dropped:
+            self.synchronize()   # (t may go)
+        return int(m.value) if want_dropped else None
+
+    def dt_compute_voxelgrid(self, dt, voxel_size, origin, keys, grid_voxel_size, grid_origin, want_dropped=False):
+        t = self._occ_dev(keys, np.int32)
+        m = C.c_int64(0)
+        self._chk(self._L.mi_icp_dt_compute_voxelgrid(self._ctx, dt, float(voxel_size), self._f3(origin),
+                                                      C.c_void_p(t.data_ptr()), int(t.shape[0]), float(grid_voxel_size),
+                                                      self._f3(grid_origin), C.byref(m) if want_dropped else None))
+        if not want_dropped:
+            self.synchronize()   # (t may go)
+        return int(m.value) if want_dropped else None
+
+    def dt_compute_occgrid(self, dt, grid, occ_prob_thres_log):
+        self._chk(self._L.mi_icp_dt_compute_occgrid(self._ctx, dt, grid, float(occ_prob_thres_log)))
+
+    def dt_query(self, dt, voxel_size, origin, points):
+        """-> (distance [n], NaN outside the grid; nearest site [n, 3] int32, -1 without one), device tensors"""
+        t = self._occ_dev(points, np.float32)
+        n = int(t.shape[0])
+        dev = torch.device("cuda", self.device)
+        (dist, dp), (idx, ip) = self._out(MI_ICP_DEVICE, dev, (n,)), self._out(MI_ICP_DEVICE, dev, (n, 3), np.int32)
+        self._chk(self._L.mi_icp_dt_query(self._ctx, dt, float(voxel_size), self._f3(origin), C.c_void_p(t.data_ptr()), n, dp, ip))
+        self.synchronize()   # (t may go)
+        return dist, idx
+
+    def dt_get_voxels(self, dt, voxel_size, n, want_nearest=True, want_distance=True):
+        """-> the whole plane: (nearest site [n, 3] int32 or None, distance [n] or None) on the device"""
+        dev = torch.device("cuda", self.device)
+        idx, ip = self._out(MI_ICP_DEVICE, dev, (n, 3), np.int32) if want_nearest else (None, None)
+        dist, dp = self._out(MI_ICP_DEVICE, dev, (n,)) if want_distance else (None, None)
+        self._chk(self._L.mi_icp_dt_get_voxels(self._ctx, dt, float(voxel_size), ip, dp))
+        return idx, dist
 
     # -- geometry::VoxelGrid (include/mi_icp.h; keys int32 [m, 3] and colours [m, 3] are device tensors) -----------
     VOXELGRID_AVERAGE, VOXELGRID_KEEP_FIRST = 0, 1

@@ -6,10 +6,15 @@ OccupancyGrid / OccupancyVoxel mirror geometry/occupancygrid.h:31-142 (python su
 src/python/cupoch_pybind/geometry/occupancygrid.cpp); not built: OccupancyGrid.create_from_voxel_grid.
 Voxel / VoxelGrid mirror geometry/voxelgrid.h:48-214 (python surface src/python/cupoch_pybind/geometry/voxelgrid.cpp);
 not built: create_from_triangle_mesh[_within_bounds] (no TriangleMesh here), get_oriented_bounding_box, VoxelGrid file
-I/O, visualisation, DistanceTransform and collision."""
+I/O, visualisation and collision.
+DistanceVoxel / DistanceTransform mirror geometry/distancetransform.h:30-78 (python surface
+src/python/cupoch_pybind/geometry/distancetransform.cpp); not built: the collision, planning and visualisation
+consumers of a transform."""
+import sys
+
 import numpy as np
 
-from . import utility
+from . import _lib, utility
 from .engine import Engine
 
 try:
@@ -1072,6 +1077,219 @@ class VoxelGrid:
         col = torch.empty((int(idx.shape[0]), 3), dtype=torch.float32, device=idx.device)
         e.voxelgrid_paint(col, (0.0, 0.0, 1.0))
         return out._set(idx, col, True)
+
+
+def _log_error(msg):
+    print("[cupoch_amd] Error: %s" % msg, file=sys.stderr)   # utility::LogError: logs, keeps going
+
+
+class DistanceVoxel:
+    """geometry::DistanceVoxel (distancetransform.h:30-49): the nearest site's grid index and the distance to it.
+    Without a site the index is (-1, -1, -1) and the distance +inf."""
+
+    def __init__(self, nearest_index=(0, 0, 0), distance=0.0):
+        self.nearest_index = np.asarray(nearest_index, np.int32).reshape(3).copy()
+        self.distance = float(np.float32(distance))
+
+    def __repr__(self):
+        g = self.nearest_index
+        return "geometry::DistanceVoxel with nearest_index: (%d, %d, %d), distance: %g)" % (g[0], g[1], g[2], self.distance)
+
+
+class DistanceVoxels:
+    """the whole plane of a DistanceTransform: nearest_index [res^3, 3] int32 and distance [res^3] as device tensors,
+    indexed (x*res + y)*res + z.  len() and [] give DistanceVoxel objects."""
+
+    def __init__(self, nearest_index, distance):
+        self.nearest_index = nearest_index
+        self.distance = distance
+
+    def __len__(self):
+        return int(self.distance.shape[0])
+
+    def __getitem__(self, i):
+        return DistanceVoxel(self.nearest_index[i].cpu().numpy(), float(self.distance[i]))
+
+    def cpu(self):
+        """-> (nearest_index, distance) as numpy arrays"""
+        return self.nearest_index.cpu().numpy(), self.distance.cpu().numpy()
+
+
+class DistanceTransform:
+    """geometry::DistanceTransform (distancetransform.h:51-78): the exact Euclidean distance from every cell of a dense
+    resolution^3 grid to the nearest site.  The attributes are the reference's public members and are read when a call
+    is made; the cells live on the GPU, made on first use (a changed `resolution` rebuilds the transform without sites,
+    as reconstruct does).  Every compute replaces the site set.  Deviations from the reference: DESIGN.md section 6."""
+
+    def __init__(self, voxel_size=0.05, resolution=512, origin=(0.0, 0.0, 0.0), device=None):
+        self.voxel_size = float(np.float32(voxel_size))
+        self.resolution = int(resolution)
+        self.origin = np.asarray(origin, np.float32).reshape(3).copy()
+        self.dropped = None     # cells outside the grid at the last compute with count_dropped=True
+        self._device = device
+        self._eng = None
+        self._dt = None
+        self._made_res = 0
+
+    def __del__(self):
+        try:
+            if self._eng is not None:
+                self._eng.dt_destroy(self._dt)
+        except Exception:
+            pass
+        self._dt = None
+
+    # the engine and the handle of this call
+    def _call(self):
+        if self._eng is None:
+            self._eng = get_engine(self._device)
+        if self._dt is None:
+            self._dt = self._eng.dt_create(self.resolution)
+            self._made_res = int(self.resolution)
+        elif self._made_res != int(self.resolution):
+            try:
+                self._eng.dt_reconstruct(self._dt, self.resolution)
+            except _lib.MiIcpError as e:
+                if e.code == _lib.MI_ICP_ERR_HIP:      # the planes could not be made: the handle is gone
+                    self._dt, self._made_res = None, 0
+                raise                                   # (a refused resolution leaves the transform as it was)
+            self._made_res = int(self.resolution)
+        return self._eng, self._dt
+
+    def clear(self):
+        """no sites; size and memory stay (the reference's Clear() frees the voxels and zeroes the resolution)"""
+        if self._dt is not None and self._made_res == int(self.resolution):
+            self._eng.dt_compute_cells(self._dt, np.zeros((0, 3), np.int32))
+        return self
+
+    def reconstruct(self, voxel_size, resolution):
+        self.voxel_size = float(np.float32(voxel_size))
+        self.resolution = int(resolution)
+        self._call()
+        return self
+
+    def compute_edt(self, x, count_dropped=False):
+        """x: a VoxelGrid, an OccupancyGrid, or [n, 3] integer cells (tensor / array).  With count_dropped the number
+        of cells that fell outside the grid is left in self.dropped (it costs the call a wait)."""
+        if isinstance(x, VoxelGrid):
+            if abs(float(np.float32(self.voxel_size)) - float(np.float32(x.voxel_size))) > float(np.finfo(np.float32).eps):
+                _log_error("Unsupport computing Voronoi diagrams from different voxel size.")
+                return self
+            e, h = self._call()
+            keys = x._keys if x._keys is not None else np.zeros((0, 3), np.int32)
+            self.dropped = e.dt_compute_voxelgrid(h, self.voxel_size, self.origin, keys, x.voxel_size, x.origin, count_dropped)
+        elif isinstance(x, OccupancyGrid):
+            if int(x.resolution) != int(self.resolution):
+                raise ValueError("DistanceTransform.compute_edt: the occupancy grid's resolution differs")
+            e, h = self._call()
+            e2, g, _ = x._call()
+            if e2 is not e:
+                raise ValueError("DistanceTransform.compute_edt: the occupancy grid lives on another device")
+            e.dt_compute_occgrid(h, g, float(np.float32(x.occ_prob_thres_log)))
+            self.dropped = 0 if count_dropped else None
+        else:
+            cells = getattr(x, "tensor", x)
+            if not (torch is not None and torch.is_tensor(cells)):
+                cells = np.asarray(cells)
+                if cells.size and not np.issubdtype(cells.dtype, np.integer):
+                    raise TypeError("DistanceTransform.compute_edt: cells must be integers")
+                cells = cells.astype(np.int32).reshape(-1, 3)
+            elif cells.is_floating_point():
+                raise TypeError("DistanceTransform.compute_edt: cells must be integers")
+            e, h = self._call()
+            self.dropped = e.dt_compute_cells(h, cells, count_dropped)
+        return self
+
+    # the distance is derived from the nearest index, so the reference's two calls are one here
+    compute_voronoi_diagram = compute_edt
+
+    # ---- queries
+    def get_distances(self, queries):
+        """batched: [n, 3] points -> [n] distances on the device, NaN outside the grid, +inf without a site"""
+        e, h = self._call()
+        queries = queries.points.tensor if isinstance(queries, PointCloud) else getattr(queries, "tensor", queries)
+        return e.dt_query(h, self.voxel_size, self.origin, queries)[0]
+
+    def get_nearest_indices(self, queries):
+        """batched: [n, 3] points -> (distance [n], nearest site [n, 3] int32), device tensors"""
+        e, h = self._call()
+        return e.dt_query(h, self.voxel_size, self.origin, getattr(queries, "tensor", queries))
+
+    def get_distance(self, query):
+        return float(self.get_distances(np.asarray(query, np.float32).reshape(1, 3))[0])
+
+    def get_voxel(self, point):
+        """-> (inside the grid, DistanceVoxel)"""
+        dist, idx = self.get_nearest_indices(np.asarray(point, np.float32).reshape(1, 3))
+        d = float(dist[0])
+        if d != d:
+            return False, DistanceVoxel()
+        return True, DistanceVoxel(idx[0].cpu().numpy(), d)
+
+    @property
+    def voxels(self):
+        """the whole plane (DistanceVoxels); 16 bytes per cell on the device"""
+        e, h = self._call()
+        return DistanceVoxels(*e.dt_get_voxels(h, self.voxel_size, int(self.resolution) ** 3))
+
+    def get_nearest_index_plane(self):
+        """[resolution^3, 3] int32 on the device, indexed (x*res + y)*res + z; -1 without a site"""
+        e, h = self._call()
+        return e.dt_get_voxels(h, self.voxel_size, int(self.resolution) ** 3, want_distance=False)[0]
+
+    def get_distance_plane(self):
+        """[resolution^3] float32 on the device, indexed (x*res + y)*res + z; +inf without a site"""
+        e, h = self._call()
+        return e.dt_get_voxels(h, self.voxel_size, int(self.resolution) ** 3, want_nearest=False)[1]
+
+    def has_voxels(self):
+        return True
+
+    def __repr__(self):
+        return "geometry::DistanceTransform with %d resolution." % int(self.resolution)
+
+    # ---- DenseGrid / GeometryBase3D (densegrid.inl:53-125)
+    def get_min_bound(self):
+        length = np.float32(np.float32(self.voxel_size) * np.float32(self.resolution)) * np.float32(0.5)
+        return (np.asarray(self.origin, np.float32) - length).astype(np.float32)
+
+    def get_max_bound(self):
+        length = np.float32(np.float32(self.voxel_size) * np.float32(self.resolution)) * np.float32(0.5)
+        return (np.asarray(self.origin, np.float32) + length).astype(np.float32)
+
+    def get_center(self):
+        return np.asarray(self.origin, np.float32).copy()
+
+    def get_axis_aligned_bounding_box(self):
+        return AxisAlignedBoundingBox(self.get_min_bound(), self.get_max_bound())
+
+    def is_empty(self):
+        return False
+
+    def translate(self, translation, relative=True):
+        t = np.asarray(translation, np.float32).reshape(3)
+        self.origin = (np.asarray(self.origin, np.float32) + t).astype(np.float32) if relative else t.copy()
+        return self
+
+    def scale(self, scale, center=True):
+        self.voxel_size = float(np.float32(self.voxel_size) * np.float32(scale))
+        return self
+
+    def transform(self, transformation):
+        _log_error("DenseGrid::Transform is not supported")
+        return self
+
+    def rotate(self, R, center=True):
+        _log_error("DenseGrid::Rotate is not supported")
+        return self
+
+    @staticmethod
+    def create_from_occupancy_grid(input):
+        """the COMPUTED transform of the occupied voxels of an OccupancyGrid, with its voxel_size, resolution and origin"""
+        if not (float(input.voxel_size) > 0.0):
+            _log_error("[CreateOccupancyGrid] occupancy grid  voxel_size <= 0.")
+        out = DistanceTransform(input.voxel_size, input.resolution, input.origin, device=input._call()[0].device)
+        return out.compute_edt(input)
 
 
 def _v3(v):

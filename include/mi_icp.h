@@ -25,8 +25,8 @@
  *     MI_ICP_ERR_INVALID before any buffer is read or written.  The caller owns all
  *     buffers it passes; the context owns its internal SoA copies, LBVH and
  *     scratch arena.
- *     THE ONE EXCEPTION is the mi_icp_occgrid_* family and the mi_icp_voxelgrid_*
- *     family beside it: their arrays (points, voxel
+ *     THE ONE EXCEPTION is the mi_icp_occgrid_* family and the mi_icp_voxelgrid_* and
+ *     mi_icp_dt_* families beside it: their arrays (points, voxel
  *     indices, outputs) are HIP device pointers only and they have no memory-kind
  *     argument; their small fixed-size arguments (the parameter block, viewpoint3,
  *     corners, bounds, counts) are host pointers or values.
@@ -792,7 +792,8 @@ MI_ICP_API int mi_icp_tsdf_get_voxels(mi_icp_ctx* ctx, mi_icp_tsdf* volume, floa
  * context that made it: destroyed with mi_icp_occgrid_destroy, or with the context.  Stored as the
  * log-odds plane alone, 4 bytes per voxel (the reference keeps 24: a grid index that is the voxel's
  * position and a colour it never writes, always (0, 0, 1)), beside a one-byte mark per voxel that is
- * zero between calls.  Not built: CreateFromVoxelGrid, and the DistanceTransform and collision consumers.
+ * zero between calls.  Not built: CreateFromVoxelGrid and the collision consumers.  The distance field of
+ * the occupied voxels is geometry::DistanceTransform (mi_icp_dt_compute_occgrid, below).
  * The occupied space leaves the library as a geometry::VoxelGrid (VoxelGrid::CreateFromOccupancyGrid, below).
  *
  * ARRAYS ARE DEVICE POINTERS; there is no memory-kind argument in this family (the preamble's one
@@ -893,8 +894,8 @@ MI_ICP_API int mi_icp_occgrid_get_voxels(mi_icp_ctx* ctx, mi_icp_occgrid* grid, 
  * between calls.  Every producer below emits keys DISTINCT and ASCENDING lexicographically, x most
  * significant (the reference's operator< on Vector3i, utility/helper.h:114).  Not built:
  * CreateFromTriangleMesh[WithinBounds] (no TriangleMesh here), GetOrientedBoundingBox, file I/O,
- * visualisation, DistanceTransform, collision; OccupancyGrid::CreateFromVoxelGrid and
- * UniformTSDFVolume::ExtractVoxelGrid.
+ * visualisation, collision; OccupancyGrid::CreateFromVoxelGrid and UniformTSDFVolume::ExtractVoxelGrid.
+ * The distance field of a grid's voxels is geometry::DistanceTransform (mi_icp_dt_compute_voxelgrid, below).
  *
  * ARRAYS ARE DEVICE POINTERS; there is no memory-kind argument in this family (the preamble's
  * exception).  voxel_size, bounds, origin, camera matrices, counts and the three bounds outputs are host
@@ -980,6 +981,71 @@ MI_ICP_API int mi_icp_voxelgrid_select_by_index(mi_icp_ctx* ctx, const int32_t* 
                                                 int32_t* out_keys, float* out_colors, int64_t* m_out);
 MI_ICP_API int mi_icp_voxelgrid_paint(mi_icp_ctx* ctx, float* colors, int64_t m, const int64_t* indices,
                                       int64_t n_indices, const float* color3);
+
+/* ---- geometry::DistanceTransform (geometry/distancetransform.{h,cu}, distancetransform_factory.cu) ----
+ * The exact Euclidean distance transform of a set of SITES (obstacle cells) in a dense cube of
+ * resolution^3 cells of side voxel_size around origin; linear index (x*res + y)*res + z; h = res / 2
+ * (integer).  A transform belongs to the context that made it: destroyed with mi_icp_dt_destroy, or with
+ * the context.  Stored as one 32-bit word per cell -- the nearest site's three 10-bit coordinates and two
+ * state bits, hence the cap of 1024 -- in two planes: 8 bytes per cell, 8 GiB at 1024^3, 1 GiB at 512^3
+ * (the reference keeps a 12-byte record and a buffer of the same size beside it).  Not built: the
+ * collision, planning and visualisation consumers of a transform.
+ *
+ * ARRAYS ARE DEVICE POINTERS; there is no memory-kind argument in this family (the preamble's
+ * exception).  voxel_size, the origins, the threshold and the counts are host memory or values.
+ * voxel_size and origin travel with every call that reads them (the reference's public members are read
+ * when a call is made); only the resolution is the transform's own.
+ *
+ * CONTRACT.
+ *  compute_*: every cell gets a NEAREST SITE: a site whose integer squared distance d2 = dx^2 + dy^2 +
+ *   dz^2 to the cell is the minimum over all sites -- exact, at every resolution (the one test that
+ *   decides between three sites is done in 64-bit integers).  Which of several equidistant sites is
+ *   reported is a pure function of the site SET: the same set in any order, with any duplicates, gives
+ *   the same bytes.  With no site every cell has no nearest site.  EVERY compute REPLACES the site set.
+ *   The cell's distance is sqrtf((float)d2) * voxel_size in fp32 (d2 <= 3 * 1023^2 is exact in fp32; the
+ *   square root is correctly rounded; the product is not fused), +inf without a site.  Only the nearest
+ *   index is stored; the distance is derived, with the voxel_size given, when it is read.
+ *  compute_cells(cells int32[n][3])  ComputeEDT(device_vector<Vector3i>): grid indices.  A cell outside
+ *   [0, res)^3 on any axis is dropped (the reference writes out of bounds); *dropped (optional) is their
+ *   number, and asking for it costs the call its one wait.  Duplicates are fine.  n == 0: no sites.
+ *  compute_voxelgrid(keys int32[m][3], grid_voxel_size, grid_origin)  ComputeEDT(VoxelGrid): the cell of a
+ *   key is, in fp32 and in this order, floor((((float)key * voxel_size + grid_origin) - origin) /
+ *   voxel_size) + h per axis (compute_obstacle_cells_functor; floor(.) to int holds the value inside
+ *   +-1e9 first), dropped like the cells above.  |voxel_size - grid_voxel_size| > FLT_EPSILON:
+ *   MI_ICP_ERR_INVALID, nothing changed.
+ *  compute_occgrid(grid, occ_prob_thres_log)  CreateFromOccupancyGrid: the sites are exactly the voxels
+ *   mi_icp_occgrid_extract(MI_ICP_OCCGRID_OCCUPIED) lists -- inside the grid's bounds box, p >
+ *   occ_prob_thres_log -- read from the log-odds plane on the device.  The grid must be of this context
+ *   and of the same resolution, else MI_ICP_ERR_INVALID, nothing changed.
+ *  query(queries float[n][3]): the cell of a point is floor((q - origin) / voxel_size) + h per axis
+ *   (DenseGrid::GetVoxelIndex; the reference's GetDistance uses another formula and reads out of bounds
+ *   outside the grid).  out_distance[i] is the cell's distance; out_nearest (optional) int32[n][3] its
+ *   nearest site, (-1, -1, -1) when there is none.  A point outside the grid on any axis (or not finite)
+ *   gives NaN and (-1, -1, -1).
+ *  get_voxels: the whole plane: out_nearest int32[res^3][3] and / or out_distance float[res^3].
+ *  reconstruct: a new resolution, no sites.
+ * Limits: 2 <= resolution <= MI_ICP_DT_MAX_RESOLUTION, any value in that range; voxel_size positive and
+ * finite and origin finite wherever they are read; counts up to 0x7fffff00.  Else MI_ICP_ERR_INVALID and
+ * nothing changes.  A plane that cannot be allocated is MI_ICP_ERR_HIP, not a crash (a failed
+ * reconstruct leaves no handle, as mi_icp_occgrid_reconstruct).
+ * Waits: compute_cells / compute_voxelgrid once when `dropped` is asked for, else none; get_voxels waits;
+ * the others only enqueue. */
+#define MI_ICP_DT_MAX_RESOLUTION 1024
+typedef struct mi_icp_dt mi_icp_dt;
+MI_ICP_API int mi_icp_dt_create(mi_icp_ctx* ctx, int resolution, mi_icp_dt** out);
+MI_ICP_API int mi_icp_dt_destroy(mi_icp_ctx* ctx, mi_icp_dt* dt);
+MI_ICP_API int mi_icp_dt_reconstruct(mi_icp_ctx* ctx, mi_icp_dt* dt, int resolution);
+MI_ICP_API int mi_icp_dt_compute_cells(mi_icp_ctx* ctx, mi_icp_dt* dt, const int32_t* cells, int64_t n,
+                                       int64_t* dropped);
+MI_ICP_API int mi_icp_dt_compute_voxelgrid(mi_icp_ctx* ctx, mi_icp_dt* dt, float voxel_size, const float* origin3,
+                                           const int32_t* keys, int64_t m, float grid_voxel_size,
+                                           const float* grid_origin3, int64_t* dropped);
+MI_ICP_API int mi_icp_dt_compute_occgrid(mi_icp_ctx* ctx, mi_icp_dt* dt, const mi_icp_occgrid* grid,
+                                         float occ_prob_thres_log);
+MI_ICP_API int mi_icp_dt_query(mi_icp_ctx* ctx, mi_icp_dt* dt, float voxel_size, const float* origin3,
+                               const float* queries, int64_t n, float* out_distance, int32_t* out_nearest);
+MI_ICP_API int mi_icp_dt_get_voxels(mi_icp_ctx* ctx, mi_icp_dt* dt, float voxel_size, int32_t* out_nearest,
+                                    float* out_distance);
 
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
