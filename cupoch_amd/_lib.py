@@ -18,7 +18,7 @@ INCLUDE = os.path.join(ROOT, "include")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I/opt/rocm/include"]
 # the library's translation units (csrc/ctx.h says what each holds); compiled side by side, then linked
-UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_occgrid", "mi_voxelgrid", "mi_edt", "mi_knn", "mi_comm", "mi_debug"]
+UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_occgrid", "mi_voxelgrid", "mi_collision", "mi_edt", "mi_knn", "mi_comm", "mi_debug"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 MI_ICP_HOST, MI_ICP_DEVICE = 0, 1
@@ -135,6 +135,21 @@ class OccGridParams(C.Structure):                      # mi_icp_occgrid_params
                 ("occ_prob_thres_log", C.c_float)]
 
 
+class Primitive(C.Structure):                          # mi_icp_primitive (80 bytes)
+    _fields_ = [("type", C.c_int32), ("transform", C.c_float * 16), ("param", C.c_float * 3)]
+
+
+class CollisionSide(C.Structure):                      # mi_icp_collision_side
+    _fields_ = [("kind", C.c_int32), ("keys_sorted", C.c_int32), ("keys", C.c_void_p), ("keys_index", C.c_void_p),
+                ("m", C.c_int64),
+                ("voxel_size", C.c_float), ("origin", C.c_float * 3), ("grid", C.c_void_p),
+                ("grid_params", OccGridParams), ("points", C.c_void_p), ("n_points", C.c_int64),
+                ("lines", C.c_void_p), ("n_lines", C.c_int64), ("primitives", C.c_void_p),
+                ("n_primitives", C.c_int64)]
+
+
+COLLISION_VOXELGRID, COLLISION_OCCGRID, COLLISION_LINESET, COLLISION_PRIMITIVES = 1, 2, 3, 4
+
 # name -> (restype, argtypes); must list every MI_ICP_API symbol of include/mi_icp.h
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SIGNATURES = {
@@ -217,6 +232,10 @@ SIGNATURES = {
     "mi_icp_voxelgrid_bounds": (_I, [_P, _P, _L, _F, _P, _P, _P, _P]),
     "mi_icp_voxelgrid_select_by_index": (_I, [_P, _P, _P, _L, _P, _L, _I, _P, _P, C.POINTER(_L)]),
     "mi_icp_voxelgrid_paint": (_I, [_P, _P, _L, _P, _L, _P]),
+    "mi_icp_collision_compute": (_I, [_P, C.POINTER(CollisionSide), C.POINTER(CollisionSide), _F, _P, _L, C.POINTER(_L)]),
+    "mi_icp_collision_voxelize_primitive": (_I, [_P, C.POINTER(Primitive), _F, _P, _P, _L, C.POINTER(_L), _P]),
+    "mi_icp_collision_sort_keys": (_I, [_P, _P, _L, _P, _P, C.POINTER(_L)]),
+    "mi_icp_primitive_aabb": (_I, [C.POINTER(Primitive), _P, _P]),
     "mi_icp_covariances_from_normals": (_I, [_P, _P, _L, _F, _P, _I]),
     "mi_icp_estimate_normals_knn": (_I, [_P, _P, _L, _I, _P, _I]),
     "mi_icp_estimate_normals_radius": (_I, [_P, _P, _L, _F, _I, _P, _I]),

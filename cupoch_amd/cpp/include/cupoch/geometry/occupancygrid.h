@@ -5,9 +5,9 @@
 // OccupancyVoxel records whose grid_index_ is the voxel's position and whose colour is the constant (0, 0, 1).
 // The public members are read when a call is made, as in the reference; min_bound_ / max_bound_ are refreshed by every
 // call that changes them.  Clear() leaves a usable grid (every voxel unknown), where the reference's leaves none.
-// Not built: CreateFromVoxelGrid and the collision consumers (VoxelGrid::CreateFromOccupancyGrid takes the occupied
-// space out: geometry/voxelgrid.h; DistanceTransform::CreateFromOccupancyGrid its distance field:
-// geometry/distancetransform.h).
+// Not built: CreateFromVoxelGrid (VoxelGrid::CreateFromOccupancyGrid takes the occupied space out:
+// geometry/voxelgrid.h; DistanceTransform::CreateFromOccupancyGrid its distance field: geometry/distancetransform.h;
+// collisions: collision/collision.h).
 #pragma once
 #include <limits>
 #include <memory>

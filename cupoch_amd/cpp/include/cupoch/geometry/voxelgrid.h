@@ -5,7 +5,7 @@
 // Every factory, operator+= and AddVoxel[s] leave the keys distinct and ascending (x most significant).  LogError logs
 // and returns, as in the reference.  Deviations from the reference: DESIGN.md section 6.
 // Not built: CreateFromTriangleMesh[WithinBounds] (no TriangleMesh here), GetOrientedBoundingBox, VoxelGrid file I/O,
-// visualisation, collision.  (The distance field of a grid: geometry/distancetransform.h.)
+// visualisation.  (The distance field of a grid: geometry/distancetransform.h; collisions: collision/collision.h.)
 #pragma once
 #include <array>
 #include <memory>
@@ -65,6 +65,8 @@ public:
 
     bool HasVoxels() const { return voxels_keys_.size() > 0; }
     bool HasColors() const { return true; }  // by default the colours are (1, 1, 1)
+    /// the keys are known to ascend (every producer here; not after SetVoxels / SelectByIndex)
+    bool KeysSorted() const { return sorted_; }
     Eigen::Vector3i GetVoxel(const Eigen::Vector3f& point) const;
     /// the zero vector when the grid has no such voxel
     Eigen::Vector3f GetVoxelCenterCoordinate(const Eigen::Vector3i& idx) const;

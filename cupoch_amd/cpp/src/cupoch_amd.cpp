@@ -1539,6 +1539,97 @@ std::shared_ptr<VoxelGrid> VoxelGrid::CreateFromOccupancyGrid(const OccupancyGri
     return output;
 }
 
+// ---- geometry::LineSet<3> (lineset.cu): the cloud's bounds and moves on its points
+LineSet<3>::LineSet() : GeometryBase3D(GeometryType::LineSet) {}
+LineSet<3>::LineSet(const utility::device_vector<Eigen::Vector3f>& points, const utility::device_vector<Eigen::Vector2i>& lines)
+    : GeometryBase3D(GeometryType::LineSet), points_(points), lines_(lines) {}
+LineSet<3>::LineSet(const thrust::host_vector<Eigen::Vector3f>& points, const thrust::host_vector<Eigen::Vector2i>& lines)
+    : GeometryBase3D(GeometryType::LineSet), points_(points), lines_(lines) {}
+LineSet<3>::~LineSet() {}
+
+LineSet<3>& LineSet<3>::Clear() {
+    points_.clear();
+    lines_.clear();
+    colors_.clear();
+    return *this;
+}
+Eigen::Vector3f LineSet<3>::GetMinBound() const {
+    Eigen::Vector3f b;
+    Bounds(points_, &b, nullptr, nullptr);
+    return b;
+}
+Eigen::Vector3f LineSet<3>::GetMaxBound() const {
+    Eigen::Vector3f b;
+    Bounds(points_, nullptr, &b, nullptr);
+    return b;
+}
+Eigen::Vector3f LineSet<3>::GetCenter() const {
+    Eigen::Vector3f b;
+    Bounds(points_, nullptr, nullptr, &b);
+    return b;
+}
+AxisAlignedBoundingBox3 LineSet<3>::GetAxisAlignedBoundingBox() const {
+    Eigen::Vector3f mn, mx;
+    Bounds(points_, &mn, &mx, nullptr);
+    return AxisAlignedBoundingBox3(mn, mx);
+}
+LineSet<3>& LineSet<3>::Transform(const Eigen::Matrix4f& transformation) {
+    Check(mi_icp_transform(Engine(), transformation.data(), points_.empty() ? nullptr : points_.data()->data(), nullptr, nullptr,
+                           (int64_t)points_.size(), MI_ICP_DEVICE));
+    return *this;
+}
+LineSet<3>& LineSet<3>::Translate(const Eigen::Vector3f& translation, bool relative) {
+    Eigen::Vector3f t = translation;
+    if (!relative) t -= GetCenter();
+    Check(mi_icp_affine(Engine(), nullptr, 0.0f, 0, nullptr, t.data(), points_.empty() ? nullptr : points_.data()->data(), nullptr, nullptr,
+                        (int64_t)points_.size(), MI_ICP_DEVICE));
+    return *this;
+}
+LineSet<3>& LineSet<3>::Scale(const float scale, bool center) {
+    Eigen::Vector3f c = Eigen::Vector3f::Zero();
+    const bool use_c = center && !points_.empty();
+    if (use_c) c = GetCenter();
+    Check(mi_icp_affine(Engine(), nullptr, scale, 1, use_c ? c.data() : nullptr, nullptr, points_.empty() ? nullptr : points_.data()->data(),
+                        nullptr, nullptr, (int64_t)points_.size(), MI_ICP_DEVICE));
+    return *this;
+}
+LineSet<3>& LineSet<3>::Rotate(const Eigen::Matrix3f& R, bool center) {
+    Eigen::Vector3f c = Eigen::Vector3f::Zero();
+    const bool use_c = center && !points_.empty();
+    if (use_c) c = GetCenter();
+    Check(mi_icp_affine(Engine(), R.data(), 0.0f, 0, use_c ? c.data() : nullptr, nullptr, points_.empty() ? nullptr : points_.data()->data(),
+                        nullptr, nullptr, (int64_t)points_.size(), MI_ICP_DEVICE));
+    return *this;
+}
+std::pair<Eigen::Vector3f, Eigen::Vector3f> LineSet<3>::GetLineCoordinate(size_t line_index) const {
+    std::pair<Eigen::Vector3f, Eigen::Vector3f> out(Eigen::Vector3f::Zero(), Eigen::Vector3f::Zero());
+    if (line_index >= lines_.size()) return out;
+    Eigen::Vector2i l;
+    utility::hip_check(hipMemcpy(&l, lines_.data() + line_index, sizeof(l), hipMemcpyDeviceToHost), "hipMemcpy");
+    if (l(0) < 0 || l(1) < 0 || (size_t)l(0) >= points_.size() || (size_t)l(1) >= points_.size()) return out;
+    utility::hip_check(hipMemcpy(&out.first, points_.data() + l(0), sizeof(Eigen::Vector3f), hipMemcpyDeviceToHost), "hipMemcpy");
+    utility::hip_check(hipMemcpy(&out.second, points_.data() + l(1), sizeof(Eigen::Vector3f), hipMemcpyDeviceToHost), "hipMemcpy");
+    return out;
+}
+LineSet<3>& LineSet<3>::PaintUniformColor(const Eigen::Vector3f& color) {
+    colors_ = std::vector<Eigen::Vector3f>(lines_.size(), color);
+    return *this;
+}
+std::shared_ptr<LineSet<3>> LineSet<3>::CreateFromAxisAlignedBoundingBox(const AxisAlignedBoundingBox3& box) {
+    const Eigen::Vector3f lo = box.GetMinBound(), hi = box.GetMaxBound();
+    std::vector<Eigen::Vector3f> p = {{lo(0), lo(1), lo(2)}, {hi(0), lo(1), lo(2)}, {hi(0), hi(1), lo(2)}, {lo(0), hi(1), lo(2)},
+                                      {lo(0), lo(1), hi(2)}, {hi(0), lo(1), hi(2)}, {hi(0), hi(1), hi(2)}, {lo(0), hi(1), hi(2)}};
+    const int e[12][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 0}, {4, 5}, {5, 6}, {6, 7}, {7, 4}, {0, 4}, {1, 5}, {2, 6}, {3, 7}};
+    std::vector<Eigen::Vector2i> l;
+    for (auto& q : e) {
+        Eigen::Vector2i v;
+        v(0) = q[0];
+        v(1) = q[1];
+        l.push_back(v);
+    }
+    return std::make_shared<LineSet<3>>(p, l);
+}
+
 // ---- geometry::DistanceTransform (distancetransform.cu, distancetransform_factory.cu, densegrid.inl) over mi_icp_dt_*
 namespace {
 DistanceVoxel MakeDistanceVoxel(const Eigen::Vector3i& nearest, float distance) {
@@ -1696,6 +1787,179 @@ std::shared_ptr<DistanceTransform> DistanceTransform::CreateFromOccupancyGrid(co
 }  // namespace geometry
 
 // ---------------------------------------------------------------- integration
+// ---------------------------------------------------------------- collision (collision.cu, primitives.cu) over mi_icp_collision_*
+namespace collision {
+
+namespace {
+
+using geometry::KeyPtr;
+
+mi_icp_primitive Record(const PrimitivePack& p) {
+    mi_icp_primitive r;
+    static_assert(sizeof(r) == sizeof(p), "one layout");
+    std::memcpy(&r, &p, sizeof(r));
+    return r;
+}
+
+// a side of a call and whatever device memory it needs for the call's duration
+struct Side {
+    mi_icp_collision_side s;
+    utility::device_vector<PrimitivePack> records;
+    Side() { std::memset(&s, 0, sizeof(s)); }
+};
+
+void Fill(Side* d, const geometry::VoxelGrid& g) {
+    d->s.kind = MI_ICP_COLLISION_VOXELGRID;
+    d->s.keys = KeyPtr(g.voxels_keys_);
+    d->s.m = (int64_t)g.voxels_keys_.size();
+    d->s.keys_sorted = g.KeysSorted() ? 1 : 0;
+    d->s.voxel_size = g.voxel_size_;
+    for (int k = 0; k < 3; ++k) d->s.origin[k] = g.origin_(k);
+}
+void Fill(Side* d, const geometry::OccupancyGrid& g) {
+    d->s.kind = MI_ICP_COLLISION_OCCGRID;
+    d->s.grid = g.Handle();
+    d->s.grid_params = geometry::OccParams(g);
+}
+void Fill(Side* d, const geometry::LineSet<3>& l) {
+    d->s.kind = MI_ICP_COLLISION_LINESET;
+    d->s.points = l.points_.empty() ? nullptr : l.points_.data()->data();
+    d->s.n_points = (int64_t)l.points_.size();
+    d->s.lines = l.lines_.empty() ? nullptr : l.lines_.data()->data();
+    d->s.n_lines = (int64_t)l.lines_.size();
+}
+void Fill(Side* d, const PrimitiveArray& p) {
+    d->records = p;
+    d->s.kind = MI_ICP_COLLISION_PRIMITIVES;
+    d->s.primitives = p.empty() ? nullptr : reinterpret_cast<const mi_icp_primitive*>(d->records.data());
+    d->s.n_primitives = (int64_t)p.size();
+}
+
+CollisionResult::CollisionType TypeOf(const geometry::VoxelGrid&) { return CollisionResult::CollisionType::VoxelGrid; }
+CollisionResult::CollisionType TypeOf(const geometry::OccupancyGrid&) { return CollisionResult::CollisionType::OccupancyGrid; }
+CollisionResult::CollisionType TypeOf(const geometry::LineSet<3>&) { return CollisionResult::CollisionType::LineSet; }
+CollisionResult::CollisionType TypeOf(const PrimitiveArray&) { return CollisionResult::CollisionType::Primitives; }
+
+// the capacity rule: once for the count, again with room; a refusal logs and gives no pairs
+std::shared_ptr<CollisionResult> Run(const Side& a, const Side& b, float margin, CollisionResult::CollisionType ta,
+                                     CollisionResult::CollisionType tb) {
+    auto out = std::make_shared<CollisionResult>(ta, tb);
+    int64_t m = 0;
+    if (geometry::Refused(mi_icp_collision_compute(Engine(), &a.s, &b.s, margin, nullptr, 0, &m)) || m == 0) return out;
+    out->collision_index_pairs_.resize((size_t)m);
+    Check(mi_icp_collision_compute(Engine(), &a.s, &b.s, margin, out->collision_index_pairs_.data()->data(), m, &m));
+    Check(mi_icp_synchronize(Engine()));
+    out->collision_index_pairs_.resize((size_t)m);
+    return out;
+}
+
+template <class A, class B>
+std::shared_ptr<CollisionResult> Intersect(const A& a, const B& b, float margin) {
+    Side sa, sb;
+    Fill(&sa, a);
+    Fill(&sb, b);
+    return Run(sa, sb, margin, TypeOf(a), TypeOf(b));
+}
+
+utility::device_vector<size_t> Column(const utility::device_vector<Eigen::Vector2i>& pairs, int col) {
+    const std::vector<Eigen::Vector2i> h = pairs.to_host();
+    std::vector<size_t> out(h.size());
+    for (size_t i = 0; i < h.size(); ++i) out[i] = (size_t)h[i](col);
+    return utility::device_vector<size_t>(out);
+}
+
+}  // namespace
+
+utility::device_vector<size_t> CollisionResult::GetFirstCollisionIndices() const { return Column(collision_index_pairs_, 0); }
+utility::device_vector<size_t> CollisionResult::GetSecondCollisionIndices() const { return Column(collision_index_pairs_, 1); }
+
+#define CUPOCH_AMD_INTERSECTION(A, B) \
+    std::shared_ptr<CollisionResult> ComputeIntersection(const A& a, const B& b, float margin) { return Intersect(a, b, margin); }
+CUPOCH_AMD_INTERSECTION(geometry::VoxelGrid, geometry::VoxelGrid)
+CUPOCH_AMD_INTERSECTION(geometry::VoxelGrid, geometry::LineSet<3>)
+CUPOCH_AMD_INTERSECTION(geometry::LineSet<3>, geometry::VoxelGrid)
+CUPOCH_AMD_INTERSECTION(geometry::VoxelGrid, geometry::OccupancyGrid)
+CUPOCH_AMD_INTERSECTION(geometry::OccupancyGrid, geometry::VoxelGrid)
+CUPOCH_AMD_INTERSECTION(geometry::LineSet<3>, geometry::OccupancyGrid)
+CUPOCH_AMD_INTERSECTION(geometry::OccupancyGrid, geometry::LineSet<3>)
+CUPOCH_AMD_INTERSECTION(PrimitiveArray, geometry::VoxelGrid)
+CUPOCH_AMD_INTERSECTION(geometry::VoxelGrid, PrimitiveArray)
+CUPOCH_AMD_INTERSECTION(PrimitiveArray, geometry::OccupancyGrid)
+CUPOCH_AMD_INTERSECTION(geometry::OccupancyGrid, PrimitiveArray)
+#undef CUPOCH_AMD_INTERSECTION
+
+// Intersection<TargetT>: an unsorted VoxelGrid target is sorted once, here
+template <>
+void Intersection<geometry::VoxelGrid>::Construct() {
+    const size_t m = target_.voxels_keys_.size();
+    if (target_.KeysSorted() || m < 2) return;
+    sorted_keys_.resize(m);
+    sorted_index_.resize(m);
+    int64_t mo = 0;
+    Check(mi_icp_collision_sort_keys(Engine(), KeyPtr(target_.voxels_keys_), (int64_t)m, KeyPtr(sorted_keys_), sorted_index_.data(), &mo));
+    sorted_keys_.resize((size_t)mo);
+    sorted_index_.resize((size_t)mo);
+}
+template <>
+void Intersection<geometry::OccupancyGrid>::Construct() {}
+
+namespace {
+template <class T>
+void FillTarget(Side* d, const Intersection<T>& it) {
+    Fill(d, it.target_);
+}
+template <>
+void FillTarget(Side* d, const Intersection<geometry::VoxelGrid>& it) {
+    Fill(d, it.target_);
+    if (it.sorted_keys_.empty()) return;
+    d->s.keys = KeyPtr(it.sorted_keys_);
+    d->s.keys_index = it.sorted_index_.data();
+    d->s.m = (int64_t)it.sorted_keys_.size();
+    d->s.keys_sorted = 1;
+}
+}  // namespace
+
+template <typename TargetT>
+template <typename QueryT>
+std::shared_ptr<CollisionResult> Intersection<TargetT>::Compute(const QueryT& query, float margin) const {
+    Side sa, sb;
+    FillTarget(&sa, *this);
+    Fill(&sb, query);
+    return Run(sa, sb, margin, TypeOf(target_), TypeOf(query));
+}
+template std::shared_ptr<CollisionResult> Intersection<geometry::VoxelGrid>::Compute(const geometry::VoxelGrid&, float) const;
+template std::shared_ptr<CollisionResult> Intersection<geometry::VoxelGrid>::Compute(const geometry::LineSet<3>&, float) const;
+template std::shared_ptr<CollisionResult> Intersection<geometry::VoxelGrid>::Compute(const geometry::OccupancyGrid&, float) const;
+template std::shared_ptr<CollisionResult> Intersection<geometry::VoxelGrid>::Compute(const PrimitiveArray&, float) const;
+template std::shared_ptr<CollisionResult> Intersection<geometry::OccupancyGrid>::Compute(const geometry::VoxelGrid&, float) const;
+template std::shared_ptr<CollisionResult> Intersection<geometry::OccupancyGrid>::Compute(const geometry::LineSet<3>&, float) const;
+template std::shared_ptr<CollisionResult> Intersection<geometry::OccupancyGrid>::Compute(const PrimitiveArray&, float) const;
+
+geometry::AxisAlignedBoundingBox3 Primitive::GetAxisAlignedBoundingBox() const {
+    const mi_icp_primitive r = Record(PrimitivePack(*this));
+    Eigen::Vector3f mn, mx;
+    Check(mi_icp_primitive_aabb(&r, mn.data(), mx.data()));
+    return geometry::AxisAlignedBoundingBox3(mn, mx);
+}
+
+std::shared_ptr<geometry::VoxelGrid> CreateVoxelGrid(const Primitive& primitive, float voxel_size) {
+    auto output = std::make_shared<geometry::VoxelGrid>();
+    const mi_icp_primitive r = Record(PrimitivePack(primitive));
+    int64_t m = 0;
+    Eigen::Vector3f origin;
+    if (geometry::Refused(mi_icp_collision_voxelize_primitive(Engine(), &r, voxel_size, nullptr, nullptr, 0, &m, origin.data()))) return output;
+    output->voxel_size_ = voxel_size;
+    output->origin_ = origin;
+    if (m == 0) return output;
+    utility::device_vector<Eigen::Vector3i> ok((size_t)m);
+    utility::device_vector<Eigen::Vector3f> oc((size_t)m);
+    Check(mi_icp_collision_voxelize_primitive(Engine(), &r, voxel_size, KeyPtr(ok), geometry::ColPtr(oc), m, &m, origin.data()));
+    geometry::SetVoxelArrays(output.get(), ok, oc, (size_t)m);
+    return output;
+}
+
+}  // namespace collision
+
 namespace integration {
 
 UniformTSDFVolume::UniformTSDFVolume(float length, int resolution, float sdf_trunc, TSDFVolumeColorType color_type,

@@ -30,6 +30,7 @@
 
 #include "cupoch/camera/pinhole_camera_intrinsic.h"
 #include "cupoch/camera/pinhole_camera_parameters.h"
+#include "cupoch/collision/collision.h"
 #include "cupoch/geometry/distancetransform.h"
 #include "cupoch/geometry/image.h"
 #include "cupoch/geometry/keypoint.h"
@@ -56,6 +57,14 @@ Eigen::Matrix4f to_matrix4(const farray& a) {
     Eigen::Matrix4f m;
     for (int r = 0; r < 4; ++r)
         for (int c = 0; c < 4; ++c) m(r, c) = a.at(r, c);
+    return m;
+}
+
+Eigen::Matrix3f to_matrix3(const farray& a) {
+    if (a.ndim() != 2 || a.shape(0) != 3 || a.shape(1) != 3) throw std::invalid_argument("expected a 3x3 float32 array");
+    Eigen::Matrix3f m;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) m(r, c) = a.at(r, c);
     return m;
 }
 
@@ -979,6 +988,139 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             .def_property(
                     "origin", [](const geometry::DistanceTransform& d) { return from_vector3(d.origin_); },
                     [](geometry::DistanceTransform& d, const farray& v) { d.origin_ = to_vector3(v); });
+
+    // geometry.LineSet (cupoch_pybind/geometry/lineset.cpp): points / lines / colors as numpy arrays in and out
+    typedef py::array_t<int, py::array::c_style | py::array::forcecast> iarray2;
+    py::class_<geometry::LineSet<3>, std::shared_ptr<geometry::LineSet<3>>>(mg, "LineSet")
+            .def(py::init<>())
+            .def(py::init([](const farray& points, const iarray2& lines) {
+                     auto l = std::make_shared<geometry::LineSet<3>>();
+                     l->points_ = Vector3fVector(points).data;
+                     l->lines_ = Vector2iVector(lines).data;
+                     return l;
+                 }),
+                 "points"_a, "lines"_a)
+            .def("__repr__", [](const geometry::LineSet<3>& l) { return std::string("geometry::LineSet with ") + std::to_string(l.lines_.size()) + " lines."; })
+            .def_property(
+                    "points", [](const geometry::LineSet<3>& l) { Vector3fVector v; v.data = l.points_; return v; },
+                    [](geometry::LineSet<3>& l, const Vector3fVector& v) { l.points_ = v.data; })
+            .def_property(
+                    "lines", [](const geometry::LineSet<3>& l) { Vector2iVector v; v.data = l.lines_; return v; },
+                    [](geometry::LineSet<3>& l, const Vector2iVector& v) { l.lines_ = v.data; })
+            .def_property(
+                    "colors", [](const geometry::LineSet<3>& l) { Vector3fVector v; v.data = l.colors_; return v; },
+                    [](geometry::LineSet<3>& l, const Vector3fVector& v) { l.colors_ = v.data; })
+            .def("has_points", &geometry::LineSet<3>::HasPoints)
+            .def("has_lines", &geometry::LineSet<3>::HasLines)
+            .def("has_colors", &geometry::LineSet<3>::HasColors)
+            .def("is_empty", &geometry::LineSet<3>::IsEmpty)
+            .def("clear", [](geometry::LineSet<3>& l) { l.Clear(); })
+            .def("get_min_bound", [](const geometry::LineSet<3>& l) { return from_vector3(l.GetMinBound()); })
+            .def("get_max_bound", [](const geometry::LineSet<3>& l) { return from_vector3(l.GetMaxBound()); })
+            .def("get_center", [](const geometry::LineSet<3>& l) { return from_vector3(l.GetCenter()); })
+            .def("get_axis_aligned_bounding_box", &geometry::LineSet<3>::GetAxisAlignedBoundingBox)
+            .def("get_line_coordinate",
+                 [](const geometry::LineSet<3>& l, size_t i) {
+                     const auto p = l.GetLineCoordinate(i);
+                     return py::make_tuple(from_vector3(p.first), from_vector3(p.second));
+                 },
+                 "line_index"_a)
+            .def("paint_uniform_color", [](std::shared_ptr<geometry::LineSet<3>> l, const farray& c) { l->PaintUniformColor(to_vector3(c)); return l; }, "color"_a)
+            .def("translate", [](std::shared_ptr<geometry::LineSet<3>> l, const farray& t, bool relative) { l->Translate(to_vector3(t), relative); return l; },
+                 "translation"_a, "relative"_a = true)
+            .def("scale", [](std::shared_ptr<geometry::LineSet<3>> l, float s, bool center) { l->Scale(s, center); return l; }, "scale"_a, "center"_a = true)
+            .def("rotate", [](std::shared_ptr<geometry::LineSet<3>> l, const farray& R, bool center) { l->Rotate(to_matrix3(R), center); return l; }, "R"_a, "center"_a = true)
+            .def("transform", [](std::shared_ptr<geometry::LineSet<3>> l, const farray& T) { l->Transform(to_matrix4(T)); return l; }, "transformation"_a)
+            .def_static("create_from_axis_aligned_bounding_box", &geometry::LineSet<3>::CreateFromAxisAlignedBoundingBox, "box"_a);
+
+    // ---------------------------------------------------------------- collision
+    // cupoch_pybind/collision: the primitives, PrimitiveArray, CollitionResult (the reference's spelling; CollisionResult
+    // names the same class) and compute_intersection / create_voxel_grid.  Not bound, as not built:
+    // create_voxel_grid_with_sweeping, create_triangle_mesh, Primitives x Primitives.
+    py::module mcol = m.def_submodule("collision");
+    py::class_<collision::Primitive, std::shared_ptr<collision::Primitive>> primitive(mcol, "Primitive");
+    primitive.def(py::init<>())
+            .def("get_axis_aligned_bounding_box", &collision::Primitive::GetAxisAlignedBoundingBox)
+            .def_property(
+                    "transform", [](const collision::Primitive& p) { return from_matrix4(p.transform_); },
+                    [](collision::Primitive& p, const farray& T) { p.transform_ = to_matrix4(T); })
+            .def_readonly("type", &collision::Primitive::type_);
+    py::enum_<collision::Primitive::PrimitiveType>(primitive, "Type")
+            .value("Unspecified", collision::Primitive::PrimitiveType::Unspecified)
+            .value("Box", collision::Primitive::PrimitiveType::Box)
+            .value("Sphere", collision::Primitive::PrimitiveType::Sphere)
+            .value("Capsule", collision::Primitive::PrimitiveType::Capsule)
+            .value("Cylinder", collision::Primitive::PrimitiveType::Cylinder)
+            .value("Mesh", collision::Primitive::PrimitiveType::Mesh);
+    py::class_<collision::Box, std::shared_ptr<collision::Box>, collision::Primitive>(mcol, "Box")
+            .def(py::init([](const farray& lengths) { return std::make_shared<collision::Box>(to_vector3(lengths)); }), "lengths"_a)
+            .def(py::init([](const farray& lengths, const farray& T) { return std::make_shared<collision::Box>(to_vector3(lengths), to_matrix4(T)); }),
+                 "lengths"_a, "transform"_a)
+            .def_property(
+                    "lengths", [](const collision::Box& b) { return from_vector3(b.lengths_); },
+                    [](collision::Box& b, const farray& v) { b.lengths_ = to_vector3(v); });
+    py::class_<collision::Sphere, std::shared_ptr<collision::Sphere>, collision::Primitive>(mcol, "Sphere")
+            .def(py::init<float>(), "radius"_a)
+            .def(py::init([](float radius, const farray& c) { return std::make_shared<collision::Sphere>(radius, to_vector3(c)); }), "radius"_a, "center"_a)
+            .def_readwrite("radius", &collision::Sphere::radius_);
+    py::class_<collision::Capsule, std::shared_ptr<collision::Capsule>, collision::Primitive>(mcol, "Capsule")
+            .def(py::init<float, float>(), "radius"_a, "height"_a)
+            .def(py::init([](float r, float h, const farray& T) { return std::make_shared<collision::Capsule>(r, h, to_matrix4(T)); }), "radius"_a,
+                 "height"_a, "transform"_a)
+            .def_readwrite("radius", &collision::Capsule::radius_)
+            .def_readwrite("height", &collision::Capsule::height_);
+    py::class_<collision::Cylinder, std::shared_ptr<collision::Cylinder>, collision::Primitive>(mcol, "Cylinder")
+            .def(py::init<float, float>(), "radius"_a, "height"_a)
+            .def(py::init([](float r, float h, const farray& T) { return std::make_shared<collision::Cylinder>(r, h, to_matrix4(T)); }), "radius"_a,
+                 "height"_a, "transform"_a)
+            .def_readwrite("radius", &collision::Cylinder::radius_)
+            .def_readwrite("height", &collision::Cylinder::height_);
+    struct PrimitiveArrayBox {
+        collision::PrimitiveArray data;
+    };
+    py::class_<PrimitiveArrayBox>(mcol, "PrimitiveArray")
+            .def(py::init<>())
+            .def("append", [](PrimitiveArrayBox& a, const collision::Primitive& p) { a.data.push_back(collision::PrimitivePack(p)); }, "primitive"_a)
+            .def("__len__", [](const PrimitiveArrayBox& a) { return a.data.size(); });
+    py::class_<collision::CollisionResult, std::shared_ptr<collision::CollisionResult>> col_res(mcol, "CollitionResult");
+    col_res.def(py::init<>())
+            .def("is_collided", &collision::CollisionResult::IsCollided)
+            .def("__repr__",
+                 [](const collision::CollisionResult& r) {
+                     return std::string("collision::CollisionResult with ") + std::to_string(r.collision_index_pairs_.size()) + " collisions.";
+                 })
+            .def("get_collision_index_pairs", [](const collision::CollisionResult& r) { return corres_to_array(r.collision_index_pairs_); })
+            .def("get_first_collision_indices", [](const collision::CollisionResult& r) { ULongVector v; v.data = r.GetFirstCollisionIndices(); return v; })
+            .def("get_second_collision_indices", [](const collision::CollisionResult& r) { ULongVector v; v.data = r.GetSecondCollisionIndices(); return v; })
+            .def_readwrite("first", &collision::CollisionResult::first_)
+            .def_readwrite("second", &collision::CollisionResult::second_)
+            .def_property(
+                    "collision_index_pairs", [](const collision::CollisionResult& r) { Vector2iVector v; v.data = r.collision_index_pairs_; return v; },
+                    [](collision::CollisionResult& r, const Vector2iVector& v) { r.collision_index_pairs_ = v.data; });
+    mcol.attr("CollisionResult") = mcol.attr("CollitionResult");
+    py::enum_<collision::CollisionResult::CollisionType>(col_res, "Type")
+            .value("Unspecified", collision::CollisionResult::CollisionType::Unspecified)
+            .value("Primitives", collision::CollisionResult::CollisionType::Primitives)
+            .value("VoxelGrid", collision::CollisionResult::CollisionType::VoxelGrid)
+            .value("OccupancyGrid", collision::CollisionResult::CollisionType::OccupancyGrid)
+            .value("LineSet", collision::CollisionResult::CollisionType::LineSet);
+#define CUPOCH_AMD_BIND(A, B, NA, NB, GA, GB)                                                                              \
+    mcol.def("compute_intersection",                                                                                       \
+             [](const A& a, const B& b, float margin) { return collision::ComputeIntersection(GA, GB, margin); }, NA##_a, NB##_a, \
+             "margin"_a = 0.0f)
+    CUPOCH_AMD_BIND(geometry::VoxelGrid, geometry::VoxelGrid, "voxelgrid1", "voxelgrid2", a, b);
+    CUPOCH_AMD_BIND(geometry::VoxelGrid, geometry::LineSet<3>, "voxelgrid", "lineset", a, b);
+    CUPOCH_AMD_BIND(geometry::LineSet<3>, geometry::VoxelGrid, "lineset", "voxelgrid", a, b);
+    CUPOCH_AMD_BIND(geometry::VoxelGrid, geometry::OccupancyGrid, "voxelgrid", "occgrid", a, b);
+    CUPOCH_AMD_BIND(geometry::OccupancyGrid, geometry::VoxelGrid, "occgrid", "voxelgrid", a, b);
+    CUPOCH_AMD_BIND(geometry::LineSet<3>, geometry::OccupancyGrid, "lineset", "occgrid", a, b);
+    CUPOCH_AMD_BIND(geometry::OccupancyGrid, geometry::LineSet<3>, "occgrid", "lineset", a, b);
+    CUPOCH_AMD_BIND(PrimitiveArrayBox, geometry::VoxelGrid, "primitives", "voxelgrid", a.data, b);
+    CUPOCH_AMD_BIND(geometry::VoxelGrid, PrimitiveArrayBox, "voxelgrid", "primitives", a, b.data);
+    CUPOCH_AMD_BIND(PrimitiveArrayBox, geometry::OccupancyGrid, "primitives", "occgrid", a.data, b);
+    CUPOCH_AMD_BIND(geometry::OccupancyGrid, PrimitiveArrayBox, "occgrid", "primitives", a, b.data);
+#undef CUPOCH_AMD_BIND
+    mcol.def("create_voxel_grid", &collision::CreateVoxelGrid, "primitive"_a, "voxel_size"_a);
 
     // ---------------------------------------------------------------- integration
     // cupoch_pybind/integration/integration.cpp: TSDFVolumeColorType and UniformTSDFVolume with the reference's names.

@@ -10,6 +10,7 @@
 //   mi_occgrid.hip   OccupancyGrid
 //   mi_edt.hip       DistanceTransform
 //   mi_voxelgrid.hip VoxelGrid (from points, dense, merge, carve, query, bounds, selections, paint)
+//   mi_collision.hip collision::ComputeIntersection (grids against grids, line sets, primitives), CreateVoxelGrid
 //   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry,
 //                    RemoveStatisticalOutliers / RemoveRadiusOutliers, ClusterDBSCAN, ComputeISSKeypoints
 //   mi_comm.hip      the ranks' exchange: mailbox, device inboxes, in-library RCCL, self-test and choice
@@ -525,6 +526,14 @@ void tsdf_release_all(mi_icp_ctx* c);     // mi_icp_destroy: the volumes of mi_i
 void occgrid_release_all(mi_icp_ctx* c);  // mi_icp_destroy: the grids of mi_icp_occgrid_create
 // a grid's log-odds plane, resolution and inclusive bounds (min[3], max[3]) for a reader on the device
 int occgrid_view(mi_icp_ctx* c, const mi_icp_occgrid* o, const char* what, const float** prob, int* resolution, int* bounds6);
+// ---- mi_voxelgrid.hip
+struct VgRuns {
+    const uint32_t* order = nullptr;      // sorted position -> entry of keys3
+    const uint32_t* run_start = nullptr;  // [nvox + 1]
+    int64_t nvox = 0;
+};
+// the stable order of keys3[n][3] and its runs of equal keys (in the context's sort and scan buffers); waits twice
+int vg_sort_runs(mi_icp_ctx* c, const int32_t* keys3, int64_t n, VgRuns* r);
 // ---- mi_edt.hip
 void dt_release_all(mi_icp_ctx* c);       // mi_icp_destroy: the transforms of mi_icp_dt_create
 // ---- mi_geometry.hip

@@ -38,16 +38,10 @@ static int bit_length(uint64_t v) {
     return b;
 }
 
-struct VgRuns {
-    const uint32_t* order = nullptr;      // sorted position -> entry of keys3
-    const uint32_t* run_start = nullptr;  // [nvox + 1]
-    int64_t nvox = 0;
-};
-
 // Brings equal keys together: keys3[n][3] on the device (x == kVgNoKey: the entry does not count) -> the stable order,
 // the runs of equal keys and their number.  Two waits: the extents of the keys size the packed key (the sort's passes),
 // the number of runs sizes the caller's output.  Extents that need more than 64 bits together take two sorts.
-static int vg_sort_runs(mi_icp_ctx* c, const int32_t* keys3, int64_t n, VgRuns* r) {
+int mi::eng::vg_sort_runs(mi_icp_ctx* c, const int32_t* keys3, int64_t n, VgRuns* r) {
     *r = VgRuns();
     if (n == 0) return MI_ICP_OK;
     int32_t *part, *bnd;

@@ -1029,6 +1029,72 @@ class Engine:
                                                  self._f3(color)))
         self.synchronize()   # (idx may go)
 
+    # -- collision (include/mi_icp.h; a side is built by one of the four makers below and keeps its tensors alive) ----
+    def collision_voxel_side(self, keys, voxel_size, origin, keys_sorted=False):
+        s = _lib.CollisionSide()
+        k = self._vg_dev(keys, np.int32)
+        s.kind, s.keys_sorted, s.m = _lib.COLLISION_VOXELGRID, int(bool(keys_sorted)), int(k.shape[0])
+        s.keys = k.data_ptr() if s.m else None
+        s.voxel_size = float(voxel_size)
+        s.origin[:] = [float(v) for v in np.asarray(origin, np.float32).reshape(3)]
+        return s, (k,)
+
+    @staticmethod
+    def collision_occgrid_side(grid, params):
+        s = _lib.CollisionSide()
+        s.kind, s.grid_params = _lib.COLLISION_OCCGRID, params
+        s.grid = grid.value if isinstance(grid, C.c_void_p) else grid
+        return s, (grid, params)
+
+    def collision_lineset_side(self, points, lines):
+        s = _lib.CollisionSide()
+        p, l = self._vg_dev(points, np.float32), self._vg_dev(lines, np.int32, 2)
+        s.kind, s.n_points, s.n_lines = _lib.COLLISION_LINESET, int(p.shape[0]), int(l.shape[0])
+        s.points = p.data_ptr() if s.n_points else None
+        s.lines = l.data_ptr() if s.n_lines else None
+        return s, (p, l)
+
+    def collision_primitives_side(self, records):
+        """records: numpy structured array / bytes of 80-byte mi_icp_primitive records"""
+        s = _lib.CollisionSide()
+        raw = np.ascontiguousarray(np.frombuffer(np.ascontiguousarray(records).tobytes(), np.uint8))
+        n = raw.size // C.sizeof(_lib.Primitive)
+        t = torch.from_numpy(raw.copy()).to(torch.device("cuda", self.device))
+        s.kind, s.n_primitives = _lib.COLLISION_PRIMITIVES, n
+        s.primitives = t.data_ptr() if n else None
+        return s, (t,)
+
+    def collision_compute(self, side_a, side_b, margin=0.0, first_capacity=None):
+        """-> pairs [m, 2] int32 on the device (mi_icp_collision_compute); the capacity rule of include/mi_icp.h"""
+        (a, keep_a), (b, keep_b) = side_a, side_b
+        dev = torch.device("cuda", self.device)
+        m = C.c_int64(0)
+        capacity = max(int(first_capacity if first_capacity is not None else 1 << 16), 1)
+        for _ in range(2):
+            pairs, pp = self._out(MI_ICP_DEVICE, dev, (capacity, 2), np.int32)
+            self._chk(self._L.mi_icp_collision_compute(self._ctx, C.byref(a), C.byref(b), float(margin), pp, capacity, C.byref(m)))
+            if int(m.value) <= capacity:
+                break
+            capacity = int(m.value)
+        self.synchronize()   # (uploaded inputs may go)
+        del keep_a, keep_b
+        return pairs[:int(m.value)]
+
+    def collision_voxelize_primitive(self, record, voxel_size):
+        """-> (keys [m, 3] int32 ascending, colors [m, 3], origin [3] numpy) (mi_icp_collision_voxelize_primitive)"""
+        P = _lib.Primitive.from_buffer_copy(np.ascontiguousarray(record).tobytes())
+        origin = (C.c_float * 3)()
+        keys, cols = self._vg_counted(1 << 16, lambda kp, cp, cap, m: self._L.mi_icp_collision_voxelize_primitive(
+            self._ctx, C.byref(P), float(voxel_size), kp, cp, cap, m, origin))
+        return keys, cols, np.array(list(origin), np.float32)
+
+    @staticmethod
+    def primitive_aabb(record):
+        P = _lib.Primitive.from_buffer_copy(np.ascontiguousarray(record).tobytes())
+        lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        _lib.load().mi_icp_primitive_aabb(C.byref(P), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p))
+        return lo, hi
+
     def compute_rgbd_odometry(self, source_color, source_depth, target_color, target_depth, intrinsic4,
                               odo_init=None, jacobian=1, iterations=(20, 10, 5), max_depth_diff=0.03,
                               min_depth=0.0, max_depth=4.0, weighted=False, prev_twist=None, nu=5.0,

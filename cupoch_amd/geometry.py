@@ -6,10 +6,12 @@ OccupancyGrid / OccupancyVoxel mirror geometry/occupancygrid.h:31-142 (python su
 src/python/cupoch_pybind/geometry/occupancygrid.cpp); not built: OccupancyGrid.create_from_voxel_grid.
 Voxel / VoxelGrid mirror geometry/voxelgrid.h:48-214 (python surface src/python/cupoch_pybind/geometry/voxelgrid.cpp);
 not built: create_from_triangle_mesh[_within_bounds] (no TriangleMesh here), get_oriented_bounding_box, VoxelGrid file
-I/O, visualisation and collision.
+I/O and visualisation.  The collision queries on both grid types are cupoch_amd.collision.
 DistanceVoxel / DistanceTransform mirror geometry/distancetransform.h:30-78 (python surface
-src/python/cupoch_pybind/geometry/distancetransform.cpp); not built: the collision, planning and visualisation
-consumers of a transform."""
+src/python/cupoch_pybind/geometry/distancetransform.cpp); not built: the planning and visualisation consumers of a
+transform, and a transform as a collision target.
+LineSet mirrors geometry/lineset.h (LineSet<3>; python surface src/python/cupoch_pybind/geometry/lineset.cpp); not
+built: the factories from meshes, clouds with correspondences and oriented boxes, and file I/O."""
 import sys
 
 import numpy as np
@@ -1292,5 +1294,131 @@ class DistanceTransform:
         return out.compute_edt(input)
 
 
+class LineSet:
+    """geometry::LineSet<3> (lineset.h): points float32 [n, 3], lines int32 [l, 2] (point indices) and optional colours
+    float32 [l, 3], one per line, as device vectors.  The bounds and the moves are the point cloud's, through the same
+    entry points."""
+
+    def __init__(self, points=None, lines=None):
+        self._points = utility.Vector3fVector() if points is None else _v3(points)
+        self._lines = utility.Vector2iVector() if lines is None else _v2i(lines)
+        self._colors = None
+
+    @property
+    def points(self):
+        return self._points
+
+    @points.setter
+    def points(self, v):
+        self._points = _v3(v)
+
+    @property
+    def lines(self):
+        return self._lines
+
+    @lines.setter
+    def lines(self, v):
+        self._lines = _v2i(v)
+
+    @property
+    def colors(self):
+        return self._colors if self._colors is not None else utility.Vector3fVector()
+
+    @colors.setter
+    def colors(self, v):
+        self._colors = _v3(v)
+
+    def has_points(self):
+        return len(self._points) > 0
+
+    def has_lines(self):
+        return self.has_points() and len(self._lines) > 0
+
+    def has_colors(self):
+        return self.has_lines() and self._colors is not None and len(self._colors) == len(self._lines)
+
+    def is_empty(self):
+        return not self.has_points()
+
+    def clear(self):
+        self._points, self._lines, self._colors = utility.Vector3fVector(), utility.Vector2iVector(), None
+        return self
+
+    def __repr__(self):
+        return "geometry::LineSet with %d lines." % len(self._lines)
+
+    def _engine(self):
+        return get_engine(self._points.tensor.device.index if self._points.tensor.is_cuda else None)
+
+    def _bounds(self):
+        return self._engine().compute_bounds(self._points.tensor)
+
+    def get_min_bound(self):
+        return self._bounds()[0]
+
+    def get_max_bound(self):
+        return self._bounds()[1]
+
+    def get_center(self):
+        return self._bounds()[2]
+
+    def get_axis_aligned_bounding_box(self):
+        mn, mx, _ = self._bounds()
+        return AxisAlignedBoundingBox(mn, mx)
+
+    def get_line_coordinate(self, line_index):
+        """-> the two end points of a line (numpy [3] each); zeros for an index, of the line or of a point, that is out
+        of range, as the C++ surface gives"""
+        i = int(line_index)
+        zero = np.zeros(3, np.float32)
+        if not 0 <= i < len(self._lines):
+            return zero, zero.copy()
+        a, b = [int(v) for v in self._lines.tensor[i].cpu().numpy()]
+        if not (0 <= a < len(self._points) and 0 <= b < len(self._points)):
+            return zero, zero.copy()
+        p = self._points.tensor[[a, b]].cpu().numpy()
+        return p[0], p[1]
+
+    def paint_uniform_color(self, color):
+        c = np.asarray(color, np.float32).reshape(1, 3)
+        self._colors = utility.Vector3fVector(np.repeat(c, len(self._lines), axis=0))
+        return self
+
+    def translate(self, translation, relative=True):
+        t = np.asarray(translation, np.float32).reshape(3)
+        if not relative:
+            t = (t - self.get_center()).astype(np.float32)
+        self._engine().affine(self._points.tensor, translate=t)
+        return self
+
+    def scale(self, scale, center=True):
+        c = self.get_center() if center and len(self._points) else None
+        self._engine().affine(self._points.tensor, scale=float(scale), center=c)
+        return self
+
+    def rotate(self, R, center=True):
+        c = self.get_center() if center and len(self._points) else None
+        self._engine().affine(self._points.tensor, R=np.asarray(R, np.float32).reshape(3, 3), center=c)
+        return self
+
+    def transform(self, transformation):
+        self._engine().transform(np.asarray(transformation, np.float32), self._points.tensor, None, None)
+        return self
+
+    _BOX_LINES = ((0, 1), (1, 2), (2, 3), (3, 0), (4, 5), (5, 6), (6, 7), (7, 4), (0, 4), (1, 5), (2, 6), (3, 7))
+
+    @staticmethod
+    def create_from_axis_aligned_bounding_box(box):
+        """the twelve edges of a box: corners in the order (x, y, z) = (min|max) with x fastest on each z face"""
+        lo, hi = np.asarray(box.get_min_bound(), np.float32), np.asarray(box.get_max_bound(), np.float32)
+        corners = np.array([[lo[0], lo[1], lo[2]], [hi[0], lo[1], lo[2]], [hi[0], hi[1], lo[2]], [lo[0], hi[1], lo[2]],
+                            [lo[0], lo[1], hi[2]], [hi[0], lo[1], hi[2]], [hi[0], hi[1], hi[2]], [lo[0], hi[1], hi[2]]], np.float32)
+        return LineSet(corners, np.array(LineSet._BOX_LINES, np.int32))
+
+
 def _v3(v):
     return v if isinstance(v, utility.Vector3fVector) else utility.Vector3fVector(v)
+
+
+def _v2i(v):
+    return v if isinstance(v, utility.Vector2iVector) else utility.Vector2iVector(v)

@@ -792,8 +792,8 @@ MI_ICP_API int mi_icp_tsdf_get_voxels(mi_icp_ctx* ctx, mi_icp_tsdf* volume, floa
  * context that made it: destroyed with mi_icp_occgrid_destroy, or with the context.  Stored as the
  * log-odds plane alone, 4 bytes per voxel (the reference keeps 24: a grid index that is the voxel's
  * position and a colour it never writes, always (0, 0, 1)), beside a one-byte mark per voxel that is
- * zero between calls.  Not built: CreateFromVoxelGrid and the collision consumers.  The distance field of
- * the occupied voxels is geometry::DistanceTransform (mi_icp_dt_compute_occgrid, below).
+ * zero between calls.  Not built: CreateFromVoxelGrid.  The collision queries are mi_icp_collision_compute
+ * (below).  The distance field of the occupied voxels is geometry::DistanceTransform (mi_icp_dt_compute_occgrid, below).
  * The occupied space leaves the library as a geometry::VoxelGrid (VoxelGrid::CreateFromOccupancyGrid, below).
  *
  * ARRAYS ARE DEVICE POINTERS; there is no memory-kind argument in this family (the preamble's one
@@ -894,7 +894,8 @@ MI_ICP_API int mi_icp_occgrid_get_voxels(mi_icp_ctx* ctx, mi_icp_occgrid* grid, 
  * between calls.  Every producer below emits keys DISTINCT and ASCENDING lexicographically, x most
  * significant (the reference's operator< on Vector3i, utility/helper.h:114).  Not built:
  * CreateFromTriangleMesh[WithinBounds] (no TriangleMesh here), GetOrientedBoundingBox, file I/O,
- * visualisation, collision; OccupancyGrid::CreateFromVoxelGrid and UniformTSDFVolume::ExtractVoxelGrid.
+ * visualisation; OccupancyGrid::CreateFromVoxelGrid and UniformTSDFVolume::ExtractVoxelGrid.  The collision
+ * queries are mi_icp_collision_compute (below).
  * The distance field of a grid's voxels is geometry::DistanceTransform (mi_icp_dt_compute_voxelgrid, below).
  *
  * ARRAYS ARE DEVICE POINTERS; there is no memory-kind argument in this family (the preamble's
@@ -989,7 +990,7 @@ MI_ICP_API int mi_icp_voxelgrid_paint(mi_icp_ctx* ctx, float* colors, int64_t m,
  * the context.  Stored as one 32-bit word per cell -- the nearest site's three 10-bit coordinates and two
  * state bits, hence the cap of 1024 -- in two planes: 8 bytes per cell, 8 GiB at 1024^3, 1 GiB at 512^3
  * (the reference keeps a 12-byte record and a buffer of the same size beside it).  Not built: the
- * collision, planning and visualisation consumers of a transform.
+ * planning and visualisation consumers of a transform; the collision family (below) takes grids, not transforms.
  *
  * ARRAYS ARE DEVICE POINTERS; there is no memory-kind argument in this family (the preamble's
  * exception).  voxel_size, the origins, the threshold and the counts are host memory or values.
@@ -1046,6 +1047,143 @@ MI_ICP_API int mi_icp_dt_query(mi_icp_ctx* ctx, mi_icp_dt* dt, float voxel_size,
                                const float* queries, int64_t n, float* out_distance, int32_t* out_nearest);
 MI_ICP_API int mi_icp_dt_get_voxels(mi_icp_ctx* ctx, mi_icp_dt* dt, float voxel_size, int32_t* out_nearest,
                                     float* out_distance);
+
+/* ---- collision (collision/{collision,primitives}.{h,cu}) ------------------------------------------------
+ * ComputeIntersection between a grid (geometry::VoxelGrid keys, or an OccupancyGrid of this context) and
+ * another grid, a LineSet or an array of primitives, and CreateVoxelGrid of one primitive.  The reference
+ * walks an LBVH over the target with a per-thread buffer of 10,000 hits; here the target is addressed
+ * directly -- a binary search in the ascending keys, or the dense log-odds plane -- so the structure is "the
+ * cells near the query".  Not built: Primitives x Primitives (declared, never defined in the reference),
+ * CreateVoxelGridWithSweeping, CreateTriangleMesh, Mesh primitives, a DistanceTransform as a target, and the
+ * planning and kinematics modules that call these.
+ *
+ * ARRAYS ARE DEVICE POINTERS (keys, points, lines, primitive records, out_pairs, out_keys, out_colors); the
+ * side structs, the one primitive of voxelize_primitive, margin, counts are host memory.
+ *
+ * NUMERIC CONTRACT.  fp32 in exactly the order written; products are never fused.  tests/collision_exact.py
+ * restates it in numpy, csrc/collision_predicates.h is the code.
+ *  CELL BOX.  A VoxelGrid voxel with key k: lo = (float)k * vs + origin, hi = (float)(k + 1) * vs + origin
+ *   per axis.  An OccupancyGrid voxel with index g: the same with k = g - h, h = resolution / 2 -- the
+ *   position the grid's own extract and query use, everywhere (the reference uses the shifted origin for
+ *   its tree and the unshifted one for its exact tests).  Centre c = (lo + hi) * 0.5f, half extent e = hi -
+ *   c.  A margin inflates a cell to lo - margin, hi + margin; against a box primitive it is added to e,
+ *   against a sphere or capsule to the radius.  An occupancy grid's voxels are those
+ *   mi_icp_occgrid_extract(MI_ICP_OCCGRID_OCCUPIED) lists; their index in a pair is (x*res + y)*res + z.
+ *  PREDICATES, all closed (touching counts).
+ *   cell-cell: per axis a.lo <= b.hi && b.lo <= a.hi, the ENUMERATED side's cell inflated.  Two grids on
+ *    one lattice collide on all 26 neighbours at margin 0 (lbvh::intersects does the same).
+ *   segment-cell: LineSegmentAABB (intersection_test.inl:93-118) on the inflated cell: center = (lo + hi)
+ *    * 0.5f, ext = hi - center, mid = (p0 + p1) * 0.5f, dst = p1 - mid, mid -= center; reject if |mid_i| >
+ *    ext_i + |dst_i|; |dst| += FLT_EPSILON; reject on the cross axes (1,2), (2,0), (0,1):
+ *    |mid_a*dst_b - mid_b*dst_a| > ext_a*|dst|_b + ext_b*|dst|_a.
+ *   sphere-cell: e_i = max(max(lo_i - q_i, q_i - hi_i), 0), d2 = (e0*e0 + e1*e1) + e2*e2, hit iff d2 <=
+ *    (radius + margin)^2 with the sum squared as one product; q is the transform's translation.
+ *   box-cell: fifteen separating axes.  R[i][j] = rot[j][i] (the box's axes are the columns of its
+ *    rotation), dc = c_cell - translation, t_i = (R[i][0]*dc0 + R[i][1]*dc1) + R[i][2]*dc2 (the reference
+ *    multiplies by rot, right only for symmetric rotations); A = |R| + FLT_EPSILON, ea = lengths * 0.5f,
+ *    eb = e + margin; reject if |t_i| > ea_i + ((eb0*A[i][0] + eb1*A[i][1]) + eb2*A[i][2]); reject if
+ *    |(t0*R[0][j] + t1*R[1][j]) + t2*R[2][j]| > ((ea0*A[0][j] + ea1*A[1][j]) + ea2*A[2][j]) + eb_j; for
+ *    i, j row-major, i1 = (i+1)%3, i2 = (i+2)%3, j1, j2 likewise, reject if |t[i2]*R[i1][j] -
+ *    t[i1]*R[i2][j]| > (ea[i1]*A[i2][j] + ea[i2]*A[i1][j]) + (eb[j1]*A[i][j2] + eb[j2]*A[i][j1]).
+ *    A box with finite fields whose rotation is not orthonormal within 1e-4 (max |rot^T rot - I|, columns
+ *    dotted (x*x + y*y) + z*z), e.g. a scaled transform, is MI_ICP_ERR_INVALID with nothing written, in
+ *    compute and in voxelize_primitive: the candidate cells below are bounded for such rotations only.
+ *   capsule-cell: z = the rotation's third column, p = translation - (0.5f*height)*z, d = height*z; hit
+ *    iff min over 34 parameters t of the sphere rule's d2 at q = p + t*d is <= (radius + margin)^2.  Each
+ *    t is clamped to [0, 1], a t that is not finite counts as 0.  In order: 0; 1; (b_a - p_a) / d_a for a
+ *    = 0..2, b = lo then hi; then for the 26 non-empty choices per axis of {inactive, lo, hi},
+ *    lexicographic with axis 0 most significant, t = -(sum_a d_a*(p_a - b_a)) / (sum_a d_a*d_a) over the
+ *    active axes, both sums from 0 in axis order.  (CapsuleAABB of the reference returns true for every
+ *    corner case; not restated.)
+ *   NEVER COLLIDING: Cylinder, Mesh and Unspecified primitives (as in the reference); a primitive with a
+ *    field that is not finite; a line with an end point that is not finite.  A line whose point index is
+ *    outside [0, n_points) is MI_ICP_ERR_INVALID with nothing written.  margin must be finite and >= 0.
+ *  RESULT.  pairs int32[m][2], column 0 indexes A, column 1 indexes B (the reference swaps the columns of
+ *   its Primitives-first overloads).  One side is ENUMERATED: the lines whenever a LineSet is either
+ *   argument, else B.  Every enumerated element that collides gives exactly one pair; the other column is
+ *   the SMALLEST index of the other side the predicate accepts (the reference: whichever its tree walk met
+ *   first).  Pairs ascend in the enumerated index.  THE CAPACITY RULE: *m is the count; with capacity <
+ *   *m nothing is written.  An empty side: m = 0 without a launch.
+ *   Pairs built: VoxelGrid x VoxelGrid; VoxelGrid x OccupancyGrid and the reverse; {VoxelGrid,
+ *   OccupancyGrid} x LineSet and the reverse; {VoxelGrid, OccupancyGrid} x Primitives and the reverse.
+ *   Every other pair of kinds is MI_ICP_ERR_INVALID.  A VoxelGrid side with keys_sorted == 0 that is NOT
+ *   enumerated is sorted once into scratch with its permutation (equal keys: the smallest index stands);
+ *   with keys_index the caller passes such a sorted copy and the pairs name keys_index[i].
+ *  CANDIDATE CELLS.  For an enumerated voxel the other grid's cells that meet its inflated box are found
+ *   EXACTLY: lo and hi above are non-decreasing in k, so the keys with b.hi >= a.lo are all keys from some
+ *   key on, those with b.lo <= a.hi all keys up to some key, and a binary search finds both ends: no slack.
+ *   For a line or primitive the cells are those that meet its bounds (margin included) widened by
+ *   s = 1e-5 * M + 1e-30, M the largest magnitude of a bound: the predicates' axis tests are that overlap
+ *   in fp32 through at most a dozen roundings, below 2e-6 * M.  A box primitive's half widths get a further
+ *   1e-3 of the largest of them and of the cell size, for the rotation's tolerance.  A line is taken one
+ *   x-slab at a time: the parameter interval in which it is inside the slab (widened by 8 * FLT_EPSILON *
+ *   (|x0| + |x_slab| + |dx|) / |dx|, the whole line when that is not finite) bounds its y and z there.
+ *   Because segment-cell adds FLT_EPSILON to |dst| before its cross-axis tests, the line may pass an
+ *   accepted cell at FLT_EPSILON * (ext_0 + ext_a) / |dst_0|; that span is therefore widened by 4 *
+ *   FLT_EPSILON * (vs + 2 margin) / |dx| (twice the bound) and, for the products' rounding, by 16 *
+ *   FLT_EPSILON * ((vs + 2 margin) * |d_a| / |dx| + |d_a| + vs + 2 margin); a segment with |dx| <= 1e-5 *
+ *   (|x0| + |x1|) takes its whole y / z range; the result is cut to the segment's whole bounds, which the
+ *   three opening rejects enforce (csrc/collision_predicates.h, segment_slab_cells).
+ *   Ranges are clamped to the occupancy grid's bounds box or to the VoxelGrid's key extents; a searched
+ *   key whose x is INT32_MIN is no key.  k + 1 and the like are computed in 64 bits.
+ *  voxelize_primitive(primitive, voxel_size)  CreateVoxelGrid (primitives.cu:238-265).  origin = the
+ *   translation (*out_origin3).  [mn, mx] = GetAxisAlignedBoundingBox; per axis min_b = (mn - origin) -
+ *   vs*0.5f, max_b = (mx - origin) + vs*0.5f, num = (int)roundf((max_b - min_b) / vs).  idx -> (w, h, d) =
+ *   (idx/(nh*nd) - nw/2, (idx%(nh*nd))/nd - nh/2, idx%nd - nd/2); the cell is kept iff the primitive with
+ *   its translation set to zero collides with the cell box of key (w, h, d) at origin 0, margin 0.  Keys
+ *   ascend; colours (1, 1, 1).  Refused: voxel_size <= 0 or not finite, a type other than Box, Sphere,
+ *   Capsule, a field that is not finite, a box's rotation that is not orthonormal, more than 2^31 - 1 cells.
+ *  GetAxisAlignedBoundingBox (host, mi_icp_primitive_aabb): Box translation -+ |rot| * (lengths * 0.5f),
+ *   row sums left to right (the reference takes |rot * half|, a bound for axis-aligned boxes only);
+ *   Sphere -+ radius; Capsule pa = z * (0.5f*height), (min(pa, -pa) - radius) + translation and (max(pa,
+ *   -pa) + radius) + translation; Cylinder the reference's formula with max in the max bound (it writes
+ *   min); other types zeros.
+ * Waits: compute waits once for the count (twice more when it sorts a VoxelGrid, once more when it lists an
+ * occupancy grid, once more to check a LineSet's indices or a primitive array's boxes); voxelize_primitive
+ * once; sort_keys twice. */
+#define MI_ICP_PRIMITIVE_UNSPECIFIED 0
+#define MI_ICP_PRIMITIVE_BOX 1
+#define MI_ICP_PRIMITIVE_SPHERE 2
+#define MI_ICP_PRIMITIVE_CAPSULE 3
+#define MI_ICP_PRIMITIVE_CYLINDER 4
+#define MI_ICP_PRIMITIVE_MESH 5
+typedef struct mi_icp_primitive { /* 80 bytes */
+    int32_t type;
+    float transform[16]; /* column-major, as extrinsic16 is */
+    float param[3];      /* Box: lengths; Sphere: radius; Capsule, Cylinder: radius, height */
+} mi_icp_primitive;
+#define MI_ICP_COLLISION_VOXELGRID 1
+#define MI_ICP_COLLISION_OCCGRID 2
+#define MI_ICP_COLLISION_LINESET 3
+#define MI_ICP_COLLISION_PRIMITIVES 4
+typedef struct mi_icp_collision_side {
+    int32_t kind;        /* MI_ICP_COLLISION_*: which of the groups below is read */
+    int32_t keys_sorted; /* VOXELGRID: keys ascend and are distinct */
+    const int32_t* keys; /* VOXELGRID: int32[m][3] */
+    const int32_t* keys_index; /* NULL, or with keys_sorted: the index reported for keys[i] (mi_icp_collision_sort_keys) */
+    int64_t m;
+    float voxel_size;    /* VOXELGRID */
+    float origin[3];
+    const mi_icp_occgrid* grid;        /* OCCGRID */
+    mi_icp_occgrid_params grid_params; /* (voxel_size, origin and occ_prob_thres_log are read) */
+    const float* points;  /* LINESET: float[n_points][3] */
+    int64_t n_points;
+    const int32_t* lines; /* int32[n_lines][2] */
+    int64_t n_lines;
+    const mi_icp_primitive* primitives; /* PRIMITIVES: [n_primitives] */
+    int64_t n_primitives;
+} mi_icp_collision_side;
+MI_ICP_API int mi_icp_collision_compute(mi_icp_ctx* ctx, const mi_icp_collision_side* a, const mi_icp_collision_side* b,
+                                        float margin, int32_t* out_pairs, int64_t capacity, int64_t* m);
+MI_ICP_API int mi_icp_collision_voxelize_primitive(mi_icp_ctx* ctx, const mi_icp_primitive* primitive, float voxel_size,
+                                                   int32_t* out_keys, float* out_colors, int64_t capacity, int64_t* m,
+                                                   float* out_origin3);
+/* The distinct keys of keys[m], ascending, and for each the smallest index it has in keys: what compute makes of a
+ * searched VoxelGrid side with keys_sorted == 0, for a caller that asks many queries of one grid.  out arrays of m
+ * entries; waits twice. */
+MI_ICP_API int mi_icp_collision_sort_keys(mi_icp_ctx* ctx, const int32_t* keys, int64_t m, int32_t* out_keys,
+                                          int32_t* out_index, int64_t* m_out);
+MI_ICP_API int mi_icp_primitive_aabb(const mi_icp_primitive* primitive, float* out_min3, float* out_max3);
 
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
