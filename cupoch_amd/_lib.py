@@ -18,7 +18,7 @@ INCLUDE = os.path.join(ROOT, "include")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I/opt/rocm/include"]
 # the library's translation units (csrc/ctx.h says what each holds); compiled side by side, then linked
-UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_occgrid", "mi_voxelgrid", "mi_collision", "mi_edt", "mi_knn", "mi_comm", "mi_debug"]
+UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_occgrid", "mi_voxelgrid", "mi_collision", "mi_graph", "mi_edt", "mi_knn", "mi_comm", "mi_debug"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 MI_ICP_HOST, MI_ICP_DEVICE = 0, 1
@@ -236,6 +236,14 @@ SIGNATURES = {
     "mi_icp_collision_voxelize_primitive": (_I, [_P, C.POINTER(Primitive), _F, _P, _P, _L, C.POINTER(_L), _P]),
     "mi_icp_collision_sort_keys": (_I, [_P, _P, _L, _P, _P, C.POINTER(_L)]),
     "mi_icp_primitive_aabb": (_I, [C.POINTER(Primitive), _P, _P]),
+    "mi_icp_graph_construct": (_I, [_P, _P, _P, _P, _L, _L, _P]),
+    "mi_icp_graph_weights_from_distance": (_I, [_P, _P, _L, _P, _L, _P]),
+    "mi_icp_graph_node_distances": (_I, [_P, _P, _L, _P, _P]),
+    "mi_icp_graph_lattice": (_I, [_P, _P, _P, _P, _P, _L, _P, _P, _L, _P, C.POINTER(_L), C.POINTER(_L)]),
+    "mi_icp_graph_set_edge_weights": (_I, [_P, _P, _P, _L, _P, _L, _I, _F]),
+    "mi_icp_graph_remove_edges": (_I, [_P, _P, _P, _P, _L, _L, _P, _L, _I, _P, C.POINTER(_L)]),
+    "mi_icp_graph_sssp": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _P, _P, _P]),
+    "mi_icp_graph_sssp_limits": (_I, [C.POINTER(_L), C.POINTER(_L), C.POINTER(C.c_int32)]),
     "mi_icp_covariances_from_normals": (_I, [_P, _P, _L, _F, _P, _I]),
     "mi_icp_estimate_normals_knn": (_I, [_P, _P, _L, _I, _P, _I]),
     "mi_icp_estimate_normals_radius": (_I, [_P, _P, _L, _F, _I, _P, _I]),

@@ -1,7 +1,7 @@
 // cupoch/geometry/lineset.h -- geometry::LineSet<3> (reference: geometry/lineset.h): points, lines (pairs of point
 // indices) and optional colours, one per line, on the device.  The bounds and the moves are the point cloud's, through
 // the same entry points (mi_icp_compute_bounds, mi_icp_affine, mi_icp_transform).  Its consumer here is
-// collision::ComputeIntersection (collision/collision.h).
+// collision::ComputeIntersection (collision/collision.h); geometry::Graph<3> (geometry/graph.h) derives from it.
 // Not built: the factories from triangle meshes, oriented boxes and clouds with correspondences, other dimensions,
 // file I/O, visualisation.
 #pragma once
@@ -51,6 +51,9 @@ public:
 
     /// the twelve edges of a box
     static std::shared_ptr<LineSet<3>> CreateFromAxisAlignedBoundingBox(const AxisAlignedBoundingBox3& box);
+
+protected:
+    explicit LineSet(GeometryType type);  // (a subclass with a type of its own: geometry::Graph<3>)
 
 public:
     utility::device_vector<Eigen::Vector3f> points_;

@@ -18,7 +18,7 @@ namespace geometry {
 
 class Geometry {
 public:
-    enum class GeometryType { Unspecified = 0, PointCloud = 1, VoxelGrid = 2, OccupancyGrid = 3, DistanceTransform = 4, LineSet = 5, AxisAlignedBoundingBox = 13 };  // geometry.h:37-68
+    enum class GeometryType { Unspecified = 0, PointCloud = 1, VoxelGrid = 2, OccupancyGrid = 3, DistanceTransform = 4, LineSet = 5, Graph = 6, AxisAlignedBoundingBox = 13 };  // geometry.h:37-68
     virtual ~Geometry() {}
     GeometryType GetGeometryType() const { return type_; }
     int Dimension() const { return dimension_; }

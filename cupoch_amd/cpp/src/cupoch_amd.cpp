@@ -8,7 +8,9 @@
 #include <typeinfo>
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cfloat>
+#include <limits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1959,6 +1961,332 @@ std::shared_ptr<geometry::VoxelGrid> CreateVoxelGrid(const Primitive& primitive,
 }
 
 }  // namespace collision
+
+// ---------------------------------------------------------------- geometry::Graph<3> (graph.cu, graph_factory.cu) over mi_icp_graph_*
+namespace geometry {
+
+namespace {
+int* LinePtr(utility::device_vector<Eigen::Vector2i>& v) { return v.empty() ? nullptr : v.data()->data(); }
+const int* LinePtr(const utility::device_vector<Eigen::Vector2i>& v) { return v.empty() ? nullptr : v.data()->data(); }
+float* Vec3Ptr(utility::device_vector<Eigen::Vector3f>& v) { return v.empty() ? nullptr : v.data()->data(); }
+
+template <class T>
+void Append(utility::device_vector<T>* dst, const utility::device_vector<T>& src) {
+    const size_t n = dst->size();
+    dst->resize(n + src.size());
+    if (src.size()) utility::copy_d2d(dst->data() + n, src.data(), src.size() * sizeof(T));
+}
+
+// every line has a weight: missing ones are 1.0
+void FillWeights(Graph<3>* g) {
+    const size_t m = g->lines_.size(), have = g->edge_weights_.size();
+    if (have == m) return;
+    std::vector<float> w = g->edge_weights_.to_host();
+    w.resize(m, 1.0f);
+    g->edge_weights_ = w;
+}
+}  // namespace
+
+LineSet<3>::LineSet(GeometryType type) : GeometryBase3D(type) {}
+
+Graph<3>::Graph() : LineSet<3>(GeometryType::Graph) {}
+Graph<3>::Graph(const utility::device_vector<Eigen::Vector3f>& points) : LineSet<3>(GeometryType::Graph) { points_ = points; }
+Graph<3>::Graph(const thrust::host_vector<Eigen::Vector3f>& points) : LineSet<3>(GeometryType::Graph) { points_ = points; }
+Graph<3>::Graph(const Graph& other)
+    : LineSet<3>(GeometryType::Graph),
+      edge_index_offsets_(other.edge_index_offsets_),
+      edge_weights_(other.edge_weights_),
+      node_colors_(other.node_colors_),
+      is_directed_(other.is_directed_),
+      sorted_(other.sorted_) {
+    points_ = other.points_;
+    lines_ = other.lines_;
+    colors_ = other.colors_;
+}
+Graph<3>::~Graph() {}
+
+Graph<3>& Graph<3>::Clear() {
+    LineSet<3>::Clear();
+    edge_index_offsets_.clear();
+    edge_weights_.clear();
+    node_colors_.clear();
+    sorted_ = false;
+    return *this;
+}
+
+Graph<3>& Graph<3>::ConstructGraph(bool set_edge_weights_from_distance) {
+    if (lines_.empty()) {
+        LogError("[ConstructGraph] Graph has no edges.");
+        return *this;
+    }
+    FillWeights(this);
+    edge_index_offsets_.resize(points_.size() + 1);
+    Check(mi_icp_graph_construct(Engine(), LinePtr(lines_), edge_weights_.data(), HasColors() ? Vec3Ptr(colors_) : nullptr,
+                                 (int64_t)lines_.size(), (int64_t)points_.size(), edge_index_offsets_.data()));
+    sorted_ = true;
+    if (set_edge_weights_from_distance) SetEdgeWeightsFromDistance();
+    return *this;
+}
+
+Graph<3>& Graph<3>::SetEdgeWeightsFromDistance() {
+    edge_weights_.resize(lines_.size());
+    Check(mi_icp_graph_weights_from_distance(Engine(), Vec3Ptr(points_), (int64_t)points_.size(), LinePtr(lines_), (int64_t)lines_.size(),
+                                             edge_weights_.data()));
+    return *this;
+}
+
+Graph<3>& Graph<3>::SetEdgeWeights(const utility::device_vector<Eigen::Vector2i>& edges, float weight) {
+    if (lines_.empty() || edges.empty()) return *this;
+    if (!IsConstructed()) ConstructGraph(false);
+    Check(mi_icp_graph_set_edge_weights(Engine(), LinePtr(lines_), edge_weights_.data(), (int64_t)lines_.size(), LinePtr(edges),
+                                        (int64_t)edges.size(), is_directed_ ? 1 : 0, weight));
+    Check(mi_icp_synchronize(Engine()));
+    return *this;
+}
+
+Graph<3>& Graph<3>::AddEdges(const utility::device_vector<Eigen::Vector2i>& edges, const utility::device_vector<float>& weights, bool lazy_add) {
+    if (!weights.empty() && edges.size() != weights.size()) {
+        LogError("[AddEdges] edges size is not equal to weights size.");
+        return *this;
+    }
+    FillWeights(this);
+    const bool had_colors = HasColors();
+    std::vector<Eigen::Vector2i> e = edges.to_host();
+    std::vector<float> w = weights.empty() ? std::vector<float>(e.size(), 1.0f) : weights.to_host();  // (the reference's resize here is wrong)
+    if (!is_directed_) {
+        const size_t k = e.size();
+        for (size_t i = 0; i < k; ++i) {
+            e.push_back(Eigen::Vector2i(e[i](1), e[i](0)));
+            w.push_back(w[i]);
+        }
+    }
+    Append(&lines_, utility::device_vector<Eigen::Vector2i>(e));
+    Append(&edge_weights_, utility::device_vector<float>(w));
+    if (had_colors) Append(&colors_, utility::device_vector<Eigen::Vector3f>(std::vector<Eigen::Vector3f>(e.size(), Eigen::Vector3f(1.0f, 1.0f, 1.0f))));
+    sorted_ = false;
+    return lazy_add ? *this : ConstructGraph(false);
+}
+Graph<3>& Graph<3>::AddEdges(const thrust::host_vector<Eigen::Vector2i>& edges, const thrust::host_vector<float>& weights, bool lazy_add) {
+    return AddEdges(utility::device_vector<Eigen::Vector2i>(edges), utility::device_vector<float>(weights), lazy_add);
+}
+Graph<3>& Graph<3>::AddEdge(const Eigen::Vector2i& edge, float weight, bool lazy_add) {
+    return AddEdges(std::vector<Eigen::Vector2i>{edge}, std::vector<float>{weight}, lazy_add);
+}
+
+Graph<3>& Graph<3>::RemoveEdges(const utility::device_vector<Eigen::Vector2i>& edges) {
+    if (lines_.empty()) return *this;
+    if (!IsConstructed()) ConstructGraph(false);
+    const bool has_colors = HasColors();
+    int64_t m = 0;
+    edge_index_offsets_.resize(points_.size() + 1);
+    Check(mi_icp_graph_remove_edges(Engine(), LinePtr(lines_), edge_weights_.data(), has_colors ? Vec3Ptr(colors_) : nullptr,
+                                    (int64_t)lines_.size(), (int64_t)points_.size(), LinePtr(edges), (int64_t)edges.size(),
+                                    is_directed_ ? 1 : 0, edge_index_offsets_.data(), &m));
+    Check(mi_icp_synchronize(Engine()));
+    lines_.resize((size_t)m);
+    edge_weights_.resize((size_t)m);
+    if (has_colors) colors_.resize((size_t)m);
+    return *this;
+}
+Graph<3>& Graph<3>::RemoveEdges(const thrust::host_vector<Eigen::Vector2i>& edges) { return RemoveEdges(utility::device_vector<Eigen::Vector2i>(edges)); }
+Graph<3>& Graph<3>::RemoveEdge(const Eigen::Vector2i& edge) { return RemoveEdges(std::vector<Eigen::Vector2i>{edge}); }
+
+Graph<3>& Graph<3>::AddNodeAndConnect(const Eigen::Vector3f& point, float max_edge_distance, bool lazy_add) {
+    const size_t n = points_.size();
+    std::vector<Eigen::Vector2i> e;
+    std::vector<float> w;
+    if (n) {
+        utility::device_vector<float> d(n);
+        Check(mi_icp_graph_node_distances(Engine(), Vec3Ptr(points_), (int64_t)n, point.data(), d.data()));
+        Check(mi_icp_synchronize(Engine()));
+        const std::vector<float> h = d.to_host();
+        for (size_t i = 0; i < n; ++i)
+            if (h[i] < max_edge_distance) {  // strictly nearer
+                e.push_back(Eigen::Vector2i((int)i, (int)n));
+                w.push_back(h[i]);
+            }
+    }
+    Append(&points_, utility::device_vector<Eigen::Vector3f>(std::vector<Eigen::Vector3f>{point}));
+    if (!node_colors_.empty()) Append(&node_colors_, utility::device_vector<Eigen::Vector3f>(std::vector<Eigen::Vector3f>{Eigen::Vector3f(1.0f, 1.0f, 1.0f)}));
+    sorted_ = false;
+    if (e.empty()) return (lazy_add || lines_.empty()) ? *this : ConstructGraph(false);
+    return AddEdges(e, w, lazy_add);
+}
+
+Graph<3>& Graph<3>::ConnectToNearestNeighbors(float max_edge_distance, size_t max_num_edges) {
+    const size_t n = points_.size();
+    if (n == 0) return *this;
+    const int knn = (int)max_num_edges + 1;
+    if (knn < 1 || knn > 100) {
+        LogError("[ConnectToNearestNeighbors] max_num_edges + 1 must be in [1, 100].");
+        return *this;
+    }
+    knn::KDTreeFlann tree(points_);
+    utility::device_vector<int> di;
+    utility::device_vector<float> dd;
+    if (tree.SearchRadius(points_, max_edge_distance, knn, di, dd) < 0) return *this;
+    const std::vector<int> idx = di.to_host();
+    std::vector<uint64_t> keys;  // first * n + second: the row is the query
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < knn; ++k) {
+            const int j = idx[i * (size_t)knn + (size_t)k];
+            if (j < 0 || (size_t)j == i) continue;
+            keys.push_back((uint64_t)i * n + (uint64_t)j);
+            if (!is_directed_) keys.push_back((uint64_t)j * n + (uint64_t)i);
+        }
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    std::vector<uint64_t> have;
+    for (const auto& l : lines_.to_host()) have.push_back((uint64_t)l(0) * n + (uint64_t)l(1));
+    std::sort(have.begin(), have.end());
+    std::vector<Eigen::Vector2i> fresh;
+    for (uint64_t k : keys)
+        if (!std::binary_search(have.begin(), have.end(), k)) fresh.push_back(Eigen::Vector2i((int)(k / n), (int)(k % n)));
+    FillWeights(this);
+    const bool had_colors = HasColors();
+    utility::device_vector<Eigen::Vector2i> dl(fresh);
+    utility::device_vector<float> dw(fresh.size());
+    Check(mi_icp_graph_weights_from_distance(Engine(), Vec3Ptr(points_), (int64_t)n, LinePtr(dl), (int64_t)dl.size(), dw.data()));
+    Append(&lines_, dl);
+    Append(&edge_weights_, dw);
+    if (had_colors) Append(&colors_, utility::device_vector<Eigen::Vector3f>(std::vector<Eigen::Vector3f>(fresh.size(), Eigen::Vector3f(1.0f, 1.0f, 1.0f))));
+    sorted_ = false;
+    return ConstructGraph(false);
+}
+
+Graph<3>& Graph<3>::PaintEdgesColor(const thrust::host_vector<Eigen::Vector2i>& edges, const Eigen::Vector3f& color) {
+    std::vector<Eigen::Vector3f> c = HasColors() ? colors_.to_host() : std::vector<Eigen::Vector3f>(lines_.size(), Eigen::Vector3f(1.0f, 1.0f, 1.0f));
+    const std::vector<Eigen::Vector2i> l = lines_.to_host();
+    for (size_t i = 0; i < l.size(); ++i)
+        for (const auto& e : edges)
+            if ((l[i](0) == e(0) && l[i](1) == e(1)) || (!is_directed_ && l[i](0) == e(1) && l[i](1) == e(0))) c[i] = color;
+    colors_ = c;
+    return *this;
+}
+Graph<3>& Graph<3>::PaintEdgeColor(const Eigen::Vector2i& edge, const Eigen::Vector3f& color) {
+    return PaintEdgesColor(std::vector<Eigen::Vector2i>{edge}, color);
+}
+Graph<3>& Graph<3>::PaintNodesColor(const thrust::host_vector<int>& nodes, const Eigen::Vector3f& color) {
+    std::vector<Eigen::Vector3f> c = HasNodeColors() ? node_colors_.to_host() : std::vector<Eigen::Vector3f>(points_.size(), Eigen::Vector3f(1.0f, 1.0f, 1.0f));
+    for (int i : nodes)
+        if (i >= 0 && (size_t)i < c.size()) c[(size_t)i] = color;
+    node_colors_ = c;
+    return *this;
+}
+Graph<3>& Graph<3>::PaintNodeColor(int node, const Eigen::Vector3f& color) { return PaintNodesColor(std::vector<int>{node}, color); }
+
+std::shared_ptr<Graph<3>::SSSPResultHostArray> Graph<3>::DijkstraPathsHost(int start_node_index, int end_node_index) const {
+    auto out = std::make_shared<SSSPResultHostArray>(points_.size());
+    if (!IsConstructed()) {
+        LogError("[DijkstraPath] this graph is not constructed.");
+        return out;
+    }
+    const size_t n = points_.size();
+    utility::device_vector<float> d(n);
+    utility::device_vector<int> p(n);
+    Check(mi_icp_graph_sssp(Engine(), edge_index_offsets_.data(), LinePtr(lines_), edge_weights_.data(), (int64_t)n, (int64_t)lines_.size(),
+                            start_node_index, end_node_index, d.data(), p.data(), nullptr));
+    Check(mi_icp_synchronize(Engine()));
+    const std::vector<float> hd = d.to_host();
+    const std::vector<int> hp = p.to_host();
+    for (size_t i = 0; i < n; ++i) (*out)[i] = SSSPResult(hd[i], hp[i]);
+    return out;
+}
+std::shared_ptr<Graph<3>::SSSPResultArray> Graph<3>::DijkstraPaths(int start_node_index, int end_node_index) const {
+    auto out = std::make_shared<SSSPResultArray>();
+    *out = *DijkstraPathsHost(start_node_index, end_node_index);
+    return out;
+}
+std::pair<std::shared_ptr<thrust::host_vector<int>>, float> Graph<3>::DijkstraPath(int start_node_index, int end_node_index) const {
+    auto nodes = std::make_shared<thrust::host_vector<int>>();
+    const float inf = std::numeric_limits<float>::infinity();
+    if (end_node_index < 0 || (size_t)end_node_index >= points_.size()) return std::make_pair(nodes, inf);
+    const auto res = DijkstraPathsHost(start_node_index, end_node_index);
+    if ((*res)[(size_t)end_node_index].prev_index_ < 0) return std::make_pair(nodes, inf);
+    int v = end_node_index;
+    nodes->push_back(v);
+    while (v != start_node_index && nodes->size() <= res->size()) {
+        v = (*res)[(size_t)v].prev_index_;
+        nodes->push_back(v);
+    }
+    std::reverse(nodes->begin(), nodes->end());
+    return std::make_pair(nodes, (*res)[(size_t)end_node_index].shortest_distance_);
+}
+
+std::shared_ptr<Graph<3>> Graph<3>::CreateFromAxisAlignedBoundingBox(const AxisAlignedBoundingBox3& bbox, const Eigen::Vector3i& resolutions) {
+    return CreateFromAxisAlignedBoundingBox(bbox.GetMinBound(), bbox.GetMaxBound(), resolutions);
+}
+std::shared_ptr<Graph<3>> Graph<3>::CreateFromAxisAlignedBoundingBox(const Eigen::Vector3f& min_bound, const Eigen::Vector3f& max_bound,
+                                                                     const Eigen::Vector3i& resolutions) {
+    auto out = std::make_shared<Graph<3>>();
+    int64_t n = 0, m = 0;
+    const int32_t res[3] = {resolutions(0), resolutions(1), resolutions(2)};
+    if (Refused(mi_icp_graph_lattice(Engine(), min_bound.data(), max_bound.data(), res, nullptr, 0, nullptr, nullptr, 0, nullptr, &n, &m))) return out;
+    out->points_.resize((size_t)n);
+    out->lines_.resize((size_t)m);
+    out->edge_weights_.resize((size_t)m);
+    out->edge_index_offsets_.resize((size_t)n + 1);
+    Check(mi_icp_graph_lattice(Engine(), min_bound.data(), max_bound.data(), res, Vec3Ptr(out->points_), n, LinePtr(out->lines_),
+                               out->edge_weights_.data(), m, out->edge_index_offsets_.data(), &n, &m));
+    Check(mi_icp_synchronize(Engine()));
+    out->sorted_ = true;
+    return out;
+}
+
+}  // namespace geometry
+
+// ---------------------------------------------------------------- planning (planner.cu)
+namespace planning {
+
+Pos3DPlanner::Pos3DPlanner(const geometry::Graph<3>& graph, float object_radius, float max_edge_distance)
+    : graph_(graph), object_radius_(object_radius), max_edge_distance_(max_edge_distance) {}
+Pos3DPlanner::~Pos3DPlanner() {}
+Pos3DPlanner::Pos3DPlanner(const Pos3DPlanner& other)
+    : PlannerBase(other), graph_(other.graph_), object_radius_(other.object_radius_), max_edge_distance_(other.max_edge_distance_) {}
+
+Pos3DPlanner& Pos3DPlanner::UpdateGraph() {
+    RemoveCollisionEdges(graph_);
+    return *this;
+}
+
+void Pos3DPlanner::RemoveCollisionEdges(geometry::Graph<3>& graph) const {
+    graph.SetEdgeWeightsFromDistance();
+    for (const auto& obstacle : obstacles_) {
+        std::shared_ptr<collision::CollisionResult> res;
+        const geometry::LineSet<3>& lines = graph;
+        switch (obstacle->GetGeometryType()) {
+            case geometry::Geometry::GeometryType::VoxelGrid:
+                res = collision::ComputeIntersection((const geometry::VoxelGrid&)(*obstacle), lines, object_radius_);
+                break;
+            case geometry::Geometry::GeometryType::OccupancyGrid:
+                res = collision::ComputeIntersection((const geometry::OccupancyGrid&)(*obstacle), lines, object_radius_);
+                break;
+            default: LogError("Unsupported obstacle type.");
+        }
+        if (!res || !res->IsCollided()) continue;
+        const std::vector<Eigen::Vector2i> pairs = res->collision_index_pairs_.to_host(), all = graph.lines_.to_host();
+        std::vector<Eigen::Vector2i> hit;
+        for (const auto& p : pairs) hit.push_back(all[(size_t)p(1)]);
+        graph.SetEdgeWeights(utility::device_vector<Eigen::Vector2i>(hit), std::numeric_limits<float>::infinity());
+    }
+}
+
+std::shared_ptr<Path> Pos3DPlanner::FindPath(const Eigen::Vector3f& start, const Eigen::Vector3f& goal) const {
+    auto out = std::make_shared<Path>();
+    geometry::Graph<3> g = graph_;
+    const size_t n = g.points_.size();
+    g.AddNodeAndConnect(start, max_edge_distance_, true);
+    g.AddNodeAndConnect(goal, max_edge_distance_, false);
+    if (!g.IsConstructed()) return out;  // (no edge reached either node)
+    RemoveCollisionEdges(g);
+    const auto path = g.DijkstraPath((int)n, (int)n + 1);
+    if (std::isinf(path.second)) return out;
+    const std::vector<Eigen::Vector3f> pts = g.points_.to_host();
+    for (int i : *path.first) out->push_back(pts[(size_t)i]);
+    return out;
+}
+
+}  // namespace planning
 
 namespace integration {
 

@@ -32,6 +32,7 @@
 #include "cupoch/camera/pinhole_camera_parameters.h"
 #include "cupoch/collision/collision.h"
 #include "cupoch/geometry/distancetransform.h"
+#include "cupoch/geometry/graph.h"
 #include "cupoch/geometry/image.h"
 #include "cupoch/geometry/keypoint.h"
 #include "cupoch/geometry/occupancygrid.h"
@@ -40,6 +41,7 @@
 #include "cupoch/integration/uniform_tsdfvolume.h"
 #include "cupoch/knn/kdtree_flann.h"
 #include "cupoch/knn/kdtree_search_param.h"
+#include "cupoch/planning/planner.h"
 #include "cupoch/registration/generalized_icp.h"
 #include "cupoch/registration/registration.h"
 #include "cupoch/registration/transformation_estimation.h"
@@ -342,7 +344,7 @@ typedef struct MiDLManagedTensor {
 } MiDLManagedTensor;
 }
 enum { kMiDLCPU = 1, kMiDLCUDA = 2, kMiDLCUDAHost = 3, kMiDLROCM = 10, kMiDLROCMHost = 11 };
-enum { kMiDLFloat = 2 };
+enum { kMiDLInt = 0, kMiDLFloat = 2 };
 
 struct Vec3Export {
     std::shared_ptr<void> handle;  // the cloud's block, shared
@@ -350,7 +352,9 @@ struct Vec3Export {
     MiDLManagedTensor tensor;
 };
 
-py::capsule to_dlpack_capsule(const utility::device_vector<Eigen::Vector3f>& src) {
+// V: rows of `cols` 32-bit words (Eigen::Vector3f: 3 floats; Eigen::Vector2i, a graph's edges: 2 ints, code kMiDLInt)
+template <class V>
+py::capsule to_dlpack_capsule(const utility::device_vector<V>& src, int cols = 3, int code = kMiDLFloat) {
     Vec3Export* e = new Vec3Export();
     e->handle = src.share();  // no copy: the tensor and the cloud hold the same block
     int dev = 0;
@@ -359,13 +363,13 @@ py::capsule to_dlpack_capsule(const utility::device_vector<Eigen::Vector3f>& src
     // consumer on any stream sees the pointer -- ADVICE r5; INTEGRATION.md section 2 lists what aliasing means otherwise)
     (void)hipDeviceSynchronize();
     e->shape[0] = (int64_t)src.size();
-    e->shape[1] = 3;
+    e->shape[1] = cols;
     MiDLTensor& t = e->tensor.dl_tensor;
     t.data = (void*)src.data();
     t.device.device_type = kMiDLROCM;
     t.device.device_id = dev;
     t.ndim = 2;
-    t.dtype.code = kMiDLFloat;
+    t.dtype.code = (uint8_t)code;
     t.dtype.bits = 32;
     t.dtype.lanes = 1;
     t.shape = e->shape;
@@ -385,16 +389,17 @@ py::capsule to_dlpack_capsule(const utility::device_vector<Eigen::Vector3f>& src
     });
 }
 
-void from_dlpack_capsule(const py::capsule& cap, utility::device_vector<Eigen::Vector3f>& dst) {
+template <class V>
+void from_dlpack_capsule(const py::capsule& cap, utility::device_vector<V>& dst, int cols = 3, int code = kMiDLFloat) {
     if (!PyCapsule_IsValid(cap.ptr(), "dltensor")) {
         PyErr_Clear();
         throw std::invalid_argument("expected a DLPack capsule named \"dltensor\" (not yet consumed)");
     }
     const MiDLManagedTensor* m = static_cast<const MiDLManagedTensor*>(PyCapsule_GetPointer(cap.ptr(), "dltensor"));
     const MiDLTensor& t = m->dl_tensor;
-    if (t.ndim != 2 || t.shape[1] != 3 || t.dtype.code != kMiDLFloat || t.dtype.bits != 32 || t.dtype.lanes != 1)
-        throw std::invalid_argument("from_*_dlpack: expected an (n, 3) float32 tensor");
-    if (t.strides && t.shape[0] > 0 && (t.strides[1] != 1 || (t.shape[0] > 1 && t.strides[0] != 3)))
+    if (t.ndim != 2 || t.shape[1] != cols || t.dtype.code != code || t.dtype.bits != 32 || t.dtype.lanes != 1)
+        throw std::invalid_argument(code == kMiDLFloat ? "from_*_dlpack: expected an (n, 3) float32 tensor" : "from_*_dlpack: expected an (n, 2) int32 tensor");
+    if (t.strides && t.shape[0] > 0 && (t.strides[1] != 1 || (t.shape[0] > 1 && t.strides[0] != cols)))
         throw std::invalid_argument("from_*_dlpack: the tensor must be contiguous");
     const size_t n = (size_t)t.shape[0];
     const char* src = static_cast<const char*>(t.data) + t.byte_offset;
@@ -402,7 +407,7 @@ void from_dlpack_capsule(const py::capsule& cap, utility::device_vector<Eigen::V
     dst.resize(0);
     dst.resize(n);
     if (n == 0) return;
-    const size_t bytes = n * sizeof(Eigen::Vector3f);
+    const size_t bytes = n * sizeof(V);
     hipError_t e;
     if (kind == kMiDLCPU || kind == kMiDLCUDAHost || kind == kMiDLROCMHost) e = hipMemcpy(dst.data(), src, bytes, hipMemcpyHostToDevice);
     else if (kind == kMiDLROCM || kind == kMiDLCUDA) e = hipMemcpy(dst.data(), src, bytes, hipMemcpyDeviceToDevice);
@@ -1032,6 +1037,113 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             .def("rotate", [](std::shared_ptr<geometry::LineSet<3>> l, const farray& R, bool center) { l->Rotate(to_matrix3(R), center); return l; }, "R"_a, "center"_a = true)
             .def("transform", [](std::shared_ptr<geometry::LineSet<3>> l, const farray& T) { l->Transform(to_matrix4(T)); return l; }, "transformation"_a)
             .def_static("create_from_axis_aligned_bounding_box", &geometry::LineSet<3>::CreateFromAxisAlignedBoundingBox, "box"_a);
+
+    // geometry.Graph (cupoch_pybind/geometry/graph.cpp): the reference's names and defaults over geometry::Graph<3>
+    typedef geometry::Graph<3> Graph3;
+    py::class_<Graph3, std::shared_ptr<Graph3>, geometry::LineSet<3>>(mg, "Graph")
+            .def(py::init<>())
+            .def(py::init([](const farray& points) {
+                     auto g = std::make_shared<Graph3>();
+                     g->points_ = Vector3fVector(points).data;
+                     return g;
+                 }),
+                 "points"_a)
+            .def("__repr__", [](const Graph3& g) { return std::string("geometry::Graph with ") + std::to_string(g.points_.size()) + " nodes and " + std::to_string(g.lines_.size()) + " edges."; })
+            .def_property(
+                    "edges", [](const Graph3& g) { Vector2iVector v; v.data = g.lines_; return v; },
+                    [](Graph3& g, const Vector2iVector& v) { g.lines_ = v.data; g.sorted_ = false; })
+            .def_property(
+                    "edge_weights", [](const Graph3& g) { const std::vector<float> h = g.GetEdgeWeights(); return farray(h.size(), h.data()); },
+                    [](Graph3& g, const farray& w) { g.SetEdgeWeights(std::vector<float>(w.data(), w.data() + w.size())); })
+            .def_property(
+                    "edge_index_offsets", [](const Graph3& g) { const std::vector<int> h = g.GetEdgeIndexOffsets(); return iarray2(h.size(), h.data()); },
+                    [](Graph3& g, const iarray2& o) { g.SetEdgeIndexOffsets(std::vector<int>(o.data(), o.data() + o.size())); })
+            .def_property(
+                    "node_colors", [](const Graph3& g) { Vector3fVector v; v.data = g.node_colors_; return v; },
+                    [](Graph3& g, const Vector3fVector& v) { g.node_colors_ = v.data; })
+            .def_readwrite("is_directed", &Graph3::is_directed_)
+            .def("has_weights", &Graph3::HasWeights)
+            .def("has_node_colors", &Graph3::HasNodeColors)
+            .def("is_constructed", &Graph3::IsConstructed)
+            .def("construct_graph", [](std::shared_ptr<Graph3> g, bool from_distance) { g->ConstructGraph(from_distance); return g; },
+                 "set_edge_weights_from_distance"_a = true)
+            .def("connect_to_nearest_neighbors", [](std::shared_ptr<Graph3> g, float d, size_t k) { g->ConnectToNearestNeighbors(d, k); return g; },
+                 "max_edge_distance"_a, "max_num_edges"_a = 30)
+            .def("add_node_and_connect", [](std::shared_ptr<Graph3> g, const farray& p, float d, bool lazy) { g->AddNodeAndConnect(to_vector3(p), d, lazy); return g; },
+                 "point"_a, "max_edge_distance"_a = 0.0f, "lazy_add"_a = false)
+            .def("add_edge", [](std::shared_ptr<Graph3> g, const iarray2& e, float w, bool lazy) { g->AddEdge(Eigen::Vector2i(e.data()[0], e.data()[1]), w, lazy); return g; },
+                 "edge"_a, "weight"_a = 1.0f, "lazy_add"_a = false)
+            .def("add_edges",
+                 [](std::shared_ptr<Graph3> g, const Vector2iVector& e, const farray& w, bool lazy) {
+                     g->AddEdges(e.data, utility::device_vector<float>(std::vector<float>(w.data(), w.data() + w.size())), lazy);
+                     return g;
+                 },
+                 "edges"_a, "weights"_a = farray(0), "lazy_add"_a = false)
+            .def("remove_edge", [](std::shared_ptr<Graph3> g, const iarray2& e) { g->RemoveEdge(Eigen::Vector2i(e.data()[0], e.data()[1])); return g; }, "edge"_a)
+            .def("remove_edges", [](std::shared_ptr<Graph3> g, const Vector2iVector& e) { g->RemoveEdges(e.data); return g; }, "edges"_a)
+            .def("paint_edge_color", [](std::shared_ptr<Graph3> g, const iarray2& e, const farray& c) { g->PaintEdgeColor(Eigen::Vector2i(e.data()[0], e.data()[1]), to_vector3(c)); return g; },
+                 "edge"_a, "color"_a)
+            .def("paint_edges_color", [](std::shared_ptr<Graph3> g, const Vector2iVector& e, const farray& c) { g->PaintEdgesColor(e.data.to_host(), to_vector3(c)); return g; },
+                 "edges"_a, "color"_a)
+            .def("paint_node_color", [](std::shared_ptr<Graph3> g, int node, const farray& c) { g->PaintNodeColor(node, to_vector3(c)); return g; }, "node"_a, "color"_a)
+            .def("paint_nodes_color", [](std::shared_ptr<Graph3> g, const std::vector<int>& nodes, const farray& c) { g->PaintNodesColor(nodes, to_vector3(c)); return g; },
+                 "nodes"_a, "color"_a)
+            .def("set_edge_weights_from_distance", [](std::shared_ptr<Graph3> g) { g->SetEdgeWeightsFromDistance(); return g; })
+            .def("set_edge_weights", [](std::shared_ptr<Graph3> g, const Vector2iVector& e, float w) { g->SetEdgeWeights(e.data, w); return g; }, "edges"_a, "weight"_a)
+            .def("dijkstra_paths",
+                 [](const Graph3& g, int start, int end) {
+                     const auto res = g.DijkstraPathsHost(start, end);
+                     farray dist(res->size());
+                     iarray2 prev(res->size());
+                     for (size_t i = 0; i < res->size(); ++i) {
+                         dist.mutable_data()[i] = (*res)[i].shortest_distance_;
+                         prev.mutable_data()[i] = (*res)[i].prev_index_;
+                     }
+                     return py::make_tuple(dist, prev);
+                 },
+                 "start_node_index"_a, "end_node_index"_a = -1)
+            .def("dijkstra_path",
+                 [](const Graph3& g, int start, int end) {
+                     const auto p = g.DijkstraPath(start, end);
+                     return py::make_tuple(*p.first, p.second);
+                 },
+                 "start_node_index"_a, "end_node_index"_a)
+            .def("to_edges_dlpack", [](Graph3& g) { return to_dlpack_capsule(g.lines_, 2, kMiDLInt); })
+            .def("from_edges_dlpack", [](Graph3& g, py::capsule c) { from_dlpack_capsule(c, g.lines_, 2, kMiDLInt); g.sorted_ = false; })
+            .def_static("create_from_axis_aligned_bounding_box",
+                        [](const geometry::AxisAlignedBoundingBox3& box, const iarray2& res) {
+                            return Graph3::CreateFromAxisAlignedBoundingBox(box, Eigen::Vector3i(res.data()[0], res.data()[1], res.data()[2]));
+                        },
+                        "bbox"_a, "resolutions"_a)
+            .def_static("create_from_axis_aligned_bounding_box",
+                        [](const farray& lo, const farray& hi, const iarray2& res) {
+                            return Graph3::CreateFromAxisAlignedBoundingBox(to_vector3(lo), to_vector3(hi), Eigen::Vector3i(res.data()[0], res.data()[1], res.data()[2]));
+                        },
+                        "min_bound"_a, "max_bound"_a, "resolutions"_a);
+
+    // ---------------------------------------------------------------- planning (cupoch_pybind/planning)
+    py::module mpl = m.def_submodule("planning");
+    py::class_<planning::Pos3DPlanner, std::shared_ptr<planning::Pos3DPlanner>>(mpl, "Pos3DPlanner")
+            .def(py::init([](const Graph3& graph, float object_radius, float max_edge_distance) {
+                     return std::make_shared<planning::Pos3DPlanner>(graph, object_radius, max_edge_distance);
+                 }),
+                 "graph"_a, "object_radius"_a = 0.1, "max_edge_distance"_a = 1.0)
+            .def("add_obstacle", [](std::shared_ptr<planning::Pos3DPlanner> p, std::shared_ptr<geometry::VoxelGrid> o) { p->AddObstacle(o); return p; }, "obstacle"_a)
+            .def("add_obstacle", [](std::shared_ptr<planning::Pos3DPlanner> p, std::shared_ptr<geometry::OccupancyGrid> o) { p->AddObstacle(o); return p; }, "obstacle"_a)
+            .def("add_obstacle", [](std::shared_ptr<planning::Pos3DPlanner> p, std::shared_ptr<geometry::PointCloud> o) { p->AddObstacle(o); return p; }, "obstacle"_a)
+            .def("update_graph", [](std::shared_ptr<planning::Pos3DPlanner> p) { p->UpdateGraph(); return p; })
+            .def("find_path",
+                 [](const planning::Pos3DPlanner& p, const farray& start, const farray& goal) {
+                     const auto path = p.FindPath(to_vector3(start), to_vector3(goal));
+                     farray out({(py::ssize_t)path->size(), (py::ssize_t)3});
+                     for (size_t i = 0; i < path->size(); ++i)
+                         for (int k = 0; k < 3; ++k) out.mutable_data()[i * 3 + (size_t)k] = (*path)[i](k);
+                     return out;
+                 },
+                 "start"_a, "goal"_a)
+            .def("get_graph", [](const planning::Pos3DPlanner& p) { return std::make_shared<Graph3>(p.GetGraph()); })
+            .def_readwrite("object_radius", &planning::Pos3DPlanner::object_radius_)
+            .def_readwrite("max_edge_distance", &planning::Pos3DPlanner::max_edge_distance_);
 
     // ---------------------------------------------------------------- collision
     // cupoch_pybind/collision: the primitives, PrimitiveArray, CollitionResult (the reference's spelling; CollisionResult

@@ -1095,6 +1095,75 @@ class Engine:
         _lib.load().mi_icp_primitive_aabb(C.byref(P), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p))
         return lo, hi
 
+    # -- graph (include/mi_icp.h "graph"; every array a device tensor of this engine's GPU) ----------------------------
+    def graph_construct(self, lines, n_points, weights=None, colors=None):
+        """sorts lines [m, 2] (and weights [m], colors [m, 3] with them) IN PLACE, stably -> offsets [n_points + 1]"""
+        dev = torch.device("cuda", self.device)
+        off, op = self._out(MI_ICP_DEVICE, dev, (int(n_points) + 1,), np.int32)
+        self._chk(self._L.mi_icp_graph_construct(self._ctx, self._ptr(lines), self._ptr(weights), self._ptr(colors),
+                                                 int(lines.shape[0]), int(n_points), op))
+        return off
+
+    def graph_weights_from_distance(self, points, lines):
+        dev = torch.device("cuda", self.device)
+        m = int(lines.shape[0])
+        w, wp = self._out(MI_ICP_DEVICE, dev, (m,), np.float32)
+        self._chk(self._L.mi_icp_graph_weights_from_distance(self._ctx, self._ptr(points), int(points.shape[0]),
+                                                             self._ptr(lines), m, wp))
+        return w
+
+    def graph_node_distances(self, points, point):
+        dev = torch.device("cuda", self.device)
+        d, dp = self._out(MI_ICP_DEVICE, dev, (int(points.shape[0]),), np.float32)
+        self._chk(self._L.mi_icp_graph_node_distances(self._ctx, self._ptr(points), int(points.shape[0]), self._f3(point), dp))
+        return d
+
+    def graph_lattice(self, min_bound, max_bound, resolutions):
+        """-> (points [n, 3], lines [m, 2], weights [m], offsets [n + 1]) (mi_icp_graph_lattice)"""
+        dev = torch.device("cuda", self.device)
+        lo, hi = self._f3(min_bound), self._f3(max_bound)
+        res = (C.c_int32 * 3)(*[int(v) for v in np.asarray(resolutions).reshape(3)])
+        n, m = C.c_int64(0), C.c_int64(0)
+        self._chk(self._L.mi_icp_graph_lattice(self._ctx, lo, hi, res, None, 0, None, None, 0, None, C.byref(n), C.byref(m)))
+        nn, mm = int(n.value), int(m.value)
+        (p, pp), (l, lp) = self._out(MI_ICP_DEVICE, dev, (nn, 3)), self._out(MI_ICP_DEVICE, dev, (max(mm, 1), 2), np.int32)
+        (w, wp), (o, op) = self._out(MI_ICP_DEVICE, dev, (max(mm, 1),)), self._out(MI_ICP_DEVICE, dev, (nn + 1,), np.int32)
+        self._chk(self._L.mi_icp_graph_lattice(self._ctx, lo, hi, res, pp, nn, lp, wp, mm, op, C.byref(n), C.byref(m)))
+        return p, l[:mm], w[:mm], o
+
+    def graph_set_edge_weights(self, lines, weights, edges, weight, is_directed):
+        """weights [m] changed in place; lines sorted (graph_construct)"""
+        self._chk(self._L.mi_icp_graph_set_edge_weights(self._ctx, self._ptr(lines), self._ptr(weights), int(lines.shape[0]),
+                                                        self._ptr(edges), int(edges.shape[0]), int(bool(is_directed)),
+                                                        float(weight)))
+
+    def graph_remove_edges(self, lines, n_points, edges, is_directed, weights=None, colors=None):
+        """compacts lines / weights / colors in place -> (the number of lines that stay, offsets)"""
+        dev = torch.device("cuda", self.device)
+        off, op = self._out(MI_ICP_DEVICE, dev, (int(n_points) + 1,), np.int32)
+        m = C.c_int64(0)
+        self._chk(self._L.mi_icp_graph_remove_edges(self._ctx, self._ptr(lines), self._ptr(weights), self._ptr(colors),
+                                                    int(lines.shape[0]), int(n_points), self._ptr(edges), int(edges.shape[0]),
+                                                    int(bool(is_directed)), op, C.byref(m)))
+        return int(m.value), off
+
+    def graph_sssp(self, offsets, lines, weights, n, start, end=-1, want_info=False):
+        """-> (dist [n] float32, prev [n] int32) on the device (mi_icp_graph_sssp); with want_info also the five words
+        (regime, launches, host waits, rounds, tier-2 rounds)"""
+        dev = torch.device("cuda", self.device)
+        (d, dp), (p, pp) = self._out(MI_ICP_DEVICE, dev, (int(n),)), self._out(MI_ICP_DEVICE, dev, (int(n),), np.int32)
+        info = (C.c_int32 * 5)()
+        self._chk(self._L.mi_icp_graph_sssp(self._ctx, self._ptr(offsets), self._ptr(lines), self._ptr(weights), int(n),
+                                            int(lines.shape[0]), int(start), int(end), dp, pp, info))
+        return (d, p, [int(v) for v in info]) if want_info else (d, p)
+
+    @staticmethod
+    def graph_sssp_limits():
+        """-> (the small regime's largest n, its largest m, the rounds of a batch in the large regime)"""
+        n, m, b = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        _lib.load().mi_icp_graph_sssp_limits(C.byref(n), C.byref(m), C.byref(b))
+        return int(n.value), int(m.value), int(b.value)
+
     def compute_rgbd_odometry(self, source_color, source_depth, target_color, target_depth, intrinsic4,
                               odo_init=None, jacobian=1, iterations=(20, 10, 5), max_depth_diff=0.03,
                               min_depth=0.0, max_depth=4.0, weighted=False, prev_twist=None, nu=5.0,

@@ -11,7 +11,9 @@ DistanceVoxel / DistanceTransform mirror geometry/distancetransform.h:30-78 (pyt
 src/python/cupoch_pybind/geometry/distancetransform.cpp); not built: the planning and visualisation consumers of a
 transform, and a transform as a collision target.
 LineSet mirrors geometry/lineset.h (LineSet<3>; python surface src/python/cupoch_pybind/geometry/lineset.cpp); not
-built: the factories from meshes, clouds with correspondences and oriented boxes, and file I/O."""
+built: the factories from meshes, clouds with correspondences and oriented boxes, and file I/O.
+Graph mirrors geometry/graph.h (Graph<3>; python surface src/python/cupoch_pybind/geometry/graph.cpp): the roadmap
+cupoch_amd.planning searches; not built: Graph2D, create_from_triangle_mesh, file I/O and visualisation."""
 import sys
 
 import numpy as np
@@ -1422,3 +1424,329 @@ def _v3(v):
 
 def _v2i(v):
     return v if isinstance(v, utility.Vector2iVector) else utility.Vector2iVector(v)
+
+
+def _t2i(eng, edges):
+    """edges as an int32 [k, 2] tensor on the engine's GPU"""
+    if isinstance(edges, utility.DeviceVector):
+        edges = edges.tensor
+    return eng._vg_dev(edges, np.int32, 2)
+
+
+class Graph(LineSet):
+    """geometry::Graph<3> (graph.h): a LineSet whose lines are directed edges, with one weight per edge and, once
+    constructed, the lines sorted by (first, second) and a CSR offset per node.  An undirected graph (is_directed =
+    False, the default) holds both directions of every edge.  The contract is in include/mi_icp.h ("graph"): the sort,
+    the lattice, the weight and removal updates and the shortest-path search run on the GPU through the
+    mi_icp_graph_* family.  Not built: Graph2D, create_from_triangle_mesh, visualisation, file I/O.  Deviations from
+    the reference: DESIGN.md section 6."""
+
+    def __init__(self, points=None):
+        if isinstance(points, Graph):
+            other = points
+            LineSet.__init__(self, other._points.tensor.clone(), other._lines.tensor.clone())
+            self._colors = None if other._colors is None else utility.Vector3fVector(other._colors.tensor.clone())
+            self._weights = None if other._weights is None else other._weights.clone()
+            self._offsets = None if other._offsets is None else other._offsets.clone()
+            self._node_colors = None if other._node_colors is None else utility.Vector3fVector(other._node_colors.tensor.clone())
+            self._sorted, self.is_directed = other._sorted, other.is_directed
+            return
+        LineSet.__init__(self, points, None)
+        self._weights = None          # float32 [m] on the device
+        self._offsets = None          # int32 [n + 1] on the device
+        self._node_colors = None
+        self._sorted = False          # the lines are as construct_graph left them
+        self.is_directed = False
+
+    def clone(self):
+        return Graph(self)
+
+    # ---- members
+    @property
+    def lines(self):
+        return self._lines
+
+    @lines.setter
+    def lines(self, v):
+        self._lines = _v2i(v)
+        self._sorted = False
+
+    edges = lines
+
+    @property
+    def edge_weights(self):
+        return self._weights if self._weights is not None else self._engine()._vg_dev(np.zeros(0, np.float32), np.float32, 1)
+
+    @edge_weights.setter
+    def edge_weights(self, v):
+        self._weights = self._engine()._vg_dev(v, np.float32, 1)
+
+    @property
+    def edge_index_offsets(self):
+        return self._offsets if self._offsets is not None else self._engine()._vg_dev(np.zeros(0, np.int32), np.int32, 1)
+
+    @edge_index_offsets.setter
+    def edge_index_offsets(self, v):
+        self._offsets = self._engine()._vg_dev(v, np.int32, 1)
+
+    @property
+    def node_colors(self):
+        return self._node_colors if self._node_colors is not None else utility.Vector3fVector()
+
+    @node_colors.setter
+    def node_colors(self, v):
+        self._node_colors = _v3(v)
+
+    def has_weights(self):
+        return self.has_lines() and self._weights is not None and int(self._weights.shape[0]) == len(self._lines)
+
+    def has_node_colors(self):
+        return self.has_points() and self._node_colors is not None and len(self._node_colors) == len(self._points)
+
+    def is_constructed(self):
+        return self._sorted and self._offsets is not None and int(self._offsets.shape[0]) == len(self._points) + 1
+
+    def clear(self):
+        LineSet.clear(self)
+        self._weights = self._offsets = self._node_colors = None
+        self._sorted = False
+        return self
+
+    def __repr__(self):
+        return "geometry::Graph with %d nodes and %d edges." % (len(self._points), len(self._lines))
+
+    def _m(self):
+        return len(self._lines)
+
+    def _fill_weights(self):
+        """every line has a weight: missing ones are 1.0 (the reference's resize)"""
+        m = self._m()
+        have = 0 if self._weights is None else int(self._weights.shape[0])
+        if have != m:
+            w = torch.ones(m, dtype=torch.float32, device=self._lines.tensor.device)
+            if have:
+                w[:min(have, m)] = self._weights[:min(have, m)]
+            self._weights = w
+
+    # ---- ConstructGraph and the weights
+    def construct_graph(self, set_edge_weights_from_distance=True):
+        if self._m() == 0:
+            _log_error("[ConstructGraph] Graph has no edges.")
+            return self
+        self._fill_weights()
+        col = self._colors.tensor if self.has_colors() else None
+        self._offsets = self._engine().graph_construct(self._lines.tensor, len(self._points), self._weights, col)
+        self._sorted = True
+        if set_edge_weights_from_distance:
+            self.set_edge_weights_from_distance()
+        return self
+
+    def set_edge_weights_from_distance(self):
+        self._weights = self._engine().graph_weights_from_distance(self._points.tensor, self._lines.tensor)
+        return self
+
+    def set_edge_weights(self, edges, weight):
+        """every line equal to a listed edge (undirected: or to its reverse) gets `weight`"""
+        if self._m() == 0:
+            return self
+        if not self.is_constructed():
+            self.construct_graph(False)
+        self._fill_weights()
+        eng = self._engine()
+        e = _t2i(eng, edges)
+        if int(e.shape[0]):
+            eng.graph_set_edge_weights(self._lines.tensor, self._weights, e, weight, self.is_directed)
+            eng.synchronize()    # (an uploaded list may go)
+        return self
+
+    # ---- edges in and out
+    def add_edges(self, edges, weights=None, lazy_add=False):
+        eng = self._engine()
+        e = _t2i(eng, edges)
+        k = int(e.shape[0])
+        if weights is not None:
+            w = eng._vg_dev(weights.tensor if isinstance(weights, utility.DeviceVector) else weights, np.float32, 1)
+            if int(w.shape[0]) == 0:
+                w = None
+            elif int(w.shape[0]) != k:
+                _log_error("[AddEdges] edges size is not equal to weights size.")
+                return self
+        else:
+            w = None
+        if w is None:
+            w = torch.ones(k, dtype=torch.float32, device=e.device)   # (the reference's resize here is wrong: DESIGN section 6)
+        self._fill_weights()
+        had_colors = self.has_colors()
+        new_l, new_w = (e, w) if self.is_directed else (torch.cat([e, e.flip(1)]), torch.cat([w, w]))
+        old_w = self._weights if self._weights is not None else w[:0]
+        self._lines = utility.Vector2iVector(torch.cat([self._lines.tensor, new_l]))
+        self._weights = torch.cat([old_w, new_w])
+        if had_colors:
+            ones = torch.ones((int(new_l.shape[0]), 3), dtype=torch.float32, device=e.device)
+            self._colors = utility.Vector3fVector(torch.cat([self._colors.tensor, ones]))
+        self._sorted = False
+        return self if lazy_add else self.construct_graph(False)
+
+    def add_edge(self, edge, weight=1.0, lazy_add=False):
+        return self.add_edges(np.asarray(edge, np.int32).reshape(1, 2), np.array([weight], np.float32), lazy_add)
+
+    def remove_edges(self, edges):
+        if self._m() == 0:
+            return self
+        if not self.is_constructed():
+            self.construct_graph(False)
+        self._fill_weights()
+        eng = self._engine()
+        col = self._colors.tensor if self.has_colors() else None
+        m, off = eng.graph_remove_edges(self._lines.tensor, len(self._points), _t2i(eng, edges), self.is_directed,
+                                        self._weights, col)
+        self._lines = utility.Vector2iVector(self._lines.tensor[:m])
+        self._weights = self._weights[:m]
+        if col is not None:
+            self._colors = utility.Vector3fVector(col[:m])
+        self._offsets = off
+        return self
+
+    def remove_edge(self, edge):
+        return self.remove_edges(np.asarray(edge, np.int32).reshape(1, 2))
+
+    def connect_to_nearest_neighbors(self, max_edge_distance, max_num_edges=30):
+        """ConnectToNearestNeighbors: every node to its max_num_edges nearest nodes within max_edge_distance (a radius
+        search of max_num_edges + 1, the node itself among them); the weight is the distance; undirected: the reverse
+        of every new edge too; an edge already there is not added again."""
+        n = len(self._points)
+        if n == 0:
+            return self
+        knn = int(max_num_edges) + 1
+        if not 1 <= knn <= 100:
+            raise ValueError("connect_to_nearest_neighbors: max_num_edges + 1 must be in [1, 100]")
+        eng = self._engine()
+        pts = self._points.tensor
+        found, idx, _ = KDTreeFlann(self._points).search_radius(pts, float(max_edge_distance), knn)   # (a tree of its own)
+        if found < 0:
+            return self
+        i = torch.arange(n, device=pts.device, dtype=torch.int64).reshape(n, 1).expand(n, knn)
+        j = idx.to(torch.int64)
+        keep = (j >= 0) & (j != i)
+        key = i[keep] * n + j[keep]
+        if not self.is_directed:
+            key = torch.cat([key, j[keep] * n + i[keep]])
+        key = torch.unique(key)
+        if self._m():
+            have = self._lines.tensor.to(torch.int64)
+            key = key[~torch.isin(key, have[:, 0] * n + have[:, 1])]
+        new = torch.stack([key // n, key % n], dim=1).to(torch.int32).contiguous()
+        self._fill_weights()
+        had_colors = self.has_colors()
+        old_w = self._weights if self._weights is not None else torch.zeros(0, dtype=torch.float32, device=pts.device)
+        self._lines = utility.Vector2iVector(torch.cat([self._lines.tensor, new]))
+        self._weights = torch.cat([old_w, eng.graph_weights_from_distance(pts, new)])
+        if had_colors:
+            ones = torch.ones((int(new.shape[0]), 3), dtype=torch.float32, device=pts.device)
+            self._colors = utility.Vector3fVector(torch.cat([self._colors.tensor, ones]))
+        self._sorted = False
+        return self.construct_graph(False)
+
+    def add_node_and_connect(self, point, max_edge_distance=0.0, lazy_add=False):
+        """AddNodeAndConnect: the new node n gets an edge (i, n) from every node i strictly nearer than
+        max_edge_distance (and (n, i) when undirected), weighted by that distance"""
+        eng = self._engine()
+        q = np.asarray(point, np.float32).reshape(3)
+        pts = self._points.tensor
+        n = int(pts.shape[0])
+        qt = torch.from_numpy(q.copy()).to(pts.device).reshape(1, 3) if n else eng._vg_dev(q.reshape(1, 3), np.float32)
+        if n:
+            d = eng.graph_node_distances(pts, q)
+            near = torch.nonzero(d < float(np.float32(max_edge_distance))).reshape(-1)
+            edges = torch.stack([near.to(torch.int32), torch.full_like(near, n, dtype=torch.int32)], dim=1)
+            w = d[near]
+        else:
+            edges, w = torch.zeros((0, 2), dtype=torch.int32, device=qt.device), torch.zeros(0, dtype=torch.float32, device=qt.device)
+        self._points = utility.Vector3fVector(torch.cat([pts, qt]))
+        if self._node_colors is not None:
+            self._node_colors = None if not len(self._node_colors) else utility.Vector3fVector(
+                torch.cat([self._node_colors.tensor, torch.ones((1, 3), dtype=torch.float32, device=qt.device)]))
+        self._sorted = False
+        if int(edges.shape[0]) == 0:
+            return self if lazy_add or self._m() == 0 else self.construct_graph(False)
+        return self.add_edges(edges, w, lazy_add)
+
+    # ---- colours
+    def _line_match(self, edges):
+        eng = self._engine()
+        e = _t2i(eng, edges).to(torch.int64)
+        if not self.is_directed:
+            e = torch.cat([e, e.flip(1)])
+        l = self._lines.tensor.to(torch.int64)
+        big = 1 << 32
+        return torch.isin(l[:, 0] * big + l[:, 1], e[:, 0] * big + e[:, 1])
+
+    def paint_edges_color(self, edges, color):
+        if not self.has_colors():
+            self._colors = utility.Vector3fVector(torch.ones((self._m(), 3), dtype=torch.float32, device=self._lines.tensor.device))
+        c = torch.tensor(np.asarray(color, np.float32).reshape(3), device=self._lines.tensor.device)
+        self._colors.tensor[self._line_match(edges)] = c
+        return self
+
+    def paint_edge_color(self, edge, color):
+        return self.paint_edges_color(np.asarray(edge, np.int32).reshape(1, 2), color)
+
+    def paint_nodes_color(self, nodes, color):
+        """paints the listed nodes (the reference paints all of them: DESIGN section 6)"""
+        dev = self._points.tensor.device
+        if not self.has_node_colors():
+            self._node_colors = utility.Vector3fVector(torch.ones((len(self._points), 3), dtype=torch.float32, device=dev))
+        if isinstance(nodes, utility.DeviceVector):
+            nodes = nodes.tensor
+        idx = torch.as_tensor(np.asarray(nodes.cpu() if _is_torch(nodes) else nodes, np.int64).reshape(-1), device=dev)
+        self._node_colors.tensor[idx] = torch.tensor(np.asarray(color, np.float32).reshape(3), device=dev)
+        return self
+
+    def paint_node_color(self, node, color):
+        return self.paint_nodes_color([int(node)], color)
+
+    # ---- the search
+    def dijkstra_paths(self, start_node_index, end_node_index=-1, want_info=False):
+        """-> (dist float32 [n], prev int32 [n]) on the device: include/mi_icp.h states both exactly"""
+        n = len(self._points)
+        if not self.is_constructed():
+            _log_error("[DijkstraPath] this graph is not constructed.")
+            dev = self._points.tensor.device
+            return (torch.full((n,), float("inf"), dtype=torch.float32, device=dev),
+                    torch.full((n,), -1, dtype=torch.int32, device=dev))
+        self._fill_weights()
+        return self._engine().graph_sssp(self._offsets, self._lines.tensor, self._weights, n, start_node_index,
+                                         end_node_index, want_info)
+
+    def dijkstra_path(self, start_node_index, end_node_index):
+        """-> (node indices from start to end, length); ([], inf) when there is no path, ([start], 0.0) for start == end"""
+        start, end = int(start_node_index), int(end_node_index)
+        dist, prev = self.dijkstra_paths(start, end)
+        prev, length = prev.cpu().numpy(), float(dist[end].item())
+        if prev[end] < 0:
+            return [], float("inf")
+        nodes = [end]
+        while nodes[-1] != start:
+            nodes.append(int(prev[nodes[-1]]))
+            if len(nodes) > len(prev):
+                raise _lib.MiIcpError("dijkstra_path: the predecessors cycle")
+        return nodes[::-1], length
+
+    @staticmethod
+    def create_from_axis_aligned_bounding_box(*args):
+        """(bbox, resolutions) or (min_bound, max_bound, resolutions): a lattice of resolutions nodes, 26-connected,
+        constructed, weighted by distance; steps = (max - min) / resolutions, so the last node is one step short of max"""
+        if len(args) == 2:
+            box, res = args
+            lo, hi = box.get_min_bound(), box.get_max_bound()
+        else:
+            lo, hi, res = args
+        out = Graph()
+        p, l, w, o = out._engine().graph_lattice(lo, hi, res)
+        out._points, out._lines = utility.Vector3fVector(p), utility.Vector2iVector(l)
+        out._weights, out._offsets, out._sorted = w, o, True
+        return out
+
+
+def _is_torch(a):
+    return torch is not None and isinstance(a, torch.Tensor)

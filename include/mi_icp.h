@@ -1055,7 +1055,7 @@ MI_ICP_API int mi_icp_dt_get_voxels(mi_icp_ctx* ctx, mi_icp_dt* dt, float voxel_
  * directly -- a binary search in the ascending keys, or the dense log-odds plane -- so the structure is "the
  * cells near the query".  Not built: Primitives x Primitives (declared, never defined in the reference),
  * CreateVoxelGridWithSweeping, CreateTriangleMesh, Mesh primitives, a DistanceTransform as a target, and the
- * planning and kinematics modules that call these.
+ * kinematics module that calls these (planning is built: the graph family below).
  *
  * ARRAYS ARE DEVICE POINTERS (keys, points, lines, primitive records, out_pairs, out_keys, out_colors); the
  * side structs, the one primitive of voxelize_primitive, margin, counts are host memory.
@@ -1184,6 +1184,89 @@ MI_ICP_API int mi_icp_collision_voxelize_primitive(mi_icp_ctx* ctx, const mi_icp
 MI_ICP_API int mi_icp_collision_sort_keys(mi_icp_ctx* ctx, const int32_t* keys, int64_t m, int32_t* out_keys,
                                           int32_t* out_index, int64_t* m_out);
 MI_ICP_API int mi_icp_primitive_aabb(const mi_icp_primitive* primitive, float* out_min3, float* out_max3);
+
+/* ---- graph (geometry/graph.{h,cu}, graph_factory.cu; the search planning::Pos3DPlanner runs) ---------------
+ * geometry::Graph<3>: a LineSet<3> whose lines[m][2] are directed edges sorted ascending by (first, second),
+ * with edge_index_offsets[n_points + 1] (the edges of node v are offsets[v] .. offsets[v + 1]) and one weight
+ * per edge.  An undirected graph stores both directions of every edge.  Not built: Graph<2> (there is no
+ * LineSet<2>), CreateFromTriangleMesh, visualisation, file I/O, and the kinematics module.
+ *
+ * ARRAYS ARE DEVICE POINTERS (points, lines, weights, colours, offsets, the listed edges, out_dist, out_prev);
+ * counts, scalars, min3 / max3 / resolutions3 / point3 and info5 are host memory.  THE CAPACITY RULE of the
+ * collision family holds for lattice: the counts are always written, and with too little room nothing else.
+ *
+ * NUMERIC CONTRACT.  fp32 in exactly the order written; products are never fused; sqrtf correctly rounded.
+ * tests/graph_exact.py restates it in numpy; csrc/graph_rules.h holds what host and device share.
+ *  construct(lines, weights, colors, m, n_points, out_offsets)  ConstructGraph.  Sorts the lines IN PLACE,
+ *   stably: equal lines keep their input order.  weights[m] and colors[m][3] (each may be NULL) travel with
+ *   their lines.  out_offsets[v] = the number of lines whose first index is below v.  A line with an index
+ *   outside [0, n_points) is MI_ICP_ERR_INVALID with nothing written.  The sort is the library's radix sort
+ *   (csrc/primitives.h) on the key first << b | second, b the bits of n_points - 1.
+ *  weights_from_distance  SetEdgeWeightsFromDistance: with d = points[first] - points[second] per axis,
+ *   w = sqrtf((dx*dx + dy*dy) + dz*dz).  An index out of range: MI_ICP_ERR_INVALID (other lines are written).
+ *  node_distances(points, n, point3, out)  the same formula with d = points[i] - point3: what
+ *   AddNodeAndConnect compares with max_edge_distance (strictly below) and stores as the weight.
+ *  lattice(min3, max3, resolutions3, ...)  CreateFromAxisAlignedBoundingBox.  steps = (max - min) /
+ *   (float)resolution per axis (the reference's formula: the last node is one step short of max); node
+ *   (x*ry + y)*rz + z is min + (float)(x, y, z) * steps; every node has an edge to each of its up to 26
+ *   neighbours inside the lattice, written directly at their place in ascending (i, j) order with offsets and
+ *   distance weights: the count, (3rx-2)(3ry-2)(3rz-2) - rx*ry*rz, and every node's first edge are closed
+ *   forms (graph_rules.h), so there is no sort and no compaction.  Refused: a resolution < 1, more than
+ *   0x7fffff00 nodes or 2^31 - 1 edges.
+ *  set_edge_weights(lines, weights, m, edges, k, is_directed, weight)  SetEdgeWeights: every line equal to a
+ *   listed edge gets `weight`; with is_directed == 0 every line equal to the reverse of a listed edge too.
+ *   The lines must be sorted (construct).  Each listed edge (and its reverse) finds the run of its lines by a
+ *   binary search in the lines -- k log m steps and no sort of the list, against m log k and a sort the other
+ *   way round.  A listed edge that is no line changes nothing.
+ *  remove_edges(lines, weights, colors, m, n_points, edges, k, is_directed, out_offsets, m_out)  RemoveEdges:
+ *   the same matching; the lines that stay are compacted IN PLACE in their order (flags, the scan, one gather:
+ *   csrc/select.h's scheme), weights and colours with them, and the offsets rewritten.  *m_out = their count.
+ *  sssp(offsets, lines, weights, n, m, start, end, out_dist, out_prev, info5)  DijkstraPaths.
+ *   Weights are >= 0 or +inf; a negative or NaN weight is MI_ICP_ERR_INVALID, checked once on the device
+ *   before any relaxation, as are the lines' indices and the offsets' ranges.
+ *   DISTANCES.  dist[start] = 0, else dist[v] = min over edges (u, v) of (float)(dist[u] + w(u, v)), the
+ *   least such assignment; +inf where there is no path.  With such weights the fixed point is unique --
+ *   label-setting Dijkstra and Bellman-Ford in any edge order reach the same bits -- so the relaxation order
+ *   is free and the result is bit-identical on every run.  An edge of weight +inf relaxes nothing.
+ *   PREDECESSORS.  prev[start] = start; prev[v] = -1 where dist[v] is +inf; else
+ *    tier 1: the SMALLEST u with an edge (u, v), dist[u] < dist[v] and (float)(dist[u] + w) == dist[v];
+ *    tier 2, for the nodes tier 1 leaves (reached only through edges that add nothing in fp32), in rounds
+ *    until none is left: every unresolved v takes the smallest u RESOLVED BEFORE THE ROUND with an edge
+ *    (u, v), dist[u] == dist[v] and (float)(dist[u] + w) == dist[v].  (The plain "smallest tight u" lets two
+ *    nodes joined by a zero-weight edge name each other.)
+ *   EARLY END.  With end >= 0 the search stops once no open node has a tentative distance <= dist[end].  The
+ *   result equals the end = -1 result at every node whose distance is <= dist[end]; every other entry is
+ *   (+inf, -1).  An unreachable end gives the full result.
+ *   REGIMES, chosen from n and m alone (mi_icp_graph_sssp_limits).  SMALL, n <= 8192 and m <= 262144: one
+ *   workgroup keeps distance, predecessor, candidate and two open flags per node in LDS (14 bytes: 112 of
+ *   the CU's 160 KiB; twice the nodes would not fit) and streams the edges (12 bytes each: 3 MiB, inside
+ *   one XCD's 4 MiB L2) round after round to the end, predecessors included, in ONE launch.  LARGE: frontier
+ *   rounds over the whole device, node-parallel over byte flags, launched in batches of 32; a round whose
+ *   frontier is empty returns at once; the host reads one counter per batch.
+ *   info5 (host, may be NULL): regime (0 small, 1 large), launches, host waits, relaxation rounds that did
+ *   work, tier-2 rounds that resolved a node.
+ * Waits: construct once (the index check, behind the sort); weights_from_distance once; node_distances,
+ * lattice and set_edge_weights never; remove_edges once (the count); sssp once in the small regime, in the
+ * large one once for the checks, once per batch of rounds and once per predecessor pass (one without tier 2). */
+MI_ICP_API int mi_icp_graph_construct(mi_icp_ctx* ctx, int32_t* lines, float* weights, float* colors, int64_t m,
+                                      int64_t n_points, int32_t* out_offsets);
+MI_ICP_API int mi_icp_graph_weights_from_distance(mi_icp_ctx* ctx, const float* points, int64_t n_points,
+                                                  const int32_t* lines, int64_t m, float* out_weights);
+MI_ICP_API int mi_icp_graph_node_distances(mi_icp_ctx* ctx, const float* points, int64_t n_points, const float* point3,
+                                           float* out_distances);
+MI_ICP_API int mi_icp_graph_lattice(mi_icp_ctx* ctx, const float* min3, const float* max3, const int32_t* resolutions3,
+                                    float* out_points, int64_t point_capacity, int32_t* out_lines, float* out_weights,
+                                    int64_t edge_capacity, int32_t* out_offsets, int64_t* n_points, int64_t* m);
+MI_ICP_API int mi_icp_graph_set_edge_weights(mi_icp_ctx* ctx, const int32_t* lines, float* weights, int64_t m,
+                                             const int32_t* edges, int64_t k, int is_directed, float weight);
+MI_ICP_API int mi_icp_graph_remove_edges(mi_icp_ctx* ctx, int32_t* lines, float* weights, float* colors, int64_t m,
+                                         int64_t n_points, const int32_t* edges, int64_t k, int is_directed,
+                                         int32_t* out_offsets, int64_t* m_out);
+MI_ICP_API int mi_icp_graph_sssp(mi_icp_ctx* ctx, const int32_t* offsets, const int32_t* lines, const float* weights,
+                                 int64_t n, int64_t m, int64_t start, int64_t end, float* out_dist, int32_t* out_prev,
+                                 int32_t* info5);
+/* the small regime's largest n and m, and the rounds of a batch in the large one (no context, no device) */
+MI_ICP_API int mi_icp_graph_sssp_limits(int64_t* small_max_nodes, int64_t* small_max_edges, int32_t* batch_rounds);
 
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
