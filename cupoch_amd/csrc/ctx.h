@@ -76,6 +76,7 @@ struct mi_icp_ctx {
     bool links_inflight = false;
     int last_search_kind = -1;  // mi_icp_debug.h
     int last_voxel_path = -1;   // mi_icp_debug.h
+    int32_t last_voxel_plan[8] = {-1, 0, 0, 0, 0, 0, 0, 0};  // mi_icp_debug_last_voxel_plan ([0] is filled from last_voxel_path)
     mi::eng::HaloPolicy halo;    // when they are built (loop_policy.h)
     bool halo_use = false;       // the loop's launches take the halos (looked up once per chunk: an event query costs microseconds)
     mi::eng::DevBuf halo_want;            // the counter (nn_search.h kWantSlots words, summed by the host)

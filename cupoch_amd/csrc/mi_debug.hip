@@ -135,6 +135,13 @@ int mi_icp_debug_get_leaf_halos(mi_icp_ctx* c, float* halos_out) {
 int mi_icp_debug_last_search_kind(const mi_icp_ctx* c) { return c ? c->last_search_kind : -1; }
 int mi_icp_debug_last_voxel_path(const mi_icp_ctx* c) { return c ? c->last_voxel_path : -1; }
 
+int mi_icp_debug_last_voxel_plan(const mi_icp_ctx* c, int32_t out[8]) {
+    if (!c || !out) return MI_ICP_ERR_INVALID;
+    std::memcpy(out, c->last_voxel_plan, 8 * sizeof(int32_t));
+    out[0] = c->last_voxel_path;
+    return MI_ICP_OK;
+}
+
 int mi_icp_debug_occupancy(int which) {
     if (which == 0 || which == 4) return occupancy_build(which);
     if ((which >= 1 && which <= 3) || which == 9) return occupancy_loop(which);

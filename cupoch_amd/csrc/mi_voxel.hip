@@ -212,6 +212,10 @@ static int voxel_downsample_keys32(mi_icp_ctx* c, const float* const in[3], int6
         L = 0;
         passes = (bits + 7) / 8;
     }
+    int32_t* const plan = c->last_voxel_plan;
+    plan[2] = L;
+    plan[3] = passes;
+    plan[4] = passes > 0 ? 1 : 0;
     const Pay3* first[3] = {reinterpret_cast<const Pay3*>(in[0]), reinterpret_cast<const Pay3*>(in[1]), reinterpret_cast<const Pay3*>(in[2])};
     const Pay3* pay[3];
     const uint32_t* skeys;
@@ -220,6 +224,8 @@ static int voxel_downsample_keys32(mi_icp_ctx* c, const float* const in[3], int6
     if (wide) {
         // a large cloud, the key sorted whole: 11-bit digits, the keys made once, from the sorted points
         TRY(voxel_wide_sort(c, first, n, g, bits, pay));
+        plan[3] = (bits + 10) / 11;  // (voxel_wide_sort's npass)
+        plan[4] = 2;
         voxel_keys32<<<blocks_for(n), 256, 0, c->stream>>>(reinterpret_cast<const float*>(pay[0]), n, g, keys[0]);
         KCHK(c);
         skeys = keys[0];
@@ -255,6 +261,8 @@ static int voxel_downsample_keys32(mi_icp_ctx* c, const float* const in[3], int6
     TRY(read_total(c, total));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int64_t nvox = (int64_t)c->u_host[0];
+    plan[5] = L > 0 ? 1 : (n <= 16 * nvox ? 3 : 2);  // (the branches below)
+    plan[6] = (int32_t)nvox;
     TRY(cloud_emit(c, in, out, nvox, nvox, mem_kind, c->stage + 3, [&](float* const dst[3]) {
         if (L > 0) {  // a wave per run
             const int64_t rmax = (bits - L >= 31) ? n : std::min<int64_t>(n, (int64_t)1 << (bits - L));
@@ -276,6 +284,7 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
                             float* out_normals, float* out_colors, int64_t* m, int mem_kind) {
     TRY(check_sizes(c, "voxel_downsample", n, m, mem_kind));
     c->last_voxel_path = -1;
+    std::memset(c->last_voxel_plan, 0, sizeof(c->last_voxel_plan));  // (mi_icp_debug_last_voxel_plan: what this call decides, below)
     if (n == 0 || !(voxel > 0.0f)) return MI_ICP_OK;  // down_sample.cu:173-176
     Cloud cl{{xyz, normals, colors}, {out_xyz, out_normals, out_colors}};
     TRY(cloud_in(c, "voxel_downsample", &cl, n, mem_kind, c->stage));
@@ -312,6 +321,11 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
         if (dst[0] != out[0]) HIPCHK(c, hipStreamSynchronize(c->stream));  // (staged: the copies; device arrays: already waited for)
         *m = nvox;
         c->last_voxel_path = 1;
+        {   // the plan word: the key's bits as the device plan counted them (the same bounds, the same function); no sort, vx_finish
+            const VoxelGridFit df = voxel_grid_fit(c->f_host, voxel);
+            c->last_voxel_plan[1] = df.bits[0] + df.bits[1] + df.bits[2];
+            c->last_voxel_plan[6] = (int32_t)nvox;
+        }
         return MI_ICP_OK;
     }
     const VoxelGridFit f = voxel_grid_fit(c->f_host, voxel);
@@ -319,6 +333,8 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
     c->last_voxel_path = 0;
     const VoxelGrid& g = f.g;
     const int bits = f.bits[0] + f.bits[1] + f.bits[2];
+    int32_t* const plan = c->last_voxel_plan;
+    plan[1] = bits;
 
     // (grids whose packed key needs more than 32 bits keep the first form below: 64-bit keys + indices, one gather)
     if (bits <= 32) return voxel_downsample_keys32(c, in, n, g, bits, out, m, mem_kind);
@@ -333,6 +349,8 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
         voxel_keys<<<nb, 256, 0, c->stream>>>(dp, n, g, -1, nullptr, sb.keys[0], sb.vals[0]);
         KCHK(c);
         const int cur = radix_sort_pairs<uint64_t>(c->stream, sb, n, bits);
+        plan[3] = (bits + 7) / 8;  // (radix_sort_pairs' passes)
+        plan[4] = 3;
         order = sb.vals[cur];
         packed_sorted = sb.keys[cur];
     } else {
@@ -347,7 +365,9 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
             voxel_keys<<<nb, 256, 0, c->stream>>>(dp, n, g, axis, tmp_order, sb.keys[0], sb.vals[0]);
             KCHK(c);
             prev = sb.vals[radix_sort_pairs<uint64_t>(c->stream, sb, n, f.bits[axis])];
+            plan[3] += (f.bits[axis] + 7) / 8;
         }
+        plan[4] = 4;
         order = prev;
     }
     KCHK(c);
@@ -362,6 +382,8 @@ int mi_icp_voxel_downsample(mi_icp_ctx* c, const float* xyz, const float* normal
     TRY(read_total(c, total));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int64_t nvox = (int64_t)c->u_host[0];
+    plan[5] = 4;
+    plan[6] = (int32_t)nvox;
     // `order` may live in seg_start's buffer only in the fallback's intermediate rounds, never at the end
     TRY(ensure(c, c->seg_start, (size_t)n + 1, &seg_start));
     voxel_seg_starts<<<nb, 256, 0, c->stream>>>(head, pos, n, seg_start);

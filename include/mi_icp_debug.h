@@ -44,6 +44,13 @@ MI_ICP_API int mi_icp_debug_last_search_kind(const mi_icp_ctx* ctx);
  * early: an empty cloud, a voxel size <= 0, a grid beyond int32).  Both are exact; tests run each on purpose
  * (the switch MI_ICP_NO_DENSE_VOXEL is read at every call). */
 MI_ICP_API int mi_icp_debug_last_voxel_path(const mi_icp_ctx* ctx);
+/* What the last mi_icp_voxel_downsample call ran, as the host decided it (csrc/mi_voxel.hip; no launch, no wait):
+ * out[0] = the path as above (-1 / 0 / 1), [1] = the packed key's bits (x + y + z), [2] = L (the low key bits left
+ * unsorted), [3] = sort passes, [4] = sort kind (0 none, 1 payload radix of 8-bit digits, 2 wide sort of 11-bit digits,
+ * 3 64-bit (key, index) pairs, 4 three sorts, one per axis), [5] = means kernel (0 vx_finish of the dense path,
+ * 1 voxel_means_wave, 2 voxel_means_runs, 3 voxel_means_thread, 4 voxel_means), [6] = voxels written, [7] = 0.
+ * The dense path sorts nothing: [2] .. [5] are 0 there.  A call that returned early leaves [1] .. [7] zero. */
+MI_ICP_API int mi_icp_debug_last_voxel_plan(const mi_icp_ctx* ctx, int32_t out[8]);
 /* Resident workgroups per CU the runtime grants a kernel at its launch shape (hipOccupancyMaxActiveBlocksPerMultiprocessor):
  * which = 0 kd_build_groups, 1 nn_packet_kernel<seeded>, 2 nn_packet_kernel<from the root>, 3 reduce_pt2pl_kernel<2,1> with the pair stream,
  * 4 leaf_halo_build, 5 rs_scatter_pay<8>, 6 voxel_means_wave, 7 vx_scatter<1>, 8 vx_finish<points only>,
