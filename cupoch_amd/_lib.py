@@ -266,8 +266,12 @@ SIGNATURES = {
     "mi_icp_get_profile": (_I, [_P, _P]),
     # include/mi_icp_debug.h (test-only)
     "mi_icp_debug_sort_pairs": (_I, [_P, _P, _P, _L, _I]),
+    "mi_icp_debug_sort_pairs32": (_I, [_P, _P, _P, _L, _I]),
+    "mi_icp_debug_sort_payload32": (_I, [_P, _P, _P, _P, _P, _L, _I, _I]),
+    "mi_icp_debug_sort_plan": (_I, [_L, _P]),
     "mi_icp_debug_exclusive_scan": (_I, [_P, _P, _P, _L, _P]),
     "mi_icp_debug_morton_order": (_I, [_P, _P, _L, _P]),
+    "mi_icp_debug_morton_order_bits": (_I, [_P, _P, _L, _I, _P]),
     "mi_icp_debug_nn_stats": (_I, [_P, _P, _F, _I, _P]),
     "mi_icp_debug_nn_stats8": (_I, [_P, _P, _F, _I, _P]),
     "mi_icp_debug_get_tree": (_I, [_P, C.POINTER(_L), _P, _P]),

@@ -69,6 +69,88 @@ int mi_icp_debug_sort_pairs(mi_icp_ctx* c, uint64_t* keys, uint32_t* vals, int64
     return MI_ICP_OK;
 }
 
+int mi_icp_debug_sort_pairs32(mi_icp_ctx* c, uint32_t* keys, uint32_t* vals, int64_t n, int key_bits) {
+    TRY(check_ctx(c));
+    if (n < 0 || key_bits < 1 || key_bits > 32 || (n > 0 && (!keys || !vals)))
+        return fail(c, MI_ICP_ERR_INVALID, "debug_sort_pairs32: bad arguments");
+    if (n == 0) return MI_ICP_OK;
+    SortBuffers sb;
+    TRY(sort_buffers(c, n, &sb));
+    uint32_t* const dkeys[2] = {reinterpret_cast<uint32_t*>(sb.keys[0]), reinterpret_cast<uint32_t*>(sb.keys[1])};
+    HIPCHK(c, hipMemcpyAsync(dkeys[0], keys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sb.vals[0], vals, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    const int cur = radix_sort_pairs<uint32_t>(c->stream, sb, n, key_bits);
+    KCHK(c);
+    HIPCHK(c, hipMemcpyAsync(keys, dkeys[cur], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(vals, sb.vals[cur], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MI_ICP_OK;
+}
+
+int mi_icp_debug_sort_payload32(mi_icp_ctx* c, uint32_t* keys, float* a0, float* a1, float* a2, int64_t n, int lo_bit,
+                                int hi_bit) {
+    TRY(check_ctx(c));
+    if (n < 0 || lo_bit < 0 || hi_bit > 32 || lo_bit > hi_bit || (n > 0 && !keys))
+        return fail(c, MI_ICP_ERR_INVALID, "debug_sort_payload32: bad arguments");
+    if (n == 0) return MI_ICP_OK;
+    float* const host[3] = {a0, a1, a2};
+    // every buffer first (ensure may wait and free), then the copies: the caller's arrays through stage[0..2], the
+    // passes' two scratch sets in vpay as voxel_downsample_keys32 takes them (one set for a single pass)
+    SortBuffers sb;
+    TRY(sort_buffers(c, n, &sb));
+    const int passes = (hi_bit - lo_bit + 7) / 8;
+    Pay3* scratch[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    for (int set = 0; set < std::min(passes, 2); ++set)
+        for (int a = 0; a < 3; ++a)
+            if (host[a]) TRY(ensure(c, c->vpay[set * 3 + a], (size_t)n, &scratch[set][a]));
+    const Pay3* first[3] = {nullptr, nullptr, nullptr};
+    for (int a = 0; a < 3; ++a) {
+        const float* d;
+        TRY(to_device(c, (const float*)host[a], (size_t)n * 3, MI_ICP_HOST, c->stage[a], &d));
+        first[a] = reinterpret_cast<const Pay3*>(d);
+    }
+    uint32_t* const dkeys[2] = {reinterpret_cast<uint32_t*>(sb.keys[0]), reinterpret_cast<uint32_t*>(sb.keys[1])};
+    HIPCHK(c, hipMemcpyAsync(dkeys[0], keys, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    const Pay3* pay[3];
+    const int cur = radix_sort_payload32(c->stream, sb, first, scratch, n, lo_bit, hi_bit, pay);
+    KCHK(c);
+    HIPCHK(c, hipMemcpyAsync(keys, dkeys[cur], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    for (int a = 0; a < 3; ++a)
+        if (host[a]) HIPCHK(c, hipMemcpyAsync(host[a], pay[a], (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MI_ICP_OK;
+}
+
+int mi_icp_debug_sort_plan(int64_t n, int32_t out[8]) {
+    if (n < 1 || !out) return MI_ICP_ERR_INVALID;
+    const int pair_chunks = sort_chunks_for(kPairTiers, n), pay_chunks = sort_chunks_for(kPayTiers, n);
+    const int hist = sort_hist_segments(n);
+    out[0] = n <= kSortWholeMax ? 1 : 0;
+    out[1] = pair_chunks;
+    out[2] = sort_num_segments(n, pair_chunks);
+    out[3] = pay_chunks;
+    out[4] = sort_num_segments(n, pay_chunks);
+    out[5] = hist;
+    out[6] = scan_num_tiles((int64_t)256 * hist);
+    out[7] = 0;
+    return MI_ICP_OK;
+}
+
+int mi_icp_debug_morton_order_bits(mi_icp_ctx* c, const float* xyz, int64_t n, int bits, uint32_t* order_out) {
+    TRY(check_ctx(c));
+    if (n <= 0 || n > 0x7fffff00ll || bits < 1 || bits > 21 || !xyz || !order_out)
+        return fail(c, MI_ICP_ERR_INVALID, "debug_morton_order_bits: bad arguments");
+    const float* d_pts;
+    TRY(to_device(c, xyz, (size_t)n * 3, MI_ICP_HOST, c->stage[0], &d_pts));
+    float* bnd;
+    TRY(compute_bounds(c, d_pts, n, &bnd));
+    const uint32_t* order;
+    TRY(morton_order(c, d_pts, n, &order, bnd, bits, nullptr));  // (morton_order's grid_bounds / grid_bits form)
+    TRY(from_device(c, order, order_out, (size_t)n, MI_ICP_HOST));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MI_ICP_OK;
+}
+
 int mi_icp_debug_exclusive_scan(mi_icp_ctx* c, const uint32_t* in, uint32_t* out, int64_t n,
                                 uint64_t* total) {
     TRY(check_ctx(c));

@@ -15,12 +15,31 @@ extern "C" {
 /* stable LSD radix sort of (key, value) pairs by the low key_bits bits, in place */
 MI_ICP_API int mi_icp_debug_sort_pairs(mi_icp_ctx* ctx, uint64_t* keys, uint32_t* vals,
                                        int64_t n, int key_bits);
+/* the same sort in its narrow form (32-bit keys: radix_sort_pairs<uint32_t>), key_bits 1 .. 32 */
+MI_ICP_API int mi_icp_debug_sort_pairs32(mi_icp_ctx* ctx, uint32_t* keys, uint32_t* vals,
+                                         int64_t n, int key_bits);
+/* the payload form (radix_sort_payload32): 32-bit keys sorted stably on the bits [lo_bit, hi_bit), up to three arrays
+ * of n * 3 floats (NULL: absent) travelling with them; keys and the present arrays are sorted in place.
+ * 0 <= lo_bit <= hi_bit <= 32, else MI_ICP_ERR_INVALID; lo_bit == hi_bit is no pass: the input comes back unchanged. */
+MI_ICP_API int mi_icp_debug_sort_payload32(mi_icp_ctx* ctx, uint32_t* keys, float* a0, float* a1, float* a2,
+                                           int64_t n, int lo_bit, int hi_bit);
+/* What the sort drivers choose for n >= 1 elements, from the drivers' own tables (csrc/primitives.h; no context, no GPU
+ * call): out[0] = 1 if the pair sort takes its one-launch path (tiles of 2048, whatever [1] and [2] say), [1] = the
+ * pair tiers' 64-element chunks per wave (a tile is 512 * chunks elements), [2] = the tiles of that size in n,
+ * [3], [4] = the same of the payload sort, [5] = sort_hist_segments(n): the histogram segments a buffer set for n
+ * holds, for every sort of m <= n elements, [6] = scan_num_tiles(256 * [5]), [7] = 0. */
+MI_ICP_API int mi_icp_debug_sort_plan(int64_t n, int32_t out[8]);
 /* out[i] = sum of in[0..i); *total = sum of all (out may alias in) */
 MI_ICP_API int mi_icp_debug_exclusive_scan(mi_icp_ctx* ctx, const uint32_t* in, uint32_t* out,
                                            int64_t n, uint64_t* total);
 /* Morton order of a cloud as the engine computes it: order[sorted] = original */
 MI_ICP_API int mi_icp_debug_morton_order(mi_icp_ctx* ctx, const float* xyz, int64_t n,
                                          uint32_t* order);
+/* The same order on the cloud's own bounds with a grid of 2^bits cells per axis given from outside (bits 1 .. 21:
+ * morton_order's grid_bits form).  The engine's own choice of bits stays at or below 10
+ * (32-bit keys) for every cloud below 2^30 points; 3 * bits > 32 runs the 64-bit keys and their sort. */
+MI_ICP_API int mi_icp_debug_morton_order_bits(mi_icp_ctx* ctx, const float* xyz, int64_t n, int bits,
+                                              uint32_t* order);
 /* traversal census of one nearest-neighbour pass: out4 = {node visits summed over
  * packets, leaf visits, packets, visits (nodes + leaves) of the slowest packet}.
  * use_seed != 0 seeds from the previous pass. */
