@@ -18,7 +18,7 @@ namespace geometry {
 
 class Geometry {
 public:
-    enum class GeometryType { Unspecified = 0, PointCloud = 1, VoxelGrid = 2, OccupancyGrid = 3, DistanceTransform = 4, LineSet = 5, Graph = 6, AxisAlignedBoundingBox = 13 };  // geometry.h:37-68
+    enum class GeometryType { Unspecified = 0, PointCloud = 1, VoxelGrid = 2, OccupancyGrid = 3, DistanceTransform = 4, LineSet = 5, Graph = 6, AxisAlignedBoundingBox = 13, LaserScanBuffer = 14 };  // geometry.h:37-68
     virtual ~Geometry() {}
     GeometryType GetGeometryType() const { return type_; }
     int Dimension() const { return dimension_; }
@@ -35,6 +35,7 @@ private:
 
 class AxisAlignedBoundingBox3;
 class OccupancyGrid;
+class LaserScanBuffer;
 
 /// geometry/geometry_base.h:33-90 with VectorT = Vector3f, MatrixT = Matrix3f, TransformT = Matrix4f
 class GeometryBase3D : public Geometry {
@@ -206,6 +207,9 @@ public:
                                                            float depth_cutoff = -1.0f, bool compute_normals = false);
     /// pointcloud_factory.cu:418-430: the centres of the grid's occupied voxels, every colour (0, 0, 1)
     static std::shared_ptr<PointCloud> CreateFromOccupancyGrid(const OccupancyGrid& occgrid);
+    /// pointcloud_factory.cu:375-420: the LIVE scans' readings inside [min_range, max_range] as points in the frame of their
+    /// origins, oldest scan first, non-finite points removed; intensities become grey colours (include/mi_icp.h "laserscan")
+    static std::shared_ptr<PointCloud> CreateFromLaserScanBuffer(const LaserScanBuffer& scan, float min_range, float max_range);
 
 public:
     utility::device_vector<Eigen::Vector3f> points_;

@@ -2438,4 +2438,326 @@ std::tuple<Eigen::Matrix4f, bool> PoseEstimation(const KinfuOption& option, cons
 
 }  // namespace kinfu
 
+// ---------------------------------------------------------------- geometry::LaserScanBuffer (laserscanbuffer.cu, laserscanbuffer_factory.cu) over mi_icp_laserscan_*
+namespace geometry {
+
+namespace {
+// a*b, every element ((a0*b0 + a1*b1) + a2*b2) + a3*b3 (include/mi_icp.h "laserscan")
+Eigen::Matrix4f Mul4(const Eigen::Matrix4f& a, const Eigen::Matrix4f& b) {
+    Eigen::Matrix4f out;
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) out(r, c) = ((a(r, 0) * b(0, c) + a(r, 1) * b(1, c)) + a(r, 2) * b(2, c)) + a(r, 3) * b(3, c);
+    return out;
+}
+
+Eigen::Matrix4f QuarterTurnX() {  // the exact -pi/2 about X: rows (1,0,0), (0,0,1), (0,-1,0)
+    Eigen::Matrix4f q = Eigen::Matrix4f::Identity();
+    q(1, 1) = 0.0f;
+    q(1, 2) = 1.0f;
+    q(2, 1) = -1.0f;
+    q(2, 2) = 0.0f;
+    return q;
+}
+
+void MakeStorage(LaserScanBuffer* b, bool with_intensities) {
+    const size_t count = (size_t)b->num_max_scans_ * (size_t)b->num_steps_;
+    if (b->ranges_.size() != count) {
+        b->ranges_ = std::vector<float>(count, std::numeric_limits<float>::quiet_NaN());
+    }
+    if (with_intensities && b->intensities_.size() != count) b->intensities_ = std::vector<float>(count, 0.0f);
+}
+
+// one scan into the ring; `device`: where ranges / intensities live
+LaserScanBuffer& AddScan(LaserScanBuffer* b, const float* ranges, size_t n, const Eigen::Matrix4f& transformation,
+                         const float* intensities, size_t ni, bool device) {
+    if ((int)n != b->num_steps_ || b->num_max_scans_ < 1) {
+        LogError("[AddRanges] Invalid size of input ranges.");
+        return *b;
+    }
+    if (b->HasIntensities() && n != ni) {
+        LogError("[AddRanges] Invalid size of intensities.");
+        return *b;
+    }
+    const bool first_with = b->IsEmpty() && !b->HasIntensities() && ni == n;
+    MakeStorage(b, first_with);
+    if (b->IsFull()) b->top_++;
+    const size_t slot = (size_t)(b->bottom_ % b->num_max_scans_), bytes = n * sizeof(float);
+    auto put = device ? utility::copy_d2d : utility::copy_h2d;
+    put(b->ranges_.data() + slot * n, ranges, bytes);
+    if (b->HasIntensities()) put(b->intensities_.data() + slot * n, intensities, bytes);
+    b->origins_[slot] = transformation;
+    b->bottom_++;
+    return *b;
+}
+
+std::vector<float> Live(const LaserScanBuffer& b, const utility::device_vector<float>& store) {
+    std::vector<float> out;
+    if (store.empty()) return out;
+    const size_t n = (size_t)b.num_steps_;
+    out.resize((size_t)b.GetNumScans() * n);
+    for (int k = 0; k < b.GetNumScans(); ++k)
+        utility::copy_d2h(out.data() + (size_t)k * n, store.data() + (size_t)((b.top_ + k) % b.num_max_scans_) * n, n * sizeof(float));
+    return out;
+}
+
+bool FactoryCheck(const char* what, const char* low_name, const char* high_name, float angle_increment, float low, float high,
+                  float min_range, float max_range, float min_angle, float max_angle) {
+    std::string msg;
+    if (!(angle_increment > 0.0f)) msg = "angle_increment must be positive.";
+    else if (!(low < high)) msg = std::string(low_name) + " must be smaller than " + high_name + ".";
+    else if (!(min_range < max_range)) msg = "min_range must be smaller than max_range.";
+    else if (!(min_angle < max_angle)) msg = "min_angle must be smaller than max_angle.";
+    if (msg.empty()) return true;
+    LogError((std::string("[LaserScanBuffer::") + what + "] " + msg).c_str());
+    return false;
+}
+
+// the factories' buffer: max(DEFAULT_NUM_MAX_SCANS, divisions) NaN slots with their origins, `divisions` of them live
+std::shared_ptr<LaserScanBuffer> FactoryBuffer(float angle_increment, float low, float high, unsigned int divisions, float min_angle,
+                                               float max_angle, const Eigen::Matrix4f* left) {
+    const float q = std::ceil((max_angle - min_angle) / angle_increment);
+    int64_t lds = 0, most = 0;
+    mi_icp_laserscan_limits(&lds, &most);
+    if (!(q >= 1.0f && q <= (float)most) || divisions < 1 || (double)q * divisions > (double)most) {
+        LogError("[LaserScanBuffer] too many bins, or none.");
+        return nullptr;
+    }
+    auto out = std::make_shared<LaserScanBuffer>((int)q, (int)std::max(DEFAULT_NUM_MAX_SCANS, divisions), min_angle, max_angle);
+    MakeStorage(out.get(), false);
+    for (int i = 0; i < out->num_max_scans_; ++i) {
+        Eigen::Matrix4f o = Eigen::Matrix4f::Identity();
+        o(2, 3) = low + ((high - low) * (float)i) / (float)divisions;
+        out->origins_[(size_t)i] = left ? Mul4(*left, o) : o;
+    }
+    out->bottom_ = (int)divisions;
+    return out;
+}
+}  // namespace
+
+LaserScanBuffer::LaserScanBuffer(int num_steps, int num_max_scans, float min_angle, float max_angle)
+    : GeometryBase3D(GeometryType::LaserScanBuffer),
+      num_steps_(num_steps),
+      num_max_scans_(num_max_scans),
+      min_angle_(min_angle),
+      max_angle_(max_angle),
+      origins_((size_t)std::max(num_max_scans, 0), Eigen::Matrix4f::Identity()) {}
+LaserScanBuffer::~LaserScanBuffer() {}
+LaserScanBuffer::LaserScanBuffer(const LaserScanBuffer& other)
+    : GeometryBase3D(GeometryType::LaserScanBuffer),
+      ranges_(other.ranges_),
+      intensities_(other.intensities_),
+      top_(other.top_),
+      bottom_(other.bottom_),
+      num_steps_(other.num_steps_),
+      num_max_scans_(other.num_max_scans_),
+      min_angle_(other.min_angle_),
+      max_angle_(other.max_angle_),
+      origins_(other.origins_) {}
+
+thrust::host_vector<float> LaserScanBuffer::GetRanges() const { return Live(*this, ranges_); }
+thrust::host_vector<float> LaserScanBuffer::GetIntensities() const { return Live(*this, intensities_); }
+
+LaserScanBuffer& LaserScanBuffer::Clear() {
+    top_ = bottom_ = 0;
+    ranges_ = utility::device_vector<float>();
+    intensities_ = utility::device_vector<float>();
+    std::fill(origins_.begin(), origins_.end(), Eigen::Matrix4f::Identity());
+    return *this;
+}
+bool LaserScanBuffer::IsEmpty() const { return bottom_ == top_; }
+
+Eigen::Vector3f LaserScanBuffer::GetMinBound() const {
+    LogError("LaserScanBuffer::GetMinBound is not supported");
+    return Eigen::Vector3f::Zero();
+}
+Eigen::Vector3f LaserScanBuffer::GetMaxBound() const {
+    LogError("LaserScanBuffer::GetMaxBound is not supported");
+    return Eigen::Vector3f::Zero();
+}
+Eigen::Vector3f LaserScanBuffer::GetCenter() const {
+    LogError("LaserScanBuffer::GetCenter is not supported");
+    return Eigen::Vector3f::Zero();
+}
+AxisAlignedBoundingBox<3> LaserScanBuffer::GetAxisAlignedBoundingBox() const {
+    LogError("LaserScanBuffer::GetAxisAlignedBoundingBox is not supported");
+    return AxisAlignedBoundingBox<3>();
+}
+
+LaserScanBuffer& LaserScanBuffer::Transform(const Eigen::Matrix4f& transformation) {
+    for (auto& o : origins_) o = Mul4(o, transformation);
+    return *this;
+}
+LaserScanBuffer& LaserScanBuffer::Translate(const Eigen::Vector3f& translation, bool) {
+    for (auto& o : origins_)
+        for (int r = 0; r < 3; ++r) o(r, 3) = o(r, 3) + translation(r);
+    return *this;
+}
+LaserScanBuffer& LaserScanBuffer::Scale(const float scale, bool) {
+    Check(mi_icp_laserscan_scale(Engine(), ranges_.data(), (int64_t)ranges_.size(), scale));
+    return *this;
+}
+LaserScanBuffer& LaserScanBuffer::Rotate(const Eigen::Matrix3f& R, bool) {
+    for (auto& o : origins_) {
+        const Eigen::Matrix4f a = o;
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) o(r, c) = (a(r, 0) * R(0, c) + a(r, 1) * R(1, c)) + a(r, 2) * R(2, c);
+    }
+    return *this;
+}
+
+LaserScanBuffer& LaserScanBuffer::AddRanges(const utility::device_vector<float>& ranges, const Eigen::Matrix4f& transformation,
+                                            const utility::device_vector<float>& intensities) {
+    return AddScan(this, ranges.data(), ranges.size(), transformation, intensities.data(), intensities.size(), true);
+}
+LaserScanBuffer& LaserScanBuffer::AddRanges(const thrust::host_vector<float>& ranges, const Eigen::Matrix4f& transformation,
+                                            const thrust::host_vector<float>& intensities) {
+    return AddScan(this, ranges.data(), ranges.size(), transformation, intensities.data(), intensities.size(), false);
+}
+LaserScanBuffer& LaserScanBuffer::AddRanges(const float* ranges, const Eigen::Matrix4f& transformation, const float* intensities) {
+    return AddScan(this, ranges, ranges ? (size_t)num_steps_ : 0, transformation, intensities, intensities ? (size_t)num_steps_ : 0, false);
+}
+
+LaserScanBuffer& LaserScanBuffer::Merge(const LaserScanBuffer& other) {
+    if (other.IsEmpty()) {
+        LogError("[Merge] Input buffer is empty.");
+        return *this;
+    }
+    if (other.num_steps_ != num_steps_) {
+        LogError("[Merge] Input buffer has different num_steps.");
+        return *this;
+    }
+    if (other.HasIntensities() != HasIntensities()) {
+        LogError("[Merge] Input buffer has different intensities.");
+        return *this;
+    }
+    if (other.min_angle_ != min_angle_ || other.max_angle_ != max_angle_) {
+        LogError("[Merge] Input buffer has different angle range.");
+        return *this;
+    }
+    if (other.bottom_ - other.top_ + bottom_ - top_ > num_max_scans_) {
+        LogError("[Merge] Buffer is full.");
+        return *this;
+    }
+    const size_t n = (size_t)num_steps_;
+    for (int k = 0; k < other.GetNumScans(); ++k) {
+        const size_t slot = (size_t)((other.top_ + k) % other.num_max_scans_);
+        AddScan(this, other.ranges_.data() + slot * n, n, other.origins_[slot],
+                other.HasIntensities() ? other.intensities_.data() + slot * n : nullptr, other.HasIntensities() ? n : 0, true);
+    }
+    return *this;
+}
+
+std::shared_ptr<LaserScanBuffer> LaserScanBuffer::PopOneScan() {
+    if (IsEmpty()) {
+        LogError("[PopRange] Buffer is empty.");
+        return nullptr;
+    }
+    const size_t slot = (size_t)(top_ % num_max_scans_), n = (size_t)num_steps_;
+    auto out = std::make_shared<LaserScanBuffer>(num_steps_, num_max_scans_, min_angle_, max_angle_);
+    AddScan(out.get(), ranges_.data() + slot * n, n, origins_[slot], HasIntensities() ? intensities_.data() + slot * n : nullptr,
+            HasIntensities() ? n : 0, true);
+    top_++;
+    return out;
+}
+
+std::pair<std::unique_ptr<utility::pinned_host_vector<float>>, std::unique_ptr<utility::pinned_host_vector<float>>>
+LaserScanBuffer::PopHostOneScan() {
+    auto r = std::make_unique<utility::pinned_host_vector<float>>();
+    auto v = std::make_unique<utility::pinned_host_vector<float>>();
+    if (IsEmpty()) {
+        LogError("[PopRange] Buffer is empty.");
+        return std::make_pair(std::move(r), std::move(v));
+    }
+    const size_t slot = (size_t)(top_ % num_max_scans_), n = (size_t)num_steps_;
+    r->resize(n);
+    utility::copy_d2h(r->data(), ranges_.data() + slot * n, n * sizeof(float));
+    if (HasIntensities()) {
+        v->resize(n);
+        utility::copy_d2h(v->data(), intensities_.data() + slot * n, n * sizeof(float));
+    }
+    top_++;
+    return std::make_pair(std::move(r), std::move(v));
+}
+
+std::shared_ptr<LaserScanBuffer> LaserScanBuffer::RangeFilter(float min_range, float max_range) const {
+    auto out = std::make_shared<LaserScanBuffer>(*this);
+    if (max_range <= min_range) LogError("[RangeFilter] Invalid parameter with min_range greater than max_range.");
+    Check(mi_icp_laserscan_range_filter(Engine(), ranges_.data(), (int64_t)ranges_.size(), min_range, max_range, out->ranges_.data()));
+    return out;
+}
+
+std::shared_ptr<LaserScanBuffer> LaserScanBuffer::ScanShadowsFilter(float min_angle, float max_angle, int window, int neighbors,
+                                                                    bool remove_shadow_start_point) const {
+    auto out = std::make_shared<LaserScanBuffer>(*this);
+    if (ranges_.empty()) return out;
+    Check(mi_icp_laserscan_shadow_filter(Engine(), ranges_.data(), num_steps_, num_max_scans_, min_angle_, max_angle_, min_angle,
+                                         max_angle, window, neighbors, remove_shadow_start_point ? 1 : 0, out->ranges_.data()));
+    return out;
+}
+
+std::shared_ptr<LaserScanBuffer> LaserScanBuffer::CreateFromPointCloud(const geometry::PointCloud& pcd, float angle_increment,
+                                                                       float min_height, float max_height,
+                                                                       unsigned int num_vertical_divisions, float min_range,
+                                                                       float max_range, float min_angle, float max_angle) {
+    if (!FactoryCheck("CreateFromPointCloud", "min_height", "max_height", angle_increment, min_height, max_height, min_range,
+                      max_range, min_angle, max_angle))
+        return nullptr;
+    auto out = FactoryBuffer(angle_increment, min_height, max_height, num_vertical_divisions, min_angle, max_angle, nullptr);
+    if (!out) return nullptr;
+    Check(mi_icp_laserscan_from_points(Engine(), Ptr(pcd.points_), (int64_t)pcd.points_.size(), angle_increment, min_height, max_height,
+                                       (int32_t)num_vertical_divisions, min_range, max_range, min_angle, max_angle, out->num_steps_,
+                                       out->ranges_.data(), nullptr));
+    return out;
+}
+
+std::shared_ptr<LaserScanBuffer> LaserScanBuffer::CreateFromDepthImage(const geometry::Image& depth,
+                                                                       const camera::PinholeCameraIntrinsic& intrinsic,
+                                                                       float angle_increment, float min_y, float max_y,
+                                                                       unsigned int num_vertical_divisions, float min_range,
+                                                                       float max_range, float min_angle, float max_angle,
+                                                                       float depth_scale, float depth_trunc, int stride) {
+    if (!FactoryCheck("CreateFromDepthImage", "min_y", "max_y", angle_increment, min_y, max_y, min_range, max_range, min_angle,
+                      max_angle))
+        return nullptr;
+    if (depth.num_of_channels_ != 1 || (depth.bytes_per_channel_ != 2 && depth.bytes_per_channel_ != 4) || stride < 1) {
+        LogError("[LaserScanBuffer::CreateFromDepthImage] Unsupported image format.");
+        return nullptr;
+    }
+    const Eigen::Matrix4f q = QuarterTurnX();
+    auto out = FactoryBuffer(angle_increment, min_y, max_y, num_vertical_divisions, min_angle, max_angle, &q);
+    if (!out) return nullptr;
+    const float k4[4] = {intrinsic.fx_, intrinsic.fy_, intrinsic.cx_, intrinsic.cy_};
+    Check(mi_icp_laserscan_from_depth(Engine(), depth.data_.data(), depth.bytes_per_channel_ == 2 ? MI_ICP_DEPTH_U16 : MI_ICP_DEPTH_F32,
+                                      depth.width_, depth.height_, k4, depth_scale, depth_trunc, stride, angle_increment, min_y, max_y,
+                                      (int32_t)num_vertical_divisions, min_range, max_range, min_angle, max_angle, out->num_steps_,
+                                      out->ranges_.data(), nullptr));
+    return out;
+}
+
+std::shared_ptr<PointCloud> PointCloud::CreateFromLaserScanBuffer(const LaserScanBuffer& scan, float min_range, float max_range) {
+    auto out = std::make_shared<PointCloud>();
+    if (scan.ranges_.size() == 0 || scan.IsEmpty()) {
+        LogError("[PointCloud::CreateFromLaserScanBuffer] Empty scan, return empty pointcloud.");
+        return out;
+    }
+    if (min_range >= max_range) {
+        LogError("[PointCloud::CreateFromLaserScanBuffer] min_range must be smaller than max_range.");
+        return out;
+    }
+    const size_t room = (size_t)scan.GetNumScans() * (size_t)scan.num_steps_;
+    out->points_.resize(room);
+    if (scan.HasIntensities()) out->colors_.resize(room);
+    int64_t m = 0;
+    Check(mi_icp_laserscan_to_points(Engine(), scan.ranges_.data(), scan.HasIntensities() ? scan.intensities_.data() : nullptr,
+                                     scan.origins_.data()->data(), scan.num_steps_, scan.num_max_scans_, scan.top_ % scan.num_max_scans_,
+                                     scan.GetNumScans(), scan.min_angle_, scan.max_angle_, min_range, max_range,
+                                     out->points_.data()->data(), scan.HasIntensities() ? out->colors_.data()->data() : nullptr,
+                                     (int64_t)room, &m));
+    out->points_.resize((size_t)m);
+    if (scan.HasIntensities()) out->colors_.resize((size_t)m);
+    return out;
+}
+
+}  // namespace geometry
+
 }  // namespace cupoch

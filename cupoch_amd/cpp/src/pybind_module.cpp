@@ -35,6 +35,7 @@
 #include "cupoch/geometry/graph.h"
 #include "cupoch/geometry/image.h"
 #include "cupoch/geometry/keypoint.h"
+#include "cupoch/geometry/laserscanbuffer.h"
 #include "cupoch/geometry/occupancygrid.h"
 #include "cupoch/geometry/pointcloud.h"
 #include "cupoch/geometry/voxelgrid.h"
@@ -1120,6 +1121,72 @@ PYBIND11_MODULE(cupoch_pybind, m) {
                             return Graph3::CreateFromAxisAlignedBoundingBox(to_vector3(lo), to_vector3(hi), Eigen::Vector3i(res.data()[0], res.data()[1], res.data()[2]));
                         },
                         "min_bound"_a, "max_bound"_a, "resolutions"_a);
+
+    // geometry.LaserScanBuffer (cupoch_pybind/geometry/laserscanbuffer.cpp): the reference's names and defaults, except
+    // min_angle, which is -pi here (the reference's binding says +pi: with max_angle = +pi an empty angle range).  Scans go
+    // in and come out as numpy float32 arrays; `ranges` / `intensities` are the live scans, oldest first.
+    typedef geometry::LaserScanBuffer Scan;
+    auto scan_rows = [](const std::vector<float>& h) { return farray(h.size(), h.data()); };
+    auto scan_add = [](std::shared_ptr<Scan> s, const farray& ranges, const farray& T, const farray& intensities) {
+        s->AddRanges(std::vector<float>(ranges.data(), ranges.data() + ranges.size()), to_matrix4(T),
+                     std::vector<float>(intensities.data(), intensities.data() + intensities.size()));
+        return s;
+    };
+    py::class_<Scan, std::shared_ptr<Scan>>(mg, "LaserScanBuffer", "LaserScanBuffer define a sets of scan from a planar laser range-finder.")
+            .def(py::init<int, int, float, float>(), "Create a LaserScanBuffer from given a number of points and angle ranges "
+                 "(min_angle defaults to -pi; the reference's +pi makes an empty angle range)",
+                 "num_steps"_a, "num_max_scans"_a = 10, "min_angle"_a = (float)-M_PI, "max_angle"_a = (float)M_PI)
+            .def("__repr__", [](const Scan& s) { return std::string("geometry::LaserScanBuffer with ") + std::to_string(s.GetNumScans()) + " scans of " + std::to_string(s.num_steps_) + " steps."; })
+            .def("is_full", &Scan::IsFull)
+            .def("is_empty", &Scan::IsEmpty)
+            .def("has_intensities", &Scan::HasIntensities)
+            .def("get_angle_increment", &Scan::GetAngleIncrement)
+            .def("clear", [](std::shared_ptr<Scan> s) { s->Clear(); return s; })
+            .def("add_ranges", scan_add, "Add single scan ranges", "ranges"_a, "transformation"_a = identity4(), "intensities"_a = farray(0))
+            .def("add_host_ranges", scan_add, "Add host single scan ranges", "ranges"_a, "transformation"_a = identity4(),
+                 "intensities"_a = farray(0))
+            .def("merge", [](std::shared_ptr<Scan> s, const Scan& other) { s->Merge(other); return s; }, "Merge other LaserScanBuffer into this one", "other"_a)
+            .def("pop_one_scan", &Scan::PopOneScan, "Pop one scan from the buffer")
+            .def("pop_host_one_scan",
+                 [scan_rows](Scan& s) {
+                     auto p = s.PopHostOneScan();
+                     return py::make_tuple(scan_rows(*p.first), scan_rows(*p.second));
+                 },
+                 "Pop host one scan from the buffer")
+            .def("range_filter", &Scan::RangeFilter, "min_range"_a, "max_range"_a)
+            .def("scan_shadow_filter", &Scan::ScanShadowsFilter,
+                 "This filter removes laser readings that are most likely caused by the veiling effect when the edge of an object is being scanned.",
+                 "min_angle"_a, "max_angle"_a, "window"_a, "neighbors"_a = 0, "remove_shadow_start_point"_a = false)
+            .def("transform", [](std::shared_ptr<Scan> s, const farray& T) { s->Transform(to_matrix4(T)); return s; }, "transformation"_a)
+            .def("translate", [](std::shared_ptr<Scan> s, const farray& t, bool relative) { s->Translate(to_vector3(t), relative); return s; },
+                 "translation"_a, "relative"_a = true)
+            .def("rotate", [](std::shared_ptr<Scan> s, const farray& R, bool center) { s->Rotate(to_matrix3(R), center); return s; }, "R"_a, "center"_a = true)
+            .def("scale", [](std::shared_ptr<Scan> s, float k, bool center) { s->Scale(k, center); return s; }, "scale"_a, "center"_a = true)
+            .def("get_min_bound", [](const Scan& s) { return from_vector3(s.GetMinBound()); })
+            .def("get_max_bound", [](const Scan& s) { return from_vector3(s.GetMaxBound()); })
+            .def("get_center", [](const Scan& s) { return from_vector3(s.GetCenter()); })
+            .def("get_axis_aligned_bounding_box", &Scan::GetAxisAlignedBoundingBox)
+            .def_static("create_from_point_cloud", &Scan::CreateFromPointCloud, "Create a LaserScanBuffer from a point cloud", "pcd"_a,
+                        "angle_increment"_a, "min_height"_a, "max_height"_a, "num_vertical_divisions"_a = 1, "min_range"_a = 0.0,
+                        "max_range"_a = std::numeric_limits<float>::infinity(), "min_angle"_a = (float)-M_PI, "max_angle"_a = (float)M_PI)
+            .def_static("create_from_depth_image", &Scan::CreateFromDepthImage, "Create a LaserScanBuffer from a depth image", "depth"_a,
+                        "intrinsic"_a, "angle_increment"_a, "min_y"_a, "max_y"_a, "num_vertical_divisions"_a = 1, "min_range"_a = 0.0,
+                        "max_range"_a = std::numeric_limits<float>::infinity(), "min_angle"_a = (float)-M_PI, "max_angle"_a = (float)M_PI,
+                        "depth_scale"_a = 1000.0, "depth_trunc"_a = 1000.0, "stride"_a = 1)
+            .def_readonly("num_steps", &Scan::num_steps_, "Integer: Number of steps per scan.")
+            .def_readonly("num_max_scans", &Scan::num_max_scans_, "Integer: Maximum buffer size.")
+            .def_readwrite("min_angle", &Scan::min_angle_)
+            .def_readwrite("max_angle", &Scan::max_angle_)
+            .def_property_readonly("num_scans", &Scan::GetNumScans, "Integer: Number of scans in the buffer.")
+            .def_property_readonly("ranges", [scan_rows](const Scan& s) { return scan_rows(s.GetRanges()); })
+            .def_property_readonly("intensities", [scan_rows](const Scan& s) { return scan_rows(s.GetIntensities()); })
+            .def_property_readonly("origins", [](const Scan& s) {
+                py::list out;
+                for (int k = 0; k < s.GetNumScans(); ++k) out.append(from_matrix4(s.origins_[(size_t)((s.top_ + k) % s.num_max_scans_)]));
+                return out;
+            });
+    py::reinterpret_borrow<py::class_<geometry::PointCloud, std::shared_ptr<geometry::PointCloud>>>(mg.attr("PointCloud"))
+            .def_static("create_from_laserscanbuffer", &geometry::PointCloud::CreateFromLaserScanBuffer, "scan"_a, "min_range"_a, "max_range"_a);
 
     // ---------------------------------------------------------------- planning (cupoch_pybind/planning)
     py::module mpl = m.def_submodule("planning");

@@ -1164,6 +1164,100 @@ class Engine:
         _lib.load().mi_icp_graph_sssp_limits(C.byref(n), C.byref(m), C.byref(b))
         return int(n.value), int(m.value), int(b.value)
 
+    # -- laserscan (include/mi_icp.h "laserscan"; ranges / intensities / points device tensors, origins host) --------
+    def laserscan_to_points(self, ranges, intensities, origins, num_steps, num_max_scans, first_slot, num_scans,
+                            min_angle, max_angle, min_range, max_range, capacity=None):
+        """-> (points [m, 3], colours [m, 3] or None, m) on the device.  origins: [num_max_scans, 4, 4] row-major numpy.
+        capacity=None asks for the count first and then makes room; a given capacity is passed as it is (too little
+        room: empty arrays and the count)."""
+        dev = torch.device("cuda", self.device)
+        O = np.ascontiguousarray(np.asarray(origins, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1))
+        m = C.c_int64(0)
+
+        def call(cap):
+            (p, pp) = self._out(MI_ICP_DEVICE, dev, (max(cap, 1), 3))
+            (c, cp) = self._out(MI_ICP_DEVICE, dev, (max(cap, 1), 3)) if intensities is not None else (None, None)
+            self._chk(self._L.mi_icp_laserscan_to_points(
+                self._ctx, self._ptr(ranges), self._ptr(intensities), O.ctypes.data_as(C.c_void_p), int(num_steps),
+                int(num_max_scans), int(first_slot), int(num_scans), float(min_angle), float(max_angle), float(min_range),
+                float(max_range), pp if cap > 0 else None, cp if cap > 0 else None, int(cap), C.byref(m)))
+            return p, c
+        if capacity is None:
+            p, c = call(int(num_scans) * int(num_steps))
+        else:
+            p, c = call(int(capacity))
+            if int(m.value) > int(capacity):
+                return p[:0], (None if c is None else c[:0]), int(m.value)
+        k = int(m.value)
+        return p[:k], (None if c is None else c[:k]), k
+
+    def _laserscan_bins(self, angle_increment, min_angle, max_angle):
+        q = np.ceil((np.float32(max_angle) - np.float32(min_angle)) / np.float32(angle_increment))
+        return int(q) if np.isfinite(q) and 0 < q < 2 ** 31 else 0
+
+    def laserscan_from_points(self, points, angle_increment, min_height, max_height, num_vertical_divisions=1,
+                              min_range=0.0, max_range=float("inf"), min_angle=-np.pi, max_angle=np.pi):
+        """-> (ranges [num_vertical_divisions, num_steps] on the device, the path: 0 LDS, 1 global)"""
+        dev = torch.device("cuda", self.device)
+        with np.errstate(all="ignore"):
+            steps = self._laserscan_bins(angle_increment, min_angle, max_angle)
+        div = int(num_vertical_divisions)
+        room = steps * div if 0 < steps * max(div, 0) <= self.laserscan_limits()[1] else 1
+        out, op = self._out(MI_ICP_DEVICE, dev, (room,))
+        info = C.c_int32(-1)
+        self._chk(self._L.mi_icp_laserscan_from_points(
+            self._ctx, self._ptr(points), int(points.shape[0]), float(angle_increment), float(min_height), float(max_height),
+            div, float(min_range), float(max_range), float(min_angle), float(max_angle), steps, op, C.byref(info)))
+        return out.reshape(div, steps), int(info.value)
+
+    def laserscan_from_depth(self, depth, intrinsic4, angle_increment, min_y, max_y, num_vertical_divisions=1, min_range=0.0,
+                             max_range=float("inf"), min_angle=-np.pi, max_angle=np.pi, depth_scale=1000.0,
+                             depth_trunc=1000.0, stride=1):
+        """depth: [H, W] float32 or uint16 device tensor -> (ranges [num_vertical_divisions, num_steps], the path)"""
+        dev = torch.device("cuda", self.device)
+        name = str(depth.dtype).replace("torch.", "")
+        if depth.ndim != 2 or name not in ("float32", "uint16"):
+            raise TypeError("depth must be [H, W] float32 or uint16")
+        d = depth.contiguous()
+        with np.errstate(all="ignore"):
+            steps = self._laserscan_bins(angle_increment, min_angle, max_angle)
+        div = int(num_vertical_divisions)
+        room = steps * div if 0 < steps * max(div, 0) <= self.laserscan_limits()[1] else 1
+        out, op = self._out(MI_ICP_DEVICE, dev, (room,))
+        info = C.c_int32(-1)
+        K = (C.c_float * 4)(*[float(v) for v in intrinsic4])
+        self._chk(self._L.mi_icp_laserscan_from_depth(
+            self._ctx, C.c_void_p(d.data_ptr()), 1 if name == "uint16" else 0, int(d.shape[1]), int(d.shape[0]), K,
+            float(depth_scale), float(depth_trunc), int(stride), float(angle_increment), float(min_y), float(max_y), div,
+            float(min_range), float(max_range), float(min_angle), float(max_angle), steps, op, C.byref(info)))
+        return out.reshape(div, steps), int(info.value)
+
+    def laserscan_range_filter(self, ranges, min_range, max_range):
+        out = torch.empty_like(ranges)
+        self._chk(self._L.mi_icp_laserscan_range_filter(self._ctx, self._ptr(ranges), int(ranges.numel()), float(min_range),
+                                                        float(max_range), self._ptr(out)))
+        return out
+
+    def laserscan_shadow_filter(self, ranges, num_steps, scan_min_angle, scan_max_angle, min_angle, max_angle, window,
+                                neighbors=0, remove_shadow_start_point=False):
+        """ranges: [rows, num_steps] -> the filtered copy"""
+        out = torch.empty_like(ranges)
+        self._chk(self._L.mi_icp_laserscan_shadow_filter(
+            self._ctx, self._ptr(ranges), int(num_steps), int(ranges.numel() // max(int(num_steps), 1)), float(scan_min_angle),
+            float(scan_max_angle), float(min_angle), float(max_angle), int(window), int(neighbors),
+            int(bool(remove_shadow_start_point)), self._ptr(out)))
+        return out
+
+    def laserscan_scale(self, ranges, scale):
+        self._chk(self._L.mi_icp_laserscan_scale(self._ctx, self._ptr(ranges), int(ranges.numel()), float(scale)))
+
+    @staticmethod
+    def laserscan_limits():
+        """-> (the LDS path's largest bin count, the largest bin count taken at all)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        _lib.load().mi_icp_laserscan_limits(C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def compute_rgbd_odometry(self, source_color, source_depth, target_color, target_depth, intrinsic4,
                               odo_init=None, jacobian=1, iterations=(20, 10, 5), max_depth_diff=0.03,
                               min_depth=0.0, max_depth=4.0, weighted=False, prev_twist=None, nu=5.0,

@@ -13,7 +13,9 @@ transform, and a transform as a collision target.
 LineSet mirrors geometry/lineset.h (LineSet<3>; python surface src/python/cupoch_pybind/geometry/lineset.cpp); not
 built: the factories from meshes, clouds with correspondences and oriented boxes, and file I/O.
 Graph mirrors geometry/graph.h (Graph<3>; python surface src/python/cupoch_pybind/geometry/graph.cpp): the roadmap
-cupoch_amd.planning searches; not built: Graph2D, create_from_triangle_mesh, file I/O and visualisation."""
+cupoch_amd.planning searches; not built: Graph2D, create_from_triangle_mesh, file I/O and visualisation.
+LaserScanBuffer mirrors geometry/laserscanbuffer.h (python surface src/python/cupoch_pybind/geometry/laserscanbuffer.cpp)
+with PointCloud.create_from_laserscanbuffer; not built: file I/O and visualisation."""
 import sys
 
 import numpy as np
@@ -1750,3 +1752,352 @@ class Graph(LineSet):
 
 def _is_torch(a):
     return torch is not None and isinstance(a, torch.Tensor)
+
+
+# ---- geometry::LaserScanBuffer (geometry/laserscanbuffer.h; python surface cupoch_pybind/geometry/laserscanbuffer.cpp) ----
+_QUARTER_TURN_X = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float32)   # exact -pi/2 about X
+
+
+def _matmul4(a, b):
+    """a*b in fp32, every element ((a0*b0 + a1*b1) + a2*b2) + a3*b3 (include/mi_icp.h "laserscan")"""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    out = np.empty((4, 4), np.float32)
+    for r in range(4):
+        for c in range(4):
+            out[r, c] = ((a[r, 0] * b[0, c] + a[r, 1] * b[1, c]) + a[r, 2] * b[2, c]) + a[r, 3] * b[3, c]
+    return out
+
+
+class LaserScanBuffer:
+    """A ring of scans from a planar laser range-finder, each with the pose (origin) it was taken from.
+
+    ranges / intensities live on the GPU as [num_max_scans, num_steps] torch tensors, the origins on the host as
+    [num_max_scans, 4, 4]; include/mi_icp.h ("laserscan") states what every operation computes.  The ring: the newest
+    scan goes to slot bottom % num_max_scans; a full ring overwrites its oldest scan and advances top; the live scans
+    are slots top .. bottom - 1 (mod num_max_scans), oldest first.  A buffer has intensities when the first scan added
+    to it while empty carried them.
+    Defaults follow the reference's Python (num_max_scans=10) except min_angle, which is -pi here: the reference's
+    binding says +pi, which with max_angle=+pi makes an empty angle range.
+    As in the reference, errors are printed and the call returns (self, None or an empty result); nothing is raised."""
+
+    def __init__(self, num_steps, num_max_scans=10, min_angle=-np.pi, max_angle=np.pi, device=None):
+        self._num_steps = int(num_steps)
+        self._num_max_scans = int(num_max_scans)
+        self.min_angle = float(np.float32(min_angle))
+        self.max_angle = float(np.float32(max_angle))
+        self._device = device
+        self.top_ = 0
+        self.bottom_ = 0
+        self._ranges = None          # [num_max_scans, num_steps], made with the first scan
+        self._intensities = None
+        self._origins = np.tile(np.eye(4, dtype=np.float32), (max(self._num_max_scans, 0), 1, 1))
+
+    # ---- attributes of the reference's binding
+    @property
+    def num_steps(self):
+        return self._num_steps
+
+    @property
+    def num_max_scans(self):
+        return self._num_max_scans
+
+    @property
+    def num_scans(self):
+        return self.bottom_ - self.top_
+
+    @property
+    def ranges(self):
+        """the live scans, oldest first: a [num_scans * num_steps] device tensor (GetRanges keeps them on the host)"""
+        return self._live(self._ranges)
+
+    @property
+    def intensities(self):
+        return self._live(self._intensities)
+
+    @property
+    def origins(self):
+        """the live scans' origins, oldest first: [num_scans, 4, 4] numpy"""
+        return self._origins[self._slots()].copy()
+
+    def _eng(self):
+        if self._device is None:
+            self._device = utility.default_device()
+        return get_engine(self._device)
+
+    def _slots(self):
+        return [(self.top_ + k) % self._num_max_scans for k in range(self.num_scans)]
+
+    def _live(self, store):
+        if store is None or self.num_scans == 0:
+            return self._eng()._vg_dev(np.zeros(0, np.float32), np.float32, 1)
+        return store[self._slots()].reshape(-1)
+
+    def _row(self, values):
+        return self._eng()._vg_dev(values, np.float32, 1)
+
+    @staticmethod
+    def _size(v):
+        if v is None:
+            return 0
+        return int(v.numel()) if _is_torch(v) else int(np.asarray(v).size)
+
+    # ---- laserscanbuffer.h:67-73
+    def has_intensities(self):
+        return self._intensities is not None
+
+    def get_angle_increment(self):
+        with np.errstate(all="ignore"):
+            return float((np.float32(self.max_angle) - np.float32(self.min_angle)) / np.float32(self._num_steps - 1))
+
+    def is_full(self):
+        return self.num_scans == self._num_max_scans
+
+    def get_num_scans(self):
+        return self.num_scans
+
+    def is_empty(self):
+        return self.bottom_ == self.top_
+
+    def clear(self):
+        self.top_ = self.bottom_ = 0
+        self._ranges = self._intensities = None
+        self._origins[:] = np.eye(4, dtype=np.float32)
+        return self
+
+    def get_ranges(self):
+        """GetRanges: the live scans oldest first, on the host"""
+        return self.ranges.cpu().numpy()
+
+    def get_intensities(self):
+        return self.intensities.cpu().numpy()
+
+    def _unsupported(self, what):
+        _log_error("LaserScanBuffer::%s is not supported" % what)
+        return np.zeros(3, np.float32)
+
+    def get_min_bound(self):
+        return self._unsupported("GetMinBound")
+
+    def get_max_bound(self):
+        return self._unsupported("GetMaxBound")
+
+    def get_center(self):
+        return self._unsupported("GetCenter")
+
+    def get_axis_aligned_bounding_box(self):
+        self._unsupported("GetAxisAlignedBoundingBox")
+        return AxisAlignedBoundingBox()
+
+    # ---- AddRanges / Merge / Pop
+    def add_ranges(self, ranges, transformation=None, intensities=None):
+        n, ni = self._size(ranges), self._size(intensities)
+        if n != self._num_steps or self._num_max_scans < 1:
+            _log_error("[AddRanges] Invalid size of input ranges.")
+            return self
+        if self.has_intensities() and n != ni:
+            _log_error("[AddRanges] Invalid size of intensities.")
+            return self
+        T = np.eye(4, dtype=np.float32) if transformation is None else np.asarray(transformation, np.float32).reshape(4, 4)
+        row = self._row(ranges)
+        if self._ranges is None:
+            self._ranges = torch.full((self._num_max_scans, self._num_steps), float("nan"), dtype=torch.float32, device=row.device)
+        if self.is_empty() and self._intensities is None and ni == n:
+            self._intensities = torch.zeros_like(self._ranges)
+        if self.is_full():
+            self.top_ += 1
+        slot = self.bottom_ % self._num_max_scans
+        self._ranges[slot] = row
+        if self._intensities is not None:
+            self._intensities[slot] = self._row(intensities)
+        self._origins[slot] = T
+        self.bottom_ += 1
+        return self
+
+    def add_host_ranges(self, ranges, transformation=None, intensities=None):
+        return self.add_ranges(ranges, transformation, intensities)
+
+    def merge(self, other):
+        if other.is_empty():
+            _log_error("[Merge] Input buffer is empty.")
+            return self
+        if other.num_steps != self._num_steps:
+            _log_error("[Merge] Input buffer has different num_steps.")
+            return self
+        if other.has_intensities() != self.has_intensities():
+            _log_error("[Merge] Input buffer has different intensities.")
+            return self
+        if other.min_angle != self.min_angle or other.max_angle != self.max_angle:
+            _log_error("[Merge] Input buffer has different angle range.")
+            return self
+        if other.num_scans + self.num_scans > self._num_max_scans:
+            _log_error("[Merge] Buffer is full.")
+            return self
+        for s in other._slots():
+            self.add_ranges(other._ranges[s], other._origins[s], None if other._intensities is None else other._intensities[s])
+        return self
+
+    def _pop_slot(self):
+        if self.is_empty():
+            _log_error("[PopRange] Buffer is empty.")
+            return None
+        slot = self.top_ % self._num_max_scans
+        self.top_ += 1
+        return slot
+
+    def pop_one_scan(self):
+        slot = self._pop_slot()
+        if slot is None:
+            return None
+        out = LaserScanBuffer(self._num_steps, self._num_max_scans, self.min_angle, self.max_angle, self._device)
+        out.add_ranges(self._ranges[slot], self._origins[slot], None if self._intensities is None else self._intensities[slot])
+        return out
+
+    def pop_host_one_scan(self):
+        """-> (ranges, intensities) of the oldest scan as numpy arrays (intensities empty without them)"""
+        slot = self._pop_slot()
+        if slot is None:
+            return np.zeros(0, np.float32), np.zeros(0, np.float32)
+        r = self._ranges[slot].cpu().numpy()
+        return r, (np.zeros(0, np.float32) if self._intensities is None else self._intensities[slot].cpu().numpy())
+
+    # ---- the filters: a new buffer that keeps origins, intensities, top and bottom
+    def _like(self, new_ranges):
+        out = LaserScanBuffer(self._num_steps, self._num_max_scans, self.min_angle, self.max_angle, self._device)
+        out.top_, out.bottom_ = self.top_, self.bottom_
+        out._ranges = new_ranges
+        out._intensities = None if self._intensities is None else self._intensities.clone()
+        out._origins = self._origins.copy()
+        return out
+
+    def range_filter(self, min_range, max_range):
+        if max_range <= min_range:
+            _log_error("[RangeFilter] Invalid parameter with min_range greater than max_range.")
+        if self._ranges is None:
+            return self._like(None)
+        return self._like(self._eng().laserscan_range_filter(self._ranges, min_range, max_range))
+
+    def scan_shadow_filter(self, min_angle, max_angle, window, neighbors=0, remove_shadow_start_point=False):
+        if self._ranges is None:
+            return self._like(None)
+        return self._like(self._eng().laserscan_shadow_filter(self._ranges, self._num_steps, self.min_angle, self.max_angle,
+                                                              min_angle, max_angle, window, neighbors,
+                                                              remove_shadow_start_point))
+
+    # ---- GeometryBase3D: the origins' arithmetic on the host, Scale on the ranges
+    def transform(self, transformation):
+        T = np.asarray(transformation, np.float32).reshape(4, 4)
+        for s in range(self._num_max_scans):
+            self._origins[s] = _matmul4(self._origins[s], T)
+        return self
+
+    def translate(self, translation, relative=True):
+        t = np.asarray(translation, np.float32).reshape(3)
+        self._origins[:, :3, 3] = self._origins[:, :3, 3] + t
+        return self
+
+    def rotate(self, R, center=True):
+        R = np.asarray(R, np.float32).reshape(3, 3)
+        for s in range(self._num_max_scans):
+            a = self._origins[s, :3, :3].copy()
+            for r in range(3):
+                for c in range(3):
+                    self._origins[s, r, c] = (a[r, 0] * R[0, c] + a[r, 1] * R[1, c]) + a[r, 2] * R[2, c]
+        return self
+
+    def scale(self, scale, center=True):
+        if self._ranges is not None:
+            self._eng().laserscan_scale(self._ranges, scale)
+        return self
+
+    # ---- the virtual lidars
+    @staticmethod
+    def _factory_check(what, low_name, angle_increment, low, high, min_range, max_range, min_angle, max_angle):
+        msg = None
+        if not angle_increment > 0.0:
+            msg = "angle_increment must be positive."
+        elif not low < high:
+            msg = "%s must be smaller than %s." % (low_name, low_name.replace("min", "max"))
+        elif not min_range < max_range:
+            msg = "min_range must be smaller than max_range."
+        elif not min_angle < max_angle:
+            msg = "min_angle must be smaller than max_angle."
+        if msg:
+            _log_error("[LaserScanBuffer::%s] %s" % (what, msg))
+        return msg is None
+
+    @staticmethod
+    def _from_bins(bins, device, low, high, divisions, min_angle, max_angle, left=None):
+        steps = int(bins.shape[1])
+        out = LaserScanBuffer(steps, max(50, divisions), min_angle, max_angle, device)
+        out._ranges = torch.full((out._num_max_scans, steps), float("nan"), dtype=torch.float32, device=bins.device)
+        out._ranges[:divisions] = bins
+        lo, hi = np.float32(low), np.float32(high)
+        for i in range(out._num_max_scans):
+            O = np.eye(4, dtype=np.float32)
+            O[2, 3] = lo + ((hi - lo) * np.float32(i)) / np.float32(divisions)
+            out._origins[i] = O if left is None else _matmul4(left, O)
+        out.bottom_ = divisions
+        return out
+
+    @staticmethod
+    def create_from_point_cloud(pcd, angle_increment, min_height, max_height, num_vertical_divisions=1, min_range=0.0,
+                                max_range=float("inf"), min_angle=-np.pi, max_angle=np.pi):
+        if not LaserScanBuffer._factory_check("CreateFromPointCloud", "min_height", angle_increment, min_height, max_height,
+                                              min_range, max_range, min_angle, max_angle):
+            return None
+        pts = pcd.points.tensor
+        eng = get_engine(pts.device.index)
+        try:
+            bins, _ = eng.laserscan_from_points(pts, angle_increment, min_height, max_height, num_vertical_divisions,
+                                                min_range, max_range, min_angle, max_angle)
+        except _lib.MiIcpError as e:
+            if e.code != _lib.MI_ICP_ERR_INVALID:
+                raise
+            _log_error("[LaserScanBuffer::CreateFromPointCloud] %s" % e)
+            return None
+        return LaserScanBuffer._from_bins(bins, eng.device, min_height, max_height, int(num_vertical_divisions),
+                                          float(np.float32(min_angle)), float(np.float32(max_angle)))
+
+    @staticmethod
+    def create_from_depth_image(depth, intrinsic, angle_increment, min_y, max_y, num_vertical_divisions=1, min_range=0.0,
+                                max_range=float("inf"), min_angle=-np.pi, max_angle=np.pi, depth_scale=1000.0,
+                                depth_trunc=1000.0, stride=1):
+        if not LaserScanBuffer._factory_check("CreateFromDepthImage", "min_y", angle_increment, min_y, max_y, min_range,
+                                              max_range, min_angle, max_angle):
+            return None
+        d = _img(depth)
+        if not _is_torch(d):
+            d = torch.from_numpy(np.ascontiguousarray(d)).to(torch.device("cuda", utility.default_device()))
+        eng = get_engine(d.device.index)
+        try:
+            bins, _ = eng.laserscan_from_depth(d, intrinsic.as4(), angle_increment, min_y, max_y, num_vertical_divisions,
+                                               min_range, max_range, min_angle, max_angle, depth_scale, depth_trunc, stride)
+        except (TypeError, _lib.MiIcpError) as e:
+            if isinstance(e, _lib.MiIcpError) and e.code != _lib.MI_ICP_ERR_INVALID:
+                raise
+            _log_error("[LaserScanBuffer::CreateFromDepthImage] %s" % e)
+            return None
+        return LaserScanBuffer._from_bins(bins, eng.device, min_y, max_y, int(num_vertical_divisions),
+                                          float(np.float32(min_angle)), float(np.float32(max_angle)), left=_QUARTER_TURN_X)
+
+
+def _create_from_laserscanbuffer(scan, min_range, max_range):
+    """PointCloud::CreateFromLaserScanBuffer (pointcloud_factory.cu:375-420): the live scans' readings inside
+    [min_range, max_range] as points in the frame of their origins, oldest scan first; intensities become grey colours."""
+    out = PointCloud()
+    if scan.is_empty() or scan._ranges is None:
+        _log_error("[PointCloud::CreateFromLaserScanBuffer] Empty scan, return empty pointcloud.")
+        return out
+    if min_range >= max_range:
+        _log_error("[PointCloud::CreateFromLaserScanBuffer] min_range must be smaller than max_range.")
+        return out
+    p, c, _ = scan._eng().laserscan_to_points(scan._ranges, scan._intensities, scan._origins, scan.num_steps, scan.num_max_scans,
+                                              scan.top_ % scan.num_max_scans, scan.num_scans, scan.min_angle, scan.max_angle,
+                                              min_range, max_range)
+    out._points = utility.Vector3fVector(p)
+    if c is not None:
+        out._colors = utility.Vector3fVector(c)
+    return out
+
+
+PointCloud.create_from_laserscanbuffer = staticmethod(_create_from_laserscanbuffer)

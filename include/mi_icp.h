@@ -1268,6 +1268,88 @@ MI_ICP_API int mi_icp_graph_sssp(mi_icp_ctx* ctx, const int32_t* offsets, const 
 /* the small regime's largest n and m, and the rounds of a batch in the large one (no context, no device) */
 MI_ICP_API int mi_icp_graph_sssp_limits(int64_t* small_max_nodes, int64_t* small_max_edges, int32_t* batch_rounds);
 
+/* ---- laserscan (geometry/laserscanbuffer.{h,cu}, laserscanbuffer_factory.cu, PointCloud::CreateFromLaserScanBuffer) ----
+ * geometry::LaserScanBuffer: a ring of planar scans.  THE STORAGE BELONGS TO THE CALLER (the C++ or Python object):
+ * ranges[num_max_scans][num_steps] and the optional intensities of the same shape are DEVICE memory; the library keeps
+ * no scan handle.  ORIGINS ARE HOST MEMORY: origins[num_max_scans][16], one column-major 4x4 per slot, kept by the
+ * surfaces on the host and passed with each call that needs them (64 bytes per scan; Transform / Rotate / Translate
+ * are host arithmetic, stated below).  Counts, scalars, intrinsic4, *m and *info are host memory too.
+ * The ring: live scan k (oldest first, 0 <= k < num_scans) sits in slot (first_slot + k) % num_max_scans; the surfaces
+ * keep top / bottom as the reference does (first_slot = top % num_max_scans, num_scans = bottom - top, the newest
+ * scan's slot is bottom % num_max_scans; a full ring overwrites its oldest scan and advances top).
+ *
+ * NUMERIC CONTRACT.  fp32 in exactly the order written, products never fused, division and sqrtf correctly rounded;
+ * tests/laserscan_exact.py restates it in numpy.  The reference's bin update is a read, a compare and an exchange (the
+ * smaller range can lose) and it reads and writes out of bounds where noted: this is a stated contract, not a
+ * transcription.
+ *  to_points  PointCloud::CreateFromLaserScanBuffer.  Only LIVE scans are converted, oldest first (the reference walks
+ *   raw storage, popped scans included).  num_steps >= 2, else MI_ICP_ERR_INVALID.
+ *   inc = (max_angle - min_angle) / (float)(num_steps - 1); a_i = min_angle + (float)i * inc; c_i, s_i = cos, sin of
+ *   (double)a_i computed ON THE HOST in double and rounded to float (a table uploaded with the call: device cosf / sinf
+ *   would not be bit-reproducible).  A reading r is kept when !isnan(r) && !(r < min_range) && !(max_range < r); then
+ *   x = r*c_i, y = r*s_i, p_k = (O(k,0)*x + O(k,1)*y) + O(k,3) for k = 0, 1, 2 with O the scan's origin; points with a
+ *   non-finite coordinate are then removed (RemoveNoneFinitePoints(true, true)), order kept.  With intensities the
+ *   colour of a point is (v, v, v).  THE CAPACITY RULE: *m is always the count; with capacity < *m nothing is written.
+ *   min_range >= max_range or no live scan: *m = 0, MI_ICP_OK.  Waits once (the count).
+ *  from_points  LaserScanBuffer::CreateFromPointCloud into out_ranges[num_vertical_divisions][num_steps], where the
+ *   CALLER computes num_steps = (int)ceilf((max_angle - min_angle) / angle_increment) (checked).  Every bin starts as
+ *   the quiet NaN 0x7fc00000.  Per point: range = sqrtf(x*x + y*y) (for hypotf: the same except where the squares
+ *   overflow or underflow), angle = atan2f(y, x), height_increment = (max_height - min_height) /
+ *   (float)num_vertical_divisions, j = (int)((z - min_height) / height_increment), i = (int)((angle - min_angle) /
+ *   angle_increment).  Dropped: a non-finite coordinate; range < min_range || range > max_range; angle < min_angle ||
+ *   angle > max_angle; z < min_height; j >= num_vertical_divisions; i >= num_steps (the last three are out-of-bounds
+ *   writes in the reference).  A bin ends as the EXACT MINIMUM of its points' ranges whatever the order of arrival:
+ *   ranges are >= 0, so their bit patterns order as unsigned integers with the NaN pattern above +inf's, and one
+ *   unsigned atomic minimum per point is the whole reduction; every run gives the same bytes.
+ *   TWO PATHS, chosen from the bin count alone (mi_icp_laserscan_limits): bins <= 18432 the LDS path -- each workgroup
+ *   keeps the table in LDS (72 KiB, so two workgroups share a CU's 160 KiB), reduces a contiguous share of the points
+ *   with LDS atomic minima and flushes the bins it touched with global atomic minima; otherwise atomics straight to
+ *   memory.  *info (may be NULL) = 0 for the LDS path, 1 for the global one.
+ *   MI_ICP_ERR_INVALID: angle_increment <= 0, min_height >= max_height, min_range >= max_range, min_angle >= max_angle,
+ *   num_vertical_divisions < 1, a num_steps that is not the formula's, more than 2^26 bins.  Never waits.
+ *  from_depth  LaserScanBuffer::CreateFromDepthImage, one fused kernel from depth pixel to bin, no cloud in between.
+ *   Pixel selection, stride, the U16 depth_scale / depth_trunc rule and depth <= 0 are exactly those of
+ *   mi_icp_create_from_depth (rgbd = 0).  Camera point x = ((float)col - cx) * z / fx, y = ((float)row - cy) * z / fy;
+ *   scan-frame point (x, -z, y): the inverse of the EXACT quarter turn about X with rows (1,0,0), (0,0,1), (0,-1,0)
+ *   (the reference builds it from AngleAxisf(-M_PI_2, UnitX), which is not exact in float).  Then binned as above with
+ *   min_y / max_y in the place of the heights.
+ *  range_filter  out = (r < min_range || r > max_range) ? NaN : r over `count` readings (out may be ranges itself).
+ *  shadow_filter  ScanShadowsFilter over num_rows scans of num_steps readings.  Host: min_tan = |(float)tan((double)
+ *   min_angle)|, max_tan = -|(float)tan((double)max_angle)|, inc as in to_points from scan_min_angle / scan_max_angle,
+ *   and a table c_y, s_y = cos, sin of (double)((float)y * inc) for y in [-window, window].  Reading (n, i) is a shadow
+ *   start when for some j = i + y with 0 <= j < num_steps, j != i: py = r_j * s_y, px = r_i - r_j * c_y,
+ *   t = fabsf(py) / px and (t > 0) ? (t < min_tan) : (t > max_tan).  Then out[n][index] = NaN for every index in
+ *   [max(i - neighbors, 0), min(i + neighbors, num_steps - 1)] with r[n][i] < r[n][index] (the reference compares
+ *   inside scan 0), and out[n][i] = NaN if remove_shadow_start_point.  Reads come from `ranges`, writes go to
+ *   out_ranges, which starts as a copy (it must be another buffer): the result does not depend on order.  Waits once.
+ *  scale  LaserScanBuffer::Scale: r = r * scale over `count` readings, in place.
+ * The origins' arithmetic, which the surfaces do on the host: Transform O <- O*T, every element ((a0*b0 + a1*b1) +
+ * a2*b2) + a3*b3; Rotate the 3x3 block times R, ((a0*b0 + a1*b1) + a2*b2); Translate adds to column 3.  The
+ * factories' origins: identity with O(2,3) = min_height + ((max_height - min_height) * (float)i) /
+ * (float)num_vertical_divisions for slot i; from_depth multiplies each on the left by the exact quarter turn. */
+MI_ICP_API int mi_icp_laserscan_to_points(mi_icp_ctx* ctx, const float* ranges, const float* intensities,
+                                          const float* origins, int32_t num_steps, int32_t num_max_scans, int32_t first_slot,
+                                          int32_t num_scans, float min_angle, float max_angle, float min_range,
+                                          float max_range, float* out_xyz, float* out_colors, int64_t capacity, int64_t* m);
+MI_ICP_API int mi_icp_laserscan_from_points(mi_icp_ctx* ctx, const float* points, int64_t n, float angle_increment,
+                                            float min_height, float max_height, int32_t num_vertical_divisions,
+                                            float min_range, float max_range, float min_angle, float max_angle,
+                                            int32_t num_steps, float* out_ranges, int32_t* info);
+MI_ICP_API int mi_icp_laserscan_from_depth(mi_icp_ctx* ctx, const void* depth, int depth_type, int width, int height,
+                                           const float* intrinsic4, float depth_scale, float depth_trunc, int stride,
+                                           float angle_increment, float min_y, float max_y, int32_t num_vertical_divisions,
+                                           float min_range, float max_range, float min_angle, float max_angle,
+                                           int32_t num_steps, float* out_ranges, int32_t* info);
+MI_ICP_API int mi_icp_laserscan_range_filter(mi_icp_ctx* ctx, const float* ranges, int64_t count, float min_range,
+                                             float max_range, float* out_ranges);
+MI_ICP_API int mi_icp_laserscan_shadow_filter(mi_icp_ctx* ctx, const float* ranges, int32_t num_steps, int32_t num_rows,
+                                              float scan_min_angle, float scan_max_angle, float min_angle, float max_angle,
+                                              int32_t window, int32_t neighbors, int remove_shadow_start_point,
+                                              float* out_ranges);
+MI_ICP_API int mi_icp_laserscan_scale(mi_icp_ctx* ctx, float* ranges, int64_t count, float scale);
+/* the LDS path's largest bin count and the largest bin count taken at all (no context, no device) */
+MI_ICP_API int mi_icp_laserscan_limits(int64_t* lds_max_bins, int64_t* max_bins);
+
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
  * float[nq][3] against the cloud given to mi_icp_set_target: per query the knn
