@@ -18,7 +18,7 @@ INCLUDE = os.path.join(ROOT, "include")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I/opt/rocm/include"]
 # the library's translation units (csrc/ctx.h says what each holds); compiled side by side, then linked
-UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_occgrid", "mi_voxelgrid", "mi_collision", "mi_graph", "mi_laserscan", "mi_edt", "mi_knn", "mi_comm", "mi_debug"]
+UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_occgrid", "mi_voxelgrid", "mi_collision", "mi_graph", "mi_laserscan", "mi_image", "mi_edt", "mi_knn", "mi_comm", "mi_debug"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 MI_ICP_HOST, MI_ICP_DEVICE = 0, 1
@@ -252,6 +252,20 @@ SIGNATURES = {
     "mi_icp_laserscan_shadow_filter": (_I, [_P, _P, C.c_int32, C.c_int32, _F, _F, _F, _F, C.c_int32, C.c_int32, _I, _P]),
     "mi_icp_laserscan_scale": (_I, [_P, _P, _L, _F]),
     "mi_icp_laserscan_limits": (_I, [C.POINTER(_L), C.POINTER(_L)]),
+    "mi_icp_image_filter": (_I, [_P, _P, _I, _I, _P, _I, _P, _I, _P]),
+    "mi_icp_image_downsample": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "mi_icp_image_pyramid_level": (_I, [_P, _P, _I, _I, _P]),
+    "mi_icp_image_bilateral_table": (_I, [_I, _F, _P]),
+    "mi_icp_image_bilateral": (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),
+    "mi_icp_image_create_float": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "mi_icp_image_depth_to_float": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P]),
+    "mi_icp_image_create_gray": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "mi_icp_image_from_float": (_I, [_P, _P, _I, _I, _I, _P]),
+    "mi_icp_image_linear_transform": (_I, [_P, _P, _I, _I, _I, _I, _F, _F]),
+    "mi_icp_image_clip": (_I, [_P, _P, _I, _I, _F, _F]),
+    "mi_icp_image_move": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "mi_icp_image_depth_format": (_I, [_P, _P, _I, _I, _I, _P]),
+    "mi_icp_image_limits": (_I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mi_icp_covariances_from_normals": (_I, [_P, _P, _L, _F, _P, _I]),
     "mi_icp_estimate_normals_knn": (_I, [_P, _P, _L, _I, _P, _I]),
     "mi_icp_estimate_normals_radius": (_I, [_P, _P, _L, _F, _I, _P, _I]),
@@ -300,6 +314,7 @@ SIGNATURES = {
     "mi_icp_debug_get_leaf_halos": (_I, [_P, _P]),
     "mi_icp_debug_eigen3": (_I, [_I, _P, _L, _P, _P, _P]),
     "mi_icp_debug_odometry_image": (_I, [_P, _I, _I, _P, C.POINTER(_I), C.POINTER(_I)]),
+    "mi_icp_debug_image_bilateral": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _I]),
 }
 
 _lib = None

@@ -2760,4 +2760,291 @@ std::shared_ptr<PointCloud> PointCloud::CreateFromLaserScanBuffer(const LaserSca
 
 }  // namespace geometry
 
+// ---------------------------------------------------------------- geometry::Image / RGBDImage processing
+// (geometry/image.cu, image_factory.cu, rgbdimage.cu, rgbdimage_factory.cu over mi_icp_image_*)
+namespace geometry {
+
+namespace {
+
+bool IsFormat(const Image& im, int channels, int bytes) { return im.num_of_channels_ == channels && im.bytes_per_channel_ == bytes; }
+
+bool KnownFormat(const Image& im) {
+    return im.num_of_channels_ >= 1 && im.num_of_channels_ <= 4 && (im.bytes_per_channel_ == 1 || im.bytes_per_channel_ == 2 || im.bytes_per_channel_ == 4);
+}
+
+void FilterTaps(Image::FilterType type, std::vector<float>* dx, std::vector<float>* dy) {
+    const std::vector<float> s1 = {-1.0f, 0.0f, 1.0f}, s2 = {1.0f, 2.0f, 1.0f};
+    switch (type) {
+        case Image::FilterType::Gaussian3: *dx = *dy = {0.25f, 0.5f, 0.25f}; break;
+        case Image::FilterType::Gaussian5: *dx = *dy = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f}; break;
+        case Image::FilterType::Gaussian7: *dx = *dy = {0.03125f, 0.109375f, 0.21875f, 0.28125f, 0.21875f, 0.109375f, 0.03125f}; break;
+        case Image::FilterType::Sobel3Dx: *dx = s1; *dy = s2; break;
+        case Image::FilterType::Sobel3Dy: *dx = s2; *dy = s1; break;
+        default: dx->clear(); dy->clear(); break;
+    }
+}
+
+bool GoodTaps(const std::vector<float>& k) { return k.size() % 2 == 1 && k.size() <= (size_t)MI_ICP_IMAGE_MAX_TAPS; }
+
+std::shared_ptr<Image> Move(const Image& im, int op, const char* error) {
+    auto out = std::make_shared<Image>();
+    if (im.IsEmpty()) return out;
+    if (!KnownFormat(im)) {
+        LogError(error);
+        return out;
+    }
+    if (op == MI_ICP_IMAGE_TRANSPOSE) out->Prepare(im.height_, im.width_, im.num_of_channels_, im.bytes_per_channel_);
+    else out->Prepare(im.width_, im.height_, im.num_of_channels_, im.bytes_per_channel_);
+    Check(mi_icp_image_move(Engine(), im.data_.data(), im.width_, im.height_, im.num_of_channels_ * im.bytes_per_channel_, op, out->data_.data()));
+    return out;
+}
+
+// one format factory: the depth decoded (format >= 0), then CreateFromColorAndDepth
+std::shared_ptr<RGBDImage> FromFormat(const Image& color, const Image& depth, int format, const char* error, float scale, float trunc,
+                                      bool convert_rgb_to_intensity) {
+    if (color.height_ != depth.height_ || color.width_ != depth.width_ || !IsFormat(depth, 1, 2)) {
+        LogError(error);
+        return std::make_shared<RGBDImage>();
+    }
+    Image decoded = depth;
+    if (!depth.IsEmpty())
+        Check(mi_icp_image_depth_format(Engine(), (const uint16_t*)depth.data_.data(), depth.width_, depth.height_, format, (uint16_t*)decoded.data_.data()));
+    return RGBDImage::CreateFromColorAndDepth(color, decoded, scale, trunc, convert_rgb_to_intensity);
+}
+
+}  // namespace
+
+std::shared_ptr<Image> Image::ConvertDepthToFloatImage(float depth_scale, float depth_trunc) const {
+    auto out = std::make_shared<Image>();
+    if (IsEmpty()) return out;
+    if (!KnownFormat(*this)) {
+        LogError("[ConvertDepthToFloatImage] Unsupported image format.");
+        return out;
+    }
+    out->Prepare(width_, height_, 1, 4);
+    Check(mi_icp_image_depth_to_float(Engine(), data_.data(), width_, height_, num_of_channels_, bytes_per_channel_, depth_scale, depth_trunc,
+                                      (float*)out->data_.data()));
+    return out;
+}
+
+std::shared_ptr<Image> Image::Transpose() const { return Move(*this, MI_ICP_IMAGE_TRANSPOSE, "[Transpose] Unsupported image format."); }
+std::shared_ptr<Image> Image::FlipHorizontal() const { return Move(*this, MI_ICP_IMAGE_FLIP_HORIZONTAL, "[FlipHorizontal] Unsupported image format."); }
+std::shared_ptr<Image> Image::FlipVertical() const { return Move(*this, MI_ICP_IMAGE_FLIP_VERTICAL, "[FlipVertical] Unsupported image format."); }
+
+std::shared_ptr<Image> Image::FilterHorizontal(const std::vector<float>& kernel) const {
+    auto out = std::make_shared<Image>();
+    if (IsEmpty() || !IsFormat(*this, 1, 4) || !GoodTaps(kernel)) {
+        LogError("[FilterHorizontal] Unsupported image format or kernel size.");
+        return out;
+    }
+    out->Prepare(width_, height_, 1, 4);
+    Check(mi_icp_image_filter(Engine(), (const float*)data_.data(), width_, height_, kernel.data(), (int)kernel.size(), nullptr, 0,
+                              (float*)out->data_.data()));
+    return out;
+}
+
+std::shared_ptr<Image> Image::Filter(const std::vector<float>& dx, const std::vector<float>& dy) const {
+    auto out = std::make_shared<Image>();
+    if (IsEmpty() || !IsFormat(*this, 1, 4)) {
+        LogError("[Filter] Unsupported image format.");
+        return out;
+    }
+    if (!GoodTaps(dx) || !GoodTaps(dy)) {
+        LogError("[FilterHorizontal] Unsupported image format or kernel size.");
+        return out;
+    }
+    out->Prepare(width_, height_, 1, 4);
+    Check(mi_icp_image_filter(Engine(), (const float*)data_.data(), width_, height_, dx.data(), (int)dx.size(), dy.data(), (int)dy.size(),
+                              (float*)out->data_.data()));
+    return out;
+}
+
+std::shared_ptr<Image> Image::Filter(FilterType type) const {
+    std::vector<float> dx, dy;
+    FilterTaps(type, &dx, &dy);
+    if (dx.empty()) {
+        LogError("[Filter] Unsupported filter type.");
+        return std::make_shared<Image>();
+    }
+    return Filter(dx, dy);
+}
+
+std::shared_ptr<Image> Image::Downsample() const {
+    auto out = std::make_shared<Image>();
+    if (IsEmpty() || (!IsFormat(*this, 1, 4) && !IsFormat(*this, 3, 1))) {
+        LogError("[Downsample] Unsupported image format.");
+        return out;
+    }
+    if (width_ / 2 == 0 || height_ / 2 == 0) return out;
+    out->Prepare(width_ / 2, height_ / 2, num_of_channels_, bytes_per_channel_);
+    Check(mi_icp_image_downsample(Engine(), data_.data(), width_, height_, num_of_channels_, bytes_per_channel_, out->data_.data()));
+    return out;
+}
+
+std::shared_ptr<Image> Image::BilateralFilter(int diameter, float sigma_color, float sigma_space) const {
+    auto out = std::make_shared<Image>();
+    if (diameter < 0 || diameter > MI_ICP_IMAGE_MAX_DIAMETER) {
+        LogError("[BilateralFilter] Diameter should be in [0, 31].");
+        return out;
+    }
+    if (IsEmpty() || !IsFormat(*this, 1, 4)) {
+        LogError("[BilateralFilter] Unsupported image format.");
+        return out;
+    }
+    float table[2 * MI_ICP_IMAGE_MAX_DIAMETER + 1];
+    Check(mi_icp_image_bilateral_table(diameter, sigma_space, table));
+    out->Prepare(width_, height_, 1, 4);
+    Check(mi_icp_image_bilateral(Engine(), (const float*)data_.data(), width_, height_, diameter, sigma_color, table, (float*)out->data_.data()));
+    return out;
+}
+
+Image& Image::ClipIntensity(float min, float max) {
+    if (IsEmpty() || !IsFormat(*this, 1, 4)) {
+        LogError("[ClipIntensity] Unsupported image format.");
+        return *this;
+    }
+    Check(mi_icp_image_clip(Engine(), (float*)data_.data(), width_, height_, min, max));
+    return *this;
+}
+
+Image& Image::LinearTransform(float scale, float offset) {
+    if (IsEmpty() || !KnownFormat(*this) || (bytes_per_channel_ != 1 && !IsFormat(*this, 1, 4))) {
+        LogError("[LinearTransform] Unsupported image format.");
+        return *this;
+    }
+    Check(mi_icp_image_linear_transform(Engine(), data_.data(), width_, height_, num_of_channels_, bytes_per_channel_, scale, offset));
+    return *this;
+}
+
+std::shared_ptr<Image> Image::CreateGrayImage(ColorToIntensityConversionType type) const {
+    auto out = std::make_shared<Image>();
+    if (IsEmpty()) return out;
+    if (!KnownFormat(*this)) {
+        LogError("[CreateGrayImage] Unsupported image format.");
+        return out;
+    }
+    out->Prepare(width_, height_, 1, 1);
+    Check(mi_icp_image_create_gray(Engine(), data_.data(), width_, height_, num_of_channels_, bytes_per_channel_, (int)type, out->data_.data()));
+    return out;
+}
+
+std::shared_ptr<Image> Image::CreateFloatImage(ColorToIntensityConversionType type) const {
+    auto out = std::make_shared<Image>();
+    if (IsEmpty()) return out;
+    if (!KnownFormat(*this)) {
+        LogError("[CreateFloatImage] Unsupported image format.");
+        return out;
+    }
+    out->Prepare(width_, height_, 1, 4);
+    Check(mi_icp_image_create_float(Engine(), data_.data(), width_, height_, num_of_channels_, bytes_per_channel_, (int)type,
+                                    (float*)out->data_.data()));
+    return out;
+}
+
+template <typename T>
+std::shared_ptr<Image> Image::CreateImageFromFloatImage() const {
+    auto out = std::make_shared<Image>();
+    if (IsEmpty() || !IsFormat(*this, 1, 4)) {
+        LogError("[CreateImageFromFloatImage] Unsupported image format.");
+        return out;
+    }
+    out->Prepare(width_, height_, 1, (int)sizeof(T));
+    Check(mi_icp_image_from_float(Engine(), (const float*)data_.data(), width_, height_, (int)sizeof(T), out->data_.data()));
+    return out;
+}
+template std::shared_ptr<Image> Image::CreateImageFromFloatImage<uint8_t>() const;
+template std::shared_ptr<Image> Image::CreateImageFromFloatImage<uint16_t>() const;
+
+ImagePyramid Image::CreatePyramid(size_t num_of_levels, bool with_gaussian_filter) const {
+    ImagePyramid pyramid;
+    if (IsEmpty() || (!IsFormat(*this, 1, 4) && !IsFormat(*this, 3, 1))) {
+        LogError("[CreateImagePyramid] Unsupported image format.");
+        return pyramid;
+    }
+    for (size_t i = 0; i < num_of_levels; ++i) {
+        if (i == 0) {
+            pyramid.emplace_back(std::make_shared<Image>(*this));
+            continue;
+        }
+        const Image& prev = *pyramid[i - 1];
+        auto level = std::make_shared<Image>();
+        if (prev.width_ / 2 > 0 && prev.height_ / 2 > 0) {
+            if (with_gaussian_filter && num_of_channels_ == 1) {   // Downsample(Filter(Gaussian3)) in one kernel
+                level->Prepare(prev.width_ / 2, prev.height_ / 2, 1, 4);
+                Check(mi_icp_image_pyramid_level(Engine(), (const float*)prev.data_.data(), prev.width_, prev.height_, (float*)level->data_.data()));
+            } else {
+                level = prev.Downsample();
+            }
+        }
+        pyramid.emplace_back(level);
+    }
+    return pyramid;
+}
+
+ImagePyramid Image::FilterPyramid(const ImagePyramid& input, FilterType type) {
+    ImagePyramid out;
+    for (const auto& level : input) out.emplace_back(level->Filter(type));
+    return out;
+}
+
+ImagePyramid Image::BilateralFilterPyramid(const ImagePyramid& input, int diameter, float sigma_color, float sigma_space) {
+    ImagePyramid out;
+    for (const auto& level : input) out.emplace_back(level->BilateralFilter(diameter, sigma_color, sigma_space));
+    return out;
+}
+
+std::shared_ptr<RGBDImage> RGBDImage::CreateFromColorAndDepth(const Image& color, const Image& depth, float depth_scale, float depth_trunc,
+                                                              bool convert_rgb_to_intensity) {
+    auto out = std::make_shared<RGBDImage>();
+    if (color.height_ != depth.height_ || color.width_ != depth.width_) {
+        LogError("[CreateFromColorAndDepth] Unsupported image format.");
+        return out;
+    }
+    out->depth_ = *depth.ConvertDepthToFloatImage(depth_scale, depth_trunc);
+    out->color_ = convert_rgb_to_intensity ? *color.CreateFloatImage() : color;
+    return out;
+}
+
+std::shared_ptr<RGBDImage> RGBDImage::CreateFromRedwoodFormat(const Image& color, const Image& depth, bool convert_rgb_to_intensity) {
+    return CreateFromColorAndDepth(color, depth, 1000.0f, 4.0f, convert_rgb_to_intensity);
+}
+
+std::shared_ptr<RGBDImage> RGBDImage::CreateFromTUMFormat(const Image& color, const Image& depth, bool convert_rgb_to_intensity) {
+    return CreateFromColorAndDepth(color, depth, 5000.0f, 4.0f, convert_rgb_to_intensity);
+}
+
+std::shared_ptr<RGBDImage> RGBDImage::CreateFromSUNFormat(const Image& color, const Image& depth, bool convert_rgb_to_intensity) {
+    return FromFormat(color, depth, MI_ICP_IMAGE_SUN, "[CreateRGBDImageFromSUNFormat] Unsupported image format.", 1000.0f, 7.0f, convert_rgb_to_intensity);
+}
+
+std::shared_ptr<RGBDImage> RGBDImage::CreateFromNYUFormat(const Image& color, const Image& depth, bool convert_rgb_to_intensity) {
+    return FromFormat(color, depth, MI_ICP_IMAGE_NYU, "[CreateRGBDImageFromNYUFormat] Unsupported image format.", 1000.0f, 7.0f, convert_rgb_to_intensity);
+}
+
+RGBDImagePyramid RGBDImage::CreatePyramid(size_t num_of_levels, bool with_gaussian_filter_for_color, bool with_gaussian_filter_for_depth) const {
+    RGBDImagePyramid out;
+    const ImagePyramid color = color_.CreatePyramid(num_of_levels, with_gaussian_filter_for_color);
+    const ImagePyramid depth = depth_.CreatePyramid(num_of_levels, with_gaussian_filter_for_depth);
+    if (color.size() != num_of_levels || depth.size() != num_of_levels) return out;
+    for (size_t i = 0; i < num_of_levels; ++i) out.emplace_back(std::make_shared<RGBDImage>(*color[i], *depth[i]));
+    return out;
+}
+
+RGBDImagePyramid RGBDImage::FilterPyramid(const RGBDImagePyramid& rgbd_image_pyramid, Image::FilterType type) {
+    RGBDImagePyramid out;
+    for (const auto& level : rgbd_image_pyramid)
+        out.emplace_back(std::make_shared<RGBDImage>(*level->color_.Filter(type), *level->depth_.Filter(type)));
+    return out;
+}
+
+RGBDImagePyramid RGBDImage::BilateralFilterPyramidDepth(const RGBDImagePyramid& rgbd_image_pyramid, int diameter, float sigma_depth,
+                                                        float sigma_space) {
+    RGBDImagePyramid out;
+    for (const auto& level : rgbd_image_pyramid)
+        out.emplace_back(std::make_shared<RGBDImage>(level->color_, *level->depth_.BilateralFilter(diameter, sigma_depth, sigma_space)));
+    return out;
+}
+
+}  // namespace geometry
+
 }  // namespace cupoch

@@ -627,20 +627,93 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             "input"_a, "salient_radius"_a = 0.0f, "non_max_radius"_a = 0.0f, "gamma_21"_a = 0.975f, "gamma_32"_a = 0.975f,
             "min_neighbors"_a = 5, "max_neighbors"_a = knn::NUM_MAX_NN);
 
-    // geometry.Image / geometry.RGBDImage as containers (cupoch_pybind/geometry/image.cpp): what integrate takes
-    py::class_<geometry::Image, std::shared_ptr<geometry::Image>>(mg, "Image")
+    // geometry.Image / geometry.RGBDImage (cupoch_pybind/geometry/image.cpp) with the reference's names and defaults.  As
+    // there, filter, bilateral_filter and create_pyramid first make a float image of anything that is not 1 x float32.
+    // The reference's module names ImageColorToIntensityConversionType's two values Gaussian3 and Gaussian5; Equal and
+    // Weighted are the values, the two misnomers stay as attributes.
+    typedef geometry::Image Img;
+    py::enum_<Img::FilterType>(mg, "ImageFilterType", "Enum class for Image filter types.")
+            .value("Gaussian3", Img::FilterType::Gaussian3)
+            .value("Gaussian5", Img::FilterType::Gaussian5)
+            .value("Gaussian7", Img::FilterType::Gaussian7)
+            .value("Sobel3dx", Img::FilterType::Sobel3Dx)
+            .value("Sobel3dy", Img::FilterType::Sobel3Dy)
+            .export_values();
+    py::enum_<Img::ColorToIntensityConversionType> c2i(mg, "ImageColorToIntensityConversionType");
+    c2i.value("Equal", Img::ColorToIntensityConversionType::Equal).value("Weighted", Img::ColorToIntensityConversionType::Weighted);
+    c2i.attr("Gaussian3") = c2i.attr("Equal");
+    c2i.attr("Gaussian5") = c2i.attr("Weighted");
+    auto as_float = [](const Img& im) { return im.num_of_channels_ != 1 || im.bytes_per_channel_ != 4 ? im.CreateFloatImage() : std::make_shared<Img>(im); };
+    py::class_<Img, std::shared_ptr<Img>>(mg, "Image", "The image class stores image with customizable width, height, num of channels and bytes per channel.")
             .def(py::init<>())
-            .def(py::init([](const py::array& a) { return std::make_shared<geometry::Image>(image_from_array(a)); }), "array"_a)
-            .def_readonly("width", &geometry::Image::width_)
-            .def_readonly("height", &geometry::Image::height_)
-            .def_readonly("num_of_channels", &geometry::Image::num_of_channels_)
-            .def_readonly("bytes_per_channel", &geometry::Image::bytes_per_channel_)
-            .def("is_empty", &geometry::Image::IsEmpty);
-    py::class_<geometry::RGBDImage, std::shared_ptr<geometry::RGBDImage>>(mg, "RGBDImage")
+            .def(py::init([](const py::array& a) { return std::make_shared<Img>(image_from_array(a)); }), "array"_a)
+            .def("__repr__", [](const Img& im) {
+                return std::string("Image of size ") + std::to_string(im.width_) + "x" + std::to_string(im.height_) + ", with " +
+                       std::to_string(im.num_of_channels_) + " channels.";
+            })
+            .def("__array__", [](const Img& im, const py::object&, const py::object&) -> py::array {
+                const char* kind = im.bytes_per_channel_ == 1 ? "uint8" : (im.bytes_per_channel_ == 2 ? "uint16" : "float32");
+                std::vector<py::ssize_t> shape = {im.height_, im.width_};
+                if (im.num_of_channels_ != 1) shape.push_back(im.num_of_channels_);
+                if (im.IsEmpty() || (im.bytes_per_channel_ != 1 && im.bytes_per_channel_ != 2 && im.bytes_per_channel_ != 4))
+                    return py::array(py::dtype("uint8"), std::vector<py::ssize_t>{0, 0});
+                py::array out(py::dtype(kind), shape);
+                const std::vector<uint8_t> h = im.GetData();
+                std::memcpy(out.mutable_data(), h.data(), h.size());
+                return out;
+            }, "dtype"_a = py::none(), "copy"_a = py::none())
+            .def("clip_intensity", [](std::shared_ptr<Img> im, float lo, float hi) { im->ClipIntensity(lo, hi); return im; },
+                 "Function to clip intensity", "min"_a = 0.0, "max"_a = 1.0)
+            .def("linear_transform", [](std::shared_ptr<Img> im, float scale, float offset) { im->LinearTransform(scale, offset); return im; },
+                 "Function to transform linearly", "scale"_a = 1.0, "offset"_a = 0.0)
+            .def("downsample", &Img::Downsample)
+            .def("filter", [as_float](const Img& im, Img::FilterType t) { return as_float(im)->Filter(t); }, "Function to filter Image", "filter_type"_a)
+            .def("flip_vertical", &Img::FlipVertical, "Function to flip image vertically (upside down)")
+            .def("flip_horizontal", &Img::FlipHorizontal, "Function to flip image horizontally (from left to right)")
+            .def("transpose", &Img::Transpose)
+            .def("bilateral_filter", [as_float](const Img& im, int diameter, float sigma_color, float sigma_space) {
+                return as_float(im)->BilateralFilter(diameter, sigma_color, sigma_space);
+            }, "Function to apply bilateral filter to the image", "diameter"_a, "sigma_color"_a, "sigma_space"_a)
+            .def("create_gray_image", &Img::CreateGrayImage, "Create gray image.", "type"_a = Img::ColorToIntensityConversionType::Weighted)
+            .def("create_float_image", &Img::CreateFloatImage, "Create float gray image.", "type"_a = Img::ColorToIntensityConversionType::Weighted)
+            .def("convert_depth_to_float_image", &Img::ConvertDepthToFloatImage, "depth_scale"_a = 1000.0, "depth_trunc"_a = 3.0)
+            .def("create_pyramid", [as_float](const Img& im, size_t n, bool g) { return as_float(im)->CreatePyramid(n, g); },
+                 "Function to create ImagePyramid", "num_of_levels"_a, "with_gaussian_filter"_a)
+            .def_static("filter_pyramid", &Img::FilterPyramid, "Function to filter ImagePyramid", "image_pyramid"_a, "filter_type"_a)
+            .def_static("bilateral_filter_pyramid", &Img::BilateralFilterPyramid, "Function to filter ImagePyramid", "image_pyramid"_a,
+                        "diameter"_a, "sigma_color"_a, "sigma_space"_a)
+            .def_readonly("width", &Img::width_)
+            .def_readonly("height", &Img::height_)
+            .def_readonly("num_of_channels", &Img::num_of_channels_)
+            .def_readonly("bytes_per_channel", &Img::bytes_per_channel_)
+            .def("is_empty", &Img::IsEmpty);
+    typedef geometry::RGBDImage Rgbd;
+    py::class_<Rgbd, std::shared_ptr<Rgbd>>(mg, "RGBDImage", "RGBDImage is for a pair of registered color and depth images, viewed from the same "
+                                                             "view, of the same resolution. If you have other format, convert it first.")
             .def(py::init<>())
-            .def(py::init<const geometry::Image&, const geometry::Image&>(), "color"_a, "depth"_a)
-            .def_readwrite("color", &geometry::RGBDImage::color_)
-            .def_readwrite("depth", &geometry::RGBDImage::depth_);
+            .def(py::init<const Img&, const Img&>(), "color"_a, "depth"_a)
+            .def_readwrite("color", &Rgbd::color_)
+            .def_readwrite("depth", &Rgbd::depth_)
+            .def("__repr__", [](const Rgbd& r) {
+                auto one = [](const Img& im) { return std::to_string(im.width_) + "x" + std::to_string(im.height_) + ", with " + std::to_string(im.num_of_channels_) + " channels.\n"; };
+                return std::string("RGBDImage of size \nColor image : ") + one(r.color_) + "Depth image : " + one(r.depth_) + "Use numpy.asarray to access buffer data.";
+            })
+            .def("is_empty", &Rgbd::IsEmpty)
+            .def("create_pyramid", &Rgbd::CreatePyramid, "num_of_levels"_a, "with_gaussian_filter_for_color"_a = true,
+                 "with_gaussian_filter_for_depth"_a = false)
+            .def_static("filter_pyramid", &Rgbd::FilterPyramid, "rgbd_image_pyramid"_a, "filter_type"_a)
+            .def_static("bilateral_filter_pyramid_depth", &Rgbd::BilateralFilterPyramidDepth, "rgbd_image_pyramid"_a, "diameter"_a,
+                        "sigma_depth"_a, "sigma_space"_a)
+            .def_static("create_from_color_and_depth", &Rgbd::CreateFromColorAndDepth, "Function to make RGBDImage from color and depth image",
+                        "color"_a, "depth"_a, "depth_scale"_a = 1000.0, "depth_trunc"_a = 3.0, "convert_rgb_to_intensity"_a = true)
+            .def_static("create_from_redwood_format", &Rgbd::CreateFromRedwoodFormat, "Function to make RGBDImage (for Redwood format)",
+                        "color"_a, "depth"_a, "convert_rgb_to_intensity"_a = true)
+            .def_static("create_from_tum_format", &Rgbd::CreateFromTUMFormat, "Function to make RGBDImage (for TUM format)", "color"_a,
+                        "depth"_a, "convert_rgb_to_intensity"_a = true)
+            .def_static("create_from_sun_format", &Rgbd::CreateFromSUNFormat, "Function to make RGBDImage (for SUN format)", "color"_a,
+                        "depth"_a, "convert_rgb_to_intensity"_a = true)
+            .def_static("create_from_nyu_format", &Rgbd::CreateFromNYUFormat, "Function to make RGBDImage (for NYU format)", "color"_a,
+                        "depth"_a, "convert_rgb_to_intensity"_a = true);
 
     // geometry.OccupancyVoxel / geometry.OccupancyGrid (cupoch_pybind/geometry/occupancygrid.cpp) with the reference's
     // names, defaults and read-write attributes.  Not bound, as not built: create_from_voxel_grid.

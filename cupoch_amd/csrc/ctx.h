@@ -13,6 +13,7 @@
 //   mi_collision.hip collision::ComputeIntersection (grids against grids, line sets, primitives), CreateVoxelGrid
 //   mi_graph.hip     geometry::Graph<3> (construct, lattice, edge weights and removal) and its shortest-path search
 //   mi_laserscan.hip geometry::LaserScanBuffer (scans to points, points / depth frames to scans, the two filters)
+//   mi_image.hip     geometry::Image / RGBDImage processing (filters, the pyramid level, bilateral, conversions, moves)
 //   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry,
 //                    RemoveStatisticalOutliers / RemoveRadiusOutliers, ClusterDBSCAN, ComputeISSKeypoints
 //   mi_comm.hip      the ranks' exchange: mailbox, device inboxes, in-library RCCL, self-test and choice

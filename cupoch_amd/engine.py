@@ -1258,6 +1258,138 @@ class Engine:
         _lib.load().mi_icp_laserscan_limits(C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
+    # -- image (include/mi_icp.h "image"; pixels are contiguous device tensors [H, W] or [H, W, C], taps and the table host) --
+    @staticmethod
+    def _image_dims(t):
+        """-> (height, width, channels, bytes per channel) of a device tensor [H, W] or [H, W, C]"""
+        if t.dim() not in (2, 3) or not t.is_cuda or not t.is_contiguous():
+            raise TypeError("an image is a contiguous device tensor [H, W] or [H, W, C]")
+        return int(t.shape[0]), int(t.shape[1]), (int(t.shape[2]) if t.dim() == 3 else 1), int(t.element_size())
+
+    @staticmethod
+    def _taps(k):
+        k = np.ascontiguousarray(np.asarray(k, np.float32).reshape(-1))
+        return k, k.ctypes.data_as(C.c_void_p), int(k.size)
+
+    def image_filter(self, src, dx, dy=None):
+        """Image::Filter(dx, dy), or Image::FilterHorizontal(dx) with dy None; src [H, W] float32 -> the filtered copy"""
+        h, w, ch, b = self._image_dims(src)
+        if (ch, b) != (1, 4) or src.dim() != 2:
+            raise TypeError("image_filter takes a 1 x float32 image")
+        out = torch.empty_like(src)
+        kx, px, nx = self._taps(dx)
+        ky, py, ny = self._taps(dy) if dy is not None else (None, None, 0)
+        self._chk(self._L.mi_icp_image_filter(self._ctx, self._ptr(src), w, h, px, nx, py, ny, self._ptr(out)))
+        return out
+
+    def image_downsample(self, src):
+        """Image::Downsample: [H, W] float32 or [H, W, 3] uint8 -> [H // 2, W // 2(, 3)]"""
+        h, w, ch, b = self._image_dims(src)
+        out = torch.empty((h // 2, w // 2) + tuple(src.shape[2:]), dtype=src.dtype, device=src.device)
+        self._chk(self._L.mi_icp_image_downsample(self._ctx, self._ptr(src), w, h, ch, b, self._ptr(out)))
+        return out
+
+    def image_pyramid_level(self, src):
+        """Downsample(Filter(Gaussian3)) of [H, W] float32 in one kernel"""
+        h, w, ch, b = self._image_dims(src)
+        if (ch, b) != (1, 4) or src.dim() != 2:
+            raise TypeError("image_pyramid_level takes a 1 x float32 image")
+        out = torch.empty((h // 2, w // 2), dtype=src.dtype, device=src.device)
+        self._chk(self._L.mi_icp_image_pyramid_level(self._ctx, self._ptr(src), w, h, self._ptr(out)))
+        return out
+
+    @staticmethod
+    def image_bilateral_table(diameter, sigma_space):
+        """the spatial table of Image::BilateralFilter, 2 * diameter + 1 floats (host arithmetic)"""
+        t = np.zeros(2 * max(int(diameter), 0) + 1, np.float32)
+        if _lib.load().mi_icp_image_bilateral_table(int(diameter), float(sigma_space), t.ctypes.data_as(C.c_void_p)) < 0:
+            raise MiIcpError("image_bilateral_table: diameter must be in [0, %d]" % Engine.image_limits()[1])
+        return t
+
+    def image_bilateral(self, src, diameter, sigma_color, sigma_space, exp_kind=None):
+        """Image::BilateralFilter of [H, W] float32.  exp_kind (measurements and tests only): 1 the hardware
+        exponential, which is what runs by default, 0 expf."""
+        h, w, ch, b = self._image_dims(src)
+        if (ch, b) != (1, 4) or src.dim() != 2:
+            raise TypeError("image_bilateral takes a 1 x float32 image")
+        t = self.image_bilateral_table(diameter, sigma_space)
+        out = torch.empty_like(src)
+        args = (self._ctx, self._ptr(src), w, h, int(diameter), float(sigma_color), t.ctypes.data_as(C.c_void_p), self._ptr(out))
+        if exp_kind is None:
+            self._chk(self._L.mi_icp_image_bilateral(*args))
+        else:
+            self._chk(self._L.mi_icp_debug_image_bilateral(*(args + (int(exp_kind),))))
+        return out
+
+    def image_create_float(self, src, type=1):
+        """Image::CreateFloatImage -> [H, W] float32"""
+        h, w, ch, b = self._image_dims(src)
+        out = torch.empty((h, w), dtype=torch.float32, device=src.device)
+        self._chk(self._L.mi_icp_image_create_float(self._ctx, self._ptr(src), w, h, ch, b, int(type), self._ptr(out)))
+        return out
+
+    def image_depth_to_float(self, src, depth_scale=1000.0, depth_trunc=3.0):
+        """Image::ConvertDepthToFloatImage -> [H, W] float32"""
+        h, w, ch, b = self._image_dims(src)
+        out = torch.empty((h, w), dtype=torch.float32, device=src.device)
+        self._chk(self._L.mi_icp_image_depth_to_float(self._ctx, self._ptr(src), w, h, ch, b, float(depth_scale),
+                                                      float(depth_trunc), self._ptr(out)))
+        return out
+
+    def image_create_gray(self, src, type=1):
+        """Image::CreateGrayImage -> [H, W] uint8"""
+        h, w, ch, b = self._image_dims(src)
+        out = torch.empty((h, w), dtype=torch.uint8, device=src.device)
+        self._chk(self._L.mi_icp_image_create_gray(self._ctx, self._ptr(src), w, h, ch, b, int(type), self._ptr(out)))
+        return out
+
+    def image_from_float(self, src, bytes_per_channel):
+        """Image::CreateImageFromFloatImage<uint8_t | uint16_t>: [H, W] float32 -> [H, W] uint8 (1) or uint16 (2)"""
+        h, w, ch, b = self._image_dims(src)
+        if (ch, b) != (1, 4) or src.dim() != 2:
+            raise TypeError("image_from_float takes a 1 x float32 image")
+        if int(bytes_per_channel) not in (1, 2):
+            raise ValueError("bytes_per_channel must be 1 or 2")
+        out = torch.empty((h, w), dtype=torch.uint8 if int(bytes_per_channel) == 1 else torch.uint16, device=src.device)
+        self._chk(self._L.mi_icp_image_from_float(self._ctx, self._ptr(src), w, h, int(bytes_per_channel), self._ptr(out)))
+        return out
+
+    def image_linear_transform(self, data, scale=1.0, offset=0.0):
+        """Image::LinearTransform in place ([H, W] float32 or uint8 of any channel count)"""
+        h, w, ch, b = self._image_dims(data)
+        self._chk(self._L.mi_icp_image_linear_transform(self._ctx, self._ptr(data), w, h, ch, b, float(scale), float(offset)))
+
+    def image_clip(self, data, min=0.0, max=1.0):
+        """Image::ClipIntensity in place ([H, W] float32)"""
+        h, w, ch, b = self._image_dims(data)
+        if (ch, b) != (1, 4):
+            raise TypeError("image_clip takes a 1 x float32 image")
+        self._chk(self._L.mi_icp_image_clip(self._ctx, self._ptr(data), w, h, float(min), float(max)))
+
+    def image_move(self, src, op):
+        """op 0 Image::Transpose, 1 FlipVertical, 2 FlipHorizontal -> the moved copy"""
+        h, w, ch, b = self._image_dims(src)
+        shape = ((w, h) if int(op) == 0 else (h, w)) + tuple(src.shape[2:])
+        out = torch.empty(shape, dtype=src.dtype, device=src.device)
+        self._chk(self._L.mi_icp_image_move(self._ctx, self._ptr(src), w, h, ch * b, int(op), self._ptr(out)))
+        return out
+
+    def image_depth_format(self, src, format):
+        """format 0 SUN, 1 NYU: [H, W] uint16 -> the decoded copy"""
+        h, w, ch, b = self._image_dims(src)
+        if (ch, b) != (1, 2):
+            raise TypeError("image_depth_format takes a 1 x uint16 image")
+        out = torch.empty_like(src)
+        self._chk(self._L.mi_icp_image_depth_format(self._ctx, self._ptr(src), w, h, int(format), self._ptr(out)))
+        return out
+
+    @staticmethod
+    def image_limits():
+        """-> (the longest filter, the largest bilateral radius)"""
+        a, b = C.c_int32(0), C.c_int32(0)
+        _lib.load().mi_icp_image_limits(C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def compute_rgbd_odometry(self, source_color, source_depth, target_color, target_depth, intrinsic4,
                               odo_init=None, jacobian=1, iterations=(20, 10, 5), max_depth_diff=0.03,
                               min_depth=0.0, max_depth=4.0, weighted=False, prev_twist=None, nu=5.0,

@@ -15,7 +15,11 @@ built: the factories from meshes, clouds with correspondences and oriented boxes
 Graph mirrors geometry/graph.h (Graph<3>; python surface src/python/cupoch_pybind/geometry/graph.cpp): the roadmap
 cupoch_amd.planning searches; not built: Graph2D, create_from_triangle_mesh, file I/O and visualisation.
 LaserScanBuffer mirrors geometry/laserscanbuffer.h (python surface src/python/cupoch_pybind/geometry/laserscanbuffer.cpp)
-with PointCloud.create_from_laserscanbuffer; not built: file I/O and visualisation."""
+with PointCloud.create_from_laserscanbuffer; not built: file I/O and visualisation.
+Image / RGBDImage mirror geometry/image.h and geometry/rgbdimage.h (python surface
+src/python/cupoch_pybind/geometry/image.cpp): filters, bilateral filter, pyramids, format conversions and the RGB-D
+factories; not built: Image.FloatValueAt, image file I/O, PointCloud.create_from_disparity."""
+import enum
 import sys
 
 import numpy as np
@@ -446,21 +450,276 @@ class keypoint:
         return input.select_by_mask(mask), utility.BoolVector(mask)
 
 
+class ImageFilterType(enum.IntEnum):
+    """Image::FilterType with the names of the reference's Python module"""
+    Gaussian3 = 0
+    Gaussian5 = 1
+    Gaussian7 = 2
+    Sobel3dx = 3
+    Sobel3dy = 4
+
+
+class ImageColorToIntensityConversionType(enum.IntEnum):
+    """Image::ColorToIntensityConversionType.  The reference's Python module misnames the two values Gaussian3 and
+    Gaussian5; those names stay as aliases."""
+    Equal = 0
+    Weighted = 1
+    Gaussian3 = 0
+    Gaussian5 = 1
+
+
+_FILTER_TAPS = {
+    ImageFilterType.Gaussian3: ((.25, .5, .25),) * 2,
+    ImageFilterType.Gaussian5: ((.0625, .25, .375, .25, .0625),) * 2,
+    ImageFilterType.Gaussian7: ((.03125, .109375, .21875, .28125, .21875, .109375, .03125),) * 2,
+    ImageFilterType.Sobel3dx: ((-1.0, 0.0, 1.0), (1.0, 2.0, 1.0)),
+    ImageFilterType.Sobel3dy: ((1.0, 2.0, 1.0), (-1.0, 0.0, 1.0)),
+}
+IMAGE_MAX_TAPS = 31           # MI_ICP_IMAGE_MAX_TAPS
+IMAGE_MAX_DIAMETER = 31       # MI_ICP_IMAGE_MAX_DIAMETER
+
+
+def _image_error(name, what="Unsupported image format."):
+    print("[cupoch_amd] Error: [%s] %s" % (name, what))
+
+
 class Image:
-    """geometry::Image as the factories below see it (geometry/image.h:52-110): a [H, W] or
-    [H, W, C] array (numpy, or a torch tensor on either side); float32 / uint16 depth,
-    uint8 x 3 or float32 x 1 colour.  Image processing (pyramids, filters) is out of scope."""
+    """geometry::Image (geometry/image.h; python surface cupoch_pybind/geometry/image.cpp): a [H, W] or [H, W, C] array
+    of uint8, uint16 or float32 -- numpy, or a torch tensor on either side -- in `data`.  include/mi_icp.h ("image")
+    states what every operation computes.  Results are new Images whose pixels stay on the device (a torch tensor);
+    np.asarray(img) brings them to the host.  As in the reference, a format an operation does not take is printed
+    ("[cupoch_amd] Error: [<Name>] Unsupported image format.") and the call returns an empty Image (self for the two
+    in-place calls); nothing is raised.  filter, bilateral_filter and create_pyramid first make a float image of
+    anything that is not 1 x float32, as the reference's Python module does; filter_taps / filter_horizontal, the C++
+    Filter(dx, dy) / FilterHorizontal, turn such input away.  Not built: FloatValueAt, file I/O."""
 
     def __init__(self, data=None):
-        self.data = data
+        self.data = _img(data)
 
+    # ---- the container
     @property
     def height(self):
         return 0 if self.data is None else int(self.data.shape[0])
 
     @property
     def width(self):
-        return 0 if self.data is None else int(self.data.shape[1])
+        return 0 if self.data is None or len(self.data.shape) < 2 else int(self.data.shape[1])
+
+    @property
+    def num_of_channels(self):
+        return 0 if self.data is None else (int(self.data.shape[2]) if len(self.data.shape) == 3 else 1)
+
+    @property
+    def bytes_per_channel(self):
+        if self.data is None:
+            return 0
+        return int(self.data.element_size()) if _is_torch(self.data) else int(self.data.dtype.itemsize)
+
+    def is_empty(self):
+        return self.width <= 0 or self.height <= 0 or self.num_of_channels <= 0
+
+    def __repr__(self):
+        return "Image of size %dx%d, with %d channels." % (self.width, self.height, self.num_of_channels)
+
+    def __array__(self, dtype=None, copy=None):
+        d = self.data
+        a = np.zeros((0, 0), np.uint8) if d is None else (d.detach().cpu().numpy() if _is_torch(d) else np.asarray(d))
+        return a if dtype is None else a.astype(dtype)
+
+    def test_image_boundary(self, u, v, inner_margin=0.0):
+        """Image::TestImageBoundary"""
+        return bool(u >= inner_margin and u < self.width - inner_margin and v >= inner_margin and v < self.height - inner_margin)
+
+    # ---- staging
+    def _is(self, channels, bytes_per_channel):
+        return (not self.is_empty()) and self.num_of_channels == channels and self.bytes_per_channel == bytes_per_channel
+
+    def _kind_ok(self):
+        name = str(self.data.dtype).replace("torch.", "")
+        return name in ("uint8", "uint16", "float32") and len(self.data.shape) in (2, 3)
+
+    def _staged(self):
+        """(engine, the pixels as a contiguous device tensor)"""
+        d = self.data
+        if _is_torch(d) and d.is_cuda:
+            return get_engine(d.device.index), d.contiguous()
+        eng = get_engine()
+        a = d.detach().numpy() if _is_torch(d) else np.asarray(d)
+        return eng, torch.from_numpy(np.ascontiguousarray(a)).to(torch.device("cuda", eng.device))
+
+    @staticmethod
+    def _empty():
+        return Image()
+
+    # ---- in place
+    def clip_intensity(self, min=0.0, max=1.0):
+        if not self._is(1, 4):
+            _image_error("ClipIntensity")
+            return self
+        eng, t = self._staged()
+        eng.image_clip(t, min, max)
+        self.data = t
+        return self
+
+    def linear_transform(self, scale=1.0, offset=0.0):
+        if self.is_empty() or not (self.bytes_per_channel == 1 or self._is(1, 4)) or self.num_of_channels > 4:
+            _image_error("LinearTransform")
+            return self
+        eng, t = self._staged()
+        eng.image_linear_transform(t, scale, offset)
+        self.data = t
+        return self
+
+    # ---- new images
+    def downsample(self):
+        if not (self._is(1, 4) or self._is(3, 1)):
+            _image_error("Downsample")
+            return self._empty()
+        if self.width // 2 == 0 or self.height // 2 == 0:
+            return self._empty()
+        eng, t = self._staged()
+        return Image(eng.image_downsample(t))
+
+    def filter_horizontal(self, kernel):
+        """Image::FilterHorizontal (C++ only in the reference)"""
+        k = np.asarray(kernel, np.float32).reshape(-1)
+        if not self._is(1, 4) or k.size % 2 != 1 or k.size > IMAGE_MAX_TAPS:
+            _image_error("FilterHorizontal", "Unsupported image format or kernel size.")
+            return self._empty()
+        eng, t = self._staged()
+        return Image(eng.image_filter(t.reshape(self.height, self.width), k))
+
+    def filter_taps(self, dx, dy):
+        """Image::Filter(dx, dy) (C++ only in the reference): odd tap counts up to IMAGE_MAX_TAPS"""
+        kx, ky = np.asarray(dx, np.float32).reshape(-1), np.asarray(dy, np.float32).reshape(-1)
+        if not self._is(1, 4):
+            _image_error("Filter")
+            return self._empty()
+        if kx.size % 2 != 1 or ky.size % 2 != 1 or kx.size > IMAGE_MAX_TAPS or ky.size > IMAGE_MAX_TAPS:
+            _image_error("FilterHorizontal", "Unsupported image format or kernel size.")
+            return self._empty()
+        eng, t = self._staged()
+        return Image(eng.image_filter(t.reshape(self.height, self.width), kx, ky))
+
+    def _as_float(self):
+        return self if self._is(1, 4) else self.create_float_image()
+
+    def filter(self, filter_type):
+        try:
+            taps = _FILTER_TAPS[ImageFilterType(int(filter_type))]
+        except ValueError:
+            _image_error("Filter", "Unsupported filter type.")
+            return self._empty()
+        f = self._as_float()
+        return self._empty() if f.is_empty() else f.filter_taps(*taps)
+
+    def flip_vertical(self):
+        return self._move(1, "FlipVertical")
+
+    def flip_horizontal(self):
+        return self._move(2, "FlipHorizontal")
+
+    def transpose(self):
+        """Image::Transpose (C++ only in the reference)"""
+        return self._move(0, "Transpose")
+
+    def _move(self, op, name):
+        if self.is_empty():
+            return self._empty()
+        if not self._kind_ok() or self.num_of_channels * self.bytes_per_channel > 16:
+            _image_error(name)
+            return self._empty()
+        eng, t = self._staged()
+        return Image(eng.image_move(t, op))
+
+    def bilateral_filter(self, diameter, sigma_color, sigma_space):
+        """`diameter` is a radius: the window is (2 diameter + 1)^2, diameter in [0, IMAGE_MAX_DIAMETER]"""
+        if int(diameter) < 0 or int(diameter) > IMAGE_MAX_DIAMETER:
+            _image_error("BilateralFilter", "Diameter should be in [0, %d]." % IMAGE_MAX_DIAMETER)
+            return self._empty()
+        f = self._as_float()
+        if f.is_empty():
+            return self._empty()
+        eng, t = f._staged()
+        return Image(eng.image_bilateral(t.reshape(f.height, f.width), int(diameter), sigma_color, sigma_space))
+
+    def _convertible(self, name):
+        if self.is_empty():
+            return False
+        if not self._kind_ok() or self.num_of_channels > 4:
+            _image_error(name)
+            return False
+        return True
+
+    def create_gray_image(self, type=ImageColorToIntensityConversionType.Weighted):
+        if not self._convertible("CreateGrayImage"):
+            return self._empty()
+        eng, t = self._staged()
+        return Image(eng.image_create_gray(t, int(type)))
+
+    def create_float_image(self, type=ImageColorToIntensityConversionType.Weighted):
+        if not self._convertible("CreateFloatImage"):
+            return self._empty()
+        eng, t = self._staged()
+        return Image(eng.image_create_float(t, int(type)))
+
+    def convert_depth_to_float_image(self, depth_scale=1000.0, depth_trunc=3.0):
+        """Image::ConvertDepthToFloatImage (C++ only in the reference)"""
+        if not self._convertible("ConvertDepthToFloatImage"):
+            return self._empty()
+        eng, t = self._staged()
+        return Image(eng.image_depth_to_float(t, depth_scale, depth_trunc))
+
+    def create_image_from_float_image(self, bytes_per_channel):
+        """Image::CreateImageFromFloatImage<uint8_t> (1) / <uint16_t> (2) (C++ only in the reference)"""
+        if not self._is(1, 4) or int(bytes_per_channel) not in (1, 2):
+            _image_error("CreateImageFromFloatImage")
+            return self._empty()
+        eng, t = self._staged()
+        return Image(eng.image_from_float(t.reshape(self.height, self.width), int(bytes_per_channel)))
+
+    def _pyramid(self, num_of_levels, with_gaussian_filter):
+        """Image::CreatePyramid on 1 x float32 or 3 x uint8 (the C++ rule)"""
+        if not (self._is(1, 4) or self._is(3, 1)):
+            _image_error("CreateImagePyramid")
+            return []
+        eng, t = self._staged()
+        if self.num_of_channels == 1:
+            t = t.reshape(self.height, self.width)
+        levels = []
+        for i in range(int(num_of_levels)):
+            if i == 0:
+                levels.append(Image(t.clone()))
+                continue
+            prev = levels[-1]
+            if prev.is_empty() or prev.width // 2 == 0 or prev.height // 2 == 0:
+                levels.append(Image())
+            elif with_gaussian_filter and self.num_of_channels == 1:
+                levels.append(Image(eng.image_pyramid_level(prev.data)))
+            else:
+                levels.append(Image(eng.image_downsample(prev.data)))
+        return levels
+
+    def create_pyramid(self, num_of_levels, with_gaussian_filter):
+        f = self._as_float()
+        return [] if f.is_empty() else f._pyramid(num_of_levels, with_gaussian_filter)
+
+    @staticmethod
+    def filter_pyramid(image_pyramid, filter_type):
+        taps = _FILTER_TAPS[ImageFilterType(int(filter_type))]
+        return [Image(level).filter_taps(*taps) for level in image_pyramid]
+
+    @staticmethod
+    def bilateral_filter_pyramid(image_pyramid, diameter, sigma_color, sigma_space):
+        out = []
+        for level in image_pyramid:
+            level = Image(level)
+            if not level._is(1, 4):
+                _image_error("BilateralFilter")
+                out.append(Image())
+            else:
+                out.append(level.bilateral_filter(diameter, sigma_color, sigma_space))
+        return out
 
 
 def _img(x):
@@ -468,11 +727,79 @@ def _img(x):
 
 
 class RGBDImage:
-    """geometry::RGBDImage (geometry/rgbdimage.h:38-120): color + float depth."""
+    """geometry::RGBDImage (geometry/rgbdimage.h; python surface cupoch_pybind/geometry/image.cpp): colour + depth.
+    `color` and `depth` hold the pixel arrays themselves (what Image.data holds), as every consumer here reads them;
+    the factories below leave device tensors there.  Errors are printed, as for Image."""
 
     def __init__(self, color=None, depth=None):
         self.color = _img(color)
         self.depth = _img(depth)
+
+    def is_empty(self):
+        return Image(self.color).is_empty() or Image(self.depth).is_empty()
+
+    def __repr__(self):
+        c, d = Image(self.color), Image(self.depth)
+        return ("RGBDImage of size \nColor image : %dx%d, with %d channels.\nDepth image : %dx%d, with %d channels.\n"
+                "Use numpy.asarray to access buffer data." % (c.width, c.height, c.num_of_channels, d.width, d.height,
+                                                               d.num_of_channels))
+
+    @staticmethod
+    def create_from_color_and_depth(color, depth, depth_scale=1000.0, depth_trunc=3.0, convert_rgb_to_intensity=True,
+                                    _name="CreateFromColorAndDepth"):
+        color, depth = Image(color), Image(depth)
+        if color.height != depth.height or color.width != depth.width:
+            _image_error(_name)
+            return RGBDImage()
+        d = depth.convert_depth_to_float_image(depth_scale, depth_trunc)
+        if convert_rgb_to_intensity:
+            c = color.create_float_image()
+        else:
+            c = Image() if color.is_empty() else Image(color._staged()[1].clone())
+        return RGBDImage(c, d)
+
+    @staticmethod
+    def create_from_redwood_format(color, depth, convert_rgb_to_intensity=True):
+        return RGBDImage.create_from_color_and_depth(color, depth, 1000.0, 4.0, convert_rgb_to_intensity)
+
+    @staticmethod
+    def create_from_tum_format(color, depth, convert_rgb_to_intensity=True):
+        return RGBDImage.create_from_color_and_depth(color, depth, 5000.0, 4.0, convert_rgb_to_intensity)
+
+    @staticmethod
+    def _decoded(color, depth, fmt, name, convert_rgb_to_intensity):
+        color, depth = Image(color), Image(depth)
+        if color.height != depth.height or color.width != depth.width or not depth._is(1, 2):
+            _image_error(name)
+            return RGBDImage()
+        eng, t = depth._staged()
+        decoded = Image(eng.image_depth_format(t.reshape(depth.height, depth.width), fmt))
+        return RGBDImage.create_from_color_and_depth(color, decoded, 1000.0, 7.0, convert_rgb_to_intensity, _name=name)
+
+    @staticmethod
+    def create_from_sun_format(color, depth, convert_rgb_to_intensity=True):
+        return RGBDImage._decoded(color, depth, 0, "CreateRGBDImageFromSUNFormat", convert_rgb_to_intensity)
+
+    @staticmethod
+    def create_from_nyu_format(color, depth, convert_rgb_to_intensity=True):
+        return RGBDImage._decoded(color, depth, 1, "CreateRGBDImageFromNYUFormat", convert_rgb_to_intensity)
+
+    def create_pyramid(self, num_of_levels, with_gaussian_filter_for_color=True, with_gaussian_filter_for_depth=False):
+        """RGBDImage::CreatePyramid: the C++ rule for both images (1 x float32 or 3 x uint8)"""
+        c = Image(self.color)._pyramid(num_of_levels, with_gaussian_filter_for_color)
+        d = Image(self.depth)._pyramid(num_of_levels, with_gaussian_filter_for_depth)
+        if len(c) != int(num_of_levels) or len(d) != int(num_of_levels):
+            return []
+        return [RGBDImage(a, b) for a, b in zip(c, d)]
+
+    @staticmethod
+    def filter_pyramid(rgbd_image_pyramid, filter_type):
+        return [RGBDImage(*Image.filter_pyramid([level.color, level.depth], filter_type)) for level in rgbd_image_pyramid]
+
+    @staticmethod
+    def bilateral_filter_pyramid_depth(rgbd_image_pyramid, diameter, sigma_depth, sigma_space):
+        return [RGBDImage(level.color, Image.bilateral_filter_pyramid([level.depth], diameter, sigma_depth, sigma_space)[0])
+                for level in rgbd_image_pyramid]
 
 
 def _create_from_depth_image(depth, intrinsic, extrinsic=None, depth_scale=1000.0, depth_trunc=1000.0, stride=1):

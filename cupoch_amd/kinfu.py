@@ -1,8 +1,9 @@
 """The ICP and volume sides of cupoch.kinfu.KinfuPipeline (src/cupoch/kinfu/kinfu.h:36-121, kinfu.cpp:51-143): the
 depth-frame -> point-cloud pyramid of SurfaceMeasurement, the coarse-to-fine PoseEstimation that calls
 RegistrationICP / RegistrationColoredICP once per pyramid level, and the two volume steps of ProcessFrame
-(Integrate, then one Raycast per pyramid level).  ProcessFrame as a whole is not built: it also needs the image
-pyramid and the bilateral depth filter (scope)."""
+(Integrate, then one Raycast per pyramid level).  The image pyramid and the bilateral depth filter that ProcessFrame
+needs in front of them exist now (geometry.RGBDImage.create_pyramid / bilateral_filter_pyramid_depth);
+ProcessFrame as a whole is still not composed from these pieces."""
 import numpy as np
 
 from . import geometry, registration
@@ -12,7 +13,8 @@ from .registration import TransformationEstimationType
 
 class KinfuOption:
     """kinfu.h:36-82, the fields PoseEstimation / SurfaceMeasurement and the volume read (diameter, sigma_depth and
-    sigma_space belong to the bilateral filter, which is not built)."""
+    sigma_space belong to the bilateral filter, geometry.RGBDImage.bilateral_filter_pyramid_depth, which ProcessFrame would
+    call; it is not composed here)."""
 
     def __init__(self, num_pyramid_levels=4, depth_cutoff=3.0, distance_threshold=0.5,
                  icp_iterations=(20, 20, 20, 20), tf_type=TransformationEstimationType.PointToPlane,

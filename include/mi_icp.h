@@ -1350,6 +1350,90 @@ MI_ICP_API int mi_icp_laserscan_scale(mi_icp_ctx* ctx, float* ranges, int64_t co
 /* the LDS path's largest bin count and the largest bin count taken at all (no context, no device) */
 MI_ICP_API int mi_icp_laserscan_limits(int64_t* lds_max_bins, int64_t* max_bins);
 
+/* ---- image (geometry/image.{h,cu}, image_factory.cu, rgbdimage.{h,cu}, rgbdimage_factory.cu) ----
+ * Image processing in front of everything that takes an image: filters, pyramids, the bilateral filter and the
+ * conversions between pixel formats.  An image is [height][width][channels] elements of bytes_per_channel bytes, row
+ * after row, in DEVICE memory (no mem_kind: a surface stages host pixels itself); filter taps and the spatial table are
+ * small HOST arrays that travel with the launch.  width and height are at most MI_ICP_TSDF_MAX_IMAGE_SIDE (else
+ * MI_ICP_ERR_INVALID); a width or height of 0 launches nothing and is MI_ICP_OK.  Outputs are other buffers than inputs
+ * (else MI_ICP_ERR_INVALID) except where "in place" is said.  No call waits for the stream.  All arithmetic is fp32,
+ * unfused, in the order written (tests/image_exact.py restates it in numpy); clamp(v, hi) = min(max(0, v), hi).
+ *  filter  Image::FilterHorizontal / Image::Filter(dx, dy) on 1 x float32, nx and ny odd, at most
+ *   MI_ICP_IMAGE_MAX_TAPS (else MI_ICP_ERR_INVALID), hx = nx / 2, hy = ny / 2:
+ *     rowsum(y, x) = t, where t = 0 and then, for i = -hx .. hx, t = t + src[y][clamp(x + i, w - 1)] * dx[i + hx];
+ *     dy == NULL (ny = 0): out[y][x] = rowsum(y, x) -- FilterHorizontal;
+ *     else out[y][x] = o, where o = 0 and then, for j = -hy .. hy, o = o + rowsum(clamp(y + j, h - 1), x) * dy[j + hy]
+ *   -- the words of the reference's horizontal(dx), transpose, horizontal(dy), transpose, in ONE kernel with no
+ *   intermediate image.  The named filters: Gaussian3 {.25, .5, .25}, Gaussian5 {.0625, .25, .375, .25, .0625}, Gaussian7
+ *   {.03125, .109375, .21875, .28125, .21875, .109375, .03125} in both directions; Sobel3Dx dx = {-1, 0, 1}, dy =
+ *   {1, 2, 1}; Sobel3Dy the other way round.
+ *  downsample  Image::Downsample into (w / 2) x (h / 2): 1 x float32 (((p00 + p01) + p10) + p11) / 4.0f over the 2 x 2
+ *   block (p01 to the right, p10 below); 3 x uint8 per channel the integer (p00 + p01 + p10 + p11) / 4.  Other formats
+ *   MI_ICP_ERR_INVALID.
+ *  pyramid_level  one level of Image::CreatePyramid with the Gaussian, 1 x float32: the words of downsample(filter(
+ *   Gaussian3)), in one kernel that writes the quarter-size image only.
+ *  bilateral_table  (host arithmetic, no context) table[i] = (float)exp((double)(-(x * x) / (2 * sigma2))) for i = 0 ..
+ *   2 * diameter, x = (float)(i - diameter), sigma2 = sigma_space * sigma_space, the argument in fp32.
+ *  bilateral  Image::BilateralFilter on 1 x float32; `diameter` is a RADIUS in [0, MI_ICP_IMAGE_MAX_DIAMETER] (else
+ *   MI_ICP_ERR_INVALID), the window (2 diameter + 1)^2, table as above.  Per pixel: filtered = total = 0; for dy = -d ..
+ *   d, for dx = -d .. d: cur = src[clamp(y + dy, h - 1)][clamp(x + dx, w - 1)], c = center - cur, w = (table[dy + d] *
+ *   table[dx + d]) * exp(-(c * c) / ((2.0f * sigma_color) * sigma_color)), filtered = filtered + w * cur, total = total +
+ *   w; out = filtered / total.  The exponential is the device's (2^x in hardware of the argument times log2(e)), so this
+ *   one operation is not pinned to the bit: a result lies within (4 T + 64) 2^-24 M of the same sums carried in double,
+ *   T the number of taps, M the largest |value| in the window.  (The reference clamps to h and w, one past the end.)
+ *  create_float  Image::CreateFloatImage: the value of an element by bytes_per_channel (1 uint8, 2 uint16, 4 float, 3:
+ *   0.0f); one channel value * denom; three channels ((w0 * v0 + w1 * v1) + w2 * v2) * denom; any other channel count 0;
+ *   weights MI_ICP_IMAGE_EQUAL (float)(1.0 / 3.0) each, MI_ICP_IMAGE_WEIGHTED {0.2990f, 0.5870f, 0.1140f}; denom =
+ *   (float)(1.0 / 255.0) for one byte per channel, else 1.0f.
+ *  depth_to_float  Image::ConvertDepthToFloatImage: create_float (weighted), then f = f / (float)(int)depth_scale; if
+ *   (f >= (float)(int)depth_trunc) f = 0 -- the reference holds both as int.  |depth_scale|, |depth_trunc| < 2e9.
+ *  create_gray  Image::CreateGrayImage: the same sum with denom 1.0f (one byte per channel), (float)(255.0 / 65535.0)
+ *   (two), 255.0f (else), to uint8.
+ *  from_float  Image::CreateImageFromFloatImage: bytes_per_channel 1 (uint8)(f * 255.0f), 2 (uint16)f.
+ *  linear_transform  Image::LinearTransform in place: 1 x float32 scale * f + offset; uint8 (any channel count up to 4)
+ *   (uint8)(scale * (float)f + offset), every channel.
+ *  clip  Image::ClipIntensity in place, 1 x float32: fmaxf(fminf(max, f), min) (a NaN pixel becomes max).
+ *   Every float -> uint8 / uint16 conversion above truncates toward zero and SATURATES; NaN becomes 0.
+ *  move  Image::Transpose (dst is `height` wide and `width` high), FlipVertical, FlipHorizontal: whole pixels of
+ *   bytes_per_pixel bytes, 1 .. 16.
+ *  depth_format  uint16 to uint16: MI_ICP_IMAGE_SUN d = (d >> 3) | (d << 13); MI_ICP_IMAGE_NYU swap the two bytes, xx =
+ *   (float)(351.3 / (1092.5 - (double)d)), d = xx <= 0 ? 0 : (uint16)floor((double)xx * 1000 + 0.5), saturating.  src
+ *   may equal dst. */
+#define MI_ICP_IMAGE_MAX_TAPS 31
+#define MI_ICP_IMAGE_MAX_DIAMETER 31
+#define MI_ICP_IMAGE_EQUAL 0
+#define MI_ICP_IMAGE_WEIGHTED 1
+#define MI_ICP_IMAGE_TRANSPOSE 0
+#define MI_ICP_IMAGE_FLIP_VERTICAL 1
+#define MI_ICP_IMAGE_FLIP_HORIZONTAL 2
+#define MI_ICP_IMAGE_SUN 0
+#define MI_ICP_IMAGE_NYU 1
+MI_ICP_API int mi_icp_image_filter(mi_icp_ctx* ctx, const float* src, int width, int height, const float* dx, int nx,
+                                   const float* dy, int ny, float* dst);
+MI_ICP_API int mi_icp_image_downsample(mi_icp_ctx* ctx, const void* src, int width, int height, int channels,
+                                       int bytes_per_channel, void* dst);
+MI_ICP_API int mi_icp_image_pyramid_level(mi_icp_ctx* ctx, const float* src, int width, int height, float* dst);
+MI_ICP_API int mi_icp_image_bilateral_table(int diameter, float sigma_space, float* table);
+MI_ICP_API int mi_icp_image_bilateral(mi_icp_ctx* ctx, const float* src, int width, int height, int diameter,
+                                      float sigma_color, const float* table, float* dst);
+MI_ICP_API int mi_icp_image_create_float(mi_icp_ctx* ctx, const void* src, int width, int height, int channels,
+                                         int bytes_per_channel, int type, float* dst);
+MI_ICP_API int mi_icp_image_depth_to_float(mi_icp_ctx* ctx, const void* src, int width, int height, int channels,
+                                           int bytes_per_channel, float depth_scale, float depth_trunc, float* dst);
+MI_ICP_API int mi_icp_image_create_gray(mi_icp_ctx* ctx, const void* src, int width, int height, int channels,
+                                        int bytes_per_channel, int type, uint8_t* dst);
+MI_ICP_API int mi_icp_image_from_float(mi_icp_ctx* ctx, const float* src, int width, int height, int bytes_per_channel,
+                                       void* dst);
+MI_ICP_API int mi_icp_image_linear_transform(mi_icp_ctx* ctx, void* data, int width, int height, int channels,
+                                             int bytes_per_channel, float scale, float offset);
+MI_ICP_API int mi_icp_image_clip(mi_icp_ctx* ctx, float* data, int width, int height, float min_value, float max_value);
+MI_ICP_API int mi_icp_image_move(mi_icp_ctx* ctx, const void* src, int width, int height, int bytes_per_pixel, int op,
+                                 void* dst);
+MI_ICP_API int mi_icp_image_depth_format(mi_icp_ctx* ctx, const uint16_t* src, int width, int height, int format,
+                                         uint16_t* dst);
+/* the longest filter and the largest bilateral radius taken (no context, no device) */
+MI_ICP_API int mi_icp_image_limits(int32_t* max_taps, int32_t* max_diameter);
+
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
  * float[nq][3] against the cloud given to mi_icp_set_target: per query the knn

@@ -158,6 +158,11 @@ MI_ICP_API int mi_icp_debug_get_leaf_regions(mi_icp_ctx* ctx, float* regions_out
  * entries +inf / -1).  Every point of another leaf nearer to the region than reach k is in the lines 0 .. k.
  * Call mi_icp_debug_get_leaf_regions afterwards for the regions and reaches. */
 MI_ICP_API int mi_icp_debug_get_leaf_halos(mi_icp_ctx* ctx, float* halos_out);
+/* mi_icp_image_bilateral with the exponential named: exp_kind 1 the hardware 2^x of arg * log2(e) (what
+ * mi_icp_image_bilateral runs), 0 the library's expf.  For scripts/dev/image_rows.py, which times both, and for the
+ * test that holds both to the same bound. */
+MI_ICP_API int mi_icp_debug_image_bilateral(mi_icp_ctx* ctx, const float* src, int width, int height, int diameter,
+                                            float sigma_color, const float* table, float* dst, int exp_kind);
 #ifdef __cplusplus
 }
 #endif
