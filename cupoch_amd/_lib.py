@@ -18,7 +18,7 @@ INCLUDE = os.path.join(ROOT, "include")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I/opt/rocm/include"]
 # the library's translation units (csrc/ctx.h says what each holds); compiled side by side, then linked
-UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_occgrid", "mi_voxelgrid", "mi_collision", "mi_graph", "mi_laserscan", "mi_image", "mi_edt", "mi_knn", "mi_comm", "mi_debug"]
+UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_stsdf", "mi_occgrid", "mi_voxelgrid", "mi_collision", "mi_graph", "mi_laserscan", "mi_image", "mi_edt", "mi_knn", "mi_comm", "mi_debug"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 MI_ICP_HOST, MI_ICP_DEVICE = 0, 1
@@ -205,6 +205,14 @@ SIGNATURES = {
     "mi_icp_tsdf_extract_voxel_point_cloud": (_I, [_P, _P, _P, _P, _L, C.POINTER(_L), _I]),
     "mi_icp_tsdf_raycast": (_I, [_P, _P, _I, _I, _P, _P, _F, _I, _P, _P, _P, _L, C.POINTER(_L), _I]),
     "mi_icp_tsdf_get_voxels": (_I, [_P, _P, _P, _P, _P, _I]),
+    "mi_icp_stsdf_create": (_I, [_P, _F, _F, _I, _I, _I, C.POINTER(_P)]),
+    "mi_icp_stsdf_destroy": (_I, [_P, _P]),
+    "mi_icp_stsdf_reset": (_I, [_P, _P]),
+    "mi_icp_stsdf_integrate": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "mi_icp_stsdf_extract_point_cloud": (_I, [_P, _P, _P, _P, _P, _L, C.POINTER(_L)]),
+    "mi_icp_stsdf_extract_voxel_point_cloud": (_I, [_P, _P, _P, _P, _L, C.POINTER(_L)]),
+    "mi_icp_stsdf_get_units": (_I, [_P, _P, _P, _P, _P, _P, _L, C.POINTER(_L)]),
+    "mi_icp_stsdf_num_units": (_I, [_P, _P, C.POINTER(_L), C.POINTER(_L)]),
     "mi_icp_occgrid_create": (_I, [_P, _I, C.POINTER(_P)]),
     "mi_icp_occgrid_destroy": (_I, [_P, _P]),
     "mi_icp_occgrid_reset": (_I, [_P, _P]),

@@ -3,7 +3,8 @@
 // contract).  The voxels live in the engine's context as planes; GetVoxels() reads them back in the
 // reference's TSDFVoxel form instead of a public voxels_ vector.
 // Not built: ExtractTriangleMesh (no TriangleMesh type here), ExtractVoxelGrid,
-// ScalableTSDFVolume, IntegrateWithDepthToCameraDistanceMultiplier as a public entry.
+// IntegrateWithDepthToCameraDistanceMultiplier as a public entry.  ScalableTSDFVolume is in
+// cupoch/integration/scalable_tsdfvolume.h.
 #pragma once
 #include <vector>
 

@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <stdexcept>
 
@@ -2385,6 +2386,86 @@ std::vector<geometry::TSDFVoxel> UniformTSDFVolume::GetVoxels() const {
         out[i].tsdf_ = t[i];
         out[i].weight_ = w[i];
         if (colored) out[i].color_ = Eigen::Vector3f(c[i], c[n + i], c[2 * n + i]);
+    }
+    return out;
+}
+
+ScalableTSDFVolume::ScalableTSDFVolume(float voxel_length, float sdf_trunc, TSDFVolumeColorType color_type,
+                                       int depth_sampling_stride, int map_size)
+    : TSDFVolume(voxel_length, sdf_trunc, color_type),
+      volume_unit_length_(voxel_length * 16.0f),
+      resolution_(16),
+      volume_unit_voxel_num_(4096),
+      depth_sampling_stride_(depth_sampling_stride) {
+    Check(mi_icp_stsdf_create(Engine(), voxel_length, sdf_trunc, (int)color_type, depth_sampling_stride, map_size, &volume_));
+}
+
+ScalableTSDFVolume::~ScalableTSDFVolume() {
+    if (volume_) (void)mi_icp_stsdf_destroy(Engine(), volume_);
+}
+
+void ScalableTSDFVolume::Reset() { Check(mi_icp_stsdf_reset(Engine(), volume_)); }
+
+void ScalableTSDFVolume::Integrate(const geometry::RGBDImage& image, const camera::PinholeCameraIntrinsic& intrinsic,
+                                   const Eigen::Matrix4f& extrinsic) {
+    const geometry::Image &d = image.depth_, &c = image.color_;
+    const float k4[4] = {intrinsic.fx_, intrinsic.fy_, intrinsic.cx_, intrinsic.cy_};
+    const bool colored = color_type_ != TSDFVolumeColorType::NoColor;
+    const int rc = mi_icp_stsdf_integrate(Engine(), volume_, d.data_.empty() ? nullptr : d.data_.data(), d.width_, d.height_,
+                                          d.num_of_channels_, d.bytes_per_channel_,
+                                          (!colored || c.data_.empty()) ? nullptr : c.data_.data(), c.width_, c.height_,
+                                          c.num_of_channels_, c.bytes_per_channel_, intrinsic.width_, intrinsic.height_, k4,
+                                          extrinsic.data());
+    if (rc == MI_ICP_ERR_INVALID && std::strstr(mi_icp_last_error(Engine()), "Unsupported image format")) {
+        LogError("[ScalableTSDFVolume::Integrate] Unsupported image format.");  // scalable_tsdfvolume.cu:318-336
+        return;
+    }
+    Check(rc);
+}
+
+std::shared_ptr<geometry::PointCloud> ScalableTSDFVolume::ExtractPointCloud() {
+    mi_icp_stsdf* v = volume_;
+    return FillCloud(true, color_type_ != TSDFVolumeColorType::NoColor, kFirstCapacity, [v](float* p, float* n, float* c, int64_t cap, int64_t* m) {
+        return mi_icp_stsdf_extract_point_cloud(Engine(), v, p, n, c, cap, m);
+    });
+}
+
+std::shared_ptr<geometry::PointCloud> ScalableTSDFVolume::ExtractVoxelPointCloud() {
+    mi_icp_stsdf* v = volume_;
+    return FillCloud(false, true, kFirstCapacity, [v](float* p, float*, float* c, int64_t cap, int64_t* m) {
+        return mi_icp_stsdf_extract_voxel_point_cloud(Engine(), v, p, c, cap, m);
+    });
+}
+
+size_t ScalableTSDFVolume::NumVolumeUnits() const {
+    int64_t n = 0;
+    Check(mi_icp_stsdf_num_units(Engine(), volume_, &n, nullptr));
+    return (size_t)n;
+}
+
+std::vector<ScalableTSDFVolume::VolumeUnit> ScalableTSDFVolume::GetVolumeUnits() const {
+    const size_t units = NumVolumeUnits(), n = units * 4096;
+    const bool colored = color_type_ != TSDFVolumeColorType::NoColor;
+    std::vector<VolumeUnit> none;
+    if (units == 0) return none;
+    // the read-back fills device arrays: keys [units][3], then tsdf, weight and colour planes as floats
+    utility::device_vector<int32_t> dkeys(units * 3);
+    utility::device_vector<float> dt(n), dw(n), dc(colored ? 3 * n : 0);
+    int64_t m = 0;
+    Check(mi_icp_stsdf_get_units(Engine(), volume_, dkeys.data(), dt.data(), dw.data(), colored ? dc.data() : nullptr,
+                                 (int64_t)units, &m));
+    const std::vector<int32_t> keys = dkeys.to_host();
+    const std::vector<float> t = dt.to_host(), w = dw.to_host(), c = dc.to_host();
+    std::vector<VolumeUnit> out(units);
+    for (size_t e = 0; e < units; ++e) {
+        out[e].index_ = Eigen::Vector3i(keys[e * 3], keys[e * 3 + 1], keys[e * 3 + 2]);
+        out[e].voxels_.resize(4096);
+        for (size_t v = 0; v < 4096; ++v) {
+            const size_t i = e * 4096 + v;
+            out[e].voxels_[v].tsdf_ = t[i];
+            out[e].voxels_[v].weight_ = w[i];
+            if (colored) out[e].voxels_[v].color_ = Eigen::Vector3f(c[i], c[n + i], c[2 * n + i]);
+        }
     }
     return out;
 }

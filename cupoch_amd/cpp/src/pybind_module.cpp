@@ -39,6 +39,7 @@
 #include "cupoch/geometry/occupancygrid.h"
 #include "cupoch/geometry/pointcloud.h"
 #include "cupoch/geometry/voxelgrid.h"
+#include "cupoch/integration/scalable_tsdfvolume.h"
 #include "cupoch/integration/uniform_tsdfvolume.h"
 #include "cupoch/knn/kdtree_flann.h"
 #include "cupoch/knn/kdtree_search_param.h"
@@ -1376,7 +1377,8 @@ PYBIND11_MODULE(cupoch_pybind, m) {
 
     // ---------------------------------------------------------------- integration
     // cupoch_pybind/integration/integration.cpp: TSDFVolumeColorType and UniformTSDFVolume with the reference's names.
-    // Not bound, as not built: extract_triangle_mesh, extract_voxel_grid, ScalableTSDFVolume.
+    // Not bound, as not built: extract_triangle_mesh, extract_voxel_grid.  ScalableTSDFVolume is bound in the
+    // submodule integration_scalable below (this submodule's names are pinned by its surface test).
     py::module mi = m.def_submodule("integration");
     py::enum_<integration::TSDFVolumeColorType>(mi, "TSDFVolumeColorType", py::arithmetic())
             .value("NoColor", integration::TSDFVolumeColorType::NoColor)
@@ -1419,6 +1421,37 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             .def_readonly("length", &integration::UniformTSDFVolume::length_)
             .def_readonly("resolution", &integration::UniformTSDFVolume::resolution_)
             .def_property_readonly("origin", [](const integration::UniformTSDFVolume& v) { return from_vector3(v.origin_); });
+    // integration.cpp:153-195: the reference's constructor and __repr__; map_size (the C++ constructor's last argument)
+    // may be given by name.  The units are read back through the ctypes mirror (cupoch_amd.integration_scalable).
+    py::module mis = m.def_submodule("integration_scalable");
+    py::class_<integration::ScalableTSDFVolume, std::shared_ptr<integration::ScalableTSDFVolume>>(mis, "ScalableTSDFVolume")
+            .def(py::init([](float voxel_length, float sdf_trunc, integration::TSDFVolumeColorType color_type,
+                             int depth_sampling_stride, int map_size) {
+                     return std::make_shared<integration::ScalableTSDFVolume>(voxel_length, sdf_trunc, color_type,
+                                                                              depth_sampling_stride, map_size);
+                 }),
+                 "voxel_length"_a, "sdf_trunc"_a, "color_type"_a, "depth_sampling_stride"_a = 4, "map_size"_a = 1000)
+            .def("__repr__",
+                 [](const integration::ScalableTSDFVolume& v) {
+                     return std::string("pipelines::integration::ScalableTSDFVolume ") +
+                            (v.color_type_ == integration::TSDFVolumeColorType::NoColor ? "without color." : "with color.");
+                 })
+            .def("reset", &integration::ScalableTSDFVolume::Reset)
+            .def("integrate",
+                 [](integration::ScalableTSDFVolume& v, const geometry::RGBDImage& image,
+                    const camera::PinholeCameraIntrinsic& intrinsic,
+                    const farray& extrinsic) { v.Integrate(image, intrinsic, to_matrix4(extrinsic)); },
+                 "image"_a, "intrinsic"_a, "extrinsic"_a)
+            .def("extract_point_cloud", &integration::ScalableTSDFVolume::ExtractPointCloud)
+            .def("extract_voxel_point_cloud", &integration::ScalableTSDFVolume::ExtractVoxelPointCloud)
+            .def("num_volume_units", &integration::ScalableTSDFVolume::NumVolumeUnits)
+            .def_readonly("voxel_length", &integration::ScalableTSDFVolume::voxel_length_)
+            .def_readonly("sdf_trunc", &integration::ScalableTSDFVolume::sdf_trunc_)
+            .def_readonly("color_type", &integration::ScalableTSDFVolume::color_type_)
+            .def_readonly("volume_unit_length", &integration::ScalableTSDFVolume::volume_unit_length_)
+            .def_readonly("resolution", &integration::ScalableTSDFVolume::resolution_)
+            .def_readonly("volume_unit_voxel_num", &integration::ScalableTSDFVolume::volume_unit_voxel_num_)
+            .def_readonly("depth_sampling_stride", &integration::ScalableTSDFVolume::depth_sampling_stride_);
 
 
     // ---------------------------------------------------------------- registration

@@ -7,6 +7,7 @@
 //   mi_voxel.hip     VoxelDownSample (the dense-grid path and the general one)
 //   mi_rgbd.hip      depth / RGB-D frame -> cloud, RGB-D odometry
 //   mi_tsdf.hip      UniformTSDFVolume
+//   mi_stsdf.hip     ScalableTSDFVolume
 //   mi_occgrid.hip   OccupancyGrid
 //   mi_edt.hip       DistanceTransform
 //   mi_voxelgrid.hip VoxelGrid (from points, dense, merge, carve, query, bounds, selections, paint)
@@ -170,6 +171,8 @@ struct mi_icp_ctx {
 
     // ---- integration::UniformTSDFVolume: the volumes this context made (mi_tsdf.hip), freed with it ----
     std::vector<mi_icp_tsdf*> tsdf_volumes;
+    // ---- integration::ScalableTSDFVolume: likewise (mi_stsdf.hip) ----
+    std::vector<mi_icp_stsdf*> stsdf_volumes;
     // ---- geometry::OccupancyGrid: the grids this context made (mi_occgrid.hip), freed with it ----
     std::vector<mi_icp_occgrid*> occ_grids;
     // ---- geometry::DistanceTransform: the transforms this context made (mi_edt.hip), freed with it ----
@@ -524,8 +527,12 @@ bool planes_available(const mi_icp_ctx* c);
 int launch_locate_by_planes(mi_icp_ctx* c, const Xform& X, const DevLoop* loop, int gated);
 // ---- mi_voxel.hip
 int occupancy_geometry(int which);
+// ---- mi_rgbd.hip
+bool invert4(const float* M, float* out);  // column-major 4x4 inverse (false: singular); the pose of CreateFromDepthImage
 // ---- mi_tsdf.hip
 void tsdf_release_all(mi_icp_ctx* c);     // mi_icp_destroy: the volumes of mi_icp_tsdf_create
+// ---- mi_stsdf.hip
+void stsdf_release_all(mi_icp_ctx* c);    // mi_icp_destroy: the volumes of mi_icp_stsdf_create
 // ---- mi_occgrid.hip
 void occgrid_release_all(mi_icp_ctx* c);  // mi_icp_destroy: the grids of mi_icp_occgrid_create
 // a grid's log-odds plane, resolution and inclusive bounds (min[3], max[3]) for a reader on the device

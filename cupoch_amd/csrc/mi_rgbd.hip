@@ -8,11 +8,10 @@ using namespace mi;
 using namespace mi::eng;
 using host::Mat4;
 
-extern "C" {
-
-// ---------------------------------------------------------------------------
-// PointCloud::CreateFromDepthImage / CreateFromRGBDImage (geometry/pointcloud_factory.cu)
-static bool invert4(const float* M, float* out) {  // column-major general inverse, in double
+namespace mi {
+namespace eng {
+// column-major general inverse, in double (the camera pose of an extrinsic)
+bool invert4(const float* M, float* out) {
     double a[4][8];
     for (int r = 0; r < 4; ++r)
         for (int k = 0; k < 4; ++k) {
@@ -39,7 +38,13 @@ static bool invert4(const float* M, float* out) {  // column-major general inver
         for (int k = 0; k < 4; ++k) out[k * 4 + r] = (float)a[r][4 + k];
     return true;
 }
+}  // namespace eng
+}  // namespace mi
 
+extern "C" {
+
+// ---------------------------------------------------------------------------
+// PointCloud::CreateFromDepthImage / CreateFromRGBDImage (geometry/pointcloud_factory.cu)
 int mi_icp_create_from_depth(mi_icp_ctx* c, const void* depth, int depth_type, const void* color, int color_type,
                              int width, int height, const float* intrinsic4, const float* extrinsic,
                              float depth_scale, float depth_trunc, float depth_cutoff, int stride, int rgbd,

@@ -741,6 +741,91 @@ class Engine:
         self._chk(self._L.mi_icp_tsdf_get_voxels(self._ctx, vol, tp, wp, cp, kind))
         return t, w, (None if c is None else (c.T.contiguous() if on_device else np.ascontiguousarray(c.T)))
 
+    # -- integration::ScalableTSDFVolume (include/mi_icp.h) ---------------------------------------------
+    def stsdf_create(self, voxel_length, sdf_trunc, color_type, depth_sampling_stride=4, map_size=1000):
+        """-> an opaque volume handle of this engine (mi_icp_stsdf_create)"""
+        h = C.c_void_p()
+        self._chk(self._L.mi_icp_stsdf_create(self._ctx, float(voxel_length), float(sdf_trunc), int(color_type),
+                                              int(depth_sampling_stride), int(map_size), C.byref(h)))
+        return h
+
+    def stsdf_destroy(self, vol):
+        if getattr(self, "_ctx", None) and vol:
+            self._chk(self._L.mi_icp_stsdf_destroy(self._ctx, vol))
+
+    def stsdf_reset(self, vol):
+        self._chk(self._L.mi_icp_stsdf_reset(self._ctx, vol))
+
+    def stsdf_num_units(self, vol):
+        """-> (open units, unit slots)"""
+        n, cap = C.c_int64(0), C.c_int64(0)
+        self._chk(self._L.mi_icp_stsdf_num_units(self._ctx, vol, C.byref(n), C.byref(cap)))
+        return int(n.value), int(cap.value)
+
+    def stsdf_integrate(self, vol, depth, color, width, height, intrinsic4, extrinsic=None):
+        """ScalableTSDFVolume::Integrate; depth / color numpy or torch, both on the same side.  The C ABI of this family
+        reads device memory only: host images are uploaded here, and the call waits before they are let go.  A format
+        the reference turns away raises MiIcpError."""
+        bad = "[ScalableTSDFVolume::Integrate] Unsupported image format."
+        try:
+            d, _, _, _, _, _, d_dev = self._image_desc(depth)
+            col, _, _, _, _, _, c_dev = self._image_desc(color)
+        except MiIcpError:
+            raise MiIcpError(bad)
+        if d is None:
+            raise MiIcpError(bad)
+        if col is not None and c_dev != d_dev:
+            raise MiIcpError("depth and color must live on the same side")
+        if d_dev:   # a float image must be float: the C ABI sees bytes per channel only
+            ok = d.dtype == torch.float32 and (col is None or col.dtype in (torch.float32, torch.uint8))
+        else:
+            ok = d.dtype == np.float32 and (col is None or col.dtype in (np.float32, np.uint8))
+        if not ok:
+            raise MiIcpError(bad)
+        if not d_dev:
+            dev = torch.device("cuda", self.device)
+            d = torch.from_numpy(d).to(dev)
+            col = None if col is None else torch.from_numpy(col).to(dev)
+            torch.cuda.synchronize(dev)
+        d, dptr, dw, dh, dc, db, _ = self._image_desc(d)
+        col, cptr, cw, ch, cc, cb, _ = self._image_desc(col)
+        K = (C.c_float * 4)(*[float(v) for v in intrinsic4])
+        _, Eptr = _T_in(extrinsic)
+        self._chk(self._L.mi_icp_stsdf_integrate(self._ctx, vol, dptr, dw, dh, dc, db, cptr, cw, ch, cc, cb, int(width),
+                                                 int(height), K, Eptr))
+        if not d_dev:
+            self.synchronize()
+
+    def _stsdf_cloud(self, call, want, on_device):
+        """the capacity rule on device arrays; on_device False: the result as numpy arrays"""
+        out = self._tsdf_cloud(lambda p, cap, m, kind: call(p, cap, m), want, self.TSDF_FIRST_CAPACITY, self._tsdf_device(True))
+        return out if on_device else [None if a is None else a.cpu().numpy() for a in out]
+
+    def stsdf_extract_point_cloud(self, vol, colored, on_device=True):
+        """-> (points, normals, colors or None)"""
+        return self._stsdf_cloud(lambda p, cap, m: self._L.mi_icp_stsdf_extract_point_cloud(
+            self._ctx, vol, p[0], p[1], p[2], cap, m), [True, True, bool(colored)], on_device)
+
+    def stsdf_extract_voxel_point_cloud(self, vol, on_device=True):
+        """-> (points, colors)"""
+        return self._stsdf_cloud(lambda p, cap, m: self._L.mi_icp_stsdf_extract_voxel_point_cloud(
+            self._ctx, vol, p[0], p[1], cap, m), [True, True], on_device)
+
+    def stsdf_get_units(self, vol, colored, on_device=False):
+        """-> (keys[m, 3] int32 ascending, tsdf[m, 4096], weight[m, 4096], color[m, 4096, 3] or None)"""
+        dev = self._tsdf_device(True)
+        n = self.stsdf_num_units(vol)[0]
+        (k, kp) = self._out(MI_ICP_DEVICE, dev, (n, 3), np.int32)
+        (t, tp), (w, wp) = self._out(MI_ICP_DEVICE, dev, (n, 4096)), self._out(MI_ICP_DEVICE, dev, (n, 4096))
+        c, cp = self._out(MI_ICP_DEVICE, dev, (3, n, 4096)) if colored else (None, None)
+        m = C.c_int64(0)
+        self._chk(self._L.mi_icp_stsdf_get_units(self._ctx, vol, kp, tp, wp, cp, n, C.byref(m)))
+        assert int(m.value) == n
+        if c is not None:
+            c = c.permute(1, 2, 0).contiguous()
+        out = (k, t, w, c)
+        return out if on_device else tuple(None if a is None else a.cpu().numpy() for a in out)
+
     # -- geometry::OccupancyGrid (include/mi_icp.h; arrays are device tensors, numpy inputs are uploaded) ----------
     @staticmethod
     def occgrid_params(voxel_size, origin, clamping_thres_min, clamping_thres_max, prob_hit_log, prob_miss_log,

@@ -1,8 +1,9 @@
 """cupoch.integration mirror (src/cupoch/integration/tsdfvolume.h, uniform_tsdfvolume.h; python surface
 src/python/cupoch_pybind/integration/integration.cpp): TSDFVolumeColorType and UniformTSDFVolume.  The volume lives
 on the GPU, owned by the process-wide engine of its device; every operation runs HIP kernels through the C ABI
-(include/mi_icp.h has the numeric contract).  Not built: extract_triangle_mesh (no TriangleMesh type here),
-extract_voxel_grid, ScalableTSDFVolume, integrate_with_depth_to_camera_distance_multiplier."""
+(include/mi_icp.h has the numeric contract).  ScalableTSDFVolume is in cupoch_amd.integration_scalable (this module's
+names are pinned by its surface test).  Not built: extract_triangle_mesh (no TriangleMesh type here),
+extract_voxel_grid, integrate_with_depth_to_camera_distance_multiplier."""
 import enum
 
 import numpy as np

@@ -34,4 +34,5 @@ def _load():
 _m = _load()
 utility, geometry, registration = _m.utility, _m.geometry, _m.registration
 camera, integration, collision, planning = _m.camera, _m.integration, _m.collision, _m.planning
+integration_scalable = _m.integration_scalable
 initialize_allocator = _m.initialize_allocator

@@ -656,7 +656,7 @@ MI_ICP_API int mi_icp_gaussian_filter(mi_icp_ctx* ctx, const float* xyz, const f
  * mi_icp_destroy frees the volumes still alive, and a volume is only accepted by its own context.
  * Stored as planes (tsdf, weight, and three colour planes only when color_type != NO_COLOR): 8 or 20
  * bytes per voxel.  Not built: ExtractTriangleMesh (there is no TriangleMesh type here), ExtractVoxelGrid,
- * ScalableTSDFVolume, IntegrateWithDepthToCameraDistanceMultiplier as an entry.
+ * IntegrateWithDepthToCameraDistanceMultiplier as an entry.  ScalableTSDFVolume is the next section.
  *
  * THE NUMERIC CONTRACT.  Everything is fp32, products and sums unfused, division and square root
  * correctly rounded, in the order written; three-term sums and dot products run left to right,
@@ -784,6 +784,98 @@ MI_ICP_API int mi_icp_tsdf_raycast(mi_icp_ctx* ctx, mi_icp_tsdf* volume, int wid
                                    int64_t capacity, int64_t* m, int mem_kind);
 MI_ICP_API int mi_icp_tsdf_get_voxels(mi_icp_ctx* ctx, mi_icp_tsdf* volume, float* tsdf_out, float* weight_out,
                                       float* color_out, int mem_kind);
+
+/* ---- integration::ScalableTSDFVolume (integration/scalable_tsdfvolume.{h,cu}, integrate_functor.h:84-139;
+ * python surface integration.cpp:153-195) ----------------------------------------------------------
+ * A sparse volume: units of 16^3 voxels of edge voxel_length, opened around the surface a frame observes.
+ * Unit (kx, ky, kz) -- three signed indices, each within +-(2^20 - 1) -- spans [k*L, (k+1)*L) per axis,
+ * L = voxel_length * 16.0f (one fp32 product).  A voxel of a unit has index x*256 + y*16 + z and holds
+ * (tsdf, weight, colour[3]).  Stored as planes over a pool of unit slots (tsdf, weight, and three colour
+ * planes only when color_type != NO_COLOR: 8 or 20 bytes per voxel), slot s at [s*4096, (s+1)*4096) of
+ * each plane, beside a directory: the open units' keys in ascending (kx, ky, kz) order with their slots,
+ * looked up by binary search.  The volume belongs to the context that made it, as a uniform one does.
+ * ARRAYS ARE DEVICE POINTERS; there is no memory-kind argument in this family (as for the occupancy grid):
+ * the images and every output live on the device, a caller with host arrays copies them itself.
+ * Not built: ExtractTriangleMesh (the reference's own only logs an error), a raycast (the reference has
+ * none), IntegrateWithDepthToCameraDistanceMultiplier as an entry.
+ *
+ * THE NUMERIC CONTRACT, in the terms of the uniform volume's above (fp32, unfused, in the order written;
+ * half = 0.5f * voxel_length; floor -> int as there).  tests/scalable_tsdf_exact.py restates it.
+ *  Open       For each sampled pixel (row = i*stride, col = j*stride, i < height/stride, j < width/stride,
+ *             integer divisions) with !(d <= 0): the world point p of mi_icp_create_from_depth(rgbd = 0,
+ *             depth_scale 1000, depth_trunc 1000, stride), bit for bit: x = ((float)col - cx)*d / fx,
+ *             y = ((float)row - cy)*d / fy, p[r] = ((pose[r][0]*x + pose[r][1]*y) + pose[r][2]*d) + pose[r][3],
+ *             pose = the extrinsic's inverse computed in double and rounded to float.  A point with a
+ *             non-finite coordinate opens nothing.  Else every unit k with
+ *               floorf((p[a] - sdf_trunc) / L) <= k[a] <= floorf((p[a] + sdf_trunc) / L)   on each axis a
+ *             that is not open is opened: reset to tsdf 0, weight 0, colour (1, 1, 1).  Keys outside
+ *             +-(2^20 - 1) are not opened.  (The reference tests idx > n and reads one point past the end;
+ *             here idx >= n.)  A frame's new keys get the slots after those in use, in ascending key
+ *             order: nothing depends on thread timing.
+ *  Integrate  then every voxel (x, y, z) of every open unit gets the uniform volume's Integrate lines with
+ *             xr, yr, zr = x, y, z (h = 0) and origin[a] = (float)k[a] * L; the multiplier image is the same.
+ *             A voxel that is skipped is neither read nor written.
+ *  valid      as above.  A voxel in a unit that is not open counts as weight 0 (invalid), tsdf 0.
+ *  Order of both extractions (ours; the reference's is its hash map's): units in ascending (kx, ky, kz),
+ *             within a unit ascending voxel index, then the axis.
+ *  ExtractVoxelPointCloud   the valid voxels: point (half + voxel_length*x) + (float)k[0]*L, ...; colour
+ *             (c, c, c), c = (float)(((double)tsdf + 1.0) * 0.5).  (Declared and never defined in the
+ *             reference: the uniform volume's rule.)
+ *  ExtractPointCloud   for a valid voxel 0 = (x, y, z) of unit k and each axis: voxel 1 = the voxel at +1
+ *             along the axis -- in the same unit, or at coordinate 0 of unit k + e_axis --, valid, f0*f1 < 0.
+ *             Then r0 = |f0|, r1 = |f1|,
+ *               p0[a] = (half + voxel_length*(float)x_a) + (float)k[a]*L;  p = p0
+ *               p[axis] = (p0[axis]*r1 + (p0[axis] + voxel_length)*r0) / (r0 + r1)     -- the point
+ *               colour = (c0*r1 + c1*r0) / (r0 + r1), for RGB8 then / 255.0f; none for NO_COLOR (the
+ *               reference returns NaN colours there)
+ *               normal: gap = (float)(0.99 * (double)voxel_length) (a float, unlike the uniform volume's);
+ *               n[a] = T(p with p[a] := p[a] + gap) - T(p with p[a] := p[a] - gap); zz = (n0*n0 + n1*n1) +
+ *               n2*n2; n / sqrtf(zz) when zz > 0, else n as it is.
+ *               T(p) (GetTSDFAt): q[a] = p[a] - half; u[a] = floorf(q[a] / L); 0 when unit u is not open;
+ *               g[a] = (q[a] - (float)u[a]*L) / voxel_length; i[a] = floor(g[a]) held inside [0, 15];
+ *               r[a] = g[a] - (float)i[a]; f(dx, dy, dz) = the tsdf of voxel i + (dx, dy, dz) of unit u,
+ *               a coordinate of 16 being coordinate 0 of the next unit along that axis, 0 where that unit
+ *               is not open;
+ *               T = (1-r0)*((1-r1)*((1-r2)*f(0,0,0) + r2*f(0,0,1)) + r1*((1-r2)*f(0,1,0) + r2*f(0,1,1)))
+ *                 + r0*((1-r1)*((1-r2)*f(1,0,0) + r2*f(1,0,1)) + r1*((1-r2)*f(1,1,0) + r2*f(1,1,1)))
+ *  Reset      closes every unit; the capacity stays.
+ *  Deviations (deliberate): capacity.  map_size is the initial number of unit slots; a frame that needs
+ *  more makes the pool and the directory grow by doubling before anything of the frame is integrated (the
+ *  reference's map has a fixed capacity and silently drops units, which ones depending on a race).  When
+ *  that allocation fails the call is MI_ICP_ERR_HIP and the volume is as it was before the frame.
+ *  Outputs hold the actual count (the capacity / *m rule above).
+ *
+ * mi_icp_stsdf_create turns away (MI_ICP_ERR_INVALID): voxel_length or sdf_trunc not positive and finite,
+ * sdf_trunc > L (so a point opens at most 4 units per axis), depth_sampling_stride < 1, map_size < 1 or
+ * above MI_ICP_STSDF_MAX_UNITS, an unknown colour type.
+ * mi_icp_stsdf_integrate: the images described as for mi_icp_tsdf_integrate, checked as scalable_tsdfvolume.cu:318-336
+ * does; otherwise MI_ICP_ERR_INVALID ("[ScalableTSDFVolume::Integrate] Unsupported image format."), the
+ * volume untouched.  A singular extrinsic is MI_ICP_ERR_INVALID.  The call waits for the stream once in
+ * every frame (the number of candidate keys: zero ends stage 1) and once more in a frame that opens units
+ * (their number, which growth needs); the integrate launch itself is not waited for.
+ * mi_icp_stsdf_get_units: the open units in ascending key order, under the capacity rule with capacity
+ * and *m in units: keys_out[m][3], tsdf_out / weight_out [m][4096], color_out[3][m][4096] (planes;
+ * NO_COLOR volumes have none: pass NULL); each may be NULL.
+ * mi_icp_stsdf_num_units: the number of open units and of slots (either may be NULL); does not wait. */
+#define MI_ICP_STSDF_MAX_UNITS 262144
+typedef struct mi_icp_stsdf mi_icp_stsdf;
+MI_ICP_API int mi_icp_stsdf_create(mi_icp_ctx* ctx, float voxel_length, float sdf_trunc, int color_type,
+                                   int depth_sampling_stride, int map_size, mi_icp_stsdf** out);
+MI_ICP_API int mi_icp_stsdf_destroy(mi_icp_ctx* ctx, mi_icp_stsdf* volume);
+MI_ICP_API int mi_icp_stsdf_reset(mi_icp_ctx* ctx, mi_icp_stsdf* volume);
+MI_ICP_API int mi_icp_stsdf_integrate(mi_icp_ctx* ctx, mi_icp_stsdf* volume, const void* depth, int depth_width,
+                                      int depth_height, int depth_channels, int depth_bytes_per_channel,
+                                      const void* color, int color_width, int color_height, int color_channels,
+                                      int color_bytes_per_channel, int width, int height, const float* intrinsic4,
+                                      const float* extrinsic);
+MI_ICP_API int mi_icp_stsdf_extract_point_cloud(mi_icp_ctx* ctx, mi_icp_stsdf* volume, float* out_xyz,
+                                                float* out_normals, float* out_colors, int64_t capacity,
+                                                int64_t* m);
+MI_ICP_API int mi_icp_stsdf_extract_voxel_point_cloud(mi_icp_ctx* ctx, mi_icp_stsdf* volume, float* out_xyz,
+                                                      float* out_colors, int64_t capacity, int64_t* m);
+MI_ICP_API int mi_icp_stsdf_get_units(mi_icp_ctx* ctx, mi_icp_stsdf* volume, int32_t* keys_out, float* tsdf_out,
+                                      float* weight_out, float* color_out, int64_t capacity, int64_t* m);
+MI_ICP_API int mi_icp_stsdf_num_units(mi_icp_ctx* ctx, mi_icp_stsdf* volume, int64_t* n_units, int64_t* capacity);
 
 /* ---- geometry::OccupancyGrid (geometry/occupancygrid.{h,cu}, densegrid.inl; the cloud of
  * geometry/pointcloud_factory.cu:418-430) ---------------------------------------------------------

@@ -3,7 +3,7 @@ counts, per kernel, the global loads that are followed at once by `s_waitcnt vmc
 (`if (i < n) x = p[i]`) or behind a possibly-aliasing store compiles to.  CPU only (hipcc cross-compiles)."""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-units = sys.argv[1:] or ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_knn"]
+units = sys.argv[1:] or ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_stsdf", "mi_knn"]
 seen = set()
 for u in units:
     out = os.path.join(tempfile.gettempdir(), u + ".s")
