@@ -2307,16 +2307,26 @@ UniformTSDFVolume::~UniformTSDFVolume() {
 
 void UniformTSDFVolume::Reset() { Check(mi_icp_tsdf_reset(Engine(), volume_)); }
 
-void UniformTSDFVolume::Integrate(const geometry::RGBDImage& image, const camera::PinholeCameraIntrinsic& intrinsic,
-                                  const Eigen::Matrix4f& extrinsic) {
+namespace {
+// mi_icp_tsdf_integrate or mi_icp_stsdf_integrate (`tail`: what the one takes after the extrinsic) on an RGBDImage and
+// an intrinsic, described as the C ABI takes them; no colour image goes to a volume without colour
+template <class Vol, class... Tail>
+int IntegrateFrame(int (*integrate)(mi_icp_ctx*, Vol*, const void*, int, int, int, int, const void*, int, int, int, int, int, int,
+                                    const float*, const float*, Tail...),
+                   Vol* volume, const geometry::RGBDImage& image, const camera::PinholeCameraIntrinsic& intrinsic,
+                   const Eigen::Matrix4f& extrinsic, TSDFVolumeColorType color_type, Tail... tail) {
     const geometry::Image &d = image.depth_, &c = image.color_;
     const float k4[4] = {intrinsic.fx_, intrinsic.fy_, intrinsic.cx_, intrinsic.cy_};
-    const bool colored = color_type_ != TSDFVolumeColorType::NoColor;
-    const int rc = mi_icp_tsdf_integrate(Engine(), volume_, d.data_.empty() ? nullptr : d.data_.data(), d.width_, d.height_,
-                                         d.num_of_channels_, d.bytes_per_channel_,
-                                         (!colored || c.data_.empty()) ? nullptr : c.data_.data(), c.width_, c.height_,
-                                         c.num_of_channels_, c.bytes_per_channel_, intrinsic.width_, intrinsic.height_, k4,
-                                         extrinsic.data(), MI_ICP_DEVICE);
+    const bool colored = color_type != TSDFVolumeColorType::NoColor;
+    return integrate(Engine(), volume, d.data_.empty() ? nullptr : d.data_.data(), d.width_, d.height_, d.num_of_channels_,
+                     d.bytes_per_channel_, (!colored || c.data_.empty()) ? nullptr : c.data_.data(), c.width_, c.height_,
+                     c.num_of_channels_, c.bytes_per_channel_, intrinsic.width_, intrinsic.height_, k4, extrinsic.data(), tail...);
+}
+}  // namespace
+
+void UniformTSDFVolume::Integrate(const geometry::RGBDImage& image, const camera::PinholeCameraIntrinsic& intrinsic,
+                                  const Eigen::Matrix4f& extrinsic) {
+    const int rc = IntegrateFrame(mi_icp_tsdf_integrate, volume_, image, intrinsic, extrinsic, color_type_, (int)MI_ICP_DEVICE);
     if (rc == MI_ICP_ERR_INVALID) {  // uniform_tsdfvolume.cu:677-695
         LogError("[UniformTSDFVolume::Integrate] Unsupported image format.");
         return;
@@ -2408,14 +2418,7 @@ void ScalableTSDFVolume::Reset() { Check(mi_icp_stsdf_reset(Engine(), volume_));
 
 void ScalableTSDFVolume::Integrate(const geometry::RGBDImage& image, const camera::PinholeCameraIntrinsic& intrinsic,
                                    const Eigen::Matrix4f& extrinsic) {
-    const geometry::Image &d = image.depth_, &c = image.color_;
-    const float k4[4] = {intrinsic.fx_, intrinsic.fy_, intrinsic.cx_, intrinsic.cy_};
-    const bool colored = color_type_ != TSDFVolumeColorType::NoColor;
-    const int rc = mi_icp_stsdf_integrate(Engine(), volume_, d.data_.empty() ? nullptr : d.data_.data(), d.width_, d.height_,
-                                          d.num_of_channels_, d.bytes_per_channel_,
-                                          (!colored || c.data_.empty()) ? nullptr : c.data_.data(), c.width_, c.height_,
-                                          c.num_of_channels_, c.bytes_per_channel_, intrinsic.width_, intrinsic.height_, k4,
-                                          extrinsic.data());
+    const int rc = IntegrateFrame(mi_icp_stsdf_integrate, volume_, image, intrinsic, extrinsic, color_type_);
     if (rc == MI_ICP_ERR_INVALID && std::strstr(mi_icp_last_error(Engine()), "Unsupported image format")) {
         LogError("[ScalableTSDFVolume::Integrate] Unsupported image format.");  // scalable_tsdfvolume.cu:318-336
         return;

@@ -7,7 +7,7 @@
 //   mi_voxel.hip     VoxelDownSample (the dense-grid path and the general one)
 //   mi_rgbd.hip      depth / RGB-D frame -> cloud, RGB-D odometry
 //   mi_tsdf.hip      UniformTSDFVolume
-//   mi_stsdf.hip     ScalableTSDFVolume
+//   mi_stsdf.hip     ScalableTSDFVolume (tsdf_host.h: the host side the two volumes' units share)
 //   mi_occgrid.hip   OccupancyGrid
 //   mi_edt.hip       DistanceTransform
 //   mi_voxelgrid.hip VoxelGrid (from points, dense, merge, carve, query, bounds, selections, paint)
@@ -384,6 +384,13 @@ inline int check_ctx(mi_icp_ctx* c, int mem_kind, const char* what) {
     TRY(check_ctx(c));
     if (mem_kind != MI_ICP_HOST && mem_kind != MI_ICP_DEVICE) return fail(c, MI_ICP_ERR_INVALID, "%s: bad mem_kind", what);
     return MI_ICP_OK;
+}
+
+// Is the handle `h` (a volume, a grid, a transform) one that context c made and still holds in `list`?  The caller has
+// the message for a handle that is not.
+template <class T>
+bool owned(const mi_icp_ctx* c, const T* h, const std::vector<T*>& list) {
+    return h && h->owner == c && std::find(list.begin(), list.end(), h) != list.end();
 }
 
 // ---- What the cloud-in, cloud-out entry points share.  A cloud is three arrays: points, normals, colours (the last two

@@ -38,7 +38,7 @@ void dt_release_all(mi_icp_ctx* c) {
 }  // namespace mi
 
 static int dt_check(mi_icp_ctx* c, const mi_icp_dt* d, const char* what) {
-    if (!d || d->owner != c || std::find(c->dts.begin(), c->dts.end(), d) == c->dts.end())
+    if (!owned(c, d, c->dts))
         return fail(c, MI_ICP_ERR_INVALID, "%s: not a distance transform of this context", what);
     return MI_ICP_OK;
 }

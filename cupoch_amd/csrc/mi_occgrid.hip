@@ -36,9 +36,13 @@ void occgrid_release_all(mi_icp_ctx* c) {
     c->occ_grids.clear();
 }
 
+static int occ_check(mi_icp_ctx* c, const mi_icp_occgrid* o, const char* what) {
+    if (!owned(c, o, c->occ_grids)) return fail(c, MI_ICP_ERR_INVALID, "%s: not a grid of this context", what);
+    return MI_ICP_OK;
+}
+
 int occgrid_view(mi_icp_ctx* c, const mi_icp_occgrid* o, const char* what, const float** prob, int* resolution, int* bounds6) {
-    if (!o || o->owner != c || std::find(c->occ_grids.begin(), c->occ_grids.end(), o) == c->occ_grids.end())
-        return fail(c, MI_ICP_ERR_INVALID, "%s: not a grid of this context", what);
+    TRY(occ_check(c, o, what));
     *prob = o->g.prob;
     *resolution = o->g.res;
     for (int k = 0; k < 6; ++k) bounds6[k] = o->bounds[k];
@@ -46,12 +50,6 @@ int occgrid_view(mi_icp_ctx* c, const mi_icp_occgrid* o, const char* what, const
 }
 }  // namespace eng
 }  // namespace mi
-
-static int occ_check(mi_icp_ctx* c, const mi_icp_occgrid* o, const char* what) {
-    if (!o || o->owner != c || std::find(c->occ_grids.begin(), c->occ_grids.end(), o) == c->occ_grids.end())
-        return fail(c, MI_ICP_ERR_INVALID, "%s: not a grid of this context", what);
-    return MI_ICP_OK;
-}
 
 static bool finite3(const float* v) { return v && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 

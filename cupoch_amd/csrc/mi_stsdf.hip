@@ -2,6 +2,7 @@
 // (one translation unit of libmi_icp.so; csrc/ctx.h lists them)
 #include "ctx.h"
 #include "scalable_tsdf_kernels.h"
+#include "tsdf_host.h"
 
 using namespace mi;
 using namespace mi::eng;
@@ -20,19 +21,18 @@ struct mi_icp_stsdf {
     int cur = 0;                        // which of the two holds it
     DevBuf fresh;   // a frame's new keys
     DevBuf edges;   // ExtractPointCloud's list of crossing edges
-    DevBuf mult;    // the depth -> camera-distance multiplier image of the intrinsic below
-    int mult_w = 0, mult_h = 0;
-    float mult_k[4] = {0, 0, 0, 0};
+    TsdfMult mult;
 };
 
 static int stsdf_planes_of(int color_type) { return color_type == MI_ICP_TSDF_NO_COLOR ? 2 : 5; }
 
 static void stsdf_point_planes(mi_icp_stsdf* t, void* planes, int capacity) {
     float* base = (float*)planes;
-    t->v.plane = (int64_t)capacity * kStsdfUnit;
-    t->v.tsdf = base;
-    t->v.weight = base + t->v.plane;
-    t->v.color = t->v.color_type == MI_ICP_TSDF_NO_COLOR ? nullptr : base + 2 * t->v.plane;
+    TsdfPlanes& p = t->v.p;
+    p.stride = (int64_t)capacity * kStsdfUnit;
+    p.tsdf = base;
+    p.weight = base + p.stride;
+    p.color = p.color_type == MI_ICP_TSDF_NO_COLOR ? nullptr : base + 2 * p.stride;
 }
 
 static uint64_t* dir_keys(void* d) { return (uint64_t*)d; }
@@ -52,7 +52,7 @@ static void stsdf_free(mi_icp_stsdf* t) {
         if (t->dir[k]) (void)hipFree(t->dir[k]);
     release(t->fresh);
     release(t->edges);
-    release(t->mult);
+    release(t->mult.buf);
     delete t;
 }
 
@@ -60,7 +60,7 @@ static void stsdf_free(mi_icp_stsdf* t) {
 // allocated and the volume moves, or nothing changes and the call reports MI_ICP_ERR_HIP.
 static int stsdf_reserve(mi_icp_ctx* c, mi_icp_stsdf* t, int capacity) {
     void *planes = nullptr, *d0 = nullptr, *d1 = nullptr;
-    const int np = stsdf_planes_of(t->v.color_type);
+    const int np = stsdf_planes_of(t->v.p.color_type);
     const size_t pbytes = (size_t)capacity * kStsdfUnit * np * sizeof(float), dbytes = (size_t)capacity * 12;
     if (hipMalloc(&planes, pbytes) != hipSuccess || hipMalloc(&d0, dbytes) != hipSuccess || hipMalloc(&d1, dbytes) != hipSuccess) {
         (void)hipGetLastError();
@@ -72,7 +72,7 @@ static int stsdf_reserve(mi_icp_ctx* c, mi_icp_stsdf* t, int capacity) {
     if (t->n_units > 0) {
         const size_t live = (size_t)t->n_units * kStsdfUnit * sizeof(float);
         for (int p = 0; p < np; ++p)
-            HIPCHK(c, hipMemcpyAsync((float*)planes + (size_t)p * capacity * kStsdfUnit, (const float*)t->planes + (size_t)p * t->v.plane,
+            HIPCHK(c, hipMemcpyAsync((float*)planes + (size_t)p * capacity * kStsdfUnit, (const float*)t->planes + (size_t)p * t->v.p.stride,
                                      live, hipMemcpyDeviceToDevice, c->stream));
         const StsdfDir d = stsdf_dir(t);
         HIPCHK(c, hipMemcpyAsync(dir_keys(d0), d.keys, (size_t)t->n_units * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -101,9 +101,7 @@ void stsdf_release_all(mi_icp_ctx* c) {
 }  // namespace mi
 
 static int stsdf_check(mi_icp_ctx* c, const mi_icp_stsdf* t, const char* what) {
-    if (!t || t->owner != c || std::find(c->stsdf_volumes.begin(), c->stsdf_volumes.end(), t) == c->stsdf_volumes.end())
-        return fail(c, MI_ICP_ERR_INVALID, "%s: not a volume of this context", what);
-    return MI_ICP_OK;
+    return tsdf_volume_check(c, t, c->stsdf_volumes, what);
 }
 
 // Stage 1 of Integrate: the units this frame's sampled points want and the directory lacks are opened.
@@ -154,7 +152,7 @@ static int stsdf_open_units(mi_icp_ctx* c, mi_icp_stsdf* t, const DepthArgs& a) 
     void* dst = t->dir[t->cur ^ 1];
     stsdf_merge<<<blocks_for(need), 256, 0, c->stream>>>(old, fresh, (int)n_new, dir_keys(dst), dir_slots(dst, t->capacity));
     KCHK(c);
-    stsdf_reset_units<<<blocks_for(n_new * kStsdfUnit), 256, 0, c->stream>>>(t->v, t->n_units, n_new * kStsdfUnit);
+    tsdf_reset<<<blocks_for(n_new * kStsdfUnit), 256, 0, c->stream>>>(t->v.p, (int64_t)t->n_units * kStsdfUnit, n_new * kStsdfUnit);
     KCHK(c);
     t->cur ^= 1;
     t->n_units = (int)need;
@@ -181,7 +179,7 @@ int mi_icp_stsdf_create(mi_icp_ctx* c, float voxel_length, float sdf_trunc, int 
     t->v.half = 0.5f * voxel_length;
     t->v.unit_length = L;
     t->v.sdf_trunc = sdf_trunc;
-    t->v.color_type = color_type;
+    t->v.p.color_type = color_type;
     const int rc = stsdf_reserve(c, t, map_size);
     if (rc != MI_ICP_OK) {
         stsdf_free(t);
@@ -224,19 +222,9 @@ int mi_icp_stsdf_integrate(mi_icp_ctx* c, mi_icp_stsdf* t, const void* depth, in
     const char* what = "stsdf_integrate";
     TRY(check_ctx(c));
     TRY(stsdf_check(c, t, what));
-    if (!intrinsic4) return fail(c, MI_ICP_ERR_INVALID, "%s: null intrinsic", what);
-    const int ct = t->v.color_type;
-    // the reference's format checks (scalable_tsdfvolume.cu:318-336)
-    if (depth_channels != 1 || depth_bytes_per_channel != 4 || depth_width != width || depth_height != height ||
-        (ct == MI_ICP_TSDF_RGB8 && (color_channels != 3 || color_bytes_per_channel != 1)) ||
-        (ct == MI_ICP_TSDF_GRAY32 && (color_channels != 1 || color_bytes_per_channel != 4)) ||
-        (ct != MI_ICP_TSDF_NO_COLOR && (color_width != width || color_height != height)))
-        return fail(c, MI_ICP_ERR_INVALID, "[ScalableTSDFVolume::Integrate] Unsupported image format.");
-    if (width < 1 || height < 1 || width > MI_ICP_TSDF_MAX_IMAGE_SIDE || height > MI_ICP_TSDF_MAX_IMAGE_SIDE)
-        return fail(c, MI_ICP_ERR_INVALID, "%s: bad image size (a side is at most %d)", what, MI_ICP_TSDF_MAX_IMAGE_SIDE);
-    if (!depth || (ct != MI_ICP_TSDF_NO_COLOR && !color)) return fail(c, MI_ICP_ERR_INVALID, "%s: null image", what);
-    const int64_t npix = (int64_t)width * height;
-    const float fx = intrinsic4[0], fy = intrinsic4[1], cx = intrinsic4[2], cy = intrinsic4[3];
+    const int ct = t->v.p.color_type;
+    TRY(tsdf_frame_check(c, "ScalableTSDFVolume", what, ct, {depth, depth_width, depth_height, depth_channels, depth_bytes_per_channel},
+                         {color, color_width, color_height, color_channels, color_bytes_per_channel}, width, height, intrinsic4));
     const Mat4 E = load_T(extrinsic);
 
     DepthArgs da = {};
@@ -246,63 +234,30 @@ int mi_icp_stsdf_integrate(mi_icp_ctx* c, mi_icp_stsdf* t, const void* depth, in
     da.depth_scale = 1000;
     da.depth_trunc = 1000;
     da.depth_cutoff = -1.0f;
-    da.fx = fx;
-    da.fy = fy;
-    da.cx = cx;
-    da.cy = cy;
+    da.fx = intrinsic4[0];
+    da.fy = intrinsic4[1];
+    da.cx = intrinsic4[2];
+    da.cy = intrinsic4[3];
     if (!invert4(E.data(), da.pose)) return fail(c, MI_ICP_ERR_INVALID, "%s: singular extrinsic", what);
+    da.depth = (const uint8_t*)depth;
 
-    const uint8_t* dd = (const uint8_t*)depth;
-    const uint8_t* dc = ct == MI_ICP_TSDF_NO_COLOR ? nullptr : (const uint8_t*)color;
-    da.depth = dd;
-
-    if (!t->mult.p || t->mult_w != width || t->mult_h != height || std::memcmp(t->mult_k, intrinsic4, sizeof(float) * 4) != 0) {
-        float* m;
-        TRY(ensure(c, t->mult, (size_t)npix, &m));
-        tsdf_multiplier<<<blocks_for(npix), 256, 0, c->stream>>>(m, width, height, cx, cy, 1.0f / fx, 1.0f / fy);
-        KCHK(c);
-        t->mult_w = width;
-        t->mult_h = height;
-        std::memcpy(t->mult_k, intrinsic4, sizeof(float) * 4);
-    }
-
+    TRY(tsdf_mult_ensure(c, t->mult, width, height, intrinsic4));
     TRY(stsdf_open_units(c, t, da));
     if (t->n_units == 0) return MI_ICP_OK;  // nothing to integrate into
 
-    TsdfIntegrate a = {};
-    a.depth = (const float*)dd;
-    a.color = dc;
-    a.mult = (const float*)t->mult.p;
-    for (int r = 0; r < 3; ++r) {
-        for (int k = 0; k < 4; ++k) a.E[r][k] = E.data()[k * 4 + r];
-        a.D[r] = t->v.voxel_length * a.E[r][2];
-    }
-    a.fx = fx;
-    a.fy = fy;
-    a.cx = cx;
-    a.cy = cy;
-    a.width = width;
-    a.height = height;
-    a.safe_w = (float)width - 0.0001f;
-    a.safe_h = (float)height - 0.0001f;
-    a.sdf_trunc = t->v.sdf_trunc;
-    a.sdf_trunc_inv = (float)(1.0 / (double)t->v.sdf_trunc);
+    TsdfIntegrate a = tsdf_frame_args(E, intrinsic4, width, height, t->v.voxel_length, t->v.sdf_trunc);
+    a.depth = (const float*)depth;
+    a.color = ct == MI_ICP_TSDF_NO_COLOR ? nullptr : color;
+    a.mult = (const float*)t->mult.buf.p;
     stsdf_integrate<<<(unsigned)t->n_units, 256, 0, c->stream>>>(t->v, stsdf_dir(t), a);
     KCHK(c);
-    return MI_ICP_OK;
-}
-
-static int stsdf_extract_args(mi_icp_ctx* c, mi_icp_stsdf* t, const char* what, int64_t capacity, int64_t* m) {
-    TRY(check_sizes(c, what, 0, m, MI_ICP_DEVICE));  // (no cloud comes in: the sizes are the volume's)
-    TRY(stsdf_check(c, t, what));
-    if (capacity < 0) return fail(c, MI_ICP_ERR_INVALID, "%s: negative capacity", what);
     return MI_ICP_OK;
 }
 
 int mi_icp_stsdf_extract_voxel_point_cloud(mi_icp_ctx* c, mi_icp_stsdf* t, float* out_xyz, float* out_colors, int64_t capacity,
                                            int64_t* m) {
     const char* what = "stsdf_extract_voxel_point_cloud";
-    TRY(stsdf_extract_args(c, t, what, capacity, m));
+    TRY(tsdf_extract_args(c, t, c->stsdf_volumes, what, capacity, m, MI_ICP_DEVICE));
     const int64_t n = (int64_t)t->n_units * kStsdfUnit;
     if (n == 0) return MI_ICP_OK;
     uint32_t* flags;
@@ -320,7 +275,7 @@ int mi_icp_stsdf_extract_voxel_point_cloud(mi_icp_ctx* c, mi_icp_stsdf* t, float
 int mi_icp_stsdf_extract_point_cloud(mi_icp_ctx* c, mi_icp_stsdf* t, float* out_xyz, float* out_normals, float* out_colors,
                                      int64_t capacity, int64_t* m) {
     const char* what = "stsdf_extract_point_cloud";
-    TRY(stsdf_extract_args(c, t, what, capacity, m));
+    TRY(tsdf_extract_args(c, t, c->stsdf_volumes, what, capacity, m, MI_ICP_DEVICE));
     const int64_t n = (int64_t)t->n_units * kStsdfUnit;  // every voxel has three candidate edges
     if (n == 0) return MI_ICP_OK;
     uint32_t* count;
@@ -330,7 +285,7 @@ int mi_icp_stsdf_extract_point_cloud(mi_icp_ctx* c, mi_icp_stsdf* t, float* out_
     KCHK(c);
     float* const out[3] = {out_xyz, out_normals, out_colors};
     int listed = MI_ICP_OK;
-    TRY(cloud_emit_counted(c, what, count, n, out, {true, true, t->v.color_type != MI_ICP_TSDF_NO_COLOR}, capacity, m, MI_ICP_DEVICE,
+    TRY(cloud_emit_counted(c, what, count, n, out, {true, true, t->v.p.color_type != MI_ICP_TSDF_NO_COLOR}, capacity, m, MI_ICP_DEVICE,
                            [&](const uint32_t* pos, float* const dst[3]) {
                                uint32_t* list;  // (*m is the count by now)
                                if ((listed = ensure(c, t->edges, (size_t)*m, &list)) != MI_ICP_OK) return;
@@ -343,8 +298,8 @@ int mi_icp_stsdf_extract_point_cloud(mi_icp_ctx* c, mi_icp_stsdf* t, float* out_
 int mi_icp_stsdf_get_units(mi_icp_ctx* c, mi_icp_stsdf* t, int32_t* keys_out, float* tsdf_out, float* weight_out,
                            float* color_out, int64_t capacity, int64_t* m) {
     const char* what = "stsdf_get_units";
-    TRY(stsdf_extract_args(c, t, what, capacity, m));
-    if (color_out && !t->v.color) return fail(c, MI_ICP_ERR_INVALID, "%s: the volume has no colour planes", what);
+    TRY(tsdf_extract_args(c, t, c->stsdf_volumes, what, capacity, m, MI_ICP_DEVICE));
+    if (color_out && !t->v.p.color) return fail(c, MI_ICP_ERR_INVALID, "%s: the volume has no colour planes", what);
     *m = t->n_units;
     if (t->n_units == 0 || capacity < t->n_units) return MI_ICP_OK;
     const int64_t n = (int64_t)t->n_units * kStsdfUnit;

@@ -2,7 +2,7 @@
 // (one translation unit of libmi_icp.so; csrc/ctx.h lists them)
 #include "ctx.h"
 #include "select.h"
-#include "tsdf_kernels.h"
+#include "tsdf_host.h"
 
 using namespace mi;
 using namespace mi::eng;
@@ -16,9 +16,7 @@ struct mi_icp_tsdf {
     TsdfVol v = {};
     float length = 0.0f, sdf_trunc = 0.0f;
     DevBuf planes;  // tsdf, weight and, with a colour type, three colour planes
-    DevBuf mult;    // the depth -> camera-distance multiplier image of the intrinsic below
-    int mult_w = 0, mult_h = 0;
-    float mult_k[4] = {0, 0, 0, 0};
+    TsdfMult mult;
 };
 
 namespace mi {
@@ -26,7 +24,7 @@ namespace eng {
 void tsdf_release_all(mi_icp_ctx* c) {
     for (mi_icp_tsdf* t : c->tsdf_volumes) {
         release(t->planes);
-        release(t->mult);
+        release(t->mult.buf);
         delete t;
     }
     c->tsdf_volumes.clear();
@@ -35,9 +33,7 @@ void tsdf_release_all(mi_icp_ctx* c) {
 }  // namespace mi
 
 static int tsdf_check(mi_icp_ctx* c, const mi_icp_tsdf* t, const char* what) {
-    if (!t || t->owner != c || std::find(c->tsdf_volumes.begin(), c->tsdf_volumes.end(), t) == c->tsdf_volumes.end())
-        return fail(c, MI_ICP_ERR_INVALID, "%s: not a volume of this context", what);
-    return MI_ICP_OK;
+    return tsdf_volume_check(c, t, c->tsdf_volumes, what);
 }
 
 extern "C" {
@@ -58,21 +54,18 @@ int mi_icp_tsdf_create(mi_icp_ctx* c, float length, int resolution, float sdf_tr
     TsdfVol& v = t->v;
     v.res = resolution;
     v.h_res = resolution / 2;
-    v.n = (int64_t)resolution * resolution * resolution;
+    const int64_t n = (int64_t)resolution * resolution * resolution;
     v.voxel_length = length / (float)resolution;
     v.half = 0.5f * v.voxel_length;
     for (int k = 0; k < 3; ++k) v.origin[k] = origin3 ? origin3[k] : 0.0f;
-    v.color_type = color_type;
     float* base;
-    const int rc = ensure(c, t->planes, (size_t)v.n * (color_type == MI_ICP_TSDF_NO_COLOR ? 2 : 5), &base);
+    const int rc = ensure(c, t->planes, (size_t)n * (color_type == MI_ICP_TSDF_NO_COLOR ? 2 : 5), &base);
     if (rc != MI_ICP_OK) {
         delete t;
         return rc;
     }
-    v.tsdf = base;
-    v.weight = base + v.n;
-    v.color = color_type == MI_ICP_TSDF_NO_COLOR ? nullptr : base + 2 * v.n;
-    tsdf_reset<<<blocks_for(v.n), 256, 0, c->stream>>>(v);
+    v.p = {base, base + n, color_type == MI_ICP_TSDF_NO_COLOR ? nullptr : base + 2 * n, n, color_type};
+    tsdf_reset<<<blocks_for(n), 256, 0, c->stream>>>(v.p, 0, n);
     if (hipGetLastError() != hipSuccess) {
         release(t->planes);
         delete t;
@@ -90,7 +83,7 @@ int mi_icp_tsdf_destroy(mi_icp_ctx* c, mi_icp_tsdf* t) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->tsdf_volumes.erase(std::find(c->tsdf_volumes.begin(), c->tsdf_volumes.end(), t));
     release(t->planes);
-    release(t->mult);
+    release(t->mult.buf);
     delete t;
     return MI_ICP_OK;
 }
@@ -98,7 +91,7 @@ int mi_icp_tsdf_destroy(mi_icp_ctx* c, mi_icp_tsdf* t) {
 int mi_icp_tsdf_reset(mi_icp_ctx* c, mi_icp_tsdf* t) {
     TRY(check_ctx(c));
     TRY(tsdf_check(c, t, "tsdf_reset"));
-    tsdf_reset<<<blocks_for(t->v.n), 256, 0, c->stream>>>(t->v);
+    tsdf_reset<<<blocks_for(t->v.p.stride), 256, 0, c->stream>>>(t->v.p, 0, t->v.p.stride);
     KCHK(c);
     return MI_ICP_OK;
 }
@@ -110,58 +103,20 @@ int mi_icp_tsdf_integrate(mi_icp_ctx* c, mi_icp_tsdf* t, const void* depth, int 
     const char* what = "tsdf_integrate";
     TRY(check_ctx(c, mem_kind, what));
     TRY(tsdf_check(c, t, what));
-    if (!intrinsic4) return fail(c, MI_ICP_ERR_INVALID, "%s: null intrinsic", what);
-    const int ct = t->v.color_type;
-    // the reference's format checks (uniform_tsdfvolume.cu:677-695)
-    if (depth_channels != 1 || depth_bytes_per_channel != 4 || depth_width != width || depth_height != height ||
-        (ct == MI_ICP_TSDF_RGB8 && (color_channels != 3 || color_bytes_per_channel != 1)) ||
-        (ct == MI_ICP_TSDF_GRAY32 && (color_channels != 1 || color_bytes_per_channel != 4)) ||
-        (ct != MI_ICP_TSDF_NO_COLOR && (color_width != width || color_height != height)))
-        return fail(c, MI_ICP_ERR_INVALID, "[UniformTSDFVolume::Integrate] Unsupported image format.");
-    if (width < 1 || height < 1 || width > MI_ICP_TSDF_MAX_IMAGE_SIDE || height > MI_ICP_TSDF_MAX_IMAGE_SIDE)
-        return fail(c, MI_ICP_ERR_INVALID, "%s: bad image size (a side is at most %d)", what, MI_ICP_TSDF_MAX_IMAGE_SIDE);
-    if (!depth || (ct != MI_ICP_TSDF_NO_COLOR && !color)) return fail(c, MI_ICP_ERR_INVALID, "%s: null image", what);
+    const int ct = t->v.p.color_type;
+    TRY(tsdf_frame_check(c, "UniformTSDFVolume", what, ct, {depth, depth_width, depth_height, depth_channels, depth_bytes_per_channel},
+                         {color, color_width, color_height, color_channels, color_bytes_per_channel}, width, height, intrinsic4));
     const int64_t npix = (int64_t)width * height;
-    const float fx = intrinsic4[0], fy = intrinsic4[1], cx = intrinsic4[2], cy = intrinsic4[3];
+    TRY(tsdf_mult_ensure(c, t->mult, width, height, intrinsic4));
 
-    if (!t->mult.p || t->mult_w != width || t->mult_h != height || std::memcmp(t->mult_k, intrinsic4, sizeof(float) * 4) != 0) {
-        float* m;
-        TRY(ensure(c, t->mult, (size_t)npix, &m));
-        tsdf_multiplier<<<blocks_for(npix), 256, 0, c->stream>>>(m, width, height, cx, cy, 1.0f / fx, 1.0f / fy);
-        KCHK(c);
-        t->mult_w = width;
-        t->mult_h = height;
-        std::memcpy(t->mult_k, intrinsic4, sizeof(float) * 4);
-    }
-
-    TsdfIntegrate a;
     const uint8_t *dd, *dc;
     TRY(to_device(c, (const uint8_t*)depth, (size_t)npix * 4, mem_kind, c->stage[0], &dd));
     TRY(to_device(c, (const uint8_t*)(ct == MI_ICP_TSDF_NO_COLOR ? nullptr : color),
                   (size_t)npix * (ct == MI_ICP_TSDF_RGB8 ? 3 : 4), mem_kind, c->stage[1], &dc));
+    TsdfIntegrate a = tsdf_frame_args(load_T(extrinsic), intrinsic4, width, height, t->v.voxel_length, t->sdf_trunc);
     a.depth = (const float*)dd;
     a.color = dc;
-    a.mult = (const float*)t->mult.p;
-    const Mat4 E = load_T(extrinsic);
-    for (int r = 0; r < 3; ++r) {
-        for (int k = 0; k < 4; ++k) a.E[r][k] = E.data()[k * 4 + r];
-        a.D[r] = t->v.voxel_length * a.E[r][2];
-    }
-    a.fx = fx;
-    a.fy = fy;
-    a.cx = cx;
-    a.cy = cy;
-    a.width = width;
-    a.height = height;
-    a.safe_w = (float)width - 0.0001f;
-    a.safe_h = (float)height - 0.0001f;
-    a.sdf_trunc = t->sdf_trunc;
-    a.sdf_trunc_inv = (float)(1.0 / (double)t->sdf_trunc);
-    a.cull = (std::fabs(cx) <= 65536.0f && std::fabs(cy) <= 65536.0f) ? 1 : 0;  // (the sides are at most 2^15)
-    a.k_left = cx + 1.5f;
-    a.k_right = ((float)width + 0.5f) - cx;
-    a.k_top = cy + 1.5f;
-    a.k_bottom = ((float)height + 0.5f) - cy;
+    a.mult = (const float*)t->mult.buf.p;
     const int zchunks = (t->v.res + 255) / 256;
     tsdf_integrate<<<(unsigned)((int64_t)t->v.res * t->v.res * zchunks), 256, 0, c->stream>>>(t->v, a, zchunks);
     KCHK(c);
@@ -169,18 +124,11 @@ int mi_icp_tsdf_integrate(mi_icp_ctx* c, mi_icp_tsdf* t, const void* depth, int 
     return MI_ICP_OK;
 }
 
-static int tsdf_extract_args(mi_icp_ctx* c, mi_icp_tsdf* t, const char* what, int64_t capacity, int64_t* m, int mem_kind) {
-    TRY(check_sizes(c, what, 0, m, mem_kind));  // (no cloud comes in: the sizes are the volume's)
-    TRY(tsdf_check(c, t, what));
-    if (capacity < 0) return fail(c, MI_ICP_ERR_INVALID, "%s: negative capacity", what);
-    return MI_ICP_OK;
-}
-
 int mi_icp_tsdf_extract_voxel_point_cloud(mi_icp_ctx* c, mi_icp_tsdf* t, float* out_xyz, float* out_colors, int64_t capacity,
                                           int64_t* m, int mem_kind) {
     const char* what = "tsdf_extract_voxel_point_cloud";
-    TRY(tsdf_extract_args(c, t, what, capacity, m, mem_kind));
-    const int64_t n = t->v.n;
+    TRY(tsdf_extract_args(c, t, c->tsdf_volumes, what, capacity, m, mem_kind));
+    const int64_t n = t->v.p.stride;
     uint32_t* flags;
     TRY(ensure(c, c->flags, (size_t)n, &flags));
     tsdf_voxel_flags<<<blocks_for(n), 256, 0, c->stream>>>(t->v, flags);
@@ -195,14 +143,14 @@ int mi_icp_tsdf_extract_voxel_point_cloud(mi_icp_ctx* c, mi_icp_tsdf* t, float* 
 int mi_icp_tsdf_extract_point_cloud(mi_icp_ctx* c, mi_icp_tsdf* t, float* out_xyz, float* out_normals, float* out_colors,
                                     int64_t capacity, int64_t* m, int mem_kind) {
     const char* what = "tsdf_extract_point_cloud";
-    TRY(tsdf_extract_args(c, t, what, capacity, m, mem_kind));
+    TRY(tsdf_extract_args(c, t, c->tsdf_volumes, what, capacity, m, mem_kind));
     const int64_t r2 = t->v.res - 2, n = r2 * r2 * r2;  // the interior voxels; each has three candidate edges
     uint32_t* count;
     TRY(ensure(c, c->flags, (size_t)n, &count));
     tsdf_cloud_count<<<blocks_for(n), 256, 0, c->stream>>>(t->v, n, count);
     KCHK(c);
     float* const out[3] = {out_xyz, out_normals, out_colors};
-    return cloud_emit_counted(c, what, count, n, out, {true, true, t->v.color_type != MI_ICP_TSDF_NO_COLOR}, capacity, m, mem_kind,
+    return cloud_emit_counted(c, what, count, n, out, {true, true, t->v.p.color_type != MI_ICP_TSDF_NO_COLOR}, capacity, m, mem_kind,
                               [&](const uint32_t* pos, float* const dst[3]) {
                                   tsdf_cloud_gather<<<blocks_for(n), 256, 0, c->stream>>>(t->v, n, count, pos, dst[0], dst[1], dst[2]);
                               });
@@ -212,7 +160,7 @@ int mi_icp_tsdf_raycast(mi_icp_ctx* c, mi_icp_tsdf* t, int width, int height, co
                         float sdf_trunc, int valid_only, float* out_xyz, float* out_normals, float* out_colors,
                         int64_t capacity, int64_t* m, int mem_kind) {
     const char* what = "tsdf_raycast";
-    TRY(tsdf_extract_args(c, t, what, capacity, m, mem_kind));
+    TRY(tsdf_extract_args(c, t, c->tsdf_volumes, what, capacity, m, mem_kind));
     if (!intrinsic4 || width < 0 || height < 0 || width > MI_ICP_TSDF_MAX_IMAGE_SIDE || height > MI_ICP_TSDF_MAX_IMAGE_SIDE)
         return fail(c, MI_ICP_ERR_INVALID, "%s: bad arguments (an image side is at most %d)", what, MI_ICP_TSDF_MAX_IMAGE_SIDE);
     // the march takes length * sqrt(2) / (sdf_trunc / 2) steps at most
@@ -270,10 +218,10 @@ int mi_icp_tsdf_get_voxels(mi_icp_ctx* c, mi_icp_tsdf* t, float* tsdf_out, float
     const char* what = "tsdf_get_voxels";
     TRY(check_ctx(c, mem_kind, what));
     TRY(tsdf_check(c, t, what));
-    if (color_out && !t->v.color) return fail(c, MI_ICP_ERR_INVALID, "%s: the volume has no colour planes", what);
-    TRY(from_device(c, (const float*)t->v.tsdf, tsdf_out, (size_t)t->v.n, mem_kind));
-    TRY(from_device(c, (const float*)t->v.weight, weight_out, (size_t)t->v.n, mem_kind));
-    TRY(from_device(c, (const float*)t->v.color, color_out, (size_t)t->v.n * 3, mem_kind));
+    if (color_out && !t->v.p.color) return fail(c, MI_ICP_ERR_INVALID, "%s: the volume has no colour planes", what);
+    TRY(from_device(c, (const float*)t->v.p.tsdf, tsdf_out, (size_t)t->v.p.stride, mem_kind));
+    TRY(from_device(c, (const float*)t->v.p.weight, weight_out, (size_t)t->v.p.stride, mem_kind));
+    TRY(from_device(c, (const float*)t->v.p.color, color_out, (size_t)t->v.p.stride * 3, mem_kind));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MI_ICP_OK;
 }

@@ -13,12 +13,15 @@
 //   (radix_sort_pairs) + stsdf_heads + (scan) + stsdf_new_keys   the frame's new keys once each, ascending
 //   stsdf_merge       old and new lists into the other directory buffer: every entry's place is its own rank plus the
 //                     number of entries of the other list below it.  New key j gets slot n_old + j.
-//   stsdf_reset_units the new slots' voxels
-//   stsdf_integrate   one workgroup per open unit, a wave on four 16-z columns; the uniform volume's per-voxel rule
+//   (tsdf_reset)      the new slots' voxels
+//   stsdf_integrate   one workgroup per open unit, a wave on four 16-z columns; every voxel goes through
+//                     tsdf_update_voxel (tsdf_kernels.h), the one per-voxel rule of both volumes
 //   stsdf_voxel_flags / stsdf_voxel_gather   ExtractVoxelPointCloud, over the directory's order
 //   stsdf_cloud_count / stsdf_cloud_list / stsdf_cloud_points   ExtractPointCloud: per voxel the number of crossing
 //                     edges; after the scan the edges as a compact list; then one lane per surface point
 //   stsdf_gather_units   the read-back
+// The planes (TsdfPlanes), their reset, the rule and the emit paths' colour blend, normalisation and grey are those of
+// tsdf_kernels.h, which also says what the two volumes keep apart.
 // No kernel here keeps an array that is indexed at run time: none uses scratch memory.
 #pragma once
 #include "depth_kernels.h"
@@ -71,13 +74,9 @@ __device__ __forceinline__ int stsdf_find(const StsdfDir& d, int x, int y, int z
 }
 
 struct StsdfVol {
-    float* tsdf;
-    float* weight;
-    float* color;    // three planes of `plane` floats, or null (NoColor)
-    int64_t plane;   // capacity * 4096
+    TsdfPlanes p;  // stride = capacity * 4096
     float voxel_length, half, unit_length;  // half = 0.5 * voxel_length, unit_length = voxel_length * 16.0f
     float sdf_trunc;
-    int color_type;
 };
 
 // ---- open -----------------------------------------------------------------------------------------------------------
@@ -147,20 +146,6 @@ static __global__ __launch_bounds__(256) void stsdf_merge(StsdfDir old, const ui
     }
 }
 
-// slots [first, first + count) back to tsdf 0, weight 0, colour (1, 1, 1)
-static __global__ __launch_bounds__(256) void stsdf_reset_units(StsdfVol v, int first, int64_t nvox) {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= nvox) return;
-    const int64_t i = (int64_t)first * kStsdfUnit + j;
-    v.tsdf[i] = 0.0f;
-    v.weight[i] = 0.0f;
-    if (v.color) {
-        v.color[i] = 1.0f;
-        v.color[v.plane + i] = 1.0f;
-        v.color[2 * v.plane + i] = 1.0f;
-    }
-}
-
 // ---- integrate ------------------------------------------------------------------------------------------------------
 // block = one open unit (directory entry blockIdx.x); thread t takes voxels (x, t >> 4, t & 15), x = 0..15: a wave reads
 // and writes four whole 16-z columns, 256 consecutive bytes of a plane, per step.
@@ -180,31 +165,7 @@ static __global__ __launch_bounds__(256) void stsdf_integrate(StsdfVol v, StsdfD
         const float X = (((a.E[0][0] * px + a.E[0][1] * py) + a.E[0][2] * pz) + a.E[0][3]) + zf * a.D[0];
         const float Y = (((a.E[1][0] * px + a.E[1][1] * py) + a.E[1][2] * pz) + a.E[1][3]) + zf * a.D[1];
         const float Z = (((a.E[2][0] * px + a.E[2][1] * py) + a.E[2][2] * pz) + a.E[2][3]) + zf * a.D[2];
-        if (Z <= 0.0f) continue;
-        const float u_f = (X * a.fx / Z + a.cx) + 0.5f;
-        const float v_f = (Y * a.fy / Z + a.cy) + 0.5f;
-        if (!(u_f >= 0.0001f && u_f < a.safe_w && v_f >= 0.0001f && v_f < a.safe_h)) continue;
-        // 0.0001 <= u_f < safe_w <= width: the pixel is inside the image
-        const int pu = (int)floorf(u_f), pv = (int)floorf(v_f);
-        const int64_t pix = (int64_t)pv * a.width + pu;
-        const float d = a.depth[pix];
-        if (d <= 0.0f) continue;
-        const float sdf = (d - Z) * a.mult[pix];
-        if (!(sdf > -a.sdf_trunc)) continue;
-        const float t = fminf(1.0f, sdf * a.sdf_trunc_inv);
-        const int64_t i = base + x * 256 + (int)threadIdx.x;
-        const float w = v.weight[i], w1 = w + 1.0f;
-        v.tsdf[i] = (v.tsdf[i] * w + t) / w1;
-        if (v.color_type == kTsdfRGB8) {
-            const uint8_t* rgb = (const uint8_t*)a.color + pix * 3;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) v.color[k * v.plane + i] = (v.color[k * v.plane + i] * w + (float)rgb[k]) / w1;
-        } else if (v.color_type == kTsdfGray32) {
-            const float g = ((const float*)a.color)[pix];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) v.color[k * v.plane + i] = (v.color[k * v.plane + i] * w + g) / w1;
-        }
-        v.weight[i] = w1;
+        tsdf_update_voxel(v.p, base + x * 256 + (int)threadIdx.x, X, Y, Z, a);
     }
 }
 
@@ -215,7 +176,7 @@ static __global__ __launch_bounds__(256) void stsdf_voxel_flags(StsdfVol v, Stsd
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
     const int64_t i = (int64_t)dir.slots[j >> 12] * kStsdfUnit + (j & 4095);
-    flags[j] = tsdf_valid(v.weight[i], v.tsdf[i]) ? 1u : 0u;
+    flags[j] = tsdf_valid(v.p.weight[i], v.p.tsdf[i]) ? 1u : 0u;
 }
 
 static __global__ __launch_bounds__(256) void stsdf_voxel_gather(StsdfVol v, StsdfDir dir, int64_t n,
@@ -232,7 +193,7 @@ static __global__ __launch_bounds__(256) void stsdf_voxel_gather(StsdfVol v, Sts
     const int64_t p = pos[j];
 #pragma unroll
     for (int k = 0; k < 3; ++k) oxyz[p * 3 + k] = (v.half + v.voxel_length * (float)xyz[k]) + (float)key[k] * v.unit_length;
-    const float c = (float)(((double)v.tsdf[i] + 1.0) * 0.5);
+    const float c = tsdf_grey(v.p.tsdf[i]);
     ocol[p * 3] = c;
     ocol[p * 3 + 1] = c;
     ocol[p * 3 + 2] = c;
@@ -254,8 +215,8 @@ __device__ __forceinline__ bool stsdf_edge(const StsdfVol& v, const StsdfDir& di
                                            int64_t* i1, float* f1) {
     *i1 = stsdf_next<AX>(dir, key, slot, vox);
     if (*i1 < 0) return false;  // (weight 0)
-    *f1 = v.tsdf[*i1];
-    return tsdf_valid(v.weight[*i1], *f1) && f0 * *f1 < 0.0f;
+    *f1 = v.p.tsdf[*i1];
+    return tsdf_valid(v.p.weight[*i1], *f1) && f0 * *f1 < 0.0f;
 }
 
 static __global__ __launch_bounds__(256) void stsdf_cloud_count(StsdfVol v, StsdfDir dir, int64_t n, uint32_t* __restrict__ count) {
@@ -264,9 +225,9 @@ static __global__ __launch_bounds__(256) void stsdf_cloud_count(StsdfVol v, Stsd
     const int e = (int)(j >> 12), vox = (int)(j & 4095);
     const int slot = (int)dir.slots[e];
     const int64_t i0 = (int64_t)slot * kStsdfUnit + vox;
-    const float f0 = v.tsdf[i0];
+    const float f0 = v.p.tsdf[i0];
     uint32_t cnt = 0;
-    if (tsdf_valid(v.weight[i0], f0)) {
+    if (tsdf_valid(v.p.weight[i0], f0)) {
         int key[3];
         stsdf_unpack(dir.keys[e], &key[0], &key[1], &key[2]);
         int64_t i1;
@@ -308,7 +269,7 @@ __device__ __forceinline__ float stsdf_at(const StsdfVol& v, const StsdfDir& dir
                 int s = s0;
                 if (wx | wy | wz) s = stsdf_find(dir, u[0] + wx, u[1] + wy, u[2] + wz);
                 f[dx][dy][dz] =
-                    s < 0 ? 0.0f : v.tsdf[(int64_t)s * kStsdfUnit + (cx - 16 * wx) * 256 + (cy - 16 * wy) * 16 + (cz - 16 * wz)];
+                    s < 0 ? 0.0f : v.p.tsdf[(int64_t)s * kStsdfUnit + (cx - 16 * wx) * 256 + (cy - 16 * wy) * 16 + (cz - 16 * wz)];
             }
     const float a0 = 1.0f - r[0], a1 = 1.0f - r[1], a2 = 1.0f - r[2];
     return a0 * (a1 * (a2 * f[0][0][0] + r[2] * f[0][0][1]) + r[1] * (a2 * f[0][1][0] + r[2] * f[0][1][1])) +
@@ -335,10 +296,7 @@ __device__ __forceinline__ void stsdf_cloud_emit(const StsdfVol& v, const StsdfD
     oxyz[p * 3 + 2] = q2;
     if (ocol) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float c = (v.color[k * v.plane + i0] * r1 + v.color[k * v.plane + i1] * r0) / rs;
-            ocol[p * 3 + k] = v.color_type == kTsdfRGB8 ? c / 255.0f : c;
-        }
+        for (int k = 0; k < 3; ++k) ocol[p * 3 + k] = tsdf_blend_color(v.p, k, i0, i1, r0, r1, rs);
     }
     // GetNormalAt: half_gap is a float here
     const float gap = (float)(0.99 * (double)v.voxel_length);
@@ -346,12 +304,7 @@ __device__ __forceinline__ void stsdf_cloud_emit(const StsdfVol& v, const StsdfD
     n[0] = stsdf_at(v, dir, q0 + gap, q1, q2) - stsdf_at(v, dir, q0 - gap, q1, q2);
     n[1] = stsdf_at(v, dir, q0, q1 + gap, q2) - stsdf_at(v, dir, q0, q1 - gap, q2);
     n[2] = stsdf_at(v, dir, q0, q1, q2 + gap) - stsdf_at(v, dir, q0, q1, q2 - gap);
-    const float zz = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
-    if (zz > 0.0f) {
-        const float len = sqrtf(zz);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) n[k] = n[k] / len;
-    }
+    tsdf_normalize(n);
 #pragma unroll
     for (int k = 0; k < 3; ++k) onrm[p * 3 + k] = n[k];
 }
@@ -364,7 +317,7 @@ static __global__ __launch_bounds__(256) void stsdf_cloud_list(StsdfVol v, Stsdf
     if (j >= n || !count[j]) return;
     const int e = (int)(j >> 12), vox = (int)(j & 4095);
     const int slot = (int)dir.slots[e];
-    const float f0 = v.tsdf[(int64_t)slot * kStsdfUnit + vox];
+    const float f0 = v.p.tsdf[(int64_t)slot * kStsdfUnit + vox];
     int key[3];
     stsdf_unpack(dir.keys[e], &key[0], &key[1], &key[2]);
     int64_t p = pos[j], i1;
@@ -390,7 +343,7 @@ static __global__ __launch_bounds__(256) void stsdf_cloud_points(StsdfVol v, Sts
     stsdf_unpack(dir.keys[e], &key[0], &key[1], &key[2]);
     const int64_t i1 = ax == 0 ? stsdf_next<0>(dir, key, slot, vox) : (ax == 1 ? stsdf_next<1>(dir, key, slot, vox) : stsdf_next<2>(dir, key, slot, vox));
     if (i1 < 0) return;  // (the list holds crossing edges only: voxel 1 is there)
-    stsdf_cloud_emit(v, dir, key, vox, ax, i0, i1, v.tsdf[i0], v.tsdf[i1], p, oxyz, onrm, ocol);
+    stsdf_cloud_emit(v, dir, key, vox, ax, i0, i1, v.p.tsdf[i0], v.p.tsdf[i1], p, oxyz, onrm, ocol);
 }
 
 // ---- read-back ------------------------------------------------------------------------------------------------------
@@ -407,11 +360,11 @@ static __global__ __launch_bounds__(256) void stsdf_gather_units(StsdfVol v, Sts
         stsdf_unpack(dir.keys[e], &key[0], &key[1], &key[2]);
         keys[(int64_t)e * 3 + vox] = vox == 0 ? key[0] : (vox == 1 ? key[1] : key[2]);
     }
-    if (tsdf) tsdf[j] = v.tsdf[i];
-    if (weight) weight[j] = v.weight[i];
+    if (tsdf) tsdf[j] = v.p.tsdf[i];
+    if (weight) weight[j] = v.p.weight[i];
     if (color) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) color[k * n + j] = v.color[k * v.plane + i];
+        for (int k = 0; k < 3; ++k) color[k * n + j] = v.p.color[k * v.p.stride + i];
     }
 }
 

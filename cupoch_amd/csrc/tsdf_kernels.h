@@ -4,11 +4,14 @@
 //
 // The volume is five planes of resolution^3 floats -- tsdf, weight and (only with a colour type) three colour planes
 // -- indexed x*res*res + y*res + z, z fastest.  The reference keeps an array of 20-byte voxels.
+// TsdfPlanes, tsdf_reset, tsdf_update_voxel (the per-voxel rule) and the small tsdf_blend_color / tsdf_normalize /
+// tsdf_grey below are also ScalableTSDFVolume's (scalable_tsdf_kernels.h): each stands here once.
 //   tsdf_multiplier   the depth -> camera-distance multiplier image, once per intrinsic (cached on the volume)
-//   tsdf_integrate    a wave takes 64 consecutive z of one (x, y) column.  Whether a voxel is updated is decided from
-//                     its projection and one depth gather; only then are its planes loaded and stored (8 bytes each
-//                     way without colour, 20 with).  A wave whose z-span lies behind the camera or beside the image by
-//                     a margin that covers every rounding of the per-voxel arithmetic leaves before any of it.
+//   tsdf_integrate    a wave takes 64 consecutive z of one (x, y) column and hands each voxel's camera point to
+//                     tsdf_update_voxel: whether a voxel is updated is decided from its projection and one depth
+//                     gather; only then are its planes loaded and stored (8 bytes each way without colour, 20 with).
+//                     A wave whose z-span lies behind the camera or beside the image by a margin that covers every
+//                     rounding of the per-voxel arithmetic leaves before any of it.
 //   tsdf_raycast      one lane per pixel, an 8x8 pixel tile per wave, so that neighbouring rays gather neighbouring
 //                     voxels.  Writes NaN for an invalid pixel; finite_flags + scan + select_gather (select.h) remove
 //                     those when asked.
@@ -24,27 +27,33 @@ namespace mi {
 
 constexpr int kTsdfNoColor = 0, kTsdfRGB8 = 1, kTsdfGray32 = 2;
 
-struct TsdfVol {
+// the planes of a volume or of a pool of units; plane k of the colour starts at color + k * stride
+struct TsdfPlanes {
     float* tsdf;
     float* weight;
-    float* color;  // three planes of n floats, or null (NoColor)
-    int64_t n;     // res^3
-    int res, h_res;
-    float voxel_length, half;  // half = 0.5 * voxel_length
-    float origin[3];
+    float* color;    // three planes of `stride` floats, or null (NoColor)
+    int64_t stride;  // floats in a plane
     int color_type;
 };
 
-// every voxel back to tsdf 0, weight 0, colour (1, 1, 1)
-static __global__ __launch_bounds__(256) void tsdf_reset(TsdfVol v) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= v.n) return;
-    v.tsdf[i] = 0.0f;
-    v.weight[i] = 0.0f;
-    if (v.color) {
-        v.color[i] = 1.0f;
-        v.color[v.n + i] = 1.0f;
-        v.color[2 * v.n + i] = 1.0f;
+struct TsdfVol {
+    TsdfPlanes p;  // stride = res^3
+    int res, h_res;
+    float voxel_length, half;  // half = 0.5 * voxel_length
+    float origin[3];
+};
+
+// voxels [first, first + count) back to tsdf 0, weight 0, colour (1, 1, 1)
+static __global__ __launch_bounds__(256) void tsdf_reset(TsdfPlanes p, int64_t first, int64_t count) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= count) return;
+    const int64_t i = first + j;
+    p.tsdf[i] = 0.0f;
+    p.weight[i] = 0.0f;
+    if (p.color) {
+        p.color[i] = 1.0f;
+        p.color[p.stride + i] = 1.0f;
+        p.color[2 * p.stride + i] = 1.0f;
     }
 }
 
@@ -70,6 +79,39 @@ struct TsdfIntegrate {
     int cull;
     float k_left, k_right, k_top, k_bottom;  // cx + 1.5, width + 0.5 - cx, cy + 1.5, height + 0.5 - cy
 };
+
+// THE PER-VOXEL RULE of both volumes (integrate_functor.h): voxel i of the planes, whose centre is the camera point
+// (X, Y, Z), takes the frame's observation -- project, gather the depth, truncate, running mean of tsdf and of the
+// three colour planes, weight + 1 -- or is left as it is.  It knows nothing of the volume that calls it.
+// What the two volumes do NOT share, because the reference's own two classes differ there: tsdf_at / stsdf_at (and
+// GetNormalAt's half_gap, a double in the uniform volume, a float in the scalable one), the template-axis
+// tsdf_cloud_emit against the run-time-axis stsdf_cloud_emit, and tsdf_raycast (the scalable volume has none).
+__device__ __forceinline__ void tsdf_update_voxel(const TsdfPlanes& p, int64_t i, float X, float Y, float Z, const TsdfIntegrate& a) {
+    if (Z <= 0.0f) return;
+    const float u_f = (X * a.fx / Z + a.cx) + 0.5f;
+    const float v_f = (Y * a.fy / Z + a.cy) + 0.5f;
+    if (!(u_f >= 0.0001f && u_f < a.safe_w && v_f >= 0.0001f && v_f < a.safe_h)) return;
+    // 0.0001 <= u_f < safe_w <= width: the pixel is inside the image
+    const int pu = (int)floorf(u_f), pv = (int)floorf(v_f);
+    const int64_t pix = (int64_t)pv * a.width + pu;
+    const float d = a.depth[pix];
+    if (d <= 0.0f) return;
+    const float sdf = (d - Z) * a.mult[pix];
+    if (!(sdf > -a.sdf_trunc)) return;
+    const float t = fminf(1.0f, sdf * a.sdf_trunc_inv);
+    const float w = p.weight[i], w1 = w + 1.0f;
+    p.tsdf[i] = (p.tsdf[i] * w + t) / w1;
+    if (p.color_type == kTsdfRGB8) {
+        const uint8_t* rgb = (const uint8_t*)a.color + pix * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p.color[k * p.stride + i] = (p.color[k * p.stride + i] * w + (float)rgb[k]) / w1;
+    } else if (p.color_type == kTsdfGray32) {
+        const float g = ((const float*)a.color)[pix];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p.color[k * p.stride + i] = (p.color[k * p.stride + i] * w + g) / w1;
+    }
+    p.weight[i] = w1;
+}
 
 // X*fx + k*Z at one end of a span (the quantity whose sign says on which side of an image edge, moved out by one
 // pixel, the point projects)
@@ -119,31 +161,7 @@ static __global__ __launch_bounds__(256) void tsdf_integrate(TsdfVol v, TsdfInte
     if (z >= v.res) return;
     const float zf = (float)(z - v.h_res);
     const float X = X0 + zf * a.D[0], Y = Y0 + zf * a.D[1], Z = Z0 + zf * a.D[2];
-    if (Z <= 0.0f) return;
-    const float u_f = (X * a.fx / Z + a.cx) + 0.5f;
-    const float v_f = (Y * a.fy / Z + a.cy) + 0.5f;
-    if (!(u_f >= 0.0001f && u_f < a.safe_w && v_f >= 0.0001f && v_f < a.safe_h)) return;
-    // 0.0001 <= u_f < safe_w <= width: the pixel is inside the image
-    const int pu = (int)floorf(u_f), pv = (int)floorf(v_f);
-    const int64_t pix = (int64_t)pv * a.width + pu;
-    const float d = a.depth[pix];
-    if (d <= 0.0f) return;
-    const float sdf = (d - Z) * a.mult[pix];
-    if (!(sdf > -a.sdf_trunc)) return;
-    const float t = fminf(1.0f, sdf * a.sdf_trunc_inv);
-    const int64_t i = (int64_t)col * v.res + z;
-    const float w = v.weight[i], w1 = w + 1.0f;
-    v.tsdf[i] = (v.tsdf[i] * w + t) / w1;
-    if (v.color_type == kTsdfRGB8) {
-        const uint8_t* rgb = (const uint8_t*)a.color + pix * 3;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v.color[k * v.n + i] = (v.color[k * v.n + i] * w + (float)rgb[k]) / w1;
-    } else if (v.color_type == kTsdfGray32) {
-        const float g = ((const float*)a.color)[pix];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v.color[k * v.n + i] = (v.color[k * v.n + i] * w + g) / w1;
-    }
-    v.weight[i] = w1;
+    tsdf_update_voxel(v.p, (int64_t)col * v.res + z, X, Y, Z, a);
 }
 
 // ---- extraction -----------------------------------------------------------------------------------------------------
@@ -152,24 +170,43 @@ __device__ __forceinline__ bool tsdf_valid(float w, float f) { return w != 0.0f 
 // floor to int with the value held inside +-1e9 first (a NaN becomes -1e9): no conversion is undefined
 __device__ __forceinline__ int tsdf_floor_int(float x) { return (int)fminf(fmaxf(floorf(x), -1.0e9f), 1.0e9f); }
 
+// colour plane k of a surface point between voxels i0 and i1 (|tsdf| r0 and r1, rs their sum), RGB8 scaled to [0, 1]
+__device__ __forceinline__ float tsdf_blend_color(const TsdfPlanes& p, int k, int64_t i0, int64_t i1, float r0, float r1, float rs) {
+    const float c = (p.color[k * p.stride + i0] * r1 + p.color[k * p.stride + i1] * r0) / rs;
+    return p.color_type == kTsdfRGB8 ? c / 255.0f : c;
+}
+
+// a normal to unit length; a zero one stays
+__device__ __forceinline__ void tsdf_normalize(float n[3]) {
+    const float zz = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+    if (zz > 0.0f) {
+        const float len = sqrtf(zz);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) n[k] = n[k] / len;
+    }
+}
+
+// ExtractVoxelPointCloud's colour of a voxel
+__device__ __forceinline__ float tsdf_grey(float tsdf) { return (float)(((double)tsdf + 1.0) * 0.5); }
+
 static __global__ __launch_bounds__(256) void tsdf_voxel_flags(TsdfVol v, uint32_t* __restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= v.n) return;
-    flags[i] = tsdf_valid(v.weight[i], v.tsdf[i]) ? 1u : 0u;
+    if (i >= v.p.stride) return;
+    flags[i] = tsdf_valid(v.p.weight[i], v.p.tsdf[i]) ? 1u : 0u;
 }
 
 static __global__ __launch_bounds__(256) void tsdf_voxel_gather(TsdfVol v, const uint32_t* __restrict__ flags,
                                                                const uint32_t* __restrict__ pos, float* __restrict__ oxyz,
                                                                float* __restrict__ ocol) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= v.n || !flags[i]) return;
+    if (i >= v.p.stride || !flags[i]) return;
     const int64_t p = pos[i];
     const int res2 = v.res * v.res;
     const int x = (int)(i / res2), yz = (int)(i % res2), y = yz / v.res, z = yz % v.res;
     oxyz[p * 3] = (v.half + v.voxel_length * (float)(x - v.h_res)) + v.origin[0];
     oxyz[p * 3 + 1] = (v.half + v.voxel_length * (float)(y - v.h_res)) + v.origin[1];
     oxyz[p * 3 + 2] = (v.half + v.voxel_length * (float)(z - v.h_res)) + v.origin[2];
-    const float c = (float)(((double)v.tsdf[i] + 1.0) * 0.5);
+    const float c = tsdf_grey(v.p.tsdf[i]);
     ocol[p * 3] = c;
     ocol[p * 3 + 1] = c;
     ocol[p * 3 + 2] = c;
@@ -187,8 +224,8 @@ __device__ __forceinline__ void tsdf_interior(int64_t j, int res, int* x, int* y
 // does the edge from voxel i0 (valid, tsdf f0) to its neighbour at +stride along an axis with coordinate c cross zero?
 __device__ __forceinline__ bool tsdf_edge(const TsdfVol& v, int64_t i0, float f0, int c, int64_t stride, float* f1) {
     if (!(c + 1 < v.res - 1)) return false;
-    *f1 = v.tsdf[i0 + stride];
-    return tsdf_valid(v.weight[i0 + stride], *f1) && f0 * *f1 < 0.0f;
+    *f1 = v.p.tsdf[i0 + stride];
+    return tsdf_valid(v.p.weight[i0 + stride], *f1) && f0 * *f1 < 0.0f;
 }
 
 static __global__ __launch_bounds__(256) void tsdf_cloud_count(TsdfVol v, int64_t ninner, uint32_t* __restrict__ count) {
@@ -197,9 +234,9 @@ static __global__ __launch_bounds__(256) void tsdf_cloud_count(TsdfVol v, int64_
     int x, y, z;
     tsdf_interior(j, v.res, &x, &y, &z);
     const int64_t i0 = ((int64_t)x * v.res + y) * v.res + z;
-    const float f0 = v.tsdf[i0];
+    const float f0 = v.p.tsdf[i0];
     uint32_t cnt = 0;
-    if (tsdf_valid(v.weight[i0], f0)) {
+    if (tsdf_valid(v.p.weight[i0], f0)) {
         float f1;
         cnt += tsdf_edge(v, i0, f0, x, (int64_t)v.res * v.res, &f1) ? 1u : 0u;
         cnt += tsdf_edge(v, i0, f0, y, v.res, &f1) ? 1u : 0u;
@@ -216,7 +253,7 @@ __device__ __forceinline__ float tsdf_at(const TsdfVol& v, float p0, float p1, f
     const int i0 = min(max(tsdf_floor_int(g0), 0), top), i1 = min(max(tsdf_floor_int(g1), 0), top),
               i2 = min(max(tsdf_floor_int(g2), 0), top);
     const float r0 = g0 - (float)i0, r1 = g1 - (float)i1, r2 = g2 - (float)i2;
-    const float* __restrict__ T = v.tsdf + ((int64_t)i0 * v.res + i1) * v.res + i2;
+    const float* __restrict__ T = v.p.tsdf + ((int64_t)i0 * v.res + i1) * v.res + i2;
     const int64_t sx = (int64_t)v.res * v.res, sy = v.res;
     float s = 0.0f;
     s += (1.0f - r0) * (1.0f - r1) * (1.0f - r2) * T[0];
@@ -243,10 +280,7 @@ __device__ __forceinline__ void tsdf_cloud_emit(const TsdfVol& v, int64_t i0, in
     for (int k = 0; k < 3; ++k) oxyz[p * 3 + k] = (q[k] + v.origin[k]) - hres;
     if (ocol) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float c = (v.color[k * v.n + i0] * r1 + v.color[k * v.n + i0 + stride] * r0) / rs;
-            ocol[p * 3 + k] = v.color_type == kTsdfRGB8 ? c / 255.0f : c;
-        }
+        for (int k = 0; k < 3; ++k) ocol[p * 3 + k] = tsdf_blend_color(v.p, k, i0, i0 + stride, r0, r1, rs);
     }
     // GetNormalAt: half_gap = 0.99 * voxel_length in double, applied to a float
     const double gap = 0.99 * (double)v.voxel_length;
@@ -258,12 +292,7 @@ __device__ __forceinline__ void tsdf_cloud_emit(const TsdfVol& v, int64_t i0, in
         const float b = tsdf_at(v, k == 0 ? lo : q[0], k == 1 ? lo : q[1], k == 2 ? lo : q[2]);
         n[k] = a - b;
     }
-    const float zz = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
-    if (zz > 0.0f) {
-        const float len = sqrtf(zz);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) n[k] = n[k] / len;
-    }
+    tsdf_normalize(n);
 #pragma unroll
     for (int k = 0; k < 3; ++k) onrm[p * 3 + k] = n[k];
 }
@@ -276,7 +305,7 @@ static __global__ __launch_bounds__(256) void tsdf_cloud_gather(TsdfVol v, int64
     int x, y, z;
     tsdf_interior(j, v.res, &x, &y, &z);
     const int64_t i0 = ((int64_t)x * v.res + y) * v.res + z;
-    const float f0 = v.tsdf[i0];
+    const float f0 = v.p.tsdf[i0];
     int64_t p = pos[j];
     float f1;
     const int64_t sx = (int64_t)v.res * v.res, sy = v.res;
@@ -307,7 +336,7 @@ __device__ __forceinline__ float tsdf_trilinear(const TsdfVol& v, float p0, floa
     i0 = min(max(i0, 0), top);
     i1 = min(max(i1, 0), top);
     i2 = min(max(i2, 0), top);
-    const float* __restrict__ T = v.tsdf + ((int64_t)i0 * v.res + i1) * v.res + i2;
+    const float* __restrict__ T = v.p.tsdf + ((int64_t)i0 * v.res + i1) * v.res + i2;
     const int64_t sx = (int64_t)v.res * v.res, sy = v.res;
     return ((((((T[0] * (1.0f - a) * (1.0f - b) * (1.0f - c) + T[1] * (1.0f - a) * (1.0f - b) * c) +
                 T[sy] * (1.0f - a) * b * (1.0f - c)) +
@@ -361,7 +390,7 @@ static __global__ __launch_bounds__(256) void tsdf_raycast(TsdfVol v, TsdfRaycas
         int g1 = tsdf_floor_int((t1 + d1 * ray_len) / vl) + v.h_res;
         int g2 = tsdf_floor_int((t2 + d2 * ray_len) / vl) + v.h_res;
         if (!tsdf_inside(g0, g1, g2, 0, res)) break;
-        float cur = v.tsdf[((int64_t)g0 * res + g1) * res + g2];
+        float cur = v.p.tsdf[((int64_t)g0 * res + g1) * res + g2];
         const float max_len = ray_len + length * 1.41421354f;  // sqrt(2.0f)
         const float step = a.sdf_trunc * 0.5f;
         // The march must advance: a step below half an ulp of the ray length would leave ray_len where it is for ever
@@ -375,7 +404,7 @@ static __global__ __launch_bounds__(256) void tsdf_raycast(TsdfVol v, TsdfRaycas
             g2 = tsdf_floor_int((t2 + d2 * ahead) / vl) + v.h_res;
             if (!tsdf_inside(g0, g1, g2, 1, res)) continue;
             const float prev = cur;
-            cur = v.tsdf[((int64_t)g0 * res + g1) * res + g2];
+            cur = v.p.tsdf[((int64_t)g0 * res + g1) * res + g2];
             if (prev < 0.0f && cur > 0.0f) break;
             if (prev > 0.0f && cur < 0.0f) {
                 const float t_star = ray_len - step * prev / (cur - prev);
@@ -401,8 +430,8 @@ static __global__ __launch_bounds__(256) void tsdf_raycast(TsdfVol v, TsdfRaycas
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     float c = 0.0f;
-                    if (v.color_type == kTsdfRGB8) c = (float)((double)v.color[k * v.n + ci] / 255.0);
-                    else if (v.color_type == kTsdfGray32) c = v.color[k * v.n + ci];
+                    if (v.p.color_type == kTsdfRGB8) c = (float)((double)v.p.color[k * v.p.stride + ci] / 255.0);
+                    else if (v.p.color_type == kTsdfGray32) c = v.p.color[k * v.p.stride + ci];
                     C[k] = c;
                 }
                 break;

@@ -659,9 +659,9 @@ class Engine:
         self._chk(self._L.mi_icp_tsdf_reset(self._ctx, vol))
 
     @staticmethod
-    def _image_desc(x):
+    def _image_desc(x, bad=None):
         """(array kept alive, pointer, width, height, channels, bytes per channel, on the device?) of an image:
-        [H, W] or [H, W, C], numpy or torch"""
+        [H, W] or [H, W, C], numpy or torch; anything else raises MiIcpError(bad)"""
         if x is None:
             return None, None, 0, 0, 0, 0, None
         on_dev = _is_tensor(x) and x.is_cuda
@@ -670,26 +670,31 @@ class Engine:
         else:
             x = np.ascontiguousarray(x)
         if x.ndim not in (2, 3):
-            raise MiIcpError("[UniformTSDFVolume::Integrate] Unsupported image format.")
+            raise MiIcpError(bad)
         bpc = int(x.element_size()) if on_dev else int(x.dtype.itemsize)
         ptr = C.c_void_p(x.data_ptr()) if on_dev else x.ctypes.data_as(C.c_void_p)
         return x, ptr, int(x.shape[1]), int(x.shape[0]), (int(x.shape[2]) if x.ndim == 3 else 1), bpc, on_dev
 
+    def _tsdf_frame(self, label, depth, color):
+        """-> (depth, color) of an Integrate call as _image_desc describes them.  A pair the reference's `label` class
+        turns away raises MiIcpError("[label::Integrate] Unsupported image format.")."""
+        bad = "[%s::Integrate] Unsupported image format." % label
+        d, col = self._image_desc(depth, bad), self._image_desc(color, bad)
+        if d[0] is None:
+            raise MiIcpError(bad)
+        if col[0] is not None and col[6] != d[6]:
+            raise MiIcpError("depth and color must live on the same side")
+        f32, u8 = (torch.float32, torch.uint8) if d[6] else (np.float32, np.uint8)
+        # a float image must be float: the C ABI sees bytes per channel only
+        if d[0].dtype != f32 or not (col[0] is None or col[0].dtype in (f32, u8)):
+            raise MiIcpError(bad)
+        return d, col
+
     def tsdf_integrate(self, vol, depth, color, width, height, intrinsic4, extrinsic=None):
         """UniformTSDFVolume::Integrate; depth / color numpy or torch, both on the same side.  A format the
         reference turns away raises MiIcpError."""
-        d, dptr, dw, dh, dc, db, d_dev = self._image_desc(depth)
-        col, cptr, cw, ch, cc, cb, c_dev = self._image_desc(color)
-        if d is None:
-            raise MiIcpError("[UniformTSDFVolume::Integrate] Unsupported image format.")
-        if col is not None and c_dev != d_dev:
-            raise MiIcpError("depth and color must live on the same side")
-        if d_dev:   # a float image must be float: the C ABI sees bytes per channel only
-            ok = d.dtype == torch.float32 and (col is None or col.dtype in (torch.float32, torch.uint8))
-        else:
-            ok = d.dtype == np.float32 and (col is None or col.dtype in (np.float32, np.uint8))
-        if not ok:
-            raise MiIcpError("[UniformTSDFVolume::Integrate] Unsupported image format.")
+        d, col = self._tsdf_frame("UniformTSDFVolume", depth, color)     # (they keep the arrays alive through the call)
+        (_, dptr, dw, dh, dc, db, d_dev), (_, cptr, cw, ch, cc, cb, _) = d, col
         K = (C.c_float * 4)(*[float(v) for v in intrinsic4])
         _, Eptr = _T_in(extrinsic)
         self._chk(self._L.mi_icp_tsdf_integrate(self._ctx, vol, dptr, dw, dh, dc, db, cptr, cw, ch, cc, cb, int(width),
@@ -766,29 +771,13 @@ class Engine:
         """ScalableTSDFVolume::Integrate; depth / color numpy or torch, both on the same side.  The C ABI of this family
         reads device memory only: host images are uploaded here, and the call waits before they are let go.  A format
         the reference turns away raises MiIcpError."""
-        bad = "[ScalableTSDFVolume::Integrate] Unsupported image format."
-        try:
-            d, _, _, _, _, _, d_dev = self._image_desc(depth)
-            col, _, _, _, _, _, c_dev = self._image_desc(color)
-        except MiIcpError:
-            raise MiIcpError(bad)
-        if d is None:
-            raise MiIcpError(bad)
-        if col is not None and c_dev != d_dev:
-            raise MiIcpError("depth and color must live on the same side")
-        if d_dev:   # a float image must be float: the C ABI sees bytes per channel only
-            ok = d.dtype == torch.float32 and (col is None or col.dtype in (torch.float32, torch.uint8))
-        else:
-            ok = d.dtype == np.float32 and (col is None or col.dtype in (np.float32, np.uint8))
-        if not ok:
-            raise MiIcpError(bad)
+        d, col = self._tsdf_frame("ScalableTSDFVolume", depth, color)
+        d_dev = d[6]
         if not d_dev:
             dev = torch.device("cuda", self.device)
-            d = torch.from_numpy(d).to(dev)
-            col = None if col is None else torch.from_numpy(col).to(dev)
+            d, col = [self._image_desc(None if x[0] is None else torch.from_numpy(x[0]).to(dev)) for x in (d, col)]
             torch.cuda.synchronize(dev)
-        d, dptr, dw, dh, dc, db, _ = self._image_desc(d)
-        col, cptr, cw, ch, cc, cb, _ = self._image_desc(col)
+        (_, dptr, dw, dh, dc, db, _), (_, cptr, cw, ch, cc, cb, _) = d, col
         K = (C.c_float * 4)(*[float(v) for v in intrinsic4])
         _, Eptr = _T_in(extrinsic)
         self._chk(self._L.mi_icp_stsdf_integrate(self._ctx, vol, dptr, dw, dh, dc, db, cptr, cw, ch, cc, cb, int(width),

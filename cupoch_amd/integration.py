@@ -18,15 +18,6 @@ class TSDFVolumeColorType(enum.IntEnum):
     Gray32 = 2
 
 
-class TSDFVolume:
-    """tsdfvolume.h:44-74: the base class's fields"""
-
-    def __init__(self, voxel_length, sdf_trunc, color_type):
-        self.voxel_length = float(np.float32(voxel_length))
-        self.sdf_trunc = float(np.float32(sdf_trunc))
-        self.color_type = TSDFVolumeColorType(color_type)
-
-
 def _cloud(p, n, c):
     out = geometry.PointCloud()
     out._points = utility.Vector3fVector(p)
@@ -37,7 +28,59 @@ def _cloud(p, n, c):
     return out
 
 
+class TSDFVolume:
+    """tsdfvolume.h:44-74: the base class's fields, and what the two volumes do alike.  A subclass names the
+    reference's class (_LABEL) and the prefix of its engine functions (_API), and keeps its engine and handle in _eng
+    and _vol."""
+    _LABEL = _API = _vol = None
+
+    def __init__(self, voxel_length, sdf_trunc, color_type):
+        self.voxel_length = float(np.float32(voxel_length))
+        self.sdf_trunc = float(np.float32(sdf_trunc))
+        self.color_type = TSDFVolumeColorType(color_type)
+
+    def _call(self, name, *args):
+        return getattr(self._eng, self._API + name)(self._vol, *args)
+
+    def __del__(self):
+        try:
+            self._call("_destroy")
+        except Exception:
+            pass
+        self._vol = None
+
+    def reset(self):
+        self._call("_reset")
+
+    def integrate(self, image, intrinsic, extrinsic):
+        """<class>::Integrate(RGBDImage, PinholeCameraIntrinsic, extrinsic).  Returns True; a format the reference turns
+        away ([<class>::Integrate] Unsupported image format.) is reported, the volume is left as it was and False
+        comes back."""
+        bad = "[%s::Integrate] Unsupported image format." % self._LABEL
+        color = None if self.color_type == TSDFVolumeColorType.NoColor else image.color
+        try:
+            if color is None and self.color_type != TSDFVolumeColorType.NoColor:
+                raise MiIcpError(bad)
+            self._call("_integrate", image.depth, color, intrinsic.width, intrinsic.height, intrinsic.as4(), extrinsic)
+        except MiIcpError as e:
+            if "Unsupported image format" not in str(e):
+                raise
+            print("[cupoch_amd] Error: " + bad)
+            return False
+        return True
+
+    def extract_point_cloud(self):
+        p, n, c = self._call("_extract_point_cloud", self.color_type != TSDFVolumeColorType.NoColor)
+        return _cloud(p, n, c)
+
+    def extract_voxel_point_cloud(self):
+        p, c = self._call("_extract_voxel_point_cloud")
+        return _cloud(p, None, c)
+
+
 class UniformTSDFVolume(TSDFVolume):
+    _LABEL, _API = "UniformTSDFVolume", "tsdf"
+
     def __init__(self, length, resolution, sdf_trunc, color_type, origin=(0.0, 0.0, 0.0), device=None):
         color_type = TSDFVolumeColorType(color_type)
         resolution = int(resolution)
@@ -48,41 +91,6 @@ class UniformTSDFVolume(TSDFVolume):
         self.origin = np.asarray(origin, np.float32).reshape(3).copy()
         self._eng = geometry.get_engine(device)
         self._vol = self._eng.tsdf_create(self.length, resolution, self.sdf_trunc, int(color_type), self.origin)
-
-    def __del__(self):
-        try:
-            self._eng.tsdf_destroy(self._vol)
-        except Exception:
-            pass
-        self._vol = None
-
-    def reset(self):
-        self._eng.tsdf_reset(self._vol)
-
-    def integrate(self, image, intrinsic, extrinsic):
-        """UniformTSDFVolume::Integrate(RGBDImage, PinholeCameraIntrinsic, extrinsic).  Returns True; a format the
-        reference turns away ([UniformTSDFVolume::Integrate] Unsupported image format.) is reported, the volume is
-        left as it was and False comes back."""
-        color = None if self.color_type == TSDFVolumeColorType.NoColor else image.color
-        try:
-            if color is None and self.color_type != TSDFVolumeColorType.NoColor:
-                raise MiIcpError("[UniformTSDFVolume::Integrate] Unsupported image format.")
-            self._eng.tsdf_integrate(self._vol, image.depth, color, intrinsic.width, intrinsic.height, intrinsic.as4(),
-                                     extrinsic)
-        except MiIcpError as e:
-            if "Unsupported image format" not in str(e):
-                raise
-            print("[cupoch_amd] Error: [UniformTSDFVolume::Integrate] Unsupported image format.")
-            return False
-        return True
-
-    def extract_point_cloud(self):
-        p, n, c = self._eng.tsdf_extract_point_cloud(self._vol, self.color_type != TSDFVolumeColorType.NoColor)
-        return _cloud(p, n, c)
-
-    def extract_voxel_point_cloud(self):
-        p, c = self._eng.tsdf_extract_voxel_point_cloud(self._vol)
-        return _cloud(p, None, c)
 
     def raycast(self, intrinsic, extrinsic, sdf_trunc, project_valid_depth_only=True):
         p, n, c = self._eng.tsdf_raycast(self._vol, intrinsic.width, intrinsic.height, intrinsic.as4(), extrinsic,

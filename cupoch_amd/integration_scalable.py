@@ -7,13 +7,13 @@ integrate_with_depth_to_camera_distance_multiplier."""
 import numpy as np
 
 from . import geometry
-from ._lib import MiIcpError
-from .integration import TSDFVolume, TSDFVolumeColorType, _cloud
+from .integration import TSDFVolume, TSDFVolumeColorType
 
 
 class ScalableTSDFVolume(TSDFVolume):
     """scalable_tsdfvolume.h: a sparse volume of 16^3-voxel units opened around the observed surface.  map_size is the
     initial number of unit slots: the volume grows by doubling where the reference drops units."""
+    _LABEL, _API = "ScalableTSDFVolume", "stsdf"
 
     def __init__(self, voxel_length, sdf_trunc, color_type, depth_sampling_stride=4, map_size=1000, device=None):
         color_type = TSDFVolumeColorType(color_type)
@@ -22,45 +22,9 @@ class ScalableTSDFVolume(TSDFVolume):
         self.volume_unit_length = float(np.float32(voxel_length) * np.float32(16.0))
         self.volume_unit_voxel_num = 4096
         self.depth_sampling_stride = int(depth_sampling_stride)
-        self._vol = None
         self._eng = geometry.get_engine(device)
         self._vol = self._eng.stsdf_create(self.voxel_length, self.sdf_trunc, int(color_type), self.depth_sampling_stride,
                                            int(map_size))
-
-    def __del__(self):
-        try:
-            self._eng.stsdf_destroy(self._vol)
-        except Exception:
-            pass
-        self._vol = None
-
-    def reset(self):
-        self._eng.stsdf_reset(self._vol)
-
-    def integrate(self, image, intrinsic, extrinsic):
-        """ScalableTSDFVolume::Integrate(RGBDImage, PinholeCameraIntrinsic, extrinsic).  Returns True; a format the
-        reference turns away ([ScalableTSDFVolume::Integrate] Unsupported image format.) is reported, the volume is
-        left as it was and False comes back."""
-        color = None if self.color_type == TSDFVolumeColorType.NoColor else image.color
-        try:
-            if color is None and self.color_type != TSDFVolumeColorType.NoColor:
-                raise MiIcpError("[ScalableTSDFVolume::Integrate] Unsupported image format.")
-            self._eng.stsdf_integrate(self._vol, image.depth, color, intrinsic.width, intrinsic.height, intrinsic.as4(),
-                                      extrinsic)
-        except MiIcpError as e:
-            if "Unsupported image format" not in str(e):
-                raise
-            print("[cupoch_amd] Error: [ScalableTSDFVolume::Integrate] Unsupported image format.")
-            return False
-        return True
-
-    def extract_point_cloud(self):
-        p, n, c = self._eng.stsdf_extract_point_cloud(self._vol, self.color_type != TSDFVolumeColorType.NoColor)
-        return _cloud(p, n, c)
-
-    def extract_voxel_point_cloud(self):
-        p, c = self._eng.stsdf_extract_voxel_point_cloud(self._vol)
-        return _cloud(p, None, c)
 
     def num_volume_units(self):
         """(open units, unit slots allocated)"""

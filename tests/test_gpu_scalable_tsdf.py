@@ -300,14 +300,17 @@ def test_units_without_a_crossing_give_an_empty_surface_cloud():
     assert nv > 0 and len(vol.extract_voxel_point_cloud().points) == nv
 
 
-def test_uniform_volume_agrees_voxel_for_voxel():
-    """the second witness, on the GPU: of the exact scene's 69 units the 63 inside a UniformTSDFVolume of 128^3 equal
-    its voxels at 16*key + 64 bit for bit (tsdf, weight, colour)"""
+@pytest.mark.parametrize("color_type", [tx.NO_COLOR, tx.RGB8, tx.GRAY32], ids=["NoColor", "RGB8", "Gray32"])
+def test_uniform_volume_agrees_voxel_for_voxel(color_type):
+    """the second witness, on the GPU, that the two volumes apply one rule, for every colour type: of the exact scene's
+    69 units (they depend on the depth alone) the 63 inside a UniformTSDFVolume of 128^3 equal its voxels at
+    16*key + 64 bit for bit (tsdf, weight, colour; a NoColor volume reports the starting colour on both sides)"""
     from cupoch_amd import geometry, integration
     d, c, E = exact_scene()
+    c = {tx.NO_COLOR: None, tx.RGB8: c, tx.GRAY32: np.ascontiguousarray(c[..., 0].astype(F))}[color_type]
     K = intrinsic_of("64x48")
-    sv = gpu_volume("dyadic", tx.RGB8, 4)
-    uv = integration.UniformTSDFVolume(2.0, 128, 0.05, integration.TSDFVolumeColorType.RGB8, (0.0, 0.0, 0.0))
+    sv = gpu_volume("dyadic", color_type, 4)
+    uv = integration.UniformTSDFVolume(2.0, 128, 0.05, integration.TSDFVolumeColorType(color_type), (0.0, 0.0, 0.0))
     for _ in range(2):
         assert sv.integrate(geometry.RGBDImage(c, d), K, E) and uv.integrate(geometry.RGBDImage(c, d), K, E)
     keys, t, w, col = sv.get_volume_units()
