@@ -9,12 +9,12 @@ from . import _lib, utility                                    # noqa: F401
 from ._lib import MiIcpError, build                           # noqa: F401
 from .utility import initialize_allocator                     # noqa: F401
 
-__all__ = ["geometry", "registration", "utility", "io", "engine", "distributed", "camera", "kinfu", "odometry", "integration", "integration_scalable", "collision", "planning", "build",
+__all__ = ["geometry", "registration", "utility", "io", "engine", "distributed", "camera", "kinfu", "odometry", "integration", "integration_scalable", "collision", "planning", "imageproc", "build",
            "initialize_allocator", "MiIcpError"]
 
 
 def __getattr__(name):
-    if name in ("geometry", "registration", "io", "engine", "distributed", "camera", "kinfu", "odometry", "integration", "integration_scalable", "collision", "planning"):
+    if name in ("geometry", "registration", "io", "engine", "distributed", "camera", "kinfu", "odometry", "integration", "integration_scalable", "collision", "planning", "imageproc"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

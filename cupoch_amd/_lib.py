@@ -18,7 +18,7 @@ INCLUDE = os.path.join(ROOT, "include")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I/opt/rocm/include"]
 # the library's translation units (csrc/ctx.h says what each holds); compiled side by side, then linked
-UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_stsdf", "mi_occgrid", "mi_voxelgrid", "mi_collision", "mi_graph", "mi_laserscan", "mi_image", "mi_edt", "mi_knn", "mi_comm", "mi_debug"]
+UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_stsdf", "mi_occgrid", "mi_voxelgrid", "mi_collision", "mi_graph", "mi_laserscan", "mi_image", "mi_sgm", "mi_edt", "mi_knn", "mi_comm", "mi_debug"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 MI_ICP_HOST, MI_ICP_DEVICE = 0, 1
@@ -274,6 +274,13 @@ SIGNATURES = {
     "mi_icp_image_move": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "mi_icp_image_depth_format": (_I, [_P, _P, _I, _I, _I, _P]),
     "mi_icp_image_limits": (_I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mi_icp_sgm_create": (_I, [_P, _I, _I, _I, _I, _F, _I, _I, _I, _I, C.POINTER(_P)]),
+    "mi_icp_sgm_destroy": (_I, [_P, _P]),
+    "mi_icp_sgm_process": (_I, [_P, _P, _P, _P, _P]),
+    "mi_icp_sgm_census": (_I, [_P, _P, _I, _I, _P]),
+    "mi_icp_sgm_get_sums": (_I, [_P, _P, _P]),
+    "mi_icp_sgm_limits": (_I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mi_icp_create_from_disparity": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "mi_icp_covariances_from_normals": (_I, [_P, _P, _L, _F, _P, _I]),
     "mi_icp_estimate_normals_knn": (_I, [_P, _P, _L, _I, _P, _I]),
     "mi_icp_estimate_normals_radius": (_I, [_P, _P, _L, _F, _I, _P, _I]),

@@ -205,6 +205,15 @@ public:
                                                            const Eigen::Matrix4f& extrinsic = Eigen::Matrix4f::Identity(),
                                                            bool project_valid_depth_only = true,
                                                            float depth_cutoff = -1.0f, bool compute_normals = false);
+    /// pointcloud_factory.cu:432-482: one point and one colour per pixel of an 8-bit disparity image (as
+    /// imageproc::SemiGlobalMatching makes it) in raster order, none left out; `color` has the same size and 3 channels
+    /// of 1 or 2 bytes (else "[PointCloud::CreateFromDisparity] Unsupported image format." and an empty cloud).  A
+    /// disparity at which w = 0 gives non-finite coordinates: RemoveNoneFinitePoints takes them out.  The arithmetic:
+    /// include/mi_icp.h "stereo".
+    static std::shared_ptr<PointCloud> CreateFromDisparity(const Image& disp, const Image& color,
+                                                           const camera::PinholeCameraIntrinsic& left_intrinsic,
+                                                           const camera::PinholeCameraIntrinsic& right_intrinsic,
+                                                           float baseline);
     /// pointcloud_factory.cu:418-430: the centres of the grid's occupied voxels, every colour (0, 0, 1)
     static std::shared_ptr<PointCloud> CreateFromOccupancyGrid(const OccupancyGrid& occgrid);
     /// pointcloud_factory.cu:375-420: the LIVE scans' readings inside [min_range, max_range] as points in the frame of their

@@ -594,7 +594,87 @@ std::shared_ptr<PointCloud> PointCloud::CreateFromRGBDImage(const RGBDImage& ima
                      1000.0f, 1000.0f, depth_cutoff, 1, true, compute_normals, project_valid_depth_only);
 }
 
+std::shared_ptr<PointCloud> PointCloud::CreateFromDisparity(const Image& disp, const Image& color,
+                                                            const camera::PinholeCameraIntrinsic& left_intrinsic,
+                                                            const camera::PinholeCameraIntrinsic& right_intrinsic,
+                                                            float baseline) {
+    auto out = std::make_shared<PointCloud>();
+    if (!(disp.num_of_channels_ == 1 && disp.bytes_per_channel_ == 1 && disp.width_ == color.width_ &&
+          disp.height_ == color.height_ && color.num_of_channels_ == 3 &&
+          (color.bytes_per_channel_ == 1 || color.bytes_per_channel_ == 2))) {
+        LogError("[PointCloud::CreateFromDisparity] Unsupported image format.");  // pointcloud_factory.cu:479-481
+        return out;
+    }
+    const float tx = -baseline;
+    const auto f = left_intrinsic.GetFocalLength();
+    const auto pl = left_intrinsic.GetPrincipalPoint();
+    const auto pr = right_intrinsic.GetPrincipalPoint();
+    // pointcloud_factory.cu:444-455, every product and difference rounded to float in the order written
+    volatile float q[7];
+    q[0] = f.second * tx;
+    q[1] = -f.second * pl.first;
+    q[1] = q[1] * tx;
+    q[2] = f.first * tx;
+    q[3] = -f.first * pl.second;
+    q[3] = q[3] * tx;
+    q[4] = f.first * f.second;
+    q[4] = q[4] * tx;
+    q[5] = -f.second;
+    q[6] = pl.first - pr.first;
+    q[6] = f.second * q[6];
+    const float qs[7] = {q[0], q[1], q[2], q[3], q[4], q[5], q[6]};
+    const size_t n = (size_t)disp.width_ * (size_t)disp.height_;
+    out->points_.resize(n);
+    out->colors_.resize(n);
+    if (n == 0) return out;
+    Check(mi_icp_create_from_disparity(Engine(), disp.data_.data(), color.data_.data(), disp.width_, disp.height_,
+                                       color.bytes_per_channel_, qs, out->points_.data()->data(), out->colors_.data()->data()));
+    return out;
+}
+
 }  // namespace geometry
+
+// ---------------------------------------------------------------- imageproc
+namespace imageproc {
+
+SemiGlobalMatching::SemiGlobalMatching(const SGMOption& option) : option_(option) {
+    const SGMOption& o = option_;
+    if (o.width_ <= 0 || o.height_ <= 0) {   // (before any engine: no device is needed to be turned away)
+        LogError("[SemiGlobalMatching::SemiGlobalMatching] Invalid SGM parameters: width and height must be positive.");
+        return;
+    }
+    const int rc = mi_icp_sgm_create(Engine(), o.width_, o.height_, o.p1_, o.p2_, o.uniqueness_, (int)o.disp_size_,
+                                     (int)o.path_type_, o.min_disp_, o.lr_max_diff_, &matcher_);
+    if (rc == MI_ICP_ERR_INVALID) {
+        LogError((std::string("[SemiGlobalMatching::SemiGlobalMatching] Invalid SGM parameters: ") + mi_icp_last_error(Engine())).c_str());
+        matcher_ = nullptr;
+        return;
+    }
+    Check(rc);
+}
+
+SemiGlobalMatching::~SemiGlobalMatching() {
+    if (matcher_) (void)mi_icp_sgm_destroy(Engine(), matcher_);
+}
+
+std::shared_ptr<geometry::Image> SemiGlobalMatching::ProcessFrame(const geometry::Image& left, const geometry::Image& right) {
+    auto output = std::make_shared<geometry::Image>();
+    if (!matcher_) {
+        LogError("[SemiGlobalMatching::ProcessFrame] Invalid SGM parameters.");  // sgm.cpp:49-53
+        return output;
+    }
+    if (left.width_ != option_.width_ || left.height_ != option_.height_ || right.width_ != option_.width_ ||
+        right.height_ != option_.height_ || left.num_of_channels_ != 1 || right.num_of_channels_ != 1 ||
+        left.bytes_per_channel_ != 1 || right.bytes_per_channel_ != 1) {
+        LogError("[SemiGlobalMatching::ProcessFrame] Unsupport image type.");  // sgm.cpp:54-60
+        return output;
+    }
+    output->Prepare(left.width_, left.height_, 1, 1);
+    Check(mi_icp_sgm_process(Engine(), matcher_, left.data_.data(), right.data_.data(), output->data_.data()));
+    return output;
+}
+
+}  // namespace imageproc
 
 // ---------------------------------------------------------------- registration
 namespace registration {

@@ -39,6 +39,7 @@
 #include "cupoch/geometry/occupancygrid.h"
 #include "cupoch/geometry/pointcloud.h"
 #include "cupoch/geometry/voxelgrid.h"
+#include "cupoch/imageproc/sgm.h"
 #include "cupoch/integration/scalable_tsdfvolume.h"
 #include "cupoch/integration/uniform_tsdfvolume.h"
 #include "cupoch/knn/kdtree_flann.h"
@@ -1260,7 +1261,11 @@ PYBIND11_MODULE(cupoch_pybind, m) {
                 return out;
             });
     py::reinterpret_borrow<py::class_<geometry::PointCloud, std::shared_ptr<geometry::PointCloud>>>(mg.attr("PointCloud"))
-            .def_static("create_from_laserscanbuffer", &geometry::PointCloud::CreateFromLaserScanBuffer, "scan"_a, "min_range"_a, "max_range"_a);
+            .def_static("create_from_laserscanbuffer", &geometry::PointCloud::CreateFromLaserScanBuffer, "scan"_a, "min_range"_a, "max_range"_a)
+            // geometry/pointcloud.cpp:296-299
+            .def_static("create_from_disparity", &geometry::PointCloud::CreateFromDisparity,
+                        "Factory function to create a pointcloud from a disparity image.", "disp"_a, "color"_a, "left_intrinsic"_a,
+                        "right_intrinsic"_a, "baseline"_a);
 
     // ---------------------------------------------------------------- planning (cupoch_pybind/planning)
     py::module mpl = m.def_submodule("planning");
@@ -1452,6 +1457,35 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             .def_readonly("resolution", &integration::ScalableTSDFVolume::resolution_)
             .def_readonly("volume_unit_voxel_num", &integration::ScalableTSDFVolume::volume_unit_voxel_num_)
             .def_readonly("depth_sampling_stride", &integration::ScalableTSDFVolume::depth_sampling_stride_);
+
+    // ---------------------------------------------------------------- imageproc (cupoch_pybind/imageproc/imageproc.cpp)
+    py::module mip = m.def_submodule("imageproc");
+    py::enum_<imageproc::SGMOption::DisparitySizeType>(mip, "DisparitySizeType")
+            .value("DisparitySize64", imageproc::SGMOption::DisparitySize64)
+            .value("DisparitySize128", imageproc::SGMOption::DisparitySize128)
+            .value("DisparitySize256", imageproc::SGMOption::DisparitySize256)
+            .export_values();
+    py::enum_<imageproc::SGMOption::PathType>(mip, "PathType")
+            .value("ScanPath4", imageproc::SGMOption::ScanPath4)
+            .value("ScanPath8", imageproc::SGMOption::ScanPath8)
+            .export_values();
+    py::class_<imageproc::SGMOption>(mip, "SGMOption", "Parameters for Semi-Global Matching.")
+            .def(py::init<>())
+            .def(py::init<const imageproc::SGMOption&>())
+            .def("__copy__", [](const imageproc::SGMOption& o) { return imageproc::SGMOption(o); })
+            .def("__deepcopy__", [](const imageproc::SGMOption& o, py::dict&) { return imageproc::SGMOption(o); })
+            .def_readwrite("width", &imageproc::SGMOption::width_)
+            .def_readwrite("height", &imageproc::SGMOption::height_)
+            .def_readwrite("p1", &imageproc::SGMOption::p1_)
+            .def_readwrite("p2", &imageproc::SGMOption::p2_)
+            .def_readwrite("uniqueness", &imageproc::SGMOption::uniqueness_)
+            .def_readwrite("disp_size", &imageproc::SGMOption::disp_size_)
+            .def_readwrite("path_type", &imageproc::SGMOption::path_type_)
+            .def_readwrite("min_disp", &imageproc::SGMOption::min_disp_)
+            .def_readwrite("lr_max_diff", &imageproc::SGMOption::lr_max_diff_);
+    py::class_<imageproc::SemiGlobalMatching>(mip, "SemiGlobalMatching", "This class implements Semi-Global Matching algorithm.")
+            .def(py::init([](const imageproc::SGMOption& params) { return new imageproc::SemiGlobalMatching(params); }))
+            .def("process_frame", &imageproc::SemiGlobalMatching::ProcessFrame);
 
 
     // ---------------------------------------------------------------- registration

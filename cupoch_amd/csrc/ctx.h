@@ -15,6 +15,7 @@
 //   mi_graph.hip     geometry::Graph<3> (construct, lattice, edge weights and removal) and its shortest-path search
 //   mi_laserscan.hip geometry::LaserScanBuffer (scans to points, points / depth frames to scans, the two filters)
 //   mi_image.hip     geometry::Image / RGBDImage processing (filters, the pyramid level, bilateral, conversions, moves)
+//   mi_sgm.hip       imageproc::SemiGlobalMatching, PointCloud::CreateFromDisparity
 //   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry,
 //                    RemoveStatisticalOutliers / RemoveRadiusOutliers, ClusterDBSCAN, ComputeISSKeypoints
 //   mi_comm.hip      the ranks' exchange: mailbox, device inboxes, in-library RCCL, self-test and choice
@@ -177,6 +178,8 @@ struct mi_icp_ctx {
     std::vector<mi_icp_occgrid*> occ_grids;
     // ---- geometry::DistanceTransform: the transforms this context made (mi_edt.hip), freed with it ----
     std::vector<mi_icp_dt*> dts;
+    // ---- imageproc::SemiGlobalMatching: the matchers this context made (mi_sgm.hip), freed with it ----
+    std::vector<mi_icp_sgm*> sgm_matchers;
 
     // ---- instrumentation ----
     mi::eng::DevBuf stamps;    // loop.h "where an iteration's time goes" (mi_icp_debug_set_step_stamps)
@@ -554,6 +557,8 @@ struct VgRuns {
 int vg_sort_runs(mi_icp_ctx* c, const int32_t* keys3, int64_t n, VgRuns* r);
 // ---- mi_edt.hip
 void dt_release_all(mi_icp_ctx* c);       // mi_icp_destroy: the transforms of mi_icp_dt_create
+// ---- mi_sgm.hip
+void sgm_release_all(mi_icp_ctx* c);      // mi_icp_destroy: the matchers of mi_icp_sgm_create
 // ---- mi_geometry.hip
 // The points whose flags[0..n) are set, ascending (select.h: exclusive_scan_u32 + select_gather), into out[] (the
 // caller's, staged when mem_kind is MI_ICP_HOST) and their original indices into out_idx (may be null); *m = their

@@ -374,6 +374,7 @@ void mi_icp_destroy(mi_icp_ctx* c) {
     if (c->aux) mi_icp_destroy(c->aux);
     tsdf_release_all(c);
     stsdf_release_all(c);
+    sgm_release_all(c);
     occgrid_release_all(c);
     dt_release_all(c);
     if (c->side) {

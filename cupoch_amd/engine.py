@@ -1464,6 +1464,67 @@ class Engine:
         _lib.load().mi_icp_image_limits(C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
+    # -- stereo (include/mi_icp.h "stereo"; images are contiguous device tensors) ---------------------------
+    def sgm_create(self, width, height, p1=10, p2=120, uniqueness=0.95, disp_size=128, path_type=1, min_disp=0,
+                   lr_max_diff=1):
+        """-> an opaque matcher handle of this engine (mi_icp_sgm_create); invalid options raise MiIcpError (code -1)"""
+        h = C.c_void_p()
+        self._chk(self._L.mi_icp_sgm_create(self._ctx, int(width), int(height), int(p1), int(p2), float(uniqueness),
+                                            int(disp_size), int(path_type), int(min_disp), int(lr_max_diff), C.byref(h)))
+        return h
+
+    def sgm_destroy(self, matcher):
+        if getattr(self, "_ctx", None) and matcher:
+            self._chk(self._L.mi_icp_sgm_destroy(self._ctx, matcher))
+
+    def _gray8(self, t, what):
+        h, w, ch, b = self._image_dims(t)
+        if (ch, b) != (1, 1) or t.dim() != 2:
+            raise TypeError("%s takes a 1 x uint8 image" % what)
+        return h, w
+
+    def sgm_process(self, matcher, left, right):
+        """SemiGlobalMatching::ProcessFrame: two [H, W] uint8 images of the matcher's size -> the disparity image"""
+        self._gray8(left, "sgm_process")
+        self._gray8(right, "sgm_process")
+        out = torch.empty_like(left)
+        self._chk(self._L.mi_icp_sgm_process(self._ctx, matcher, self._ptr(left), self._ptr(right), self._ptr(out)))
+        return out
+
+    def sgm_census(self, src):
+        """[H, W] uint8 -> the census words, [H, W] int32 holding the unsigned words' bits"""
+        h, w = self._gray8(src, "sgm_census")
+        out = torch.empty((h, w), dtype=torch.int32, device=src.device)
+        self._chk(self._L.mi_icp_sgm_census(self._ctx, self._ptr(src), w, h, self._ptr(out)))
+        return out
+
+    def sgm_get_sums(self, matcher, width, height, disp_size):
+        """S of the matcher's last frame -> [H, W, D] uint16"""
+        out = torch.empty((int(height), int(width), int(disp_size)), dtype=torch.uint16, device=torch.device("cuda", self.device))
+        self._chk(self._L.mi_icp_sgm_get_sums(self._ctx, matcher, self._ptr(out)))
+        return out
+
+    @staticmethod
+    def sgm_limits():
+        """-> (the largest image side, the largest p2)"""
+        a, b = C.c_int32(0), C.c_int32(0)
+        _lib.load().mi_icp_sgm_limits(C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
+    def create_from_disparity(self, disp, color, q):
+        """PointCloud::CreateFromDisparity: disp [H, W] uint8, color [H, W, 3] uint8 or uint16 (device tensors), q the
+        seven float32 of include/mi_icp.h -> (points [H * W, 3], colors [H * W, 3]) device tensors"""
+        h, w = self._gray8(disp, "create_from_disparity")
+        ch, cw, cc, cb = self._image_dims(color)
+        if (ch, cw, cc) != (h, w, 3) or cb not in (1, 2):
+            raise TypeError("create_from_disparity takes a colour image of the disparity's size, 3 x uint8 or 3 x uint16")
+        q = np.ascontiguousarray(np.asarray(q, np.float32).reshape(7))
+        pts = torch.empty((h * w, 3), dtype=torch.float32, device=disp.device)
+        col = torch.empty((h * w, 3), dtype=torch.float32, device=disp.device)
+        self._chk(self._L.mi_icp_create_from_disparity(self._ctx, self._ptr(disp), self._ptr(color), w, h, cb,
+                                                       q.ctypes.data_as(C.c_void_p), self._ptr(pts), self._ptr(col)))
+        return pts, col
+
     def compute_rgbd_odometry(self, source_color, source_depth, target_color, target_depth, intrinsic4,
                               odo_init=None, jacobian=1, iterations=(20, 10, 5), max_depth_diff=0.03,
                               min_depth=0.0, max_depth=4.0, weighted=False, prev_twist=None, nu=5.0,

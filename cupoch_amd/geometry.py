@@ -18,7 +18,8 @@ LaserScanBuffer mirrors geometry/laserscanbuffer.h (python surface src/python/cu
 with PointCloud.create_from_laserscanbuffer; not built: file I/O and visualisation.
 Image / RGBDImage mirror geometry/image.h and geometry/rgbdimage.h (python surface
 src/python/cupoch_pybind/geometry/image.cpp): filters, bilateral filter, pyramids, format conversions and the RGB-D
-factories; not built: Image.FloatValueAt, image file I/O, PointCloud.create_from_disparity."""
+factories, and PointCloud.create_from_disparity for the disparity image of cupoch_amd.imageproc; not built:
+Image.FloatValueAt, image file I/O."""
 import enum
 import sys
 
@@ -841,7 +842,39 @@ def _create_from_rgbd_image(image, intrinsic, extrinsic=None, project_valid_dept
     return out
 
 
+def disparity_q(left_intrinsic, right_intrinsic, baseline):
+    """the seven entries {q00, q03, q11, q13, q23, q32, q33} of CreateFromDisparity's matrix (pointcloud_factory.cu:444-455),
+    formed in fp32 from left to right"""
+    F = np.float32
+    (fx, fy), (cx, cy) = [tuple(F(v) for v in pair) for pair in (left_intrinsic.get_focal_length(), left_intrinsic.get_principal_point())]
+    cxr = F(right_intrinsic.get_principal_point()[0])
+    tx = -F(baseline)
+    return np.array([fy * tx, -fy * cx * tx, fx * tx, -fx * cy * tx, fx * fy * tx, -fy, fy * (cx - cxr)], F)
+
+
+def _create_from_disparity(disp, color, left_intrinsic, right_intrinsic, baseline):
+    """PointCloud::CreateFromDisparity (pointcloud_factory.cu:432-482): one point and one colour per pixel in raster
+    order, nothing left out -- a disparity at which w = 0 gives non-finite coordinates (remove_none_finite_points takes
+    them out).  disp 1 x uint8, color the same size with 3 channels of uint8 or uint16; anything else is logged and
+    gives an empty cloud."""
+    disp, color = (x if isinstance(x, Image) else Image(x) for x in (disp, color))
+    out = PointCloud()
+    if not (disp._is(1, 1) and (color._is(3, 1) or color._is(3, 2)) and (disp.width, disp.height) == (color.width, color.height)):
+        print("[cupoch_amd] Error: [PointCloud::CreateFromDisparity] Unsupported image format.")
+        return out
+    eng, d = disp._staged()
+    c = color.data
+    if not (_is_torch(c) and c.is_cuda):
+        c = torch.from_numpy(np.ascontiguousarray(c.detach().numpy() if _is_torch(c) else np.asarray(c))).to(d.device)
+    p, col = eng.create_from_disparity(d.reshape(disp.height, disp.width), c.contiguous(),
+                                       disparity_q(left_intrinsic, right_intrinsic, baseline))
+    out._points = utility.Vector3fVector(p)
+    out._colors = utility.Vector3fVector(col)
+    return out
+
+
 PointCloud.create_from_depth_image = staticmethod(_create_from_depth_image)
+PointCloud.create_from_disparity = staticmethod(_create_from_disparity)
 PointCloud.create_from_rgbd_image = staticmethod(_create_from_rgbd_image)
 
 

@@ -1526,6 +1526,66 @@ MI_ICP_API int mi_icp_image_depth_format(mi_icp_ctx* ctx, const uint16_t* src, i
 /* the longest filter and the largest bilateral radius taken (no context, no device) */
 MI_ICP_API int mi_icp_image_limits(int32_t* max_taps, int32_t* max_diameter);
 
+/* ---- stereo (imageproc/sgm.{h,cpp}: imageproc::SemiGlobalMatching; pointcloud_factory.cu:432-482:
+ * ---- PointCloud::CreateFromDisparity) ----
+ * Semi-global matching after Hirschmueller: two rectified 8-bit images in, one 8-bit disparity image out.  The
+ * reference wraps libSGM, whose sources its checkout does not hold; the contract below is this library's own, with
+ * exactly the parameters of the reference's SGMOption, and tests/sgm_exact.py restates it in numpy.  Every step up to
+ * the disparity image is integer arithmetic, so results are the same bytes on every run.  Images are [height][width]
+ * in DEVICE memory (no mem_kind: a surface stages host pixels itself); no call here waits for the stream.
+ *  mi_icp_sgm_create  a matcher for width x height frames; all of its workspace (two census planes, 4 or 8 path
+ *   volumes of width * height * disp_size bytes, the two maps) is allocated here, a frame allocates nothing.  Turned
+ *   away with MI_ICP_ERR_INVALID: width or height outside [1, MI_ICP_SGM_MAX_SIDE]; not 0 <= p1 <= p2 <=
+ *   MI_ICP_SGM_MAX_P2 (the bound keeps every path cost within a byte); disp_size not 64, 128 or 256; path_type not
+ *   MI_ICP_SGM_PATH4 / MI_ICP_SGM_PATH8; min_disp < 0 or min_disp + disp_size > 256.  MI_ICP_ERR_HIP: no memory.
+ *   A matcher belongs to its context and is freed with it at the latest.
+ *  mi_icp_sgm_process  left, right, dst: width * height bytes each, dst another buffer than the inputs.  With D =
+ *   disp_size, H x W images, row y, column x:
+ *   1 census  (mi_icp_sgm_census computes this alone) the window offsets (dy, dx), dy = -3 .. 3 outer, dx = -4 .. 4
+ *     inner; bit k (bit 0 first) of the word is I(y + dy, x + dx) > I(y - dy, x - dx) for the k-th of the 31 offsets
+ *     before the centre; bit 31 clear; the word is 0 where the window leaves the image (rows < 3 or >= H - 3, columns
+ *     < 4 or >= W - 4).
+ *   2 cost  C(y, x, d) = popcount(cenL(y, x) xor cenR(y, x - d - min_disp)), d = 0 .. D - 1, cenR = 0 left of the image.
+ *   3 paths  directions r = (dy, dx): (0,1), (0,-1), (1,0), (-1,0) and, with MI_ICP_SGM_PATH8, (1,1), (1,-1), (-1,1),
+ *     (-1,-1).  L_r(p, d) = C(p, d) where p - r lies outside the image (a diagonal that reaches a side border starts
+ *     anew); else, with m = min_k L_r(p - r, k), L_r(p, d) = C(p, d) + min(L_r(p - r, d), L_r(p - r, d - 1) + p1,
+ *     L_r(p - r, d + 1) + p1, m + p2) - m, the d - 1 and d + 1 terms dropped outside 0 .. D - 1.  S = sum_r L_r
+ *     (mi_icp_sgm_get_sums: S of the last frame as uint16 [y][x][d]; MI_ICP_ERR_STATE before the first frame).
+ *   4 left map (uint16, invalid 0xFFFF)  dL = argmin_d S(y, x, d), the smallest d of equals, s1 that minimum, s2 =
+ *     min S(y, x, d) over |d - dL| > 1; invalid where (float)uniqueness * (float)s2 < (float)s1 (one fp32 product).
+ *   5 right map  dR(y, x) = argmin_d S(y, x + d + min_disp, d) over the d with x + d + min_disp < W, the smallest d of
+ *     equals, 0 where there is none; no uniqueness test.
+ *   6 median  both maps, 3 x 3, on the unsigned 16-bit values (invalid sorts high); the outermost rows and columns,
+ *     and a map with H < 3 or W < 3, are copied.
+ *   7 check  a left value d != 0xFFFF is valid iff lr_max_diff < 0, or k = x - (d + min_disp) >= 0 and
+ *     |dR(y, k) - d| <= lr_max_diff (the medianed maps).  dst = (uint8)(d + min_disp) where valid, else
+ *     (uint8)(min_disp - 1): 255 at min_disp 0 -- at D = 256 that value is a disparity as well as the invalid mark.
+ *  mi_icp_create_from_disparity  disp width * height bytes, color the same size with 3 channels of bytes_per_channel
+ *   (1 or 2, else MI_ICP_ERR_INVALID) bytes; q the HOST array {q00, q03, q11, q13, q23, q32, q33} (with tx = -baseline:
+ *   fy * tx, -fy * cx * tx, fx * tx, -fx * cy * tx, fx * fy * tx, -fy, fy * (cx - cx_right), formed by the caller in
+ *   fp32, left to right).  points and colors: width * height * 3 floats, pixel after pixel, none left out.  Pixel
+ *   (u, v) of disparity d: w = q32 * d + q33, r = (float)(1.0 / (double)w), point = ((q00 * u + q03) * r,
+ *   (q11 * v + q13) * r, q23 * r), every operation one fp32 rounding, nothing fused; w = 0 gives non-finite
+ *   coordinates, which are kept.  Colour channel value / 255.0f or value / 65535.0f.  (The reference reads the colour
+ *   through a byte's VALUE as an address; this reads the channel stored at that place.) */
+#define MI_ICP_SGM_MAX_SIDE 8192
+#define MI_ICP_SGM_MAX_P2 224
+#define MI_ICP_SGM_PATH4 0
+#define MI_ICP_SGM_PATH8 1
+typedef struct mi_icp_sgm mi_icp_sgm;
+MI_ICP_API int mi_icp_sgm_create(mi_icp_ctx* ctx, int width, int height, int p1, int p2, float uniqueness,
+                                 int disp_size, int path_type, int min_disp, int lr_max_diff, mi_icp_sgm** out);
+MI_ICP_API int mi_icp_sgm_destroy(mi_icp_ctx* ctx, mi_icp_sgm* matcher);
+MI_ICP_API int mi_icp_sgm_process(mi_icp_ctx* ctx, mi_icp_sgm* matcher, const uint8_t* left, const uint8_t* right,
+                                  uint8_t* dst);
+MI_ICP_API int mi_icp_sgm_census(mi_icp_ctx* ctx, const uint8_t* src, int width, int height, uint32_t* dst);
+MI_ICP_API int mi_icp_sgm_get_sums(mi_icp_ctx* ctx, mi_icp_sgm* matcher, uint16_t* dst);
+/* the largest image side and the largest p2 taken (no context, no device) */
+MI_ICP_API int mi_icp_sgm_limits(int32_t* max_side, int32_t* max_p2);
+MI_ICP_API int mi_icp_create_from_disparity(mi_icp_ctx* ctx, const uint8_t* disp, const void* color, int width,
+                                            int height, int bytes_per_channel, const float* q, float* points,
+                                            float* colors);
+
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
  * float[nq][3] against the cloud given to mi_icp_set_target: per query the knn
