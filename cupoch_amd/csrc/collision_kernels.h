@@ -12,7 +12,8 @@
 // x-major order visits a sorted VoxelGrid's indices and an occupancy grid's linear indices ascending, so the first slab
 // (the first cell) with a hit ends the work; a VoxelGrid that came unsorted is searched through its sorted copy and
 // perm[], and then the minimum of perm over all hits is taken.  Every kernel writes hit[i]: the other side's index or -1;
-// flags + the scan + col_emit_pairs compact them.  No atomics, no scratch arrays.
+// flags + the scan + col_emit_pairs compact them.  No atomics.  The code object reports 28 bytes of
+// scratch per lane for col_prims_grid, col_cells_prims and col_voxelize_flags, and none for every other kernel here.
 #pragma once
 #include "collision_predicates.h"
 #include "device_utils.h"
@@ -30,14 +31,14 @@ struct ColGrid {           // the side that is searched
     int res, h;
     int b[6];              // the bounds box, inclusive, as grid indices
     float thres;
-    float vs, origin[3];
+    GridFrame f;
 };
 
 struct ColCells {  // the enumerated voxels: keys[n][3]; res > 0: they are occupancy-grid indices, key = index - h
     const int32_t* keys;
     int64_t n;
     int res, h;
-    float vs, origin[3];
+    GridFrame f;
 };
 
 constexpr int32_t kColNone = 0x7fffffff;
@@ -52,42 +53,15 @@ __device__ __forceinline__ void col_key_span(const ColGrid& G, int a, int32_t* k
     }
 }
 
-// the first position whose key is not less than (x, y, z)
-__device__ __forceinline__ int64_t col_lower(const int32_t* __restrict__ keys, int64_t m, int32_t x, int32_t y, int32_t z) {
-    int64_t lo = 0, hi = m;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (vg_key_less(keys + mid * 3, x, y, z)) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// the first position whose key is greater than (x, y, z)
-__device__ __forceinline__ int64_t col_upper(const int32_t* __restrict__ keys, int64_t m, int32_t x, int32_t y, int32_t z) {
-    int64_t lo = 0, hi = m;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        const int32_t* k = keys + mid * 3;
-        const bool greater = k[0] != x ? k[0] > x : (k[1] != y ? k[1] > y : k[2] > z);
-        if (greater) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
 // the smallest x >= x0 that a key of a VoxelGrid has; above every key: none (an occupancy grid has every x)
 __device__ __forceinline__ int64_t col_next_x(const ColGrid& G, int64_t x0) {
     if (G.occ) return x0;
     if (x0 > INT32_MAX) return (int64_t)INT32_MAX + 1;
-    const int64_t p = col_lower(G.keys, G.m, (int32_t)x0, INT32_MIN, INT32_MIN);
+    const int64_t p = keys3_lower(G.keys, G.m, (int32_t)x0, INT32_MIN, INT32_MIN);
     return p < G.m ? (int64_t)G.keys[p * 3] : (int64_t)INT32_MAX + 1;
 }
 
-__device__ __forceinline__ bool col_occupied(const ColGrid& G, int64_t idx) {
-    const float p = G.prob[idx];
-    return !isnan(p) && p > G.thres;
-}
+__device__ __forceinline__ bool col_occupied(const ColGrid& G, int64_t idx) { return occupied(G.prob[idx], G.thres); }
 
 __device__ __forceinline__ int32_t col_wave_min_all(int32_t v) {
 #pragma unroll
@@ -96,12 +70,12 @@ __device__ __forceinline__ int32_t col_wave_min_all(int32_t v) {
 }
 
 __device__ __forceinline__ void col_cell_box(const ColGrid& G, int32_t x, int32_t y, int32_t z, float* lo, float* hi) {
-    lo[0] = col::cell_lo(x, G.vs, G.origin[0]);
-    hi[0] = col::cell_hi(x, G.vs, G.origin[0]);
-    lo[1] = col::cell_lo(y, G.vs, G.origin[1]);
-    hi[1] = col::cell_hi(y, G.vs, G.origin[1]);
-    lo[2] = col::cell_lo(z, G.vs, G.origin[2]);
-    hi[2] = col::cell_hi(z, G.vs, G.origin[2]);
+    lo[0] = col::cell_lo(x, G.f.vs, G.f.origin[0]);
+    hi[0] = col::cell_hi(x, G.f.vs, G.f.origin[0]);
+    lo[1] = col::cell_lo(y, G.f.vs, G.f.origin[1]);
+    hi[1] = col::cell_hi(y, G.f.vs, G.f.origin[1]);
+    lo[2] = col::cell_lo(z, G.f.vs, G.f.origin[2]);
+    hi[2] = col::cell_hi(z, G.f.vs, G.f.origin[2]);
 }
 
 // ---- voxels against a grid: the cell-cell predicate is the candidate range itself, so every cell present in it is a hit
@@ -112,17 +86,17 @@ static __global__ __launch_bounds__(256) void col_cells_grid(ColCells E, ColGrid
     bool empty = false;
     for (int a = 0; a < 3; ++a) {
         const int32_t k = E.keys[i * 3 + a] - (E.res > 0 ? E.h : 0);
-        const float alo = col::cell_lo(k, E.vs, E.origin[a]) - margin, ahi = col::cell_hi(k, E.vs, E.origin[a]) + margin;
+        const float alo = col::cell_lo(k, E.f.vs, E.f.origin[a]) - margin, ahi = col::cell_hi(k, E.f.vs, E.f.origin[a]) + margin;
         int32_t klo, khi;
         col_key_span(G, a, &klo, &khi);
-        col::cell_range(alo, ahi, G.vs, G.origin[a], klo, khi, &r0[a], &r1[a]);
+        col::cell_range(alo, ahi, G.f.vs, G.f.origin[a], klo, khi, &r0[a], &r1[a]);
         empty = empty || r0[a] > r1[a];
     }
     int32_t best = kColNone;
     if (!empty && G.occ) {
         for (int32_t x = r0[0]; x <= r1[0] && best == kColNone; ++x)
             for (int32_t y = r0[1]; y <= r1[1] && best == kColNone; ++y) {
-                const int64_t row = ((int64_t)(x + G.h) * G.res + (y + G.h)) * G.res + G.h;
+                const int64_t row = cube_index(G.res, x + G.h, y + G.h, G.h);
                 for (int32_t z = r0[2]; z <= r1[2]; ++z)
                     if (col_occupied(G, row + z)) {
                         best = (int32_t)(row + z);
@@ -130,8 +104,8 @@ static __global__ __launch_bounds__(256) void col_cells_grid(ColCells E, ColGrid
                     }
             }
     } else if (!empty) {
-        const int64_t p0 = col_lower(G.keys, G.m, r0[0], r0[1], r0[2]);
-        const int64_t p1 = col_upper(G.keys, G.m, r1[0], r1[1], r1[2]);
+        const int64_t p0 = keys3_lower(G.keys, G.m, r0[0], r0[1], r0[2]);
+        const int64_t p1 = keys3_upper(G.keys, G.m, r1[0], r1[1], r1[2]);
         // fewer voxels between the corners than a search per column would cost: walk them.  (cols below 2^28 each
         // before they are multiplied, so no product overflows whatever the key extents)
         const int64_t nx = (int64_t)r1[0] - r0[0] + 1, ny = (int64_t)r1[1] - r0[1] + 1, cols = (p1 - p0 + 7) >> 3;
@@ -148,7 +122,7 @@ static __global__ __launch_bounds__(256) void col_cells_grid(ColCells E, ColGrid
         } else {
             for (int32_t x = r0[0]; x <= r1[0]; ++x) {
                 for (int32_t y = r0[1]; y <= r1[1]; ++y) {
-                    for (int64_t p = col_lower(G.keys, G.m, x, y, r0[2]); p < G.m; ++p) {
+                    for (int64_t p = keys3_lower(G.keys, G.m, x, y, r0[2]); p < G.m; ++p) {
                         if (G.keys[p * 3] != x || G.keys[p * 3 + 1] != y || G.keys[p * 3 + 2] > r1[2]) break;
                         best = min(best, G.perm ? (int32_t)G.perm[p] : (int32_t)p);
                         if (!G.perm) break;
@@ -174,7 +148,7 @@ __device__ __forceinline__ int32_t col_slab_min(const ColGrid& G, int lane, int3
         const int64_t nz = (int64_t)z1 - z0 + 1, cnt = ((int64_t)y1 - y0 + 1) * nz;
         for (int64_t t = lane; t < cnt; t += 64) {
             const int32_t y = y0 + (int32_t)(t / nz), z = z0 + (int32_t)(t % nz);
-            const int64_t idx = ((int64_t)(x + G.h) * G.res + (y + G.h)) * G.res + (z + G.h);
+            const int64_t idx = cube_index(G.res, x + G.h, y + G.h, z + G.h);
             if (!col_occupied(G, idx)) continue;
             col_cell_box(G, x, y, z, lo, hi);
             if (pred(lo, hi)) {
@@ -183,7 +157,7 @@ __device__ __forceinline__ int32_t col_slab_min(const ColGrid& G, int lane, int3
             }
         }
     } else {
-        const int64_t p0 = col_lower(G.keys, G.m, x, y0, z0), p1 = col_upper(G.keys, G.m, x, y1, z1);
+        const int64_t p0 = keys3_lower(G.keys, G.m, x, y0, z0), p1 = keys3_upper(G.keys, G.m, x, y1, z1);
         for (int64_t p = p0 + lane; p < p1; p += 64) {
             const int32_t y = G.keys[p * 3 + 1], z = G.keys[p * 3 + 2];
             if (z < z0 || z > z1) continue;
@@ -202,7 +176,7 @@ __device__ __forceinline__ bool col_axis_range(const ColGrid& G, int a, float bl
     int32_t klo, khi;
     col_key_span(G, a, &klo, &khi);
     if (klo > khi) return false;
-    col::cell_range(blo, bhi, G.vs, G.origin[a], klo, khi, k0, k1);
+    col::cell_range(blo, bhi, G.f.vs, G.f.origin[a], klo, khi, k0, k1);
     return *k0 <= *k1;
 }
 
@@ -219,7 +193,7 @@ static __global__ __launch_bounds__(256) void col_lines_grid(const float* __rest
     float s[3];
     int32_t klo[3], khi[3], r0[3], r1[3], k0[3], k1[3];
     for (int a = 0; a < 3; ++a) col_key_span(G, a, &klo[a], &khi[a]);
-    if (col::segment_cells(p0, p1, margin, G.vs, G.origin, klo, khi, s, r0, r1)) {
+    if (col::segment_cells(p0, p1, margin, G.f.vs, G.f.origin, klo, khi, s, r0, r1)) {
         auto pred = [&](const float* lo, const float* hi) {
             const float ilo[3] = {lo[0] - margin, lo[1] - margin, lo[2] - margin};
             const float ihi[3] = {hi[0] + margin, hi[1] + margin, hi[2] + margin};
@@ -227,7 +201,7 @@ static __global__ __launch_bounds__(256) void col_lines_grid(const float* __rest
         };
         // slab by slab, over the x a VoxelGrid has keys at: the cost follows the voxels that exist, not the extents
         for (int64_t x = col_next_x(G, r0[0]); x <= r1[0]; x = col_next_x(G, x + 1)) {
-            if (!col::segment_slab_cells(p0, p1, margin, s, G.vs, G.origin, (int32_t)x, r0, r1, k0, k1)) continue;
+            if (!col::segment_slab_cells(p0, p1, margin, s, G.f.vs, G.f.origin, (int32_t)x, r0, r1, k0, k1)) continue;
             best = min(best, col_slab_min(G, lane, (int32_t)x, k0[1], k1[1], k0[2], k1[2], pred));
             if (!G.perm && best != kColNone) break;
         }
@@ -250,7 +224,7 @@ static __global__ __launch_bounds__(256) void col_prims_grid(const mi_icp_primit
     int32_t r0[3], r1[3];
     if (live) {
         float blo[3], bhi[3];
-        col::primitive_reach(P, margin, G.vs, blo, bhi);
+        col::primitive_reach(P, margin, G.f.vs, blo, bhi);
         for (int a = 0; a < 3 && live; ++a) live = col_axis_range(G, a, blo[a], bhi[a], &r0[a], &r1[a]);
     }
     if (live) {
@@ -298,8 +272,8 @@ static __global__ __launch_bounds__(256) void col_cells_prims(ColCells E, const 
     float lo[3], hi[3];
     for (int a = 0; a < 3; ++a) {
         const int32_t k = E.keys[i * 3 + a] - (E.res > 0 ? E.h : 0);
-        lo[a] = col::cell_lo(k, E.vs, E.origin[a]);
-        hi[a] = col::cell_hi(k, E.vs, E.origin[a]);
+        lo[a] = col::cell_lo(k, E.f.vs, E.f.origin[a]);
+        hi[a] = col::cell_hi(k, E.f.vs, E.f.origin[a]);
     }
     int32_t best = -1;
     for (int64_t j = 0; j < np; ++j) {
@@ -343,32 +317,10 @@ static __global__ __launch_bounds__(256) void col_emit_pairs(const int32_t* __re
                                                             int32_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || hit[i] < 0) return;
-    const int32_t me = occ_index ? (int32_t)(((int64_t)occ_index[i * 3] * res + occ_index[i * 3 + 1]) * res + occ_index[i * 3 + 2]) : (int32_t)i;
+    const int32_t me = occ_index ? (int32_t)cube_index(res, occ_index[i * 3], occ_index[i * 3 + 1], occ_index[i * 3 + 2]) : (int32_t)i;
     const int64_t p = pos[i];
     out[p * 2] = enumerated_first ? me : hit[i];
     out[p * 2 + 1] = enumerated_first ? hit[i] : me;
-}
-
-// the flagged voxels of an occupancy grid's bounds box as index triples, ascending
-static __global__ __launch_bounds__(256) void col_occ_list(int x0, int y0, int z0, int ey, int ez, int64_t count,
-                                                          const uint32_t* __restrict__ flags, const uint32_t* __restrict__ pos,
-                                                          int32_t* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= count || !flags[t]) return;
-    const int64_t eyz = (int64_t)ey * ez, p = pos[t];
-    out[p * 3] = x0 + (int32_t)(t / eyz);
-    out[p * 3 + 1] = y0 + (int32_t)((t % eyz) / ez);
-    out[p * 3 + 2] = z0 + (int32_t)(t % ez);
-}
-
-static __global__ __launch_bounds__(256) void col_occ_flags(const float* __restrict__ prob, int res, int x0, int y0, int z0, int ey, int ez,
-                                                           int64_t count, float thres, uint32_t* __restrict__ flags) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= count) return;
-    const int64_t eyz = (int64_t)ey * ez;
-    const int x = x0 + (int)(t / eyz), y = y0 + (int)((t % eyz) / ez), z = z0 + (int)(t % ez);
-    const float p = prob[((int64_t)x * res + y) * res + z];
-    flags[t] = (!isnan(p) && p > thres) ? 1u : 0u;
 }
 
 // the caller's index of every distinct sorted key: the first of its run in the stable order

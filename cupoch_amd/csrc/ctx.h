@@ -37,6 +37,7 @@
 #include "../../include/mi_icp.h"
 #include "../../include/mi_icp_debug.h"
 #include "device_utils.h"
+#include "grid_rules.h"
 #include "host_solver.h"
 #include "loop.h"
 #include "loop_policy.h"
@@ -389,22 +390,78 @@ inline int check_ctx(mi_icp_ctx* c, int mem_kind, const char* what) {
     return MI_ICP_OK;
 }
 
-// Is the handle `h` (a volume, a grid, a transform) one that context c made and still holds in `list`?  The caller has
-// the message for a handle that is not.
+// ---- The life of a handle (a volume, a grid, a distance transform, a matcher): a struct with an `owner` and a member
+// ---- free_buffers(), kept in the list of the context that made it and freed with that context at the latest.
+// Is `h` one that context c made and still holds in `list`?  `noun` names the kind in the message.  (The list is looked
+// at first: a handle that is not in it may have been destroyed, and is not read.)
 template <class T>
-bool owned(const mi_icp_ctx* c, const T* h, const std::vector<T*>& list) {
-    return h && h->owner == c && std::find(list.begin(), list.end(), h) != list.end();
+int handle_check(mi_icp_ctx* c, const T* h, const std::vector<T*>& list, const char* what, const char* noun) {
+    if (!h || std::find(list.begin(), list.end(), h) == list.end() || h->owner != c)
+        return fail(c, MI_ICP_ERR_INVALID, "%s: not a %s of this context", what, noun);
+    return MI_ICP_OK;
+}
+
+// out of the list and deleted; its buffers are the caller's business
+template <class T>
+void handle_drop(T* h, std::vector<T*>& list) {
+    list.erase(std::find(list.begin(), list.end(), h));
+    delete h;
+}
+
+// the destroy entry point: a null handle is fine; work in flight may still use the buffers, so the stream is waited for
+template <class T>
+int handle_destroy(mi_icp_ctx* c, T* h, std::vector<T*>& list, const char* what, const char* noun) {
+    TRY(check_ctx(c));
+    if (!h) return MI_ICP_OK;
+    TRY(handle_check(c, h, list, what, noun));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    h->free_buffers();
+    handle_drop(h, list);
+    return MI_ICP_OK;
+}
+
+template <class T>
+void handle_release_all(std::vector<T*>& list) {
+    for (T* h : list) {
+        h->free_buffers();
+        delete h;
+    }
+    list.clear();
+}
+
+// ---- The argument checks the entry points share.  An entry point makes each check where its contract places it: the
+// ---- order is part of the interface.
+constexpr int64_t kMaxCount = 0x7fffff00ll;  // positions and counts are 32-bit
+
+inline int count_ok(mi_icp_ctx* c, const char* what, int64_t n) {
+    if (n < 0 || n > kMaxCount) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    return MI_ICP_OK;
+}
+
+inline bool finite3(const float* v) { return v && mi::finite3(v[0], v[1], v[2]); }
+
+// a grid's frame at the time of a call -> *f
+inline int frame_check(mi_icp_ctx* c, const char* what, float voxel_size, const float* origin3, GridFrame* f) {
+    if (!(voxel_size > 0.0f) || !std::isfinite(voxel_size) || !finite3(origin3))
+        return fail(c, MI_ICP_ERR_INVALID, "%s: voxel_size must be positive and finite, the origin finite", what);
+    f->vs = voxel_size;
+    for (int k = 0; k < 3; ++k) f->origin[k] = origin3[k];
+    return MI_ICP_OK;
+}
+
+inline int resolution_ok(mi_icp_ctx* c, const char* what, int resolution, int max) {
+    if (resolution < 2 || resolution > max) return fail(c, MI_ICP_ERR_INVALID, "%s: the resolution must be in [2, %d]", what, max);
+    return MI_ICP_OK;
 }
 
 // ---- What the cloud-in, cloud-out entry points share.  A cloud is three arrays: points, normals, colours (the last two
-// ---- optional).  An entry point makes each check where its contract places it: the order is part of the interface.
-// Sizes: the context and the memory kind, m (zeroed from here on), 0 <= n <= 0x7fffff00 (positions and counts are 32-bit).
+// ---- optional).
+// Sizes: the context and the memory kind, m (zeroed from here on), 0 <= n <= kMaxCount.
 inline int check_sizes(mi_icp_ctx* c, const char* what, int64_t n, int64_t* m, int mem_kind) {
     TRY(check_ctx(c, mem_kind, what));
     if (!m) return fail(c, MI_ICP_ERR_INVALID, "%s: m is null", what);
     *m = 0;
-    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
-    return MI_ICP_OK;
+    return count_ok(c, what, n);
 }
 
 struct Cloud {
@@ -547,6 +604,11 @@ void stsdf_release_all(mi_icp_ctx* c);    // mi_icp_destroy: the volumes of mi_i
 void occgrid_release_all(mi_icp_ctx* c);  // mi_icp_destroy: the grids of mi_icp_occgrid_create
 // a grid's log-odds plane, resolution and inclusive bounds (min[3], max[3]) for a reader on the device
 int occgrid_view(mi_icp_ctx* c, const mi_icp_occgrid* o, const char* what, const float** prob, int* resolution, int* bounds6);
+// The listing of a grid's voxels, ascending linear index.  occgrid_select: those of the bounds box that `which`
+// (MI_ICP_OCCGRID_*) selects at threshold `thres`; their flags and positions stay in c->flags and c->dense_idx, *count is
+// their number (one wait).  occgrid_gather, while those stand: their indices and, where asked for, log-odds and points.
+int occgrid_select(mi_icp_ctx* c, const mi_icp_occgrid* o, int which, float thres, int64_t* count);
+int occgrid_gather(mi_icp_ctx* c, const mi_icp_occgrid* o, const GridFrame& f, int32_t* out_index, float* out_prob_log, float* out_xyz);
 // ---- mi_voxelgrid.hip
 struct VgRuns {
     const uint32_t* order = nullptr;      // sorted position -> entry of keys3

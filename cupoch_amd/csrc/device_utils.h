@@ -156,6 +156,27 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
     return v;
 }
+// ... of integers, and their sum: the result is in lane 0
+__device__ __forceinline__ int32_t wave_min(int32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_down(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ int32_t wave_max(int32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_down(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_down((int)v, o, 64));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_add(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
 
 // Workgroups are dealt to XCDs round-robin (block b -> XCD b % 8).  Remap so
 // that each XCD walks one contiguous eighth of the (Morton-ordered) work list

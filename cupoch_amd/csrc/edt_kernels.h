@@ -18,6 +18,7 @@
 #pragma once
 #include "device_utils.h"
 #include "edt_envelope.h"
+#include "grid_rules.h"
 
 namespace mi {
 
@@ -33,23 +34,14 @@ struct EdtGrid {
     int res, h_res;
 };
 
-struct EdtFrame {  // voxel_size_ and origin_ at the time of the call
-    float vs;
-    float origin[3];
-};
-
 __device__ __forceinline__ uint32_t edt_pack(int x, int y, int z) { return (uint32_t)x | ((uint32_t)y << 10) | ((uint32_t)z << 20); }
 __device__ __forceinline__ int edt_field(uint32_t w, int k) { return (int)((w >> (10 * k)) & 1023u); }
-__device__ __forceinline__ int edt_floor_int(float x) { return (int)fminf(fmaxf(floorf(x), -1.0e9f), 1.0e9f); }
-__device__ __forceinline__ bool edt_inside(int res, int x, int y, int z) {
-    return x >= 0 && x < res && y >= 0 && y < res && z >= 0 && z < res;
-}
 
 // the site's own word at its cell, or one more in *dropped (one atomic per wave with a cell outside; a count is the
 // same in any order)
 __device__ __forceinline__ void edt_seed_one(const EdtGrid& g, bool live, int x, int y, int z, unsigned long long* dropped) {
-    const bool in = live && edt_inside(g.res, x, y, z);
-    if (in) g.a[((int64_t)x * g.res + y) * g.res + z] = edt_pack(x, y, z);
+    const bool in = live && cube_inside(g.res, x, y, z);
+    if (in) g.a[cube_index(g.res, x, y, z)] = edt_pack(x, y, z);
     const uint64_t out = __ballot(live && !in);
     if (out && lane_id() == (int)__builtin_ctzll(out)) atomicAdd(dropped, (unsigned long long)__builtin_popcountll(out));
 }
@@ -69,8 +61,8 @@ static __global__ __launch_bounds__(256) void edt_seed_cells(EdtGrid g, const in
 
 // VoxelGrid keys: cell = floor(((float)key * vs + origin_grid - origin_dt) / vs) + h per axis, in that order, vs the
 // transform's (the grid's equals it within FLT_EPSILON, or the call was refused)
-static __global__ __launch_bounds__(256) void edt_seed_keys(EdtGrid g, const int32_t* __restrict__ keys, int64_t n, EdtFrame grid,
-                                                           EdtFrame dt, unsigned long long* dropped) {
+static __global__ __launch_bounds__(256) void edt_seed_keys(EdtGrid g, const int32_t* __restrict__ keys, int64_t n, GridFrame grid,
+                                                           GridFrame dt, unsigned long long* dropped) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool live = i < n;
     int c[3] = {0, 0, 0};
@@ -78,22 +70,20 @@ static __global__ __launch_bounds__(256) void edt_seed_keys(EdtGrid g, const int
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float p = ((float)keys[i * 3 + k] * dt.vs + grid.origin[k]) - dt.origin[k];
-            c[k] = edt_floor_int(p / dt.vs) + g.h_res;
+            c[k] = floor_int(p / dt.vs) + g.h_res;
         }
     }
     edt_seed_one(g, live, c[0], c[1], c[2], dropped);
 }
 
-// an OccupancyGrid's occupied voxels: those of its bounds box [lo, hi] with p > thres (a NaN, unknown, is not)
-static __global__ __launch_bounds__(256) void edt_seed_occupied(EdtGrid g, const float* __restrict__ prob, int x0, int y0, int z0,
-                                                               int ey, int ez, int64_t count, float thres) {
+// an OccupancyGrid's occupied voxels: those of its bounds box
+static __global__ __launch_bounds__(256) void edt_seed_occupied(EdtGrid g, const float* __restrict__ prob, GridBox b, float thres) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= count) return;
-    const int z = z0 + (int)(t % ez);
-    const int y = y0 + (int)((t / ez) % ey);
-    const int x = x0 + (int)(t / ((int64_t)ez * ey));
-    const int64_t idx = ((int64_t)x * g.res + y) * g.res + z;
-    if (prob[idx] > thres) g.a[idx] = edt_pack(x, y, z);
+    if (t >= b.count) return;
+    int x, y, z;
+    box_voxel(b, t, &x, &y, &z);
+    const int64_t idx = cube_index(g.res, x, y, z);
+    if (occupied(prob[idx], thres)) g.a[idx] = edt_pack(x, y, z);
 }
 
 // inclusive max-scan upwards / min-scan downwards over the lanes of the wave
@@ -212,15 +202,15 @@ __device__ __forceinline__ void edt_store_nearest(int32_t* __restrict__ o, int64
 }
 
 // the cell of a point is floor((q - origin) / vs) + h per axis; outside the grid on any axis: NaN and (-1, -1, -1)
-static __global__ __launch_bounds__(256) void edt_query(EdtGrid g, EdtFrame f, const float* __restrict__ pts, int64_t n,
+static __global__ __launch_bounds__(256) void edt_query(EdtGrid g, GridFrame f, const float* __restrict__ pts, int64_t n,
                                                        float* __restrict__ odist, int32_t* __restrict__ onear) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int x = edt_floor_int((pts[i * 3] - f.origin[0]) / f.vs) + g.h_res;
-    const int y = edt_floor_int((pts[i * 3 + 1] - f.origin[1]) / f.vs) + g.h_res;
-    const int z = edt_floor_int((pts[i * 3 + 2] - f.origin[2]) / f.vs) + g.h_res;
-    const bool in = edt_inside(g.res, x, y, z);
-    const uint32_t w = in ? g.b[((int64_t)x * g.res + y) * g.res + z] : kEdtNone;
+    const int x = cell_of(f, pts[i * 3], 0) + g.h_res;
+    const int y = cell_of(f, pts[i * 3 + 1], 1) + g.h_res;
+    const int z = cell_of(f, pts[i * 3 + 2], 2) + g.h_res;
+    const bool in = cube_inside(g.res, x, y, z);
+    const uint32_t w = in ? g.b[cube_index(g.res, x, y, z)] : kEdtNone;
     odist[i] = in ? edt_distance(w, x, y, z, f.vs) : __builtin_nanf("");
     if (onear) edt_store_nearest(onear, i, w);
 }

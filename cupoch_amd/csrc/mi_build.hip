@@ -327,7 +327,7 @@ extern "C" {
 int mi_icp_set_target(mi_icp_ctx* c, const float* xyz, const float* normals, const float* covs,
                       int64_t n, int mem_kind) {
     TRY(check_ctx(c, mem_kind, "set_target"));
-    if (n < 0 || n > 0x7fffff00ll || (n > 0 && !xyz)) return fail(c, MI_ICP_ERR_INVALID, "set_target: bad size/pointer");
+    if (n < 0 || n > kMaxCount || (n > 0 && !xyz)) return fail(c, MI_ICP_ERR_INVALID, "set_target: bad size/pointer");
     TRY(drain_links(c));
     TRY(drop_expiry(c));
     c->nt = 0;
@@ -452,7 +452,7 @@ int mi_icp_set_target(mi_icp_ctx* c, const float* xyz, const float* normals, con
 int mi_icp_set_source(mi_icp_ctx* c, const float* xyz, const float* normals, const float* covs,
                       int64_t n, int mem_kind) {
     TRY(check_ctx(c, mem_kind, "set_source"));
-    if (n < 0 || n > 0x7fffff00ll || (n > 0 && !xyz)) return fail(c, MI_ICP_ERR_INVALID, "set_source: bad size/pointer");
+    if (n < 0 || n > kMaxCount || (n > 0 && !xyz)) return fail(c, MI_ICP_ERR_INVALID, "set_source: bad size/pointer");
     c->ns = 0;
     c->inv_s_valid = false;
     c->nn_valid = false;
@@ -524,7 +524,7 @@ int mi_icp_set_source(mi_icp_ctx* c, const float* xyz, const float* normals, con
 
 int mi_icp_spatial_order(mi_icp_ctx* c, const float* xyz, int64_t n, uint32_t* order_out, int mem_kind) {
     TRY(check_ctx(c, mem_kind, "spatial_order"));
-    if (n < 0 || n > 0x7fffff00ll || (n > 0 && (!xyz || !order_out)))
+    if (n < 0 || n > kMaxCount || (n > 0 && (!xyz || !order_out)))
         return fail(c, MI_ICP_ERR_INVALID, "spatial_order: bad arguments");
     if (n == 0) return MI_ICP_OK;
     const float* d_pts;

@@ -15,8 +15,6 @@ using namespace mi::eng;
 // stage[3] / stage[4] a VoxelGrid's sorted copy and its permutation, stage[5] an occupancy grid's listed voxels,
 // bounds the key extents.
 
-static bool finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
-
 static bool is_grid(const mi_icp_collision_side* s) { return s->kind == MI_ICP_COLLISION_VOXELGRID || s->kind == MI_ICP_COLLISION_OCCGRID; }
 
 static int64_t side_count(const mi_icp_collision_side* s) {
@@ -29,14 +27,13 @@ static int64_t side_count(const mi_icp_collision_side* s) {
 }
 
 static int side_check(mi_icp_ctx* c, const char* what, const mi_icp_collision_side* s) {
-    const int64_t big = 0x7fffff00ll;
     switch (s->kind) {
-        case MI_ICP_COLLISION_VOXELGRID:
-            if (s->m < 0 || s->m > big) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+        case MI_ICP_COLLISION_VOXELGRID: {
+            TRY(count_ok(c, what, s->m));
             if (s->m > 0 && !s->keys) return fail(c, MI_ICP_ERR_INVALID, "%s: null keys", what);
-            if (s->m > 0 && (!(s->voxel_size > 0.0f) || !std::isfinite(s->voxel_size) || !finite3(s->origin)))
-                return fail(c, MI_ICP_ERR_INVALID, "%s: voxel_size must be positive and finite, the origin finite", what);
-            return MI_ICP_OK;
+            GridFrame f;  // (an empty grid's frame is not looked at)
+            return s->m > 0 ? frame_check(c, what, s->voxel_size, s->origin, &f) : MI_ICP_OK;
+        }
         case MI_ICP_COLLISION_OCCGRID: {
             const mi_icp_occgrid_params& p = s->grid_params;
             if (!(p.voxel_size > 0.0f) || !std::isfinite(p.voxel_size) || !finite3(p.origin) || std::isnan(p.occ_prob_thres_log))
@@ -44,43 +41,38 @@ static int side_check(mi_icp_ctx* c, const char* what, const mi_icp_collision_si
             return MI_ICP_OK;
         }
         case MI_ICP_COLLISION_LINESET:
-            if (s->n_lines < 0 || s->n_lines > big || s->n_points < 0 || s->n_points > big) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+            TRY(count_ok(c, what, s->n_lines));
+            TRY(count_ok(c, what, s->n_points));
             if (s->n_lines > 0 && (!s->lines || (s->n_points > 0 && !s->points))) return fail(c, MI_ICP_ERR_INVALID, "%s: null lines or points", what);
             return MI_ICP_OK;
         case MI_ICP_COLLISION_PRIMITIVES:
-            if (s->n_primitives < 0 || s->n_primitives > big) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+            TRY(count_ok(c, what, s->n_primitives));
             if (s->n_primitives > 0 && !s->primitives) return fail(c, MI_ICP_ERR_INVALID, "%s: null primitives", what);
             return MI_ICP_OK;
         default: return fail(c, MI_ICP_ERR_INVALID, "%s: bad side kind %d", what, (int)s->kind);
     }
 }
 
-struct OccView {
-    const float* prob = nullptr;
-    int res = 0, b[6] = {0, 0, 0, 0, 0, 0};
-    bool empty() const { return b[0] > b[3] || b[1] > b[4] || b[2] > b[5]; }
-};
+// a grid side's frame: a VoxelGrid's own, an occupancy grid's from its parameters
+static GridFrame side_frame(const mi_icp_collision_side* s) {
+    const bool occ = s->kind == MI_ICP_COLLISION_OCCGRID;
+    const float* o = occ ? s->grid_params.origin : s->origin;
+    return {occ ? s->grid_params.voxel_size : s->voxel_size, {o[0], o[1], o[2]}};
+}
 
 // the side that is searched; *none: it has no voxel a query could meet
 static int make_grid(mi_icp_ctx* c, const char* what, const mi_icp_collision_side* s, ColGrid* G, bool* none) {
     std::memset(G, 0, sizeof(*G));
     *none = false;
+    G->f = side_frame(s);
     if (s->kind == MI_ICP_COLLISION_OCCGRID) {
-        OccView v;
-        TRY(occgrid_view(c, s->grid, what, &v.prob, &v.res, v.b));
+        TRY(occgrid_view(c, s->grid, what, &G->prob, &G->res, G->b));
         G->occ = 1;
-        G->prob = v.prob;
-        G->res = v.res;
-        G->h = v.res / 2;
-        for (int k = 0; k < 6; ++k) G->b[k] = v.b[k];
+        G->h = G->res / 2;
         G->thres = s->grid_params.occ_prob_thres_log;
-        G->vs = s->grid_params.voxel_size;
-        for (int k = 0; k < 3; ++k) G->origin[k] = s->grid_params.origin[k];
-        *none = v.empty();
+        *none = box_of_bounds(G->b).count == 0;
         return MI_ICP_OK;
     }
-    G->vs = s->voxel_size;
-    for (int k = 0; k < 3; ++k) G->origin[k] = s->origin[k];
     G->keys = s->keys;
     G->m = s->m;
     if (s->keys_sorted && s->keys_index) G->perm = reinterpret_cast<const uint32_t*>(s->keys_index);
@@ -118,37 +110,22 @@ static int make_grid(mi_icp_ctx* c, const char* what, const mi_icp_collision_sid
 // the enumerated voxels of a grid side; an occupancy grid is listed first (one wait)
 static int make_cells(mi_icp_ctx* c, const char* what, const mi_icp_collision_side* s, ColCells* E) {
     std::memset(E, 0, sizeof(*E));
+    E->f = side_frame(s);
     if (s->kind == MI_ICP_COLLISION_VOXELGRID) {
         E->keys = s->keys;
         E->n = s->m;
-        E->vs = s->voxel_size;
-        for (int k = 0; k < 3; ++k) E->origin[k] = s->origin[k];
         return MI_ICP_OK;
     }
-    OccView v;
-    TRY(occgrid_view(c, s->grid, what, &v.prob, &v.res, v.b));
-    E->res = v.res;
-    E->h = v.res / 2;
-    E->vs = s->grid_params.voxel_size;
-    for (int k = 0; k < 3; ++k) E->origin[k] = s->grid_params.origin[k];
-    if (v.empty()) return MI_ICP_OK;
-    const int ex = v.b[3] - v.b[0] + 1, ey = v.b[4] - v.b[1] + 1, ez = v.b[5] - v.b[2] + 1;
-    const int64_t count = (int64_t)ex * ey * ez;
-    uint32_t *flags, *pos;
-    const uint32_t* total;
-    TRY(ensure(c, c->flags, (size_t)count, &flags));
-    col_occ_flags<<<blocks_for(count), 256, 0, c->stream>>>(v.prob, v.res, v.b[0], v.b[1], v.b[2], ey, ez, count,
-                                                          s->grid_params.occ_prob_thres_log, flags);
-    KCHK(c);
-    TRY(scan_flags(c, flags, count, &pos, &total));
-    TRY(read_total(c, total));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const int64_t n = (int64_t)c->u_host[0];
+    const float* prob;
+    int bd[6];
+    TRY(occgrid_view(c, s->grid, what, &prob, &E->res, bd));
+    E->h = E->res / 2;
+    int64_t n;
+    TRY(occgrid_select(c, s->grid, MI_ICP_OCCGRID_OCCUPIED, s->grid_params.occ_prob_thres_log, &n));
     if (n == 0) return MI_ICP_OK;
     int32_t* list;
     TRY(ensure(c, c->stage[5], (size_t)n * 3, &list));
-    col_occ_list<<<blocks_for(count), 256, 0, c->stream>>>(v.b[0], v.b[1], v.b[2], ey, ez, count, flags, pos, list);
-    KCHK(c);
+    TRY(occgrid_gather(c, s->grid, E->f, list, nullptr, nullptr));
     E->keys = list;
     E->n = n;
     return MI_ICP_OK;
@@ -211,7 +188,7 @@ int mi_icp_collision_compute(mi_icp_ctx* c, const mi_icp_collision_side* a, cons
         float* reach;
         TRY(ensure(c, c->stage[1], (size_t)ot->n_primitives * 6, &reach));
         TRY(ensure(c, c->stage[0], (size_t)E.n, &hit));
-        col_prim_reach<<<blocks_for(ot->n_primitives), 256, 0, c->stream>>>(ot->primitives, ot->n_primitives, margin, E.vs, reach);
+        col_prim_reach<<<blocks_for(ot->n_primitives), 256, 0, c->stream>>>(ot->primitives, ot->n_primitives, margin, E.f.vs, reach);
         KCHK(c);
         col_cells_prims<<<blocks_for(E.n), 256, 0, c->stream>>>(E, ot->primitives, reach, ot->n_primitives, margin, hit);
         KCHK(c);
@@ -270,7 +247,7 @@ int mi_icp_collision_sort_keys(mi_icp_ctx* c, const int32_t* keys, int64_t m, in
     TRY(check_ctx(c));
     if (!m_out) return fail(c, MI_ICP_ERR_INVALID, "%s: m_out is null", what);
     *m_out = 0;
-    if (m < 0 || m > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    TRY(count_ok(c, what, m));
     if (m == 0) return MI_ICP_OK;
     if (!keys || !out_keys || !out_index) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
     VgRuns r;

@@ -138,7 +138,7 @@ int mi_icp_debug_sort_plan(int64_t n, int32_t out[8]) {
 
 int mi_icp_debug_morton_order_bits(mi_icp_ctx* c, const float* xyz, int64_t n, int bits, uint32_t* order_out) {
     TRY(check_ctx(c));
-    if (n <= 0 || n > 0x7fffff00ll || bits < 1 || bits > 21 || !xyz || !order_out)
+    if (n <= 0 || n > kMaxCount || bits < 1 || bits > 21 || !xyz || !order_out)
         return fail(c, MI_ICP_ERR_INVALID, "debug_morton_order_bits: bad arguments");
     const float* d_pts;
     TRY(to_device(c, xyz, (size_t)n * 3, MI_ICP_HOST, c->stage[0], &d_pts));

@@ -17,45 +17,17 @@ struct mi_icp_dt {
     EdtGrid g = {};
     DevBuf a, b;
     DevBuf dropped;  // one 64-bit counter
+    void free_buffers() {
+        release(a);
+        release(b);
+        release(dropped);
+    }
 };
 
-namespace mi {
-namespace eng {
-static void dt_release(mi_icp_dt* d) {
-    release(d->a);
-    release(d->b);
-    release(d->dropped);
-}
-
-void dt_release_all(mi_icp_ctx* c) {
-    for (mi_icp_dt* d : c->dts) {
-        dt_release(d);
-        delete d;
-    }
-    c->dts.clear();
-}
-}  // namespace eng
-}  // namespace mi
+void mi::eng::dt_release_all(mi_icp_ctx* c) { handle_release_all(c->dts); }
 
 static int dt_check(mi_icp_ctx* c, const mi_icp_dt* d, const char* what) {
-    if (!owned(c, d, c->dts))
-        return fail(c, MI_ICP_ERR_INVALID, "%s: not a distance transform of this context", what);
-    return MI_ICP_OK;
-}
-
-static int dt_resolution_ok(mi_icp_ctx* c, int resolution, const char* what) {
-    if (resolution < 2 || resolution > MI_ICP_DT_MAX_RESOLUTION)
-        return fail(c, MI_ICP_ERR_INVALID, "%s: the resolution must be in [2, %d]", what, MI_ICP_DT_MAX_RESOLUTION);
-    return MI_ICP_OK;
-}
-
-static int dt_frame(mi_icp_ctx* c, float vs, const float* origin3, const char* what, EdtFrame* f) {
-    if (!(vs > 0.0f) || !std::isfinite(vs) || !origin3 || !std::isfinite(origin3[0]) || !std::isfinite(origin3[1]) ||
-        !std::isfinite(origin3[2]))
-        return fail(c, MI_ICP_ERR_INVALID, "%s: voxel_size must be positive and finite, the origin finite", what);
-    f->vs = vs;
-    for (int k = 0; k < 3; ++k) f->origin[k] = origin3[k];
-    return MI_ICP_OK;
+    return handle_check(c, d, c->dts, what, "distance transform");
 }
 
 // both planes of a transform of `resolution`, no site anywhere; on failure *d is left without buffers.  A plane that
@@ -71,12 +43,12 @@ static int dt_allocate(mi_icp_ctx* c, mi_icp_dt* d, int resolution) {
     if (rc == MI_ICP_OK) rc = ensure(c, d->dropped, (size_t)1, &cnt);
     if (rc != MI_ICP_OK) {
         (void)hipGetLastError();
-        dt_release(d);
+        d->free_buffers();
         return rc;
     }
     if (hipMemsetAsync(g.b, 0xff, (size_t)g.n * sizeof(uint32_t), c->stream) != hipSuccess) {
         (void)hipGetLastError();
-        dt_release(d);
+        d->free_buffers();
         return fail(c, MI_ICP_ERR_HIP, "distance transform: the plane could not be cleared");
     }
     return MI_ICP_OK;
@@ -114,12 +86,12 @@ int mi_icp_dt_create(mi_icp_ctx* c, int resolution, mi_icp_dt** out) {
     TRY(check_ctx(c));
     if (!out) return fail(c, MI_ICP_ERR_INVALID, "dt_create: out is null");
     *out = nullptr;
-    TRY(dt_resolution_ok(c, resolution, "dt_create"));
+    TRY(resolution_ok(c, "dt_create", resolution, MI_ICP_DT_MAX_RESOLUTION));
     mi_icp_dt* d = new mi_icp_dt;
     d->owner = c;
     const int rc = dt_allocate(c, d, resolution);
     if (rc != MI_ICP_OK) {
-        dt_release(d);
+        d->free_buffers();
         delete d;
         return rc;
     }
@@ -129,25 +101,15 @@ int mi_icp_dt_create(mi_icp_ctx* c, int resolution, mi_icp_dt** out) {
 }
 
 int mi_icp_dt_destroy(mi_icp_ctx* c, mi_icp_dt* d) {
-    TRY(check_ctx(c));
-    if (!d) return MI_ICP_OK;
-    TRY(dt_check(c, d, "dt_destroy"));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->dts.erase(std::find(c->dts.begin(), c->dts.end(), d));
-    dt_release(d);
-    delete d;
-    return MI_ICP_OK;
+    return handle_destroy(c, d, c->dts, "dt_destroy", "distance transform");
 }
 
 int mi_icp_dt_reconstruct(mi_icp_ctx* c, mi_icp_dt* d, int resolution) {
     TRY(check_ctx(c));
     TRY(dt_check(c, d, "dt_reconstruct"));
-    TRY(dt_resolution_ok(c, resolution, "dt_reconstruct"));
+    TRY(resolution_ok(c, "dt_reconstruct", resolution, MI_ICP_DT_MAX_RESOLUTION));
     const int rc = dt_allocate(c, d, resolution);
-    if (rc != MI_ICP_OK) {  // no planes left: the handle is gone
-        c->dts.erase(std::find(c->dts.begin(), c->dts.end(), d));
-        delete d;
-    }
+    if (rc != MI_ICP_OK) handle_drop(d, c->dts);  // no planes left: the handle is gone
     return rc;
 }
 
@@ -155,7 +117,7 @@ int mi_icp_dt_compute_cells(mi_icp_ctx* c, mi_icp_dt* d, const int32_t* cells, i
     const char* what = "dt_compute_cells";
     TRY(check_ctx(c));
     TRY(dt_check(c, d, what));
-    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    TRY(count_ok(c, what, n));
     if (n > 0 && !cells) return fail(c, MI_ICP_ERR_INVALID, "%s: null cells", what);
     TRY(dt_begin(c, d));
     if (n > 0) {
@@ -170,10 +132,10 @@ int mi_icp_dt_compute_voxelgrid(mi_icp_ctx* c, mi_icp_dt* d, float voxel_size, c
     const char* what = "dt_compute_voxelgrid";
     TRY(check_ctx(c));
     TRY(dt_check(c, d, what));
-    EdtFrame dt, grid;
-    TRY(dt_frame(c, voxel_size, origin3, what, &dt));
-    TRY(dt_frame(c, grid_voxel_size, grid_origin3, what, &grid));
-    if (m < 0 || m > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    GridFrame dt, grid;
+    TRY(frame_check(c, what, voxel_size, origin3, &dt));
+    TRY(frame_check(c, what, grid_voxel_size, grid_origin3, &grid));
+    TRY(count_ok(c, what, m));
     if (m > 0 && !keys) return fail(c, MI_ICP_ERR_INVALID, "%s: null keys", what);
     if (std::fabs(voxel_size - grid_voxel_size) > FLT_EPSILON)
         return fail(c, MI_ICP_ERR_INVALID, "Unsupport computing Voronoi diagrams from different voxel size.");
@@ -195,10 +157,9 @@ int mi_icp_dt_compute_occgrid(mi_icp_ctx* c, mi_icp_dt* d, const mi_icp_occgrid*
     if (std::isnan(occ_prob_thres_log)) return fail(c, MI_ICP_ERR_INVALID, "%s: the threshold is not a number", what);
     if (res != d->g.res) return fail(c, MI_ICP_ERR_INVALID, "%s: the resolutions differ (%d, %d)", what, res, d->g.res);
     TRY(dt_begin(c, d));
-    if (bd[0] <= bd[3] && bd[1] <= bd[4] && bd[2] <= bd[5]) {
-        const int ey = bd[4] - bd[1] + 1, ez = bd[5] - bd[2] + 1;
-        const int64_t count = (int64_t)(bd[3] - bd[0] + 1) * ey * ez;
-        edt_seed_occupied<<<blocks_for(count), 256, 0, c->stream>>>(d->g, prob, bd[0], bd[1], bd[2], ey, ez, count, occ_prob_thres_log);
+    const GridBox box = box_of_bounds(bd);
+    if (box.count > 0) {
+        edt_seed_occupied<<<blocks_for(box.count), 256, 0, c->stream>>>(d->g, prob, box, occ_prob_thres_log);
         KCHK(c);
     }
     return dt_passes(c, d, nullptr);
@@ -209,9 +170,9 @@ int mi_icp_dt_query(mi_icp_ctx* c, mi_icp_dt* d, float voxel_size, const float* 
     const char* what = "dt_query";
     TRY(check_ctx(c));
     TRY(dt_check(c, d, what));
-    EdtFrame f;
-    TRY(dt_frame(c, voxel_size, origin3, what, &f));
-    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    GridFrame f;
+    TRY(frame_check(c, what, voxel_size, origin3, &f));
+    TRY(count_ok(c, what, n));
     if (n == 0) return MI_ICP_OK;
     if (!queries || !out_distance) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
     edt_query<<<blocks_for(n), 256, 0, c->stream>>>(d->g, f, queries, n, out_distance, out_nearest);

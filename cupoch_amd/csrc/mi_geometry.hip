@@ -160,7 +160,7 @@ int mi_icp_select_by_index(mi_icp_ctx* c, const float* xyz, const float* normals
                            const int64_t* indices, int64_t n_indices, int invert, float* out_xyz, float* out_normals,
                            float* out_colors, int64_t* m, int mem_kind) {
     TRY(check_sizes(c, "select_by_index", n, m, mem_kind));
-    if (n_indices < 0 || n_indices > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "select_by_index: bad size");
+    TRY(count_ok(c, "select_by_index", n_indices));
     // (its own null-buffer rule: an empty cloud or an empty list needs no array)
     if ((n > 0 && !xyz) || (n_indices > 0 && !indices)) return fail(c, MI_ICP_ERR_INVALID, "select_by_index: null buffer");
     const int64_t count = invert ? n : n_indices;  // the most points the output can hold
@@ -393,7 +393,7 @@ int mi_icp_segment_plane(mi_icp_ctx* c, const float* xyz, int64_t n, float dista
     *m = 0;
     if (best_iteration) *best_iteration = -1;
     if (best_count) *best_count = 0;
-    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    TRY(count_ok(c, what, n));
     if (num_iterations > kSegMaxIterations)
         return fail(c, MI_ICP_ERR_INVALID, "%s: more than %lld iterations are not supported", what, (long long)kSegMaxIterations);
     if (ransac_n < 3 || n < ransac_n) return MI_ICP_OK;  // segmentation.cu:204-212: the zero plane, no inliers

@@ -15,8 +15,6 @@ using namespace mi::eng;
 // the compaction's positions; the search keeps its distances in stage[3], its candidates in stage[4], its two flag
 // planes in stage[5] and its control words in bounds.
 
-static const int64_t kGrBig = 0x7fffff00ll;
-
 static int bits_for(int64_t n) {
     int b = 1;
     while (b < 31 && ((int64_t)1 << b) < n) ++b;
@@ -30,7 +28,8 @@ static int status_word(mi_icp_ctx* c, uint32_t** status) {
 }
 
 static int sizes_ok(mi_icp_ctx* c, const char* what, int64_t n_points, int64_t m) {
-    if (n_points < 0 || n_points > kGrBig || m < 0 || m > kGrBig) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    TRY(count_ok(c, what, n_points));
+    TRY(count_ok(c, what, m));
     return MI_ICP_OK;
 }
 
@@ -120,7 +119,7 @@ int mi_icp_graph_lattice(mi_icp_ctx* c, const float* min3, const float* max3, co
     const int64_t rx = resolutions3[0], ry = resolutions3[1], rz = resolutions3[2];
     if (rx < 1 || ry < 1 || rz < 1) return fail(c, MI_ICP_ERR_INVALID, "%s: a resolution below 1", what);
     // (each factor is below 2^33, so the products are taken one at a time against the limit)
-    if (rx * ry > (int64_t)INT_MAX || rx * ry * rz > kGrBig) return fail(c, MI_ICP_ERR_INVALID, "%s: too many nodes", what);
+    if (rx * ry > (int64_t)INT_MAX || rx * ry * rz > kMaxCount) return fail(c, MI_ICP_ERR_INVALID, "%s: too many nodes", what);
     const int64_t n = rx * ry * rz;
     const double edges = (3.0 * rx - 2.0) * (3.0 * ry - 2.0) * (3.0 * rz - 2.0) - (double)n;
     if (edges > (double)INT_MAX) return fail(c, MI_ICP_ERR_INVALID, "%s: more than 2^31 - 1 edges", what);
@@ -150,7 +149,7 @@ static int match_open(mi_icp_ctx* c, const char* what, const int32_t* lines, int
                       int64_t k) {
     TRY(check_ctx(c));
     TRY(sizes_ok(c, what, n_points, m));
-    if (k < 0 || k > kGrBig / 2) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    if (k < 0 || k > kMaxCount / 2) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
     if ((m > 0 && !lines) || (k > 0 && !edges)) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
     return MI_ICP_OK;
 }
@@ -158,7 +157,7 @@ static int match_open(mi_icp_ctx* c, const char* what, const int32_t* lines, int
 int mi_icp_graph_set_edge_weights(mi_icp_ctx* c, const int32_t* lines, float* weights, int64_t m, const int32_t* edges, int64_t k,
                                   int is_directed, float weight) {
     const char* what = "graph_set_edge_weights";
-    TRY(match_open(c, what, lines, m, kGrBig, edges, k));
+    TRY(match_open(c, what, lines, m, kMaxCount, edges, k));
     if (m == 0 || k == 0) return MI_ICP_OK;
     if (!weights) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
     const int both = is_directed ? 0 : 1;

@@ -239,7 +239,7 @@ int mi_icp_cluster_dbscan(mi_icp_ctx* c, const float* xyz, int64_t n, float eps,
     TRY(check_ctx(c, mem_kind, what));
     if (!n_clusters) return fail(c, MI_ICP_ERR_INVALID, "%s: n_clusters is null", what);
     *n_clusters = 0;
-    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    TRY(count_ok(c, what, n));
     if (n > 0 && (!xyz || !labels)) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
     if (!(eps > 0.0f) || !(eps * eps < INFINITY))
         return fail(c, MI_ICP_ERR_INVALID, "%s: eps must be positive, and finite when squared", what);
@@ -331,7 +331,7 @@ int mi_icp_iss_keypoints(mi_icp_ctx* c, const float* xyz, int64_t n, float salie
         radii_out[0] = salient_radius;
         radii_out[1] = non_max_radius;
     }
-    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    TRY(count_ok(c, what, n));
     if (n > 0 && (!xyz || !mask_out)) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
     if (!(salient_radius >= 0.0f) || !(non_max_radius >= 0.0f) || !(salient_radius * salient_radius < INFINITY) ||
         !(non_max_radius * non_max_radius < INFINITY))
@@ -351,7 +351,7 @@ int mi_icp_gaussian_filter(mi_icp_ctx* c, const float* xyz, const float* normals
                            float* out_normals, float* out_colors, int mem_kind) {
     const char* what = "gaussian_filter";
     TRY(check_ctx(c, mem_kind, what));
-    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    TRY(count_ok(c, what, n));
     if (!(search_radius > 0.0f) || !(search_radius * search_radius < INFINITY))
         return fail(c, MI_ICP_ERR_INVALID, "%s: search_radius must be positive, and finite when squared", what);
     if (!(sigma2 > 0.0f) || !(sigma2 < INFINITY)) return fail(c, MI_ICP_ERR_INVALID, "%s: sigma2 must be positive and finite", what);

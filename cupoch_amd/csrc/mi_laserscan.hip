@@ -90,7 +90,7 @@ int mi_icp_laserscan_to_points(mi_icp_ctx* c, const float* ranges, const float* 
     if (num_max_scans < 1 || num_scans < 0 || num_scans > num_max_scans || first_slot < 0 || first_slot >= num_max_scans || capacity < 0)
         return fail(c, MI_ICP_ERR_INVALID, "%s: bad ring arguments", what);
     const int64_t count = (int64_t)num_scans * num_steps;
-    if ((int64_t)num_max_scans * num_steps > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    if ((int64_t)num_max_scans * num_steps > kMaxCount) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
     if (!(min_range < max_range) || count == 0) return MI_ICP_OK;
     if (!ranges || !origins) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
 
@@ -143,7 +143,7 @@ int mi_icp_laserscan_from_points(mi_icp_ctx* c, const float* points, int64_t n, 
     const char* what = "laserscan_from_points";
     TRY(check_ctx(c));
     if (info) *info = -1;
-    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    TRY(count_ok(c, what, n));
     LsBins a;
     TRY(bins_open(c, what, angle_increment, min_height, max_height, num_vertical_divisions, min_range, max_range, min_angle,
                   max_angle, num_steps, &a));
@@ -161,7 +161,7 @@ int mi_icp_laserscan_from_depth(mi_icp_ctx* c, const void* depth, int depth_type
     if (info) *info = -1;
     if (width < 0 || height < 0 || stride < 1 || !intrinsic4 || (depth_type != MI_ICP_DEPTH_F32 && depth_type != MI_ICP_DEPTH_U16))
         return fail(c, MI_ICP_ERR_INVALID, "%s: bad arguments", what);
-    if ((int64_t)width * height > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: image too large", what);
+    if ((int64_t)width * height > kMaxCount) return fail(c, MI_ICP_ERR_INVALID, "%s: image too large", what);
     LsBins a;
     TRY(bins_open(c, what, angle_increment, min_y, max_y, num_vertical_divisions, min_range, max_range, min_angle, max_angle,
                   num_steps, &a));
@@ -187,7 +187,7 @@ int mi_icp_laserscan_range_filter(mi_icp_ctx* c, const float* ranges, int64_t co
                                   float* out_ranges) {
     const char* what = "laserscan_range_filter";
     TRY(check_ctx(c));
-    if (count < 0 || count > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    TRY(count_ok(c, what, count));
     if (count == 0) return MI_ICP_OK;
     if (!ranges || !out_ranges) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
     ls_range_filter<<<blocks_for(count), 256, 0, c->stream>>>(ranges, count, min_range, max_range, out_ranges);
@@ -201,7 +201,7 @@ int mi_icp_laserscan_shadow_filter(mi_icp_ctx* c, const float* ranges, int32_t n
     const char* what = "laserscan_shadow_filter";
     TRY(check_ctx(c));
     if (num_steps < 2) return fail(c, MI_ICP_ERR_INVALID, "%s: num_steps below 2", what);
-    if (num_rows < 0 || window < 0 || neighbors < 0 || window > (1 << 20) || (int64_t)num_rows * num_steps > 0x7fffff00ll)
+    if (num_rows < 0 || window < 0 || neighbors < 0 || window > (1 << 20) || (int64_t)num_rows * num_steps > kMaxCount)
         return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
     const int64_t count = (int64_t)num_rows * num_steps;
     if (count == 0) return MI_ICP_OK;
@@ -228,7 +228,7 @@ int mi_icp_laserscan_shadow_filter(mi_icp_ctx* c, const float* ranges, int32_t n
 int mi_icp_laserscan_scale(mi_icp_ctx* c, float* ranges, int64_t count, float scale) {
     const char* what = "laserscan_scale";
     TRY(check_ctx(c));
-    if (count < 0 || count > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    TRY(count_ok(c, what, count));
     if (count == 0) return MI_ICP_OK;
     if (!ranges) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
     ls_scale<<<blocks_for(count), 256, 0, c->stream>>>(ranges, count, scale);

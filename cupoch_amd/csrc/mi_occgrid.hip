@@ -15,30 +15,22 @@ struct mi_icp_occgrid {
     OccGrid g = {};
     DevBuf prob, marks, touch, state;
     DevBuf part;        // occ_prepare's per-block maxima
-    int bounds[6] = {0, 0, 0, 0, 0, 0};  // min[3], max[3], inclusive
+    int bounds[6] = {0, 0, 0, 0, 0, 0};  // min[3], max[3], inclusive (a SetFreeArea beside the grid leaves min > max on an axis)
+    void free_buffers() {
+        release(prob);
+        release(marks);
+        release(touch);
+        release(state);
+        release(part);
+    }
 };
 
 namespace mi {
 namespace eng {
-static void occgrid_release(mi_icp_occgrid* o) {
-    release(o->prob);
-    release(o->marks);
-    release(o->touch);
-    release(o->state);
-    release(o->part);
-}
-
-void occgrid_release_all(mi_icp_ctx* c) {
-    for (mi_icp_occgrid* o : c->occ_grids) {
-        occgrid_release(o);
-        delete o;
-    }
-    c->occ_grids.clear();
-}
+void occgrid_release_all(mi_icp_ctx* c) { handle_release_all(c->occ_grids); }
 
 static int occ_check(mi_icp_ctx* c, const mi_icp_occgrid* o, const char* what) {
-    if (!owned(c, o, c->occ_grids)) return fail(c, MI_ICP_ERR_INVALID, "%s: not a grid of this context", what);
-    return MI_ICP_OK;
+    return handle_check(c, o, c->occ_grids, what, "grid");
 }
 
 int occgrid_view(mi_icp_ctx* c, const mi_icp_occgrid* o, const char* what, const float** prob, int* resolution, int* bounds6) {
@@ -48,24 +40,43 @@ int occgrid_view(mi_icp_ctx* c, const mi_icp_occgrid* o, const char* what, const
     for (int k = 0; k < 6; ++k) bounds6[k] = o->bounds[k];
     return MI_ICP_OK;
 }
+
+int occgrid_select(mi_icp_ctx* c, const mi_icp_occgrid* o, int which, float thres, int64_t* count) {
+    *count = 0;
+    const GridBox b = box_of_bounds(o->bounds);
+    if (b.count == 0) return MI_ICP_OK;
+    uint32_t *flags, *pos;
+    const uint32_t* total;
+    TRY(ensure(c, c->flags, (size_t)b.count, &flags));
+    occ_box_flags<<<blocks_for(b.count), 256, 0, c->stream>>>(o->g, b, which, thres, flags);
+    KCHK(c);
+    TRY(scan_flags(c, flags, b.count, &pos, &total));
+    TRY(read_total(c, total));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *count = (int64_t)c->u_host[0];
+    return MI_ICP_OK;
+}
+
+int occgrid_gather(mi_icp_ctx* c, const mi_icp_occgrid* o, const GridFrame& f, int32_t* out_index, float* out_prob_log, float* out_xyz) {
+    const GridBox b = box_of_bounds(o->bounds);
+    occ_box_gather<<<blocks_for(b.count), 256, 0, c->stream>>>(o->g, b, f, (const uint32_t*)c->flags.p, (const uint32_t*)c->dense_idx.p,
+                                                             out_index, out_prob_log, out_xyz);
+    KCHK(c);
+    return MI_ICP_OK;
+}
 }  // namespace eng
 }  // namespace mi
 
-static bool finite3(const float* v) { return v && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
-
 // the context, the grid, and the parameters every call reads: voxel_size positive and finite, a finite origin, no NaN
 // among the log-odds parameters and finite hit / miss steps
-static int occ_args(mi_icp_ctx* c, const mi_icp_occgrid* o, const mi_icp_occgrid_params* p, const char* what, OccFrame* f) {
+static int occ_args(mi_icp_ctx* c, const mi_icp_occgrid* o, const mi_icp_occgrid_params* p, const char* what, GridFrame* f) {
     TRY(check_ctx(c));
     TRY(occ_check(c, o, what));
     if (!p) return fail(c, MI_ICP_ERR_INVALID, "%s: null parameters", what);
-    if (!(p->voxel_size > 0.0f) || !std::isfinite(p->voxel_size) || !finite3(p->origin))
-        return fail(c, MI_ICP_ERR_INVALID, "%s: voxel_size must be positive and finite, the origin finite", what);
+    TRY(frame_check(c, what, p->voxel_size, p->origin, f));
     if (std::isnan(p->clamping_thres_min) || std::isnan(p->clamping_thres_max) || !std::isfinite(p->prob_hit_log) ||
         !std::isfinite(p->prob_miss_log) || std::isnan(p->occ_prob_thres_log))
         return fail(c, MI_ICP_ERR_INVALID, "%s: a log-odds parameter is not a number", what);
-    f->vs = p->voxel_size;
-    for (int k = 0; k < 3; ++k) f->origin[k] = p->origin[k];
     return MI_ICP_OK;
 }
 
@@ -81,7 +92,7 @@ static int occ_allocate(mi_icp_ctx* c, mi_icp_occgrid* o, int resolution) {
     if (rc == MI_ICP_OK) rc = ensure(c, o->touch, (size_t)3 * resolution, &g.touch);
     if (rc == MI_ICP_OK) rc = ensure(c, o->state, (size_t)kOccStateWords, &g.state);
     if (rc != MI_ICP_OK) {
-        occgrid_release(o);
+        o->free_buffers();
         return rc;
     }
     // (whole buffers: a grid rebuilt smaller keeps its larger ones, and everything past the marks in use stays zero)
@@ -91,12 +102,6 @@ static int occ_allocate(mi_icp_ctx* c, mi_icp_occgrid* o, int resolution) {
     occ_reset<<<blocks_for(g.n), 256, 0, c->stream>>>(g);
     KCHK(c);
     for (int k = 0; k < 6; ++k) o->bounds[k] = g.h_res;
-    return MI_ICP_OK;
-}
-
-static int occ_resolution_ok(mi_icp_ctx* c, int resolution, const char* what) {
-    if (resolution < 2 || resolution > MI_ICP_OCCGRID_MAX_RESOLUTION)
-        return fail(c, MI_ICP_ERR_INVALID, "%s: the resolution must be in [2, %d]", what, MI_ICP_OCCGRID_MAX_RESOLUTION);
     return MI_ICP_OK;
 }
 
@@ -120,36 +125,18 @@ static int occ_sweep_and_wait(mi_icp_ctx* c, mi_icp_occgrid* o, const mi_icp_occ
     return MI_ICP_OK;
 }
 
-// the bounds box, or an empty one (a SetFreeArea beside the grid leaves min > max on an axis)
-static OccBox occ_bounds_box(const mi_icp_occgrid* o) {
-    OccBox b = {};
-    const int* lo = o->bounds;
-    const int* hi = o->bounds + 3;
-    if (lo[0] > hi[0] || lo[1] > hi[1] || lo[2] > hi[2]) return b;
-    b.x0 = lo[0];
-    b.y0 = lo[1];
-    b.z0 = lo[2];
-    b.ex = hi[0] - lo[0] + 1;
-    b.ey = hi[1] - lo[1] + 1;
-    b.ez = hi[2] - lo[2] + 1;
-    b.count = (int64_t)b.ex * b.ey * b.ez;
-    return b;
-}
-
-static int host_floor_int(float x) { return (int)std::fmin(std::fmax(std::floor(x), -1.0e9f), 1.0e9f); }
-
 extern "C" {
 
 int mi_icp_occgrid_create(mi_icp_ctx* c, int resolution, mi_icp_occgrid** out) {
     TRY(check_ctx(c));
     if (!out) return fail(c, MI_ICP_ERR_INVALID, "occgrid_create: out is null");
     *out = nullptr;
-    TRY(occ_resolution_ok(c, resolution, "occgrid_create"));
+    TRY(resolution_ok(c, "occgrid_create", resolution, MI_ICP_OCCGRID_MAX_RESOLUTION));
     mi_icp_occgrid* o = new mi_icp_occgrid;
     o->owner = c;
     const int rc = occ_allocate(c, o, resolution);
     if (rc != MI_ICP_OK) {
-        occgrid_release(o);
+        o->free_buffers();
         delete o;
         return rc;
     }
@@ -159,14 +146,7 @@ int mi_icp_occgrid_create(mi_icp_ctx* c, int resolution, mi_icp_occgrid** out) {
 }
 
 int mi_icp_occgrid_destroy(mi_icp_ctx* c, mi_icp_occgrid* o) {
-    TRY(check_ctx(c));
-    if (!o) return MI_ICP_OK;
-    TRY(occ_check(c, o, "occgrid_destroy"));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->occ_grids.erase(std::find(c->occ_grids.begin(), c->occ_grids.end(), o));
-    occgrid_release(o);
-    delete o;
-    return MI_ICP_OK;
+    return handle_destroy(c, o, c->occ_grids, "occgrid_destroy", "grid");
 }
 
 int mi_icp_occgrid_reset(mi_icp_ctx* c, mi_icp_occgrid* o) {
@@ -181,21 +161,18 @@ int mi_icp_occgrid_reset(mi_icp_ctx* c, mi_icp_occgrid* o) {
 int mi_icp_occgrid_reconstruct(mi_icp_ctx* c, mi_icp_occgrid* o, int resolution) {
     TRY(check_ctx(c));
     TRY(occ_check(c, o, "occgrid_reconstruct"));
-    TRY(occ_resolution_ok(c, resolution, "occgrid_reconstruct"));
+    TRY(resolution_ok(c, "occgrid_reconstruct", resolution, MI_ICP_OCCGRID_MAX_RESOLUTION));
     const int rc = occ_allocate(c, o, resolution);
-    if (rc != MI_ICP_OK) {  // no planes left: the handle is gone
-        c->occ_grids.erase(std::find(c->occ_grids.begin(), c->occ_grids.end(), o));
-        delete o;
-    }
+    if (rc != MI_ICP_OK) handle_drop(o, c->occ_grids);  // no planes left: the handle is gone
     return rc;
 }
 
 int mi_icp_occgrid_insert(mi_icp_ctx* c, mi_icp_occgrid* o, const mi_icp_occgrid_params* p, const float* points, int64_t n,
                           const float* viewpoint3, float max_range) {
     const char* what = "occgrid_insert";
-    OccFrame f;
+    GridFrame f;
     TRY(occ_args(c, o, p, what, &f));
-    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    TRY(count_ok(c, what, n));
     if (n == 0) return MI_ICP_OK;
     if (!points || !finite3(viewpoint3) || std::isnan(max_range))
         return fail(c, MI_ICP_ERR_INVALID, "%s: null points, or a viewpoint or range that is not a number", what);
@@ -220,9 +197,9 @@ int mi_icp_occgrid_insert(mi_icp_ctx* c, mi_icp_occgrid* o, const mi_icp_occgrid
 int mi_icp_occgrid_add_voxels(mi_icp_ctx* c, mi_icp_occgrid* o, const mi_icp_occgrid_params* p, const int32_t* indices,
                               int64_t n, int occupied) {
     const char* what = "occgrid_add_voxels";
-    OccFrame f;
+    GridFrame f;
     TRY(occ_args(c, o, p, what, &f));
-    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    TRY(count_ok(c, what, n));
     if (n == 0) return MI_ICP_OK;
     if (!indices) return fail(c, MI_ICP_ERR_INVALID, "%s: null indices", what);
     const OccGrid& g = o->g;
@@ -237,20 +214,20 @@ int mi_icp_occgrid_add_voxels(mi_icp_ctx* c, mi_icp_occgrid* o, const mi_icp_occ
 int mi_icp_occgrid_set_free_area(mi_icp_ctx* c, mi_icp_occgrid* o, const mi_icp_occgrid_params* p, const float* min3,
                                  const float* max3) {
     const char* what = "occgrid_set_free_area";
-    OccFrame f;
+    GridFrame f;
     TRY(occ_args(c, o, p, what, &f));
     if (!finite3(min3) || !finite3(max3)) return fail(c, MI_ICP_ERR_INVALID, "%s: a corner is not a number", what);
     const OccGrid& g = o->g;
     int lo[3], hi[3];
     for (int k = 0; k < 3; ++k) {
-        lo[k] = std::max(host_floor_int((min3[k] - f.origin[k]) / f.vs) + g.h_res, 0);
-        hi[k] = std::min(host_floor_int((max3[k] - f.origin[k]) / f.vs) + g.h_res, g.res - 1);
+        lo[k] = std::max(cell_of(f, min3[k], k) + g.h_res, 0);
+        hi[k] = std::min(cell_of(f, max3[k], k) + g.h_res, g.res - 1);
     }
     for (int k = 0; k < 3; ++k) {
         o->bounds[k] = lo[k];
         o->bounds[3 + k] = hi[k];
     }
-    const OccBox b = occ_bounds_box(o);
+    const GridBox b = box_of_bounds(o->bounds);
     occ_free_box<<<blocks_for(b.count), 256, 0, c->stream>>>(g, b, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], p->prob_miss_log);
     KCHK(c);
     return MI_ICP_OK;
@@ -259,9 +236,9 @@ int mi_icp_occgrid_set_free_area(mi_icp_ctx* c, mi_icp_occgrid* o, const mi_icp_
 int mi_icp_occgrid_query(mi_icp_ctx* c, mi_icp_occgrid* o, const mi_icp_occgrid_params* p, const float* points, int64_t n,
                          float* out_prob_log, int32_t* out_index) {
     const char* what = "occgrid_query";
-    OccFrame f;
+    GridFrame f;
     TRY(occ_args(c, o, p, what, &f));
-    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
+    TRY(count_ok(c, what, n));
     if (n == 0) return MI_ICP_OK;
     if (!points || !out_prob_log) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
     occ_query<<<blocks_for(n), 256, 0, c->stream>>>(o->g, f, points, n, out_prob_log, out_index);
@@ -272,28 +249,15 @@ int mi_icp_occgrid_query(mi_icp_ctx* c, mi_icp_occgrid* o, const mi_icp_occgrid_
 int mi_icp_occgrid_extract(mi_icp_ctx* c, mi_icp_occgrid* o, const mi_icp_occgrid_params* p, int which, int32_t* out_index,
                            float* out_prob_log, float* out_xyz, int64_t capacity, int64_t* m) {
     const char* what = "occgrid_extract";
-    OccFrame f;
+    GridFrame f;
     TRY(occ_args(c, o, p, what, &f));
     if (!m) return fail(c, MI_ICP_ERR_INVALID, "%s: m is null", what);
     *m = 0;
     if (which < MI_ICP_OCCGRID_KNOWN || which > MI_ICP_OCCGRID_OCCUPIED || capacity < 0)
         return fail(c, MI_ICP_ERR_INVALID, "%s: bad selection or negative capacity", what);
-    const OccBox b = occ_bounds_box(o);
-    if (b.count == 0) return MI_ICP_OK;
-    uint32_t *flags, *pos;
-    const uint32_t* total;
-    TRY(ensure(c, c->flags, (size_t)b.count, &flags));
-    occ_box_flags<<<blocks_for(b.count), 256, 0, c->stream>>>(o->g, b, which, p->occ_prob_thres_log, flags);
-    KCHK(c);
-    TRY(scan_flags(c, flags, b.count, &pos, &total));
-    TRY(read_total(c, total));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const int64_t cnt = (int64_t)c->u_host[0];
-    *m = cnt;
-    if (cnt == 0 || capacity < cnt) return MI_ICP_OK;  // nothing is written: the caller learns the room to make
-    occ_box_gather<<<blocks_for(b.count), 256, 0, c->stream>>>(o->g, b, f, flags, pos, out_index, out_prob_log, out_xyz);
-    KCHK(c);
-    return MI_ICP_OK;
+    TRY(occgrid_select(c, o, which, p->occ_prob_thres_log, m));
+    if (*m == 0 || capacity < *m) return MI_ICP_OK;  // nothing is written: the caller learns the room to make
+    return occgrid_gather(c, o, f, out_index, out_prob_log, out_xyz);
 }
 
 int mi_icp_occgrid_get_bounds(mi_icp_ctx* c, mi_icp_occgrid* o, int32_t* min3, int32_t* max3) {

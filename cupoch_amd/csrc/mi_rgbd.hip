@@ -62,7 +62,7 @@ int mi_icp_create_from_depth(mi_icp_ctx* c, const void* depth, int depth_type, c
         return fail(c, MI_ICP_ERR_INVALID, "create_from_depth: color and color_type disagree");
     const int64_t npix = (int64_t)width * height;
     const int64_t count = (int64_t)(width / stride) * (height / stride);
-    if (npix > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "create_from_depth: image too large");
+    if (npix > kMaxCount) return fail(c, MI_ICP_ERR_INVALID, "create_from_depth: image too large");
     if (count == 0) return MI_ICP_OK;
     if (!depth || !out_xyz || (color && !out_colors) || (compute_normals && !out_normals))
         return fail(c, MI_ICP_ERR_INVALID, "create_from_depth: null buffer");

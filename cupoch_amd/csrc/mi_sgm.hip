@@ -20,29 +20,19 @@ struct mi_icp_sgm {
     uint16_t* lmap = nullptr;   // the left map before its median
     uint32_t* rcand = nullptr;  // the right map before its median, as (S << 8 | d) or kSgmNoCandidate
     bool has_frame = false;
+    void free_buffers() {
+        for (int k = 0; k < 2; ++k)
+            if (census[k]) (void)hipFree(census[k]);
+        if (vol) (void)hipFree(vol);
+        if (lmap) (void)hipFree(lmap);
+        if (rcand) (void)hipFree(rcand);
+    }
 };
 
-static void sgm_free(mi_icp_sgm* s) {
-    for (int k = 0; k < 2; ++k)
-        if (s->census[k]) (void)hipFree(s->census[k]);
-    if (s->vol) (void)hipFree(s->vol);
-    if (s->lmap) (void)hipFree(s->lmap);
-    if (s->rcand) (void)hipFree(s->rcand);
-    delete s;
-}
-
-namespace mi {
-namespace eng {
-void sgm_release_all(mi_icp_ctx* c) {
-    for (mi_icp_sgm* s : c->sgm_matchers) sgm_free(s);
-    c->sgm_matchers.clear();
-}
-}  // namespace eng
-}  // namespace mi
+void mi::eng::sgm_release_all(mi_icp_ctx* c) { handle_release_all(c->sgm_matchers); }
 
 static int sgm_check(mi_icp_ctx* c, const mi_icp_sgm* s, const char* what) {
-    if (!owned(c, s, c->sgm_matchers)) return fail(c, MI_ICP_ERR_INVALID, "%s: not a matcher of this context", what);
-    return MI_ICP_OK;
+    return handle_check(c, s, c->sgm_matchers, what, "matcher");
 }
 
 static dim3 pixel_grid(int width, int height, int planes = 1) {
@@ -105,7 +95,8 @@ int mi_icp_sgm_create(mi_icp_ctx* c, int width, int height, int p1, int p2, floa
         hipMalloc((void**)&s->vol, total) != hipSuccess || hipMalloc((void**)&s->lmap, s->pixels * 2) != hipSuccess ||
         hipMalloc((void**)&s->rcand, s->pixels * 4) != hipSuccess) {
         (void)hipGetLastError();
-        sgm_free(s);
+        s->free_buffers();
+        delete s;
         return fail(c, MI_ICP_ERR_HIP, "%s: out of memory for the workspace (%zu bytes of path costs)", what, total);
     }
     c->sgm_matchers.push_back(s);
@@ -114,13 +105,7 @@ int mi_icp_sgm_create(mi_icp_ctx* c, int width, int height, int p1, int p2, floa
 }
 
 int mi_icp_sgm_destroy(mi_icp_ctx* c, mi_icp_sgm* s) {
-    TRY(check_ctx(c));
-    if (!s) return MI_ICP_OK;
-    TRY(sgm_check(c, s, "sgm_destroy"));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->sgm_matchers.erase(std::find(c->sgm_matchers.begin(), c->sgm_matchers.end(), s));
-    sgm_free(s);
-    return MI_ICP_OK;
+    return handle_destroy(c, s, c->sgm_matchers, "sgm_destroy", "matcher");
 }
 
 int mi_icp_sgm_census(mi_icp_ctx* c, const uint8_t* src, int width, int height, uint32_t* dst) {

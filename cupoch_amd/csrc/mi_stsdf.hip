@@ -22,6 +22,14 @@ struct mi_icp_stsdf {
     DevBuf fresh;   // a frame's new keys
     DevBuf edges;   // ExtractPointCloud's list of crossing edges
     TsdfMult mult;
+    void free_buffers() {
+        if (planes) (void)hipFree(planes);
+        for (int k = 0; k < 2; ++k)
+            if (dir[k]) (void)hipFree(dir[k]);
+        release(fresh);
+        release(edges);
+        release(mult.buf);
+    }
 };
 
 static int stsdf_planes_of(int color_type) { return color_type == MI_ICP_TSDF_NO_COLOR ? 2 : 5; }
@@ -44,16 +52,6 @@ static StsdfDir stsdf_dir(const mi_icp_stsdf* t) {
     d.slots = dir_slots(t->dir[t->cur], t->capacity);
     d.n = t->n_units;
     return d;
-}
-
-static void stsdf_free(mi_icp_stsdf* t) {
-    if (t->planes) (void)hipFree(t->planes);
-    for (int k = 0; k < 2; ++k)
-        if (t->dir[k]) (void)hipFree(t->dir[k]);
-    release(t->fresh);
-    release(t->edges);
-    release(t->mult.buf);
-    delete t;
 }
 
 // Room for `capacity` units: new planes and directories, the open units' contents copied over.  Either everything is
@@ -91,17 +89,10 @@ static int stsdf_reserve(mi_icp_ctx* c, mi_icp_stsdf* t, int capacity) {
     return MI_ICP_OK;
 }
 
-namespace mi {
-namespace eng {
-void stsdf_release_all(mi_icp_ctx* c) {
-    for (mi_icp_stsdf* t : c->stsdf_volumes) stsdf_free(t);
-    c->stsdf_volumes.clear();
-}
-}  // namespace eng
-}  // namespace mi
+void mi::eng::stsdf_release_all(mi_icp_ctx* c) { handle_release_all(c->stsdf_volumes); }
 
 static int stsdf_check(mi_icp_ctx* c, const mi_icp_stsdf* t, const char* what) {
-    return tsdf_volume_check(c, t, c->stsdf_volumes, what);
+    return handle_check(c, t, c->stsdf_volumes, what, "volume");
 }
 
 // Stage 1 of Integrate: the units this frame's sampled points want and the directory lacks are opened.
@@ -120,7 +111,7 @@ static int stsdf_open_units(mi_icp_ctx* c, mi_icp_stsdf* t, const DepthArgs& a) 
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the wait of every frame: how many candidate keys
     const int64_t ncand = (int64_t)c->u_host[0];
     if (ncand == 0) return MI_ICP_OK;
-    if (ncand > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "stsdf_integrate: too many candidate units in one frame");
+    if (ncand > kMaxCount) return fail(c, MI_ICP_ERR_INVALID, "stsdf_integrate: too many candidate units in one frame");
 
     SortBuffers sb;
     TRY(sort_buffers(c, ncand, &sb));
@@ -182,7 +173,8 @@ int mi_icp_stsdf_create(mi_icp_ctx* c, float voxel_length, float sdf_trunc, int 
     t->v.p.color_type = color_type;
     const int rc = stsdf_reserve(c, t, map_size);
     if (rc != MI_ICP_OK) {
-        stsdf_free(t);
+        t->free_buffers();
+        delete t;
         return rc;
     }
     c->stsdf_volumes.push_back(t);
@@ -191,13 +183,7 @@ int mi_icp_stsdf_create(mi_icp_ctx* c, float voxel_length, float sdf_trunc, int 
 }
 
 int mi_icp_stsdf_destroy(mi_icp_ctx* c, mi_icp_stsdf* t) {
-    TRY(check_ctx(c));
-    if (!t) return MI_ICP_OK;
-    TRY(stsdf_check(c, t, "stsdf_destroy"));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->stsdf_volumes.erase(std::find(c->stsdf_volumes.begin(), c->stsdf_volumes.end(), t));
-    stsdf_free(t);
-    return MI_ICP_OK;
+    return handle_destroy(c, t, c->stsdf_volumes, "stsdf_destroy", "volume");
 }
 
 int mi_icp_stsdf_reset(mi_icp_ctx* c, mi_icp_stsdf* t) {

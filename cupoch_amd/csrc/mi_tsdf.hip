@@ -17,23 +17,16 @@ struct mi_icp_tsdf {
     float length = 0.0f, sdf_trunc = 0.0f;
     DevBuf planes;  // tsdf, weight and, with a colour type, three colour planes
     TsdfMult mult;
+    void free_buffers() {
+        release(planes);
+        release(mult.buf);
+    }
 };
 
-namespace mi {
-namespace eng {
-void tsdf_release_all(mi_icp_ctx* c) {
-    for (mi_icp_tsdf* t : c->tsdf_volumes) {
-        release(t->planes);
-        release(t->mult.buf);
-        delete t;
-    }
-    c->tsdf_volumes.clear();
-}
-}  // namespace eng
-}  // namespace mi
+void mi::eng::tsdf_release_all(mi_icp_ctx* c) { handle_release_all(c->tsdf_volumes); }
 
 static int tsdf_check(mi_icp_ctx* c, const mi_icp_tsdf* t, const char* what) {
-    return tsdf_volume_check(c, t, c->tsdf_volumes, what);
+    return handle_check(c, t, c->tsdf_volumes, what, "volume");
 }
 
 extern "C" {
@@ -67,7 +60,7 @@ int mi_icp_tsdf_create(mi_icp_ctx* c, float length, int resolution, float sdf_tr
     v.p = {base, base + n, color_type == MI_ICP_TSDF_NO_COLOR ? nullptr : base + 2 * n, n, color_type};
     tsdf_reset<<<blocks_for(n), 256, 0, c->stream>>>(v.p, 0, n);
     if (hipGetLastError() != hipSuccess) {
-        release(t->planes);
+        t->free_buffers();
         delete t;
         return fail(c, MI_ICP_ERR_HIP, "tsdf_create: launch failed");
     }
@@ -77,15 +70,7 @@ int mi_icp_tsdf_create(mi_icp_ctx* c, float length, int resolution, float sdf_tr
 }
 
 int mi_icp_tsdf_destroy(mi_icp_ctx* c, mi_icp_tsdf* t) {
-    TRY(check_ctx(c));
-    if (!t) return MI_ICP_OK;
-    TRY(tsdf_check(c, t, "tsdf_destroy"));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->tsdf_volumes.erase(std::find(c->tsdf_volumes.begin(), c->tsdf_volumes.end(), t));
-    release(t->planes);
-    release(t->mult.buf);
-    delete t;
-    return MI_ICP_OK;
+    return handle_destroy(c, t, c->tsdf_volumes, "tsdf_destroy", "volume");
 }
 
 int mi_icp_tsdf_reset(mi_icp_ctx* c, mi_icp_tsdf* t) {

@@ -14,21 +14,6 @@ using namespace mi::eng;
 // keys int32[m][3] + colors float[m][3] on the device and voxel_size / origin on the host: no handle, nothing kept
 // between calls but the context's scratch buffers.
 
-static bool finite3(const float* v) { return v && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
-
-static int vg_size_ok(mi_icp_ctx* c, const char* what, int64_t n) {
-    if (n < 0 || n > 0x7fffff00ll) return fail(c, MI_ICP_ERR_INVALID, "%s: bad size", what);
-    return MI_ICP_OK;
-}
-
-static int vg_frame(mi_icp_ctx* c, const char* what, float voxel_size, const float* origin3, VgFrame* f) {
-    if (!(voxel_size > 0.0f) || !std::isfinite(voxel_size) || !finite3(origin3))
-        return fail(c, MI_ICP_ERR_INVALID, "%s: voxel_size must be positive and finite, the origin finite", what);
-    f->vs = voxel_size;
-    for (int k = 0; k < 3; ++k) f->origin[k] = origin3[k];
-    return MI_ICP_OK;
-}
-
 static int bit_length(uint64_t v) {
     int b = 0;
     while (v) {
@@ -124,13 +109,13 @@ int mi_icp_voxelgrid_from_points(mi_icp_ctx* c, const float* xyz, const float* c
     TRY(check_ctx(c));
     if (!m) return fail(c, MI_ICP_ERR_INVALID, "%s: m is null", what);
     *m = 0;
-    TRY(vg_size_ok(c, what, n));
+    TRY(count_ok(c, what, n));
     if (capacity < 0) return fail(c, MI_ICP_ERR_INVALID, "%s: negative capacity", what);
-    VgFrame f;
+    GridFrame f;
     if (!(voxel_size > 0.0f) || !std::isfinite(voxel_size))
         return fail(c, MI_ICP_ERR_INVALID, "[VoxelGridFromPointCloud] voxel_size <= 0.");
     if (!finite3(min_bound3) || !finite3(max_bound3)) return fail(c, MI_ICP_ERR_INVALID, "%s: a bound is not a number", what);
-    TRY(vg_frame(c, what, voxel_size, min_bound3, &f));
+    TRY(frame_check(c, what, voxel_size, min_bound3, &f));
     const float span = std::max(std::max(max_bound3[0] - min_bound3[0], max_bound3[1] - min_bound3[1]), max_bound3[2] - min_bound3[2]);
     if (voxel_size * (float)INT_MAX < span) return fail(c, MI_ICP_ERR_INVALID, "[VoxelGridFromPointCloud] voxel_size is too small.");
     if (n == 0) return MI_ICP_OK;
@@ -179,9 +164,9 @@ int mi_icp_voxelgrid_merge(mi_icp_ctx* c, const int32_t* keys_a, const float* co
     TRY(check_ctx(c));
     if (!m) return fail(c, MI_ICP_ERR_INVALID, "%s: m is null", what);
     *m = 0;
-    TRY(vg_size_ok(c, what, m_a));
-    TRY(vg_size_ok(c, what, m_b));
-    TRY(vg_size_ok(c, what, m_a + m_b));
+    TRY(count_ok(c, what, m_a));
+    TRY(count_ok(c, what, m_b));
+    TRY(count_ok(c, what, m_a + m_b));
     if (capacity < 0) return fail(c, MI_ICP_ERR_INVALID, "%s: negative capacity", what);
     if (mode != MI_ICP_VOXELGRID_AVERAGE && mode != MI_ICP_VOXELGRID_KEEP_FIRST)
         return fail(c, MI_ICP_ERR_INVALID, "%s: bad mode", what);
@@ -223,9 +208,9 @@ int mi_icp_voxelgrid_carve(mi_icp_ctx* c, const int32_t* keys, const float* colo
     TRY(check_ctx(c));
     if (!m_out) return fail(c, MI_ICP_ERR_INVALID, "%s: m_out is null", what);
     *m_out = 0;
-    TRY(vg_size_ok(c, what, m));
-    VgFrame f;
-    TRY(vg_frame(c, what, voxel_size, origin3, &f));
+    TRY(count_ok(c, what, m));
+    GridFrame f;
+    TRY(frame_check(c, what, voxel_size, origin3, &f));
     if (width < 2 || height < 2) return fail(c, MI_ICP_ERR_INVALID, "%s: the image must be at least 2 x 2", what);
     if (channels < 1 || bytes_per_channel < 1 || !intrinsic4) return fail(c, MI_ICP_ERR_INVALID, "%s: bad image or camera", what);
     VgCamera cam;
@@ -264,10 +249,10 @@ int mi_icp_voxelgrid_query(mi_icp_ctx* c, const int32_t* keys, int64_t m, int ke
                            const float* queries, int64_t nq, uint8_t* out_included, int32_t* out_index) {
     const char* what = "voxelgrid_query";
     TRY(check_ctx(c));
-    TRY(vg_size_ok(c, what, m));
-    TRY(vg_size_ok(c, what, nq));
-    VgFrame f;
-    TRY(vg_frame(c, what, voxel_size, origin3, &f));
+    TRY(count_ok(c, what, m));
+    TRY(count_ok(c, what, nq));
+    GridFrame f;
+    TRY(frame_check(c, what, voxel_size, origin3, &f));
     if (nq == 0) return MI_ICP_OK;
     if (!queries || !out_included || (m > 0 && !keys)) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
     const int32_t* sorted = keys;
@@ -291,13 +276,13 @@ int mi_icp_voxelgrid_bounds(mi_icp_ctx* c, const int32_t* keys, int64_t m, float
                             int32_t* out_min_index3, int32_t* out_max_index3, double* out_center_sum3) {
     const char* what = "voxelgrid_bounds";
     TRY(check_ctx(c));
-    TRY(vg_size_ok(c, what, m));
+    TRY(count_ok(c, what, m));
     if (!out_min_index3 || !out_max_index3 || !out_center_sum3) return fail(c, MI_ICP_ERR_INVALID, "%s: null output", what);
     if (m == 0) return fail(c, MI_ICP_ERR_INVALID, "%s: an empty grid has no index bounds", what);
     if (!keys) return fail(c, MI_ICP_ERR_INVALID, "%s: null keys", what);
     // (voxel_size may be anything finite here: Clear() leaves 0, Scale may make it negative)
     if (!std::isfinite(voxel_size) || !finite3(origin3)) return fail(c, MI_ICP_ERR_INVALID, "%s: voxel_size or origin is not finite", what);
-    VgFrame f;
+    GridFrame f;
     f.vs = voxel_size;
     for (int k = 0; k < 3; ++k) f.origin[k] = origin3[k];
     int32_t *ipart, *iout;
@@ -327,8 +312,8 @@ int mi_icp_voxelgrid_select_by_index(mi_icp_ctx* c, const int32_t* keys, const f
     TRY(check_ctx(c));
     if (!m_out) return fail(c, MI_ICP_ERR_INVALID, "%s: m_out is null", what);
     *m_out = 0;
-    TRY(vg_size_ok(c, what, m));
-    TRY(vg_size_ok(c, what, n_indices));
+    TRY(count_ok(c, what, m));
+    TRY(count_ok(c, what, n_indices));
     if ((m > 0 && (!keys || !colors)) || (n_indices > 0 && !indices)) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
     const int64_t count = invert ? m : n_indices;
     if (count > 0 && (!out_keys || !out_colors)) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
@@ -371,8 +356,8 @@ int mi_icp_voxelgrid_select_by_index(mi_icp_ctx* c, const int32_t* keys, const f
 int mi_icp_voxelgrid_paint(mi_icp_ctx* c, float* colors, int64_t m, const int64_t* indices, int64_t n_indices, const float* color3) {
     const char* what = "voxelgrid_paint";
     TRY(check_ctx(c));
-    TRY(vg_size_ok(c, what, m));
-    TRY(vg_size_ok(c, what, n_indices));
+    TRY(count_ok(c, what, m));
+    TRY(count_ok(c, what, n_indices));
     if (!color3) return fail(c, MI_ICP_ERR_INVALID, "%s: null colour", what);
     if (!indices && n_indices > 0) return fail(c, MI_ICP_ERR_INVALID, "%s: null indices", what);
     const int64_t count = indices ? n_indices : m;

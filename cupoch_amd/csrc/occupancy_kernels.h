@@ -24,6 +24,7 @@
 // No kernel here keeps an array that is indexed at run time: none uses scratch memory.
 #pragma once
 #include "device_utils.h"
+#include "grid_rules.h"
 
 namespace mi {
 
@@ -42,26 +43,10 @@ struct OccGrid {
     int res, h_res;
 };
 
-struct OccFrame {  // voxel_size_ and origin_ at the time of the call
-    float vs;
-    float origin[3];
-};
-
 struct OccRays {  // Insert's viewpoint and range
     float vp[3];
     float max_range;
 };
-
-// floor to int with the value held inside +-1e9 first (a NaN becomes -1e9): no conversion is undefined
-__device__ __forceinline__ int occ_floor_int(float x) { return (int)fminf(fmaxf(floorf(x), -1.0e9f), 1.0e9f); }
-
-__device__ __forceinline__ bool occ_inside(const OccGrid& g, int x, int y, int z) {
-    return x >= 0 && x < g.res && y >= 0 && y < g.res && z >= 0 && z < g.res;
-}
-
-__device__ __forceinline__ int64_t occ_index(const OccGrid& g, int x, int y, int z) {
-    return ((int64_t)x * g.res + y) * g.res + z;
-}
 
 // every voxel unknown, the bounds back to (h, h, h)
 static __global__ __launch_bounds__(256) void occ_reset(OccGrid g) {
@@ -97,11 +82,19 @@ __device__ __forceinline__ int occ_ranged_point(const float* __restrict__ pts, i
     return 2;
 }
 
+// the maximum of r over the workgroup's four waves
+__device__ __forceinline__ uint32_t occ_block_max(uint32_t r) {
+    __shared__ uint32_t wmax[4];
+    r = wave_max(r);
+    if (lane_id() == 0) wmax[threadIdx.x >> 6] = r;
+    __syncthreads();
+    return max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+}
+
 // part[block] = the bits of max_k |q_k - viewpoint_k| over the block's points.  The values are not negative, so their
 // bits order as they do, and a NaN (sign cleared) lies above them all: it reaches occ_plan, which refuses.
 static __global__ __launch_bounds__(256) void occ_prepare(const float* __restrict__ pts, int64_t n, OccRays a,
                                                          uint32_t* __restrict__ part) {
-    __shared__ uint32_t wmax[4];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t r = 0;
     float qx, qy, qz;
@@ -109,26 +102,19 @@ static __global__ __launch_bounds__(256) void occ_prepare(const float* __restric
         r = max(max(__float_as_uint(fabsf(qx - a.vp[0])), __float_as_uint(fabsf(qy - a.vp[1]))),
                 __float_as_uint(fabsf(qz - a.vp[2])));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) r = max(r, (uint32_t)__shfl_down((int)r, o, 64));
-    if (lane_id() == 0) wmax[threadIdx.x >> 6] = r;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+    r = occ_block_max(r);
+    if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
 // one workgroup: n_div = (int)ceil(max r / voxel_size), n_buf = 3 (n_div + 1); a count above max_ndiv (or no number)
 // refuses the call: the marking kernels then do nothing
 static __global__ __launch_bounds__(256) void occ_plan(OccGrid g, const uint32_t* __restrict__ part, int64_t nparts, float vs,
                                                       int max_ndiv) {
-    __shared__ uint32_t wmax[4];
     uint32_t r = 0;
     for (int64_t i = threadIdx.x; i < nparts; i += 256) r = max(r, part[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) r = max(r, (uint32_t)__shfl_down((int)r, o, 64));
-    if (lane_id() == 0) wmax[threadIdx.x >> 6] = r;
-    __syncthreads();
+    r = occ_block_max(r);
     if (threadIdx.x != 0) return;
-    const float max_r = __uint_as_float(max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
+    const float max_r = __uint_as_float(r);
     const float nd = ceilf(max_r / vs);
     const bool ok = nd <= (float)max_ndiv;  // (false for a NaN)
     g.state[kOccNDiv] = ok ? (int)nd : 0;
@@ -146,9 +132,9 @@ __device__ __forceinline__ bool occ_gone(int c, int step, const OccGrid& g) {
 __device__ __forceinline__ void occ_mark_at(const OccGrid& g, int x, int y, int z, uint8_t value, bool all_axes, int axis,
                                             bool* in) {
     const int ix = x + g.h_res, iy = y + g.h_res, iz = z + g.h_res;
-    *in = occ_inside(g, ix, iy, iz);
+    *in = cube_inside(g.res, ix, iy, iz);
     if (!*in) return;
-    g.marks[occ_index(g, ix, iy, iz)] = value;
+    g.marks[cube_index(g.res, ix, iy, iz)] = value;
     if (all_axes || axis == 0) g.touch[ix] = 1;
     if (all_axes || axis == 1) g.touch[g.res + iy] = 1;
     if (all_axes || axis == 2) g.touch[2 * g.res + iz] = 1;
@@ -159,7 +145,7 @@ __device__ __forceinline__ void occ_mark_at(const OccGrid& g, int x, int y, int 
 // and at most n_buf voxels are.  A walk that has left the grid on an axis it does not step back along can only emit
 // voxels outside the grid: it stops.  One that starts outside walks on exactly, its state must be the reference's
 // when it enters.
-static __global__ __launch_bounds__(256) void occ_mark_rays(OccGrid g, OccFrame f, const float* __restrict__ pts, int64_t n,
+static __global__ __launch_bounds__(256) void occ_mark_rays(OccGrid g, GridFrame f, const float* __restrict__ pts, int64_t n,
                                                            OccRays a) {
     const int n_buf = g.state[kOccNBuf];
     if (g.state[kOccBad] || g.state[kOccNDiv] <= 0) return;
@@ -175,8 +161,8 @@ static __global__ __launch_bounds__(256) void occ_mark_rays(OccGrid g, OccFrame 
     rx = rx / length;
     ry = ry / length;
     rz = rz / length;
-    int cx = occ_floor_int(sx / vs), cy = occ_floor_int(sy / vs), cz = occ_floor_int(sz / vs);
-    const int lx = occ_floor_int(ex / vs), ly = occ_floor_int(ey / vs), lz = occ_floor_int(ez / vs);
+    int cx = floor_int(sx / vs), cy = floor_int(sy / vs), cz = floor_int(sz / vs);
+    const int lx = floor_int(ex / vs), ly = floor_int(ey / vs), lz = floor_int(ez / vs);
     const int stx = rx > 0.0f ? 1 : (rx < 0.0f ? -1 : 0);
     const int sty = ry > 0.0f ? 1 : (ry < 0.0f ? -1 : 0);
     const int stz = rz > 0.0f ? 1 : (rz < 0.0f ? -1 : 0);
@@ -222,22 +208,21 @@ static __global__ __launch_bounds__(256) void occ_mark_rays(OccGrid g, OccFrame 
 }
 
 // the voxels of the hit points: floor((q - origin) / vs) + h
-static __global__ __launch_bounds__(256) void occ_mark_hits(OccGrid g, OccFrame f, const float* __restrict__ pts, int64_t n,
+static __global__ __launch_bounds__(256) void occ_mark_hits(OccGrid g, GridFrame f, const float* __restrict__ pts, int64_t n,
                                                            OccRays a) {
     if (g.state[kOccBad]) return;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     float qx, qy, qz;
     if (i >= n || occ_ranged_point(pts, i, a, &qx, &qy, &qz) != 1) return;
     bool in;
-    occ_mark_at(g, occ_floor_int((qx - f.origin[0]) / f.vs), occ_floor_int((qy - f.origin[1]) / f.vs),
-                occ_floor_int((qz - f.origin[2]) / f.vs), kOccHit, true, 0, &in);
+    occ_mark_at(g, cell_of(f, qx, 0), cell_of(f, qy, 1), cell_of(f, qz, 2), kOccHit, true, 0, &in);
 }
 
 // AddVoxels: an index outside the grid refuses the whole list
 static __global__ __launch_bounds__(256) void occ_check_indices(OccGrid g, const int32_t* __restrict__ idx, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    if (!occ_inside(g, idx[i * 3], idx[i * 3 + 1], idx[i * 3 + 2])) g.state[kOccBad] = kOccBadIndex;
+    if (!cube_inside(g.res, idx[i * 3], idx[i * 3 + 1], idx[i * 3 + 2])) g.state[kOccBad] = kOccBadIndex;
 }
 
 static __global__ __launch_bounds__(256) void occ_mark_indices(OccGrid g, const int32_t* __restrict__ idx, int64_t n,
@@ -307,21 +292,8 @@ static __global__ __launch_bounds__(256) void occ_bounds(OccGrid g) {
     }
 }
 
-struct OccBox {  // the voxels [x0, x0+ex) x [y0, y0+ey) x [z0, z0+ez), count of them; all inside the grid
-    int x0, y0, z0, ex, ey, ez;
-    int64_t count;
-};
-
-__device__ __forceinline__ void occ_box_voxel(const OccBox& b, int64_t t, int* x, int* y, int* z) {
-    const int64_t eyz = (int64_t)b.ey * b.ez;
-    const int yz = (int)(t % eyz);
-    *x = b.x0 + (int)(t / eyz);
-    *y = b.y0 + yz / b.ez;
-    *z = b.z0 + yz % b.ez;
-}
-
 // SetFreeArea: the bounds are OVERWRITTEN with (lo, hi) and every voxel of the box gets the miss, unclamped
-static __global__ __launch_bounds__(256) void occ_free_box(OccGrid g, OccBox b, int lo0, int lo1, int lo2, int hi0, int hi1,
+static __global__ __launch_bounds__(256) void occ_free_box(OccGrid g, GridBox b, int lo0, int lo1, int lo2, int hi0, int hi1,
                                                           int hi2, float miss) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t == 0) {
@@ -334,22 +306,22 @@ static __global__ __launch_bounds__(256) void occ_free_box(OccGrid g, OccBox b, 
     }
     if (t >= b.count) return;
     int x, y, z;
-    occ_box_voxel(b, t, &x, &y, &z);
-    const int64_t i = occ_index(g, x, y, z);
+    box_voxel(b, t, &x, &y, &z);
+    const int64_t i = cube_index(g.res, x, y, z);
     float p = g.prob[i];
     p = isnan(p) ? 0.0f : p;
     g.prob[i] = p + miss;
 }
 
 // the voxel of a point, floor((p - origin) / vs) + h per axis, and its log-odds; NaN outside the grid on any axis
-static __global__ __launch_bounds__(256) void occ_query(OccGrid g, OccFrame f, const float* __restrict__ pts, int64_t n,
+static __global__ __launch_bounds__(256) void occ_query(OccGrid g, GridFrame f, const float* __restrict__ pts, int64_t n,
                                                        float* __restrict__ oprob, int32_t* __restrict__ oidx) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int x = occ_floor_int((pts[i * 3] - f.origin[0]) / f.vs) + g.h_res;
-    const int y = occ_floor_int((pts[i * 3 + 1] - f.origin[1]) / f.vs) + g.h_res;
-    const int z = occ_floor_int((pts[i * 3 + 2] - f.origin[2]) / f.vs) + g.h_res;
-    oprob[i] = occ_inside(g, x, y, z) ? g.prob[occ_index(g, x, y, z)] : __builtin_nanf("");
+    const int x = cell_of(f, pts[i * 3], 0) + g.h_res;
+    const int y = cell_of(f, pts[i * 3 + 1], 1) + g.h_res;
+    const int z = cell_of(f, pts[i * 3 + 2], 2) + g.h_res;
+    oprob[i] = cube_inside(g.res, x, y, z) ? g.prob[cube_index(g.res, x, y, z)] : __builtin_nanf("");
     if (oidx) {
         oidx[i * 3] = x;
         oidx[i * 3 + 1] = y;
@@ -358,32 +330,32 @@ static __global__ __launch_bounds__(256) void occ_query(OccGrid g, OccFrame f, c
 }
 
 // which: 0 known, 1 free (known && p <= thres), 2 occupied (known && p > thres)
-static __global__ __launch_bounds__(256) void occ_box_flags(OccGrid g, OccBox b, int which, float thres,
+static __global__ __launch_bounds__(256) void occ_box_flags(OccGrid g, GridBox b, int which, float thres,
                                                            uint32_t* __restrict__ flags) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= b.count) return;
     int x, y, z;
-    occ_box_voxel(b, t, &x, &y, &z);
-    const float p = g.prob[occ_index(g, x, y, z)];
+    box_voxel(b, t, &x, &y, &z);
+    const float p = g.prob[cube_index(g.res, x, y, z)];
     const bool known = !isnan(p);
-    flags[t] = (known && (which == 0 || (which == 1 ? p <= thres : p > thres))) ? 1u : 0u;
+    flags[t] = (known && (which == 0 || (which == 1 ? p <= thres : occupied(p, thres)))) ? 1u : 0u;
 }
 
 // the flagged voxels: index, log-odds and (CreateFromOccupancyGrid) the point (index + (0.5 - h)) * vs + origin
-static __global__ __launch_bounds__(256) void occ_box_gather(OccGrid g, OccBox b, OccFrame f, const uint32_t* __restrict__ flags,
+static __global__ __launch_bounds__(256) void occ_box_gather(OccGrid g, GridBox b, GridFrame f, const uint32_t* __restrict__ flags,
                                                             const uint32_t* __restrict__ pos, int32_t* __restrict__ oidx,
                                                             float* __restrict__ oprob, float* __restrict__ oxyz) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= b.count || !flags[t]) return;
     int x, y, z;
-    occ_box_voxel(b, t, &x, &y, &z);
+    box_voxel(b, t, &x, &y, &z);
     const int64_t p = pos[t];
     if (oidx) {
         oidx[p * 3] = x;
         oidx[p * 3 + 1] = y;
         oidx[p * 3 + 2] = z;
     }
-    if (oprob) oprob[p] = g.prob[occ_index(g, x, y, z)];
+    if (oprob) oprob[p] = g.prob[cube_index(g.res, x, y, z)];
     if (oxyz) {
         const float c = (float)(0.5 - (double)g.h_res);
         oxyz[p * 3] = ((float)x + c) * f.vs + f.origin[0];

@@ -96,8 +96,8 @@ static __global__ __launch_bounds__(256) void stsdf_open(DepthArgs a, int64_t co
         int lo[3], hi[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            lo[k] = tsdf_floor_int((p[k] - trunc) / L);
-            hi[k] = min(tsdf_floor_int((p[k] + trunc) / L), lo[k] + 3);  // (sdf_trunc <= L: never more than three apart)
+            lo[k] = floor_int((p[k] - trunc) / L);
+            hi[k] = min(floor_int((p[k] + trunc) / L), lo[k] + 3);  // (sdf_trunc <= L: never more than three apart)
         }
         const uint32_t base = WRITE ? pos[idx] : 0u;
         for (int x = lo[0]; x <= hi[0]; ++x)
@@ -245,7 +245,7 @@ __device__ __forceinline__ float stsdf_at(const StsdfVol& v, const StsdfDir& dir
     const float pl[3] = {p0 - v.half, p1 - v.half, p2 - v.half};
     int u[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) u[k] = tsdf_floor_int(pl[k] / v.unit_length);
+    for (int k = 0; k < 3; ++k) u[k] = floor_int(pl[k] / v.unit_length);
     const int s0 = stsdf_find(dir, u[0], u[1], u[2]);
     if (s0 < 0) return 0.0f;
     int i[3];
@@ -253,7 +253,7 @@ __device__ __forceinline__ float stsdf_at(const StsdfVol& v, const StsdfDir& dir
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float g = (pl[k] - (float)u[k] * v.unit_length) / v.voxel_length;
-        i[k] = min(max(tsdf_floor_int(g), 0), kStsdfRes - 1);
+        i[k] = min(max(floor_int(g), 0), kStsdfRes - 1);
         r[k] = g - (float)i[k];
     }
     // the corners (dx, dy, dz); a coordinate of 16 is coordinate 0 of the next unit along that axis

@@ -1,5 +1,5 @@
 // tsdf_host.h -- the host side that mi_tsdf.hip (UniformTSDFVolume) and mi_stsdf.hip (ScalableTSDFVolume) share: the
-// volume-handle check, the checks of an Integrate frame, the cached multiplier image, the filling of TsdfIntegrate and
+// checks of an Integrate frame, the cached multiplier image, the filling of TsdfIntegrate and
 // the argument checks of the extractions.  The kernels' shared parts are in tsdf_kernels.h.
 #pragma once
 #include "ctx.h"
@@ -7,12 +7,6 @@
 
 namespace mi {
 namespace eng {
-
-template <class T>
-int tsdf_volume_check(mi_icp_ctx* c, const T* t, const std::vector<T*>& list, const char* what) {
-    if (!owned(c, t, list)) return fail(c, MI_ICP_ERR_INVALID, "%s: not a volume of this context", what);
-    return MI_ICP_OK;
-}
 
 // an image as the reference's Image describes it
 struct TsdfImage {
@@ -91,7 +85,7 @@ template <class T>
 int tsdf_extract_args(mi_icp_ctx* c, const T* t, const std::vector<T*>& list, const char* what, int64_t capacity, int64_t* m,
                       int mem_kind) {
     TRY(check_sizes(c, what, 0, m, mem_kind));
-    TRY(tsdf_volume_check(c, t, list, what));
+    TRY(handle_check(c, t, list, what, "volume"));
     if (capacity < 0) return fail(c, MI_ICP_ERR_INVALID, "%s: negative capacity", what);
     return MI_ICP_OK;
 }

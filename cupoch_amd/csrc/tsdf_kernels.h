@@ -22,6 +22,7 @@
 // No kernel here keeps an array that is indexed at run time: none uses scratch memory.
 #pragma once
 #include "device_utils.h"
+#include "grid_rules.h"
 
 namespace mi {
 
@@ -167,9 +168,6 @@ static __global__ __launch_bounds__(256) void tsdf_integrate(TsdfVol v, TsdfInte
 // ---- extraction -----------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool tsdf_valid(float w, float f) { return w != 0.0f && f < 0.98f && f >= -0.98f; }
 
-// floor to int with the value held inside +-1e9 first (a NaN becomes -1e9): no conversion is undefined
-__device__ __forceinline__ int tsdf_floor_int(float x) { return (int)fminf(fmaxf(floorf(x), -1.0e9f), 1.0e9f); }
-
 // colour plane k of a surface point between voxels i0 and i1 (|tsdf| r0 and r1, rs their sum), RGB8 scaled to [0, 1]
 __device__ __forceinline__ float tsdf_blend_color(const TsdfPlanes& p, int k, int64_t i0, int64_t i1, float r0, float r1, float rs) {
     const float c = (p.color[k * p.stride + i0] * r1 + p.color[k * p.stride + i1] * r0) / rs;
@@ -250,8 +248,8 @@ static __global__ __launch_bounds__(256) void tsdf_cloud_count(TsdfVol v, int64_
 __device__ __forceinline__ float tsdf_at(const TsdfVol& v, float p0, float p1, float p2) {
     const float g0 = p0 / v.voxel_length - 0.5f, g1 = p1 / v.voxel_length - 0.5f, g2 = p2 / v.voxel_length - 0.5f;
     const int top = v.res - 2;
-    const int i0 = min(max(tsdf_floor_int(g0), 0), top), i1 = min(max(tsdf_floor_int(g1), 0), top),
-              i2 = min(max(tsdf_floor_int(g2), 0), top);
+    const int i0 = min(max(floor_int(g0), 0), top), i1 = min(max(floor_int(g1), 0), top),
+              i2 = min(max(floor_int(g2), 0), top);
     const float r0 = g0 - (float)i0, r1 = g1 - (float)i1, r2 = g2 - (float)i2;
     const float* __restrict__ T = v.p.tsdf + ((int64_t)i0 * v.res + i1) * v.res + i2;
     const int64_t sx = (int64_t)v.res * v.res, sy = v.res;
@@ -386,9 +384,9 @@ static __global__ __launch_bounds__(256) void tsdf_raycast(TsdfVol v, TsdfRaycas
         if (ray_len >= tmax) break;
         if (!(ray_len < INFINITY)) break;  // (tmax NaN: all three quotients 0/0 -- no ray to march)
         ray_len = ray_len + vl;
-        int g0 = tsdf_floor_int((t0 + d0 * ray_len) / vl) + v.h_res;
-        int g1 = tsdf_floor_int((t1 + d1 * ray_len) / vl) + v.h_res;
-        int g2 = tsdf_floor_int((t2 + d2 * ray_len) / vl) + v.h_res;
+        int g0 = floor_int((t0 + d0 * ray_len) / vl) + v.h_res;
+        int g1 = floor_int((t1 + d1 * ray_len) / vl) + v.h_res;
+        int g2 = floor_int((t2 + d2 * ray_len) / vl) + v.h_res;
         if (!tsdf_inside(g0, g1, g2, 0, res)) break;
         float cur = v.p.tsdf[((int64_t)g0 * res + g1) * res + g2];
         const float max_len = ray_len + length * 1.41421354f;  // sqrt(2.0f)
@@ -399,9 +397,9 @@ static __global__ __launch_bounds__(256) void tsdf_raycast(TsdfVol v, TsdfRaycas
         if (!(step > 0.0f) || !(max_len + step > max_len)) break;
         for (; ray_len < max_len; ray_len = ray_len + step) {
             const float ahead = ray_len + step;
-            g0 = tsdf_floor_int((t0 + d0 * ahead) / vl) + v.h_res;
-            g1 = tsdf_floor_int((t1 + d1 * ahead) / vl) + v.h_res;
-            g2 = tsdf_floor_int((t2 + d2 * ahead) / vl) + v.h_res;
+            g0 = floor_int((t0 + d0 * ahead) / vl) + v.h_res;
+            g1 = floor_int((t1 + d1 * ahead) / vl) + v.h_res;
+            g2 = floor_int((t2 + d2 * ahead) / vl) + v.h_res;
             if (!tsdf_inside(g0, g1, g2, 1, res)) continue;
             const float prev = cur;
             cur = v.p.tsdf[((int64_t)g0 * res + g1) * res + g2];

@@ -17,6 +17,7 @@
 // every sum has a fixed order.
 #pragma once
 #include "device_utils.h"
+#include "grid_rules.h"
 
 namespace mi {
 
@@ -24,49 +25,62 @@ constexpr int32_t kVgNoKey = INT32_MIN;  // x of a key that does not count (keys
 constexpr int kVgBlocks = 512;           // blocks of the partial reductions at most
 constexpr uint32_t kVgThreadRun = 32u;   // runs up to this long are added up by one thread, longer ones by a wave
 
-// floor(x) as an int, held inside +-1e9 before the conversion (occupancy_kernels.h does the same); NaN gives -1e9
-__device__ __forceinline__ int32_t vg_floor_int(float x) { return (int32_t)fminf(fmaxf(floorf(x), -1.0e9f), 1.0e9f); }
-
-__device__ __forceinline__ bool vg_finite3(float x, float y, float z) {
-    return (x - x == 0.0f) && (y - y == 0.0f) && (z - z == 0.0f);
-}
-
-struct VgFrame {
-    float vs;
-    float origin[3];
-};
-
 // create_from_pointcloud_functor (voxelgrid_factory.cu:67-72): floor((p - min_bound) / voxel_size) per axis, in fp32
-static __global__ __launch_bounds__(256) void vg_point_keys(const float* __restrict__ xyz, int64_t n, VgFrame f,
+static __global__ __launch_bounds__(256) void vg_point_keys(const float* __restrict__ xyz, int64_t n, GridFrame f,
                                                            int32_t* __restrict__ keys3) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float x = xyz[i * 3], y = xyz[i * 3 + 1], z = xyz[i * 3 + 2];
     int32_t k[3] = {kVgNoKey, 0, 0};
-    if (vg_finite3(x, y, z)) {
-        k[0] = vg_floor_int((x - f.origin[0]) / f.vs);
-        k[1] = vg_floor_int((y - f.origin[1]) / f.vs);
-        k[2] = vg_floor_int((z - f.origin[2]) / f.vs);
+    if (finite3(x, y, z)) {
+        k[0] = cell_of(f, x, 0);
+        k[1] = cell_of(f, y, 1);
+        k[2] = cell_of(f, z, 2);
     }
     keys3[i * 3] = k[0];
     keys3[i * 3 + 1] = k[1];
     keys3[i * 3 + 2] = k[2];
 }
 
-__device__ __forceinline__ int32_t vg_wave_min(int32_t v) {
+// The fold of per-lane key bounds lo[3], hi[3] with either a count or (SUMS) fp64 sums s[3].  A wave: lane 0 leaves
+// min[3], max[3] and the count in iout[0..7), the wave_sum lane the sums in dout[0..3).
+template <bool SUMS>
+__device__ __forceinline__ void vg_fold_wave(const int32_t* lo, const int32_t* hi, uint32_t cnt, const double* s,
+                                             int32_t* iout, double* dout) {
+    const int lane = lane_id();
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_down(v, o, 64));
-    return v;  // lane 0
+    for (int d = 0; d < 3; ++d) {
+        const int32_t a = wave_min(lo[d]), b = wave_max(hi[d]);
+        if (lane == 0) {
+            iout[d] = a;
+            iout[3 + d] = b;
+        }
+        if (SUMS) {
+            const double t = wave_sum(s[d]);
+            if (lane == kWaveSumLane) dout[d] = t;
+        }
+    }
+    if (!SUMS) {
+        const uint32_t t = wave_add(cnt);
+        if (lane == 0) iout[6] = (int32_t)t;
+    }
 }
-__device__ __forceinline__ int32_t vg_wave_max(int32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_down(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ uint32_t vg_wave_add(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
+
+// The block's four waves, after a barrier behind their vg_fold_wave into ired[w] and dred[w]: the first WORDS (6, or 7
+// with the count) of the fold to iout, the sums ((w0 + w1) + w2) + w3 to dout.
+template <int WORDS, int STRIDE>
+__device__ __forceinline__ void vg_fold_block(const int32_t (*ired)[STRIDE], const double (*dred)[3], int32_t* iout, double* dout) {
+    const int d = (int)threadIdx.x;
+    if (d < WORDS) {
+        int32_t v = ired[0][d];
+        for (int w = 1; w < 4; ++w) {
+            if (d < 3) v = min(v, ired[w][d]);
+            else if (d < 6) v = max(v, ired[w][d]);
+            else v = (int32_t)((uint32_t)v + (uint32_t)ired[w][d]);
+        }
+        iout[d] = v;
+    }
+    if (dred && d < 3) dout[d] = ((dred[0][d] + dred[1][d]) + dred[2][d]) + dred[3][d];
 }
 
 // per block: min[3], max[3] of the keys that count, their number, a spare word -> part[block][8]
@@ -86,36 +100,16 @@ static __global__ __launch_bounds__(256) void vg_key_bounds_partial(const int32_
         }
         ++cnt;
     }
-    const int lane = lane_id(), wid = (int)(threadIdx.x >> 6);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const int32_t a = vg_wave_min(lo[d]), b = vg_wave_max(hi[d]);
-        if (lane == 0) {
-            red[wid][d] = a;
-            red[wid][3 + d] = b;
-        }
-    }
-    const uint32_t t = vg_wave_add(cnt);
-    if (lane == 0) red[wid][6] = (int32_t)t;
+    vg_fold_wave<false>(lo, hi, cnt, nullptr, red[threadIdx.x >> 6], nullptr);
     __syncthreads();
-    if (threadIdx.x < 7) {
-        const int d = (int)threadIdx.x;
-        int32_t v = red[0][d];
-        for (int w = 1; w < 4; ++w) {
-            if (d < 3) v = min(v, red[w][d]);
-            else if (d < 6) v = max(v, red[w][d]);
-            else v = (int32_t)((uint32_t)v + (uint32_t)red[w][d]);
-        }
-        part[blockIdx.x * 8 + d] = v;
-    }
+    vg_fold_block<7>(red, nullptr, part + blockIdx.x * 8, nullptr);
 }
 
 static __global__ __launch_bounds__(64) void vg_key_bounds_final(const int32_t* __restrict__ part, int nblocks,
                                                                 int32_t* __restrict__ out /*[8]*/) {
-    const int lane = lane_id();
     int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
     uint32_t cnt = 0u;
-    for (int b = lane; b < nblocks; b += 64) {
+    for (int b = lane_id(); b < nblocks; b += 64) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             lo[d] = min(lo[d], part[b * 8 + d]);
@@ -123,19 +117,8 @@ static __global__ __launch_bounds__(64) void vg_key_bounds_final(const int32_t* 
         }
         cnt += (uint32_t)part[b * 8 + 6];
     }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const int32_t a = vg_wave_min(lo[d]), b = vg_wave_max(hi[d]);
-        if (lane == 0) {
-            out[d] = a;
-            out[3 + d] = b;
-        }
-    }
-    const uint32_t t = vg_wave_add(cnt);
-    if (lane == 0) {
-        out[6] = (int32_t)t;
-        out[7] = 0;
-    }
+    vg_fold_wave<false>(lo, hi, cnt, nullptr, out, nullptr);
+    if (lane_id() == 0) out[7] = 0;
 }
 
 // how key - lo is packed: x above y above z; nokey_x (the x extent) is the x slot of the keys that do not count, so
@@ -349,7 +332,7 @@ struct VgCamera {
 
 // compute_carve_functor (voxelgrid.cu:58-123) in fp32, unfused, in the reference's order; FloatValueAt is image.h:240-264.
 // flags[i] = 1: voxel i stays.
-static __global__ __launch_bounds__(256) void vg_carve_flags(const int32_t* __restrict__ keys, int64_t m, VgFrame f, VgCamera cam,
+static __global__ __launch_bounds__(256) void vg_carve_flags(const int32_t* __restrict__ keys, int64_t m, GridFrame f, VgCamera cam,
                                                             const float* __restrict__ image, uint32_t* __restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
@@ -385,15 +368,9 @@ static __global__ __launch_bounds__(256) void vg_carve_flags(const int32_t* __re
     flags[i] = stay ? 1u : 0u;
 }
 
-__device__ __forceinline__ bool vg_key_less(const int32_t* __restrict__ a, int32_t x, int32_t y, int32_t z) {
-    if (a[0] != x) return a[0] < x;
-    if (a[1] != y) return a[1] < y;
-    return a[2] < z;
-}
-
 // CheckIfIncluded (voxelgrid.cu:365-376): the voxel of a query is floor((q - origin) / voxel_size); it is included iff
 // that key is among the ascending keys[m] -- a binary search.  A non-finite query is not included and has index (0, 0, 0).
-static __global__ __launch_bounds__(256) void vg_query(const int32_t* __restrict__ keys, int64_t m, VgFrame f,
+static __global__ __launch_bounds__(256) void vg_query(const int32_t* __restrict__ keys, int64_t m, GridFrame f,
                                                       const float* __restrict__ queries, int64_t nq,
                                                       uint8_t* __restrict__ included, int32_t* __restrict__ out_index) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -401,16 +378,11 @@ static __global__ __launch_bounds__(256) void vg_query(const int32_t* __restrict
     const float x = queries[i * 3], y = queries[i * 3 + 1], z = queries[i * 3 + 2];
     int32_t k[3] = {0, 0, 0};
     bool hit = false;
-    if (vg_finite3(x, y, z)) {
-        k[0] = vg_floor_int((x - f.origin[0]) / f.vs);
-        k[1] = vg_floor_int((y - f.origin[1]) / f.vs);
-        k[2] = vg_floor_int((z - f.origin[2]) / f.vs);
-        int64_t lo = 0, hi = m;  // the first entry not less than k
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (vg_key_less(keys + mid * 3, k[0], k[1], k[2])) lo = mid + 1;
-            else hi = mid;
-        }
+    if (finite3(x, y, z)) {
+        k[0] = cell_of(f, x, 0);
+        k[1] = cell_of(f, y, 1);
+        k[2] = cell_of(f, z, 2);
+        const int64_t lo = keys3_lower(keys, m, k[0], k[1], k[2]);
         hit = lo < m && keys[lo * 3] == k[0] && keys[lo * 3 + 1] == k[1] && keys[lo * 3 + 2] == k[2];
     }
     included[i] = hit ? 1 : 0;
@@ -423,7 +395,7 @@ static __global__ __launch_bounds__(256) void vg_query(const int32_t* __restrict
 
 // GetMinBound / GetMaxBound / GetCenter (voxelgrid.cu:161-200): per block the min and max index per axis and the fp64
 // sum of the voxels' centres, each centre ((float)key * vs + origin) + 0.5f * vs in fp32.  ipart[block][8], dpart[block][4].
-static __global__ __launch_bounds__(256) void vg_bounds_partial(const int32_t* __restrict__ keys, int64_t m, VgFrame f,
+static __global__ __launch_bounds__(256) void vg_bounds_partial(const int32_t* __restrict__ keys, int64_t m, GridFrame f,
                                                                int32_t* __restrict__ ipart, double* __restrict__ dpart) {
     __shared__ int32_t ired[4][6];
     __shared__ double dred[4][3];
@@ -439,37 +411,18 @@ static __global__ __launch_bounds__(256) void vg_bounds_partial(const int32_t* _
             s[d] += (double)(((float)k * f.vs + f.origin[d]) + half);
         }
     }
-    const int lane = lane_id(), wid = (int)(threadIdx.x >> 6);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const int32_t a = vg_wave_min(lo[d]), b = vg_wave_max(hi[d]);
-        if (lane == 0) {
-            ired[wid][d] = a;
-            ired[wid][3 + d] = b;
-        }
-        const double t = wave_sum(s[d]);
-        if (lane == kWaveSumLane) dred[wid][d] = t;
-    }
+    const int wid = (int)(threadIdx.x >> 6);
+    vg_fold_wave<true>(lo, hi, 0u, s, ired[wid], dred[wid]);
     __syncthreads();
-    if (threadIdx.x < 6) {
-        const int d = (int)threadIdx.x;
-        int32_t v = ired[0][d];
-        for (int w = 1; w < 4; ++w) v = d < 3 ? min(v, ired[w][d]) : max(v, ired[w][d]);
-        ipart[blockIdx.x * 8 + d] = v;
-    }
-    if (threadIdx.x < 3) {
-        const int d = (int)threadIdx.x;
-        dpart[blockIdx.x * 4 + d] = ((dred[0][d] + dred[1][d]) + dred[2][d]) + dred[3][d];
-    }
+    vg_fold_block<6>(ired, dred, ipart + blockIdx.x * 8, dpart + blockIdx.x * 4);
 }
 
 static __global__ __launch_bounds__(64) void vg_bounds_final(const int32_t* __restrict__ ipart, const double* __restrict__ dpart,
                                                             int nblocks, int32_t* __restrict__ iout /*[6]*/,
                                                             double* __restrict__ dout /*[3]*/) {
-    const int lane = lane_id();
     int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
     double s[3] = {0.0, 0.0, 0.0};
-    for (int b = lane; b < nblocks; b += 64) {
+    for (int b = lane_id(); b < nblocks; b += 64) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             lo[d] = min(lo[d], ipart[b * 8 + d]);
@@ -477,16 +430,7 @@ static __global__ __launch_bounds__(64) void vg_bounds_final(const int32_t* __re
             s[d] += dpart[b * 4 + d];
         }
     }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const int32_t a = vg_wave_min(lo[d]), b = vg_wave_max(hi[d]);
-        if (lane == 0) {
-            iout[d] = a;
-            iout[3 + d] = b;
-        }
-        const double t = wave_sum(s[d]);
-        if (lane == kWaveSumLane) dout[d] = t;
-    }
+    vg_fold_wave<true>(lo, hi, 0u, s, iout, dout);
 }
 
 // PaintIndexedColor's indices: *status is set when one lies outside [0, m)

@@ -325,3 +325,53 @@ def test_free_area_beside_the_grid_is_empty():
     apply(grid, op)
     ox.apply(ref, op)
     check(grid, ref)
+
+
+# ---- a bounds box whose three extents differ, through everything that decodes it ----------------------------------------
+def test_a_box_with_three_different_extents_through_every_consumer():
+    """The occupancy input of the other tests is a shell seen from its centre: a bounds box that is nearly a cube, which
+    a decode with two extents swapped would pass.  Here the box is 5 x 11 x 23 voxels, (3, 9, 5) .. (7, 19, 27)."""
+    import collision_exact as cx
+    from cupoch_amd import collision, geometry
+    res, origin, lo, hi = 32, ox.ORIGINS[33], np.array([3, 9, 5]), np.array([7, 19, 27])
+    grid, ref = geometry.OccupancyGrid(ox.VOXEL, res, origin), ox.Grid(ox.VOXEL, res, origin)
+
+    def centre(ijk):
+        return ((np.asarray(ijk, F) + F(0.5 - res // 2)) * F(ox.VOXEL) + np.asarray(origin, F)).astype(F)
+    rng = np.random.default_rng(5)
+    inner = np.stack([rng.integers(lo[k], hi[k] + 1, 40) for k in range(3)], 1)
+    corners = np.array([[3, 9, 5], [7, 19, 27], [3, 19, 5], [7, 9, 27]])
+    for op in (("free", centre(lo), centre(hi)), ("add", np.concatenate([inner, corners]).astype(np.int32), True)):
+        apply(grid, op)
+        ox.apply(ref, op)
+    assert np.array_equal(ref.min_bound, lo) and np.array_equal(ref.max_bound, hi)
+    e, g, p = grid._call()
+    for which, count in ((ox.KNOWN, 1265), (ox.FREE, 1221), (ox.OCCUPIED, 44)):
+        ijk, prob, pts = ox.extract(ref, which)
+        assert len(ijk) == count
+        gi, gp, gx = e.occgrid_extract(g, p, which, want_points=True)
+        assert np.array_equal(to_np(gi), ijk) and same(gp, prob) and same(gx, pts)
+    check(grid, ref)
+    occupied = ox.extract(ref, ox.OCCUPIED)[0]
+
+    d = geometry.DistanceTransform.create_from_occupancy_grid(grid)
+    near, dist = d.voxels.cpu()
+    near1, dist1 = geometry.DistanceTransform(ox.VOXEL, res, origin).compute_edt(occupied).voxels.cpu()
+    assert np.array_equal(near, near1) and same(dist, dist1)
+    assert np.count_nonzero(dist) == res ** 3 - 44 and np.isfinite(dist).all()
+
+    v = geometry.VoxelGrid.create_from_occupancy_grid(grid)
+    assert np.array_equal(to_np(v.voxels.grid_index), occupied)
+
+    # a small VoxelGrid in a frame of its own, with a voxel over each of two corners and two voxels beside the box
+    vs_q, origin_q = ox.VOXEL, np.asarray(origin, F) + F(0.037)
+    keys = np.array(sorted(map(tuple, [corners[0] - 16, corners[1] - 16, corners[2] - 16 + [0, 1, 0], [9, 9, 9]])), np.int32)
+    q = geometry.VoxelGrid()
+    q.voxel_size, q.origin = float(vs_q), origin_q
+    q.add_voxels((keys, np.ones((len(keys), 3), F)))
+    assert np.array_equal(to_np(q.voxels.grid_index), keys)
+    oside, qside = ("occ", occupied, res, ox.VOXEL, np.asarray(origin, F)), ("voxel", keys, vs_q, origin_q)
+    for a, b, sa, sb in ((grid, q, oside, qside), (q, grid, qside, oside)):
+        want = cx.compute_intersection(sa, sb, 0.0)
+        got = collision.compute_intersection(a, b, 0.0).get_collision_index_pairs()
+        assert np.array_equal(got, want) and len(want) >= 2
