@@ -204,6 +204,7 @@ SIGNATURES = {
     "mi_icp_tsdf_extract_point_cloud": (_I, [_P, _P, _P, _P, _P, _L, C.POINTER(_L), _I]),
     "mi_icp_tsdf_extract_voxel_point_cloud": (_I, [_P, _P, _P, _P, _L, C.POINTER(_L), _I]),
     "mi_icp_tsdf_raycast": (_I, [_P, _P, _I, _I, _P, _P, _F, _I, _P, _P, _P, _L, C.POINTER(_L), _I]),
+    "mi_icp_tsdf_raycast_levels": (_I, [_P, _P, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _L, C.POINTER(_L)]),
     "mi_icp_tsdf_get_voxels": (_I, [_P, _P, _P, _P, _P, _I]),
     "mi_icp_stsdf_create": (_I, [_P, _F, _F, _I, _I, _I, C.POINTER(_P)]),
     "mi_icp_stsdf_destroy": (_I, [_P, _P]),

@@ -40,11 +40,19 @@ public:
     /// ("[UniformTSDFVolume::Integrate] Unsupported image format.") and leaves the volume as it was.
     void Integrate(const geometry::RGBDImage& image, const camera::PinholeCameraIntrinsic& intrinsic,
                    const Eigen::Matrix4f& extrinsic) override;
+    /// Integrate; false (after the same log line) when the format was turned away
+    bool TryIntegrate(const geometry::RGBDImage& image, const camera::PinholeCameraIntrinsic& intrinsic,
+                      const Eigen::Matrix4f& extrinsic);
     std::shared_ptr<geometry::PointCloud> ExtractPointCloud() override;
     std::shared_ptr<geometry::PointCloud> ExtractVoxelPointCloud() const;
     std::shared_ptr<geometry::PointCloud> Raycast(const camera::PinholeCameraIntrinsic& intrinsic,
                                                   const Eigen::Matrix4f& extrinsic, float sdf_trunc,
                                                   bool project_valid_depth_only = true) const;
+    /// Raycast(intrinsic.CreatePyramidLevel(i), extrinsic, sdf_trunc, project_valid_depth_only) for i = 0 .. levels-1,
+    /// the same values, in one pass over the volume (mi_icp_tsdf_raycast_levels); 1 <= levels <= 16
+    std::vector<std::shared_ptr<geometry::PointCloud>> RaycastLevels(const camera::PinholeCameraIntrinsic& intrinsic,
+                                                                     const Eigen::Matrix4f& extrinsic, float sdf_trunc,
+                                                                     int levels, bool project_valid_depth_only = true) const;
     /// voxel_num_ voxels, indexed x*res*res + y*res + z (a NoColor volume reports colour (1, 1, 1))
     std::vector<geometry::TSDFVoxel> GetVoxels() const;
 

@@ -2406,12 +2406,18 @@ int IntegrateFrame(int (*integrate)(mi_icp_ctx*, Vol*, const void*, int, int, in
 
 void UniformTSDFVolume::Integrate(const geometry::RGBDImage& image, const camera::PinholeCameraIntrinsic& intrinsic,
                                   const Eigen::Matrix4f& extrinsic) {
+    (void)TryIntegrate(image, intrinsic, extrinsic);
+}
+
+bool UniformTSDFVolume::TryIntegrate(const geometry::RGBDImage& image, const camera::PinholeCameraIntrinsic& intrinsic,
+                                     const Eigen::Matrix4f& extrinsic) {
     const int rc = IntegrateFrame(mi_icp_tsdf_integrate, volume_, image, intrinsic, extrinsic, color_type_, (int)MI_ICP_DEVICE);
     if (rc == MI_ICP_ERR_INVALID) {  // uniform_tsdfvolume.cu:677-695
         LogError("[UniformTSDFVolume::Integrate] Unsupported image format.");
-        return;
+        return false;
     }
     Check(rc);
+    return true;
 }
 
 namespace {
@@ -2464,6 +2470,38 @@ std::shared_ptr<geometry::PointCloud> UniformTSDFVolume::Raycast(const camera::P
         return mi_icp_tsdf_raycast(Engine(), v, w, h, k4, extrinsic.data(), sdf_trunc, project_valid_depth_only ? 1 : 0, p, n,
                                    c, cap, m, MI_ICP_DEVICE);
     });
+}
+
+std::vector<std::shared_ptr<geometry::PointCloud>> UniformTSDFVolume::RaycastLevels(const camera::PinholeCameraIntrinsic& intrinsic,
+                                                                                    const Eigen::Matrix4f& extrinsic,
+                                                                                    float sdf_trunc, int levels,
+                                                                                    bool project_valid_depth_only) const {
+    const float k4[4] = {intrinsic.fx_, intrinsic.fy_, intrinsic.cx_, intrinsic.cy_};
+    const int w = intrinsic.width_, h = intrinsic.height_;
+    size_t capacity = 0;  // every pixel of every level: always enough
+    for (int i = 0; i < levels && i < MI_ICP_TSDF_MAX_LEVELS; ++i)
+        if (w > 0 && h > 0) capacity += (size_t)(w >> i) * (size_t)(h >> i);
+    utility::device_vector<Eigen::Vector3f> all[3];
+    for (auto& a : all) a.resize(capacity);
+    int64_t m[MI_ICP_TSDF_MAX_LEVELS] = {};
+    Check(mi_icp_tsdf_raycast_levels(Engine(), volume_, levels, w, h, k4, extrinsic.data(), sdf_trunc,
+                                     project_valid_depth_only ? 1 : 0, capacity ? all[0].data()->data() : nullptr,
+                                     capacity ? all[1].data()->data() : nullptr, capacity ? all[2].data()->data() : nullptr,
+                                     (int64_t)capacity, m));
+    std::vector<std::shared_ptr<geometry::PointCloud>> out((size_t)levels);
+    size_t first = 0;
+    for (int i = 0; i < levels; ++i) {
+        auto cloud = std::make_shared<geometry::PointCloud>();
+        const size_t n = (size_t)m[i];
+        utility::device_vector<Eigen::Vector3f>* dst[3] = {&cloud->points_, &cloud->normals_, &cloud->colors_};
+        for (int k = 0; k < 3; ++k) {
+            dst[k]->resize(n);
+            if (n) utility::copy_d2d(dst[k]->data(), all[k].data() + first, n * sizeof(Eigen::Vector3f));
+        }
+        first += n;
+        out[(size_t)i] = cloud;
+    }
+    return out;
 }
 
 std::vector<geometry::TSDFVoxel> UniformTSDFVolume::GetVoxels() const {
@@ -2558,16 +2596,28 @@ std::vector<ScalableTSDFVolume::VolumeUnit> ScalableTSDFVolume::GetVolumeUnits()
 // ---------------------------------------------------------------- kinfu
 namespace kinfu {
 
-PointCloudPyramid CreatePointCloudPyramid(const std::vector<geometry::RGBDImage>& image_pyramid,
-                                          const camera::PinholeCameraIntrinsic& intrinsic,
-                                          const KinfuOption& option) {
+namespace {
+template <class Level>
+PointCloudPyramid CloudPyramid(const camera::PinholeCameraIntrinsic& intrinsic, const KinfuOption& option, Level level) {
     PointCloudPyramid out((size_t)option.num_pyramid_levels_);
     for (int i = 0; i < option.num_pyramid_levels_; ++i)
-        out[(size_t)i] = geometry::PointCloud::CreateFromRGBDImage(image_pyramid[(size_t)i],
-                                                                   intrinsic.CreatePyramidLevel((size_t)i),
+        out[(size_t)i] = geometry::PointCloud::CreateFromRGBDImage(level((size_t)i), intrinsic.CreatePyramidLevel((size_t)i),
                                                                    Eigen::Matrix4f::Identity(), true,
                                                                    option.depth_cutoff_, true);
     return out;
+}
+}  // namespace
+
+PointCloudPyramid CreatePointCloudPyramid(const std::vector<geometry::RGBDImage>& image_pyramid,
+                                          const camera::PinholeCameraIntrinsic& intrinsic,
+                                          const KinfuOption& option) {
+    return CloudPyramid(intrinsic, option, [&](size_t i) -> const geometry::RGBDImage& { return image_pyramid[i]; });
+}
+
+PointCloudPyramid CreatePointCloudPyramid(const geometry::RGBDImagePyramid& image_pyramid,
+                                          const camera::PinholeCameraIntrinsic& intrinsic,
+                                          const KinfuOption& option) {
+    return CloudPyramid(intrinsic, option, [&](size_t i) -> const geometry::RGBDImage& { return *image_pyramid[i]; });
 }
 
 std::tuple<Eigen::Matrix4f, bool> PoseEstimation(const KinfuOption& option, const Eigen::Matrix4f& extrinsic,
@@ -2599,6 +2649,50 @@ std::tuple<Eigen::Matrix4f, bool> PoseEstimation(const KinfuOption& option, cons
     }
     return std::make_tuple(cur, true);
 }
+
+KinfuPipeline::KinfuPipeline(const camera::PinholeCameraIntrinsic& intrinsic, const KinfuOption& option)
+    : intrinsic_(intrinsic),
+      volume_(option.tsdf_length_, option.tsdf_resolution_, option.sdf_trunc_, option.tsdf_color_type_, option.tsdf_origin_),
+      option_(option) {}
+
+KinfuPipeline::~KinfuPipeline() {}
+
+void KinfuPipeline::Reset() {
+    cur_pose_ = Eigen::Matrix4f::Identity();
+    volume_.Reset();
+    model_pyramid_.clear();
+    frame_id_ = 0;
+}
+
+bool KinfuPipeline::ProcessFrame(const geometry::RGBDImage& image) {
+    const auto refuse = [](const char* why) {
+        LogError((std::string("[KinfuPipeline::ProcessFrame] ") + why).c_str());
+        return false;
+    };
+    const int levels = option_.num_pyramid_levels_;
+    if (!image.color_.HasData() || !image.depth_.HasData()) return refuse("The frame has no colour or no depth data.");
+    if (levels < 1 || levels > kMaxPyramidLevels) return refuse("num_pyramid_levels must be in [1, 16].");
+    if (option_.icp_iterations_.size() < (size_t)levels) return refuse("icp_iterations has fewer entries than num_pyramid_levels.");
+    if (image.color_.width_ != intrinsic_.width_ || image.color_.height_ != intrinsic_.height_ ||
+        image.depth_.width_ != intrinsic_.width_ || image.depth_.height_ != intrinsic_.height_)
+        return refuse("The frame's size is not the intrinsic's.");
+    // SurfaceMeasurement (kinfu.cpp:86-104)
+    const geometry::RGBDImagePyramid pyramid = image.CreatePyramid((size_t)levels);
+    if (pyramid.size() != (size_t)levels) return refuse("Unsupported image format.");
+    const geometry::RGBDImagePyramid smooth =
+            geometry::RGBDImage::BilateralFilterPyramidDepth(pyramid, option_.diameter_, option_.sigma_depth_, option_.sigma_space_);
+    const PointCloudPyramid pc_pyramid = CreatePointCloudPyramid(smooth, intrinsic_, option_);
+    Eigen::Matrix4f extrinsic = utility::InverseTransform(cur_pose_);
+    if (frame_id_ > 0) extrinsic = std::get<0>(PoseEstimation(option_, extrinsic, model_pyramid_, pc_pyramid));
+    // the volume turns a format away before it changes anything: the pose is kept only with an integrated frame
+    if (!volume_.TryIntegrate(*smooth[0], intrinsic_, extrinsic)) return refuse("Unsupported image format.");
+    if (frame_id_ > 0) cur_pose_ = utility::InverseTransform(extrinsic);
+    model_pyramid_ = volume_.RaycastLevels(intrinsic_, extrinsic, option_.sdf_trunc_, levels);
+    frame_id_++;
+    return true;
+}
+
+std::shared_ptr<geometry::PointCloud> KinfuPipeline::ExtractPointCloud() { return volume_.ExtractPointCloud(); }
 
 }  // namespace kinfu
 

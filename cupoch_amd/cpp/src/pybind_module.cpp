@@ -42,6 +42,7 @@
 #include "cupoch/imageproc/sgm.h"
 #include "cupoch/integration/scalable_tsdfvolume.h"
 #include "cupoch/integration/uniform_tsdfvolume.h"
+#include "cupoch/kinfu/kinfu.h"
 #include "cupoch/knn/kdtree_flann.h"
 #include "cupoch/knn/kdtree_search_param.h"
 #include "cupoch/planning/planner.h"
@@ -1593,4 +1594,40 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             },
             "source"_a, "target"_a, "max_distance"_a, "init"_a = identity4(),
             "criteria"_a = registration::ICPConvergenceCriteria(), "lambda_geometric"_a = 0.968f, "det_thresh"_a = 1e-6f);
+
+    // ---------------------------------------------------------------- kinfu (cupoch_pybind/kinfu/kinfu.cpp)
+    // The reference's names.  Not bound, as not built: extract_triangle_mesh; the pipeline has no copy functions
+    // (its volume is not copyable here).
+    py::module mkf = m.def_submodule("kinfu");
+    py::class_<kinfu::KinfuOption>(mkf, "KinfuOption", "Parameters for Kinect Fusion.")
+            .def(py::init<>())
+            .def(py::init<const kinfu::KinfuOption&>())
+            .def("__copy__", [](const kinfu::KinfuOption& o) { return kinfu::KinfuOption(o); })
+            .def("__deepcopy__", [](const kinfu::KinfuOption& o, py::dict&) { return kinfu::KinfuOption(o); })
+            .def_readwrite("num_pyramid_levels", &kinfu::KinfuOption::num_pyramid_levels_)
+            .def_readwrite("diameter", &kinfu::KinfuOption::diameter_)
+            .def_readwrite("sigma_depth", &kinfu::KinfuOption::sigma_depth_)
+            .def_readwrite("sigma_space", &kinfu::KinfuOption::sigma_space_)
+            .def_readwrite("depth_cutoff", &kinfu::KinfuOption::depth_cutoff_)
+            .def_readwrite("tsdf_length", &kinfu::KinfuOption::tsdf_length_)
+            .def_readwrite("tsdf_resolution", &kinfu::KinfuOption::tsdf_resolution_)
+            .def_readwrite("sdf_trunc", &kinfu::KinfuOption::sdf_trunc_)
+            .def_readwrite("tsdf_color_type", &kinfu::KinfuOption::tsdf_color_type_)
+            .def_property(
+                    "tsdf_origin", [](const kinfu::KinfuOption& o) { return from_vector3(o.tsdf_origin_); },
+                    [](kinfu::KinfuOption& o, const farray& v) { o.tsdf_origin_ = to_vector3(v); })
+            .def_readwrite("distance_threshold", &kinfu::KinfuOption::distance_threshold_)
+            .def_readwrite("icp_iterations", &kinfu::KinfuOption::icp_iterations_)
+            .def_readwrite("tf_type", &kinfu::KinfuOption::tf_type_);
+    py::class_<kinfu::KinfuPipeline>(mkf, "KinfuPipeline", "KinfuPipeline implements Kinect fusion algorithm.")
+            .def(py::init([](const camera::PinholeCameraIntrinsic& intrinsic, const kinfu::KinfuOption& params) {
+                return new kinfu::KinfuPipeline(intrinsic, params);
+            }))
+            .def("reset", &kinfu::KinfuPipeline::Reset)
+            .def("process_frame", &kinfu::KinfuPipeline::ProcessFrame)
+            .def("extract_point_cloud", &kinfu::KinfuPipeline::ExtractPointCloud)
+            .def_property(
+                    "cur_pose", [](const kinfu::KinfuPipeline& p) { return from_matrix4(p.cur_pose_); },
+                    [](kinfu::KinfuPipeline& p, const farray& T) { p.cur_pose_ = to_matrix4(T); })
+            .def_readwrite("model_pyramid", &kinfu::KinfuPipeline::model_pyramid_);
 }

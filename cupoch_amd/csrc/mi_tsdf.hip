@@ -29,6 +29,91 @@ static int tsdf_check(mi_icp_ctx* c, const mi_icp_tsdf* t, const char* what) {
     return handle_check(c, t, c->tsdf_volumes, what, "volume");
 }
 
+static_assert(kTsdfMaxLevels == MI_ICP_TSDF_MAX_LEVELS, "the kernel's level table holds every level of the C ABI");
+
+// Raycast for `levels` levels of the camera's pyramid in one pass (include/mi_icp.h "Raycast", "raycast_levels"): one
+// tsdf_raycast launch over the tiles of every level, and with valid_only one finite_flags, one scan and one
+// select_gather over the concatenated pixels; m[i] = the points of level i.  mi_icp_tsdf_raycast is levels == 1.
+static int tsdf_raycast_levels(mi_icp_ctx* c, mi_icp_tsdf* t, const char* what, int levels, int width, int height,
+                               const float* intrinsic4, const float* extrinsic, float sdf_trunc, int valid_only,
+                               float* const out[3], int64_t capacity, int64_t* m, int mem_kind) {
+    TRY(tsdf_extract_args(c, t, c->tsdf_volumes, what, capacity, m, mem_kind));
+    if (levels < 1 || levels > MI_ICP_TSDF_MAX_LEVELS)
+        return fail(c, MI_ICP_ERR_INVALID, "%s: levels must be in [1, %d]", what, MI_ICP_TSDF_MAX_LEVELS);
+    for (int i = 0; i < levels; ++i) m[i] = 0;
+    if (!intrinsic4 || width < 0 || height < 0 || width > MI_ICP_TSDF_MAX_IMAGE_SIDE || height > MI_ICP_TSDF_MAX_IMAGE_SIDE)
+        return fail(c, MI_ICP_ERR_INVALID, "%s: bad arguments (an image side is at most %d)", what, MI_ICP_TSDF_MAX_IMAGE_SIDE);
+    // the march takes length * sqrt(2) / (sdf_trunc / 2) steps at most
+    if (!(sdf_trunc > 0.0f) || !std::isfinite(sdf_trunc) ||
+        !((double)t->v.res * t->v.voxel_length * 1.4142136 / (0.5 * (double)sdf_trunc) <= (double)MI_ICP_TSDF_MAX_MARCH))
+        return fail(c, MI_ICP_ERR_INVALID, "%s: sdf_trunc must be positive and at least length * sqrt(2) * 2 / %d", what,
+                    MI_ICP_TSDF_MAX_MARCH);
+
+    TsdfRaycast a = {};
+    const Mat4 E = load_T(extrinsic);
+    // utility::InverseTransform: R^T and -(R^T t), the sums left to right
+    for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 3; ++k) a.R[r][k] = E.data()[r * 4 + k];  // R^T[r][k] = E(k, r)
+        const float t0 = E.data()[12], t1 = E.data()[13], t2 = E.data()[14];
+        const float p = ((-a.R[r][0]) * t0 + (-a.R[r][1]) * t1) + (-a.R[r][2]) * t2;
+        a.t[r] = p - t->v.origin[r];
+    }
+    a.sdf_trunc = sdf_trunc;
+    a.levels = levels;
+    // the levels' cameras (PinholeCameraIntrinsic::CreatePyramidLevel), tiles and pixels, one level after the other
+    int64_t npix = 0, ntiles = 0;
+    for (int i = 0; i < levels; ++i) {
+        TsdfRayLevel& L = a.level[i];
+        const float s = i == 0 ? 1.0f : powf(0.5f, (float)i);
+        L.fx = i == 0 ? intrinsic4[0] : intrinsic4[0] * s;
+        L.fy = i == 0 ? intrinsic4[1] : intrinsic4[1] * s;
+        L.cx = i == 0 ? intrinsic4[2] : (intrinsic4[2] + 0.5f) * s - 0.5f;
+        L.cy = i == 0 ? intrinsic4[3] : (intrinsic4[3] + 0.5f) * s - 0.5f;
+        L.width = width >> i;
+        L.height = height >> i;
+        L.tiles_x = (L.width + 15) / 16;
+        L.first_tile = (int)ntiles;
+        L.first_pixel = npix;
+        m[i] = (int64_t)L.width * L.height;  // (valid_only: until the counts are known)
+        npix += m[i];
+        ntiles += m[i] ? (int64_t)L.tiles_x * ((L.height + 15) / 16) : 0;
+    }
+    if (npix == 0) return MI_ICP_OK;  // (the sides are at most 2^15: npix < 2^31 and ntiles < 2^23)
+
+    if (!valid_only) {  // every pixel stays, an invalid one as NaN
+        if (capacity < npix) return MI_ICP_OK;
+        if (!out[0] || !out[1] || !out[2]) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+        return cloud_emit(c, out, out, npix, npix, mem_kind, c->vpay, [&](float* const dst[3]) {
+            tsdf_raycast<<<(unsigned)ntiles, 256, 0, c->stream>>>(t->v, a, dst[0], dst[1], dst[2]);
+        });
+    }
+    for (int i = 0; i < levels; ++i) m[i] = 0;
+    float* raw[3];
+    for (int k = 0; k < 3; ++k) TRY(ensure(c, c->stage[3 + k], (size_t)npix * 3, &raw[k]));
+    uint32_t *flags, *pos;
+    TRY(ensure(c, c->flags, (size_t)npix + MI_ICP_TSDF_MAX_LEVELS, &flags));  // and, behind them, the levels' ends
+    uint32_t* const ends = flags + npix;
+    tsdf_raycast<<<(unsigned)ntiles, 256, 0, c->stream>>>(t->v, a, raw[0], raw[1], raw[2]);
+    KCHK(c);
+    finite_flags<<<blocks_for(npix), 256, 0, c->stream>>>(raw[0], npix, 1, 1, flags);  // RemoveNoneFinitePoints(true, true)
+    KCHK(c);
+    // the counts before anything is written (the capacity rule), all levels' in one read-back
+    const uint32_t* total;
+    TRY(scan_flags(c, flags, npix, &pos, &total));
+    tsdf_level_ends<<<1, 64, 0, c->stream>>>(a, npix, pos, total, ends);
+    KCHK(c);
+    HIPCHK(c, hipMemcpyAsync(c->u_host, ends, (size_t)levels * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < levels; ++i) m[i] = (int64_t)c->u_host[i] - (i ? (int64_t)c->u_host[i - 1] : 0);
+    const int64_t cnt = (int64_t)c->u_host[levels - 1];
+    if (cnt == 0 || capacity < cnt) return MI_ICP_OK;
+    if (!out[0] || !out[1] || !out[2]) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
+    return cloud_emit(c, out, out, cnt, cnt, mem_kind, c->vpay, [&](float* const dst[3]) {
+        select_gather<<<blocks_for(npix), 256, 0, c->stream>>>(flags, pos, npix, raw[0], raw[1], raw[2], dst[0], dst[1], dst[2],
+                                                              (int64_t*)nullptr);
+    });
+}
+
 extern "C" {
 
 int mi_icp_tsdf_create(mi_icp_ctx* c, float length, int resolution, float sdf_trunc, int color_type, const float* origin3,
@@ -144,59 +229,17 @@ int mi_icp_tsdf_extract_point_cloud(mi_icp_ctx* c, mi_icp_tsdf* t, float* out_xy
 int mi_icp_tsdf_raycast(mi_icp_ctx* c, mi_icp_tsdf* t, int width, int height, const float* intrinsic4, const float* extrinsic,
                         float sdf_trunc, int valid_only, float* out_xyz, float* out_normals, float* out_colors,
                         int64_t capacity, int64_t* m, int mem_kind) {
-    const char* what = "tsdf_raycast";
-    TRY(tsdf_extract_args(c, t, c->tsdf_volumes, what, capacity, m, mem_kind));
-    if (!intrinsic4 || width < 0 || height < 0 || width > MI_ICP_TSDF_MAX_IMAGE_SIDE || height > MI_ICP_TSDF_MAX_IMAGE_SIDE)
-        return fail(c, MI_ICP_ERR_INVALID, "%s: bad arguments (an image side is at most %d)", what, MI_ICP_TSDF_MAX_IMAGE_SIDE);
-    // the march takes length * sqrt(2) / (sdf_trunc / 2) steps at most
-    if (!(sdf_trunc > 0.0f) || !std::isfinite(sdf_trunc) ||
-        !((double)t->v.res * t->v.voxel_length * 1.4142136 / (0.5 * (double)sdf_trunc) <= (double)MI_ICP_TSDF_MAX_MARCH))
-        return fail(c, MI_ICP_ERR_INVALID, "%s: sdf_trunc must be positive and at least length * sqrt(2) * 2 / %d", what,
-                    MI_ICP_TSDF_MAX_MARCH);
-    const int64_t npix = (int64_t)width * height;
-    if (npix == 0) return MI_ICP_OK;
-
-    TsdfRaycast a;
-    const Mat4 E = load_T(extrinsic);
-    // utility::InverseTransform: R^T and -(R^T t), the sums left to right
-    for (int r = 0; r < 3; ++r) {
-        for (int k = 0; k < 3; ++k) a.R[r][k] = E.data()[r * 4 + k];  // R^T[r][k] = E(k, r)
-        const float t0 = E.data()[12], t1 = E.data()[13], t2 = E.data()[14];
-        const float p = ((-a.R[r][0]) * t0 + (-a.R[r][1]) * t1) + (-a.R[r][2]) * t2;
-        a.t[r] = p - t->v.origin[r];
-    }
-    a.fx = intrinsic4[0];
-    a.fy = intrinsic4[1];
-    a.cx = intrinsic4[2];
-    a.cy = intrinsic4[3];
-    a.sdf_trunc = sdf_trunc;
-    a.width = width;
-    a.height = height;
-    const dim3 grid((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16));
     float* const out[3] = {out_xyz, out_normals, out_colors};
+    return tsdf_raycast_levels(c, t, "tsdf_raycast", 1, width, height, intrinsic4, extrinsic, sdf_trunc, valid_only, out, capacity,
+                               m, mem_kind);
+}
 
-    if (!valid_only) {  // every pixel stays, an invalid one as NaN
-        *m = npix;
-        if (capacity < npix) return MI_ICP_OK;
-        if (!out_xyz || !out_normals || !out_colors) return fail(c, MI_ICP_ERR_INVALID, "%s: null buffer", what);
-        return cloud_emit(c, out, out, npix, npix, mem_kind, c->vpay, [&](float* const dst[3]) {
-            tsdf_raycast<<<grid, 256, 0, c->stream>>>(t->v, a, dst[0], dst[1], dst[2]);
-        });
-    }
-    float* raw[3];
-    for (int k = 0; k < 3; ++k) TRY(ensure(c, c->stage[3 + k], (size_t)npix * 3, &raw[k]));
-    uint32_t* flags;
-    TRY(ensure(c, c->flags, (size_t)npix, &flags));
-    tsdf_raycast<<<grid, 256, 0, c->stream>>>(t->v, a, raw[0], raw[1], raw[2]);
-    KCHK(c);
-    finite_flags<<<blocks_for(npix), 256, 0, c->stream>>>(raw[0], npix, 1, 1, flags);  // RemoveNoneFinitePoints(true, true)
-    KCHK(c);
-    // (the count before anything is written: compact_by_flags would have to write first)
-    return cloud_emit_counted(c, what, flags, npix, out, {true, true, true}, capacity, m, mem_kind,
-                              [&](const uint32_t* pos, float* const dst[3]) {
-                                  select_gather<<<blocks_for(npix), 256, 0, c->stream>>>(flags, pos, npix, raw[0], raw[1], raw[2],
-                                                                                        dst[0], dst[1], dst[2], (int64_t*)nullptr);
-                              });
+int mi_icp_tsdf_raycast_levels(mi_icp_ctx* c, mi_icp_tsdf* t, int levels, int width, int height, const float* intrinsic4,
+                               const float* extrinsic, float sdf_trunc, int valid_only, float* out_xyz, float* out_normals,
+                               float* out_colors, int64_t capacity, int64_t* m) {
+    float* const out[3] = {out_xyz, out_normals, out_colors};
+    return tsdf_raycast_levels(c, t, "tsdf_raycast_levels", levels, width, height, intrinsic4, extrinsic, sdf_trunc, valid_only, out,
+                               capacity, m, MI_ICP_DEVICE);
 }
 
 int mi_icp_tsdf_get_voxels(mi_icp_ctx* c, mi_icp_tsdf* t, float* tsdf_out, float* weight_out, float* color_out, int mem_kind) {

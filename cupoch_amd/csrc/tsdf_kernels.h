@@ -13,13 +13,16 @@
 //                     A wave whose z-span lies behind the camera or beside the image by a margin that covers every
 //                     rounding of the per-voxel arithmetic leaves before any of it.
 //   tsdf_raycast      one lane per pixel, an 8x8 pixel tile per wave, so that neighbouring rays gather neighbouring
-//                     voxels.  Writes NaN for an invalid pixel; finite_flags + scan + select_gather (select.h) remove
-//                     those when asked.
+//                     voxels; one launch covers every level of a camera pyramid (TsdfRayLevel), a workgroup finds its
+//                     level from its index.  Writes NaN for an invalid pixel; finite_flags + scan + select_gather
+//                     (select.h) over the concatenated pixels remove those when asked, tsdf_level_ends reads the
+//                     levels' counts from the scan.
 //   tsdf_cloud_count / tsdf_cloud_gather   ExtractPointCloud: per interior voxel the number of its +x, +y, +z edges
 //                     that cross zero; after the scan the gather recomputes the survivors' points, colours and
 //                     normals (6 x 8 tsdf gathers each, GetNormalAt).
 //   tsdf_voxel_flags / tsdf_voxel_gather   ExtractVoxelPointCloud: the valid voxels, ascending.
-// No kernel here keeps an array that is indexed at run time: none uses scratch memory.
+// No kernel here keeps an array in registers that is indexed at run time: none uses scratch memory (tsdf_raycast's table
+// of levels is a kernel argument read through a workgroup-uniform index, i.e. scalar loads).
 #pragma once
 #include "device_utils.h"
 #include "grid_rules.h"
@@ -313,10 +316,22 @@ static __global__ __launch_bounds__(256) void tsdf_cloud_gather(TsdfVol v, int64
 }
 
 // ---- raycast --------------------------------------------------------------------------------------------------------
+constexpr int kTsdfMaxLevels = 16;  // MI_ICP_TSDF_MAX_LEVELS
+
+// one level of the camera's pyramid (PinholeCameraIntrinsic::CreatePyramidLevel) and where its work and output start
+struct TsdfRayLevel {
+    float fx, fy, cx, cy;
+    int width, height;
+    int tiles_x;          // 16 x 16 tiles in a row of this level
+    int first_tile;       // the level's first workgroup; an empty level has the next level's
+    int64_t first_pixel;  // the level's first pixel in the concatenated output
+};
+
 struct TsdfRaycast {
     float R[3][3], t[3];  // camera pose (the inverse of the extrinsic) with the volume's origin taken off t
-    float fx, fy, cx, cy, sdf_trunc;
-    int width, height;
+    float sdf_trunc;
+    int levels;
+    TsdfRayLevel level[kTsdfMaxLevels];  // read through a workgroup-uniform index: scalar loads of the kernel's arguments
 };
 
 __device__ __forceinline__ bool tsdf_inside(int g0, int g1, int g2, int lo, int res) {
@@ -351,20 +366,15 @@ __device__ __forceinline__ void tsdf_store3(float* __restrict__ o, int64_t i, fl
     o[i * 3 + 2] = c;
 }
 
-// block = 16 x 16 pixels, each wave an 8 x 8 tile of it
-static __global__ __launch_bounds__(256) void tsdf_raycast(TsdfVol v, TsdfRaycast a, float* __restrict__ oxyz,
-                                                          float* __restrict__ onrm, float* __restrict__ ocol) {
-    const int lane = (int)(threadIdx.x & 63u), wid = (int)(threadIdx.x >> 6);
-    const int x = (int)blockIdx.x * 16 + (wid & 1) * 8 + (lane & 7);
-    const int y = (int)blockIdx.y * 16 + (wid >> 1) * 8 + (lane >> 3);
-    if (x >= a.width || y >= a.height) return;
-    const int64_t pix = (int64_t)y * a.width + x;
-    float P[3] = {NAN, NAN, NAN}, N[3] = {NAN, NAN, NAN}, C[3] = {NAN, NAN, NAN};
+// THE PER-PIXEL RULE of Raycast (include/mi_icp.h): the ray of pixel (x, y) of the camera L, marched through the volume;
+// point, normal and colour of its first crossing from positive to negative, else P, N and C stay as they came
+__device__ __forceinline__ void tsdf_raycast_pixel(const TsdfVol& v, const TsdfRaycast& a, const TsdfRayLevel& L, int x, int y,
+                                                   float (&P)[3], float (&N)[3], float (&C)[3]) {
     const int res = v.res;
     const float vl = v.voxel_length;
     do {
         const float length = (float)res * vl;
-        const float ppx = ((float)x - a.cx) / a.fx, ppy = ((float)y - a.cy) / a.fy;
+        const float ppx = ((float)x - L.cx) / L.fx, ppy = ((float)y - L.cy) / L.fy;
         float d0 = (a.R[0][0] * ppx + a.R[0][1] * ppy) + a.R[0][2];
         float d1 = (a.R[1][0] * ppx + a.R[1][1] * ppy) + a.R[1][2];
         float d2 = (a.R[2][0] * ppx + a.R[2][1] * ppy) + a.R[2][2];
@@ -436,9 +446,38 @@ static __global__ __launch_bounds__(256) void tsdf_raycast(TsdfVol v, TsdfRaycas
             }
         }
     } while (false);
+}
+
+// block = 16 x 16 pixels, each wave an 8 x 8 tile of it; the blocks of the levels one after the other (level 0 first,
+// each level's tiles row by row), a block finds its level from its index.  The levels' pixels are written one level
+// after the other, each in pixel order.
+static __global__ __launch_bounds__(256) void tsdf_raycast(TsdfVol v, TsdfRaycast a, float* __restrict__ oxyz,
+                                                          float* __restrict__ onrm, float* __restrict__ ocol) {
+    const int tile = (int)blockIdx.x;
+    int lv = 0;
+    for (int i = 1; i < a.levels; ++i) lv = tile >= a.level[i].first_tile ? i : lv;
+    const TsdfRayLevel& L = a.level[lv];
+    const int t = tile - L.first_tile, ty = t / L.tiles_x, tx = t - ty * L.tiles_x;
+    const int lane = (int)(threadIdx.x & 63u), wid = (int)(threadIdx.x >> 6);
+    const int x = tx * 16 + (wid & 1) * 8 + (lane & 7);
+    const int y = ty * 16 + (wid >> 1) * 8 + (lane >> 3);
+    if (x >= L.width || y >= L.height) return;
+    const int64_t pix = L.first_pixel + (int64_t)y * L.width + x;
+    float P[3] = {NAN, NAN, NAN}, N[3] = {NAN, NAN, NAN}, C[3] = {NAN, NAN, NAN};
+    tsdf_raycast_pixel(v, a, L, x, y, P, N, C);
     tsdf_store3(oxyz, pix, P[0], P[1], P[2]);
     tsdf_store3(onrm, pix, N[0], N[1], N[2]);
     tsdf_store3(ocol, pix, C[0], C[1], C[2]);
+}
+
+// after the scan of the concatenated pixels' flags: end[i] = the kept pixels of the levels 0..i (pos at the next level's
+// first pixel; *total where no pixel follows)
+static __global__ __launch_bounds__(64) void tsdf_level_ends(TsdfRaycast a, int64_t npix, const uint32_t* __restrict__ pos,
+                                                            const uint32_t* __restrict__ total, uint32_t* __restrict__ end) {
+    const int i = (int)threadIdx.x;
+    if (i >= a.levels) return;
+    const int64_t next = i + 1 < a.levels ? a.level[i + 1].first_pixel : npix;
+    end[i] = next < npix ? pos[next] : *total;
 }
 
 }  // namespace mi

@@ -737,6 +737,29 @@ class Engine:
             self._ctx, vol, int(width), int(height), K, Eptr, float(sdf_trunc), int(bool(valid_only)), p[0], p[1], p[2],
             cap, m, kind), [True, True, True], int(width) * int(height), self._tsdf_device(on_device))
 
+    TSDF_MAX_LEVELS = 16            # MI_ICP_TSDF_MAX_LEVELS
+
+    def tsdf_raycast_levels(self, vol, levels, width, height, intrinsic4, extrinsic, sdf_trunc, valid_only=True,
+                            on_device=True):
+        """-> [(points, normals, colors) of level i, in pixel order] for the `levels` levels of the camera's pyramid
+        (mi_icp_tsdf_raycast_levels): one call, with room for every pixel of every level.  The levels are slices of
+        three device arrays."""
+        levels, width, height = int(levels), int(width), int(height)
+        K = (C.c_float * 4)(*[float(v) for v in intrinsic4])
+        keep, Eptr = _T_in(extrinsic)
+        capacity = sum(max(width >> i, 0) * max(height >> i, 0) for i in range(max(0, min(levels, self.TSDF_MAX_LEVELS))))
+        m = (C.c_int64 * self.TSDF_MAX_LEVELS)()
+        outs = [self._out(MI_ICP_DEVICE, self._tsdf_device(True), (capacity, 3)) for _ in range(3)]
+        self._chk(self._L.mi_icp_tsdf_raycast_levels(self._ctx, vol, levels, width, height, K, Eptr, float(sdf_trunc),
+                                                     int(bool(valid_only)), outs[0][1], outs[1][1], outs[2][1], capacity, m))
+        clouds, first = [], 0
+        for i in range(levels):
+            k = int(m[i])
+            level = [a[first:first + k] for a, _ in outs]
+            clouds.append(tuple(level if on_device else [a.cpu().numpy() for a in level]))
+            first += k
+        return clouds
+
     def tsdf_get_voxels(self, vol, n, colored, on_device=False):
         """-> (tsdf[n], weight[n], color[n, 3] or None)"""
         dev = self._tsdf_device(on_device)

@@ -97,6 +97,13 @@ class UniformTSDFVolume(TSDFVolume):
                                          sdf_trunc, project_valid_depth_only)
         return _cloud(p, n, c)
 
+    def raycast_levels(self, intrinsic, extrinsic, sdf_trunc, levels, project_valid_depth_only=True):
+        """[raycast(intrinsic.create_pyramid_level(i), extrinsic, sdf_trunc, project_valid_depth_only) for i in
+        range(levels)], the same bytes, in one pass over the volume (mi_icp_tsdf_raycast_levels)"""
+        return [_cloud(p, n, c) for p, n, c in self._eng.tsdf_raycast_levels(
+            self._vol, levels, intrinsic.width, intrinsic.height, intrinsic.as4(), extrinsic, sdf_trunc,
+            project_valid_depth_only)]
+
     def get_voxels(self):
         """(tsdf[n], weight[n], color[n, 3]) as numpy arrays, n = resolution^3 indexed x*res*res + y*res + z; a
         NoColor volume reports the colour every voxel starts with, (1, 1, 1)"""

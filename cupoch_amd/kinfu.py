@@ -1,25 +1,27 @@
-"""The ICP and volume sides of cupoch.kinfu.KinfuPipeline (src/cupoch/kinfu/kinfu.h:36-121, kinfu.cpp:51-143): the
-depth-frame -> point-cloud pyramid of SurfaceMeasurement, the coarse-to-fine PoseEstimation that calls
-RegistrationICP / RegistrationColoredICP once per pyramid level, and the two volume steps of ProcessFrame
-(Integrate, then one Raycast per pyramid level).  The image pyramid and the bilateral depth filter that ProcessFrame
-needs in front of them exist now (geometry.RGBDImage.create_pyramid / bilateral_filter_pyramid_depth);
-ProcessFrame as a whole is still not composed from these pieces."""
+"""cupoch.kinfu (src/cupoch/kinfu/kinfu.h:36-121, kinfu.cpp:29-143; python surface cupoch_pybind/kinfu/kinfu.cpp):
+KinfuOption and KinfuPipeline, the KinectFusion frame loop -- image pyramid and bilateral depth filter
+(geometry.RGBDImage.create_pyramid / bilateral_filter_pyramid_depth), the depth-frame -> point-cloud pyramid of
+SurfaceMeasurement, the coarse-to-fine PoseEstimation that calls RegistrationICP / RegistrationColoredICP once per
+pyramid level, Integrate, and the model pyramid of the next frame, raycast for all levels in one pass
+(UniformTSDFVolume.raycast_levels).  The pieces stay public functions of this module; DESIGN.md 4.14 has the data flow
+of a frame and where the pipeline refuses a call the reference would go on with.  Not built: extract_triangle_mesh (no
+TriangleMesh type here)."""
 import numpy as np
 
 from . import geometry, registration
 from .integration import TSDFVolumeColorType, UniformTSDFVolume
 from .registration import TransformationEstimationType
 
+MAX_PYRAMID_LEVELS = 16     # MI_ICP_TSDF_MAX_LEVELS: what one raycast_levels call takes
+
 
 class KinfuOption:
-    """kinfu.h:36-82, the fields PoseEstimation / SurfaceMeasurement and the volume read (diameter, sigma_depth and
-    sigma_space belong to the bilateral filter, geometry.RGBDImage.bilateral_filter_pyramid_depth, which ProcessFrame would
-    call; it is not composed here)."""
+    """kinfu.h:36-80; the reference's defaults"""
 
     def __init__(self, num_pyramid_levels=4, depth_cutoff=3.0, distance_threshold=0.5,
                  icp_iterations=(20, 20, 20, 20), tf_type=TransformationEstimationType.PointToPlane,
                  tsdf_length=8.0, tsdf_resolution=512, sdf_trunc=0.05, tsdf_color_type=TSDFVolumeColorType.RGB8,
-                 tsdf_origin=(0.0, 0.0, 0.0)):
+                 tsdf_origin=(0.0, 0.0, 0.0), diameter=1, sigma_depth=1.0, sigma_space=10.0):
         self.num_pyramid_levels = int(num_pyramid_levels)
         self.depth_cutoff = float(depth_cutoff)
         self.distance_threshold = float(distance_threshold)
@@ -30,6 +32,9 @@ class KinfuOption:
         self.sdf_trunc = float(sdf_trunc)
         self.tsdf_color_type = TSDFVolumeColorType(tsdf_color_type)
         self.tsdf_origin = np.asarray(tsdf_origin, np.float32).reshape(3)
+        self.diameter = int(diameter)
+        self.sigma_depth = float(sigma_depth)
+        self.sigma_space = float(sigma_space)
 
 
 def create_volume(option, device=None):
@@ -40,12 +45,12 @@ def create_volume(option, device=None):
 
 def integrate_and_raycast(volume, option, image, intrinsic, extrinsic):
     """ProcessFrame's volume steps (kinfu.cpp:69-73): volume.Integrate(image, intrinsic, extrinsic), then
-    volume.Raycast(intrinsic.CreatePyramidLevel(i), extrinsic, sdf_trunc) for every level -- the model pyramid that
-    pose_estimation takes as target_data for the next frame.  None when the frame's format is turned away."""
+    volume.Raycast(intrinsic.CreatePyramidLevel(i), extrinsic, sdf_trunc) for every level (one raycast_levels call, the
+    same bytes) -- the model pyramid of the next frame's pose_estimation.  None when the frame's format is turned
+    away."""
     if not volume.integrate(image, intrinsic, extrinsic):
         return None
-    return [volume.raycast(intrinsic.create_pyramid_level(i), extrinsic, option.sdf_trunc)
-            for i in range(option.num_pyramid_levels)]
+    return volume.raycast_levels(intrinsic, extrinsic, option.sdf_trunc, option.num_pyramid_levels)
 
 
 def point_cloud_pyramid(depth_pyramid, intrinsic, option, color_pyramid=None):
@@ -80,3 +85,80 @@ def pose_estimation(option, extrinsic, frame_data, target_data):
         else:
             print("[cupoch_amd] Error: [KinfuPipeline::PoseEstimation] Unsupported transformation type.")
     return cur, True
+
+
+def inverse_transform(T):
+    """utility::InverseTransform (utility/eigen.cu:69-75) in fp32: R^T and -(R^T t)"""
+    T = np.asarray(T, np.float32).reshape(4, 4)
+    inv = np.eye(4, dtype=np.float32)
+    inv[:3, :3] = T[:3, :3].T
+    for r in range(3):
+        inv[r, 3] = -((inv[r, 0] * T[0, 3] + inv[r, 1] * T[1, 3]) + inv[r, 2] * T[2, 3])
+    return inv
+
+
+class KinfuPipeline:
+    """kinfu::KinfuPipeline (kinfu.h:82-111).  process_frame is kinfu.cpp:51-76 composed from this module's functions.
+    Where the reference reads out of bounds or goes on with garbage the call is refused: a line
+    "[cupoch_amd] Error: [KinfuPipeline::ProcessFrame] ..." is printed, False comes back, and cur_pose, volume,
+    model_pyramid and frame_id are as they were."""
+
+    def __init__(self, intrinsic, option=None, device=None):
+        self.intrinsic = intrinsic
+        self.option = KinfuOption() if option is None else option
+        self.cur_pose = np.eye(4, dtype=np.float32)
+        self.frame_id = 0
+        self.volume = create_volume(self.option, device)
+        self.model_pyramid = []
+
+    def reset(self):
+        self.cur_pose = np.eye(4, dtype=np.float32)
+        self.volume.reset()
+        self.model_pyramid = []
+        self.frame_id = 0
+
+    @staticmethod
+    def _refuse(why):
+        print("[cupoch_amd] Error: [KinfuPipeline::ProcessFrame] " + why)
+        return False
+
+    def surface_measurement(self, image):
+        """KinfuPipeline::SurfaceMeasurement (kinfu.cpp:86-104) -> (image pyramid, filtered pyramid, cloud pyramid);
+        the image pyramid is empty when the images' formats have none"""
+        o = self.option
+        pyramid = image.create_pyramid(o.num_pyramid_levels)
+        if len(pyramid) != o.num_pyramid_levels:
+            return [], [], []
+        smooth = geometry.RGBDImage.bilateral_filter_pyramid_depth(pyramid, o.diameter, o.sigma_depth, o.sigma_space)
+        clouds = point_cloud_pyramid([s.depth for s in smooth], self.intrinsic, o, [s.color for s in smooth])
+        return pyramid, smooth, clouds
+
+    def process_frame(self, image):
+        o = self.option
+        color, depth = geometry.Image(image.color), geometry.Image(image.depth)
+        if color.is_empty() or depth.is_empty():
+            return self._refuse("The frame has no colour or no depth data.")
+        if not 1 <= o.num_pyramid_levels <= MAX_PYRAMID_LEVELS:
+            return self._refuse("num_pyramid_levels must be in [1, %d]." % MAX_PYRAMID_LEVELS)
+        if len(o.icp_iterations) < o.num_pyramid_levels:
+            return self._refuse("icp_iterations has fewer entries than num_pyramid_levels.")
+        size = (self.intrinsic.width, self.intrinsic.height)
+        if (color.width, color.height) != size or (depth.width, depth.height) != size:
+            return self._refuse("The frame's size is not the intrinsic's.")
+        _, smooth, pc_pyramid = self.surface_measurement(image)
+        if not smooth:
+            return self._refuse("Unsupported image format.")
+        extrinsic = inverse_transform(self.cur_pose)
+        if self.frame_id > 0:
+            extrinsic, _ = pose_estimation(o, extrinsic, self.model_pyramid, pc_pyramid)
+        # the volume turns a format away before it changes anything: the pose is kept only with an integrated frame
+        if not self.volume.integrate(smooth[0], self.intrinsic, extrinsic):
+            return self._refuse("Unsupported image format.")
+        if self.frame_id > 0:
+            self.cur_pose = inverse_transform(extrinsic)
+        self.model_pyramid = self.volume.raycast_levels(self.intrinsic, extrinsic, o.sdf_trunc, o.num_pyramid_levels)
+        self.frame_id += 1
+        return True
+
+    def extract_point_cloud(self):
+        return self.volume.extract_point_cloud()

@@ -1,4 +1,4 @@
-"""The reference's pybind11 module (`cupoch_pybind`: utility / geometry / camera / integration / imageproc / collision / planning / registration) built on this
+"""The reference's pybind11 module (`cupoch_pybind`: utility / geometry / camera / integration / imageproc / collision / planning / registration / kinfu) built on this
 repository's C++ surface -- cupoch_amd/cpp/src/pybind_module.cpp, compiled by `make -C cupoch_amd/cpp`
 (`__graft_entry__.build()`).  Usage, as with the reference's package:
 
@@ -36,4 +36,5 @@ utility, geometry, registration = _m.utility, _m.geometry, _m.registration
 camera, integration, collision, planning = _m.camera, _m.integration, _m.collision, _m.planning
 integration_scalable = _m.integration_scalable
 imageproc = _m.imageproc
+kinfu = _m.kinfu
 initialize_allocator = _m.initialize_allocator

@@ -739,6 +739,23 @@ MI_ICP_API int mi_icp_gaussian_filter(mi_icp_ctx* ctx, const float* xyz, const f
  *  Deviation (deliberate): the reference sizes ExtractPointCloud's outputs by the number of valid
  *  voxels and writes up to three points per voxel into them; here outputs hold the actual count.
  *
+ *  raycast_levels  Raycast for every level of the camera's pyramid in one pass: mi_icp_tsdf_raycast_levels(levels, width,
+ *             height, intrinsic4, ...) gives what `levels` Raycast calls with the cameras
+ *             PinholeCameraIntrinsic::CreatePyramidLevel(i), i = 0 .. levels-1, give (pinhole_camera_intrinsic.h:31-36),
+ *             the same extrinsic and sdf_trunc: level 0 is the intrinsic as passed; for i > 0, s = powf(0.5f, (float)i),
+ *             size (width >> i) x (height >> i), fx*s, fy*s, (cx + 0.5f)*s - 0.5f, (cy + 0.5f)*s - 0.5f.  The values
+ *             per pixel are those of "Raycast" above.  The levels' points are concatenated in level order, each level
+ *             in pixel order: level i starts at point m[0] + ... + m[i-1] and has m[i] points (m is int64_t[levels]).
+ *             `capacity` is the total in points: when it is smaller than m[0] + ... + m[levels-1] nothing is written
+ *             and every m[i] is still filled.  With valid_only == 0, m[i] = (width >> i) * (height >> i) and an
+ *             invalid pixel is NaN.  A level whose size is zero has 0 points.  1 <= levels <=
+ *             MI_ICP_TSDF_MAX_LEVELS (an image side is at most 2^15: level 16 is always empty); otherwise the
+ *             argument checks and status codes of mi_icp_tsdf_raycast.  ARRAYS ARE DEVICE POINTERS; this entry has
+ *             no memory-kind argument (as the scalable volume's and the occupancy grid's).  mi_icp_tsdf_raycast is
+ *             its levels == 1 form and adds the staging of MI_ICP_HOST arrays.  One launch marches every level's
+ *             rays; with valid_only one scan over the concatenated pixels serves all levels, and the stream is
+ *             waited for once for the counts and once after the fill, whatever the number of levels.
+ *
  * OUTPUTS OF UNKNOWN SIZE follow one rule in all three calls: the caller passes a `capacity` (in
  * points) and gets the needed count in *m.  When capacity >= *m the arrays are filled with *m points;
  * otherwise nothing is written and the call is MI_ICP_OK -- call again with room (capacity 0 and null
@@ -762,6 +779,7 @@ MI_ICP_API int mi_icp_gaussian_filter(mi_icp_ctx* ctx, const float* xyz, const f
 #define MI_ICP_TSDF_MAX_RESOLUTION 1024
 #define MI_ICP_TSDF_MAX_MARCH 1048576
 #define MI_ICP_TSDF_MAX_IMAGE_SIDE 32768
+#define MI_ICP_TSDF_MAX_LEVELS 16
 typedef struct mi_icp_tsdf mi_icp_tsdf;
 MI_ICP_API int mi_icp_tsdf_create(mi_icp_ctx* ctx, float length, int resolution, float sdf_trunc, int color_type,
                                   const float* origin3, mi_icp_tsdf** out);
@@ -782,6 +800,10 @@ MI_ICP_API int mi_icp_tsdf_raycast(mi_icp_ctx* ctx, mi_icp_tsdf* volume, int wid
                                    const float* intrinsic4, const float* extrinsic, float sdf_trunc,
                                    int valid_only, float* out_xyz, float* out_normals, float* out_colors,
                                    int64_t capacity, int64_t* m, int mem_kind);
+MI_ICP_API int mi_icp_tsdf_raycast_levels(mi_icp_ctx* ctx, mi_icp_tsdf* volume, int levels, int width, int height,
+                                          const float* intrinsic4, const float* extrinsic, float sdf_trunc,
+                                          int valid_only, float* out_xyz, float* out_normals, float* out_colors,
+                                          int64_t capacity, int64_t* m);
 MI_ICP_API int mi_icp_tsdf_get_voxels(mi_icp_ctx* ctx, mi_icp_tsdf* volume, float* tsdf_out, float* weight_out,
                                       float* color_out, int mem_kind);
 
