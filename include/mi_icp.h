@@ -358,7 +358,40 @@ MI_ICP_API int mi_icp_remove_none_finite(mi_icp_ctx* ctx, const float* xyz, cons
  *               flipped to z <= 0 (:161-199); valid_only = 0 keeps one point per
  *               pixel, rejected ones +inf.
  * Outputs must hold (width/stride)*(height/stride) points; *m = points written, in
- * pixel order. */
+ * pixel order.
+ *
+ * THE NUMERIC CONTRACT (fp32, products never fused, division and sqrtf correctly rounded, in exactly the
+ * order written; tests/depth_exact.py restates it in numpy).
+ *  pose     the extrinsic's inverse (the identity's for NULL), computed IN DOUBLE by Gauss-Jordan elimination
+ *           with partial pivoting (the pivot of a column is the first row of the largest magnitude at or below
+ *           the diagonal; the pivot row is divided by the pivot, then taken times the entry from every other
+ *           row whose entry in that column is not zero), every entry rounded to float at the end.  A column
+ *           whose pivot is 0: MI_ICP_ERR_INVALID.  Only its rows 0..2 are used.
+ *  pixels   output element idx stands for row = (idx / (width/stride)) * stride, col = (idx % (width/stride))
+ *           * stride (integer divisions), pix = row*width + col.
+ *  d        the depth of the pixel; for MI_ICP_DEPTH_U16 (float)v / (float)(int)depth_scale, set to 0 when
+ *           >= (float)(int)depth_trunc.
+ *  accepted rgbd = 0: !(d <= 0) -- NaN and +inf are accepted.  rgbd = 1: d > 0 && (depth_cutoff <= 0 ||
+ *           depth_cutoff > d).
+ *  point    x = ((float)col - cx) * d / fx,  y = ((float)row - cy) * d / fy,
+ *           p[r] = ((pose[r][0]*x + pose[r][1]*y) + pose[r][2]*d) + pose[r][3]  for r = 0, 1, 2.
+ *           A rejected pixel's point is (+inf, +inf, +inf).
+ *  colour   MI_ICP_COLOR_U8X3: (float)u8 / 255.0f per channel; MI_ICP_COLOR_F32X1: the value, three times.
+ *           A rejected pixel's colour is (+inf, +inf, +inf); an accepted pixel keeps its colour even where
+ *           its point is not finite.
+ *  normal   (rgbd = 1, stride 1) of pixel pix: zero when row < 1 || col < 1.  Otherwise, with the points of
+ *           l = pixel pix-1, r = pixel pix+1, u = pixel pix-width, d = pixel pix+width -- so the right
+ *           neighbour of the last column is the next row's first pixel; r and d count as (0,0,0) when their
+ *           index is >= width*height; any neighbour with a coordinate that is not finite counts as (0,0,0):
+ *           h = l - r,  v = u - d,  c = (h1*v2 - h2*v1, h2*v0 - h0*v2, h0*v1 - h1*v0),
+ *           norm = sqrtf((c0*c0 + c1*c1) + c2*c2).  norm == 0: the normal is (0,0,0).  Otherwise n = c / norm,
+ *           and if n2 > 0 every component is multiplied by -1.0f (a zero component becomes -0).  The pixel's
+ *           own point plays no part: a pixel without a point has a normal (seen with valid_only = 0).
+ *  valid_only  keeps the pixels whose three coordinates are finite, in pixel order, with their normals and
+ *           colours; 0 writes every sampled pixel.  rgbd = 0 always compacts.
+ *  A comparison may rely on every word written, the sign of zeros and infinities included; only the sign and
+ *  payload of a NaN are not defined (a NaN arises from 0 * inf and inf - inf: col == cx under an infinite
+ *  depth, overflowing products). */
 #define MI_ICP_DEPTH_F32 0
 #define MI_ICP_DEPTH_U16 1
 #define MI_ICP_COLOR_NONE 0

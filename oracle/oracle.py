@@ -354,8 +354,9 @@ def pyramid_level_intrinsic(width, height, fx, fy, cx, cy, level):
 
 def create_from_depth(depth, intrinsic4, extrinsic=None, color=None, depth_scale=1000.0,
                       depth_trunc=1000.0, depth_cutoff=-1.0, stride=1, rgbd=False,
-                      compute_normals=False, valid_only=True):
-    """PointCloud::CreateFromDepthImage / CreateFromRGBDImage (pointcloud_factory.cu:286-376)."""
+                      compute_normals=False, valid_only=True, pose=None):
+    """PointCloud::CreateFromDepthImage / CreateFromRGBDImage (pointcloud_factory.cu:286-376).
+    pose: the extrinsic's inverse (row-major 4x4) where the caller has its own; else numpy.linalg.inv's."""
     depth = np.ascontiguousarray(depth)
     h, w = depth.shape
     if depth.dtype == np.uint16:
@@ -369,7 +370,8 @@ def create_from_depth(depth, intrinsic4, extrinsic=None, color=None, depth_scale
         color = np.ascontiguousarray(color)
         kind = 1 if color.dtype == np.uint8 else 2
     E = np.eye(4) if extrinsic is None else np.asarray(extrinsic, np.float64).reshape(4, 4)
-    pose = np.ascontiguousarray(np.linalg.inv(E).astype(np.float32).T)   # column-major
+    pose = np.linalg.inv(E) if pose is None else np.asarray(pose).reshape(4, 4)
+    pose = np.ascontiguousarray(pose.astype(np.float32).T)               # column-major
     K = _f32(np.asarray(intrinsic4, np.float32))
     count = (w // stride) * (h // stride)
     op = np.empty((count, 3), np.float32)

@@ -6,50 +6,12 @@ a test."""
 import numpy as np
 
 import tsdf_exact as tx
+from depth_exact import depth_points, invert4          # noqa: F401 (the pose and stage 1's points: one restatement)
 
 F = np.float32
 NO_COLOR, RGB8, GRAY32 = tx.NO_COLOR, tx.RGB8, tx.GRAY32
 RES, UNIT = 16, 4096
 KEY_MAX = (1 << 20) - 1
-
-
-def invert4(E):
-    """the pose of an extrinsic as the library computes it: Gauss-Jordan with partial pivoting in double, rounded to
-    float at the end (row-major in, row-major out)"""
-    a = [[float(E[r][k]) for k in range(4)] + [1.0 if r == k else 0.0 for k in range(4)] for r in range(4)]
-    for col in range(4):
-        piv = col
-        for r in range(col + 1, 4):
-            if abs(a[r][col]) > abs(a[piv][col]):
-                piv = r
-        assert abs(a[piv][col]) > 0.0, "singular extrinsic"
-        a[piv], a[col] = a[col], a[piv]
-        d = a[col][col]
-        a[col] = [v / d for v in a[col]]
-        for r in range(4):
-            if r != col and a[r][col] != 0.0:
-                f = a[r][col]
-                a[r] = [a[r][k] - f * a[col][k] for k in range(8)]
-    return np.array([[a[r][4 + k] for k in range(4)] for r in range(4)], np.float64).astype(F)
-
-
-def depth_points(depth, width, height, fx, fy, cx, cy, extrinsic, stride):
-    """the world points of the sampled pixels (PointCloud::CreateFromDepthImage, depth_scale 1000, depth_trunc 1000,
-    project_valid_depth_only), in pixel order"""
-    fx, fy, cx, cy = F(fx), F(fy), F(cx), F(cy)
-    pose = invert4(np.asarray(extrinsic, F).reshape(4, 4))
-    rows = (np.arange(height // stride) * stride)
-    cols = (np.arange(width // stride) * stride)
-    r, c = np.meshgrid(rows, cols, indexing="ij")
-    r, c = r.reshape(-1), c.reshape(-1)
-    d = np.asarray(depth, F)[r, c]
-    ok = ~(d <= F(0))
-    r, c, z = r[ok], c[ok], d[ok]
-    with np.errstate(all="ignore"):
-        x = (c.astype(F) - cx) * z / fx
-        y = (r.astype(F) - cy) * z / fy
-        p = np.stack([((pose[k, 0] * x + pose[k, 1] * y) + pose[k, 2] * z) + pose[k, 3] for k in range(3)], 1).astype(F)
-    return p[np.isfinite(p).all(1)]
 
 
 def keys_of_points(p, sdf_trunc, L):

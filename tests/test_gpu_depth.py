@@ -1,13 +1,13 @@
-"""GPU: depth / RGB-D image -> point cloud (PointCloud::CreateFromDepthImage,
-CreateFromRGBDImage, pointcloud_factory.cu:286-376) and the KinFu pose estimation that
-feeds those clouds to RegistrationICP level by level (kinfu.cpp:105-143), against the
-oracle's restatement.  The kernel recomputes points instead of storing a structured cloud
-and the compiler may contract a*b+c on the GPU, so coordinates are compared to 2 ulp-ish
-(2e-6 relative); counts, validity and pixel order must be identical."""
+"""GPU: depth / RGB-D image -> point cloud (PointCloud::CreateFromDepthImage, CreateFromRGBDImage,
+pointcloud_factory.cu:286-376) held to the numpy restatement of its contract (tests/depth_exact.py, which
+test_depth_exact_cpu.py pins to the C oracle and to hand-worked images): the count and the pixel order first, then every
+word of the points, normals and colours of every pixel, from numpy arrays and from device tensors.  And the KinFu pose
+estimation that feeds those clouds to RegistrationICP level by level (kinfu.cpp:105-143), whose bounds are ICP's."""
 import numpy as np
 import pytest
 import torch
 
+import depth_exact as dx
 from conftest import render_depth, small_pose
 from oracle import oracle as orc
 
@@ -24,13 +24,40 @@ def eng():
     e.close()
 
 
-def _close(a, b, tol=2e-6):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape
-    fin = np.isfinite(b)
-    assert (np.isfinite(a) == fin).all()
-    assert (a[~fin] == b[~fin]).all()
-    np.testing.assert_allclose(a[fin], b[fin], rtol=tol, atol=tol)
+def to_np(v):
+    return None if v is None else np.asarray(v.cpu() if hasattr(v, "cpu") else v)
+
+
+def on_device(a):
+    if a is None:
+        return None
+    if a.dtype == np.uint16:
+        return torch.from_numpy(a.view(np.int16)).cuda().view(torch.uint16)
+    return torch.from_numpy(a).cuda()
+
+
+def held(got, want, width):
+    """got = (points, normals, colors) of the library, want = depth_exact.cloud's four: count and order, then every word"""
+    wp, wn, wc, pix = want
+    gp, gn, gc = (to_np(g) for g in got)
+    assert len(gp) == len(wp), "%d points, the restatement has %d" % (len(gp), len(wp))
+    for what, g, w in (("points", gp, wp), ("normals", gn, wn), ("colors", gc, wc)):
+        assert (g is None) == (w is None), what
+        if w is not None:
+            msg = dx.difference(what, g, w, pix, width)
+            assert msg is None, msg
+
+
+def both_kinds(eng, d, K4, E, color, kw, want, **u16):
+    """the call from numpy arrays and from device tensors: each exact, and the two the same bytes"""
+    out = []
+    for dev in (False, True):
+        got = eng.create_from_depth(on_device(d) if dev else d, K4, E, color=(on_device(color) if dev else color), **kw, **u16)
+        assert all(g is None or torch.is_tensor(g) == dev for g in got)
+        held(got, want, d.shape[1])
+        out.append([to_np(g) for g in got])
+    for a, b in zip(*out):
+        assert (a is None and b is None) or a.tobytes() == b.tobytes()
 
 
 def _depth_with_defects(w=640, h=480, seed=3):
@@ -47,78 +74,91 @@ def _depth_with_defects(w=640, h=480, seed=3):
 @pytest.mark.parametrize("with_extrinsic", [False, True])
 def test_depth_image_float(eng, stride, with_extrinsic):
     d = _depth_with_defects()
-    E = np.linalg.inv(small_pose(0.3, 0.5)) if with_extrinsic else None
-    ref, _, _ = orc.create_from_depth(d, K, E, stride=stride)
-    for dev in (False, True):
-        got, n, c = eng.create_from_depth(torch.from_numpy(d).cuda() if dev else d, K, E, stride=stride)
-        assert n is None and c is None
-        _close(got.cpu().numpy() if dev else got, ref)
-    assert 0 < len(ref) < (640 // stride) * (480 // stride)
+    E = np.linalg.inv(small_pose(0.3, 0.5)).astype(np.float32) if with_extrinsic else None
+    want = dx.cloud(d, K, E, stride=stride)
+    both_kinds(eng, d, K, E, None, dict(stride=stride), want)
+    assert 0 < len(want[0]) < (640 // stride) * (480 // stride)
+
+
+@pytest.mark.parametrize("c", dx.depth_cases(), ids=dx.case_id)
+def test_depth_form_exact(eng, c):
+    """rgbd = 0 at the sizes, strides, extrinsics and intrinsics of depth_exact.depth_cases"""
+    d, K4, E, kw, _ = dx.case_inputs(c, False)
+    want = dx.cloud(d, K4, E, **kw)
+    both_kinds(eng, d, K4, E, None, kw, want)
+    assert (len(want[0]) > 0) == (c["stride"] <= c["w"])
 
 
 def test_depth_image_u16_scale_and_trunc(eng):
-    d = (np.clip(render_depth(320, 240, [262.5, 262.5, 159.5, 119.5], np.eye(4), holes=0.02), 0, 60) * 1000.0).astype(np.uint16)
-    for scale, trunc in ((1000.0, 1000.0), (1000.0, 3.0), (999.7, 2.9), (500.0, 4.5)):
-        ref, _, _ = orc.create_from_depth(d, [262.5, 262.5, 159.5, 119.5], None, depth_scale=scale, depth_trunc=trunc)
-        got, _, _ = eng.create_from_depth(torch.from_numpy(d.view(np.int16)).cuda().view(torch.uint16),
-                                          [262.5, 262.5, 159.5, 119.5], None, depth_scale=scale, depth_trunc=trunc)
-        _close(got.cpu().numpy(), ref)
-        got_h, _, _ = eng.create_from_depth(d, [262.5, 262.5, 159.5, 119.5], None, depth_scale=scale, depth_trunc=trunc)
-        _close(got_h, ref)
+    """values up to 65535; depth_scale and depth_trunc are held as ints (999.7 is 999, 2.9 is 2, 4.5 is 4)"""
+    u = dx.u16_image()
+    counts = []
+    for scale, trunc in dx.U16_PARAMS:
+        want = dx.cloud(dx.u16_to_float(u, scale, trunc), dx.U16_K, None)
+        both_kinds(eng, u, dx.U16_K, None, None, {}, want, depth_scale=scale, depth_trunc=trunc)
+        counts.append(len(want[0]))
+    assert counts[0] > counts[1] > counts[3] > counts[2] > 0
     # the reference holds depth_trunc as an int: 2.9 behaves as 2
-    a, _, _ = eng.create_from_depth(d, [262.5, 262.5, 159.5, 119.5], None, depth_trunc=2.9)
-    b, _, _ = eng.create_from_depth(d, [262.5, 262.5, 159.5, 119.5], None, depth_trunc=2.0)
-    assert len(a) == len(b) and len(a) > 0
+    a, _, _ = eng.create_from_depth(u, dx.U16_K, None, depth_trunc=2.9)
+    b, _, _ = eng.create_from_depth(u, dx.U16_K, None, depth_trunc=2.0)
+    assert len(a) > 0 and a.tobytes() == b.tobytes()
 
 
 @pytest.mark.parametrize("valid_only", [True, False])
 @pytest.mark.parametrize("color_kind", ["u8", "f32", None])
 def test_rgbd_image_colors_normals_cutoff(eng, valid_only, color_kind):
     d = _depth_with_defects(seed=9)
-    rng = np.random.default_rng(5)
-    col = None
-    if color_kind == "u8":
-        col = rng.integers(0, 256, (480, 640, 3), dtype=np.uint8)
-    elif color_kind == "f32":
-        col = rng.random((480, 640), dtype=np.float32)
-    E = np.linalg.inv(small_pose(0.1, 0.2))
-    kw = dict(color=col, depth_cutoff=3.0, rgbd=True, compute_normals=True, valid_only=valid_only)
-    rp, rn, rc = orc.create_from_depth(d, K, E, **kw)
-    gp, gn, gc = eng.create_from_depth(torch.from_numpy(d).cuda(), K, E,
-                                       **dict(kw, color=None if col is None else torch.from_numpy(col).cuda()))
-    _close(gp.cpu().numpy(), rp)
-    if col is None:
-        assert gc is None
-    else:
-        _close(gc.cpu().numpy(), rc, 1e-7)
-    # normals: unit vectors from differences of nearby points -- compare by angle; where the
-    # cross product is nearly degenerate the direction amplifies the 1e-7 coordinate noise
-    gn = gn.cpu().numpy()
-    assert gn.shape == rn.shape
-    zero_r, zero_g = (np.abs(rn).sum(1) == 0), (np.abs(gn).sum(1) == 0)
-    assert (zero_r == zero_g).mean() > 0.9999
-    both = ~zero_r & ~zero_g
-    cosang = (gn[both] * rn[both]).sum(1)
-    assert (cosang > 1 - 1e-6).mean() > 0.999
-    assert (gn[both][:, 2] <= 0).all()
+    col = dx.colors_of(color_kind, 640, 480, 5)
+    E = np.linalg.inv(small_pose(0.1, 0.2)).astype(np.float32)
+    kw = dict(depth_cutoff=3.0, rgbd=True, compute_normals=True, valid_only=valid_only)
+    want = dx.cloud(d, K, E, color=col, **kw)
+    both_kinds(eng, d, K, E, col, kw, want)
+    wp, wn = want[0], want[1]
+    assert (wn[:, 2] <= 0).all() and (wn != 0).any(1).sum() > len(wn) // 4    # (the scene is not mostly background)
     if valid_only:
-        assert np.isfinite(gp.cpu().numpy()).all() and len(rp) < 640 * 480
-        assert (gp.cpu().numpy()[:, 2] < 3.0 + 1.0).all()
+        assert np.isfinite(wp).all() and len(wp) < 640 * 480
     else:
-        assert len(rp) == 640 * 480
+        assert len(wp) == 640 * 480
+
+
+@pytest.mark.parametrize("c", dx.rgbd_cases(), ids=dx.case_id)
+def test_rgbd_form_exact(eng, c):
+    """rgbd = 1: the cross of colour x cutoff x valid_only x compute_normals at 37x23 (3 blocks + 83), KinFu's setting
+    and its valid_only = 0 twin at the other sizes (70x50 crosses a block and the scan tile)"""
+    d, K4, E, kw, color = dx.case_inputs(c, True)
+    want = dx.cloud(d, K4, E, color=color, **kw)
+    both_kinds(eng, d, K4, E, color, kw, want)
 
 
 def test_last_row_and_column_conventions(eng):
-    """documented handling of the reference's loose bounds test (pointcloud_factory.cu:173)"""
-    d = np.full((6, 8), 2.0, np.float32)
-    d[2, 3] = 0.0
-    _, n, _ = eng.create_from_depth(d, [4.0, 4.0, 3.5, 2.5], rgbd=True, compute_normals=True, valid_only=False)
-    _, rn, _ = orc.create_from_depth(d, [4.0, 4.0, 3.5, 2.5], rgbd=True, compute_normals=True, valid_only=False)
-    np.testing.assert_allclose(n, rn, atol=1e-6)
+    """the reference's loose bounds test (pointcloud_factory.cu:173): the right neighbour of the last column is the next
+    row's first pixel, the lower neighbour of the last row is zero, a rejected neighbour counts as (0, 0, 0)"""
+    images = dx.convention_images() + [(name, d, dx.HAND_K, -1.0) for name, d in dx.hand_images()]
+    for name, d, K4, cutoff in images:
+        for valid_only in (False, True):
+            kw = dict(rgbd=True, depth_cutoff=cutoff, compute_normals=True, valid_only=valid_only)
+            both_kinds(eng, d, K4, None, None, kw, dx.cloud(d, K4, None, **kw))
+    d = images[0][1]
+    _, n, _ = eng.create_from_depth(d, images[0][2], rgbd=True, compute_normals=True, valid_only=False)
     n = n.reshape(6, 8, 3)
     assert (n[0] == 0).all() and (n[:, 0] == 0).all()          # first row / column: zero normal
     assert (n[1:5, 1:7, 2] < 0).all()                           # interior: facing the camera
     assert np.abs(n[5, 1:7]).sum() > 0                          # last row: lower neighbour taken as zero
+
+
+def test_one_engine_a_sequence(eng):
+    """a large compacted call, a small uncompacted one, a middle compacted one, the large one again: no flag, position
+    or staged image of an earlier call is read by a later one"""
+    cases = {(c["w"], c["h"], c["valid_only"]): c for c in dx.rgbd_cases() if c["cutoff"] > 0 and c["normals"]}
+    order = [cases[640, 480, True], cases[8, 6, False], cases[70, 50, True], cases[640, 480, True]]
+    wants = {}
+    for dev in (False, True):
+        for c in order:
+            d, K4, E, kw, color = dx.case_inputs(c, True)
+            if dx.case_id(c) not in wants:
+                wants[dx.case_id(c)] = dx.cloud(d, K4, E, color=color, **kw)
+            got = eng.create_from_depth(on_device(d) if dev else d, K4, E, color=(on_device(color) if dev else color), **kw)
+            held(got, wants[dx.case_id(c)], c["w"])
 
 
 def test_argument_errors(eng):
@@ -146,20 +186,43 @@ def test_python_factories_and_pyramid_intrinsics():
         lv = intr.create_pyramid_level(level)
         assert (lv.width, lv.height) == (w, h)
         np.testing.assert_array_equal(np.float32(lv.as4()), np.float32([fx, fy, cx, cy]))
-    d = render_depth(640, 480, K, np.eye(4), holes=0.03)
-    pc = geometry.PointCloud.create_from_depth_image(geometry.Image(d), intr, np.eye(4, dtype=np.float32), 1000.0, 1000.0, 2)
-    ref, _, _ = orc.create_from_depth(d, K, stride=2)
-    _close(pc.points.cpu(), ref)
-    assert not pc.has_normals()
-    col = np.random.default_rng(1).integers(0, 256, (480, 640, 3), dtype=np.uint8)
-    pc = geometry.PointCloud.create_from_rgbd_image(geometry.RGBDImage(col, torch.from_numpy(d)), intr,
-                                                    compute_normals=True, depth_cutoff=3.5)
-    rp, rn, rc = orc.create_from_depth(d, K, color=col, rgbd=True, compute_normals=True, depth_cutoff=3.5)
-    _close(pc.points.cpu(), rp)
-    _close(pc.colors.cpu(), rc, 1e-7)
+    d, K4 = dx.scene(70, 50, 21), dx.intrinsic_of(70, 50)
+    intr = camera.PinholeCameraIntrinsic(70, 50, *[float(v) for v in K4])
+    E = dx.extrinsic_of("rigid")
+    pc = geometry.PointCloud.create_from_depth_image(geometry.Image(d), intr, E, 1000.0, 1000.0, 2)
+    held((pc.points, None, None), dx.cloud(d, K4, E, stride=2), 70)
+    assert not pc.has_normals() and not pc.has_colors() and len(pc.points) > 0
+    col = dx.colors_of("u8", 70, 50, 1)
+    pc = geometry.PointCloud.create_from_rgbd_image(geometry.RGBDImage(col, torch.from_numpy(d)), intr, E,
+                                                    compute_normals=True, depth_cutoff=dx.CUTOFF)
     assert pc.has_normals() and pc.has_colors()
+    held((pc.points, pc.normals, pc.colors),
+         dx.cloud(d, K4, E, color=col, rgbd=True, compute_normals=True, depth_cutoff=dx.CUTOFF), 70)
     bad = geometry.PointCloud.create_from_depth_image(np.zeros((4, 4, 3), np.uint8), intr)
     assert bad.is_empty()
+
+
+def test_kinfu_point_cloud_pyramid_exact():
+    """kinfu.point_cloud_pyramid on three levels (70x50, 35x25, 17x12): each level is CreateFromRGBDImage with that
+    level's intrinsic, the identity, the option's cutoff, normals, valid points only"""
+    from cupoch_amd import camera, kinfu
+    K4 = dx.intrinsic_of(70, 50)
+    intr = camera.PinholeCameraIntrinsic(70, 50, *[float(v) for v in K4])
+    sizes = [(70, 50), (35, 25), (17, 12)]
+    depth = [dx.scene(w, h, 31 + i) for i, (w, h) in enumerate(sizes)]
+    color = [dx.colors_of("f32", w, h, 41 + i) for i, (w, h) in enumerate(sizes)]
+    opt = kinfu.KinfuOption(num_pyramid_levels=3, depth_cutoff=dx.CUTOFF)
+    for cols in (color, None):
+        clouds = kinfu.point_cloud_pyramid(depth, intr, opt, cols)
+        assert len(clouds) == 3
+        for i, (w, h) in enumerate(sizes):
+            lv = intr.create_pyramid_level(i)
+            assert (lv.width, lv.height) == (w, h)
+            want = dx.cloud(depth[i], np.float32(lv.as4()), np.eye(4, dtype=np.float32), color=(cols[i] if cols else None),
+                            rgbd=True, depth_cutoff=dx.CUTOFF, compute_normals=True)
+            pc = clouds[i]
+            assert pc.has_normals() and pc.has_colors() == (cols is not None) and 0 < len(want[0]) < w * h
+            held((pc.points, pc.normals, pc.colors if cols else None), want, w)
 
 
 def _pyramids(levels, pose_b, scale):

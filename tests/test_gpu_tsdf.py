@@ -141,6 +141,45 @@ def test_integrate_extract_raycast_bit_equal(res, image, origin, kind, color_typ
     assert len(vol.extract_point_cloud().points) == 0 and len(vol.extract_voxel_point_cloud().points) == 0
 
 
+Z_CHUNK = 256      # tsdf_integrate walks a z-column in chunks of 256 voxels (one block each, four waves of 64)
+TALL_CASES = [     # resolution, origin, extrinsic, frames -> (voxels updated at z >= 256 per frame, columns they lie in)
+    ((257, (0.0, 0.0, -0.5), "rotated", 1), ([45350], 45350)),           # the second chunk is the single layer z = 256
+    ((257, (0.0, 0.0, -0.5), "inside", 1), ([15442], 15442)),
+    ((300, (0.13, -0.07, -0.4), "inside", 2), ([783443, 791964], 27774)),  # its only wave is partial: z 256..299
+    ((320, (0.0, 0.0, 0.0), "inside", 1), ([513557], 30168)),            # a full second wave
+]
+
+
+@pytest.mark.parametrize("case,counts", TALL_CASES, ids=["%d-%s" % (c[0], c[2]) for c, _ in TALL_CASES])
+def test_resolutions_above_one_z_chunk_bit_equal(case, counts):
+    """Resolutions above 256 (KinfuOption's default is 512): the second z-chunk's block index, its waves' span test and
+    its partial last wave.  RGB8, the 64x48 image; every voxel after every frame, then both extractions and the
+    raycasts.  From the restatement alone: voxels at z >= 256 are updated (the counts were worked out with
+    tests/tsdf_exact.py) and some columns have none there, so neither a chunk that never runs nor a span test that
+    lets everything through or nothing could pass."""
+    from cupoch_amd import geometry
+    res, origin, kind, frames = case
+    ref = tx.Volume(LENGTH, res, TRUNC, tx.RGB8, origin)
+    vol = gpu_volume(res, tx.RGB8, origin)
+    w, h, fx, fy, cx, cy = IMAGES["64x48"]
+    K = intrinsic_of("64x48")
+    high, touched = [], np.zeros((res, res), bool)
+    for k in range(frames):
+        d, c, E = frame("64x48", kind, k, tx.RGB8)
+        before = ref.grid(ref.weight)[:, :, Z_CHUNK:].copy()
+        tx.integrate(ref, d, c, w, h, fx, fy, cx, cy, E)
+        upd = ref.grid(ref.weight)[:, :, Z_CHUNK:] != before              # (every update adds 1 to the weight)
+        high.append(int(upd.sum()))
+        touched |= upd.any(2)
+        assert vol.integrate(geometry.RGBDImage(c, d), K, E)
+        check_voxels(vol, ref)
+    print("res %d %s: voxels updated at z >= 256 per frame %s, in %d of %d columns" % (res, kind, high, int(touched.sum()), res * res))
+    assert min(high) > 0 and 0 < int(touched.sum()) < res * res
+    assert (high, int(touched.sum())) == counts
+    nv, npnt, hits = check_clouds(vol, ref, "64x48", E, (TRUNC, 2 * TRUNC))
+    assert nv > 0 and npnt > 0 and hits > 0
+
+
 def scene_volume(res=64, color_type=tx.RGB8, origin=(0.0, 0.0, 0.0), kinds=("rotated", "identity")):
     from cupoch_amd import geometry
     ref, vol = tx.Volume(LENGTH, res, TRUNC, color_type, origin), gpu_volume(res, color_type, origin)
