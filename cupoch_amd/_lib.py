@@ -18,7 +18,7 @@ INCLUDE = os.path.join(ROOT, "include")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I/opt/rocm/include"]
 # the library's translation units (csrc/ctx.h says what each holds); compiled side by side, then linked
-UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_stsdf", "mi_occgrid", "mi_voxelgrid", "mi_collision", "mi_graph", "mi_laserscan", "mi_image", "mi_sgm", "mi_edt", "mi_knn", "mi_comm", "mi_debug"]
+UNITS = ["mi_icp", "mi_build", "mi_geometry", "mi_voxel", "mi_rgbd", "mi_tsdf", "mi_stsdf", "mi_occgrid", "mi_voxelgrid", "mi_collision", "mi_graph", "mi_laserscan", "mi_image", "mi_sgm", "mi_feature", "mi_edt", "mi_knn", "mi_comm", "mi_debug"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 MI_ICP_HOST, MI_ICP_DEVICE = 0, 1
@@ -146,6 +146,12 @@ class CollisionSide(C.Structure):                      # mi_icp_collision_side
                 ("grid_params", OccGridParams), ("points", C.c_void_p), ("n_points", C.c_int64),
                 ("lines", C.c_void_p), ("n_lines", C.c_int64), ("primitives", C.c_void_p),
                 ("n_primitives", C.c_int64)]
+
+
+class FgrOption(C.Structure):                          # mi_icp_fgr_option (the reference's seven defaults)
+    _fields_ = [("division_factor", C.c_float), ("use_absolute_scale", C.c_int32), ("decrease_mu", C.c_int32),
+                ("maximum_correspondence_distance", C.c_float), ("iteration_number", C.c_int32),
+                ("tuple_scale", C.c_float), ("maximum_tuple_count", C.c_int32)]
 
 
 COLLISION_VOXELGRID, COLLISION_OCCGRID, COLLISION_LINESET, COLLISION_PRIMITIVES = 1, 2, 3, 4
@@ -282,6 +288,11 @@ SIGNATURES = {
     "mi_icp_sgm_get_sums": (_I, [_P, _P, _P]),
     "mi_icp_sgm_limits": (_I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mi_icp_create_from_disparity": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "mi_icp_feature_match": (_I, [_P, _P, _L, _P, _L, _I, _P, _P, _P, _P]),
+    "mi_icp_fgr_correspondences": (_I, [_P, _P, _L, _P, _L, _P, _P, _F, _L, C.c_uint64, _P, C.POINTER(_L), _P, C.POINTER(_L)]),
+    "mi_icp_fgr_optimize": (_I, [_P, _P, _L, _P, _L, _P, _L, _F, C.POINTER(FgrOption), _P, _P, _P]),
+    "mi_icp_correspondences_from_features": (_I, [_P, _P, _L, _P, _L, _I, _I, _F, _P, C.POINTER(_L)]),
+    "mi_icp_fast_global_registration": (_I, [_P, _P, _P, _L, _P, _P, _L, _I, C.POINTER(FgrOption), C.c_uint64, C.POINTER(Result)]),
     "mi_icp_covariances_from_normals": (_I, [_P, _P, _L, _F, _P, _I]),
     "mi_icp_estimate_normals_knn": (_I, [_P, _P, _L, _I, _P, _I]),
     "mi_icp_estimate_normals_radius": (_I, [_P, _P, _L, _F, _I, _P, _I]),

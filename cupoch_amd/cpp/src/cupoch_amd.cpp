@@ -855,11 +855,76 @@ Eigen::Matrix4f_u Kabsch(const utility::device_vector<Eigen::Vector3f>& model,
     return ComputeWith(MI_ICP_EST_POINT_TO_POINT, -1.0f, s, t, corres);
 }
 
+// registration::CorrespondencesFromFeatures / FastGlobalRegistration (include/mi_icp.h "feature matching and
+// FastGlobalRegistration"); a Feature's data_ is [Num()][Dim] floats, the layout the C ABI takes
+template <int Dim>
+CorrespondenceSet CorrespondencesFromFeatures(const Feature<Dim>& source_features, const Feature<Dim>& target_features,
+                                              bool mutual_filter, float mutual_consistency_ratio) {
+    CorrespondenceSet out;
+    if (source_features.IsEmpty() || target_features.IsEmpty()) return out;
+    out.resize(source_features.Num());
+    int64_t m = 0;
+    Check(mi_icp_correspondences_from_features(Engine(), source_features.data_.data()->data(), (int64_t)source_features.Num(),
+                                               target_features.data_.data()->data(), (int64_t)target_features.Num(), Dim,
+                                               mutual_filter ? 1 : 0, mutual_consistency_ratio, out.data()->data(), &m));
+    out.resize((size_t)m);
+    return out;
+}
+
+template <int Dim>
+RegistrationResult FastGlobalRegistration(const geometry::PointCloud& source, const geometry::PointCloud& target,
+                                          const Feature<Dim>& source_feature, const Feature<Dim>& target_feature,
+                                          const FastGlobalRegistrationOption& option, uint64_t seed) {
+    if (!source.HasPoints() || !target.HasPoints() || source_feature.IsEmpty() || target_feature.IsEmpty()) {
+        LogError("Invalid source or target pointcloud.");  // fast_global_registration.cu:401-405
+        return RegistrationResult();
+    }
+    if (source_feature.Num() != source.points_.size() || target_feature.Num() != target.points_.size())
+        throw std::runtime_error("FastGlobalRegistration: one descriptor per point is needed");
+    const mi_icp_fgr_option o = {option.division_factor_, option.use_absolute_scale_ ? 1 : 0, option.decrease_mu_ ? 1 : 0,
+                                 option.maximum_correspondence_distance_, option.iteration_number_, option.tuple_scale_,
+                                 option.maximum_tuple_count_};
+    ++g_load_generation;  // (the call loads both clouds for its EvaluateRegistration)
+    mi_icp_result r;
+    Check(mi_icp_fast_global_registration(Engine(), Ptr(source.points_), source_feature.data_.data()->data(),
+                                          (int64_t)source.points_.size(), Ptr(target.points_), target_feature.data_.data()->data(),
+                                          (int64_t)target.points_.size(), Dim, &o, seed, &r));
+    return MakeResult(r);
+}
+
+#define CUPOCH_AMD_FEATURE_DIM(Dim)                                                                                               \
+    template CorrespondenceSet CorrespondencesFromFeatures<Dim>(const Feature<Dim>&, const Feature<Dim>&, bool, float);           \
+    template RegistrationResult FastGlobalRegistration<Dim>(const geometry::PointCloud&, const geometry::PointCloud&,             \
+                                                            const Feature<Dim>&, const Feature<Dim>&,                             \
+                                                            const FastGlobalRegistrationOption&, uint64_t);
+CUPOCH_AMD_FEATURE_DIM(33)
+CUPOCH_AMD_FEATURE_DIM(352)
+#undef CUPOCH_AMD_FEATURE_DIM
+
 }  // namespace registration
 // ============================================================================
-// knn::KDTreeFlann (knn/kdtree_flann.h:43-124)
+// knn::BruteForceNN (knn/bruteforce_nn.h), knn::KDTreeFlann (knn/kdtree_flann.h:43-124)
 // ============================================================================
 namespace knn {
+
+template <int Dim>
+void BruteForceNN(const utility::device_vector<Eigen::Matrix<float, Dim, 1>>& ref,
+                  const utility::device_vector<Eigen::Matrix<float, Dim, 1>>& query, utility::device_vector<int>& indices,
+                  utility::device_vector<float>& distances) {
+    indices.resize(query.size());
+    distances.resize(query.size());
+    if (query.empty()) return;
+    if (ref.empty()) throw std::runtime_error("BruteForceNN: no reference rows");
+    Check(mi_icp_feature_match(Engine(), query.data()->data(), (int64_t)query.size(), ref.data()->data(), (int64_t)ref.size(), Dim,
+                               indices.data(), distances.data(), nullptr, nullptr));
+    Check(mi_icp_synchronize(Engine()));
+}
+template void BruteForceNN<33>(const utility::device_vector<Eigen::Matrix<float, 33, 1>>&,
+                               const utility::device_vector<Eigen::Matrix<float, 33, 1>>&, utility::device_vector<int>&,
+                               utility::device_vector<float>&);
+template void BruteForceNN<352>(const utility::device_vector<Eigen::Matrix<float, 352, 1>>&,
+                                const utility::device_vector<Eigen::Matrix<float, 352, 1>>&, utility::device_vector<int>&,
+                                utility::device_vector<float>&);
 
 static void CheckCtx(mi_icp_ctx* c, int rc) {
     if (rc < 0) throw std::runtime_error(std::string("mi_icp: ") + mi_icp_last_error(c));

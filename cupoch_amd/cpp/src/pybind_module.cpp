@@ -46,6 +46,8 @@
 #include "cupoch/knn/kdtree_flann.h"
 #include "cupoch/knn/kdtree_search_param.h"
 #include "cupoch/planning/planner.h"
+#include "cupoch/registration/fast_global_registration.h"
+#include "cupoch/registration/feature.h"
 #include "cupoch/registration/generalized_icp.h"
 #include "cupoch/registration/registration.h"
 #include "cupoch/registration/transformation_estimation.h"
@@ -261,6 +263,40 @@ py::array_t<int> corres_to_array(const registration::CorrespondenceSet& c) {
     py::array_t<int> a({(py::ssize_t)h.size(), (py::ssize_t)2});
     if (!h.empty()) std::memcpy(a.mutable_data(), (const void*)h.data(), h.size() * sizeof(Eigen::Vector2i));
     return a;
+}
+
+// registration::Feature<Dim> (cupoch_pybind/registration/feature.cpp: FeatureFPFH, FeatureSHOT): `data` is an (n, Dim)
+// float32 array, copied from / to the device on access
+template <int Dim>
+void bind_feature(py::module& mr, const char* name, const char* doc) {
+    using F = registration::Feature<Dim>;
+    py::class_<F, std::shared_ptr<F>>(mr, name, doc)
+            .def(py::init<>())
+            .def(py::init<const F&>())
+            .def("__copy__", [](const F& f) { return F(f); })
+            .def("__deepcopy__", [](const F& f, py::dict&) { return F(f); })
+            .def("resize", &F::Resize, py::arg("n"))
+            .def("dimension", &F::Dimension)
+            .def("num", &F::Num)
+            .def("is_empty", &F::IsEmpty)
+            .def_property(
+                    "data",
+                    [](const F& f) {
+                        const auto h = f.GetData();
+                        py::array_t<float> a({(py::ssize_t)h.size(), (py::ssize_t)Dim});
+                        if (!h.empty()) std::memcpy(a.mutable_data(), (const void*)h.data(), h.size() * sizeof(typename F::FeatureType));
+                        return a;
+                    },
+                    [](F& f, const py::array_t<float, py::array::c_style | py::array::forcecast>& a) {
+                        if (a.ndim() != 2 || a.shape(1) != Dim) throw py::value_error("Feature data must be (n, " + std::to_string(Dim) + ")");
+                        std::vector<typename F::FeatureType> h((size_t)a.shape(0));
+                        if (!h.empty()) std::memcpy((void*)h.data(), a.data(), h.size() * sizeof(typename F::FeatureType));
+                        f.SetData(h);
+                    })
+            .def("__repr__", [](const F& f) {
+                return "registration::Feature class with dimension = " + std::to_string(f.Dimension()) + " and num = " +
+                       std::to_string(f.Num()) + "\nAccess its data via data member.";
+            });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1594,6 +1630,49 @@ PYBIND11_MODULE(cupoch_pybind, m) {
             },
             "source"_a, "target"_a, "max_distance"_a, "init"_a = identity4(),
             "criteria"_a = registration::ICPConvergenceCriteria(), "lambda_geometric"_a = 0.968f, "det_thresh"_a = 1e-6f);
+
+    // FeatureFPFH / FeatureSHOT, FastGlobalRegistrationOption, registration_fast_based_on_feature_matching (both
+    // overloads) and correspondences_from_features.  Not bound, as not built: compute_fpfh_feature, compute_shot_feature.
+    bind_feature<33>(mr, "FeatureFPFH", "Class to store FPFH features for registration.");
+    bind_feature<352>(mr, "FeatureSHOT", "Class to store SHOT features for registration.");
+    using FgrOption = registration::FastGlobalRegistrationOption;
+    py::class_<FgrOption>(mr, "FastGlobalRegistrationOption", "Options for FastGlobalRegistration.")
+            .def(py::init<float, bool, bool, float, int, float, int>(), "division_factor"_a = 1.4f, "use_absolute_scale"_a = false,
+                 "decrease_mu"_a = true, "maximum_correspondence_distance"_a = 0.025f, "iteration_number"_a = 64,
+                 "tuple_scale"_a = 0.95f, "maximum_tuple_count"_a = 1000)
+            .def(py::init<const FgrOption&>())
+            .def("__copy__", [](const FgrOption& o) { return FgrOption(o); })
+            .def("__deepcopy__", [](const FgrOption& o, py::dict&) { return FgrOption(o); })
+            .def_readwrite("division_factor", &FgrOption::division_factor_)
+            .def_readwrite("use_absolute_scale", &FgrOption::use_absolute_scale_)
+            .def_readwrite("decrease_mu", &FgrOption::decrease_mu_)
+            .def_readwrite("maximum_correspondence_distance", &FgrOption::maximum_correspondence_distance_)
+            .def_readwrite("iteration_number", &FgrOption::iteration_number_)
+            .def_readwrite("tuple_scale", &FgrOption::tuple_scale_)
+            .def_readwrite("maximum_tuple_count", &FgrOption::maximum_tuple_count_)
+            .def("__repr__", [](const FgrOption& o) {
+                return "registration::FastGlobalRegistrationOption class with \ndivision_factor=" + std::to_string(o.division_factor_) +
+                       "\nuse_absolute_scale=" + std::to_string(o.use_absolute_scale_) + "\ndecrease_mu=" + std::to_string(o.decrease_mu_) +
+                       "\nmaximum_correspondence_distance=" + std::to_string(o.maximum_correspondence_distance_) +
+                       "\niteration_number=" + std::to_string(o.iteration_number_) + "\ntuple_scale=" + std::to_string(o.tuple_scale_) +
+                       "\nmaximum_tuple_count=" + std::to_string(o.maximum_tuple_count_);
+            });
+    mr.def("registration_fast_based_on_feature_matching", &registration::FastGlobalRegistration<33>, "source"_a, "target"_a,
+           "source_feature"_a, "target_feature"_a, "option"_a = FgrOption(), "seed"_a = (uint64_t)0);
+    mr.def("registration_fast_based_on_feature_matching", &registration::FastGlobalRegistration<352>, "source"_a, "target"_a,
+           "source_feature"_a, "target_feature"_a, "option"_a = FgrOption(), "seed"_a = (uint64_t)0);
+    mr.def(
+            "correspondences_from_features",
+            [](const registration::Feature<33>& s, const registration::Feature<33>& t, bool mutual_filter, float ratio) {
+                return corres_to_array(registration::CorrespondencesFromFeatures<33>(s, t, mutual_filter, ratio));
+            },
+            "source_features"_a, "target_features"_a, "mutual_filter"_a = false, "mutual_consistency_ratio"_a = 0.1f);
+    mr.def(
+            "correspondences_from_features",
+            [](const registration::Feature<352>& s, const registration::Feature<352>& t, bool mutual_filter, float ratio) {
+                return corres_to_array(registration::CorrespondencesFromFeatures<352>(s, t, mutual_filter, ratio));
+            },
+            "source_features"_a, "target_features"_a, "mutual_filter"_a = false, "mutual_consistency_ratio"_a = 0.1f);
 
     // ---------------------------------------------------------------- kinfu (cupoch_pybind/kinfu/kinfu.cpp)
     // The reference's names.  Not bound, as not built: extract_triangle_mesh; the pipeline has no copy functions

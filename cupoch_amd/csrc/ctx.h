@@ -16,6 +16,7 @@
 //   mi_laserscan.hip geometry::LaserScanBuffer (scans to points, points / depth frames to scans, the two filters)
 //   mi_image.hip     geometry::Image / RGBDImage processing (filters, the pyramid level, bilateral, conversions, moves)
 //   mi_sgm.hip       imageproc::SemiGlobalMatching, PointCloud::CreateFromDisparity
+//   mi_feature.hip   registration::Feature matching, CorrespondencesFromFeatures, FastGlobalRegistration
 //   mi_knn.hip       EstimateNormals, KDTreeFlann::SearchKNN / SearchRadius, colour gradients, Colored ICP's entry,
 //                    RemoveStatisticalOutliers / RemoveRadiusOutliers, ClusterDBSCAN, ComputeISSKeypoints
 //   mi_comm.hip      the ranks' exchange: mailbox, device inboxes, in-library RCCL, self-test and choice
@@ -121,6 +122,7 @@ struct mi_icp_ctx {
     mi::eng::DevBuf knn_idx, knn_flags;  // the k-NN lists' index rows, [XCD][row][slot][lane], and the rows' claim flags (knn_normals.h KnnSlab)
     mi::eng::DevBuf dbs[4];   // ClusterDBSCAN (dbscan.h): the rows, the per-point words, the one-way masks, the state
     mi::eng::DevBuf seg[4];   // SegmentPlane (segment_plane.h): the planes, the per-hypothesis words and the state, the tie sums, the refit's sums
+    mi::eng::DevBuf fgr[8];   // Feature matching and FastGlobalRegistration (mi_feature.hip says what each holds)
     float vx_refused_voxel = 0.0f;  // the last voxel size / cloud size the dense path's plan turned away (mi_icp_voxel_downsample)
     int64_t vx_refused_n = 0;
     int vx_order = 0;         // LDS adds of one instruction served in lane order (voxel_dense.h)?  0: not checked yet, 1: yes, -1: no

@@ -14,6 +14,7 @@
 // The number of launches does not depend on the iteration count, and nothing comes back to the host before the end.
 #pragma once
 #include "device_utils.h"
+#include "fgr_rules.h"
 
 namespace mi {
 
@@ -35,12 +36,7 @@ struct SegState {
 };
 
 // ---- the sampler (include/mi_icp.h): u(j) = output j of splitmix64 seeded with `seed` -------------------------------
-__host__ __device__ inline uint64_t seg_u(uint64_t seed, uint64_t j) {
-    uint64_t z = seed + (j + 1ull) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+__host__ __device__ inline uint64_t seg_u(uint64_t seed, uint64_t j) { return fgr::stream_u(seed, j); }  // (fgr_rules.h)
 
 __device__ __forceinline__ uint64_t seg_below(uint64_t u, uint64_t m) { return __umul64hi(u, m); }  // floor(u * m / 2^64)
 

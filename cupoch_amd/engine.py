@@ -1548,6 +1548,95 @@ class Engine:
                                                        q.ctypes.data_as(C.c_void_p), self._ptr(pts), self._ptr(col)))
         return pts, col
 
+    # -- feature matching and FastGlobalRegistration (include/mi_icp.h; every array becomes a device tensor) ----------
+    @staticmethod
+    def fgr_option(division_factor=1.4, use_absolute_scale=False, decrease_mu=True, maximum_correspondence_distance=0.025,
+                   iteration_number=64, tuple_scale=0.95, maximum_tuple_count=1000):
+        return _lib.FgrOption(float(division_factor), int(bool(use_absolute_scale)), int(bool(decrease_mu)),
+                              float(maximum_correspondence_distance), int(iteration_number), float(tuple_scale),
+                              int(maximum_tuple_count))
+
+    def _features(self, a, what):
+        if not _is_tensor(a):
+            a = np.asarray(a, np.float32)
+        if a.ndim != 2:
+            raise TypeError("%s takes features as [n, dim]" % what)
+        dim = int(a.shape[1])
+        return self._vg_dev(a, np.float32, max(dim, 1)), int(a.shape[0]), dim
+
+    def feature_match(self, query, ref):
+        """mi_icp_feature_match -> (q_idx int32 [nq], q_d [nq], r_idx int32 [nr], r_d [nr]) device tensors"""
+        q, nq, dim = self._features(query, "feature_match")
+        r, nr, rdim = self._features(ref, "feature_match")
+        if dim != rdim:
+            raise MiIcpError("feature_match: dimensions %d and %d differ" % (dim, rdim))
+        dev = torch.device("cuda", self.device)
+        (qi, qip), (qd, qdp) = self._out(MI_ICP_DEVICE, dev, (nq,), np.int32), self._out(MI_ICP_DEVICE, dev, (nq,))
+        (ri, rip), (rd, rdp) = self._out(MI_ICP_DEVICE, dev, (nr,), np.int32), self._out(MI_ICP_DEVICE, dev, (nr,))
+        self._chk(self._L.mi_icp_feature_match(self._ctx, self._ptr(q), nq, self._ptr(r), nr, dim, qip, qdp, rip, rdp))
+        self.synchronize()   # (uploaded inputs may go)
+        return qi, qd, ri, rd
+
+    def fgr_correspondences(self, s_idx, t_idx, source, target, tuple_scale=0.95, maximum_tuple_count=1000, seed=0):
+        """mi_icp_fgr_correspondences -> (pairs int32 [ncorr, 2], corr int32 [m, 2]) device tensors"""
+        si, ti = self._vg_dev(s_idx, np.int32, 1), self._vg_dev(t_idx, np.int32, 1)
+        p, q = self._vg_dev(source, np.float32), self._vg_dev(target, np.float32)
+        ns, nt = int(p.shape[0]), int(q.shape[0])
+        if int(si.shape[0]) != ns or int(ti.shape[0]) != nt:
+            raise MiIcpError("fgr_correspondences: one neighbour per point is needed")
+        dev = torch.device("cuda", self.device)
+        room = max(0, min(int(maximum_tuple_count), 300 * min(ns, nt)))
+        pairs, pp = self._out(MI_ICP_DEVICE, dev, (max(min(ns, nt), 1), 2), np.int32)
+        corr, cp = self._out(MI_ICP_DEVICE, dev, (max(room, 1), 2), np.int32)
+        n_pairs, n_corr = C.c_int64(0), C.c_int64(0)
+        self._chk(self._L.mi_icp_fgr_correspondences(self._ctx, self._ptr(si), ns, self._ptr(ti), nt, self._ptr(p), self._ptr(q),
+                                                     float(tuple_scale), int(maximum_tuple_count), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                     pp, C.byref(n_pairs), cp, C.byref(n_corr)))
+        return pairs[:int(n_pairs.value)], corr[:int(n_corr.value)]
+
+    def fgr_optimize(self, source, target, corr, par_start, option=None):
+        """mi_icp_fgr_optimize -> (T [4, 4] row-major numpy, the last iteration's 27 sums (float64), par after it)"""
+        p, q = self._vg_dev(source, np.float32), self._vg_dev(target, np.float32)
+        cr = self._vg_dev(corr, np.int32, 2)
+        opt = self.fgr_option() if option is None else option
+        dev = torch.device("cuda", self.device)
+        T = torch.empty(16, dtype=torch.float32, device=dev)
+        sums = torch.empty(27, dtype=torch.float64, device=dev)
+        par = torch.empty(1, dtype=torch.float32, device=dev)
+        self._chk(self._L.mi_icp_fgr_optimize(self._ctx, self._ptr(p), int(p.shape[0]), self._ptr(q), int(q.shape[0]), self._ptr(cr),
+                                              int(cr.shape[0]), float(par_start), C.byref(opt), self._ptr(T), self._ptr(sums),
+                                              self._ptr(par)))
+        self.synchronize()
+        return _T_out(T.cpu().numpy()), sums.cpu().numpy(), float(par.cpu()[0])
+
+    def correspondences_from_features(self, source_features, target_features, mutual_filter=False, mutual_consistency_ratio=0.1):
+        """mi_icp_correspondences_from_features -> int32 [m, 2] device tensor"""
+        s, ns, dim = self._features(source_features, "correspondences_from_features")
+        t, nt, tdim = self._features(target_features, "correspondences_from_features")
+        if dim != tdim:
+            raise MiIcpError("correspondences_from_features: dimensions %d and %d differ" % (dim, tdim))
+        corr, cp = self._out(MI_ICP_DEVICE, torch.device("cuda", self.device), (max(ns, 1), 2), np.int32)
+        m = C.c_int64(0)
+        self._chk(self._L.mi_icp_correspondences_from_features(self._ctx, self._ptr(s), ns, self._ptr(t), nt, dim, int(bool(mutual_filter)),
+                                                               float(mutual_consistency_ratio), cp, C.byref(m)))
+        return corr[:int(m.value)]
+
+    def fast_global_registration(self, source, target, source_features, target_features, option=None, seed=0):
+        """mi_icp_fast_global_registration -> Result; the clouds stay loaded, get_correspondences() gives the set"""
+        p, q = self._vg_dev(source, np.float32), self._vg_dev(target, np.float32)
+        s, ns, dim = self._features(source_features, "fast_global_registration")
+        t, nt, tdim = self._features(target_features, "fast_global_registration")
+        if dim != tdim or ns != int(p.shape[0]) or nt != int(q.shape[0]):
+            raise MiIcpError("fast_global_registration: one descriptor of one dimension per point is needed")
+        opt = self.fgr_option() if option is None else option
+        self.generation = getattr(self, "generation", 0) + 1   # (the call loads both clouds)
+        res = Result()
+        self._chk(self._L.mi_icp_fast_global_registration(self._ctx, self._ptr(p), self._ptr(s), ns, self._ptr(q), self._ptr(t), nt, dim,
+                                                          C.byref(opt), C.c_uint64(int(seed) & (2 ** 64 - 1)), C.byref(res)))
+        self.synchronize()
+        self.n_source, self.n_target = ns, nt
+        return res
+
     def compute_rgbd_odometry(self, source_color, source_depth, target_color, target_depth, intrinsic4,
                               odo_init=None, jacobian=1, iterations=(20, 10, 5), max_depth_diff=0.03,
                               min_depth=0.0, max_depth=4.0, weighted=False, prev_twist=None, nu=5.0,

@@ -258,3 +258,112 @@ def registration_generalized_icp(source, target, max_correspondence_distance, in
     return registration_icp(_initialize_for_gicp(source, est.epsilon),
                             _initialize_for_gicp(target, est.epsilon),
                             max_correspondence_distance, init, est, criteria)
+
+
+class Feature:
+    """registration::Feature<Dim> (registration/feature.h): one descriptor of `dim` floats per point, held as [n, dim]
+    float32 -- a numpy array or a CUDA tensor, as it was given.  The reference instantiates 33 (FeatureFPFH) and 352
+    (FeatureSHOT); any dimension up to 512 works here (learned descriptors)."""
+
+    def __init__(self, dim=33, data=None):
+        self._dim = int(dim)
+        self._data = np.zeros((0, self._dim), np.float32)
+        if data is not None:
+            self.data = data
+
+    def resize(self, n):
+        self._data = np.zeros((int(n), self._dim), np.float32)
+
+    def dimension(self):
+        return self._dim
+
+    def num(self):
+        return int(self._data.shape[0])
+
+    def is_empty(self):
+        return self.num() == 0
+
+    @property
+    def data(self):
+        return self._data
+
+    @data.setter
+    def data(self, v):
+        if not hasattr(v, "is_cuda"):
+            v = np.ascontiguousarray(np.asarray(v, np.float32))
+        if v.ndim != 2 or int(v.shape[1]) != self._dim:
+            raise ValueError("Feature data must be [n, %d]" % self._dim)
+        self._data = v
+
+    def __copy__(self):
+        return type(self)(self._dim, self._data.clone() if hasattr(self._data, "clone") else self._data.copy())
+
+    def __deepcopy__(self, memo):
+        return self.__copy__()
+
+    def __repr__(self):
+        return ("registration::Feature class with dimension = {:d} and num = {:d}\n"
+                "Access its data via data member.").format(self._dim, self.num())
+
+
+class FeatureFPFH(Feature):
+    def __init__(self, dim=33, data=None):
+        super().__init__(33, data)
+
+
+class FeatureSHOT(Feature):
+    def __init__(self, dim=352, data=None):
+        super().__init__(352, data)
+
+
+class FastGlobalRegistrationOption:
+    # registration/fast_global_registration.h: the struct's own defaults
+    def __init__(self, division_factor=1.4, use_absolute_scale=False, decrease_mu=True,
+                 maximum_correspondence_distance=0.025, iteration_number=64, tuple_scale=0.95,
+                 maximum_tuple_count=1000):
+        self.division_factor = float(division_factor)
+        self.use_absolute_scale = bool(use_absolute_scale)
+        self.decrease_mu = bool(decrease_mu)
+        self.maximum_correspondence_distance = float(maximum_correspondence_distance)
+        self.iteration_number = int(iteration_number)
+        self.tuple_scale = float(tuple_scale)
+        self.maximum_tuple_count = int(maximum_tuple_count)
+
+    def _c(self):
+        from .engine import Engine
+        return Engine.fgr_option(self.division_factor, self.use_absolute_scale, self.decrease_mu,
+                                 self.maximum_correspondence_distance, self.iteration_number, self.tuple_scale,
+                                 self.maximum_tuple_count)
+
+    def __repr__(self):
+        return ("registration::FastGlobalRegistrationOption class with \ndivision_factor={}\nuse_absolute_scale={}"
+                "\ndecrease_mu={}\nmaximum_correspondence_distance={}\niteration_number={}\ntuple_scale={}"
+                "\nmaximum_tuple_count={}").format(self.division_factor, self.use_absolute_scale, self.decrease_mu,
+                                                    self.maximum_correspondence_distance, self.iteration_number,
+                                                    self.tuple_scale, self.maximum_tuple_count)
+
+
+def registration_fast_based_on_feature_matching(source, target, source_feature, target_feature, option=None, seed=0):
+    """registration::FastGlobalRegistration<Dim> (fast_global_registration.cu:393-432).  `seed` feeds the tuple draw
+    (the reference's engine is default-seeded): the same input and seed give the same result, byte for byte."""
+    if (not source.has_points() or not target.has_points() or source_feature.is_empty()
+            or target_feature.is_empty()):
+        print("[cupoch_amd] Error: Invalid source or target pointcloud.")
+        return RegistrationResult()
+    opt = FastGlobalRegistrationOption() if option is None else option
+    eng = get_engine()
+    res = eng.fast_global_registration(source.points.tensor, target.points.tensor, source_feature.data,
+                                       target_feature.data, opt._c(), seed)
+    return _result_from(eng, res)
+
+
+def correspondences_from_features(source_features, target_features, mutual_filter=False,
+                                  mutual_consistency_ratio=0.1):
+    """registration::CorrespondencesFromFeatures (declared in feature.h; include/mi_icp.h holds its definition here):
+    row i = (i, nearest target feature), with mutual_filter only the rows whose neighbour points back, unless fewer
+    than mutual_consistency_ratio * n remain.  -> int32 [m, 2] numpy"""
+    if source_features.is_empty() or target_features.is_empty():
+        return np.zeros((0, 2), np.int32)
+    corr = get_engine().correspondences_from_features(source_features.data, target_features.data, mutual_filter,
+                                                      mutual_consistency_ratio)
+    return corr.cpu().numpy()

@@ -1641,6 +1641,107 @@ MI_ICP_API int mi_icp_create_from_disparity(mi_icp_ctx* ctx, const uint8_t* disp
                                             int height, int bytes_per_channel, const float* q, float* points,
                                             float* colors);
 
+/* ---- feature matching and FastGlobalRegistration (registration/feature.h, knn/bruteforce_nn.{h,inl},
+ * ---- registration/fast_global_registration.{h,cu}) ----
+ * Everything downstream of the descriptors: they come in as data, float[n][dim] row-major.  Every array below is in
+ * DEVICE memory (no mem_kind: a surface stages host arrays itself); counts and the option are host values.  The calls
+ * run in the private scratch context: the caller's target / source / loop state survive, except that
+ * mi_icp_fast_global_registration ends with EvaluateRegistration on the caller's context and loads both clouds there.
+ * tests/fgr_exact.py restates all of it in numpy; csrc/fgr_rules.h holds the sampler, the tuple test and the par
+ * schedule for host and device alike.
+ *  mi_icp_feature_match  (knn::BruteForceNN in both directions at once) features q[nq][dim], r[nr][dim]:
+ *   distance  D(i, j): acc = 0; for k = 0 .. dim - 1 in order: e = q[i][k] - r[j][k] (one fp32 rounding),
+ *             acc = fma(e, e, acc).  fp32 subtraction is sign-symmetric, so D is the same bits from either side; the
+ *             kernel computes every D once and both directions read that value.  (The difference form, not
+ *             |q|^2 + |r|^2 - 2 q.r, whose cancellation error is of the size of the distances between like descriptors.)
+ *   neighbour q_idx[i] = the j of smallest D(i, j), the smallest j among equals; q_d[i] = that D.  r_idx[j] / r_d[j]
+ *             likewise over i.  A NaN distance never wins; a row whose distances are all NaN gets -1 and a NaN.
+ *             Any of the four outputs may be NULL.
+ *   method    one pass over the pair space: 128 x 128 tiles staged through LDS, 8 x 8 pairs per lane, running minima
+ *             joined by 64-bit unsigned atomic minima on (bits of D) << 32 | index (D >= 0, so the bits order as the
+ *             values, the smallest index wins ties and the order of arrival cannot matter).  The nq x nr matrix is
+ *             never written: memory beyond the arguments is 8 (nq + nr) bytes.
+ *   limits    dim in [1, MI_ICP_FEATURE_MAX_DIM], nq, nr in [1, 2^31); else, or with q or r NULL, MI_ICP_ERR_INVALID
+ *             before any launch.  Does not wait for the stream.
+ *  mi_icp_fgr_correspondences  (AdvancedMatching behind its two searches) s_idx[ns]: every source point's neighbour
+ *   among the target's features, t_idx[nt] the reverse (mi_icp_feature_match's q_idx / r_idx); src_xyz, tgt_xyz the
+ *   points.
+ *   pairs     (i, j) with s_idx[i] = j in [0, nt) and t_idx[j] = i, ascending in i -> pairs (room for min(ns, nt) rows
+ *             of two int32), *n_pairs = ncorr.
+ *   trials    100 * ncorr of them.  Trial t takes the pairs numbered floor(u(3t + m) * ncorr / 2^64), m = 0, 1, 2, u(j)
+ *             = output j of the splitmix64 stream seeded with `seed` that mi_icp_segment_plane draws from.  With p0, p1,
+ *             p2 its source points and q0, q1, q2 the target points paired with them -- the caller's coordinates: the
+ *             test is invariant to the normalisation -- the squared sides are L(a, b) = (dx*dx + dy*dy) + dz*dz, d = a
+ *             - b, every operation one fp32 rounding, none fused; Li = L(p0,p1), L(p1,p2), L(p2,p0), Lj likewise; s2 =
+ *             tuple_scale * tuple_scale.  The trial PASSES iff for all three sides Li * s2 < Lj and Lj * s2 < Li.  No
+ *             square root, no division; a repeated pair fails by itself.
+ *   list      the passing trials' three correspondences (source index, target index), in trial order, cut to
+ *             maximum_tuple_count entries (1000: 333 triples and one more) -> corr (room for min(maximum_tuple_count,
+ *             300 * min(ns, nt)) rows), *n_corr.  Only the first ceil(max / 3) passing trials are written.
+ *   limits    ns, nt in [1, 0x7fffff00], 100 * ncorr <= 0x7fffff00, maximum_tuple_count >= 0; else MI_ICP_ERR_INVALID.
+ *             Integers throughout: the same bytes on every run and context.  Waits for the stream twice.
+ *  mi_icp_fgr_optimize  (OptimizePairwiseRegistration) points as given (normalised or not), corr[n_corr][2]:
+ *   fewer than 10 correspondences, or iteration_number = 0: T16 = identity, the sums zero, *par_out = par_start.  Else
+ *   q_c = tgt[j_c] for every correspondence c = (i_c, j_c), par = par_start, trans = I, and iteration_number times:
+ *   weight  r = p - q (p = src[i_c]), w = t * t, t = par / (((rx*rx + ry*ry) + rz*rz) + par): fp32, every operation
+ *           rounded, IEEE division;
+ *   sums    JTJ (21 upper-triangle entries, row-major) and JTr (6) of the rows (0, -qz, qy, -1, 0, 0 | rx), (qz, 0,
+ *           -qx, 0, -1, 0 | ry), (-qy, qx, 0, 0, 0, -1 | rz), each weighted by w: every term formed and added in fp64
+ *           from the fp32 p, q, r, w, in a fixed order (per thread, wave, then the four waves);
+ *   step    x solves (-JTJ) x = JTr in fp32 (the LDL^T of mi_icp_solve_system, no determinant check), delta =
+ *           mi_icp_vector6_to_matrix4(x), trans = delta * trans, q_c = ((d00 x + d01 y) + d02 z) + t0, ... in fp32,
+ *           nothing fused;
+ *   par     if decrease_mu and itr % 4 == 0 and par > maximum_correspondence_distance: par = par / division_factor.
+ *   T16 (column-major) = trans; sums27 (may be NULL) = the last iteration's 27 sums; par_out (may be NULL) = par
+ *   after the last iteration.  One workgroup runs all iterations: no host round trip, no wait.  A correspondence with
+ *   an index outside its cloud takes no part.  Same input, same bytes.
+ *  mi_icp_correspondences_from_features  (declared in feature.h, defined nowhere in the reference; this definition is
+ *   the library's) row i = (i, nn(i)) for every source row that has a neighbour, ascending; with mutual_filter only
+ *   the rows whose neighbour points back -- unless fewer than mutual_consistency_ratio * ns (one fp32 product) remain:
+ *   then the unfiltered list.  corr: room for ns rows.  Waits once, twice when it falls back.
+ *  mi_icp_fast_global_registration  the whole call:
+ *   1 match   mi_icp_feature_match(source features, target features), the reciprocal pairs, the cut tuple list;
+ *   2 normalise  per cloud mean = (float)(sum / n), the sums in fp64 in a fixed order; points centred in fp32; scale
+ *             = sqrt of the largest (x*x + y*y) + z*z over both centred clouds; scale_global = use_absolute_scale ? 1
+ *             : scale; points / scale_global (IEEE division);
+ *   3 optimise  mi_icp_fgr_optimize on the normalised clouds with par_start = scale_global (the reference hands
+ *             scale_global to the parameter its optimiser calls scale_start; kept, callers see its effect);
+ *   4 map back  (GetInvTransformationOriginalScale) R, t of trans; v = (-(R m_tgt) + t * scale_global) + m_src; T =
+ *             [R^T, -(R^T v)] in fp32, products summed left to right;
+ *   5 result  mi_icp_set_target(target), mi_icp_set_source(source) and mi_icp_evaluate_registration(
+ *             maximum_correspondence_distance, T) on the caller's context: *out is its result, and
+ *             mi_icp_get_correspondences gives its correspondence_set.
+ *   The number of waits and launches does not depend on iteration_number.  Same input and seed, same bytes.
+ * Deviations (deliberate): the pairs ascend in the source index (the reference orders them by the larger cloud's index
+ * after a swap; the order only feeds the random draw).  The random stream is not thrust::default_random_engine's: same
+ * distribution of triples, other triples.  The tuple test compares squared lengths by multiplication (the reference:
+ * norms and a division).  The sums are fp64 (the reference: fp32 in thrust's order). */
+#define MI_ICP_FEATURE_MAX_DIM 512
+typedef struct mi_icp_fgr_option {        /* registration::FastGlobalRegistrationOption and its defaults */
+    float division_factor;                /* 1.4 */
+    int32_t use_absolute_scale;           /* 0 */
+    int32_t decrease_mu;                  /* 1 */
+    float maximum_correspondence_distance;/* 0.025 */
+    int32_t iteration_number;             /* 64 */
+    float tuple_scale;                    /* 0.95 */
+    int32_t maximum_tuple_count;          /* 1000 */
+} mi_icp_fgr_option;
+MI_ICP_API int mi_icp_feature_match(mi_icp_ctx* ctx, const float* q, int64_t nq, const float* r, int64_t nr, int dim,
+                                    int32_t* q_idx, float* q_d, int32_t* r_idx, float* r_d);
+MI_ICP_API int mi_icp_fgr_correspondences(mi_icp_ctx* ctx, const int32_t* s_idx, int64_t ns, const int32_t* t_idx,
+                                          int64_t nt, const float* src_xyz, const float* tgt_xyz, float tuple_scale,
+                                          int64_t maximum_tuple_count, uint64_t seed, int32_t* pairs, int64_t* n_pairs,
+                                          int32_t* corr, int64_t* n_corr);
+MI_ICP_API int mi_icp_fgr_optimize(mi_icp_ctx* ctx, const float* src_xyz, int64_t ns, const float* tgt_xyz, int64_t nt,
+                                   const int32_t* corr, int64_t n_corr, float par_start,
+                                   const mi_icp_fgr_option* option, float* T16, double* sums27, float* par_out);
+MI_ICP_API int mi_icp_correspondences_from_features(mi_icp_ctx* ctx, const float* src_feat, int64_t ns,
+                                                    const float* tgt_feat, int64_t nt, int dim, int mutual_filter,
+                                                    float mutual_consistency_ratio, int32_t* corr, int64_t* n_corr);
+MI_ICP_API int mi_icp_fast_global_registration(mi_icp_ctx* ctx, const float* src_xyz, const float* src_feat, int64_t ns,
+                                               const float* tgt_xyz, const float* tgt_feat, int64_t nt, int dim,
+                                               const mi_icp_fgr_option* option, uint64_t seed, mi_icp_result* out);
+
 /* ---- knn::KDTreeFlann as a search object (knn/kdtree_flann.h:43-124) ---------
  * SearchKNN / SearchRadius (knn/kdtree_flann.inl:46-122) of arbitrary queries
  * float[nq][3] against the cloud given to mi_icp_set_target: per query the knn
