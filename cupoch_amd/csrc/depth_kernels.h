@@ -23,22 +23,30 @@ struct DepthArgs {
     const void* depth;   // [height][width] float32, or uint16 when depth_u16
     const void* color;   // null, [h][w][3] uint8, or [h][w] float32
     int width, height, stride;
-    int depth_u16;       // uint16 input: value / depth_scale, >= depth_trunc -> 0 (image.cu:339-348)
+    int depth_u16;       // uint16 input: depth_metres(value) (image.cu:339-348)
     int color_kind;      // 0 none, 1 uint8 x 3, 2 float32 x 1
     int rgbd;            // CreateFromRGBDImage's validity rule (depth_cutoff) instead of CreateFromDepthImage's
-    int depth_scale, depth_trunc;  // the reference holds both as int (image.cu:340-343)
+    float depth_recip;   // depth_reciprocal((int)depth_scale)
+    int depth_trunc;     // the reference holds scale and truncation as int (image.cu:340-343)
     float depth_cutoff;
     float fx, fy, cx, cy;
     float pose[16];      // camera pose = extrinsic^-1, column-major
 };
 
+// depth_to_float_functor (image.cu:339-348) as the reference is built: under fast math `f /= (float)depth_scale_` is a
+// multiplication by the reciprocal, and the reference's own vector (TEST(Image, ConvertDepthToFloatImage), scale 1000)
+// is reproduced byte for byte by the correctly rounded one, r = (float)(1.0 / (double)(float)(int)depth_scale).  For
+// other scales that r is this project's extrapolation (mi_icp.h "image").  The one rule of every depth entry.
+__host__ __device__ __forceinline__ float depth_reciprocal(int depth_scale) { return (float)(1.0 / (double)(float)depth_scale); }
+
+__device__ __forceinline__ float depth_metres(float f, float recip, float trunc) {
+    f = f * recip;
+    if (f >= trunc) f = 0.0f;
+    return f;
+}
+
 __device__ __forceinline__ float depth_value(const DepthArgs& a, int64_t pix) {
-    if (a.depth_u16) {
-        float f = (float)((const uint16_t*)a.depth)[pix];
-        f /= (float)a.depth_scale;
-        if (f >= (float)a.depth_trunc) f = 0.0f;
-        return f;
-    }
+    if (a.depth_u16) return depth_metres((float)((const uint16_t*)a.depth)[pix], a.depth_recip, (float)a.depth_trunc);
     return ((const float*)a.depth)[pix];
 }
 

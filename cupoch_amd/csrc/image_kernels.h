@@ -1,8 +1,10 @@
 // image_kernels.h -- geometry::Image / geometry::RGBDImage processing: separable filters, the fused pyramid level, the
 // bilateral filter, downsampling, the conversions between pixel formats, transpose and the flips (image.cu,
 // image_factory.cu, rgbdimage_factory.cu).  The contract is in include/mi_icp.h ("image"); tests/image_exact.py
-// restates it in numpy.  All arithmetic is fp32, unfused (the library is built with -ffp-contract=off), in the order
-// the contract writes it; csrc/odometry.h keeps its own od_filter3 / od_downsample, which compute the same words.
+// restates it in numpy.  All arithmetic is fp32 in the order the contract writes it, unfused (the library is built with
+// -ffp-contract=off) except where fmaf is written: the filter taps and the three-channel intensity, which the
+// reference's own byte vectors pin (tests/golden/reference_tests.json).  csrc/odometry.h keeps its own od_filter3 /
+// od_downsample, which compute the same words (Gaussian3 and the Sobel taps are powers of two: exact products).
 //
 // SEPARABLE FILTER (img_filter).  A workgroup of four waves writes a tile of 64 x 16 pixels: a wave's 64 lanes are 64
 // consecutive x (256-byte rows on both the global and the LDS side, one bank per lane).  It first puts the row sums
@@ -21,6 +23,7 @@
 // TRANSPOSE goes through a 32 x 32 LDS tile of pixels' bytes so that reads and writes are both along rows.
 // No kernel here keeps a per-lane array that is indexed at run time: there is no scratch.  Nothing needs an atomic.
 #pragma once
+#include "depth_kernels.h"
 #include "device_utils.h"
 
 namespace mi {
@@ -43,10 +46,11 @@ struct ImgTable {
 
 __device__ __forceinline__ int img_clamp(int v, int hi) { return min(max(0, v), hi); }
 
-// the horizontal sum of row `ys` at column x: t = 0; t = t + src[clamp(x + i)] * k[i + half], ascending i
+// the horizontal sum of row `ys` at column x: t = 0; t = fmaf(src[clamp(x + i)], k[i + half], t), ascending i: one
+// rounding per tap, as the reference's vectors pin it (Filter_Gaussian5, Filter_Gaussian7; mi_icp.h "image")
 __device__ __forceinline__ float img_row_sum(const float* __restrict__ row, int x, int w, const float* k, int half) {
     float t = 0.0f;
-    for (int i = -half; i <= half; ++i) t = t + row[img_clamp(x + i, w - 1)] * k[i + half];
+    for (int i = -half; i <= half; ++i) t = fmaf(row[img_clamp(x + i, w - 1)], k[i + half], t);
     return t;
 }
 
@@ -74,7 +78,7 @@ static __global__ __launch_bounds__(kImgThreads) void img_filter(const float* __
         const int y = y0 + r;
         if (x >= w || y >= h) continue;
         float out = 0.0f;
-        for (int j = 0; j <= 2 * hy; ++j) out = out + rows[(r + j) * kImgTileW + lane] * a.dy[j];
+        for (int j = 0; j <= 2 * hy; ++j) out = fmaf(rows[(r + j) * kImgTileW + lane], a.dy[j], out);
         dst[(int64_t)y * w + x] = out;
     }
 }
@@ -93,9 +97,9 @@ static __global__ __launch_bounds__(kImgThreads) void img_pyramid_level(const fl
         if (x < w) {
             const float* row = src + (int64_t)ys * w;
             float t = 0.0f;
-            t = t + row[img_clamp(x - 1, w - 1)] * g0;
-            t = t + row[x] * g1;
-            t = t + row[img_clamp(x + 1, w - 1)] * g2;
+            t = fmaf(row[img_clamp(x - 1, w - 1)], g0, t);
+            t = fmaf(row[x], g1, t);
+            t = fmaf(row[img_clamp(x + 1, w - 1)], g2, t);
             rows[r * kImgTileW + lane] = t;
         }
     }
@@ -103,9 +107,9 @@ static __global__ __launch_bounds__(kImgThreads) void img_pyramid_level(const fl
     for (int r = wave; r < kImgTileH; r += 4) {
         if (x >= w || y0 + r >= h) continue;
         float out = 0.0f;
-        out = out + rows[r * kImgTileW + lane] * g0;
-        out = out + rows[(r + 1) * kImgTileW + lane] * g1;
-        out = out + rows[(r + 2) * kImgTileW + lane] * g2;
+        out = fmaf(rows[r * kImgTileW + lane], g0, out);
+        out = fmaf(rows[(r + 1) * kImgTileW + lane], g1, out);
+        out = fmaf(rows[(r + 2) * kImgTileW + lane], g2, out);
         filt[r * kImgTileW + lane] = out;
     }
     __syncthreads();
@@ -193,7 +197,8 @@ struct ImgFormat {
 };
 
 // the value make_gray_image_functor forms before the conversion to the output type: one channel value * denom, three
-// channels ((w0 v0 + w1 v1) + w2 v2) * denom, anything else 0
+// channels fmaf(w2, v2, fmaf(w0, v0, w1 * v1)) * denom -- the contraction the reference's vectors pin
+// (CreateFloatImage_3_1 / 3_2 / 3_4; both weight sets: the reference compiles one expression) --, anything else 0
 __device__ __forceinline__ float img_intensity(const uint8_t* __restrict__ src, int64_t idx, const ImgFormat& f) {
     float v[3] = {0.0f, 0.0f, 0.0f};
     const int n = f.channels == 3 ? 3 : (f.channels == 1 ? 1 : 0);
@@ -206,21 +211,18 @@ __device__ __forceinline__ float img_intensity(const uint8_t* __restrict__ src, 
         else if (f.bytes == 4) v[k] = reinterpret_cast<const float*>(src)[e];
     }
     if (n == 1) return v[0] * f.denom;
-    if (n == 3) return ((f.w0 * v[0] + f.w1 * v[1]) + f.w2 * v[2]) * f.denom;
+    if (n == 3) return fmaf(f.w2, v[2], fmaf(f.w0, v[0], f.w1 * v[1])) * f.denom;
     return 0.0f;
 }
 
-// Image::CreateFloatImage; DEPTH: ConvertDepthToFloatImage's division and truncation in the same pass
+// Image::CreateFloatImage; DEPTH: ConvertDepthToFloatImage's depth_metres (depth_kernels.h) in the same pass
 template <bool DEPTH>
-__global__ __launch_bounds__(256) void img_to_float(const uint8_t* __restrict__ src, int64_t count, ImgFormat f, float scale,
+__global__ __launch_bounds__(256) void img_to_float(const uint8_t* __restrict__ src, int64_t count, ImgFormat f, float recip,
                                                     float trunc, float* __restrict__ dst) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= count) return;
     float v = img_intensity(src, idx, f);
-    if (DEPTH) {
-        v = v / scale;
-        if (v >= trunc) v = 0.0f;
-    }
+    if (DEPTH) v = depth_metres(v, recip, trunc);
     dst[idx] = v;
 }
 

@@ -172,7 +172,7 @@ int mi_icp_image_depth_to_float(mi_icp_ctx* c, const void* src, int width, int h
     if (empty) return MI_ICP_OK;
     if (!src || !dst || src == (const void*)dst) return fail(c, MI_ICP_ERR_INVALID, "%s: null or aliased buffer", what);
     const int64_t count = (int64_t)width * height;
-    img_to_float<true><<<blocks_for(count), 256, 0, c->stream>>>(static_cast<const uint8_t*>(src), count, f, (float)(int)depth_scale,
+    img_to_float<true><<<blocks_for(count), 256, 0, c->stream>>>(static_cast<const uint8_t*>(src), count, f, depth_reciprocal((int)depth_scale),
                                                                  (float)(int)depth_trunc, dst);
     KCHK(c);
     return MI_ICP_OK;

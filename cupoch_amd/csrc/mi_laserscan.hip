@@ -174,7 +174,7 @@ int mi_icp_laserscan_from_depth(mi_icp_ctx* c, const void* depth, int depth_type
     src.d.height = height;
     src.d.stride = stride;
     src.d.depth_u16 = depth_type == MI_ICP_DEPTH_U16;
-    src.d.depth_scale = (int)depth_scale;
+    src.d.depth_recip = depth_reciprocal((int)depth_scale);
     src.d.depth_trunc = (int)depth_trunc;
     src.d.fx = intrinsic4[0];
     src.d.fy = intrinsic4[1];

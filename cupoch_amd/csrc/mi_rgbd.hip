@@ -81,7 +81,7 @@ int mi_icp_create_from_depth(mi_icp_ctx* c, const void* depth, int depth_type, c
     a.depth_u16 = depth_type == MI_ICP_DEPTH_U16;
     a.color_kind = color_type;
     a.rgbd = rgbd ? 1 : 0;
-    a.depth_scale = (int)depth_scale;  // image.cu:340-343 holds both as int
+    a.depth_recip = depth_reciprocal((int)depth_scale);  // image.cu:340-343 holds both as int
     a.depth_trunc = (int)depth_trunc;
     a.depth_cutoff = depth_cutoff;
     a.fx = intrinsic4[0];

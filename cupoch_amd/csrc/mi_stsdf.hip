@@ -217,7 +217,7 @@ int mi_icp_stsdf_integrate(mi_icp_ctx* c, mi_icp_stsdf* t, const void* depth, in
     da.width = width;
     da.height = height;
     da.stride = t->stride;
-    da.depth_scale = 1000;
+    da.depth_recip = depth_reciprocal(1000);
     da.depth_trunc = 1000;
     da.depth_cutoff = -1.0f;
     da.fx = intrinsic4[0];

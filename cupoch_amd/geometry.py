@@ -206,6 +206,11 @@ class PointCloud:
     def is_empty(self):
         return not self.has_points()
 
+    def clear(self):
+        """PointCloud::Clear"""
+        self._points, self._normals, self._colors, self._covariances = utility.Vector3fVector(), None, None, None
+        return self
+
     def clone(self):
         out = PointCloud()
         out._points = utility.Vector3fVector(self._points.tensor.clone())
@@ -526,6 +531,21 @@ class Image:
         d = self.data
         a = np.zeros((0, 0), np.uint8) if d is None else (d.detach().cpu().numpy() if _is_torch(d) else np.asarray(d))
         return a if dtype is None else a.astype(dtype)
+
+    def clear(self):
+        """Image::Clear"""
+        self.data = None
+        return self
+
+    def get_min_bound(self):
+        return np.zeros(2, np.float32)
+
+    def get_max_bound(self):
+        return np.array([self.width, self.height], np.float32)
+
+    def bytes_per_line(self):
+        """Image::BytesPerLine"""
+        return self.width * self.num_of_channels * self.bytes_per_channel
 
     def test_image_boundary(self, u, v, inner_margin=0.0):
         """Image::TestImageBoundary"""

@@ -342,9 +342,10 @@ MI_ICP_API int mi_icp_remove_none_finite(mi_icp_ctx* ctx, const float* xyz, cons
  * (geometry/pointcloud_factory.cu:43-110,117-220,286-376) incl. the
  * RemoveNoneFinitePoints pass that follows (geometry/pointcloud.cu:40-54,360-385):
  * the depth-image side of the path's tracker callers (kinfu/kinfu.cpp:87-104).
- *   depth       [height][width], MI_ICP_DEPTH_F32 or MI_ICP_DEPTH_U16 (then value /
- *               (int)depth_scale, values >= (int)depth_trunc dropped, image.cu:339-348;
- *               both are truncated to int as the reference does)
+ *   depth       [height][width], MI_ICP_DEPTH_F32 or MI_ICP_DEPTH_U16 (then value * the
+ *               reciprocal of (int)depth_scale, values >= (int)depth_trunc dropped,
+ *               image.cu:339-348 as the reference is built -- "depth_to_float" under
+ *               "image" below; both are truncated to int as the reference does)
  *   color       NULL, MI_ICP_COLOR_U8X3 [h][w][3] (scaled by 1/255) or
  *               MI_ICP_COLOR_F32X1 [h][w] (replicated to 3 channels)
  *   intrinsic4  fx, fy, cx, cy;   extrinsic: 4x4 column-major or NULL (identity);
@@ -369,8 +370,10 @@ MI_ICP_API int mi_icp_remove_none_finite(mi_icp_ctx* ctx, const float* xyz, cons
  *           whose pivot is 0: MI_ICP_ERR_INVALID.  Only its rows 0..2 are used.
  *  pixels   output element idx stands for row = (idx / (width/stride)) * stride, col = (idx % (width/stride))
  *           * stride (integer divisions), pix = row*width + col.
- *  d        the depth of the pixel; for MI_ICP_DEPTH_U16 (float)v / (float)(int)depth_scale, set to 0 when
- *           >= (float)(int)depth_trunc.
+ *  d        the depth of the pixel; for MI_ICP_DEPTH_U16 (float)v * r, r = (float)(1.0 / (double)(float)(int)
+ *           depth_scale), set to 0 when >= (float)(int)depth_trunc: the one rule of "depth_to_float" under "image"
+ *           below, which the reference's vector TEST(Image, ConvertDepthToFloatImage) pins.  LaserScanBuffer's depth
+ *           entry and Image::ConvertDepthToFloatImage give the same words.
  *  accepted rgbd = 0: !(d <= 0) -- NaN and +inf are accepted.  rgbd = 1: d > 0 && (depth_cutoff <= 0 ||
  *           depth_cutoff > d).
  *  point    x = ((float)col - cx) * d / fx,  y = ((float)row - cy) * d / fy,
@@ -1504,14 +1507,21 @@ MI_ICP_API int mi_icp_laserscan_limits(int64_t* lds_max_bins, int64_t* max_bins)
  * small HOST arrays that travel with the launch.  width and height are at most MI_ICP_TSDF_MAX_IMAGE_SIDE (else
  * MI_ICP_ERR_INVALID); a width or height of 0 launches nothing and is MI_ICP_OK.  Outputs are other buffers than inputs
  * (else MI_ICP_ERR_INVALID) except where "in place" is said.  No call waits for the stream.  All arithmetic is fp32,
- * unfused, in the order written (tests/image_exact.py restates it in numpy); clamp(v, hi) = min(max(0, v), hi).
+ * in the order written, unfused EXCEPT where fmaf is written (tests/image_exact.py restates it in numpy); clamp(v, hi) =
+ * min(max(0, v), hi).  fmaf(a, b, c) is the exact a * b + c rounded once.  It stands where the reference's own test
+ * vectors pin it: src/tests/geometry/image.cpp compares BYTES, the reference is built with nvcc's multiply-add
+ * contraction and --use_fast_math, and its bytes are those of the fused forms below, not of the source read literally
+ * (tests/golden/reference_tests.json records the vectors; tests/test_reference_vectors_cpu.py and
+ * tests/test_gpu_reference_vectors.py replay them).
  *  filter  Image::FilterHorizontal / Image::Filter(dx, dy) on 1 x float32, nx and ny odd, at most
  *   MI_ICP_IMAGE_MAX_TAPS (else MI_ICP_ERR_INVALID), hx = nx / 2, hy = ny / 2:
- *     rowsum(y, x) = t, where t = 0 and then, for i = -hx .. hx, t = t + src[y][clamp(x + i, w - 1)] * dx[i + hx];
+ *     rowsum(y, x) = t, where t = 0 and then, for i = -hx .. hx, t = fmaf(src[y][clamp(x + i, w - 1)], dx[i + hx], t);
  *     dy == NULL (ny = 0): out[y][x] = rowsum(y, x) -- FilterHorizontal;
- *     else out[y][x] = o, where o = 0 and then, for j = -hy .. hy, o = o + rowsum(clamp(y + j, h - 1), x) * dy[j + hy]
+ *     else out[y][x] = o, where o = 0 and then, for j = -hy .. hy, o = fmaf(rowsum(clamp(y + j, h - 1), x), dy[j + hy], o)
  *   -- the words of the reference's horizontal(dx), transpose, horizontal(dy), transpose, in ONE kernel with no
- *   intermediate image.  The named filters: Gaussian3 {.25, .5, .25}, Gaussian5 {.0625, .25, .375, .25, .0625}, Gaussian7
+ *   intermediate image.  The fused tap (image.cu:201) is pinned by TEST(Image, Filter_Gaussian5) and Filter_Gaussian7,
+ *   whose bytes the unfused sum misses in 3 and 4 of 25 words; taps that are powers of two (Gaussian3, the Sobels) have
+ *   exact products and give the same words either way.  The named filters: Gaussian3 {.25, .5, .25}, Gaussian5 {.0625, .25, .375, .25, .0625}, Gaussian7
  *   {.03125, .109375, .21875, .28125, .21875, .109375, .03125} in both directions; Sobel3Dx dx = {-1, 0, 1}, dy =
  *   {1, 2, 1}; Sobel3Dy the other way round.
  *  downsample  Image::Downsample into (w / 2) x (h / 2): 1 x float32 (((p00 + p01) + p10) + p11) / 4.0f over the 2 x 2
@@ -1529,11 +1539,21 @@ MI_ICP_API int mi_icp_laserscan_limits(int64_t* lds_max_bins, int64_t* max_bins)
  *   one operation is not pinned to the bit: a result lies within (4 T + 64) 2^-24 M of the same sums carried in double,
  *   T the number of taps, M the largest |value| in the window.  (The reference clamps to h and w, one past the end.)
  *  create_float  Image::CreateFloatImage: the value of an element by bytes_per_channel (1 uint8, 2 uint16, 4 float, 3:
- *   0.0f); one channel value * denom; three channels ((w0 * v0 + w1 * v1) + w2 * v2) * denom; any other channel count 0;
- *   weights MI_ICP_IMAGE_EQUAL (float)(1.0 / 3.0) each, MI_ICP_IMAGE_WEIGHTED {0.2990f, 0.5870f, 0.1140f}; denom =
- *   (float)(1.0 / 255.0) for one byte per channel, else 1.0f.
- *  depth_to_float  Image::ConvertDepthToFloatImage: create_float (weighted), then f = f / (float)(int)depth_scale; if
- *   (f >= (float)(int)depth_trunc) f = 0 -- the reference holds both as int.  |depth_scale|, |depth_trunc| < 2e9.
+ *   0.0f); one channel value * denom; three channels fmaf(w2, v2, fmaf(w0, v0, w1 * v1)) * denom; any other channel
+ *   count 0; weights MI_ICP_IMAGE_EQUAL (float)(1.0 / 3.0) each, MI_ICP_IMAGE_WEIGHTED {0.2990f, 0.5870f, 0.1140f}; denom
+ *   = (float)(1.0 / 255.0) for one byte per channel, else 1.0f.  The order of the three-channel sum
+ *   (image_factory.cu:88-105) is pinned by TEST(Image, CreateFloatImage_3_1_Weighted), _3_2_Weighted and _3_4_Weighted
+ *   (the unfused sum misses 7, 7 and 2 of 25 words).  The EQUAL weights have no vector of their own -- the reference's
+ *   _Equal cases call CreateFloatImage() with the default type and hold the Weighted bytes --; they take the same order
+ *   because the reference compiles one expression for both weight sets.
+ *  depth_to_float  Image::ConvertDepthToFloatImage: create_float (weighted), then f = f * r, r = (float)(1.0 /
+ *   (double)(float)(int)depth_scale); if (f >= (float)(int)depth_trunc) f = 0 -- the reference holds both as int.
+ *   |depth_scale|, |depth_trunc| < 2e9.  Under fast math the reference's `f /= (float)depth_scale_` (image.cu:345) is a
+ *   product with a reciprocal; TEST(Image, ConvertDepthToFloatImage) pins it AT SCALE 1000 ONLY, where the correctly
+ *   rounded reciprocal gives its bytes (the division misses 17 of 25 words, each by one ulp).  For every other scale the
+ *   correctly rounded reciprocal is this library's extrapolation of fast-math division, not something a vector shows.
+ *   The same rule, in one device function, serves mi_icp_create_from_depth's MI_ICP_DEPTH_U16 and LaserScanBuffer's
+ *   depth entry.
  *  create_gray  Image::CreateGrayImage: the same sum with denom 1.0f (one byte per channel), (float)(255.0 / 65535.0)
  *   (two), 255.0f (else), to uint8.
  *  from_float  Image::CreateImageFromFloatImage: bytes_per_channel 1 (uint8)(f * 255.0f), 2 (uint16)f.

@@ -1473,8 +1473,10 @@ ORACLE_API int64_t oracle_voxel_downsample(const float *pts, const float *nrm,
 /* own order: a structured cloud of one point per pixel (+inf where the */
 /* depth is rejected), normals from that cloud's 4-neighbourhood        */
 /* (:161-199), then RemoveNoneFinitePoints (pointcloud.cu:40-54).       */
-/* depth is float; the uint16 conversion (image.cu:339-348: divide by   */
-/* (int)scale, >= (int)trunc -> 0) is oracle_depth_u16_to_float.        */
+/* depth is float; the uint16 conversion (image.cu:339-348 as built     */
+/* with fast math: times the correctly rounded reciprocal of (int)scale */
+/* -- pinned by TEST(Image, ConvertDepthToFloatImage) at scale 1000 --,  */
+/* >= (int)trunc -> 0) is oracle_depth_u16_to_float.                    */
 /* pose = extrinsic^-1, column-major.  rgbd = 0: :43-82 (stride, d <= 0 */
 /* rejected); rgbd = 1: :117-160 (cutoff, colours, optional normals).   */
 /* The last row's lower neighbour is past the end of the reference's    */
@@ -1485,9 +1487,10 @@ ORACLE_API int64_t oracle_voxel_downsample(const float *pts, const float *nrm,
 ORACLE_API void oracle_depth_u16_to_float(const uint16_t *in, int64_t n, float depth_scale,
                                           float depth_trunc, float *out) {
     const int iscale = (int)depth_scale, itrunc = (int)depth_trunc;
+    const float recip = (float)(1.0 / (double)(float)iscale);
     for (int64_t i = 0; i < n; ++i) {
         float f = (float)in[i];
-        f /= (float)iscale;
+        f = f * recip;
         if (f >= (float)itrunc) f = 0.0f;
         out[i] = f;
     }

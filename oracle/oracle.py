@@ -563,6 +563,16 @@ def ref_rand_vec4i(n, vmin, vmax, seed):
     return out
 
 
+def ref_rand_u8(n, vmin, vmax, seed):
+    """unit_test::Rand(host_vector<uint8_t>) driven by the reference's Raw generator."""
+    L = _ref_lib("libref_raw.so")
+    if L is None:
+        raise FileNotFoundError("oracle/_ref/libref_raw.so not built (needs /root/reference)")
+    out = np.empty(n, np.uint8)
+    L.ref_rand_u8(out.ctypes.data_as(C.c_void_p), C.c_int(n), C.c_ubyte(vmin), C.c_ubyte(vmax), C.c_int(seed))
+    return out
+
+
 def ref_lzf():
     """The reference's vendored liblzf (third_party/liblzf/lzf_c.c, lzf_d.c compiled in place into
     oracle/_ref/libref_lzf.so) or None where it was not built."""

@@ -35,4 +35,11 @@ void ref_rand_vec4i(int* out, int n, int vmin, int vmax, int seed) {
     for (int i = 0; i < 4 * n; ++i) out[i] = vmin + (int)(raw.Next<int>() * factor);
 }
 
+// unit_test::Rand(host_vector<uint8_t>&, uint8_t vmin, uint8_t vmax, seed) (rand.cpp:181-191)
+void ref_rand_u8(unsigned char* out, int n, unsigned char vmin, unsigned char vmax, int seed) {
+    unit_test::Raw raw(seed);
+    const float factor = (float)(vmax - vmin) / unit_test::Raw::VMAX;
+    for (int i = 0; i < n; ++i) out[i] = vmin + (unsigned char)(raw.Next<unsigned char>() * factor);
+}
+
 }  // extern "C"

@@ -1,6 +1,8 @@
 // geometry::Image / geometry::RGBDImage through the C++ surface, with the reference's signatures.  argv[1]: a directory
 // holding gray.f32 ([23][37] float), color.u8 ([48][64][3] uint8) and depth.u16 ([48][64] uint16); every result goes
-// there as <name>.bin with its width, height, channels and bytes per channel in the JSON line this prints.
+// there as <name>.bin with its width, height, channels and bytes per channel in the JSON line this prints.  The directory
+// also holds the 5 x 5 inputs of three of the reference's own cases (src/tests/geometry/image.cpp: Filter_Gaussian7,
+// CreateFloatImage_3_1_Weighted, ConvertDepthToFloatImage) as ref_f32.u8, ref_rgb.u8 and ref_depth.u8.
 // tests/test_gpu_image_cpp.py compiles and runs it and holds the bytes to tests/image_exact.py.
 #include <cstdio>
 #include <memory>
@@ -101,6 +103,13 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < sobel.size(); ++i) Put("plain_sobel" + std::to_string(i), *sobel[i]);
     const auto smooth = Image::BilateralFilterPyramid(plain, 2, 0.5f, 1.5f);
     for (size_t i = 0; i < smooth.size(); ++i) Put("plain_bilateral" + std::to_string(i), *smooth[i]);
+
+    {   // the reference's own 5 x 5 cases, called as its tests call them
+        const Image f = Load("ref_f32.u8", 5, 5, 1, 4), rgb = Load("ref_rgb.u8", 5, 5, 3, 1), d = Load("ref_depth.u8", 5, 5, 1, 1);
+        Put("ref_gaussian7", *f.CreateFloatImage()->Filter(Image::FilterType::Gaussian7));
+        Put("ref_float_3_1", *rgb.CreateFloatImage());
+        Put("ref_depth_float", *d.ConvertDepthToFloatImage());
+    }
 
     const auto rgbd = RGBDImage::CreateFromColorAndDepth(color, depth);
     Put("rgbd_color", rgbd->color_);

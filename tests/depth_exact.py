@@ -33,8 +33,10 @@ def pose_of(extrinsic):
 
 
 def u16_to_float(depth, depth_scale, depth_trunc):
-    """Image::ConvertDepthToFloatImage as the entry applies it: both parameters held as int"""
-    f = np.asarray(depth, np.uint16).astype(F) / F(int(depth_scale))
+    """Image::ConvertDepthToFloatImage as the entry applies it: both parameters held as int, the division a product with
+    the correctly rounded reciprocal (the reference's vector TEST(Image, ConvertDepthToFloatImage) pins it at 1000)"""
+    with np.errstate(all="ignore"):
+        f = np.asarray(depth, np.uint16).astype(F) * F(np.float64(1.0) / np.float64(F(int(depth_scale))))
     return np.where(f >= F(int(depth_trunc)), F(0), f).astype(F)
 
 

@@ -1,7 +1,9 @@
 """The image contract of include/mi_icp.h ("image") restated in numpy: a helper, not a test.  Every operation is carried
-in float32 one rounding at a time in the order the contract writes it (numpy never fuses a multiply with an add), so
-the results are the words the kernels must produce -- except the bilateral filter, whose restatement carries the
-exponential, the two sums and the quotient in float64 and is compared under a bound (bilateral_bound)."""
+in float32 one rounding at a time in the order the contract writes it (numpy never fuses a multiply with an add; where
+the contract writes fmaf, fma32 below rounds the exact product-plus-addend once), so the results are the words the
+kernels must produce -- except the bilateral filter, whose restatement carries the exponential, the two sums and the
+quotient in float64 and is compared under a bound (bilateral_bound).  The filters, the three-channel intensity and the
+depth value are held to the reference's own byte vectors (tests/test_reference_vectors_cpu.py)."""
 import numpy as np
 
 F = np.float32
@@ -41,6 +43,25 @@ def float_image(w, h, seed=0, specials=True):
     return img
 
 
+def fma32(a, b, c):
+    """fmaf(a, b, c) element-wise: the exact a * b + c rounded to float32 once.  The product of two float32 is exact in
+    float64 (48 bits), but float64(product + c) -> float32 rounds twice and is wrong on ties (math.fma on doubles would
+    round the same two times).  So the float64 sum is made round-to-odd from its exact error term (Knuth's two-sum):
+    with 53 >= 24 + 2 bits the final rounding to float32 is then the correct single rounding."""
+    with np.errstate(all="ignore"):
+        p = np.asarray(a, F).astype(np.float64) * np.asarray(b, F).astype(np.float64)
+        c = np.asarray(c, F).astype(np.float64)
+        p, c = np.broadcast_arrays(p, c)
+        s = p + c
+        bb = s - p
+        e = (p - (s - bb)) + (c - bb)            # p + c = s + e exactly
+        even = ((np.ascontiguousarray(s).reshape(-1).view(np.uint64) & np.uint64(1)) == 0).reshape(s.shape)
+        fix = np.isfinite(s) & (e != 0) & even   # s is not exact and its last bit is even: step towards the true sum
+        toward = np.where(e > 0, np.inf, -np.inf)
+        s = np.where(fix, np.nextafter(s, toward), s)
+        return s.astype(F)[()]
+
+
 def filter_horizontal(src, k):
     src, k = np.asarray(src, F), np.asarray(k, F)
     h, w = src.shape
@@ -49,7 +70,7 @@ def filter_horizontal(src, k):
     t = np.zeros((h, w), F)
     with np.errstate(all="ignore"):
         for i in range(-half, half + 1):
-            t = t + src[:, np.clip(x + i, 0, w - 1)] * k[i + half]
+            t = fma32(src[:, np.clip(x + i, 0, w - 1)], k[i + half], t)
     return t
 
 
@@ -68,7 +89,7 @@ def filter_taps(src, dx, dy):
     out = np.zeros((h, w), F)
     with np.errstate(all="ignore"):
         for j in range(-half, half + 1):
-            out = out + rows[np.clip(y + j, 0, h - 1), :] * dy[j + half]
+            out = fma32(rows[np.clip(y + j, 0, h - 1), :], dy[j + half], out)
     return out
 
 
@@ -194,7 +215,7 @@ def _intensity(img, kind, denom):
             return v[:, :, 0] * denom
         if ch == 3:
             w = _weights(kind)
-            return ((w[0] * v[:, :, 0] + w[1] * v[:, :, 1]) + w[2] * v[:, :, 2]) * denom
+            return fma32(w[2], v[:, :, 2], fma32(w[0], v[:, :, 0], w[1] * v[:, :, 1])) * denom
     return np.zeros(v.shape[:2], F)
 
 
@@ -211,7 +232,7 @@ def create_gray(img, kind=WEIGHTED):
 
 def depth_to_float(img, scale=1000.0, trunc=3.0):
     with np.errstate(all="ignore"):
-        f = create_float(img) / F(int(scale))
+        f = create_float(img) * F(np.float64(1.0) / np.float64(F(int(scale))))
     return np.where(f >= F(int(trunc)), F(0), f).astype(F)
 
 

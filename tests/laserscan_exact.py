@@ -85,9 +85,11 @@ def from_points(points, angle_inc, min_height, max_height, divisions=1, min_rang
 
 
 def depth_values(depth, depth_scale, depth_trunc):
-    """mi_icp_create_from_depth's rule: U16 value / (int)depth_scale, values >= (int)depth_trunc dropped (0)"""
+    """mi_icp_create_from_depth's rule: U16 value * the correctly rounded reciprocal of (int)depth_scale, values
+    >= (int)depth_trunc dropped (0)"""
     if depth.dtype == np.uint16:
-        d = depth.astype(F) / F(int(depth_scale))
+        with np.errstate(all="ignore"):
+            d = depth.astype(F) * F(np.float64(1.0) / np.float64(F(int(depth_scale))))
         return np.where(d >= F(int(depth_trunc)), F(0), d).astype(F)
     return np.asarray(depth, F)
 

@@ -1,7 +1,8 @@
 """GPU: geometry::Image / geometry::RGBDImage through the C++ surface (tests/cpp/test_image.cpp: every method, Transpose,
 FilterHorizontal, Filter(dx, dy), CreateImageFromFloatImage and the RGBDImage statics included), built as the other
 tests/cpp programs are.  The program writes every result's bytes; they are held to the numpy restatement of the
-contract (tests/image_exact.py): bit for bit, the bilateral results under the bound of tests/test_gpu_image.py."""
+contract (tests/image_exact.py): bit for bit, the bilateral results under the bound of tests/test_gpu_image.py.  Three of
+the reference's own 5 x 5 cases (tests/golden/reference_tests.json) go through the same run and are held to its bytes."""
 import json
 import os
 import subprocess
@@ -18,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DTYPES = {1: np.uint8, 2: np.uint16, 4: F}
 
 
-def test_cpp_surface(tmp_path):
+def test_cpp_surface(tmp_path, golden):
     from cupoch_amd import _lib
     _lib.build()
     cpp = os.path.join(ROOT, "cupoch_amd", "cpp")
@@ -39,6 +40,11 @@ def test_cpp_surface(tmp_path):
     gray.tofile(str(tmp_path / "gray.f32"))
     color.tofile(str(tmp_path / "color.u8"))
     depth.tofile(str(tmp_path / "depth.u16"))
+    reference = {"ref_gaussian7": ("ref_f32.u8", golden["image_Filter_Gaussian7"]),
+                 "ref_float_3_1": ("ref_rgb.u8", golden["image_CreateFloatImage_3_1_Weighted"]),
+                 "ref_depth_float": ("ref_depth.u8", golden["image_ConvertDepthToFloatImage"])}
+    for file, e in reference.values():
+        np.array(e["input"], np.uint8).tofile(str(tmp_path / file))
     out = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads(out.stdout.strip().splitlines()[-1])
@@ -65,6 +71,9 @@ def test_cpp_surface(tmp_path):
         ok = np.isfinite(ref) & np.isfinite(bound)
         assert ok.any() and (np.abs(a.astype(np.float64) - ref)[ok] <= bound[ok]).all(), name
 
+    for name, (_, e) in reference.items():              # as the reference compares: the dimensions, then every byte
+        assert r["images"][name] == [e["ref_width"], e["ref_height"], e["ref_channels"], e["ref_bytes_per_channel"]], name
+        assert got(name).tobytes() == bytes(e["ref_bytes"]), (name, e["cite"])
     k5, k3 = [0.5, -1.25, 2.0, 0.75, -0.5], [1.0, -2.0, 0.5]
     same("transpose", gray.T)
     same("transpose_rgb", np.swapaxes(color, 0, 1))

@@ -1,4 +1,6 @@
-"""PCD reader + the real-scan fixture on the CPU side (oracle only)."""
+"""PCD reader + the real-scan fixture on the CPU side (oracle only).  The reference's own test of the reader,
+TEST(PointCloud, CreatePointCloudFromFile) (src/tests/io/class_io/pointcloud_io.cpp), has an empty body: the reader's
+tests are the ones here."""
 import os
 
 import numpy as np

@@ -192,10 +192,10 @@ def test_depth_restatement_obeys_the_pinhole_model_and_the_reference_rules():
     s3, _, _ = orc.create_from_depth(d, K, stride=3)
     sub = d[: (480 // 3) * 3: 3, : (640 // 3) * 3: 3]
     assert len(s3) == int((sub > 0).sum())
-    # uint16 depth: / (int)scale, >= (int)trunc dropped
+    # uint16 depth: * the correctly rounded reciprocal of (int)scale, >= (int)trunc dropped
     d16 = (np.clip(d, 0, 60) * 1000).astype(np.uint16)
     a, _, _ = orc.create_from_depth(d16, K, depth_scale=1000.9, depth_trunc=2.9)
-    assert len(a) == int(((d16 > 0) & (d16.astype(np.float32) / np.float32(1000) < 2)).sum())
+    assert len(a) == int(((d16 > 0) & (d16.astype(np.float32) * np.float32(1.0 / np.float64(np.float32(1000))) < 2)).sum())
     # RGB-D form: cutoff, colours scaled by 1/255, rejected pixels +inf when not compacted
     col = np.random.default_rng(0).integers(0, 256, (480, 640, 3), dtype=np.uint8)
     p2, n2, c2 = orc.create_from_depth(d, K, color=col, depth_cutoff=2.5, rgbd=True, compute_normals=True,

@@ -1,6 +1,7 @@
 """geometry.Image / geometry.RGBDImage of the reference's pybind11 module (cupoch_amd/cpp/src/pybind_module.cpp) with the
 reference's Python names and defaults: names on the CPU, and on the GPU the same bytes as the ctypes mirror for a filter,
-the bilateral filter, a pyramid and one factory.  Skips only where there is nothing to build the module with."""
+the bilateral filter, a pyramid and one factory, and the reference's own bytes for three of its 5 x 5 cases
+(tests/golden/reference_tests.json).  Skips only where there is nothing to build the module with."""
 import re
 
 import numpy as np
@@ -88,3 +89,17 @@ def test_same_bytes_as_the_ctypes_mirror():
     assert all(ix.same_words(np.asarray(x.depth), np.asarray(g.Image(y.depth))) for x, y in zip(smooth, mirror))
     u8 = cph.geometry.Image(color)
     assert u8.linear_transform(1.5, -40.0) is u8 and np.asarray(u8).tobytes() == ix.linear_transform(color, 1.5, -40.0).tobytes()
+
+
+@pytest.mark.gpu
+def test_reference_vectors_through_the_pybind_surface(golden):
+    """src/tests/geometry/image.cpp: Filter_Gaussian7, CreateFloatImage_3_1_Weighted, ConvertDepthToFloatImage"""
+    cph = module()
+    import test_reference_vectors_cpu as rv
+    I = cph.geometry.Image
+    e = golden["image_Filter_Gaussian7"]
+    rv.image_compare(e, np.asarray(I(rv.image_input(e)).create_float_image().filter(cph.geometry.ImageFilterType.Gaussian7)))
+    e = golden["image_CreateFloatImage_3_1_Weighted"]
+    rv.image_compare(e, np.asarray(I(rv.image_input(e)).create_float_image()))
+    e = golden["image_ConvertDepthToFloatImage"]
+    rv.image_compare(e, np.asarray(I(rv.image_input(e)).convert_depth_to_float_image()))

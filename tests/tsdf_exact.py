@@ -311,7 +311,8 @@ PRIMESENSE = (640, 480, 525.0, 525.0, 319.5, 239.5)       # PinholeCameraIntrins
 def load_rgbd_frames(root):
     """the reference's five RGB-D frames (tests/golden/rgbd): [(depth float32 [480, 640] in metres with values >= 4
     set to 0, colour uint8 [480, 640, 3], extrinsic = inverse of the frame's pose)], as the reference's RealData test
-    prepares them (RGBDImage::CreateFromColorAndDepth(color, depth, 1000, 4, false))"""
+    prepares them (RGBDImage::CreateFromColorAndDepth(color, depth, 1000, 4, false): the depth rule of include/mi_icp.h
+    "image", value * the correctly rounded reciprocal of the scale, pinned by the reference's own vector)"""
     import os
     from PIL import Image
     lines = open(os.path.join(root, "odometry.log")).read().split("\n")
@@ -319,7 +320,7 @@ def load_rgbd_frames(root):
     k = 0
     while k * 5 + 4 < len(lines) and lines[k * 5].strip():
         pose = np.array([[float(x) for x in lines[k * 5 + 1 + r].split()] for r in range(4)], F)
-        d = np.asarray(Image.open(os.path.join(root, "depth", "%05d.png" % k))).astype(F) / F(1000)
+        d = np.asarray(Image.open(os.path.join(root, "depth", "%05d.png" % k))).astype(F) * F(np.float64(1.0) / np.float64(F(1000)))
         d = np.where(d >= F(4.0), F(0), d).astype(F)
         c = np.ascontiguousarray(np.asarray(Image.open(os.path.join(root, "color", "%05d.jpg" % k)).convert("RGB")))
         frames.append((d, c, np.linalg.inv(pose).astype(F)))
